@@ -4,8 +4,19 @@
 Metric (BASELINE.json): ADMM iterations/sec (+ achieved HBM GB/s of the PCG SpMV) on the n=100k, m=200k, nnz(A)=1M,
 nnz(P)=200k sparse QP (BASELINE configs[1], generator problems.banded_qp), indirect PCG.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   N>1:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run does only what the headline figure needs: setup, W warm-up steps, the K timed steps, the outputs of the last timed
+step when --dump-outputs is given, and the result line.  --full adds everything else this script measures (below: the
+roofline, the CPU baseline, the device state, config.batch, the lasso / portfolio legs, the perturbed re-solve, the
+unstructured and HBM-resident points); the options that tune those parts act only with --full.
+
+--dump-outputs DIR: what the timed path handed its caller in the last timed step, as DIR/<name>.npy (float64): x (primal
+solution), y (dual solution) and info (status_val, status_polish, iter, rho_updates, obj_val, dual_obj_val, prim_res, dual_res,
+duality_gap, rho_estimate); a vector longer than DUMP_MAX_ELEMS is written as a fixed, seeded sample of its entries.  The
+inputs are generated from fixed seeds, so two builds run with the same arguments can be compared output for output (bench_out/
+is git-ignored for the purpose).
 
 A "step" is one complete cold-started solve of the QP (setup -- scaling, CSR/B assembly, H2D -- is done once, outside the
 timed region: all inputs are resident in HBM when the clock starts).  value = ADMM iterations executed by all ranks in the
@@ -14,7 +25,7 @@ latency-bound over xGMI: DESIGN.md §6), so with N > 1 every rank solves its own
 problem per GPU, no data-path collective; the only communication is the final all_gather of {status, iter, obj, prim_res,
 dual_res} over RCCL (scaling: weak).  The batched-QP path that really shards a workload is bench_batch.py.
 
-Rank 0 also reports
+With --full, rank 0 also reports
   roofline      algorithmic bytes per launch / mean launch time (hipEvent pair on the solver's stream) of the dominant PCG
                 kernel (the SpMV over B = [P+sigma I | A']), against the 8 TB/s HBM peak;
   cpu_baseline  the oracle (oracle/osqp_oracle.c: the CPU restatement of the reference algorithm with a direct LDL' KKT
@@ -34,6 +45,26 @@ for _p in (ROOT, os.path.join(ROOT, 'osqp-python_amd'), os.path.join(ROOT, 'orac
         sys.path.insert(0, _p)
 
 HBM_PEAK_GBS = 8000.0     # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+
+
+DUMP_MAX_ELEMS = 1500000  # per dumped vector (12 MB of float64): four such vectors stay under 64 MB
+DUMP_INFO_FIELDS = ('status_val', 'status_polish', 'iter', 'rho_updates', 'obj_val', 'dual_obj_val', 'prim_res', 'dual_res', 'duality_gap', 'rho_estimate')
+
+
+def dump_outputs(d, res):
+    """--dump-outputs: the solution and info record of the last timed step as DIR/<name>.npy (float64).  The infeasibility
+    certificates are written only when the status is an infeasible one (otherwise they carry nothing a caller may read)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    arrays = {'x': res.x, 'y': res.y}
+    if res.info.status_val in (3, 4, 5, 6):          # (PRIMAL / DUAL_INFEASIBLE and their _INACCURATE forms)
+        arrays['prim_inf_cert'], arrays['dual_inf_cert'] = res.prim_inf_cert, res.dual_inf_cert
+    for name, v in arrays.items():
+        v = np.asarray(v, dtype=np.float64).ravel()
+        if v.size > DUMP_MAX_ELEMS:
+            v = v[np.sort(np.random.default_rng(20240611).choice(v.size, DUMP_MAX_ELEMS, replace=False))]
+        np.save(os.path.join(d, name + '.npy'), v)
+    np.save(os.path.join(d, 'info.npy'), np.array([float(getattr(res.info, k)) for k in DUMP_INFO_FIELDS], dtype=np.float64))
 
 
 def median(v):
@@ -457,6 +488,9 @@ def main():
     ap.add_argument('--jacobi-leg', type=int, default=1, help='lasso / portfolio: also solve once with the plain Jacobi preconditioner (config.jacobi_only); 0 for profiling runs, whose kernel statistics it would dominate')
     ap.add_argument('--extra-legs', type=int, default=1, help='N = 1, headline config only: short legs of BASELINE configs[2] (lasso) and configs[3] (portfolio) reported as config.lasso / config.portfolio, and the perturbed re-solve of the headline QP (0 disables)')
     ap.add_argument('--unstructured-leg', type=int, default=1, help='N = 1, headline config only: also solve the unstructured variant of the same sizes and report its PCG iteration as roofline.unstructured (0 disables)')
+    ap.add_argument('--full', action='store_true', help='also measure everything beyond the headline figure: roofline, CPU baseline, device state, config.batch and the extra legs '
+                                                         '(--cpu-seconds, --probe-reps, --batch*, --hbm-n, --jacobi-leg, --extra-legs and --unstructured-leg act only with --full)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write x, y and info of the last timed step to DIR/<name>.npy (float64)')
     args = ap.parse_args()
     warnings.simplefilter('ignore')
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -556,6 +590,8 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     stats = m._solver.hip_stats()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
 
     # whole-job aggregate: total ADMM iterations / max-over-ranks time; final status/objective gather over RCCL
     rec = torch.tensor([float(res.info.status_val), float(res.info.iter), res.info.obj_val, res.info.prim_res, res.info.dual_res,
@@ -572,7 +608,7 @@ def main():
     # one all_gather of the records) -- on every rank, at any N: `value` stays the replica metric, the batch travels as config.batch so that
     # a scaling run of this script shows its strong-scaling curve (reference analogue: /root/reference/src/osqp/nn/torch.py:200-224)
     batch_out = None
-    if args.batch > 0 and args.config == 'banded' and (args.dist_backend == 'nccl' or hostsim):
+    if args.full and args.batch > 0 and args.config == 'banded' and (args.dist_backend == 'nccl' or hostsim):
         import bench_batch
         if hostsim:
             batch_out = bench_batch.measure_sharded_host(args.batch, args.batch_steps, rank, world, use_dist)
@@ -582,9 +618,12 @@ def main():
     if rank == 0:
         mm = len(l)
         s = m._solver
-        dev_state = None if hostsim else device_state(local)
+        dev_state = device_state(local) if (args.full and not hostsim) else None
         if hostsim:
             probes = kb = dom = dom_kernel = streamed = None; pcg_bytes = pcg_ms = survey_pcg_bytes = 0; f1 = fused = False; f1_D = 0
+        elif not args.full:     # (the form of the PCG iteration from the solver's counters; the kernels are timed with --full only)
+            probes = kb = dom = dom_kernel = streamed = None; pcg_bytes = pcg_ms = survey_pcg_bytes = 0
+            fused = bool(stats.get('pcg_fused', 0)); f1 = int(stats.get('pcg_fused', 0)) == 2; f1_D = int(stats.get('f1_replicas', 0))
         else:
             probes, kb, pcg_bytes, pcg_ms, dom, dom_kernel, survey_pcg_bytes, streamed, f1, fused, f1_D = measure_roofline(s, stats, n, mm, args)
         tts_ms = 1e3 * tmax / args.steps
@@ -617,7 +656,7 @@ def main():
                        'pcg_kernels_per_iteration': 1 if f1 else (2 if fused else 3), 'f1_replicas': int(stats.get('f1_replicas', 0)), 'f1_far_columns': int(stats.get('f1_far_columns', 0)), 'kernel_launches_per_solve': stats['kernel_launches'], 'graph_launches_per_solve': stats['graph_launches'],
                        'setup_s': t_setup, 'per_rank': [{'status': int(r[0]), 'iter': int(r[1]), 'obj': r[2]} for r in allrec]},
             'device': dev_state,
-            'roofline': None if hostsim else {'bound': 'hbm', 'kernel': dom + (' -- in solves this body runs as the K2F phase of k_slot_b' if (fused and not f1) else ''), 'achieved': probes[dom]['GBps'], 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+            'roofline': None if (hostsim or not args.full) else {'bound': 'hbm', 'kernel': dom + (' -- in solves this body runs as the K2F phase of k_slot_b' if (fused and not f1) else ''), 'achieved': probes[dom]['GBps'], 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
                          'frac': probes[dom]['GBps'] / HBM_PEAK_GBS, 'traffic': pmc_traffic(dom_kernel, wl_tag),
                          'bytes_per_launch': kb[dom], 'ms_per_launch': probes[dom]['ms'],
                          'pcg_iteration': {'bytes': pcg_bytes, 'ms': pcg_ms, 'GBps': pcg_bytes / (pcg_ms * 1e-3) / 1e9,
@@ -626,13 +665,13 @@ def main():
                                            'frac_survey_8d': survey_pcg_bytes / (pcg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS},
                          'kernels': probes},
         }
-        if f1:
+        if f1 and out['roofline'] is not None:
             out['roofline']['streamed_bytes'] = streamed
             out['roofline']['frac_streamed'] = streamed / (pcg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
             out['roofline']['replicas'] = f1_D
             if out['roofline']['traffic']:
                 out['roofline']['frac_traffic'] = out['roofline']['traffic'] / (pcg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS      # by the bytes the PMC counters saw
-        if int(stats.get('woodbury_rows', 0)) > 0 and args.jacobi_leg:
+        if args.full and int(stats.get('woodbury_rows', 0)) > 0 and args.jacobi_leg:
             # the figure with the reference's literal preconditioner next to it: the same QP, same settings, plain Jacobi (OSQPHipPolicy::woodbury = 0)
             os.environ['OSQP_HIP_WOODBURY'] = '0'
             try:
@@ -653,7 +692,7 @@ def main():
                 cb = bench_batch.cpu_batch_baseline(*bdata)
                 batch_out['cpu_baseline'] = cb
                 batch_out['gpu_over_cpu_all_cores'] = batch_out['QP_per_s'] / cb['value']
-        if args.hbm_n > n and args.config == 'banded' and world == 1 and f1 and args.cpu_seconds > 0:      # (--cpu-seconds 0: the profiling runs -- no extra legs)
+        if args.full and args.hbm_n > n and args.config == 'banded' and world == 1 and f1 and args.cpu_seconds > 0:      # (--cpu-seconds 0: the profiling runs -- no extra legs)
             # The headline QP's working set (~50 MB) lives in the Infinity Cache: the fraction above is a cache-resident figure.  The same kernel on the
             # same generator at hbm_n variables (n = 1M: ~0.5 GB of matrices and vectors per launch) is the HBM-resident point of the roofline.
             Pb, qb, Ab, lb, ub = problems.banded_qp(args.hbm_n, seed=12345)
@@ -673,7 +712,7 @@ def main():
                     'traffic': tr, 'frac_traffic': (tr / (ms_l * 1e-3) / 1e9 / HBM_PEAK_GBS) if tr else None,
                     'solve': {'status': rb.info.status, 'admm_iters': int(rb.info.iter), 'first_cold_solve_ms': 1e3 * rb.info.solve_time}}
             del mb
-        if args.unstructured_leg and args.config == 'banded' and world == 1 and not hostsim and args.cpu_seconds > 0:
+        if args.full and args.unstructured_leg and args.config == 'banded' and world == 1 and not hostsim and args.cpu_seconds > 0:
             # "also run an unstructured variant for GB/s only" -- the same sizes with every row's columns drawn from the
             # whole range: no permutation gives its row blocks a compact window, so the PCG iteration runs as the two-kernel
             # pair with global gathers.  One solve + the pair's launch time, in the driver's record next to the banded figure.
@@ -716,7 +755,7 @@ def main():
             finally:
                 os.environ.pop('OSQP_HIP_KFORM', None)
             del mu
-        if args.extra_legs and args.config == 'banded' and world == 1 and not hostsim and args.cpu_seconds > 0:
+        if args.full and args.extra_legs and args.config == 'banded' and world == 1 and not hostsim and args.cpu_seconds > 0:
             out['config']['perturbed_resolve'] = perturbed_resolves(m, q, l, u, 20, rho0, torch)
             out['config']['perturbed_resolve_ms'] = out['config']['perturbed_resolve']['solve_ms_median']
             for leg in ('lasso', 'portfolio'):
@@ -724,7 +763,7 @@ def main():
                     out['config'][leg] = config_leg(leg, args, settings, osqp_amd, problems, torch)
                 except Exception as e:          # noqa: BLE001 -- an extra leg must not lose the headline line
                     out['config'][leg] = {'error': repr(e)}
-        if args.cpu_seconds > 0 and world == 1:          # (the CPU baseline is timed at N = 1 only: the other ranks would wait 40 s at the barrier)
+        if args.full and args.cpu_seconds > 0 and world == 1:          # (the CPU baseline is timed at N = 1 only: the other ranks would wait 40 s at the barrier)
             cb = cpu_baseline(P, q, A, l, u, settings, args.cpu_seconds)
             cb['upstream_osqp'] = upstream_osqp_line(P, q, A, l, u, settings)      # "if `import osqp` happens to succeed on the box ..."; never required
             out['cpu_baseline'] = cb
