@@ -101,6 +101,10 @@ struct DevF1 {
   // set of D vectors: KA leaves the slices of rhs = sigma x - q + A' v in the parity-1 set and those of K x_g in the third (pcg_hip.hip f1_ka_body).
   // Dev::Minv / xs / p / r / s point into it.  r_k, s_{k-1} and rep_k (what launch F_k writes) live in parity k & 1.
   double *va = nullptr; size_t ns = 0;
+  // The same allocation continues with every other array the F body's load phase reads: rho (Dev::rho points here), pval, pcol, prp, a copy of
+  // A.rowptr and cptr, at the byte offsets below.  The F body reads all of them through ONE buffer resource over the arena (base va, vbytes records)
+  // at 32-bit offsets: no 64-bit pointer per array to fetch, hold or re-fetch (pcg_hip.hip F1Arena).  upload_f1 refuses an arena of 2 GiB or more.
+  unsigned vbytes = 0, o_rho = 0, o_pval = 0, o_pcol = 0, o_prp = 0, o_rowptr = 0, o_cptr = 0, nsb = 0;     // (nsb = 8 ns: the stride in bytes)
   // Per-block mixing (mix = 1): a row block of A whose columns do not fit one window keeps a window of at most kF1Win - kF1MaxFar columns and
   // treats the remaining columns -- at most kF1MaxFar distinct ones -- as FAR columns.  They occupy the LAST kF1MaxFar slots of the block's gather
   // list (the same 4 + D vector loads at column fcol[.] instead of g0 + e; which lanes serve them does not depend on the block's record) and

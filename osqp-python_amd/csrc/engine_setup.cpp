@@ -308,13 +308,29 @@ bool Engine::plan_f1(const std::vector<int> &rb, const std::vector<int> &Arp, co
   return true;
 }
 
-void Engine::upload_f1(const F1Plan &pl) {
+void Engine::upload_f1(const F1Plan &pl, const std::vector<int> &Arp) {
   d_.f1 = DevF1();
   if (!pl.ok) return;
+  // the arena (backend.h DevF1::va): the n-vectors, then rho, pval, pcol, prp, A's row pointers and cptr, each region 256-byte aligned
+  const size_t ns = ((size_t)n + 31) / 32 * 32;             // 256-byte aligned vectors
+  size_t at = 8 * (7 + 3 * (size_t)pl.D) * ns;
+  auto region = [&at](size_t bytes) { const size_t o = at; at += (std::max<size_t>(bytes, 1) + 255) / 256 * 256; return o; };
+  const size_t o_rho = region(8 * (size_t)m), o_pval = region(8 * (size_t)pl.pnnz), o_pcol = region(sizeof(int) * pl.pcol.size()),
+               o_prp = region(sizeof(int) * pl.prp.size()), o_rowptr = region(sizeof(int) * Arp.size()), o_cptr = region(sizeof(unsigned short) * pl.cptr.size());
+  if (at >= ((size_t)1 << 31)) return;                     // (32-bit buffer offsets: the two-kernel form instead)
   auto up_i = [&](const std::vector<int> &h) { int *p = dev_vec<int>(d_, h.size()); if (!h.empty()) be::h2d(d_, p, h.data(), sizeof(int) * h.size()); return p; };
   DevF1 &f = d_.f1;
   f.D = pl.D; f.pnnz = pl.pnnz;
-  f.blk = up_i(pl.blk); f.prp = up_i(pl.prp); f.pcol = up_i(pl.pcol); f.psrc = up_i(pl.psrc);
+  f.ns = ns; f.nsb = (unsigned)(8 * ns);
+  f.va = dev_vec<double>(d_, at / 8); f.vbytes = (unsigned)at;
+  unsigned char *ab = reinterpret_cast<unsigned char *>(f.va);
+  f.o_rho = (unsigned)o_rho; f.o_pval = (unsigned)o_pval; f.o_pcol = (unsigned)o_pcol; f.o_prp = (unsigned)o_prp; f.o_rowptr = (unsigned)o_rowptr; f.o_cptr = (unsigned)o_cptr;
+  f.pval = reinterpret_cast<double *>(ab + o_pval); f.pcol = reinterpret_cast<int *>(ab + o_pcol); f.prp = reinterpret_cast<int *>(ab + o_prp);
+  f.cptr = reinterpret_cast<unsigned short *>(ab + o_cptr);
+  auto put = [&](size_t o, const void *h, size_t bytes) { if (bytes) be::h2d(d_, ab + o, h, bytes); };
+  put(o_pcol, pl.pcol.data(), sizeof(int) * pl.pcol.size()); put(o_prp, pl.prp.data(), sizeof(int) * pl.prp.size());
+  put(o_rowptr, Arp.data(), sizeof(int) * Arp.size()); put(o_cptr, pl.cptr.data(), sizeof(unsigned short) * pl.cptr.size());
+  f.blk = up_i(pl.blk); f.psrc = up_i(pl.psrc);
   { // the blocks' matrix streams (backend.h DevF1::stream): the index words now, the values by be::f1_refresh once A.val is assembled
     const size_t nb = pl.blk.size() / 16;
     std::vector<unsigned char> hs(nb * (size_t)kF1StreamBytes, 0);
@@ -324,10 +340,6 @@ void Engine::upload_f1(const F1Plan &pl) {
     }
     f.stream = dev_vec<unsigned char>(d_, hs.size()); be::h2d(d_, f.stream, hs.data(), hs.size());
   }
-  f.cptr = dev_vec<unsigned short>(d_, pl.cptr.size()); be::h2d(d_, f.cptr, pl.cptr.data(), sizeof(unsigned short) * pl.cptr.size());
-  f.pval = dev_vec<double>(d_, pl.pnnz);
-  f.ns = ((size_t)n + 31) / 32 * 32;                       // 256-byte aligned vectors
-  f.va = dev_vec<double>(d_, (7 + 3 * (size_t)pl.D) * f.ns);
   if (pl.mix) {
     std::vector<int> spk((size_t)n), fc2(2 * pl.fcol.size(), 0);
     for (int j = 0; j < n; j++) spk[j] = (pl.sp_ptr[j] << 6) | (pl.sp_ptr[j + 1] - pl.sp_ptr[j]);
@@ -748,7 +760,7 @@ int Engine::setup(const OSQPCscMatrix *P, const double *q, const OSQPCscMatrix *
   prepare_wb(Arp, Arj);
   if (d_.wb.on) d_.fused = 0;                        // (the Woodbury-corrected preconditioner lives in the three-kernel PCG form)
   d_.f1 = DevF1();
-  if (d_.fused && f1ok) upload_f1(plan);
+  if (d_.fused && f1ok) upload_f1(plan, Arp);
   // (neither the one-launch form on A alone nor a Woodbury mode: the explicit reduced matrix, where its fill is moderate -- backend.h DevKf)
   if (d_.fused && !d_.f1.on && use_slots_) prepare_kf(Arp, Arj, Brp, Bj);
   if (reordered_) {
@@ -829,7 +841,7 @@ int Engine::setup(const OSQPCscMatrix *P, const double *q, const OSQPCscMatrix *
   lap("upload structure");
   auto dv = [&](size_t cnt) { return dev_vec<double>(d_, cnt); };
   d_.q = dv(n); d_.l = dv(m); d_.u = dv(m); d_.D = dv(n); d_.Dinv = dv(n); d_.E = dv(m); d_.Einv = dv(m);
-  d_.rho = dv(m); d_.rho_inv = dv(m); d_.ctype = dev_vec<int>(d_, m);
+  d_.rho = d_.f1.on ? reinterpret_cast<double *>(reinterpret_cast<unsigned char *>(d_.f1.va) + d_.f1.o_rho) : dv(m); d_.rho_inv = dv(m); d_.ctype = dev_vec<int>(d_, m);      // (F1: rho inside the arena)
   d_.x = dv(n); d_.z = dv(m); d_.y = dv(m); d_.dx = dv(n); d_.dy = dv(m); d_.zt = dv(m); d_.t0 = dv(m); d_.v = dv(m);
   d_.xg = dv(n); d_.xsp = dv(n); d_.ztg = dv(m);
   d_.theta = pol_.extrap;                            // PCG start extrapolation (backend.h Dev::xg)

@@ -736,6 +736,25 @@ __device__ __forceinline__ void gst_(double *p, double v) {
   if constexpr (WT) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else *p = v;
 }
 #define gst gst_<WT>
+// The F body's reads of the arena (backend.h DevF1::va: the n-vectors, rho, the P arrays, A's row pointers, cptr) through ONE buffer resource: a
+// read is  voffset (32 bits, per lane) + soffset (the array's place in the arena: an SGPR or a constant) -- four resource SGPRs and a few 32-bit
+// offsets instead of a 64-bit pointer per array, which the compiler, short of scalar registers, fetched from Dev again in front of its use
+// (s_load -> wait -> 64-bit address -> global_load, one scalar round trip per array on the block's critical path).  Plain loads (aux 0), as before.
+struct F1Arena {
+#if defined(__HIP_DEVICE_COMPILE__)
+  __amdgpu_buffer_rsrc_t r;
+  __device__ __forceinline__ F1Arena(const double *va, unsigned bytes) : r(__builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(va), 0, (int)bytes, 0x00020000)) {}
+  __device__ __forceinline__ double d(unsigned vo, unsigned so) const { return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, vo, so, 0)); }
+  __device__ __forceinline__ int i(unsigned vo, unsigned so) const { return (int)__builtin_amdgcn_raw_buffer_load_b32(r, vo, so, 0); }
+  __device__ __forceinline__ int h(unsigned vo, unsigned so) const { return (int)__builtin_amdgcn_raw_buffer_load_b16(r, vo, so, 0); }
+#else
+  const unsigned char *b;
+  __device__ F1Arena(const double *va, unsigned) : b(reinterpret_cast<const unsigned char *>(va)) {}
+  __device__ double d(unsigned vo, unsigned so) const { return *reinterpret_cast<const double *>(b + vo + so); }
+  __device__ int i(unsigned vo, unsigned so) const { return *reinterpret_cast<const int *>(b + vo + so); }
+  __device__ int h(unsigned vo, unsigned so) const { return *reinterpret_cast<const unsigned short *>(b + vo + so); }
+#endif
+};
 template <int D, bool FIRST, bool MIX, bool WT>
 __device__ __forceinline__ void f1_body(const Dev &d, const int k, const bool vec_only, const F1Scal sc, F1Lds &L, F1Stream &S, const F1Rec &rec0, const int par) {
   const DevF1 &f = d.f1;
@@ -744,15 +763,18 @@ __device__ __forceinline__ void f1_body(const Dev &d, const int k, const bool ve
   KT(1);
   // every n-vector of the iteration lives in ONE arena (DevF1::va, stride ns): the addresses derive from one base pointer by scalar
   // adds instead of a kernel-argument load per vector
-  const double *va = gptr(f.va); const size_t ns = f.ns;
-  const double *Minv = va, *xs_r = va + ns, *p_r = va + 2 * ns;
+  // (reads: through the arena's buffer resource at byte offsets -- F1Arena; stores: global pointers into the same arena)
+  const size_t ns = f.ns;
+  const F1Arena ar(f.va, f.vbytes);
+  const unsigned nsb = f.nsb;
+  const unsigned oxs = nsb, op = 2 * nsb;                   // Minv at 0, x~, p
+  const unsigned orr = (3 + cur) * nsb;                     // r_{k-1}
+  const unsigned osp = (5 + cur) * nsb;                     // s_{k-2}: stored next to r_{k-1}
+  const unsigned orep = (7 + cur * D) * nsb;                // K u_{k-1} in D partial vectors  (F_0: the slices of r_0 = rhs - K x_g that f1_ka_body left)
+  [[maybe_unused]] const unsigned orepV = (7 + 2 * D) * nsb;      // F_0: the slices of rhs = sigma x - q + A' v alone (||rhs||_inf: read on the own columns only)
   double *xs_w = gptr(f.va) + ns, *p_w = gptr(f.va) + 2 * ns;
-  const double *rread = va + (3 + (cur == 0 ? 0 : 1)) * ns;                 // r_{k-1}
   double *rnxt = gptr(f.va) + (3 + nxt) * ns;                     // r_k
-  const double *sprev = va + (5 + cur) * ns;                // s_{k-2}: stored next to r_{k-1}
   double *snew = gptr(f.va) + (5 + nxt) * ns;                     // s_{k-1}: stored next to r_k
-  const double *repcur = va + (7 + (size_t)cur * D) * ns;   // K u_{k-1} in D partial vectors  (F_0: the slices of r_0 = rhs - K x_g that f1_ka_body left)
-  const double *repV = va + (7 + (size_t)2 * D) * ns;       // F_0: the slices of rhs = sigma x - q + A' v alone (||rhs||_inf: read on the own columns only)
   double *repnxt = gptr(f.va) + (7 + (size_t)nxt * D) * ns;
   // per-block mixing: the spill sets that go with the three replica sets, the spill slots by column
   [[maybe_unused]] const double *spcur = MIX ? gptr(f.spill) + (size_t)cur * (f.nsp + 2) : nullptr, *spV = MIX ? gptr(f.spill) + 2 * (f.nsp + 2) : nullptr;
@@ -802,7 +824,7 @@ __device__ __forceinline__ void f1_body(const Dev &d, const int k, const bool ve
     //  block's stores.  The last budgeted update (vec_only) requests a few values it does not use.)
     const bool hasp = !vec_only && tid < pcnt;
     const int pe = min(pk0 + max(0, min(tid, pcnt - 1)), f.pnnz - 1);
-    const double pv = gptr(f.pval)[pe]; const int pc = gptr(f.pcol)[pe];
+    const double pv = ar.d(8u * pe, f.o_pval); const int pc = ar.i(4u * pe, f.o_pcol);
     // ---- window parts (+ p, x~ where the window column is one of the block's own)
     double wm[CW], wr[CW], wsv[CW], wq[CW][D], wpp[CW], wx[CW];
     bool wown[CW];
@@ -815,15 +837,15 @@ __device__ __forceinline__ void f1_body(const Dev &d, const int k, const bool ve
         int c = g0 + min(e, gl - 1);
         if constexpr (MIX) { const bool isfar = u == CW - 1 && e >= kFB && e - kFB < nfc; if (isfar) c = fcl.x; wsw[u] = isfar ? fcl.y : spk[c]; }
         wown[u] = e < gl && c >= cs0 && c - cs0 < nown;
-        wm[u] = Minv[c];
+        wm[u] = ar.d(8u * c, 0);
 #pragma unroll
-        for (int q = 0; q < D; q++) wq[u][q] = repcur[q * ns + c];
+        for (int q = 0; q < D; q++) wq[u][q] = ar.d(8u * c, orep + q * nsb);
         const int co = wown[u] ? c : g0;                    // (other lanes re-read one valid element: no branch around the loads)
         if (!FIRST) {
-          wr[u] = rread[c];
-          wsv[u] = sprev[c];
-          wx[u] = xs_r[co]; wpp[u] = p_r[co];
-        } else { wx[u] = xs_r[co]; wpp[u] = gptr(d.xg)[co]; }      // F_0: the own lane also moves x~ on (x~_prev <- x~, x~ <- x_g)
+          wr[u] = ar.d(8u * c, orr);
+          wsv[u] = ar.d(8u * c, osp);
+          wx[u] = ar.d(8u * co, oxs); wpp[u] = ar.d(8u * co, op);
+        } else { wx[u] = ar.d(8u * co, oxs); wpp[u] = gptr(d.xg)[co]; }      // F_0: the own lane also moves x~ on (x~_prev <- x~, x~ <- x_g)
       }
     }
     if constexpr (MIX) {                                     // the spill slots: behind the packed words alone (the first of this lane's requests to return)
@@ -833,17 +855,17 @@ __device__ __forceinline__ void f1_body(const Dev &d, const int k, const bool ve
     // ---- row / column pointers (the matrix entries themselves arrive in LDS: S, requested one block ahead)
     int cp0[CW], cp1[CW];
     const int prow = r0 + min(tid, nrows - 1);
-    const int rp0 = gptr(d.A.rowptr)[prow], rp1 = gptr(d.A.rowptr)[prow + 1]; const double rrho = gptr(d.rho)[prow];
+    const int rp0 = ar.i(4u * prow, f.o_rowptr), rp1 = ar.i(4u * prow, f.o_rowptr + 4); const double rrho = ar.d(8u * prow, f.o_rho);
 #pragma unroll
     for (int u = 0; u < CW; u++) {
       if (u < ns2) {
         int c = min(tid + u * kBlock, wl - 1);
         if constexpr (MIX) { const int cf = tid + u * kBlock - kFB; if (u == CW - 1 && cf >= 0 && cf < nfc) c = wl + cf; }      // a far segment: behind the window's
-        cp0[u] = gptr(f.cptr)[cpo + c]; cp1[u] = gptr(f.cptr)[cpo + c + 1];
+        cp0[u] = ar.h(2u * (cpo + c), f.o_cptr); cp1[u] = ar.h(2u * (cpo + c), f.o_cptr + 2);
       }
     }
     const int pj = min(cs0 + max(0, min(tid, nown - 1)), n - 1);
-    const int pp0 = gptr(f.prp)[pj], pp1 = gptr(f.prp)[pj + 1];
+    const int pp0 = ar.i(4u * pj, f.o_prp), pp1 = ar.i(4u * pj, f.o_prp + 4);
     // ---- a (P + sigma I) entry whose column lies outside the window: its operand is recomputed from its parts in the product phase below (requested
     //      THERE: held from here they would cost 7 + 2 D registers across the block's register peak for a case banded problems never meet)
     const int pcl = pc - g0;
@@ -878,19 +900,19 @@ __device__ __forceinline__ void f1_body(const Dev &d, const int k, const bool ve
     for (int jj = tid; jj < nown; jj += kBlock) {
       const int j = cs0 + jj;
       if (j >= g0 && j - g0 < gl) continue;
-      const double mi = Minv[j];
+      const double mi = ar.d(8u * j, 0);
       double rp[D];
 #pragma unroll
-      for (int q = 0; q < D; q++) rp[q] = repcur[q * ns + j];
+      for (int q = 0; q < D; q++) rp[q] = ar.d(8u * j, orep + q * nsb);
       double un;
       double wj = f1_w<D>(rp);
       if constexpr (MIX) wj += f1_spill_sum(spcur, spk, j);
       if constexpr (FIRST) {
         const double r0 = wj;
         un = mi * r0;
-        gst(rnxt + j, r0); gst(gptr(d.xsp) + j, xs_r[j]); gst(xs_w + j, gptr(d.xg)[j]);
+        gst(rnxt + j, r0); gst(gptr(d.xsp) + j, ar.d(8u * j, oxs)); gst(xs_w + j, gptr(d.xg)[j]);
         g_acc += r0 * un; rn_acc = nanmax(rn_acc, fabs(r0));
-      } else un = own_update(j, mi, rread[j], wj, sprev[j], p_r[j], xs_r[j]);
+      } else un = own_update(j, mi, ar.d(8u * j, orr), wj, ar.d(8u * j, osp), ar.d(8u * j, op), ar.d(8u * j, oxs));
       if (!vec_only) L.uown[jj] = un;
     }
     if (vec_only) continue;
@@ -912,7 +934,7 @@ __device__ __forceinline__ void f1_body(const Dev &d, const int k, const bool ve
     if constexpr (FIRST) {
       const int j = cs0 + max(0, min(tid, nown - 1));
 #pragma unroll
-      for (int q = 0; q < D; q++) bv[q] = repV[q * ns + j];
+      for (int q = 0; q < D; q++) bv[q] = ar.d(8u * j, orepV + q * nsb);
       if constexpr (MIX) bsw = spk[j];
     }
     // ---- products: A entries against the window; the (P + sigma I) entry against the window or its recomputed operand
@@ -927,12 +949,12 @@ __device__ __forceinline__ void f1_body(const Dev &d, const int k, const bool ve
       else {
         double eq[D];
 #pragma unroll
-        for (int q = 0; q < D; q++) eq[q] = repcur[q * ns + pc];
-        const double em = Minv[pc];
+        for (int q = 0; q < D; q++) eq[q] = ar.d(8u * pc, orep + q * nsb);
+        const double em = ar.d(8u * pc, 0);
         double ew = f1_w<D>(eq);
         if constexpr (MIX) ew += f1_spill_sum(spcur, spk, pc);
         if constexpr (FIRST) uv = em * ew;
-        else { double sn, rn; f1_upd(sc, em, rread[pc], ew, sprev[pc], sn, rn, uv); }
+        else { double sn, rn; f1_upd(sc, em, ar.d(8u * pc, orr), ew, ar.d(8u * pc, osp), sn, rn, uv); }
       }
       L.pprod[tid] = pv * uv;
     }
@@ -952,8 +974,8 @@ __device__ __forceinline__ void f1_body(const Dev &d, const int k, const bool ve
       L.tvec[tid] = t; dl_acc += t * au;
     }
     for (int row = tid + kBlock; row < nrows; row += kBlock) {
-      const int q0 = gptr(d.A.rowptr)[r0 + row], q1 = gptr(d.A.rowptr)[r0 + row + 1];
-      const double au = f1_segsum<6>(L.prod, q0 - k0, q1 - k0), t = gptr(d.rho)[r0 + row] * au;
+      const int q0 = ar.i(4u * (r0 + row), f.o_rowptr), q1 = ar.i(4u * (r0 + row), f.o_rowptr + 4);
+      const double au = f1_segsum<6>(L.prod, q0 - k0, q1 - k0), t = ar.d(8u * (r0 + row), f.o_rho) * au;
       L.tvec[row] = t; dl_acc += t * au;
     }
     KT(6);
@@ -966,7 +988,7 @@ __device__ __forceinline__ void f1_body(const Dev &d, const int k, const bool ve
       L.puown[tid] = pu; dl_acc += L.uown[tid] * pu;
     }
     for (int jj = tid + kBlock; jj < nown; jj += kBlock) {
-      const int q0 = gptr(f.prp)[cs0 + jj], q1 = gptr(f.prp)[cs0 + jj + 1];
+      const int q0 = ar.i(4u * (cs0 + jj), f.o_prp), q1 = ar.i(4u * (cs0 + jj), f.o_prp + 4);
       const double pu = f1_segsum<4>(L.pprod, q0 - pk0, q1 - pk0);
       L.puown[jj] = pu; dl_acc += L.uown[jj] * pu;
     }
@@ -995,7 +1017,7 @@ __device__ __forceinline__ void f1_body(const Dev &d, const int k, const bool ve
       for (int jj = tid + kBlock; jj < nown; jj += kBlock) {
         double rv[D];
 #pragma unroll
-        for (int q = 0; q < D; q++) rv[q] = repV[q * ns + cs0 + jj];
+        for (int q = 0; q < D; q++) rv[q] = ar.d(8u * (cs0 + jj), orepV + q * nsb);
         bn_acc = nanmax(bn_acc, fabs(MIX ? f1_w<D>(rv) + f1_spill_sum(spV, spk, cs0 + jj) : f1_w<D>(rv)));
       }
     }
