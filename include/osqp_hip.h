@@ -205,8 +205,9 @@ typedef struct {
                                  3: ... and the short rows / columns by one thread each (k_wbf_rb, k_wbf_s2: seven launches) */
   double woodbury_one_launch; /* 1: the Woodbury direct mode of a few dense rows runs ONE launch per ADMM iteration (k_wbz; woodbury_direct = 2 and OSQPHipPolicy::woodbury_fused = 1) */
   double kform_nnz;           /* K form: stored entries of the explicit reduced matrix K = P + sigma I + A' diag(rho) A (0: the form is not in use) */
-  double batch_wave_split;    /* last batch solve: -1 = workgroup-per-problem kernels only; >= 0 = the wave-per-problem kernel ran, with this many of the
-                                 longest-expected problems on the workgroup kernel beside it (0: no launch order yet) */
+  double batch_wave_split;    /* last batch solve, as launched: -1 = workgroup-per-problem kernels only; >= 0 = the wave-per-problem kernel ran, with this
+                                 many of the longest-expected problems on the workgroup kernel beside it (0: the wave kernel took them all -- no launch
+                                 order yet, or a batch or device too small to split) */
 } OSQPHipStats;
 /* OSQPHipStats::preconditioner.  `cg_precond = OSQP_DIAGONAL_PRECONDITIONER` (bindings.cpp.in:426, the reference's only preconditioner) selects the
    Jacobi family: plain Jacobi M = diag(K), and -- this engine's addition, on by default, OSQPHipPolicy::woodbury / woodbury_large = 0 switch it

@@ -309,6 +309,9 @@ struct Dev {
   double *r = nullptr, *uu = nullptr, *p = nullptr, *s = nullptr, *w = nullptr, *t = nullptr, *Minv = nullptr;
   double *uu2 = nullptr, *ms = nullptr;  // fused PCG: u_k lives in (k&1 ? uu2 : uu); ms (2n) = interleaved pairs {u_k[j], (Minv .* s_k)[j]}
   int fused = 0;                 // 1: two kernels per PCG iteration (vector update k-1 fused into the SpMV-A kernel of iteration k)
+  // what the last be::batch_solve launched (OSQPHipStats::batch_wave_split): -1 no wave-per-problem kernel; >= 0 the wave kernel, with this many
+  // positions of the launch order on the workgroup kernel beside it.  (In the padding in front of f1: the layout kernels receive by value stays.)
+  int batch_wave_ran = -1;
   DevF1 f1;                      // one launch per PCG iteration (slot form only; f1.on)
   DevKf kf;                      // one launch per PCG iteration on the explicit reduced matrix (slot form only; kf.on; never together with f1.on)
   DevWb wb;                      // Woodbury-corrected preconditioner for a few dense rows (three-kernel PCG form; wb.on)
@@ -388,6 +391,7 @@ struct BatchParams {
   int wv_first = 0;              // positions [0, wv_first) of the launch order are not the wave kernel's (be::batch_solve sends them to the workgroup kernel)
   int wv_split = 0;              // how many of the first positions the engine wants treated that way (0: none; needs a launch order)
   int wv_cus = 0;                // ... and on how many CUs (the wave kernel's grid leaves them free; wv_split > wv_cus: several problems per CU, one after the other)
+  int wide_rounds = 1 << 20;     // the spectral workgroup kernel takes its two-per-CU form for more than wide_rounds rounds of one workgroup per CU (A/B runs)
   int *wv_queue = nullptr;       // device counter: the next position of the launch order not yet taken by a wave (zeroed before the launch)
 };
 constexpr int kBatchWaveW = 8;          // waves (= problems in flight) per workgroup of the wave-per-problem kernel; one workgroup per CU
@@ -395,10 +399,34 @@ constexpr int kBatchWaveSA = 128, kBatchWaveST = 128;   // most ELL steps of A /
 constexpr int kBatchSpecN = 128;        // the spectral form keeps K^-1 in registers: row i = thread / 2, 64 columns per thread
 constexpr double kBatchUnsolved = -1000.0;
 
+// Doubles of LDS taken by the index arrays of the batch kernel's register path: row pointers of A (m + 1) and B (n + 1), permutation (n).
+constexpr int batch_index_doubles(int n, int m) { return (m + 2 * n + 2 + 1) / 2; }
+
+// What be::batch_solve launches for a BatchParams (batch_plan.cpp, host arithmetic only): an optional spectral stage for the problems whose
+// constraint classes are the reference's, then the follow-up kernel for the rest (only the problems the spectral stage marked, if it ran).
+struct BatchPlan {
+  enum Spec { kNoSpec, kSpecWorkgroup, kSpecWave };
+  int spec = kNoSpec;
+  // spectral workgroup kernel k_batch_admm<256, spec_e, spec_e, true, false, false, true, W>: W = spec_w for a launch of the whole batch,
+  // split_w for one of the first `split` positions of the launch order
+  int spec_e = 0, spec_w = 1, split_w = 1;
+  size_t lds_spec = 0;
+  // wave kernel k_batch_wave<n8>: the first `split` positions go to the workgroup kernel on a second stream; grid wgs, or wgs_all without the split
+  int n8 = 0, split = 0, wgs = 0, wgs_all = 0;
+  size_t lds_w = 0;
+  // follow-up k_batch_admm<tb, e, e, direct, pol, small>; variant as OSQPHipPolicy::batch_variant (1 direct, 2 direct256, 3 w64, 4 w256, 5 generic),
+  // 0: no variant fits
+  int variant = 0, tb = 0, e = 0;
+  bool direct = false, pol = false, small = false;
+  size_t lds = 0;
+};
+BatchPlan plan_batch(const BatchParams &p, int cus);        // cus: compute units of the device
+
 namespace be {
 
 size_t batch_lds_bytes(int n, int m);                       // 0 if a problem does not fit one workgroup's LDS
-// stream == nullptr: on d.stream, synchronous.  Otherwise enqueued on that hipStream_t and NOT waited for.  OSQP_FUNC_NOT_IMPLEMENTED if it does not fit
+// stream == nullptr: on d.stream, synchronous.  Otherwise enqueued on that hipStream_t and NOT waited for.  OSQP_FUNC_NOT_IMPLEMENTED if it does not fit.
+// Sets d.batch_wave_ran.
 int batch_solve(Dev &d, const BatchParams &p, void *stream = nullptr);
 size_t batch_direct_lds_bytes(int n, int m, int nnz, int bw); // 0 if the banded factor does not fit next to the iterates
 bool batch_direct_selected(const BatchParams &p);              // would batch_solve run a direct (banded LDL') variant for p?

@@ -12,11 +12,9 @@
 // /root/reference/src/osqppurepy/_osqp.py.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <string>
+#include <type_traits>
 
 #include "../../include/osqp_hip.h"
 #include "backend.h"
@@ -126,8 +124,6 @@ struct Red {
 
 namespace {
 
-// Doubles of LDS taken by the index arrays of the register path: row pointers of A (m + 1) and B (n + 1), permutation (n).
-__host__ __device__ inline int batch_index_doubles(int n, int m) { return (m + 2 * n + 2 + 1) / 2; }
 // sum of prod[a .. z) in entry order; the loads of a batch of eight are independent (one LDS latency per batch, not per entry)
 __device__ __forceinline__ double row_sum(const double *prod, int a, int z) {
   double acc = 0.0;
@@ -1287,19 +1283,6 @@ __global__ __launch_bounds__(64 * kBatchWaveW, 1) void k_batch_wave(BatchParams 
 
 }  // namespace
 
-// LDS needed per problem (bytes); 0 if the problem does not fit one workgroup's LDS.  nnz > 0 adds the product buffer of
-// the register-resident path.
-size_t batch_lds_bytes_nnz(int n, int m, int nnz) {
-  const size_t b = sizeof(double) * ((size_t)10 * n + (size_t)8 * m + 16 + (nnz > 0 ? (size_t)((nnz + 1) & ~1) + batch_index_doubles(n, m) : 0));
-  return b <= 64 * 1024 ? b : 0;
-}
-size_t batch_lds_bytes(int n, int m) { return batch_lds_bytes_nnz(n, m, 0); }
-size_t batch_direct_lds_bytes(int n, int m, int nnz, int bw) {
-  if (bw < 0 || bw > kBatchDirectMaxBw) return 0;
-  const size_t n8 = (size_t)(n + kBatchNB - 1) / kBatchNB * kBatchNB;
-  const size_t b = sizeof(double) * ((size_t)10 * n + (size_t)8 * m + 16 + (size_t)((nnz + 1) & ~1) + batch_index_doubles(n, m) + kBatchNB + n8 * (bw + kBatchNB) + 64);
-  return b <= 144 * 1024 ? b : 0;         // (above the default 64 KB dynamic-LDS limit: batch_solve raises it; gfx950 has 160 KB per CU)
-}
 __global__ void k_batch_products(DevCsr A, int nprod, const int *a, const int *b, double *out) {
   for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < nprod; p += gridDim.x * blockDim.x) out[p] = A.val[a[p]] * A.val[b[p]];
 }
@@ -1389,98 +1372,51 @@ int batch_prepare(Dev &d, const BatchParams &p, const double *Px_b, const double
   return OSQP_NO_ERROR;
 }
 
-namespace {
-struct BatchChoice { bool dir256, dir64, w64, w256, generic; int e64, e256; size_t lds_reg, lds_gen, lds_dir; };
-BatchChoice choose_batch_variant(const BatchParams &p) {
-  BatchChoice c{};
-  const int mx = p.A.nnz > p.B.nnz ? p.A.nnz : p.B.nnz;
-  c.lds_reg = batch_lds_bytes_nnz(p.n, p.m, mx); c.lds_gen = batch_lds_bytes(p.n, p.m);
-  static const char *const names[] = {nullptr, "direct", "direct256", "w64", "w256", "generic"};      // OSQPHipPolicy::batch_variant (debugging / A-B runs)
-  const char *force = (p.variant >= 1 && p.variant <= 5) ? names[p.variant] : nullptr;
-  c.e64 = (mx + 63) / 64; c.e256 = (mx + 255) / 256;
-  const bool can64 = c.lds_reg && c.e64 <= 24 && p.n <= 1024 && p.m <= 2048, can256 = c.lds_reg && c.e256 <= 8;
-  c.lds_dir = batch_direct_lds_bytes(p.n, p.m, mx, p.bw);
-  // (the direct variant with four waves also comes with 16 entries per lane: up to 4096 stored entries per matrix, one problem per CU)
-  const bool can_dir = can64 && c.lds_dir && p.perm, can_dir256 = c.lds_reg && c.e256 <= 16 && c.lds_dir && p.perm;
-  // default: the direct solve with four waves per problem (MPC batch: 14.2 ms; one wave 18.6 ms; PCG, one wave: 37 ms)
-  c.dir256 = force ? !std::strcmp(force, "direct256") && can_dir256 : can_dir256;
-  c.dir64 = !c.dir256 && (force ? !std::strcmp(force, "direct") && can_dir : can_dir);
-  c.w64 = !c.dir64 && !c.dir256 && (force ? !std::strcmp(force, "w64") && can64 : can64);
-  c.w256 = !c.dir64 && !c.dir256 && !c.w64 && (force ? !std::strcmp(force, "w256") && can256 : can256);
-  c.generic = !c.dir64 && !c.dir256 && !c.w64 && !c.w256 && c.lds_gen;
-  return c;
-}
-}  // namespace
 void batch_release(Dev &d) {
   if (d.bside) { (void)hipStreamDestroy(static_cast<hipStream_t>(d.bside)); d.bside = nullptr; }
   if (d.bev0) { (void)hipEventDestroy(static_cast<hipEvent_t>(d.bev0)); d.bev0 = nullptr; }
   if (d.bev1) { (void)hipEventDestroy(static_cast<hipEvent_t>(d.bev1)); d.bev1 = nullptr; }
 }
-bool batch_direct_selected(const BatchParams &p) { const BatchChoice c = choose_batch_variant(p); return c.dir256 || c.dir64; }
-// rows / columns of V in the wave kernel's LDS: compile-time, three instantiations (n <= 64: 33 KB; n <= 120: the MPC batch's 116 KB; n <= 128)
-static int batch_wave_n8(int n) { return n <= 64 ? 64 : (n <= 120 ? 120 : 128); }
-size_t batch_wave_lds_bytes(int n, int m, int steps) {
-  if (n < 1 || n > kBatchSpecN || m < 1 || m > 256) return 0;
-  const size_t n8 = (size_t)batch_wave_n8(n), S = n8 + 1, stg = (size_t)((n > m ? n : m) + 1) & ~(size_t)1;
-  const size_t b = sizeof(double) * (((n8 * S + 1) & ~(size_t)1) + (size_t)steps * 64 + (size_t)kBatchWaveW * stg) + sizeof(unsigned short) * (size_t)steps * 64;
-  // (V t reads row min(64 + lane, n - 1) and V' rhs reads 64 words past a row's start: both stay inside V + staging)
-  return b <= 160 * 1024 ? b : 0;
-}
+namespace {
+// run-time value -> compile-time constant: f(std::integral_constant<int, V>()) for the V of Vs equal to v (plan_batch picks v from the same list)
+template <int... Vs, class F>
+void with_const(int v, F &&f) { (void)((v == Vs && (f(std::integral_constant<int, Vs>()), true)) || ...); }
+template <class F>
+void with_bool(bool b, F &&f) { if (b) f(std::true_type()); else f(std::false_type()); }
+using BatchKernel = void (*)(BatchParams);
+bool reserve_lds(BatchKernel k, size_t lds) { return hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess; }
+}  // namespace
 
+// Carries out plan_batch(p): the spectral stage, if planned, then the follow-up.  A stage whose LDS the device refuses falls back: the wave form to the
+// spectral workgroup form (its split positions to the wave kernel), the spectral workgroup form to the follow-up alone.  d.batch_wave_ran reports
+// what was launched.
 int batch_solve(Dev &d, const BatchParams &p, void *stream) {
+  d.batch_wave_ran = -1;
   if (hipSetDevice(d.device) != hipSuccess) return OSQP_ALGEBRA_LOAD_ERROR;
   hipStream_t st = static_cast<hipStream_t>(stream ? stream : d.stream);
-  const BatchChoice ch = choose_batch_variant(p);
-  const int e64 = ch.e64, e256 = ch.e256;
-  const size_t lds_reg = ch.lds_reg, lds_gen = ch.lds_gen, lds_dir = ch.lds_dir;
-  const bool use_dir256 = ch.dir256, use_dir = ch.dir64, use64 = ch.w64, use256 = ch.w256;
-#define BATCH_LAUNCH(TB, E, LDS) hipLaunchKernelGGL((k_batch_admm<TB, E, E, false>), dim3(p.nbatch), dim3(TB), LDS, st, p)
-#define BATCH_LAUNCH_DIRECT_P(TB, E, POL, SMALL) do { \
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_batch_admm<TB, E, E, true, POL, SMALL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_dir) != hipSuccess) \
-      throw DeviceError("osqp_hip: cannot reserve LDS for the direct batch kernel"); \
-    hipLaunchKernelGGL((k_batch_admm<TB, E, E, true, POL, SMALL>), dim3(p.nbatch), dim3(TB), lds_dir, st, p); } while (0)
-#define BATCH_LAUNCH_DIRECT_N(TB, E, SMALL) do { if (p.polish) BATCH_LAUNCH_DIRECT_P(TB, E, true, SMALL); else BATCH_LAUNCH_DIRECT_P(TB, E, false, SMALL); } while (0)
-  // (256-thread kernels: n <= 128 takes the instantiation whose substitutions keep every element in registers, ksolve)
-#define BATCH_LAUNCH_DIRECT(TB, E) do { if (TB == 256 && p.n <= 128) BATCH_LAUNCH_DIRECT_N(TB, E, (TB == 256)); else BATCH_LAUNCH_DIRECT_N(TB, E, false); } while (0)
-  // The spectral form of the direct solve where the engine has prepared it (BatchParams::sp_V): every problem whose constraint classes are the
-  // reference's is solved by this launch; the others are marked and left to the banded kernel launched right behind (only_marked).
-  bool spectral = false;
-  const int prod_len = ((p.A.nnz > p.B.nnz ? p.A.nnz : p.B.nnz) + 1) & ~1;
   int cus = 256;
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, d.device);
-  const bool spec_ok = use_dir256 && p.sp_V && !p.mat_on && !p.polish && p.n <= kBatchSpecN && e256 <= 8 && prod_len >= 4 * (kBatchSpecN + 2) && !p.only_marked;
-  // workgroup-per-problem spectral launch of the first q.nbatch positions of the launch order, on stream s; false: the device refused the LDS reservation
-  // (the banded launch below then takes the whole batch)
-  auto spec_launch = [&](const BatchParams &q, hipStream_t s) -> bool {
-    const size_t lds_spec = lds_reg + sizeof(double) * (kBatchNB + 2 * kBatchSpecN + 4);
-    bool ok = true;
-#define BATCH_LAUNCH_SPEC_W(E, W) do { \
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_batch_admm<256, E, E, true, false, false, true, W>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_spec) != hipSuccess) { (void)hipGetLastError(); ok = false; } \
-    else hipLaunchKernelGGL((k_batch_admm<256, E, E, true, false, false, true, W>), dim3(q.nbatch), dim3(256), lds_spec, s, q); } while (0)
-    // One workgroup per CU (everything in registers) at every batch size: since K^-1 lives in the matrix instruction's result registers the two-per-CU
-    // form (256 registers, scratch) no longer wins on large batches either -- 4096 QPs 5.9 ms against 6.2 ms.  OSQP_HIP_BATCH_WIDE_ROUNDS=r selects it for
-    // batches of more than r rounds of one workgroup per CU (A/B runs).
-    static const int wide_rounds = std::getenv("OSQP_HIP_BATCH_WIDE_ROUNDS") ? std::atoi(std::getenv("OSQP_HIP_BATCH_WIDE_ROUNDS")) : (1 << 20);
-    const bool wide = q.nbatch > wide_rounds * cus;
-#define BATCH_LAUNCH_SPEC(E) do { if (wide) BATCH_LAUNCH_SPEC_W(E, 2); else BATCH_LAUNCH_SPEC_W(E, 1); } while (0)
-    if (e256 <= 2) BATCH_LAUNCH_SPEC(2); else if (e256 <= 4) BATCH_LAUNCH_SPEC(4); else if (e256 <= 6) BATCH_LAUNCH_SPEC(6); else BATCH_LAUNCH_SPEC(8);
-#undef BATCH_LAUNCH_SPEC
-#undef BATCH_LAUNCH_SPEC_W
+  const BatchPlan pl = plan_batch(p, cus);
+  bool spectral = false;
+  // spectral workgroup kernel on the first q.nbatch positions of the launch order, on stream s; false: the device refused the LDS reservation
+  auto spec_launch = [&](const BatchParams &q, int w, hipStream_t s) {
+    bool ok = false;
+    with_const<2, 4, 6, 8>(pl.spec_e, [&](auto E) {
+      with_const<1, 2>(w, [&](auto W) {
+        const BatchKernel k = &k_batch_admm<256, decltype(E)::value, decltype(E)::value, true, false, false, true, decltype(W)::value>;
+        ok = reserve_lds(k, pl.lds_spec);
+        if (ok) hipLaunchKernelGGL(k, dim3(q.nbatch), dim3(256), pl.lds_spec, s, q); else (void)hipGetLastError();
+      });
+    });
     return ok;
   };
-  if (spec_ok && !p.wv_on) spectral = spec_launch(p, st);
-  // ... one WAVE per problem where the engine has prepared that form (wv_on): eight problems in flight per CU.  A problem on one wave takes ~12 us per ADMM
-  // iteration against 3.7 for a workgroup, and a batch ends with its slowest problem: with a launch order (longest-expected first) the first wv_split
-  // positions -- the outliers, 38 of the MPC batch's 4096 problems take 200 .. 375 iterations against a mean of 95 -- go to the workgroup kernel on a second
-  // stream, one CU each, while the wave kernel runs on the other CUs.
-  if (spec_ok && p.wv_on) {
-    const size_t lds_w = batch_wave_lds_bytes(p.n, p.m, p.wv_aend[3] + p.wv_tend[1]);
-    const int split = (p.order && p.wv_split > 0 && p.wv_cus > 0 && p.nbatch >= 8 * p.wv_split && cus > 2 * p.wv_cus) ? p.wv_split : 0;
-    auto launch = [&](auto kern) {
-      if (!lds_w || hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_w) != hipSuccess) { (void)hipGetLastError(); return; }
+  if (pl.spec == BatchPlan::kSpecWave) {
+    with_const<64, 120, 128>(pl.n8, [&](auto N8) {
+      const BatchKernel k = &k_batch_wave<decltype(N8)::value>;
+      if (!reserve_lds(k, pl.lds_w)) { (void)hipGetLastError(); return; }
       BatchParams pw = p;
       hipStream_t side = nullptr; hipEvent_t ev0 = nullptr, ev1 = nullptr;
-      if (split) {
+      if (pl.split) {
         if (!d.bside) {
           hipStream_t s2; hipEvent_t a, b;
           if (hipStreamCreateWithFlags(&s2, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&a, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&b, hipEventDisableTiming) != hipSuccess)
@@ -1488,41 +1424,37 @@ int batch_solve(Dev &d, const BatchParams &p, void *stream) {
           d.bside = s2; d.bev0 = a; d.bev1 = b;
         }
         side = static_cast<hipStream_t>(d.bside); ev0 = static_cast<hipEvent_t>(d.bev0); ev1 = static_cast<hipEvent_t>(d.bev1);
-        BatchParams ph = p; ph.nbatch = split; ph.wv_on = 0;
+        BatchParams ph = p; ph.nbatch = pl.split; ph.wv_on = 0;
         if (hipEventRecord(ev0, st) != hipSuccess || hipStreamWaitEvent(side, ev0, 0) != hipSuccess) throw DeviceError("osqp_hip: batch stream fork failed");
-        if (spec_launch(ph, side)) pw.wv_first = split;               // (refused: the wave kernel takes them as well)
+        if (spec_launch(ph, pl.split_w, side)) pw.wv_first = pl.split;               // (refused: the wave kernel takes them as well)
         if (hipEventRecord(ev1, side) != hipSuccess) throw DeviceError("osqp_hip: batch stream join failed");
       }
       if (hipMemsetAsync(p.wv_queue, 0, sizeof(int), st) != hipSuccess) throw DeviceError("osqp_hip: batch queue reset failed");
-      const int wgs = std::max(1, std::min(cus - (pw.wv_first ? p.wv_cus : 0), p.nbatch - pw.wv_first));      // (fewer problems than CUs: one wave per workgroup gets one)
-      hipLaunchKernelGGL(kern, dim3(wgs), dim3(64 * kBatchWaveW), lds_w, st, pw);
-      if (split && hipStreamWaitEvent(st, ev1, 0) != hipSuccess) throw DeviceError("osqp_hip: batch stream join failed");
-      spectral = true;
-    };
-    if (batch_wave_n8(p.n) == 64) launch(&k_batch_wave<64>); else if (batch_wave_n8(p.n) == 120) launch(&k_batch_wave<120>); else launch(&k_batch_wave<128>);
-    if (!spectral) spectral = spec_launch(p, st);       // (no room for the wave form's LDS: the workgroup form)
+      hipLaunchKernelGGL(k, dim3(pw.wv_first ? pl.wgs : pl.wgs_all), dim3(64 * kBatchWaveW), pl.lds_w, st, pw);
+      if (pl.split && hipStreamWaitEvent(st, ev1, 0) != hipSuccess) throw DeviceError("osqp_hip: batch stream join failed");
+      d.batch_wave_ran = pw.wv_first; spectral = true;
+    });
   }
+  if (pl.spec != BatchPlan::kNoSpec && !spectral) spectral = spec_launch(p, pl.spec_w, st);
   BatchParams pm = p;
   if (spectral) pm.only_marked = 1;
-#define p pm
-  if (use_dir256) {
-    if (e256 <= 2) BATCH_LAUNCH_DIRECT(256, 2); else if (e256 <= 4) BATCH_LAUNCH_DIRECT(256, 4); else if (e256 <= 6) BATCH_LAUNCH_DIRECT(256, 6); else if (e256 <= 8) BATCH_LAUNCH_DIRECT(256, 8); else BATCH_LAUNCH_DIRECT(256, 16);
-  } else if (use_dir) {
-    if (e64 <= 8) BATCH_LAUNCH_DIRECT(64, 8); else if (e64 <= 16) BATCH_LAUNCH_DIRECT(64, 16); else BATCH_LAUNCH_DIRECT(64, 24);
-  } else if (use64) {
-    if (e64 <= 8) BATCH_LAUNCH(64, 8, lds_reg); else if (e64 <= 16) BATCH_LAUNCH(64, 16, lds_reg); else BATCH_LAUNCH(64, 24, lds_reg);
-  } else if (use256) {
-    if (e256 <= 2) BATCH_LAUNCH(256, 2, lds_reg); else if (e256 <= 4) BATCH_LAUNCH(256, 4, lds_reg); else BATCH_LAUNCH(256, 8, lds_reg);
-  } else if (lds_gen) {
-    BATCH_LAUNCH(256, 0, lds_gen);
-  } else {
-    return OSQP_FUNC_NOT_IMPLEMENTED;
+  auto launch = [&](BatchKernel k) {
+    if (pl.direct && !reserve_lds(k, pl.lds)) throw DeviceError("osqp_hip: cannot reserve LDS for the direct batch kernel");
+    hipLaunchKernelGGL(k, dim3(p.nbatch), dim3(pl.tb), pl.lds, st, pm);
+  };
+  switch (pl.variant) {
+    case 2:
+      with_const<2, 4, 6, 8, 16>(pl.e, [&](auto E) { with_bool(pl.pol, [&](auto POL) { with_bool(pl.small, [&](auto SMALL) {
+        launch(&k_batch_admm<256, decltype(E)::value, decltype(E)::value, true, decltype(POL)::value, decltype(SMALL)::value>); }); }); });
+      break;
+    case 1:
+      with_const<8, 16, 24>(pl.e, [&](auto E) { with_bool(pl.pol, [&](auto POL) { launch(&k_batch_admm<64, decltype(E)::value, decltype(E)::value, true, decltype(POL)::value, false>); }); });
+      break;
+    case 3: with_const<8, 16, 24>(pl.e, [&](auto E) { launch(&k_batch_admm<64, decltype(E)::value, decltype(E)::value, false>); }); break;
+    case 4: with_const<2, 4, 8>(pl.e, [&](auto E) { launch(&k_batch_admm<256, decltype(E)::value, decltype(E)::value, false>); }); break;
+    case 5: launch(&k_batch_admm<256, 0, 0, false>); break;
+    default: return OSQP_FUNC_NOT_IMPLEMENTED;
   }
-#undef p
-#undef BATCH_LAUNCH
-#undef BATCH_LAUNCH_DIRECT
-#undef BATCH_LAUNCH_DIRECT_P
-#undef BATCH_LAUNCH_DIRECT_N
   hipError_t e = stream ? hipGetLastError() : hipStreamSynchronize(st);
   if (e != hipSuccess) throw DeviceError(std::string("osqp_hip: batch kernel failed: ") + hipGetErrorString(e));
   return OSQP_NO_ERROR;

@@ -10,7 +10,15 @@
 namespace osqp_hip {
 
 // ------------------------------------------------------------------------------------------------ policy
-// include/osqp_hip.h OSQPHipPolicy.  The ONLY place of the library that reads the environment is policy_from_env().
+// include/osqp_hip.h OSQPHipPolicy.  The ONLY place of the library that reads the environment is policy_from_env(), and batch_env() below
+// for the batch path's A/B knobs that have no policy field.
+const BatchEnv &batch_env() {
+  static const BatchEnv e = [] {                 // (once per process)
+    auto num = [](const char *name, int dflt) { const char *v = std::getenv(name); return v ? std::atoi(v) : dflt; };
+    return BatchEnv{num("OSQP_HIP_WAVE_SPLIT", -1), num("OSQP_HIP_WAVE_CUS", -1), num("OSQP_HIP_BATCH_WIDE_ROUNDS", 1 << 20)};
+  }();
+  return e;
+}
 namespace {
 thread_local OSQPHipPolicy g_default_policy;
 thread_local bool g_default_policy_set = false;

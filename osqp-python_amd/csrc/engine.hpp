@@ -132,7 +132,9 @@ class Engine {
   void prepare_batch_wave();
   void free_batch_wave();
   void attach_batch_wave(BatchParams &p, int nbatch);
-  int batch_wave_last_ = -1;            // OSQPHipStats::batch_wave_split
+  int batch_wave_last_ = -1;            // OSQPHipStats::batch_wave_split (set by launch_batch from what ran)
+  void reserve_batch_order(int nbatch);
+  int launch_batch(BatchParams &p, int nbatch, const double *Px, const double *Ax, void *stream, bool wait_solver);
   // Spectral form of the batch path's direct solve (batch_hip.hip, SPEC): every problem of a batch shares P, A and the constraint classes, and
   // rho enters K only through ONE scalar -- K(rho) = K_ref + (rho - rho_ref) M1, M1 = A' W A (W: 1 on inequality rows, the equality weight on
   // equality rows).  With K_ref = L L', L^-1 M1 L^-T = Q Lambda Q' and V = L^-T Q:  K(rho)^-1 = V diag(1 / (1 + (rho - rho_ref) lambda)) V'.

@@ -346,12 +346,11 @@ void Engine::attach_batch_wave(BatchParams &p, int nbatch) {
   p.wv_tend[0] = bwv_.tend[0]; p.wv_tend[1] = bwv_.tend[1];
   // the longest-expected problems to the workgroup kernel (be::batch_solve applies it when there is a launch order): wv_cus CUs are left free for it
   // and take wv_split problems, several each, one after the other
-  static const int env_split = std::getenv("OSQP_HIP_WAVE_SPLIT") ? std::atoi(std::getenv("OSQP_HIP_WAVE_SPLIT")) : -1;
-  static const int env_cus = std::getenv("OSQP_HIP_WAVE_CUS") ? std::atoi(std::getenv("OSQP_HIP_WAVE_CUS")) : -1;
   // (tools/batch_size_sweep.py under OSQP_HIP_WAVE_SPLIT / OSQP_HIP_WAVE_CUS, MPC batch: 2048 QPs 2.21 ms with 32 / 32, 2.84 with 64 / 16; 4096 QPs 3.26 ms
   //  with 48 / 16, 3.41 with 32 / 32; 8192 QPs 5.66 against 6.18 -- a large batch is bound by the wave kernel's throughput and wants its CUs back)
-  p.wv_cus = env_cus >= 0 ? env_cus : (nbatch < 3072 ? 32 : 16);
-  p.wv_split = env_split >= 0 ? env_split : (nbatch < 3072 ? 32 : 48);
+  const BatchEnv &env = batch_env();
+  p.wv_cus = env.wave_cus >= 0 ? env.wave_cus : (nbatch < 3072 ? 32 : 16);
+  p.wv_split = env.wave_split >= 0 ? env.wave_split : (nbatch < 3072 ? 32 : 48);
   p.wv_Aidx = bwv_.Aidx; p.wv_Acol = bwv_.Acol; p.wv_Tidx = bwv_.Tidx; p.wv_Tcol = bwv_.Tcol; p.wv_row = bwv_.row; p.wv_queue = bwv_.queue;
 }
 
@@ -610,7 +609,7 @@ void Engine::fill_batch_params(BatchParams &p, int nbatch, int warm) {
   p.cg_max = settings.cg_max_iter; p.unscaled = settings.scaling && !settings.scaled_termination; p.scaling = settings.scaling;
   p.precond = settings.cg_precond == OSQP_DIAGONAL_PRECONDITIONER; p.rho_is_vec = settings.rho_is_vec; p.warm = warm;
   p.polish = settings.polishing; p.refine = settings.polish_refine_iter; p.delta = settings.delta;      // (honoured by the direct variants)
-  p.variant = pol_.batch_variant;
+  p.variant = pol_.batch_variant; p.wide_rounds = batch_env().wide_rounds;
 }
 
 void Engine::attach_batch_direct(BatchParams &p, bool spectral) {
@@ -747,6 +746,34 @@ int Engine::attach_batch_matrices(BatchParams &p, const double *Px_dev, const do
   return be::batch_prepare(d_, p, Px_dev, Ax_dev, settings.scaling, stream);
 }
 
+// The launch-order buffer holds at least nbatch positions (growing it drops the device path's iteration counts as well)
+void Engine::reserve_batch_order(int nbatch) {
+  if ((size_t)nbatch <= batch_order_cap_) return;
+  if (d_batch_order_) be::dfree(d_, d_batch_order_);
+  if (d_batch_iters_) { be::dfree(d_, d_batch_iters_); d_batch_iters_ = nullptr; }
+  d_batch_order_ = dev_vec<int>(d_, nbatch); batch_order_cap_ = nbatch; d_batch_iters_n_ = 0;
+}
+
+// The common tail of batch_solve and batch_solve_device, in this order:
+//   1. on the solver's stream: the direct form's symbolic data, the refresh of its products (A's values may have changed since the last call), the
+//      direct / spectral / wave forms attached to p;
+//   2. wait_solver: the device path waits for the solver's stream here (its launches go on the caller's stream; the host path's uploads were waited for);
+//   3. on `stream` (nullptr: the solver's): the per-problem matrices (be::batch_prepare), then be::batch_solve -- synchronous for nullptr.
+// OSQPHipStats::batch_wave_split reports what be::batch_solve launched.
+int Engine::launch_batch(BatchParams &p, int nbatch, const double *Px, const double *Ax, void *stream, bool wait_solver) {
+  prepare_batch_direct();
+  if (bd_.ok) {
+    be::batch_products(d_, bd_.nprod, bd_.kp_a, bd_.kp_b, bd_.kp_val);
+    attach_batch_direct(p, nbatch >= kBatchSpectralMin && !Px && !Ax);
+    if (!Px && !Ax) attach_batch_wave(p, nbatch);
+  }
+  if (wait_solver) be::sync(d_);
+  int err = (Px || Ax) ? attach_batch_matrices(p, Px, Ax, stream) : OSQP_NO_ERROR;
+  if (!err) err = be::batch_solve(d_, p, stream);
+  batch_wave_last_ = err ? -1 : d_.batch_wave_ran;
+  return err;
+}
+
 int Engine::batch_solve(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, double *zs_dev, const double *Px, const double *Ax) {
   if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   if (nbatch <= 0 || !x || !y || !rec) return OSQP_DATA_VALIDATION_ERROR;
@@ -787,24 +814,12 @@ int Engine::batch_solve(int nbatch, const double *q, const double *l, const doub
   // 4096 MPC QPs 13.3 -> 11 ms).  Scheduling only: every problem is solved by its own workgroup exactly as before.
   const bool reorder = pol_.batch_reorder != 0;
   if (reorder && nbatch > 1 && (int)batch_order_.size() == nbatch) {
-    if ((size_t)nbatch > batch_order_cap_) {
-      if (d_batch_order_) be::dfree(d_, d_batch_order_);
-      if (d_batch_iters_) { be::dfree(d_, d_batch_iters_); d_batch_iters_ = nullptr; d_batch_iters_n_ = 0; }
-      d_batch_order_ = dev_vec<int>(d_, nbatch); batch_order_cap_ = nbatch;
-    }
+    reserve_batch_order(nbatch);
     be::h2d(d_, d_batch_order_, batch_order_.data(), sizeof(int) * nbatch);
     p.order = d_batch_order_;
   }
   d_batch_iters_n_ = 0;                            // (the device-pointer path's history does not describe this call)
-  prepare_batch_direct();
-  if (bd_.ok) {
-    be::batch_products(d_, bd_.nprod, bd_.kp_a, bd_.kp_b, bd_.kp_val);             // A's values may have changed since the last call
-    attach_batch_direct(p, nbatch >= kBatchSpectralMin && !Px && !Ax);
-    if (!Px && !Ax) attach_batch_wave(p, nbatch);
-    batch_wave_last_ = p.wv_on ? ((p.order && p.wv_cus > 0 && nbatch >= 8 * p.wv_split) ? p.wv_split : 0) : -1;
-  }
-  if (Px || Ax) { const int e2 = attach_batch_matrices(p, Px ? dPx : nullptr, Ax ? dAx : nullptr, nullptr); if (e2) return e2; }
-  int err = be::batch_solve(d_, p);
+  const int err = launch_batch(p, nbatch, Px ? dPx : nullptr, Ax ? dAx : nullptr, nullptr, false);
   tph[3] = now_s();
   if (!err) {
     be::d2h(d_, x, dx, sizeof(double) * N); be::d2h(d_, y, dy, sizeof(double) * M); be::d2h(d_, rec, drec, sizeof(double) * kBatchRec * nbatch);
@@ -841,11 +856,7 @@ int Engine::batch_solve_device(int nbatch, const double *q, const double *l, con
   // the previous call's counts into this call's order (both on the caller's stream: ordered with the batch kernels themselves)
   const bool reorder = pol_.batch_reorder != 0;
   if (reorder && nbatch > 1) {
-    if ((size_t)nbatch > batch_order_cap_) {           // (both buffers have the same capacity)
-      if (d_batch_order_) be::dfree(d_, d_batch_order_);
-      if (d_batch_iters_) be::dfree(d_, d_batch_iters_);
-      d_batch_order_ = dev_vec<int>(d_, nbatch); d_batch_iters_ = nullptr; batch_order_cap_ = nbatch; d_batch_iters_n_ = 0;
-    }
+    reserve_batch_order(nbatch);                     // (both buffers have the same capacity)
     if (!d_batch_iters_) { d_batch_iters_ = dev_vec<int>(d_, batch_order_cap_); d_batch_iters_n_ = 0; }
     be::sync(d_);                                    // (allocations / zero fills ran on the solver's stream)
     if (d_batch_iters_n_ == nbatch) { be::batch_order(d_, nbatch, d_batch_iters_, d_batch_order_, stream); p.order = d_batch_order_; }
@@ -853,16 +864,7 @@ int Engine::batch_solve_device(int nbatch, const double *q, const double *l, con
     d_batch_iters_n_ = nbatch;
     batch_order_.clear();                            // (the host path's order does not describe this call)
   }
-  prepare_batch_direct();
-  if (bd_.ok) {
-    be::batch_products(d_, bd_.nprod, bd_.kp_a, bd_.kp_b, bd_.kp_val);
-    attach_batch_direct(p, nbatch >= kBatchSpectralMin && !Px && !Ax);
-    if (!Px && !Ax) attach_batch_wave(p, nbatch);
-    batch_wave_last_ = p.wv_on ? ((p.order && p.wv_cus > 0 && nbatch >= 8 * p.wv_split) ? p.wv_split : 0) : -1;
-  }
-  be::sync(d_);                                   // the uploads and the product refresh ran on the solver's stream
-  if (Px || Ax) { const int e2 = attach_batch_matrices(p, Px, Ax, stream); if (e2) return e2; }      // (on the caller's stream, in front of the solve launch)
-  const int err = be::batch_solve(d_, p, stream);
+  const int err = launch_batch(p, nbatch, Px, Ax, stream, true);
   if (!err) be::ext_record(d_, stream);           // later calls that overwrite or free what this kernel reads wait for it (ext_wait)
   return err;
 }

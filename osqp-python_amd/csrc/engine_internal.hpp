@@ -17,6 +17,13 @@
 
 namespace osqp_hip {
 
+// The batch path's A/B knobs (engine.cpp; not OSQPHipPolicy fields: that layout is part of the C ABI).  -1: the engine's choice.
+struct BatchEnv {
+  int wave_split, wave_cus;     // OSQP_HIP_WAVE_SPLIT / OSQP_HIP_WAVE_CUS: BatchParams::wv_split / wv_cus
+  int wide_rounds;              // OSQP_HIP_BATCH_WIDE_ROUNDS: BatchParams::wide_rounds
+};
+const BatchEnv &batch_env();
+
 namespace {
 constexpr double kRhoMin = 1e-6, kRhoMax = 1e6, kRhoTol = 1e-4;   // _osqp.py:25-28 (RHO_EQ_OVER_RHO_INEQ = 1e3 is applied in the set_rho kernel)
 constexpr double kMinScaling = 1e-4, kMaxScaling = 1e4;                                 // _osqp.py:44-45

@@ -155,6 +155,7 @@ class OSQPSolver:
                 raise TypeError('q, l, u must be float64 numpy arrays')
         q, l, u = _vec(q), _vec(l), _vec(u)
         Ps, As = P._struct(), A._struct()
+        self.nnz_P, self.nnz_A = P.nzmax, A.nzmax          # widths of hip_batch_solve's Px / Ax (P as given: its upper triangle)
         status = self._lib.osqp_setup(C.byref(self._p), C.byref(Ps), _ptr(q, _lib.c_double_p), C.byref(As),
                                       _ptr(l, _lib.c_double_p), _ptr(u, _lib.c_double_p), self.m, self.n, C.byref(settings))
         if status:
@@ -292,14 +293,20 @@ class OSQPSolver:
         per-element P_val / A_val, nn/torch.py:128-157) -- still one launch.  Returns x (B, n), y (B, m), rec (B, BATCH_REC) with columns BATCH_FIELDS."""
         arrs = [a for a in (q, l, u, x0, y0, Px, Ax) if a is not None]
         B = int(nbatch) if nbatch is not None else int(np.asarray(arrs[0]).shape[0])
-        q, l, u = (None if a is None else np.ascontiguousarray(a, dtype=np.float64).reshape(B, -1) for a in (q, l, u))
+
+        def rows(a, name, width):                   # (B, width) float64, C order: the C side reads exactly B * width entries
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.size != B * width or (a.ndim > 1 and a.shape[-1] != width):
+                raise ValueError('%s: expected %d problems of width %d, got shape %s' % (name, B, width, a.shape))
+            return a.reshape(B, width)
+        q, l, u = (None if a is None else rows(a, name, w) for a, name, w in ((q, 'q', self.n), (l, 'l', self.m), (u, 'u', self.m)))
         warm = x0 is not None or y0 is not None      # a missing one starts from zero, like warm_start(x=None) / (y=None) of a single solver
         # (l, u are clamped to +-OSQP_INFTY inside the kernel, like interface.py:334-337)
-        x = np.zeros((B, self.n)) if x0 is None else np.ascontiguousarray(x0, dtype=np.float64).reshape(B, self.n).copy()
-        y = np.zeros((B, self.m)) if y0 is None else np.ascontiguousarray(y0, dtype=np.float64).reshape(B, self.m).copy()
+        x = np.zeros((B, self.n)) if x0 is None else rows(x0, 'x0', self.n).copy()
+        y = np.zeros((B, self.m)) if y0 is None else rows(y0, 'y0', self.m).copy()
         rec = np.zeros((B, self.BATCH_REC))
         if Px is not None or Ax is not None:
-            Px, Ax = (None if a is None else np.ascontiguousarray(a, dtype=np.float64).reshape(B, -1) for a in (Px, Ax))
+            Px, Ax = (None if a is None else rows(a, name, w) for a, name, w in ((Px, 'Px', self.nnz_P), (Ax, 'Ax', self.nnz_A)))
             st = self._lib.osqp_hip_batch_solve_mat(self._p, B, _ptr(Px, _lib.c_double_p), _ptr(Ax, _lib.c_double_p), _ptr(q, _lib.c_double_p), _ptr(l, _lib.c_double_p),
                                                     _ptr(u, _lib.c_double_p), _ptr(x, _lib.c_double_p), _ptr(y, _lib.c_double_p), _ptr(rec, _lib.c_double_p), int(warm))
             if st:

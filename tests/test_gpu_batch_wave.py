@@ -142,14 +142,15 @@ def test_wave_is_the_default_for_large_batches():
     assert (rd[:, 0] == 1).all() and np.array_equal(xd, xw) and np.array_equal(yd, yw) and np.array_equal(rd[:, :7], rw[:, :7])
 
 
-@pytest.mark.parametrize('shape', ['random30', 'banded60', 'mpc_small'])
+@pytest.mark.parametrize('shape', ['random30', 'banded60', 'mpc_n60'])
 def test_wave_on_other_patterns(shape):
     """other sizes and sparsity patterns than the MPC batch: n far below the padded size of the LDS copy of V, fewer rows than lane slots, rows of A of
     mixed lengths (the ELL groups), per-problem q -- against the workgroup kernel and the oracle"""
     B = 48
     rng = np.random.default_rng(11)
-    if shape == 'mpc_small':
-        P, q, A, L, U = problems.mpc_batch(B, nx=3, nu=2, N=4)
+    if shape == 'mpc_n60':
+        # (n = 60 under the n8 = 64 copy of V; nx = 3, nu = 2, N = 4 is too small for the spectral form: test_wave_stat_reports_what_ran)
+        P, q, A, L, U = problems.mpc_batch(B, nx=8, nu=4, N=5)
         Q = np.repeat(q[None, :], B, axis=0)
     else:
         P, q, A, l, u = problems.random_qp(30, 50, density=0.15, seed=5) if shape == 'random30' else problems.banded_qp(60, window=8, seed=5)
@@ -171,3 +172,19 @@ def test_wave_on_other_patterns(shape):
         # (the kernels' common trajectory may pass a termination check the oracle's misses by rounding, or the other way round: one check interval apart)
         assert io.status_val == SOLVED and abs(int(rw[i, 1]) - io.iter) <= 25, (i, rw[i, 1], io.iter)
         assert np.abs(xw[i] - xo).max() <= 1e-4 * (1 + np.abs(xo).max()) and abs(rw[i, 2] - io.obj_val) <= 1e-5 * (1 + abs(io.obj_val))
+
+
+def test_wave_stat_reports_what_ran():
+    """a pattern whose products are too few for the spectral form's scratch (batch_hip.hip: prod_len < 4 (kBatchSpecN + 2)): batch_wave = 1 attaches the
+    wave form, but the batch runs on the banded kernel alone -- OSQPHipStats::batch_wave_split says so, with and without a launch order, and the results
+    are those of batch_wave = -1"""
+    B = 48
+    P, q, A, L, U = problems.mpc_batch(B, nx=3, nu=2, N=4)
+    sw, ss = _solver(P, q, A, L[0], U[0], wave=1), _solver(P, q, A, L[0], U[0], wave=-1)
+    xw, yw, rw = sw._solver.hip_batch_solve(l=L, u=U)
+    assert sw._solver.hip_stats()['batch_wave_split'] == -1
+    sw._solver.hip_batch_solve(l=L, u=U)                               # (launch order from the first call)
+    assert sw._solver.hip_stats()['batch_wave_split'] == -1
+    xs, ys, rs = ss._solver.hip_batch_solve(l=L, u=U)
+    assert ss._solver.hip_stats()['batch_wave_split'] == -1
+    assert (rw[:, 0] == 1).all() and np.array_equal(xw, xs) and np.array_equal(yw, ys) and np.array_equal(rw[:, :7], rs[:, :7])
