@@ -637,8 +637,8 @@ __device__ __forceinline__ double f1_segsum(const double *seg, int a, int z) {
 }
 // The scalar part of launch F_k.  The per-workgroup partials (gamma, delta, ||r||) are double-buffered by the parity of the LAUNCH, not of k:
 // a launch reads what the previous launch of the string wrote -- KB: gamma_0, ||r_0||, ||rhs|| (in delta's slot); F_k: gamma_k, delta_k, ||r_k|| --
-// so the three loads depend on nothing but the kernel's `par` argument and leave at the very head of the launch (f1_fold_issue), next to
-// the phase record instead of behind it.  f1_fold_finish returns false when the PCG had already converged (the caller runs KA in this launch).
+// so the three loads depend on nothing but the kernel's `par` and `part` arguments (f1_fold_issue): in k_slot1 they leave right behind the
+// one wait for the phase and block records.  f1_fold_finish returns false when the PCG had already converged (the caller runs KA in this launch).
 struct F1Fold { PartRegs a, b, c; };
 __device__ __forceinline__ F1Fold f1_fold_issue(const double *part, const int par, const int probe) {
   F1Fold f;
@@ -1327,26 +1327,37 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
 // Dev reaches this kernel through MEMORY, not as a by-value argument: the compiler lowers a by-value struct into loads of every used field at
 // the kernel's entry -- some sixty here -- and, short of scalar registers, spills each batch to vector lanes before it fetches the next: ten
 // dependent load-wait-spill rounds in front of the first request of every launch (measured: +2 us per launch against the probe kernel that
-// holds one phase).  From memory the fields are fetched where the phase that runs needs them; the head's own six values sit in front of the
-// copy as one 48-byte block.  be::dev_publish keeps the copy current (slot_begin / ctl_begin: once per chunk, never inside a capture).
-struct F1Head { const unsigned char *stream; const int *blk; const double *part; const int *slot; int nblk, pad; };
-struct F1DevBlock { F1Head h; Dev d; };
+// holds one phase).  From memory the fields are fetched where the phase that runs needs them.  be::dev_publish keeps the copy current
+// (slot_begin / ctl_begin: once per chunk, never inside a capture).
+// The head of the launch -- what the first requests are addressed from -- comes as separate SCALAR arguments, preloaded into user SGPRs
+// (-mllvm -amdgpu-kernarg-preload-count, Makefile; a by-value struct is not preloaded): the first block's stream leaves at the first
+// instructions, the slot record and the first block record behind it, both behind ONE wait, and the fold's partials right after that wait.
+// (With the head in memory: the argument, then the head, then the partials' phase record and Dev -- three round trips after the kernel
+// start's cache invalidation before the first request.)  Every value passed is fixed from setup on: the F1 plan's stream and records
+// (upload_f1), part and slot (setup), the device copy of Dev (allocated once per handle, kept current by dev_publish) -- and a new setup
+// drops the captured strings before it replaces any of them (Engine::setup).
+// (Tried: the fold's partials issued unconditionally at the head too, kept there with register pins in the other phases: the phase chain is
+//  structurized into one linear order, so the 24 partial registers stay live across the KB / KA bodies -- 121 -> 127 VGPRs and 12 - 44
+//  bytes of scratch per lane.  Left where the F phase uses them.)
+struct F1DevBlock { Dev d; };
 // (Per-block mixing, tried: the far lanes of the workgroup's first row block touching their lines at the head of the launch -- both parities, as LDS-direct
 //  loads into a scratch KB, so that the body's requests find them in this XCD's L2 instead of waiting for memory: the solve got SLOWER, 80 -> 95 ms on
 //  `bench.py --config mixed` (tools/mix_ab.py); the extra requests ahead of the fold's partials cost more than the late far lines do.)
 template <int D, bool MIX, bool WT>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_slot1(const F1DevBlock *__restrict__ blk, int par) {
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_slot1(const unsigned char *__restrict__ stream, const int *__restrict__ fblk, int nblk, int par,
+                                                                                             const double *__restrict__ part, const int *__restrict__ slot, const F1DevBlock *__restrict__ blk) {
   __shared__ F1Lds lds;
   __shared__ F1Stream sbuf;
   static_assert(sizeof(F1Lds) + sizeof(F1Stream) <= 160 * 1024 / 4, "four workgroups per CU");
-  const F1Head h = blk->h;
   const Dev &d = blk->d;
-  const int *R = h.slot + (par ? SR_WORDS : 0);
-  int *W = gptr(d.slot) + (par ? 0 : SR_WORDS);
+  const int *R = slot + (par ? SR_WORDS : 0);
+  // the other record of the pair, derived from R: `slot` and `par` are not both held to the end of the launch (SGPR spills of <4,false,true>
+  // 72 -> 71).  (Taken from Dev::slot instead, the compiler hoisted the fetch to the entry and waited for it before the first stream request.)
+  int *W = const_cast<int *>(R) + (par ? -SR_WORDS : SR_WORDS);
   // every phase but the idle one consumes the first block's stream: requested before anything else has arrived
-  f1_stream_first<!WT>(h.stream, h.nblk, sbuf);
-  const F1Fold fold = f1_fold_issue(gptr(h.part), par, 0);    // the previous launch's partials: their address depends on `par` alone
-  const F1Rec rec0 = f1_first_record(h.blk, h.nblk);
+  f1_stream_first<!WT>(stream, nblk, sbuf);
+  const F1Fold fold = f1_fold_issue(gptr(part), par, 0);      // the previous launch's partials: their address depends on `par` alone
+  const F1Rec rec0 = f1_first_record(fblk, nblk);
   SlotState st = slot_read_scalar(R);
   if (st.ph == P_KB) {
     if (st.admm >= st.target) { st.ph = P_IDLE; f1_stream_wait(); slot_write(W, st); return; }
@@ -1533,7 +1544,6 @@ void dev_publish(Dev &d) {
   }
   F1DevBlock nb;
   std::memset(static_cast<void *>(&nb), 0, sizeof(nb));
-  nb.h = F1Head{d.f1.stream, d.f1.blk, d.part, d.slot, d.A.nblk, 0};
   std::memcpy(static_cast<void *>(&nb.d), static_cast<const void *>(&d), sizeof(Dev));
   if (std::memcmp(&nb, p.shadow_block, sizeof(nb)) == 0) return;
   // (the pinned staging block may still be the source of an upload in flight: drain the stream before rewriting it -- rare: a setting changed)
@@ -1567,8 +1577,8 @@ void slot_pair(Dev &d) {
     const F1DevBlock *db = static_cast<const F1DevBlock *>(im(d).dev_block);      // (current as of the chunk's slot_begin / ctl_begin: dev_publish)
     f1_dispatch(d, [&](auto Dc, auto Mc, auto Wc) {
       constexpr int DD = decltype(Dc)::value; constexpr bool MM = decltype(Mc)::value, WW = decltype(Wc)::value;
-      hipLaunchKernelGGL((k_slot1<DD, MM, WW>), dim3(kGrid), dim3(kBlock), 0, st(d), db, 0);
-      hipLaunchKernelGGL((k_slot1<DD, MM, WW>), dim3(kGrid), dim3(kBlock), 0, st(d), db, 1);
+      hipLaunchKernelGGL((k_slot1<DD, MM, WW>), dim3(kGrid), dim3(kBlock), 0, st(d), static_cast<const unsigned char *>(d.f1.stream), static_cast<const int *>(d.f1.blk), d.A.nblk, 0, static_cast<const double *>(d.part), static_cast<const int *>(d.slot), db);
+      hipLaunchKernelGGL((k_slot1<DD, MM, WW>), dim3(kGrid), dim3(kBlock), 0, st(d), static_cast<const unsigned char *>(d.f1.stream), static_cast<const int *>(d.f1.blk), d.A.nblk, 1, static_cast<const double *>(d.part), static_cast<const int *>(d.slot), db);
     });
   }
   else if (d.kf.on) { LAUNCH(k_slotk, d, d, 0); LAUNCH(k_slotk, d, d, 1); }
