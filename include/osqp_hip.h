@@ -162,7 +162,13 @@ OSQPInt osqp_update_settings(OSQPSolver *solver, const OSQPSettings *new_setting
 OSQPInt osqp_update_rho(OSQPSolver *solver, OSQPFloat rho_new);         /* bindings.cpp.in:213 */
 void    osqp_get_dimensions(OSQPSolver *solver, OSQPInt *m, OSQPInt *n);   /* codegen/pywrapper/bindings.cpp.jinja:21 */
 
-/* Out of scope (derivatives / codegen): present so the reference binding links; return OSQP_FUNC_NOT_IMPLEMENTED. */
+/* Adjoint derivatives of the last solution (bindings.cpp.in:283-319), for a problem that fits the batch kernel's direct variant (see osqp_hip_batch_solve
+   below); a larger problem -- the PCG path -- returns OSQP_FUNC_NOT_IMPLEMENTED.  compute: needs a previous osqp_solve that ended OSQP_SOLVED on the
+   current data (OSQP_DATA_NOT_INITIALIZED otherwise: every data update resets the status); dx (n) = dL/dx, dy (m) = dL/dy, either may be NULL (zero).
+   It runs the adjoint kernel (osqp_hip_batch_adjoint) with a batch of one and keeps the result in the handle.  get_mat: fills the x arrays of the
+   caller's CSC structs, which carry the patterns of P's upper triangle and of A as given at setup (interface.py:558-564); get_vec: dq (n), dl, du (m).
+   Both return OSQP_DATA_NOT_INITIALIZED before a successful compute.  An argument may be NULL (skipped).
+   Codegen is out of scope: present so the reference binding links; returns OSQP_FUNC_NOT_IMPLEMENTED. */
 OSQPInt osqp_adjoint_derivative_compute(OSQPSolver *solver, OSQPFloat *dx, OSQPFloat *dy);            /* :302 */
 OSQPInt osqp_adjoint_derivative_get_mat(OSQPSolver *solver, OSQPCscMatrix *dP, OSQPCscMatrix *dA);    /* :310 */
 OSQPInt osqp_adjoint_derivative_get_vec(OSQPSolver *solver, OSQPFloat *dq, OSQPFloat *dl, OSQPFloat *du);   /* :318 */
@@ -272,6 +278,39 @@ OSQPInt osqp_hip_batch_solve_mat(OSQPSolver *solver, OSQPInt nbatch, const OSQPF
 OSQPInt osqp_hip_batch_solve_mat_device(OSQPSolver *solver, OSQPInt nbatch, const OSQPFloat *Px_dev, const OSQPFloat *Ax_dev, const OSQPFloat *q_dev,
                                         const OSQPFloat *l_dev, const OSQPFloat *u_dev, OSQPFloat *x_dev, OSQPFloat *y_dev, OSQPFloat *rec_dev,
                                         OSQPInt warm_start, void *stream);
+
+/* ADJOINT DERIVATIVES of a batch of solved QPs -- the backward pass of osqp_hip_batch_solve[_mat]: ONE launch, one workgroup per problem
+ * (batch_hip.hip k_batch_adjoint).  For problem b with solution x (n), y (m) and incoming gradients dx = dL/dx (n), dy = dL/dy (m; NULL = 0):
+ *   active rows by polish's rule on z = A x (lower-active: z_i - l_i < -y_i; else upper-active: u_i - z_i < y_i; l_i == u_i: always active, lower if y_i < 0),
+ *   [P, A_a'; A_a, 0] [r_x; r_a] = -[dx; dy_a]  (A_a: the active rows), r_y = r_a on active rows and 0 elsewhere,
+ *   dq = r_x;  dl_i = -r_y,i on lower-active rows, du_i = -r_y,i on upper-active rows, 0 elsewhere;
+ *   dP_ij = (r_x,i x_j + r_x,j x_i) / 2 at every stored entry of P (upper triangle, the CSC order given at setup; the diagonal is r_x,i x_i);
+ *   dA_ij = y_i r_x,j + r_y,i x_j at every stored entry of A (CSC order).
+ * The system is solved as polish solves its own: the banded LDL' of P + delta I + A_a' A_a / delta in LDS (`delta` setting, in the caller's unscaled
+ * units: the kernel works on the unscaled matrices), the first solve and `polish_refine_iter` refinement steps against the unregularised residual.
+ * Px / Ax: nbatch x nnz per-problem values as for osqp_hip_batch_solve_mat, l / u: nbatch x m; NULL = this solver's own values for every problem.
+ * x, dx: nbatch x n; y, dy: nbatch x m.  Outputs dP: nbatch x nnz(P), dq: nbatch x n, dA: nbatch x nnz(A), dl, du: nbatch x m, arec: nbatch x
+ * OSQP_HIP_ADJOINT_REC doubles {status, active rows, final residual max |g - K r| / max |g| of the unregularised system, reserved}; any output may be
+ * NULL (skipped).  status 0: residual < OSQP_HIP_ADJOINT_TOL; 1: a pivot of the factorisation was not positive; 2: more active rows than variables
+ * (the system is singular); 3: the refinement stalled above the threshold (dependent active rows).  The outputs of an element with a nonzero status are
+ * still written: they are the regularised solution.  (q does not enter the derivative.)
+ * Returns OSQP_FUNC_NOT_IMPLEMENTED unless the banded factor exists for the problem (permuted half bandwidth <= 56, as for the forward's direct variant) and
+ * the kernel's own LDS fits (both matrices' values + 7n + 6m doubles + the band <= 144 KB), for a problem the batch path takes at all (10n + 8m doubles
+ * <= 64 KB, a handle that does not work on a reordered copy: the conditions of osqp_hip_batch_solve).  The forward's limit of 4096 stored entries per matrix does not
+ * apply: a problem may be differentiated here whose forward ran on another variant.
+ * _device: every array in device memory, asynchronous on `stream` with the semantics of osqp_hip_batch_solve_device (like that call it first waits, on the
+ * host, for the solver's OWN stream -- pending data updates of the handle -- never for `stream`); nbatch == 0 only answers whether the problem fits. */
+#define OSQP_HIP_ADJOINT_REC 4
+#define OSQP_HIP_ADJOINT_TOL 1e-6
+OSQPInt osqp_hip_batch_adjoint(OSQPSolver *solver, OSQPInt nbatch, const OSQPFloat *Px, const OSQPFloat *Ax, const OSQPFloat *l, const OSQPFloat *u,
+                               const OSQPFloat *x, const OSQPFloat *y, const OSQPFloat *dx, const OSQPFloat *dy, OSQPFloat *dP, OSQPFloat *dq,
+                               OSQPFloat *dA, OSQPFloat *dl, OSQPFloat *du, OSQPFloat *arec);
+OSQPInt osqp_hip_batch_adjoint_device(OSQPSolver *solver, OSQPInt nbatch, const OSQPFloat *Px_dev, const OSQPFloat *Ax_dev, const OSQPFloat *l_dev,
+                                      const OSQPFloat *u_dev, const OSQPFloat *x_dev, const OSQPFloat *y_dev, const OSQPFloat *dx_dev,
+                                      const OSQPFloat *dy_dev, OSQPFloat *dP_dev, OSQPFloat *dq_dev, OSQPFloat *dA_dev, OSQPFloat *dl_dev,
+                                      OSQPFloat *du_dev, OSQPFloat *arec_dev, void *stream);
+/* osqp_capabilities() reports what the reference's binding asks about and stays as it is; this adds OSQP_CAPABILITY_DERIVATIVES (the adjoint above). */
+OSQPInt osqp_hip_capabilities(void);
 
 /* Parametric re-solve with the new data ALREADY ON THE GPU (the reference's update(q, l, u) + solve() loop,
  * src/osqp/nn/torch.py:136-140, /root/reference/src/osqppurepy/_osqp.py:1312-1367 and :1493-1545 restated as kernels):

@@ -31,6 +31,7 @@ OSQPInt osqp_hip_set_print(OSQPSolver *s, osqp_hip_print_fn fn, void *user) { re
 const char *osqp_hip_backend(void) { return osqp_hip::be::name(); }
 
 OSQPInt osqp_capabilities(void) { return OSQP_CAPABILITY_INDIRECT_SOLVER | OSQP_CAPABILITY_UPDATE_MATRICES; }
+OSQPInt osqp_hip_capabilities(void) { return osqp_capabilities() | OSQP_CAPABILITY_DERIVATIVES; }
 
 // Defaults: values of the v1.0.0 C core as recalled in SURVEY.md Appendix C [UPSTREAM-UNVERIFIED]; the reference's
 // tests pass the settings that matter explicitly (basic_test.py:20-31).  linsys_solver defaults to the only solver
@@ -76,9 +77,9 @@ OSQPInt osqp_update_settings(OSQPSolver *s, const OSQPSettings *ns) { return gua
 OSQPInt osqp_update_rho(OSQPSolver *s, OSQPFloat rho) { return guarded(s, [&](Engine &e) { return e.update_rho(rho); }); }
 void osqp_get_dimensions(OSQPSolver *s, OSQPInt *m, OSQPInt *n) { Engine *e = eng(s); if (e) { if (m) *m = e->m; if (n) *n = e->n; } }
 
-OSQPInt osqp_adjoint_derivative_compute(OSQPSolver *, OSQPFloat *, OSQPFloat *) { return OSQP_FUNC_NOT_IMPLEMENTED; }
-OSQPInt osqp_adjoint_derivative_get_mat(OSQPSolver *, OSQPCscMatrix *, OSQPCscMatrix *) { return OSQP_FUNC_NOT_IMPLEMENTED; }
-OSQPInt osqp_adjoint_derivative_get_vec(OSQPSolver *, OSQPFloat *, OSQPFloat *, OSQPFloat *) { return OSQP_FUNC_NOT_IMPLEMENTED; }
+OSQPInt osqp_adjoint_derivative_compute(OSQPSolver *s, OSQPFloat *dx, OSQPFloat *dy) { return guarded(s, [&](Engine &e) { return e.adjoint_compute(dx, dy); }); }
+OSQPInt osqp_adjoint_derivative_get_mat(OSQPSolver *s, OSQPCscMatrix *dP, OSQPCscMatrix *dA) { return guarded(s, [&](Engine &e) { return e.adjoint_get_mat(dP, dA); }); }
+OSQPInt osqp_adjoint_derivative_get_vec(OSQPSolver *s, OSQPFloat *dq, OSQPFloat *dl, OSQPFloat *du) { return guarded(s, [&](Engine &e) { return e.adjoint_get_vec(dq, dl, du); }); }
 OSQPInt osqp_codegen(OSQPSolver *, const char *, const char *, OSQPCodegenDefines *) { return OSQP_FUNC_NOT_IMPLEMENTED; }
 void osqp_set_default_codegen_defines(OSQPCodegenDefines *d) {
   if (!d) return;
@@ -105,6 +106,14 @@ OSQPInt osqp_hip_batch_solve_mat_device(OSQPSolver *s, OSQPInt nbatch, const OSQ
 }
 OSQPInt osqp_hip_batch_solve_device(OSQPSolver *s, OSQPInt nbatch, const OSQPFloat *q, const OSQPFloat *l, const OSQPFloat *u, OSQPFloat *x, OSQPFloat *y, OSQPFloat *rec, OSQPInt warm, void *stream) {
   return guarded(s, [&](Engine &e) { return e.batch_solve_device(nbatch, q, l, u, x, y, rec, warm, stream); });
+}
+OSQPInt osqp_hip_batch_adjoint(OSQPSolver *s, OSQPInt nbatch, const OSQPFloat *Px, const OSQPFloat *Ax, const OSQPFloat *l, const OSQPFloat *u, const OSQPFloat *x, const OSQPFloat *y,
+                               const OSQPFloat *dx, const OSQPFloat *dy, OSQPFloat *dP, OSQPFloat *dq, OSQPFloat *dA, OSQPFloat *dl, OSQPFloat *du, OSQPFloat *arec) {
+  return guarded(s, [&](Engine &e) { return e.batch_adjoint(nbatch, Px, Ax, l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec); });
+}
+OSQPInt osqp_hip_batch_adjoint_device(OSQPSolver *s, OSQPInt nbatch, const OSQPFloat *Px, const OSQPFloat *Ax, const OSQPFloat *l, const OSQPFloat *u, const OSQPFloat *x, const OSQPFloat *y,
+                                      const OSQPFloat *dx, const OSQPFloat *dy, OSQPFloat *dP, OSQPFloat *dq, OSQPFloat *dA, OSQPFloat *dl, OSQPFloat *du, OSQPFloat *arec, void *stream) {
+  return guarded(s, [&](Engine &e) { return e.batch_adjoint_device(nbatch, Px, Ax, l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec, stream); });
 }
 OSQPInt osqp_hip_update_data_vec_device(OSQPSolver *s, const OSQPFloat *q, const OSQPFloat *l, const OSQPFloat *u, void *stream) {
   return guarded(s, [&](Engine &e) { return e.update_data_vec_device(q, l, u, stream); });

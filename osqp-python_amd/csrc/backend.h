@@ -422,8 +422,38 @@ struct BatchPlan {
 };
 BatchPlan plan_batch(const BatchParams &p, int cus);        // cus: compute units of the device
 
+// Adjoint derivatives of a batch of solved QPs (batch_hip.hip k_batch_adjoint; include/osqp_hip.h osqp_hip_batch_adjoint): one workgroup per problem.
+// The kernel works on the caller's UNSCALED matrices -- the resident raw values Dev::Praw / Dev::Araw, or the caller's own per-problem values --
+// so that every result is in the caller's units; what it shares with the forward's direct variant is the symbolic data of the banded factor
+// (Engine::prepare_batch_direct: permutation, band slots, products).
+constexpr int kAdjointRec = 4;          // doubles per problem in the adjoint record (OSQP_HIP_ADJOINT_REC): status, active rows, relative residual, reserved
+constexpr double kAdjointTol = 1e-6;    // status 0: final relative residual of the unregularised system below this (OSQP_HIP_ADJOINT_TOL)
+struct AdjointParams {
+  int n = 0, m = 0, nbatch = 0, nzP = 0, nzA = 0;
+  DevCsr A, B;                  // structure of A (CSR) and B = [P | A'] (CSR); their scaled values are not read
+  const double *Praw = nullptr, *Araw = nullptr;      // shared UNSCALED values in the caller's CSC order (P: upper triangle)
+  const double *Px_b = nullptr, *Ax_b = nullptr;      // per-problem values [nbatch][nzP] / [nbatch][nzA]; nullptr = the shared ones
+  const int *Pi = nullptr, *Pj = nullptr, *Pm1 = nullptr, *Pm2 = nullptr, *Ai = nullptr, *Aj = nullptr, *AmA = nullptr, *AmB = nullptr;   // Dev's assembly maps
+  const double *l = nullptr, *u = nullptr, *l0 = nullptr, *u0 = nullptr;      // [nbatch][m] or nullptr = the shared l0 / u0 [m]
+  const double *x = nullptr, *y = nullptr, *dx = nullptr, *dy = nullptr;      // [nbatch][n] / [nbatch][m]; dy == nullptr: zero
+  double *dP = nullptr, *dq = nullptr, *dA = nullptr, *dl = nullptr, *du = nullptr, *arec = nullptr;      // outputs, each optional
+  double delta = 1e-6; int refine = 3;
+  int bw = -1, nents = 0, ntri = 0;
+  const int *perm = nullptr, *bp_slot = nullptr, *ke_slot = nullptr, *ke_ptr = nullptr, *kp_row = nullptr, *kp_a = nullptr, *kp_b = nullptr, *tri = nullptr;
+};
+// LDS of k_batch_adjoint (bytes): both matrices' values, seven n-vectors, six m-vectors, the reduction scratch and the padded band; 0: does not fit
+inline size_t batch_adjoint_lds_bytes(int n, int m, int nzA, int nzB, int bw) {
+  if (bw < 0 || bw > kBatchDirectMaxBw) return 0;
+  const size_t n8 = (size_t)(n + kBatchNB - 1) / kBatchNB * kBatchNB;
+  const size_t b = sizeof(double) * ((size_t)((nzA + 1) & ~1) + (size_t)((nzB + 1) & ~1) + (size_t)7 * n + (size_t)6 * m + 16 + kBatchNB + n8 * (size_t)(bw + kBatchNB) + 64);
+  return b <= 144 * 1024 ? b : 0;
+}
+
 namespace be {
 
+// stream == nullptr: on d.stream, synchronous; otherwise enqueued on that hipStream_t and not waited for.  Weak: the host simulator of the CPU test
+// tier has no such kernel -- the driver answers OSQP_FUNC_NOT_IMPLEMENTED where the symbol is absent.
+int batch_adjoint(Dev &d, const AdjointParams &p, void *stream) __attribute__((weak));
 size_t batch_lds_bytes(int n, int m);                       // 0 if a problem does not fit one workgroup's LDS
 // stream == nullptr: on d.stream, synchronous.  Otherwise enqueued on that hipStream_t and NOT waited for.  OSQP_FUNC_NOT_IMPLEMENTED if it does not fit.
 // Sets d.batch_wave_ran.

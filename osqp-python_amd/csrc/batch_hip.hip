@@ -438,6 +438,8 @@ __global__ __launch_bounds__(kBB, (DIRECT && kBB == 256 && EA <= 8) ? (SPEC ? SP
   // an LDS round trip 178 per 8 values): resolving a block of 8 through its inverted diagonal block (two rounds of 8 INDEPENDENT
   // broadcasts instead of a chain of 8) was tried and is slower, 12.6 vs 9.0 us per solve -- twice the broadcasts, and they do
   // not pipeline.
+  // (k_batch_adjoint below carries a COPY of the general form of these substitutions and of factorize's elimination loop: a change to the padding
+  //  invariants -- the zero slot at Lr - 1, the kBatchNB zeros per column, the 64 doubles of read slack -- has to be made in both places.)
   auto ksolve = [&](const double *rhs, double *out) {
     if constexpr (SPEC) {
       if (tid < kBatchSpecN) sp_rhs[tid + (tid >= 64)] = tid < n ? rhs[tid] : 0.0;
@@ -1369,6 +1371,254 @@ int batch_prepare(Dev &d, const BatchParams &p, const double *Px_b, const double
   if (lds > 144 * 1024) return OSQP_FUNC_NOT_IMPLEMENTED;
   if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(&k_batch_prepare), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { (void)hipGetLastError(); return OSQP_FUNC_NOT_IMPLEMENTED; }
   hipLaunchKernelGGL(k_batch_prepare, dim3(p.nbatch), dim3(256), lds, static_cast<hipStream_t>(stream ? stream : d.stream), p, d, Px_b, Ax_b, scaling_iters);
+  return OSQP_NO_ERROR;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- adjoint derivatives
+// Backward pass of a batch of solved QPs: given (x, y) of  min 1/2 x'Px + q'x, l <= Ax <= u  and incoming gradients dx = dL/dx, dy = dL/dy, the
+// gradients of L with respect to q, l, u and the stored entries of P and A.  ONE WORKGROUP PER PROBLEM, everything in LDS, in the caller's UNSCALED
+// units (the raw matrix values are assembled into the CSR layouts of A and B = [P | A'] exactly as k_batch_prepare does, without equilibration).
+//   1. z = A x; active rows by polish's rule (k_batch_admm: low = z - l < -y, upp = u - z < y; an equality row is always active).
+//   2. [P, A_a'; A_a, 0] [r_x; r_a] = -[dx; dy_a]  through the regularised system of polish: ONE banded factorisation of
+//      S = P + delta I + A_a' A_a / delta  (the forward's permutation, band slots and product lists), then the first solve and `refine` refinement
+//      steps against the UNREGULARISED residual, each of the form
+//          t = r_a + (A_a r_x - g_a) / delta,   rhs = g_x - P r_x - A_a' t,   s = S^-1 rhs,   r_x += s,   r_a = t + A_a s / delta
+//      with the constraint residual accumulated in double-double (it is amplified by 1 / delta, as in polish).
+//   3. dq = r_x;  dl / du = -r_a on lower- / upper-active rows;  dP_ij = (r_i x_j + r_j x_i) / 2 and dA_ij = y_i r_x,j + r_y,i x_j on the stored
+//      entries, in the caller's CSC order: one writer per entry, no atomics.
+// Record per problem (kAdjointRec doubles): status, active rows, final relative residual max |g - K r| / max |g|, reserved.
+//   status 0: residual < kAdjointTol;  1: a pivot of S was not positive (replaced by its magnitude or 1: the problem is not convex or the inputs are
+//   not finite);  2: more active rows than variables (K is singular whatever the values);  3: the refinement stalled above kAdjointTol (a dependent
+//   active set).  The outputs of such an element are the regularised solution.
+namespace {
+__global__ __launch_bounds__(256) void k_batch_adjoint(AdjointParams P) {
+  constexpr int kBB = 256, NB = kBatchNB;
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  const int n = P.n, m = P.m, tid = threadIdx.x, b = blockIdx.x, nzA = P.A.nnz, nzB = P.B.nnz;
+  if (b >= P.nbatch) return;
+  const int bw = P.bw, W = P.bw + NB, n8 = (n + NB - 1) / NB * NB;
+  double *Av = sm, *Bv = Av + ((nzA + 1) & ~1), *x = Bv + ((nzB + 1) & ~1), *rx = x + n, *gx = rx + n, *rhs = gx + n, *sol = rhs + n, *wbuf = sol + n, *dinv = wbuf + n;
+  double *y = dinv + n, *w = y + m, *ra = w + m, *ga = ra + m, *t = ga + m, *sd = t + m;
+  Red<kBB / 64> red{sd + m};
+  double *Lb = sd + m + 16 + NB;
+  const int *Arp = P.A.rowptr, *Ac = P.A.col, *Brp = P.B.rowptr, *Bc = P.B.col;
+  // ---- the problem's own unscaled matrices in the CSR layouts ----
+  const double *Ar = P.Ax_b ? P.Ax_b + (size_t)b * P.nzA : P.Araw, *Pr = P.Px_b ? P.Px_b + (size_t)b * P.nzP : P.Praw;
+  for (int k = tid; k < nzB; k += kBB) Bv[k] = 0.0;
+  __syncthreads();
+  for (int k = tid; k < P.nzA; k += kBB) { const double v = Ar[k]; Av[P.AmA[k]] = v; Bv[P.AmB[k]] = v; }
+  for (int k = tid; k < P.nzP; k += kBB) {
+    const int i = P.Pi[k], j = P.Pj[k]; const double v = Pr[k];
+    if (i == j) atomicAdd(&Bv[P.Pm1[k]], v);            // (repeated (j, j) entries of a valid CSC sum up)
+    else { Bv[P.Pm1[k]] = v; Bv[P.Pm2[k]] = v; }
+  }
+  double gmax_l = 0.0;
+  for (int j = tid; j < n; j += kBB) { x[j] = P.x[(size_t)b * n + j]; const double g = -P.dx[(size_t)b * n + j]; gx[j] = g; rx[j] = 0.0; gmax_l = nmax(gmax_l, fabs(g)); }
+  for (int i = tid; i < m; i += kBB) y[i] = P.y[(size_t)b * m + i];
+  __syncthreads();
+  // ---- z = A x, the active set, the right-hand side of the active rows ----
+  const double idel = 1.0 / P.delta;
+  double nact_l = 0.0;
+  for (int i = tid; i < m; i += kBB) {
+    double z = 0.0;
+    for (int k = Arp[i]; k < Arp[i + 1]; k++) z += Av[k] * x[Ac[k]];
+    const double li = fmax(P.l ? P.l[(size_t)b * m + i] : P.l0[i], -OSQP_INFTY), ui = fmin(P.u ? P.u[(size_t)b * m + i] : P.u0[i], OSQP_INFTY), yi = y[i];
+    bool low = z - li < -yi, upp = !low && (ui - z < yi);
+    if (li == ui) { low = yi < 0.0; upp = !low; }
+    const bool act = low || upp;
+    const double g = act ? -(P.dy ? P.dy[(size_t)b * m + i] : 0.0) : 0.0;
+    w[i] = act ? idel : 0.0; sd[i] = low ? -1.0 : (upp ? 1.0 : 0.0); ga[i] = g; ra[i] = 0.0;
+    nact_l += act ? 1.0 : 0.0; gmax_l = nmax(gmax_l, fabs(g));
+  }
+  __syncthreads();
+  const double nact = red.sum(nact_l), gmax = red.max(gmax_l);
+  // ---- S = P + delta I + A_a' A_a / delta in the band (lower, permuted: k_batch_admm factorize) and its Cholesky factor ----
+  bool bad = false;
+  for (int s_ = tid - NB; s_ < n8 * W + 64; s_ += kBB) Lb[s_] = 0.0;
+  __syncthreads();
+  for (int k = tid; k < nzB; k += kBB) { const int s_ = P.bp_slot[k]; if (s_ >= 0) Lb[s_] = Bv[k]; }
+  __syncthreads();
+  for (int c = tid; c < n; c += kBB) Lb[c * W] += P.delta;
+  __syncthreads();
+  for (int e = tid; e < P.nents; e += kBB) {
+    double acc = 0.0;
+    for (int q_ = P.ke_ptr[e]; q_ < P.ke_ptr[e + 1]; q_++) acc += w[P.kp_row[q_]] * (Av[P.kp_a[q_]] * Av[P.kp_b[q_]]);
+    Lb[P.ke_slot[e]] += acc;
+  }
+  __syncthreads();
+  for (int c = 0; c < n; c++) {
+    double pv = Lb[c * W];
+    if (!(pv > 0.0) || pv > 1e300) { bad = true; pv = (fabs(pv) > P.delta && fabs(pv) <= 1e300) ? fabs(pv) : 1.0; }      // (block-uniform: every thread reads the same pivot)
+    const double di = 1.0 / sqrt(pv);
+    const int kmax = min(bw, n - 1 - c);
+    const bool mine = tid >= 1 && tid <= kmax;
+    double v = 0.0;
+    if (mine) v = Lb[c * W + tid] * di;
+    __syncthreads();
+    if (mine) Lb[c * W + tid] = v;
+    if (tid == 0) dinv[c] = di;
+    __syncthreads();
+    for (int t_ = tid; t_ < P.ntri; t_ += kBB) {
+      const int ab = P.tri[t_], a = ab & 255, b_ = ab >> 8;
+      if (b_ <= kmax) Lb[(c + a) * W + (b_ - a)] -= Lb[c * W + b_] * Lb[c * W + a];
+    }
+    __syncthreads();
+  }
+  // S = L^ D L^' with unit-lower L^: Lb <- L^ (strictly lower part, diagonal slots read as zero), dinv <- 1 / D
+  for (int s_ = tid; s_ < n * W; s_ += kBB) { const int c = s_ / W, k = s_ - c * W; if (k >= 1 && k <= bw) Lb[s_] *= dinv[c]; }
+  __syncthreads();
+  for (int c = tid; c < n; c += kBB) { const double di = dinv[c]; dinv[c] = di * di; Lb[c * W] = 0.0; }
+  __syncthreads();
+  // out = S^-1 in: the substitutions of k_batch_admm's ksolve (general form): wave 0, element e in lane e % 64 while within 64 of the pivots
+  auto ksolve = [&](const double *in, double *out) {
+    const double *__restrict__ Lr = Lb;
+    double *__restrict__ buf = wbuf;
+    for (int k = tid; k < n; k += kBB) buf[k] = in[P.perm[k]];
+    __syncthreads();
+    const int nblk = n8 / NB;
+    const bool w0 = tid < 64;
+    if (w0) {
+      double cur = tid < n ? buf[tid] : 0.0, nxt = 64 + tid < n ? buf[64 + tid] : 0.0;
+      auto fetch = [&](int p0, double (&l)[NB]) {
+        const int dl = (tid - p0) & 63;
+        const bool act = dl < bw + NB && p0 < n8;
+        const double *col = act ? Lr + p0 * W + dl : Lr - 1;
+        const int stride = act ? W - 1 : 0;
+#pragma unroll
+        for (int q = 0; q < NB; q++) l[q] = col[q * stride];
+      };
+      auto block = [&](int p0, const double (&l)[NB]) {
+#pragma unroll
+        for (int q = 0; q < NB; q++) { const double vq = readlane_f64(cur, (p0 + q) & 63); cur -= l[q] * vq; }
+        const int dl = (tid - p0) & 63;
+        if (dl < NB) {
+          const int e = p0 + dl;
+          if (e < n) buf[e] = cur;
+          cur = nxt; nxt = e + 128 < n ? buf[e + 128] : 0.0;
+        }
+      };
+      double la[NB], lb[NB];
+      fetch(0, la);
+      for (int k = 0; k < nblk; k += 2) {
+        fetch((k + 1) * NB, lb);
+        block(k * NB, la);
+        if (k + 1 < nblk) { fetch((k + 2) * NB, la); block((k + 1) * NB, lb); }
+      }
+    }
+    __syncthreads();
+    for (int k = tid; k < n; k += kBB) buf[k] *= dinv[k];
+    __syncthreads();
+    if (w0) {
+      auto elem = [&](int top) { return top - ((top - tid) & 63); };
+      const int i0 = elem(n8 - 1);
+      double cur = (i0 >= 0 && i0 < n) ? buf[i0] : 0.0, nxt = i0 - 64 >= 0 ? buf[i0 - 64] : 0.0;
+      auto fetch = [&](int top, double (&l)[NB]) {
+        const int dl = (top - tid) & 63, i = top - dl;
+        const bool act = dl < bw + NB && i >= 0 && top >= 0;
+        const double *row = act ? Lr + i * W + dl : Lr - 1;
+        const int stride = act ? 1 : 0;
+#pragma unroll
+        for (int q = 0; q < NB; q++) l[q] = row[-q * stride];
+      };
+      auto block = [&](int top, const double (&l)[NB]) {
+#pragma unroll
+        for (int q = 0; q < NB; q++) { const double xq = readlane_f64(cur, (top - q) & 63); cur -= l[q] * xq; }
+        const int dl = (top - tid) & 63;
+        if (dl < NB) {
+          const int i = top - dl;
+          if (i < n) buf[i] = cur;
+          cur = nxt; nxt = i - 128 >= 0 ? buf[i - 128] : 0.0;
+        }
+      };
+      double la[NB], lb[NB];
+      fetch(n8 - 1, la);
+      for (int k = nblk - 1; k >= 0; k -= 2) {
+        fetch(k * NB - 1, lb);
+        block(k * NB + NB - 1, la);
+        if (k >= 1) { fetch(k * NB - NB - 1, la); block(k * NB - 1, lb); }
+      }
+    }
+    __syncthreads();
+    for (int k = tid; k < n; k += kBB) out[P.perm[k]] = buf[k];
+    __syncthreads();
+  };
+  // ---- first solve + refinement steps ----
+  for (int it = 0; it <= P.refine; it++) {
+    for (int i = tid; i < m; i += kBB) {
+      double tv = 0.0;
+      if (w[i] != 0.0) {
+        double hi = -ga[i], lo = 0.0;                                       // (A r_x)_i - g_a,i
+        for (int e = Arp[i]; e < Arp[i + 1]; e++) dd_acc(Av[e], rx[Ac[e]], hi, lo);
+        tv = ra[i] + (hi + lo) * idel;
+      }
+      t[i] = tv;
+    }
+    __syncthreads();
+    for (int j = tid; j < n; j += kBB) {
+      double a = 0.0;
+      for (int k = Brp[j]; k < Brp[j + 1]; k++) { const int c = Bc[k]; a += Bv[k] * (c < n ? rx[c] : t[c - n]); }
+      rhs[j] = gx[j] - a;
+    }
+    __syncthreads();
+    ksolve(rhs, sol);
+    for (int j = tid; j < n; j += kBB) rx[j] += sol[j];
+    for (int i = tid; i < m; i += kBB) {
+      if (w[i] != 0.0) {
+        double a = 0.0;
+        for (int e = Arp[i]; e < Arp[i + 1]; e++) a += Av[e] * sol[Ac[e]];
+        ra[i] = t[i] + a * idel;
+      }
+    }
+    __syncthreads();
+  }
+  // ---- residual of the unregularised system ----
+  double rmax_l = 0.0;
+  for (int j = tid; j < n; j += kBB) {
+    double a = 0.0;
+    for (int k = Brp[j]; k < Brp[j + 1]; k++) { const int c = Bc[k]; a += Bv[k] * (c < n ? rx[c] : ra[c - n]); }
+    rmax_l = nmax(rmax_l, fabs(gx[j] - a));
+  }
+  for (int i = tid; i < m; i += kBB) {
+    if (w[i] != 0.0) {
+      double a = 0.0;
+      for (int e = Arp[i]; e < Arp[i + 1]; e++) a += Av[e] * rx[Ac[e]];
+      rmax_l = nmax(rmax_l, fabs(ga[i] - a));
+    }
+  }
+  const double rmax = red.max(rmax_l);
+  const double resid = gmax > 0.0 ? rmax / gmax : rmax;
+  // ---- gradients ----
+  if (P.dq) for (int j = tid; j < n; j += kBB) P.dq[(size_t)b * n + j] = rx[j];
+  for (int i = tid; i < m; i += kBB) {
+    const double v = -ra[i], s_ = sd[i];
+    if (P.dl) P.dl[(size_t)b * m + i] = s_ < 0.0 ? v : 0.0;
+    if (P.du) P.du[(size_t)b * m + i] = s_ > 0.0 ? v : 0.0;
+  }
+  if (P.dP) for (int k = tid; k < P.nzP; k += kBB) {
+    const int i = P.Pi[k], j = P.Pj[k];
+    P.dP[(size_t)b * P.nzP + k] = i == j ? rx[i] * x[i] : 0.5 * (rx[i] * x[j] + rx[j] * x[i]);
+  }
+  if (P.dA) for (int k = tid; k < P.nzA; k += kBB) {
+    const int i = P.Ai[k], j = P.Aj[k];
+    P.dA[(size_t)b * P.nzA + k] = y[i] * rx[j] + ra[i] * x[j];
+  }
+  if (tid == 0 && P.arec) {
+    double *rc = P.arec + (size_t)b * kAdjointRec;
+    rc[0] = bad ? 1.0 : (nact > (double)n ? 2.0 : (resid < kAdjointTol ? 0.0 : 3.0)); rc[1] = nact; rc[2] = resid; rc[3] = 0.0;
+  }
+}
+
+}  // namespace
+
+int batch_adjoint(Dev &d, const AdjointParams &p, void *stream) {
+  if (hipSetDevice(d.device) != hipSuccess) return OSQP_ALGEBRA_LOAD_ERROR;
+  const size_t lds = batch_adjoint_lds_bytes(p.n, p.m, p.A.nnz, p.B.nnz, p.bw);
+  if (!lds || !p.perm) return OSQP_FUNC_NOT_IMPLEMENTED;
+  if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(&k_batch_adjoint), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { (void)hipGetLastError(); return OSQP_FUNC_NOT_IMPLEMENTED; }
+  hipStream_t st = static_cast<hipStream_t>(stream ? stream : d.stream);
+  hipLaunchKernelGGL(k_batch_adjoint, dim3(p.nbatch), dim3(256), lds, st, p);
+  const hipError_t e = stream ? hipGetLastError() : hipStreamSynchronize(st);
+  if (e != hipSuccess) throw DeviceError(std::string("osqp_hip: adjoint kernel failed: ") + hipGetErrorString(e));
   return OSQP_NO_ERROR;
 }
 

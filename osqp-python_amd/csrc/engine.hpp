@@ -57,6 +57,16 @@ class Engine {
   // values for every problem) -- the reference's forward with a P_val / A_val per batch element (nn/torch.py:128-157): still ONE launch
   int batch_solve(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, double *zs_dev = nullptr, const double *Px = nullptr, const double *Ax = nullptr);
   int batch_solve_device(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream, const double *Px = nullptr, const double *Ax = nullptr);
+  // Adjoint derivatives (include/osqp_hip.h osqp_hip_batch_adjoint; batch_hip.hip k_batch_adjoint): one launch for the batch.  Host arrays, or -- _device --
+  // device arrays and a caller's stream with the semantics of batch_solve_device.  Px / Ax / l / u: nullptr = this solver's own values for every problem.
+  int batch_adjoint(int nbatch, const double *Px, const double *Ax, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
+                    double *dP, double *dq, double *dA, double *dl, double *du, double *arec);
+  int batch_adjoint_device(int nbatch, const double *Px, const double *Ax, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
+                           double *dP, double *dq, double *dA, double *dl, double *du, double *arec, void *stream);
+  // the reference's three calls on one handle (bindings.cpp.in:283-319): compute runs the kernel with a batch of one on the last solution and keeps the result
+  int adjoint_compute(const double *dx, const double *dy);
+  int adjoint_get_mat(OSQPCscMatrix *dP, OSQPCscMatrix *dA);
+  int adjoint_get_vec(double *dq, double *dl, double *du);
   int attach_batch_matrices(BatchParams &p, const double *Px_dev, const double *Ax_dev, void *stream);      // per-problem matrices: scratch + be::batch_prepare
   void fill_batch_params(BatchParams &p, int nbatch, int warm);
   // LinSysSolver slot (include/osqp_hip.h): this Engine instance is then used ONLY as the reduced-KKT solver
@@ -108,6 +118,10 @@ class Engine {
   std::map<std::pair<int, int>, void *> graphs_;
   double *bbuf_ = nullptr; size_t bbuf_cap_ = 0;      // device scratch of batch_solve, kept across calls
   double *bmat_ = nullptr; size_t bmat_cap_ = 0;      // per-problem matrices: scaled values, equilibration and products of every problem (BatchParams::Aval_b ..), kept across calls
+  double *abuf_ = nullptr; size_t abuf_cap_ = 0;      // device scratch of batch_adjoint (host-array entry point), kept across calls
+  bool adjoint_applicable();                          // the problem fits k_batch_adjoint (the forward's direct variant + the adjoint's own LDS)
+  void fill_adjoint_params(AdjointParams &p, int nbatch);
+  std::vector<double> adj_dP_, adj_dA_, adj_dq_, adj_dl_, adj_du_; bool adj_ok_ = false;      // result of the last adjoint_compute
   int *d_batch_iters_ = nullptr; int d_batch_iters_n_ = 0;      // device-pointer path: iteration counts of the previous call (its records never reach the host)
   std::vector<int> batch_order_; int *d_batch_order_ = nullptr; size_t batch_order_cap_ = 0;   // problems by descending iteration count of the previous batch call
   double *ckpt_ = nullptr;                            // device copy of (x, x~, z, y) taken before a solve's first chunk (cg cap escalation)

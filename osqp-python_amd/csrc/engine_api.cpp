@@ -869,6 +869,109 @@ int Engine::batch_solve_device(int nbatch, const double *q, const double *l, con
   return err;
 }
 
+// ------------------------------------------------------------------------------------------------ adjoint derivatives
+// The backward pass of the batch path (batch_hip.hip k_batch_adjoint).  A problem is eligible when the forward's direct variant holds it (banded factor
+// under the engine's ordering: prepare_batch_direct) and the adjoint kernel's own LDS fits; everything else -- large single QPs on the PCG path, the
+// host simulator -- answers OSQP_FUNC_NOT_IMPLEMENTED.
+bool Engine::adjoint_applicable() {
+  if (!be::batch_adjoint || !be::device_assembly() || !be::device_vec_updates() || reordered_ || !be::batch_lds_bytes(n, m)) return false;
+  prepare_batch_direct();
+  return bd_.ok && batch_adjoint_lds_bytes(n, m, d_.A.nnz, d_.B.nnz, bd_.bw) != 0;
+}
+
+void Engine::fill_adjoint_params(AdjointParams &p, int nbatch) {
+  p.n = n; p.m = m; p.nbatch = nbatch; p.nzP = d_.nzP; p.nzA = d_.nzA; p.A = d_.A; p.B = d_.B; p.Praw = d_.Praw; p.Araw = d_.Araw;
+  p.Pi = d_.Pi; p.Pj = d_.Pj; p.Pm1 = d_.Pm1; p.Pm2 = d_.Pm2; p.Ai = d_.Ai; p.Aj = d_.Aj; p.AmA = d_.AmA; p.AmB = d_.AmB;
+  p.l0 = d_.lraw; p.u0 = d_.uraw; p.delta = settings.delta; p.refine = settings.polish_refine_iter;
+  p.bw = bd_.bw; p.nents = bd_.nents; p.ntri = bd_.ntri; p.perm = bd_.perm; p.bp_slot = bd_.bp_slot; p.ke_slot = bd_.ke_slot; p.ke_ptr = bd_.ke_ptr;
+  p.kp_row = bd_.kp_row; p.kp_a = bd_.kp_a; p.kp_b = bd_.kp_b; p.tri = bd_.tri;
+}
+
+int Engine::batch_adjoint(int nbatch, const double *Px, const double *Ax, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
+                          double *dP, double *dq, double *dA, double *dl, double *du, double *arec) {
+  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (nbatch <= 0 || !x || !y || !dx) return OSQP_DATA_VALIDATION_ERROR;
+  be::activate(d_);
+  if (!adjoint_applicable()) return OSQP_FUNC_NOT_IMPLEMENTED;
+  be::ext_wait(d_);
+  const size_t nb = (size_t)nbatch, N = nb * n, M = nb * m, NP = nb * (size_t)d_.nzP, NA = nb * (size_t)d_.nzA;
+  // one device scratch block, kept for the next call: [Px | Ax | l | u | x | y | dx | dy | dP | dq | dA | dl | du | arec]
+  const size_t need = 2 * NP + 2 * NA + 3 * N + 6 * M + nb * kAdjointRec;
+  if (need > abuf_cap_) { if (abuf_) be::dfree(d_, abuf_); abuf_ = dev_vec<double>(d_, need); abuf_cap_ = need; }
+  double *dPx = abuf_, *dAx = dPx + NP, *d_l = dAx + NA, *d_u = d_l + M, *d_x = d_u + M, *d_y = d_x + N, *d_dx = d_y + M, *d_dy = d_dx + N;
+  double *o_dP = d_dy + M, *o_dq = o_dP + NP, *o_dA = o_dq + N, *o_dl = o_dA + NA, *o_du = o_dl + M, *o_rec = o_du + M;
+  auto up = [&](double *dst, const double *src, size_t cnt) { if (src && cnt) be::h2d(d_, dst, src, sizeof(double) * cnt); };
+  up(dPx, Px, NP); up(dAx, Ax, NA); up(d_l, l, M); up(d_u, u, M); up(d_x, x, N); up(d_y, y, M); up(d_dx, dx, N); up(d_dy, dy, M);
+  AdjointParams p{};
+  fill_adjoint_params(p, nbatch);
+  p.Px_b = Px ? dPx : nullptr; p.Ax_b = Ax ? dAx : nullptr; p.l = l ? d_l : nullptr; p.u = u ? d_u : nullptr;
+  p.x = d_x; p.y = d_y; p.dx = d_dx; p.dy = dy ? d_dy : nullptr;
+  p.dP = dP ? o_dP : nullptr; p.dq = dq ? o_dq : nullptr; p.dA = dA ? o_dA : nullptr; p.dl = dl ? o_dl : nullptr; p.du = du ? o_du : nullptr; p.arec = arec ? o_rec : nullptr;
+  be::sync(d_);
+  const int err = be::batch_adjoint(d_, p, nullptr);
+  if (err) return err;
+  auto down = [&](double *dst, const double *src, size_t cnt) { if (dst && cnt) be::d2h(d_, dst, src, sizeof(double) * cnt); };
+  down(dP, o_dP, NP); down(dq, o_dq, N); down(dA, o_dA, NA); down(dl, o_dl, M); down(du, o_du, M); down(arec, o_rec, nb * kAdjointRec);
+  return OSQP_NO_ERROR;
+}
+
+int Engine::batch_adjoint_device(int nbatch, const double *Px, const double *Ax, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
+                                 double *dP, double *dq, double *dA, double *dl, double *du, double *arec, void *stream) {
+  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (nbatch < 0) return OSQP_DATA_VALIDATION_ERROR;
+  be::activate(d_);
+  if (!adjoint_applicable()) return OSQP_FUNC_NOT_IMPLEMENTED;
+  if (nbatch == 0) return OSQP_NO_ERROR;                     // (the applicability query, as osqp_hip_batch_solve_device answers it)
+  if (!x || !y || !dx) return OSQP_DATA_VALIDATION_ERROR;
+  be::ext_wait(d_);
+  AdjointParams p{};
+  fill_adjoint_params(p, nbatch);
+  p.Px_b = Px; p.Ax_b = Ax; p.l = l; p.u = u; p.x = x; p.y = y; p.dx = dx; p.dy = dy;
+  p.dP = dP; p.dq = dq; p.dA = dA; p.dl = dl; p.du = du; p.arec = arec;
+  be::sync(d_);                                              // as batch_solve_device (launch_batch, wait_solver): the kernel goes on the CALLER's stream and reads what the solver's own stream may still be writing -- the symbolic data's uploads, a pending update of the resident P / A / l / u
+  const int err = be::batch_adjoint(d_, p, stream);
+  if (!err) be::ext_record(d_, stream);                      // the kernel reads the solver's own matrices and bounds
+  return err;
+}
+
+// osqp_adjoint_derivative_compute: needs the solution of a solve that ended OSQP_SOLVED on the current data (every data update resets the status);
+// OSQP_DATA_NOT_INITIALIZED otherwise.
+int Engine::adjoint_compute(const double *dx, const double *dy) {
+  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  adj_ok_ = false;
+  be::activate(d_);
+  if (!adjoint_applicable()) return OSQP_FUNC_NOT_IMPLEMENTED;
+  if (info.status_val != OSQP_SOLVED) return OSQP_DATA_NOT_INITIALIZED;
+  std::vector<double> zero;
+  if (!dx) { zero.assign(n, 0.0); dx = zero.data(); }
+  adj_dP_.assign(P_.nnz(), 0.0); adj_dA_.assign(A_.nnz(), 0.0); adj_dq_.assign(n, 0.0); adj_dl_.assign(m, 0.0); adj_du_.assign(m, 0.0);
+  std::vector<double> yv(std::max(m, 1), 0.0);
+  std::copy(sol_y_.begin(), sol_y_.begin() + m, yv.begin());
+  const int err = batch_adjoint(1, nullptr, nullptr, nullptr, nullptr, sol_x_.data(), yv.data(), dx, m > 0 ? dy : nullptr,
+                                adj_dP_.empty() ? nullptr : adj_dP_.data(), adj_dq_.data(), adj_dA_.empty() ? nullptr : adj_dA_.data(),
+                                m > 0 ? adj_dl_.data() : nullptr, m > 0 ? adj_du_.data() : nullptr, nullptr);
+  adj_ok_ = err == OSQP_NO_ERROR;
+  return err;
+}
+
+int Engine::adjoint_get_mat(OSQPCscMatrix *dP, OSQPCscMatrix *dA) {
+  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (!adj_ok_) return adjoint_applicable() ? OSQP_DATA_NOT_INITIALIZED : OSQP_FUNC_NOT_IMPLEMENTED;
+  // the caller passes the patterns of P's upper triangle and of A as given at setup; the values arrive in that order
+  if (dP) { if (!dP->x || dP->n != n || !dP->p || dP->p[n] != P_.nnz()) return OSQP_DATA_VALIDATION_ERROR; std::copy(adj_dP_.begin(), adj_dP_.end(), dP->x); }
+  if (dA) { if (!dA->x || dA->n != n || dA->m != m || !dA->p || dA->p[n] != A_.nnz()) return OSQP_DATA_VALIDATION_ERROR; std::copy(adj_dA_.begin(), adj_dA_.end(), dA->x); }
+  return OSQP_NO_ERROR;
+}
+
+int Engine::adjoint_get_vec(double *dq, double *dl, double *du) {
+  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (!adj_ok_) return adjoint_applicable() ? OSQP_DATA_NOT_INITIALIZED : OSQP_FUNC_NOT_IMPLEMENTED;
+  if (dq) std::copy(adj_dq_.begin(), adj_dq_.end(), dq);
+  if (dl) std::copy(adj_dl_.begin(), adj_dl_.end(), dl);
+  if (du) std::copy(adj_du_.begin(), adj_du_.end(), du);
+  return OSQP_NO_ERROR;
+}
+
 int Engine::get_stats(OSQPHipStats *out) {
   if (!out) return OSQP_DATA_VALIDATION_ERROR;
   *out = stats_; out->pcg_fused = (d_.f1.on && use_slots_) ? 2.0 : ((d_.kf.on && use_slots_) ? 3.0 : (be::pcg_fused(d_) ? 1.0 : 0.0)); out->batch_direct_bw = bd_.bw_symbolic;

@@ -102,6 +102,11 @@ def osqp_capabilities():                       # bindings.cpp.in:402
     return int(_lib.handle().osqp_capabilities())
 
 
+def osqp_hip_capabilities():
+    """osqp_capabilities() plus what this engine adds to the reference's list: OSQP_CAPABILITY_DERIVATIVES (the adjoint kernel)."""
+    return int(_lib.handle().osqp_hip_capabilities())
+
+
 def _info_property(name, typ, writable):
     def get(self):
         v = getattr(self._s.contents, name)
@@ -216,10 +221,26 @@ class OSQPSolver:
     def update_rho(self, rho_new):
         return self._lib.osqp_update_rho(self._p, float(rho_new))
 
-    # ---- out of scope (derivatives / codegen): the engine reports OSQP_FUNC_NOT_IMPLEMENTED ----
+    # ---- adjoint derivatives (bindings.cpp.in:283-319): the C call's osqp_error_type is returned, as the pybind layer does ----
     def adjoint_derivative_compute(self, dx=None, dy=None):
-        return self._lib.osqp_adjoint_derivative_compute(self._p, None, None)
+        dx, dy = _vec(dx), _vec(dy)
+        for a, k, name in ((dx, self.n, 'dx'), (dy, self.m, 'dy')):
+            if a is not None and a.size != k:
+                raise ValueError('%s: expected %d entries, got %d' % (name, k, a.size))
+        return self._lib.osqp_adjoint_derivative_compute(self._p, _ptr(dx, _lib.c_double_p), _ptr(dy, _lib.c_double_p))
 
+    def adjoint_derivative_get_mat(self, dP, dA):
+        """dP, dA: CSC objects carrying the patterns of P's upper triangle and of A; their x arrays are filled."""
+        Ps, As = dP._struct(), dA._struct()
+        return self._lib.osqp_adjoint_derivative_get_mat(self._p, C.byref(Ps), C.byref(As))
+
+    def adjoint_derivative_get_vec(self, dq, dl, du):
+        for a, k in ((dq, self.n), (dl, self.m), (du, self.m)):
+            if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.size == k):
+                raise TypeError('dq, dl, du must be contiguous float64 numpy arrays of length n, m, m')
+        return self._lib.osqp_adjoint_derivative_get_vec(self._p, _ptr(dq, _lib.c_double_p), _ptr(dl, _lib.c_double_p), _ptr(du, _lib.c_double_p))
+
+    # ---- out of scope (codegen): the engine reports OSQP_FUNC_NOT_IMPLEMENTED ----
     def codegen(self, output_dir, file_prefix, defines):
         return self._lib.osqp_codegen(self._p, None, None, None)
 
@@ -326,6 +347,50 @@ class OSQPSolver:
             st = self._lib.osqp_hip_batch_solve_mat_device(self._p, int(nbatch), Px_ptr, Ax_ptr, q_ptr, l_ptr, u_ptr, x_ptr, y_ptr, rec_ptr, int(bool(warm)), stream)
         else:
             st = self._lib.osqp_hip_batch_solve_device(self._p, int(nbatch), q_ptr, l_ptr, u_ptr, x_ptr, y_ptr, rec_ptr, int(bool(warm)), stream)
+        if st:
+            raise self._batch_error(st)
+
+    ADJOINT_FIELDS = ('status', 'active_rows', 'residual', 'reserved')
+    ADJOINT_REC = len(ADJOINT_FIELDS)    # OSQP_HIP_ADJOINT_REC
+    ADJOINT_TOL = 1e-6                   # OSQP_HIP_ADJOINT_TOL
+
+    def hip_batch_adjoint(self, x, y, dx, dy=None, l=None, u=None, Px=None, Ax=None, want=('dP', 'dq', 'dA', 'dl', 'du')):
+        """Adjoint derivatives of a batch of solved QPs (osqp_hip_batch_adjoint: one launch).  x, dx: (B, n); y, dy: (B, m), dy None = 0;
+        l / u (B, m), Px (B, nnz(triu P)), Ax (B, nnz(A)): what the batch was solved with, None = this solver's own values.
+        Returns a dict with the arrays named in `want` -- dP (B, nnz(triu P)) and dA (B, nnz(A)) in the CSC order given at setup, dq (B, n),
+        dl, du (B, m) -- and 'rec' (B, ADJOINT_REC) with columns ADJOINT_FIELDS."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        B = 1 if x.ndim == 1 else int(x.shape[0])
+
+        def rows(a, name, width):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.size != B * width or (a.ndim > 1 and a.shape[-1] != width):
+                raise ValueError('%s: expected %d problems of width %d, got shape %s' % (name, B, width, a.shape))
+            return a.reshape(B, width)
+        x, y, dx, dy, l, u = (rows(a, nm, w) for a, nm, w in ((x, 'x', self.n), (y, 'y', self.m), (dx, 'dx', self.n), (dy, 'dy', self.m), (l, 'l', self.m), (u, 'u', self.m)))
+        Px, Ax = rows(Px, 'Px', self.nnz_P), rows(Ax, 'Ax', self.nnz_A)
+        if x is None or y is None or dx is None:
+            raise ValueError('x, y and dx are required')
+        widths = {'dP': self.nnz_P, 'dq': self.n, 'dA': self.nnz_A, 'dl': self.m, 'du': self.m}
+        out = {k: (np.zeros((B, widths[k])) if k in want else None) for k in widths}
+        rec = np.zeros((B, self.ADJOINT_REC))
+        dp = _lib.c_double_p
+        st = self._lib.osqp_hip_batch_adjoint(self._p, B, _ptr(Px, dp), _ptr(Ax, dp), _ptr(l, dp), _ptr(u, dp), _ptr(x, dp), _ptr(y, dp), _ptr(dx, dp), _ptr(dy, dp),
+                                              _ptr(out['dP'], dp), _ptr(out['dq'], dp), _ptr(out['dA'], dp), _ptr(out['dl'], dp), _ptr(out['du'], dp), _ptr(rec, dp))
+        if st:
+            raise self._batch_error(st)
+        res = {k: v for k, v in out.items() if v is not None}
+        res['rec'] = rec
+        return res
+
+    def hip_batch_adjoint_device(self, nbatch, x_ptr, y_ptr, dx_ptr, dy_ptr=None, l_ptr=None, u_ptr=None, Px_ptr=None, Ax_ptr=None,
+                                 dP_ptr=None, dq_ptr=None, dA_ptr=None, dl_ptr=None, du_ptr=None, rec_ptr=None, stream=None):
+        """osqp_hip_batch_adjoint_device: raw device addresses (int or None) of float64 arrays laid out as in hip_batch_adjoint; enqueued on `stream`
+        (hipStream_t handle as int; None: the solver's stream, synchronous).  nbatch == 0 only asks whether the problem fits."""
+        st = self._lib.osqp_hip_batch_adjoint_device(self._p, int(nbatch), Px_ptr, Ax_ptr, l_ptr, u_ptr, x_ptr, y_ptr, dx_ptr, dy_ptr,
+                                                     dP_ptr, dq_ptr, dA_ptr, dl_ptr, du_ptr, rec_ptr, stream)
         if st:
             raise self._batch_error(st)
 

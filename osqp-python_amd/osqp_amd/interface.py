@@ -5,7 +5,8 @@ update_settings / warm_start``, the module helpers and the two status enums; /ro
 :120-434).  Names, keyword arguments, exception types and the numeric error mapping are the reference's -- they are what
 ``tests/test_reference_suite.py::test_frontend_contract`` pins -- the implementation is this repository's own: one
 normalisation pipeline for the problem data, one table for the settings that are not plain ``OSQPSettings`` fields.
-Code generation and the adjoint-derivative entry points are out of scope and say so when called.
+``adjoint_derivative_compute / _get_mat / _get_vec`` (reference interface.py:519-598) run the engine's adjoint kernel for problems the batch
+kernel's direct variant holds; code generation is out of scope and says so when called.
 """
 import functools
 import importlib as _importlib
@@ -133,6 +134,7 @@ class OSQP:
         self.m = self.n = None
         self.settings = None
         self._solver = None
+        self._derivative_cache = {}
 
     def __str__(self):
         state = 'Uninitialized OSQP' if self._solver is None else 'OSQP'
@@ -154,7 +156,7 @@ class OSQP:
 
     @property
     def capabilities(self):
-        mask = self.ext.osqp_capabilities()
+        mask = self.ext.osqp_hip_capabilities()      # (the reference's list + OSQP_CAPABILITY_DERIVATIVES; the C symbol osqp_capabilities() stays as it was)
         return int(mask)
 
     def has_capability(self, capability: str):
@@ -241,6 +243,7 @@ class OSQP:
         self.ext.osqp_set_default_settings(defaults)
         self.update_settings(**settings)                           # validates names; nothing is sent yet (no solver)
         self._solver = self.raises_error(self.ext.OSQPSolver, self.ext.CSC(P), q, self.ext.CSC(A), l, u, self.m, self.n, self.settings)
+        self._derivative_cache = {'P': P, 'A': A}                  # the patterns adjoint_derivative_get_mat answers on
         rho = settings.get('rho')
         if rho is not None:
             self._solver.update_rho(rho)
@@ -253,6 +256,8 @@ class OSQP:
                    'u': None if kwargs.get('u') is None else np.minimum(kwargs['u'], big)}
         if any(v is not None for v in vectors.values()):
             self._solver.update_data_vec(**vectors)
+        if any(kwargs.get(k) is not None for k in ('q', 'l', 'u', 'Px', 'Ax')):
+            self._derivative_cache.pop('results', None)            # (the engine resets its status as well: derivatives need a new solve)
         if {'Px', 'Px_idx', 'Ax', 'Ax_idx'} & set(kwargs):
             self._solver.update_data_mat(P_x=kwargs.get('Px'), P_i=kwargs.get('Px_idx'), A_x=kwargs.get('Ax'), A_i=kwargs.get('Ax_idx'))
 
@@ -271,10 +276,52 @@ class OSQP:
             raise OSQPException(raw.status_val)
         info = _Namespace(**{name: getattr(raw, name) for name in vars(type(raw)) if not name.startswith('_')})
         sol = self._solver.solution
-        return _Namespace(x=sol.x, y=sol.y, prim_inf_cert=sol.prim_inf_cert, dual_inf_cert=sol.dual_inf_cert, info=info)
+        results = _Namespace(x=sol.x, y=sol.y, prim_inf_cert=sol.prim_inf_cert, dual_inf_cert=sol.dual_inf_cert, info=info)
+        self._derivative_cache['results'] = results
+        return results
+
+    # ------------------------------------------------------------------ adjoint derivatives
+    def _solved_or_raise(self):
+        _require(self.has_capability('OSQP_CAPABILITY_DERIVATIVES'), 'This OSQP object does not support derivatives')
+        if 'results' not in self._derivative_cache:
+            raise ValueError('Problem has not been solved. You cannot take derivatives. Please call the solve function.')
+        if self._derivative_cache['results'].info.status_val != SolverStatus.OSQP_SOLVED:
+            raise ValueError('Problem has not been solved to optimality. You cannot take derivatives')
+
+    def _adjoint_status(self, status):
+        if status == SolverError.OSQP_FUNC_NOT_IMPLEMENTED:
+            raise NotImplementedError('adjoint derivatives exist for problems the batch kernel\'s direct variant holds (one workgroup\'s LDS, '
+                                      'permuted half bandwidth <= 56); this problem takes the PCG path')
+        if status:
+            raise OSQPException(int(status))
+
+    def adjoint_derivative_compute(self, dx=None, dy=None):
+        """Adjoint derivatives of the last solution with respect to the problem data, for incoming gradients dx = dL/dx (n) and dy = dL/dy (m)
+        (None: zero).  Needs a solve() that ended OSQP_SOLVED on the current data; results through adjoint_derivative_get_mat / _get_vec."""
+        self._solved_or_raise()
+        dy = np.zeros(self.m) if dy is None else dy
+        self._adjoint_status(self._solver.adjoint_derivative_compute(dx, dy))
+
+    def adjoint_derivative_get_mat(self, as_dense=True, dP_as_triu=True):
+        """(dP, dA) after adjoint_derivative_compute: gradients at the stored entries of P (its upper triangle, or -- dP_as_triu=False -- mirrored
+        to the full symmetric pattern with the same value in either triangle) and of A; dense arrays or -- as_dense=False -- scipy CSC."""
+        self._solved_or_raise()
+        dP, dA = self.ext.CSC(self._derivative_cache['P'].copy()), self.ext.CSC(self._derivative_cache['A'].copy())
+        self._adjoint_status(self._solver.adjoint_derivative_get_mat(dP, dA))
+        dP, dA = (spa.csc_matrix((c.x, c.i, c.p), shape=(c.m, c.n)) for c in (dP, dA))
+        if not dP_as_triu:
+            dP = (dP + spa.triu(dP, 1).T).tocsc()
+        return (dP.toarray(), dA.toarray()) if as_dense else (dP, dA)
+
+    def adjoint_derivative_get_vec(self):
+        """(dq, dl, du) after adjoint_derivative_compute."""
+        self._solved_or_raise()
+        dq, dl, du = np.empty(self.n, dtype=self._dtype), np.zeros(self.m, dtype=self._dtype), np.zeros(self.m, dtype=self._dtype)
+        self._adjoint_status(self._solver.adjoint_derivative_get_vec(dq, dl, du))
+        return dq, dl, du
 
     # ------------------------------------------------------------------ not part of this engine
     def _out_of_scope(self, *_args, **_kwargs):
-        raise NotImplementedError('code generation and adjoint derivatives are outside the MI355X engine (SURVEY.md section 2)')
+        raise NotImplementedError('code generation is outside the MI355X engine (SURVEY.md section 2)')
 
-    codegen = adjoint_derivative_compute = adjoint_derivative_get_mat = adjoint_derivative_get_vec = _out_of_scope
+    codegen = _out_of_scope

@@ -15,8 +15,16 @@ threads.  Here one persistent engine handle plays that role:
     and equilibrated per element by a launch in front of it (osqp_hip_batch_solve_mat); only a problem too large for one workgroup falls back to the
     single-QP handle, one element after the other.
 
-Like the reference, a batch element that is not solved raises RuntimeError (:158-162).  Backward (adjoint derivatives,
-:233-290) is out of scope of this engine: the returned tensor carries no grad_fn.
+Like the reference, a batch element that is not solved raises RuntimeError (:158-162).
+
+Backward (the reference's :233-290): when an input requires grad, ``forward`` runs as a ``torch.autograd.Function`` and the returned tensor carries a
+grad_fn.  ``backward(dl_dx)`` makes ONE launch of the adjoint kernel for the whole batch (``osqp_hip_batch_adjoint``; ``adjoint_launches`` counts
+them) on the solution and duals the forward kept, and returns (dP, dq, dA, dl, du) shaped like the inputs: an input shared by the batch (1-D) gets
+the sum over the batch, as autograd's ``expand`` would give.  dP holds, for every entry of P_val (the full symmetric pattern P_idx), the value
+(r_i x_j + r_j x_i) / 2 of its position -- the same in either triangle.  Gradients arriving on the GPU go through the device-pointer entry point
+on torch's current stream, zero-copy.  ``last_adjoint_rec`` keeps the kernel's record per element (status, active rows, residual).  A problem the
+batch kernel cannot hold, and a ``torch.distributed`` job (world size > 1), raise NotImplementedError in backward.  With no input requiring grad,
+forward behaves exactly as before.
 """
 import numpy as np
 import scipy.sparse as spa
@@ -51,6 +59,9 @@ class OSQP(Module):
         self._triu_pick = None       # positions of the upper-triangle entries of P inside P_val
         self.setup_count = 0         # number of osqp_setup calls made by this layer (1 after any number of same-structure forwards)
         self.last_dual = None
+        self.adjoint_launches = 0    # launches of the adjoint kernel made by this layer's backward passes (one per backward)
+        self.last_adjoint_rec = None # (nb, 4) record of the last backward: status, active rows, residual, reserved (ext_hip ADJOINT_FIELDS)
+        self._grad_maps = None
 
     # ------------------------------------------------------------------ the persistent handle
     def _matrices(self, P_val, A_val):
@@ -78,6 +89,12 @@ class OSQP(Module):
 
     # ------------------------------------------------------------------ forward
     def forward(self, P_val, q_val, A_val, l_val, u_val):
+        params = (P_val, q_val, A_val, l_val, u_val)
+        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            return _OSQPFunction.apply(self, *params)
+        return self._solve(*params)
+
+    def _solve(self, P_val, q_val, A_val, l_val, u_val):
         params = [P_val, q_val, A_val, l_val, u_val]
         for p in params:
             assert p.ndimension() <= 2, 'Unexpected number of dimensions'
@@ -187,3 +204,85 @@ class OSQP(Module):
             x[i] = r.x
             rec[i, 0], rec[i, 1], rec[i, 2] = r.info.status_val, r.info.iter, r.info.obj_val
         return x, rec
+
+    # ------------------------------------------------------------------ backward
+    def _p_map(self, nP):
+        """P_val position -> position of its upper-triangle twin in the engine's dP (upper triangle of P, CSC order)."""
+        if self._grad_maps is None:
+            rows, cols = (np.asarray(a).astype(np.int64) for a in self.P_idx)
+            tr, tc = np.minimum(rows, cols), np.maximum(rows, cols)
+            where = {(int(tr[k]), int(tc[k])): t for t, k in enumerate(self._triu_pick)}
+            self._grad_maps = np.array([where[(int(tr[k]), int(tc[k]))] for k in range(nP)], dtype=np.int64)
+        return self._grad_maps
+
+    def _backward(self, saved, x, y, dl_dx, needs):
+        P_val, q_val, A_val, l_val, u_val = saved
+        params = [P_val, q_val, A_val, l_val, u_val]
+        batched = [p.ndimension() == 2 for p in params]
+        nb = max([p.size(0) for p, b in zip(params, batched) if b], default=1)
+        if _distributed()[1] > 1:
+            raise NotImplementedError('osqp_amd.nn.torch.OSQP: backward in a torch.distributed job (world size > 1) is not implemented')
+        if y is None:
+            raise NotImplementedError('osqp_amd.nn.torch.OSQP: backward needs the adjoint kernel, which holds problems with a banded factor in one workgroup\'s LDS (permuted half bandwidth <= 56, matrices + band <= 144 KB); this problem is outside it')
+        s = self._solver
+        Pn, An = _np(P_val), _np(A_val)
+        # the handle's own values of a SHARED side are what the forward solved with (an intermediate forward may have replaced them)
+        self._handle(self._Pv if batched[0] else Pn, self._Av if batched[2] else An, None, None, None, device=self._device)
+        p_map = self._p_map(Pn.shape[-1])      # (A_val is in the CSC order of A, as the forward takes it)
+        want = tuple(k for k, need in zip(('dP', 'dq', 'dA', 'dl', 'du'), needs) if need)
+        g = dl_dx.detach().reshape(-1, self.n)
+        if g.shape[0] != nb:
+            g = g.expand(nb, self.n)
+        try:
+            if g.is_cuda:
+                dev = g.device
+                f64 = lambda t, k: torch.as_tensor(t).detach().to(device=dev, dtype=torch.float64).reshape(-1, k).expand(nb, k).contiguous()
+                xd, yd, gd, ld, ud = f64(x, self.n), f64(y, self.m), f64(g, self.n), f64(l_val, self.m), f64(u_val, self.m)
+                Pxd = f64(P_val, Pn.shape[-1])[:, torch.as_tensor(self._triu_pick, device=dev)].contiguous() if batched[0] else None
+                Axd = f64(A_val, An.shape[-1]) if batched[2] else None
+                widths = {'dP': len(self._triu_pick), 'dq': self.n, 'dA': An.shape[-1], 'dl': self.m, 'du': self.m}
+                res = {k: torch.empty((nb, widths[k]), dtype=torch.float64, device=dev) for k in want}
+                res['rec'] = torch.empty((nb, 4), dtype=torch.float64, device=dev)     # OSQP_HIP_ADJOINT_REC
+                ptr = lambda t: None if t is None else t.data_ptr()
+                s._solver.hip_batch_adjoint_device(nb, xd.data_ptr(), yd.data_ptr(), gd.data_ptr(), None, ld.data_ptr(), ud.data_ptr(), ptr(Pxd), ptr(Axd),
+                                                   ptr(res.get('dP')), ptr(res.get('dq')), ptr(res.get('dA')), ptr(res.get('dl')), ptr(res.get('du')),
+                                                   res['rec'].data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
+            else:
+                bc = lambda a, k: np.broadcast_to(np.asarray(a, dtype=float).reshape(-1, k), (nb, k))
+                res = s._solver.hip_batch_adjoint(bc(_np(torch.as_tensor(x)), self.n), bc(_np(torch.as_tensor(y)), self.m), bc(_np(g), self.n), None,
+                                                  l=bc(_np(l_val), self.m), u=bc(_np(u_val), self.m),
+                                                  Px=Pn[:, self._triu_pick] if batched[0] else None, Ax=An if batched[2] else None, want=want)
+                res = {k: torch.as_tensor(v) for k, v in res.items()}
+        except ValueError as e:
+            if str(e) != str(int(osqp_amd.SolverError.OSQP_FUNC_NOT_IMPLEMENTED)):
+                raise
+            raise NotImplementedError('osqp_amd.nn.torch.OSQP: backward needs the adjoint kernel, which holds problems with a banded factor in one workgroup\'s LDS (permuted half bandwidth <= 56, matrices + band <= 144 KB); this problem is outside it')
+        self.adjoint_launches += 1
+        self.last_adjoint_rec = res['rec']
+        if 'dP' in res:                                    # engine order (upper triangle, CSC) -> the order of P_val, either triangle the same value
+            res['dP'] = res['dP'][:, torch.as_tensor(p_map, device=res['dP'].device)]
+        grads = []
+        for key, p, b in zip(('dP', 'dq', 'dA', 'dl', 'du'), params, batched):
+            if key not in res:
+                grads.append(None)
+                continue
+            v = res[key] if b else res[key].sum(0)
+            grads.append(v.to(device=p.device, dtype=p.dtype).reshape(p.shape))
+        return tuple(grads)
+
+
+class _OSQPFunction(torch.autograd.Function):
+    """forward = the layer's solve; backward = one launch of the adjoint kernel on what the forward kept (x, the duals, the inputs)."""
+
+    @staticmethod
+    def forward(ctx, layer, P_val, q_val, A_val, l_val, u_val):
+        layer.last_dual = None
+        out = layer._solve(P_val.detach(), q_val.detach(), A_val.detach(), l_val.detach(), u_val.detach())
+        ctx.layer, ctx.dual = layer, layer.last_dual
+        ctx.save_for_backward(P_val, q_val, A_val, l_val, u_val, out)
+        return out
+
+    @staticmethod
+    def backward(ctx, dl_dx):
+        *saved, out = ctx.saved_tensors
+        return (None,) + ctx.layer._backward(saved, out, ctx.dual, dl_dx, ctx.needs_input_grad[1:])
