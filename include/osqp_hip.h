@@ -162,10 +162,11 @@ OSQPInt osqp_update_settings(OSQPSolver *solver, const OSQPSettings *new_setting
 OSQPInt osqp_update_rho(OSQPSolver *solver, OSQPFloat rho_new);         /* bindings.cpp.in:213 */
 void    osqp_get_dimensions(OSQPSolver *solver, OSQPInt *m, OSQPInt *n);   /* codegen/pywrapper/bindings.cpp.jinja:21 */
 
-/* Adjoint derivatives of the last solution (bindings.cpp.in:283-319), for a problem that fits the batch kernel's direct variant (see osqp_hip_batch_solve
-   below); a larger problem -- the PCG path -- returns OSQP_FUNC_NOT_IMPLEMENTED.  compute: needs a previous osqp_solve that ended OSQP_SOLVED on the
+/* Adjoint derivatives of the last solution (bindings.cpp.in:283-319): by the batch kernel for a problem that fits its direct variant (see
+   osqp_hip_batch_adjoint below), by the PCG route for every other handle (see osqp_hip_adjoint_last_record below for its contract and for the one
+   kind of handle that returns OSQP_FUNC_NOT_IMPLEMENTED).  compute: needs a previous osqp_solve that ended OSQP_SOLVED on the
    current data (OSQP_DATA_NOT_INITIALIZED otherwise: every data update resets the status); dx (n) = dL/dx, dy (m) = dL/dy, either may be NULL (zero).
-   It runs the adjoint kernel (osqp_hip_batch_adjoint) with a batch of one and keeps the result in the handle.  get_mat: fills the x arrays of the
+   It keeps the result in the handle.  get_mat: fills the x arrays of the
    caller's CSC structs, which carry the patterns of P's upper triangle and of A as given at setup (interface.py:558-564); get_vec: dq (n), dl, du (m).
    Both return OSQP_DATA_NOT_INITIALIZED before a successful compute.  An argument may be NULL (skipped).
    Codegen is out of scope: present so the reference binding links; returns OSQP_FUNC_NOT_IMPLEMENTED. */
@@ -309,6 +310,30 @@ OSQPInt osqp_hip_batch_adjoint_device(OSQPSolver *solver, OSQPInt nbatch, const 
                                       const OSQPFloat *u_dev, const OSQPFloat *x_dev, const OSQPFloat *y_dev, const OSQPFloat *dx_dev,
                                       const OSQPFloat *dy_dev, OSQPFloat *dP_dev, OSQPFloat *dq_dev, OSQPFloat *dA_dev, OSQPFloat *dl_dev,
                                       OSQPFloat *du_dev, OSQPFloat *arec_dev, void *stream);
+/* ADJOINT DERIVATIVES OF ONE HANDLE ON THE PCG PATH.  osqp_adjoint_derivative_compute / _get_mat / _get_vec run the batch kernel above (a batch of one)
+ * where it holds the problem.  Every other handle -- the large QPs this engine exists for, reordered handles (OSQPHipStats::reordered) included --
+ * takes the PCG route (adjoint_hip.hip): the rows are classified on the device by the rule above, in the caller's units, on the stored solution;
+ * the adjoint system, which is polish's reduced KKT matrix with the right-hand side -[dx; dy_a], is solved by the recurrence polish runs (the
+ * proximal method of multipliers at delta_eff = max(delta, OSQPHipPolicy::polish_delta_floor) with the engine's PCG kernels, from a zero start, at
+ * least 1 + polish_refine_iter steps, until the residuals stall); the result is unscaled, its residual max |g - K_a r| / max |g| is evaluated on the
+ * UNREGULARISED system in the caller's units, and dP / dA are written one thread per stored entry in the caller's CSC order.  The call leaves no trace
+ * on the handle: q, the bounds, the iterates and warm-start vectors, rho, info, solution and the launch history are restored exactly, and an
+ * osqp_solve after it gives the bits it would have given without it.
+ * Return value of osqp_adjoint_derivative_compute on this route: OSQP_NO_ERROR with residual < OSQP_HIP_ADJOINT_TOL; OSQP_LINSYS_SOLVER_INIT_ERROR
+ * when the recurrence stalled at or above it (status 3: dependent active rows -- the derivative is not defined, or was not reached) or when there are
+ * more active rows than variables (status 2); _get_mat / _get_vec then answer OSQP_DATA_NOT_INITIALIZED.
+ * NOT on this route: a handle whose PCG runs a Woodbury-corrected preconditioner (OSQPHipStats::woodbury_rows > 0; the portfolio one-launch form is
+ * one of its modes) answers OSQP_FUNC_NOT_IMPLEMENTED -- the route changes the constraint classes on the device and does not keep the correction's
+ * cached inverses and state consistent with them, as polish's host-side classification does; so does the host simulator.  osqp_hip_batch_adjoint[_device] keep their own eligibility.
+ * osqp_hip_adjoint_last_record: what the last osqp_adjoint_derivative_compute of the handle found, OSQP_HIP_ADJOINT_LAST_REC doubles
+ *   {status (0 / 2 / 3 as above; the batch kernel's own codes on its route), active rows, residual, recurrence steps (0 on the batch route),
+ *    seconds in the recurrence, seconds in the gradient kernels, seconds of the whole call, reserved};  all zero before the first call. */
+#define OSQP_HIP_ADJOINT_LAST_REC 8
+/* osqp_hip_adjoint_compute_at: osqp_adjoint_derivative_compute (either route) at a solution the CALLER holds -- x (n), y (m) of an earlier solve with the
+ * data now on the handle.  The derivative depends on (P, A, l, u, x, y) only, so no OSQP_SOLVED solve on the current data is asked for; x = y = NULL
+ * means the handle's own last solution, with that requirement.  Results through osqp_adjoint_derivative_get_mat / _get_vec as usual. */
+OSQPInt osqp_hip_adjoint_compute_at(OSQPSolver *solver, const OSQPFloat *x, const OSQPFloat *y, const OSQPFloat *dx, const OSQPFloat *dy);
+OSQPInt osqp_hip_adjoint_last_record(OSQPSolver *solver, OSQPFloat *rec);
 /* osqp_capabilities() reports what the reference's binding asks about and stays as it is; this adds OSQP_CAPABILITY_DERIVATIVES (the adjoint above). */
 OSQPInt osqp_hip_capabilities(void);
 

@@ -449,7 +449,28 @@ inline size_t batch_adjoint_lds_bytes(int n, int m, int nzA, int nzB, int bw) {
   return b <= 144 * 1024 ? b : 0;
 }
 
+// Adjoint derivatives of ONE QP on the PCG path (adjoint_hip.hip; Engine::adjoint_compute_pcg): device arrays in the engine's numbering and the
+// caller's units.  The kernels read the scaled matrices and the raw bounds of Dev and write the recurrence's data into Dev itself.
+constexpr int kAdjointPcgRec = 4;       // doubles of AdjointPcg::rec: active rows, max |g - K_a r|, max |g|, reserved
+struct AdjointPcg {
+  const double *x = nullptr, *y = nullptr, *dx = nullptr, *dy = nullptr;      // stored solution and incoming gradients (n / m); dy == nullptr: zero
+  int *code = nullptr;                  // [m] per row: 0 inactive, 1 lower-active, 2 upper-active
+  double *rx = nullptr, *ry = nullptr;  // [n], [m] solution of the adjoint system (r_y = 0 on inactive rows)
+  double *dP = nullptr, *dA = nullptr, *dl = nullptr, *du = nullptr;          // [nzP], [nzA] in the CSC order of Dev::Pi / Ai; [m], [m]
+  double *rec = nullptr;                // [kAdjointPcgRec]
+  double c = 1.0, cinv = 1.0;           // cost scaling
+  int rho_is_vec = 1;
+};
+
 namespace be {
+
+// Weak, like batch_adjoint: the host simulator has no such kernels and the driver answers OSQP_FUNC_NOT_IMPLEMENTED where the symbols are absent.
+// adjoint_load: classification of the rows (code, rec[0]) and the recurrence's data -- Dev::q = c D dx, l = u = z = -E dy on the active rows (free
+// elsewhere), ctype, x = x~ = y = 0.  adjoint_residual: from the recurrence's (Dev::x, Dev::y) to rx, ry, dl, du and rec[1..2].  adjoint_gradients:
+// dP, dA from (x, y, rx, ry).  All stream-ordered.
+void adjoint_load(Dev &d, const AdjointPcg &a) __attribute__((weak));
+void adjoint_residual(Dev &d, const AdjointPcg &a) __attribute__((weak));
+void adjoint_gradients(Dev &d, const AdjointPcg &a) __attribute__((weak));
 
 // stream == nullptr: on d.stream, synchronous; otherwise enqueued on that hipStream_t and not waited for.  Weak: the host simulator of the CPU test
 // tier has no such kernel -- the driver answers OSQP_FUNC_NOT_IMPLEMENTED where the symbol is absent.

@@ -155,6 +155,7 @@ void Engine::free_all() {
   if (bbuf_) { be::dfree(d_, bbuf_); bbuf_ = nullptr; bbuf_cap_ = 0; }
   if (bmat_) { be::dfree(d_, bmat_); bmat_ = nullptr; bmat_cap_ = 0; }
   if (abuf_) { be::dfree(d_, abuf_); abuf_ = nullptr; abuf_cap_ = 0; }
+  if (adjw_) { be::dfree(d_, adjw_); adjw_ = nullptr; adjw_cap_ = 0; }
   adj_ok_ = false;
   if (d_batch_order_) { be::dfree(d_, d_batch_order_); d_batch_order_ = nullptr; batch_order_cap_ = 0; }
   if (d_batch_iters_) { be::dfree(d_, d_batch_iters_); d_batch_iters_ = nullptr; d_batch_iters_n_ = 0; }
@@ -975,6 +976,63 @@ void Engine::admm_core(double t0, double *res) {
   stats_.cg_cap_escalations = c.escalations;
 }
 
+// The recurrence itself, shared by polish and by the adjoint derivatives of the PCG path (engine_api.cpp adjoint_compute_pcg: the same matrix,
+// another right-hand side).  The caller has put the bounds (active rows: equalities; the others: free), the constraint classes, q and the
+// starting iterates on the device, and has taken a RecurrenceSave.  Here: rho_i = 1 / delta_eff on the active rows, alpha = 1, then steps until
+// the reduced system's residuals stop improving -- at least 1 + polish_refine_iter, at most RecurrenceRule::max_steps.  Returns the steps taken; res:
+// the residual block of the last one.  RecurrenceRule says how a caller measures progress: rhs_norm -- the residuals against the right-hand side
+// (the adjoint system's b may be zero and its solution small: polish's measure, relative to the products A x and P x, has no scale there); gain --
+// a step that does not bring the error below gain * best counts as no progress, two in a row end the recurrence; max_steps.
+void Engine::recurrence_save(RecurrenceSave &s) const {
+  s.stats = stats_; s.rho = rho_bar_; s.alpha = d_.alpha; s.eq_from_cnt = d_.eq_from_cnt; s.eq_factor = d_.rho_eq_factor;
+  for (int k = 0; k < 3; k++) s.pred[k] = slot_pred_[k];
+}
+
+int Engine::run_recurrence(const RecurrenceRule &rule, double *res) {
+  const bool rhs_norm = rule.rhs_norm;
+  const int kRecurrenceMaxSteps = rule.max_steps;
+  const double gain = rule.gain;
+  const double de = std::max(settings.delta, pol_.polish_delta_floor);
+  d_.rho_eq_factor = 1.0; d_.eq_from_cnt = 0;       // rho_i = rho_bar = 1 / delta_eff on the active rows
+  rho_bar_ = clamp_rho(1.0 / de);
+  be::set_rho(d_, rho_bar_);
+  be::precond(d_, settings.cg_precond == OSQP_DIAGONAL_PRECONDITIONER);
+  be::init_iterates(d_, 0);
+  d_.alpha = 1.0; drop_graphs();                    // (no relaxation: the refinement recurrence; alpha is baked into captured launches)
+  int flags[F_COUNT];
+  double best = std::numeric_limits<double>::infinity();
+  int worse = 0, steps = 0;
+  const int min_steps = 1 + std::max(0, settings.polish_refine_iter);
+  for (int s = 0; s < kRecurrenceMaxSteps; s++) {
+    be::set_pcg_tol(d_, pol_.polish_pcg_tol, 1e-15);  // ||r|| <= polish_pcg_tol ||rhs||
+    exec_chunk_sync(1, kMaxCg, true, 1, res, flags);
+    steps = s + 1;
+    // residuals of the reduced KKT system: Aa x - ba (active rows) and P x + q + Aa' ya, in the scaled space
+    const double err = rhs_norm ? std::max(res[R_PRI_S], res[R_DUA_S]) / (std::max(res[R_QN_S], res[R_Z_S]) + 1e-30)
+                                : std::max(res[R_PRI_S] / (std::max(res[R_AX_S], res[R_Z_S]) + 1e-30),
+                                           res[R_DUA_S] / (std::max(std::max(res[R_ATY_S], res[R_PX_S]), res[R_QN_S]) + 1e-30));
+    if (!(err < gain * best)) worse++; else worse = 0;
+    best = std::min(best, err);
+    if (s + 1 >= min_steps && (err < 1e-13 || worse >= 2)) break;
+  }
+  return steps;
+}
+
+// what the recurrence's launches changed on the host side: alpha (and the graphs captured with it), the slot predictions, the statistics
+void Engine::recurrence_restore_launch(const RecurrenceSave &s) {
+  d_.alpha = s.alpha; drop_graphs();
+  for (int k = 0; k < 3; k++) slot_pred_[k] = s.pred[k];
+  stats_ = s.stats;
+}
+
+// the solve's weights back on the device (the caller has restored the bounds and classes they are derived from)
+void Engine::recurrence_restore_rho(const RecurrenceSave &s) {
+  rho_bar_ = s.rho; settings.rho = s.rho;
+  d_.eq_from_cnt = s.eq_from_cnt; if (s.eq_from_cnt) d_.rho_eq_factor = s.eq_factor;
+  be::set_rho(d_, rho_bar_);
+  be::precond(d_, settings.cg_precond == OSQP_DIAGONAL_PRECONDITIONER);
+}
+
 // Solution polish (_osqp.py:1710-1828) on the multi-kernel (PCG) path.  The reference guesses the active constraints from (z, y)
 // (:1719-1720), solves the reduced KKT system of the equality-constrained QP on that active set
 //     [ P   Aa' ] [x ]   [ -q ]
@@ -996,7 +1054,6 @@ void Engine::admm_core(double t0, double *res) {
 //     (tests/test_gpu_polish.py compares with the oracle's polish, pinned to the reference, to 1e-8);
 //   * the proximal term uses sigma (already on B's diagonal) in place of delta: any positive weight has the same fixed point.
 void Engine::polish() {
-  constexpr int kPolishMaxSteps = 30;
   const double tp = now_s();
   ensure_host_vectors();
   const bool unsc = settings.scaling && !settings.scaled_termination;
@@ -1005,10 +1062,9 @@ void Engine::polish() {
   be::d2h(d_, y.data(), d_.y, sizeof(double) * m);
   // keep the ADMM result
   const OSQPInfo info0 = info;
-  const OSQPHipStats stats0 = stats_;
-  const double rho0 = rho_bar_, alpha0 = d_.alpha;
-  const int eq_from_cnt0 = d_.eq_from_cnt; const double eq_factor0 = d_.rho_eq_factor;
-  const double pred0[3] = {slot_pred_[0], slot_pred_[1], slot_pred_[2]};
+  RecurrenceSave keep;
+  recurrence_save(keep);
+  const double rho0 = keep.rho;
   const std::vector<double> ls0 = ls_, us0 = us_, y0 = y, z0 = z;
   std::vector<double> hx(n);
   be::d2h(d_, hx.data(), d_.x, sizeof(double) * n);
@@ -1020,37 +1076,13 @@ void Engine::polish() {
     else if (upp) { lp[i] = up[i] = us0[i]; z[i] = us0[i]; }
     else { lp[i] = -OSQP_INFTY; up[i] = OSQP_INFTY; y[i] = 0.0; }
   }
-  auto restore = [&]() {
-    d_.alpha = alpha0; drop_graphs();
-    for (int k = 0; k < 3; k++) slot_pred_[k] = pred0[k];
-    stats_ = stats0;
-  };
+  auto restore = [&]() { recurrence_restore_launch(keep); };
   double res[R_COUNT];
   try {
     apply_scaled_bounds(lp, up);                      // active rows: equalities at their bound; the others: loose (rho = 1e-6, y = 0)
     be::h2d(d_, d_.z, z.data(), sizeof(double) * m);
     be::h2d(d_, d_.y, y.data(), sizeof(double) * m);
-    const double de = std::max(settings.delta, pol_.polish_delta_floor);
-    d_.rho_eq_factor = 1.0; d_.eq_from_cnt = 0;       // rho_i = rho_bar = 1 / delta_eff on the active rows
-    rho_bar_ = clamp_rho(1.0 / de);
-    be::set_rho(d_, rho_bar_);
-    be::precond(d_, settings.cg_precond == OSQP_DIAGONAL_PRECONDITIONER);
-    be::init_iterates(d_, 0);
-    d_.alpha = 1.0; drop_graphs();                    // (no relaxation: the refinement recurrence; alpha is baked into captured launches)
-    int flags[F_COUNT];
-    double best = std::numeric_limits<double>::infinity();
-    int worse = 0;
-    const int min_steps = 1 + std::max(0, settings.polish_refine_iter);
-    for (int s = 0; s < kPolishMaxSteps; s++) {
-      be::set_pcg_tol(d_, pol_.polish_pcg_tol, 1e-15);  // ||r|| <= polish_pcg_tol ||rhs||
-      exec_chunk_sync(1, kMaxCg, true, 1, res, flags);
-      // residuals of the reduced KKT system: Aa x - ba (active rows) and P x + q + Aa' ya, in the scaled space
-      const double err = std::max(res[R_PRI_S] / (std::max(res[R_AX_S], res[R_Z_S]) + 1e-30),
-                                  res[R_DUA_S] / (std::max(std::max(res[R_ATY_S], res[R_PX_S]), res[R_QN_S]) + 1e-30));
-      if (!(err < 0.5 * best)) worse++; else worse = 0;
-      best = std::min(best, err);
-      if (s + 1 >= min_steps && (err < 1e-13 || worse >= 2)) break;
-    }
+    run_recurrence(RecurrenceRule{false, 0.5, 30}, res);      // (a correction of the ADMM solution: a step that does not halve the error is no progress)
   } catch (...) {                       // a device failure mid-polish must not leave the polish's weights / bounds on the handle
     restore();
     info = info0; rho_bar_ = rho0; settings.rho = rho0; ls_ = ls0; us_ = us0;
@@ -1069,10 +1101,7 @@ void Engine::polish() {
   const double pol_obj = (0.5 * res[R_XPX] + res[R_QX]) * (settings.scaling ? cinv_ : 1.0);
   const bool ok = (pol_pri < info0.prim_res && pol_dua < info0.dual_res) || (pol_pri < info0.prim_res && info0.dual_res < 1e-10) ||
                   (pol_dua < info0.dual_res && info0.prim_res < 1e-10);                 // :1786-1793
-  rho_bar_ = rho0; settings.rho = rho0;
-  d_.eq_from_cnt = eq_from_cnt0; if (eq_from_cnt0) d_.rho_eq_factor = eq_factor0;
-  be::set_rho(d_, rho_bar_);
-  be::precond(d_, settings.cg_precond == OSQP_DIAGONAL_PRECONDITIONER);
+  recurrence_restore_rho(keep);
   if (ok) {
     info.obj_val = pol_obj; info.prim_res = pol_pri; info.dual_res = pol_dua; info.status_polish = 1;       // :1797-1807
     update_gap_info(res, -1.0);

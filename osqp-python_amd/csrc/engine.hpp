@@ -67,6 +67,8 @@ class Engine {
   int adjoint_compute(const double *dx, const double *dy);
   int adjoint_get_mat(OSQPCscMatrix *dP, OSQPCscMatrix *dA);
   int adjoint_get_vec(double *dq, double *dl, double *du);
+  int adjoint_last_record(double *rec) const;
+  int adjoint_compute_at(const double *x, const double *y, const double *dx, const double *dy);
   int attach_batch_matrices(BatchParams &p, const double *Px_dev, const double *Ax_dev, void *stream);      // per-problem matrices: scratch + be::batch_prepare
   void fill_batch_params(BatchParams &p, int nbatch, int warm);
   // LinSysSolver slot (include/osqp_hip.h): this Engine instance is then used ONLY as the reduced-KKT solver
@@ -122,6 +124,11 @@ class Engine {
   bool adjoint_applicable();                          // the problem fits k_batch_adjoint (the forward's direct variant + the adjoint's own LDS)
   void fill_adjoint_params(AdjointParams &p, int nbatch);
   std::vector<double> adj_dP_, adj_dA_, adj_dq_, adj_dl_, adj_du_; bool adj_ok_ = false;      // result of the last adjoint_compute
+  // the PCG path's adjoint (adjoint_hip.hip): where the batch kernel does not hold the problem
+  bool adjoint_pcg_applicable() const;
+  int adjoint_compute_pcg(const double *x, const double *y, const double *dx, const double *dy);
+  double *adjw_ = nullptr; size_t adjw_cap_ = 0;      // its device scratch (saved state, inputs, results), kept across calls
+  double adj_rec_[OSQP_HIP_ADJOINT_LAST_REC] = {0, 0, 0, 0, 0, 0, 0, 0};      // record of the last adjoint_compute (include/osqp_hip.h osqp_hip_adjoint_last_record)
   int *d_batch_iters_ = nullptr; int d_batch_iters_n_ = 0;      // device-pointer path: iteration counts of the previous call (its records never reach the host)
   std::vector<int> batch_order_; int *d_batch_order_ = nullptr; size_t batch_order_cap_ = 0;   // problems by descending iteration count of the previous batch call
   double *ckpt_ = nullptr;                            // device copy of (x, x~, z, y) taken before a solve's first chunk (cg cap escalation)
@@ -228,6 +235,13 @@ class Engine {
   void run_group(int diagonal);
   std::vector<int> feed_hist_;          // slot launches per chunk of the previous device-driven solve (Ctl::hist; index = boundaries processed when the chunk began)
   void polish();
+  // the proximal-method-of-multipliers recurrence polish runs, shared with the adjoint derivatives of the PCG path (engine.cpp run_recurrence)
+  struct RecurrenceSave { OSQPHipStats stats; double rho, alpha, eq_factor; int eq_from_cnt; double pred[3]; };
+  void recurrence_save(RecurrenceSave &s) const;
+  struct RecurrenceRule { bool rhs_norm; double gain; int max_steps; };
+  int run_recurrence(const RecurrenceRule &rule, double *res);
+  void recurrence_restore_launch(const RecurrenceSave &s);
+  void recurrence_restore_rho(const RecurrenceSave &s);
   void apply_scaled_bounds(const std::vector<double> &ls, const std::vector<double> &us);
   void drop_graphs();
   // Captured launches take Dev BY VALUE: its scalar fields (theta, alpha, sigma, the equality-weight rule k_set_rho reads) are frozen into

@@ -871,8 +871,8 @@ int Engine::batch_solve_device(int nbatch, const double *q, const double *l, con
 
 // ------------------------------------------------------------------------------------------------ adjoint derivatives
 // The backward pass of the batch path (batch_hip.hip k_batch_adjoint).  A problem is eligible when the forward's direct variant holds it (banded factor
-// under the engine's ordering: prepare_batch_direct) and the adjoint kernel's own LDS fits; everything else -- large single QPs on the PCG path, the
-// host simulator -- answers OSQP_FUNC_NOT_IMPLEMENTED.
+// under the engine's ordering: prepare_batch_direct) and the adjoint kernel's own LDS fits; the batch entry points answer OSQP_FUNC_NOT_IMPLEMENTED for
+// everything else.  osqp_adjoint_derivative_compute goes on to the PCG route for a single handle (adjoint_compute_pcg below).
 bool Engine::adjoint_applicable() {
   if (!be::batch_adjoint || !be::device_assembly() || !be::device_vec_updates() || reordered_ || !be::batch_lds_bytes(n, m)) return false;
   prepare_batch_direct();
@@ -934,29 +934,159 @@ int Engine::batch_adjoint_device(int nbatch, const double *Px, const double *Ax,
   return err;
 }
 
+// The PCG path's adjoint (adjoint_hip.hip) holds every handle whose solve runs the multi-kernel PCG form with a Jacobi-family preconditioner.  A handle
+// with a Woodbury-corrected preconditioner (dense rows; the portfolio one-launch form is one of its modes) is left out.  polish runs the same
+// recurrence there, but through the host classification (classify_constraints), which also invalidates the cached Woodbury inverses when the
+// classes change; this route changes the classes on the device, past that bookkeeping, and saves / restores none of DevWb's state.  Not built, not
+// measured: OSQP_FUNC_NOT_IMPLEMENTED.
+bool Engine::adjoint_pcg_applicable() const {
+  return be::adjoint_load && be::adjoint_residual && be::adjoint_gradients && be::device_assembly() && be::device_vec_updates() && !d_.wb.on;
+}
+
 // osqp_adjoint_derivative_compute: needs the solution of a solve that ended OSQP_SOLVED on the current data (every data update resets the status);
-// OSQP_DATA_NOT_INITIALIZED otherwise.
-int Engine::adjoint_compute(const double *dx, const double *dy) {
+// OSQP_DATA_NOT_INITIALIZED otherwise.  The batch kernel where it holds the problem, the PCG route otherwise.
+int Engine::adjoint_compute(const double *dx, const double *dy) { return adjoint_compute_at(nullptr, nullptr, dx, dy); }
+
+// The same at a solution the CALLER holds (x, y in the caller's numbering; nullptr: the handle's last solution, which then has to be OSQP_SOLVED on
+// the current data): the derivative is a function of (P, A, l, u, x, y) alone, so a caller that kept (x, y) of an earlier solve -- the torch layer's
+// backward, one element after the other on one handle -- needs the data on the handle, not another solve.
+int Engine::adjoint_compute_at(const double *x, const double *y, const double *dx, const double *dy) {
   if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   adj_ok_ = false;
+  for (double &v : adj_rec_) v = 0.0;
   be::activate(d_);
-  if (!adjoint_applicable()) return OSQP_FUNC_NOT_IMPLEMENTED;
-  if (info.status_val != OSQP_SOLVED) return OSQP_DATA_NOT_INITIALIZED;
+  const bool batch = adjoint_applicable();
+  if (!batch && !adjoint_pcg_applicable()) return OSQP_FUNC_NOT_IMPLEMENTED;
+  if (!x != !y && m > 0) return OSQP_DATA_VALIDATION_ERROR;
+  if (!x) { if (info.status_val != OSQP_SOLVED) return OSQP_DATA_NOT_INITIALIZED; x = sol_x_.data(); y = sol_y_.data(); }
   std::vector<double> zero;
   if (!dx) { zero.assign(n, 0.0); dx = zero.data(); }
   adj_dP_.assign(P_.nnz(), 0.0); adj_dA_.assign(A_.nnz(), 0.0); adj_dq_.assign(n, 0.0); adj_dl_.assign(m, 0.0); adj_du_.assign(m, 0.0);
+  if (!batch) return adjoint_compute_pcg(x, y, dx, m > 0 ? dy : nullptr);
   std::vector<double> yv(std::max(m, 1), 0.0);
-  std::copy(sol_y_.begin(), sol_y_.begin() + m, yv.begin());
-  const int err = batch_adjoint(1, nullptr, nullptr, nullptr, nullptr, sol_x_.data(), yv.data(), dx, m > 0 ? dy : nullptr,
+  if (m > 0) std::copy(y, y + m, yv.begin());
+  double arec[kAdjointRec] = {0, 0, 0, 0};
+  const int err = batch_adjoint(1, nullptr, nullptr, nullptr, nullptr, x, yv.data(), dx, m > 0 ? dy : nullptr,
                                 adj_dP_.empty() ? nullptr : adj_dP_.data(), adj_dq_.data(), adj_dA_.empty() ? nullptr : adj_dA_.data(),
-                                m > 0 ? adj_dl_.data() : nullptr, m > 0 ? adj_du_.data() : nullptr, nullptr);
+                                m > 0 ? adj_dl_.data() : nullptr, m > 0 ? adj_du_.data() : nullptr, arec);
   adj_ok_ = err == OSQP_NO_ERROR;
+  for (int k = 0; k < 3; k++) adj_rec_[k] = arec[k];
   return err;
+}
+
+// The PCG route: classify the rows on the device, load q~ = c D dx and the bounds b~ = -E dy of the active rows, run polish's recurrence from a
+// zero start, unscale, evaluate the unregularised residual, run the gradient kernels.  Everything the recurrence touches -- q, the bounds and
+// classes, the iterates and the PCG's starting vectors, rho, alpha, the predictions and statistics -- is saved first and put back bit for bit: a
+// solve after this call runs as if the call had not been made.  info, solution and the history feed are never written.
+int Engine::adjoint_compute_pcg(const double *x, const double *y, const double *dx, const double *dy) {
+  const double t_begin = now_s();
+  be::ext_wait(d_);
+  const size_t N = (size_t)n, M = (size_t)m, NP = (size_t)d_.nzP, NA = (size_t)d_.nzA, MI = (M + 1) / 2;      // MI: doubles that hold m ints
+  // one device block, kept for the next call: saved state | inputs | work | results
+  const size_t need = 6 * N + 9 * M + MI + 2 * N + 2 * M + N + M + MI + NP + NA + 2 * M + kAdjointPcgRec;
+  if (need > adjw_cap_) { if (adjw_) be::dfree(d_, adjw_); adjw_cap_ = 0; adjw_ = dev_vec<double>(d_, need); adjw_cap_ = need; }
+  double *p = adjw_;
+  auto take = [&p](size_t cnt) { double *r = p; p += cnt; return r; };
+  struct Kept { double *dev, *copy; size_t bytes; };
+  std::vector<Kept> kept;
+  for (double *v : {d_.x, d_.xs, d_.xg, d_.xsp, d_.dx, d_.q}) kept.push_back({v, take(N), sizeof(double) * N});
+  for (double *v : {d_.z, d_.y, d_.zt, d_.ztg, d_.t0, d_.v, d_.dy, d_.l, d_.u}) kept.push_back({v, take(M), sizeof(double) * M});
+  kept.push_back({reinterpret_cast<double *>(d_.ctype), take(MI), sizeof(int) * M});
+  double *i_x = take(N), *i_dx = take(N), *i_y = take(M), *i_dy = take(M);
+  double *w_rx = take(N), *w_ry = take(M); int *w_code = reinterpret_cast<int *>(take(MI));
+  double *o_dP = take(NP), *o_dA = take(NA), *o_dl = take(M), *o_du = take(M), *o_rec = take(kAdjointPcgRec);
+  for (const Kept &k : kept) be::copy_in(d_, k.copy, k.dev, k.bytes, 1);
+  // the stored solution and the incoming gradients, in the engine's numbering
+  {
+    std::vector<double> t;
+    auto up_n = [&](double *dst, const double *src) { if (reordered_) { t = to_internal_n(src); src = t.data(); } be::h2d(d_, dst, src, sizeof(double) * N); };
+    auto up_m = [&](double *dst, const double *src) { if (!M) return; if (reordered_) { t = to_internal_m(src); src = t.data(); } be::h2d(d_, dst, src, sizeof(double) * M); };
+    up_n(i_x, x); up_n(i_dx, dx); up_m(i_y, y); if (dy) up_m(i_dy, dy);
+  }
+  AdjointPcg a;
+  a.x = i_x; a.y = i_y; a.dx = i_dx; a.dy = dy ? i_dy : nullptr; a.code = w_code; a.rx = w_rx; a.ry = w_ry;
+  a.dP = o_dP; a.dA = o_dA; a.dl = o_dl; a.du = o_du; a.rec = o_rec; a.c = c_; a.cinv = cinv_; a.rho_is_vec = settings.rho_is_vec;
+  const OSQPInfo info0 = info;
+  RecurrenceSave keep;
+  recurrence_save(keep);
+  auto put_back = [&]() {
+    recurrence_restore_launch(keep);
+    for (const Kept &k : kept) if (k.dev == d_.l || k.dev == d_.u || k.dev == reinterpret_cast<double *>(d_.ctype)) be::copy_in(d_, k.dev, k.copy, k.bytes, 1);
+    d_.rho_eq_factor = keep.eq_factor;
+    recurrence_restore_rho(keep);                   // rho, the preconditioner (and K's values) from the solve's classes again ...
+    for (const Kept &k : kept) be::copy_in(d_, k.dev, k.copy, k.bytes, 1);      // ... then every vector as the solve left it (set_rho rewrites v, t0 and the PCG's start)
+    info = info0;
+    be::sync(d_);
+  };
+  double rec[kAdjointPcgRec] = {0, 0, 0, 0};
+  int steps = 0;
+  double t_rec = 0, t_grad = 0;
+  bool singular = false;
+  try {
+    be::adjoint_load(d_, a);
+    be::d2h(d_, rec, o_rec, sizeof(double));
+    singular = rec[0] > (double)n;                  // more active rows than variables: K_a is singular, nothing to iterate on
+    if (!singular) {
+      double res[R_COUNT];
+      const double t0 = now_s();
+      // from a zero start the recurrence has to converge, not correct: it ends when two steps in a row gain less than 10 %, within twice polish's
+      // cap (under polish's rule the n = 100k banded QP with a random dy ended at 3.2e-5 after 12 steps; with this one at 5.4e-10 after 23:
+      // DESIGN.md section 6)
+      steps = run_recurrence(RecurrenceRule{true, 0.9, 60}, res);
+      t_rec = now_s() - t0;
+      be::adjoint_residual(d_, a);
+      be::sync(d_);
+      const double t1 = now_s();
+      be::adjoint_gradients(d_, a);
+      be::sync(d_);
+      t_grad = now_s() - t1;
+      be::d2h(d_, rec, o_rec, sizeof(double) * kAdjointPcgRec);
+    }
+  } catch (...) {
+    put_back();
+    throw;
+  }
+  const double resid = singular ? INFINITY : (rec[2] > 0.0 ? rec[1] / rec[2] : (rec[1] > 0.0 ? INFINITY : 0.0));
+  const int status = singular ? 2 : (resid < kAdjointTol ? 0 : 3);
+  if (status == 0) {
+    std::vector<double> t;
+    auto down = [&](std::vector<double> &dst, const double *src, const std::vector<int> *perm) {      // perm: engine position -> caller's
+      if (dst.empty()) return;
+      if (!perm) { be::d2h(d_, dst.data(), src, sizeof(double) * dst.size()); return; }
+      t.resize(dst.size());
+      be::d2h(d_, t.data(), src, sizeof(double) * dst.size());
+      for (size_t k = 0; k < dst.size(); k++) dst[(*perm)[k]] = t[k];
+    };
+    const bool ro = reordered_;
+    down(adj_dq_, w_rx, ro ? &pc_ : nullptr); down(adj_dl_, o_dl, ro ? &pr_ : nullptr); down(adj_du_, o_du, ro ? &pr_ : nullptr);
+    if (!ro) { down(adj_dP_, o_dP, nullptr); down(adj_dA_, o_dA, nullptr); }
+    else {                                          // PvalMap_ / AvalMap_: caller's position -> the engine's
+      auto gather = [&](std::vector<double> &dst, const double *src, const std::vector<int> &map) {
+        if (dst.empty()) return;
+        t.resize(dst.size());
+        be::d2h(d_, t.data(), src, sizeof(double) * dst.size());
+        for (size_t k = 0; k < dst.size(); k++) dst[k] = t[map[k]];
+      };
+      gather(adj_dP_, o_dP, PvalMap_); gather(adj_dA_, o_dA, AvalMap_);
+    }
+  }
+  put_back();
+  adj_rec_[0] = status; adj_rec_[1] = rec[0]; adj_rec_[2] = resid; adj_rec_[3] = steps;
+  adj_rec_[4] = t_rec; adj_rec_[5] = t_grad; adj_rec_[6] = now_s() - t_begin;
+  adj_ok_ = status == 0;
+  return adj_ok_ ? OSQP_NO_ERROR : OSQP_LINSYS_SOLVER_INIT_ERROR;
+}
+
+int Engine::adjoint_last_record(double *rec) const {
+  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (!rec) return OSQP_DATA_VALIDATION_ERROR;
+  std::copy(adj_rec_, adj_rec_ + OSQP_HIP_ADJOINT_LAST_REC, rec);
+  return OSQP_NO_ERROR;
 }
 
 int Engine::adjoint_get_mat(OSQPCscMatrix *dP, OSQPCscMatrix *dA) {
   if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  if (!adj_ok_) return adjoint_applicable() ? OSQP_DATA_NOT_INITIALIZED : OSQP_FUNC_NOT_IMPLEMENTED;
+  if (!adj_ok_) return (adjoint_applicable() || adjoint_pcg_applicable()) ? OSQP_DATA_NOT_INITIALIZED : OSQP_FUNC_NOT_IMPLEMENTED;
   // the caller passes the patterns of P's upper triangle and of A as given at setup; the values arrive in that order
   if (dP) { if (!dP->x || dP->n != n || !dP->p || dP->p[n] != P_.nnz()) return OSQP_DATA_VALIDATION_ERROR; std::copy(adj_dP_.begin(), adj_dP_.end(), dP->x); }
   if (dA) { if (!dA->x || dA->n != n || dA->m != m || !dA->p || dA->p[n] != A_.nnz()) return OSQP_DATA_VALIDATION_ERROR; std::copy(adj_dA_.begin(), adj_dA_.end(), dA->x); }
@@ -965,7 +1095,7 @@ int Engine::adjoint_get_mat(OSQPCscMatrix *dP, OSQPCscMatrix *dA) {
 
 int Engine::adjoint_get_vec(double *dq, double *dl, double *du) {
   if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  if (!adj_ok_) return adjoint_applicable() ? OSQP_DATA_NOT_INITIALIZED : OSQP_FUNC_NOT_IMPLEMENTED;
+  if (!adj_ok_) return (adjoint_applicable() || adjoint_pcg_applicable()) ? OSQP_DATA_NOT_INITIALIZED : OSQP_FUNC_NOT_IMPLEMENTED;
   if (dq) std::copy(adj_dq_.begin(), adj_dq_.end(), dq);
   if (dl) std::copy(adj_dl_.begin(), adj_dl_.end(), dl);
   if (du) std::copy(adj_du_.begin(), adj_du_.end(), du);

@@ -66,6 +66,9 @@ for _e in (osqp_linsys_solver_type, osqp_status_type, osqp_precond_type):
     globals().update(_e.__members__)
 
 
+OSQP_HIP_ADJOINT_TOL = 1e-6      # include/osqp_hip.h: an adjoint residual below this is status 0
+
+
 def _ptr(a, typ):
     return None if a is None else a.ctypes.data_as(typ)
 
@@ -228,6 +231,29 @@ class OSQPSolver:
             if a is not None and a.size != k:
                 raise ValueError('%s: expected %d entries, got %d' % (name, k, a.size))
         return self._lib.osqp_adjoint_derivative_compute(self._p, _ptr(dx, _lib.c_double_p), _ptr(dy, _lib.c_double_p))
+
+    def adjoint_derivative_compute_at(self, x, y, dx, dy=None):
+        """osqp_hip_adjoint_compute_at: the adjoint at a solution (x, y) the caller kept, with the data now on the handle; returns the error code."""
+        x, y, dx, dy = _vec(x), _vec(y), _vec(dx), _vec(dy)
+        for a, k, name in ((x, self.n, 'x'), (y, self.m, 'y'), (dx, self.n, 'dx'), (dy, self.m, 'dy')):
+            if a is not None and a.size != k:
+                raise ValueError('%s: expected %d entries, got %d' % (name, k, a.size))
+        dp = _lib.c_double_p
+        return self._lib.osqp_hip_adjoint_compute_at(self._p, _ptr(x, dp), _ptr(y, dp), _ptr(dx, dp), _ptr(dy, dp))
+
+    # OSQP_HIP_ADJOINT_LAST_REC doubles of osqp_hip_adjoint_last_record
+    ADJOINT_LAST_FIELDS = ('status', 'active_rows', 'residual', 'steps', 'recurrence_s', 'gradient_s', 'total_s', 'reserved')
+
+    def adjoint_last_record(self):
+        """osqp_hip_adjoint_last_record as a dict (ADJOINT_LAST_FIELDS): what the last adjoint_derivative_compute of this handle found."""
+        rec = np.zeros(len(self.ADJOINT_LAST_FIELDS))
+        st = self._lib.osqp_hip_adjoint_last_record(self._p, _ptr(rec, _lib.c_double_p))
+        if st:
+            raise ValueError(str(int(st)))
+        out = dict(zip(self.ADJOINT_LAST_FIELDS, rec.tolist()))
+        for k in ('status', 'active_rows', 'steps'):
+            out[k] = int(out[k])
+        return out
 
     def adjoint_derivative_get_mat(self, dP, dA):
         """dP, dA: CSC objects carrying the patterns of P's upper triangle and of A; their x arrays are filled."""

@@ -5,8 +5,8 @@ update_settings / warm_start``, the module helpers and the two status enums; /ro
 :120-434).  Names, keyword arguments, exception types and the numeric error mapping are the reference's -- they are what
 ``tests/test_reference_suite.py::test_frontend_contract`` pins -- the implementation is this repository's own: one
 normalisation pipeline for the problem data, one table for the settings that are not plain ``OSQPSettings`` fields.
-``adjoint_derivative_compute / _get_mat / _get_vec`` (reference interface.py:519-598) run the engine's adjoint kernel for problems the batch
-kernel's direct variant holds; code generation is out of scope and says so when called.
+``adjoint_derivative_compute / _get_mat / _get_vec`` (reference interface.py:519-598) run the engine's adjoint kernels: the batch kernel
+for problems its direct variant holds, the PCG route for every other handle; code generation is out of scope and says so when called.
 """
 import functools
 import importlib as _importlib
@@ -290,17 +290,27 @@ class OSQP:
 
     def _adjoint_status(self, status):
         if status == SolverError.OSQP_FUNC_NOT_IMPLEMENTED:
-            raise NotImplementedError('adjoint derivatives exist for problems the batch kernel\'s direct variant holds (one workgroup\'s LDS, '
-                                      'permuted half bandwidth <= 56); this problem takes the PCG path')
+            raise NotImplementedError('adjoint derivatives are not available on this handle: its PCG runs a Woodbury-corrected preconditioner '
+                                      '(dense rows), which neither the batch kernel nor the PCG route of the adjoint holds -- or the backend has no adjoint kernels')
         if status:
             raise OSQPException(int(status))
+
+    def adjoint_last_record(self):
+        """What the last adjoint_derivative_compute found: dict(status, active_rows, residual, steps, recurrence_s, gradient_s, total_s, reserved)."""
+        return self._solver.adjoint_last_record()
 
     def adjoint_derivative_compute(self, dx=None, dy=None):
         """Adjoint derivatives of the last solution with respect to the problem data, for incoming gradients dx = dL/dx (n) and dy = dL/dy (m)
         (None: zero).  Needs a solve() that ended OSQP_SOLVED on the current data; results through adjoint_derivative_get_mat / _get_vec."""
         self._solved_or_raise()
         dy = np.zeros(self.m) if dy is None else dy
-        self._adjoint_status(self._solver.adjoint_derivative_compute(dx, dy))
+        status = self._solver.adjoint_derivative_compute(dx, dy)
+        rec = self._solver.adjoint_last_record() if status == SolverError.OSQP_LINSYS_SOLVER_INIT_ERROR and hasattr(self._solver, 'adjoint_last_record') else None
+        if rec is not None and rec['status'] in (2, 3):
+            raise ArithmeticError('adjoint derivatives: the adjoint system of the active set was not solved (status %d, %d active rows, residual %.3e after %d '
+                                  'recurrence steps; the threshold is %g): dependent active rows or more active rows than variables -- the derivative is not defined there'
+                                  % (rec['status'], rec['active_rows'], rec['residual'], rec['steps'], self.ext.OSQP_HIP_ADJOINT_TOL))
+        self._adjoint_status(status)
 
     def adjoint_derivative_get_mat(self, as_dense=True, dP_as_triu=True):
         """(dP, dA) after adjoint_derivative_compute: gradients at the stored entries of P (its upper triangle, or -- dP_as_triu=False -- mirrored

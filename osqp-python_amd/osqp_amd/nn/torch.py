@@ -23,7 +23,9 @@ them) on the solution and duals the forward kept, and returns (dP, dq, dA, dl, d
 the sum over the batch, as autograd's ``expand`` would give.  dP holds, for every entry of P_val (the full symmetric pattern P_idx), the value
 (r_i x_j + r_j x_i) / 2 of its position -- the same in either triangle.  Gradients arriving on the GPU go through the device-pointer entry point
 on torch's current stream, zero-copy.  ``last_adjoint_rec`` keeps the kernel's record per element (status, active rows, residual).  A problem the
-batch kernel cannot hold, and a ``torch.distributed`` job (world size > 1), raise NotImplementedError in backward.  With no input requiring grad,
+batch kernel cannot hold (its forward ran one element after the other on the handle) is differentiated the same way: the single-handle adjoint
+(``osqp_hip_adjoint_compute_at``: the PCG route for large QPs, at the (x, y) the forward kept) once per element, ``adjoint_launches`` counting every call, shared inputs receiving
+the batch sum.  A ``torch.distributed`` job (world size > 1) raises NotImplementedError in backward.  With no input requiring grad,
 forward behaves exactly as before.
 """
 import numpy as np
@@ -59,7 +61,7 @@ class OSQP(Module):
         self._triu_pick = None       # positions of the upper-triangle entries of P inside P_val
         self.setup_count = 0         # number of osqp_setup calls made by this layer (1 after any number of same-structure forwards)
         self.last_dual = None
-        self.adjoint_launches = 0    # launches of the adjoint kernel made by this layer's backward passes (one per backward)
+        self.adjoint_launches = 0    # launches of the adjoint kernel made by this layer's backward passes (one per backward; one per element where the batch kernel does not hold the problem)
         self.last_adjoint_rec = None # (nb, 4) record of the last backward: status, active rows, residual, reserved (ext_hip ADJOINT_FIELDS)
         self._grad_maps = None
 
@@ -194,7 +196,7 @@ class OSQP(Module):
     def _loop(self, Pn, qn, An, ln, un, nb, batched, dev_index=0):
         """Per-element matrices (or a problem too large for the batch kernel): the single-QP engine, one element after the
         other on the persistent handle -- update(Px, Ax, q, l, u) + solve(), as nn/torch.py:136-157."""
-        x = np.zeros((nb, self.n)); rec = np.zeros((nb, 8))
+        x = np.zeros((nb, self.n)); y = np.zeros((nb, self.m)); rec = np.zeros((nb, 8))
         for i in range(nb):
             Pv = Pn[i] if batched[0] else Pn
             Av = An[i] if batched[2] else An
@@ -202,7 +204,9 @@ class OSQP(Module):
             s.update(q=qn[i], l=ln[i], u=un[i])
             r = s.solve()
             x[i] = r.x
+            y[i] = r.y
             rec[i, 0], rec[i, 1], rec[i, 2] = r.info.status_val, r.info.iter, r.info.obj_val
+        self.last_dual = y
         return x, rec
 
     # ------------------------------------------------------------------ backward
@@ -215,6 +219,36 @@ class OSQP(Module):
             self._grad_maps = np.array([where[(int(tr[k]), int(tc[k]))] for k in range(nP)], dtype=np.int64)
         return self._grad_maps
 
+    def _backward_loop(self, Pn, An, ln, un, X, Y, g, nb, batched, want):
+        """Backward of a batch the batch adjoint kernel does not hold (the forward's _loop): the single-handle adjoint (the PCG route for large QPs)
+        once per element at the (x, y) the forward kept -- osqp_hip_adjoint_compute_at: the element's matrices and bounds go onto the handle, no
+        solve is repeated.  Every call is counted in adjoint_launches."""
+        widths = {'dP': len(self._triu_pick), 'dq': self.n, 'dA': An.shape[-1], 'dl': self.m, 'du': self.m}
+        res = {k: np.zeros((nb, widths[k])) for k in want}
+        res['rec'] = np.zeros((nb, 4))
+        NI = int(osqp_amd.SolverError.OSQP_FUNC_NOT_IMPLEMENTED)
+        for i in range(nb):
+            s = self._handle(Pn[i] if batched[0] else Pn, An[i] if batched[2] else An, None, ln[i], un[i], device=self._device)
+            s.update(l=ln[i], u=un[i])      # (leaves the last element's bounds on the handle and its status reset: every forward updates all data before it solves)
+            ext = s._solver
+            st = ext.adjoint_derivative_compute_at(X[i], Y[i], np.ascontiguousarray(g[i], dtype=float))
+            self.adjoint_launches += 1
+            rec = ext.adjoint_last_record()
+            res['rec'][i] = (rec['status'], rec['active_rows'], rec['residual'], rec['steps'])
+            if st == NI:
+                raise NotImplementedError('osqp_amd.nn.torch.OSQP: backward is not available on this handle (Woodbury-corrected preconditioner; include/osqp_hip.h)')
+            if st:
+                raise RuntimeError('adjoint derivatives of batch element %d: error %d (status %d, residual %.3e)' % (i, int(st), rec['status'], rec['residual']))
+            dP, dA = s.ext.CSC(s._derivative_cache['P'].copy()), s.ext.CSC(s._derivative_cache['A'].copy())
+            st = ext.adjoint_derivative_get_mat(dP, dA)
+            dq, dl, du = np.empty(self.n), np.zeros(self.m), np.zeros(self.m)
+            st = st or ext.adjoint_derivative_get_vec(dq, dl, du)
+            if st:
+                raise RuntimeError('adjoint derivatives of batch element %d: error %d' % (i, int(st)))
+            for k, v in (('dP', dP.x), ('dA', dA.x), ('dq', dq), ('dl', dl), ('du', du)):
+                if k in res: res[k][i] = v
+        return {k: torch.as_tensor(v) for k, v in res.items()}
+
     def _backward(self, saved, x, y, dl_dx, needs):
         P_val, q_val, A_val, l_val, u_val = saved
         params = [P_val, q_val, A_val, l_val, u_val]
@@ -223,7 +257,7 @@ class OSQP(Module):
         if _distributed()[1] > 1:
             raise NotImplementedError('osqp_amd.nn.torch.OSQP: backward in a torch.distributed job (world size > 1) is not implemented')
         if y is None:
-            raise NotImplementedError('osqp_amd.nn.torch.OSQP: backward needs the adjoint kernel, which holds problems with a banded factor in one workgroup\'s LDS (permuted half bandwidth <= 56, matrices + band <= 144 KB); this problem is outside it')
+            raise NotImplementedError('osqp_amd.nn.torch.OSQP: backward needs the duals of the forward, which this forward did not keep')
         s = self._solver
         Pn, An = _np(P_val), _np(A_val)
         # the handle's own values of a SHARED side are what the forward solved with (an intermediate forward may have replaced them)
@@ -253,11 +287,14 @@ class OSQP(Module):
                                                   l=bc(_np(l_val), self.m), u=bc(_np(u_val), self.m),
                                                   Px=Pn[:, self._triu_pick] if batched[0] else None, Ax=An if batched[2] else None, want=want)
                 res = {k: torch.as_tensor(v) for k, v in res.items()}
+            self.adjoint_launches += 1
         except ValueError as e:
             if str(e) != str(int(osqp_amd.SolverError.OSQP_FUNC_NOT_IMPLEMENTED)):
                 raise
-            raise NotImplementedError('osqp_amd.nn.torch.OSQP: backward needs the adjoint kernel, which holds problems with a banded factor in one workgroup\'s LDS (permuted half bandwidth <= 56, matrices + band <= 144 KB); this problem is outside it')
-        self.adjoint_launches += 1
+            # outside the batch kernel (the forward ran _loop): the single-handle adjoint per element
+            bc = lambda a, k: np.broadcast_to(np.asarray(a, dtype=float).reshape(-1, k), (nb, k))
+            res = self._backward_loop(Pn, An, bc(_np(l_val), self.m), bc(_np(u_val), self.m), bc(_np(torch.as_tensor(x)), self.n), bc(_np(torch.as_tensor(y)), self.m),
+                                      _np(g).reshape(nb, self.n), nb, batched, want)
         self.last_adjoint_rec = res['rec']
         if 'dP' in res:                                    # engine order (upper triangle, CSC) -> the order of P_val, either triangle the same value
             res['dP'] = res['dP'][:, torch.as_tensor(p_map, device=res['dP'].device)]

@@ -2,6 +2,7 @@
 stream, after a warm-up, over several repetitions; median and spread reported).
 
     python tools/adjoint_bench.py [--batch 4096] [--reps 20] [--warmup 5] [--out profiles/NAME.json]
+    python tools/adjoint_bench.py --single [--n 100000] [--eps 1e-8] [--reps 20] [--warmup 5] [--out profiles/NAME.json]      (see single())
 
 forward  = osqp_hip_batch_solve_device (every solve launch of the batch);  backward = osqp_hip_batch_adjoint_device (ONE launch: k_batch_adjoint)
 with all five gradients, and with dq alone (what the dP / dA stores of nbatch x (nnz(P) + nnz(A)) doubles cost).  One JSON line."""
@@ -16,14 +17,62 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, 'osqp-python_amd')]
 
 
+def single(a):
+    """--single: the backward of ONE large QP on the PCG path (BASELINE configs[1], problems.banded_qp(n)): osqp_adjoint_derivative_compute after a
+    solve at --eps, wall time per call (the call synchronises) -- median over --reps after --warmup -- with the engine's own split into the
+    recurrence and the gradient kernel (osqp_hip_adjoint_last_record), and the same handle's polish time for comparison (the same recurrence,
+    started from the solution instead of zero).  Gradient kernel traffic: per stored entry two 4-byte indices and one 8-byte store, plus the
+    gathered vectors once (3 n + 2 m doubles), against 8 TB/s."""
+    import time
+    import osqp_amd
+    import problems
+    P, q, A, l, u = problems.banded_qp(a.n, seed=12345)
+    n, m = len(q), len(l)
+    st = dict(eps_abs=a.eps, eps_rel=a.eps, verbose=False, max_iter=200000)
+    s = osqp_amd.OSQP(algebra='hip')
+    s.setup(P, q, A, l, u, **st)
+    r = s.solve()
+    assert r.info.status_val == osqp_amd.SolverStatus.OSQP_SOLVED
+    dx = r.x - 0.1 * np.random.default_rng(7).standard_normal(n)
+    tot, rec_s, grad_s = [], [], []
+    for k in range(a.warmup + a.reps):
+        t0 = time.perf_counter()
+        s.adjoint_derivative_compute(dx=dx)
+        t1 = time.perf_counter()
+        rec = s.adjoint_last_record()
+        if k >= a.warmup:
+            tot.append(t1 - t0); rec_s.append(rec['recurrence_s']); grad_s.append(rec['gradient_s'])
+    sp_ = osqp_amd.OSQP(algebra='hip')
+    sp_.setup(P, q, A, l, u, polishing=True, **st)
+    pol = [sp_.solve().info.polish_time for _ in range(3)]
+    import scipy.sparse as spa
+    nzP, nzA = spa.triu(P).nnz, A.nnz
+    gbytes = 16.0 * (nzP + nzA) + 8.0 * (3 * n + 2 * m)
+    med = lambda v: float(np.median(v))
+    line = dict(tool='adjoint_bench --single', n=n, m=m, nnzP_triu=int(nzP), nnzA=int(nzA), eps=a.eps, reps=a.reps, warmup=a.warmup, iter=int(r.info.iter),
+                backward_ms_median=1e3 * med(tot), backward_ms_min=1e3 * min(tot), backward_ms_max=1e3 * max(tot),
+                recurrence_ms_median=1e3 * med(rec_s), gradient_kernel_ms_median=1e3 * med(grad_s), recurrence_steps=rec['steps'], active_rows=rec['active_rows'],
+                residual=rec['residual'], polish_ms=[1e3 * p for p in pol], recurrence_over_polish=med(rec_s) / float(np.median(pol)),
+                gradient_bytes=gbytes, gradient_fraction_of_8TBs=gbytes / max(med(grad_s), 1e-12) / 8e12)
+    text = json.dumps(line)
+    print(text)
+    if a.out:
+        with open(a.out, 'w') as f:
+            f.write(text + '\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--single', action='store_true', help='one large QP on the PCG path instead of the MPC batch')
+    ap.add_argument('--n', type=int, default=100000)
     ap.add_argument('--batch', type=int, default=4096)
     ap.add_argument('--reps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--eps', type=float, default=1e-6)
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
+    if a.single:
+        return single(a)
     import torch
     import osqp_amd
     import problems
