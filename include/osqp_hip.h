@@ -280,6 +280,36 @@ OSQPInt osqp_hip_batch_solve_mat_device(OSQPSolver *solver, OSQPInt nbatch, cons
                                         const OSQPFloat *l_dev, const OSQPFloat *u_dev, OSQPFloat *x_dev, OSQPFloat *y_dev, OSQPFloat *rec_dev,
                                         OSQPInt warm_start, void *stream);
 
+/* LOCKSTEP: the same batch -- QPs that share this handle's P, A, scaling and settings and differ in q / l / u -- at ANY size a handle can be set up for
+ * (lockstep_hip.hip).  osqp_hip_batch_solve keeps one problem in one workgroup's LDS and declines above 10n + 8m doubles = 64 KB; here the ADMM / PCG
+ * iteration of its PCG variants runs on block vectors, OSQP_HIP_LOCKSTEP_WIDTH problems at a time (a batch is processed in chunks of that width, the
+ * last one ragged): lanes are problems, one pass over the matrix serves the whole chunk, every per-problem reduction is a lane-local sum.  Same
+ * arguments, same conventions (NULL = the handle's own vector, warm != 0: x / y hold the unscaled warm start on entry, rec: nbatch x
+ * OSQP_HIP_BATCH_REC) and the same per-problem rules as the PCG variants of osqp_hip_batch_solve: Jacobi-preconditioned CG on K_b = P + sigma I +
+ * A' diag(rho_b) A stopped per problem at cg_tol_fraction x the scaled dual residual (non-increasing; relative before the first residual), equality
+ * weight and adaptive rho per problem, termination / approximate statuses at max_iter / infeasibility certificates in x, y / OSQP_NON_CVX on
+ * non-finite residuals decided per problem on the device every check_termination / adaptive_rho_interval iterations; time_limit ends a chunk with
+ * OSQP_TIME_LIMIT_REACHED for its unfinished problems.  No polish (status_polish = 0), check_dualgap is ignored, no per-problem matrices.
+ * INDEPENDENCE: no quantity of one problem enters another problem's arithmetic and no summation order depends on a chunk's fill -- a problem's x, y
+ * and record are bit-identical whatever else is in the batch and wherever in it the problem sits.
+ * A handle that works on a permuted copy (OSQPHipStats::reordered) is served: the arrays keep the caller's numbering.  The handle's own iterates,
+ * solution, info and launch history are not touched: an osqp_solve after the call gives the bits it would have given without it.
+ * Returns OSQP_FUNC_NOT_IMPLEMENTED for a handle whose PCG runs a Woodbury-corrected preconditioner (OSQPHipStats::woodbury_rows > 0) and in the host
+ * simulator.  l <= u is validated on the host-pointer path only.
+ * _device: every array in device memory of this solver's device; the work goes on `stream` (NULL: the solver's own) after the solver's own stream has
+ * been waited for.  Unlike osqp_hip_batch_solve_device the call RETURNS WHEN THE RESULTS ARE THERE: the host reads a few status words from `stream`
+ * at every termination check.  nbatch == 0 launches nothing and answers whether the route applies.
+ * osqp_hip_lockstep_last_record: what the last lockstep call of the handle did, OSQP_HIP_LOCKSTEP_LAST_REC doubles {chunks, chunk width, ADMM
+ * iterations of the slowest problem, PCG iterations summed over the problems, kernel launches, GPU ms, workspace bytes, reserved}; all zero before
+ * the first call. */
+#define OSQP_HIP_LOCKSTEP_WIDTH 64
+#define OSQP_HIP_LOCKSTEP_LAST_REC 8
+OSQPInt osqp_hip_batch_solve_lockstep(OSQPSolver *solver, OSQPInt nbatch, const OSQPFloat *q, const OSQPFloat *l, const OSQPFloat *u,
+                                      OSQPFloat *x, OSQPFloat *y, OSQPFloat *rec, OSQPInt warm);
+OSQPInt osqp_hip_batch_solve_lockstep_device(OSQPSolver *solver, OSQPInt nbatch, const OSQPFloat *q_dev, const OSQPFloat *l_dev, const OSQPFloat *u_dev,
+                                             OSQPFloat *x_dev, OSQPFloat *y_dev, OSQPFloat *rec_dev, OSQPInt warm_start, void *stream);
+OSQPInt osqp_hip_lockstep_last_record(OSQPSolver *solver, OSQPFloat *rec);
+
 /* ADJOINT DERIVATIVES of a batch of solved QPs -- the backward pass of osqp_hip_batch_solve[_mat]: ONE launch, one workgroup per problem
  * (batch_hip.hip k_batch_adjoint).  For problem b with solution x (n), y (m) and incoming gradients dx = dL/dx (n), dy = dL/dy (m; NULL = 0):
  *   active rows by polish's rule on z = A x (lower-active: z_i - l_i < -y_i; else upper-active: u_i - z_i < y_i; l_i == u_i: always active, lower if y_i < 0),

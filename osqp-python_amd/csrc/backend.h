@@ -462,7 +462,38 @@ struct AdjointPcg {
   int rho_is_vec = 1;
 };
 
+// Lockstep batch route (lockstep_hip.hip; include/osqp_hip.h osqp_hip_batch_solve_lockstep): QPs that share the handle's scaled A / B and differ in
+// q / l / u, at any size, kLsW problems at a time on block vectors (element (j, b) at j * kLsW + b: lanes are problems).
+constexpr int kLsW = 64;          // chunk width: one wave's lanes
+constexpr int kLsSlots = 32;      // partial-reduction slots of a chunk ([slot][workgroup][kLsW])
+constexpr int kLsScal = 16, kLsInt = 12;      // rows of the per-problem fp64 / int32 state ([row][kLsW])
+// workgroups of the row passes (four waves each, a wave owns a strip of rows): from the row counts alone, so that the partition -- and with it every
+// sum's order -- does not depend on what a chunk holds
+inline int lockstep_grid(int n, int m) { const int r = n > m ? n : m, g = (r + 15) / 16; return g < 1 ? 1 : (g > 256 ? 256 : g); }
+// doubles of a chunk's workspace: eight n- and nine m-block vectors, the partials, the per-problem state and records
+inline size_t lockstep_ws_doubles(int n, int m) {
+  return (size_t)kLsW * (8 * (size_t)n + 9 * (size_t)m + (size_t)kLsSlots * lockstep_grid(n, m) + (size_t)(m + 63) / 64 + 1 + kLsScal + kBatchRec + kLsInt) + 64;
+}
+struct LockstepParams {
+  int n = 0, m = 0, count = 0;  // count: problems of this chunk (1 .. kLsW)
+  DevCsr A, B;
+  const double *D = nullptr, *Dinv = nullptr, *E = nullptr, *Einv = nullptr;
+  double c = 1, cinv = 1, sigma = 0, alpha = 0, rho0 = 0, eq_factor = 0, eps_abs = 0, eps_rel = 0, eps_pinf = 0, eps_dinf = 0, cg_frac = 0, rho_tol = 0;
+  double time_limit = 0;        // seconds this chunk may still take (<= 0: none)
+  int max_iter = 0, check = 0, rho_interval = 0, cg_max = 0, unscaled = 0, scaling = 0, precond = 0, rho_is_vec = 0, warm = 0;
+  const double *q = nullptr, *l = nullptr, *u = nullptr;        // the chunk's rows of the UNSCALED [nbatch][n] / [nbatch][m] arrays, the CALLER's numbering; nullptr = the shared vector
+  const double *q0 = nullptr, *l0 = nullptr, *u0 = nullptr;     // UNSCALED shared vectors, the ENGINE's numbering
+  double *x = nullptr, *y = nullptr, *rec = nullptr;            // the chunk's rows: in UNSCALED warm start (if warm), out UNSCALED solution; [count][kBatchRec]
+  const int *pc = nullptr, *pr = nullptr;                       // reordered handle: engine column / row -> the caller's; nullptr: identity
+  double *ws = nullptr;         // lockstep_ws_doubles(n, m) doubles
+};
+
 namespace be {
+
+// Weak, like adjoint_*: the host simulator has no such kernels and the driver answers OSQP_FUNC_NOT_IMPLEMENTED where the symbol is absent.  One chunk,
+// start to finish, on `stream` (nullptr: d.stream); synchronises with that stream.  stat[4]: ADMM iterations of the slowest problem, PCG iterations
+// summed over the problems, kernel launches, GPU ms.
+int lockstep_chunk(Dev &d, const LockstepParams &p, void *stream, double *stat) __attribute__((weak));
 
 // Weak, like batch_adjoint: the host simulator has no such kernels and the driver answers OSQP_FUNC_NOT_IMPLEMENTED where the symbols are absent.
 // adjoint_load: classification of the rows (code, rec[0]) and the recurrence's data -- Dev::q = c D dx, l = u = z = -E dy on the active rows (free

@@ -161,6 +161,7 @@ void Engine::free_all() {
   if (d_batch_iters_) { be::dfree(d_, d_batch_iters_); d_batch_iters_ = nullptr; d_batch_iters_n_ = 0; }
   batch_order_.clear();
   if (ckpt_) { be::dfree(d_, ckpt_); ckpt_ = nullptr; }
+  if (lsw_) { be::dfree(d_, lsw_); lsw_ = nullptr; }
   free_batch_direct(); free_batch_spectral(); free_batch_wave();
   if (d_.f1.va) {                                                // (these point into the F1 arena, freed as one block below)
     d_.Minv = d_.xs = d_.p = d_.r = d_.s = d_.rho = d_.f1.pval = nullptr; d_.f1.pcol = d_.f1.prp = nullptr; d_.f1.cptr = nullptr;

@@ -57,6 +57,11 @@ class Engine {
   // values for every problem) -- the reference's forward with a P_val / A_val per batch element (nn/torch.py:128-157): still ONE launch
   int batch_solve(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, double *zs_dev = nullptr, const double *Px = nullptr, const double *Ax = nullptr);
   int batch_solve_device(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream, const double *Px = nullptr, const double *Ax = nullptr);
+  // The lockstep route (include/osqp_hip.h osqp_hip_batch_solve_lockstep; lockstep_hip.hip): shared P / A, any size, kLsW problems at a time on block
+  // vectors.  Host arrays, or -- _device -- device arrays and a caller's stream; both return when the results are there.
+  int batch_solve_lockstep(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm);
+  int batch_solve_lockstep_device(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream);
+  int lockstep_last_record(double *rec) const;
   // Adjoint derivatives (include/osqp_hip.h osqp_hip_batch_adjoint; batch_hip.hip k_batch_adjoint): one launch for the batch.  Host arrays, or -- _device --
   // device arrays and a caller's stream with the semantics of batch_solve_device.  Px / Ax / l / u: nullptr = this solver's own values for every problem.
   int batch_adjoint(int nbatch, const double *Px, const double *Ax, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
@@ -120,6 +125,9 @@ class Engine {
   std::map<std::pair<int, int>, void *> graphs_;
   double *bbuf_ = nullptr; size_t bbuf_cap_ = 0;      // device scratch of batch_solve, kept across calls
   double *bmat_ = nullptr; size_t bmat_cap_ = 0;      // per-problem matrices: scaled values, equilibration and products of every problem (BatchParams::Aval_b ..), kept across calls
+  double *lsw_ = nullptr;                             // workspace of one lockstep chunk (lockstep_ws_doubles(n, m)), allocated on first use
+  double ls_rec_[OSQP_HIP_LOCKSTEP_LAST_REC] = {0, 0, 0, 0, 0, 0, 0, 0};      // record of the last lockstep call (osqp_hip_lockstep_last_record)
+  int run_lockstep(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream);
   double *abuf_ = nullptr; size_t abuf_cap_ = 0;      // device scratch of batch_adjoint (host-array entry point), kept across calls
   bool adjoint_applicable();                          // the problem fits k_batch_adjoint (the forward's direct variant + the adjoint's own LDS)
   void fill_adjoint_params(AdjointParams &p, int nbatch);

@@ -869,6 +869,87 @@ int Engine::batch_solve_device(int nbatch, const double *q, const double *l, con
   return err;
 }
 
+// ------------------------------------------------------------------------------------------------ lockstep route
+// Chunks of kLsW problems, one after the other, each from its transposes in to its transposes out (be::lockstep_chunk).  q / l / u / x / y / rec are
+// DEVICE arrays in the caller's numbering; the settings are read once, in front of the first chunk.  The handle's iterates are not touched: the route
+// has its own workspace (lsw_, allocated on first use, freed with the handle).
+int Engine::run_lockstep(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream) {
+  const size_t need = lockstep_ws_doubles(n, m);
+  if (!lsw_) { lsw_ = dev_vec<double>(d_, need); be::sync(d_); }
+  BatchParams b{};
+  fill_batch_params(b, nbatch, warm);                 // the settings snapshot of the batch path
+  LockstepParams p;
+  p.n = n; p.m = m; p.A = d_.A; p.B = d_.B; p.D = d_.D; p.Dinv = d_.Dinv; p.E = d_.E; p.Einv = d_.Einv;
+  p.c = b.c; p.cinv = b.cinv; p.sigma = b.sigma; p.alpha = b.alpha; p.rho0 = b.rho0; p.eq_factor = b.eq_factor; p.eps_abs = b.eps_abs; p.eps_rel = b.eps_rel;
+  p.eps_pinf = b.eps_pinf; p.eps_dinf = b.eps_dinf; p.cg_frac = b.cg_frac; p.rho_tol = b.rho_tol;
+  p.max_iter = b.max_iter; p.check = b.check; p.rho_interval = b.rho_interval; p.cg_max = b.cg_max; p.unscaled = b.unscaled; p.scaling = b.scaling;
+  p.precond = b.precond; p.rho_is_vec = b.rho_is_vec; p.warm = warm;
+  p.q0 = d_.qraw; p.l0 = d_.lraw; p.u0 = d_.uraw; p.pc = reordered_ ? d_pc_ : nullptr; p.pr = reordered_ ? d_pr_ : nullptr; p.ws = lsw_;
+  const double t0 = now_s(), limit = settings.time_limit > 0 && settings.time_limit < 1e9 ? settings.time_limit : 0.0;
+  double tot[4] = {0, 0, 0, 0};
+  int chunks = 0;
+  for (int b0 = 0; b0 < nbatch; b0 += kLsW, chunks++) {
+    p.count = std::min(kLsW, nbatch - b0);
+    p.q = q ? q + (size_t)b0 * n : nullptr; p.l = l ? l + (size_t)b0 * m : nullptr; p.u = u ? u + (size_t)b0 * m : nullptr;
+    p.x = x + (size_t)b0 * n; p.y = y + (size_t)b0 * m; p.rec = rec + (size_t)b0 * kBatchRec;
+    p.time_limit = limit > 0 ? std::max(limit - (now_s() - t0), 1e-9) : 0.0;
+    double st[4] = {0, 0, 0, 0};
+    const int err = be::lockstep_chunk(d_, p, stream, st);
+    if (err) return err;
+    tot[0] = std::max(tot[0], st[0]); tot[1] += st[1]; tot[2] += st[2]; tot[3] += st[3];
+  }
+  const double r[OSQP_HIP_LOCKSTEP_LAST_REC] = {(double)chunks, (double)kLsW, tot[0], tot[1], tot[2], tot[3], (double)(need * sizeof(double)), 0.0};
+  std::copy(r, r + OSQP_HIP_LOCKSTEP_LAST_REC, ls_rec_);
+  return OSQP_NO_ERROR;
+}
+
+int Engine::batch_solve_lockstep(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm) {
+  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (nbatch <= 0 || !x || !y || !rec) return OSQP_DATA_VALIDATION_ERROR;
+  if (!be::lockstep_chunk || !be::device_vec_updates() || d_.wb.on) return OSQP_FUNC_NOT_IMPLEMENTED;
+  be::activate(d_);
+  be::ext_wait(d_);                                 // the scratch block may still be read by a kernel on a caller's stream
+  const size_t N = (size_t)nbatch * n, M = (size_t)nbatch * m;
+  if ((l || u) && !(l && u)) ensure_host_vectors();
+  for (int b = 0; b < nbatch && (l || u); b++)                                                       // _osqp.py:1348-1349
+    for (int i = 0; i < m; i++) {
+      const int ii = reordered_ ? ipr_[i] : i;       // (the host copies of the handle's own bounds are kept in the engine's numbering)
+      const double li = l ? l[(size_t)b * m + i] : l0_[ii], ui = u ? u[(size_t)b * m + i] : u0_[ii];
+      if (!(li <= ui)) return OSQP_DATA_VALIDATION_ERROR;
+    }
+  // the batch path's device scratch block: [q | l | u | x | y | rec]
+  const size_t need = 2 * N + 3 * M + (size_t)nbatch * kBatchRec;
+  if (need > bbuf_cap_) { if (bbuf_) be::dfree(d_, bbuf_); bbuf_ = dev_vec<double>(d_, need); bbuf_cap_ = need; }
+  double *dq = bbuf_, *dl = dq + N, *du = dl + M, *dx = du + M, *dy = dx + N, *drec = dy + M;
+  if (q) be::h2d(d_, dq, q, sizeof(double) * N);
+  if (l) be::h2d(d_, dl, l, sizeof(double) * M);
+  if (u) be::h2d(d_, du, u, sizeof(double) * M);
+  if (warm) { be::h2d(d_, dx, x, sizeof(double) * N); be::h2d(d_, dy, y, sizeof(double) * M); }
+  be::sync(d_);
+  const int err = run_lockstep(nbatch, q ? dq : nullptr, l ? dl : nullptr, u ? du : nullptr, dx, dy, drec, warm, nullptr);
+  if (!err) { be::d2h(d_, x, dx, sizeof(double) * N); if (M) be::d2h(d_, y, dy, sizeof(double) * M); be::d2h(d_, rec, drec, sizeof(double) * kBatchRec * nbatch); }
+  return err;
+}
+
+int Engine::batch_solve_lockstep_device(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream) {
+  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  const bool applies = be::lockstep_chunk && be::device_vec_updates() && !d_.wb.on;
+  if (nbatch == 0) return applies ? OSQP_NO_ERROR : OSQP_FUNC_NOT_IMPLEMENTED;
+  if (nbatch < 0 || !x || !y || !rec) return OSQP_DATA_VALIDATION_ERROR;
+  if (!applies) return OSQP_FUNC_NOT_IMPLEMENTED;
+  be::activate(d_);
+  be::ext_wait(d_);
+  be::sync(d_);                                     // the solver's own stream first: pending updates of the resident q / l / u, the matrices
+  return run_lockstep(nbatch, q, l, u, x, y, rec, warm, stream);
+}
+
+int Engine::lockstep_last_record(double *rec) const {
+  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (!rec) return OSQP_DATA_VALIDATION_ERROR;
+  std::copy(ls_rec_, ls_rec_ + OSQP_HIP_LOCKSTEP_LAST_REC, rec);
+  return OSQP_NO_ERROR;
+}
+
 // ------------------------------------------------------------------------------------------------ adjoint derivatives
 // The backward pass of the batch path (batch_hip.hip k_batch_adjoint).  A problem is eligible when the forward's direct variant holds it (banded factor
 // under the engine's ordering: prepare_batch_direct) and the adjoint kernel's own LDS fits; the batch entry points answer OSQP_FUNC_NOT_IMPLEMENTED for

@@ -1,0 +1,663 @@
+// lockstep_hip.hip -- the LOCKSTEP batch route (include/osqp_hip.h osqp_hip_batch_solve_lockstep; engine_api.cpp Engine::batch_solve_lockstep):
+// a batch of QPs that share this handle's P, A, scaling and settings and differ in q / l / u, at ANY size a handle can be set up for.  The two batch
+// kernels of batch_hip.hip keep one problem in one workgroup's LDS; here the ADMM / PCG iteration of k_batch_admm's non-direct variants runs on BLOCK
+// VECTORS instead: kLsW = 64 problems advance together, LANES ARE PROBLEMS.
+//
+//   layout      element (j, b) of a block vector sits at j * kLsW + b (problem-minor): every access of a wave is one contiguous 512-byte line.
+//   products    Z = A X over the engine's scaled CSR of A, Y = B [X; T] over B = [P + sigma I | A'].  A wave owns a strip of rows and all 64 problems; a
+//               row's column indices and values are wave-uniform (scalar loads / a broadcast), each stored entry is one 512-byte gather and 64 FMAs;
+//               four entries are in flight per wave (indices, then gathers, then FMAs).  No atomics.
+//   scalars     every dot product / max-norm is, per problem, a sum over rows: a lane accumulates over its wave's rows, the four waves of a workgroup
+//               are combined in index order, the workgroup's partial goes to part[slot][workgroup][lane] and a one-workgroup fold kernel adds the
+//               partials in index order.  alpha, beta, ||r||, the residual norms, rho ... live as [kLsW] device arrays.  The row partition and
+//               the fold order depend on (n, m) alone -- never on the chunk's fill -- and no quantity of one problem enters another problem's
+//               arithmetic: a problem's x, y and record are bit-identical whatever else is in the batch and wherever in it the problem sits.
+//   freezing    a problem whose PCG has converged takes alpha = 0 and stores nothing; a problem whose ADMM has terminated stores nothing at all
+//               (its record is written at that moment).  Lanes >= count are "terminated" from the start.
+//   driving     per ADMM iteration the host enqueues the PCG iterations (six launches each) the previous one needed, plus one, without synchronising,
+//               reads the word block, and goes on in groups of four up to cg_max_iter while the device word "some problem's PCG is still running"
+//               is set; that word makes the launches past the last problem's convergence return at once.  Termination, the infeasibility tests, the
+//               statuses at max_iter and adaptive rho are decided per problem on the device (k_ls_decide: k_batch_admm's formulas, cited there);
+//               the host reads one small word block per termination check.
+// Transposes (LDS tiles, coalesced on both sides) move a chunk between the API's [nbatch][n] row-major arrays and the block vectors; they apply
+// k_batch_admm's load / store scaling and, for a handle that works on a permuted copy, gather / scatter through the permutations.
+#include "hip_common.h"
+
+namespace osqp_hip {
+namespace be {
+
+namespace {
+
+constexpr int W = kLsW;
+
+// partial slots (part[slot][workgroup][lane]); within a group the max-type slots come first
+enum LsSlot {
+  PS_BN = 0, PS_RN, PS_RZ, PS_PKP,
+  PS_M0,                         // m side, max: pri_u ax_u z_u pri_s ax_s z_s dy_u dy_s adx_max -adx_min ; sum: pinf_lhs
+  PS_N0 = PS_M0 + 11,            // n side, max: dua_u px_u aty_u dua_s px_s aty_s dx_u dx_s qn_s qn_u atdy_u atdy_s pdx_u pdx_s ; sum: xpx qx qdx
+  PS_COUNT = PS_N0 + 17
+};
+static_assert(PS_COUNT <= kLsSlots, "lockstep_ws_doubles reserves kLsSlots partial slots");
+enum LsScal { SC_RHOBAR = 0, SC_EQF, SC_EPSCG, SC_EPSPREV, SC_RZ, SC_RN, SC_TOL, SC_ALPHA, SC_BETA, SC_COUNT };
+enum LsInt { IW_DONE = 0, IW_STATUS, IW_RHOUPD, IW_PCG, IW_RELRULE, IW_CGON, IW_RHOCH, IW_COUNT };
+enum LsWord { WD_CGANY = 0, WD_LIVE, WD_RHOANY, WD_PCGSUM, WD_CGIT /* PCG iterations of the current ADMM iteration that some problem needed */, WD_COUNT };
+static_assert(SC_COUNT <= kLsScal && IW_COUNT + 1 <= kLsInt, "lockstep_ws_doubles reserves kLsScal / kLsInt rows");
+
+struct LsWs {
+  double *x, *xs, *r, *p, *Kp, *q, *Minv, *dx;        // n x W
+  double *z, *y, *t, *t2, *l, *u, *rho, *zt, *dy;     // m x W
+  double *part, *parti, *sc, *rec;
+  int *iw, *word;
+  int G;
+};
+struct LsK { LockstepParams P; LsWs w; };
+
+__device__ __forceinline__ int ls_lane() { return threadIdx.x & 63; }
+__device__ __forceinline__ int ls_wave() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
+__device__ __forceinline__ int ls_ctype(double li, double ui, int rho_is_vec) {          // _osqp.py:505-518
+  const int ty = (li < -OSQP_INFTY * 1e-4 && ui > OSQP_INFTY * 1e-4) ? -1 : ((ui - li < 1e-4) ? 1 : 0);
+  return rho_is_vec ? ty : 0;
+}
+
+// the four waves' values of KM max-type and KS sum-type statistics, combined in wave order, to the workgroup's partials
+template <int KM, int KS>
+__device__ __forceinline__ void ls_put(double *part, int slot0, const double *vm, const double *vs, double *lds) {
+  const int lane = ls_lane(), wv = ls_wave(), G = gridDim.x;
+#pragma unroll
+  for (int k = 0; k < KM; k++) lds[(k * 4 + wv) * 64 + lane] = vm[k];
+#pragma unroll
+  for (int k = 0; k < KS; k++) lds[((KM + k) * 4 + wv) * 64 + lane] = vs[k];
+  __syncthreads();
+  for (int k = wv; k < KM + KS; k += 4) {
+    const double *s = lds + k * 256 + lane;
+    double v;
+    if (k < KM) { v = nanmax(s[0], s[64]); v = nanmax(v, s[128]); v = nanmax(v, s[192]); }
+    else v = ((s[0] + s[64]) + s[128]) + s[192];
+    part[((size_t)(slot0 + k) * G + blockIdx.x) * 64 + lane] = v;
+  }
+}
+// sum / max of a slot's G partials in a fixed order: wave w takes g = w, w + 4, ..; the four results are combined in wave order.  One workgroup.
+template <bool MAX>
+__device__ __forceinline__ double ls_fold(const double *part, int G, int slot, double *lds) {
+  const int lane = ls_lane(), wv = ls_wave();
+  const double *s = part + (size_t)slot * G * 64 + lane;
+  double a = MAX ? -INFINITY : 0.0;
+  for (int g = wv; g < G; g += 4) { const double v = s[(size_t)g * 64]; a = MAX ? nanmax(a, v) : a + v; }
+  lds[wv * 64 + lane] = a;
+  __syncthreads();
+  double v;
+  if (MAX) { v = nanmax(lds[lane], lds[64 + lane]); v = nanmax(v, lds[128 + lane]); v = nanmax(v, lds[192 + lane]); }
+  else v = ((lds[lane] + lds[64 + lane]) + lds[128 + lane]) + lds[192 + lane];
+  __syncthreads();
+  return v;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- row passes
+// Rows [r0, r1) of M belong to this wave (the partition depends on the row count and the grid alone).  F: begin(row); load(c, g) issues the gathers
+// of one entry; fma(c, v, g, acc) adds it; row(row, acc) is the epilogue.  Everything about an entry but the gathered operands is wave-uniform.
+template <int NG, int NA, class F>
+__device__ __forceinline__ void ls_rows(const DevCsr &M, F &f) {
+  const int nw = gridDim.x * 4, rpw = (M.nrows + nw - 1) / nw;
+  const int r0 = ((int)blockIdx.x * 4 + ls_wave()) * rpw, r1 = min(r0 + rpw, M.nrows);
+  const int *__restrict__ rp = M.rowptr, *__restrict__ col = M.col;
+  const double *__restrict__ val = M.val;
+  for (int row = r0; row < r1; row++) {
+    int k = __builtin_amdgcn_readfirstlane(rp[row]);
+    const int k1 = __builtin_amdgcn_readfirstlane(rp[row + 1]);
+    double acc[NA];
+#pragma unroll
+    for (int a = 0; a < NA; a++) acc[a] = 0.0;
+    f.begin(row);
+    for (; k + 4 <= k1; k += 4) {
+      int c[4]; double v[4], g[4][NG];
+#pragma unroll
+      for (int u = 0; u < 4; u++) { c[u] = __builtin_amdgcn_readfirstlane(col[k + u]); v[u] = val[k + u]; }
+#pragma unroll
+      for (int u = 0; u < 4; u++) f.load(c[u], g[u]);
+#pragma unroll
+      for (int u = 0; u < 4; u++) f.fma(c[u], v[u], g[u], acc);
+    }
+    for (; k < k1; k++) {
+      const int c = __builtin_amdgcn_readfirstlane(col[k]); const double v = val[k];
+      double g[NG];
+      f.load(c, g); f.fma(c, v, g, acc);
+    }
+    f.row(row, acc);
+  }
+}
+#define IX(j) ((size_t)(j) * 64 + lane)
+
+// Minv = 1 / diag(K_b) = 1 / (B_jj + sum_i rho_i,b A_ij^2), for the problems whose rho has just been set (one pass over the A' part of B, squared entries)
+struct FMinv {
+  const double *rho; double *Minv; const int *flag; int n, precond, lane, cur;
+  __device__ __forceinline__ void begin(int row) { cur = row; }
+  __device__ __forceinline__ void load(int c, double (&g)[1]) const { g[0] = c >= n ? rho[IX(c - n)] : 0.0; }
+  __device__ __forceinline__ void fma(int c, double v, const double (&g)[1], double (&a)[2]) const { if (c >= n) a[0] += g[0] * v * v; else if (c == cur) a[1] = v; }
+  __device__ __forceinline__ void row(int j, const double (&a)[2]) const { if (flag[lane]) Minv[IX(j)] = precond ? 1.0 / (a[1] + a[0]) : 1.0; }
+};
+__global__ __launch_bounds__(256) void k_ls_minv(LsK k) {
+  if (!k.w.word[WD_RHOANY]) return;
+  FMinv f{k.w.rho, k.w.Minv, k.w.iw + IW_RHOCH * W, k.P.n, k.P.precond, ls_lane(), 0};
+  ls_rows<1, 2>(k.P.B, f);
+}
+
+// rhs = sigma x - q + A'(rho z - y);  r = rhs - K x~ with K x~ = B [x~; rho z~];  p = Minv r   (k_batch_admm: "rhs = ...", _osqp.py:649-650)
+struct FRhs {
+  const LsWs &w; double sigma; int n, lane, live;
+  double bn = 0, rn = 0, rz = 0;
+  __device__ __forceinline__ void begin(int) {}
+  __device__ __forceinline__ void load(int c, double (&g)[2]) const {
+    if (c < n) { g[0] = w.xs[IX(c)]; g[1] = 0.0; } else { g[0] = w.t[IX(c - n)]; g[1] = w.t2[IX(c - n)]; }
+  }
+  __device__ __forceinline__ void fma(int c, double v, const double (&g)[2], double (&a)[2]) const {
+    if (c < n) a[1] += v * g[0]; else { a[0] += v * g[0]; a[1] += v * g[1]; }
+  }
+  __device__ __forceinline__ void row(int j, const double (&a)[2]) {
+    const double rhs = sigma * w.x[IX(j)] - w.q[IX(j)] + a[0], rr = rhs - a[1], zz = w.Minv[IX(j)] * rr;
+    if (live) { w.r[IX(j)] = rr; w.p[IX(j)] = zz; }
+    rz += rr * zz; rn = nanmax(rn, fabs(rr)); bn = nanmax(bn, fabs(rhs));
+  }
+};
+__global__ __launch_bounds__(256) void k_ls_rhs(LsK k) {
+  __shared__ double lds[3 * 256];
+  const int lane = ls_lane();
+  FRhs f{k.w, k.P.sigma, k.P.n, lane, !k.w.iw[IW_DONE * W + lane]};
+  ls_rows<2, 2>(k.P.B, f);
+  const double vm[2] = {f.bn, f.rn}, vs[1] = {f.rz};
+  ls_put<2, 1>(k.w.part, PS_BN, vm, vs, lds);
+}
+
+// Kp = B [p; t],  <p, Kp>
+struct FKp {
+  const LsWs &w; int n, lane, on;
+  double pkp = 0;
+  __device__ __forceinline__ void begin(int) {}
+  __device__ __forceinline__ void load(int c, double (&g)[1]) const { g[0] = c < n ? w.p[IX(c)] : w.t[IX(c - n)]; }
+  __device__ __forceinline__ void fma(int, double v, const double (&g)[1], double (&a)[1]) const { a[0] += v * g[0]; }
+  __device__ __forceinline__ void row(int j, const double (&a)[1]) { if (on) w.Kp[IX(j)] = a[0]; pkp += a[0] * w.p[IX(j)]; }
+};
+__global__ __launch_bounds__(256) void k_ls_kp(LsK k) {
+  __shared__ double lds[256];
+  if (!k.w.word[WD_CGANY]) return;
+  const int lane = ls_lane();
+  FKp f{k.w, k.P.n, lane, k.w.iw[IW_CGON * W + lane]};
+  ls_rows<1, 1>(k.P.B, f);
+  const double vs[1] = {f.pkp};
+  ls_put<0, 1>(k.w.part, PS_PKP, vs, vs, lds);
+}
+
+// the n side of k_batch_admm's residuals(), with the second stage of both infeasibility tests (A' dy, P dx) from the same pass
+struct FResN {
+  const LsWs &w; const double *D, *Dinv; double sigma; int n, lane;
+  double vm[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, vs[3] = {0, 0, 0};
+  __device__ __forceinline__ void begin(int) {}
+  __device__ __forceinline__ void load(int c, double (&g)[2]) const {
+    if (c < n) { g[0] = w.x[IX(c)]; g[1] = w.dx[IX(c)]; } else { g[0] = w.y[IX(c - n)]; g[1] = w.dy[IX(c - n)]; }
+  }
+  __device__ __forceinline__ void fma(int c, double v, const double (&g)[2], double (&a)[4]) const {
+    const double p0 = v * g[0], p1 = v * g[1]; const bool pn = c < n;       // (selects, not indexed accumulators: those would live in scratch)
+    a[0] += pn ? p0 : 0.0; a[2] += pn ? p1 : 0.0; a[1] += pn ? 0.0 : p0; a[3] += pn ? 0.0 : p1;
+  }
+  __device__ __forceinline__ void row(int j, const double (&a)[4]) {
+    const double xj = w.x[IX(j)], qj = w.q[IX(j)], dxj = w.dx[IX(j)], di = Dinv[j];
+    const double px = a[0] - sigma * xj, sa = a[1], dr = px + qj + sa, pdx = a[2] - sigma * dxj, atdy = a[3];
+    vm[0] = nanmax(vm[0], fabs(di * dr)); vm[1] = nanmax(vm[1], fabs(di * px)); vm[2] = nanmax(vm[2], fabs(di * sa));
+    vm[3] = nanmax(vm[3], fabs(dr)); vm[4] = nanmax(vm[4], fabs(px)); vm[5] = nanmax(vm[5], fabs(sa));
+    vm[6] = nanmax(vm[6], fabs(D[j] * dxj)); vm[7] = nanmax(vm[7], fabs(dxj)); vm[8] = nanmax(vm[8], fabs(qj)); vm[9] = nanmax(vm[9], fabs(di * qj));
+    vm[10] = nanmax(vm[10], fabs(di * atdy)); vm[11] = nanmax(vm[11], fabs(atdy)); vm[12] = nanmax(vm[12], fabs(di * pdx)); vm[13] = nanmax(vm[13], fabs(pdx));
+    vs[0] += xj * px; vs[1] += qj * xj; vs[2] += qj * dxj;
+  }
+};
+__global__ __launch_bounds__(256) void k_ls_resn(LsK k) {
+  __shared__ double lds[17 * 256];
+  FResN f{k.w, k.P.D, k.P.Dinv, k.P.sigma, k.P.n, ls_lane()};
+  ls_rows<2, 4>(k.P.B, f);
+  ls_put<14, 3>(k.w.part, PS_N0, f.vm, f.vs, lds);
+}
+
+// z = z~ = A x at the start;  t = rho z - y,  t2 = rho z~  (what the next k_ls_rhs gathers)
+struct FInitZ {
+  const LsWs &w; int lane;
+  __device__ __forceinline__ void begin(int) {}
+  __device__ __forceinline__ void load(int c, double (&g)[1]) const { g[0] = w.x[IX(c)]; }
+  __device__ __forceinline__ void fma(int, double v, const double (&g)[1], double (&a)[1]) const { a[0] += v * g[0]; }
+  __device__ __forceinline__ void row(int i, const double (&a)[1]) const {
+    const double rh = w.rho[IX(i)];
+    w.z[IX(i)] = a[0]; w.zt[IX(i)] = a[0]; w.t[IX(i)] = rh * a[0] - w.y[IX(i)]; w.t2[IX(i)] = rh * a[0];
+  }
+};
+__global__ __launch_bounds__(256) void k_ls_initz(LsK k) {
+  FInitZ f{k.w, ls_lane()};
+  ls_rows<1, 1>(k.P.A, f);
+}
+
+// t = rho .* (A p)
+struct FT {
+  const LsWs &w; int lane, on;
+  __device__ __forceinline__ void begin(int) {}
+  __device__ __forceinline__ void load(int c, double (&g)[1]) const { g[0] = w.p[IX(c)]; }
+  __device__ __forceinline__ void fma(int, double v, const double (&g)[1], double (&a)[1]) const { a[0] += v * g[0]; }
+  __device__ __forceinline__ void row(int i, const double (&a)[1]) const { if (on) w.t[IX(i)] = w.rho[IX(i)] * a[0]; }
+};
+__global__ __launch_bounds__(256) void k_ls_t(LsK k) {
+  if (!k.w.word[WD_CGANY]) return;
+  const int lane = ls_lane();
+  FT f{k.w, lane, k.w.iw[IW_CGON * W + lane]};
+  ls_rows<1, 1>(k.P.A, f);
+}
+
+// z~ = A x~;  z, y update (_osqp.py:660-703);  and, elementwise,  x = alpha x~ + (1 - alpha) x,  dx
+struct FUpd {
+  const LsWs &w; double alpha; int lane, live;
+  __device__ __forceinline__ void begin(int) {}
+  __device__ __forceinline__ void load(int c, double (&g)[1]) const { g[0] = w.xs[IX(c)]; }
+  __device__ __forceinline__ void fma(int, double v, const double (&g)[1], double (&a)[1]) const { a[0] += v * g[0]; }
+  __device__ __forceinline__ void row(int i, const double (&acc)[1]) const {
+    if (!live) return;
+    const double a = acc[0], rh = w.rho[IX(i)], yi = w.y[IX(i)];
+    const double zr = alpha * a + (1.0 - alpha) * w.z[IX(i)];
+    const double zn = fmin(fmax(zr + yi / rh, w.l[IX(i)]), w.u[IX(i)]);
+    const double dyi = rh * (zr - zn), yn = yi + dyi;
+    w.y[IX(i)] = yn; w.dy[IX(i)] = dyi; w.z[IX(i)] = zn; w.zt[IX(i)] = a;
+    w.t[IX(i)] = rh * zn - yn; w.t2[IX(i)] = rh * a;
+  }
+};
+__global__ __launch_bounds__(256) void k_ls_upd(LsK k) {
+  const int lane = ls_lane(), live = !k.w.iw[IW_DONE * W + lane];
+  if (k.P.m > 0) { FUpd f{k.w, k.P.alpha, lane, live}; ls_rows<1, 1>(k.P.A, f); }
+  if (!live) return;
+  const size_t tot = (size_t)k.P.n * 64;
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < tot; e += (size_t)gridDim.x * 256) {
+    const double xo = k.w.x[e], xn = k.P.alpha * k.w.xs[e] + (1.0 - k.P.alpha) * xo;
+    k.w.dx[e] = xn - xo; k.w.x[e] = xn;
+  }
+}
+
+// the m side of residuals(), with A dx of the dual infeasibility test (largest value over the rows with a finite upper bound, largest negated value over
+// those with a finite lower one: "no row violates" is two comparisons of these with the threshold, which only the fold knows)
+struct FResM {
+  const LsWs &w; const double *E, *Einv; int lane, unsc;
+  double vm[10] = {0, 0, 0, 0, 0, 0, 0, 0, -INFINITY, -INFINITY}, vs[1] = {0};
+  __device__ __forceinline__ void begin(int) {}
+  __device__ __forceinline__ void load(int c, double (&g)[2]) const { g[0] = w.x[IX(c)]; g[1] = w.dx[IX(c)]; }
+  __device__ __forceinline__ void fma(int, double v, const double (&g)[2], double (&a)[2]) const { a[0] += v * g[0]; a[1] += v * g[1]; }
+  __device__ __forceinline__ void row(int i, const double (&a)[2]) {
+    const double ax = a[0], zi = w.z[IX(i)], pr = ax - zi, ei = Einv[i], dyi = w.dy[IX(i)], li = w.l[IX(i)], ui = w.u[IX(i)];
+    vm[0] = nanmax(vm[0], fabs(ei * pr)); vm[1] = nanmax(vm[1], fabs(ei * ax)); vm[2] = nanmax(vm[2], fabs(ei * zi));
+    vm[3] = nanmax(vm[3], fabs(pr)); vm[4] = nanmax(vm[4], fabs(ax)); vm[5] = nanmax(vm[5], fabs(zi));
+    vm[6] = nanmax(vm[6], fabs(E[i] * dyi)); vm[7] = nanmax(vm[7], fabs(dyi));
+    const double adx = unsc ? ei * a[1] : a[1];
+    if (ui < OSQP_INFTY * 1e-4) vm[8] = nanmax(vm[8], adx);
+    if (li > -OSQP_INFTY * 1e-4) vm[9] = nanmax(vm[9], -adx);
+    vs[0] += ui * fmax(dyi, 0.0) + li * fmin(dyi, 0.0);
+  }
+};
+__global__ __launch_bounds__(256) void k_ls_resm(LsK k) {
+  __shared__ double lds[11 * 256];
+  FResM f{k.w, k.P.E, k.P.Einv, ls_lane(), k.P.unscaled};
+  ls_rows<2, 2>(k.P.A, f);
+  ls_put<10, 1>(k.w.part, PS_M0, f.vm, f.vs, lds);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- elementwise kernels
+// rho by constraint class and the problem's rho_bar (_osqp.py:520-522), for the problems whose rho has just been set; t, t2 follow
+__global__ __launch_bounds__(256) void k_ls_setrho(LsK k) {
+  if (!k.w.word[WD_RHOANY]) return;
+  const int lane = ls_lane();
+  if (!k.w.iw[IW_RHOCH * W + lane]) return;
+  const double rb = k.w.sc[SC_RHOBAR * W + lane], eqf = k.w.sc[SC_EQF * W + lane];
+  const size_t tot = (size_t)k.P.m * 64;
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < tot; e += (size_t)gridDim.x * 256) {
+    const int ty = ls_ctype(k.w.l[e], k.w.u[e], k.P.rho_is_vec);
+    const double rh = ty == -1 ? 1e-6 : (ty == 1 ? eqf * rb : rb);
+    k.w.rho[e] = rh; k.w.t[e] = rh * k.w.z[e] - k.w.y[e]; k.w.t2[e] = rh * k.w.zt[e];
+  }
+}
+
+// x~ += alpha p;  r -= alpha Kp;  <r, Minv r>, ||r||_inf.   Wave w of workgroup g takes rows (4 g + w), + 4 G, ..: fixed by the grid
+__global__ __launch_bounds__(256) void k_ls_cgupd(LsK k) {
+  __shared__ double lds[2 * 256];
+  if (!k.w.word[WD_CGANY]) return;
+  const int lane = ls_lane(), on = k.w.iw[IW_CGON * W + lane];
+  const double al = k.w.sc[SC_ALPHA * W + lane];
+  double rz = 0, rn = 0;
+  for (int j = (int)blockIdx.x * 4 + ls_wave(); j < k.P.n; j += (int)gridDim.x * 4) {
+    if (on) {
+      k.w.xs[IX(j)] += al * k.w.p[IX(j)];
+      const double rr = k.w.r[IX(j)] - al * k.w.Kp[IX(j)], zz = k.w.Minv[IX(j)] * rr;
+      k.w.r[IX(j)] = rr;
+      rz += rr * zz; rn = nanmax(rn, fabs(rr));
+    }
+  }
+  const double vm[1] = {rn}, vs[1] = {rz};
+  ls_put<1, 1>(k.w.part, PS_RN, vm, vs, lds);
+}
+// p = Minv r + beta p  (for the problems whose PCG goes on)
+__global__ __launch_bounds__(256) void k_ls_cgp(LsK k) {
+  if (!k.w.word[WD_CGANY]) return;
+  const int lane = ls_lane();
+  if (!k.w.iw[IW_CGON * W + lane]) return;
+  const double be = k.w.sc[SC_BETA * W + lane];
+  const size_t tot = (size_t)k.P.n * 64;
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < tot; e += (size_t)gridDim.x * 256) k.w.p[e] = k.w.Minv[e] * k.w.r[e] + be * k.w.p[e];
+}
+
+// ---------------------------------------------------------------------------------------------------------------- folds (one workgroup each)
+__device__ __forceinline__ void ls_any(int *word, int flag) {
+  const unsigned long long bal = __ballot(flag);
+  if (threadIdx.x == 0) *word = bal != 0ull;
+}
+// PCG start: <r, Minv r>, ||r||, ||rhs||;  the stopping threshold of k_batch_admm's PCG variants
+__global__ __launch_bounds__(256) void k_ls_cginit(LsK k) {
+  __shared__ double lds[256];
+  const int lane = ls_lane(), G = k.w.G;
+  const double bn = ls_fold<true>(k.w.part, G, PS_BN, lds), rn = ls_fold<true>(k.w.part, G, PS_RN, lds), rz = ls_fold<false>(k.w.part, G, PS_RZ, lds);
+  if (threadIdx.x >= 64) return;
+  const double eps_cg = k.w.sc[SC_EPSCG * W + lane];
+  const double tol = k.w.iw[IW_RELRULE * W + lane] ? fmax(0.1 * bn, 1e-13) : fmax(1e-14 * bn, eps_cg);
+  const int on = !k.w.iw[IW_DONE * W + lane] && k.P.cg_max > 0 && rn > tol;
+  k.w.sc[SC_RZ * W + lane] = rz; k.w.sc[SC_RN * W + lane] = rn; k.w.sc[SC_TOL * W + lane] = tol;
+  k.w.iw[IW_CGON * W + lane] = on;
+  ls_any(k.w.word + WD_CGANY, on);
+  if (threadIdx.x == 0) k.w.word[WD_CGIT] = 0;
+}
+__global__ __launch_bounds__(256) void k_ls_cgalpha(LsK k) {
+  __shared__ double lds[256];
+  if (!k.w.word[WD_CGANY]) return;
+  const int lane = ls_lane();
+  const double pkp = ls_fold<false>(k.w.part, k.w.G, PS_PKP, lds);
+  if (threadIdx.x >= 64) return;
+  k.w.sc[SC_ALPHA * W + lane] = k.w.iw[IW_CGON * W + lane] ? k.w.sc[SC_RZ * W + lane] / pkp : 0.0;
+}
+__global__ __launch_bounds__(256) void k_ls_cgbeta(LsK k) {
+  __shared__ double lds[256];
+  if (!k.w.word[WD_CGANY]) return;
+  const int lane = ls_lane(), G = k.w.G;
+  const double rn2 = ls_fold<true>(k.w.part, G, PS_RN, lds), rz2 = ls_fold<false>(k.w.part, G, PS_RZ, lds);
+  if (threadIdx.x >= 64) return;
+  int on = k.w.iw[IW_CGON * W + lane];
+  if (on) {
+    k.w.sc[SC_BETA * W + lane] = rz2 / k.w.sc[SC_RZ * W + lane];
+    k.w.sc[SC_RZ * W + lane] = rz2; k.w.sc[SC_RN * W + lane] = rn2;
+    k.w.iw[IW_PCG * W + lane] += 1;
+    on = rn2 > k.w.sc[SC_TOL * W + lane];
+    k.w.iw[IW_CGON * W + lane] = on;
+  }
+  ls_any(k.w.word + WD_CGANY, on);
+  if (threadIdx.x == 0) k.w.word[WD_CGIT] += 1;
+}
+
+// Every check_termination / adaptive_rho_interval iterations: k_batch_admm's decisions (non-direct formulas), per problem.
+// mode 0: a boundary of the loop;  1: the residuals of the start (sets the first inner tolerance);  2: the time limit has passed.
+__global__ __launch_bounds__(256) void k_ls_decide(LsK k, int iter, int at_check, int at_rho, int mode) {
+  __shared__ double lds[256];
+  const LockstepParams &P = k.P;
+  const int lane = ls_lane(), G = k.w.G;
+  double M_[11], N_[17];
+#pragma unroll
+  for (int s = 0; s < 10; s++) M_[s] = ls_fold<true>(k.w.part, G, PS_M0 + s, lds);
+  M_[10] = ls_fold<false>(k.w.part, G, PS_M0 + 10, lds);
+#pragma unroll
+  for (int s = 0; s < 14; s++) N_[s] = ls_fold<true>(k.w.part, G, PS_N0 + s, lds);
+#pragma unroll
+  for (int s = 14; s < 17; s++) N_[s] = ls_fold<false>(k.w.part, G, PS_N0 + s, lds);
+  if (threadIdx.x >= 64) return;
+  int *iw = k.w.iw; double *sc = k.w.sc;
+  const int done = iw[IW_DONE * W + lane];
+  int rhoch = 0;
+  if (!done) {
+    const double pri_u = M_[0], ax_u = M_[1], z_u = M_[2], pri_s = M_[3], ax_s = M_[4], z_s = M_[5], dy_u = M_[6], dy_s = M_[7], adx_hi = M_[8], adx_lo = M_[9], pinf_lhs = M_[10];
+    const double dua_u = N_[0], px_u = N_[1], aty_u = N_[2], dua_s = N_[3], px_s = N_[4], aty_s = N_[5], dxn_u = N_[6], dxn_s = N_[7], qn_s = N_[8], qn_u = N_[9];
+    const double atdy_u = N_[10], atdy_s = N_[11], pdx_u = N_[12], pdx_s = N_[13], xpx = N_[14], qx = N_[15], qdx = N_[16];
+    if (mode == 1) {
+      const double eps_cg = P.cg_frac * dua_s;
+      sc[SC_EPSCG * W + lane] = eps_cg; sc[SC_EPSPREV * W + lane] = INFINITY;
+      iw[IW_RELRULE * W + lane] = !(eps_cg > 1e-13) || !isfinite(eps_cg);
+    } else {
+      const bool unsc = P.unscaled != 0;
+      const int m = P.m;
+      double rho_bar = sc[SC_RHOBAR * W + lane];
+      double obj = (0.5 * xpx + qx) * (P.scaling ? P.cinv : 1.0);                           // _osqp.py:705-712
+      const double prim_res = m == 0 ? 0.0 : (unsc ? pri_u : pri_s), dual_res = unsc ? P.cinv * dua_u : dua_s;
+      int status = OSQP_UNSOLVED;
+      bool stop = false;
+      for (int approx = 0; approx < 2 && !stop && at_check; approx++) {                     // _osqp.py:998-1077, :1264-1266
+        if (approx && iter < P.max_iter) break;
+        const double f = approx ? 10.0 : 1.0;
+        const double ea = f * P.eps_abs, er = f * P.eps_rel, epi = f * P.eps_pinf, edi = f * P.eps_dinf;
+        if (prim_res > OSQP_INFTY || dual_res > OSQP_INFTY || prim_res != prim_res || dual_res != dual_res) { status = OSQP_NON_CVX; obj = NAN; stop = true; break; }
+        bool pri_ok = false, dua_ok = false, pinf = false, dinf = false;
+        if (m == 0) pri_ok = true;
+        else if (prim_res < ea + er * (unsc ? fmax(ax_u, z_u) : fmax(ax_s, z_s))) pri_ok = true;
+        else {                                                                              // is_primal_infeasible :796-820
+          const double nd = unsc ? dy_u : dy_s;
+          if (nd > epi && pinf_lhs < -epi * nd) pinf = (unsc ? atdy_u : atdy_s) < epi * nd;
+        }
+        const double mx = unsc ? P.cinv * fmax(fmax(aty_u, px_u), qn_u) : fmax(fmax(aty_s, px_s), qn_s);
+        if (dual_res < ea + er * mx) dua_ok = true;
+        else {                                                                              // is_dual_infeasible :822-878
+          const double nd = unsc ? dxn_u : dxn_s, sc_ = unsc ? P.c : 1.0;
+          if (nd > edi && qdx < -sc_ * edi * nd && (unsc ? pdx_u : pdx_s) < sc_ * edi * nd) dinf = !(adx_hi > edi * nd) && !(adx_lo > edi * nd);
+        }
+        if (pri_ok && dua_ok) { status = approx ? OSQP_SOLVED_INACCURATE : OSQP_SOLVED; stop = true; }
+        else if (pinf) { status = approx ? OSQP_PRIMAL_INFEASIBLE_INACCURATE : OSQP_PRIMAL_INFEASIBLE; obj = OSQP_INFTY; stop = true; }
+        else if (dinf) { status = approx ? OSQP_DUAL_INFEASIBLE_INACCURATE : OSQP_DUAL_INFEASIBLE; obj = -OSQP_INFTY; stop = true; }
+      }
+      if (!stop && iter >= P.max_iter) { status = OSQP_MAX_ITER_REACHED; stop = true; }
+      if (!stop && mode == 2) { status = OSQP_TIME_LIMIT_REACHED; stop = true; }
+      const double pr = pri_s / (fmax(ax_s, z_s) + 1e-10), du = dua_s / (fmax(fmax(aty_s, px_s), qn_s) + 1e-10);
+      const double rho_new = fmin(fmax(rho_bar * sqrt(pr / (du + 1e-10)), 1e-6), 1e6);       // adapt_rho :880-930
+      if (stop) {
+        double *rc = k.w.rec + (size_t)lane * kBatchRec;
+        rc[0] = status; rc[1] = iter; rc[2] = obj; rc[3] = prim_res; rc[4] = dual_res; rc[5] = rho_bar; rc[6] = iw[IW_RHOUPD * W + lane]; rc[7] = iw[IW_PCG * W + lane];
+        rc[8] = 0.0; rc[9] = 0.0; rc[10] = rho_new; rc[11] = 0.0;
+        iw[IW_DONE * W + lane] = 1; iw[IW_STATUS * W + lane] = status;
+      } else {
+        if (at_rho && (rho_new > P.rho_tol * rho_bar || rho_new < rho_bar / P.rho_tol)) {
+          sc[SC_RHOBAR * W + lane] = rho_new; iw[IW_RHOUPD * W + lane] += 1; rhoch = 1;
+        }
+        double e2 = fmax(fmin(P.cg_frac * dua_s, sc[SC_EPSPREV * W + lane]), 1e-13);        // inner tolerance: non-increasing
+        if (isfinite(e2)) { sc[SC_EPSPREV * W + lane] = e2; sc[SC_EPSCG * W + lane] = e2; iw[IW_RELRULE * W + lane] = 0; }
+      }
+    }
+  }
+  iw[IW_RHOCH * W + lane] = rhoch;
+  const unsigned long long live = __ballot(!iw[IW_DONE * W + lane]), chg = __ballot(rhoch);
+  int pcg = iw[IW_PCG * W + lane];                      // (statistics only: the sum over the chunk's problems)
+  for (int o = 32; o > 0; o >>= 1) pcg += __shfl_xor(pcg, o);
+  if (threadIdx.x == 0) { k.w.word[WD_LIVE] = __popcll(live); k.w.word[WD_RHOANY] = chg != 0ull; k.w.word[WD_PCGSUM] = pcg; }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- transposes
+// tile[b][jl] <- src[b][perm(j0 + jl)] for the chunk's problems (coalesced along j without a permutation), zero elsewhere
+__device__ __forceinline__ void ls_tile_in(const double *src, int width, int j0, int count, const int *perm, double (*tile)[65]) {
+  const int lane = ls_lane(), wv = ls_wave(), j = j0 + lane;
+  const int sj = j < width ? (perm ? perm[j] : j) : 0;
+  for (int b = wv; b < 64; b += 4) tile[b][lane] = (b < count && j < width) ? src[(size_t)b * width + sj] : 0.0;
+  __syncthreads();
+}
+__device__ __forceinline__ void ls_tile_out(double *dst, int width, int j0, int count, const int *perm, double (*tile)[65]) {
+  const int lane = ls_lane(), wv = ls_wave(), j = j0 + lane;
+  __syncthreads();
+  if (j < width) {
+    const int sj = perm ? perm[j] : j;
+    for (int b = wv; b < count; b += 4) dst[(size_t)b * width + sj] = tile[b][lane];
+  }
+  __syncthreads();
+}
+
+// q <- c D q,  x <- Dinv x (warm) or 0,  x~ = x,  dx = 0   (k_batch_admm "load the problem")
+__global__ __launch_bounds__(256) void k_ls_load_n(LsK k) {
+  __shared__ double tile[64][65];
+  const LockstepParams &P = k.P;
+  const int lane = ls_lane(), wv = ls_wave(), j0 = blockIdx.x * 64;
+  const bool mine = lane < P.count;
+  if (P.q) ls_tile_in(P.q, P.n, j0, P.count, P.pc, tile);
+  for (int jl = wv; jl < 64 && j0 + jl < P.n; jl += 4) {
+    const int j = j0 + jl;
+    const double qv = P.q ? tile[lane][jl] : P.q0[j];
+    k.w.q[IX(j)] = mine ? P.c * P.D[j] * qv : 0.0;
+  }
+  __syncthreads();
+  if (P.warm) ls_tile_in(P.x, P.n, j0, P.count, P.pc, tile);
+  for (int jl = wv; jl < 64 && j0 + jl < P.n; jl += 4) {
+    const int j = j0 + jl;
+    const double xv = (P.warm && mine) ? tile[lane][jl] * P.Dinv[j] : 0.0;
+    k.w.x[IX(j)] = xv; k.w.xs[IX(j)] = xv; k.w.dx[IX(j)] = 0.0;
+  }
+}
+// l, u <- E clamp(l, u),  y <- c Einv y (warm) or 0,  dy = 0;  the problem's number of inequality rows (decides its equality weight)
+__global__ __launch_bounds__(256) void k_ls_load_m(LsK k) {
+  __shared__ double tile[64][65];
+  __shared__ double red[256];
+  const LockstepParams &P = k.P;
+  const int lane = ls_lane(), wv = ls_wave(), i0 = blockIdx.x * 64;
+  const bool mine = lane < P.count;
+  double lo[16], cnt = 0.0;
+  if (P.l) ls_tile_in(P.l, P.m, i0, P.count, P.pr, tile);
+#pragma unroll
+  for (int s = 0; s < 16; s++) { const int il = wv + 4 * s, i = min(i0 + il, P.m - 1); lo[s] = P.l ? tile[lane][il] : P.l0[i]; }
+  __syncthreads();
+  if (P.u) ls_tile_in(P.u, P.m, i0, P.count, P.pr, tile);
+#pragma unroll
+  for (int s = 0; s < 16; s++) {
+    const int il = wv + 4 * s, i = i0 + il;
+    if (i < P.m) {
+      const double uv = P.u ? tile[lane][il] : P.u0[i];
+      const double li = mine ? P.E[i] * fmax(lo[s], -OSQP_INFTY) : -OSQP_INFTY, ui = mine ? P.E[i] * fmin(uv, OSQP_INFTY) : OSQP_INFTY;
+      k.w.l[IX(i)] = li; k.w.u[IX(i)] = ui; k.w.dy[IX(i)] = 0.0;
+      cnt += ls_ctype(li, ui, P.rho_is_vec) == 0 ? 1.0 : 0.0;
+    }
+  }
+  __syncthreads();
+  if (P.warm) ls_tile_in(P.y, P.m, i0, P.count, P.pr, tile);
+  for (int il = wv; il < 64 && i0 + il < P.m; il += 4) {
+    const int i = i0 + il;
+    k.w.y[IX(i)] = (P.warm && mine) ? tile[lane][il] * P.Einv[i] * P.c : 0.0;
+  }
+  red[wv * 64 + lane] = cnt;
+  __syncthreads();
+  if (wv == 0) k.w.parti[(size_t)blockIdx.x * 64 + lane] = ((red[lane] + red[64 + lane]) + red[128 + lane]) + red[192 + lane];
+}
+// the chunk's per-problem state: rho_bar, the equality weight (engine.cpp classify_constraints), counters; lanes >= count are terminated
+__global__ __launch_bounds__(256) void k_ls_init(LsK k, int tiles_m) {
+  __shared__ double lds[256];
+  const int lane = ls_lane();
+  const double n_ineq = ls_fold<false>(k.w.parti, tiles_m, 0, lds);
+  if (threadIdx.x >= 64) return;
+  double *sc = k.w.sc; int *iw = k.w.iw;
+  sc[SC_RHOBAR * W + lane] = k.P.rho0; sc[SC_EQF * W + lane] = (n_ineq == 0.0) ? 1e3 : k.P.eq_factor;
+  sc[SC_EPSCG * W + lane] = 0.0; sc[SC_EPSPREV * W + lane] = INFINITY;
+  iw[IW_DONE * W + lane] = lane >= k.P.count; iw[IW_STATUS * W + lane] = OSQP_UNSOLVED; iw[IW_RHOUPD * W + lane] = 0; iw[IW_PCG * W + lane] = 0;
+  iw[IW_RELRULE * W + lane] = 1; iw[IW_CGON * W + lane] = 0; iw[IW_RHOCH * W + lane] = 1;
+  if (threadIdx.x == 0) { k.w.word[WD_CGANY] = 0; k.w.word[WD_LIVE] = k.P.count; k.w.word[WD_RHOANY] = 1; k.w.word[WD_PCGSUM] = 0; k.w.word[WD_CGIT] = 0; }
+}
+
+// x = D x, y = cinv E y (_osqp.py:1110-1112); certificates in place of x / y for infeasible problems; the records
+__global__ __launch_bounds__(256) void k_ls_store_n(LsK k) {
+  __shared__ double tile[64][65];
+  const LockstepParams &P = k.P;
+  const int lane = ls_lane(), wv = ls_wave(), j0 = blockIdx.x * 64, status = k.w.iw[IW_STATUS * W + lane];
+  const bool pinf = status == OSQP_PRIMAL_INFEASIBLE || status == OSQP_PRIMAL_INFEASIBLE_INACCURATE;
+  const bool dinf = status == OSQP_DUAL_INFEASIBLE || status == OSQP_DUAL_INFEASIBLE_INACCURATE;
+  for (int jl = wv; jl < 64 && j0 + jl < P.n; jl += 4) {
+    const int j = j0 + jl;
+    const double dxj = k.w.dx[IX(j)], xj = k.w.x[IX(j)];
+    tile[lane][jl] = dinf ? (P.unscaled ? P.D[j] * dxj : dxj) : (pinf ? NAN : (P.scaling ? P.D[j] * xj : xj));
+  }
+  ls_tile_out(P.x, P.n, j0, P.count, P.pc, tile);
+  if (blockIdx.x == 0) for (int e = threadIdx.x; e < P.count * kBatchRec; e += 256) P.rec[e] = k.w.rec[e];
+}
+__global__ __launch_bounds__(256) void k_ls_store_m(LsK k) {
+  __shared__ double tile[64][65];
+  const LockstepParams &P = k.P;
+  const int lane = ls_lane(), wv = ls_wave(), i0 = blockIdx.x * 64, status = k.w.iw[IW_STATUS * W + lane];
+  const bool pinf = status == OSQP_PRIMAL_INFEASIBLE || status == OSQP_PRIMAL_INFEASIBLE_INACCURATE;
+  const bool dinf = status == OSQP_DUAL_INFEASIBLE || status == OSQP_DUAL_INFEASIBLE_INACCURATE;
+  for (int il = wv; il < 64 && i0 + il < P.m; il += 4) {
+    const int i = i0 + il;
+    const double dyi = k.w.dy[IX(i)], yi = k.w.y[IX(i)];
+    tile[lane][il] = pinf ? (P.unscaled ? P.E[i] * dyi : dyi) : (dinf ? NAN : (P.scaling ? P.cinv * P.E[i] * yi : yi));
+  }
+  ls_tile_out(P.y, P.m, i0, P.count, P.pr, tile);
+}
+#undef IX
+
+}  // namespace
+
+// One chunk of at most kLsW problems, from the transposes in to the transposes out, on `stream` (nullptr: the solver's); returns when the chunk's
+// results are in p.x / p.y / p.rec.  stat: {ADMM iterations of the slowest problem, PCG iterations summed, kernel launches, GPU ms}.
+int lockstep_chunk(Dev &d, const LockstepParams &p, void *stream, double *stat) {
+  HIP_CHECK(hipSetDevice(d.device));
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : st(d);
+  const int n = p.n, m = p.m, G = lockstep_grid(n, m), tn = (n + 63) / 64, tm = (m + 63) / 64;
+  const size_t nW = (size_t)n * W, mW = (size_t)m * W;
+  LsK k{p, {}};
+  LsWs &w = k.w;
+  double *c = p.ws;
+  auto take = [&c](size_t cnt) { double *r = c; c += cnt; return r; };
+  w.x = take(nW); w.xs = take(nW); w.r = take(nW); w.p = take(nW); w.Kp = take(nW); w.q = take(nW); w.Minv = take(nW); w.dx = take(nW);
+  w.z = take(mW); w.y = take(mW); w.t = take(mW); w.t2 = take(mW); w.l = take(mW); w.u = take(mW); w.rho = take(mW); w.zt = take(mW); w.dy = take(mW);
+  w.part = take((size_t)kLsSlots * G * W); w.parti = take((size_t)(tm > 0 ? tm : 1) * W); w.sc = take((size_t)kLsScal * W); w.rec = take((size_t)W * kBatchRec);
+  w.iw = reinterpret_cast<int *>(take((size_t)kLsInt * W / 2)); w.word = w.iw + IW_COUNT * W;
+  w.G = G;
+  if ((size_t)(c - p.ws) > lockstep_ws_doubles(n, m)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  long launches = 0;
+  auto go = [&](auto kern, int grid, auto... args) { hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, k, args...); launches++; };
+  hipEvent_t e0, e1;
+  HIP_CHECK(hipEventCreate(&e0)); HIP_CHECK(hipEventCreate(&e1));
+  HIP_CHECK(hipEventRecord(e0, s));
+  const double t_begin = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+  int words[WD_COUNT] = {0, p.count, 0, 0, 0};
+  auto fetch = [&]() { HIP_CHECK(hipMemcpyAsync(words, w.word, sizeof(words), hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s)); };
+  auto residuals = [&]() { if (m > 0) go(k_ls_resm, G); go(k_ls_resn, G); };
+  auto new_rho = [&]() { if (m > 0) go(k_ls_setrho, G); go(k_ls_minv, G); };
+
+  go(k_ls_load_n, tn);
+  if (m > 0) go(k_ls_load_m, tm);
+  go(k_ls_init, 1, m > 0 ? tm : 0);
+  new_rho();
+  if (m > 0) go(k_ls_initz, G);
+  residuals();
+  go(k_ls_decide, 1, 0, 0, 0, 1);
+  int iter = 0, cg_est = 4;
+  while (words[WD_LIVE] > 0 && iter < p.max_iter) {
+    iter++;
+    go(k_ls_rhs, G);
+    go(k_ls_cginit, 1);
+    // PCG: as many iterations as the previous ADMM iteration needed (+ 1) are enqueued without synchronising; then the host reads the words and
+    // goes on in groups of four while some problem's PCG is still running, up to cg_max_iter.  The estimate decides how many launches return at
+    // once, never how far a problem's PCG runs.
+    for (int it = 0, grp = cg_est; it < p.cg_max; grp = 4) {
+      for (const int end = std::min(it + grp, p.cg_max); it < end; it++) {
+        if (m > 0) go(k_ls_t, G);
+        go(k_ls_kp, G); go(k_ls_cgalpha, 1); go(k_ls_cgupd, G); go(k_ls_cgbeta, 1); go(k_ls_cgp, G);
+      }
+      fetch();
+      if (!words[WD_CGANY]) break;
+    }
+    cg_est = std::max(2, words[WD_CGIT] + 1);
+    go(k_ls_upd, G);
+    const int at_check = (p.check > 0 && iter % p.check == 0) || iter >= p.max_iter;
+    const int at_rho = p.rho_interval > 0 && iter % p.rho_interval == 0;
+    const bool late = p.time_limit > 0 && std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - t_begin > p.time_limit;
+    if (!at_check && !at_rho && !late) continue;
+    residuals();
+    go(k_ls_decide, 1, iter, late ? 1 : at_check, at_rho, late ? 2 : 0);
+    if (at_rho && !late) new_rho();
+    if (at_check || late) fetch();
+  }
+  go(k_ls_store_n, tn);
+  if (m > 0) go(k_ls_store_m, tm);
+  HIP_CHECK(hipEventRecord(e1, s));
+  fetch();
+  float ms = 0.f;
+  HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+  HIP_CHECK(hipEventDestroy(e0)); HIP_CHECK(hipEventDestroy(e1));
+  HIP_CHECK(hipGetLastError());
+  if (stat) { stat[0] = iter; stat[1] = words[WD_PCGSUM]; stat[2] = (double)launches; stat[3] = ms; }
+  return OSQP_NO_ERROR;
+}
+
+}  // namespace be
+}  // namespace osqp_hip

@@ -127,6 +127,9 @@ PROTOTYPES = {
     'osqp_hip_batch_solve_mat_device': (C.c_int, [SolverP, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     'osqp_hip_adjoint_compute_at': (C.c_int, [SolverP] + [c_double_p] * 4),
     'osqp_hip_adjoint_last_record': (C.c_int, [SolverP, c_double_p]),
+    'osqp_hip_batch_solve_lockstep': (C.c_int, [SolverP, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int]),
+    'osqp_hip_batch_solve_lockstep_device': (C.c_int, [SolverP, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    'osqp_hip_lockstep_last_record': (C.c_int, [SolverP, c_double_p]),
     'osqp_hip_batch_adjoint': (C.c_int, [SolverP, C.c_int] + [c_double_p] * 14),
     'osqp_hip_batch_adjoint_device': (C.c_int, [SolverP, C.c_int] + [C.c_void_p] * 15),
     'osqp_hip_capabilities': (C.c_int, []),

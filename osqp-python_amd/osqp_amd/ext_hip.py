@@ -376,6 +376,49 @@ class OSQPSolver:
         if st:
             raise self._batch_error(st)
 
+    def hip_batch_solve_lockstep(self, q=None, l=None, u=None, x0=None, y0=None, nbatch=None):
+        """hip_batch_solve for problems of ANY size (osqp_hip_batch_solve_lockstep): shared P / A, 64 problems at a time on block vectors.
+        Same arguments (no Px / Ax), same checks, same returns: x (B, n), y (B, m), rec (B, BATCH_REC)."""
+        arrs = [a for a in (q, l, u, x0, y0) if a is not None]
+        B = int(nbatch) if nbatch is not None else int(np.asarray(arrs[0]).shape[0])
+
+        def rows(a, name, width):
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.size != B * width or (a.ndim > 1 and a.shape[-1] != width):
+                raise ValueError('%s: expected %d problems of width %d, got shape %s' % (name, B, width, a.shape))
+            return a.reshape(B, width)
+        q, l, u = (None if a is None else rows(a, name, w) for a, name, w in ((q, 'q', self.n), (l, 'l', self.m), (u, 'u', self.m)))
+        warm = x0 is not None or y0 is not None      # a missing one starts from zero, as in hip_batch_solve
+        x = np.zeros((B, self.n)) if x0 is None else rows(x0, 'x0', self.n).copy()
+        y = np.zeros((B, self.m)) if y0 is None else rows(y0, 'y0', self.m).copy()
+        rec = np.zeros((B, self.BATCH_REC))
+        st = self._lib.osqp_hip_batch_solve_lockstep(self._p, B, _ptr(q, _lib.c_double_p), _ptr(l, _lib.c_double_p), _ptr(u, _lib.c_double_p),
+                                                     _ptr(x, _lib.c_double_p), _ptr(y, _lib.c_double_p), _ptr(rec, _lib.c_double_p), int(warm))
+        if st:
+            raise self._batch_error(st)
+        return x, y, rec
+
+    def hip_batch_solve_lockstep_device(self, nbatch, q_ptr, l_ptr, u_ptr, x_ptr, y_ptr, rec_ptr, warm=False, stream=None):
+        """osqp_hip_batch_solve_lockstep_device: raw device addresses (int or None) laid out as in hip_batch_solve_lockstep; the work goes on `stream`
+        (None: the solver's) and the call returns when the results are there.  nbatch == 0: does the route apply?"""
+        st = self._lib.osqp_hip_batch_solve_lockstep_device(self._p, int(nbatch), q_ptr, l_ptr, u_ptr, x_ptr, y_ptr, rec_ptr, int(bool(warm)), stream)
+        if st:
+            raise self._batch_error(st)
+
+    # OSQP_HIP_LOCKSTEP_LAST_REC doubles of osqp_hip_lockstep_last_record
+    LOCKSTEP_LAST_FIELDS = ('chunks', 'width', 'admm_iters_max', 'pcg_iters', 'kernel_launches', 'gpu_ms', 'workspace_bytes', 'reserved')
+
+    def lockstep_last_record(self):
+        """osqp_hip_lockstep_last_record as a dict (LOCKSTEP_LAST_FIELDS): what the last lockstep call of this handle did; zeros before the first."""
+        rec = np.zeros(len(self.LOCKSTEP_LAST_FIELDS))
+        st = self._lib.osqp_hip_lockstep_last_record(self._p, _ptr(rec, _lib.c_double_p))
+        if st:
+            raise ValueError(str(int(st)))
+        out = dict(zip(self.LOCKSTEP_LAST_FIELDS, rec.tolist()))
+        for k in ('chunks', 'width', 'admm_iters_max', 'pcg_iters', 'kernel_launches', 'workspace_bytes'):
+            out[k] = int(out[k])
+        return out
+
     ADJOINT_FIELDS = ('status', 'active_rows', 'residual', 'reserved')
     ADJOINT_REC = len(ADJOINT_FIELDS)    # OSQP_HIP_ADJOINT_REC
     ADJOINT_TOL = 1e-6                   # OSQP_HIP_ADJOINT_TOL
