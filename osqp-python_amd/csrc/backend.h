@@ -331,12 +331,15 @@ constexpr int kBatchNB = 8;             // pivots per block of the batch kernel'
 constexpr int kBatchDirectMaxBw = 64 - kBatchNB;   // band limit of the batch kernel's direct solve: one wave holds the live window of a block
 
 constexpr int kBatchRec = 12;     // doubles per problem in the result record of the batch kernels (OSQP_HIP_BATCH_REC in include/osqp_hip.h)
-struct BatchParams {
+// The settings snapshot every batch route runs with (Engine::fill_batch_settings): base of BatchParams and LockstepParams
+struct BatchSettings {
+  double c = 1, cinv = 1, sigma = 0, alpha = 0, rho0 = 0, eq_factor = 0, eps_abs = 0, eps_rel = 0, eps_pinf = 0, eps_dinf = 0, cg_frac = 0, rho_tol = 0;
+  int max_iter = 0, check = 0, rho_interval = 0, cg_max = 0, unscaled = 0, scaling = 0, precond = 0, rho_is_vec = 0, warm = 0;
+};
+struct BatchParams : BatchSettings {
   int n, m, nbatch;
   DevCsr A, B;
   const double *D, *Dinv, *E, *Einv;
-  double c, cinv, sigma, alpha, rho0, eq_factor, eps_abs, eps_rel, eps_pinf, eps_dinf, cg_frac, rho_tol;
-  int max_iter, check, rho_interval, cg_max, unscaled, scaling, precond, rho_is_vec, warm;
   const double *q, *l, *u;      // UNSCALED, [nbatch][n] / [nbatch][m]; nullptr = the shared vector q0 / l0 / u0 for every problem
   const double *q0, *l0, *u0;   // UNSCALED shared vectors [n] / [m]
   double *x, *y;                // in: UNSCALED warm start (if warm), out: UNSCALED solution  [nbatch][n] / [nbatch][m]
@@ -474,13 +477,11 @@ inline int lockstep_grid(int n, int m) { const int r = n > m ? n : m, g = (r + 1
 inline size_t lockstep_ws_doubles(int n, int m) {
   return (size_t)kLsW * (8 * (size_t)n + 9 * (size_t)m + (size_t)kLsSlots * lockstep_grid(n, m) + (size_t)(m + 63) / 64 + 1 + kLsScal + kBatchRec + kLsInt) + 64;
 }
-struct LockstepParams {
+struct LockstepParams : BatchSettings {
   int n = 0, m = 0, count = 0;  // count: problems of this chunk (1 .. kLsW)
   DevCsr A, B;
   const double *D = nullptr, *Dinv = nullptr, *E = nullptr, *Einv = nullptr;
-  double c = 1, cinv = 1, sigma = 0, alpha = 0, rho0 = 0, eq_factor = 0, eps_abs = 0, eps_rel = 0, eps_pinf = 0, eps_dinf = 0, cg_frac = 0, rho_tol = 0;
   double time_limit = 0;        // seconds this chunk may still take (<= 0: none)
-  int max_iter = 0, check = 0, rho_interval = 0, cg_max = 0, unscaled = 0, scaling = 0, precond = 0, rho_is_vec = 0, warm = 0;
   const double *q = nullptr, *l = nullptr, *u = nullptr;        // the chunk's rows of the UNSCALED [nbatch][n] / [nbatch][m] arrays, the CALLER's numbering; nullptr = the shared vector
   const double *q0 = nullptr, *l0 = nullptr, *u0 = nullptr;     // UNSCALED shared vectors, the ENGINE's numbering
   double *x = nullptr, *y = nullptr, *rec = nullptr;            // the chunk's rows: in UNSCALED warm start (if warm), out UNSCALED solution; [count][kBatchRec]

@@ -18,6 +18,7 @@
 
 #include "../../include/osqp_hip.h"
 #include "backend.h"
+#include "term_rules.h"
 
 namespace osqp_hip {
 namespace be {
@@ -656,7 +657,8 @@ __global__ __launch_bounds__(kBB, (DIRECT && kBB == 256 && EA <= 8) ? (SPEC ? SP
   __syncthreads();
 
   // residuals of the current (x, z, y): returns through references; all threads hold identical values
-  double pri_u, ax_u, z_u, pri_s, ax_s, z_s, dy_u, dy_s, pinf_lhs, dua_u, px_u, aty_u, dua_s, px_s, aty_s, dxn_u, dxn_s, xpx, qx, qdx, qn_s, qn_u;
+  TermRes R;
+  const TermSet tset = {P.eps_abs, P.eps_rel, P.eps_pinf, P.eps_dinf, P.c, P.cinv, m, P.unscaled, P.scaling};
   auto residuals = [&]() {
     double a1 = 0, a2 = 0, a3 = 0, a4 = 0, a5 = 0, a6 = 0, a7 = 0, a8 = 0, s1 = 0;
     for (int i = tid; i < m; i += kBB) {
@@ -670,7 +672,7 @@ __global__ __launch_bounds__(kBB, (DIRECT && kBB == 256 && EA <= 8) ? (SPEC ? SP
     }
     { double g1[4] = {a1, a2, a3, a4}, g2[4] = {a5, a6, a7, a8}, g3[1] = {s1}, none[1] = {0.0};
       red.template max_sum_n<4, 0>(g1, none); red.template max_sum_n<4, 0>(g2, none); red.template max_sum_n<0, 1>(none, g3);
-      pri_u = g1[0]; ax_u = g1[1]; z_u = g1[2]; pri_s = g1[3]; ax_s = g2[0]; z_s = g2[1]; dy_u = g2[2]; dy_s = g2[3]; pinf_lhs = g3[0]; }
+      R.pri_u = g1[0]; R.ax_u = g1[1]; R.z_u = g1[2]; R.pri_s = g1[3]; R.ax_s = g2[0]; R.z_s = g2[1]; R.dy_u = g2[2]; R.dy_s = g2[3]; R.pinf_lhs = g3[0]; }
     double b1 = 0, b2 = 0, b3 = 0, b4 = 0, b5 = 0, b6 = 0, b7 = 0, b8 = 0, b9 = 0, b10 = 0, t1 = 0, t2 = 0, t3 = 0;
     for (int j = tid; j < n; j += kBB) {
       double sp = 0.0, sa = 0.0;
@@ -683,17 +685,47 @@ __global__ __launch_bounds__(kBB, (DIRECT && kBB == 256 && EA <= 8) ? (SPEC ? SP
     }
     { double g1[4] = {b1, b2, b3, b4}, g2[4] = {b5, b6, b7, b8}, g3[2] = {b9, b10}, sm[2] = {t1, t2}, g4[1] = {t3}, none[1] = {0.0};
       red.template max_sum_n<4, 0>(g1, none); red.template max_sum_n<4, 0>(g2, none); red.template max_sum_n<2, 2>(g3, sm); red.template max_sum_n<0, 1>(none, g4);
-      dua_u = g1[0]; px_u = g1[1]; aty_u = g1[2]; dua_s = g1[3]; px_s = g2[0]; aty_s = g2[1]; dxn_u = g2[2]; dxn_s = g2[3]; qn_s = g3[0]; qn_u = g3[1];
-      xpx = sm[0]; qx = sm[1]; qdx = g4[0]; }
+      R.dua_u = g1[0]; R.px_u = g1[1]; R.aty_u = g1[2]; R.dua_s = g1[3]; R.px_s = g2[0]; R.aty_s = g2[1]; R.dxn_u = g2[2]; R.dxn_s = g2[3]; R.qn_s = g3[0]; R.qn_u = g3[1];
+      R.xpx = sm[0]; R.qx = sm[1]; R.qdx = g4[0]; }
   };
 
   int status = OSQP_UNSOLVED, iter = 0, rho_updates = 0;
   long pcg_total = 0;
   double obj = 0, prim_res = 0, dual_res = 0;
   residuals();
-  double eps_cg = P.cg_frac * dua_s, eps_prev = INFINITY;
-  bool rel_rule = !(eps_cg > 1e-13) || !isfinite(eps_cg);
+  double eps_cg, eps_prev;
+  bool rel_rule;
+  batch_tol_init(P.cg_frac, R.dua_s, &eps_prev, &eps_cg, &rel_rule);
   const bool unsc = P.unscaled != 0;
+  // the second stages of the infeasibility tests (term_rules.h batch_check calls them when a first stage passed: uniform over the workgroup)
+  auto pinf_stage2 = [&](double &mu, double &ms) {                                     // A' dy   (is_primal_infeasible :815-818)
+    for (int j = tid; j < n; j += kBB) {
+      double sa = 0.0;
+      for (int k = B.rowptr[j]; k < B.rowptr[j + 1]; k++) { const int c = B.col[k]; if (c >= n) sa += B.val[k] * dy[c - n]; }
+      mu = nmax(mu, fabs(P.Dinv[j] * sa)); ms = nmax(ms, fabs(sa));
+    }
+    mu = red.max(mu); ms = red.max(ms);
+  };
+  auto pdx_stage2 = [&](double &mu, double &ms) {                                      // P dx    (is_dual_infeasible :846-853)
+    for (int j = tid; j < n; j += kBB) {
+      double sp = 0.0;
+      for (int k = B.rowptr[j]; k < B.rowptr[j + 1]; k++) { const int c = B.col[k]; if (c < n) sp += B.val[k] * dx[c]; }
+      sp -= P.sigma * dx[j];
+      mu = nmax(mu, fabs(P.Dinv[j] * sp)); ms = nmax(ms, fabs(sp));
+    }
+    mu = red.max(mu); ms = red.max(ms);
+  };
+  auto adx_stage2 = [&](double thr) {                                                  // A dx    (:855-872)
+    double viol = 0;
+    for (int i = tid; i < m; i += kBB) {
+      double a = 0.0;
+      for (int k = A.rowptr[i]; k < A.rowptr[i + 1]; k++) a += A.val[k] * dx[A.col[k]];
+      if (unsc) a *= P.Einv[i];
+      if ((u[i] < OSQP_INFTY * 1e-4 && a > thr) || (l[i] > -OSQP_INFTY * 1e-4 && a < -thr)) viol += 1.0;
+    }
+    viol = red.sum(viol);
+    return viol == 0.0;
+  };
 
   while (true) {
     iter++;
@@ -761,72 +793,12 @@ __global__ __launch_bounds__(kBB, (DIRECT && kBB == 256 && EA <= 8) ? (SPEC ? SP
     BT2_BEGIN();
     residuals();
     BT2_END(tk_res);
-    obj = (0.5 * xpx + qx) * (P.scaling ? P.cinv : 1.0);                               // _osqp.py:705-712
-    prim_res = m == 0 ? 0.0 : (unsc ? pri_u : pri_s);
-    dual_res = unsc ? P.cinv * dua_u : dua_s;
-    bool stop = false;
-    for (int approx = 0; approx < 2 && !stop && at_check; approx++) {                  // _osqp.py:998-1077, :1264-1266
-      if (approx && iter < P.max_iter) break;
-      const double f = approx ? 10.0 : 1.0;
-      const double ea = f * P.eps_abs, er = f * P.eps_rel, epi = f * P.eps_pinf, edi = f * P.eps_dinf;
-      if (prim_res > OSQP_INFTY || dual_res > OSQP_INFTY || prim_res != prim_res || dual_res != dual_res) { status = OSQP_NON_CVX; obj = NAN; stop = true; break; }
-      bool pri_ok = false, dua_ok = false, pinf = false, dinf = false;
-      if (m == 0) pri_ok = true;
-      else if (prim_res < ea + er * (unsc ? fmax(ax_u, z_u) : fmax(ax_s, z_s))) pri_ok = true;
-      else {                                                                          // is_primal_infeasible :796-820
-        const double nd = unsc ? dy_u : dy_s;
-        if (nd > epi && pinf_lhs < -epi * nd) {
-          double mu = 0, ms = 0;
-          for (int j = tid; j < n; j += kBB) {
-            double sa = 0.0;
-            for (int k = B.rowptr[j]; k < B.rowptr[j + 1]; k++) { const int c = B.col[k]; if (c >= n) sa += B.val[k] * dy[c - n]; }
-            mu = nmax(mu, fabs(P.Dinv[j] * sa)); ms = nmax(ms, fabs(sa));
-          }
-          mu = red.max(mu); ms = red.max(ms);
-          pinf = (unsc ? mu : ms) < epi * nd;
-        }
-      }
-      const double mx = unsc ? P.cinv * fmax(fmax(aty_u, px_u), qn_u) : fmax(fmax(aty_s, px_s), qn_s);
-      if (dual_res < ea + er * mx) dua_ok = true;
-      else {                                                                          // is_dual_infeasible :822-878
-        const double nd = unsc ? dxn_u : dxn_s, sc = unsc ? P.c : 1.0;
-        if (nd > edi && qdx < -sc * edi * nd) {
-          double mu = 0, ms = 0, viol = 0;
-          for (int j = tid; j < n; j += kBB) {
-            double sp = 0.0;
-            for (int k = B.rowptr[j]; k < B.rowptr[j + 1]; k++) { const int c = B.col[k]; if (c < n) sp += B.val[k] * dx[c]; }
-            sp -= P.sigma * dx[j];
-            mu = nmax(mu, fabs(P.Dinv[j] * sp)); ms = nmax(ms, fabs(sp));
-          }
-          mu = red.max(mu); ms = red.max(ms);
-          if ((unsc ? mu : ms) < sc * edi * nd) {
-            for (int i = tid; i < m; i += kBB) {
-              double a = 0.0;
-              for (int k = A.rowptr[i]; k < A.rowptr[i + 1]; k++) a += A.val[k] * dx[A.col[k]];
-              if (unsc) a *= P.Einv[i];
-              if ((u[i] < OSQP_INFTY * 1e-4 && a > edi * nd) || (l[i] > -OSQP_INFTY * 1e-4 && a < -edi * nd)) viol += 1.0;
-            }
-            viol = red.sum(viol);
-            dinf = viol == 0.0;
-          }
-        }
-      }
-      if (pri_ok && dua_ok) { status = approx ? OSQP_SOLVED_INACCURATE : OSQP_SOLVED; stop = true; }
-      else if (pinf) { status = approx ? OSQP_PRIMAL_INFEASIBLE_INACCURATE : OSQP_PRIMAL_INFEASIBLE; obj = OSQP_INFTY; stop = true; }
-      else if (dinf) { status = approx ? OSQP_DUAL_INFEASIBLE_INACCURATE : OSQP_DUAL_INFEASIBLE; obj = -OSQP_INFTY; stop = true; }
-    }
-    if (stop) break;
-    if (iter >= P.max_iter) { status = OSQP_MAX_ITER_REACHED; break; }
-    if (at_rho) {                                                                      // adapt_rho :880-930
-      const double pr = pri_s / (fmax(ax_s, z_s) + 1e-10), du = dua_s / (fmax(fmax(aty_s, px_s), qn_s) + 1e-10);
-      double rn_ = rho_bar * sqrt(pr / (du + 1e-10));
-      rn_ = fmin(fmax(rn_, 1e-6), 1e6);
-      if (rn_ > P.rho_tol * rho_bar || rn_ < rho_bar / P.rho_tol) { rho_bar = rn_; set_rho(rho_bar); rho_updates++; }
-    }
-    double e2 = P.cg_frac * dua_s;                                                     // inner tolerance: engine.cpp solve()
-    if (m == 0) e2 = P.cg_frac * dua_s;
-    e2 = fmax(fmin(e2, eps_prev), 1e-13);
-    if (isfinite(e2)) { eps_prev = e2; eps_cg = e2; rel_rule = false; }
+    term_info(tset, R, &obj, &prim_res, &dual_res);
+    const int st = batch_check(tset, R, prim_res, dual_res, iter, P.max_iter, at_check, pinf_stage2, pdx_stage2, adx_stage2, &obj);
+    if (st != kBatchGoOn) { status = st; break; }
+    double rho_new;
+    if (at_rho && batch_rho_rule(rho_bar, P.rho_tol, R, &rho_new)) { rho_bar = rho_new; set_rho(rho_bar); rho_updates++; }
+    batch_tol_rule(P.cg_frac, R.dua_s, &eps_prev, &eps_cg, &rel_rule);                 // inner tolerance: engine.cpp solve()
   }
   // ---- polish (_osqp.py:1710-1828), direct variants only: the reference's algorithm on the factor already in LDS ----
   // Active rows guessed from the scaled (z, y) (:1719-1720); the regularised reduced KKT system
@@ -837,7 +809,7 @@ __global__ __launch_bounds__(kBB, (DIRECT && kBB == 256 && EA <= 8) ? (SPEC ? SP
   //     t = y - (b - A_act x) / delta,   rhs = -q - P x - A_act' t,   dx = K^-1 rhs,   x += dx,   y = t + A_act dx / delta.
   // Then z = A x, the normal-cone projection (:1773-1780) and the accept test on the residuals (:1786-1793).
   // rho estimate of the ADMM point (_osqp.py:1275, :880-908), before any polish
-  const double rho_est = fmin(fmax(rho_bar * sqrt((pri_s / (fmax(ax_s, z_s) + 1e-10)) / (dua_s / (fmax(fmax(aty_s, px_s), qn_s) + 1e-10) + 1e-10)), 1e-6), 1e6);
+  const double rho_est = term_rho_estimate(rho_bar, R);
   int status_polish = 0;
   [[maybe_unused]] unsigned long long pol_ticks = 0;
   if constexpr (DIRECT && POLISH) {
@@ -882,9 +854,10 @@ __global__ __launch_bounds__(kBB, (DIRECT && kBB == 256 && EA <= 8) ? (SPEC ? SP
       applyA(x, [&](int i, double ax) { const double tmp = ax + y[i], zc = fmin(fmax(tmp, l[i]), u[i]); z[i] = zc; y[i] = tmp - zc; });
       const double pri0 = prim_res, dua0 = dual_res;
       residuals();
-      const double ppri = m == 0 ? 0.0 : (unsc ? pri_u : pri_s), pdua = unsc ? P.cinv * dua_u : dua_s;
+      double pobj, ppri, pdua;
+      term_info(tset, R, &pobj, &ppri, &pdua);
       const bool ok = (ppri < pri0 && pdua < dua0) || (ppri < pri0 && dua0 < 1e-10) || (pdua < dua0 && pri0 < 1e-10);
-      if (ok) { obj = (0.5 * xpx + qx) * (P.scaling ? P.cinv : 1.0); prim_res = ppri; dual_res = pdua; status_polish = 1; }
+      if (ok) { obj = pobj; prim_res = ppri; dual_res = pdua; status_polish = 1; }
       else {
         status_polish = -1;
         for (int j = tid; j < n; j += kBB) x[j] = p[j];
@@ -895,16 +868,13 @@ __global__ __launch_bounds__(kBB, (DIRECT && kBB == 256 && EA <= 8) ? (SPEC ? SP
     }
   }
   // ---- store: x = D x, y = cinv E y (_osqp.py:1110-1112); certificates in place of x / y for infeasible problems ----
-  const bool pinf = status == OSQP_PRIMAL_INFEASIBLE || status == OSQP_PRIMAL_INFEASIBLE_INACCURATE;
-  const bool dinf = status == OSQP_DUAL_INFEASIBLE || status == OSQP_DUAL_INFEASIBLE_INACCURATE;
-  for (int j = tid; j < n; j += kBB) P.x[(size_t)b * n + j] = dinf ? (unsc ? P.D[j] * dx[j] : dx[j]) : (pinf ? NAN : (P.scaling ? P.D[j] * x[j] : x[j]));
+  for (int j = tid; j < n; j += kBB) P.x[(size_t)b * n + j] = batch_out_x(status, P.unscaled, P.scaling, P.D[j], x[j], dx[j]);
   if (P.zs) for (int i = tid; i < m; i += kBB) P.zs[(size_t)b * m + i] = z[i];
-  for (int i = tid; i < m; i += kBB) P.y[(size_t)b * m + i] = pinf ? (unsc ? P.E[i] * dy[i] : dy[i]) : (dinf ? NAN : (P.scaling ? P.cinv * P.E[i] * y[i] : y[i]));
+  for (int i = tid; i < m; i += kBB) P.y[(size_t)b * m + i] = batch_out_y(status, P.unscaled, P.scaling, P.cinv, P.E[i], y[i], dy[i]);
   if (tid == 0) {
     double *rc = P.rec + (size_t)b * kBatchRec;
-    rc[0] = status; rc[1] = iter; rc[2] = obj; rc[3] = prim_res; rc[4] = dual_res; rc[5] = rho_bar; rc[6] = rho_updates; rc[7] = (double)pcg_total;
+    batch_record(rc, status, iter, obj, prim_res, dual_res, rho_bar, rho_updates, (double)pcg_total, rho_est);
     rc[8] = status_polish; rc[9] = 1e-8 * (double)pol_ticks;      // (100 MHz wall clock -> seconds)
-    rc[10] = rho_est; rc[11] = 0.0;
     if (P.iters_out) P.iters_out[b] = iter;
 #ifdef OSQP_HIP_KTRACE
     rc[5] = (double)tk_fact; rc[6] = (double)tk_solve; rc[7] = (double)(wall_clock64() - tk_all);
@@ -1072,6 +1042,7 @@ __global__ __launch_bounds__(64 * kBatchWaveW, 1) void k_batch_wave(BatchParams 
     v_mul(vn[0] ? dk0 * w0 : 0.0, vn[1] ? dk1 * w1 : 0.0, out[0], out[1]);
   };
   const bool unsc = P.unscaled != 0;
+  const TermSet tset = {P.eps_abs, P.eps_rel, P.eps_pinf, P.eps_dinf, P.c, P.cinv, m, P.unscaled, P.scaling};
   bool first = true;
 
   while (true) {
@@ -1125,8 +1096,7 @@ __global__ __launch_bounds__(64 * kBatchWaveW, 1) void k_batch_wave(BatchParams 
 #pragma unroll
       for (int s = 0; s < 4; s++) if (vm[s]) z[s] = P.zs[(size_t)b * m + rowm[s]];
     }
-    double pri_u = 0, ax_u = 0, z_u = 0, pri_s = 0, ax_s = 0, z_s = 0, dy_u = 0, dy_s = 0, pinf_lhs = 0, dua_u = 0, px_u = 0, aty_u = 0, dua_s = 0, px_s = 0, aty_s = 0,
-           dxn_u = 0, dxn_s = 0, xpx = 0, qx = 0, qdx = 0, qn_s = 0, qn_u = 0;
+    TermRes R = {};
     auto residuals = [&]() {
       double a1 = 0, a2 = 0, a3 = 0, a4 = 0, a5 = 0, a6 = 0, a7 = 0, a8 = 0, s1 = 0;
       stage_n(x);
@@ -1141,7 +1111,7 @@ __global__ __launch_bounds__(64 * kBatchWaveW, 1) void k_batch_wave(BatchParams 
         a7 = nmax(a7, fabs(P.E[i] * dyi)); a8 = nmax(a8, fabs(dyi));
         s1 += u[s] * fmax(dyi, 0.0) + l[s] * fmin(dyi, 0.0);
       }
-      pri_u = wmax(a1); ax_u = wmax(a2); z_u = wmax(a3); pri_s = wmax(a4); ax_s = wmax(a5); z_s = wmax(a6); dy_u = wmax(a7); dy_s = wmax(a8); pinf_lhs = wsum(s1);
+      R.pri_u = wmax(a1); R.ax_u = wmax(a2); R.z_u = wmax(a3); R.pri_s = wmax(a4); R.ax_s = wmax(a5); R.z_s = wmax(a6); R.dy_u = wmax(a7); R.dy_s = wmax(a8); R.pinf_lhs = wsum(s1);
       stage_m(y);
       mulT(sa);
       double b1 = 0, b2 = 0, b3 = 0, b4 = 0, b5 = 0, b6 = 0, b7 = 0, b8 = 0, b9 = 0, b10 = 0, t1 = 0, t2 = 0, t3 = 0;
@@ -1154,8 +1124,36 @@ __global__ __launch_bounds__(64 * kBatchWaveW, 1) void k_batch_wave(BatchParams 
         b7 = nmax(b7, fabs(P.D[j] * dx[s])); b8 = nmax(b8, fabs(dx[s])); b9 = nmax(b9, fabs(q[s])); b10 = nmax(b10, fabs(di * q[s]));
         t1 += x[s] * px; t2 += q[s] * x[s]; t3 += q[s] * dx[s];
       }
-      dua_u = wmax(b1); px_u = wmax(b2); aty_u = wmax(b3); dua_s = wmax(b4); px_s = wmax(b5); aty_s = wmax(b6); dxn_u = wmax(b7); dxn_s = wmax(b8); qn_s = wmax(b9); qn_u = wmax(b10);
-      xpx = wsum(t1); qx = wsum(t2); qdx = wsum(t3);
+      R.dua_u = wmax(b1); R.px_u = wmax(b2); R.aty_u = wmax(b3); R.dua_s = wmax(b4); R.px_s = wmax(b5); R.aty_s = wmax(b6); R.dxn_u = wmax(b7); R.dxn_s = wmax(b8);
+      R.qn_s = wmax(b9); R.qn_u = wmax(b10);
+      R.xpx = wsum(t1); R.qx = wsum(t2); R.qdx = wsum(t3);
+    };
+    // the second stages of the infeasibility tests (term_rules.h batch_check calls them when a first stage passed: uniform over the wave)
+    auto pinf_stage2 = [&](double &mu, double &ms) {                                     // A' dy   (is_primal_infeasible :815-818)
+      double sa[2];
+      stage_m(dy); mulT(sa);
+#pragma unroll
+      for (int s = 0; s < 2; s++) if (vn[s]) { mu = nmax(mu, fabs(P.Dinv[s * 64 + L] * sa[s])); ms = nmax(ms, fabs(sa[s])); }
+      mu = wmax(mu); ms = wmax(ms);
+    };
+    auto pdx_stage2 = [&](double &mu, double &ms) {                                      // P dx    (is_dual_infeasible :846-853)
+      double sp[2];
+      stage_n(dx); mulP(sp);
+#pragma unroll
+      for (int s = 0; s < 2; s++) if (vn[s]) { const double v = sp[s] - P.sigma * dx[s]; mu = nmax(mu, fabs(P.Dinv[s * 64 + L] * v)); ms = nmax(ms, fabs(v)); }
+      mu = wmax(mu); ms = wmax(ms);
+    };
+    auto adx_stage2 = [&](double thr) {                                                  // A dx    (:855-872; dx is staged)
+      double adx[4], viol = 0;
+      mulA(adx);
+#pragma unroll
+      for (int s = 0; s < 4; s++) if (vm[s]) {
+        double a = adx[s];
+        if (unsc) a *= P.Einv[rowm[s]];
+        if ((u[s] < OSQP_INFTY * 1e-4 && a > thr) || (l[s] > -OSQP_INFTY * 1e-4 && a < -thr)) viol += 1.0;
+      }
+      viol = wsum(viol);
+      return viol == 0.0;
     };
     int status = OSQP_UNSOLVED, iter = 0, rho_updates = 0;
     double obj = 0, prim_res = 0, dual_res = 0;
@@ -1199,82 +1197,25 @@ __global__ __launch_bounds__(64 * kBatchWaveW, 1) void k_batch_wave(BatchParams 
       WT_MARK(c4);
       residuals();
       WT_MARK(c5); WT_ADD(tkR, c5 - c4);
-      obj = (0.5 * xpx + qx) * (P.scaling ? P.cinv : 1.0);                               // _osqp.py:705-712
-      prim_res = m == 0 ? 0.0 : (unsc ? pri_u : pri_s);
-      dual_res = unsc ? P.cinv * dua_u : dua_s;
-      bool stop = false;
-      for (int approx = 0; approx < 2 && !stop && at_check; approx++) {                  // _osqp.py:998-1077, :1264-1266
-        if (approx && iter < P.max_iter) break;
-        const double f = approx ? 10.0 : 1.0;
-        const double ea = f * P.eps_abs, er = f * P.eps_rel, epi = f * P.eps_pinf, edi = f * P.eps_dinf;
-        if (prim_res > OSQP_INFTY || dual_res > OSQP_INFTY || prim_res != prim_res || dual_res != dual_res) { status = OSQP_NON_CVX; obj = NAN; stop = true; break; }
-        bool pri_ok = false, dua_ok = false, pinf = false, dinf = false;
-        if (m == 0) pri_ok = true;
-        else if (prim_res < ea + er * (unsc ? fmax(ax_u, z_u) : fmax(ax_s, z_s))) pri_ok = true;
-        else {                                                                          // is_primal_infeasible :796-820
-          const double nd = unsc ? dy_u : dy_s;
-          if (nd > epi && pinf_lhs < -epi * nd) {
-            double sa[2], mu = 0, ms = 0;
-            stage_m(dy); mulT(sa);
-#pragma unroll
-            for (int s = 0; s < 2; s++) if (vn[s]) { mu = nmax(mu, fabs(P.Dinv[s * 64 + L] * sa[s])); ms = nmax(ms, fabs(sa[s])); }
-            mu = wmax(mu); ms = wmax(ms);
-            pinf = (unsc ? mu : ms) < epi * nd;
-          }
-        }
-        const double mx = unsc ? P.cinv * fmax(fmax(aty_u, px_u), qn_u) : fmax(fmax(aty_s, px_s), qn_s);
-        if (dual_res < ea + er * mx) dua_ok = true;
-        else {                                                                          // is_dual_infeasible :822-878
-          const double nd = unsc ? dxn_u : dxn_s, sc = unsc ? P.c : 1.0;
-          if (nd > edi && qdx < -sc * edi * nd) {
-            double sp[2], mu = 0, ms = 0, viol = 0;
-            stage_n(dx); mulP(sp);
-#pragma unroll
-            for (int s = 0; s < 2; s++) if (vn[s]) { const double v = sp[s] - P.sigma * dx[s]; mu = nmax(mu, fabs(P.Dinv[s * 64 + L] * v)); ms = nmax(ms, fabs(v)); }
-            mu = wmax(mu); ms = wmax(ms);
-            if ((unsc ? mu : ms) < sc * edi * nd) {
-              double adx[4];
-              mulA(adx);
-#pragma unroll
-              for (int s = 0; s < 4; s++) if (vm[s]) {
-                double a = adx[s];
-                if (unsc) a *= P.Einv[rowm[s]];
-                if ((u[s] < OSQP_INFTY * 1e-4 && a > edi * nd) || (l[s] > -OSQP_INFTY * 1e-4 && a < -edi * nd)) viol += 1.0;
-              }
-              viol = wsum(viol);
-              dinf = viol == 0.0;
-            }
-          }
-        }
-        if (pri_ok && dua_ok) { status = approx ? OSQP_SOLVED_INACCURATE : OSQP_SOLVED; stop = true; }
-        else if (pinf) { status = approx ? OSQP_PRIMAL_INFEASIBLE_INACCURATE : OSQP_PRIMAL_INFEASIBLE; obj = OSQP_INFTY; stop = true; }
-        else if (dinf) { status = approx ? OSQP_DUAL_INFEASIBLE_INACCURATE : OSQP_DUAL_INFEASIBLE; obj = -OSQP_INFTY; stop = true; }
-      }
-      if (stop) break;
-      if (iter >= P.max_iter) { status = OSQP_MAX_ITER_REACHED; break; }
-      if (at_rho) {                                                                      // adapt_rho :880-930
-        const double pr = pri_s / (fmax(ax_s, z_s) + 1e-10), du = dua_s / (fmax(fmax(aty_s, px_s), qn_s) + 1e-10);
-        double rn_ = rho_bar * sqrt(pr / (du + 1e-10));
-        rn_ = fmin(fmax(rn_, 1e-6), 1e6);
-        if (rn_ > P.rho_tol * rho_bar || rn_ < rho_bar / P.rho_tol) { rho_bar = rn_; set_rho(rho_bar); rho_updates++; }
-      }
+      term_info(tset, R, &obj, &prim_res, &dual_res);
+      const int st = batch_check(tset, R, prim_res, dual_res, iter, P.max_iter, at_check, pinf_stage2, pdx_stage2, adx_stage2, &obj);
+      if (st != kBatchGoOn) { status = st; break; }
+      double rho_new;
+      if (at_rho && batch_rho_rule(rho_bar, P.rho_tol, R, &rho_new)) { rho_bar = rho_new; set_rho(rho_bar); rho_updates++; }
     }
-    const double rho_est = fmin(fmax(rho_bar * sqrt((pri_s / (fmax(ax_s, z_s) + 1e-10)) / (dua_s / (fmax(fmax(aty_s, px_s), qn_s) + 1e-10) + 1e-10)), 1e-6), 1e6);
+    const double rho_est = term_rho_estimate(rho_bar, R);
     // ---- store: x = D x, y = cinv E y (_osqp.py:1110-1112); certificates in place of x / y for infeasible problems ----
-    const bool pinf = status == OSQP_PRIMAL_INFEASIBLE || status == OSQP_PRIMAL_INFEASIBLE_INACCURATE;
-    const bool dinf = status == OSQP_DUAL_INFEASIBLE || status == OSQP_DUAL_INFEASIBLE_INACCURATE;
 #pragma unroll
-    for (int s = 0; s < 2; s++) if (vn[s]) { const int j = s * 64 + L; P.x[(size_t)b * n + j] = dinf ? (unsc ? P.D[j] * dx[s] : dx[s]) : (pinf ? NAN : (P.scaling ? P.D[j] * x[s] : x[s])); }
+    for (int s = 0; s < 2; s++) if (vn[s]) { const int j = s * 64 + L; P.x[(size_t)b * n + j] = batch_out_x(status, P.unscaled, P.scaling, P.D[j], x[s], dx[s]); }
 #pragma unroll
     for (int s = 0; s < 4; s++) if (vm[s]) {
       const int i = rowm[s];
       if (P.zs) P.zs[(size_t)b * m + i] = z[s];
-      P.y[(size_t)b * m + i] = pinf ? (unsc ? P.E[i] * dy[s] : dy[s]) : (dinf ? NAN : (P.scaling ? P.cinv * P.E[i] * y[s] : y[s]));
+      P.y[(size_t)b * m + i] = batch_out_y(status, P.unscaled, P.scaling, P.cinv, P.E[i], y[s], dy[s]);
     }
     if (L == 0) {
       double *rc = P.rec + (size_t)b * kBatchRec;
-      rc[0] = status; rc[1] = iter; rc[2] = obj; rc[3] = prim_res; rc[4] = dual_res; rc[5] = rho_bar; rc[6] = rho_updates; rc[7] = 0.0;
-      rc[8] = 0.0; rc[9] = 0.0; rc[10] = rho_est; rc[11] = 0.0;
+      batch_record(rc, status, iter, obj, prim_res, dual_res, rho_bar, rho_updates, 0.0, rho_est);
 #ifdef OSQP_HIP_KTRACE
       rc[7] = (double)tkT; rc[8] = (double)tkS; rc[9] = (double)tkA; rc[11] = (double)tkR; rc[10] = (double)(wall_clock64() - tk0);      // 100 MHz ticks per phase (tools/batch_wave_probe.py)
 #endif

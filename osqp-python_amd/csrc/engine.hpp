@@ -75,6 +75,7 @@ class Engine {
   int adjoint_last_record(double *rec) const;
   int adjoint_compute_at(const double *x, const double *y, const double *dx, const double *dy);
   int attach_batch_matrices(BatchParams &p, const double *Px_dev, const double *Ax_dev, void *stream);      // per-problem matrices: scratch + be::batch_prepare
+  void fill_batch_settings(BatchSettings &p, int warm);         // what BatchParams and LockstepParams share
   void fill_batch_params(BatchParams &p, int nbatch, int warm);
   // LinSysSolver slot (include/osqp_hip.h): this Engine instance is then used ONLY as the reduced-KKT solver
   int ls_setup(const OSQPCscMatrix *P, const OSQPCscMatrix *A, const double *rho_vec, const OSQPSettings *s);

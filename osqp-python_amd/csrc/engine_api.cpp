@@ -600,14 +600,17 @@ void Engine::prepare_batch_direct() {
   bd_.ok = true;
 }
 
-void Engine::fill_batch_params(BatchParams &p, int nbatch, int warm) {
-  p.n = n; p.m = m; p.nbatch = nbatch; p.A = d_.A; p.B = d_.B; p.D = d_.D; p.Dinv = d_.Dinv; p.E = d_.E; p.Einv = d_.Einv;
+void Engine::fill_batch_settings(BatchSettings &p, int warm) {
   p.c = c_; p.cinv = cinv_; p.sigma = settings.sigma; p.alpha = settings.alpha; p.rho0 = clamp_rho(settings.rho); p.eq_factor = eq_factor_mixed_;
   p.eps_abs = settings.eps_abs; p.eps_rel = settings.eps_rel; p.eps_pinf = settings.eps_prim_inf; p.eps_dinf = settings.eps_dual_inf;
   p.cg_frac = settings.cg_tol_fraction; p.rho_tol = settings.adaptive_rho_tolerance;
   p.max_iter = settings.max_iter; p.check = settings.check_termination; p.rho_interval = settings.adaptive_rho ? auto_rho_interval() : 0;
   p.cg_max = settings.cg_max_iter; p.unscaled = settings.scaling && !settings.scaled_termination; p.scaling = settings.scaling;
   p.precond = settings.cg_precond == OSQP_DIAGONAL_PRECONDITIONER; p.rho_is_vec = settings.rho_is_vec; p.warm = warm;
+}
+void Engine::fill_batch_params(BatchParams &p, int nbatch, int warm) {
+  fill_batch_settings(p, warm);
+  p.n = n; p.m = m; p.nbatch = nbatch; p.A = d_.A; p.B = d_.B; p.D = d_.D; p.Dinv = d_.Dinv; p.E = d_.E; p.Einv = d_.Einv;
   p.polish = settings.polishing; p.refine = settings.polish_refine_iter; p.delta = settings.delta;      // (honoured by the direct variants)
   p.variant = pol_.batch_variant; p.wide_rounds = batch_env().wide_rounds;
 }
@@ -876,14 +879,9 @@ int Engine::batch_solve_device(int nbatch, const double *q, const double *l, con
 int Engine::run_lockstep(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream) {
   const size_t need = lockstep_ws_doubles(n, m);
   if (!lsw_) { lsw_ = dev_vec<double>(d_, need); be::sync(d_); }
-  BatchParams b{};
-  fill_batch_params(b, nbatch, warm);                 // the settings snapshot of the batch path
   LockstepParams p;
+  fill_batch_settings(p, warm);                       // the settings snapshot of the batch path
   p.n = n; p.m = m; p.A = d_.A; p.B = d_.B; p.D = d_.D; p.Dinv = d_.Dinv; p.E = d_.E; p.Einv = d_.Einv;
-  p.c = b.c; p.cinv = b.cinv; p.sigma = b.sigma; p.alpha = b.alpha; p.rho0 = b.rho0; p.eq_factor = b.eq_factor; p.eps_abs = b.eps_abs; p.eps_rel = b.eps_rel;
-  p.eps_pinf = b.eps_pinf; p.eps_dinf = b.eps_dinf; p.cg_frac = b.cg_frac; p.rho_tol = b.rho_tol;
-  p.max_iter = b.max_iter; p.check = b.check; p.rho_interval = b.rho_interval; p.cg_max = b.cg_max; p.unscaled = b.unscaled; p.scaling = b.scaling;
-  p.precond = b.precond; p.rho_is_vec = b.rho_is_vec; p.warm = warm;
   p.q0 = d_.qraw; p.l0 = d_.lraw; p.u0 = d_.uraw; p.pc = reordered_ ? d_pc_ : nullptr; p.pr = reordered_ ? d_pr_ : nullptr; p.ws = lsw_;
   const double t0 = now_s(), limit = settings.time_limit > 0 && settings.time_limit < 1e9 ? settings.time_limit : 0.0;
   double tot[4] = {0, 0, 0, 0};

@@ -387,7 +387,7 @@ __global__ __launch_bounds__(256) void k_ls_cgbeta(LsK k) {
   if (threadIdx.x == 0) k.w.word[WD_CGIT] += 1;
 }
 
-// Every check_termination / adaptive_rho_interval iterations: k_batch_admm's decisions (non-direct formulas), per problem.
+// Every check_termination / adaptive_rho_interval iterations: the batch family's decisions (term_rules.h: batch_check, batch_rho_rule, batch_tol_rule), per problem.
 // mode 0: a boundary of the loop;  1: the residuals of the start (sets the first inner tolerance);  2: the time limit has passed.
 __global__ __launch_bounds__(256) void k_ls_decide(LsK k, int iter, int at_check, int at_rho, int mode) {
   __shared__ double lds[256];
@@ -406,58 +406,30 @@ __global__ __launch_bounds__(256) void k_ls_decide(LsK k, int iter, int at_check
   const int done = iw[IW_DONE * W + lane];
   int rhoch = 0;
   if (!done) {
-    const double pri_u = M_[0], ax_u = M_[1], z_u = M_[2], pri_s = M_[3], ax_s = M_[4], z_s = M_[5], dy_u = M_[6], dy_s = M_[7], adx_hi = M_[8], adx_lo = M_[9], pinf_lhs = M_[10];
-    const double dua_u = N_[0], px_u = N_[1], aty_u = N_[2], dua_s = N_[3], px_s = N_[4], aty_s = N_[5], dxn_u = N_[6], dxn_s = N_[7], qn_s = N_[8], qn_u = N_[9];
-    const double atdy_u = N_[10], atdy_s = N_[11], pdx_u = N_[12], pdx_s = N_[13], xpx = N_[14], qx = N_[15], qdx = N_[16];
-    if (mode == 1) {
-      const double eps_cg = P.cg_frac * dua_s;
-      sc[SC_EPSCG * W + lane] = eps_cg; sc[SC_EPSPREV * W + lane] = INFINITY;
-      iw[IW_RELRULE * W + lane] = !(eps_cg > 1e-13) || !isfinite(eps_cg);
-    } else {
-      const bool unsc = P.unscaled != 0;
-      const int m = P.m;
-      double rho_bar = sc[SC_RHOBAR * W + lane];
-      double obj = (0.5 * xpx + qx) * (P.scaling ? P.cinv : 1.0);                           // _osqp.py:705-712
-      const double prim_res = m == 0 ? 0.0 : (unsc ? pri_u : pri_s), dual_res = unsc ? P.cinv * dua_u : dua_s;
-      int status = OSQP_UNSOLVED;
-      bool stop = false;
-      for (int approx = 0; approx < 2 && !stop && at_check; approx++) {                     // _osqp.py:998-1077, :1264-1266
-        if (approx && iter < P.max_iter) break;
-        const double f = approx ? 10.0 : 1.0;
-        const double ea = f * P.eps_abs, er = f * P.eps_rel, epi = f * P.eps_pinf, edi = f * P.eps_dinf;
-        if (prim_res > OSQP_INFTY || dual_res > OSQP_INFTY || prim_res != prim_res || dual_res != dual_res) { status = OSQP_NON_CVX; obj = NAN; stop = true; break; }
-        bool pri_ok = false, dua_ok = false, pinf = false, dinf = false;
-        if (m == 0) pri_ok = true;
-        else if (prim_res < ea + er * (unsc ? fmax(ax_u, z_u) : fmax(ax_s, z_s))) pri_ok = true;
-        else {                                                                              // is_primal_infeasible :796-820
-          const double nd = unsc ? dy_u : dy_s;
-          if (nd > epi && pinf_lhs < -epi * nd) pinf = (unsc ? atdy_u : atdy_s) < epi * nd;
-        }
-        const double mx = unsc ? P.cinv * fmax(fmax(aty_u, px_u), qn_u) : fmax(fmax(aty_s, px_s), qn_s);
-        if (dual_res < ea + er * mx) dua_ok = true;
-        else {                                                                              // is_dual_infeasible :822-878
-          const double nd = unsc ? dxn_u : dxn_s, sc_ = unsc ? P.c : 1.0;
-          if (nd > edi && qdx < -sc_ * edi * nd && (unsc ? pdx_u : pdx_s) < sc_ * edi * nd) dinf = !(adx_hi > edi * nd) && !(adx_lo > edi * nd);
-        }
-        if (pri_ok && dua_ok) { status = approx ? OSQP_SOLVED_INACCURATE : OSQP_SOLVED; stop = true; }
-        else if (pinf) { status = approx ? OSQP_PRIMAL_INFEASIBLE_INACCURATE : OSQP_PRIMAL_INFEASIBLE; obj = OSQP_INFTY; stop = true; }
-        else if (dinf) { status = approx ? OSQP_DUAL_INFEASIBLE_INACCURATE : OSQP_DUAL_INFEASIBLE; obj = -OSQP_INFTY; stop = true; }
-      }
-      if (!stop && iter >= P.max_iter) { status = OSQP_MAX_ITER_REACHED; stop = true; }
-      if (!stop && mode == 2) { status = OSQP_TIME_LIMIT_REACHED; stop = true; }
-      const double pr = pri_s / (fmax(ax_s, z_s) + 1e-10), du = dua_s / (fmax(fmax(aty_s, px_s), qn_s) + 1e-10);
-      const double rho_new = fmin(fmax(rho_bar * sqrt(pr / (du + 1e-10)), 1e-6), 1e6);       // adapt_rho :880-930
-      if (stop) {
-        double *rc = k.w.rec + (size_t)lane * kBatchRec;
-        rc[0] = status; rc[1] = iter; rc[2] = obj; rc[3] = prim_res; rc[4] = dual_res; rc[5] = rho_bar; rc[6] = iw[IW_RHOUPD * W + lane]; rc[7] = iw[IW_PCG * W + lane];
-        rc[8] = 0.0; rc[9] = 0.0; rc[10] = rho_new; rc[11] = 0.0;
+    const TermRes R = {M_[0], M_[1], M_[2], M_[3], M_[4], M_[5], M_[6], M_[7], M_[10], N_[0], N_[1], N_[2], N_[3], N_[4], N_[5], N_[6], N_[7], N_[9], N_[8], N_[14], N_[15], N_[16]};
+    const double adx_hi = M_[8], adx_lo = M_[9], atdy_u = N_[10], atdy_s = N_[11], pdx_u = N_[12], pdx_s = N_[13];      // second stages: folded with the rest
+    double eps_prev, eps_cg;
+    bool rel_rule;
+    auto put_tol = [&]() { sc[SC_EPSPREV * W + lane] = eps_prev; sc[SC_EPSCG * W + lane] = eps_cg; iw[IW_RELRULE * W + lane] = rel_rule; };
+    if (mode == 1) { batch_tol_init(P.cg_frac, R.dua_s, &eps_prev, &eps_cg, &rel_rule); put_tol(); }
+    else {
+      const TermSet tset = {P.eps_abs, P.eps_rel, P.eps_pinf, P.eps_dinf, P.c, P.cinv, P.m, P.unscaled, P.scaling};
+      const double rho_bar = sc[SC_RHOBAR * W + lane];
+      double obj, prim_res, dual_res, rho_new;
+      term_info(tset, R, &obj, &prim_res, &dual_res);
+      int status = batch_check(tset, R, prim_res, dual_res, iter, P.max_iter, at_check != 0,
+                               [&](double &au, double &as) { au = atdy_u; as = atdy_s; }, [&](double &pu, double &ps) { pu = pdx_u; ps = pdx_s; },
+                               [&](double thr) { return !(adx_hi > thr) && !(adx_lo > thr); }, &obj);
+      if (status == kBatchGoOn && mode == 2) status = OSQP_TIME_LIMIT_REACHED;
+      const bool rho_big = batch_rho_rule(rho_bar, P.rho_tol, R, &rho_new);                  // (rho_new: also the record's rho estimate)
+      if (status != kBatchGoOn) {
+        batch_record(k.w.rec + (size_t)lane * kBatchRec, status, iter, obj, prim_res, dual_res, rho_bar, iw[IW_RHOUPD * W + lane], iw[IW_PCG * W + lane], rho_new);
         iw[IW_DONE * W + lane] = 1; iw[IW_STATUS * W + lane] = status;
       } else {
-        if (at_rho && (rho_new > P.rho_tol * rho_bar || rho_new < rho_bar / P.rho_tol)) {
-          sc[SC_RHOBAR * W + lane] = rho_new; iw[IW_RHOUPD * W + lane] += 1; rhoch = 1;
-        }
-        double e2 = fmax(fmin(P.cg_frac * dua_s, sc[SC_EPSPREV * W + lane]), 1e-13);        // inner tolerance: non-increasing
-        if (isfinite(e2)) { sc[SC_EPSPREV * W + lane] = e2; sc[SC_EPSCG * W + lane] = e2; iw[IW_RELRULE * W + lane] = 0; }
+        if (at_rho && rho_big) { sc[SC_RHOBAR * W + lane] = rho_new; iw[IW_RHOUPD * W + lane] += 1; rhoch = 1; }
+        eps_prev = sc[SC_EPSPREV * W + lane]; eps_cg = sc[SC_EPSCG * W + lane]; rel_rule = iw[IW_RELRULE * W + lane] != 0;
+        batch_tol_rule(P.cg_frac, R.dua_s, &eps_prev, &eps_cg, &rel_rule);
+        put_tol();
       }
     }
   }
@@ -558,12 +530,9 @@ __global__ __launch_bounds__(256) void k_ls_store_n(LsK k) {
   __shared__ double tile[64][65];
   const LockstepParams &P = k.P;
   const int lane = ls_lane(), wv = ls_wave(), j0 = blockIdx.x * 64, status = k.w.iw[IW_STATUS * W + lane];
-  const bool pinf = status == OSQP_PRIMAL_INFEASIBLE || status == OSQP_PRIMAL_INFEASIBLE_INACCURATE;
-  const bool dinf = status == OSQP_DUAL_INFEASIBLE || status == OSQP_DUAL_INFEASIBLE_INACCURATE;
   for (int jl = wv; jl < 64 && j0 + jl < P.n; jl += 4) {
     const int j = j0 + jl;
-    const double dxj = k.w.dx[IX(j)], xj = k.w.x[IX(j)];
-    tile[lane][jl] = dinf ? (P.unscaled ? P.D[j] * dxj : dxj) : (pinf ? NAN : (P.scaling ? P.D[j] * xj : xj));
+    tile[lane][jl] = batch_out_x(status, P.unscaled, P.scaling, P.D[j], k.w.x[IX(j)], k.w.dx[IX(j)]);
   }
   ls_tile_out(P.x, P.n, j0, P.count, P.pc, tile);
   if (blockIdx.x == 0) for (int e = threadIdx.x; e < P.count * kBatchRec; e += 256) P.rec[e] = k.w.rec[e];
@@ -572,12 +541,9 @@ __global__ __launch_bounds__(256) void k_ls_store_m(LsK k) {
   __shared__ double tile[64][65];
   const LockstepParams &P = k.P;
   const int lane = ls_lane(), wv = ls_wave(), i0 = blockIdx.x * 64, status = k.w.iw[IW_STATUS * W + lane];
-  const bool pinf = status == OSQP_PRIMAL_INFEASIBLE || status == OSQP_PRIMAL_INFEASIBLE_INACCURATE;
-  const bool dinf = status == OSQP_DUAL_INFEASIBLE || status == OSQP_DUAL_INFEASIBLE_INACCURATE;
   for (int il = wv; il < 64 && i0 + il < P.m; il += 4) {
     const int i = i0 + il;
-    const double dyi = k.w.dy[IX(i)], yi = k.w.y[IX(i)];
-    tile[lane][il] = pinf ? (P.unscaled ? P.E[i] * dyi : dyi) : (dinf ? NAN : (P.scaling ? P.cinv * P.E[i] * yi : yi));
+    tile[lane][il] = batch_out_y(status, P.unscaled, P.scaling, P.cinv, P.E[i], k.w.y[IX(i)], k.w.dy[IX(i)]);
   }
   ls_tile_out(P.y, P.m, i0, P.count, P.pr, tile);
 }

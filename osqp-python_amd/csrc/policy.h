@@ -7,7 +7,9 @@
 //   ctl_next_chunk      where the next chunk of ADMM iterations ends: the next termination check (_osqp.py:1254-1262), the next rho
 //                       adaptation point (:1229-1245), or the start of the tight-tolerance window in front of it
 //   ctl_stage1          residuals -> info fields, tolerances, the termination test proper (:998-1077) and the FIRST stage of the
-//                       infeasibility tests (:796-878) -- the second stage needs two more SpMVs and is run by the host on demand
+//                       infeasibility tests (:796-878) -- the second stage needs two more SpMVs and is run by the host on demand.
+//                       The tests themselves are term_rules.h's (one text with the batch kernels); Ctl adds the duality-gap check,
+//                       the need bits and the inf_* bookkeeping
 //   ctl_rho_rule        adaptive rho (:880-930) with this engine's square-root tolerance and persistence test
 //   ctl_tol_rule        PCG tolerance for the next chunk (a fraction of the scaled dual residual, never loosening; dropped while the
 //                       iterates run away)
@@ -18,17 +20,9 @@
 
 #include "../../include/osqp_hip.h"
 #include "backend.h"
-
-#if defined(__HIPCC__)
-#define OSQP_HD __host__ __device__
-#else
-#define OSQP_HD
-#endif
+#include "term_rules.h"           // the termination tests and the rho estimate themselves (shared with the batch kernels); OSQP_HD
 
 namespace osqp_hip {
-
-constexpr double kPolRhoMin = 1e-6, kPolRhoMax = 1e6;            // _osqp.py:25-26
-constexpr double kPolCgTolAbsMin = 1e-13;
 
 enum CtlStatus { CTL_RUNNING = 0, CTL_DONE = 1, CTL_NEED_HOST = 2 };
 // why a boundary was handed to the host
@@ -72,14 +66,15 @@ constexpr int kCtlLog = 16, kCtlPrintInterval = 200, kCtlHist = 64;
 
 OSQP_HD inline int pol_imin(int a, int b) { return a < b ? a : b; }
 OSQP_HD inline int pol_imax(int a, int b) { return a > b ? a : b; }
-OSQP_HD inline double pol_clamp_rho(double r) { return fmin(fmax(r, kPolRhoMin), kPolRhoMax); }
 
-// (_osqp.py:880-908, scaled quantities)
-OSQP_HD inline double pol_rho_estimate(double rho_bar, const double *res) {
-  const double pri = res[R_PRI_S] / (fmax(res[R_AX_S], res[R_Z_S]) + 1e-10);
-  const double dua = res[R_DUA_S] / (fmax(fmax(res[R_ATY_S], res[R_PX_S]), res[R_QN_S]) + 1e-10);
-  return pol_clamp_rho(rho_bar * sqrt(pri / (dua + 1e-10)));
+// the residual block Dev::res and the settings snapshot in the form term_rules.h reads
+OSQP_HD inline TermRes ctl_term_res(const double *res) {
+  return {res[R_PRI_U], res[R_AX_U], res[R_Z_U], res[R_PRI_S], res[R_AX_S], res[R_Z_S], res[R_DY_U], res[R_DY_S], res[R_PINF_LHS],
+          res[R_DUA_U], res[R_PX_U], res[R_ATY_U], res[R_DUA_S], res[R_PX_S], res[R_ATY_S], res[R_DX_U], res[R_DX_S], res[R_QN_U], res[R_QN_S],
+          res[R_XPX], res[R_QX], res[R_QDX]};
 }
+OSQP_HD inline TermSet ctl_term_set(const Ctl &c, int unscaled) { return {c.eps_abs, c.eps_rel, c.eps_pinf, c.eps_dinf, c.c, c.cinv, c.m, unscaled, c.scaling}; }
+OSQP_HD inline double pol_rho_estimate(double rho_bar, const double *res) { return term_rho_estimate(rho_bar, ctl_term_res(res)); }
 
 // PCG tolerance of the first chunk from the residuals of the starting point: a warm start near the optimum must not be perturbed by a
 // loose first-chunk solve (warm_start_test.py:52-57 expects < 10 iterations)
@@ -145,6 +140,8 @@ OSQP_HD inline void ctl_account(Ctl &c, const int *flags) {
 
 // info fields of a check (_osqp.py:705-764) + the v1 gap fields (engine.cpp update_gap_info; [UPSTREAM-UNVERIFIED] formulas)
 OSQP_HD inline void ctl_info(Ctl &c, const double *res) {
+  // (written out on Ctl's own fields, not through term_info: routed through it the device compiler fuses the product of obj_val into the
+  //  subtraction of duality_gap, and the gap's last bits change)
   const bool unsc = c.scaling && !c.scaled_termination;
   const double ci = c.scaling ? c.cinv : 1.0;
   c.obj_val = (0.5 * res[R_XPX] + res[R_QX]) * ci;
@@ -160,49 +157,32 @@ OSQP_HD inline void ctl_info(Ctl &c, const double *res) {
   for (int q = 0; q < R_COUNT; q++) c.res[q] = res[q];
 }
 
-// First stage of check_termination (_osqp.py:998-1077).  Returns an osqp_status_type value when the status is decided without
-// the infeasibility tests' second stage, 0 when the solve goes on, and -1 with c.need set when the host has to run the second stage
-// (is_primal_infeasible :815-818 / is_dual_infeasible :846-872 need A' dy, P dx, A dx).
+// First stage of check_termination (term_rules.h term_stage1 + this path's duality-gap test).  Returns an osqp_status_type value when the status
+// is decided without the infeasibility tests' second stage, 0 when the solve goes on, and -1 with c.need set when the host has to run the second
+// stage (is_primal_infeasible :815-818 / is_dual_infeasible :846-872 need A' dy, P dx, A dx).
 OSQP_HD inline int ctl_stage1(Ctl &c, const double *res, bool approximate, bool *pri_ok_out, bool *dua_ok_out) {
-  double ea = c.eps_abs, er = c.eps_rel, epi = c.eps_pinf, edi = c.eps_dinf;
-  if (approximate) { ea *= 10; er *= 10; epi *= 10; edi *= 10; }
-  const bool unsc = c.scaling && !c.scaled_termination;
-  if (c.prim_res > OSQP_INFTY || c.dual_res > OSQP_INFTY || c.prim_res != c.prim_res || c.dual_res != c.dual_res) return OSQP_NON_CVX;   // :1025-1028
-  bool pri_ok = false, dua_ok = false;
+  const int unsc = c.scaling && !c.scaled_termination;
+  const TermSet s = ctl_term_set(c, unsc);
+  const TermStage1 t = term_stage1(s, ctl_term_res(res), c.prim_res, c.dual_res, approximate);
+  if (t.non_cvx) return OSQP_NON_CVX;                                                                                    // :1025-1028
   c.need = NEED_NONE;
-  c.inf_unscaled = unsc ? 1 : 0;
-  if (c.m == 0) pri_ok = true;
-  else {
-    const double eps_pri = ea + er * (unsc ? fmax(res[R_AX_U], res[R_Z_U]) : fmax(res[R_AX_S], res[R_Z_S]));   // :728-751
-    if (c.prim_res < eps_pri) pri_ok = true;
-    else {
-      const double nd = unsc ? res[R_DY_U] : res[R_DY_S];
-      if (nd > epi && res[R_PINF_LHS] < -epi * nd) { c.need |= NEED_PINF; c.inf_nd_p = nd; }
-    }
-  }
-  const double mx = unsc ? c.cinv * fmax(fmax(res[R_ATY_U], res[R_PX_U]), res[R_QN_U]) : fmax(fmax(res[R_ATY_S], res[R_PX_S]), res[R_QN_S]);   // :766-794
-  if (c.dual_res < ea + er * mx) dua_ok = true;
-  else {
-    const double nd = unsc ? res[R_DX_U] : res[R_DX_S], sc = unsc ? c.c : 1.0;
-    if (nd > edi && res[R_QDX] < -sc * edi * nd) { c.need |= NEED_DINF; c.inf_nd_d = nd; c.inf_thr_d = edi * nd; }
-  }
-  const bool gap_ok = !c.check_dualgap || fabs(c.duality_gap) < ea + er * fmax(fabs(c.obj_val), fabs(c.dual_obj_val));
-  if (pri_ok_out) *pri_ok_out = pri_ok;
-  if (dua_ok_out) *dua_ok_out = dua_ok;
-  if (pri_ok && dua_ok && gap_ok) return approximate ? OSQP_SOLVED_INACCURATE : OSQP_SOLVED;
+  c.inf_unscaled = unsc;
+  if (t.need_pinf) { c.need |= NEED_PINF; c.inf_nd_p = t.nd_p; }
+  if (t.need_dinf) { c.need |= NEED_DINF; c.inf_nd_d = t.nd_d; c.inf_thr_d = term_adx_thr(s, approximate, t.nd_d); }
+  const bool gap_ok = !c.check_dualgap || fabs(c.duality_gap) < term_eps(c.eps_abs, approximate) + term_eps(c.eps_rel, approximate) * fmax(fabs(c.obj_val), fabs(c.dual_obj_val));
+  if (pri_ok_out) *pri_ok_out = t.pri_ok;
+  if (dua_ok_out) *dua_ok_out = t.dua_ok;
+  if (t.pri_ok && t.dua_ok && gap_ok) return approximate ? OSQP_SOLVED_INACCURATE : OSQP_SOLVED;
   return c.need ? -1 : 0;
 }
 
 // Second stage (r2: the block with R_ATDY_*, R_PDX_*, R_ADX_VIOL filled by the second-stage kernels for the tests in c.need):
 // an osqp_status_type value when an infeasibility certificate holds (:815-818, :846-872), else 0.
 OSQP_HD inline int ctl_stage2(const Ctl &c, const double *r2, bool approximate) {
-  double epi = c.eps_pinf, edi = c.eps_dinf;
-  if (approximate) { epi *= 10; edi *= 10; }
-  const bool unsc = c.inf_unscaled != 0;
-  if ((c.need & NEED_PINF) && (unsc ? r2[R_ATDY_U] : r2[R_ATDY_S]) < epi * c.inf_nd_p)
+  const TermSet s = ctl_term_set(c, c.inf_unscaled);
+  if ((c.need & NEED_PINF) && term_pinf_holds(s, approximate, c.inf_nd_p, r2[R_ATDY_U], r2[R_ATDY_S]))
     return approximate ? OSQP_PRIMAL_INFEASIBLE_INACCURATE : OSQP_PRIMAL_INFEASIBLE;
-  const double sc = unsc ? c.c : 1.0;
-  if ((c.need & NEED_DINF) && (unsc ? r2[R_PDX_U] : r2[R_PDX_S]) < sc * edi * c.inf_nd_d && r2[R_ADX_VIOL] == 0.0)
+  if ((c.need & NEED_DINF) && term_dinf_pdx_ok(s, approximate, c.inf_nd_d, r2[R_PDX_U], r2[R_PDX_S]) && r2[R_ADX_VIOL] == 0.0)
     return approximate ? OSQP_DUAL_INFEASIBLE_INACCURATE : OSQP_DUAL_INFEASIBLE;
   return 0;
 }

@@ -1,5 +1,6 @@
 // TEST INFRASTRUCTURE: the rules of osqp-python_amd/csrc/policy.h (one text, compiled for the host driver and for the device's k_decide)
-// behind a C ABI, so that the CPU tier can exercise each rule on its own (tests/test_policy_rules.py).  Never part of the product.
+// and of term_rules.h (the termination / rho / record rules it shares with the batch kernels) behind a C ABI, so that the CPU tier can exercise
+// each rule on its own (tests/test_policy_rules.py, tests/test_batch_rules.py).  Never part of the product.
 #include <cstring>
 #include <string>
 
@@ -74,4 +75,50 @@ void pp_init_tol(void *p, double dua0) {
   double res[R_COUNT]; res_block(res, 0.0, 1.0, dua0, 1.0);
   ctl_init_tol(*static_cast<Ctl *>(p), res);
 }
+
+// ---- term_rules.h.  set9: eps_abs, eps_rel, eps_pinf, eps_dinf, c, cinv, m, unscaled, scaling;  R22: the fields of TermRes in their order;
+// stage2: atdy_u, atdy_s, pdx_u, pdx_s, "no row of A dx violates" (0 / 1)
+static TermSet br_set(const double *s) { return {s[0], s[1], s[2], s[3], s[4], s[5], (int)s[6], (int)s[7], (int)s[8]}; }
+static TermRes br_res(const double *r) { TermRes R; static_assert(sizeof(TermRes) == 22 * sizeof(double), "TermRes: 22 doubles"); std::memcpy(&R, r, sizeof(R)); return R; }
+// out: obj, prim_res, dual_res, which second stages were asked for (1 A' dy, 2 P dx, 4 A dx), the threshold the A dx callable was given
+int br_check(const double *set9, const double *R22, int iter, int max_iter, int at_check, const double *stage2, double *out) {
+  const TermSet s = br_set(set9); const TermRes R = br_res(R22);
+  int asked = 0; double thr = NAN;
+  term_info(s, R, &out[0], &out[1], &out[2]);
+  const int st = batch_check(s, R, out[1], out[2], iter, max_iter, at_check != 0,
+                             [&](double &u, double &v) { asked |= 1; u = stage2[0]; v = stage2[1]; }, [&](double &u, double &v) { asked |= 2; u = stage2[2]; v = stage2[3]; },
+                             [&](double t) { asked |= 4; thr = t; return stage2[4] != 0.0; }, &out[0]);
+  out[3] = asked; out[4] = thr;
+  return st;
+}
+// the same block through the single-QP path's ctl_info / ctl_stage1 / ctl_stage2 (check_dualgap off); info3: ctl_info's obj_val, prim_res, dual_res
+int br_ctl_check(const double *set9, const double *R22, int approx, const double *stage2, double *info3) {
+  Ctl c; std::memset(&c, 0, sizeof(c));
+  c.eps_abs = set9[0]; c.eps_rel = set9[1]; c.eps_pinf = set9[2]; c.eps_dinf = set9[3]; c.c = set9[4]; c.cinv = set9[5]; c.m = (int)set9[6];
+  c.scaling = (int)set9[8]; c.scaled_termination = (c.scaling && !(int)set9[7]) ? 1 : 0;
+  const TermRes R = br_res(R22);
+  double res[R_COUNT] = {0};
+  res[R_PRI_U] = R.pri_u; res[R_AX_U] = R.ax_u; res[R_Z_U] = R.z_u; res[R_PRI_S] = R.pri_s; res[R_AX_S] = R.ax_s; res[R_Z_S] = R.z_s; res[R_DY_U] = R.dy_u; res[R_DY_S] = R.dy_s;
+  res[R_PINF_LHS] = R.pinf_lhs; res[R_DUA_U] = R.dua_u; res[R_PX_U] = R.px_u; res[R_ATY_U] = R.aty_u; res[R_DUA_S] = R.dua_s; res[R_PX_S] = R.px_s; res[R_ATY_S] = R.aty_s;
+  res[R_DX_U] = R.dxn_u; res[R_DX_S] = R.dxn_s; res[R_QN_U] = R.qn_u; res[R_QN_S] = R.qn_s; res[R_XPX] = R.xpx; res[R_QX] = R.qx; res[R_QDX] = R.qdx;
+  ctl_info(c, res);
+  info3[0] = c.obj_val; info3[1] = c.prim_res; info3[2] = c.dual_res;
+  int st = ctl_stage1(c, res, approx != 0, nullptr, nullptr);
+  if (st >= 0) return st;
+  res[R_ATDY_U] = stage2[0]; res[R_ATDY_S] = stage2[1]; res[R_PDX_U] = stage2[2]; res[R_PDX_S] = stage2[3]; res[R_ADX_VIOL] = stage2[4] != 0.0 ? 0.0 : 1.0;
+  return ctl_stage2(c, res, approx != 0);
+}
+double br_rho_estimate(double rho_bar, const double *R22) { return term_rho_estimate(rho_bar, br_res(R22)); }
+int br_rho_rule(double rho_bar, double rho_tol, const double *R22, double *rho_new) { return batch_rho_rule(rho_bar, rho_tol, br_res(R22), rho_new) ? 1 : 0; }
+// state3: eps_prev, eps_cg, rel_rule
+void br_tol(int init, double cg_frac, double dua_s, double *state3) {
+  bool rel = state3[2] != 0.0;
+  if (init) batch_tol_init(cg_frac, dua_s, &state3[0], &state3[1], &rel); else batch_tol_rule(cg_frac, dua_s, &state3[0], &state3[1], &rel);
+  state3[2] = rel ? 1.0 : 0.0;
+}
+void br_record(double *rc, int status, int iter, double obj, double prim_res, double dual_res, double rho_bar, int rho_updates, double pcg, double rho_est) {
+  batch_record(rc, status, iter, obj, prim_res, dual_res, rho_bar, rho_updates, pcg, rho_est);
+}
+double br_out_x(int status, int unscaled, int scaling, double Dj, double xj, double dxj) { return batch_out_x(status, unscaled, scaling, Dj, xj, dxj); }
+double br_out_y(int status, int unscaled, int scaling, double cinv, double Ei, double yi, double dyi) { return batch_out_y(status, unscaled, scaling, cinv, Ei, yi, dyi); }
 }

@@ -1,0 +1,264 @@
+"""CPU tier: osqp-python_amd/csrc/term_rules.h -- the termination tests, the rho estimate / rule, the inner-tolerance rule, the record and the
+x / y store rule that the batch kernels (k_batch_admm, k_batch_wave, k_ls_decide, k_ls_store_*) and policy.h share -- behind
+tests/hostsim/policy_probe.cpp.  Every case is a hand-made residual block of 22 numbers; what is expected comes from `ref_check` /
+`ref_rho` below, which restate the reference's rules from their description: check_termination (_osqp.py:998-1077
+with update_info :705-764, the tolerances :728-794, the approximate pass at max_iter :1264-1266), is_primal_infeasible / is_dual_infeasible
+(:796-878) and compute_rho_estimate (:880-908)."""
+import ctypes as C
+import math
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from test_policy_rules import DEPS, OUT, ROOT, SRC
+
+SOLVED, SOLVED_INACC, PINF, PINF_INACC, DINF, DINF_INACC, MAX_ITER, TIME_LIMIT, NON_CVX = 1, 2, 3, 4, 5, 6, 7, 8, 9
+GO_ON = 0
+INFTY = 1e30
+FIELDS = ('pri_u ax_u z_u pri_s ax_s z_s dy_u dy_s pinf_lhs dua_u px_u aty_u dua_s px_s aty_s dxn_u dxn_s qn_u qn_s xpx qx qdx').split()
+DP = C.POINTER(C.c_double)
+
+
+@pytest.fixture(scope='module')
+def lib():
+    if not (os.path.exists(OUT) and all(os.path.getmtime(OUT) >= os.path.getmtime(f) for f in DEPS)):
+        os.makedirs(os.path.dirname(OUT), exist_ok=True)
+        subprocess.check_call(['g++', '-O2', '-std=c++17', '-shared', '-fPIC', '-I', os.path.join(ROOT, 'include'), '-o', OUT, SRC])
+    L = C.CDLL(OUT)
+    L.br_check.argtypes = [DP, DP, C.c_int, C.c_int, C.c_int, DP, DP]; L.br_check.restype = C.c_int
+    L.br_ctl_check.argtypes = [DP, DP, C.c_int, DP, DP]; L.br_ctl_check.restype = C.c_int
+    L.br_rho_estimate.argtypes = [C.c_double, DP]; L.br_rho_estimate.restype = C.c_double
+    L.br_rho_rule.argtypes = [C.c_double, C.c_double, DP, DP]; L.br_rho_rule.restype = C.c_int
+    L.br_tol.argtypes = [C.c_int, C.c_double, C.c_double, DP]
+    L.br_record.argtypes = [DP, C.c_int, C.c_int] + [C.c_double] * 4 + [C.c_int] + [C.c_double] * 2
+    L.br_out_x.argtypes = [C.c_int] * 3 + [C.c_double] * 3; L.br_out_x.restype = C.c_double
+    L.br_out_y.argtypes = [C.c_int] * 3 + [C.c_double] * 4; L.br_out_y.restype = C.c_double
+    return L
+
+
+def arr(v):
+    return (C.c_double * len(v))(*[float(e) for e in v])
+
+
+def settings(**kw):
+    s = dict(eps_abs=1e-3, eps_rel=1e-3, eps_pinf=1e-4, eps_dinf=1e-4, c=1.0, cinv=1.0, m=5, unscaled=0, scaling=1)
+    s.update(kw)
+    return s
+
+
+def block(**kw):
+    """a point that is neither converged nor a certificate: residuals 0.1 against normalisations 1, steps dy, dx of size 1 with non-negative
+    support / cost terms (the first stage of both infeasibility tests fails)"""
+    r = dict(pri_u=0.1, ax_u=1, z_u=1, pri_s=0.1, ax_s=1, z_s=1, dy_u=1, dy_s=1, pinf_lhs=0.5, dua_u=0.1, px_u=1, aty_u=1, dua_s=0.1, px_s=1, aty_s=1,
+             dxn_u=1, dxn_s=1, qn_u=1, qn_s=1, xpx=2.0, qx=-3.0, qdx=0.5)
+    r.update(kw)
+    return r
+
+
+def ref_check(S, R, it, max_iter, at_check, atdy=(0, 0), pdx=(0, 0), adx_ok=True):
+    """-> (status or GO_ON, obj, prim_res, dual_res, second stages asked for)"""
+    un = bool(S['unscaled'])
+    obj = (0.5 * R['xpx'] + R['qx']) * (S['cinv'] if S['scaling'] else 1.0)
+    prim = 0.0 if S['m'] == 0 else (R['pri_u'] if un else R['pri_s'])
+    dual = S['cinv'] * R['dua_u'] if un else R['dua_s']
+    asked = 0
+    for approx in (0, 1):
+        if not at_check or (approx and it < max_iter):
+            break
+        f = 10.0 if approx else 1.0
+        ea, er, epi, edi = f * S['eps_abs'], f * S['eps_rel'], f * S['eps_pinf'], f * S['eps_dinf']
+        if prim > INFTY or dual > INFTY or math.isnan(prim) or math.isnan(dual):
+            return NON_CVX, math.nan, prim, dual, asked
+        pri_ok = dua_ok = pinf = dinf = False
+        if S['m'] == 0 or prim < ea + er * (max(R['ax_u'], R['z_u']) if un else max(R['ax_s'], R['z_s'])):
+            pri_ok = True
+        else:
+            nd = R['dy_u'] if un else R['dy_s']
+            if nd > epi and R['pinf_lhs'] < -epi * nd:
+                asked |= 1
+                pinf = (atdy[0] if un else atdy[1]) < epi * nd
+        if dual < ea + er * (S['cinv'] * max(R['aty_u'], R['px_u'], R['qn_u']) if un else max(R['aty_s'], R['px_s'], R['qn_s'])):
+            dua_ok = True
+        else:
+            nd, sc = (R['dxn_u'], S['c']) if un else (R['dxn_s'], 1.0)
+            if nd > edi and R['qdx'] < -sc * edi * nd:
+                asked |= 2
+                if (pdx[0] if un else pdx[1]) < sc * edi * nd:
+                    asked |= 4
+                    dinf = adx_ok
+        if pri_ok and dua_ok:
+            return SOLVED + approx, obj, prim, dual, asked
+        if pinf:
+            return PINF + approx, INFTY, prim, dual, asked
+        if dinf:
+            return DINF + approx, -INFTY, prim, dual, asked
+    return (MAX_ITER if it >= max_iter else GO_ON), obj, prim, dual, asked
+
+
+def run_check(lib, S, R, it=25, max_iter=4000, at_check=1, atdy=(0, 0), pdx=(0, 0), adx_ok=True):
+    out = arr([0] * 5)
+    st = lib.br_check(arr([S[k] for k in ('eps_abs', 'eps_rel', 'eps_pinf', 'eps_dinf', 'c', 'cinv', 'm', 'unscaled', 'scaling')]), arr([R[k] for k in FIELDS]),
+                      it, max_iter, at_check, arr(list(atdy) + list(pdx) + [1.0 if adx_ok else 0.0]), out)
+    return st, out[0], out[1], out[2], int(out[3]), out[4]
+
+
+def agree(lib, S, R, **kw):
+    got, want = run_check(lib, S, R, **kw), ref_check(S, R, kw.get('it', 25), kw.get('max_iter', 4000), kw.get('at_check', 1), kw.get('atdy', (0, 0)), kw.get('pdx', (0, 0)), kw.get('adx_ok', True))
+    assert got[0] == want[0] and got[4] == want[4], (got, want)
+    for g, w in zip(got[1:4], want[1:4]):
+        assert (math.isnan(g) and math.isnan(w)) or g == w, (got, want)
+    return got
+
+
+def test_solved_scaled_and_unscaled(lib):
+    R = block(pri_s=1e-4, dua_s=1e-4, pri_u=1e-4, dua_u=1.5e-3)
+    st, obj, prim, dual, asked, _ = agree(lib, settings(), R)
+    assert st == SOLVED and obj == -2.0 and prim == 1e-4 and dual == 1e-4 and asked == 0
+    assert agree(lib, settings(), block(pri_s=1e-4, dua_s=2.1e-3))[0] == GO_ON             # eps_dual = 1e-3 + 1e-3 * 1
+    # unscaled: dual_res = cinv * ||Dinv (P x + q + A' y)||, its normalisation carries cinv as well; with the normalisations at zero the
+    # tolerance is eps_abs alone, and cinv decides: 0.8e-3 passes at cinv = 1 and fails at cinv = 2
+    Ru = block(pri_u=1e-4, dua_u=0.8e-3, px_u=0, aty_u=0, qn_u=0, pri_s=0.5, dua_s=0.5)
+    a = agree(lib, settings(unscaled=1, c=1.0, cinv=1.0), Ru)
+    b = agree(lib, settings(unscaled=1, c=0.5, cinv=2.0), Ru)
+    assert a[0] == SOLVED and a[3] == 0.8e-3 and b[0] == GO_ON and b[3] == 1.6e-3 and b[1] == -4.0        # (obj carries cinv too)
+    assert agree(lib, settings(scaling=0, cinv=2.0), block(pri_s=1e-4, dua_s=1e-4))[1] == -2.0             # no scaling: no cinv in obj
+
+
+def test_no_constraints(lib):
+    st, obj, prim, dual, asked, _ = agree(lib, settings(m=0), block(pri_s=5.0, pri_u=5.0, dua_s=1e-4, pinf_lhs=-1.0))
+    assert st == SOLVED and prim == 0.0 and asked == 0
+
+
+def test_primal_infeasible_three_ways(lib):
+    R = block(pinf_lhs=-1.0, dy_s=2.0)                      # first stage: ||dy|| = 2 > eps, support term -1 < -eps ||dy||
+    a = agree(lib, settings(), R, atdy=(9.0, 1e-4))         # ||A' dy|| = 1e-4 < 1e-4 * 2
+    assert a[0] == PINF and a[1] == INFTY and a[4] == 1
+    b = agree(lib, settings(), R, atdy=(0.0, 3e-4))         # second stage fails
+    assert b[0] == GO_ON and b[4] == 1 and b[1] == -2.0
+    c = agree(lib, settings(), block(pinf_lhs=-1e-4, dy_s=2.0), atdy=(0.0, 0.0))      # first stage fails: -1e-4 is not below -2e-4; nothing asked
+    assert c[0] == GO_ON and c[4] == 0
+    u = agree(lib, settings(unscaled=1), block(pinf_lhs=-1.0, dy_u=2.0, dy_s=0.0), atdy=(1e-4, 9.0))      # unscaled: the _u quantities decide
+    assert u[0] == PINF
+
+
+def test_dual_infeasible_three_ways(lib):
+    R = block(qdx=-1.0, dxn_s=2.0)
+    a = agree(lib, settings(), R, pdx=(9.0, 1e-4), adx_ok=True)
+    assert a[0] == DINF and a[1] == -INFTY and a[4] == 6 and a[5] == 1e-4 * 2.0        # the A dx rows are tested against eps_dual_inf ||dx||
+    assert agree(lib, settings(), R, pdx=(9.0, 1e-4), adx_ok=False)[0] == GO_ON        # a row of A dx violates its bound's side
+    b = agree(lib, settings(), R, pdx=(0.0, 3e-4))                                     # ||P dx|| too large: A dx is not looked at
+    assert b[0] == GO_ON and b[4] == 2
+    c = agree(lib, settings(), block(qdx=-1e-4, dxn_s=2.0))                            # first stage fails
+    assert c[0] == GO_ON and c[4] == 0
+    # unscaled: q' dx and ||P dx|| are measured against c eps ||dx||, the rows of A dx against eps ||dx||
+    Ru = block(qdx=-1.5e-4, dxn_u=2.0, dxn_s=0.0)
+    assert agree(lib, settings(unscaled=1, c=0.5, cinv=2.0), Ru, pdx=(0.9e-4, 9.0))[0] == DINF
+    assert agree(lib, settings(unscaled=1, c=1.0, cinv=1.0), Ru, pdx=(0.9e-4, 9.0))[0] == GO_ON
+    d = agree(lib, settings(unscaled=1, c=0.5, cinv=2.0), Ru, pdx=(1.1e-4, 9.0))
+    assert d[0] == GO_ON and d[4] == 2
+
+
+def test_non_convex_guard(lib):
+    for kw in (dict(pri_s=math.nan), dict(dua_s=math.nan), dict(pri_s=2e30), dict(dua_s=2e30)):
+        a = agree(lib, settings(), block(**kw))
+        assert a[0] == NON_CVX and math.isnan(a[1])
+    a = agree(lib, settings(), block(pri_s=math.nan, dua_s=1e-4, ax_s=math.inf))
+    assert a[0] == NON_CVX
+
+
+def test_approximate_pass_runs_at_max_iter_only(lib):
+    R = block(pri_s=5e-3, dua_s=5e-3)                       # between eps (2e-3) and 10 eps (2e-2)
+    assert agree(lib, settings(), R, it=4000, max_iter=4000)[0] == SOLVED_INACC
+    assert agree(lib, settings(), R, it=3975, max_iter=4000)[0] == GO_ON
+    assert agree(lib, settings(), block(pri_s=5e-2, dua_s=5e-3), it=4000, max_iter=4000)[0] == MAX_ITER
+    # certificates at the x10 tolerances
+    Rp = block(pinf_lhs=-1.0, dy_s=2.0)
+    assert agree(lib, settings(), Rp, it=4000, max_iter=4000, atdy=(0.0, 1.5e-3))[0] == PINF_INACC
+    assert agree(lib, settings(), Rp, it=3975, max_iter=4000, atdy=(0.0, 1.5e-3))[0] == GO_ON
+    Rd = block(qdx=-1.0, dxn_s=2.0)
+    a = agree(lib, settings(), Rd, it=4000, max_iter=4000, pdx=(0.0, 1.5e-3))
+    assert a[0] == DINF_INACC and a[5] == 10 * 1e-4 * 2.0
+    # between checks (a rho adaptation point): nothing is tested, max_iter still ends the solve
+    assert agree(lib, settings(), block(pri_s=1e-4, dua_s=1e-4), at_check=0)[0] == GO_ON
+    assert agree(lib, settings(), block(pri_s=1e-4, dua_s=1e-4), at_check=0, it=4000, max_iter=4000)[0] == MAX_ITER
+
+
+def test_single_qp_rules_and_batch_check_agree(lib):
+    """the same block through policy.h's ctl_info + ctl_stage1 + ctl_stage2 and through term_info + batch_check: same status, same info fields"""
+    cases = [(settings(), block(pri_s=1e-4, dua_s=1e-4), {}), (settings(unscaled=1, c=0.5, cinv=2.0), block(pri_u=1e-4, dua_u=0.8e-3, px_u=0, aty_u=0, qn_u=0), {}),
+             (settings(), block(pinf_lhs=-1.0, dy_s=2.0), dict(atdy=(9.0, 1e-4))), (settings(), block(pinf_lhs=-1.0, dy_s=2.0), dict(atdy=(9.0, 3e-4))),
+             (settings(), block(qdx=-1.0, dxn_s=2.0), dict(pdx=(9.0, 1e-4))), (settings(), block(qdx=-1.0, dxn_s=2.0), dict(pdx=(9.0, 1e-4), adx_ok=False)),
+             (settings(unscaled=1, c=0.5, cinv=2.0), block(qdx=-1.5e-4, dxn_u=2.0), dict(pdx=(0.9e-4, 9.0))), (settings(), block(pri_s=math.nan), {})]
+    seen = set()
+    for S, R, kw in cases:
+        st, obj, prim, dual = run_check(lib, S, R, **kw)[:4]
+        info = arr([0.0] * 3)
+        s2 = arr(list(kw.get('atdy', (0, 0))) + list(kw.get('pdx', (0, 0))) + [1.0 if kw.get('adx_ok', True) else 0.0])
+        ctl = lib.br_ctl_check(arr([S[k] for k in ('eps_abs', 'eps_rel', 'eps_pinf', 'eps_dinf', 'c', 'cinv', 'm', 'unscaled', 'scaling')]), arr([R[k] for k in FIELDS]), 0, s2, info)
+        assert ctl == st, (S, R, kw, ctl, st)
+        # ctl_info keeps its own text of term_info's three expressions: the two must give the same bits (obj before the status conventions)
+        want = ref_check(S, R, 25, 4000, 0)
+        for g, w in zip(info, want[1:4]):
+            assert g == w or (math.isnan(g) and math.isnan(w)), (S, R, list(info), want)
+        assert (prim == info[1] or math.isnan(prim)) and (dual == info[2] or math.isnan(dual)) and (obj == info[0] or st in (PINF, DINF, NON_CVX))
+        seen.add(st)
+    assert seen == {SOLVED, GO_ON, PINF, DINF, NON_CVX}
+
+
+def ref_rho(rho_bar, R):
+    pr = R['pri_s'] / (max(R['ax_s'], R['z_s']) + 1e-10)
+    du = R['dua_s'] / (max(R['aty_s'], R['px_s'], R['qn_s']) + 1e-10)
+    return min(max(rho_bar * math.sqrt(pr / (du + 1e-10)), 1e-6), 1e6)
+
+
+def test_rho_estimate_and_factor_rule(lib):
+    new = C.c_double()
+    for factor, fires in ((4.99, 0), (5.01, 1), (1 / 4.99, 0), (1 / 5.01, 1)):        # just inside / outside adaptive_rho_tolerance = 5, both sides
+        R = block(pri_s=factor * factor * 1e-3, dua_s=1e-3, ax_s=2.0, z_s=1.0, aty_s=0.5, px_s=2.0, qn_s=1.0)
+        Rv = arr([R[k] for k in FIELDS])
+        assert lib.br_rho_rule(0.1, 5.0, Rv, C.byref(new)) == fires, factor
+        assert new.value == ref_rho(0.1, R) == lib.br_rho_estimate(0.1, Rv) and new.value == pytest.approx(0.1 * factor, rel=1e-6)
+    hi, lo = block(pri_s=1e6, dua_s=1e-6), block(pri_s=1e-9, dua_s=1e3)               # both clamps (_osqp.py:25-26)
+    assert lib.br_rho_rule(1e3, 5.0, arr([hi[k] for k in FIELDS]), C.byref(new)) == 1 and new.value == 1e6
+    assert lib.br_rho_rule(1e-3, 5.0, arr([lo[k] for k in FIELDS]), C.byref(new)) == 1 and new.value == 1e-6
+    zero = block(pri_s=0.0, dua_s=0.0, ax_s=0.0, z_s=0.0, aty_s=0.0, px_s=0.0, qn_s=0.0)      # the 1e-10 guards: no 0 / 0
+    assert lib.br_rho_estimate(0.1, arr([zero[k] for k in FIELDS])) == ref_rho(0.1, zero) == 1e-6
+
+
+def test_inner_tolerance_rule(lib):
+    st = arr([0.0, 0.0, 0.0])                                # eps_prev, eps_cg, rel_rule
+    lib.br_tol(1, 0.15, 2.0, st)
+    assert st[0] == math.inf and st[1] == 0.15 * 2.0 and st[2] == 0.0
+    for dua0 in (0.0, 1e-13, math.nan, math.inf):            # no usable absolute value at the start: the relative rule
+        lib.br_tol(1, 0.15, dua0, st)
+        assert st[2] == 1.0, dua0
+    lib.br_tol(1, 0.15, 2.0, st)
+    lib.br_tol(0, 0.15, 1.0, st); assert (st[0], st[1], st[2]) == (0.15, 0.15, 0.0)
+    lib.br_tol(0, 0.15, 4.0, st); assert (st[0], st[1]) == (0.15, 0.15)                       # never loosens
+    lib.br_tol(0, 0.15, 1e-3, st); assert st[1] == 0.15 * 1e-3 == st[0]
+    lib.br_tol(0, 0.15, math.nan, st); assert st[1] == 0.15 * 1e-3 == st[0]                   # fmin / fmax drop a NaN: the previous value stays
+    lib.br_tol(0, 0.15, 1e-20, st); assert st[1] == 1e-13 == st[0]                            # floor
+    st = arr([math.inf, 0.0, 1.0])
+    lib.br_tol(0, 0.15, math.inf, st)                        # non-finite: state unchanged, the relative rule stays
+    assert (st[0], st[1], st[2]) == (math.inf, 0.0, 1.0)
+    lib.br_tol(0, 0.15, 1.0, st); assert st[2] == 0.0 and st[1] == 0.15
+
+
+def test_record_has_twelve_fields(lib):
+    rc = arr([7.0] * 13)
+    lib.br_record(rc, SOLVED, 75, -2.5, 1e-7, 2e-7, 0.3, 2, 410.0, 0.25)
+    assert list(rc) == [1.0, 75.0, -2.5, 1e-7, 2e-7, 0.3, 2.0, 410.0, 0.0, 0.0, 0.25, 0.0, 7.0]
+
+
+def test_what_the_caller_reads_in_x_and_y(lib):
+    D, E, cinv, x, dx, y, dy = 2.0, 3.0, 4.0, 0.5, 0.25, 0.7, 0.125
+    for st in (SOLVED, SOLVED_INACC, MAX_ITER, TIME_LIMIT, NON_CVX):                          # an iterate: x = D x, y = cinv E y; as it is without scaling
+        for un in (0, 1):
+            assert lib.br_out_x(st, un, 1, D, x, dx) == D * x and lib.br_out_y(st, un, 1, cinv, E, y, dy) == cinv * E * y
+        assert lib.br_out_x(st, 0, 0, D, x, dx) == x and lib.br_out_y(st, 0, 0, cinv, E, y, dy) == y
+    for st in (PINF, PINF_INACC):                                                             # certificate dy in y (unscaled: E dy), NaN in x
+        assert math.isnan(lib.br_out_x(st, 0, 1, D, x, dx)) and lib.br_out_y(st, 0, 1, cinv, E, y, dy) == dy and lib.br_out_y(st, 1, 1, cinv, E, y, dy) == E * dy
+    for st in (DINF, DINF_INACC):                                                             # certificate dx in x (unscaled: D dx), NaN in y
+        assert math.isnan(lib.br_out_y(st, 0, 1, cinv, E, y, dy)) and lib.br_out_x(st, 0, 1, D, x, dx) == dx and lib.br_out_x(st, 1, 1, D, x, dx) == D * dx
