@@ -498,6 +498,25 @@ void    osqp_hip_set_default_policy(const OSQPHipPolicy *policy);      /* NULL: 
 OSQPInt osqp_hip_trace_read(OSQPSolver *solver, unsigned long long *out, OSQPInt count);
 /* Test hook (used by tests/ only): which = 0: out = A in (n -> m); 1: out = B [in_n; in_m] (n + m -> n), with the scaled device matrices. */
 OSQPInt osqp_hip_test_spmv(OSQPSolver *solver, OSQPInt which, const OSQPFloat *in, OSQPFloat *out);
+/* Test hook (used by tests/ only): one routine of the dense fp64 kernels (dense_hip.hip) on the CALLER's data.  The three host buffers are copied to the
+   solver's device, the routine runs on the solver's stream, and C comes back whole (c_len doubles: a test sees every cell the routine wrote).  Element
+   (i, k) of A is A[a_off + i as_i + k as_k], (k, j) of B is B[b_off + k bs_k + j bs_j], (i, j) of C is C[c_off + i cs_i + j cs_j]; an operand that does
+   not fit its buffer is OSQP_DATA_VALIDATION_ERROR, an operand without a unit stride the routine's own error (OSQP_ALGEBRA_LOAD_ERROR).
+     op 0  dense_gemm:         C (M x N) = beta C + alpha A B, inner dimension K
+     op 1  dense_gemm_sym:     C (N x N, row-major, leading dimension cs_i) = alpha A B for a symmetric product; M, beta, cs_j unused
+     op 2  dense_spd_inverse:  C (N x N, row-major, leading dimension cs_i) <- C^-1 in place; minpiv = the smallest pivot met (<= 0 or NaN: not positive
+                               definite); A, B, M, K, alpha, beta unused */
+typedef struct {
+  OSQPInt op, M, N, K;
+  OSQPFloat alpha, beta;
+  long long as_i, as_k, bs_k, bs_j, cs_i, cs_j;
+  long long a_off, b_off, c_off;
+  long long a_len, b_len, c_len;
+  const OSQPFloat *A, *B;
+  OSQPFloat *C;
+  OSQPFloat minpiv;                /* out (op 2) */
+} OSQPHipDenseTest;
+OSQPInt osqp_hip_test_dense(OSQPSolver *solver, OSQPHipDenseTest *t);
 /* Weight of equality rows relative to inequality rows, rho_eq = factor * rho, used when equality and inequality rows are
    mixed (default 10; the reference's 1e3 is kept when every active row is an equality).  See engine.cpp (Engine::classify_constraints)
    classify_constraints() for the rationale.  Takes effect immediately (rho vector + preconditioner are rebuilt). */

@@ -662,6 +662,11 @@ void scale_warm(Dev &d, const double *x_dev, const double *y_dev, double c);   /
 // ---- probes / tests ----
 bool ktrace_read(Dev &d, unsigned long long *out, int count);   // diagnostic build only (OSQP_HIP_KTRACE); false otherwise
 void test_spmv(Dev &d, int which, const double *in_dev, double *out_dev);   // 0: out = A in ; 1: out = B in
+// one routine of the dense fp64 kernels on the caller's DEVICE operands (include/osqp_hip.h osqp_hip_test_dense: op 0 dense_gemm, 1 dense_gemm_sym,
+// 2 dense_spd_inverse with its own work space); runs on d.stream and synchronises; returns the smallest pivot (op 2; 0 otherwise).  Weak, like
+// lockstep_chunk: a backend without it still links, and the driver answers OSQP_FUNC_NOT_IMPLEMENTED.
+struct DenseProbe { int op, M, N, K; double alpha, beta; long as_i, as_k, bs_k, bs_j, cs_i, cs_j; const double *A, *B; double *C; };
+double test_dense(Dev &d, const DenseProbe &p) __attribute__((weak));
 float time_kernel(Dev &d, int which, int reps);                             // mean ms per launch
 
 }  // namespace be

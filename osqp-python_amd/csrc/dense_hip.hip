@@ -302,5 +302,25 @@ void dense_spd_inverse(void *stream, double *A, long ld, int n, double *work, do
   hipLaunchKernelGGL(k_sym_mirror, dim3((n + 31) / 32, (n + 31) / 32), dim3(256), 0, s, A, ld, n);
 }
 
+// the diagnostic entry (backend.h test_dense, include/osqp_hip.h osqp_hip_test_dense): the three routines above, unchanged, on a test's operands
+double test_dense(Dev &d, const DenseProbe &p) {
+  HIP_CHECK(hipSetDevice(d.device));
+  double minpiv = 0.0;
+  if (p.op == 0) dense_gemm(d.stream, p.M, p.N, p.K, p.alpha, p.A, p.as_i, p.as_k, p.B, p.bs_k, p.bs_j, p.beta, p.C, p.cs_i, p.cs_j);
+  else if (p.op == 1) dense_gemm_sym(d.stream, p.N, p.K, p.alpha, p.A, p.as_i, p.as_k, p.B, p.bs_k, p.bs_j, p.C, p.cs_i);
+  else if (p.N > 0) {
+    const size_t nw = dense_spd_inverse_work(p.N);
+    double *work = static_cast<double *>(alloc(d, sizeof(double) * (nw + 1)));
+    try {
+      dense_spd_inverse(d.stream, p.C, p.cs_i, p.N, work, work + nw);
+      d2h(d, &minpiv, work + nw, sizeof(double));
+    } catch (...) { dfree(d, work); throw; }
+    dfree(d, work);
+  }
+  sync(d);
+  HIP_CHECK(hipGetLastError());
+  return minpiv;
+}
+
 }  // namespace be
 }  // namespace osqp_hip

@@ -1229,6 +1229,35 @@ int Engine::test_spmv(int which, const double *in, double *out) {
   be::dfree(d_, din); be::dfree(d_, dout);
   return OSQP_NO_ERROR;
 }
+int Engine::test_dense(OSQPHipDenseTest *t) {
+  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (!be::test_dense) return OSQP_FUNC_NOT_IMPLEMENTED;
+  if (!t || t->op < 0 || t->op > 2 || t->M < 0 || t->N < 0 || t->K < 0 || !t->C) return OSQP_DATA_VALIDATION_ERROR;
+  // every operand inside its buffer: the last element a routine may address, from non-negative strides and offsets (checked here, not in the kernels)
+  auto fits = [](long long off, long long r, long long sr, long long c, long long sc, long long len) {
+    if (off < 0 || sr < 0 || sc < 0 || len < 0) return false;
+    if (r == 0 || c == 0) return off <= len;
+    return off + (r - 1) * sr + (c - 1) * sc < len;
+  };
+  const bool square = t->op != 0;
+  if (square && (t->cs_i < t->N || !fits(t->c_off, t->N, t->cs_i, t->N, 1, t->c_len))) return OSQP_DATA_VALIDATION_ERROR;
+  if (!square && !fits(t->c_off, t->M, t->cs_i, t->N, t->cs_j, t->c_len)) return OSQP_DATA_VALIDATION_ERROR;
+  const int rows = t->op == 0 ? t->M : t->N;
+  if (t->op != 2 && ((t->a_len > 0 && !t->A) || (t->b_len > 0 && !t->B) || !fits(t->a_off, rows, t->as_i, t->K, t->as_k, t->a_len) || !fits(t->b_off, t->K, t->bs_k, t->N, t->bs_j, t->b_len)))
+    return OSQP_DATA_VALIDATION_ERROR;
+  be::activate(d_);
+  struct Buf { Dev &d; double *p; ~Buf() { if (p) be::dfree(d, p); } };      // (the routine may throw: an operand without a unit stride)
+  const size_t na = t->op != 2 ? (size_t)t->a_len : 0, nb = t->op != 2 ? (size_t)t->b_len : 0, nc = (size_t)t->c_len;
+  Buf a{d_, dev_vec<double>(d_, na)}, b{d_, dev_vec<double>(d_, nb)}, c{d_, dev_vec<double>(d_, nc)};
+  be::h2d(d_, a.p, t->A, sizeof(double) * na);
+  be::h2d(d_, b.p, t->B, sizeof(double) * nb);
+  be::h2d(d_, c.p, t->C, sizeof(double) * nc);
+  const be::DenseProbe p{t->op, t->M, t->N, t->K, t->alpha, t->beta, (long)t->as_i, (long)t->as_k, (long)t->bs_k, (long)t->bs_j, (long)t->cs_i, (long)t->cs_j,
+                         a.p + t->a_off, b.p + t->b_off, c.p + t->c_off};
+  t->minpiv = be::test_dense(d_, p);
+  be::d2h(d_, t->C, c.p, sizeof(double) * nc);
+  return OSQP_NO_ERROR;
+}
 int Engine::get_reordering(int *perm_cols, int *perm_rows) const {
   if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   if (!perm_cols || (m > 0 && !perm_rows)) return OSQP_DATA_VALIDATION_ERROR;

@@ -572,7 +572,9 @@ void dev_publish(Dev &d);                  // pcg_hip.hip: bring the device copy
 void dev_release(Dev &d);                  // pcg_hip.hip: free it (called by destroy)
 // dense_hip.hip: the dense fp64 building blocks of the device-factorised Woodbury correction on the matrix cores (strided operands; SPD inverse in place)
 void dense_gemm(void *stream, int M, int N, int K, double alpha, const double *A, long as_i, long as_k, const double *B, long bs_k, long bs_j, double beta, double *C, long cs_i, long cs_j);
+void dense_gemm_sym(void *stream, int N, int K, double alpha, const double *A, long as_i, long as_k, const double *B, long bs_k, long bs_j, double *C, long ld);
 void dense_spd_inverse(void *stream, double *A, long ld, int n, double *work, double *minpiv);
+size_t dense_spd_inverse_work(int n);
 void wb_release_blas(void *handle);        // woodbury_hip.hip: destroy the rocBLAS handle a Dev's Impl holds (called by destroy)
 
 }  // namespace be

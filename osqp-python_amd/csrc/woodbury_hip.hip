@@ -10,9 +10,6 @@
 
 namespace osqp_hip {
 namespace be {
-// dense_hip.hip (declared here: hip_common.h is one of the two files the committed PMC summaries are stamped with)
-void dense_gemm_sym(void *stream, int N, int K, double alpha, const double *A, long as_i, long as_k, const double *B, long bs_k, long bs_j, double *C, long ld);
-
 namespace {
 
 // ---------------------------------------------------------------------------------------------- Woodbury preconditioner (backend.h DevWb)

@@ -69,6 +69,12 @@ class PolicyStruct(C.Structure):       # OSQPHipPolicy, include/osqp_hip.h (same
                  ('slot_log', C.c_int), ('setup_timing', C.c_int), ('batch_timing', C.c_int), ('woodbury_log', C.c_int), ('woodbury_direct_tol', C.c_double), ('woodbury_fused', C.c_int), ('debug_fail_refactor', C.c_int), ('reorder', C.c_int), ('woodbury_cache', C.c_int), ('kform', C.c_int), ('woodbury_dual', C.c_int), ('woodbury_vendor', C.c_int), ('batch_wave', C.c_int)])
 
 
+class DenseTestStruct(C.Structure):   # OSQPHipDenseTest, include/osqp_hip.h (same order)
+    _fields_ = ([(k, C.c_int) for k in ('op', 'M', 'N', 'K')] + [('alpha', C.c_double), ('beta', C.c_double)] +
+                [(k, C.c_longlong) for k in ('as_i', 'as_k', 'bs_k', 'bs_j', 'cs_i', 'cs_j', 'a_off', 'b_off', 'c_off', 'a_len', 'b_len', 'c_len')] +
+                [('A', c_double_p), ('B', c_double_p), ('C', c_double_p), ('minpiv', C.c_double)])
+
+
 SolverP = C.POINTER(SolverStruct)
 
 
@@ -116,6 +122,7 @@ PROTOTYPES = {
     'osqp_hip_time_kernel': (C.c_int, [SolverP, C.c_int, C.c_int, c_double_p]),
     'osqp_hip_trace_read': (C.c_int, [SolverP, C.POINTER(C.c_ulonglong), C.c_int]),
     'osqp_hip_test_spmv': (C.c_int, [SolverP, C.c_int, c_double_p, c_double_p]),
+    'osqp_hip_test_dense': (C.c_int, [SolverP, C.POINTER(DenseTestStruct)]),
     'osqp_hip_set_rho_eq_factor': (C.c_int, [SolverP, C.c_double]),
     'osqp_hip_default_policy': (None, [C.POINTER(PolicyStruct)]),
     'osqp_hip_set_default_policy': (None, [C.POINTER(PolicyStruct)]),

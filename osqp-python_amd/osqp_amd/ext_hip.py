@@ -328,6 +328,18 @@ class OSQPSolver:
         self._lib.osqp_hip_test_spmv(self._p, int(which), _ptr(vec, _lib.c_double_p), _ptr(out, _lib.c_double_p))
         return out
 
+    def hip_test_dense(self, op, C_buf, A=None, B=None, M=0, N=0, K=0, alpha=1.0, beta=0.0, a_strides=(0, 0), b_strides=(0, 0), c_strides=(0, 1), offsets=(0, 0, 0)):
+        """One routine of the dense fp64 kernels on flat float64 buffers (osqp_hip_test_dense; op 0: gemm, 1: gemm_sym, 2: spd_inverse).  a_strides = (as_i, as_k),
+        b_strides = (bs_k, bs_j), c_strides = (cs_i, cs_j) in elements, offsets = (a_off, b_off, c_off).  Returns (status, the C buffer after the call, minpiv)."""
+        A, B = (None if a is None else np.ascontiguousarray(a, dtype=np.float64).ravel() for a in (A, B))
+        out = np.array(C_buf, dtype=np.float64).ravel()                # (a copy: the caller's canvas stays as it was)
+        t = _lib.DenseTestStruct(int(op), int(M), int(N), int(K), float(alpha), float(beta), int(a_strides[0]), int(a_strides[1]), int(b_strides[0]), int(b_strides[1]),
+                                 int(c_strides[0]), int(c_strides[1]), int(offsets[0]), int(offsets[1]), int(offsets[2]),
+                                 0 if A is None else A.size, 0 if B is None else B.size, out.size,
+                                 _ptr(A, _lib.c_double_p), _ptr(B, _lib.c_double_p), _ptr(out, _lib.c_double_p), 0.0)
+        st = int(self._lib.osqp_hip_test_dense(self._p, C.byref(t)))
+        return st, out, float(t.minpiv)
+
     def hip_set_rho_eq_factor(self, factor):
         return self._lib.osqp_hip_set_rho_eq_factor(self._p, float(factor))
 

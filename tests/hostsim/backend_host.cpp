@@ -9,6 +9,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <vector>
 
 #include "../../osqp-python_amd/csrc/backend.h"
 #include "../../include/osqp_hip.h"
@@ -285,6 +286,74 @@ double ruiz(Dev &, int) { return 1.0; }
 void test_spmv(Dev &d, int which, const double *in, double *out) {
   const DevCsr &M = which == 0 ? d.A : d.B;
   for (int r = 0; r < M.nrows; r++) { double a = 0; for (int k = M.rowptr[r]; k < M.rowptr[r + 1]; k++) a += M.val[k] * in[M.col[k]]; out[r] = a; }
+}
+// The dense routines as plain loops (the CPU tier drives the GPU test's canvases, masks and bounds through them: tests/test_dense_ref.py).
+namespace {
+void host_gemm(const DenseProbe &p, int M, double beta, long cs_i, long cs_j) {
+  if (!((p.as_k == 1 || p.as_i == 1) && (p.bs_k == 1 || p.bs_j == 1))) throw DeviceError("osqp_hip: dense_gemm needs a unit stride in every operand");
+  for (int i = 0; i < M; i++)
+    for (int j = 0; j < p.N; j++) {
+      double a = 0;
+      for (int k = 0; k < p.K; k++) a += p.A[i * p.as_i + k * p.as_k] * p.B[k * p.bs_k + j * p.bs_j];
+      double *c = p.C + i * cs_i + j * cs_j;
+      *c = beta == 0.0 ? p.alpha * a : beta * *c + p.alpha * a;
+    }
+}
+// block Gauss-Jordan without pivoting, 64 columns per step, on the whole matrix; the lower triangle is the mirror of the upper one at the end
+double host_spd_inverse(double *A, long ld, int n) {
+  constexpr int nbk = 64;
+  double minpiv = 1e300;
+  std::vector<double> P(nbk * nbk), R((size_t)nbk * n), Ck((size_t)n * nbk);
+  for (int k0 = 0; k0 < n; k0 += nbk) {
+    const int nb = std::min(nbk, n - k0);
+    for (int i = 0; i < nb; i++) for (int j = 0; j < nb; j++) P[i * nbk + j] = A[(k0 + i) * ld + k0 + j];
+    for (int k = 0; k < nb; k++) {                                       // P = A_kk^-1 in place
+      const double piv = P[k * nbk + k], pi = 1.0 / piv;
+      if (!(piv >= minpiv)) minpiv = piv;
+      for (int j = 0; j < nb; j++) P[k * nbk + j] = (j == k) ? pi : P[k * nbk + j] * pi;
+      for (int i = 0; i < nb; i++) {
+        if (i == k) continue;
+        const double c = P[i * nbk + k];
+        for (int j = 0; j < nb; j++) P[i * nbk + j] = (j == k) ? -c * pi : P[i * nbk + j] - c * P[k * nbk + j];
+      }
+    }
+    if (nb < nbk && !(1.0 >= minpiv)) minpiv = 1.0;                      // (the kernel pads a partial block with the identity: pivots 1)
+    auto inblk = [&](int j) { return j >= k0 && j < k0 + nb; };
+    for (int i = 0; i < n; i++) for (int c = 0; c < nb; c++) Ck[(size_t)i * nbk + c] = inblk(i) ? 0.0 : A[i * ld + k0 + c];
+    for (int i = 0; i < nb; i++)                                         // R = P A_k:  (block k's own columns: zero)
+      for (int j = 0; j < n; j++) {
+        double a = 0;
+        if (!inblk(j)) for (int c = 0; c < nb; c++) a += P[i * nbk + c] * A[(k0 + c) * ld + j];
+        R[(size_t)i * n + j] = a;
+      }
+    for (int i = 0; i < n; i++) {
+      if (inblk(i)) continue;
+      for (int j = 0; j < n; j++) {                                      // A_ij -= A_ik R_j
+        if (inblk(j)) continue;
+        double a = 0;
+        for (int c = 0; c < nb; c++) a += Ck[(size_t)i * nbk + c] * R[(size_t)c * n + j];
+        A[i * ld + j] -= a;
+      }
+      for (int j = 0; j < nb; j++) {                                     // A_ik = -A_ik P
+        double a = 0;
+        for (int c = 0; c < nb; c++) a += Ck[(size_t)i * nbk + c] * P[c * nbk + j];
+        A[i * ld + k0 + j] = -a;
+      }
+    }
+    for (int i = 0; i < nb; i++) for (int j = 0; j < n; j++) A[(k0 + i) * ld + j] = inblk(j) ? P[i * nbk + (j - k0)] : R[(size_t)i * n + j];
+  }
+  for (int i = 0; i < n; i++) for (int j = 0; j < i; j++) A[i * ld + j] = A[j * ld + i];
+  return minpiv;
+}
+}  // namespace
+double test_dense(Dev &, const DenseProbe &p) {
+  if (p.op == 0) { host_gemm(p, p.M, p.beta, p.cs_i, p.cs_j); return 0.0; }
+  if (p.op == 1) {
+    host_gemm(p, p.N, 0.0, p.cs_i, 1);
+    for (int i = 0; i < p.N; i++) for (int j = 0; j < i; j++) p.C[i * p.cs_i + j] = p.C[j * p.cs_i + i];
+    return 0.0;
+  }
+  return p.N > 0 ? host_spd_inverse(p.C, p.cs_i, p.N) : 0.0;
 }
 float time_kernel(Dev &, int, int) { return 0.f; }
 

@@ -1,7 +1,8 @@
 """GPU tier: the dense fp64 kernels of the device-factorised Woodbury correction (dense_hip.hip: strided GEMM on v_mfma_f64_16x16x4, block Gauss-Jordan
 inverse of an SPD matrix) through the paths that use them -- the row-space and the column-space form of the correction (OSQPHipPolicy::woodbury_dual)
 with this engine's own kernels (the default) against the vendor route (OSQPHipPolicy::woodbury_vendor = 1: rocBLAS + rocSOLVER, the A/B switch)
-and the oracle; sizes that are no multiple of the 64 x 64 tile or of the 64-column block step."""
+and the oracle; sizes that are no multiple of the 64 x 64 tile or of the 64-column block step, and one shape on the block boundaries (column-space order 128 =
+two full block steps, row-space order 193 = three and a one-column tail).  The kernels on their own: tests/test_gpu_dense_kernels.py."""
 import contextlib
 import os
 import warnings
@@ -35,7 +36,7 @@ def _rel(a, b):
     return np.abs(a - b).max() / (1 + np.abs(b).max())
 
 
-@pytest.mark.parametrize('nf,ns', [(150, 333), (301, 650)])
+@pytest.mark.parametrize('nf,ns', [(150, 333), (301, 650), (128, 193)])
 @pytest.mark.parametrize('dual', ['1', '0'])
 def test_own_dense_kernels_equal_the_vendor_route_and_the_oracle(nf, ns, dual):
     P, q, A, l, u = problems.lasso_qp(nf, ns)
