@@ -19,6 +19,8 @@
 #include <cstdint>
 #include <stdexcept>
 
+#include "band_ldl.h"            // the padded band of the batch path's direct solve: kBatchNB, kBatchDirectMaxBw, the layout
+
 namespace osqp_hip {
 
 // A failed HIP runtime call.  Thrown by the backend, caught at the C-API boundary (api.cpp) and reported as an
@@ -327,9 +329,6 @@ struct Dev {
 };
 
 // Batched small-QP solve (batch_hip.hip): nbatch problems sharing the solver's scaled A / B, one workgroup each.
-constexpr int kBatchNB = 8;             // pivots per block of the batch kernel's substitutions; the band is stored with kBatchNB zeros of padding per column
-constexpr int kBatchDirectMaxBw = 64 - kBatchNB;   // band limit of the batch kernel's direct solve: one wave holds the live window of a block
-
 constexpr int kBatchRec = 12;     // doubles per problem in the result record of the batch kernels (OSQP_HIP_BATCH_REC in include/osqp_hip.h)
 // The settings snapshot every batch route runs with (Engine::fill_batch_settings): base of BatchParams and LockstepParams
 struct BatchSettings {
@@ -360,7 +359,7 @@ struct BatchParams : BatchSettings {
                                  // the PCG variants exists only to keep K well conditioned for CG (engine.cpp classify_constraints)
   int nents = 0, ntri = 0;
   const int *perm = nullptr;    // [n] position in the permuted order -> variable
-  const int *bp_slot = nullptr; // [nnz(B)] band slot (column * (bw + kBatchNB) + row - column) of each (P + sigma I) entry of B in the permuted lower triangle, else -1
+  const int *bp_slot = nullptr; // [nnz(B)] band slot (band_ldl.h band_slot) of each (P + sigma I) entry of B in the permuted lower triangle, else -1
   const int *ke_slot = nullptr, *ke_ptr = nullptr;   // band slots that receive A' rho A terms, and their product ranges
   const int *kp_row = nullptr;  // per product: constraint row i (-> rho_i)
   const double *kp_val = nullptr;                    // per product: A_ia * A_ib (scaled values; refreshed before every batch call)
@@ -447,8 +446,7 @@ struct AdjointParams {
 // LDS of k_batch_adjoint (bytes): both matrices' values, seven n-vectors, six m-vectors, the reduction scratch and the padded band; 0: does not fit
 inline size_t batch_adjoint_lds_bytes(int n, int m, int nzA, int nzB, int bw) {
   if (bw < 0 || bw > kBatchDirectMaxBw) return 0;
-  const size_t n8 = (size_t)(n + kBatchNB - 1) / kBatchNB * kBatchNB;
-  const size_t b = sizeof(double) * ((size_t)((nzA + 1) & ~1) + (size_t)((nzB + 1) & ~1) + (size_t)7 * n + (size_t)6 * m + 16 + kBatchNB + n8 * (size_t)(bw + kBatchNB) + 64);
+  const size_t b = sizeof(double) * ((size_t)((nzA + 1) & ~1) + (size_t)((nzB + 1) & ~1) + (size_t)7 * n + (size_t)6 * m + 16 + band_doubles(n, bw));
   return b <= 144 * 1024 ? b : 0;
 }
 

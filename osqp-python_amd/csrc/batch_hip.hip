@@ -26,11 +26,6 @@ namespace be {
 namespace {
 
 __device__ __forceinline__ double nmax(double r, double a) { return (a > r || a != a) ? a : r; }
-// value of v in lane `lane` (wave-uniform index) broadcast to the whole wave: two v_readlane_b32
-__device__ __forceinline__ double readlane_f64(double v, int lane) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane), hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-  return __hiloint2double(hi, lo);
-}
 
 // Wave64 reductions with DPP moves (VALU rate; HIP's __shfl_* compile to ds_bpermute_b32 -- an LDS round trip per 32-bit half
 // and step; see backend_hip.hip wave_sum).  Zero fill = identity of the sums and of the maxima of magnitudes.  Result in LANE 63.
@@ -166,7 +161,7 @@ __device__ __forceinline__ void dd_acc(double a, double v, double &hi, double &l
 //
 // DIRECT: the linear system of every ADMM iteration is solved exactly, as the reference's direct path does
 // (_osqp.py:286-311), instead of by PCG.  K = P + sigma I + A' diag(rho) A is assembled in LDS under the bandwidth-reducing
-// permutation prepared by the engine (column-major lower band, W = bw + 1 doubles per column), Cholesky-factorised in
+// permutation prepared by the engine (column-major lower band, padded: band_ldl.h), Cholesky-factorised in
 // place at every rho change, and each solve is two substitutions that keep the live window of the right-hand side in
 // REGISTERS: element e of the vector lives in lane e % 64 from the step that loads it until its own pivot step (bw < 64),
 // a pivot is broadcast with v_readlane, every other lane applies its one update -- no LDS traffic on the dependency chain
@@ -216,14 +211,12 @@ __global__ __launch_bounds__(kBB, (DIRECT && kBB == 256 && EA <= 8) ? (SPEC ? SP
   Red<kBB / 64> red{dy + m};
   double *prod = dy + m + 16;                       // max(nnzA, nnzB) products (register path only)
   const DevCsr &A = P.A, &B = P.B;
-  // DIRECT: band factor.  Column c occupies Lb[c W .. c W + bw] (W = bw + kBatchNB: kBatchNB zeros of padding per column, and
-  // kBatchNB zeros in front of column 0), for n rounded up to a multiple of kBatchNB columns, + 64 doubles of read slack.
-  const int bw = P.bw, W = P.bw + kBatchNB, n8 = (n + kBatchNB - 1) / kBatchNB * kBatchNB;
+  [[maybe_unused]] const int bw = P.bw, W = band_stride(bw), n8 = band_cols(n);      // DIRECT: the band (band_ldl.h)
   // register path: the row pointers of A and B and the direct variant's permutation live in LDS too (they are read in every
   // SpMV / solve of every iteration: an L2 round trip each time otherwise)
   const int prod_len = ((A.nnz > B.nnz ? A.nnz : B.nnz) + 1) & ~1;
   int *rpA = reinterpret_cast<int *>(prod + prod_len), *rpB = rpA + (m + 1), *perm_l = rpB + (n + 1);
-  double *Lb = prod + prod_len + batch_index_doubles(n, m) + kBatchNB;
+  double *Lb = prod + prod_len + batch_index_doubles(n, m) + kBandFront;      // DIRECT: the band factor (band_ldl.h) behind everything else
   double *dinv = zv, *wbuf = r;                     // DIRECT: 1/D and the permuted right-hand side / solution reuse PCG vectors
   constexpr bool kReg = EA > 0;
   double aA[EA > 0 ? EA : 1], aB[EB > 0 ? EB : 1];
@@ -373,40 +366,17 @@ __global__ __launch_bounds__(kBB, (DIRECT && kBB == 256 && EA <= 8) ? (SPEC ? SP
   [[maybe_unused]] auto factorize = [&](double shift) {
     BT_BEGIN();
     // ---- assemble K (lower band, permuted) ----
-    for (int s_ = tid - kBatchNB; s_ < n8 * W + 64; s_ += kBB) Lb[s_] = 0.0;
-    __syncthreads();
+    band_clear<kBB>(Lb, n, bw);
     for (int k = tid; k < B.nnz; k += kBB) { const int s_ = P.bp_slot[k]; if (s_ >= 0) Lb[s_] = B.val[k]; }      // P + sigma I
     __syncthreads();
-    if (shift != 0.0) { for (int c = tid; c < n; c += kBB) Lb[c * W] += shift; __syncthreads(); }
+    if (shift != 0.0) { for (int c = tid; c < n; c += kBB) Lb[band_slot(bw, c, c)] += shift; __syncthreads(); }
     for (int e = tid; e < P.nents; e += kBB) {                                                              // + A' rho A
       double acc = 0.0;
       for (int q_ = P.ke_ptr[e]; q_ < P.ke_ptr[e + 1]; q_++) acc += rho[P.kp_row[q_]] * P.kp_val[q_];
       Lb[P.ke_slot[e]] += acc;
     }
     __syncthreads();
-    // ---- banded Cholesky, right-looking: column c, then the (bw x bw)/2 trailing update spread over the wave ----
-    for (int c = 0; c < n; c++) {
-      const double di = 1.0 / sqrt(Lb[c * W]);
-      const int kmax = min(bw, n - 1 - c);
-      const bool mine = tid >= 1 && tid <= kmax;
-      double v = 0.0;
-      if (mine) v = Lb[c * W + tid] * di;
-      __syncthreads();
-      if (mine) Lb[c * W + tid] = v;
-      if (tid == 0) dinv[c] = di;
-      __syncthreads();
-      for (int t_ = tid; t_ < P.ntri; t_ += kBB) {
-        const int ab = P.tri[t_], a = ab & 255, b_ = ab >> 8;
-        if (b_ <= kmax) Lb[(c + a) * W + (b_ - a)] -= Lb[c * W + b_] * Lb[c * W + a];
-      }
-      __syncthreads();
-    }
-    // K = L L' = L^ D L^' with unit-lower L^ = L diag(1/L_jj), D = diag(L_jj^2): the substitutions then carry no
-    // division or pivot scaling on their dependency chain.  Lb <- L^ (strictly lower part), dinv <- 1/D.
-    for (int s_ = tid; s_ < n * W; s_ += kBB) { const int c = s_ / W, k = s_ - c * W; if (k >= 1 && k <= bw) Lb[s_] *= dinv[c]; }
-    __syncthreads();
-    for (int c = tid; c < n; c += kBB) { const double di = dinv[c]; dinv[c] = di * di; Lb[c * W] = 0.0; }   // (diagonal slots read as L^ = 0)
-    __syncthreads();
+    band_factor<kBB, false>(Lb, n, bw, dinv, P.tri, P.ntri, 0.0);
     BT_END(tk_fact);
   };
   auto set_rho = [&](double rb) {
@@ -428,19 +398,8 @@ __global__ __launch_bounds__(kBB, (DIRECT && kBB == 256 && EA <= 8) ? (SPEC ? SP
       __syncthreads();
     }
   };
-  // DIRECT: out = K^-1 rhs  (both in the caller's variable order):  L^ v = P rhs ;  g = D^-1 v ;  L^' x = g ;  out = P' x.
-  // Substitutions on ONE wave, kBatchNB pivots per block.  Element e lives in lane e % 64 while it is within 64 of the
-  // pivots.  Per block a lane fetches its kBatchNB entries of L^ with plain strided LDS reads one block AHEAD (the padded
-  // band makes every out-of-band read a zero, lanes beyond the block's reach are masked once), then for each pivot:
-  // v_readlane broadcast + one FMA.  Lanes whose element has pivoted store it and continue with the element 64 further on,
-  // already waiting in a register.  ~8 instructions per pivot, no LDS access, branch or division on the dependency chain.
-  // What a pivot costs is the broadcast itself (tools/lane_bcast_bench.hip, one wave: v_readlane_b32 ~14 cycles whether or not it
-  // is on a dependency chain -> 43.5 cycles per pivot for the two halves + FMA; DPP row_newbcast 30.6 but only inside a row of 16;
-  // an LDS round trip 178 per 8 values): resolving a block of 8 through its inverted diagonal block (two rounds of 8 INDEPENDENT
-  // broadcasts instead of a chain of 8) was tried and is slower, 12.6 vs 9.0 us per solve -- twice the broadcasts, and they do
-  // not pipeline.
-  // (k_batch_adjoint below carries a COPY of the general form of these substitutions and of factorize's elimination loop: a change to the padding
-  //  invariants -- the zero slot at Lr - 1, the kBatchNB zeros per column, the 64 doubles of read slack -- has to be made in both places.)
+  // DIRECT: out = K^-1 rhs  (both in the caller's variable order) by the band's substitutions (band_ldl.h); the diagnostic build times the forward pass
+  [[maybe_unused]] auto stamp_fwd = [&](int after) { if (after) BT2_END(tk_fwd); else BT2_BEGIN(); };
   auto ksolve = [&](const double *rhs, double *out) {
     if constexpr (SPEC) {
       if (tid < kBatchSpecN) sp_rhs[tid + (tid >= 64)] = tid < n ? rhs[tid] : 0.0;
@@ -484,7 +443,6 @@ __global__ __launch_bounds__(kBB, (DIRECT && kBB == 256 && EA <= 8) ? (SPEC ? SP
       return;
     }
     const double *__restrict__ Lr = Lb;
-    double *__restrict__ buf = wbuf;
     constexpr int NB = kBatchNB;
     // N128 (n <= 128, chosen by the host for the 256-thread kernels): a lane's (at most) two elements e = tid, tid + 64 stay in
     // registers from the right-hand side to the solution -- no store / refill of finished elements (an LDS round trip behind the
@@ -493,6 +451,10 @@ __global__ __launch_bounds__(kBB, (DIRECT && kBB == 256 && EA <= 8) ? (SPEC ? SP
     // told: not to unroll the block loop (it then keeps every block's LDS addresses and masks live: 80 spilled VGPRs), and not to
     // sink the next block's factor reads below the chain they are meant to overlap (without an LDS write in the loop nothing
     // stops it): 286 k QP/s without the pin, 327 k with it, 310 k for the general form.
+    // (This form and its two fetch lambdas -- the text of band_ldl.h's band_fetch_fwd / band_fetch_bwd -- stay HERE: moved into the header, in any shape,
+    //  the instantiations at the 256-register limit spill 12 - 28 bytes more and one that had no scratch starts to: profiles/band_ldl_ab.txt.  The
+    //  lambdas read the band by the same padding invariants as the header's helpers -- the zero slot at Lr - 1, the kBatchNB zeros per column, the
+    //  read slack: the two texts have to be kept in step.)
     if constexpr (N128) {
 #define KSOLVE_PIN() do { asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
       BT2_BEGIN();
@@ -564,80 +526,7 @@ __global__ __launch_bounds__(kBB, (DIRECT && kBB == 256 && EA <= 8) ? (SPEC ? SP
       return;
 #undef KSOLVE_PIN
     }
-    for (int k = tid; k < n; k += kBB) buf[k] = rhs[perm_l[k]];
-    __syncthreads();
-    const int nblk = n8 / NB;
-    const bool w0 = tid < 64;                                   // the substitutions run on wave 0; other waves wait at the barriers
-    BT2_BEGIN();
-    // ---- forward, unit lower:  v_e = w_e - sum_{j in [e-bw, e)} L^[e][j] v_j ;  L^[p0 + dl][p0 + q] = Lr[(p0 + q) W + dl - q] ----
-    if (w0) {
-      double cur = tid < n ? buf[tid] : 0.0, nxt = 64 + tid < n ? buf[64 + tid] : 0.0;
-      // lanes beyond the block's reach read the zero in front of column 0 eight times (stride 0): no masking after the load
-      auto fetch = [&](int p0, double (&l)[NB]) {
-        const int dl = (tid - p0) & 63;
-        const bool act = dl < bw + NB && p0 < n8;
-        const double *col = act ? Lr + p0 * W + dl : Lr - 1;
-        const int stride = act ? W - 1 : 0;
-#pragma unroll
-        for (int q = 0; q < NB; q++) l[q] = col[q * stride];
-      };
-      auto block = [&](int p0, const double (&l)[NB]) {
-#pragma unroll
-        for (int q = 0; q < NB; q++) { const double vq = readlane_f64(cur, (p0 + q) & 63); cur -= l[q] * vq; }
-        const int dl = (tid - p0) & 63;
-        if (dl < NB) {                                          // pivoted in this block: final
-          const int e = p0 + dl;
-          if (e < n) buf[e] = cur;
-          cur = nxt; nxt = e + 128 < n ? buf[e + 128] : 0.0;   // (requesting this before the chain was tried: the compiler then drains the LDS counter in front of the chain, +17 %)
-        }
-      };
-      double la[NB], lb[NB];                                    // two blocks in flight, roles alternate (no register rotation)
-      fetch(0, la);
-      for (int b = 0; b < nblk; b += 2) {
-        fetch((b + 1) * NB, lb);
-        block(b * NB, la);
-        if (b + 1 < nblk) { fetch((b + 2) * NB, la); block((b + 1) * NB, lb); }
-      }
-    }
-    __syncthreads();
-    BT2_END(tk_fwd);
-    for (int k = tid; k < n; k += kBB) buf[k] *= dinv[k];                          // g = D^-1 v
-    __syncthreads();
-    // ---- backward, unit upper (L^'):  x_i = g_i - sum_{j in (i, i+bw]} L^[j][i] x_j ; blocks from the top, pivots top - q ;
-    //      lane's element i = top - dl ;  L^[top - q][i] = Lr[i W + dl - q] ----
-    if (w0) {
-      auto elem = [&](int top) { return top - ((top - tid) & 63); };
-      const int i0 = elem(n8 - 1);
-      double cur = (i0 >= 0 && i0 < n) ? buf[i0] : 0.0, nxt = i0 - 64 >= 0 ? buf[i0 - 64] : 0.0;
-      auto fetch = [&](int top, double (&l)[NB]) {
-        const int dl = (top - tid) & 63, i = top - dl;
-        const bool act = dl < bw + NB && i >= 0 && top >= 0;
-        const double *row = act ? Lr + i * W + dl : Lr - 1;
-        const int stride = act ? 1 : 0;
-#pragma unroll
-        for (int q = 0; q < NB; q++) l[q] = row[-q * stride];
-      };
-      auto block = [&](int top, const double (&l)[NB]) {
-#pragma unroll
-        for (int q = 0; q < NB; q++) { const double xq = readlane_f64(cur, (top - q) & 63); cur -= l[q] * xq; }
-        const int dl = (top - tid) & 63;
-        if (dl < NB) {
-          const int i = top - dl;
-          if (i < n) buf[i] = cur;
-          cur = nxt; nxt = i - 128 >= 0 ? buf[i - 128] : 0.0;
-        }
-      };
-      double la[NB], lb[NB];
-      fetch(n8 - 1, la);
-      for (int b = nblk - 1; b >= 0; b -= 2) {
-        fetch(b * NB - 1, lb);
-        block(b * NB + NB - 1, la);
-        if (b >= 1) { fetch(b * NB - NB - 1, la); block(b * NB - 1, lb); }
-      }
-    }
-    __syncthreads();
-    for (int k = tid; k < n; k += kBB) out[perm_l[k]] = buf[k];
-    __syncthreads();
+    band_solve<kBB>(Lb, n, bw, dinv, perm_l, wbuf, rhs, out, stamp_fwd);
   };
   set_rho(rho_bar);
   // y = A v   (thread per row of A)
@@ -1333,15 +1222,15 @@ int batch_prepare(Dev &d, const BatchParams &p, const double *Px_b, const double
 //   active set).  The outputs of such an element are the regularised solution.
 namespace {
 __global__ __launch_bounds__(256) void k_batch_adjoint(AdjointParams P) {
-  constexpr int kBB = 256, NB = kBatchNB;
+  constexpr int kBB = 256;
   extern __shared__ __attribute__((aligned(16))) double sm[];
   const int n = P.n, m = P.m, tid = threadIdx.x, b = blockIdx.x, nzA = P.A.nnz, nzB = P.B.nnz;
   if (b >= P.nbatch) return;
-  const int bw = P.bw, W = P.bw + NB, n8 = (n + NB - 1) / NB * NB;
   double *Av = sm, *Bv = Av + ((nzA + 1) & ~1), *x = Bv + ((nzB + 1) & ~1), *rx = x + n, *gx = rx + n, *rhs = gx + n, *sol = rhs + n, *wbuf = sol + n, *dinv = wbuf + n;
   double *y = dinv + n, *w = y + m, *ra = w + m, *ga = ra + m, *t = ga + m, *sd = t + m;
   Red<kBB / 64> red{sd + m};
-  double *Lb = sd + m + 16 + NB;
+  const int bw = P.bw;
+  double *Lb = sd + m + 16 + kBandFront;
   const int *Arp = P.A.rowptr, *Ac = P.A.col, *Brp = P.B.rowptr, *Bc = P.B.col;
   // ---- the problem's own unscaled matrices in the CSR layouts ----
   const double *Ar = P.Ax_b ? P.Ax_b + (size_t)b * P.nzA : P.Araw, *Pr = P.Px_b ? P.Px_b + (size_t)b * P.nzP : P.Praw;
@@ -1373,13 +1262,11 @@ __global__ __launch_bounds__(256) void k_batch_adjoint(AdjointParams P) {
   }
   __syncthreads();
   const double nact = red.sum(nact_l), gmax = red.max(gmax_l);
-  // ---- S = P + delta I + A_a' A_a / delta in the band (lower, permuted: k_batch_admm factorize) and its Cholesky factor ----
-  bool bad = false;
-  for (int s_ = tid - NB; s_ < n8 * W + 64; s_ += kBB) Lb[s_] = 0.0;
-  __syncthreads();
+  // ---- S = P + delta I + A_a' A_a / delta in the band (lower, permuted: the forward's slots and product lists) and its factor (band_ldl.h) ----
+  band_clear<kBB>(Lb, n, bw);
   for (int k = tid; k < nzB; k += kBB) { const int s_ = P.bp_slot[k]; if (s_ >= 0) Lb[s_] = Bv[k]; }
   __syncthreads();
-  for (int c = tid; c < n; c += kBB) Lb[c * W] += P.delta;
+  for (int c = tid; c < n; c += kBB) Lb[band_slot(bw, c, c)] += P.delta;
   __syncthreads();
   for (int e = tid; e < P.nents; e += kBB) {
     double acc = 0.0;
@@ -1387,102 +1274,8 @@ __global__ __launch_bounds__(256) void k_batch_adjoint(AdjointParams P) {
     Lb[P.ke_slot[e]] += acc;
   }
   __syncthreads();
-  for (int c = 0; c < n; c++) {
-    double pv = Lb[c * W];
-    if (!(pv > 0.0) || pv > 1e300) { bad = true; pv = (fabs(pv) > P.delta && fabs(pv) <= 1e300) ? fabs(pv) : 1.0; }      // (block-uniform: every thread reads the same pivot)
-    const double di = 1.0 / sqrt(pv);
-    const int kmax = min(bw, n - 1 - c);
-    const bool mine = tid >= 1 && tid <= kmax;
-    double v = 0.0;
-    if (mine) v = Lb[c * W + tid] * di;
-    __syncthreads();
-    if (mine) Lb[c * W + tid] = v;
-    if (tid == 0) dinv[c] = di;
-    __syncthreads();
-    for (int t_ = tid; t_ < P.ntri; t_ += kBB) {
-      const int ab = P.tri[t_], a = ab & 255, b_ = ab >> 8;
-      if (b_ <= kmax) Lb[(c + a) * W + (b_ - a)] -= Lb[c * W + b_] * Lb[c * W + a];
-    }
-    __syncthreads();
-  }
-  // S = L^ D L^' with unit-lower L^: Lb <- L^ (strictly lower part, diagonal slots read as zero), dinv <- 1 / D
-  for (int s_ = tid; s_ < n * W; s_ += kBB) { const int c = s_ / W, k = s_ - c * W; if (k >= 1 && k <= bw) Lb[s_] *= dinv[c]; }
-  __syncthreads();
-  for (int c = tid; c < n; c += kBB) { const double di = dinv[c]; dinv[c] = di * di; Lb[c * W] = 0.0; }
-  __syncthreads();
-  // out = S^-1 in: the substitutions of k_batch_admm's ksolve (general form): wave 0, element e in lane e % 64 while within 64 of the pivots
-  auto ksolve = [&](const double *in, double *out) {
-    const double *__restrict__ Lr = Lb;
-    double *__restrict__ buf = wbuf;
-    for (int k = tid; k < n; k += kBB) buf[k] = in[P.perm[k]];
-    __syncthreads();
-    const int nblk = n8 / NB;
-    const bool w0 = tid < 64;
-    if (w0) {
-      double cur = tid < n ? buf[tid] : 0.0, nxt = 64 + tid < n ? buf[64 + tid] : 0.0;
-      auto fetch = [&](int p0, double (&l)[NB]) {
-        const int dl = (tid - p0) & 63;
-        const bool act = dl < bw + NB && p0 < n8;
-        const double *col = act ? Lr + p0 * W + dl : Lr - 1;
-        const int stride = act ? W - 1 : 0;
-#pragma unroll
-        for (int q = 0; q < NB; q++) l[q] = col[q * stride];
-      };
-      auto block = [&](int p0, const double (&l)[NB]) {
-#pragma unroll
-        for (int q = 0; q < NB; q++) { const double vq = readlane_f64(cur, (p0 + q) & 63); cur -= l[q] * vq; }
-        const int dl = (tid - p0) & 63;
-        if (dl < NB) {
-          const int e = p0 + dl;
-          if (e < n) buf[e] = cur;
-          cur = nxt; nxt = e + 128 < n ? buf[e + 128] : 0.0;
-        }
-      };
-      double la[NB], lb[NB];
-      fetch(0, la);
-      for (int k = 0; k < nblk; k += 2) {
-        fetch((k + 1) * NB, lb);
-        block(k * NB, la);
-        if (k + 1 < nblk) { fetch((k + 2) * NB, la); block((k + 1) * NB, lb); }
-      }
-    }
-    __syncthreads();
-    for (int k = tid; k < n; k += kBB) buf[k] *= dinv[k];
-    __syncthreads();
-    if (w0) {
-      auto elem = [&](int top) { return top - ((top - tid) & 63); };
-      const int i0 = elem(n8 - 1);
-      double cur = (i0 >= 0 && i0 < n) ? buf[i0] : 0.0, nxt = i0 - 64 >= 0 ? buf[i0 - 64] : 0.0;
-      auto fetch = [&](int top, double (&l)[NB]) {
-        const int dl = (top - tid) & 63, i = top - dl;
-        const bool act = dl < bw + NB && i >= 0 && top >= 0;
-        const double *row = act ? Lr + i * W + dl : Lr - 1;
-        const int stride = act ? 1 : 0;
-#pragma unroll
-        for (int q = 0; q < NB; q++) l[q] = row[-q * stride];
-      };
-      auto block = [&](int top, const double (&l)[NB]) {
-#pragma unroll
-        for (int q = 0; q < NB; q++) { const double xq = readlane_f64(cur, (top - q) & 63); cur -= l[q] * xq; }
-        const int dl = (top - tid) & 63;
-        if (dl < NB) {
-          const int i = top - dl;
-          if (i < n) buf[i] = cur;
-          cur = nxt; nxt = i - 128 >= 0 ? buf[i - 128] : 0.0;
-        }
-      };
-      double la[NB], lb[NB];
-      fetch(n8 - 1, la);
-      for (int k = nblk - 1; k >= 0; k -= 2) {
-        fetch(k * NB - 1, lb);
-        block(k * NB + NB - 1, la);
-        if (k >= 1) { fetch(k * NB - NB - 1, la); block(k * NB - 1, lb); }
-      }
-    }
-    __syncthreads();
-    for (int k = tid; k < n; k += kBB) out[P.perm[k]] = buf[k];
-    __syncthreads();
-  };
+  const bool bad = band_factor<kBB, true>(Lb, n, bw, dinv, P.tri, P.ntri, P.delta);
+  auto ksolve = [&](const double *in, double *out) { band_solve<kBB>(Lb, n, bw, dinv, P.perm, wbuf, in, out, [](int) {}); };
   // ---- first solve + refinement steps ----
   for (int it = 0; it <= P.refine; it++) {
     for (int i = tid; i < m; i += kBB) {

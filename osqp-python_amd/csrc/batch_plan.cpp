@@ -22,8 +22,7 @@ int batch_wave_n8(int n) { return n <= 64 ? 64 : (n <= 120 ? 120 : 128); }
 size_t batch_lds_bytes(int n, int m) { return batch_lds_bytes_nnz(n, m, 0); }
 size_t batch_direct_lds_bytes(int n, int m, int nnz, int bw) {
   if (bw < 0 || bw > kBatchDirectMaxBw) return 0;
-  const size_t n8 = (size_t)(n + kBatchNB - 1) / kBatchNB * kBatchNB;
-  const size_t b = sizeof(double) * ((size_t)10 * n + (size_t)8 * m + 16 + (size_t)((nnz + 1) & ~1) + batch_index_doubles(n, m) + kBatchNB + n8 * (bw + kBatchNB) + 64);
+  const size_t b = sizeof(double) * ((size_t)10 * n + (size_t)8 * m + 16 + (size_t)((nnz + 1) & ~1) + batch_index_doubles(n, m) + band_doubles(n, bw));
   return b <= 144 * 1024 ? b : 0;         // (above the default 64 KB dynamic-LDS limit: batch_solve raises it; gfx950 has 160 KB per CU)
 }
 size_t batch_wave_lds_bytes(int n, int m, int steps) {

@@ -562,16 +562,15 @@ void Engine::prepare_batch_direct() {
   int bw = 0;
   for (int j = 0; j < n; j++) for (int c : adj[j]) bw = std::max(bw, std::abs(iperm[j] - iperm[c]));
   bd_.bw_symbolic = bw;
-  const int W = bw + kBatchNB;                              // column stride of the padded band (batch_hip.hip)
   if (bw > kBatchDirectMaxBw || !be::batch_direct_lds_bytes(n, m, std::max(nzA, nzB), bw)) return;
-  // band slot (column-major band: slot = col * W + (row - col), row >= col, permuted indices) of the P + sigma I entries of B
+  // band slot (band_ldl.h: column-major lower band, row >= col, permuted indices) of the P + sigma I entries of B
   std::vector<int> bp_slot(nzB, -1);
   for (int j = 0; j < n; j++)
     for (int k = Brp_[j]; k < Brp_[j + 1]; k++) {
       const int c = Bj_[k];
       if (c >= n) continue;
       const int pr = iperm[j], pc = iperm[c];
-      if (pr >= pc) bp_slot[k] = pc * W + (pr - pc);
+      if (pr >= pc) bp_slot[k] = band_slot(bw, pc, pr);
     }
   // products of A' rho A, grouped by slot
   struct Prod { int slot, row, a, b; };
@@ -581,7 +580,7 @@ void Engine::prepare_batch_direct() {
       for (int b = a; b < Arp_[i + 1]; b++) {
         const int pa = iperm[Arj_[a]], pb = iperm[Arj_[b]];
         const int r = std::max(pa, pb), c = std::min(pa, pb);
-        prods.push_back({c * W + (r - c), i, a, b});
+        prods.push_back({band_slot(bw, c, r), i, a, b});
       }
   std::stable_sort(prods.begin(), prods.end(), [](const Prod &x, const Prod &y) { return x.slot < y.slot; });
   std::vector<int> ke_slot, ke_ptr, kp_row(prods.size()), kp_a(prods.size()), kp_b(prods.size());

@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'osqp-python_amd', 'csrc')
 SRCS = [os.path.join(ROOT, 'tests', 'hostsim', 'batch_plan_probe.cpp'), os.path.join(CSRC, 'batch_plan.cpp')]
 OUT = os.path.join(ROOT, 'tests', '_build', 'libbatch_plan_probe.so')
-DEPS = SRCS + [os.path.join(CSRC, 'backend.h')]
+DEPS = SRCS + [os.path.join(CSRC, 'backend.h'), os.path.join(CSRC, 'band_ldl.h')]
 NO_SPEC, SPEC_WORKGROUP, SPEC_WAVE = 0, 1, 2                 # BatchPlan::Spec
 FIELDS = ('spec', 'split', 'variant', 'e', 'spec_e', 'spec_w', 'split_w', 'n8', 'wgs', 'wgs_all')
 

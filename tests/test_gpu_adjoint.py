@@ -202,6 +202,39 @@ def test_batch_of_mpc_problems():
     assert set(only) == {'dq', 'rec'} and np.array_equal(only['dq'], res['dq'])
 
 
+@pytest.mark.parametrize('N', [11, 15])
+def test_batch_of_mpc_problems_beyond_128_variables(N):
+    """The substitutions past n = 128 (csrc/band_ldl.h band_solve, the adjoint kernel's own instance): N = 11 gives n = 132, m = 264 -- a lane's third
+    element, the e + 128 refill, first exists; N = 15 gives n = 180, m = 360 -- the refill reads real elements and the elimination runs a third
+    64-pivot epoch.  Same assertions and bounds as test_batch_of_mpc_problems."""
+    B = 4
+    P, q, A, L, U = problems.mpc_batch(B, N=N, seed=2)
+    n, m = P.shape[0], A.shape[0]
+    assert (n, m) == (12 * N, 24 * N) and n > 128
+    s = _setup(P, q, A, L[0], U[0])
+    x, y, rec = s._solver.hip_batch_solve(l=L, u=U)
+    assert (rec[:, 0] == SOLVED).all(), rec[:, 0]
+    dx = np.random.default_rng(5).standard_normal((B, n))
+    res = s._solver.hip_batch_adjoint(x, y, dx, l=L, u=U)
+    assert res['rec'].shape == (B, 4) and (res['rec'][:, 0] == 0).all(), res['rec'][:, :3]
+    assert (res['rec'][:, 2] < s._solver.ADJOINT_TOL).all()
+    worst = {}
+    for b in range(B):
+        _conditions(P, A, L[b], U[b], x[b], y[b])
+        dev, bound, g = _deviations({k: res[k][b] for k in ('dP', 'dq', 'dA', 'dl', 'du')}, P, A, L[b], U[b], x[b], y[b], dx[b])
+        assert int(res['rec'][b, 1]) == int((g['low'] | g['upp']).sum())
+        print(N, b, 'bound %.2e' % bound, dev, 'residual %.2e' % res['rec'][b, 2])
+        assert max(dev.values()) <= 1.0, (b, dev, bound)
+        for k, v in dev.items():
+            worst[k] = max(worst.get(k, 0.0), v)
+    record_deviation('test_batch_of_mpc_problems_beyond_128_variables', 'N=%d B=%d' % (N, B), worst_residual=float(res['rec'][:, 2].max()), **worst)
+    again = s._solver.hip_batch_adjoint(x, y, dx, l=L, u=U)
+    on_dev = _device_adjoint(s, x, y, dx, L, U)
+    for k in ('dP', 'dq', 'dA', 'dl', 'du', 'rec'):
+        assert np.array_equal(res[k], again[k]), k                          # deterministic: bit-identical
+        assert np.array_equal(res[k], on_dev[k]), k                         # host-array and device entry points: bit for bit
+
+
 def test_largest_dense_problem_the_band_limit_allows():
     """n = 57 dense: half bandwidth 56 = the limit, LDS above 64 KB.  (x, y) from the oracle: the adjoint does not depend on which variant solved."""
     from oracle import Oracle, SOLVED as OSOLVED
