@@ -36,9 +36,8 @@ struct EAdjClass : NoPrefetch {
   double cnt = 0;
   __device__ __forceinline__ void operator()(int i, const double (&s)[1]) {
     const double zi = Einv[i] * s[0], yi = y[i], li = lraw[i], ui = uraw[i];
-    bool low = zi - li < -yi, upp = !low && (ui - zi < yi);
-    if (li == ui) { low = yi < 0.0; upp = !low; }
-    const int k = low ? 1 : (upp ? 2 : 0);
+    const RowActive act = adjoint_active(zi, li, ui, yi);
+    const int k = act.low ? 1 : (act.upp ? 2 : 0);
     const double b = (k && dy) ? -(E[i] * dy[i]) : 0.0;
     code[i] = k;
     l[i] = k ? b : -OSQP_INFTY; u[i] = k ? b : OSQP_INFTY;      // active rows: equalities at b~; the others: free

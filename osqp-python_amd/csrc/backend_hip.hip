@@ -33,9 +33,8 @@ struct EKr1 : NoPrefetch {
     pu = nanmax(pu, fabs(ei * pr)); au = nanmax(au, fabs(ei * ax)); zu = nanmax(zu, fabs(ei * zi));
     ps = nanmax(ps, fabs(pr)); as = nanmax(as, fabs(ax)); zs = nanmax(zs, fabs(zi));
     du = nanmax(du, fabs(E[i] * dyi)); ds = nanmax(ds, fabs(dyi));
-    lhs += ui * fmax(dyi, 0.0) + li * fmin(dyi, 0.0);                        // _osqp.py:811-813
-    if (yi > 0.0 && ui < OSQP_INFTY * 1e-4) sup += ui * yi;
-    else if (yi < 0.0 && li > -OSQP_INFTY * 1e-4) sup += li * yi;
+    lhs += support_term(li, ui, dyi);
+    sup += support_finite(li, ui, yi);
   }
 };
 // cond != 0 (boundary group of a device-driven solve): run only when the chunk has finished at a termination check / adaptation point
@@ -137,7 +136,7 @@ struct EViol : NoPrefetch {
   const double *l, *u, *Einv; double thr; int unscaled; double viol = 0;
   __device__ __forceinline__ void operator()(int i, const double (&s)[1]) {    // _osqp.py:861-872
     const double a = unscaled ? Einv[i] * s[0] : s[0];
-    if ((u[i] < OSQP_INFTY * 1e-4 && a > thr) || (l[i] > -OSQP_INFTY * 1e-4 && a < -thr)) viol += 1.0;
+    if (adx_violates(a, l[i], u[i], thr)) viol += 1.0;
   }
 };
 __global__ __launch_bounds__(kBlock) void k_inf_dual_a(Dev d, double thr, int unscaled, int cond) {
@@ -156,8 +155,8 @@ __global__ __launch_bounds__(kBlock) void k_set_rho(Dev d, double rho_bar, int c
   const int stride = gridDim.x * kBlock;
   for (int i = blockIdx.x * kBlock + threadIdx.x; i < d.m; i += stride) {
     const int t = d.ctype[i];
-    const double eqf = d.eq_from_cnt ? (d.cnt[0] == 0 ? 1e3 : d.rho_eq_mixed) : d.rho_eq_factor;   // engine.cpp classify_constraints
-    const double r = t == -1 ? 1e-6 : (t == 1 ? eqf * rho_bar : rho_bar);                 // _osqp.py:520-522, :1590-1594
+    const double eqf = d.eq_from_cnt ? eq_weight(d.cnt[0] == 0, d.rho_eq_mixed) : d.rho_eq_factor;   // engine.cpp classify_constraints
+    const double r = row_rho(t, rho_bar, eqf * rho_bar);                                  // (_osqp.py:1590-1594)
     d.rho[i] = r; d.rho_inv[i] = 1.0 / r;
     d.v[i] = r * d.z[i] - d.y[i]; d.ztg[i] = d.zt[i]; d.t0[i] = r * d.zt[i];      // (the x~ sequence has a kink at a rho change: the next PCG starts from x~ itself)
   }
@@ -200,8 +199,8 @@ __global__ __launch_bounds__(kBlock) void k_init_m(Dev d, int full) {
 __global__ __launch_bounds__(kBlock) void k_normalcone(Dev d) {
   const int stride = gridDim.x * kBlock;
   for (int i = blockIdx.x * kBlock + threadIdx.x; i < d.m; i += stride) {
-    const double t = d.z[i] + d.y[i], zn = fmin(fmax(t, d.l[i]), d.u[i]);
-    d.z[i] = zn; d.y[i] = t - zn;
+    const ConeRow c = normal_cone(d.z[i] + d.y[i], d.l[i], d.u[i]);
+    d.z[i] = c.z; d.y[i] = c.y;
   }
 }
 __global__ void k_set_scal(double *scal, double rel, double ab) { scal[S_TOL_REL] = rel; scal[S_TOL_ABS] = ab; }
@@ -214,11 +213,7 @@ __global__ __launch_bounds__(kBlock) void k_scale_bounds(Dev d, int rho_is_vec) 
   for (int i = blockIdx.x * kBlock + threadIdx.x; i < d.m; i += gridDim.x * kBlock) {
     const double ls = d.E[i] * d.lraw[i], us = d.E[i] * d.uraw[i];
     d.l[i] = ls; d.u[i] = us;
-    int t;
-    if (ls < -OSQP_INFTY * 1e-4 && us > OSQP_INFTY * 1e-4) t = -1;
-    else if (us - ls < 1e-4) t = 1;
-    else t = 0;
-    if (!rho_is_vec) t = 0;
+    const int t = row_class(ls, us, rho_is_vec);
     d.ctype[i] = t;
     ineq += (t == 0);
   }

@@ -18,14 +18,12 @@
 
 #include "../../include/osqp_hip.h"
 #include "backend.h"
-#include "term_rules.h"
+#include "step_rules.h"
 
 namespace osqp_hip {
 namespace be {
 
 namespace {
-
-__device__ __forceinline__ double nmax(double r, double a) { return (a > r || a != a) ? a : r; }
 
 // Wave64 reductions with DPP moves (VALU rate; HIP's __shfl_* compile to ds_bpermute_b32 -- an LDS round trip per 32-bit half
 // and step; see backend_hip.hip wave_sum).  Zero fill = identity of the sums and of the maxima of magnitudes.  Result in LANE 63.
@@ -40,8 +38,8 @@ __device__ __forceinline__ double wsum63(double v) {
   return v;
 }
 __device__ __forceinline__ double wmax63(double v) {
-  v = nmax(v, bdpp<0xb1>(v)); v = nmax(v, bdpp<0x4e>(v)); v = nmax(v, bdpp<0x114>(v)); v = nmax(v, bdpp<0x118>(v));
-  v = nmax(v, bdpp<0x142, 0xa>(v)); v = nmax(v, bdpp<0x143, 0xc>(v));
+  v = nanmax(v, bdpp<0xb1>(v)); v = nanmax(v, bdpp<0x4e>(v)); v = nanmax(v, bdpp<0x114>(v)); v = nanmax(v, bdpp<0x118>(v));
+  v = nanmax(v, bdpp<0x142, 0xa>(v)); v = nanmax(v, bdpp<0x143, 0xc>(v));
   return v;
 }
 
@@ -71,7 +69,7 @@ struct Red {
       __syncthreads();
       double t = 0.0;
 #pragma unroll
-      for (int w = 0; w < NW; w++) t = nmax(t, s[w]);
+      for (int w = 0; w < NW; w++) t = nanmax(t, s[w]);
       __syncthreads();
       return t;
     }
@@ -95,7 +93,7 @@ struct Red {
       for (int k = 0; k < S; k++) { const double v = wsum63(sm[k]); if (last) scr[w * (K + S) + K + k] = v; }
       __syncthreads();
 #pragma unroll
-      for (int k = 0; k < K; k++) { double t = 0.0; for (int q = 0; q < NW; q++) t = nmax(t, scr[q * (K + S) + k]); mx[k] = t; }
+      for (int k = 0; k < K; k++) { double t = 0.0; for (int q = 0; q < NW; q++) t = nanmax(t, scr[q * (K + S) + k]); mx[k] = t; }
 #pragma unroll
       for (int k = 0; k < S; k++) { double t = 0.0; for (int q = 0; q < NW; q++) t += scr[q * (K + S) + K + k]; sm[k] = t; }
       __syncthreads();
@@ -109,7 +107,7 @@ struct Red {
       __syncthreads();
       a = 0.0; b = 0.0;
 #pragma unroll
-      for (int w = 0; w < NW; w++) { a += s[w]; b = nmax(b, s[8 + w]); }
+      for (int w = 0; w < NW; w++) { a += s[w]; b = nanmax(b, s[8 + w]); }
       __syncthreads();
     }
   }
@@ -267,22 +265,20 @@ __global__ __launch_bounds__(kBB, (DIRECT && kBB == 256 && EA <= 8) ? (SPEC ? SP
   }
   // ---- load the problem ----
   // inputs arrive UNSCALED; the scaling of update_lin_cost / update_bounds / warm_start (_osqp.py:1328, :1357-1358, :1505-1506)
-  // is applied here:  q <- c D q,  l,u <- E clamp(l,u),  x <- Dinv x,  y <- c Einv y
+  // is applied here (step_rules.h in_q / in_l / in_u / in_x / in_y)
   for (int j = tid; j < n; j += kBB) {
-    q[j] = P.c * P.D[j] * (P.q ? P.q[(size_t)b * n + j] : P.q0[j]);
-    x[j] = P.warm ? P.x[(size_t)b * n + j] * P.Dinv[j] : 0.0; dx[j] = 0.0;
+    q[j] = in_q(P.c, P.D[j], P.q ? P.q[(size_t)b * n + j] : P.q0[j]);
+    x[j] = P.warm ? in_x(P.x[(size_t)b * n + j], P.Dinv[j]) : 0.0; dx[j] = 0.0;
   }
   int n_ineq_local = 0;
   for (int i = tid; i < m; i += kBB) {
-    const double li = P.E[i] * fmax(P.l ? P.l[(size_t)b * m + i] : P.l0[i], -OSQP_INFTY), ui = P.E[i] * fmin(P.u ? P.u[(size_t)b * m + i] : P.u0[i], OSQP_INFTY);
-    l[i] = li; u[i] = ui; y[i] = P.warm ? P.y[(size_t)b * m + i] * P.Einv[i] * P.c : 0.0; dy[i] = 0.0;
-    int ty = (li < -OSQP_INFTY * 1e-4 && ui > OSQP_INFTY * 1e-4) ? -1 : ((ui - li < 1e-4) ? 1 : 0);   // _osqp.py:505-518
-    if (!P.rho_is_vec) ty = 0;
-    n_ineq_local += (ty == 0);
+    const double li = in_l(P.E[i], P.l ? P.l[(size_t)b * m + i] : P.l0[i]), ui = in_u(P.E[i], P.u ? P.u[(size_t)b * m + i] : P.u0[i]);
+    l[i] = li; u[i] = ui; y[i] = P.warm ? in_y(P.y[(size_t)b * m + i], P.Einv[i], P.c) : 0.0; dy[i] = 0.0;
+    n_ineq_local += (row_class(li, ui, P.rho_is_vec) == 0);
   }
   __syncthreads();
   const double n_ineq = red.sum((double)n_ineq_local);
-  const double eqf = (n_ineq == 0.0) ? 1e3 : (DIRECT ? P.eq_factor_direct : P.eq_factor);  // engine.cpp classify_constraints()
+  const double eqf = eq_weight(n_ineq == 0.0, DIRECT ? P.eq_factor_direct : P.eq_factor);
   double rho_bar = P.rho0;
   // SPEC: K^-1 of this problem, and the LDS the form needs (in the band's place): the zero-padded right-hand side, 1 / (1 + delta lambda)
   // SPEC: K^-1 in the register layout of the f64 matrix instruction's result (v_mfma_f64_16x16x4: lane l, register r of a 16 x 16 tile = element
@@ -293,12 +289,7 @@ __global__ __launch_bounds__(kBB, (DIRECT && kBB == 256 && EA <= 8) ? (SPEC ? SP
   if constexpr (SPEC) {
     // V was built for ONE set of constraint classes: a problem whose own bounds give other classes (or another equality weight) is not ours
     double mism = (eqf != P.sp_eqf) ? 1.0 : 0.0;
-    for (int i = tid; i < m; i += kBB) {
-      const double li = l[i], ui = u[i];
-      int ty = (li < -OSQP_INFTY * 1e-4 && ui > OSQP_INFTY * 1e-4) ? -1 : ((ui - li < 1e-4) ? 1 : 0);
-      if (!P.rho_is_vec) ty = 0;
-      if (ty != P.sp_ctype[i]) mism = 1.0;
-    }
+    for (int i = tid; i < m; i += kBB) { if (row_class(l[i], u[i], P.rho_is_vec) != P.sp_ctype[i]) mism = 1.0; }
     mism = red.sum(mism);
     if (mism != 0.0) { if (tid == 0) P.rec[(size_t)b * kBatchRec] = kBatchUnsolved; return; }
   }
@@ -380,11 +371,11 @@ __global__ __launch_bounds__(kBB, (DIRECT && kBB == 256 && EA <= 8) ? (SPEC ? SP
     BT_END(tk_fact);
   };
   auto set_rho = [&](double rb) {
+    // (step_rules.h row_rho, in this kernel's own text: with eqf * rb formed outside the equality branch, as the call needs it, three instantiations
+    //  without scratch start to spill and the 64-thread PCG one drops from three waves per SIMD to two: profiles/step_rules_ab.txt)
     for (int i = tid; i < m; i += kBB) {
-      const double li = l[i], ui = u[i];
-      int ty = (li < -OSQP_INFTY * 1e-4 && ui > OSQP_INFTY * 1e-4) ? -1 : ((ui - li < 1e-4) ? 1 : 0);
-      if (!P.rho_is_vec) ty = 0;
-      rho[i] = ty == -1 ? 1e-6 : (ty == 1 ? eqf * rb : rb);                                       // _osqp.py:520-522
+      const int ty = row_class(l[i], u[i], P.rho_is_vec);
+      rho[i] = ty == -1 ? kRowRhoLoose : (ty == 1 ? eqf * rb : rb);                               // _osqp.py:520-522
     }
     __syncthreads();
     if constexpr (SPEC) update_kinv(rb);
@@ -548,15 +539,18 @@ __global__ __launch_bounds__(kBB, (DIRECT && kBB == 256 && EA <= 8) ? (SPEC ? SP
   // residuals of the current (x, z, y): returns through references; all threads hold identical values
   TermRes R;
   const TermSet tset = {P.eps_abs, P.eps_rel, P.eps_pinf, P.eps_dinf, P.c, P.cinv, m, P.unscaled, P.scaling};
+  // (step_rules.h res_row_a / res_row_b / res_store, in this kernel's own text -- the same expressions in the same order, to be kept in step: folded
+  //  through the header's accumulators the instantiations at 256 registers spill 24 - 56 bytes more and three that had no scratch start to:
+  //  profiles/step_rules_ab.txt.  The lockstep passes call the header; k_batch_wave keeps its own text as well, for another reason, given there.)
   auto residuals = [&]() {
     double a1 = 0, a2 = 0, a3 = 0, a4 = 0, a5 = 0, a6 = 0, a7 = 0, a8 = 0, s1 = 0;
     for (int i = tid; i < m; i += kBB) {
       double ax = 0.0;
       for (int k = A.rowptr[i]; k < A.rowptr[i + 1]; k++) ax += A.val[k] * x[A.col[k]];
       const double pr = ax - z[i], ei = P.Einv[i], dyi = dy[i];
-      a1 = nmax(a1, fabs(ei * pr)); a2 = nmax(a2, fabs(ei * ax)); a3 = nmax(a3, fabs(ei * z[i]));
-      a4 = nmax(a4, fabs(pr)); a5 = nmax(a5, fabs(ax)); a6 = nmax(a6, fabs(z[i]));
-      a7 = nmax(a7, fabs(P.E[i] * dyi)); a8 = nmax(a8, fabs(dyi));
+      a1 = nanmax(a1, fabs(ei * pr)); a2 = nanmax(a2, fabs(ei * ax)); a3 = nanmax(a3, fabs(ei * z[i]));
+      a4 = nanmax(a4, fabs(pr)); a5 = nanmax(a5, fabs(ax)); a6 = nanmax(a6, fabs(z[i]));
+      a7 = nanmax(a7, fabs(P.E[i] * dyi)); a8 = nanmax(a8, fabs(dyi));
       s1 += u[i] * fmax(dyi, 0.0) + l[i] * fmin(dyi, 0.0);
     }
     { double g1[4] = {a1, a2, a3, a4}, g2[4] = {a5, a6, a7, a8}, g3[1] = {s1}, none[1] = {0.0};
@@ -567,9 +561,9 @@ __global__ __launch_bounds__(kBB, (DIRECT && kBB == 256 && EA <= 8) ? (SPEC ? SP
       double sp = 0.0, sa = 0.0;
       for (int k = B.rowptr[j]; k < B.rowptr[j + 1]; k++) { const int c = B.col[k]; if (c < n) sp += B.val[k] * x[c]; else sa += B.val[k] * y[c - n]; }
       const double px = sp - P.sigma * x[j], dr = px + q[j] + sa, di = P.Dinv[j];
-      b1 = nmax(b1, fabs(di * dr)); b2 = nmax(b2, fabs(di * px)); b3 = nmax(b3, fabs(di * sa));
-      b4 = nmax(b4, fabs(dr)); b5 = nmax(b5, fabs(px)); b6 = nmax(b6, fabs(sa));
-      b7 = nmax(b7, fabs(P.D[j] * dx[j])); b8 = nmax(b8, fabs(dx[j])); b9 = nmax(b9, fabs(q[j])); b10 = nmax(b10, fabs(di * q[j]));
+      b1 = nanmax(b1, fabs(di * dr)); b2 = nanmax(b2, fabs(di * px)); b3 = nanmax(b3, fabs(di * sa));
+      b4 = nanmax(b4, fabs(dr)); b5 = nanmax(b5, fabs(px)); b6 = nanmax(b6, fabs(sa));
+      b7 = nanmax(b7, fabs(P.D[j] * dx[j])); b8 = nanmax(b8, fabs(dx[j])); b9 = nanmax(b9, fabs(q[j])); b10 = nanmax(b10, fabs(di * q[j]));
       t1 += x[j] * px; t2 += q[j] * x[j]; t3 += q[j] * dx[j];
     }
     { double g1[4] = {b1, b2, b3, b4}, g2[4] = {b5, b6, b7, b8}, g3[2] = {b9, b10}, sm[2] = {t1, t2}, g4[1] = {t3}, none[1] = {0.0};
@@ -591,7 +585,7 @@ __global__ __launch_bounds__(kBB, (DIRECT && kBB == 256 && EA <= 8) ? (SPEC ? SP
     for (int j = tid; j < n; j += kBB) {
       double sa = 0.0;
       for (int k = B.rowptr[j]; k < B.rowptr[j + 1]; k++) { const int c = B.col[k]; if (c >= n) sa += B.val[k] * dy[c - n]; }
-      mu = nmax(mu, fabs(P.Dinv[j] * sa)); ms = nmax(ms, fabs(sa));
+      mu = nanmax(mu, fabs(P.Dinv[j] * sa)); ms = nanmax(ms, fabs(sa));
     }
     mu = red.max(mu); ms = red.max(ms);
   };
@@ -600,7 +594,7 @@ __global__ __launch_bounds__(kBB, (DIRECT && kBB == 256 && EA <= 8) ? (SPEC ? SP
       double sp = 0.0;
       for (int k = B.rowptr[j]; k < B.rowptr[j + 1]; k++) { const int c = B.col[k]; if (c < n) sp += B.val[k] * dx[c]; }
       sp -= P.sigma * dx[j];
-      mu = nmax(mu, fabs(P.Dinv[j] * sp)); ms = nmax(ms, fabs(sp));
+      mu = nanmax(mu, fabs(P.Dinv[j] * sp)); ms = nanmax(ms, fabs(sp));
     }
     mu = red.max(mu); ms = red.max(ms);
   };
@@ -610,7 +604,7 @@ __global__ __launch_bounds__(kBB, (DIRECT && kBB == 256 && EA <= 8) ? (SPEC ? SP
       double a = 0.0;
       for (int k = A.rowptr[i]; k < A.rowptr[i + 1]; k++) a += A.val[k] * dx[A.col[k]];
       if (unsc) a *= P.Einv[i];
-      if ((u[i] < OSQP_INFTY * 1e-4 && a > thr) || (l[i] > -OSQP_INFTY * 1e-4 && a < -thr)) viol += 1.0;
+      if (adx_violates(a, l[i], u[i], thr)) viol += 1.0;
     }
     viol = red.sum(viol);
     return viol == 0.0;
@@ -635,7 +629,7 @@ __global__ __launch_bounds__(kBB, (DIRECT && kBB == 256 && EA <= 8) ? (SPEC ? SP
       applyB(xs, t, [&](int j, double sK) {
         const double rhs = Kp[j], rr = rhs - sK, zz = Minv[j] * rr;
         r[j] = rr; zv[j] = zz; p[j] = zz;
-        rz_l += rr * zz; rn_l = nmax(rn_l, fabs(rr)); bn_l = nmax(bn_l, fabs(rhs));
+        rz_l += rr * zz; rn_l = nanmax(rn_l, fabs(rr)); bn_l = nanmax(bn_l, fabs(rhs));
       });
       double rz = rz_l, rn = rn_l;
       red.sum_max(rz, rn);
@@ -653,7 +647,7 @@ __global__ __launch_bounds__(kBB, (DIRECT && kBB == 256 && EA <= 8) ? (SPEC ? SP
           xs[j] += al * p[j];
           const double rr = r[j] - al * Kp[j], zz = Minv[j] * rr;
           r[j] = rr; zv[j] = zz;
-          rz2 += rr * zz; rn2 = nmax(rn2, fabs(rr));
+          rz2 += rr * zz; rn2 = nanmax(rn2, fabs(rr));
         }
         red.sum_max(rz2, rn2);
         const double be = rz2 / rz;
@@ -666,13 +660,10 @@ __global__ __launch_bounds__(kBB, (DIRECT && kBB == 256 && EA <= 8) ? (SPEC ? SP
     // ---- z~ = A xs; x, z, y update (_osqp.py:660-703) ----
     BT2_BEGIN();
     applyA(xs, [&](int i, double a) {
-      const double rh = rho[i], yi = y[i];
-      const double zr = P.alpha * a + (1.0 - P.alpha) * z[i];
-      const double zn = fmin(fmax(zr + yi / rh, l[i]), u[i]);
-      const double dyi = rh * (zr - zn);
-      y[i] = yi + dyi; dy[i] = dyi; z[i] = zn; zt[i] = a;
+      const StepRow s = step_row(P.alpha, a, rho[i], z[i], y[i], l[i], u[i]);
+      y[i] = s.y; dy[i] = s.dy; z[i] = s.z; zt[i] = a;
     });
-    for (int j = tid; j < n; j += kBB) { const double xo = x[j], xn = P.alpha * xs[j] + (1.0 - P.alpha) * xo; dx[j] = xn - xo; x[j] = xn; }
+    for (int j = tid; j < n; j += kBB) { const StepCol s = step_col(P.alpha, xs[j], x[j]); dx[j] = s.dx; x[j] = s.x; }
     __syncthreads();
     BT2_END(tk_upd);
 
@@ -710,9 +701,9 @@ __global__ __launch_bounds__(kBB, (DIRECT && kBB == 256 && EA <= 8) ? (SPEC ? SP
       for (int i = tid; i < m; i += kBB) {
         const double zi = z[i], yi = y[i];
         zt[i] = zi; dy[i] = yi;
-        const bool low = zi - l[i] < -yi, upp = !low && (u[i] - zi < yi);      // (a row active on both sides enters once, at its lower bound)
-        rho[i] = (low || upp) ? idel : 0.0;
-        z[i] = low ? l[i] : u[i];                                              // b_i of an active row (unused otherwise)
+        const RowActive act = polish_active(zi, l[i], u[i], yi);
+        rho[i] = (act.low || act.upp) ? idel : 0.0;
+        z[i] = act.low ? l[i] : u[i];                                              // b_i of an active row (unused otherwise)
         y[i] = 0.0;
       }
       __syncthreads();
@@ -740,13 +731,12 @@ __global__ __launch_bounds__(kBB, (DIRECT && kBB == 256 && EA <= 8) ? (SPEC ? SP
         __syncthreads();
         applyA(Minv, [&](int i, double adx) { if (rho[i] != 0.0) y[i] = t[i] + adx * idel; });
       }
-      applyA(x, [&](int i, double ax) { const double tmp = ax + y[i], zc = fmin(fmax(tmp, l[i]), u[i]); z[i] = zc; y[i] = tmp - zc; });
+      applyA(x, [&](int i, double ax) { const ConeRow c = normal_cone(ax + y[i], l[i], u[i]); z[i] = c.z; y[i] = c.y; });
       const double pri0 = prim_res, dua0 = dual_res;
       residuals();
       double pobj, ppri, pdua;
       term_info(tset, R, &pobj, &ppri, &pdua);
-      const bool ok = (ppri < pri0 && pdua < dua0) || (ppri < pri0 && dua0 < 1e-10) || (pdua < dua0 && pri0 < 1e-10);
-      if (ok) { obj = pobj; prim_res = ppri; dual_res = pdua; status_polish = 1; }
+      if (polish_accept(ppri, pdua, pri0, dua0)) { obj = pobj; prim_res = ppri; dual_res = pdua; status_polish = 1; }
       else {
         status_polish = -1;
         for (int j = tid; j < n; j += kBB) x[j] = p[j];
@@ -950,28 +940,27 @@ __global__ __launch_bounds__(64 * kBatchWaveW, 1) void k_batch_wave(BatchParams 
 #pragma unroll
     for (int s = 0; s < 2; s++) {
       const int j = jn[s];
-      q[s] = vn[s] ? P.c * P.D[j] * (P.q ? P.q[(size_t)b * n + j] : P.q0[j]) : 0.0;
-      x[s] = (vn[s] && P.warm) ? P.x[(size_t)b * n + j] * P.Dinv[j] : 0.0; dx[s] = 0.0; xs[s] = 0.0;
+      q[s] = vn[s] ? in_q(P.c, P.D[j], P.q ? P.q[(size_t)b * n + j] : P.q0[j]) : 0.0;
+      x[s] = (vn[s] && P.warm) ? in_x(P.x[(size_t)b * n + j], P.Dinv[j]) : 0.0; dx[s] = 0.0; xs[s] = 0.0;
     }
     double n_ineq_l = 0.0, mism = 0.0;
 #pragma unroll
     for (int s = 0; s < 4; s++) {
       const int i = rowm[s];
-      const double li = P.E[i] * fmax(P.l ? P.l[(size_t)b * m + i] : P.l0[i], -OSQP_INFTY), ui = P.E[i] * fmin(P.u ? P.u[(size_t)b * m + i] : P.u0[i], OSQP_INFTY);
+      const double li = in_l(P.E[i], P.l ? P.l[(size_t)b * m + i] : P.l0[i]), ui = in_u(P.E[i], P.u ? P.u[(size_t)b * m + i] : P.u0[i]);
       l[s] = vm[s] ? li : 0.0; u[s] = vm[s] ? ui : 0.0;
-      y[s] = (vm[s] && P.warm) ? P.y[(size_t)b * m + i] * P.Einv[i] * P.c : 0.0; dy[s] = 0.0; z[s] = 0.0;
-      int t_ = (li < -OSQP_INFTY * 1e-4 && ui > OSQP_INFTY * 1e-4) ? -1 : ((ui - li < 1e-4) ? 1 : 0);   // _osqp.py:505-518
-      if (!P.rho_is_vec) t_ = 0;
+      y[s] = (vm[s] && P.warm) ? in_y(P.y[(size_t)b * m + i], P.Einv[i], P.c) : 0.0; dy[s] = 0.0; z[s] = 0.0;
+      const int t_ = row_class(li, ui, P.rho_is_vec);
       ty[s] = t_;
       if (vm[s]) { n_ineq_l += (t_ == 0); if (t_ != P.sp_ctype[i]) mism = 1.0; }
     }
     const double n_ineq = wsum(n_ineq_l);
-    const double eqf = (n_ineq == 0.0) ? 1e3 : P.eq_factor_direct;                      // engine.cpp classify_constraints()
+    const double eqf = eq_weight(n_ineq == 0.0, P.eq_factor_direct);
     // V was built for ONE set of constraint classes: a problem whose own bounds give other classes (or another equality weight) is the banded kernel's
     mism = wsum(mism) + (eqf != P.sp_eqf ? 1.0 : 0.0);
     if (mism != 0.0) { if (L == 0) P.rec[(size_t)b * kBatchRec] = kBatchUnsolved; continue; }
     double rho_bar = P.rho0, rho_eq = 0.0, dk0 = 0.0, dk1 = 0.0;
-    auto rho_of = [&](int s) { return ty[s] == -1 ? 1e-6 : (ty[s] == 1 ? rho_eq : rho_bar); };             // _osqp.py:520-522 (three values: not kept per row)
+    auto rho_of = [&](int s) { return row_rho(ty[s], rho_bar, rho_eq); };             // (three values: not kept per row)
     auto set_rho = [&](double rb) {
       rho_eq = eqf * rb;
       const double dl = rb - P.sp_rho_ref;
@@ -986,6 +975,9 @@ __global__ __launch_bounds__(64 * kBatchWaveW, 1) void k_batch_wave(BatchParams 
       for (int s = 0; s < 4; s++) if (vm[s]) z[s] = P.zs[(size_t)b * m + rowm[s]];
     }
     TermRes R = {};
+    // (step_rules.h res_row_a / res_row_b / res_store, in this kernel's own text -- the same expressions in the same order, to be kept in step: through
+    //  the header the two products of the support term reach the compiler in the other order and the other one is contracted into the FMA, another
+    //  rounding of pinf_lhs: profiles/step_rules_ab.txt)
     auto residuals = [&]() {
       double a1 = 0, a2 = 0, a3 = 0, a4 = 0, a5 = 0, a6 = 0, a7 = 0, a8 = 0, s1 = 0;
       stage_n(x);
@@ -995,9 +987,9 @@ __global__ __launch_bounds__(64 * kBatchWaveW, 1) void k_batch_wave(BatchParams 
       for (int s = 0; s < 4; s++) if (vm[s]) {
         const int i = rowm[s];
         const double pr = ax[s] - z[s], ei = P.Einv[i], dyi = dy[s];
-        a1 = nmax(a1, fabs(ei * pr)); a2 = nmax(a2, fabs(ei * ax[s])); a3 = nmax(a3, fabs(ei * z[s]));
-        a4 = nmax(a4, fabs(pr)); a5 = nmax(a5, fabs(ax[s])); a6 = nmax(a6, fabs(z[s]));
-        a7 = nmax(a7, fabs(P.E[i] * dyi)); a8 = nmax(a8, fabs(dyi));
+        a1 = nanmax(a1, fabs(ei * pr)); a2 = nanmax(a2, fabs(ei * ax[s])); a3 = nanmax(a3, fabs(ei * z[s]));
+        a4 = nanmax(a4, fabs(pr)); a5 = nanmax(a5, fabs(ax[s])); a6 = nanmax(a6, fabs(z[s]));
+        a7 = nanmax(a7, fabs(P.E[i] * dyi)); a8 = nanmax(a8, fabs(dyi));
         s1 += u[s] * fmax(dyi, 0.0) + l[s] * fmin(dyi, 0.0);
       }
       R.pri_u = wmax(a1); R.ax_u = wmax(a2); R.z_u = wmax(a3); R.pri_s = wmax(a4); R.ax_s = wmax(a5); R.z_s = wmax(a6); R.dy_u = wmax(a7); R.dy_s = wmax(a8); R.pinf_lhs = wsum(s1);
@@ -1008,9 +1000,9 @@ __global__ __launch_bounds__(64 * kBatchWaveW, 1) void k_batch_wave(BatchParams 
       for (int s = 0; s < 2; s++) if (vn[s]) {
         const int j = s * 64 + L;
         const double px = sp[s] - P.sigma * x[s], dr = px + q[s] + sa[s], di = P.Dinv[j];
-        b1 = nmax(b1, fabs(di * dr)); b2 = nmax(b2, fabs(di * px)); b3 = nmax(b3, fabs(di * sa[s]));
-        b4 = nmax(b4, fabs(dr)); b5 = nmax(b5, fabs(px)); b6 = nmax(b6, fabs(sa[s]));
-        b7 = nmax(b7, fabs(P.D[j] * dx[s])); b8 = nmax(b8, fabs(dx[s])); b9 = nmax(b9, fabs(q[s])); b10 = nmax(b10, fabs(di * q[s]));
+        b1 = nanmax(b1, fabs(di * dr)); b2 = nanmax(b2, fabs(di * px)); b3 = nanmax(b3, fabs(di * sa[s]));
+        b4 = nanmax(b4, fabs(dr)); b5 = nanmax(b5, fabs(px)); b6 = nanmax(b6, fabs(sa[s]));
+        b7 = nanmax(b7, fabs(P.D[j] * dx[s])); b8 = nanmax(b8, fabs(dx[s])); b9 = nanmax(b9, fabs(q[s])); b10 = nanmax(b10, fabs(di * q[s]));
         t1 += x[s] * px; t2 += q[s] * x[s]; t3 += q[s] * dx[s];
       }
       R.dua_u = wmax(b1); R.px_u = wmax(b2); R.aty_u = wmax(b3); R.dua_s = wmax(b4); R.px_s = wmax(b5); R.aty_s = wmax(b6); R.dxn_u = wmax(b7); R.dxn_s = wmax(b8);
@@ -1022,14 +1014,14 @@ __global__ __launch_bounds__(64 * kBatchWaveW, 1) void k_batch_wave(BatchParams 
       double sa[2];
       stage_m(dy); mulT(sa);
 #pragma unroll
-      for (int s = 0; s < 2; s++) if (vn[s]) { mu = nmax(mu, fabs(P.Dinv[s * 64 + L] * sa[s])); ms = nmax(ms, fabs(sa[s])); }
+      for (int s = 0; s < 2; s++) if (vn[s]) { mu = nanmax(mu, fabs(P.Dinv[s * 64 + L] * sa[s])); ms = nanmax(ms, fabs(sa[s])); }
       mu = wmax(mu); ms = wmax(ms);
     };
     auto pdx_stage2 = [&](double &mu, double &ms) {                                      // P dx    (is_dual_infeasible :846-853)
       double sp[2];
       stage_n(dx); mulP(sp);
 #pragma unroll
-      for (int s = 0; s < 2; s++) if (vn[s]) { const double v = sp[s] - P.sigma * dx[s]; mu = nmax(mu, fabs(P.Dinv[s * 64 + L] * v)); ms = nmax(ms, fabs(v)); }
+      for (int s = 0; s < 2; s++) if (vn[s]) { const double v = sp[s] - P.sigma * dx[s]; mu = nanmax(mu, fabs(P.Dinv[s * 64 + L] * v)); ms = nanmax(ms, fabs(v)); }
       mu = wmax(mu); ms = wmax(ms);
     };
     auto adx_stage2 = [&](double thr) {                                                  // A dx    (:855-872; dx is staged)
@@ -1039,7 +1031,7 @@ __global__ __launch_bounds__(64 * kBatchWaveW, 1) void k_batch_wave(BatchParams 
       for (int s = 0; s < 4; s++) if (vm[s]) {
         double a = adx[s];
         if (unsc) a *= P.Einv[rowm[s]];
-        if ((u[s] < OSQP_INFTY * 1e-4 && a > thr) || (l[s] > -OSQP_INFTY * 1e-4 && a < -thr)) viol += 1.0;
+        if (adx_violates(a, l[s], u[s], thr)) viol += 1.0;
       }
       viol = wsum(viol);
       return viol == 0.0;
@@ -1071,14 +1063,11 @@ __global__ __launch_bounds__(64 * kBatchWaveW, 1) void k_batch_wave(BatchParams 
       mulA(zt);
 #pragma unroll
       for (int s = 0; s < 4; s++) {
-        const double rh = rho_of(s), yi = y[s];
-        const double zr = P.alpha * zt[s] + (1.0 - P.alpha) * z[s];
-        const double zn = fmin(fmax(zr + yi / rh, l[s]), u[s]);
-        const double dyi = rh * (zr - zn);
-        y[s] = yi + dyi; dy[s] = dyi; z[s] = zn;
+        const StepRow r = step_row(P.alpha, zt[s], rho_of(s), z[s], y[s], l[s], u[s]);
+        y[s] = r.y; dy[s] = r.dy; z[s] = r.z;
       }
 #pragma unroll
-      for (int s = 0; s < 2; s++) { const double xo = x[s], xn = P.alpha * xs[s] + (1.0 - P.alpha) * xo; dx[s] = xn - xo; x[s] = xn; }
+      for (int s = 0; s < 2; s++) { const StepCol c = step_col(P.alpha, xs[s], x[s]); dx[s] = c.dx; x[s] = c.x; }
       WT_MARK(c3); WT_ADD(tkA, c3 - c2);
       const bool at_check = (P.check > 0 && iter % P.check == 0) || iter >= P.max_iter;
       const bool at_rho = P.rho_interval > 0 && iter % P.rho_interval == 0;
@@ -1243,7 +1232,7 @@ __global__ __launch_bounds__(256) void k_batch_adjoint(AdjointParams P) {
     else { Bv[P.Pm1[k]] = v; Bv[P.Pm2[k]] = v; }
   }
   double gmax_l = 0.0;
-  for (int j = tid; j < n; j += kBB) { x[j] = P.x[(size_t)b * n + j]; const double g = -P.dx[(size_t)b * n + j]; gx[j] = g; rx[j] = 0.0; gmax_l = nmax(gmax_l, fabs(g)); }
+  for (int j = tid; j < n; j += kBB) { x[j] = P.x[(size_t)b * n + j]; const double g = -P.dx[(size_t)b * n + j]; gx[j] = g; rx[j] = 0.0; gmax_l = nanmax(gmax_l, fabs(g)); }
   for (int i = tid; i < m; i += kBB) y[i] = P.y[(size_t)b * m + i];
   __syncthreads();
   // ---- z = A x, the active set, the right-hand side of the active rows ----
@@ -1252,13 +1241,12 @@ __global__ __launch_bounds__(256) void k_batch_adjoint(AdjointParams P) {
   for (int i = tid; i < m; i += kBB) {
     double z = 0.0;
     for (int k = Arp[i]; k < Arp[i + 1]; k++) z += Av[k] * x[Ac[k]];
-    const double li = fmax(P.l ? P.l[(size_t)b * m + i] : P.l0[i], -OSQP_INFTY), ui = fmin(P.u ? P.u[(size_t)b * m + i] : P.u0[i], OSQP_INFTY), yi = y[i];
-    bool low = z - li < -yi, upp = !low && (ui - z < yi);
-    if (li == ui) { low = yi < 0.0; upp = !low; }
-    const bool act = low || upp;
+    const double li = clamp_lower(P.l ? P.l[(size_t)b * m + i] : P.l0[i]), ui = clamp_upper(P.u ? P.u[(size_t)b * m + i] : P.u0[i]), yi = y[i];
+    const RowActive ra_ = adjoint_active(z, li, ui, yi);
+    const bool low = ra_.low, upp = ra_.upp, act = low || upp;
     const double g = act ? -(P.dy ? P.dy[(size_t)b * m + i] : 0.0) : 0.0;
     w[i] = act ? idel : 0.0; sd[i] = low ? -1.0 : (upp ? 1.0 : 0.0); ga[i] = g; ra[i] = 0.0;
-    nact_l += act ? 1.0 : 0.0; gmax_l = nmax(gmax_l, fabs(g));
+    nact_l += act ? 1.0 : 0.0; gmax_l = nanmax(gmax_l, fabs(g));
   }
   __syncthreads();
   const double nact = red.sum(nact_l), gmax = red.max(gmax_l);
@@ -1310,13 +1298,13 @@ __global__ __launch_bounds__(256) void k_batch_adjoint(AdjointParams P) {
   for (int j = tid; j < n; j += kBB) {
     double a = 0.0;
     for (int k = Brp[j]; k < Brp[j + 1]; k++) { const int c = Bc[k]; a += Bv[k] * (c < n ? rx[c] : ra[c - n]); }
-    rmax_l = nmax(rmax_l, fabs(gx[j] - a));
+    rmax_l = nanmax(rmax_l, fabs(gx[j] - a));
   }
   for (int i = tid; i < m; i += kBB) {
     if (w[i] != 0.0) {
       double a = 0.0;
       for (int e = Arp[i]; e < Arp[i + 1]; e++) a += Av[e] * rx[Ac[e]];
-      rmax_l = nmax(rmax_l, fabs(ga[i] - a));
+      rmax_l = nanmax(rmax_l, fabs(ga[i] - a));
     }
   }
   const double rmax = red.max(rmax_l);

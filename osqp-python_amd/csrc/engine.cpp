@@ -274,15 +274,11 @@ void Engine::classify_constraints(const std::vector<double> &ls, const std::vect
   ctype_.resize(m);
   int n_ineq = 0;
   for (int i = 0; i < m; i++) {
-    int t;
-    if (ls[i] < -OSQP_INFTY * kMinScaling && us[i] > OSQP_INFTY * kMinScaling) t = -1;
-    else if (us[i] - ls[i] < kRhoTol) t = 1;
-    else t = 0;
-    if (!settings.rho_is_vec) t = 0;
+    const int t = row_class(ls[i], us[i], settings.rho_is_vec);
     ctype_[i] = t;
     n_ineq += (t == 0);
   }
-  d_.rho_eq_factor = (n_ineq == 0) ? 1e3 : mixed_eq_factor();
+  d_.rho_eq_factor = eq_weight(n_ineq == 0, mixed_eq_factor());
   d_.eq_from_cnt = 0;                                   // host classification: k_set_rho takes the factor from rho_eq_factor
   if (before != ctype_) for (int k = 0; k < DevWb::kCache; k++) d_.wb.cache_rho[k] = -1.0;      // other classes, another rho vector under the same rho_bar: cached Woodbury inverses are dead
 }
@@ -319,7 +315,7 @@ void Engine::ensure_host_vectors() {
 // iterations, like the oracle, with 1e3).  osqp_hip_set_rho_eq_factor() overrides both.
 double Engine::mixed_eq_factor() const {
   constexpr int kSmallEqN = 256;
-  return (!eq_factor_set_ && !eq_factor_env_ && n <= kSmallEqN) ? 1e3 : eq_factor_mixed_;
+  return (!eq_factor_set_ && !eq_factor_env_ && n <= kSmallEqN) ? kRowEqWeight : eq_factor_mixed_;
 }
 
 int Engine::set_rho_eq_factor(double f) {
@@ -451,9 +447,7 @@ void Engine::run_slots(int begin_target, int pairs, int cap) {
 }
 
 double Engine::rho_estimate(const double *res) const {                                   // _osqp.py:880-908 (scaled quantities)
-  double pri = res[R_PRI_S] / (std::max(res[R_AX_S], res[R_Z_S]) + 1e-10);
-  double dua = res[R_DUA_S] / (std::max(std::max(res[R_ATY_S], res[R_PX_S]), res[R_QN_S]) + 1e-10);
-  return clamp_rho(rho_bar_ * std::sqrt(pri / (dua + 1e-10)));
+  return pol_rho_estimate(rho_bar_, res);
 }
 
 // _osqp.py:998-1077.  Returns 1 when a terminal status was set.
@@ -1072,7 +1066,8 @@ void Engine::polish() {
   // active set (:1719-1720) on the scaled iterates; equality rows are always active
   std::vector<double> lp(m), up(m);
   for (int i = 0; i < m; i++) {
-    const bool low = (z[i] - ls0[i] < -y[i]) || ctype_[i] == 1, upp = !low && (us0[i] - z[i] < y[i]);
+    const RowActive act = polish_active(z[i], ls0[i], us0[i], y[i]);
+    const bool low = act.low || ctype_[i] == 1, upp = !low && act.upp;
     if (low) { lp[i] = up[i] = ls0[i]; z[i] = ls0[i]; }
     else if (upp) { lp[i] = up[i] = us0[i]; z[i] = us0[i]; }
     else { lp[i] = -OSQP_INFTY; up[i] = OSQP_INFTY; y[i] = 0.0; }
@@ -1100,8 +1095,7 @@ void Engine::polish() {
   const double pol_pri = (m == 0) ? 0.0 : (unsc ? res[R_PRI_U] : res[R_PRI_S]);
   const double pol_dua = unsc ? cinv_ * res[R_DUA_U] : res[R_DUA_S];
   const double pol_obj = (0.5 * res[R_XPX] + res[R_QX]) * (settings.scaling ? cinv_ : 1.0);
-  const bool ok = (pol_pri < info0.prim_res && pol_dua < info0.dual_res) || (pol_pri < info0.prim_res && info0.dual_res < 1e-10) ||
-                  (pol_dua < info0.dual_res && info0.prim_res < 1e-10);                 // :1786-1793
+  const bool ok = polish_accept(pol_pri, pol_dua, info0.prim_res, info0.dual_res);
   recurrence_restore_rho(keep);
   if (ok) {
     info.obj_val = pol_obj; info.prim_res = pol_pri; info.dual_res = pol_dua; info.status_polish = 1;       // :1797-1807

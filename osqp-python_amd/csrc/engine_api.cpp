@@ -369,12 +369,7 @@ bool Engine::prepare_batch_spectral(double rho_ref, double eqf, bool allow_build
   if (n > N || m == 0 || !be::device_assembly() || reordered_) { bs_.ok = false; return false; }
   // the reference classes: those of the solver's own bounds, classified as the kernel classifies a problem's (batch_hip.hip, _osqp.py:505-518)
   std::vector<int> ct(m);
-  for (int i = 0; i < m; i++) {
-    const double li = E_[i] * std::max(l0_[i], -OSQP_INFTY), ui = E_[i] * std::min(u0_[i], OSQP_INFTY);
-    int ty = (li < -OSQP_INFTY * 1e-4 && ui > OSQP_INFTY * 1e-4) ? -1 : ((ui - li < 1e-4) ? 1 : 0);
-    if (!settings.rho_is_vec) ty = 0;
-    ct[i] = ty;
-  }
+  for (int i = 0; i < m; i++) ct[i] = row_class(in_l(E_[i], l0_[i]), in_u(E_[i], u0_[i]), settings.rho_is_vec);
   if ((bs_.ok || bs_.failed) && bs_.mat_epoch == mat_epoch_ && bs_.eqf == eqf && bs_.sigma == settings.sigma && bs_.rho_is_vec == settings.rho_is_vec && bs_.ctype == ct) return bs_.ok;
   if (!allow_build) return false;                          // (what exists was built for other matrices / classes; this caller does not pay for a new one)
   const double rref = bs_.ok ? bs_.rho_ref : rho_ref;       // (any reference works: K(rho) = K_ref + (rho - rho_ref) M1; the first call's rho stays)
@@ -398,7 +393,7 @@ bool Engine::prepare_batch_spectral(double rho_ref, double eqf, bool allow_build
       const int ty = ct[i];
       for (auto &a : rows[i]) for (auto &b : rows[i]) {
         const double v = a.second * b.second;
-        if (ty == -1) K[(size_t)a.first * n + b.first] += 1e-6 * v;                 // loose rows keep rho_i = 1e-6 whatever rho_bar is (_osqp.py:520)
+        if (ty == -1) K[(size_t)a.first * n + b.first] += kRowRhoLoose * v;         // loose rows keep their rho whatever rho_bar is (_osqp.py:520)
         else M1[(size_t)a.first * n + b.first] += (ty == 1 ? eqf : 1.0) * v;
       }
     }
@@ -616,19 +611,15 @@ void Engine::fill_batch_params(BatchParams &p, int nbatch, int warm) {
 
 void Engine::attach_batch_direct(BatchParams &p, bool spectral) {
   if (!bd_.ok) return;
-  p.eq_factor_direct = eq_factor_set_ ? eq_factor_mixed_ : 1e3;
+  p.eq_factor_direct = eq_factor_set_ ? eq_factor_mixed_ : kRowEqWeight;
   // the spectral form of the same solve, where it applies (never with polish: that factorises another matrix in the band) -- and where the caller is a
   // batch that pays for the host-side decomposition (dense Cholesky + Jacobi sweeps: tens to hundreds of ms for a kernel that runs about one): a
   // single osqp_solve of a small QP and small batches keep the banded kernel unless a batch has prepared the form for this key before
   if (pol_.batch_variant == 0 && !settings.polishing && n <= kBatchSpecN) {
     if (raw_stale_) ensure_host_vectors();             // (the solver's own bounds define the reference classes)
     int n_ineq = 0;
-    for (int i = 0; i < m && settings.rho_is_vec; i++) {
-      const double li = E_[i] * std::max(l0_[i], -OSQP_INFTY), ui = E_[i] * std::min(u0_[i], OSQP_INFTY);
-      n_ineq += !((li < -OSQP_INFTY * 1e-4 && ui > OSQP_INFTY * 1e-4) || (ui - li < 1e-4));
-    }
-    if (!settings.rho_is_vec) n_ineq = m;
-    if (prepare_batch_spectral(p.rho0, n_ineq == 0 ? 1e3 : p.eq_factor_direct, spectral)) {
+    for (int i = 0; i < m; i++) n_ineq += row_class(in_l(E_[i], l0_[i]), in_u(E_[i], u0_[i]), settings.rho_is_vec) == 0;
+    if (prepare_batch_spectral(p.rho0, eq_weight(n_ineq == 0, p.eq_factor_direct), spectral)) {
       p.sp_V = bs_.V; p.sp_lam = bs_.lam; p.sp_ctype = bs_.d_ctype; p.sp_rho_ref = bs_.rho_ref; p.sp_eqf = bs_.eqf;
       prepare_batch_k0(p.rho0);
       if (bs_.k0_ok) { p.sp_K0 = bs_.K0; p.sp_K0_rho = bs_.k0_rho; }
@@ -702,8 +693,7 @@ int Engine::solve_small_direct(double t0) {
       double xpx = 0, sup = 0, nax = 0, nz = 0, npx = 0, naty = 0, nq = 0;
       for (int j = 0; j < n; j++) { xpx += x[j] * px[j]; npx = std::max(npx, std::fabs(px[j])); naty = std::max(naty, std::fabs(aty[j])); nq = std::max(nq, std::fabs(q0_[j])); }
       for (int i = 0; i < m; i++) {
-        if (y[i] > 0 && u0_[i] < OSQP_INFTY * kMinScaling) sup += u0_[i] * y[i];
-        else if (y[i] < 0 && l0_[i] > -OSQP_INFTY * kMinScaling) sup += l0_[i] * y[i];
+        sup += support_finite(l0_[i], u0_[i], y[i]);
         nax = std::max(nax, std::fabs(ax[i])); nz = std::max(nz, std::fabs(std::min(std::max(ax[i], l0_[i]), u0_[i])));
       }
       info.dual_obj_val = -0.5 * xpx - sup;

@@ -3,6 +3,7 @@
 // LinSysSolver slot, batch and small-problem paths, statistics).  Anonymous namespace: each unit has its own copy.
 #pragma once
 #include "engine.hpp"
+#include "step_rules.h"
 
 #include <algorithm>
 #include <chrono>
@@ -27,6 +28,7 @@ const BatchEnv &batch_env();
 namespace {
 constexpr double kRhoMin = 1e-6, kRhoMax = 1e6, kRhoTol = 1e-4;   // _osqp.py:25-28 (RHO_EQ_OVER_RHO_INEQ = 1e3 is applied in the set_rho kernel)
 constexpr double kMinScaling = 1e-4, kMaxScaling = 1e4;                                 // _osqp.py:44-45
+static_assert(kMinScaling == kRowLooseFrac && kRhoTol == kRowEqTol && kRhoMin == kRowRhoLoose, "step_rules.h states the row rules with these values");
 const double kNaN = std::numeric_limits<double>::quiet_NaN();
 
 inline double now_s() {

@@ -22,6 +22,7 @@
 #include "../../include/osqp_hip.h"
 #include "backend.h"
 #include "policy.h"
+#include "step_rules.h"
 
 namespace osqp_hip {
 namespace be {
@@ -85,7 +86,6 @@ inline hipStream_t st(Dev &d) { return static_cast<hipStream_t>(d.stream); }
 #endif
 template <class T> using gp = OSQP_GLOBAL_AS T *;
 template <class T> __device__ __forceinline__ gp<T> gptr(T *p) { return (gp<T>)p; }
-__device__ __forceinline__ double nanmax(double r, double a) { return (a > r || a != a) ? a : r; }
 // Wave64 reductions with DPP moves (VALU rate).  HIP's __shfl_* compile to ds_bpermute_b32 -- an LDS round trip of ~100+ cycles
 // per 32-bit half and step: the three block reductions of a PCG kernel cost ~1 us each that way (tools/ktrace.py: 1.07 us in the
 // late hook of k_k2f, 0.9 us in k_k1f's exit).  dpp<CTRL, ROWS>(v): v of the DPP source lane, 0.0 where there is none / the row is

@@ -54,10 +54,6 @@ struct LsK { LockstepParams P; LsWs w; };
 
 __device__ __forceinline__ int ls_lane() { return threadIdx.x & 63; }
 __device__ __forceinline__ int ls_wave() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
-__device__ __forceinline__ int ls_ctype(double li, double ui, int rho_is_vec) {          // _osqp.py:505-518
-  const int ty = (li < -OSQP_INFTY * 1e-4 && ui > OSQP_INFTY * 1e-4) ? -1 : ((ui - li < 1e-4) ? 1 : 0);
-  return rho_is_vec ? ty : 0;
-}
 
 // the four waves' values of KM max-type and KS sum-type statistics, combined in wave order, to the workgroup's partials
 template <int KM, int KS>
@@ -189,7 +185,8 @@ __global__ __launch_bounds__(256) void k_ls_kp(LsK k) {
 // the n side of k_batch_admm's residuals(), with the second stage of both infeasibility tests (A' dy, P dx) from the same pass
 struct FResN {
   const LsWs &w; const double *D, *Dinv; double sigma; int n, lane;
-  double vm[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, vs[3] = {0, 0, 0};
+  ResRowsB rb = {};                                                           // (step_rules.h: named fields)
+  double atdy_u = 0, atdy_s = 0, pdx_u = 0, pdx_s = 0;                        // second stages
   __device__ __forceinline__ void begin(int) {}
   __device__ __forceinline__ void load(int c, double (&g)[2]) const {
     if (c < n) { g[0] = w.x[IX(c)]; g[1] = w.dx[IX(c)]; } else { g[0] = w.y[IX(c - n)]; g[1] = w.dy[IX(c - n)]; }
@@ -199,20 +196,19 @@ struct FResN {
     a[0] += pn ? p0 : 0.0; a[2] += pn ? p1 : 0.0; a[1] += pn ? 0.0 : p0; a[3] += pn ? 0.0 : p1;
   }
   __device__ __forceinline__ void row(int j, const double (&a)[4]) {
-    const double xj = w.x[IX(j)], qj = w.q[IX(j)], dxj = w.dx[IX(j)], di = Dinv[j];
-    const double px = a[0] - sigma * xj, sa = a[1], dr = px + qj + sa, pdx = a[2] - sigma * dxj, atdy = a[3];
-    vm[0] = nanmax(vm[0], fabs(di * dr)); vm[1] = nanmax(vm[1], fabs(di * px)); vm[2] = nanmax(vm[2], fabs(di * sa));
-    vm[3] = nanmax(vm[3], fabs(dr)); vm[4] = nanmax(vm[4], fabs(px)); vm[5] = nanmax(vm[5], fabs(sa));
-    vm[6] = nanmax(vm[6], fabs(D[j] * dxj)); vm[7] = nanmax(vm[7], fabs(dxj)); vm[8] = nanmax(vm[8], fabs(qj)); vm[9] = nanmax(vm[9], fabs(di * qj));
-    vm[10] = nanmax(vm[10], fabs(di * atdy)); vm[11] = nanmax(vm[11], fabs(atdy)); vm[12] = nanmax(vm[12], fabs(di * pdx)); vm[13] = nanmax(vm[13], fabs(pdx));
-    vs[0] += xj * px; vs[1] += qj * xj; vs[2] += qj * dxj;
+    const double dxj = w.dx[IX(j)], di = Dinv[j];
+    res_row_b(rb, a[0], a[1], sigma, w.x[IX(j)], w.q[IX(j)], dxj, D[j], di);
+    const double pdx = a[2] - sigma * dxj, atdy = a[3];
+    atdy_u = nanmax(atdy_u, fabs(di * atdy)); atdy_s = nanmax(atdy_s, fabs(atdy)); pdx_u = nanmax(pdx_u, fabs(di * pdx)); pdx_s = nanmax(pdx_s, fabs(pdx));
   }
 };
 __global__ __launch_bounds__(256) void k_ls_resn(LsK k) {
   __shared__ double lds[17 * 256];
   FResN f{k.w, k.P.D, k.P.Dinv, k.P.sigma, k.P.n, ls_lane()};
   ls_rows<2, 4>(k.P.B, f);
-  ls_put<14, 3>(k.w.part, PS_N0, f.vm, f.vs, lds);
+  const ResRowsB &b = f.rb;                                                   // (the slot order of PS_N0)
+  const double vm[14] = {b.dua_u, b.px_u, b.aty_u, b.dua_s, b.px_s, b.aty_s, b.dxn_u, b.dxn_s, b.qn_s, b.qn_u, f.atdy_u, f.atdy_s, f.pdx_u, f.pdx_s}, vs[3] = {b.xpx, b.qx, b.qdx};
+  ls_put<14, 3>(k.w.part, PS_N0, vm, vs, lds);
 }
 
 // z = z~ = A x at the start;  t = rho z - y,  t2 = rho z~  (what the next k_ls_rhs gathers)
@@ -254,12 +250,10 @@ struct FUpd {
   __device__ __forceinline__ void fma(int, double v, const double (&g)[1], double (&a)[1]) const { a[0] += v * g[0]; }
   __device__ __forceinline__ void row(int i, const double (&acc)[1]) const {
     if (!live) return;
-    const double a = acc[0], rh = w.rho[IX(i)], yi = w.y[IX(i)];
-    const double zr = alpha * a + (1.0 - alpha) * w.z[IX(i)];
-    const double zn = fmin(fmax(zr + yi / rh, w.l[IX(i)]), w.u[IX(i)]);
-    const double dyi = rh * (zr - zn), yn = yi + dyi;
-    w.y[IX(i)] = yn; w.dy[IX(i)] = dyi; w.z[IX(i)] = zn; w.zt[IX(i)] = a;
-    w.t[IX(i)] = rh * zn - yn; w.t2[IX(i)] = rh * a;
+    const double a = acc[0], rh = w.rho[IX(i)];
+    const StepRow s = step_row(alpha, a, rh, w.z[IX(i)], w.y[IX(i)], w.l[IX(i)], w.u[IX(i)]);
+    w.y[IX(i)] = s.y; w.dy[IX(i)] = s.dy; w.z[IX(i)] = s.z; w.zt[IX(i)] = a;
+    w.t[IX(i)] = rh * s.z - s.y; w.t2[IX(i)] = rh * a;
   }
 };
 __global__ __launch_bounds__(256) void k_ls_upd(LsK k) {
@@ -268,8 +262,8 @@ __global__ __launch_bounds__(256) void k_ls_upd(LsK k) {
   if (!live) return;
   const size_t tot = (size_t)k.P.n * 64;
   for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < tot; e += (size_t)gridDim.x * 256) {
-    const double xo = k.w.x[e], xn = k.P.alpha * k.w.xs[e] + (1.0 - k.P.alpha) * xo;
-    k.w.dx[e] = xn - xo; k.w.x[e] = xn;
+    const StepCol c = step_col(k.P.alpha, k.w.xs[e], k.w.x[e]);
+    k.w.dx[e] = c.dx; k.w.x[e] = c.x;
   }
 }
 
@@ -277,26 +271,26 @@ __global__ __launch_bounds__(256) void k_ls_upd(LsK k) {
 // those with a finite lower one: "no row violates" is two comparisons of these with the threshold, which only the fold knows)
 struct FResM {
   const LsWs &w; const double *E, *Einv; int lane, unsc;
-  double vm[10] = {0, 0, 0, 0, 0, 0, 0, 0, -INFINITY, -INFINITY}, vs[1] = {0};
+  ResRowsA ra = {};                                                           // (step_rules.h: named fields)
+  double adx_hi = -INFINITY, adx_lo = -INFINITY;                              // second stage
   __device__ __forceinline__ void begin(int) {}
   __device__ __forceinline__ void load(int c, double (&g)[2]) const { g[0] = w.x[IX(c)]; g[1] = w.dx[IX(c)]; }
   __device__ __forceinline__ void fma(int, double v, const double (&g)[2], double (&a)[2]) const { a[0] += v * g[0]; a[1] += v * g[1]; }
   __device__ __forceinline__ void row(int i, const double (&a)[2]) {
-    const double ax = a[0], zi = w.z[IX(i)], pr = ax - zi, ei = Einv[i], dyi = w.dy[IX(i)], li = w.l[IX(i)], ui = w.u[IX(i)];
-    vm[0] = nanmax(vm[0], fabs(ei * pr)); vm[1] = nanmax(vm[1], fabs(ei * ax)); vm[2] = nanmax(vm[2], fabs(ei * zi));
-    vm[3] = nanmax(vm[3], fabs(pr)); vm[4] = nanmax(vm[4], fabs(ax)); vm[5] = nanmax(vm[5], fabs(zi));
-    vm[6] = nanmax(vm[6], fabs(E[i] * dyi)); vm[7] = nanmax(vm[7], fabs(dyi));
+    const double ei = Einv[i], li = w.l[IX(i)], ui = w.u[IX(i)];
+    res_row_a(ra, a[0], w.z[IX(i)], w.dy[IX(i)], li, ui, E[i], ei);
     const double adx = unsc ? ei * a[1] : a[1];
-    if (ui < OSQP_INFTY * 1e-4) vm[8] = nanmax(vm[8], adx);
-    if (li > -OSQP_INFTY * 1e-4) vm[9] = nanmax(vm[9], -adx);
-    vs[0] += ui * fmax(dyi, 0.0) + li * fmin(dyi, 0.0);
+    if (upper_is_finite(ui)) adx_hi = nanmax(adx_hi, adx);
+    if (lower_is_finite(li)) adx_lo = nanmax(adx_lo, -adx);
   }
 };
 __global__ __launch_bounds__(256) void k_ls_resm(LsK k) {
   __shared__ double lds[11 * 256];
   FResM f{k.w, k.P.E, k.P.Einv, ls_lane(), k.P.unscaled};
   ls_rows<2, 2>(k.P.A, f);
-  ls_put<10, 1>(k.w.part, PS_M0, f.vm, f.vs, lds);
+  const ResRowsA &a = f.ra;                                                   // (the slot order of PS_M0)
+  const double vm[10] = {a.pri_u, a.ax_u, a.z_u, a.pri_s, a.ax_s, a.z_s, a.dy_u, a.dy_s, f.adx_hi, f.adx_lo}, vs[1] = {a.pinf_lhs};
+  ls_put<10, 1>(k.w.part, PS_M0, vm, vs, lds);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- elementwise kernels
@@ -308,8 +302,7 @@ __global__ __launch_bounds__(256) void k_ls_setrho(LsK k) {
   const double rb = k.w.sc[SC_RHOBAR * W + lane], eqf = k.w.sc[SC_EQF * W + lane];
   const size_t tot = (size_t)k.P.m * 64;
   for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < tot; e += (size_t)gridDim.x * 256) {
-    const int ty = ls_ctype(k.w.l[e], k.w.u[e], k.P.rho_is_vec);
-    const double rh = ty == -1 ? 1e-6 : (ty == 1 ? eqf * rb : rb);
+    const double rh = row_rho(row_class(k.w.l[e], k.w.u[e], k.P.rho_is_vec), rb, eqf * rb);
     k.w.rho[e] = rh; k.w.t[e] = rh * k.w.z[e] - k.w.y[e]; k.w.t2[e] = rh * k.w.zt[e];
   }
 }
@@ -393,21 +386,21 @@ __global__ __launch_bounds__(256) void k_ls_decide(LsK k, int iter, int at_check
   __shared__ double lds[256];
   const LockstepParams &P = k.P;
   const int lane = ls_lane(), G = k.w.G;
-  double M_[11], N_[17];
-#pragma unroll
-  for (int s = 0; s < 10; s++) M_[s] = ls_fold<true>(k.w.part, G, PS_M0 + s, lds);
-  M_[10] = ls_fold<false>(k.w.part, G, PS_M0 + 10, lds);
-#pragma unroll
-  for (int s = 0; s < 14; s++) N_[s] = ls_fold<true>(k.w.part, G, PS_N0 + s, lds);
-#pragma unroll
-  for (int s = 14; s < 17; s++) N_[s] = ls_fold<false>(k.w.part, G, PS_N0 + s, lds);
+  // the slots as k_ls_resm / k_ls_resn put them (all 64 lanes of every wave fold: the barriers are uniform)
+  auto mx = [&](int slot) { return ls_fold<true>(k.w.part, G, slot, lds); };
+  auto sm = [&](int slot) { return ls_fold<false>(k.w.part, G, slot, lds); };
+  constexpr int M0 = PS_M0, N0 = PS_N0;
+  const ResRowsA ra = {mx(M0), mx(M0 + 1), mx(M0 + 2), mx(M0 + 3), mx(M0 + 4), mx(M0 + 5), mx(M0 + 6), mx(M0 + 7), sm(M0 + 10)};
+  const double adx_hi = mx(M0 + 8), adx_lo = mx(M0 + 9);                                                                      // second stages: folded with the rest
+  const ResRowsB rb = {mx(N0), mx(N0 + 1), mx(N0 + 2), mx(N0 + 3), mx(N0 + 4), mx(N0 + 5), mx(N0 + 6), mx(N0 + 7), mx(N0 + 8), mx(N0 + 9), sm(N0 + 14), sm(N0 + 15), sm(N0 + 16)};
+  const double atdy_u = mx(N0 + 10), atdy_s = mx(N0 + 11), pdx_u = mx(N0 + 12), pdx_s = mx(N0 + 13);
   if (threadIdx.x >= 64) return;
   int *iw = k.w.iw; double *sc = k.w.sc;
   const int done = iw[IW_DONE * W + lane];
   int rhoch = 0;
   if (!done) {
-    const TermRes R = {M_[0], M_[1], M_[2], M_[3], M_[4], M_[5], M_[6], M_[7], M_[10], N_[0], N_[1], N_[2], N_[3], N_[4], N_[5], N_[6], N_[7], N_[9], N_[8], N_[14], N_[15], N_[16]};
-    const double adx_hi = M_[8], adx_lo = M_[9], atdy_u = N_[10], atdy_s = N_[11], pdx_u = N_[12], pdx_s = N_[13];      // second stages: folded with the rest
+    TermRes R;
+    res_store(R, ra, rb);
     double eps_prev, eps_cg;
     bool rel_rule;
     auto put_tol = [&]() { sc[SC_EPSPREV * W + lane] = eps_prev; sc[SC_EPSCG * W + lane] = eps_cg; iw[IW_RELRULE * W + lane] = rel_rule; };
@@ -468,13 +461,13 @@ __global__ __launch_bounds__(256) void k_ls_load_n(LsK k) {
   for (int jl = wv; jl < 64 && j0 + jl < P.n; jl += 4) {
     const int j = j0 + jl;
     const double qv = P.q ? tile[lane][jl] : P.q0[j];
-    k.w.q[IX(j)] = mine ? P.c * P.D[j] * qv : 0.0;
+    k.w.q[IX(j)] = mine ? in_q(P.c, P.D[j], qv) : 0.0;
   }
   __syncthreads();
   if (P.warm) ls_tile_in(P.x, P.n, j0, P.count, P.pc, tile);
   for (int jl = wv; jl < 64 && j0 + jl < P.n; jl += 4) {
     const int j = j0 + jl;
-    const double xv = (P.warm && mine) ? tile[lane][jl] * P.Dinv[j] : 0.0;
+    const double xv = (P.warm && mine) ? in_x(tile[lane][jl], P.Dinv[j]) : 0.0;
     k.w.x[IX(j)] = xv; k.w.xs[IX(j)] = xv; k.w.dx[IX(j)] = 0.0;
   }
 }
@@ -496,16 +489,16 @@ __global__ __launch_bounds__(256) void k_ls_load_m(LsK k) {
     const int il = wv + 4 * s, i = i0 + il;
     if (i < P.m) {
       const double uv = P.u ? tile[lane][il] : P.u0[i];
-      const double li = mine ? P.E[i] * fmax(lo[s], -OSQP_INFTY) : -OSQP_INFTY, ui = mine ? P.E[i] * fmin(uv, OSQP_INFTY) : OSQP_INFTY;
+      const double li = mine ? in_l(P.E[i], lo[s]) : -OSQP_INFTY, ui = mine ? in_u(P.E[i], uv) : OSQP_INFTY;
       k.w.l[IX(i)] = li; k.w.u[IX(i)] = ui; k.w.dy[IX(i)] = 0.0;
-      cnt += ls_ctype(li, ui, P.rho_is_vec) == 0 ? 1.0 : 0.0;
+      cnt += row_class(li, ui, P.rho_is_vec) == 0 ? 1.0 : 0.0;
     }
   }
   __syncthreads();
   if (P.warm) ls_tile_in(P.y, P.m, i0, P.count, P.pr, tile);
   for (int il = wv; il < 64 && i0 + il < P.m; il += 4) {
     const int i = i0 + il;
-    k.w.y[IX(i)] = (P.warm && mine) ? tile[lane][il] * P.Einv[i] * P.c : 0.0;
+    k.w.y[IX(i)] = (P.warm && mine) ? in_y(tile[lane][il], P.Einv[i], P.c) : 0.0;
   }
   red[wv * 64 + lane] = cnt;
   __syncthreads();
@@ -518,7 +511,7 @@ __global__ __launch_bounds__(256) void k_ls_init(LsK k, int tiles_m) {
   const double n_ineq = ls_fold<false>(k.w.parti, tiles_m, 0, lds);
   if (threadIdx.x >= 64) return;
   double *sc = k.w.sc; int *iw = k.w.iw;
-  sc[SC_RHOBAR * W + lane] = k.P.rho0; sc[SC_EQF * W + lane] = (n_ineq == 0.0) ? 1e3 : k.P.eq_factor;
+  sc[SC_RHOBAR * W + lane] = k.P.rho0; sc[SC_EQF * W + lane] = eq_weight(n_ineq == 0.0, k.P.eq_factor);
   sc[SC_EPSCG * W + lane] = 0.0; sc[SC_EPSPREV * W + lane] = INFINITY;
   iw[IW_DONE * W + lane] = lane >= k.P.count; iw[IW_STATUS * W + lane] = OSQP_UNSOLVED; iw[IW_RHOUPD * W + lane] = 0; iw[IW_PCG * W + lane] = 0;
   iw[IW_RELRULE * W + lane] = 1; iw[IW_CGON * W + lane] = 0; iw[IW_RHOCH * W + lane] = 1;

@@ -12,13 +12,13 @@
 #include <vector>
 
 #include "../../osqp-python_amd/csrc/backend.h"
+#include "../../osqp-python_amd/csrc/step_rules.h"
 #include "../../include/osqp_hip.h"
 
 namespace osqp_hip {
 namespace be {
 
 namespace {
-inline double nanmax(double r, double a) { return (a > r || a != a) ? a : r; }
 inline double *gam(Dev &d) { return d.scal + S_HIST; }
 inline double *alp(Dev &d) { return d.scal + S_HIST + kMaxCg + 1; }
 struct Impl { double gamma_next = 0, rnorm = 0, bnorm = 0, delta = 0; };
@@ -178,11 +178,8 @@ void residuals(Dev &d) {
     R[R_PRI_U] = nanmax(R[R_PRI_U], std::fabs(ei * pr)); R[R_AX_U] = nanmax(R[R_AX_U], std::fabs(ei * ax)); R[R_Z_U] = nanmax(R[R_Z_U], std::fabs(ei * d.z[i]));
     R[R_PRI_S] = nanmax(R[R_PRI_S], std::fabs(pr)); R[R_AX_S] = nanmax(R[R_AX_S], std::fabs(ax)); R[R_Z_S] = nanmax(R[R_Z_S], std::fabs(d.z[i]));
     R[R_DY_U] = nanmax(R[R_DY_U], std::fabs(d.E[i] * d.dy[i])); R[R_DY_S] = nanmax(R[R_DY_S], std::fabs(d.dy[i]));
-    R[R_PINF_LHS] += d.u[i] * std::fmax(d.dy[i], 0.0) + d.l[i] * std::fmin(d.dy[i], 0.0);
-    double sup = 0;
-    if (d.y[i] > 0 && d.u[i] < OSQP_INFTY * 1e-4) sup = d.u[i] * d.y[i];
-    else if (d.y[i] < 0 && d.l[i] > -OSQP_INFTY * 1e-4) sup = d.l[i] * d.y[i];
-    R[R_SUPP] += sup;
+    R[R_PINF_LHS] += support_term(d.l[i], d.u[i], d.dy[i]);
+    R[R_SUPP] += support_finite(d.l[i], d.u[i], d.y[i]);
   }
   for (int j = 0; j < d.n; j++) {
     double sp = 0, sa = 0;
@@ -218,7 +215,7 @@ void infeas_dual(Dev &d, double thr, int unscaled) {
     double a = 0;
     for (int k = d.A.rowptr[i]; k < d.A.rowptr[i + 1]; k++) a += d.A.val[k] * d.dx[d.A.col[k]];
     if (unscaled) a *= d.Einv[i];
-    if ((d.u[i] < OSQP_INFTY * 1e-4 && a > thr) || (d.l[i] > -OSQP_INFTY * 1e-4 && a < -thr)) viol += 1;
+    if (adx_violates(a, d.l[i], d.u[i], thr)) viol += 1;
   }
   d.res[R_PDX_U] = u; d.res[R_PDX_S] = s; d.res[R_ADX_VIOL] = viol;
 }
@@ -233,7 +230,7 @@ void fetch_res_flags(Dev &d, double *hr, int *hf) { fetch_res(d, hr); fetch_flag
 void set_rho(Dev &d, double rb) {
   for (int j = 0; j < d.n; j++) { d.xg[j] = d.xs[j]; d.xsp[j] = d.xs[j]; }      // history cleared (backend_hip.hip set_rho)
   for (int i = 0; i < d.m; i++) {
-    double r = d.ctype[i] == -1 ? 1e-6 : (d.ctype[i] == 1 ? d.rho_eq_factor * rb : rb);
+    double r = row_rho(d.ctype[i], rb, d.rho_eq_factor * rb);
     d.rho[i] = r; d.rho_inv[i] = 1.0 / r;
     d.v[i] = r * d.z[i] - d.y[i]; d.ztg[i] = d.zt[i]; d.t0[i] = r * d.zt[i];
   }
@@ -260,7 +257,7 @@ void init_iterates(Dev &d, int full) {
 }
 
 void project_normalcone(Dev &d) {
-  for (int i = 0; i < d.m; i++) { double t = d.z[i] + d.y[i]; d.z[i] = std::fmin(std::fmax(t, d.l[i]), d.u[i]); d.y[i] = t - d.z[i]; }
+  for (int i = 0; i < d.m; i++) { const ConeRow c = normal_cone(d.z[i] + d.y[i], d.l[i], d.u[i]); d.z[i] = c.z; d.y[i] = c.y; }
 }
 
 size_t batch_lds_bytes(int, int) { return 0; }
