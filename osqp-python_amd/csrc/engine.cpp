@@ -446,74 +446,30 @@ void Engine::run_slots(int begin_target, int pairs, int cap) {
   }
 }
 
-double Engine::rho_estimate(const double *res) const {                                   // _osqp.py:880-908 (scaled quantities)
-  return pol_rho_estimate(rho_bar_, res);
+// a solve ends with this status: obj_val follows it (_osqp.py:1025-1028, :1045-1070)
+void Engine::finish(int st) {
+  set_status(st);
+  if (st == OSQP_NON_CVX) info.obj_val = kNaN;
+  else if (term_is_pinf(st)) info.obj_val = OSQP_INFTY;
+  else if (term_is_dinf(st)) info.obj_val = -OSQP_INFTY;
 }
 
-// _osqp.py:998-1077.  Returns 1 when a terminal status was set.
-int Engine::check_termination(const double *res, bool approximate) {
-  double ea = settings.eps_abs, er = settings.eps_rel, epi = settings.eps_prim_inf, edi = settings.eps_dual_inf;
-  if (approximate) { ea *= 10; er *= 10; epi *= 10; edi *= 10; }
-  const bool unsc = settings.scaling && !settings.scaled_termination;
-  if (info.prim_res > OSQP_INFTY || info.dual_res > OSQP_INFTY || std::isnan(info.prim_res) || std::isnan(info.dual_res)) {
-    set_status(OSQP_NON_CVX); info.obj_val = kNaN; return 1;                            // :1025-1028
-  }
-  bool pri_ok = false, dua_ok = false, prim_inf = false, dual_inf = false;
-  if (m == 0) pri_ok = true;
-  else {
-    double eps_pri = ea + er * (unsc ? std::max(res[R_AX_U], res[R_Z_U]) : std::max(res[R_AX_S], res[R_Z_S]));   // :728-751
-    if (info.prim_res < eps_pri) pri_ok = true;
-    else {                                                                              // is_primal_infeasible :796-820
-      double nd = unsc ? res[R_DY_U] : res[R_DY_S];
-      if (nd > epi && res[R_PINF_LHS] < -epi * nd) {
-        be::infeas_primal(d_);
-        double r2[R_COUNT]; be::fetch_res(d_, r2);
-        prim_inf = (unsc ? r2[R_ATDY_U] : r2[R_ATDY_S]) < epi * nd;
-      }
-    }
-  }
-  double mx = unsc ? cinv_ * std::max(std::max(res[R_ATY_U], res[R_PX_U]), res[R_QN_U])
-                   : std::max(std::max(res[R_ATY_S], res[R_PX_S]), res[R_QN_S]);             // :766-794
-  if (info.dual_res < ea + er * mx) dua_ok = true;
-  else {                                                                                // is_dual_infeasible :822-878
-    double nd = unsc ? res[R_DX_U] : res[R_DX_S], sc = unsc ? c_ : 1.0;
-    if (nd > edi && res[R_QDX] < -sc * edi * nd) {
-      be::infeas_dual(d_, edi * nd, unsc ? 1 : 0);
-      double r2[R_COUNT]; be::fetch_res(d_, r2);
-      if ((unsc ? r2[R_PDX_U] : r2[R_PDX_S]) < sc * edi * nd && r2[R_ADX_VIOL] == 0.0) dual_inf = true;
-    }
-  }
-  // check_dualgap (bindings.cpp.in:442): additionally |duality gap| < eps_abs + eps_rel max(|obj|, |dual obj|)   [UPSTREAM-UNVERIFIED form]
-  const bool gap_ok = !settings.check_dualgap ||
-                      std::fabs(info.duality_gap) < ea + er * std::max(std::fabs(info.obj_val), std::fabs(info.dual_obj_val));
-  if (pri_ok && dua_ok && gap_ok) { set_status(approximate ? OSQP_SOLVED_INACCURATE : OSQP_SOLVED); return 1; }
-  if (prim_inf) { set_status(approximate ? OSQP_PRIMAL_INFEASIBLE_INACCURATE : OSQP_PRIMAL_INFEASIBLE); info.obj_val = OSQP_INFTY; return 1; }
-  if (dual_inf) { set_status(approximate ? OSQP_DUAL_INFEASIBLE_INACCURATE : OSQP_DUAL_INFEASIBLE); info.obj_val = -OSQP_INFTY; return 1; }
-  return 0;
+// Second stage of the infeasibility tests for the bits in `need` (is_primal_infeasible :815-818 needs A' dy, is_dual_infeasible :846-872 P dx and
+// A dx): its kernels, then their results into res for ctl_stage2.  Run by whoever owns the boundary -- here the host, for the exact pass of a
+// host-synchronous boundary and for the approximate pass at max_iter.
+void Engine::run_stage2(int need, double *res) {
+  if (need & NEED_PINF) be::infeas_primal(d_);
+  if (need & NEED_DINF) be::infeas_dual(d_, ctl_.inf_thr_d, ctl_.inf_unscaled);
+  double r2[R_COUNT]; be::fetch_res(d_, r2);
+  for (int q = R_ATDY_U; q <= R_ADX_VIOL; q++) res[q] = r2[q];
 }
 
-// The v1 info fields beyond purepy's (bindings.cpp.in:475, 478, 491-492; defined by the un-vendored C core, so the formulas
-// are this engine's reading of their names [UPSTREAM-UNVERIFIED]):
-//   dual_obj_val   -1/2 x'Px - sup_{l <= z <= u} y'z   (the support function of the box at y; finite where y respects infinite bounds)
-//   duality_gap    obj_val - dual_obj_val
-//   rel_kkt_error  max( prim_res / max(||Ax||, ||z||),  dual_res / max(||Px||, ||A'y||, ||q||),  |gap| / max(|obj|, |dual obj|) )
-//   primdual_int   integral over the solve time of |duality_gap| (accumulated at the termination checks)
-// t0 < 0: no time integration (polish).
-void Engine::update_gap_info(const double *res, double t0) {
-  const bool unsc = settings.scaling && !settings.scaled_termination;
-  const double ci = settings.scaling ? cinv_ : 1.0;
-  info.dual_obj_val = (-0.5 * res[R_XPX] - res[R_SUPP]) * ci;
-  info.duality_gap = info.obj_val - info.dual_obj_val;
-  const double pn = unsc ? std::max(res[R_AX_U], res[R_Z_U]) : std::max(res[R_AX_S], res[R_Z_S]);
-  const double dn = unsc ? cinv_ * std::max(std::max(res[R_ATY_U], res[R_PX_U]), res[R_QN_U]) : std::max(std::max(res[R_ATY_S], res[R_PX_S]), res[R_QN_S]);
-  const double gn = std::max(std::fabs(info.obj_val), std::fabs(info.dual_obj_val));
-  const double tiny = 1e-10;
-  info.rel_kkt_error = std::max(std::max(m == 0 ? 0.0 : info.prim_res / (pn + tiny), info.dual_res / (dn + tiny)), std::fabs(info.duality_gap) / (gn + tiny));
-  if (t0 >= 0) {
-    const double t = now_s() - t0;
-    info.primdual_int += std::fabs(info.duality_gap) * std::max(0.0, t - gap_time_);
-    gap_time_ = t;
-  }
+// info.primdual_int: the integral over the solve time of |duality_gap|, accumulated where the host sees a termination check (the other v1 info
+// fields are policy.h ctl_info's)
+void Engine::integrate_gap(double t0) {
+  const double t = now_s() - t0;
+  info.primdual_int += std::fabs(info.duality_gap) * std::max(0.0, t - gap_time_);
+  gap_time_ = t;
 }
 
 // osqp_solve: the solve proper between a hipEvent pair on the solver's stream ("hipEvent around solve"; OSQPHipStats::gpu_solve_ms)
@@ -544,7 +500,7 @@ int Engine::solve_impl() {
   stats_.woodbury_factorisations = 0; stats_.woodbury_factor_ms = 0; stats_.woodbury_cache_hits = 0;
   double res[R_COUNT];
   admm_core(t0, res);
-  info.rho_estimate = rho_estimate(res);                                                 // :1275
+  info.rho_estimate = pol_rho_estimate(rho_bar_, res);                                   // :1275
   info.solve_time = now_s() - t0;
   if (settings.polishing && info.status_val == OSQP_SOLVED) polish();                   // :1278-1279
   store_solution();
@@ -621,19 +577,14 @@ void Engine::apply_rho(double rho) {
   }
 }
 
-// info fields of the last check from the state block (+ the time integral of |gap|, accumulated where the host sees a check)
-void Engine::info_from_ctl(double t0) {
+// info fields of the last check from the state block
+void Engine::info_from_ctl() {
   const Ctl &c = ctl_;
   info.iter = c.iter; info.obj_val = c.obj_val; info.prim_res = c.prim_res; info.dual_res = c.dual_res;
   info.dual_obj_val = c.dual_obj_val; info.duality_gap = c.duality_gap; info.rel_kkt_error = c.rel_kkt_error;
   info.rho_updates = c.rho_updates;
   if (c.rho_estimate > 0) info.rho_estimate = c.rho_estimate;
   rho_at_last_check_ = rho_bar_;
-  if (t0 >= 0) {
-    const double t = now_s() - t0;
-    info.primdual_int += std::fabs(info.duality_gap) * std::max(0.0, t - gap_time_);
-    gap_time_ = t;
-  }
 }
 
 // One chunk of `cnt` ADMM iterations with at most `lim` PCG iterations per solve, host-synchronous; afterwards `flags` holds the chunk's
@@ -922,32 +873,22 @@ void Engine::admm_core(double t0, double *res) {
       const bool was_check = c.ch_at_check;
       st = ctl_boundary(c, res, flags);
       if (st == CTL_RUNNING && c.stage2) {               // second stage of the infeasibility tests (two more SpMVs), then the rest of the boundary
-        if (c.stage2 & NEED_PINF) be::infeas_primal(d_);
-        if (c.stage2 & NEED_DINF) be::infeas_dual(d_, c.inf_thr_d, c.inf_unscaled);
-        double r2[R_COUNT]; be::fetch_res(d_, r2);
-        for (int q = R_ATDY_U; q <= R_ADX_VIOL; q++) res[q] = r2[q];
+        run_stage2(c.stage2, res);
         st = ctl_boundary_stage2(c, res, flags);
       }
       if (was_check) {
-        info_from_ctl(t0);
+        info_from_ctl(); integrate_gap(t0);
         print_log(c, t0);
       }
       (void)tight; (void)rho_was;
       if (st == CTL_RUNNING && c.rho_flag) apply_rho(c.rho_bar);
     } else {
       st = run_device_driven(t0, res, flags);
-      info_from_ctl(t0);
+      info_from_ctl(); integrate_gap(t0);
       print_log(c, t0);
       if (st == -2) { set_status(OSQP_TIME_LIMIT_REACHED); break; }
     }
-    if (st == CTL_DONE) {
-      const int os = c.osqp_status;
-      set_status(os);
-      if (os == OSQP_NON_CVX) info.obj_val = kNaN;
-      else if (os == OSQP_PRIMAL_INFEASIBLE || os == OSQP_PRIMAL_INFEASIBLE_INACCURATE) info.obj_val = OSQP_INFTY;
-      else if (os == OSQP_DUAL_INFEASIBLE || os == OSQP_DUAL_INFEASIBLE_INACCURATE) info.obj_val = -OSQP_INFTY;
-      break;
-    }
+    if (st == CTL_DONE) { finish(c.osqp_status); break; }
     if (st == CTL_NEED_HOST && (c.need & NEED_REFACTOR)) {
       // Woodbury direct mode, device-driven: at the rho update of the last boundary the device-side inversion of S missed the accuracy the
       // direct mode needs (backend k_wb_invert; the chunk it had begun was cancelled).  The solve continues on the host-synchronous path
@@ -959,8 +900,10 @@ void Engine::admm_core(double t0, double *res) {
       c.rho_flag = 0;
       continue;
     }
-    if (st == CTL_NEED_HOST) {                            // max_iter without convergence: the approximate-tolerance pass (:1264-1266)
-      if (!check_termination(res, true)) set_status(OSQP_MAX_ITER_REACHED);
+    if (st == CTL_NEED_HOST) {                            // max_iter without convergence: the approximate-tolerance pass (:1264-1266), the same two
+      int os = ctl_stage1(c, res, true, nullptr, nullptr);      // rules with approximate = true on the info fields of the boundary's check (c.prim_res ..)
+      if (os < 0) { run_stage2(c.need, res); os = ctl_stage2(c, res, true); }
+      finish(os > 0 ? os : (int)OSQP_MAX_ITER_REACHED);
       break;
     }
     if (now_s() - t0 > settings.time_limit) { set_status(OSQP_TIME_LIMIT_REACHED); break; }
@@ -1051,7 +994,6 @@ void Engine::recurrence_restore_rho(const RecurrenceSave &s) {
 void Engine::polish() {
   const double tp = now_s();
   ensure_host_vectors();
-  const bool unsc = settings.scaling && !settings.scaled_termination;
   std::vector<double> z(m), y(m);
   be::d2h(d_, z.data(), d_.z, sizeof(double) * m);
   be::d2h(d_, y.data(), d_.y, sizeof(double) * m);
@@ -1092,14 +1034,13 @@ void Engine::polish() {
   be::init_iterates(d_, 1);                        // z = A x_pol
   be::project_normalcone(d_);                      // tmp = z + y; z = clip(tmp, l, u); y = tmp - z
   be::residuals(d_); be::fetch_res(d_, res);
-  const double pol_pri = (m == 0) ? 0.0 : (unsc ? res[R_PRI_U] : res[R_PRI_S]);
-  const double pol_dua = unsc ? cinv_ * res[R_DUA_U] : res[R_DUA_S];
-  const double pol_obj = (0.5 * res[R_XPX] + res[R_QX]) * (settings.scaling ? cinv_ : 1.0);
-  const bool ok = polish_accept(pol_pri, pol_dua, info0.prim_res, info0.dual_res);
+  Ctl pol = ctl_;                                  // the info fields of the polished point by the rule of every check (policy.h ctl_info), on a copy of
+  ctl_info(pol, res);                              // the settings snapshot: the state block of the solve itself stays as the ADMM loop left it
+  const bool ok = polish_accept(pol.prim_res, pol.dual_res, info0.prim_res, info0.dual_res);
   recurrence_restore_rho(keep);
-  if (ok) {
-    info.obj_val = pol_obj; info.prim_res = pol_pri; info.dual_res = pol_dua; info.status_polish = 1;       // :1797-1807
-    update_gap_info(res, -1.0);
+  if (ok) {                                        // :1797-1807 (primdual_int: the polish adds no time to the integral)
+    info.obj_val = pol.obj_val; info.prim_res = pol.prim_res; info.dual_res = pol.dual_res; info.status_polish = 1;
+    info.dual_obj_val = pol.dual_obj_val; info.duality_gap = pol.duality_gap; info.rel_kkt_error = pol.rel_kkt_error;
   } else {                                          // keep the ADMM solution (:1813-1814)
     info.status_polish = -1;
     be::h2d(d_, d_.x, hx.data(), sizeof(double) * n);
@@ -1109,14 +1050,13 @@ void Engine::polish() {
   }
   be::init_iterates(d_, 0);
   info.polish_time = now_s() - tp;
-  if (settings.verbose) say("plsh  %11.4e   %8.2e   %8.2e   --------  %8.2es\n", pol_obj, pol_pri, pol_dua,
+  if (settings.verbose) say("plsh  %11.4e   %8.2e   %8.2e   --------  %8.2es\n", pol.obj_val, pol.prim_res, pol.dual_res,
                             (first_run_ ? info.setup_time : info.update_time) + info.solve_time + info.polish_time);      // _osqp.py:980-996
 }
 
 void Engine::store_solution() {                                                          // _osqp.py:1098-1115
   const int st = info.status_val;
-  const bool pinf = st == OSQP_PRIMAL_INFEASIBLE || st == OSQP_PRIMAL_INFEASIBLE_INACCURATE;
-  const bool dinf = st == OSQP_DUAL_INFEASIBLE || st == OSQP_DUAL_INFEASIBLE_INACCURATE;
+  const bool pinf = term_is_pinf(st), dinf = term_is_dinf(st);
   const bool unsc = settings.scaling && !settings.scaled_termination;
   std::fill(sol_pc_.begin(), sol_pc_.end(), kNaN); std::fill(sol_dc_.begin(), sol_dc_.end(), kNaN);
   if (!pinf && !dinf) {

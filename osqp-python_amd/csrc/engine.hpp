@@ -130,6 +130,12 @@ class Engine {
   double *lsw_ = nullptr;                             // workspace of one lockstep chunk (lockstep_ws_doubles(n, m)), allocated on first use
   double ls_rec_[OSQP_HIP_LOCKSTEP_LAST_REC] = {0, 0, 0, 0, 0, 0, 0, 0};      // record of the last lockstep call (osqp_hip_lockstep_last_record)
   int run_lockstep(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream);
+  // what the four batch entry points begin with, and the host staging of the two that take host arrays (engine_api.cpp)
+  bool batch_applies();                               // the workgroup route: the QP fits one workgroup's LDS and the handle is not reordered
+  bool batch_applies_prepared();
+  bool lockstep_applies();
+  int batch_enter(int nbatch, bool query, const double *x, const double *y, const double *rec, bool (Engine::*applies)());
+  struct BatchStage;
   double *abuf_ = nullptr; size_t abuf_cap_ = 0;      // device scratch of batch_adjoint (host-array entry point), kept across calls
   bool adjoint_applicable();                          // the problem fits k_batch_adjoint (the forward's direct variant + the adjoint's own LDS)
   void fill_adjoint_params(AdjointParams &p, int nbatch);
@@ -239,7 +245,7 @@ class Engine {
   Ctl ctl_{};                           // state block of the chunk-boundary rules (policy.h)
   void ctl_setup();
   void apply_rho(double rho);
-  void info_from_ctl(double t0);
+  void info_from_ctl();
   void exec_chunk_sync(int cnt, int lim, bool with_res, int kind, double *res, int *flags);
   int run_device_driven(double t0, double *res, int *flags);
   void run_group(int diagonal);
@@ -259,12 +265,12 @@ class Engine {
   // wherever launches may be replayed (admm_core, exec_chunk_sync -- hence polish; ls_solve launches eagerly and replays nothing).
   double graph_sig_[7] = {0, 0, 0, 0, 0, 0, 0};
   void sync_graph_scalars();
-  int check_termination(const double *res, bool approximate);
-  void update_gap_info(const double *res, double t0);
+  void run_stage2(int need, double *res);      // second stage of the infeasibility tests: its kernels, their results into res (for policy.h ctl_stage2)
+  void integrate_gap(double t0);               // info.primdual_int up to now
   double gap_time_ = 0;
-  double rho_estimate(const double *res) const;
   void store_solution();
   void set_status(int status);
+  void finish(int status);                     // set_status + the obj_val that goes with the status
   int auto_rho_interval() const;
 };
 

@@ -673,8 +673,7 @@ int Engine::solve_small_direct(double t0) {
     be::set_rho(d_, rho_bar_);
     be::precond(d_, settings.cg_precond == OSQP_DIAGONAL_PRECONDITIONER);
   }
-  const bool pinf = st == OSQP_PRIMAL_INFEASIBLE || st == OSQP_PRIMAL_INFEASIBLE_INACCURATE;
-  const bool dinf = st == OSQP_DUAL_INFEASIBLE || st == OSQP_DUAL_INFEASIBLE_INACCURATE;
+  const bool pinf = term_is_pinf(st), dinf = term_is_dinf(st);
   std::fill(sol_pc_.begin(), sol_pc_.end(), kNaN); std::fill(sol_dc_.begin(), sol_dc_.end(), kNaN);
   const bool finite_xy = std::isfinite(rec[2]) && st != OSQP_NON_CVX;
   if (!pinf && !dinf) {
@@ -683,7 +682,7 @@ int Engine::solve_small_direct(double t0) {
       const int keep = settings.warm_starting;
       warm_start(x.data(), m > 0 ? y.data() : nullptr, /*keep_z=*/true);   // device x, y follow; z is the kernel's own (a later solve continues from them)
       settings.warm_starting = keep;
-      // the v1 gap fields (update_gap_info) from the unscaled data on the host: a few hundred entries
+      // the v1 gap fields (policy.h ctl_info) from the unscaled data on the host -- the kernel's record carries no residual block: a few hundred entries
       ensure_host_vectors();
       std::vector<double> px(n, 0.0), ax(m, 0.0), aty(n, 0.0);
       for (int j = 0; j < n; j++)
@@ -698,9 +697,7 @@ int Engine::solve_small_direct(double t0) {
       }
       info.dual_obj_val = -0.5 * xpx - sup;
       info.duality_gap = info.obj_val - info.dual_obj_val;
-      const double tiny = 1e-10, gn = std::max(std::fabs(info.obj_val), std::fabs(info.dual_obj_val));
-      info.rel_kkt_error = std::max(std::max(m == 0 ? 0.0 : info.prim_res / (std::max(nax, nz) + tiny), info.dual_res / (std::max(std::max(npx, naty), nq) + tiny)),
-                                    std::fabs(info.duality_gap) / (gn + tiny));
+      info.rel_kkt_error = term_rel_kkt(m, info.prim_res, std::max(nax, nz), info.dual_res, std::max(std::max(npx, naty), nq), info.duality_gap, info.obj_val, info.dual_obj_val);
     } else {
       cold_start();                                             // NaN iterates (non-convex problem) are no warm start
       info.dual_obj_val = info.duality_gap = info.rel_kkt_error = kNaN;
@@ -766,40 +763,89 @@ int Engine::launch_batch(BatchParams &p, int nbatch, const double *Px, const dou
   return err;
 }
 
-int Engine::batch_solve(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, double *zs_dev, const double *Px, const double *Ax) {
+// ---- what the batch entry points share
+bool Engine::batch_applies() { return be::batch_lds_bytes(n, m) && !reordered_; }      // (a reordered handle is a large single QP: the batch kernel is for QPs that fit one workgroup)
+bool Engine::batch_applies_prepared() { prepare_batch_direct(); return batch_applies(); }      // (the symbolic part runs on every backend: tests read the bandwidth)
+bool Engine::lockstep_applies() { return be::lockstep_chunk && be::device_vec_updates() && !d_.wb.on; }
+
+// How every batch entry point begins: the handle is ready, the arguments are there, the route (`applies`) holds this handle; then the device is
+// this handle's and nothing on a caller's stream still reads what the call is about to overwrite (the scratch block, the shared vectors, kp_val).
+// query (the device-pointer entry points): nbatch == 0 asks whether the route applies -- a rank whose share of a sharded batch is empty; the answer
+// depends on the handle alone, so every rank of a job reaches the same decision before its first collective (osqp_amd/sharded.py).
+// Returns kBatchEnter to go on, else what the entry point returns.
+constexpr int kBatchEnter = -1;
+int Engine::batch_enter(int nbatch, bool query, const double *x, const double *y, const double *rec, bool (Engine::*applies)()) {
   if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (query && nbatch == 0) return (this->*applies)() ? OSQP_NO_ERROR : OSQP_FUNC_NOT_IMPLEMENTED;
   if (nbatch <= 0 || !x || !y || !rec) return OSQP_DATA_VALIDATION_ERROR;
-  prepare_batch_direct();                                     // (symbolic part runs on every backend: tests read the bandwidth)
-  if (!be::batch_lds_bytes(n, m) || reordered_) return OSQP_FUNC_NOT_IMPLEMENTED;      // (a reordered handle is a large single QP: the batch kernel is for QPs that fit one workgroup)
+  if (!(this->*applies)()) return OSQP_FUNC_NOT_IMPLEMENTED;
   be::activate(d_);
-  be::ext_wait(d_);                                 // the scratch block may still be read by a kernel on a caller's stream
-  const bool timing = pol_.batch_timing != 0;
-  double tph[5]; tph[0] = now_s();
-  const size_t N = (size_t)nbatch * n, M = (size_t)nbatch * m;
-  if ((l || u) && !(l && u)) ensure_host_vectors();
-  for (int b = 0; b < nbatch && (l || u); b++)                                                       // _osqp.py:1348-1349
-    for (int i = 0; i < m; i++) {
-      const double li = l ? l[(size_t)b * m + i] : l0_[i], ui = u ? u[(size_t)b * m + i] : u0_[i];
-      if (!(li <= ui)) return OSQP_DATA_VALIDATION_ERROR;
+  be::ext_wait(d_);
+  return kBatchEnter;
+}
+
+// Host staging of a batch given as host arrays (batch_solve, batch_solve_lockstep).  in: batch_enter, l <= u for every member, the device scratch
+// block bbuf_ = [q | l | u | x | y | rec | tail] (kept for the next call), the uploads; out: the downloads.  What the two routes do differently:
+//   own_row   where row i of the caller's numbering sits in l0_ / u0_, the host copies of the handle's own bounds (nullptr: at i).  The lockstep route
+//             passes ipr_ on a reordered handle -- the copies are kept in the engine's numbering; the workgroup route refuses reordered handles;
+//   wg        the workgroup route appends [q0 | l0 | u0 | Px | Ax]: the handle's own vectors for the arguments given as NULL, uploaded where they
+//             are not resident (!be::device_vec_updates(); dq0 .. du0 point at the resident ones otherwise), and the per-problem matrix values.  The
+//             lockstep route reads d_.qraw .. itself and has no per-problem matrices.
+struct Engine::BatchStage {
+  Engine &e; int nbatch;
+  bool (Engine::*applies)();                          // the route
+  const int *own_row; bool wg;
+  size_t N = 0, M = 0;
+  double *dq = nullptr, *dl = nullptr, *du = nullptr, *dx = nullptr, *dy = nullptr, *drec = nullptr, *dq0 = nullptr, *dl0 = nullptr, *du0 = nullptr, *dPx = nullptr, *dAx = nullptr;
+  double t[3] = {0, 0, 0};                            // in() began / validated / uploaded (batch_timing)
+  int in(const double *q, const double *l, const double *u, const double *x, const double *y, const double *rec, int warm, const double *Px = nullptr, const double *Ax = nullptr) {
+    const int err = e.batch_enter(nbatch, false, x, y, rec, applies);
+    if (err != kBatchEnter) return err;
+    const int n = e.n, m = e.m;
+    Dev &d = e.d_;
+    t[0] = now_s();
+    N = (size_t)nbatch * n; M = (size_t)nbatch * m;
+    if ((l || u) && !(l && u)) e.ensure_host_vectors();
+    for (int b = 0; b < nbatch && (l || u); b++)                                                       // _osqp.py:1348-1349
+      for (int i = 0; i < m; i++) {
+        const int ii = own_row ? own_row[i] : i;
+        const double li = l ? l[(size_t)b * m + i] : e.l0_[ii], ui = u ? u[(size_t)b * m + i] : e.u0_[ii];
+        if (!(li <= ui)) return OSQP_DATA_VALIDATION_ERROR;
+      }
+    t[1] = now_s();
+    const size_t NP = Px ? (size_t)nbatch * e.P_.nnz() : 0, NA = Ax ? (size_t)nbatch * e.A_.nnz() : 0;
+    const size_t need = 2 * N + 3 * M + (size_t)nbatch * kBatchRec + (wg ? n + 2 * (size_t)m + NP + NA : 0);
+    if (need > e.bbuf_cap_) { if (e.bbuf_) be::dfree(d, e.bbuf_); e.bbuf_ = dev_vec<double>(d, need); e.bbuf_cap_ = need; }
+    dq = e.bbuf_; dl = dq + N; du = dl + M; dx = du + M; dy = dx + N; drec = dy + M;
+    if (wg) {
+      dq0 = drec + (size_t)nbatch * kBatchRec; dl0 = dq0 + n; du0 = dl0 + m; dPx = du0 + m; dAx = dPx + NP;
+      if (Px) be::h2d(d, dPx, Px, sizeof(double) * NP);
+      if (Ax) be::h2d(d, dAx, Ax, sizeof(double) * NA);
+      const bool devv = be::device_vec_updates();       // then the solver's own q, l, u are resident (unscaled): no upload for NULL arguments
+      if (!q) { if (devv) dq0 = d.qraw; else be::h2d(d, dq0, e.q0_.data(), sizeof(double) * n); }
+      if (!l) { if (devv) dl0 = d.lraw; else be::h2d(d, dl0, e.l0_.data(), sizeof(double) * m); }
+      if (!u) { if (devv) du0 = d.uraw; else be::h2d(d, du0, e.u0_.data(), sizeof(double) * m); }
     }
-  tph[1] = now_s();
-  // one device scratch block, kept for the next call: [q | l | u | x | y | rec | q0 | l0 | u0]
-  const size_t NP = Px ? (size_t)nbatch * P_.nnz() : 0, NA = Ax ? (size_t)nbatch * A_.nnz() : 0;
-  const size_t need = 2 * N + 3 * M + (size_t)nbatch * kBatchRec + n + 2 * (size_t)m + NP + NA;
-  if (need > bbuf_cap_) { if (bbuf_) be::dfree(d_, bbuf_); bbuf_ = dev_vec<double>(d_, need); bbuf_cap_ = need; }
-  double *dq = bbuf_, *dl = dq + N, *du = dl + M, *dx = du + M, *dy = dx + N, *drec = dy + M, *dq0 = drec + (size_t)nbatch * kBatchRec, *dl0 = dq0 + n, *du0 = dl0 + m;
-  double *dPx = du0 + m, *dAx = dPx + NP;
-  if (Px) be::h2d(d_, dPx, Px, sizeof(double) * NP);
-  if (Ax) be::h2d(d_, dAx, Ax, sizeof(double) * NA);
-  const bool devv = be::device_vec_updates();         // then the solver's own q, l, u are resident (unscaled): no upload for NULL arguments
-  if (q) be::h2d(d_, dq, q, sizeof(double) * N); else if (devv) dq0 = d_.qraw; else be::h2d(d_, dq0, q0_.data(), sizeof(double) * n);
-  if (l) be::h2d(d_, dl, l, sizeof(double) * M); else if (devv) dl0 = d_.lraw; else be::h2d(d_, dl0, l0_.data(), sizeof(double) * m);
-  if (u) be::h2d(d_, du, u, sizeof(double) * M); else if (devv) du0 = d_.uraw; else be::h2d(d_, du0, u0_.data(), sizeof(double) * m);
-  if (warm) { be::h2d(d_, dx, x, sizeof(double) * N); be::h2d(d_, dy, y, sizeof(double) * M); }
-  be::sync(d_); tph[2] = now_s();
+    if (q) be::h2d(d, dq, q, sizeof(double) * N);
+    if (l) be::h2d(d, dl, l, sizeof(double) * M);
+    if (u) be::h2d(d, du, u, sizeof(double) * M);
+    if (warm) { be::h2d(d, dx, x, sizeof(double) * N); be::h2d(d, dy, y, sizeof(double) * M); }
+    be::sync(d); t[2] = now_s();
+    return OSQP_NO_ERROR;
+  }
+  void out(double *x, double *y, double *rec) const {
+    be::d2h(e.d_, x, dx, sizeof(double) * N);
+    if (M) be::d2h(e.d_, y, dy, sizeof(double) * M);  // (m == 0: nothing to read, on either route)
+    be::d2h(e.d_, rec, drec, sizeof(double) * kBatchRec * nbatch);
+  }
+};
+
+int Engine::batch_solve(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, double *zs_dev, const double *Px, const double *Ax) {
+  BatchStage s{*this, nbatch, &Engine::batch_applies_prepared, /*own_row=*/nullptr, /*wg=*/true};
+  if (const int err = s.in(q, l, u, x, y, rec, warm, Px, Ax)) return err;
   BatchParams p{};
   fill_batch_params(p, nbatch, warm);
-  p.q = q ? dq : nullptr; p.l = l ? dl : nullptr; p.u = u ? du : nullptr; p.q0 = dq0; p.l0 = dl0; p.u0 = du0; p.x = dx; p.y = dy; p.rec = drec;
+  p.q = q ? s.dq : nullptr; p.l = l ? s.dl : nullptr; p.u = u ? s.du : nullptr; p.q0 = s.dq0; p.l0 = s.dl0; p.u0 = s.du0; p.x = s.dx; p.y = s.dy; p.rec = s.drec;
   p.zs = zs_dev;
   // Launch order: the problems that took most iterations in the PREVIOUS call of the same size go first (parametric batches -- MPC
   // steps, training epochs -- repeat their hard problems; with index order the last round of workgroups waits for stragglers:
@@ -811,19 +857,18 @@ int Engine::batch_solve(int nbatch, const double *q, const double *l, const doub
     p.order = d_batch_order_;
   }
   d_batch_iters_n_ = 0;                            // (the device-pointer path's history does not describe this call)
-  const int err = launch_batch(p, nbatch, Px ? dPx : nullptr, Ax ? dAx : nullptr, nullptr, false);
-  tph[3] = now_s();
+  const int err = launch_batch(p, nbatch, Px ? s.dPx : nullptr, Ax ? s.dAx : nullptr, nullptr, false);
+  const double t_ran = now_s();
   if (!err) {
-    be::d2h(d_, x, dx, sizeof(double) * N); be::d2h(d_, y, dy, sizeof(double) * M); be::d2h(d_, rec, drec, sizeof(double) * kBatchRec * nbatch);
+    s.out(x, y, rec);
     if (reorder && nbatch > 1) {
       batch_order_.resize(nbatch);
       for (int b = 0; b < nbatch; b++) batch_order_[b] = b;
       std::stable_sort(batch_order_.begin(), batch_order_.end(), [&](int a, int b) { return rec[(size_t)a * kBatchRec + 1] > rec[(size_t)b * kBatchRec + 1]; });
     }
   }
-  tph[4] = now_s();
-  stats_.gpu_solve_ms = 1e3 * (tph[3] - tph[2]);
-  if (timing) std::fprintf(stderr, "osqp_hip batch: validate %.2f ms, H2D %.2f ms, kernel %.2f ms, D2H %.2f ms\n", 1e3 * (tph[1] - tph[0]), 1e3 * (tph[2] - tph[1]), 1e3 * (tph[3] - tph[2]), 1e3 * (tph[4] - tph[3]));
+  stats_.gpu_solve_ms = 1e3 * (t_ran - s.t[2]);
+  if (pol_.batch_timing) std::fprintf(stderr, "osqp_hip batch: validate %.2f ms, H2D %.2f ms, kernel %.2f ms, D2H %.2f ms\n", 1e3 * (s.t[1] - s.t[0]), 1e3 * (s.t[2] - s.t[1]), 1e3 * (t_ran - s.t[2]), 1e3 * (now_s() - t_ran));
   return err;
 }
 
@@ -831,14 +876,8 @@ int Engine::batch_solve(int nbatch, const double *q, const double *l, const doub
 // Device-resident variant: q, l, u, x, y, rec are device pointers on this solver's device; the kernel is
 // enqueued on the caller's stream and not waited for (stream == nullptr: the solver's stream, synchronous).
 int Engine::batch_solve_device(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream, const double *Px, const double *Ax) {
-  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  // nbatch == 0: the applicability query of a rank whose share of a sharded batch is empty -- the answer depends on (n, m) alone, so every
-  // rank of a job reaches the same decision before its first collective (osqp_amd/sharded.py)
-  if (nbatch == 0) return (be::batch_lds_bytes(n, m) && !reordered_) ? OSQP_NO_ERROR : OSQP_FUNC_NOT_IMPLEMENTED;
-  if (nbatch < 0 || !x || !y || !rec) return OSQP_DATA_VALIDATION_ERROR;
-  if (!be::batch_lds_bytes(n, m) || reordered_) return OSQP_FUNC_NOT_IMPLEMENTED;
-  be::activate(d_);
-  be::ext_wait(d_);                                 // the previous device-pointer call: its kernel reads the shared vectors and kp_val
+  const int enter = batch_enter(nbatch, true, x, y, rec, &Engine::batch_applies);
+  if (enter != kBatchEnter) return enter;
   // shared vectors (for the arguments given as NULL): the solver's own resident unscaled q, l, u
   double *dq0 = d_.qraw, *dl0 = d_.lraw, *du0 = d_.uraw;
   BatchParams p{};
@@ -891,41 +930,16 @@ int Engine::run_lockstep(int nbatch, const double *q, const double *l, const dou
 }
 
 int Engine::batch_solve_lockstep(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm) {
-  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  if (nbatch <= 0 || !x || !y || !rec) return OSQP_DATA_VALIDATION_ERROR;
-  if (!be::lockstep_chunk || !be::device_vec_updates() || d_.wb.on) return OSQP_FUNC_NOT_IMPLEMENTED;
-  be::activate(d_);
-  be::ext_wait(d_);                                 // the scratch block may still be read by a kernel on a caller's stream
-  const size_t N = (size_t)nbatch * n, M = (size_t)nbatch * m;
-  if ((l || u) && !(l && u)) ensure_host_vectors();
-  for (int b = 0; b < nbatch && (l || u); b++)                                                       // _osqp.py:1348-1349
-    for (int i = 0; i < m; i++) {
-      const int ii = reordered_ ? ipr_[i] : i;       // (the host copies of the handle's own bounds are kept in the engine's numbering)
-      const double li = l ? l[(size_t)b * m + i] : l0_[ii], ui = u ? u[(size_t)b * m + i] : u0_[ii];
-      if (!(li <= ui)) return OSQP_DATA_VALIDATION_ERROR;
-    }
-  // the batch path's device scratch block: [q | l | u | x | y | rec]
-  const size_t need = 2 * N + 3 * M + (size_t)nbatch * kBatchRec;
-  if (need > bbuf_cap_) { if (bbuf_) be::dfree(d_, bbuf_); bbuf_ = dev_vec<double>(d_, need); bbuf_cap_ = need; }
-  double *dq = bbuf_, *dl = dq + N, *du = dl + M, *dx = du + M, *dy = dx + N, *drec = dy + M;
-  if (q) be::h2d(d_, dq, q, sizeof(double) * N);
-  if (l) be::h2d(d_, dl, l, sizeof(double) * M);
-  if (u) be::h2d(d_, du, u, sizeof(double) * M);
-  if (warm) { be::h2d(d_, dx, x, sizeof(double) * N); be::h2d(d_, dy, y, sizeof(double) * M); }
-  be::sync(d_);
-  const int err = run_lockstep(nbatch, q ? dq : nullptr, l ? dl : nullptr, u ? du : nullptr, dx, dy, drec, warm, nullptr);
-  if (!err) { be::d2h(d_, x, dx, sizeof(double) * N); if (M) be::d2h(d_, y, dy, sizeof(double) * M); be::d2h(d_, rec, drec, sizeof(double) * kBatchRec * nbatch); }
+  BatchStage s{*this, nbatch, &Engine::lockstep_applies, /*own_row=*/reordered_ ? ipr_.data() : nullptr, /*wg=*/false};
+  if (const int err = s.in(q, l, u, x, y, rec, warm)) return err;
+  const int err = run_lockstep(nbatch, q ? s.dq : nullptr, l ? s.dl : nullptr, u ? s.du : nullptr, s.dx, s.dy, s.drec, warm, nullptr);
+  if (!err) s.out(x, y, rec);
   return err;
 }
 
 int Engine::batch_solve_lockstep_device(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream) {
-  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  const bool applies = be::lockstep_chunk && be::device_vec_updates() && !d_.wb.on;
-  if (nbatch == 0) return applies ? OSQP_NO_ERROR : OSQP_FUNC_NOT_IMPLEMENTED;
-  if (nbatch < 0 || !x || !y || !rec) return OSQP_DATA_VALIDATION_ERROR;
-  if (!applies) return OSQP_FUNC_NOT_IMPLEMENTED;
-  be::activate(d_);
-  be::ext_wait(d_);
+  const int enter = batch_enter(nbatch, true, x, y, rec, &Engine::lockstep_applies);
+  if (enter != kBatchEnter) return enter;
   be::sync(d_);                                     // the solver's own stream first: pending updates of the resident q / l / u, the matrices
   return run_lockstep(nbatch, q, l, u, x, y, rec, warm, stream);
 }

@@ -6,8 +6,10 @@
 // What the rules are (each cites the reference where it has a counterpart; DESIGN.md sections 2, 2.1 for the measurements behind them):
 //   ctl_next_chunk      where the next chunk of ADMM iterations ends: the next termination check (_osqp.py:1254-1262), the next rho
 //                       adaptation point (:1229-1245), or the start of the tight-tolerance window in front of it
-//   ctl_stage1          residuals -> info fields, tolerances, the termination test proper (:998-1077) and the FIRST stage of the
-//                       infeasibility tests (:796-878) -- the second stage needs two more SpMVs and is run by the host on demand.
+//   ctl_stage1 / 2      residuals -> info fields, tolerances, the termination test proper (:998-1077) and the FIRST stage of the
+//                       infeasibility tests (:796-878); the second stage needs two more SpMVs, run on demand by whoever owns the boundary
+//                       (the device's boundary group, or Engine::run_stage2), and is ctl_stage2.  `approximate`: the x10 pass at max_iter
+//                       (:1264-1266) -- the same two functions, called by the host when a solve ends with CTL_NEED_HOST.
 //                       The tests themselves are term_rules.h's (one text with the batch kernels); Ctl adds the duality-gap check,
 //                       the need bits and the inf_* bookkeeping
 //   ctl_rho_rule        adaptive rho (:880-930) with this engine's square-root tolerance and persistence test
@@ -138,10 +140,17 @@ OSQP_HD inline void ctl_account(Ctl &c, const int *flags) {
   c.iter = c.ch_next;
 }
 
-// info fields of a check (_osqp.py:705-764) + the v1 gap fields (engine.cpp update_gap_info; [UPSTREAM-UNVERIFIED] formulas)
+// info fields of a check (_osqp.py:705-764) + the v1 fields beyond purepy's (bindings.cpp.in:475, 478, 491-492; defined by the un-vendored C core, so
+// the formulas are this engine's reading of their names [UPSTREAM-UNVERIFIED]):
+//   dual_obj_val   -1/2 x'Px - sup_{l <= z <= u} y'z   (the support function of the box at y; finite where y respects infinite bounds)
+//   duality_gap    obj_val - dual_obj_val
+//   rel_kkt_error  max( prim_res / max(||Ax||, ||z||),  dual_res / max(||Px||, ||A'y||, ||q||),  |gap| / max(|obj|, |dual obj|) )
+// (primdual_int, the time integral of |duality_gap|, is the host's: engine.cpp integrate_gap).  Also the info fields of a polished point
+// (Engine::polish, on a copy of the state block).
 OSQP_HD inline void ctl_info(Ctl &c, const double *res) {
   // (written out on Ctl's own fields, not through term_info: routed through it the device compiler fuses the product of obj_val into the
-  //  subtraction of duality_gap, and the gap's last bits change)
+  //  subtraction of duality_gap, and the gap's last bits change.  For the same reason the subtraction stays here, on the stored fields, and
+  //  only what comes after it -- term_rel_kkt: quotients and maxima, nothing to fuse -- is term_rules.h's, shared with the small-problem path)
   const bool unsc = c.scaling && !c.scaled_termination;
   const double ci = c.scaling ? c.cinv : 1.0;
   c.obj_val = (0.5 * res[R_XPX] + res[R_QX]) * ci;
@@ -151,15 +160,13 @@ OSQP_HD inline void ctl_info(Ctl &c, const double *res) {
   c.duality_gap = c.obj_val - c.dual_obj_val;
   const double pn = unsc ? fmax(res[R_AX_U], res[R_Z_U]) : fmax(res[R_AX_S], res[R_Z_S]);
   const double dn = unsc ? c.cinv * fmax(fmax(res[R_ATY_U], res[R_PX_U]), res[R_QN_U]) : fmax(fmax(res[R_ATY_S], res[R_PX_S]), res[R_QN_S]);
-  const double gn = fmax(fabs(c.obj_val), fabs(c.dual_obj_val));
-  const double tiny = 1e-10;
-  c.rel_kkt_error = fmax(fmax(c.m == 0 ? 0.0 : c.prim_res / (pn + tiny), c.dual_res / (dn + tiny)), fabs(c.duality_gap) / (gn + tiny));
+  c.rel_kkt_error = term_rel_kkt(c.m, c.prim_res, pn, c.dual_res, dn, c.duality_gap, c.obj_val, c.dual_obj_val);
   for (int q = 0; q < R_COUNT; q++) c.res[q] = res[q];
 }
 
 // First stage of check_termination (term_rules.h term_stage1 + this path's duality-gap test).  Returns an osqp_status_type value when the status
-// is decided without the infeasibility tests' second stage, 0 when the solve goes on, and -1 with c.need set when the host has to run the second
-// stage (is_primal_infeasible :815-818 / is_dual_infeasible :846-872 need A' dy, P dx, A dx).
+// is decided without the infeasibility tests' second stage, 0 when the solve goes on, and -1 with c.need set when the second stage has to run
+// (is_primal_infeasible :815-818 / is_dual_infeasible :846-872 need A' dy, P dx, A dx).
 OSQP_HD inline int ctl_stage1(Ctl &c, const double *res, bool approximate, bool *pri_ok_out, bool *dua_ok_out) {
   const int unsc = c.scaling && !c.scaled_termination;
   const TermSet s = ctl_term_set(c, unsc);
@@ -232,7 +239,8 @@ OSQP_HD inline bool ctl_boundary_continue(Ctl &c, const double *res, const int *
 //   CTL_RUNNING    the next chunk is set up in ch_* (rho_flag: rho_bar changed) -- or, with c.stage2 != 0, the second stage of the
 //                  infeasibility tests is pending: its kernels have to run, then ctl_boundary_stage2 finishes the boundary;
 //   CTL_DONE       osqp_status set;
-//   CTL_NEED_HOST  max_iter reached without convergence: the approximate-tolerance pass (:1264-1266) is the host's.
+//   CTL_NEED_HOST  max_iter reached without convergence: the host runs the approximate-tolerance pass (:1264-1266) -- ctl_stage1 / ctl_stage2
+//                  with approximate = true on this block -- and ends the solve.
 OSQP_HD inline int ctl_boundary(Ctl &c, const double *res, const int *flags) {
   ctl_account(c, flags);
   c.rho_flag = 0; c.need = NEED_NONE; c.stage2 = 0;

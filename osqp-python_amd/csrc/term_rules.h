@@ -1,5 +1,7 @@
 // term_rules.h -- when a QP is finished, what its rho should be and what its caller gets back, as plain functions on scalars: ONE text for every
-// place that decides it.  policy.h (the single-QP driver: host + backend_hip.hip k_decide) builds its Ctl rules from the first part; the batch family
+// place that decides it.  policy.h (the single-QP driver: host + backend_hip.hip k_decide) builds its Ctl rules from the first part -- the host driver
+// (engine.cpp, engine_api.cpp) keeps no text of its own: the approximate pass at max_iter, the info fields of a polished point and the statuses'
+// objective values are these rules too (profiles/host_rules_ab.txt: bit for bit what its former transcriptions gave); the batch family
 // (batch_hip.hip k_batch_admm / k_batch_wave, lockstep_hip.hip k_ls_decide / k_ls_store_*) calls the second part.  Compiles for host and device and under
 // plain g++ (tests/hostsim/policy_probe.cpp, tests/test_batch_rules.py); nothing here knows a Ctl, a parameter block, a vector or LDS.  The order of the
 // floating-point operations in every expression is part of the contract: results are compared bit for bit across the kernels.
@@ -45,6 +47,13 @@ OSQP_HDI void term_info(const TermSet &s, const TermRes &R, double *obj, double 
   *obj = (0.5 * R.xpx + R.qx) * (s.scaling ? s.cinv : 1.0);
   *prim_res = (s.m == 0) ? 0.0 : (s.unscaled ? R.pri_u : R.pri_s);
   *dual_res = s.unscaled ? s.cinv * R.dua_u : R.dua_s;
+}
+// rel_kkt_error of a check: the largest of the three relative errors, each over its normalisation + 1e-10 (pn: max(||A x||, ||z||), dn: max(||P x||,
+// ||A' y||, ||q||); gap = obj - dual_obj is the CALLER's subtraction: policy.h ctl_info says why).  Only fabs, fmax, the add of a constant and divisions:
+// nothing here can be contracted into an FMA, so host and device give the same bits (profiles/host_rules_ab.txt)
+OSQP_HDI double term_rel_kkt(int m, double prim_res, double pn, double dual_res, double dn, double gap, double obj, double dual_obj) {
+  const double tiny = 1e-10, gn = fmax(fabs(obj), fabs(dual_obj));
+  return fmax(fmax(m == 0 ? 0.0 : prim_res / (pn + tiny), dual_res / (dn + tiny)), fabs(gap) / (gn + tiny));
 }
 // the x10 of the approximate pass (_osqp.py:1012-1016)
 OSQP_HDI double term_eps(double eps, bool approx) { return (approx ? 10.0 : 1.0) * eps; }

@@ -108,6 +108,8 @@ int br_ctl_check(const double *set9, const double *R22, int approx, const double
   res[R_ATDY_U] = stage2[0]; res[R_ATDY_S] = stage2[1]; res[R_PDX_U] = stage2[2]; res[R_PDX_S] = stage2[3]; res[R_ADX_VIOL] = stage2[4] != 0.0 ? 0.0 : 1.0;
   return ctl_stage2(c, res, approx != 0);
 }
+// in8: m, prim_res, pn, dual_res, dn, gap, obj, dual_obj
+double br_rel_kkt(const double *in8) { return term_rel_kkt((int)in8[0], in8[1], in8[2], in8[3], in8[4], in8[5], in8[6], in8[7]); }
 double br_rho_estimate(double rho_bar, const double *R22) { return term_rho_estimate(rho_bar, br_res(R22)); }
 int br_rho_rule(double rho_bar, double rho_tol, const double *R22, double *rho_new) { return batch_rho_rule(rho_bar, rho_tol, br_res(R22), rho_new) ? 1 : 0; }
 // state3: eps_prev, eps_cg, rel_rule
@@ -122,3 +124,27 @@ void br_record(double *rc, int status, int iter, double obj, double prim_res, do
 double br_out_x(int status, int unscaled, int scaling, double Dj, double xj, double dxj) { return batch_out_x(status, unscaled, scaling, Dj, xj, dxj); }
 double br_out_y(int status, int unscaled, int scaling, double cinv, double Ei, double yi, double dyi) { return batch_out_y(status, unscaled, scaling, cinv, Ei, yi, dyi); }
 }
+
+// Stand-alone form (-DPOLICY_PROBE_MAIN: g++ -fsanitize=address,undefined of this file alone): br_ctl_check and br_rel_kkt on a few blocks, both passes,
+// m == 0 and zero norms included; prints what it got and returns 0.
+#ifdef POLICY_PROBE_MAIN
+#include <cstdio>
+int main() {
+  const double sets[3][9] = {{1e-3, 1e-3, 1e-4, 1e-4, 1.0, 1.0, 5, 0, 1}, {1e-3, 1e-3, 1e-4, 1e-4, 0.5, 2.0, 5, 1, 1}, {1e-3, 1e-3, 1e-4, 1e-4, 1.0, 1.0, 0, 0, 0}};
+  // TermRes order: pri_u ax_u z_u pri_s ax_s z_s dy_u dy_s pinf_lhs dua_u px_u aty_u dua_s px_s aty_s dxn_u dxn_s qn_u qn_s xpx qx qdx
+  const double blocks[4][22] = {{1e-4, 1, 1, 1e-4, 1, 1, 1, 1, 0.5, 1e-4, 1, 1, 1e-4, 1, 1, 1, 1, 1, 1, 2.0, -3.0, 0.5},            // converged
+                                {0.1, 1, 1, 0.1, 1, 1, 2, 2, -1.0, 0.1, 1, 1, 0.1, 1, 1, 1, 1, 1, 1, 2.0, -3.0, 0.5},                // primal certificate pending
+                                {0.1, 1, 1, 0.1, 1, 1, 1, 1, 0.5, 0.1, 1, 1, 0.1, 1, 1, 2, 2, 1, 1, 2.0, -3.0, -1.0},                // dual certificate pending
+                                {5e-3, 0, 0, 5e-3, 0, 0, 0, 0, 0, 5e-3, 0, 0, 5e-3, 0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0}};               // zero norms
+  const double stage2[5] = {1e-5, 1e-5, 1e-5, 1e-5, 1.0};
+  for (const auto &s : sets)
+    for (const auto &b : blocks)
+      for (int approx = 0; approx < 2; approx++) {
+        double info3[3];
+        const int st = br_ctl_check(s, b, approx, stage2, info3);
+        const double in8[8] = {s[6], info3[1], b[4] > b[5] ? b[4] : b[5], info3[2], b[13], info3[0] - 1.0, info3[0], 1.0};
+        std::printf("m %d unscaled %d approx %d: status %d obj %.17g prim %.17g dual %.17g rel_kkt %.17g\n", (int)s[6], (int)s[7], approx, st, info3[0], info3[1], info3[2], br_rel_kkt(in8));
+      }
+  return 0;
+}
+#endif

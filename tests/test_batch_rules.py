@@ -29,6 +29,7 @@ def lib():
     L = C.CDLL(OUT)
     L.br_check.argtypes = [DP, DP, C.c_int, C.c_int, C.c_int, DP, DP]; L.br_check.restype = C.c_int
     L.br_ctl_check.argtypes = [DP, DP, C.c_int, DP, DP]; L.br_ctl_check.restype = C.c_int
+    L.br_rel_kkt.argtypes = [DP]; L.br_rel_kkt.restype = C.c_double
     L.br_rho_estimate.argtypes = [C.c_double, DP]; L.br_rho_estimate.restype = C.c_double
     L.br_rho_rule.argtypes = [C.c_double, C.c_double, DP, DP]; L.br_rho_rule.restype = C.c_int
     L.br_tol.argtypes = [C.c_int, C.c_double, C.c_double, DP]
@@ -205,6 +206,36 @@ def test_single_qp_rules_and_batch_check_agree(lib):
         assert (prim == info[1] or math.isnan(prim)) and (dual == info[2] or math.isnan(dual)) and (obj == info[0] or st in (PINF, DINF, NON_CVX))
         seen.add(st)
     assert seen == {SOLVED, GO_ON, PINF, DINF, NON_CVX}
+
+
+def test_rel_kkt_error_is_the_formula(lib):
+    """term_rel_kkt (policy.h ctl_info's and the small-problem path's last expression) against the formula written out in numpy float64, bit for bit:
+    random magnitudes over twenty decades, m == 0 (no primal term), zero normalisations (the 1e-10 guards), zero objective pair, negative gap."""
+    rng = np.random.default_rng(5)
+    tiny = np.float64(1e-10)
+
+    def ref(m, prim, pn, dual, dn, gap, obj, dobj):
+        prim, pn, dual, dn, gap, obj, dobj = (np.float64(v) for v in (prim, pn, dual, dn, gap, obj, dobj))
+        gn = np.maximum(np.abs(obj), np.abs(dobj))
+        first = np.float64(0.0) if m == 0 else prim / (pn + tiny)
+        return np.maximum(np.maximum(first, dual / (dn + tiny)), np.abs(gap) / (gn + tiny))
+
+    cases = []
+    for k in range(200):
+        mag = lambda: float(10.0 ** rng.uniform(-10, 10) * rng.random())
+        obj, dobj = mag() * rng.choice([-1, 1]), mag() * rng.choice([-1, 1])
+        cases.append((int(rng.integers(0, 3)) * 7, mag(), mag(), mag(), mag(), obj - dobj, obj, dobj))
+    cases += [(0, 5.0, 0.0, 1e-4, 1.0, -0.5, -2.0, -1.5), (5, 1e-3, 0.0, 1e-3, 0.0, 0.25, 0.0, 0.0), (5, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0),
+              (0, 0.0, 0.0, 0.0, 0.0, -1e-3, 0.0, 0.0), (3, 1e-7, 2.0, 3e-7, 4.0, -1e-9, 1.0, 1.0 + 1e-9)]
+    which = set()
+    for c in cases:
+        got, want = lib.br_rel_kkt(arr(c)), ref(*c)
+        assert got == want, (c, got, float(want))
+        m, prim, pn, dual, dn, gap, obj, dobj = c
+        terms = [0.0 if m == 0 else prim / (pn + 1e-10), dual / (dn + 1e-10), abs(gap) / (max(abs(obj), abs(dobj)) + 1e-10)]
+        which.add(terms.index(max(terms)))
+    assert which == {0, 1, 2}                                  # each of the three terms decides somewhere
+    assert lib.br_rel_kkt(arr(cases[-4])) == max(1e-3 / 1e-10, 0.25 / 1e-10) and lib.br_rel_kkt(arr(cases[-3])) == 0.0
 
 
 def ref_rho(rho_bar, R):
