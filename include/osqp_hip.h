@@ -309,6 +309,33 @@ OSQPInt osqp_hip_batch_solve_lockstep(OSQPSolver *solver, OSQPInt nbatch, const 
 OSQPInt osqp_hip_batch_solve_lockstep_device(OSQPSolver *solver, OSQPInt nbatch, const OSQPFloat *q_dev, const OSQPFloat *l_dev, const OSQPFloat *u_dev,
                                              OSQPFloat *x_dev, OSQPFloat *y_dev, OSQPFloat *rec_dev, OSQPInt warm_start, void *stream);
 OSQPInt osqp_hip_lockstep_last_record(OSQPSolver *solver, OSQPFloat *rec);
+/* ADJOINT DERIVATIVES ON THE LOCKSTEP ROUTE -- the backward pass of osqp_hip_batch_solve_lockstep: the quantities osqp_hip_batch_adjoint (below) defines,
+ * for a batch that shares this handle's P and A, at any size, OSQP_HIP_LOCKSTEP_WIDTH problems at a time on block vectors.  Per problem: the rows are
+ * classified by the rule given there (caller's units, z = A x on the x passed in; bounds clamped to +-OSQP_INFTY), and the adjoint system is solved by
+ * the recurrence the single-handle PCG route runs (osqp_adjoint_derivative_compute below): the route's own ADMM iteration with alpha = 1, a fixed
+ * rho = 1 / delta_eff on the active rows (delta_eff = max(delta, OSQPHipPolicy::polish_delta_floor)), the other rows free, from a zero start, the PCG
+ * driven to polish_pcg_tol; a problem ends after at least 1 + polish_refine_iter steps when its error is below 1e-13 or two steps in a row gained
+ * less than 10 %, at 60 steps at the latest, and is frozen from then on.  The result is unscaled and its residual max |g - K_a r| / max |g| is taken
+ * on the UNREGULARISED system in the caller's units.  x, dx: nbatch x n; y, dy: nbatch x m (dy NULL = 0); l, u: nbatch x m, NULL = the handle's own.
+ * Outputs as for osqp_hip_batch_adjoint, any of them NULL (skipped); dP / dA in the caller's CSC order (dP: the stored upper triangle).
+ * arec: nbatch x OSQP_HIP_ADJOINT_REC doubles {status, active rows, residual, recurrence steps}; status 0: residual < OSQP_HIP_ADJOINT_TOL; 2: more active
+ * rows than variables (nothing is iterated: steps = 0, residual = inf, outputs zero); 3: residual at or above the threshold (dependent active rows).
+ * The outputs of a problem with a nonzero status are written and hold its last iterate; the other problems are untouched by it.  INDEPENDENCE as on
+ * the forward route: a problem's outputs and record are bit-identical whatever else is in the batch and wherever in it the problem sits.
+ * A reordered handle is served in the caller's numbering.  The handle's iterates, rho, info, solution, launch graphs and history are not touched, nor
+ * are the forward route's workspace and record: the work block is this route's own (allocated by the first call, freed with the handle).  No
+ * per-problem matrices.  Returns OSQP_FUNC_NOT_IMPLEMENTED on a handle with a Woodbury-corrected preconditioner and in the host simulator.
+ * _device: stream semantics of osqp_hip_batch_solve_lockstep_device -- the call returns when the results are there; nbatch == 0 answers applicability.
+ * osqp_hip_lockstep_adjoint_last_record: OSQP_HIP_LOCKSTEP_ADJOINT_LAST_REC doubles {chunks, chunk width, recurrence steps of the slowest problem, PCG
+ * iterations summed over the problems, kernel launches, GPU ms, workspace bytes, reserved}; all zero before the first call. */
+#define OSQP_HIP_LOCKSTEP_ADJOINT_LAST_REC 8
+OSQPInt osqp_hip_batch_adjoint_lockstep(OSQPSolver *solver, OSQPInt nbatch, const OSQPFloat *l, const OSQPFloat *u, const OSQPFloat *x, const OSQPFloat *y,
+                                        const OSQPFloat *dx, const OSQPFloat *dy, OSQPFloat *dP, OSQPFloat *dq, OSQPFloat *dA, OSQPFloat *dl, OSQPFloat *du,
+                                        OSQPFloat *arec);
+OSQPInt osqp_hip_batch_adjoint_lockstep_device(OSQPSolver *solver, OSQPInt nbatch, const OSQPFloat *l_dev, const OSQPFloat *u_dev, const OSQPFloat *x_dev,
+                                               const OSQPFloat *y_dev, const OSQPFloat *dx_dev, const OSQPFloat *dy_dev, OSQPFloat *dP_dev, OSQPFloat *dq_dev,
+                                               OSQPFloat *dA_dev, OSQPFloat *dl_dev, OSQPFloat *du_dev, OSQPFloat *arec_dev, void *stream);
+OSQPInt osqp_hip_lockstep_adjoint_last_record(OSQPSolver *solver, OSQPFloat *rec);
 
 /* ADJOINT DERIVATIVES of a batch of solved QPs -- the backward pass of osqp_hip_batch_solve[_mat]: ONE launch, one workgroup per problem
  * (batch_hip.hip k_batch_adjoint).  For problem b with solution x (n), y (m) and incoming gradients dx = dL/dx (n), dy = dL/dy (m; NULL = 0):

@@ -485,7 +485,25 @@ struct LockstepParams : BatchSettings {
   double *x = nullptr, *y = nullptr, *rec = nullptr;            // the chunk's rows: in UNSCALED warm start (if warm), out UNSCALED solution; [count][kBatchRec]
   const int *pc = nullptr, *pr = nullptr;                       // reordered handle: engine column / row -> the caller's; nullptr: identity
   double *ws = nullptr;         // lockstep_ws_doubles(n, m) doubles
+  double pcg_rel = 0;           // > 0: the recurrence's PCG threshold ||r|| <= pcg_rel ||rhs|| (floor 1e-15, be::set_pcg_tol) in place of the cg_frac rule
 };
+
+// Adjoint derivatives of a chunk on the lockstep route (lockstep_hip.hip lockstep_adjoint_chunk; include/osqp_hip.h osqp_hip_batch_adjoint_lockstep):
+// the recurrence of Engine::run_recurrence per problem on block vectors.  The base carries the matrices, the scalings, the permutations, the shared
+// bounds l0 / u0, the chunk's rows of l / u and the settings the forward's kernels read (alpha = 1, cg_max = kMaxCg, pcg_rel = polish_pcg_tol, rho0 =
+// 1 / delta_eff, eq_factor = 1); q / x / y / rec of the base are not used.
+struct LockstepAdjointParams : LockstepParams {
+  int nzP = 0, nzA = 0;
+  const int *Pi = nullptr, *Pj = nullptr, *Ai = nullptr, *Aj = nullptr;       // Dev's assembly maps: row and column of every stored entry, the engine's CSC order
+  const int *Pmap = nullptr, *Amap = nullptr;                                   // reordered handle: caller's position in P.x / A.x -> the engine's; nullptr: identity
+  const double *sx = nullptr, *sy = nullptr, *gx = nullptr, *gy = nullptr;    // the chunk's rows of x, dx ([count][n]) and y, dy ([count][m]; gy == nullptr: zero), caller's numbering
+  double *dP = nullptr, *dq = nullptr, *dA = nullptr, *dl = nullptr, *du = nullptr, *arec = nullptr;      // the chunk's rows of the outputs, each optional
+  int min_steps = 1, max_steps = 60; double gain = 0.9;                        // RecurrenceRule{true, 0.9, 60} with 1 + polish_refine_iter
+};
+// doubles of the adjoint's work block: the forward's set, then x, dx, r_x (n), y, dy, r_y (m) and the row codes (m ints)
+inline size_t lockstep_adjoint_ws_doubles(int n, int m) {
+  return lockstep_ws_doubles(n, m) + (size_t)kLsW * (3 * (size_t)n + 3 * (size_t)m + ((size_t)m + 1) / 2) + 64;
+}
 
 namespace be {
 
@@ -493,6 +511,9 @@ namespace be {
 // start to finish, on `stream` (nullptr: d.stream); synchronises with that stream.  stat[4]: ADMM iterations of the slowest problem, PCG iterations
 // summed over the problems, kernel launches, GPU ms.
 int lockstep_chunk(Dev &d, const LockstepParams &p, void *stream, double *stat) __attribute__((weak));
+// The backward pass of such a chunk: transposes in, classification, the recurrence, residual, gradients, transposes out; returns when the chunk's
+// results are there.  stat[4]: recurrence steps of the slowest problem, PCG iterations summed, kernel launches, GPU ms.  Weak as well.
+int lockstep_adjoint_chunk(Dev &d, const LockstepAdjointParams &p, void *stream, double *stat) __attribute__((weak));
 
 // Weak, like batch_adjoint: the host simulator has no such kernels and the driver answers OSQP_FUNC_NOT_IMPLEMENTED where the symbols are absent.
 // adjoint_load: classification of the rows (code, rec[0]) and the recurrence's data -- Dev::q = c D dx, l = u = z = -E dy on the active rows (free

@@ -162,6 +162,10 @@ void Engine::free_all() {
   batch_order_.clear();
   if (ckpt_) { be::dfree(d_, ckpt_); ckpt_ = nullptr; }
   if (lsw_) { be::dfree(d_, lsw_); lsw_ = nullptr; }
+  if (lsaw_) { be::dfree(d_, lsaw_); lsaw_ = nullptr; }
+  if (lsabuf_) { be::dfree(d_, lsabuf_); lsabuf_ = nullptr; lsabuf_cap_ = 0; }
+  if (d_pvmap_) { be::dfree(d_, d_pvmap_); d_pvmap_ = nullptr; }
+  if (d_avmap_) { be::dfree(d_, d_avmap_); d_avmap_ = nullptr; }
   free_batch_direct(); free_batch_spectral(); free_batch_wave();
   if (d_.f1.va) {                                                // (these point into the F1 arena, freed as one block below)
     d_.Minv = d_.xs = d_.p = d_.r = d_.s = d_.rho = d_.f1.pval = nullptr; d_.f1.pcol = d_.f1.prp = nullptr; d_.f1.cptr = nullptr;
@@ -946,12 +950,10 @@ int Engine::run_recurrence(const RecurrenceRule &rule, double *res) {
     exec_chunk_sync(1, kMaxCg, true, 1, res, flags);
     steps = s + 1;
     // residuals of the reduced KKT system: Aa x - ba (active rows) and P x + q + Aa' ya, in the scaled space
-    const double err = rhs_norm ? std::max(res[R_PRI_S], res[R_DUA_S]) / (std::max(res[R_QN_S], res[R_Z_S]) + 1e-30)
+    const double err = rhs_norm ? recurrence_err_rhs(res[R_PRI_S], res[R_DUA_S], res[R_QN_S], res[R_Z_S])
                                 : std::max(res[R_PRI_S] / (std::max(res[R_AX_S], res[R_Z_S]) + 1e-30),
                                            res[R_DUA_S] / (std::max(std::max(res[R_ATY_S], res[R_PX_S]), res[R_QN_S]) + 1e-30));
-    if (!(err < gain * best)) worse++; else worse = 0;
-    best = std::min(best, err);
-    if (s + 1 >= min_steps && (err < 1e-13 || worse >= 2)) break;
+    if (recurrence_ends(err, gain, steps, min_steps, kRecurrenceMaxSteps, &best, &worse)) break;      // (term_rules.h: the lockstep adjoint's rule too)
   }
   return steps;
 }

@@ -63,6 +63,13 @@ class Engine {
   int batch_solve_lockstep(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm);
   int batch_solve_lockstep_device(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream);
   int lockstep_last_record(double *rec) const;
+  // The backward pass of such a batch (include/osqp_hip.h osqp_hip_batch_adjoint_lockstep; lockstep_hip.hip lockstep_adjoint_chunk): the adjoint system of
+  // every problem by the recurrence polish runs, on block vectors, in a work block of its own.  Any output may be nullptr.
+  int batch_adjoint_lockstep(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
+                             double *dP, double *dq, double *dA, double *dl, double *du, double *arec);
+  int batch_adjoint_lockstep_device(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
+                                    double *dP, double *dq, double *dA, double *dl, double *du, double *arec, void *stream);
+  int lockstep_adjoint_last_record(double *rec) const;
   // Adjoint derivatives (include/osqp_hip.h osqp_hip_batch_adjoint; batch_hip.hip k_batch_adjoint): one launch for the batch.  Host arrays, or -- _device --
   // device arrays and a caller's stream with the semantics of batch_solve_device.  Px / Ax / l / u: nullptr = this solver's own values for every problem.
   int batch_adjoint(int nbatch, const double *Px, const double *Ax, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
@@ -130,6 +137,13 @@ class Engine {
   double *lsw_ = nullptr;                             // workspace of one lockstep chunk (lockstep_ws_doubles(n, m)), allocated on first use
   double ls_rec_[OSQP_HIP_LOCKSTEP_LAST_REC] = {0, 0, 0, 0, 0, 0, 0, 0};      // record of the last lockstep call (osqp_hip_lockstep_last_record)
   int run_lockstep(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream);
+  double *lsaw_ = nullptr;                            // work block of one lockstep adjoint chunk (lockstep_adjoint_ws_doubles(n, m)), allocated on first use
+  double *lsabuf_ = nullptr; size_t lsabuf_cap_ = 0;  // device scratch of batch_adjoint_lockstep (host-array entry point), kept across calls
+  int *d_pvmap_ = nullptr, *d_avmap_ = nullptr;       // device copies of PvalMap_ / AvalMap_ (reordered handle), uploaded by the first lockstep adjoint
+  double lsa_rec_[OSQP_HIP_LOCKSTEP_ADJOINT_LAST_REC] = {0, 0, 0, 0, 0, 0, 0, 0};     // record of the last lockstep adjoint call (osqp_hip_lockstep_adjoint_last_record)
+  bool lockstep_adjoint_applies();
+  int run_lockstep_adjoint(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
+                           double *dP, double *dq, double *dA, double *dl, double *du, double *arec, void *stream);
   // what the four batch entry points begin with, and the host staging of the two that take host arrays (engine_api.cpp)
   bool batch_applies();                               // the workgroup route: the QP fits one workgroup's LDS and the handle is not reordered
   bool batch_applies_prepared();

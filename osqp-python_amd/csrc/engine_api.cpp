@@ -951,6 +951,92 @@ int Engine::lockstep_last_record(double *rec) const {
   return OSQP_NO_ERROR;
 }
 
+// ---- the backward pass of a lockstep batch (lockstep_hip.hip lockstep_adjoint_chunk): chunk after chunk like run_lockstep.  Every array is a DEVICE
+// array in the caller's numbering (dP / dA: the caller's CSC order).  The recurrence's settings are those of Engine::run_recurrence as the single-QP
+// adjoint calls it: rho_bar = 1 / delta_eff on the active rows with equality factor 1, alpha = 1, PCG to polish_pcg_tol within kMaxCg, progress rule
+// {rhs_norm, 0.9, 60} after at least 1 + polish_refine_iter steps.  The work block (lsaw_) is this route's own: the handle's iterates, rho, info,
+// solution, graphs and history -- and the forward route's workspace and record -- are not touched.
+bool Engine::lockstep_adjoint_applies() { return be::lockstep_adjoint_chunk && be::device_assembly() && be::device_vec_updates() && !d_.wb.on; }
+
+int Engine::run_lockstep_adjoint(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
+                                 double *dP, double *dq, double *dA, double *dl, double *du, double *arec, void *stream) {
+  const size_t need = lockstep_adjoint_ws_doubles(n, m);
+  const int nzP = d_.nzP, nzA = d_.nzA;
+  bool fresh = false;
+  if (!lsaw_) { lsaw_ = dev_vec<double>(d_, need); fresh = true; }
+  if (reordered_ && !d_pvmap_ && nzP > 0) { d_pvmap_ = dev_vec<int>(d_, nzP); be::h2d(d_, d_pvmap_, PvalMap_.data(), sizeof(int) * nzP); fresh = true; }
+  if (reordered_ && !d_avmap_ && nzA > 0) { d_avmap_ = dev_vec<int>(d_, nzA); be::h2d(d_, d_avmap_, AvalMap_.data(), sizeof(int) * nzA); fresh = true; }
+  if (fresh) be::sync(d_);
+  LockstepAdjointParams p;
+  fill_batch_settings(p, 0);
+  const double de = std::max(settings.delta, pol_.polish_delta_floor);
+  p.alpha = 1.0; p.rho0 = clamp_rho(1.0 / de); p.eq_factor = 1.0; p.cg_max = kMaxCg; p.pcg_rel = pol_.polish_pcg_tol;
+  p.min_steps = 1 + std::max(0, (int)settings.polish_refine_iter); p.max_steps = 60; p.gain = 0.9;
+  p.n = n; p.m = m; p.A = d_.A; p.B = d_.B; p.D = d_.D; p.Dinv = d_.Dinv; p.E = d_.E; p.Einv = d_.Einv;
+  p.l0 = d_.lraw; p.u0 = d_.uraw; p.pc = reordered_ ? d_pc_ : nullptr; p.pr = reordered_ ? d_pr_ : nullptr; p.ws = lsaw_;
+  p.nzP = nzP; p.nzA = nzA; p.Pi = d_.Pi; p.Pj = d_.Pj; p.Ai = d_.Ai; p.Aj = d_.Aj; p.Pmap = reordered_ ? d_pvmap_ : nullptr; p.Amap = reordered_ ? d_avmap_ : nullptr;
+  double tot[4] = {0, 0, 0, 0};
+  int chunks = 0;
+  auto at = [](auto *a, size_t off) { return a ? a + off : nullptr; };
+  for (int b0 = 0; b0 < nbatch; b0 += kLsW, chunks++) {
+    const size_t b = (size_t)b0;
+    p.count = std::min(kLsW, nbatch - b0);
+    p.l = at(l, b * m); p.u = at(u, b * m); p.sx = x + b * n; p.sy = at(y, b * m); p.gx = dx + b * n; p.gy = at(dy, b * m);
+    p.dP = at(dP, b * nzP); p.dq = at(dq, b * n); p.dA = at(dA, b * nzA); p.dl = at(dl, b * m); p.du = at(du, b * m); p.arec = at(arec, b * kAdjointRec);
+    double st[4] = {0, 0, 0, 0};
+    const int err = be::lockstep_adjoint_chunk(d_, p, stream, st);
+    if (err) return err;
+    tot[0] = std::max(tot[0], st[0]); tot[1] += st[1]; tot[2] += st[2]; tot[3] += st[3];
+  }
+  const double r[OSQP_HIP_LOCKSTEP_ADJOINT_LAST_REC] = {(double)chunks, (double)kLsW, tot[0], tot[1], tot[2], tot[3], (double)(need * sizeof(double)), 0.0};
+  std::copy(r, r + OSQP_HIP_LOCKSTEP_ADJOINT_LAST_REC, lsa_rec_);
+  return OSQP_NO_ERROR;
+}
+
+int Engine::batch_adjoint_lockstep(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
+                                   double *dP, double *dq, double *dA, double *dl, double *du, double *arec) {
+  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (nbatch <= 0 || !x || (!y && m > 0) || !dx) return OSQP_DATA_VALIDATION_ERROR;
+  be::activate(d_);
+  if (!lockstep_adjoint_applies()) return OSQP_FUNC_NOT_IMPLEMENTED;
+  be::ext_wait(d_);
+  const size_t nb = (size_t)nbatch, N = nb * n, M = nb * m, NP = nb * (size_t)d_.nzP, NA = nb * (size_t)d_.nzA;
+  // one device scratch block, kept for the next call: [l | u | x | y | dx | dy | dP | dq | dA | dl | du | arec]
+  const size_t need = 3 * N + 6 * M + NP + NA + nb * kAdjointRec;
+  if (need > lsabuf_cap_) { if (lsabuf_) be::dfree(d_, lsabuf_); lsabuf_cap_ = 0; lsabuf_ = dev_vec<double>(d_, need); lsabuf_cap_ = need; }
+  double *d_l = lsabuf_, *d_u = d_l + M, *d_x = d_u + M, *d_y = d_x + N, *d_dx = d_y + M, *d_dy = d_dx + N;
+  double *o_dP = d_dy + M, *o_dq = o_dP + NP, *o_dA = o_dq + N, *o_dl = o_dA + NA, *o_du = o_dl + M, *o_rec = o_du + M;
+  auto up = [&](double *dst, const double *src, size_t cnt) { if (src && cnt) be::h2d(d_, dst, src, sizeof(double) * cnt); };
+  up(d_l, l, M); up(d_u, u, M); up(d_x, x, N); up(d_y, y, M); up(d_dx, dx, N); up(d_dy, dy, M);
+  be::sync(d_);
+  const int err = run_lockstep_adjoint(nbatch, l ? d_l : nullptr, u ? d_u : nullptr, d_x, d_y, d_dx, dy ? d_dy : nullptr, dP ? o_dP : nullptr, dq ? o_dq : nullptr,
+                                       dA ? o_dA : nullptr, dl ? o_dl : nullptr, du ? o_du : nullptr, arec ? o_rec : nullptr, nullptr);
+  if (err) return err;
+  auto down = [&](double *dst, const double *src, size_t cnt) { if (dst && cnt) be::d2h(d_, dst, src, sizeof(double) * cnt); };
+  down(dP, o_dP, NP); down(dq, o_dq, N); down(dA, o_dA, NA); down(dl, o_dl, M); down(du, o_du, M); down(arec, o_rec, nb * kAdjointRec);
+  return OSQP_NO_ERROR;
+}
+
+int Engine::batch_adjoint_lockstep_device(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
+                                          double *dP, double *dq, double *dA, double *dl, double *du, double *arec, void *stream) {
+  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (nbatch < 0) return OSQP_DATA_VALIDATION_ERROR;
+  be::activate(d_);
+  if (!lockstep_adjoint_applies()) return OSQP_FUNC_NOT_IMPLEMENTED;
+  if (nbatch == 0) return OSQP_NO_ERROR;              // (the applicability query, as osqp_hip_batch_solve_lockstep_device answers it)
+  if (!x || (!y && m > 0) || !dx) return OSQP_DATA_VALIDATION_ERROR;
+  be::ext_wait(d_);
+  be::sync(d_);                                       // the solver's own stream first: pending updates of the resident l / u, the matrices
+  return run_lockstep_adjoint(nbatch, l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec, stream);
+}
+
+int Engine::lockstep_adjoint_last_record(double *rec) const {
+  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (!rec) return OSQP_DATA_VALIDATION_ERROR;
+  std::copy(lsa_rec_, lsa_rec_ + OSQP_HIP_LOCKSTEP_ADJOINT_LAST_REC, rec);
+  return OSQP_NO_ERROR;
+}
+
 // ------------------------------------------------------------------------------------------------ adjoint derivatives
 // The backward pass of the batch path (batch_hip.hip k_batch_adjoint).  A problem is eligible when the forward's direct variant holds it (banded factor
 // under the engine's ordering: prepare_batch_direct) and the adjoint kernel's own LDS fits; the batch entry points answer OSQP_FUNC_NOT_IMPLEMENTED for

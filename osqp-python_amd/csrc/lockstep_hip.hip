@@ -21,6 +21,8 @@
 //               the host reads one small word block per termination check.
 // Transposes (LDS tiles, coalesced on both sides) move a chunk between the API's [nbatch][n] row-major arrays and the block vectors; they apply
 // k_batch_admm's load / store scaling and, for a handle that works on a permuted copy, gather / scatter through the permutations.
+// The BACKWARD pass of a chunk (osqp_hip_batch_adjoint_lockstep; lockstep_adjoint_chunk below): the adjoint system of every problem by the recurrence polish
+// and the single-QP adjoint run, which is this file's iteration with alpha = 1 and a fixed rho -- see "adjoint derivatives of a chunk".
 #include "hip_common.h"
 
 namespace osqp_hip {
@@ -38,8 +40,8 @@ enum LsSlot {
   PS_COUNT = PS_N0 + 17
 };
 static_assert(PS_COUNT <= kLsSlots, "lockstep_ws_doubles reserves kLsSlots partial slots");
-enum LsScal { SC_RHOBAR = 0, SC_EQF, SC_EPSCG, SC_EPSPREV, SC_RZ, SC_RN, SC_TOL, SC_ALPHA, SC_BETA, SC_COUNT };
-enum LsInt { IW_DONE = 0, IW_STATUS, IW_RHOUPD, IW_PCG, IW_RELRULE, IW_CGON, IW_RHOCH, IW_COUNT };
+enum LsScal { SC_RHOBAR = 0, SC_EQF, SC_EPSCG, SC_EPSPREV, SC_RZ, SC_RN, SC_TOL, SC_ALPHA, SC_BETA, SC_BEST /* adjoint: smallest error so far */, SC_NACT /* adjoint: active rows */, SC_COUNT };
+enum LsInt { IW_DONE = 0, IW_STATUS, IW_RHOUPD, IW_PCG, IW_RELRULE, IW_CGON, IW_RHOCH, IW_STEPS /* adjoint: recurrence steps */, IW_WORSE /* adjoint: steps in a row without progress */, IW_COUNT };
 enum LsWord { WD_CGANY = 0, WD_LIVE, WD_RHOANY, WD_PCGSUM, WD_CGIT /* PCG iterations of the current ADMM iteration that some problem needed */, WD_COUNT };
 static_assert(SC_COUNT <= kLsScal && IW_COUNT + 1 <= kLsInt, "lockstep_ws_doubles reserves kLsScal / kLsInt rows");
 
@@ -347,7 +349,8 @@ __global__ __launch_bounds__(256) void k_ls_cginit(LsK k) {
   const double bn = ls_fold<true>(k.w.part, G, PS_BN, lds), rn = ls_fold<true>(k.w.part, G, PS_RN, lds), rz = ls_fold<false>(k.w.part, G, PS_RZ, lds);
   if (threadIdx.x >= 64) return;
   const double eps_cg = k.w.sc[SC_EPSCG * W + lane];
-  const double tol = k.w.iw[IW_RELRULE * W + lane] ? fmax(0.1 * bn, 1e-13) : fmax(1e-14 * bn, eps_cg);
+  const double tol = k.P.pcg_rel > 0.0 ? fmax(k.P.pcg_rel * bn, 1e-15)                       // the recurrence's own threshold (be::set_pcg_tol as Engine::run_recurrence calls it)
+                                      : (k.w.iw[IW_RELRULE * W + lane] ? fmax(0.1 * bn, 1e-13) : fmax(1e-14 * bn, eps_cg));
   const int on = !k.w.iw[IW_DONE * W + lane] && k.P.cg_max > 0 && rn > tol;
   k.w.sc[SC_RZ * W + lane] = rz; k.w.sc[SC_RN * W + lane] = rn; k.w.sc[SC_TOL * W + lane] = tol;
   k.w.iw[IW_CGON * W + lane] = on;
@@ -540,6 +543,237 @@ __global__ __launch_bounds__(256) void k_ls_store_m(LsK k) {
   }
   ls_tile_out(P.y, P.m, i0, P.count, P.pr, tile);
 }
+// ---------------------------------------------------------------------------------------------------------------- adjoint derivatives of a chunk
+// The backward pass (include/osqp_hip.h osqp_hip_batch_adjoint_lockstep): per problem the adjoint system  [P, A_a'; A_a, 0] [r_x; r_a] = -[dx; dy_a]  is the
+// KKT system of  min 1/2 r'Pr + dx'r  s.t.  A_a r = -dy_a  and is solved by the recurrence of Engine::run_recurrence -- THIS route's ADMM iteration
+// (k_ls_rhs, the PCG, k_ls_upd, k_ls_resm / k_ls_resn) with alpha = 1, rho_bar = 1 / delta_eff on the active rows (equalities at -E dy), the other rows
+// free, q~ = c D dx, a zero start -- as adjoint_hip.hip does around the single-QP recurrence.  What is new here surrounds that iteration: the transposes
+// in with the classification (step_rules.h adjoint_active: the text k_batch_adjoint and EAdjClass call), the progress rule per problem (term_rules.h
+// recurrence_ends: Engine::run_recurrence's), the unscaling and the residual of the unregularised system, the transposes out and the gradients at the
+// stored entries.  Extra block vectors: the unscaled x, dx, r_x (n) and y, dy, r_y (m) and the row codes (ints, packed like iw).
+struct LsAdjWs { double *ax, *gdx, *rx, *ay, *gdy, *ry; int *code; };
+struct LsAK { LockstepAdjointParams P; LsWs w; LsAdjWs a; };
+enum LsAdjSlot { AS_ACT = PS_BN /* sum: active rows (before the first k_ls_rhs) */, AS_RM = PS_M0 /* max, after the last step: */, AS_GM, AS_RN, AS_GN };
+
+// x (kept), x~ = Dinv x into p (the classification's operand; k_ls_rhs overwrites it), q~ = c D dx, dx (kept), the zero start
+__global__ __launch_bounds__(256) void k_ls_adj_load_n(LsAK k) {
+  __shared__ double tile[64][65];
+  const LockstepAdjointParams &P = k.P;
+  const int lane = ls_lane(), wv = ls_wave(), j0 = blockIdx.x * 64;
+  ls_tile_in(P.sx, P.n, j0, P.count, P.pc, tile);                              // (zero for lanes >= count)
+  for (int jl = wv; jl < 64 && j0 + jl < P.n; jl += 4) {
+    const int j = j0 + jl;
+    const double xv = tile[lane][jl];
+    k.a.ax[IX(j)] = xv; k.w.p[IX(j)] = in_x(xv, P.Dinv[j]);
+    k.w.x[IX(j)] = 0.0; k.w.xs[IX(j)] = 0.0; k.w.dx[IX(j)] = 0.0;
+  }
+  __syncthreads();
+  ls_tile_in(P.gx, P.n, j0, P.count, P.pc, tile);
+  for (int jl = wv; jl < 64 && j0 + jl < P.n; jl += 4) {
+    const int j = j0 + jl;
+    const double gv = tile[lane][jl];
+    k.a.gdx[IX(j)] = gv; k.w.q[IX(j)] = in_q(P.c, P.D[j], gv);
+  }
+}
+// y, dy (kept) and the caller's bounds (clamped, unscaled: k_ls_adj_class turns them into the recurrence's)
+__global__ __launch_bounds__(256) void k_ls_adj_load_m(LsAK k) {
+  __shared__ double tile[64][65];
+  const LockstepAdjointParams &P = k.P;
+  const int lane = ls_lane(), wv = ls_wave(), i0 = blockIdx.x * 64;
+  const bool mine = lane < P.count;
+  ls_tile_in(P.sy, P.m, i0, P.count, P.pr, tile);
+  for (int il = wv; il < 64 && i0 + il < P.m; il += 4) k.a.ay[IX(i0 + il)] = tile[lane][il];
+  __syncthreads();
+  if (P.gy) ls_tile_in(P.gy, P.m, i0, P.count, P.pr, tile);
+  for (int il = wv; il < 64 && i0 + il < P.m; il += 4) k.a.gdy[IX(i0 + il)] = P.gy ? tile[lane][il] : 0.0;
+  __syncthreads();
+  if (P.l) ls_tile_in(P.l, P.m, i0, P.count, P.pr, tile);
+  for (int il = wv; il < 64 && i0 + il < P.m; il += 4) {
+    const int i = i0 + il;
+    k.w.l[IX(i)] = mine ? clamp_lower(P.l ? tile[lane][il] : P.l0[i]) : -OSQP_INFTY;
+  }
+  __syncthreads();
+  if (P.u) ls_tile_in(P.u, P.m, i0, P.count, P.pr, tile);
+  for (int il = wv; il < 64 && i0 + il < P.m; il += 4) {
+    const int i = i0 + il;
+    k.w.u[IX(i)] = mine ? clamp_upper(P.u ? tile[lane][il] : P.u0[i]) : OSQP_INFTY;
+  }
+}
+// z = Einv (A x~) in the caller's units, the row's code, the recurrence's bounds (active: l = u = z = -E dy; the others free) and zero start
+struct FAdjClass {
+  const LsWs &w; const LsAdjWs &a; const double *E, *Einv; int has_dy, lane;
+  double cnt = 0;
+  __device__ __forceinline__ void begin(int) {}
+  __device__ __forceinline__ void load(int c, double (&g)[1]) const { g[0] = w.p[IX(c)]; }
+  __device__ __forceinline__ void fma(int, double v, const double (&g)[1], double (&acc)[1]) const { acc[0] += v * g[0]; }
+  __device__ __forceinline__ void row(int i, const double (&acc)[1]) {
+    const double zi = Einv[i] * acc[0];
+    const RowActive act = adjoint_active(zi, w.l[IX(i)], w.u[IX(i)], a.ay[IX(i)]);
+    const int kc = act.low ? 1 : (act.upp ? 2 : 0);
+    const double b = (kc && has_dy) ? -(E[i] * a.gdy[IX(i)]) : 0.0;
+    a.code[IX(i)] = kc;
+    w.l[IX(i)] = kc ? b : -OSQP_INFTY; w.u[IX(i)] = kc ? b : OSQP_INFTY;
+    w.z[IX(i)] = b; w.zt[IX(i)] = 0.0; w.y[IX(i)] = 0.0; w.dy[IX(i)] = 0.0;
+    cnt += kc ? 1.0 : 0.0;
+  }
+};
+__global__ __launch_bounds__(256) void k_ls_adj_class(LsAK k) {
+  __shared__ double lds[256];
+  FAdjClass f{k.w, k.a, k.P.E, k.P.Einv, k.P.gy != nullptr, ls_lane()};
+  ls_rows<1, 1>(k.P.A, f);
+  const double vs[1] = {f.cnt};
+  ls_put<0, 1>(k.w.part, AS_ACT, vs, vs, lds);
+}
+// the chunk's per-problem state: rho_bar = 1 / delta_eff with equality factor 1; a problem with more active rows than variables (status 2) and the
+// lanes >= count are finished before the first step
+__global__ __launch_bounds__(256) void k_ls_adj_init(LsAK k) {
+  __shared__ double lds[256];
+  const int lane = ls_lane();
+  const double nact = k.P.m > 0 ? ls_fold<false>(k.w.part, k.w.G, AS_ACT, lds) : 0.0;
+  if (threadIdx.x >= 64) return;
+  double *sc = k.w.sc; int *iw = k.w.iw;
+  const bool mine = lane < k.P.count, singular = nact > (double)k.P.n;
+  sc[SC_RHOBAR * W + lane] = k.P.rho0; sc[SC_EQF * W + lane] = k.P.eq_factor; sc[SC_EPSCG * W + lane] = 0.0; sc[SC_EPSPREV * W + lane] = INFINITY;
+  sc[SC_BEST * W + lane] = INFINITY; sc[SC_NACT * W + lane] = nact;
+  iw[IW_DONE * W + lane] = !mine || singular; iw[IW_STATUS * W + lane] = (mine && singular) ? 2 : 0; iw[IW_RHOUPD * W + lane] = 0; iw[IW_PCG * W + lane] = 0;
+  iw[IW_RELRULE * W + lane] = 0; iw[IW_CGON * W + lane] = 0; iw[IW_RHOCH * W + lane] = 1; iw[IW_STEPS * W + lane] = 0; iw[IW_WORSE * W + lane] = 0;
+  const unsigned long long live = __ballot(mine && !singular);
+  if (threadIdx.x == 0) { k.w.word[WD_CGANY] = 0; k.w.word[WD_LIVE] = __popcll(live); k.w.word[WD_RHOANY] = 1; k.w.word[WD_PCGSUM] = 0; k.w.word[WD_CGIT] = 0; }
+}
+// after every step: the progress rule per problem (term_rules.h recurrence_ends on the slots k_ls_resm / k_ls_resn have put); a problem that ends is frozen
+__global__ __launch_bounds__(256) void k_ls_adj_decide(LsAK k) {
+  __shared__ double lds[256];
+  const int lane = ls_lane(), G = k.w.G;
+  const bool has_m = k.P.m > 0;                                                 // (uniform: so are the folds' barriers)
+  const double pri_s = has_m ? ls_fold<true>(k.w.part, G, PS_M0 + 3, lds) : 0.0, z_s = has_m ? ls_fold<true>(k.w.part, G, PS_M0 + 5, lds) : 0.0;
+  const double dua_s = ls_fold<true>(k.w.part, G, PS_N0 + 3, lds), qn_s = ls_fold<true>(k.w.part, G, PS_N0 + 8, lds);
+  if (threadIdx.x >= 64) return;
+  double *sc = k.w.sc; int *iw = k.w.iw;
+  if (!iw[IW_DONE * W + lane]) {
+    const int steps = iw[IW_STEPS * W + lane] + 1;
+    double best = sc[SC_BEST * W + lane]; int worse = iw[IW_WORSE * W + lane];
+    const bool end = recurrence_ends(recurrence_err_rhs(pri_s, dua_s, qn_s, z_s), k.P.gain, steps, k.P.min_steps, k.P.max_steps, &best, &worse);
+    iw[IW_STEPS * W + lane] = steps; sc[SC_BEST * W + lane] = best; iw[IW_WORSE * W + lane] = worse;
+    if (end) iw[IW_DONE * W + lane] = 1;
+  }
+  iw[IW_RHOCH * W + lane] = 0;
+  const unsigned long long live = __ballot(!iw[IW_DONE * W + lane]);
+  int pcg = iw[IW_PCG * W + lane];                      // (statistics only)
+  for (int o = 32; o > 0; o >>= 1) pcg += __shfl_xor(pcg, o);
+  if (threadIdx.x == 0) { k.w.word[WD_LIVE] = __popcll(live); k.w.word[WD_RHOANY] = 0; k.w.word[WD_PCGSUM] = pcg; }
+}
+// r_x = D x,  r_y = cinv E y on the active rows and exactly 0 elsewhere (y itself too: the residual's A' multiplies it)
+__global__ __launch_bounds__(256) void k_ls_adj_unscale(LsAK k) {
+  const size_t nt = (size_t)k.P.n * 64, mt = (size_t)k.P.m * 64, stride = (size_t)gridDim.x * 256;
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < nt; e += stride) k.a.rx[e] = k.P.D[e >> 6] * k.w.x[e];
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < mt; e += stride) {
+    const double ys = k.a.code[e] ? k.w.y[e] : 0.0;
+    k.w.y[e] = ys; k.a.ry[e] = k.P.cinv * k.P.E[e >> 6] * ys;
+  }
+}
+// rows n .. n + active of g - K_a r:  -dy_i - (A r_x)_i  on the active rows (adjoint_hip.hip EAdjResM)
+struct FAdjResM {
+  const LsWs &w; const LsAdjWs &a; const double *Einv; int lane;
+  double rm = 0, gm = 0;
+  __device__ __forceinline__ void begin(int) {}
+  __device__ __forceinline__ void load(int c, double (&g)[1]) const { g[0] = w.x[IX(c)]; }
+  __device__ __forceinline__ void fma(int, double v, const double (&g)[1], double (&acc)[1]) const { acc[0] += v * g[0]; }
+  __device__ __forceinline__ void row(int i, const double (&acc)[1]) {
+    if (!a.code[IX(i)]) return;
+    const double dyi = a.gdy[IX(i)];
+    rm = nanmax(rm, fabs(dyi + Einv[i] * acc[0])); gm = nanmax(gm, fabs(dyi));
+  }
+};
+__global__ __launch_bounds__(256) void k_ls_adj_resm(LsAK k) {
+  __shared__ double lds[2 * 256];
+  FAdjResM f{k.w, k.a, k.P.Einv, ls_lane()};
+  ls_rows<1, 1>(k.P.A, f);
+  const double vm[2] = {f.rm, f.gm};
+  ls_put<2, 0>(k.w.part, AS_RM, vm, vm, lds);
+}
+// rows 0 .. n:  -dx_j - (P r_x + A_a' r_a)_j;  row j of B [x~; y~] is  c D_j (P r_x + A' r_y)_j + sigma x~_j  (adjoint_hip.hip EAdjResN)
+struct FAdjResN {
+  const LsWs &w; const LsAdjWs &a; const double *Dinv; double sigma, cinv; int n, lane;
+  double rn = 0, gn = 0;
+  __device__ __forceinline__ void begin(int) {}
+  __device__ __forceinline__ void load(int c, double (&g)[1]) const { g[0] = c < n ? w.x[IX(c)] : w.y[IX(c - n)]; }
+  __device__ __forceinline__ void fma(int c, double v, const double (&g)[1], double (&acc)[2]) const {
+    const double p = v * g[0]; const bool pn = c < n;                          // (selects, not indexed accumulators)
+    acc[0] += pn ? p : 0.0; acc[1] += pn ? 0.0 : p;
+  }
+  __device__ __forceinline__ void row(int j, const double (&acc)[2]) {
+    const double kr = cinv * Dinv[j] * ((acc[0] - sigma * w.x[IX(j)]) + acc[1]), dxj = a.gdx[IX(j)];
+    rn = nanmax(rn, fabs(dxj + kr)); gn = nanmax(gn, fabs(dxj));
+  }
+};
+__global__ __launch_bounds__(256) void k_ls_adj_resn(LsAK k) {
+  __shared__ double lds[2 * 256];
+  FAdjResN f{k.w, k.a, k.P.Dinv, k.P.sigma, k.P.cinv, k.P.n, ls_lane()};
+  ls_rows<1, 2>(k.P.B, f);
+  const double vm[2] = {f.rn, f.gn};
+  ls_put<2, 0>(k.w.part, AS_RN, vm, vm, lds);
+}
+// the record: {status, active rows, residual max |g - K_a r| / max |g|, recurrence steps}
+__global__ __launch_bounds__(256) void k_ls_adj_final(LsAK k) {
+  __shared__ double lds[256];
+  const int lane = ls_lane(), G = k.w.G;
+  const bool has_m = k.P.m > 0;
+  const double rm = has_m ? ls_fold<true>(k.w.part, G, AS_RM, lds) : 0.0, gm = has_m ? ls_fold<true>(k.w.part, G, AS_GM, lds) : 0.0;
+  const double rn = ls_fold<true>(k.w.part, G, AS_RN, lds), gn = ls_fold<true>(k.w.part, G, AS_GN, lds);
+  if (threadIdx.x >= 64 || lane >= k.P.count || !k.P.arec) return;
+  const bool singular = k.w.iw[IW_STATUS * W + lane] == 2;
+  const double r = nanmax(rm, rn), g = nanmax(gm, gn);
+  const double resid = singular ? INFINITY : (g > 0.0 ? r / g : (r > 0.0 ? INFINITY : 0.0));
+  double *rc = k.P.arec + (size_t)lane * kAdjointRec;
+  rc[0] = singular ? 2.0 : (resid < kAdjointTol ? 0.0 : 3.0); rc[1] = k.w.sc[SC_NACT * W + lane]; rc[2] = resid; rc[3] = k.w.iw[IW_STEPS * W + lane];
+}
+// dq = r_x;  dl = -r_y on the lower-active rows, du = -r_y on the upper-active ones, 0 elsewhere
+__global__ __launch_bounds__(256) void k_ls_adj_out_n(LsAK k) {
+  __shared__ double tile[64][65];
+  const int lane = ls_lane(), wv = ls_wave(), j0 = blockIdx.x * 64;
+  for (int jl = wv; jl < 64 && j0 + jl < k.P.n; jl += 4) tile[lane][jl] = k.a.rx[IX(j0 + jl)];
+  ls_tile_out(k.P.dq, k.P.n, j0, k.P.count, k.P.pc, tile);
+}
+__global__ __launch_bounds__(256) void k_ls_adj_out_m(LsAK k) {
+  __shared__ double tile[64][65];
+  const int lane = ls_lane(), wv = ls_wave(), i0 = blockIdx.x * 64;
+  for (int side = 1; side <= 2; side++) {
+    double *dst = side == 1 ? k.P.dl : k.P.du;
+    if (!dst) continue;                                                         // (uniform)
+    for (int il = wv; il < 64 && i0 + il < k.P.m; il += 4) {
+      const size_t e = IX(i0 + il);
+      tile[lane][il] = k.a.code[e] == side ? -k.a.ry[e] : 0.0;
+    }
+    ls_tile_out(dst, k.P.m, i0, k.P.count, k.P.pr, tile);
+  }
+}
+// dP_ij = (r_x,i x_j + r_x,j x_i) / 2 (SYM) and dA_ij = y_i r_x,j + r_y,i x_j at the stored entries, [count][nnz] row-major in the CALLER's CSC order.  A workgroup
+// takes 64 of the caller's entries, a wave 16 of them: the entry's position in the engine's arrays (through the value map of a reordered handle) and its
+// (i, j) are wave-uniform, each operand is one 512-byte line, four entries are in flight; the tile goes out coalesced along the entries.  One writer each.
+template <bool SYM>
+__global__ __launch_bounds__(256) void k_ls_adj_grad(LsAK k) {
+  __shared__ double tile[64][65];
+  const LockstepAdjointParams &P = k.P;
+  const int nz = SYM ? P.nzP : P.nzA, lane = ls_lane(), wv = ls_wave(), e0 = blockIdx.x * 64;
+  const int *__restrict__ ri = SYM ? P.Pi : P.Ai, *__restrict__ cj = SYM ? P.Pj : P.Aj, *__restrict__ map = SYM ? P.Pmap : P.Amap;
+  const double *ra = SYM ? k.a.rx : k.a.ay, *ca = SYM ? k.a.ax : k.a.rx, *rb = SYM ? k.a.ax : k.a.ry, *cb = SYM ? k.a.rx : k.a.ax;
+  double *out = SYM ? P.dP : P.dA;
+  for (int s = wv * 16; s < wv * 16 + 16; s += 4) {
+    int i[4], j[4]; double g[4][4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int e = min(e0 + s + u, nz - 1), pos = __builtin_amdgcn_readfirstlane(map ? map[e] : e);
+      i[u] = __builtin_amdgcn_readfirstlane(ri[pos]); j[u] = __builtin_amdgcn_readfirstlane(cj[pos]);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; u++) { g[u][0] = ra[IX(i[u])]; g[u][1] = ca[IX(j[u])]; g[u][2] = rb[IX(i[u])]; g[u][3] = cb[IX(j[u])]; }
+#pragma unroll
+    for (int u = 0; u < 4; u++) tile[lane][s + u] = SYM ? 0.5 * (g[u][0] * g[u][1] + g[u][3] * g[u][2]) : g[u][0] * g[u][1] + g[u][2] * g[u][3];
+  }
+  __syncthreads();
+  const int e = e0 + lane;
+  if (e < nz) for (int b = wv; b < P.count; b += 4) out[(size_t)b * nz + e] = tile[b][lane];
+}
 #undef IX
 
 }  // namespace
@@ -615,6 +849,84 @@ int lockstep_chunk(Dev &d, const LockstepParams &p, void *stream, double *stat) 
   HIP_CHECK(hipEventDestroy(e0)); HIP_CHECK(hipEventDestroy(e1));
   HIP_CHECK(hipGetLastError());
   if (stat) { stat[0] = iter; stat[1] = words[WD_PCGSUM]; stat[2] = (double)launches; stat[3] = ms; }
+  return OSQP_NO_ERROR;
+}
+
+// The backward pass of one chunk, from the transposes in to the transposes out, on `stream` (nullptr: the solver's); returns when the chunk's results are
+// there.  The work block is the forward's set followed by the adjoint's own vectors.  Driving as in lockstep_chunk: per step the PCG iterations the
+// previous step needed, plus one, are enqueued without synchronising, then groups of four; after every step the host reads the word block and ends the
+// chunk when no problem is live.  stat: {recurrence steps of the slowest problem, PCG iterations summed, kernel launches, GPU ms}.
+int lockstep_adjoint_chunk(Dev &d, const LockstepAdjointParams &p, void *stream, double *stat) {
+  HIP_CHECK(hipSetDevice(d.device));
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : st(d);
+  const int n = p.n, m = p.m, G = lockstep_grid(n, m), tn = (n + 63) / 64, tm = (m + 63) / 64;
+  const size_t nW = (size_t)n * W, mW = (size_t)m * W;
+  LsAK ka{p, {}, {}};
+  LsWs &w = ka.w;
+  double *c = p.ws;
+  auto take = [&c](size_t cnt) { double *r = c; c += cnt; return r; };
+  w.x = take(nW); w.xs = take(nW); w.r = take(nW); w.p = take(nW); w.Kp = take(nW); w.q = take(nW); w.Minv = take(nW); w.dx = take(nW);
+  w.z = take(mW); w.y = take(mW); w.t = take(mW); w.t2 = take(mW); w.l = take(mW); w.u = take(mW); w.rho = take(mW); w.zt = take(mW); w.dy = take(mW);
+  w.part = take((size_t)kLsSlots * G * W); w.parti = take((size_t)(tm > 0 ? tm : 1) * W); w.sc = take((size_t)kLsScal * W); w.rec = take((size_t)W * kBatchRec);
+  w.iw = reinterpret_cast<int *>(take((size_t)kLsInt * W / 2)); w.word = w.iw + IW_COUNT * W;
+  w.G = G;
+  if ((size_t)(c - p.ws) > lockstep_ws_doubles(n, m)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  c = p.ws + lockstep_ws_doubles(n, m);
+  LsAdjWs &a = ka.a;
+  a.ax = take(nW); a.gdx = take(nW); a.rx = take(nW); a.ay = take(mW); a.gdy = take(mW); a.ry = take(mW); a.code = reinterpret_cast<int *>(take((mW + 1) / 2));
+  if ((size_t)(c - p.ws) > lockstep_adjoint_ws_doubles(n, m)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  const LsK k{p, w};                                    // what the forward's kernels take: the base of the parameters, the same block vectors
+  long launches = 0;
+  auto go = [&](auto kern, int grid) { hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, k); launches++; };
+  auto goa = [&](auto kern, int grid) { hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, ka); launches++; };
+  hipEvent_t e0, e1;
+  HIP_CHECK(hipEventCreate(&e0)); HIP_CHECK(hipEventCreate(&e1));
+  HIP_CHECK(hipEventRecord(e0, s));
+  int words[WD_COUNT] = {0, p.count, 0, 0, 0};
+  auto fetch = [&]() { HIP_CHECK(hipMemcpyAsync(words, w.word, sizeof(words), hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s)); };
+
+  goa(k_ls_adj_load_n, tn);
+  if (m > 0) { goa(k_ls_adj_load_m, tm); goa(k_ls_adj_class, G); }
+  goa(k_ls_adj_init, 1);
+  if (m > 0) go(k_ls_setrho, G);
+  go(k_ls_minv, G);
+  fetch();
+  int step = 0, cg_est = 4;
+  while (words[WD_LIVE] > 0 && step < p.max_steps) {
+    step++;
+    go(k_ls_rhs, G);
+    go(k_ls_cginit, 1);
+    for (int it = 0, grp = cg_est; it < p.cg_max; grp = 4) {
+      for (const int end = std::min(it + grp, p.cg_max); it < end; it++) {
+        if (m > 0) go(k_ls_t, G);
+        go(k_ls_kp, G); go(k_ls_cgalpha, 1); go(k_ls_cgupd, G); go(k_ls_cgbeta, 1); go(k_ls_cgp, G);
+      }
+      fetch();
+      if (!words[WD_CGANY]) break;
+    }
+    cg_est = std::max(2, words[WD_CGIT] + 1);
+    go(k_ls_upd, G);
+    if (m > 0) go(k_ls_resm, G);
+    go(k_ls_resn, G);
+    goa(k_ls_adj_decide, 1);
+    fetch();
+  }
+  goa(k_ls_adj_unscale, G);
+  if (m > 0) goa(k_ls_adj_resm, G);
+  goa(k_ls_adj_resn, G);
+  goa(k_ls_adj_final, 1);
+  if (p.dq) goa(k_ls_adj_out_n, tn);
+  if (m > 0 && (p.dl || p.du)) goa(k_ls_adj_out_m, tm);
+  if (p.dP && p.nzP > 0) goa(k_ls_adj_grad<true>, (p.nzP + 63) / 64);
+  if (p.dA && p.nzA > 0) goa(k_ls_adj_grad<false>, (p.nzA + 63) / 64);
+  HIP_CHECK(hipEventRecord(e1, s));
+  const int pcg_sum = words[WD_PCGSUM];
+  fetch();
+  float ms = 0.f;
+  HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+  HIP_CHECK(hipEventDestroy(e0)); HIP_CHECK(hipEventDestroy(e1));
+  HIP_CHECK(hipGetLastError());
+  if (stat) { stat[0] = step; stat[1] = pcg_sum; stat[2] = (double)launches; stat[3] = ms; }
   return OSQP_NO_ERROR;
 }
 

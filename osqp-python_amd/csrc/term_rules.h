@@ -153,6 +153,20 @@ OSQP_HDI void batch_tol_rule(double cg_frac, double dua_s, double *eps_prev, dou
   if (isfinite(e2)) { *eps_prev = e2; *eps_cg = e2; *rel_rule = false; }
 }
 
+// The progress rule of the recurrence polish and the adjoint derivatives run (engine.cpp Engine::run_recurrence on the host; lockstep_hip.hip
+// k_ls_adj_decide per problem on the device).  recurrence_err_rhs: the reduced system's scaled residuals against its right-hand side.  recurrence_ends:
+// `steps` steps have been taken and the last one left the error `err`; a step that does not bring the error below gain * best counts as no progress;
+// the recurrence ends after at least min_steps when the error is negligible or two steps in a row showed no progress, and at max_steps at the latest.
+// Comparisons, one product and one quotient: host and device give the same bits.
+OSQP_HDI double recurrence_err_rhs(double pri_s, double dua_s, double qn_s, double z_s) {
+  return (pri_s < dua_s ? dua_s : pri_s) / ((qn_s < z_s ? z_s : qn_s) + 1e-30);        // (std::max's selects: a NaN goes where it always went)
+}
+OSQP_HDI bool recurrence_ends(double err, double gain, int steps, int min_steps, int max_steps, double *best, int *worse) {
+  if (!(err < gain * *best)) *worse += 1; else *worse = 0;
+  *best = err < *best ? err : *best;
+  return (steps >= min_steps && (err < 1e-13 || *worse >= 2)) || steps >= max_steps;
+}
+
 // The record of a batch problem (backend.h kBatchRec = 12 doubles; include/osqp_hip.h OSQP_HIP_BATCH_REC): status, iter, obj, prim_res, dual_res, rho,
 // rho_updates, pcg_iters, status_polish, polish seconds, rho_estimate (_osqp.py:1275, at the ADMM point), reserved.  The polish fields and the reserved
 // one are zeroed: the polishing variants and the OSQP_HIP_KTRACE build overwrite theirs afterwards.

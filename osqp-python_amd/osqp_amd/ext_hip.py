@@ -475,6 +475,60 @@ class OSQPSolver:
         if st:
             raise self._batch_error(st)
 
+    LOCKSTEP_ADJOINT_FIELDS = ('status', 'active_rows', 'residual', 'steps')      # the OSQP_HIP_ADJOINT_REC doubles per problem on the lockstep route
+
+    def hip_batch_adjoint_lockstep(self, x, y, dx, dy=None, l=None, u=None, want=('dP', 'dq', 'dA', 'dl', 'du')):
+        """hip_batch_adjoint for problems of ANY size (osqp_hip_batch_adjoint_lockstep): shared P / A, 64 problems at a time on block vectors, every
+        adjoint system by the recurrence of the single-handle PCG route.  Same arguments (no Px / Ax), same checks, same returns; the columns of 'rec'
+        are LOCKSTEP_ADJOINT_FIELDS."""
+        if x is None or y is None or dx is None:
+            raise ValueError('x, y and dx are required')
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        B = 1 if x.ndim == 1 else int(x.shape[0])
+
+        def rows(a, name, width):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.size != B * width or (a.ndim > 1 and a.shape[-1] != width):
+                raise ValueError('%s: expected %d problems of width %d, got shape %s' % (name, B, width, a.shape))
+            return a.reshape(B, width)
+        x, y, dx, dy, l, u = (rows(a, nm, w) for a, nm, w in ((x, 'x', self.n), (y, 'y', self.m), (dx, 'dx', self.n), (dy, 'dy', self.m), (l, 'l', self.m), (u, 'u', self.m)))
+        widths = {'dP': self.nnz_P, 'dq': self.n, 'dA': self.nnz_A, 'dl': self.m, 'du': self.m}
+        out = {k: (np.zeros((B, widths[k])) if k in want else None) for k in widths}
+        rec = np.zeros((B, self.ADJOINT_REC))
+        dp = _lib.c_double_p
+        st = self._lib.osqp_hip_batch_adjoint_lockstep(self._p, B, _ptr(l, dp), _ptr(u, dp), _ptr(x, dp), _ptr(y, dp), _ptr(dx, dp), _ptr(dy, dp),
+                                                       _ptr(out['dP'], dp), _ptr(out['dq'], dp), _ptr(out['dA'], dp), _ptr(out['dl'], dp), _ptr(out['du'], dp), _ptr(rec, dp))
+        if st:
+            raise self._batch_error(st)
+        res = {k: v for k, v in out.items() if v is not None}
+        res['rec'] = rec
+        return res
+
+    def hip_batch_adjoint_lockstep_device(self, nbatch, x_ptr, y_ptr, dx_ptr, dy_ptr=None, l_ptr=None, u_ptr=None,
+                                          dP_ptr=None, dq_ptr=None, dA_ptr=None, dl_ptr=None, du_ptr=None, rec_ptr=None, stream=None):
+        """osqp_hip_batch_adjoint_lockstep_device: raw device addresses (int or None) laid out as in hip_batch_adjoint_lockstep; the work goes on `stream`
+        (None: the solver's) and the call returns when the results are there.  nbatch == 0: does the route apply?"""
+        st = self._lib.osqp_hip_batch_adjoint_lockstep_device(self._p, int(nbatch), l_ptr, u_ptr, x_ptr, y_ptr, dx_ptr, dy_ptr,
+                                                              dP_ptr, dq_ptr, dA_ptr, dl_ptr, du_ptr, rec_ptr, stream)
+        if st:
+            raise self._batch_error(st)
+
+    # OSQP_HIP_LOCKSTEP_ADJOINT_LAST_REC doubles of osqp_hip_lockstep_adjoint_last_record
+    LOCKSTEP_ADJOINT_LAST_FIELDS = ('chunks', 'width', 'steps_max', 'pcg_iters', 'kernel_launches', 'gpu_ms', 'workspace_bytes', 'reserved')
+
+    def lockstep_adjoint_last_record(self):
+        """osqp_hip_lockstep_adjoint_last_record as a dict (LOCKSTEP_ADJOINT_LAST_FIELDS): what the last lockstep adjoint call of this handle did; zeros before the first."""
+        rec = np.zeros(len(self.LOCKSTEP_ADJOINT_LAST_FIELDS))
+        st = self._lib.osqp_hip_lockstep_adjoint_last_record(self._p, _ptr(rec, _lib.c_double_p))
+        if st:
+            raise ValueError(str(int(st)))
+        out = dict(zip(self.LOCKSTEP_ADJOINT_LAST_FIELDS, rec.tolist()))
+        for k in ('chunks', 'width', 'steps_max', 'pcg_iters', 'kernel_launches', 'workspace_bytes'):
+            out[k] = int(out[k])
+        return out
+
     def _batch_error(self, st):
         """ValueError(str(code)) as the pybind layer raises for a failed call (callers compare str(e) with the code); `.reason` says why
         the batch kernel declined: OSQP_FUNC_NOT_IMPLEMENTED = the QP does not fit one workgroup's LDS, or this handle works on a

@@ -26,7 +26,9 @@ the sum over the batch, as autograd's ``expand`` would give.  dP holds, for ever
 on torch's current stream, zero-copy.  ``last_adjoint_rec`` keeps the kernel's record per element (status, active rows, residual).  A problem the
 batch kernel cannot hold (its forward ran one element after the other on the handle) is differentiated the same way: the single-handle adjoint
 (``osqp_hip_adjoint_compute_at``: the PCG route for large QPs, at the (x, y) the forward kept) once per element, ``adjoint_launches`` counting every call, shared inputs receiving
-the batch sum.  A ``torch.distributed`` job (world size > 1) raises NotImplementedError in backward.  With no input requiring grad,
+the batch sum -- or, with ``large_backward='lockstep'`` (default ``'loop'``: unchanged) and shared P_val / A_val, ONE call of the lockstep adjoint for the whole batch
+(``osqp_hip_batch_adjoint_lockstep``; ``adjoint_launches`` rises by 1; an element whose adjoint system was not solved raises RuntimeError as the
+per-element route does).  A ``torch.distributed`` job (world size > 1) raises NotImplementedError in backward.  With no input requiring grad,
 forward behaves exactly as before.
 """
 import numpy as np
@@ -50,10 +52,13 @@ def _distributed():
 
 
 class OSQP(Module):
-    def __init__(self, P_idx, P_shape, A_idx, A_shape, eps_rel=1e-5, eps_abs=1e-5, verbose=False, max_iter=10000, algebra='hip', solver_type='indirect', large_batch='loop'):
+    def __init__(self, P_idx, P_shape, A_idx, A_shape, eps_rel=1e-5, eps_abs=1e-5, verbose=False, max_iter=10000, algebra='hip', solver_type='indirect', large_batch='loop', large_backward='loop'):
         super().__init__()
         if large_batch not in ('loop', 'lockstep'):
             raise ValueError("large_batch: 'loop' or 'lockstep'")
+        if large_backward not in ('loop', 'lockstep'):
+            raise ValueError("large_backward: 'loop' or 'lockstep'")
+        self.large_backward = large_backward   # backward of such a batch: the single-handle adjoint per element ('loop'), or one call of the lockstep adjoint
         self.large_batch = large_batch   # shared matrices too large for the batch kernel: one element after the other ('loop'), or the lockstep route
         self.P_idx, self.P_shape, self.A_idx, self.A_shape = P_idx, P_shape, A_idx, A_shape
         self.eps_rel, self.eps_abs, self.verbose, self.max_iter = eps_rel, eps_abs, verbose, max_iter
@@ -260,6 +265,41 @@ class OSQP(Module):
                 if k in res: res[k][i] = v
         return {k: torch.as_tensor(v) for k, v in res.items()}
 
+    def _backward_lockstep(self, ext, l_val, u_val, x, y, g, nb, want):
+        """Backward of a shared-matrix batch past the batch adjoint kernel, with large_backward='lockstep': one call of the lockstep adjoint for the whole
+        batch (cuda tensors: zero-copy through the device entry on torch's current stream).  An element whose adjoint system was not solved raises as
+        _backward_loop does.  None: this handle is not on the route (the caller goes on to the per-element loop)."""
+        widths = {'dP': len(self._triu_pick), 'dq': self.n, 'dA': ext.nnz_A, 'dl': self.m, 'du': self.m}
+        try:
+            if g.is_cuda:
+                dev = g.device
+                f64 = lambda t, k: torch.as_tensor(t).detach().to(device=dev, dtype=torch.float64).reshape(-1, k).expand(nb, k).contiguous()
+                xd, yd, gd, ld, ud = f64(x, self.n), f64(y, self.m), f64(g, self.n), f64(l_val, self.m), f64(u_val, self.m)
+                res = {k: torch.empty((nb, widths[k]), dtype=torch.float64, device=dev) for k in want}
+                res['rec'] = torch.empty((nb, 4), dtype=torch.float64, device=dev)     # OSQP_HIP_ADJOINT_REC
+                ptr = lambda t: None if t is None else t.data_ptr()
+                ext.hip_batch_adjoint_lockstep_device(nb, xd.data_ptr(), yd.data_ptr(), gd.data_ptr(), None, ld.data_ptr(), ud.data_ptr(),
+                                                      ptr(res.get('dP')), ptr(res.get('dq')), ptr(res.get('dA')), ptr(res.get('dl')), ptr(res.get('du')),
+                                                      res['rec'].data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
+            else:
+                bc = lambda a, k: np.broadcast_to(np.asarray(a, dtype=float).reshape(-1, k), (nb, k))
+                res = ext.hip_batch_adjoint_lockstep(bc(_np(torch.as_tensor(x)), self.n), bc(_np(torch.as_tensor(y)), self.m), bc(_np(g), self.n), None,
+                                                     l=bc(_np(l_val), self.m), u=bc(_np(u_val), self.m), want=want)
+                res = {k: torch.as_tensor(v) for k, v in res.items()}
+        except ValueError as e:
+            if str(e) != str(int(osqp_amd.SolverError.OSQP_FUNC_NOT_IMPLEMENTED)):
+                raise
+            return None
+        self.adjoint_launches += 1
+        rec = res['rec'].cpu().numpy()
+        bad = np.nonzero(rec[:, 0] != 0)[0]
+        if bad.size:
+            i = int(bad[0])
+            self.last_adjoint_rec = res['rec']
+            raise RuntimeError('adjoint derivatives of batch element %d: error %d (status %d, residual %.3e)'
+                               % (i, int(osqp_amd.SolverError.OSQP_LINSYS_SOLVER_INIT_ERROR), int(rec[i, 0]), rec[i, 2]))
+        return res
+
     def _backward(self, saved, x, y, dl_dx, needs):
         P_val, q_val, A_val, l_val, u_val = saved
         params = [P_val, q_val, A_val, l_val, u_val]
@@ -302,6 +342,10 @@ class OSQP(Module):
         except ValueError as e:
             if str(e) != str(int(osqp_amd.SolverError.OSQP_FUNC_NOT_IMPLEMENTED)):
                 raise
+            res = None
+            if self.large_backward == 'lockstep' and not batched[0] and not batched[2]:
+                res = self._backward_lockstep(s._solver, l_val, u_val, x, y, g, nb, want)      # shared matrices, any size: ONE call (osqp_hip_batch_adjoint_lockstep)
+        if res is None:
             # outside the batch kernel (the forward ran _loop): the single-handle adjoint per element
             bc = lambda a, k: np.broadcast_to(np.asarray(a, dtype=float).reshape(-1, k), (nb, k))
             res = self._backward_loop(Pn, An, bc(_np(l_val), self.m), bc(_np(u_val), self.m), bc(_np(torch.as_tensor(x)), self.n), bc(_np(torch.as_tensor(y)), self.m),
