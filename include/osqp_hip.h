@@ -309,6 +309,30 @@ OSQPInt osqp_hip_batch_solve_lockstep(OSQPSolver *solver, OSQPInt nbatch, const 
 OSQPInt osqp_hip_batch_solve_lockstep_device(OSQPSolver *solver, OSQPInt nbatch, const OSQPFloat *q_dev, const OSQPFloat *l_dev, const OSQPFloat *u_dev,
                                              OSQPFloat *x_dev, OSQPFloat *y_dev, OSQPFloat *rec_dev, OSQPInt warm_start, void *stream);
 OSQPInt osqp_hip_lockstep_last_record(OSQPSolver *solver, OSQPFloat *rec);
+/* LOCKSTEP DIRECT: the lockstep route for the handles it declines -- a Woodbury-corrected handle (OSQPHipStats::woodbury_rows = r > 0) in the small mode
+ * (r <= 128) whose K0 = P + sigma I + A_S' rho A_S setup found structurally DIAGONAL: P diagonal, every row of A either long (one of the r dense rows A_L)
+ * or with at most one entry, no long row storing a (row, column) twice -- the factor-model portfolio QP.  Then K_b = D0_b + A_L' rho_L,b A_L and the
+ * Woodbury formula is the linear solve itself, per problem and without PCG: S_b = diag(1 / rho_L,b) + A_L D0_b^-1 A_L' (r x r, SPD) is formed and
+ * inverted on the device at the start and again for exactly the problems whose rho_bar has changed; an ADMM iteration is a fixed sequence of five
+ * launches, the host enqueues check_termination iterations back to back and reads the decision words once per check.  Arguments, checks, the nbatch ==
+ * 0 query, stream semantics, the OSQP_HIP_BATCH_REC record (pcg_iters = 0), per-problem termination / statuses / certificates / time_limit and the
+ * INDEPENDENCE guarantee are those of osqp_hip_batch_solve_lockstep[_device]; a pivot of S_b that is not positive ends that problem with OSQP_NON_CVX.
+ * ADAPTIVE RHO is per problem too, but NOT by the batch family's rule (the reference's factor test against adaptive_rho_tolerance): this route applies the
+ * rule of osqp_solve on this handle -- the tolerance on the policy's square-root scale (OSQPHipPolicy::rho_tol_exp / OSQP_HIP_RHO_TOL_EXP; the literal
+ * value for an LP) and the persistence test (rho_persist / OSQP_HIP_RHO_PERSIST) -- so an element takes the iterations, status and iterate that
+ * osqp_update_data_vec + osqp_solve give from the same settings.rho (a loop over one handle starts each solve from the rho the previous one left).  No
+ * polish, no duality-gap test, no per-problem matrices.  The decision is the structural one taken at setup, whatever became of the single handle's direct
+ * mode since.  Returns OSQP_FUNC_NOT_IMPLEMENTED for every other handle: no Woodbury correction, the large mode (r > 128: the lasso), a K0 that is not
+ * diagonal, the host simulator -- and a handle that works on a permuted copy (OSQPHipStats::reordered): this route DECLINES it rather than gather
+ * through the permutations.  The handle's own iterates, solution, info and launch history are not touched.
+ * osqp_hip_lockstep_direct_last_record: OSQP_HIP_LOCKSTEP_DIRECT_LAST_REC doubles {chunks, chunk width, ADMM iterations of the slowest problem,
+ * inversions of S summed over the problems, kernel launches, GPU ms, workspace bytes, seconds of the call's chunks}; all zero before the first call. */
+#define OSQP_HIP_LOCKSTEP_DIRECT_LAST_REC 8
+OSQPInt osqp_hip_batch_solve_lockstep_direct(OSQPSolver *solver, OSQPInt nbatch, const OSQPFloat *q, const OSQPFloat *l, const OSQPFloat *u,
+                                             OSQPFloat *x, OSQPFloat *y, OSQPFloat *rec, OSQPInt warm);
+OSQPInt osqp_hip_batch_solve_lockstep_direct_device(OSQPSolver *solver, OSQPInt nbatch, const OSQPFloat *q_dev, const OSQPFloat *l_dev, const OSQPFloat *u_dev,
+                                                    OSQPFloat *x_dev, OSQPFloat *y_dev, OSQPFloat *rec_dev, OSQPInt warm_start, void *stream);
+OSQPInt osqp_hip_lockstep_direct_last_record(OSQPSolver *solver, OSQPFloat *rec);
 /* ADJOINT DERIVATIVES ON THE LOCKSTEP ROUTE -- the backward pass of osqp_hip_batch_solve_lockstep: the quantities osqp_hip_batch_adjoint (below) defines,
  * for a batch that shares this handle's P and A, at any size, OSQP_HIP_LOCKSTEP_WIDTH problems at a time on block vectors.  Per problem: the rows are
  * classified by the rule given there (caller's units, z = A x on the x passed in; bounds clamped to +-OSQP_INFTY), and the adjoint system is solved by

@@ -116,6 +116,13 @@ OSQPInt osqp_hip_batch_solve_lockstep_device(OSQPSolver *s, OSQPInt nbatch, cons
   return guarded(s, [&](Engine &e) { return e.batch_solve_lockstep_device(nbatch, q, l, u, x, y, rec, warm, stream); });
 }
 OSQPInt osqp_hip_lockstep_last_record(OSQPSolver *s, OSQPFloat *rec) { return guarded(s, [&](Engine &e) { return e.lockstep_last_record(rec); }); }
+OSQPInt osqp_hip_batch_solve_lockstep_direct(OSQPSolver *s, OSQPInt nbatch, const OSQPFloat *q, const OSQPFloat *l, const OSQPFloat *u, OSQPFloat *x, OSQPFloat *y, OSQPFloat *rec, OSQPInt warm) {
+  return guarded(s, [&](Engine &e) { return e.batch_solve_lockstep_direct(nbatch, q, l, u, x, y, rec, warm); });
+}
+OSQPInt osqp_hip_batch_solve_lockstep_direct_device(OSQPSolver *s, OSQPInt nbatch, const OSQPFloat *q, const OSQPFloat *l, const OSQPFloat *u, OSQPFloat *x, OSQPFloat *y, OSQPFloat *rec, OSQPInt warm, void *stream) {
+  return guarded(s, [&](Engine &e) { return e.batch_solve_lockstep_direct_device(nbatch, q, l, u, x, y, rec, warm, stream); });
+}
+OSQPInt osqp_hip_lockstep_direct_last_record(OSQPSolver *s, OSQPFloat *rec) { return guarded(s, [&](Engine &e) { return e.lockstep_direct_last_record(rec); }); }
 OSQPInt osqp_hip_batch_adjoint_lockstep(OSQPSolver *s, OSQPInt nbatch, const OSQPFloat *l, const OSQPFloat *u, const OSQPFloat *x, const OSQPFloat *y, const OSQPFloat *dx,
                                         const OSQPFloat *dy, OSQPFloat *dP, OSQPFloat *dq, OSQPFloat *dA, OSQPFloat *dl, OSQPFloat *du, OSQPFloat *arec) {
   return guarded(s, [&](Engine &e) { return e.batch_adjoint_lockstep(nbatch, l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec); });

@@ -486,6 +486,9 @@ struct LockstepParams : BatchSettings {
   const int *pc = nullptr, *pr = nullptr;                       // reordered handle: engine column / row -> the caller's; nullptr: identity
   double *ws = nullptr;         // lockstep_ws_doubles(n, m) doubles
   double pcg_rel = 0;           // > 0: the recurrence's PCG threshold ||r|| <= pcg_rel ||rhs|| (floor 1e-15, be::set_pcg_tol) in place of the cg_frac rule
+  // adaptive rho by the single-QP path's rule (term_rules.h single_rho_rule) in place of batch_rho_rule: its tolerance (the setting's on the handle's
+  // square-root scale, Engine::ctl_setup) and persistence test.  0: the batch family's rule (rho_tol).  Set by the direct route only.
+  double rho_tol_single = 0; int rho_persist = 0;
 };
 
 // Adjoint derivatives of a chunk on the lockstep route (lockstep_hip.hip lockstep_adjoint_chunk; include/osqp_hip.h osqp_hip_batch_adjoint_lockstep):
@@ -505,7 +508,30 @@ inline size_t lockstep_adjoint_ws_doubles(int n, int m) {
   return lockstep_ws_doubles(n, m) + (size_t)kLsW * (3 * (size_t)n + 3 * (size_t)m + ((size_t)m + 1) / 2) + 64;
 }
 
+// The DIRECT lockstep route for a Woodbury handle whose K0 is diagonal (lockstep_hip.hip "lockstep DIRECT"; include/osqp_hip.h
+// osqp_hip_batch_solve_lockstep_direct): the base's A / B are the handle's; Av is the view of A the row passes read -- the one-entry rows as they are, long
+// row a as the single entry 1.0 at column n + a -- and WT / rows / islong are DevWb's (the dense transpose of the long rows, their indices, the row flags).
+struct LockstepDirectParams : LockstepParams {
+  int r = 0;                    // long rows (1 .. kWbMaxRows)
+  DevCsr Av;
+  const double *WT = nullptr; const int *rows = nullptr; const unsigned char *islong = nullptr;
+};
+// columns of a block of the products with the long rows (a multiple of 64, at most 128 blocks): from n alone, like lockstep_grid
+inline int lockstep_direct_colblock(int n) { const int t = (n + 63) / 64; return 64 * ((t + 127) / 128 > 0 ? (t + 127) / 128 : 1); }
+// doubles of a chunk's workspace: x, x~, dx with n + r rows, four n- and nine m-block vectors, the partials and state of the lockstep route, then S
+// (r x r per problem), two sets of column-block partials, h, the inversion counts
+inline size_t lockstep_direct_ws_doubles(int n, int m, int r) {
+  const size_t gc = ((size_t)n + lockstep_direct_colblock(n) - 1) / lockstep_direct_colblock(n);
+  return (size_t)kLsW * (3 * ((size_t)n + r) + 4 * (size_t)n + 9 * (size_t)m + (size_t)kLsSlots * lockstep_grid(n, m) + (size_t)(m + 63) / 64 + 1 + kLsScal + kBatchRec + kLsInt +
+                         (size_t)r * r + 2 * gc * r + r + 1) + 64;
+}
+
 namespace be {
+
+// The direct route's chunk and the refresh of the view's values: weak as well (the host simulator declines).  stat[4]: ADMM iterations of the slowest
+// problem, inversions of S summed over the problems, kernel launches, GPU ms.
+int lockstep_direct_chunk(Dev &d, const LockstepDirectParams &p, void *stream, double *stat) __attribute__((weak));
+int lockstep_direct_values(Dev &d, int nv, const int *src, double *out, void *stream) __attribute__((weak));
 
 // Weak, like adjoint_*: the host simulator has no such kernels and the driver answers OSQP_FUNC_NOT_IMPLEMENTED where the symbol is absent.  One chunk,
 // start to finish, on `stream` (nullptr: d.stream); synchronises with that stream.  stat[4]: ADMM iterations of the slowest problem, PCG iterations

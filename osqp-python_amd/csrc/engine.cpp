@@ -163,6 +163,10 @@ void Engine::free_all() {
   if (ckpt_) { be::dfree(d_, ckpt_); ckpt_ = nullptr; }
   if (lsw_) { be::dfree(d_, lsw_); lsw_ = nullptr; }
   if (lsaw_) { be::dfree(d_, lsaw_); lsaw_ = nullptr; }
+  if (lsdw_) { be::dfree(d_, lsdw_); lsdw_ = nullptr; }
+  if (lsd_vval_) { be::dfree(d_, lsd_vval_); lsd_vval_ = nullptr; }
+  if (lsd_vrp_) { be::dfree(d_, lsd_vrp_); be::dfree(d_, lsd_vcol_); be::dfree(d_, lsd_vsrc_); lsd_vrp_ = lsd_vcol_ = lsd_vsrc_ = nullptr; lsd_nv_ = 0; }
+  wb_k0diag_ = false;
   if (lsabuf_) { be::dfree(d_, lsabuf_); lsabuf_ = nullptr; lsabuf_cap_ = 0; }
   if (d_pvmap_) { be::dfree(d_, d_pvmap_); d_pvmap_ = nullptr; }
   if (d_avmap_) { be::dfree(d_, d_avmap_); d_avmap_ = nullptr; }
@@ -541,6 +545,11 @@ void Engine::print_footer() const {
 //   device-driven     (run_device_driven): the host only feeds strings of slot launches and boundary groups; the device applies
 //                     policy.h itself (k_decide) and the host reads the state block when it says "done" or "need host" (second
 //                     stage of an infeasibility test, approximate tolerances at max_iter).
+int Engine::has_quad() const {      // LPs adapt rho by the setting's literal tolerance (policy.h pol_rho_tol)
+  for (double v : P_.x) if (v != 0.0) return 1;
+  return 0;
+}
+
 void Engine::ctl_setup() {
   Ctl &c = ctl_;
   c = Ctl();
@@ -549,8 +558,7 @@ void Engine::ctl_setup() {
   c.tightW = (ari > 1 && pol_.rho_window > 0) ? std::min(pol_.rho_window, ari - 1) : 0;
   c.tightF = pol_.rho_window_tol; c.persist = pol_.rho_persist; c.tol_exp = pol_.rho_tol_exp;
   c.m = m; c.scaling = settings.scaling; c.scaled_termination = settings.scaled_termination; c.check_dualgap = settings.check_dualgap;
-  c.has_quad = 0;
-  for (double v : P_.x) if (v != 0.0) { c.has_quad = 1; break; }      // LPs adapt rho by the setting's literal tolerance (policy.h ctl_rho_rule)
+  c.has_quad = has_quad();
   c.esc_on = pol_.cg_escalate; c.stall_on = pol_.stall; c.full_budget = pol_.budget_full; c.cap_max = kMaxCg;
   c.cg_tol_fraction = settings.cg_tol_fraction; c.cg_tol_reduction = settings.cg_tol_reduction; c.rho_tolerance = settings.adaptive_rho_tolerance;
   c.eps_abs = settings.eps_abs; c.eps_rel = settings.eps_rel; c.eps_pinf = settings.eps_prim_inf; c.eps_dinf = settings.eps_dual_inf;

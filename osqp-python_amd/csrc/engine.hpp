@@ -63,6 +63,11 @@ class Engine {
   int batch_solve_lockstep(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm);
   int batch_solve_lockstep_device(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream);
   int lockstep_last_record(double *rec) const;
+  // The direct lockstep route for a Woodbury handle with a diagonal K0 (include/osqp_hip.h osqp_hip_batch_solve_lockstep_direct; lockstep_hip.hip "lockstep
+  // DIRECT"): the same arguments and semantics; every other handle -- a reordered one included -- gets OSQP_FUNC_NOT_IMPLEMENTED.
+  int batch_solve_lockstep_direct(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm);
+  int batch_solve_lockstep_direct_device(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream);
+  int lockstep_direct_last_record(double *rec) const;
   // The backward pass of such a batch (include/osqp_hip.h osqp_hip_batch_adjoint_lockstep; lockstep_hip.hip lockstep_adjoint_chunk): the adjoint system of
   // every problem by the recurrence polish runs, on block vectors, in a work block of its own.  Any output may be nullptr.
   int batch_adjoint_lockstep(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
@@ -137,6 +142,14 @@ class Engine {
   double *lsw_ = nullptr;                             // workspace of one lockstep chunk (lockstep_ws_doubles(n, m)), allocated on first use
   double ls_rec_[OSQP_HIP_LOCKSTEP_LAST_REC] = {0, 0, 0, 0, 0, 0, 0, 0};      // record of the last lockstep call (osqp_hip_lockstep_last_record)
   int run_lockstep(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream);
+  // direct lockstep route: the structural decision of prepare_wb (K0 diagonal, small mode -- not DevWb::exact, which a failed inversion clears), the
+  // chunk's workspace (lockstep_direct_ws_doubles(n, m, r)) and the view of A (LockstepDirectParams::Av), both built on first use, the last call's record
+  bool wb_k0diag_ = false;
+  double *lsdw_ = nullptr, *lsd_vval_ = nullptr;
+  int *lsd_vrp_ = nullptr, *lsd_vcol_ = nullptr, *lsd_vsrc_ = nullptr; int lsd_nv_ = 0;
+  double lsd_rec_[OSQP_HIP_LOCKSTEP_DIRECT_LAST_REC] = {0, 0, 0, 0, 0, 0, 0, 0};
+  bool lockstep_direct_applies();
+  int run_lockstep_direct(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream);
   double *lsaw_ = nullptr;                            // work block of one lockstep adjoint chunk (lockstep_adjoint_ws_doubles(n, m)), allocated on first use
   double *lsabuf_ = nullptr; size_t lsabuf_cap_ = 0;  // device scratch of batch_adjoint_lockstep (host-array entry point), kept across calls
   int *d_pvmap_ = nullptr, *d_avmap_ = nullptr;       // device copies of PvalMap_ / AvalMap_ (reordered handle), uploaded by the first lockstep adjoint
@@ -257,6 +270,7 @@ class Engine {
   OSQPHipPolicy pol_{};                 // this handle's policy (include/osqp_hip.h)
   bool pol_explicit_ = false;           // osqp_hip_set_policy was called: the environment no longer overrides the run-time fields
   Ctl ctl_{};                           // state block of the chunk-boundary rules (policy.h)
+  int has_quad() const;          // P has a non-zero: the rho tolerance goes on the square-root scale (policy.h pol_rho_tol)
   void ctl_setup();
   void apply_rho(double rho);
   void info_from_ctl();

@@ -951,6 +951,82 @@ int Engine::lockstep_last_record(double *rec) const {
   return OSQP_NO_ERROR;
 }
 
+// ------------------------------------------------------------------------------------------------ direct lockstep route (Woodbury handles)
+// lockstep_hip.hip "lockstep DIRECT": the lockstep iteration with the PCG replaced by the Woodbury formula per problem.  Applies to a handle in the small
+// Woodbury mode whose K0 setup found structurally diagonal (prepare_wb: wb_k0diag_), as numbered by the caller: a reordered handle declines.
+bool Engine::lockstep_direct_applies() {
+  return be::lockstep_direct_chunk && be::lockstep_direct_values && be::device_vec_updates() && d_.wb.on && !d_.wb.large && d_.wb.r >= 1 && d_.wb.r <= kWbMaxRows && wb_k0diag_ && !reordered_;
+}
+
+int Engine::run_lockstep_direct(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream) {
+  const int r = d_.wb.r;
+  const size_t need = lockstep_direct_ws_doubles(n, m, r);
+  if (!lsd_vrp_) {
+    // the view of A: a one-entry row keeps its entry (vsrc: where it sits in A.val), long row a becomes the entry 1.0 at column n + a
+    std::vector<int> vrp(m + 1, 0), vcol, vsrc;
+    int a = 0;
+    for (int i = 0; i < m; i++) {
+      if (Arp_[i + 1] - Arp_[i] > kLongRow) { vcol.push_back(n + a++); vsrc.push_back(-1); }
+      else for (int k = Arp_[i]; k < Arp_[i + 1]; k++) { vcol.push_back(Arj_[k]); vsrc.push_back(k); }
+      vrp[i + 1] = (int)vcol.size();
+    }
+    if (a != r) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+    lsd_nv_ = (int)vcol.size();
+    lsd_vrp_ = dev_vec<int>(d_, m + 1); lsd_vcol_ = dev_vec<int>(d_, vcol.size()); lsd_vsrc_ = dev_vec<int>(d_, vsrc.size()); lsd_vval_ = dev_vec<double>(d_, vcol.size());
+    be::h2d(d_, lsd_vrp_, vrp.data(), sizeof(int) * (m + 1)); be::h2d(d_, lsd_vcol_, vcol.data(), sizeof(int) * vcol.size()); be::h2d(d_, lsd_vsrc_, vsrc.data(), sizeof(int) * vsrc.size());
+    be::sync(d_);
+  }
+  if (!lsdw_) { lsdw_ = dev_vec<double>(d_, need); be::sync(d_); }
+  LockstepDirectParams p;
+  fill_batch_settings(p, warm);
+  p.n = n; p.m = m; p.A = d_.A; p.B = d_.B; p.D = d_.D; p.Dinv = d_.Dinv; p.E = d_.E; p.Einv = d_.Einv;
+  p.q0 = d_.qraw; p.l0 = d_.lraw; p.u0 = d_.uraw; p.ws = lsdw_;
+  p.r = r; p.WT = d_.wb.WT; p.rows = d_.wb.rows; p.islong = d_.wb.islong;
+  // adaptive rho as the handle's own solve decides it (ctl_setup: the tolerance on the square-root scale where P has a quadratic part, the persistence
+  // test), not as the batch family does: an element then takes the path update(q, l, u) + solve() takes from the same rho
+  p.rho_tol_single = pol_rho_tol(settings.adaptive_rho_tolerance, has_quad(), pol_.rho_tol_exp); p.rho_persist = pol_.rho_persist;
+  p.Av = d_.A; p.Av.ncols = n + r; p.Av.nnz = lsd_nv_; p.Av.rowptr = lsd_vrp_; p.Av.col = lsd_vcol_; p.Av.val = lsd_vval_;
+  if (const int err = be::lockstep_direct_values(d_, lsd_nv_, lsd_vsrc_, lsd_vval_, stream)) return err;      // (A's values may have changed since the last call)
+  const double t0 = now_s(), limit = settings.time_limit > 0 && settings.time_limit < 1e9 ? settings.time_limit : 0.0;
+  double tot[4] = {0, 0, 0, 0};
+  int chunks = 0;
+  for (int b0 = 0; b0 < nbatch; b0 += kLsW, chunks++) {
+    p.count = std::min(kLsW, nbatch - b0);
+    p.q = q ? q + (size_t)b0 * n : nullptr; p.l = l ? l + (size_t)b0 * m : nullptr; p.u = u ? u + (size_t)b0 * m : nullptr;
+    p.x = x + (size_t)b0 * n; p.y = y + (size_t)b0 * m; p.rec = rec + (size_t)b0 * kBatchRec;
+    p.time_limit = limit > 0 ? std::max(limit - (now_s() - t0), 1e-9) : 0.0;
+    double st[4] = {0, 0, 0, 0};
+    const int err = be::lockstep_direct_chunk(d_, p, stream, st);
+    if (err) return err;
+    tot[0] = std::max(tot[0], st[0]); tot[1] += st[1]; tot[2] += st[2]; tot[3] += st[3];
+  }
+  const double rr[OSQP_HIP_LOCKSTEP_DIRECT_LAST_REC] = {(double)chunks, (double)kLsW, tot[0], tot[1], tot[2], tot[3], (double)(need * sizeof(double)), now_s() - t0};
+  std::copy(rr, rr + OSQP_HIP_LOCKSTEP_DIRECT_LAST_REC, lsd_rec_);
+  return OSQP_NO_ERROR;
+}
+
+int Engine::batch_solve_lockstep_direct(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm) {
+  BatchStage s{*this, nbatch, &Engine::lockstep_direct_applies, /*own_row=*/nullptr, /*wg=*/false};
+  if (const int err = s.in(q, l, u, x, y, rec, warm)) return err;
+  const int err = run_lockstep_direct(nbatch, q ? s.dq : nullptr, l ? s.dl : nullptr, u ? s.du : nullptr, s.dx, s.dy, s.drec, warm, nullptr);
+  if (!err) s.out(x, y, rec);
+  return err;
+}
+
+int Engine::batch_solve_lockstep_direct_device(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream) {
+  const int enter = batch_enter(nbatch, true, x, y, rec, &Engine::lockstep_direct_applies);
+  if (enter != kBatchEnter) return enter;
+  be::sync(d_);                                     // the solver's own stream first: pending updates of the resident q / l / u, the matrices
+  return run_lockstep_direct(nbatch, q, l, u, x, y, rec, warm, stream);
+}
+
+int Engine::lockstep_direct_last_record(double *rec) const {
+  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (!rec) return OSQP_DATA_VALIDATION_ERROR;
+  std::copy(lsd_rec_, lsd_rec_ + OSQP_HIP_LOCKSTEP_DIRECT_LAST_REC, rec);
+  return OSQP_NO_ERROR;
+}
+
 // ---- the backward pass of a lockstep batch (lockstep_hip.hip lockstep_adjoint_chunk): chunk after chunk like run_lockstep.  Every array is a DEVICE
 // array in the caller's numbering (dP / dA: the caller's CSC order).  The recurrence's settings are those of Engine::run_recurrence as the single-QP
 // adjoint calls it: rho_bar = 1 / delta_eff on the active rows with equality factor 1, alpha = 1, PCG to polish_pcg_tol within kMaxCg, progress rule

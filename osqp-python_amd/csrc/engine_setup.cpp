@@ -429,6 +429,7 @@ void Engine::prepare_kf(const std::vector<int> &Arp, const std::vector<int> &Arj
 // in the preconditioner.  Symbolic data: the long rows as their own CSR (r x n), its transpose (n x r), where each entry sits in A.val.
 void Engine::prepare_wb(const std::vector<int> &Arp, const std::vector<int> &Arj) {
   d_.wb = DevWb();
+  wb_k0diag_ = false;
   if (!pol_.woodbury || !be::wb_supported() || settings.cg_precond != OSQP_DIAGONAL_PRECONDITIONER || m == 0) return;
   std::vector<int> rows;
   for (int i = 0; i < m; i++) if (Arp[i + 1] - Arp[i] > kLongRow) rows.push_back(i);
@@ -525,6 +526,7 @@ void Engine::prepare_wb(const std::vector<int> &Arp, const std::vector<int> &Arj
   for (int j = 0; j < n && diag; j++) for (int k = P_.p[j]; k < P_.p[j + 1]; k++) if (P_.i[k] != j) { diag = false; break; }
   for (int i = 0; i < m && diag; i++) if (!islong[i] && Arp[i + 1] - Arp[i] > 1) diag = false;
   w.exact = diag ? 1 : 0;
+  wb_k0diag_ = diag && !large;                                   // (what the direct lockstep route asks for: this decision, whatever becomes of w.exact later)
   // (large mode: decided numerically after every factorisation -- two-entry rows whose contributions to K0's off-diagonal cancel, as in
   //  the lasso's  -t <= x <= t , are as good as one-entry rows)
   if (large) { w.probe = pol_.woodbury_direct != 0; w.exact = 0; w.log = pol_.woodbury_log; w.cache_on = pol_.woodbury_cache != 0; w.exact_tol = pol_.woodbury_direct_tol > 0 ? pol_.woodbury_direct_tol : 1e-6; }

@@ -41,7 +41,8 @@ enum LsSlot {
 };
 static_assert(PS_COUNT <= kLsSlots, "lockstep_ws_doubles reserves kLsSlots partial slots");
 enum LsScal { SC_RHOBAR = 0, SC_EQF, SC_EPSCG, SC_EPSPREV, SC_RZ, SC_RN, SC_TOL, SC_ALPHA, SC_BETA, SC_BEST /* adjoint: smallest error so far */, SC_NACT /* adjoint: active rows */, SC_COUNT };
-enum LsInt { IW_DONE = 0, IW_STATUS, IW_RHOUPD, IW_PCG, IW_RELRULE, IW_CGON, IW_RHOCH, IW_STEPS /* adjoint: recurrence steps */, IW_WORSE /* adjoint: steps in a row without progress */, IW_COUNT };
+enum LsInt { IW_DONE = 0, IW_STATUS, IW_RHOUPD, IW_PCG, IW_RELRULE, IW_CGON, IW_RHOCH, IW_STEPS /* adjoint: recurrence steps */, IW_WORSE /* adjoint: steps in a row without progress */,
+             IW_SIDE /* direct route: single_rho_rule's side at the previous adaptation point */, IW_COUNT };
 enum LsWord { WD_CGANY = 0, WD_LIVE, WD_RHOANY, WD_PCGSUM, WD_CGIT /* PCG iterations of the current ADMM iteration that some problem needed */, WD_COUNT };
 static_assert(SC_COUNT <= kLsScal && IW_COUNT + 1 <= kLsInt, "lockstep_ws_doubles reserves kLsScal / kLsInt rows");
 
@@ -383,7 +384,7 @@ __global__ __launch_bounds__(256) void k_ls_cgbeta(LsK k) {
   if (threadIdx.x == 0) k.w.word[WD_CGIT] += 1;
 }
 
-// Every check_termination / adaptive_rho_interval iterations: the batch family's decisions (term_rules.h: batch_check, batch_rho_rule, batch_tol_rule), per problem.
+// Every check_termination / adaptive_rho_interval iterations: the batch family's decisions (term_rules.h: batch_check, batch_rho_rule -- single_rho_rule on the direct route --, batch_tol_rule), per problem.
 // mode 0: a boundary of the loop;  1: the residuals of the start (sets the first inner tolerance);  2: the time limit has passed.
 __global__ __launch_bounds__(256) void k_ls_decide(LsK k, int iter, int at_check, int at_rho, int mode) {
   __shared__ double lds[256];
@@ -417,7 +418,13 @@ __global__ __launch_bounds__(256) void k_ls_decide(LsK k, int iter, int at_check
                                [&](double &au, double &as) { au = atdy_u; as = atdy_s; }, [&](double &pu, double &ps) { pu = pdx_u; ps = pdx_s; },
                                [&](double thr) { return !(adx_hi > thr) && !(adx_lo > thr); }, &obj);
       if (status == kBatchGoOn && mode == 2) status = OSQP_TIME_LIMIT_REACHED;
-      const bool rho_big = batch_rho_rule(rho_bar, P.rho_tol, R, &rho_new);                  // (rho_new: also the record's rho estimate)
+      const bool single = P.rho_tol_single > 0.0;                                            // (the direct route: the rule of the handle's own solve)
+      bool rho_big = single ? false : batch_rho_rule(rho_bar, P.rho_tol, R, &rho_new);       // (rho_new: also the record's rho estimate)
+      if (single) {                                                                          // (its side is that of the last adaptation point the problem went on from)
+        int side = iw[IW_SIDE * W + lane];
+        if (at_rho && status == kBatchGoOn) { rho_big = single_rho_rule(rho_bar, P.rho_tol_single, P.rho_persist, R, &side, &rho_new); iw[IW_SIDE * W + lane] = side; }
+        else rho_new = term_rho_estimate(rho_bar, R);
+      }
       if (status != kBatchGoOn) {
         batch_record(k.w.rec + (size_t)lane * kBatchRec, status, iter, obj, prim_res, dual_res, rho_bar, iw[IW_RHOUPD * W + lane], iw[IW_PCG * W + lane], rho_new);
         iw[IW_DONE * W + lane] = 1; iw[IW_STATUS * W + lane] = status;
@@ -517,7 +524,7 @@ __global__ __launch_bounds__(256) void k_ls_init(LsK k, int tiles_m) {
   sc[SC_RHOBAR * W + lane] = k.P.rho0; sc[SC_EQF * W + lane] = eq_weight(n_ineq == 0.0, k.P.eq_factor);
   sc[SC_EPSCG * W + lane] = 0.0; sc[SC_EPSPREV * W + lane] = INFINITY;
   iw[IW_DONE * W + lane] = lane >= k.P.count; iw[IW_STATUS * W + lane] = OSQP_UNSOLVED; iw[IW_RHOUPD * W + lane] = 0; iw[IW_PCG * W + lane] = 0;
-  iw[IW_RELRULE * W + lane] = 1; iw[IW_CGON * W + lane] = 0; iw[IW_RHOCH * W + lane] = 1;
+  iw[IW_RELRULE * W + lane] = 1; iw[IW_CGON * W + lane] = 0; iw[IW_RHOCH * W + lane] = 1; iw[IW_SIDE * W + lane] = 0;
   if (threadIdx.x == 0) { k.w.word[WD_CGANY] = 0; k.w.word[WD_LIVE] = k.P.count; k.w.word[WD_RHOANY] = 1; k.w.word[WD_PCGSUM] = 0; k.w.word[WD_CGIT] = 0; }
 }
 
@@ -774,6 +781,178 @@ __global__ __launch_bounds__(256) void k_ls_adj_grad(LsAK k) {
   const int e = e0 + lane;
   if (e < nz) for (int b = wv; b < P.count; b += 4) out[(size_t)b * nz + e] = tile[b][lane];
 }
+// ---------------------------------------------------------------------------------------------------------------- lockstep DIRECT (Woodbury handles)
+// The route of osqp_hip_batch_solve_lockstep_direct (lockstep_direct_chunk below): a handle whose A is r <= kWbMaxRows dense rows A_L next to rows with one
+// entry, P diagonal -- K0 = P + sigma I + A_S' rho_S A_S is DIAGONAL (D0), K_b = D0_b + A_L' rho_L,b A_L, and the Woodbury formula is the solve:
+//     S_b = diag(1 / rho_L,b) + A_L D0_b^-1 A_L'  (r x r, SPD),   K_b^-1 v = u - D0_b^-1 A_L' S_b^-1 A_L u ,  u = D0_b^-1 v .
+// No PCG.  The iteration keeps this file's kernels: k_ls_rhs leaves r_0 = rhs - K x~ (x~ of the previous iteration: the solve is one step of refinement
+// on it) and p = Minv r_0 with Minv = 1 / D0 (k_lw_d0), then  g = A_L p  (k_lw_prod: column blocks, [GC][r][64] partials),  h = S^-1 g  (k_lw_h: the
+// partials folded in block order, rows of h spread over workgroups and waves),  x~ += p - Minv A_L' h  (k_lw_x), k_ls_upd.
+// The dense rows in the row passes over A: ls_rows gives a wave a strip of ROWS, so a row with thousands of entries is one wave's serial walk.  The passes
+// (k_ls_initz, k_ls_upd, k_ls_resm) therefore run on a VIEW of A (LockstepDirectParams::Av) in which long row a is the single entry 1.0 at column n + a,
+// and the block vectors x, x~, dx carry r more rows: (A_L x)_a, (A_L x~)_a, (A_L dx)_a.  x~'s rows follow k_wbz's identity  A_L x~ += h ./ rho_L  (A_L of
+// the update is g - (S - diag(1 / rho_L)) h = h ./ rho_L), x's and dx's follow by linearity from k_ls_upd's own elementwise loop (run over n + r rows); at
+// the start and in front of every residual pass the rows of x and x~ are recomputed from the products (k_lw_prod twice, k_lw_setl), so the carried
+// values never drift from what the residuals are about.  B = [P + sigma I | A'] has r + 2 entries per row: k_ls_rhs / k_ls_resn read it as it is.
+// S_b is formed (k_lw_s) and inverted in place (k_lw_inv: one workgroup per problem, S_b in LDS, Gauss-Jordan without pivoting) at the start and for exactly
+// the problems whose rho_bar k_ls_decide has changed.  A pivot that is not positive and finite makes that problem's inverse NaN: its x~ and residuals
+// are NaN from the next iteration on and k_ls_decide ends it with OSQP_NON_CVX (term_rules.h: non-finite residuals); no other lane reads it.
+struct LwWs {
+  double *S, *pg, *pg2, *h;             // [r][r][64] S, then S^-1;  [GC][r][64] partials of A_L v (two sets);  [r][64]
+  int *fact;                            // [64] inversions of S per problem
+  const double *WT; const int *rows; const unsigned char *islong;
+  int r, GC, cb;                        // long rows; column blocks and their width
+};
+struct LwK { LockstepParams P; LsWs w; LwWs d; };
+
+// Minv = 1 / D0,  D0 = B_jj + sum over the ONE-ENTRY rows i of column j of rho_i,b A_ij^2  (k_ls_minv's diagonal without the long rows' squares)
+struct FD0 {
+  const double *rho; double *Minv; const int *flag; const unsigned char *islong; int n, lane, cur;
+  __device__ __forceinline__ void begin(int row) { cur = row; }
+  __device__ __forceinline__ void load(int c, double (&g)[1]) const { g[0] = (c >= n && !islong[c - n]) ? rho[IX(c - n)] : 0.0; }
+  __device__ __forceinline__ void fma(int c, double v, const double (&g)[1], double (&a)[2]) const { if (c >= n) a[0] += g[0] * v * v; else if (c == cur) a[1] = v; }
+  __device__ __forceinline__ void row(int j, const double (&a)[2]) const { if (flag[lane]) Minv[IX(j)] = 1.0 / (a[1] + a[0]); }
+};
+__global__ __launch_bounds__(256) void k_lw_d0(LwK k) {
+  if (!k.w.word[WD_RHOANY]) return;
+  FD0 f{k.w.rho, k.w.Minv, k.w.iw + IW_RHOCH * W, k.d.islong, k.P.n, ls_lane(), 0};
+  ls_rows<1, 2>(k.P.B, f);
+}
+// S[a][c] = (a == c) / rho_a + sum_j A_L[a, j] Minv_j A_L[c, j] for the problems whose rho has just been set.  Workgroup (a, eight columns c): wave w takes
+// the columns j = w, w + 4, .. of A_L (WT: column j of A_L contiguous), the four waves are combined in wave order.
+__global__ __launch_bounds__(256) void k_lw_s(LwK k) {
+  __shared__ double lds[8 * 256];
+  if (!k.w.word[WD_RHOANY]) return;
+  const int lane = ls_lane(), wv = ls_wave(), r = k.d.r, n = k.P.n, cch = (r + 7) / 8;
+  const int a = (int)blockIdx.x / cch, c0 = ((int)blockIdx.x % cch) * 8;
+  const double *__restrict__ WT = k.d.WT;
+  double acc[8];
+#pragma unroll
+  for (int u = 0; u < 8; u++) acc[u] = 0.0;
+  for (int j = wv; j < n; j += 4) {
+    const double *__restrict__ wt = WT + (size_t)j * r;
+    const double va = wt[a];                            // (wave-uniform)
+    if (va == 0.0) continue;
+    const double t = va * k.w.Minv[IX(j)];
+#pragma unroll
+    for (int u = 0; u < 8; u++) acc[u] += t * (c0 + u < r ? wt[c0 + u] : 0.0);
+  }
+#pragma unroll
+  for (int u = 0; u < 8; u++) lds[(u * 4 + wv) * 64 + lane] = acc[u];
+  __syncthreads();
+  for (int u = wv; u < 8; u += 4) {
+    const int c = c0 + u;
+    if (c >= r) continue;
+    const double *s = lds + u * 256 + lane;
+    double v = ((s[0] + s[64]) + s[128]) + s[192];
+    if (c == a) v += 1.0 / k.w.rho[IX(k.d.rows[a])];
+    if (k.w.iw[IW_RHOCH * W + lane]) k.d.S[((size_t)a * r + c) * 64 + lane] = v;
+  }
+}
+// S_b <- S_b^-1 in place: workgroup b holds S_b (r x r) and the pivot column in LDS, 8 (r^2 + r) bytes <= 129 KB at r = 128
+__global__ __launch_bounds__(256) void k_lw_inv(LwK k) {
+  extern __shared__ double lw_lds[];
+  if (!k.w.word[WD_RHOANY]) return;
+  const int b = blockIdx.x, r = k.d.r, t = threadIdx.x, rr = r * r;
+  if (!k.w.iw[IW_RHOCH * W + b] || k.w.iw[IW_DONE * W + b]) return;      // (uniform over the workgroup)
+  double *M = lw_lds, *col = lw_lds + rr;
+  for (int e = t; e < rr; e += 256) M[e] = k.d.S[(size_t)e * 64 + b];
+  __syncthreads();
+  for (int kk = 0; kk < r; kk++) {
+    const double p = M[kk * r + kk], ip = (p > 0.0 && p < INFINITY) ? 1.0 / p : NAN;
+    __syncthreads();
+    for (int j = t; j < r; j += 256) {
+      if (j != kk) col[j] = M[j * r + kk];
+      M[kk * r + j] = j == kk ? ip : M[kk * r + j] * ip;
+    }
+    __syncthreads();
+    for (int e = t; e < rr; e += 256) {
+      const int i = e / r, j = e - i * r;
+      if (i != kk) M[e] = (j == kk ? 0.0 : M[e]) - col[i] * M[kk * r + j];
+    }
+    __syncthreads();
+  }
+  for (int e = t; e < rr; e += 256) k.d.S[(size_t)e * 64 + b] = M[e];
+  if (t == 0) k.d.fact[b] += 1;
+}
+// out[block][a] = sum over the block's columns j of A_L[a, j] v_j: workgroup = a block of cb columns, wave w takes the rows 8 w .. 8 w + 7, + 32, ..
+__global__ __launch_bounds__(256) void k_lw_prod(LwK k, const double *v, double *out) {
+  const int lane = ls_lane(), wv = ls_wave(), r = k.d.r, j0 = (int)blockIdx.x * k.d.cb, j1 = min(j0 + k.d.cb, k.P.n);
+  const double *__restrict__ WT = k.d.WT;
+  for (int a0 = wv * 8; a0 < r; a0 += 32) {
+    double acc[8];
+#pragma unroll
+    for (int u = 0; u < 8; u++) acc[u] = 0.0;
+    for (int j = j0; j < j1; j++) {
+      const double vj = v[IX(j)];
+      const double *__restrict__ wt = WT + (size_t)j * r + a0;
+#pragma unroll
+      for (int u = 0; u < 8; u++) acc[u] += (a0 + u < r ? wt[u] : 0.0) * vj;
+    }
+#pragma unroll
+    for (int u = 0; u < 8; u++) if (a0 + u < r) out[((size_t)blockIdx.x * r + a0 + u) * 64 + lane] = acc[u];
+  }
+}
+// the sum of GC partials `st` doubles apart, in block order, eight loads in flight (the additions keep their order)
+__device__ __forceinline__ double lw_fold(const double *s, int GC, size_t st) {
+  double a = 0.0;
+  int g = 0;
+  for (; g + 8 <= GC; g += 8) {
+    double v[8];
+#pragma unroll
+    for (int u = 0; u < 8; u++) v[u] = s[(size_t)(g + u) * st];
+#pragma unroll
+    for (int u = 0; u < 8; u++) a += v[u];
+  }
+  for (; g < GC; g++) a += s[(size_t)g * st];
+  return a;
+}
+// the rows n .. n + r - 1 of x and x~ from the products (the fold of k_lw_prod's two partial sets in block order); at the start those of dx are zero
+__global__ __launch_bounds__(256) void k_lw_setl(LwK k, int start) {
+  const int lane = ls_lane(), wv = ls_wave(), r = k.d.r, GC = k.d.GC;
+  const int live = !k.w.iw[IW_DONE * W + lane];
+  for (int a = wv; a < r; a += 4) {
+    const double sx = lw_fold(k.d.pg + (size_t)a * 64 + lane, GC, (size_t)r * 64), ss = lw_fold(k.d.pg2 + (size_t)a * 64 + lane, GC, (size_t)r * 64);
+    if (live || start) { k.w.x[IX(k.P.n + a)] = sx; k.w.xs[IX(k.P.n + a)] = ss; }
+    if (start) k.w.dx[IX(k.P.n + a)] = 0.0;
+  }
+}
+// g = the fold of the partials in block order (every workgroup, into LDS);  h_a = sum_c S^-1[a][c] g_c for the workgroup's 16 rows a, a wave per row;
+// (A_L x~)_a += h_a / rho_a
+__global__ __launch_bounds__(256) void k_lw_h(LwK k) {
+  extern __shared__ double lw_lds[];
+  const int lane = ls_lane(), wv = ls_wave(), r = k.d.r, GC = k.d.GC;
+  for (int c = wv; c < r; c += 4) {
+    lw_lds[c * 64 + lane] = lw_fold(k.d.pg + (size_t)c * 64 + lane, GC, (size_t)r * 64);
+  }
+  __syncthreads();
+  const int live = !k.w.iw[IW_DONE * W + lane], a1 = min(r, (int)blockIdx.x * 16 + 16);
+  for (int a = (int)blockIdx.x * 16 + wv; a < a1; a += 4) {
+    const double *Sa = k.d.S + (size_t)a * r * 64 + lane;
+    double h = 0.0;
+    for (int c = 0; c < r; c++) h += Sa[(size_t)c * 64] * lw_lds[c * 64 + lane];
+    if (live) { k.d.h[a * 64 + lane] = h; k.w.xs[IX(k.P.n + a)] += h / k.w.rho[IX(k.d.rows[a])]; }
+  }
+}
+// x~_j += p_j - Minv_j sum_a A_L[a, j] h_a  (h in LDS; wave w of workgroup g takes the columns 4 g + w, + 4 G, ..)
+__global__ __launch_bounds__(256) void k_lw_x(LwK k) {
+  extern __shared__ double lw_lds[];
+  const int lane = ls_lane(), r = k.d.r;
+  for (int e = threadIdx.x; e < r * 64; e += 256) lw_lds[e] = k.d.h[e];
+  __syncthreads();
+  if (k.w.iw[IW_DONE * W + lane]) return;
+  const double *__restrict__ WT = k.d.WT;
+  for (int j = (int)blockIdx.x * 4 + ls_wave(); j < k.P.n; j += (int)gridDim.x * 4) {
+    const double *__restrict__ wt = WT + (size_t)j * r;
+    double s = 0.0;
+    for (int a = 0; a < r; a++) s += wt[a] * lw_lds[a * 64 + lane];
+    k.w.xs[IX(j)] += k.w.p[IX(j)] - k.w.Minv[IX(j)] * s;
+  }
+}
+// the view's values: a copy of A's at the one-entry rows, 1.0 at a long row's single entry
+__global__ __launch_bounds__(256) void k_lw_vals(int nv, const int *src, const double *Aval, double *out) {
+  for (int e = blockIdx.x * 256 + threadIdx.x; e < nv; e += gridDim.x * 256) out[e] = src[e] >= 0 ? Aval[src[e]] : 1.0;
+}
 #undef IX
 
 }  // namespace
@@ -927,6 +1106,105 @@ int lockstep_adjoint_chunk(Dev &d, const LockstepAdjointParams &p, void *stream,
   HIP_CHECK(hipEventDestroy(e0)); HIP_CHECK(hipEventDestroy(e1));
   HIP_CHECK(hipGetLastError());
   if (stat) { stat[0] = step; stat[1] = pcg_sum; stat[2] = (double)launches; stat[3] = ms; }
+  return OSQP_NO_ERROR;
+}
+
+// One chunk of the DIRECT route ("lockstep DIRECT" above), from the transposes in to the transposes out, on `stream` (nullptr: the solver's).  A fixed
+// launch sequence without an inner convergence test: five launches per ADMM iteration (k_ls_rhs, k_lw_prod, k_lw_h, k_lw_x, k_ls_upd), enqueued back to
+// back; at a termination check the host reads the word block once.  The time limit is tested against the host's clock as of the last such read (in
+// between the host runs ahead of the GPU): a chunk past its limit ends at the iteration after the check that saw it, with OSQP_TIME_LIMIT_REACHED for the
+// problems still running.  stat: {ADMM iterations of the slowest problem, inversions of S summed over the problems, kernel launches, GPU ms}.
+int lockstep_direct_chunk(Dev &d, const LockstepDirectParams &p, void *stream, double *stat) {
+  HIP_CHECK(hipSetDevice(d.device));
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : st(d);
+  const int n = p.n, m = p.m, r = p.r, G = lockstep_grid(n, m), tn = (n + 63) / 64, tm = (m + 63) / 64;
+  if (r < 1 || r > kWbMaxRows || m < 1) return OSQP_FUNC_NOT_IMPLEMENTED;
+  const int cb = lockstep_direct_colblock(n), GC = (n + cb - 1) / cb;
+  const size_t nW = (size_t)n * W, mW = (size_t)m * W, xW = (size_t)(n + r) * W;
+  LwK k{p, {}, {}};
+  LsWs &w = k.w;
+  double *c = p.ws;
+  auto take = [&c](size_t cnt) { double *q = c; c += cnt; return q; };
+  w.x = take(xW); w.xs = take(xW); w.dx = take(xW); w.r = take(nW); w.p = take(nW); w.q = take(nW); w.Minv = take(nW); w.Kp = nullptr;
+  w.z = take(mW); w.y = take(mW); w.t = take(mW); w.t2 = take(mW); w.l = take(mW); w.u = take(mW); w.rho = take(mW); w.zt = take(mW); w.dy = take(mW);
+  w.part = take((size_t)kLsSlots * G * W); w.parti = take((size_t)tm * W); w.sc = take((size_t)kLsScal * W); w.rec = take((size_t)W * kBatchRec);
+  w.iw = reinterpret_cast<int *>(take((size_t)kLsInt * W / 2)); w.word = w.iw + IW_COUNT * W;
+  w.G = G;
+  LwWs &x = k.d;
+  x.S = take((size_t)r * r * W); x.pg = take((size_t)GC * r * W); x.pg2 = take((size_t)GC * r * W); x.h = take((size_t)r * W);
+  x.fact = reinterpret_cast<int *>(take(W / 2));
+  x.WT = p.WT; x.rows = p.rows; x.islong = p.islong; x.r = r; x.GC = GC; x.cb = cb;
+  if ((size_t)(c - p.ws) > lockstep_direct_ws_doubles(n, m, r)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  const size_t lds_inv = sizeof(double) * ((size_t)r * r + r), lds_h = sizeof(double) * (size_t)r * 64;
+  if (lds_inv > 64 * 1024) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_lw_inv), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_inv));
+  // what this file's kernels take: the same block vectors; kv reads A through the view, ku does too and runs k_ls_upd's elementwise loop over n + r rows
+  const LsK kb{p, w};
+  LsK kv = kb; kv.P.A = p.Av;
+  LsK ku = kv; ku.P.n = n + r;
+  long launches = 0;
+  auto go = [&](auto kern, int grid, const LsK &a, auto... args) { hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, a, args...); launches++; };
+  auto gow = [&](auto kern, int grid, size_t lds, auto... args) { hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, k, args...); launches++; };
+  struct Ev { hipEvent_t e = nullptr; ~Ev() { if (e) (void)hipEventDestroy(e); } } ev0, ev1;      // (destroyed on every way out: HIP_CHECK throws)
+  HIP_CHECK(hipEventCreate(&ev0.e)); HIP_CHECK(hipEventCreate(&ev1.e));
+  const hipEvent_t e0 = ev0.e, e1 = ev1.e;
+  HIP_CHECK(hipEventRecord(e0, s));
+  auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+  const double t_begin = now();
+  double t_sync = t_begin;                 // the host's clock when it last waited for the stream: the time the GPU's work is known to have taken
+  int words[WD_COUNT] = {0, p.count, 0, 0, 0};
+  auto fetch = [&]() { HIP_CHECK(hipMemcpyAsync(words, w.word, sizeof(words), hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s)); t_sync = now(); };
+  auto long_rows = [&](int start) { gow(k_lw_prod, GC, 0, (const double *)w.x, x.pg); gow(k_lw_prod, GC, 0, (const double *)w.xs, x.pg2); gow(k_lw_setl, 1, 0, start); };
+  auto residuals = [&]() { go(k_ls_resm, G, kv); go(k_ls_resn, G, kb); };
+  auto new_rho = [&]() { go(k_ls_setrho, G, kb); gow(k_lw_d0, G, 0); gow(k_lw_s, r * ((r + 7) / 8), 0); gow(k_lw_inv, W, lds_inv); };
+
+  HIP_CHECK(hipMemsetAsync(x.fact, 0, sizeof(int) * W, s));
+  go(k_ls_load_n, tn, kb);
+  go(k_ls_load_m, tm, kb);
+  go(k_ls_init, 1, kb, tm);
+  new_rho();
+  long_rows(1);
+  go(k_ls_initz, G, kv);
+  residuals();
+  go(k_ls_decide, 1, kb, 0, 0, 0, 1);
+  int iter = 0;
+  while (words[WD_LIVE] > 0 && iter < p.max_iter) {
+    iter++;
+    go(k_ls_rhs, G, kb);
+    gow(k_lw_prod, GC, 0, (const double *)w.p, x.pg);
+    gow(k_lw_h, (r + 15) / 16, lds_h);
+    gow(k_lw_x, G, lds_h);
+    go(k_ls_upd, G, ku);
+    const int at_check = (p.check > 0 && iter % p.check == 0) || iter >= p.max_iter;
+    const int at_rho = p.rho_interval > 0 && iter % p.rho_interval == 0;
+    const bool late = p.time_limit > 0 && t_sync - t_begin > p.time_limit;      // (as of the last check: the host enqueues ahead of the GPU in between)
+    if (!at_check && !at_rho && !late) continue;
+    long_rows(0);
+    residuals();
+    go(k_ls_decide, 1, kb, iter, late ? 1 : at_check, at_rho, late ? 2 : 0);
+    if (at_rho && !late) new_rho();
+    if (at_check || late) fetch();
+  }
+  go(k_ls_store_n, tn, kb);
+  go(k_ls_store_m, tm, kb);
+  HIP_CHECK(hipEventRecord(e1, s));
+  int fact[W];
+  HIP_CHECK(hipMemcpyAsync(fact, x.fact, sizeof(fact), hipMemcpyDeviceToHost, s));
+  fetch();
+  float ms = 0.f;
+  HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+  HIP_CHECK(hipGetLastError());
+  long nfact = 0;
+  for (int b = 0; b < W; b++) nfact += fact[b];
+  if (stat) { stat[0] = iter; stat[1] = (double)nfact; stat[2] = (double)launches; stat[3] = ms; }
+  return OSQP_NO_ERROR;
+}
+
+// the values of the view of A (LockstepDirectParams::Av) from A's current ones, on `stream` (nullptr: the solver's)
+int lockstep_direct_values(Dev &d, int nv, const int *src, double *out, void *stream) {
+  HIP_CHECK(hipSetDevice(d.device));
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : st(d);
+  hipLaunchKernelGGL(k_lw_vals, dim3(std::max(1, std::min(256, (nv + 255) / 256))), dim3(256), 0, s, nv, src, (const double *)d.A.val, out);
+  HIP_CHECK(hipGetLastError());
   return OSQP_NO_ERROR;
 }
 

@@ -194,19 +194,19 @@ OSQP_HD inline int ctl_stage2(const Ctl &c, const double *r2, bool approximate) 
   return 0;
 }
 
+// the tolerance of ctl_rho_rule: the setting's on this engine's square-root scale (tol_exp, default 0.5); LPs keep the literal value.  Also what the
+// direct lockstep route hands its kernel (Engine::run_lockstep_direct): one text, so a batch element and the handle's own solve test against the same value
+OSQP_HD inline double pol_rho_tol(double rho_tolerance, int has_quad, double tol_exp) { return pow(rho_tolerance, has_quad ? tol_exp : 1.0); }
 // adapt_rho (_osqp.py:910-930) on the indirect path.  Returns true when rho_bar changed.
 // An update costs this path two small kernels, not a refactorisation -- the reason for the reference's factor-5 guard -- so the tolerance
 // is spent on a square-root scale (the default 5 fires at 2.24; LPs keep the literal value), and an estimate that falls on the same side
 // of rho by more than sqrt(tolerance) at two CONSECUTIVE adaptation points is applied as well.
 OSQP_HD inline bool ctl_rho_rule(Ctl &c, const double *res) {
-  const double rn = pol_rho_estimate(c.rho_bar, res), tol = pow(c.rho_tolerance, c.has_quad ? c.tol_exp : 1.0);
+  const double tol = pol_rho_tol(c.rho_tolerance, c.has_quad, c.tol_exp);
+  double rn;
+  const bool apply = single_rho_rule(c.rho_bar, tol, c.persist, ctl_term_res(res), &c.last_side, &rn);      // (term_rules.h: one text with the direct lockstep route)
   c.rho_estimate = rn;
-  const double st = sqrt(tol);
-  const int side = rn > st * c.rho_bar ? 1 : (rn < c.rho_bar / st ? -1 : 0);
-  const bool big = rn > tol * c.rho_bar || rn < c.rho_bar / tol;
-  const bool persistent = c.persist && side != 0 && side == c.last_side;
-  c.last_side = side;
-  if (big || persistent) { c.rho_bar = rn; c.rho_updates++; c.last_side = 0; return true; }
+  if (apply) { c.rho_bar = rn; c.rho_updates++; return true; }
   return false;
 }
 

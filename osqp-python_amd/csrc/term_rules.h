@@ -142,6 +142,21 @@ OSQP_HDI bool batch_rho_rule(double rho_bar, double rho_tol, const TermRes &R, d
   return *rho_new > rho_tol * rho_bar || *rho_new < rho_bar / rho_tol;
 }
 
+// adapt_rho with the single-QP path's test (policy.h ctl_rho_rule is this text on a Ctl; the direct lockstep route runs it per problem, so that a batch
+// element takes the path update(q, l, u) + solve() on the handle takes): an update costs that path no refactorisation worth the reference's factor-5
+// guard, so `tol` is the setting's tolerance on a square-root scale (the caller's pow), and an estimate that falls on the same side of rho by more than
+// sqrt(tol) at two CONSECUTIVE adaptation points is applied as well.  *last_side: the side seen at the previous adaptation point.
+OSQP_HDI bool single_rho_rule(double rho_bar, double tol, int persist, const TermRes &R, int *last_side, double *rho_new) {
+  const double rn = term_rho_estimate(rho_bar, R);
+  *rho_new = rn;
+  const double st = sqrt(tol);
+  const int side = rn > st * rho_bar ? 1 : (rn < rho_bar / st ? -1 : 0);
+  const bool big = rn > tol * rho_bar || rn < rho_bar / tol;
+  const bool persistent = persist && side != 0 && side == *last_side;
+  *last_side = (big || persistent) ? 0 : side;
+  return big || persistent;
+}
+
 // PCG tolerance of the batch family's PCG variants: a fraction of the scaled dual residual, absolute (rel_rule: relative to ||rhs||, for a start whose
 // dual residual gives no usable value), never loosening, floor 1e-13; a non-finite value leaves the state as it is
 OSQP_HDI void batch_tol_init(double cg_frac, double dua_s, double *eps_prev, double *eps_cg, bool *rel_rule) {

@@ -391,6 +391,10 @@ class OSQPSolver:
     def hip_batch_solve_lockstep(self, q=None, l=None, u=None, x0=None, y0=None, nbatch=None):
         """hip_batch_solve for problems of ANY size (osqp_hip_batch_solve_lockstep): shared P / A, 64 problems at a time on block vectors.
         Same arguments (no Px / Ax), same checks, same returns: x (B, n), y (B, m), rec (B, BATCH_REC)."""
+        return self._lockstep_host(self._lib.osqp_hip_batch_solve_lockstep, q, l, u, x0, y0, nbatch)
+
+    def _lockstep_host(self, entry, q, l, u, x0, y0, nbatch):
+        """The host-array call of a lockstep route (`entry`: its C entry point): widths checked here, then the engine."""
         arrs = [a for a in (q, l, u, x0, y0) if a is not None]
         B = int(nbatch) if nbatch is not None else int(np.asarray(arrs[0]).shape[0])
 
@@ -404,8 +408,8 @@ class OSQPSolver:
         x = np.zeros((B, self.n)) if x0 is None else rows(x0, 'x0', self.n).copy()
         y = np.zeros((B, self.m)) if y0 is None else rows(y0, 'y0', self.m).copy()
         rec = np.zeros((B, self.BATCH_REC))
-        st = self._lib.osqp_hip_batch_solve_lockstep(self._p, B, _ptr(q, _lib.c_double_p), _ptr(l, _lib.c_double_p), _ptr(u, _lib.c_double_p),
-                                                     _ptr(x, _lib.c_double_p), _ptr(y, _lib.c_double_p), _ptr(rec, _lib.c_double_p), int(warm))
+        st = entry(self._p, B, _ptr(q, _lib.c_double_p), _ptr(l, _lib.c_double_p), _ptr(u, _lib.c_double_p),
+                   _ptr(x, _lib.c_double_p), _ptr(y, _lib.c_double_p), _ptr(rec, _lib.c_double_p), int(warm))
         if st:
             raise self._batch_error(st)
         return x, y, rec
@@ -428,6 +432,34 @@ class OSQPSolver:
             raise ValueError(str(int(st)))
         out = dict(zip(self.LOCKSTEP_LAST_FIELDS, rec.tolist()))
         for k in ('chunks', 'width', 'admm_iters_max', 'pcg_iters', 'kernel_launches', 'workspace_bytes'):
+            out[k] = int(out[k])
+        return out
+
+    def hip_batch_solve_lockstep_direct(self, q=None, l=None, u=None, x0=None, y0=None, nbatch=None):
+        """hip_batch_solve_lockstep for the handles it declines (osqp_hip_batch_solve_lockstep_direct): a Woodbury-corrected handle in the small mode
+        whose K0 is diagonal (the factor-model portfolio QP) -- the Woodbury formula per problem in place of the PCG.  Same arguments, checks and
+        returns; every other handle raises with OSQP_FUNC_NOT_IMPLEMENTED."""
+        return self._lockstep_host(self._lib.osqp_hip_batch_solve_lockstep_direct, q, l, u, x0, y0, nbatch)
+
+    def hip_batch_solve_lockstep_direct_device(self, nbatch, q_ptr, l_ptr, u_ptr, x_ptr, y_ptr, rec_ptr, warm=False, stream=None):
+        """osqp_hip_batch_solve_lockstep_direct_device: raw device addresses (int or None) laid out as in hip_batch_solve_lockstep; the work goes on
+        `stream` (None: the solver's) and the call returns when the results are there.  nbatch == 0: does the route apply?"""
+        st = self._lib.osqp_hip_batch_solve_lockstep_direct_device(self._p, int(nbatch), q_ptr, l_ptr, u_ptr, x_ptr, y_ptr, rec_ptr, int(bool(warm)), stream)
+        if st:
+            raise self._batch_error(st)
+
+    # OSQP_HIP_LOCKSTEP_DIRECT_LAST_REC doubles of osqp_hip_lockstep_direct_last_record
+    LOCKSTEP_DIRECT_LAST_FIELDS = ('chunks', 'width', 'admm_iters_max', 'factorisations', 'kernel_launches', 'gpu_ms', 'workspace_bytes', 'seconds')
+
+    def lockstep_direct_last_record(self):
+        """osqp_hip_lockstep_direct_last_record as a dict (LOCKSTEP_DIRECT_LAST_FIELDS): what the last direct lockstep call of this handle did; zeros
+        before the first."""
+        rec = np.zeros(len(self.LOCKSTEP_DIRECT_LAST_FIELDS))
+        st = self._lib.osqp_hip_lockstep_direct_last_record(self._p, _ptr(rec, _lib.c_double_p))
+        if st:
+            raise ValueError(str(int(st)))
+        out = dict(zip(self.LOCKSTEP_DIRECT_LAST_FIELDS, rec.tolist()))
+        for k in ('chunks', 'width', 'admm_iters_max', 'factorisations', 'kernel_launches', 'workspace_bytes'):
             out[k] = int(out[k])
         return out
 

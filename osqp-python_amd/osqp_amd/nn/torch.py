@@ -14,7 +14,9 @@ threads.  Here one persistent engine handle plays that role:
   * per-element P_val / A_val (2-D tensors, :128-157, 184-217): the SAME single launch -- every workgroup reads its own element's matrix values, assembled
     and equilibrated per element by a launch in front of it (osqp_hip_batch_solve_mat); only a problem too large for one workgroup falls back to the
     single-QP handle, one element after the other -- or, with ``large_batch='lockstep'``, goes to the lockstep route (osqp_hip_batch_solve_lockstep:
-    64 problems at a time on block vectors, any size; host tensors through the host entry, ROCm tensors zero-copy through the device entry).
+    64 problems at a time on block vectors, any size; host tensors through the host entry, ROCm tensors zero-copy through the device entry), or, with
+    ``large_batch='lockstep_direct'``, to its direct form for a Woodbury handle with a diagonal K0 (osqp_hip_batch_solve_lockstep_direct: the
+    factor-model portfolio QP, which the lockstep route declines); a handle the chosen route declines raises as ``'lockstep'`` always has.
 
 Like the reference, a batch element that is not solved raises RuntimeError (:158-162).
 
@@ -54,12 +56,12 @@ def _distributed():
 class OSQP(Module):
     def __init__(self, P_idx, P_shape, A_idx, A_shape, eps_rel=1e-5, eps_abs=1e-5, verbose=False, max_iter=10000, algebra='hip', solver_type='indirect', large_batch='loop', large_backward='loop'):
         super().__init__()
-        if large_batch not in ('loop', 'lockstep'):
-            raise ValueError("large_batch: 'loop' or 'lockstep'")
+        if large_batch not in ('loop', 'lockstep', 'lockstep_direct'):
+            raise ValueError("large_batch: 'loop', 'lockstep' or 'lockstep_direct'")
         if large_backward not in ('loop', 'lockstep'):
             raise ValueError("large_backward: 'loop' or 'lockstep'")
         self.large_backward = large_backward   # backward of such a batch: the single-handle adjoint per element ('loop'), or one call of the lockstep adjoint
-        self.large_batch = large_batch   # shared matrices too large for the batch kernel: one element after the other ('loop'), or the lockstep route
+        self.large_batch = large_batch   # shared matrices too large for the batch kernel: one element after the other ('loop'), the lockstep route, or its direct form for Woodbury handles ('lockstep_direct')
         self.P_idx, self.P_shape, self.A_idx, self.A_shape = P_idx, P_shape, A_idx, A_shape
         self.eps_rel, self.eps_abs, self.verbose, self.max_iter = eps_rel, eps_abs, verbose, max_iter
         self.algebra, self.solver_type = algebra, solver_type
@@ -139,6 +141,9 @@ class OSQP(Module):
                 if self.large_batch == 'lockstep' and world == 1:                      # any size, 64 problems at a time (osqp_hip_batch_solve_lockstep)
                     x, y, rec = s._solver.hip_batch_solve_lockstep(q=qn, l=ln, u=un)
                     self.last_dual = y
+                elif self.large_batch == 'lockstep_direct' and world == 1:             # a Woodbury handle with a diagonal K0 (osqp_hip_batch_solve_lockstep_direct)
+                    x, y, rec = s._solver.hip_batch_solve_lockstep_direct(q=qn, l=ln, u=un)
+                    self.last_dual = y
                 else:
                     x, rec = self._loop(Pn, qn, An, ln, un, nb, batched, dev_index)
         else:
@@ -198,9 +203,10 @@ class OSQP(Module):
         except ValueError as e:
             if str(e) != str(int(osqp_amd.SolverError.OSQP_FUNC_NOT_IMPLEMENTED)):
                 raise
-            if self.large_batch != 'lockstep':
+            if self.large_batch not in ('lockstep', 'lockstep_direct'):
                 return None                                                            # does not fit one workgroup's LDS
-            s._solver.hip_batch_solve_lockstep_device(nb, qd.data_ptr(), ld.data_ptr(), ud.data_ptr(), x.data_ptr(), y.data_ptr(), rec.data_ptr(),
+            entry = s._solver.hip_batch_solve_lockstep_device if self.large_batch == 'lockstep' else s._solver.hip_batch_solve_lockstep_direct_device
+            entry(nb, qd.data_ptr(), ld.data_ptr(), ud.data_ptr(), x.data_ptr(), y.data_ptr(), rec.data_ptr(),
                                                       warm=False, stream=stream)
         st = rec[:, 0].to('cpu')                                                        # (waits for the stream)
         bad = torch.nonzero(st != int(osqp_amd.SolverStatus.OSQP_SOLVED)).flatten()
