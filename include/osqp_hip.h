@@ -360,6 +360,25 @@ OSQPInt osqp_hip_batch_adjoint_lockstep_device(OSQPSolver *solver, OSQPInt nbatc
                                                const OSQPFloat *y_dev, const OSQPFloat *dx_dev, const OSQPFloat *dy_dev, OSQPFloat *dP_dev, OSQPFloat *dq_dev,
                                                OSQPFloat *dA_dev, OSQPFloat *dl_dev, OSQPFloat *du_dev, OSQPFloat *arec_dev, void *stream);
 OSQPInt osqp_hip_lockstep_adjoint_last_record(OSQPSolver *solver, OSQPFloat *rec);
+/* ADJOINT DERIVATIVES ON THE DIRECT LOCKSTEP ROUTE -- the backward pass of osqp_hip_batch_solve_lockstep_direct, on exactly the handles that call accepts
+ * (OSQP_FUNC_NOT_IMPLEMENTED for every other one: no Woodbury correction, r > 128, a K0 that is not diagonal, a reordered handle, the host simulator).
+ * Arguments, the classification, the recurrence and its ending rule, the unscaling, the residual of the unregularised system, the outputs (dA at every
+ * stored entry, the dense rows' included), arec, the statuses 0 / 2 / 3, INDEPENDENCE, the stream semantics and the nbatch == 0 query are those of
+ * osqp_hip_batch_adjoint_lockstep[_device] above.  What differs is the linear solve inside a step: the Woodbury formula of the forward route per problem
+ * instead of a PCG.  rho is fixed throughout the recurrence, so S_b is formed and inverted ONCE per problem (an inactive dense row has rho_min, i.e.
+ * 1e6 on S_b's diagonal); a step is a fixed sequence of launches followed by one read of the decision words.  A pivot of S_b that is not positive and
+ * finite leaves that problem's iterates NaN: it ends with status 3 and no other problem reads it.  The work block and the host entry's scratch are
+ * this route's own (allocated by the first call, freed with the handle); the handle's solve state, the forward route's workspace and record are not written.
+ * osqp_hip_lockstep_direct_adjoint_last_record: OSQP_HIP_LOCKSTEP_DIRECT_ADJOINT_LAST_REC doubles {chunks, chunk width, recurrence steps of the slowest
+ * problem, inversions of S summed over the problems, kernel launches, GPU ms, workspace bytes, reserved}; all zero before the first call. */
+#define OSQP_HIP_LOCKSTEP_DIRECT_ADJOINT_LAST_REC 8
+OSQPInt osqp_hip_batch_adjoint_lockstep_direct(OSQPSolver *solver, OSQPInt nbatch, const OSQPFloat *l, const OSQPFloat *u, const OSQPFloat *x, const OSQPFloat *y,
+                                               const OSQPFloat *dx, const OSQPFloat *dy, OSQPFloat *dP, OSQPFloat *dq, OSQPFloat *dA, OSQPFloat *dl, OSQPFloat *du,
+                                               OSQPFloat *arec);
+OSQPInt osqp_hip_batch_adjoint_lockstep_direct_device(OSQPSolver *solver, OSQPInt nbatch, const OSQPFloat *l_dev, const OSQPFloat *u_dev, const OSQPFloat *x_dev,
+                                                      const OSQPFloat *y_dev, const OSQPFloat *dx_dev, const OSQPFloat *dy_dev, OSQPFloat *dP_dev, OSQPFloat *dq_dev,
+                                                      OSQPFloat *dA_dev, OSQPFloat *dl_dev, OSQPFloat *du_dev, OSQPFloat *arec_dev, void *stream);
+OSQPInt osqp_hip_lockstep_direct_adjoint_last_record(OSQPSolver *solver, OSQPFloat *rec);
 
 /* ADJOINT DERIVATIVES of a batch of solved QPs -- the backward pass of osqp_hip_batch_solve[_mat]: ONE launch, one workgroup per problem
  * (batch_hip.hip k_batch_adjoint).  For problem b with solution x (n), y (m) and incoming gradients dx = dL/dx (n), dy = dL/dy (m; NULL = 0):

@@ -526,12 +526,28 @@ inline size_t lockstep_direct_ws_doubles(int n, int m, int r) {
                          (size_t)r * r + 2 * gc * r + r + 1) + 64;
 }
 
+// Adjoint derivatives of a chunk on the DIRECT route (lockstep_hip.hip lockstep_direct_adjoint_chunk; include/osqp_hip.h
+// osqp_hip_batch_adjoint_lockstep_direct): LockstepAdjointParams as Engine::run_lockstep_adjoint fills them (cg_max and pcg_rel are not read: there is
+// no PCG), with LockstepDirectParams' view of A and the dense rows' data.
+struct LockstepDirectAdjointParams : LockstepAdjointParams {
+  int r = 0;                    // long rows (1 .. kWbMaxRows)
+  DevCsr Av;
+  const double *WT = nullptr; const int *rows = nullptr; const unsigned char *islong = nullptr;
+};
+// doubles of its work block: the direct forward's set, then x, dx, r_x (n), y, dy, r_y (m) and the row codes (m ints)
+inline size_t lockstep_direct_adjoint_ws_doubles(int n, int m, int r) {
+  return lockstep_direct_ws_doubles(n, m, r) + (size_t)kLsW * (3 * (size_t)n + 3 * (size_t)m + ((size_t)m + 1) / 2) + 64;
+}
+
 namespace be {
 
 // The direct route's chunk and the refresh of the view's values: weak as well (the host simulator declines).  stat[4]: ADMM iterations of the slowest
 // problem, inversions of S summed over the problems, kernel launches, GPU ms.
 int lockstep_direct_chunk(Dev &d, const LockstepDirectParams &p, void *stream, double *stat) __attribute__((weak));
 int lockstep_direct_values(Dev &d, int nv, const int *src, double *out, void *stream) __attribute__((weak));
+// The backward pass of such a chunk: weak as well.  stat[4]: recurrence steps of the slowest problem, inversions of S summed over the problems, kernel
+// launches, GPU ms.
+int lockstep_direct_adjoint_chunk(Dev &d, const LockstepDirectAdjointParams &p, void *stream, double *stat) __attribute__((weak));
 
 // Weak, like adjoint_*: the host simulator has no such kernels and the driver answers OSQP_FUNC_NOT_IMPLEMENTED where the symbol is absent.  One chunk,
 // start to finish, on `stream` (nullptr: d.stream); synchronises with that stream.  stat[4]: ADMM iterations of the slowest problem, PCG iterations

@@ -164,6 +164,8 @@ void Engine::free_all() {
   if (lsw_) { be::dfree(d_, lsw_); lsw_ = nullptr; }
   if (lsaw_) { be::dfree(d_, lsaw_); lsaw_ = nullptr; }
   if (lsdw_) { be::dfree(d_, lsdw_); lsdw_ = nullptr; }
+  if (lsdaw_) { be::dfree(d_, lsdaw_); lsdaw_ = nullptr; }
+  if (lsdabuf_) { be::dfree(d_, lsdabuf_); lsdabuf_ = nullptr; lsdabuf_cap_ = 0; }
   if (lsd_vval_) { be::dfree(d_, lsd_vval_); lsd_vval_ = nullptr; }
   if (lsd_vrp_) { be::dfree(d_, lsd_vrp_); be::dfree(d_, lsd_vcol_); be::dfree(d_, lsd_vsrc_); lsd_vrp_ = lsd_vcol_ = lsd_vsrc_ = nullptr; lsd_nv_ = 0; }
   wb_k0diag_ = false;

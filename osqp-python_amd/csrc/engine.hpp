@@ -75,6 +75,13 @@ class Engine {
   int batch_adjoint_lockstep_device(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
                                     double *dP, double *dq, double *dA, double *dl, double *du, double *arec, void *stream);
   int lockstep_adjoint_last_record(double *rec) const;
+  // The backward pass of a batch on the direct lockstep route (include/osqp_hip.h osqp_hip_batch_adjoint_lockstep_direct; lockstep_hip.hip
+  // lockstep_direct_adjoint_chunk): the same arguments and semantics on the handles batch_solve_lockstep_direct accepts, OSQP_FUNC_NOT_IMPLEMENTED elsewhere.
+  int batch_adjoint_lockstep_direct(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
+                                    double *dP, double *dq, double *dA, double *dl, double *du, double *arec);
+  int batch_adjoint_lockstep_direct_device(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
+                                           double *dP, double *dq, double *dA, double *dl, double *du, double *arec, void *stream);
+  int lockstep_direct_adjoint_last_record(double *rec) const;
   // Adjoint derivatives (include/osqp_hip.h osqp_hip_batch_adjoint; batch_hip.hip k_batch_adjoint): one launch for the batch.  Host arrays, or -- _device --
   // device arrays and a caller's stream with the semantics of batch_solve_device.  Px / Ax / l / u: nullptr = this solver's own values for every problem.
   int batch_adjoint(int nbatch, const double *Px, const double *Ax, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
@@ -149,6 +156,7 @@ class Engine {
   int *lsd_vrp_ = nullptr, *lsd_vcol_ = nullptr, *lsd_vsrc_ = nullptr; int lsd_nv_ = 0;
   double lsd_rec_[OSQP_HIP_LOCKSTEP_DIRECT_LAST_REC] = {0, 0, 0, 0, 0, 0, 0, 0};
   bool lockstep_direct_applies();
+  int prepare_lockstep_direct_view();                 // builds the view of A on first use (both directions of the direct route read it)
   int run_lockstep_direct(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream);
   double *lsaw_ = nullptr;                            // work block of one lockstep adjoint chunk (lockstep_adjoint_ws_doubles(n, m)), allocated on first use
   double *lsabuf_ = nullptr; size_t lsabuf_cap_ = 0;  // device scratch of batch_adjoint_lockstep (host-array entry point), kept across calls
@@ -157,6 +165,13 @@ class Engine {
   bool lockstep_adjoint_applies();
   int run_lockstep_adjoint(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
                            double *dP, double *dq, double *dA, double *dl, double *du, double *arec, void *stream);
+  // the backward pass on the direct route: its own work block (lockstep_direct_adjoint_ws_doubles(n, m, r)), host-entry scratch and record
+  double *lsdaw_ = nullptr;
+  double *lsdabuf_ = nullptr; size_t lsdabuf_cap_ = 0;
+  double lsda_rec_[OSQP_HIP_LOCKSTEP_DIRECT_ADJOINT_LAST_REC] = {0, 0, 0, 0, 0, 0, 0, 0};
+  bool lockstep_direct_adjoint_applies();
+  int run_lockstep_direct_adjoint(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
+                                  double *dP, double *dq, double *dA, double *dl, double *du, double *arec, void *stream);
   // what the four batch entry points begin with, and the host staging of the two that take host arrays (engine_api.cpp)
   bool batch_applies();                               // the workgroup route: the QP fits one workgroup's LDS and the handle is not reordered
   bool batch_applies_prepared();

@@ -958,24 +958,28 @@ bool Engine::lockstep_direct_applies() {
   return be::lockstep_direct_chunk && be::lockstep_direct_values && be::device_vec_updates() && d_.wb.on && !d_.wb.large && d_.wb.r >= 1 && d_.wb.r <= kWbMaxRows && wb_k0diag_ && !reordered_;
 }
 
+int Engine::prepare_lockstep_direct_view() {
+  if (lsd_vrp_) return OSQP_NO_ERROR;
+  // the view of A: a one-entry row keeps its entry (vsrc: where it sits in A.val), long row a becomes the entry 1.0 at column n + a
+  std::vector<int> vrp(m + 1, 0), vcol, vsrc;
+  int a = 0;
+  for (int i = 0; i < m; i++) {
+    if (Arp_[i + 1] - Arp_[i] > kLongRow) { vcol.push_back(n + a++); vsrc.push_back(-1); }
+    else for (int k = Arp_[i]; k < Arp_[i + 1]; k++) { vcol.push_back(Arj_[k]); vsrc.push_back(k); }
+    vrp[i + 1] = (int)vcol.size();
+  }
+  if (a != d_.wb.r) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  lsd_nv_ = (int)vcol.size();
+  lsd_vrp_ = dev_vec<int>(d_, m + 1); lsd_vcol_ = dev_vec<int>(d_, vcol.size()); lsd_vsrc_ = dev_vec<int>(d_, vsrc.size()); lsd_vval_ = dev_vec<double>(d_, vcol.size());
+  be::h2d(d_, lsd_vrp_, vrp.data(), sizeof(int) * (m + 1)); be::h2d(d_, lsd_vcol_, vcol.data(), sizeof(int) * vcol.size()); be::h2d(d_, lsd_vsrc_, vsrc.data(), sizeof(int) * vsrc.size());
+  be::sync(d_);
+  return OSQP_NO_ERROR;
+}
+
 int Engine::run_lockstep_direct(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream) {
   const int r = d_.wb.r;
   const size_t need = lockstep_direct_ws_doubles(n, m, r);
-  if (!lsd_vrp_) {
-    // the view of A: a one-entry row keeps its entry (vsrc: where it sits in A.val), long row a becomes the entry 1.0 at column n + a
-    std::vector<int> vrp(m + 1, 0), vcol, vsrc;
-    int a = 0;
-    for (int i = 0; i < m; i++) {
-      if (Arp_[i + 1] - Arp_[i] > kLongRow) { vcol.push_back(n + a++); vsrc.push_back(-1); }
-      else for (int k = Arp_[i]; k < Arp_[i + 1]; k++) { vcol.push_back(Arj_[k]); vsrc.push_back(k); }
-      vrp[i + 1] = (int)vcol.size();
-    }
-    if (a != r) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-    lsd_nv_ = (int)vcol.size();
-    lsd_vrp_ = dev_vec<int>(d_, m + 1); lsd_vcol_ = dev_vec<int>(d_, vcol.size()); lsd_vsrc_ = dev_vec<int>(d_, vsrc.size()); lsd_vval_ = dev_vec<double>(d_, vcol.size());
-    be::h2d(d_, lsd_vrp_, vrp.data(), sizeof(int) * (m + 1)); be::h2d(d_, lsd_vcol_, vcol.data(), sizeof(int) * vcol.size()); be::h2d(d_, lsd_vsrc_, vsrc.data(), sizeof(int) * vsrc.size());
-    be::sync(d_);
-  }
+  if (const int err = prepare_lockstep_direct_view()) return err;
   if (!lsdw_) { lsdw_ = dev_vec<double>(d_, need); be::sync(d_); }
   LockstepDirectParams p;
   fill_batch_settings(p, warm);
@@ -1110,6 +1114,91 @@ int Engine::lockstep_adjoint_last_record(double *rec) const {
   if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   if (!rec) return OSQP_DATA_VALIDATION_ERROR;
   std::copy(lsa_rec_, lsa_rec_ + OSQP_HIP_LOCKSTEP_ADJOINT_LAST_REC, rec);
+  return OSQP_NO_ERROR;
+}
+
+// ---- the backward pass on the direct route (lockstep_hip.hip lockstep_direct_adjoint_chunk): run_lockstep_adjoint's settings and chunking on the handles
+// lockstep_direct_applies accepts.  The recurrence's rho is fixed, so S_b is inverted once per problem.  The work block (lsdaw_) and the host entry's
+// scratch are this route's own; the view of A is the forward's (read only, its values refreshed per call); the handle's solve state, the forward route's
+// workspace and its record are not written.
+bool Engine::lockstep_direct_adjoint_applies() { return lockstep_direct_applies() && be::lockstep_direct_adjoint_chunk && be::device_assembly(); }
+
+int Engine::run_lockstep_direct_adjoint(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
+                                        double *dP, double *dq, double *dA, double *dl, double *du, double *arec, void *stream) {
+  const int r = d_.wb.r, nzP = d_.nzP, nzA = d_.nzA;
+  const size_t need = lockstep_direct_adjoint_ws_doubles(n, m, r);
+  if (const int err = prepare_lockstep_direct_view()) return err;
+  if (!lsdaw_) { lsdaw_ = dev_vec<double>(d_, need); be::sync(d_); }
+  LockstepDirectAdjointParams p;
+  fill_batch_settings(p, 0);
+  const double de = std::max(settings.delta, pol_.polish_delta_floor);
+  p.alpha = 1.0; p.rho0 = clamp_rho(1.0 / de); p.eq_factor = 1.0; p.cg_max = 0; p.pcg_rel = 0.0;
+  p.min_steps = 1 + std::max(0, (int)settings.polish_refine_iter); p.max_steps = 60; p.gain = 0.9;
+  p.n = n; p.m = m; p.A = d_.A; p.B = d_.B; p.D = d_.D; p.Dinv = d_.Dinv; p.E = d_.E; p.Einv = d_.Einv;
+  p.l0 = d_.lraw; p.u0 = d_.uraw; p.ws = lsdaw_;
+  p.nzP = nzP; p.nzA = nzA; p.Pi = d_.Pi; p.Pj = d_.Pj; p.Ai = d_.Ai; p.Aj = d_.Aj;
+  p.r = r; p.WT = d_.wb.WT; p.rows = d_.wb.rows; p.islong = d_.wb.islong;
+  p.Av = d_.A; p.Av.ncols = n + r; p.Av.nnz = lsd_nv_; p.Av.rowptr = lsd_vrp_; p.Av.col = lsd_vcol_; p.Av.val = lsd_vval_;
+  if (const int err = be::lockstep_direct_values(d_, lsd_nv_, lsd_vsrc_, lsd_vval_, stream)) return err;      // (A's values may have changed since the last call)
+  double tot[4] = {0, 0, 0, 0};
+  int chunks = 0;
+  auto at = [](auto *a, size_t off) { return a ? a + off : nullptr; };
+  for (int b0 = 0; b0 < nbatch; b0 += kLsW, chunks++) {
+    const size_t b = (size_t)b0;
+    p.count = std::min(kLsW, nbatch - b0);
+    p.l = at(l, b * m); p.u = at(u, b * m); p.sx = x + b * n; p.sy = at(y, b * m); p.gx = dx + b * n; p.gy = at(dy, b * m);
+    p.dP = at(dP, b * nzP); p.dq = at(dq, b * n); p.dA = at(dA, b * nzA); p.dl = at(dl, b * m); p.du = at(du, b * m); p.arec = at(arec, b * kAdjointRec);
+    double st[4] = {0, 0, 0, 0};
+    const int err = be::lockstep_direct_adjoint_chunk(d_, p, stream, st);
+    if (err) return err;
+    tot[0] = std::max(tot[0], st[0]); tot[1] += st[1]; tot[2] += st[2]; tot[3] += st[3];
+  }
+  const double rr[OSQP_HIP_LOCKSTEP_DIRECT_ADJOINT_LAST_REC] = {(double)chunks, (double)kLsW, tot[0], tot[1], tot[2], tot[3], (double)(need * sizeof(double)), 0.0};
+  std::copy(rr, rr + OSQP_HIP_LOCKSTEP_DIRECT_ADJOINT_LAST_REC, lsda_rec_);
+  return OSQP_NO_ERROR;
+}
+
+int Engine::batch_adjoint_lockstep_direct(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
+                                          double *dP, double *dq, double *dA, double *dl, double *du, double *arec) {
+  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (nbatch <= 0 || !x || (!y && m > 0) || !dx) return OSQP_DATA_VALIDATION_ERROR;
+  be::activate(d_);
+  if (!lockstep_direct_adjoint_applies()) return OSQP_FUNC_NOT_IMPLEMENTED;
+  be::ext_wait(d_);
+  const size_t nb = (size_t)nbatch, N = nb * n, M = nb * m, NP = nb * (size_t)d_.nzP, NA = nb * (size_t)d_.nzA;
+  // one device scratch block, kept for the next call: [l | u | x | y | dx | dy | dP | dq | dA | dl | du | arec]
+  const size_t need = 3 * N + 6 * M + NP + NA + nb * kAdjointRec;
+  if (need > lsdabuf_cap_) { if (lsdabuf_) be::dfree(d_, lsdabuf_); lsdabuf_cap_ = 0; lsdabuf_ = dev_vec<double>(d_, need); lsdabuf_cap_ = need; }
+  double *d_l = lsdabuf_, *d_u = d_l + M, *d_x = d_u + M, *d_y = d_x + N, *d_dx = d_y + M, *d_dy = d_dx + N;
+  double *o_dP = d_dy + M, *o_dq = o_dP + NP, *o_dA = o_dq + N, *o_dl = o_dA + NA, *o_du = o_dl + M, *o_rec = o_du + M;
+  auto up = [&](double *dst, const double *src, size_t cnt) { if (src && cnt) be::h2d(d_, dst, src, sizeof(double) * cnt); };
+  up(d_l, l, M); up(d_u, u, M); up(d_x, x, N); up(d_y, y, M); up(d_dx, dx, N); up(d_dy, dy, M);
+  be::sync(d_);
+  const int err = run_lockstep_direct_adjoint(nbatch, l ? d_l : nullptr, u ? d_u : nullptr, d_x, d_y, d_dx, dy ? d_dy : nullptr, dP ? o_dP : nullptr, dq ? o_dq : nullptr,
+                                              dA ? o_dA : nullptr, dl ? o_dl : nullptr, du ? o_du : nullptr, arec ? o_rec : nullptr, nullptr);
+  if (err) return err;
+  auto down = [&](double *dst, const double *src, size_t cnt) { if (dst && cnt) be::d2h(d_, dst, src, sizeof(double) * cnt); };
+  down(dP, o_dP, NP); down(dq, o_dq, N); down(dA, o_dA, NA); down(dl, o_dl, M); down(du, o_du, M); down(arec, o_rec, nb * kAdjointRec);
+  return OSQP_NO_ERROR;
+}
+
+int Engine::batch_adjoint_lockstep_direct_device(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
+                                                 double *dP, double *dq, double *dA, double *dl, double *du, double *arec, void *stream) {
+  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (nbatch < 0) return OSQP_DATA_VALIDATION_ERROR;
+  be::activate(d_);
+  if (!lockstep_direct_adjoint_applies()) return OSQP_FUNC_NOT_IMPLEMENTED;
+  if (nbatch == 0) return OSQP_NO_ERROR;              // (the applicability query)
+  if (!x || (!y && m > 0) || !dx) return OSQP_DATA_VALIDATION_ERROR;
+  be::ext_wait(d_);
+  be::sync(d_);                                       // the solver's own stream first: pending updates of the resident l / u, the matrices
+  return run_lockstep_direct_adjoint(nbatch, l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec, stream);
+}
+
+int Engine::lockstep_direct_adjoint_last_record(double *rec) const {
+  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (!rec) return OSQP_DATA_VALIDATION_ERROR;
+  std::copy(lsda_rec_, lsda_rec_ + OSQP_HIP_LOCKSTEP_DIRECT_ADJOINT_LAST_REC, rec);
   return OSQP_NO_ERROR;
 }
 

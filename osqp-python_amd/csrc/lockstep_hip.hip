@@ -953,6 +953,20 @@ __global__ __launch_bounds__(256) void k_lw_x(LwK k) {
 __global__ __launch_bounds__(256) void k_lw_vals(int nv, const int *src, const double *Aval, double *out) {
   for (int e = blockIdx.x * 256 + threadIdx.x; e < nv; e += gridDim.x * 256) out[e] = src[e] >= 0 ? Aval[src[e]] : 1.0;
 }
+// ---- the backward pass of the direct route (lockstep_direct_adjoint_chunk below).  "adjoint derivatives of a chunk" with the PCG replaced by the solve
+// above: rho never changes in the recurrence (alpha = 1, rho_bar = 1 / delta_eff on the active rows, rho_min on the others), so S_b is formed and
+// inverted ONCE per problem.  The kernels are those two sections'; what they do not cover is the two below.
+// the rows n .. n + r - 1 of `dst` from ONE set of k_lw_prod's partials (pg), folded in block order, for every lane: a wave per row
+__global__ __launch_bounds__(256) void k_lwa_setl(LwK k, double *dst) {
+  const int lane = ls_lane(), r = k.d.r;
+  for (int a = (int)blockIdx.x * 4 + ls_wave(); a < r; a += (int)gridDim.x * 4)
+    dst[IX(k.P.n + a)] = lw_fold(k.d.pg + (size_t)a * 64 + lane, k.d.GC, (size_t)r * 64);
+}
+// the zero start over n + r rows: x = x~ = dx = 0 (k_ls_adj_load_n has the first n rows only, and x~ has held the classification's operand since)
+__global__ __launch_bounds__(256) void k_lwa_zero(LwK k) {
+  const size_t tot = (size_t)(k.P.n + k.d.r) * 64;
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < tot; e += (size_t)gridDim.x * 256) { k.w.x[e] = 0.0; k.w.xs[e] = 0.0; k.w.dx[e] = 0.0; }
+}
 #undef IX
 
 }  // namespace
@@ -1196,6 +1210,106 @@ int lockstep_direct_chunk(Dev &d, const LockstepDirectParams &p, void *stream, d
   long nfact = 0;
   for (int b = 0; b < W; b++) nfact += fact[b];
   if (stat) { stat[0] = iter; stat[1] = (double)nfact; stat[2] = (double)launches; stat[3] = ms; }
+  return OSQP_NO_ERROR;
+}
+
+// The backward pass of one chunk on the DIRECT route, from the transposes in to the transposes out, on `stream` (nullptr: the solver's); returns when the
+// chunk's results are there.  The sequence is lockstep_adjoint_chunk's with lockstep_direct_chunk's solve in place of the PCG; the work block is the direct
+// forward's set followed by the adjoint's own vectors.  The classification's operand x~ = Dinv x sits in the block vector x~ (n + r rows; its last r
+// from the products), so that k_ls_adj_class reads A through the view like every other row pass here; x, x~ and dx are zeroed over n + r rows afterwards.
+// rho is set, and S formed and inverted, once; a step is eleven launches and one read of the word block.  A pivot of S_b that is not positive and finite
+// leaves NaN iterates in that lane alone: its residual is not below the threshold and it ends with status 3.
+// stat: {recurrence steps of the slowest problem, inversions of S summed over the problems, kernel launches, GPU ms}.
+int lockstep_direct_adjoint_chunk(Dev &d, const LockstepDirectAdjointParams &p, void *stream, double *stat) {
+  HIP_CHECK(hipSetDevice(d.device));
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : st(d);
+  const int n = p.n, m = p.m, r = p.r, G = lockstep_grid(n, m), tn = (n + 63) / 64, tm = (m + 63) / 64;
+  if (r < 1 || r > kWbMaxRows || m < 1) return OSQP_FUNC_NOT_IMPLEMENTED;
+  const int cb = lockstep_direct_colblock(n), GC = (n + cb - 1) / cb;
+  const size_t nW = (size_t)n * W, mW = (size_t)m * W, xW = (size_t)(n + r) * W;
+  LwK k{p, {}, {}};
+  LsWs &w = k.w;
+  double *c = p.ws;
+  auto take = [&c](size_t cnt) { double *q = c; c += cnt; return q; };
+  w.x = take(xW); w.xs = take(xW); w.dx = take(xW); w.r = take(nW); w.p = take(nW); w.q = take(nW); w.Minv = take(nW); w.Kp = nullptr;
+  w.z = take(mW); w.y = take(mW); w.t = take(mW); w.t2 = take(mW); w.l = take(mW); w.u = take(mW); w.rho = take(mW); w.zt = take(mW); w.dy = take(mW);
+  w.part = take((size_t)kLsSlots * G * W); w.parti = take((size_t)tm * W); w.sc = take((size_t)kLsScal * W); w.rec = take((size_t)W * kBatchRec);
+  w.iw = reinterpret_cast<int *>(take((size_t)kLsInt * W / 2)); w.word = w.iw + IW_COUNT * W;
+  w.G = G;
+  LwWs &x = k.d;
+  x.S = take((size_t)r * r * W); x.pg = take((size_t)GC * r * W); x.pg2 = take((size_t)GC * r * W); x.h = take((size_t)r * W);
+  x.fact = reinterpret_cast<int *>(take(W / 2));
+  x.WT = p.WT; x.rows = p.rows; x.islong = p.islong; x.r = r; x.GC = GC; x.cb = cb;
+  if ((size_t)(c - p.ws) > lockstep_direct_ws_doubles(n, m, r)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  c = p.ws + lockstep_direct_ws_doubles(n, m, r);
+  LsAK ka{p, w, {}};
+  LsAdjWs &a = ka.a;
+  a.ax = take(nW); a.gdx = take(nW); a.rx = take(nW); a.ay = take(mW); a.gdy = take(mW); a.ry = take(mW); a.code = reinterpret_cast<int *>(take((mW + 1) / 2));
+  if ((size_t)(c - p.ws) > lockstep_direct_adjoint_ws_doubles(n, m, r)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  const size_t lds_inv = sizeof(double) * ((size_t)r * r + r), lds_h = sizeof(double) * (size_t)r * 64;
+  if (lds_inv > 64 * 1024) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_lw_inv), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_inv));
+  // the forward's kernels as lockstep_direct_chunk calls them: kb as the handle is, kv through the view, ku through the view with n + r rows of x
+  const LsK kb{p, w};
+  LsK kv = kb; kv.P.A = p.Av;
+  LsK ku = kv; ku.P.n = n + r;
+  // the adjoint's: kl makes k_ls_adj_load_n put x~ = Dinv x where k_ls_adj_class, through the view (kc), will gather it -- the first n rows of the block
+  // vector x~ -- by exchanging the roles of p and x~ (the zeros then go to p, which k_ls_rhs overwrites)
+  LsAK kl = ka; kl.w.p = w.xs; kl.w.xs = w.p;
+  LsAK kc = ka; kc.P.A = p.Av; kc.w.p = w.xs;
+  long launches = 0;
+  auto go = [&](auto kern, int grid, const LsK &q) { hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, q); launches++; };
+  auto goa = [&](auto kern, int grid, const LsAK &q) { hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, q); launches++; };
+  auto gow = [&](auto kern, int grid, size_t lds, auto... args) { hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, k, args...); launches++; };
+  struct Ev { hipEvent_t e = nullptr; ~Ev() { if (e) (void)hipEventDestroy(e); } } ev0, ev1;      // (destroyed on every way out: HIP_CHECK throws)
+  HIP_CHECK(hipEventCreate(&ev0.e)); HIP_CHECK(hipEventCreate(&ev1.e));
+  const hipEvent_t e0 = ev0.e, e1 = ev1.e;
+  HIP_CHECK(hipEventRecord(e0, s));
+  int words[WD_COUNT] = {0, p.count, 0, 0, 0};
+  auto fetch = [&]() { HIP_CHECK(hipMemcpyAsync(words, w.word, sizeof(words), hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s)); };
+  auto long_rows_of = [&](double *v) { gow(k_lw_prod, GC, 0, (const double *)v, x.pg); gow(k_lwa_setl, (r + 3) / 4, 0, v); };
+
+  HIP_CHECK(hipMemsetAsync(x.fact, 0, sizeof(int) * W, s));
+  goa(k_ls_adj_load_n, tn, kl);
+  goa(k_ls_adj_load_m, tm, ka);
+  long_rows_of(w.xs);
+  goa(k_ls_adj_class, G, kc);
+  goa(k_ls_adj_init, 1, ka);
+  gow(k_lwa_zero, G, 0);
+  go(k_ls_setrho, G, kb); gow(k_lw_d0, G, 0); gow(k_lw_s, r * ((r + 7) / 8), 0); gow(k_lw_inv, W, lds_inv);
+  fetch();
+  int step = 0;
+  while (words[WD_LIVE] > 0 && step < p.max_steps) {
+    step++;
+    go(k_ls_rhs, G, kb);
+    gow(k_lw_prod, GC, 0, (const double *)w.p, x.pg);
+    gow(k_lw_h, (r + 15) / 16, lds_h);
+    gow(k_lw_x, G, lds_h);
+    go(k_ls_upd, G, ku);
+    gow(k_lw_prod, GC, 0, (const double *)w.x, x.pg); gow(k_lw_prod, GC, 0, (const double *)w.xs, x.pg2); gow(k_lw_setl, 1, 0, 0);
+    go(k_ls_resm, G, kv);
+    go(k_ls_resn, G, kb);
+    goa(k_ls_adj_decide, 1, ka);
+    fetch();
+  }
+  goa(k_ls_adj_unscale, G, ka);
+  long_rows_of(w.x);
+  goa(k_ls_adj_resm, G, kc);
+  goa(k_ls_adj_resn, G, ka);
+  goa(k_ls_adj_final, 1, ka);
+  if (p.dq) goa(k_ls_adj_out_n, tn, ka);
+  if (p.dl || p.du) goa(k_ls_adj_out_m, tm, ka);
+  if (p.dP && p.nzP > 0) goa(k_ls_adj_grad<true>, (p.nzP + 63) / 64, ka);
+  if (p.dA && p.nzA > 0) goa(k_ls_adj_grad<false>, (p.nzA + 63) / 64, ka);
+  HIP_CHECK(hipEventRecord(e1, s));
+  int fact[W];
+  HIP_CHECK(hipMemcpyAsync(fact, x.fact, sizeof(fact), hipMemcpyDeviceToHost, s));
+  fetch();
+  float ms = 0.f;
+  HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+  HIP_CHECK(hipGetLastError());
+  long nfact = 0;
+  for (int b = 0; b < W; b++) nfact += fact[b];
+  if (stat) { stat[0] = step; stat[1] = (double)nfact; stat[2] = (double)launches; stat[3] = ms; }
   return OSQP_NO_ERROR;
 }
 

@@ -513,6 +513,10 @@ class OSQPSolver:
         """hip_batch_adjoint for problems of ANY size (osqp_hip_batch_adjoint_lockstep): shared P / A, 64 problems at a time on block vectors, every
         adjoint system by the recurrence of the single-handle PCG route.  Same arguments (no Px / Ax), same checks, same returns; the columns of 'rec'
         are LOCKSTEP_ADJOINT_FIELDS."""
+        return self._adjoint_lockstep_host(self._lib.osqp_hip_batch_adjoint_lockstep, x, y, dx, dy, l, u, want)
+
+    def _adjoint_lockstep_host(self, entry, x, y, dx, dy, l, u, want):
+        """The host-array call of a lockstep adjoint route (`entry`: its C entry point): widths checked here, then the engine."""
         if x is None or y is None or dx is None:
             raise ValueError('x, y and dx are required')
         x = np.ascontiguousarray(x, dtype=np.float64)
@@ -530,8 +534,8 @@ class OSQPSolver:
         out = {k: (np.zeros((B, widths[k])) if k in want else None) for k in widths}
         rec = np.zeros((B, self.ADJOINT_REC))
         dp = _lib.c_double_p
-        st = self._lib.osqp_hip_batch_adjoint_lockstep(self._p, B, _ptr(l, dp), _ptr(u, dp), _ptr(x, dp), _ptr(y, dp), _ptr(dx, dp), _ptr(dy, dp),
-                                                       _ptr(out['dP'], dp), _ptr(out['dq'], dp), _ptr(out['dA'], dp), _ptr(out['dl'], dp), _ptr(out['du'], dp), _ptr(rec, dp))
+        st = entry(self._p, B, _ptr(l, dp), _ptr(u, dp), _ptr(x, dp), _ptr(y, dp), _ptr(dx, dp), _ptr(dy, dp),
+                   _ptr(out['dP'], dp), _ptr(out['dq'], dp), _ptr(out['dA'], dp), _ptr(out['dl'], dp), _ptr(out['du'], dp), _ptr(rec, dp))
         if st:
             raise self._batch_error(st)
         res = {k: v for k, v in out.items() if v is not None}
@@ -558,6 +562,36 @@ class OSQPSolver:
             raise ValueError(str(int(st)))
         out = dict(zip(self.LOCKSTEP_ADJOINT_LAST_FIELDS, rec.tolist()))
         for k in ('chunks', 'width', 'steps_max', 'pcg_iters', 'kernel_launches', 'workspace_bytes'):
+            out[k] = int(out[k])
+        return out
+
+    def hip_batch_adjoint_lockstep_direct(self, x, y, dx, dy=None, l=None, u=None, want=('dP', 'dq', 'dA', 'dl', 'du')):
+        """hip_batch_adjoint_lockstep for the handles it declines (osqp_hip_batch_adjoint_lockstep_direct): the backward pass of
+        hip_batch_solve_lockstep_direct, on the handles that call accepts -- the recurrence's linear solve is the Woodbury formula per problem, S inverted
+        once.  Same arguments, same checks, same returns; every other handle raises ValueError with OSQP_FUNC_NOT_IMPLEMENTED."""
+        return self._adjoint_lockstep_host(self._lib.osqp_hip_batch_adjoint_lockstep_direct, x, y, dx, dy, l, u, want)
+
+    def hip_batch_adjoint_lockstep_direct_device(self, nbatch, x_ptr, y_ptr, dx_ptr, dy_ptr=None, l_ptr=None, u_ptr=None,
+                                                 dP_ptr=None, dq_ptr=None, dA_ptr=None, dl_ptr=None, du_ptr=None, rec_ptr=None, stream=None):
+        """osqp_hip_batch_adjoint_lockstep_direct_device: raw device addresses (int or None) laid out as in hip_batch_adjoint_lockstep; the work goes on
+        `stream` (None: the solver's) and the call returns when the results are there.  nbatch == 0: does the route apply?"""
+        st = self._lib.osqp_hip_batch_adjoint_lockstep_direct_device(self._p, int(nbatch), l_ptr, u_ptr, x_ptr, y_ptr, dx_ptr, dy_ptr,
+                                                                     dP_ptr, dq_ptr, dA_ptr, dl_ptr, du_ptr, rec_ptr, stream)
+        if st:
+            raise self._batch_error(st)
+
+    # OSQP_HIP_LOCKSTEP_DIRECT_ADJOINT_LAST_REC doubles of osqp_hip_lockstep_direct_adjoint_last_record
+    LOCKSTEP_DIRECT_ADJOINT_LAST_FIELDS = ('chunks', 'width', 'steps_max', 'inversions', 'kernel_launches', 'gpu_ms', 'workspace_bytes', 'reserved')
+
+    def lockstep_direct_adjoint_last_record(self):
+        """osqp_hip_lockstep_direct_adjoint_last_record as a dict (LOCKSTEP_DIRECT_ADJOINT_LAST_FIELDS): what the last direct lockstep adjoint call of this
+        handle did; zeros before the first."""
+        rec = np.zeros(len(self.LOCKSTEP_DIRECT_ADJOINT_LAST_FIELDS))
+        st = self._lib.osqp_hip_lockstep_direct_adjoint_last_record(self._p, _ptr(rec, _lib.c_double_p))
+        if st:
+            raise ValueError(str(int(st)))
+        out = dict(zip(self.LOCKSTEP_DIRECT_ADJOINT_LAST_FIELDS, rec.tolist()))
+        for k in ('chunks', 'width', 'steps_max', 'inversions', 'kernel_launches', 'workspace_bytes'):
             out[k] = int(out[k])
         return out
 

@@ -30,7 +30,9 @@ batch kernel cannot hold (its forward ran one element after the other on the han
 (``osqp_hip_adjoint_compute_at``: the PCG route for large QPs, at the (x, y) the forward kept) once per element, ``adjoint_launches`` counting every call, shared inputs receiving
 the batch sum -- or, with ``large_backward='lockstep'`` (default ``'loop'``: unchanged) and shared P_val / A_val, ONE call of the lockstep adjoint for the whole batch
 (``osqp_hip_batch_adjoint_lockstep``; ``adjoint_launches`` rises by 1; an element whose adjoint system was not solved raises RuntimeError as the
-per-element route does).  A ``torch.distributed`` job (world size > 1) raises NotImplementedError in backward.  With no input requiring grad,
+per-element route does), or, with ``large_backward='lockstep_direct'``, ONE call of its direct form on a Woodbury handle with a diagonal K0
+(``osqp_hip_batch_adjoint_lockstep_direct``: the backward of ``large_batch='lockstep_direct'``; a handle the route declines goes on to the per-element
+loop, as with ``'lockstep'``).  A ``torch.distributed`` job (world size > 1) raises NotImplementedError in backward.  With no input requiring grad,
 forward behaves exactly as before.
 """
 import numpy as np
@@ -58,9 +60,9 @@ class OSQP(Module):
         super().__init__()
         if large_batch not in ('loop', 'lockstep', 'lockstep_direct'):
             raise ValueError("large_batch: 'loop', 'lockstep' or 'lockstep_direct'")
-        if large_backward not in ('loop', 'lockstep'):
-            raise ValueError("large_backward: 'loop' or 'lockstep'")
-        self.large_backward = large_backward   # backward of such a batch: the single-handle adjoint per element ('loop'), or one call of the lockstep adjoint
+        if large_backward not in ('loop', 'lockstep', 'lockstep_direct'):
+            raise ValueError("large_backward: 'loop', 'lockstep' or 'lockstep_direct'")
+        self.large_backward = large_backward   # backward of such a batch: the single-handle adjoint per element ('loop'), or one call of the lockstep adjoint / its direct form for Woodbury handles
         self.large_batch = large_batch   # shared matrices too large for the batch kernel: one element after the other ('loop'), the lockstep route, or its direct form for Woodbury handles ('lockstep_direct')
         self.P_idx, self.P_shape, self.A_idx, self.A_shape = P_idx, P_shape, A_idx, A_shape
         self.eps_rel, self.eps_abs, self.verbose, self.max_iter = eps_rel, eps_abs, verbose, max_iter
@@ -272,10 +274,13 @@ class OSQP(Module):
         return {k: torch.as_tensor(v) for k, v in res.items()}
 
     def _backward_lockstep(self, ext, l_val, u_val, x, y, g, nb, want):
-        """Backward of a shared-matrix batch past the batch adjoint kernel, with large_backward='lockstep': one call of the lockstep adjoint for the whole
-        batch (cuda tensors: zero-copy through the device entry on torch's current stream).  An element whose adjoint system was not solved raises as
+        """Backward of a shared-matrix batch past the batch adjoint kernel, with large_backward='lockstep' or 'lockstep_direct': one call of the lockstep
+        adjoint (or of its direct form) for the whole batch (cuda tensors: zero-copy through the device entry on torch's current stream).  An element whose adjoint system was not solved raises as
         _backward_loop does.  None: this handle is not on the route (the caller goes on to the per-element loop)."""
         widths = {'dP': len(self._triu_pick), 'dq': self.n, 'dA': ext.nnz_A, 'dl': self.m, 'du': self.m}
+        direct = self.large_backward == 'lockstep_direct'
+        host_entry = ext.hip_batch_adjoint_lockstep_direct if direct else ext.hip_batch_adjoint_lockstep
+        device_entry = ext.hip_batch_adjoint_lockstep_direct_device if direct else ext.hip_batch_adjoint_lockstep_device
         try:
             if g.is_cuda:
                 dev = g.device
@@ -284,13 +289,13 @@ class OSQP(Module):
                 res = {k: torch.empty((nb, widths[k]), dtype=torch.float64, device=dev) for k in want}
                 res['rec'] = torch.empty((nb, 4), dtype=torch.float64, device=dev)     # OSQP_HIP_ADJOINT_REC
                 ptr = lambda t: None if t is None else t.data_ptr()
-                ext.hip_batch_adjoint_lockstep_device(nb, xd.data_ptr(), yd.data_ptr(), gd.data_ptr(), None, ld.data_ptr(), ud.data_ptr(),
-                                                      ptr(res.get('dP')), ptr(res.get('dq')), ptr(res.get('dA')), ptr(res.get('dl')), ptr(res.get('du')),
-                                                      res['rec'].data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
+                device_entry(nb, xd.data_ptr(), yd.data_ptr(), gd.data_ptr(), None, ld.data_ptr(), ud.data_ptr(),
+                             ptr(res.get('dP')), ptr(res.get('dq')), ptr(res.get('dA')), ptr(res.get('dl')), ptr(res.get('du')),
+                             res['rec'].data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
             else:
                 bc = lambda a, k: np.broadcast_to(np.asarray(a, dtype=float).reshape(-1, k), (nb, k))
-                res = ext.hip_batch_adjoint_lockstep(bc(_np(torch.as_tensor(x)), self.n), bc(_np(torch.as_tensor(y)), self.m), bc(_np(g), self.n), None,
-                                                     l=bc(_np(l_val), self.m), u=bc(_np(u_val), self.m), want=want)
+                res = host_entry(bc(_np(torch.as_tensor(x)), self.n), bc(_np(torch.as_tensor(y)), self.m), bc(_np(g), self.n), None,
+                                 l=bc(_np(l_val), self.m), u=bc(_np(u_val), self.m), want=want)
                 res = {k: torch.as_tensor(v) for k, v in res.items()}
         except ValueError as e:
             if str(e) != str(int(osqp_amd.SolverError.OSQP_FUNC_NOT_IMPLEMENTED)):
@@ -349,8 +354,8 @@ class OSQP(Module):
             if str(e) != str(int(osqp_amd.SolverError.OSQP_FUNC_NOT_IMPLEMENTED)):
                 raise
             res = None
-            if self.large_backward == 'lockstep' and not batched[0] and not batched[2]:
-                res = self._backward_lockstep(s._solver, l_val, u_val, x, y, g, nb, want)      # shared matrices, any size: ONE call (osqp_hip_batch_adjoint_lockstep)
+            if self.large_backward in ('lockstep', 'lockstep_direct') and not batched[0] and not batched[2]:
+                res = self._backward_lockstep(s._solver, l_val, u_val, x, y, g, nb, want)      # shared matrices, any size: ONE call (osqp_hip_batch_adjoint_lockstep[_direct])
         if res is None:
             # outside the batch kernel (the forward ran _loop): the single-handle adjoint per element
             bc = lambda a, k: np.broadcast_to(np.asarray(a, dtype=float).reshape(-1, k), (nb, k))

@@ -1,4 +1,4 @@
-"""Device-memory leak check: repeated setup / solve / update / batch / direct lockstep batch / linsys / cleanup cycles must not grow the allocation."""
+"""Device-memory leak check: repeated setup / solve / update / batch / direct lockstep batch / linsys / cleanup cycles must not grow the allocation (the direct lockstep batch with one backward call)."""
 import gc, os, sys, warnings
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, 'osqp-python_amd'), ROOT]
@@ -22,7 +22,7 @@ for cyc in range(6):
         del m
         s = osqp_amd.OSQP(); s.setup(Pm, qm, Am, L[0], U[0], verbose=False); s._solver.hip_batch_solve(l=L, u=U); del s
         w = osqp_amd.OSQP(); w.setup(Pl, ql, Al, ll, ul, verbose=False, max_iter=400); w.solve(); w.update(q=ql * 1.01); w.solve(); del w
-        d = osqp_amd.OSQP(); d.setup(Pp, qp, Ap, lp, up, verbose=False, max_iter=400); d._solver.hip_batch_solve_lockstep_direct(q=Qp); d._solver.hip_batch_solve_lockstep_direct(q=Qp[:3]); del d
+        d = osqp_amd.OSQP(); d.setup(Pp, qp, Ap, lp, up, verbose=False, max_iter=400); xd, yd, _ = d._solver.hip_batch_solve_lockstep_direct(q=Qp); d._solver.hip_batch_solve_lockstep_direct(q=Qp[:3]); d._solver.hip_batch_adjoint_lockstep_direct(xd, yd, xd); del d
         ls = LinSysSolver(sp.csc_matrix(P), sp.csc_matrix(A), np.full(A.shape[0], 0.1), polishing=True, cg_max_iter=200); ls.solve(np.ones(P.shape[0] + A.shape[0])); ls.free(); del ls
     gc.collect()
     now = used()
