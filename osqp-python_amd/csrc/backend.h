@@ -83,7 +83,7 @@ struct DevF1 {
   int D = 0;                     // replicas
   int *blk = nullptr;            // nblk(A) x 16 words, one scalar load per block:
                                  //   {first row, end row, first entry, end entry}  (the block's descriptor in A)
-                                 //   {cov0, cov1, cs0, cs1}: replica coverage [cov0, cov1) (zero outside the window), own columns [cs0, cs1)
+                                 //   {cov0, cov1, cs0, cs1}: replica coverage [cov0, cov1) (zero outside the window: zeroed by upload_f1, never stored by a kernel), own columns [cs0, cs1)
                                  //   {offset of the block's column pointers in cptr, first and end entry of its own rows in the P arrays, far columns (mix)}
                                  //   {g0, gl, a0, wl}: gather window [g0, g0 + gl) (columns of the block's rows of A -- plus those of its own
                                  //   rows of P if that widens it by at most a quarter), scatter window [a0, a0 + wl) (columns of its rows of A)

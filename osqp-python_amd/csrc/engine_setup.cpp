@@ -324,6 +324,9 @@ void Engine::upload_f1(const F1Plan &pl, const std::vector<int> &Arp) {
   f.ns = ns; f.nsb = (unsigned)(8 * ns);
   f.va = dev_vec<double>(d_, at / 8); f.vbytes = (unsigned)at;
   unsigned char *ab = reinterpret_cast<unsigned char *>(f.va);
+  // the 3 D replica vectors start as zeros and the kernels store a block's scatter window only: a replica's columns between the windows of its
+  // blocks (the records' coverage [cov0, cov1) outside [a0, a0 + wl)) are read by every gather and written by nobody after this
+  be::zero(d_, f.va + 7 * ns, 8 * 3 * (size_t)pl.D * ns);
   f.o_rho = (unsigned)o_rho; f.o_pval = (unsigned)o_pval; f.o_pcol = (unsigned)o_pcol; f.o_prp = (unsigned)o_prp; f.o_rowptr = (unsigned)o_rowptr; f.o_cptr = (unsigned)o_cptr;
   f.pval = reinterpret_cast<double *>(ab + o_pval); f.pcol = reinterpret_cast<int *>(ab + o_pcol); f.prp = reinterpret_cast<int *>(ab + o_prp);
   f.cptr = reinterpret_cast<unsigned short *>(ab + o_cptr);

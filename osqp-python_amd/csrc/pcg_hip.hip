@@ -809,19 +809,31 @@ __device__ __forceinline__ void f1_body(const Dev &d, const int k, const bool ve
     const F1Rec rec = sl == slot0 ? rec0 : f1_record(f, b);      // (the first block's record was requested before the scalar fold)
     const int4 ds = rec.ds, fa = rec.fa, fb = rec.fb, fc = rec.fc;
     const int r0 = ds.x, nrows = ds.y - ds.x, k0 = ds.z, cnt = ds.w - ds.z;
-    const int cov0 = fa.x, cov1 = fa.y, cs0 = fa.z, nown = fa.w - fa.z;
+    const int cs0 = fa.z, nown = fa.w - fa.z;
     const int cpo = fb.x, pk0 = fb.y, pcnt = fb.z - fb.y;
     const int g0 = fc.x, gl = vec_only ? 0 : fc.y, a0 = fc.z, wl = fc.w;      // gather window [g0, g0 + gl), scatter window [a0, a0 + wl)
     // MIX: the block's far columns sit in the LAST kF1MaxFar slots of the gather list and of the column-ordered pass (slots kFB ..): which lanes
     // serve them does not depend on the record (their loads were requested before it arrived)
     const int nfc = MIX && !vec_only ? fb.w : 0;
-    const int nw = nfc ? CW : (gl + kBlock - 1) / kBlock, nu = (cnt + kBlock - 1) / kBlock, ns2 = nfc ? CW : (wl + kBlock - 1) / kBlock;
+    const int nu = (cnt + kBlock - 1) / kBlock, ns2 = nfc ? CW : (wl + kBlock - 1) / kBlock;
+    // The window's requests are issued per WAVE: a wave whose 64 lanes would all be clamped for a window element (at a window of 257 - 320 columns:
+    // waves 1 - 3 of the second element) requests, stages and stores nothing for it -- every request is a wave instruction through the CU's one
+    // vector-memory path, whatever its lanes address.  The predicates are wave-uniform (scalar branches), derived where they are used from the
+    // record's scalars and the wave's first lane index; inside an active wave the lanes still clamp.
+    // (Only the window: the same predicates on the column pointers, the row stage, the prp pairs and the (P + sigma I) entry -- one or two requests
+    //  each, pinned before the barrier -- made the launch SLOWER, 11.45 -> 12.4 us, DESIGN.md section 8: those stay workgroup-wide.)
+    const int wv0 = __builtin_amdgcn_readfirstlane(tid & ~63);
+    // gather group u: a window column, or (MIX) a far slot -- the far slots belong to the last window element
+    auto gather_on = [&](int u) { const int ew = wv0 + u * kBlock; return ew < gl || (MIX && nfc > 0 && u == CW - 1 && ew + 63 >= kFB && ew < kFB + nfc); };
+    // ... and one of its window columns is an own column (far slots never are): the wave's columns [g0 + ew, g0 + min(ew + 63, gl - 1)] meet [cs0, cs0 + nown)
+    auto own_on = [&](int u) { const int ew = wv0 + u * kBlock; return ew < gl && g0 + ew < cs0 + nown && g0 + min(ew + 63, gl - 1) >= cs0; };
     KT(2);
     // ---- loads.  First the (P + sigma I) entry of this lane: its column decides whether the operand comes from the window or has
     //      to be recomputed from its parts (columns outside the window), and those loads should leave with the window's, not after it
-    // (every request of this stage is unconditional and its destination is written by nothing else: a default value assigned first makes the
-    //  compiler guard the register at the loop's head with `s_waitcnt vmcnt(0)` -- which also sits out the next block's stream and the previous
-    //  block's stores.  The last budgeted update (vec_only) requests a few values it does not use.)
+    // (the destination of every request of this stage is written by nothing else, and a request a wave skips gets NO default value -- its consumers
+    //  sit behind the same predicate: a default assigned first makes the compiler guard the register at the loop's head with `s_waitcnt vmcnt(0)` --
+    //  which also sits out the next block's stream and the previous block's stores.  The last budgeted update (vec_only) requests a few values it
+    //  does not use.)
     const bool hasp = !vec_only && tid < pcnt;
     const int pe = min(pk0 + max(0, min(tid, pcnt - 1)), f.pnnz - 1);
     const double pv = ar.d(8u * pe, f.o_pval); const int pc = ar.i(4u * pe, f.o_pcol);
@@ -832,25 +844,28 @@ __device__ __forceinline__ void f1_body(const Dev &d, const int k, const bool ve
 #pragma unroll
     for (int u = 0; u < CW; u++) {
       wown[u] = false;
-      if (u < nw) {
+      if (gather_on(u)) {
         const int e = tid + u * kBlock;
         int c = g0 + min(e, gl - 1);
         if constexpr (MIX) { const bool isfar = u == CW - 1 && e >= kFB && e - kFB < nfc; if (isfar) c = fcl.x; wsw[u] = isfar ? fcl.y : spk[c]; }
-        wown[u] = e < gl && c >= cs0 && c - cs0 < nown;
         wm[u] = ar.d(8u * c, 0);
 #pragma unroll
         for (int q = 0; q < D; q++) wq[u][q] = ar.d(8u * c, orep + q * nsb);
-        const int co = wown[u] ? c : g0;                    // (other lanes re-read one valid element: no branch around the loads)
         if (!FIRST) {
           wr[u] = ar.d(8u * c, orr);
           wsv[u] = ar.d(8u * c, osp);
-          wx[u] = ar.d(8u * co, oxs); wpp[u] = ar.d(8u * co, op);
-        } else { wx[u] = ar.d(8u * co, oxs); wpp[u] = gptr(d.xg)[co]; }      // F_0: the own lane also moves x~ on (x~_prev <- x~, x~ <- x_g)
+        }
+        if (own_on(u)) {                                    // the own columns' operands: only the waves that hold one
+          wown[u] = e < gl && c >= cs0 && c - cs0 < nown;
+          const int co = wown[u] ? c : g0;                  // (the wave's other lanes re-read one valid element: no divergent branch around the loads)
+          if (!FIRST) { wx[u] = ar.d(8u * co, oxs); wpp[u] = ar.d(8u * co, op); }
+          else { wx[u] = ar.d(8u * co, oxs); wpp[u] = gptr(d.xg)[co]; }      // F_0: the own lane also moves x~ on (x~_prev <- x~, x~ <- x_g)
+        }
       }
     }
     if constexpr (MIX) {                                     // the spill slots: behind the packed words alone (the first of this lane's requests to return)
 #pragma unroll
-      for (int u = 0; u < CW; u++) { if (u < nw) wst[u] = f1_spill_take(spcur, wsw[u]); }
+      for (int u = 0; u < CW; u++) { if (gather_on(u)) wst[u] = f1_spill_take(spcur, wsw[u]); }
     }
     // ---- row / column pointers (the matrix entries themselves arrive in LDS: S, requested one block ahead)
     int cp0[CW], cp1[CW];
@@ -866,15 +881,13 @@ __device__ __forceinline__ void f1_body(const Dev &d, const int k, const bool ve
     }
     const int pj = min(cs0 + max(0, min(tid, nown - 1)), n - 1);
     const int pp0 = ar.i(4u * pj, f.o_prp), pp1 = ar.i(4u * pj, f.o_prp + 4);
-    // ---- a (P + sigma I) entry whose column lies outside the window: its operand is recomputed from its parts in the product phase below (requested
-    //      THERE: held from here they would cost 7 + 2 D registers across the block's register peak for a case banded problems never meet)
-    const int pcl = pc - g0;
-    const bool esc = hasp && !(pcl >= 0 && pcl < gl);
+    // (a (P + sigma I) entry whose column lies outside the window: its operand is recomputed from its parts in the product phase below -- requested
+    //  THERE: held from here they would cost 7 + 2 D registers across the block's register peak for a case banded problems never meet)
     KT(3);
     // ---- u_k on the window -> LDS; the lane of an own column also performs that column's vector update
 #pragma unroll
     for (int u = 0; u < CW; u++) {
-      if (u < nw) {
+      if (gather_on(u)) {
         int e = min(tid + u * kBlock, gl - 1);
         if constexpr (MIX) { const int ef = tid + u * kBlock; if (u == CW - 1 && ef >= kFB && ef - kFB < nfc) e = ef; }
         double un;
@@ -893,7 +906,7 @@ __device__ __forceinline__ void f1_body(const Dev &d, const int k, const bool ve
           else { double sn, rn; f1_upd(sc, wm[u], wr[u], w, wsv[u], sn, rn, un); }
         }
         if (wown[u]) L.uown[g0 + e - cs0] = un;
-        L.win[e] = un;                                      // (clamped lanes store the same value)
+        L.win[e] = un;                                      // (an active wave's clamped lanes store the same value)
       }
     }
     // ---- own columns outside the gather window (none on banded problems; all of them in the last budgeted update)
@@ -945,7 +958,8 @@ __device__ __forceinline__ void f1_body(const Dev &d, const int k, const bool ve
     for (int u = 0; u < CE; u++) { if (u < nu) L.prod[tid + u * kBlock] = vw[u] * L.win[en[u] & 0x1ffu]; }
     if (hasp) {
       double uv;
-      if (!esc) uv = L.win[pcl];
+      const int pcl = pc - g0;
+      if (pcl >= 0 && pcl < gl) uv = L.win[pcl];
       else {
         double eq[D];
 #pragma unroll
@@ -1010,8 +1024,8 @@ __device__ __forceinline__ void f1_body(const Dev &d, const int k, const bool ve
         }
       }
     }
-    for (int j = cov0 + tid; j < a0; j += kBlock) gst(rout + j, 0.0);             // the replica's gap up to the next window of this replica
-    for (int j = a0 + wl + tid; j < cov1; j += kBlock) gst(rout + j, 0.0);
+    // (the replica's gaps between its windows are not stored: nothing but these windows is ever written into a replica vector, the plan is fixed for the
+    //  life of the arena, and Engine::upload_f1 zeroes the three replica sets when it creates it)
     if constexpr (FIRST) {
       if (tid < nown) bn_acc = nanmax(bn_acc, fabs(MIX ? f1_w<D>(bv) + f1_spill_sum(spV, bsw, f1_spill_take(spV, bsw)) : f1_w<D>(bv)));
       for (int jj = tid + kBlock; jj < nown; jj += kBlock) {
@@ -1098,11 +1112,17 @@ __device__ __forceinline__ void f1_ka_body(const Dev &d, F1Lds &L, F1Stream &S, 
     const F1Rec rec = sl == slot0 ? rec0 : f1_record(f, b);
     const int4 ds = rec.ds, fa = rec.fa, fb = rec.fb, fc = rec.fc;
     const int r0 = ds.x, nrows = ds.y - ds.x, k0 = ds.z, cnt = ds.w - ds.z;
-    const int cov0 = fa.x, cov1 = fa.y, cs0 = fa.z, nown = fa.w - fa.z;
+    const int cs0 = fa.z, nown = fa.w - fa.z;
     const int cpo = fb.x, pk0 = fb.y, pcnt = fb.z - fb.y;
     const int g0 = fc.x, gl = fc.y, a0 = fc.z, wl = fc.w;
     const int nfc = MIX ? fb.w : 0;                          // MIX: far columns in the last kF1MaxFar slots (f1_body)
-    const int nw = nfc ? CW : (gl + kBlock - 1) / kBlock, nu = (cnt + kBlock - 1) / kBlock, ns2 = nfc ? CW : (wl + kBlock - 1) / kBlock;
+    const int nu = (cnt + kBlock - 1) / kBlock;
+    // the wave-uniform predicates of f1_body: a wave requests (stages, sums) an element of a stage only if one of its lanes holds one
+    // (here also on the column pointers, the column sums and the prp pairs: in this body they gain 0.4 us per launch, in f1_body they cost 0.9)
+    const int wv0 = __builtin_amdgcn_readfirstlane(tid & ~63);
+    auto gather_on = [&](int u) { const int ew = wv0 + u * kBlock; return ew < gl || (MIX && nfc > 0 && u == CW - 1 && ew + 63 >= kFB && ew < kFB + nfc); };
+    auto own_on = [&](int u) { const int ew = wv0 + u * kBlock; return ew < gl && g0 + ew < cs0 + nown && g0 + min(ew + 63, gl - 1) >= cs0; };
+    auto scatter_on = [&](int u) { const int ew = wv0 + u * kBlock; return ew < wl || (MIX && nfc > 0 && u == CW - 1 && ew + 63 >= kFB && ew < kFB + nfc); };
     // ---- loads: the (P + sigma I) entry of this lane and its operand x_g[column]
     double pv = 0.0; int pc = g0;
     const bool hasp = tid < pcnt;
@@ -1118,14 +1138,17 @@ __device__ __forceinline__ void f1_ka_body(const Dev &d, F1Lds &L, F1Stream &S, 
 #pragma unroll
     for (int u = 0; u < CW; u++) {
       wown[u] = false;
-      if (u < nw) {
+      if (gather_on(u)) {
         const int e = tid + u * kBlock;
         int c = g0 + min(e, gl - 1);
         if constexpr (MIX) { if (u == CW - 1 && e >= kFB && e - kFB < nfc) c = fcl; }
-        wown[u] = e < gl && c >= cs0 && c - cs0 < nown;
-        const int co = wown[u] ? c : g0;
-        if (!SCATTER_ONLY) { wx[u] = xs_r[c]; wxp[u] = gptr(d.xsp)[co]; }
-        wxo[u] = gptr(d.x)[co]; wq[u] = gptr(d.q)[co];
+        if (!SCATTER_ONLY) wx[u] = xs_r[c];
+        if (own_on(u)) {
+          wown[u] = e < gl && c >= cs0 && c - cs0 < nown;
+          const int co = wown[u] ? c : g0;
+          if (!SCATTER_ONLY) wxp[u] = gptr(d.xsp)[co];
+          wxo[u] = gptr(d.x)[co]; wq[u] = gptr(d.q)[co];
+        }
       }
     }
     // ---- rows
@@ -1137,18 +1160,18 @@ __device__ __forceinline__ void f1_ka_body(const Dev &d, F1Lds &L, F1Stream &S, 
     int cp0[CW], cp1[CW];
 #pragma unroll
     for (int u = 0; u < CW; u++) {
-      if (u < ns2) {
+      if (scatter_on(u)) {
         int c = min(tid + u * kBlock, wl - 1);
         if constexpr (MIX) { const int cf = tid + u * kBlock - kFB; if (u == CW - 1 && cf >= 0 && cf < nfc) c = wl + cf; }
         cp0[u] = gptr(f.cptr)[cpo + c]; cp1[u] = gptr(f.cptr)[cpo + c + 1];
       }
     }
-    int pp0 = 0, pp1 = 0;
-    { const int j = min(cs0 + max(0, min(tid, nown - 1)), d.n - 1); pp0 = gptr(f.prp)[j]; pp1 = gptr(f.prp)[j + 1]; }
+    int pp0, pp1;                                            // (no default value: f1_body)
+    if (wv0 < nown) { const int j = min(cs0 + min(tid, nown - 1), d.n - 1); pp0 = gptr(f.prp)[j]; pp1 = gptr(f.prp)[j + 1]; }
     // ---- window -> LDS; the own lane updates x and leaves  sigma x - q  for its column
 #pragma unroll
     for (int u = 0; u < CW; u++) {
-      if (u < nw) {
+      if (gather_on(u)) {
         int e = min(tid + u * kBlock, gl - 1);
         if constexpr (MIX) { const int ef = tid + u * kBlock; if (u == CW - 1 && ef >= kFB && ef - kFB < nfc) e = ef; }
         if (!SCATTER_ONLY) L.win[e] = wx[u];
@@ -1167,9 +1190,10 @@ __device__ __forceinline__ void f1_ka_body(const Dev &d, F1Lds &L, F1Stream &S, 
     }
     f1_stream_wait();
 #if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("" :: "v"(rp0), "v"(rp1), "v"(el), "v"(eu), "v"(erho), "v"(erinv), "v"(ez), "v"(ey), "v"(ezt), "v"(pp0), "v"(pp1), "v"(pv), "v"(pc), "v"(pxs), "v"(pxp));
+    asm volatile("" :: "v"(rp0), "v"(rp1), "v"(el), "v"(eu), "v"(erho), "v"(erinv), "v"(ez), "v"(ey), "v"(ezt), "v"(pv), "v"(pc), "v"(pxs), "v"(pxp));
+    if (wv0 < nown) asm volatile("" :: "v"(pp0), "v"(pp1));
 #pragma unroll
-    for (int u = 0; u < CW; u++) { if (u < ns2) asm volatile("" :: "v"(cp0[u]), "v"(cp1[u])); }
+    for (int u = 0; u < CW; u++) { if (scatter_on(u)) asm volatile("" :: "v"(cp0[u]), "v"(cp1[u])); }
     if constexpr (MIX) asm volatile("" :: "v"(fql));
 #endif
     __syncthreads();
@@ -1237,7 +1261,7 @@ __device__ __forceinline__ void f1_ka_body(const Dev &d, F1Lds &L, F1Stream &S, 
 #pragma unroll
     for (int u = 0; u < CW; u++) {
       cv[u] = 0.0;
-      if (u < ns2) { const int c = tid + u * kBlock; if (c < wl || (MIX && u == CW - 1 && c >= kFB && c - kFB < nfc)) cv[u] = f1_segsum<8>(L.prod, cp0[u], cp1[u]); }
+      if (scatter_on(u)) { const int c = tid + u * kBlock; if (c < wl || (MIX && u == CW - 1 && c >= kFB && c - kFB < nfc)) cv[u] = f1_segsum<8>(L.prod, cp0[u], cp1[u]); }
     }
     __syncthreads();
     // ---- second pass: A_g' t0
@@ -1250,7 +1274,7 @@ __device__ __forceinline__ void f1_ka_body(const Dev &d, F1Lds &L, F1Stream &S, 
     double *routR = repR + (size_t)(b % D) * ns, *routV = repV + (size_t)(b % D) * ns;
 #pragma unroll
     for (int u = 0; u < CW; u++) {
-      if (u < ns2) {
+      if (scatter_on(u)) {
         const int c = tid + u * kBlock;
         if (c < wl) {
           double tv = cv[u], tt = f1_segsum<8>(L.prod, cp0[u], cp1[u]);
@@ -1262,8 +1286,6 @@ __device__ __forceinline__ void f1_ka_body(const Dev &d, F1Lds &L, F1Stream &S, 
         }
       }
     }
-    for (int j = cov0 + tid; j < a0; j += kBlock) { gst(routV + j, 0.0); gst(routR + j, 0.0); }      // the replicas' gaps up to the next window of this replica
-    for (int j = a0 + wl + tid; j < cov1; j += kBlock) { gst(routV + j, 0.0); gst(routR + j, 0.0); }
     if (sl + slots < per) __syncthreads();
   }
 }
