@@ -289,7 +289,17 @@ OSQPInt osqp_hip_batch_solve_mat_device(OSQPSolver *solver, OSQPInt nbatch, cons
  * A' diag(rho_b) A stopped per problem at cg_tol_fraction x the scaled dual residual (non-increasing; relative before the first residual), equality
  * weight and adaptive rho per problem, termination / approximate statuses at max_iter / infeasibility certificates in x, y / OSQP_NON_CVX on
  * non-finite residuals decided per problem on the device every check_termination / adaptive_rho_interval iterations; time_limit ends a chunk with
- * OSQP_TIME_LIMIT_REACHED for its unfinished problems.  No polish (status_polish = 0), check_dualgap is ignored, no per-problem matrices.
+ * OSQP_TIME_LIMIT_REACHED for its unfinished problems.  check_dualgap is ignored, no per-problem matrices.
+ * POLISH: with settings.polishing every problem of a chunk that ends OSQP_SOLVED is polished before the chunk is written out, all of them at once, by the
+ * recurrence osqp_solve's polish runs on the PCG path: the active rows guessed from the ADMM (z, y) (equality rows always), the reduced KKT system solved
+ * by steps of this route's own iteration with alpha = 1 and rho = 1 / max(delta, OSQP_HIP_POLISH_DELTA_FLOOR) on the active rows, the others free, the
+ * inner systems to OSQP_HIP_POLISH_PCG_TOL -- at least 1 + polish_refine_iter steps, at most 30, until a problem's reduced residuals stop halving --,
+ * then z = A x and the normal-cone projection against the problem's own bounds.  A problem keeps the polished point if it improves the ADMM point's
+ * residuals by the reference's rule: record fields obj / prim_res / dual_res are then the polished point's and status_polish = 1; otherwise its ADMM x, y
+ * come back bit for bit and status_polish = -1.  Field polish seconds is the chunk's polish wall time for every problem that was attempted.  Status,
+ * iter, rho, rho_updates, pcg_iters and rho_estimate stay the ADMM's (polish's PCG iterations are not added).  A problem that did not end OSQP_SOLVED
+ * keeps status_polish = 0 and its x, y / certificate untouched, and so does every problem of a chunk whose time_limit had passed when its ADMM loop ended.
+ * With polishing = 0 (the default) the route issues exactly the launches it issues without this paragraph.  INDEPENDENCE below covers the polish.
  * INDEPENDENCE: no quantity of one problem enters another problem's arithmetic and no summation order depends on a chunk's fill -- a problem's x, y
  * and record are bit-identical whatever else is in the batch and wherever in it the problem sits.
  * A handle that works on a permuted copy (OSQPHipStats::reordered) is served: the arrays keep the caller's numbering.  The handle's own iterates,
@@ -301,14 +311,19 @@ OSQPInt osqp_hip_batch_solve_mat_device(OSQPSolver *solver, OSQPInt nbatch, cons
  * at every termination check.  nbatch == 0 launches nothing and answers whether the route applies.
  * osqp_hip_lockstep_last_record: what the last lockstep call of the handle did, OSQP_HIP_LOCKSTEP_LAST_REC doubles {chunks, chunk width, ADMM
  * iterations of the slowest problem, PCG iterations summed over the problems, kernel launches, GPU ms, workspace bytes, reserved}; all zero before
- * the first call. */
+ * the first call: the ADMM part only.
+ * osqp_hip_lockstep_polish_last_record: the polish part of the same call, OSQP_HIP_LOCKSTEP_POLISH_LAST_REC doubles {problems attempted, accepted,
+ * rejected, recurrence steps of the slowest problem, PCG iterations summed over the problems, kernel launches, GPU ms, polish workspace bytes}; all
+ * zero before the first call and after a call with polishing = 0. */
 #define OSQP_HIP_LOCKSTEP_WIDTH 64
 #define OSQP_HIP_LOCKSTEP_LAST_REC 8
+#define OSQP_HIP_LOCKSTEP_POLISH_LAST_REC 8
 OSQPInt osqp_hip_batch_solve_lockstep(OSQPSolver *solver, OSQPInt nbatch, const OSQPFloat *q, const OSQPFloat *l, const OSQPFloat *u,
                                       OSQPFloat *x, OSQPFloat *y, OSQPFloat *rec, OSQPInt warm);
 OSQPInt osqp_hip_batch_solve_lockstep_device(OSQPSolver *solver, OSQPInt nbatch, const OSQPFloat *q_dev, const OSQPFloat *l_dev, const OSQPFloat *u_dev,
                                              OSQPFloat *x_dev, OSQPFloat *y_dev, OSQPFloat *rec_dev, OSQPInt warm_start, void *stream);
 OSQPInt osqp_hip_lockstep_last_record(OSQPSolver *solver, OSQPFloat *rec);
+OSQPInt osqp_hip_lockstep_polish_last_record(OSQPSolver *solver, OSQPFloat *rec);
 /* LOCKSTEP DIRECT: the lockstep route for the handles it declines -- a Woodbury-corrected handle (OSQPHipStats::woodbury_rows = r > 0) in the small mode
  * (r <= 128) whose K0 = P + sigma I + A_S' rho A_S setup found structurally DIAGONAL: P diagonal, every row of A either long (one of the r dense rows A_L)
  * or with at most one entry, no long row storing a (row, column) twice -- the factor-model portfolio QP.  Then K_b = D0_b + A_L' rho_L,b A_L and the

@@ -116,6 +116,7 @@ OSQPInt osqp_hip_batch_solve_lockstep_device(OSQPSolver *s, OSQPInt nbatch, cons
   return guarded(s, [&](Engine &e) { return e.batch_solve_lockstep_device(nbatch, q, l, u, x, y, rec, warm, stream); });
 }
 OSQPInt osqp_hip_lockstep_last_record(OSQPSolver *s, OSQPFloat *rec) { return guarded(s, [&](Engine &e) { return e.lockstep_last_record(rec); }); }
+OSQPInt osqp_hip_lockstep_polish_last_record(OSQPSolver *s, OSQPFloat *rec) { return guarded(s, [&](Engine &e) { return e.lockstep_polish_last_record(rec); }); }
 OSQPInt osqp_hip_batch_solve_lockstep_direct(OSQPSolver *s, OSQPInt nbatch, const OSQPFloat *q, const OSQPFloat *l, const OSQPFloat *u, OSQPFloat *x, OSQPFloat *y, OSQPFloat *rec, OSQPInt warm) {
   return guarded(s, [&](Engine &e) { return e.batch_solve_lockstep_direct(nbatch, q, l, u, x, y, rec, warm); });
 }

@@ -489,7 +489,18 @@ struct LockstepParams : BatchSettings {
   // adaptive rho by the single-QP path's rule (term_rules.h single_rho_rule) in place of batch_rho_rule: its tolerance (the setting's on the handle's
   // square-root scale, Engine::ctl_setup) and persistence test.  0: the batch family's rule (rho_tol).  Set by the direct route only.
   double rho_tol_single = 0; int rho_persist = 0;
+  // polish of the chunk's SOLVED problems between the ADMM loop and the transposes out (lockstep_hip.hip "polish of a chunk"; Engine::polish's semantics):
+  // on / off, rho_bar = 1 / delta_eff on the guessed-active rows, at least pol_min_steps = 1 + polish_refine_iter steps of the recurrence, its PCG to
+  // ||r|| <= pol_pcg_rel ||rhs|| within pol_cg_max iterations, the polish work block (lockstep_polish_ws_doubles(n, m) doubles, device) and where the
+  // chunk's polish statistics go (host, kLsPolStat doubles: problems attempted, accepted, rejected, recurrence steps of the slowest problem, PCG
+  // iterations summed, kernel launches, GPU ms; nullptr: not wanted).  Set by Engine::run_lockstep alone: the adjoint and direct routes leave polish off.
+  int polish = 0, pol_min_steps = 1, pol_cg_max = 0;
+  double pol_rho = 0, pol_pcg_rel = 0;
+  double *pol_ws = nullptr, *pol_stat = nullptr;
 };
+constexpr int kLsPolStat = 7;
+// doubles of the polish work block: the scaled ADMM x (n) and y, z, l, u (m) of every problem of the chunk
+inline size_t lockstep_polish_ws_doubles(int n, int m) { return (size_t)kLsW * ((size_t)n + 4 * (size_t)m) + 64; }
 
 // Adjoint derivatives of a chunk on the lockstep route (lockstep_hip.hip lockstep_adjoint_chunk; include/osqp_hip.h osqp_hip_batch_adjoint_lockstep):
 // the recurrence of Engine::run_recurrence per problem on block vectors.  The base carries the matrices, the scalings, the permutations, the shared

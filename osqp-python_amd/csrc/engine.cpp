@@ -162,6 +162,7 @@ void Engine::free_all() {
   batch_order_.clear();
   if (ckpt_) { be::dfree(d_, ckpt_); ckpt_ = nullptr; }
   if (lsw_) { be::dfree(d_, lsw_); lsw_ = nullptr; }
+  if (lspw_) { be::dfree(d_, lspw_); lspw_ = nullptr; }
   if (lsaw_) { be::dfree(d_, lsaw_); lsaw_ = nullptr; }
   if (lsdw_) { be::dfree(d_, lsdw_); lsdw_ = nullptr; }
   if (lsdaw_) { be::dfree(d_, lsdaw_); lsdaw_ = nullptr; }
@@ -961,9 +962,8 @@ int Engine::run_recurrence(const RecurrenceRule &rule, double *res) {
     steps = s + 1;
     // residuals of the reduced KKT system: Aa x - ba (active rows) and P x + q + Aa' ya, in the scaled space
     const double err = rhs_norm ? recurrence_err_rhs(res[R_PRI_S], res[R_DUA_S], res[R_QN_S], res[R_Z_S])
-                                : std::max(res[R_PRI_S] / (std::max(res[R_AX_S], res[R_Z_S]) + 1e-30),
-                                           res[R_DUA_S] / (std::max(std::max(res[R_ATY_S], res[R_PX_S]), res[R_QN_S]) + 1e-30));
-    if (recurrence_ends(err, gain, steps, min_steps, kRecurrenceMaxSteps, &best, &worse)) break;      // (term_rules.h: the lockstep adjoint's rule too)
+                                : recurrence_err_polish(res[R_PRI_S], res[R_AX_S], res[R_Z_S], res[R_DUA_S], res[R_ATY_S], res[R_PX_S], res[R_QN_S]);
+    if (recurrence_ends(err, gain, steps, min_steps, kRecurrenceMaxSteps, &best, &worse)) break;      // (term_rules.h: the lockstep adjoint's and the lockstep polish's rules too)
   }
   return steps;
 }

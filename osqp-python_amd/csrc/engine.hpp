@@ -63,6 +63,7 @@ class Engine {
   int batch_solve_lockstep(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm);
   int batch_solve_lockstep_device(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream);
   int lockstep_last_record(double *rec) const;
+  int lockstep_polish_last_record(double *rec) const;
   // The direct lockstep route for a Woodbury handle with a diagonal K0 (include/osqp_hip.h osqp_hip_batch_solve_lockstep_direct; lockstep_hip.hip "lockstep
   // DIRECT"): the same arguments and semantics; every other handle -- a reordered one included -- gets OSQP_FUNC_NOT_IMPLEMENTED.
   int batch_solve_lockstep_direct(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm);
@@ -148,6 +149,8 @@ class Engine {
   double *bmat_ = nullptr; size_t bmat_cap_ = 0;      // per-problem matrices: scaled values, equilibration and products of every problem (BatchParams::Aval_b ..), kept across calls
   double *lsw_ = nullptr;                             // workspace of one lockstep chunk (lockstep_ws_doubles(n, m)), allocated on first use
   double ls_rec_[OSQP_HIP_LOCKSTEP_LAST_REC] = {0, 0, 0, 0, 0, 0, 0, 0};      // record of the last lockstep call (osqp_hip_lockstep_last_record)
+  double *lspw_ = nullptr;                            // polish work block of one lockstep chunk (lockstep_polish_ws_doubles(n, m)), allocated by the first polishing call
+  double ls_pol_rec_[OSQP_HIP_LOCKSTEP_POLISH_LAST_REC] = {0, 0, 0, 0, 0, 0, 0, 0};      // polish record of the last lockstep call (osqp_hip_lockstep_polish_last_record)
   int run_lockstep(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream);
   // direct lockstep route: the structural decision of prepare_wb (K0 diagonal, small mode -- not DevWb::exact, which a failed inversion clears), the
   // chunk's workspace (lockstep_direct_ws_doubles(n, m, r)) and the view of A (LockstepDirectParams::Av), both built on first use, the last call's record

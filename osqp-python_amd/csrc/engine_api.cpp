@@ -903,7 +903,7 @@ int Engine::batch_solve_device(int nbatch, const double *q, const double *l, con
 // ------------------------------------------------------------------------------------------------ lockstep route
 // Chunks of kLsW problems, one after the other, each from its transposes in to its transposes out (be::lockstep_chunk).  q / l / u / x / y / rec are
 // DEVICE arrays in the caller's numbering; the settings are read once, in front of the first chunk.  The handle's iterates are not touched: the route
-// has its own workspace (lsw_, allocated on first use, freed with the handle).
+// has its own workspace (lsw_, allocated on first use, freed with the handle) and, with polishing, its own polish work block (lspw_, likewise).
 int Engine::run_lockstep(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream) {
   const size_t need = lockstep_ws_doubles(n, m);
   if (!lsw_) { lsw_ = dev_vec<double>(d_, need); be::sync(d_); }
@@ -911,21 +911,36 @@ int Engine::run_lockstep(int nbatch, const double *q, const double *l, const dou
   fill_batch_settings(p, warm);                       // the settings snapshot of the batch path
   p.n = n; p.m = m; p.A = d_.A; p.B = d_.B; p.D = d_.D; p.Dinv = d_.Dinv; p.E = d_.E; p.Einv = d_.Einv;
   p.q0 = d_.qraw; p.l0 = d_.lraw; p.u0 = d_.uraw; p.pc = reordered_ ? d_pc_ : nullptr; p.pr = reordered_ ? d_pr_ : nullptr; p.ws = lsw_;
+  // polish (settings.polishing): the recurrence of Engine::run_recurrence as Engine::polish calls it, per problem on block vectors -- rho_bar = 1 / delta_eff,
+  // at least 1 + polish_refine_iter steps, the inner systems to polish_pcg_tol within kMaxCg iterations.  Its work block is allocated by the first such call.
+  double pst[kLsPolStat] = {0, 0, 0, 0, 0, 0, 0}, ptot[kLsPolStat] = {0, 0, 0, 0, 0, 0, 0};
+  const size_t pneed = lockstep_polish_ws_doubles(n, m);
+  if (settings.polishing) {
+    if (!lspw_) { lspw_ = dev_vec<double>(d_, pneed); be::sync(d_); }
+    const double de = std::max(settings.delta, pol_.polish_delta_floor);
+    p.polish = 1; p.pol_rho = clamp_rho(1.0 / de); p.pol_min_steps = 1 + std::max(0, (int)settings.polish_refine_iter);
+    p.pol_cg_max = kMaxCg; p.pol_pcg_rel = pol_.polish_pcg_tol; p.pol_ws = lspw_; p.pol_stat = pst;
+  }
   const double t0 = now_s(), limit = settings.time_limit > 0 && settings.time_limit < 1e9 ? settings.time_limit : 0.0;
   double tot[4] = {0, 0, 0, 0};
   int chunks = 0;
+  std::fill(ls_pol_rec_, ls_pol_rec_ + OSQP_HIP_LOCKSTEP_POLISH_LAST_REC, 0.0);
   for (int b0 = 0; b0 < nbatch; b0 += kLsW, chunks++) {
     p.count = std::min(kLsW, nbatch - b0);
     p.q = q ? q + (size_t)b0 * n : nullptr; p.l = l ? l + (size_t)b0 * m : nullptr; p.u = u ? u + (size_t)b0 * m : nullptr;
     p.x = x + (size_t)b0 * n; p.y = y + (size_t)b0 * m; p.rec = rec + (size_t)b0 * kBatchRec;
     p.time_limit = limit > 0 ? std::max(limit - (now_s() - t0), 1e-9) : 0.0;
     double st[4] = {0, 0, 0, 0};
+    std::fill(pst, pst + kLsPolStat, 0.0);
     const int err = be::lockstep_chunk(d_, p, stream, st);
     if (err) return err;
     tot[0] = std::max(tot[0], st[0]); tot[1] += st[1]; tot[2] += st[2]; tot[3] += st[3];
+    for (int k = 0; k < kLsPolStat; k++) ptot[k] = k == 3 ? std::max(ptot[k], pst[k]) : ptot[k] + pst[k];
   }
   const double r[OSQP_HIP_LOCKSTEP_LAST_REC] = {(double)chunks, (double)kLsW, tot[0], tot[1], tot[2], tot[3], (double)(need * sizeof(double)), 0.0};
   std::copy(r, r + OSQP_HIP_LOCKSTEP_LAST_REC, ls_rec_);
+  std::copy(ptot, ptot + kLsPolStat, ls_pol_rec_);
+  ls_pol_rec_[kLsPolStat] = settings.polishing ? (double)(pneed * sizeof(double)) : 0.0;
   return OSQP_NO_ERROR;
 }
 
@@ -948,6 +963,13 @@ int Engine::lockstep_last_record(double *rec) const {
   if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   if (!rec) return OSQP_DATA_VALIDATION_ERROR;
   std::copy(ls_rec_, ls_rec_ + OSQP_HIP_LOCKSTEP_LAST_REC, rec);
+  return OSQP_NO_ERROR;
+}
+
+int Engine::lockstep_polish_last_record(double *rec) const {
+  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (!rec) return OSQP_DATA_VALIDATION_ERROR;
+  std::copy(ls_pol_rec_, ls_pol_rec_ + OSQP_HIP_LOCKSTEP_POLISH_LAST_REC, rec);
   return OSQP_NO_ERROR;
 }
 

@@ -23,6 +23,8 @@
 // k_batch_admm's load / store scaling and, for a handle that works on a permuted copy, gather / scatter through the permutations.
 // The BACKWARD pass of a chunk (osqp_hip_batch_adjoint_lockstep; lockstep_adjoint_chunk below): the adjoint system of every problem by the recurrence polish
 // and the single-QP adjoint run, which is this file's iteration with alpha = 1 and a fixed rho -- see "adjoint derivatives of a chunk".
+// POLISH (settings.polishing): the chunk's SOLVED problems are polished by that same recurrence between the ADMM loop and the transposes out -- see
+// "polish of a chunk".
 #include "hip_common.h"
 
 namespace osqp_hip {
@@ -31,6 +33,7 @@ namespace be {
 namespace {
 
 constexpr int W = kLsW;
+constexpr int kLsPolMaxSteps = 30;               // Engine::polish's RecurrenceRule{false, 0.5, 30}
 
 // partial slots (part[slot][workgroup][lane]); within a group the max-type slots come first
 enum LsSlot {
@@ -42,8 +45,9 @@ enum LsSlot {
 static_assert(PS_COUNT <= kLsSlots, "lockstep_ws_doubles reserves kLsSlots partial slots");
 enum LsScal { SC_RHOBAR = 0, SC_EQF, SC_EPSCG, SC_EPSPREV, SC_RZ, SC_RN, SC_TOL, SC_ALPHA, SC_BETA, SC_BEST /* adjoint: smallest error so far */, SC_NACT /* adjoint: active rows */, SC_COUNT };
 enum LsInt { IW_DONE = 0, IW_STATUS, IW_RHOUPD, IW_PCG, IW_RELRULE, IW_CGON, IW_RHOCH, IW_STEPS /* adjoint: recurrence steps */, IW_WORSE /* adjoint: steps in a row without progress */,
-             IW_SIDE /* direct route: single_rho_rule's side at the previous adaptation point */, IW_COUNT };
-enum LsWord { WD_CGANY = 0, WD_LIVE, WD_RHOANY, WD_PCGSUM, WD_CGIT /* PCG iterations of the current ADMM iteration that some problem needed */, WD_COUNT };
+             IW_SIDE /* direct route: single_rho_rule's side at the previous adaptation point */, IW_POL /* polish: 1 attempted, 2 attempted and rejected */, IW_COUNT };
+enum LsWord { WD_CGANY = 0, WD_LIVE, WD_RHOANY, WD_PCGSUM, WD_CGIT /* PCG iterations of the current ADMM iteration that some problem needed */,
+              WD_POLACC /* polish: problems accepted */, WD_POLREJ /* rejected */, WD_COUNT };
 static_assert(SC_COUNT <= kLsScal && IW_COUNT + 1 <= kLsInt, "lockstep_ws_doubles reserves kLsScal / kLsInt rows");
 
 struct LsWs {
@@ -781,6 +785,123 @@ __global__ __launch_bounds__(256) void k_ls_adj_grad(LsAK k) {
   const int e = e0 + lane;
   if (e < nz) for (int b = wv; b < P.count; b += 4) out[(size_t)b * nz + e] = tile[b][lane];
 }
+// ---------------------------------------------------------------------------------------------------------------- polish of a chunk
+// settings.polishing on this route (include/osqp_hip.h osqp_hip_batch_solve_lockstep, POLISH): every problem of the chunk that ended OSQP_SOLVED is polished
+// between the ADMM loop and the transposes out, with the semantics of Engine::polish (engine.cpp; _osqp.py:1710-1828).  The reduced KKT system on the
+// guessed active set is solved by the recurrence of Engine::run_recurrence, which is THIS route's iteration (k_ls_rhs, the PCG, k_ls_upd, k_ls_resm /
+// k_ls_resn) with alpha = 1, rho_bar = 1 / delta_eff on the active rows, the others free, from the ADMM point -- as in "adjoint derivatives of a chunk".
+// What is new surrounds it: which problems take part and their state (k_ls_pol_begin), the save and the classification (k_ls_pol_class: step_rules.h
+// polish_active), polish's progress measure per problem (k_ls_pol_decide: term_rules.h recurrence_err_polish / recurrence_ends), z = A x and the
+// normal-cone projection against the problem's own bounds (k_ls_pol_cone), the accept test against the record (k_ls_pol_accept: term_info,
+// polish_accept) and, for a rejected problem, the ADMM x, y, z back (k_ls_pol_end).  A problem that does not take part is "terminated" all the way: no
+// kernel stores to its lane.  The saved vectors live in a work block of their own (backend.h lockstep_polish_ws_doubles).
+struct LsPolWs { double *x, *y, *z, *l, *u; };        // the scaled ADMM x (n) and y, z, l, u (m)
+struct LsPK { LockstepParams P; LsWs w; LsPolWs s; };
+
+// per problem: takes part iff SOLVED; IW_DONE becomes "not in the recurrence"; rho_bar = 1 / delta_eff with equality factor 1, flagged for k_ls_setrho / k_ls_minv
+__global__ __launch_bounds__(256) void k_ls_pol_begin(LsPK k) {
+  if (threadIdx.x >= 64) return;
+  const int lane = ls_lane();
+  double *sc = k.w.sc; int *iw = k.w.iw;
+  const int pol = iw[IW_STATUS * W + lane] == OSQP_SOLVED;      // (lanes >= count: OSQP_UNSOLVED)
+  if (pol) { sc[SC_RHOBAR * W + lane] = k.P.pol_rho; sc[SC_EQF * W + lane] = 1.0; sc[SC_BEST * W + lane] = INFINITY; }      // (the record has the ADMM's rho_bar already)
+  iw[IW_POL * W + lane] = pol; iw[IW_DONE * W + lane] = !pol; iw[IW_RHOCH * W + lane] = pol; iw[IW_CGON * W + lane] = 0;
+  iw[IW_PCG * W + lane] = 0; iw[IW_STEPS * W + lane] = 0; iw[IW_WORSE * W + lane] = 0;      // (IW_PCG: the record has the ADMM's count; from here on polish's, for the statistics)
+  const unsigned long long live = __ballot(pol);
+  if (threadIdx.x == 0) { k.w.word[WD_CGANY] = 0; k.w.word[WD_LIVE] = __popcll(live); k.w.word[WD_RHOANY] = live != 0ull; k.w.word[WD_CGIT] = 0; k.w.word[WD_POLACC] = 0; k.w.word[WD_POLREJ] = 0; }
+}
+// the ADMM point saved; per row the active side (equality rows, scaled l == u, always on the lower one) and the recurrence's bounds: active rows l = u = z =
+// the bound, the others free with y = 0.  x, x~ and z~ = A x~ stay: k_ls_setrho, which follows, forms t and t2 from the new z, y.
+__global__ __launch_bounds__(256) void k_ls_pol_class(LsPK k) {
+  if (!k.w.iw[IW_POL * W + ls_lane()]) return;
+  const size_t nt = (size_t)k.P.n * 64, mt = (size_t)k.P.m * 64, stride = (size_t)gridDim.x * 256;
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < nt; e += stride) k.s.x[e] = k.w.x[e];
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < mt; e += stride) {
+    const double z = k.w.z[e], y = k.w.y[e], l = k.w.l[e], u = k.w.u[e];
+    k.s.z[e] = z; k.s.y[e] = y; k.s.l[e] = l; k.s.u[e] = u;
+    const RowActive act = polish_active(z, l, u, y);
+    const bool low = act.low || l == u, on = low || act.upp;
+    const double b = low ? l : u;
+    k.w.l[e] = on ? b : -OSQP_INFTY; k.w.u[e] = on ? b : OSQP_INFTY; k.w.z[e] = on ? b : z; k.w.y[e] = on ? y : 0.0;
+  }
+}
+// after every step: polish's measure of the reduced system's residuals and the progress rule per problem; a problem that ends is frozen
+__global__ __launch_bounds__(256) void k_ls_pol_decide(LsPK k) {
+  __shared__ double lds[256];
+  const int lane = ls_lane(), G = k.w.G;
+  const bool has_m = k.P.m > 0;                                                 // (uniform: so are the folds' barriers)
+  auto mx = [&](int slot) { return ls_fold<true>(k.w.part, G, slot, lds); };
+  const double pri_s = has_m ? mx(PS_M0 + 3) : 0.0, ax_s = has_m ? mx(PS_M0 + 4) : 0.0, z_s = has_m ? mx(PS_M0 + 5) : 0.0;
+  const double dua_s = mx(PS_N0 + 3), px_s = mx(PS_N0 + 4), aty_s = mx(PS_N0 + 5), qn_s = mx(PS_N0 + 8);
+  if (threadIdx.x >= 64) return;
+  double *sc = k.w.sc; int *iw = k.w.iw;
+  if (!iw[IW_DONE * W + lane]) {
+    const int steps = iw[IW_STEPS * W + lane] + 1;
+    double best = sc[SC_BEST * W + lane]; int worse = iw[IW_WORSE * W + lane];
+    const bool end = recurrence_ends(recurrence_err_polish(pri_s, ax_s, z_s, dua_s, aty_s, px_s, qn_s), 0.5, steps, k.P.pol_min_steps, kLsPolMaxSteps, &best, &worse);
+    iw[IW_STEPS * W + lane] = steps; sc[SC_BEST * W + lane] = best; iw[IW_WORSE * W + lane] = worse;
+    if (end) iw[IW_DONE * W + lane] = 1;
+  }
+  iw[IW_RHOCH * W + lane] = 0;
+  const unsigned long long live = __ballot(!iw[IW_DONE * W + lane]);
+  int pcg = iw[IW_PCG * W + lane];                      // (statistics only)
+  for (int o = 32; o > 0; o >>= 1) pcg += __shfl_xor(pcg, o);
+  if (threadIdx.x == 0) { k.w.word[WD_LIVE] = __popcll(live); k.w.word[WD_RHOANY] = 0; k.w.word[WD_PCGSUM] = pcg; }
+}
+// the polished point against the problem's own bounds: l, u back, z = A x, then the normal-cone projection of (z, y)  (_osqp.py:1773-1780)
+struct FPolCone {
+  const LsWs &w; const LsPolWs &s; int lane, pol;
+  __device__ __forceinline__ void begin(int) {}
+  __device__ __forceinline__ void load(int c, double (&g)[1]) const { g[0] = w.x[IX(c)]; }
+  __device__ __forceinline__ void fma(int, double v, const double (&g)[1], double (&a)[1]) const { a[0] += v * g[0]; }
+  __device__ __forceinline__ void row(int i, const double (&a)[1]) const {
+    if (!pol) return;
+    const double l = s.l[IX(i)], u = s.u[IX(i)];
+    const ConeRow c = normal_cone(a[0] + w.y[IX(i)], l, u);
+    w.l[IX(i)] = l; w.u[IX(i)] = u; w.z[IX(i)] = c.z; w.y[IX(i)] = c.y;
+  }
+};
+__global__ __launch_bounds__(256) void k_ls_pol_cone(LsPK k) {
+  const int lane = ls_lane();
+  FPolCone f{k.w, k.s, lane, k.w.iw[IW_POL * W + lane]};
+  ls_rows<1, 1>(k.P.A, f);
+}
+// the info fields of the polished point (term_rules.h term_info on the slots k_ls_resm / k_ls_resn have put) against the record's: kept or rejected
+__global__ __launch_bounds__(256) void k_ls_pol_accept(LsPK k) {
+  __shared__ double lds[256];
+  const LockstepParams &P = k.P;
+  const int lane = ls_lane(), G = k.w.G;
+  const bool has_m = P.m > 0;
+  TermRes R = {};
+  R.pri_u = has_m ? ls_fold<true>(k.w.part, G, PS_M0, lds) : 0.0; R.pri_s = has_m ? ls_fold<true>(k.w.part, G, PS_M0 + 3, lds) : 0.0;
+  R.dua_u = ls_fold<true>(k.w.part, G, PS_N0, lds); R.dua_s = ls_fold<true>(k.w.part, G, PS_N0 + 3, lds);
+  R.xpx = ls_fold<false>(k.w.part, G, PS_N0 + 14, lds); R.qx = ls_fold<false>(k.w.part, G, PS_N0 + 15, lds);
+  if (threadIdx.x >= 64) return;
+  int *iw = k.w.iw;
+  const int pol = iw[IW_POL * W + lane];
+  bool ok = false;
+  if (pol) {
+    const TermSet tset = {P.eps_abs, P.eps_rel, P.eps_pinf, P.eps_dinf, P.c, P.cinv, P.m, P.unscaled, P.scaling};
+    double obj, prim_res, dual_res;
+    term_info(tset, R, &obj, &prim_res, &dual_res);
+    double *rc = k.w.rec + (size_t)lane * kBatchRec;
+    ok = polish_accept(prim_res, dual_res, rc[3], rc[4]);
+    if (ok) { rc[2] = obj; rc[3] = prim_res; rc[4] = dual_res; rc[8] = 1.0; }
+    else { rc[8] = -1.0; iw[IW_POL * W + lane] = 2; }
+  }
+  const unsigned long long acc = __ballot(pol && ok), rej = __ballot(pol && !ok);
+  if (threadIdx.x == 0) { k.w.word[WD_POLACC] = __popcll(acc); k.w.word[WD_POLREJ] = __popcll(rej); }
+}
+// the record's polish seconds for every problem that was attempted; a rejected problem's ADMM x, y, z back
+__global__ __launch_bounds__(256) void k_ls_pol_end(LsPK k, double secs) {
+  const int lane = ls_lane(), pol = k.w.iw[IW_POL * W + lane];
+  if (!pol) return;
+  if (blockIdx.x == 0 && threadIdx.x < 64) k.w.rec[(size_t)lane * kBatchRec + 9] = secs;
+  if (pol != 2) return;
+  const size_t nt = (size_t)k.P.n * 64, mt = (size_t)k.P.m * 64, stride = (size_t)gridDim.x * 256;
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < nt; e += stride) k.w.x[e] = k.s.x[e];
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < mt; e += stride) { k.w.y[e] = k.s.y[e]; k.w.z[e] = k.s.z[e]; }
+}
 // ---------------------------------------------------------------------------------------------------------------- lockstep DIRECT (Woodbury handles)
 // The route of osqp_hip_batch_solve_lockstep_direct (lockstep_direct_chunk below): a handle whose A is r <= kWbMaxRows dense rows A_L next to rows with one
 // entry, P diagonal -- K0 = P + sigma I + A_S' rho_S A_S is DIAGONAL (D0), K_b = D0_b + A_L' rho_L,b A_L, and the Woodbury formula is the solve:
@@ -993,8 +1114,9 @@ int lockstep_chunk(Dev &d, const LockstepParams &p, void *stream, double *stat) 
   hipEvent_t e0, e1;
   HIP_CHECK(hipEventCreate(&e0)); HIP_CHECK(hipEventCreate(&e1));
   HIP_CHECK(hipEventRecord(e0, s));
-  const double t_begin = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-  int words[WD_COUNT] = {0, p.count, 0, 0, 0};
+  auto now_s = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+  const double t_begin = now_s();
+  int words[WD_COUNT] = {0, p.count, 0, 0, 0, 0, 0};
   auto fetch = [&]() { HIP_CHECK(hipMemcpyAsync(words, w.word, sizeof(words), hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s)); };
   auto residuals = [&]() { if (m > 0) go(k_ls_resm, G); go(k_ls_resn, G); };
   auto new_rho = [&]() { if (m > 0) go(k_ls_setrho, G); go(k_ls_minv, G); };
@@ -1033,15 +1155,78 @@ int lockstep_chunk(Dev &d, const LockstepParams &p, void *stream, double *stat) 
     if (at_rho && !late) new_rho();
     if (at_check || late) fetch();
   }
+  // polish ("polish of a chunk" above): driven like lockstep_adjoint_chunk's recurrence.  A chunk whose time limit has passed does not polish.
+  bool polished = false;
+  int pcg_admm = 0, pol_steps = 0, pol_pcg = 0, pol_att = 0;
+  long pol_launches = 0;
+  hipEvent_t ep0 = nullptr, ep1 = nullptr;
+  if (p.polish && p.pol_ws && !(p.time_limit > 0 && now_s() - t_begin > p.time_limit)) {
+    polished = true;
+    const long launches0 = launches;
+    const double t_pol = now_s();
+    LsPK kq{p, w, {}};
+    double *cp = p.pol_ws;
+    auto takep = [&cp](size_t cnt) { double *r = cp; cp += cnt; return r; };
+    kq.s.x = takep(nW); kq.s.y = takep(mW); kq.s.z = takep(mW); kq.s.l = takep(mW); kq.s.u = takep(mW);
+    if ((size_t)(cp - p.pol_ws) > lockstep_polish_ws_doubles(n, m)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+    LsK kp = k;                                        // what the ADMM's kernels take in the recurrence: alpha = 1, the recurrence's PCG rule
+    kp.P.alpha = 1.0; kp.P.cg_max = p.pol_cg_max; kp.P.pcg_rel = p.pol_pcg_rel;
+    auto gk = [&](auto kern, int grid) { hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, kp); launches++; };
+    auto gq = [&](auto kern, int grid, auto... args) { hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, kq, args...); launches++; };
+    HIP_CHECK(hipEventCreate(&ep0)); HIP_CHECK(hipEventCreate(&ep1));
+    HIP_CHECK(hipEventRecord(ep0, s));
+    gq(k_ls_pol_begin, 1);
+    fetch();                                           // (WD_PCGSUM: still the ADMM's)
+    pcg_admm = words[WD_PCGSUM]; pol_att = words[WD_LIVE];
+    if (pol_att > 0) {
+      gq(k_ls_pol_class, G);
+      if (m > 0) gk(k_ls_setrho, G);
+      gk(k_ls_minv, G);
+      int cg_pol = 4;
+      while (words[WD_LIVE] > 0 && pol_steps < kLsPolMaxSteps) {
+        pol_steps++;
+        gk(k_ls_rhs, G);
+        gk(k_ls_cginit, 1);
+        for (int it = 0, grp = cg_pol; it < kp.P.cg_max; grp = 4) {
+          for (const int end = std::min(it + grp, kp.P.cg_max); it < end; it++) {
+            if (m > 0) gk(k_ls_t, G);
+            gk(k_ls_kp, G); gk(k_ls_cgalpha, 1); gk(k_ls_cgupd, G); gk(k_ls_cgbeta, 1); gk(k_ls_cgp, G);
+          }
+          fetch();
+          if (!words[WD_CGANY]) break;
+        }
+        cg_pol = std::max(2, words[WD_CGIT] + 1);
+        gk(k_ls_upd, G);
+        if (m > 0) gk(k_ls_resm, G);
+        gk(k_ls_resn, G);
+        gq(k_ls_pol_decide, 1);
+        fetch();
+      }
+      pol_pcg = words[WD_PCGSUM];
+      if (m > 0) { gq(k_ls_pol_cone, G); gk(k_ls_resm, G); }
+      gk(k_ls_resn, G);
+      gq(k_ls_pol_accept, 1);
+      fetch();
+      gq(k_ls_pol_end, G, now_s() - t_pol);
+    }
+    HIP_CHECK(hipEventRecord(ep1, s));
+    pol_launches = launches - launches0;
+  }
   go(k_ls_store_n, tn);
   if (m > 0) go(k_ls_store_m, tm);
   HIP_CHECK(hipEventRecord(e1, s));
   fetch();
-  float ms = 0.f;
+  float ms = 0.f, pms = 0.f;
   HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+  if (polished) { HIP_CHECK(hipEventElapsedTime(&pms, ep0, ep1)); HIP_CHECK(hipEventDestroy(ep0)); HIP_CHECK(hipEventDestroy(ep1)); }
   HIP_CHECK(hipEventDestroy(e0)); HIP_CHECK(hipEventDestroy(e1));
   HIP_CHECK(hipGetLastError());
-  if (stat) { stat[0] = iter; stat[1] = words[WD_PCGSUM]; stat[2] = (double)launches; stat[3] = ms; }
+  // (the chunk's statistics are the ADMM part's; polish's go to their own block)
+  if (stat) { stat[0] = iter; stat[1] = polished ? pcg_admm : words[WD_PCGSUM]; stat[2] = (double)(launches - pol_launches); stat[3] = ms - pms; }
+  if (polished && p.pol_stat) {
+    double *ps = p.pol_stat;
+    ps[0] = pol_att; ps[1] = words[WD_POLACC]; ps[2] = words[WD_POLREJ]; ps[3] = pol_steps; ps[4] = pol_pcg; ps[5] = (double)pol_launches; ps[6] = pms;
+  }
   return OSQP_NO_ERROR;
 }
 
@@ -1075,7 +1260,7 @@ int lockstep_adjoint_chunk(Dev &d, const LockstepAdjointParams &p, void *stream,
   hipEvent_t e0, e1;
   HIP_CHECK(hipEventCreate(&e0)); HIP_CHECK(hipEventCreate(&e1));
   HIP_CHECK(hipEventRecord(e0, s));
-  int words[WD_COUNT] = {0, p.count, 0, 0, 0};
+  int words[WD_COUNT] = {0, p.count, 0, 0, 0, 0, 0};
   auto fetch = [&]() { HIP_CHECK(hipMemcpyAsync(words, w.word, sizeof(words), hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s)); };
 
   goa(k_ls_adj_load_n, tn);
@@ -1165,7 +1350,7 @@ int lockstep_direct_chunk(Dev &d, const LockstepDirectParams &p, void *stream, d
   auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const double t_begin = now();
   double t_sync = t_begin;                 // the host's clock when it last waited for the stream: the time the GPU's work is known to have taken
-  int words[WD_COUNT] = {0, p.count, 0, 0, 0};
+  int words[WD_COUNT] = {0, p.count, 0, 0, 0, 0, 0};
   auto fetch = [&]() { HIP_CHECK(hipMemcpyAsync(words, w.word, sizeof(words), hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s)); t_sync = now(); };
   auto long_rows = [&](int start) { gow(k_lw_prod, GC, 0, (const double *)w.x, x.pg); gow(k_lw_prod, GC, 0, (const double *)w.xs, x.pg2); gow(k_lw_setl, 1, 0, start); };
   auto residuals = [&]() { go(k_ls_resm, G, kv); go(k_ls_resn, G, kb); };
@@ -1264,7 +1449,7 @@ int lockstep_direct_adjoint_chunk(Dev &d, const LockstepDirectAdjointParams &p, 
   HIP_CHECK(hipEventCreate(&ev0.e)); HIP_CHECK(hipEventCreate(&ev1.e));
   const hipEvent_t e0 = ev0.e, e1 = ev1.e;
   HIP_CHECK(hipEventRecord(e0, s));
-  int words[WD_COUNT] = {0, p.count, 0, 0, 0};
+  int words[WD_COUNT] = {0, p.count, 0, 0, 0, 0, 0};
   auto fetch = [&]() { HIP_CHECK(hipMemcpyAsync(words, w.word, sizeof(words), hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s)); };
   auto long_rows_of = [&](double *v) { gow(k_lw_prod, GC, 0, (const double *)v, x.pg); gow(k_lwa_setl, (r + 3) / 4, 0, v); };
 

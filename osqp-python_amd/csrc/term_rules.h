@@ -169,12 +169,18 @@ OSQP_HDI void batch_tol_rule(double cg_frac, double dua_s, double *eps_prev, dou
 }
 
 // The progress rule of the recurrence polish and the adjoint derivatives run (engine.cpp Engine::run_recurrence on the host; lockstep_hip.hip
-// k_ls_adj_decide per problem on the device).  recurrence_err_rhs: the reduced system's scaled residuals against its right-hand side.  recurrence_ends:
+// k_ls_adj_decide / k_ls_pol_decide per problem on the device).  recurrence_err_rhs: the reduced system's scaled residuals against its right-hand side (the
+// adjoint's measure).  recurrence_err_polish: polish's measure, each residual relative to the products it is the difference of.  recurrence_ends:
 // `steps` steps have been taken and the last one left the error `err`; a step that does not bring the error below gain * best counts as no progress;
 // the recurrence ends after at least min_steps when the error is negligible or two steps in a row showed no progress, and at max_steps at the latest.
 // Comparisons, one product and one quotient: host and device give the same bits.
 OSQP_HDI double recurrence_err_rhs(double pri_s, double dua_s, double qn_s, double z_s) {
   return (pri_s < dua_s ? dua_s : pri_s) / ((qn_s < z_s ? z_s : qn_s) + 1e-30);        // (std::max's selects: a NaN goes where it always went)
+}
+OSQP_HDI double recurrence_err_polish(double pri_s, double ax_s, double z_s, double dua_s, double aty_s, double px_s, double qn_s) {
+  const double pn = ax_s < z_s ? z_s : ax_s, d1 = aty_s < px_s ? px_s : aty_s, dn = d1 < qn_s ? qn_s : d1;        // (std::max's selects, as above)
+  const double ep = pri_s / (pn + 1e-30), ed = dua_s / (dn + 1e-30);
+  return ep < ed ? ed : ep;
 }
 OSQP_HDI bool recurrence_ends(double err, double gain, int steps, int min_steps, int max_steps, double *best, int *worse) {
   if (!(err < gain * *best)) *worse += 1; else *worse = 0;

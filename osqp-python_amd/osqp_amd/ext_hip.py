@@ -390,7 +390,8 @@ class OSQPSolver:
 
     def hip_batch_solve_lockstep(self, q=None, l=None, u=None, x0=None, y0=None, nbatch=None):
         """hip_batch_solve for problems of ANY size (osqp_hip_batch_solve_lockstep): shared P / A, 64 problems at a time on block vectors.
-        Same arguments (no Px / Ax), same checks, same returns: x (B, n), y (B, m), rec (B, BATCH_REC)."""
+        Same arguments (no Px / Ax), same checks, same returns: x (B, n), y (B, m), rec (B, BATCH_REC).  With the setting polishing every SOLVED
+        problem is polished on the device (rec[:, 8] = 1 kept, -1 rejected; lockstep_polish_last_record)."""
         return self._lockstep_host(self._lib.osqp_hip_batch_solve_lockstep, q, l, u, x0, y0, nbatch)
 
     def _lockstep_host(self, entry, q, l, u, x0, y0, nbatch):
@@ -432,6 +433,21 @@ class OSQPSolver:
             raise ValueError(str(int(st)))
         out = dict(zip(self.LOCKSTEP_LAST_FIELDS, rec.tolist()))
         for k in ('chunks', 'width', 'admm_iters_max', 'pcg_iters', 'kernel_launches', 'workspace_bytes'):
+            out[k] = int(out[k])
+        return out
+
+    # OSQP_HIP_LOCKSTEP_POLISH_LAST_REC doubles of osqp_hip_lockstep_polish_last_record
+    LOCKSTEP_POLISH_LAST_FIELDS = ('attempted', 'accepted', 'rejected', 'steps_max', 'pcg_iters', 'kernel_launches', 'gpu_ms', 'workspace_bytes')
+
+    def lockstep_polish_last_record(self):
+        """osqp_hip_lockstep_polish_last_record as a dict (LOCKSTEP_POLISH_LAST_FIELDS): the polish part of the last lockstep call of this handle
+        (settings.polishing); zeros before the first call and after a call without polishing."""
+        rec = np.zeros(len(self.LOCKSTEP_POLISH_LAST_FIELDS))
+        st = self._lib.osqp_hip_lockstep_polish_last_record(self._p, _ptr(rec, _lib.c_double_p))
+        if st:
+            raise ValueError(str(int(st)))
+        out = dict(zip(self.LOCKSTEP_POLISH_LAST_FIELDS, rec.tolist()))
+        for k in ('attempted', 'accepted', 'rejected', 'steps_max', 'pcg_iters', 'kernel_launches', 'workspace_bytes'):
             out[k] = int(out[k])
         return out
 
