@@ -1215,7 +1215,15 @@ __device__ __forceinline__ void f1_ka_body(const Dev &d, F1Lds &L, F1Stream &S, 
       const int bn = __builtin_amdgcn_readfirstlane(xcd * per + sl + slots);
       if (bn < d.A.nblk) f1_stream_issue<!WT>(f.stream, bn, S);
     }
-    // ---- rows: z~, the z / y update, v and t0 of the row (v -> LDS now, t0 kept for the second pass)
+    // ---- rows: z~, the z / y update, v and t0 of the row.  v -> LDS now; t0 is kept for the second pass, or -- the workgroup's LAST block
+    //      (`fused`, wave-uniform) -- goes to LDS next to it: no stream follows into S, and the block's own image there is dead -- every wave took
+    //      its entries into vw / en behind the f1_stream_wait() + barrier in front of the products phase, and the barrier above closed those
+    //      reads.  The image's value half then serves as a second product array, its index half as a second tvec (kF1MaxRows doubles), and
+    //      A_g' v and A_g' t0 run as ONE staged pass: two barriers between the row phase and the stores instead of five.  The column sums are
+    //      f1_segsum<8> over the same segments of the same products either way: tv and tt get the same bits.
+    const bool fused = !(sl + slots < per);
+    double *const prod2 = S.val, *const tvec2 = reinterpret_cast<double *>(S.ent);
+    static_assert(sizeof(S.ent) >= kF1MaxRows * sizeof(double) && sizeof(S.val) >= sizeof(L.prod), "the dead stream image holds the second tvec and product arrays");
     double t0r = 0.0;
     if (tid < nrows) {
       double vi;
@@ -1231,11 +1239,12 @@ __device__ __forceinline__ void f1_ka_body(const Dev &d, F1Lds &L, F1Stream &S, 
         gst(gptr(d.y) + i, yn); gst(gptr(d.dy) + i, dyi); gst(gptr(d.z) + i, zn); gst(gptr(d.zt) + i, ztil); gst(gptr(d.v) + i, vi); gst(gptr(d.ztg) + i, zg); gst(gptr(d.t0) + i, t0r);
       }
       L.tvec[tid] = vi;
+      if (fused) tvec2[tid] = t0r;
     }
-    for (int row = tid + kBlock; row < nrows; row += kBlock) {              // (blocks of more than kBlock rows; t0 of these rows is re-read from memory below)
+    for (int row = tid + kBlock; row < nrows; row += kBlock) {              // (blocks of more than kBlock rows; two passes: t0 of these rows is re-read from memory below)
       const int i = r0 + row;
-      double vi;
-      if (SCATTER_ONLY) vi = gptr(d.v)[i];
+      double vi, ti;
+      if (SCATTER_ONLY) { vi = gptr(d.v)[i]; ti = fused ? gptr(d.t0)[i] : 0.0; }
       else {
         const int q0 = gptr(d.A.rowptr)[i], q1 = gptr(d.A.rowptr)[i + 1];
         const double rho = gptr(d.rho)[i], zo = gptr(d.z)[i], yo = gptr(d.y)[i];
@@ -1244,45 +1253,66 @@ __device__ __forceinline__ void f1_ka_body(const Dev &d, F1Lds &L, F1Stream &S, 
         const double zn = fmin(fmax(zr + gptr(d.rho_inv)[i] * yo, gptr(d.l)[i]), gptr(d.u)[i]);
         const double dyi = rho * (zr - zn), yn = yo + dyi;
         const double zg = ztil + theta * (ztil - gptr(d.zt)[i]);
-        vi = rho * zn - yn;
-        gst(gptr(d.y) + i, yn); gst(gptr(d.dy) + i, dyi); gst(gptr(d.z) + i, zn); gst(gptr(d.zt) + i, ztil); gst(gptr(d.v) + i, vi); gst(gptr(d.ztg) + i, zg); gst(gptr(d.t0) + i, rho * zg);
+        vi = rho * zn - yn; ti = rho * zg;
+        gst(gptr(d.y) + i, yn); gst(gptr(d.dy) + i, dyi); gst(gptr(d.z) + i, zn); gst(gptr(d.zt) + i, ztil); gst(gptr(d.v) + i, vi); gst(gptr(d.ztg) + i, zg); gst(gptr(d.t0) + i, ti);
       }
       L.tvec[row] = vi;
+      if (fused) tvec2[row] = ti;                                           // (the value stored to t0 above: what the second pass would re-read)
     }
     // ---- (P + sigma I) x_g on the own columns
     if (tid < nown) L.puown[tid] = f1_segsum<4>(L.pprod, pp0 - pk0, pp1 - pk0);
     for (int jj = tid + kBlock; jj < nown; jj += kBlock) { const int q0 = gptr(f.prp)[cs0 + jj], q1 = gptr(f.prp)[cs0 + jj + 1]; L.puown[jj] = f1_segsum<4>(L.pprod, q0 - pk0, q1 - pk0); }
     __syncthreads();
-    // ---- first transposed pass: A_g' v
+    double cv[CW], ct[CW];                                   // the column's (far column's) sums of A_g' v and A_g' t0
+    auto col_on = [&](int u) { const int c = tid + u * kBlock; return c < wl || (MIX && u == CW - 1 && c >= kFB && c - kFB < nfc); };
+    if (fused) {
+      // ---- both transposed passes at once: A_g' v into L.prod, A_g' t0 into the dead stream image
 #pragma unroll
-    for (int u = 0; u < CE; u++) { if (u < nu) L.prod[en[u] >> 18] = vw[u] * L.tvec[(en[u] >> 9) & 0x1ffu]; }
-    __syncthreads();
-    double cv[CW];
+      for (int u = 0; u < CE; u++) {
+        if (u < nu) { const unsigned int at = en[u] >> 18, row = (en[u] >> 9) & 0x1ffu; L.prod[at] = vw[u] * L.tvec[row]; prod2[at] = vw[u] * tvec2[row]; }
+      }
+      __syncthreads();
 #pragma unroll
-    for (int u = 0; u < CW; u++) {
-      cv[u] = 0.0;
-      if (scatter_on(u)) { const int c = tid + u * kBlock; if (c < wl || (MIX && u == CW - 1 && c >= kFB && c - kFB < nfc)) cv[u] = f1_segsum<8>(L.prod, cp0[u], cp1[u]); }
+      for (int u = 0; u < CW; u++) {
+        cv[u] = 0.0; ct[u] = 0.0;
+        if (scatter_on(u)) { if (col_on(u)) { cv[u] = f1_segsum<8>(L.prod, cp0[u], cp1[u]); ct[u] = f1_segsum<8>(prod2, cp0[u], cp1[u]); } }
+      }
+    } else {
+      // ---- first transposed pass: A_g' v  (another block follows: its stream is landing in S)
+#pragma unroll
+      for (int u = 0; u < CE; u++) { if (u < nu) L.prod[en[u] >> 18] = vw[u] * L.tvec[(en[u] >> 9) & 0x1ffu]; }
+      __syncthreads();
+#pragma unroll
+      for (int u = 0; u < CW; u++) {
+        cv[u] = 0.0;
+        if (scatter_on(u)) { if (col_on(u)) cv[u] = f1_segsum<8>(L.prod, cp0[u], cp1[u]); }
+      }
+      __syncthreads();
+      // ---- second pass: A_g' t0
+      if (tid < nrows) L.tvec[tid] = t0r;
+      for (int row = tid + kBlock; row < nrows; row += kBlock) L.tvec[row] = gptr(d.t0)[r0 + row];      // (written by this thread above, or by an earlier launch)
+      __syncthreads();
+#pragma unroll
+      for (int u = 0; u < CE; u++) { if (u < nu) L.prod[en[u] >> 18] = vw[u] * L.tvec[(en[u] >> 9) & 0x1ffu]; }
+      __syncthreads();
+#pragma unroll
+      for (int u = 0; u < CW; u++) {
+        ct[u] = 0.0;
+        if (scatter_on(u)) { if (col_on(u)) ct[u] = f1_segsum<8>(L.prod, cp0[u], cp1[u]); }
+      }
     }
-    __syncthreads();
-    // ---- second pass: A_g' t0
-    if (tid < nrows) L.tvec[tid] = t0r;
-    for (int row = tid + kBlock; row < nrows; row += kBlock) L.tvec[row] = gptr(d.t0)[r0 + row];      // (written by this thread above, or by an earlier launch)
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < CE; u++) { if (u < nu) L.prod[en[u] >> 18] = vw[u] * L.tvec[(en[u] >> 9) & 0x1ffu]; }
-    __syncthreads();
     double *routR = repR + (size_t)(b % D) * ns, *routV = repV + (size_t)(b % D) * ns;
 #pragma unroll
     for (int u = 0; u < CW; u++) {
       if (scatter_on(u)) {
         const int c = tid + u * kBlock;
         if (c < wl) {
-          double tv = cv[u], tt = f1_segsum<8>(L.prod, cp0[u], cp1[u]);
+          double tv = cv[u], tt = ct[u];
           const int jo = a0 + c - cs0;
           if (jo >= 0 && jo < nown) { tv += L.uown[jo]; tt += L.puown[jo]; }      // this block owns the column: + sigma x - q  resp.  + (P + sigma I) x_g
           gst(routV + a0 + c, tv); gst(routR + a0 + c, tv - tt);                             // slices of rhs, and of r_0 = rhs - K x_g
         } else if constexpr (MIX) {
-          if (u == CW - 1 && c >= kFB && c - kFB < nfc) { const double tv = cv[u], tt = f1_segsum<8>(L.prod, cp0[u], cp1[u]); gst(spVw + fql, tv); gst(spR + fql, tv - tt); }      // a far column: the block's spill slots
+          if (u == CW - 1 && c >= kFB && c - kFB < nfc) { const double tv = cv[u], tt = ct[u]; gst(spVw + fql, tv); gst(spR + fql, tv - tt); }      // a far column: the block's spill slots
         }
       }
     }
