@@ -289,7 +289,7 @@ OSQPInt osqp_hip_batch_solve_mat_device(OSQPSolver *solver, OSQPInt nbatch, cons
  * A' diag(rho_b) A stopped per problem at cg_tol_fraction x the scaled dual residual (non-increasing; relative before the first residual), equality
  * weight and adaptive rho per problem, termination / approximate statuses at max_iter / infeasibility certificates in x, y / OSQP_NON_CVX on
  * non-finite residuals decided per problem on the device every check_termination / adaptive_rho_interval iterations; time_limit ends a chunk with
- * OSQP_TIME_LIMIT_REACHED for its unfinished problems.  check_dualgap is ignored, no per-problem matrices.
+ * OSQP_TIME_LIMIT_REACHED for its unfinished problems.  check_dualgap is ignored; per-problem matrices: osqp_hip_batch_solve_lockstep_mat below.
  * POLISH: with settings.polishing every problem of a chunk that ends OSQP_SOLVED is polished before the chunk is written out, all of them at once, by the
  * recurrence osqp_solve's polish runs on the PCG path: the active rows guessed from the ADMM (z, y) (equality rows always), the reduced KKT system solved
  * by steps of this route's own iteration with alpha = 1 and rho = 1 / max(delta, OSQP_HIP_POLISH_DELTA_FLOOR) on the active rows, the others free, the
@@ -324,6 +324,36 @@ OSQPInt osqp_hip_batch_solve_lockstep_device(OSQPSolver *solver, OSQPInt nbatch,
                                              OSQPFloat *x_dev, OSQPFloat *y_dev, OSQPFloat *rec_dev, OSQPInt warm_start, void *stream);
 OSQPInt osqp_hip_lockstep_last_record(OSQPSolver *solver, OSQPFloat *rec);
 OSQPInt osqp_hip_lockstep_polish_last_record(OSQPSolver *solver, OSQPFloat *rec);
+/* LOCKSTEP WITH PER-PROBLEM MATRICES: the lockstep route for a batch in which every problem has its own values of P and A on the handle's sparsity pattern
+ * (the reference's forward with a P_val / A_val per batch element), at any size -- what osqp_hip_batch_solve_mat serves only while a problem fits one
+ * workgroup's LDS.  Px is nbatch x nnz(triu P), Ax nbatch x nnz(A), both in the CSC order given at setup (the layout of osqp_hip_batch_solve_mat); either
+ * may be NULL: the handle's own raw values for every problem.  Everything else -- q / l / u / x / y / rec / warm, the nbatch == 0 query, the stream
+ * semantics, the OSQP_HIP_BATCH_REC record, per-problem termination, statuses, certificates, time_limit -- is osqp_hip_batch_solve_lockstep[_device]'s.
+ * SCALING: every problem is assembled and equilibrated with its own P_b, q_b, A_b exactly as a solver set up with that data alone: settings.scaling
+ * iterations of the reference's Ruiz rule with its scaling limits, sigma added after the equilibration.  The problem's values travel problem-minor in a
+ * matrix block of 64 x (nnz(A) + nnz([P | A']) + 2n + 2m) doubles, allocated by the first call and freed with the handle; a chunk's assembly and
+ * equilibration are 5 + 4 x settings.scaling launches in front of its transposes in.
+ * INDEPENDENCE as above, a problem's matrices being part of the problem.  A reordered handle is served.  The handle's own matrices, scaling, iterates,
+ * graphs and history are not touched.
+ * POLISH is off on this entry whatever settings.polishing says: record fields 8 and 9 stay 0.
+ * Returns OSQP_FUNC_NOT_IMPLEMENTED for whatever osqp_hip_batch_solve_lockstep declines, for a handle without device-side assembly, and for a handle whose
+ * stored upper triangle of P holds a repeated (j, j) entry (the single-handle assembly sums those; this route has one writer per entry).
+ * OUT OF SCOPE: polish and adjoint derivatives with per-problem matrices, the direct (Woodbury) route, multi-rank sharding of this entry, repeated
+ * diagonal entries of P.
+ * osqp_hip_lockstep_mat_last_record: OSQP_HIP_LOCKSTEP_MAT_LAST_REC doubles {chunks, chunk width, ADMM iterations of the slowest problem, PCG iterations
+ * summed, kernel launches of the whole call, GPU ms of the whole call, bytes of the matrix block, GPU ms spent in assembly + equilibration}; all zero
+ * before the first call.  osqp_hip_lockstep_last_record is written as by any lockstep call.
+ * osqp_hip_lockstep_mat_scaling: D (n), E (m) and c of problem b of the LAST chunk the last such call processed, numbered as osqp_hip_get_scaling numbers
+ * the handle's -- so that the per-problem equilibration can be checked directly.  OSQP_DATA_NOT_INITIALIZED before the first call or for b outside
+ * that chunk. */
+#define OSQP_HIP_LOCKSTEP_MAT_LAST_REC 8
+OSQPInt osqp_hip_batch_solve_lockstep_mat(OSQPSolver *solver, OSQPInt nbatch, const OSQPFloat *Px, const OSQPFloat *Ax, const OSQPFloat *q, const OSQPFloat *l,
+                                          const OSQPFloat *u, OSQPFloat *x, OSQPFloat *y, OSQPFloat *rec, OSQPInt warm);
+OSQPInt osqp_hip_batch_solve_lockstep_mat_device(OSQPSolver *solver, OSQPInt nbatch, const OSQPFloat *Px_dev, const OSQPFloat *Ax_dev, const OSQPFloat *q_dev,
+                                                 const OSQPFloat *l_dev, const OSQPFloat *u_dev, OSQPFloat *x_dev, OSQPFloat *y_dev, OSQPFloat *rec_dev,
+                                                 OSQPInt warm_start, void *stream);
+OSQPInt osqp_hip_lockstep_mat_last_record(OSQPSolver *solver, OSQPFloat *rec);
+OSQPInt osqp_hip_lockstep_mat_scaling(OSQPSolver *solver, OSQPInt b, OSQPFloat *D, OSQPFloat *E, OSQPFloat *c);
 /* LOCKSTEP DIRECT: the lockstep route for the handles it declines -- a Woodbury-corrected handle (OSQPHipStats::woodbury_rows = r > 0) in the small mode
  * (r <= 128) whose K0 = P + sigma I + A_S' rho A_S setup found structurally DIAGONAL: P diagonal, every row of A either long (one of the r dense rows A_L)
  * or with at most one entry, no long row storing a (row, column) twice -- the factor-model portfolio QP.  Then K_b = D0_b + A_L' rho_L,b A_L and the

@@ -117,6 +117,16 @@ OSQPInt osqp_hip_batch_solve_lockstep_device(OSQPSolver *s, OSQPInt nbatch, cons
 }
 OSQPInt osqp_hip_lockstep_last_record(OSQPSolver *s, OSQPFloat *rec) { return guarded(s, [&](Engine &e) { return e.lockstep_last_record(rec); }); }
 OSQPInt osqp_hip_lockstep_polish_last_record(OSQPSolver *s, OSQPFloat *rec) { return guarded(s, [&](Engine &e) { return e.lockstep_polish_last_record(rec); }); }
+OSQPInt osqp_hip_batch_solve_lockstep_mat(OSQPSolver *s, OSQPInt nbatch, const OSQPFloat *Px, const OSQPFloat *Ax, const OSQPFloat *q, const OSQPFloat *l, const OSQPFloat *u, OSQPFloat *x, OSQPFloat *y,
+                                          OSQPFloat *rec, OSQPInt warm) {
+  return guarded(s, [&](Engine &e) { return e.batch_solve_lockstep_mat(nbatch, Px, Ax, q, l, u, x, y, rec, warm); });
+}
+OSQPInt osqp_hip_batch_solve_lockstep_mat_device(OSQPSolver *s, OSQPInt nbatch, const OSQPFloat *Px, const OSQPFloat *Ax, const OSQPFloat *q, const OSQPFloat *l, const OSQPFloat *u, OSQPFloat *x,
+                                                 OSQPFloat *y, OSQPFloat *rec, OSQPInt warm, void *stream) {
+  return guarded(s, [&](Engine &e) { return e.batch_solve_lockstep_mat_device(nbatch, Px, Ax, q, l, u, x, y, rec, warm, stream); });
+}
+OSQPInt osqp_hip_lockstep_mat_last_record(OSQPSolver *s, OSQPFloat *rec) { return guarded(s, [&](Engine &e) { return e.lockstep_mat_last_record(rec); }); }
+OSQPInt osqp_hip_lockstep_mat_scaling(OSQPSolver *s, OSQPInt b, OSQPFloat *D, OSQPFloat *E, OSQPFloat *c) { return guarded(s, [&](Engine &e) { return e.lockstep_mat_scaling(b, D, E, c); }); }
 OSQPInt osqp_hip_batch_solve_lockstep_direct(OSQPSolver *s, OSQPInt nbatch, const OSQPFloat *q, const OSQPFloat *l, const OSQPFloat *u, OSQPFloat *x, OSQPFloat *y, OSQPFloat *rec, OSQPInt warm) {
   return guarded(s, [&](Engine &e) { return e.batch_solve_lockstep_direct(nbatch, q, l, u, x, y, rec, warm); });
 }

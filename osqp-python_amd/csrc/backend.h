@@ -497,8 +497,27 @@ struct LockstepParams : BatchSettings {
   int polish = 0, pol_min_steps = 1, pol_cg_max = 0;
   double pol_rho = 0, pol_pcg_rel = 0;
   double *pol_ws = nullptr, *pol_stat = nullptr;
+  // PER-PROBLEM MATRICES (lockstep_hip.hip "matrices of a chunk"; include/osqp_hip.h osqp_hip_batch_solve_lockstep_mat): mat_ws != nullptr switches the chunk to
+  // its own matrix block (lockstep_mat_ws_doubles(n, m, nnz(A), nnz(B)) doubles, device): Aval[k * kLsW + b], Bval[k * kLsW + b], D, Dinv (n x kLsW), E, Einv
+  // (m x kLsW), assembled from the chunk's rows Px / Ax of the caller's [nbatch][nnz(triu P)] / [nbatch][nnz(A)] arrays (the caller's CSC order; nullptr: the
+  // handle's raw values for every problem) and equilibrated per problem in front of the transposes in; c and 1 / c are rows of the per-problem scalar
+  // state.  pvmap / avmap: caller's position -> the engine's (reordered handle; nullptr: identity).  mat_iters: settings.scaling.  mat_stat (host,
+  // kLsMatStat doubles, nullptr: not wanted): GPU ms and kernel launches of the assembly + equilibration.  Set by Engine::run_lockstep alone.
+  double *mat_ws = nullptr, *mat_stat = nullptr;
+  const double *Px = nullptr, *Ax = nullptr;
+  const int *pvmap = nullptr, *avmap = nullptr;
+  int mat_iters = 0;
 };
 constexpr int kLsPolStat = 7;
+constexpr int kLsMatStat = 2;
+constexpr int kLsMatScalC = 11;   // row of the per-problem scalar state that holds c (lockstep_hip.hip SC_C; 1 / c follows)
+// where the per-problem scalar state sits in a chunk's workspace (lockstep_hip.hip lockstep_chunk's carve-up: the block vectors, the partials, parti)
+inline size_t lockstep_sc_offset(int n, int m) {
+  const size_t tm = (size_t)(m + 63) / 64;
+  return (size_t)kLsW * (8 * (size_t)n + 9 * (size_t)m + (size_t)kLsSlots * lockstep_grid(n, m) + (tm > 0 ? tm : 1));
+}
+// doubles of the matrix block of a chunk with per-problem matrices: both value arrays, D, Dinv, E, Einv
+inline size_t lockstep_mat_ws_doubles(int n, int m, int nzA, int nzB) { return (size_t)kLsW * ((size_t)nzA + (size_t)nzB + 2 * (size_t)n + 2 * (size_t)m) + 64; }
 // doubles of the polish work block: the scaled ADMM x (n) and y, z, l, u (m) of every problem of the chunk
 inline size_t lockstep_polish_ws_doubles(int n, int m) { return (size_t)kLsW * ((size_t)n + 4 * (size_t)m) + 64; }
 

@@ -163,6 +163,8 @@ void Engine::free_all() {
   if (ckpt_) { be::dfree(d_, ckpt_); ckpt_ = nullptr; }
   if (lsw_) { be::dfree(d_, lsw_); lsw_ = nullptr; }
   if (lspw_) { be::dfree(d_, lspw_); lspw_ = nullptr; }
+  if (lsmw_) { be::dfree(d_, lsmw_); lsmw_ = nullptr; }
+  lsm_last_count_ = 0; std::fill(lsm_rec_, lsm_rec_ + OSQP_HIP_LOCKSTEP_MAT_LAST_REC, 0.0);
   if (lsaw_) { be::dfree(d_, lsaw_); lsaw_ = nullptr; }
   if (lsdw_) { be::dfree(d_, lsdw_); lsdw_ = nullptr; }
   if (lsdaw_) { be::dfree(d_, lsdaw_); lsdaw_ = nullptr; }

@@ -63,6 +63,12 @@ class Engine {
   int batch_solve_lockstep(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm);
   int batch_solve_lockstep_device(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream);
   int lockstep_last_record(double *rec) const;
+  // The same route with a P_val / A_val per problem (include/osqp_hip.h osqp_hip_batch_solve_lockstep_mat; lockstep_hip.hip "matrices of a chunk"): Px / Ax are
+  // [nbatch][nnz(triu P)] / [nbatch][nnz(A)] in the CSC order given at setup, either may be NULL (the handle's own raw values); no polish.
+  int batch_solve_lockstep_mat(int nbatch, const double *Px, const double *Ax, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm);
+  int batch_solve_lockstep_mat_device(int nbatch, const double *Px, const double *Ax, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream);
+  int lockstep_mat_last_record(double *rec) const;
+  int lockstep_mat_scaling(int b, double *D, double *E, double *c);
   int lockstep_polish_last_record(double *rec) const;
   // The direct lockstep route for a Woodbury handle with a diagonal K0 (include/osqp_hip.h osqp_hip_batch_solve_lockstep_direct; lockstep_hip.hip "lockstep
   // DIRECT"): the same arguments and semantics; every other handle -- a reordered one included -- gets OSQP_FUNC_NOT_IMPLEMENTED.
@@ -151,7 +157,13 @@ class Engine {
   double ls_rec_[OSQP_HIP_LOCKSTEP_LAST_REC] = {0, 0, 0, 0, 0, 0, 0, 0};      // record of the last lockstep call (osqp_hip_lockstep_last_record)
   double *lspw_ = nullptr;                            // polish work block of one lockstep chunk (lockstep_polish_ws_doubles(n, m)), allocated by the first polishing call
   double ls_pol_rec_[OSQP_HIP_LOCKSTEP_POLISH_LAST_REC] = {0, 0, 0, 0, 0, 0, 0, 0};      // polish record of the last lockstep call (osqp_hip_lockstep_polish_last_record)
-  int run_lockstep(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream);
+  // mat: the per-problem-matrix entries (Px / Ax device arrays in the caller's CSC order, either may be nullptr); the shared entries leave it false
+  int run_lockstep(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream,
+                   bool mat = false, const double *Px = nullptr, const double *Ax = nullptr);
+  double *lsmw_ = nullptr;                            // matrix block of one lockstep chunk (lockstep_mat_ws_doubles), allocated by the first call with per-problem matrices
+  double lsm_rec_[OSQP_HIP_LOCKSTEP_MAT_LAST_REC] = {0, 0, 0, 0, 0, 0, 0, 0};      // record of the last such call (osqp_hip_lockstep_mat_last_record)
+  int lsm_last_count_ = 0;                            // problems of the last chunk that call processed (0: no call yet): what lockstep_mat_scaling reads
+  bool lockstep_mat_applies();
   // direct lockstep route: the structural decision of prepare_wb (K0 diagonal, small mode -- not DevWb::exact, which a failed inversion clears), the
   // chunk's workspace (lockstep_direct_ws_doubles(n, m, r)) and the view of A (LockstepDirectParams::Av), both built on first use, the last call's record
   bool wb_k0diag_ = false;

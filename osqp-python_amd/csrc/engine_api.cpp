@@ -790,7 +790,7 @@ int Engine::batch_enter(int nbatch, bool query, const double *x, const double *y
 //             passes ipr_ on a reordered handle -- the copies are kept in the engine's numbering; the workgroup route refuses reordered handles;
 //   wg        the workgroup route appends [q0 | l0 | u0 | Px | Ax]: the handle's own vectors for the arguments given as NULL, uploaded where they
 //             are not resident (!be::device_vec_updates(); dq0 .. du0 point at the resident ones otherwise), and the per-problem matrix values.  The
-//             lockstep route reads d_.qraw .. itself and has no per-problem matrices.
+//             lockstep route reads d_.qraw .. itself; its per-problem matrix values (batch_solve_lockstep_mat) follow the records directly.
 struct Engine::BatchStage {
   Engine &e; int nbatch;
   bool (Engine::*applies)();                          // the route
@@ -814,18 +814,19 @@ struct Engine::BatchStage {
       }
     t[1] = now_s();
     const size_t NP = Px ? (size_t)nbatch * e.P_.nnz() : 0, NA = Ax ? (size_t)nbatch * e.A_.nnz() : 0;
-    const size_t need = 2 * N + 3 * M + (size_t)nbatch * kBatchRec + (wg ? n + 2 * (size_t)m + NP + NA : 0);
+    const size_t need = 2 * N + 3 * M + (size_t)nbatch * kBatchRec + (wg ? n + 2 * (size_t)m : 0) + NP + NA;
     if (need > e.bbuf_cap_) { if (e.bbuf_) be::dfree(d, e.bbuf_); e.bbuf_ = dev_vec<double>(d, need); e.bbuf_cap_ = need; }
     dq = e.bbuf_; dl = dq + N; du = dl + M; dx = du + M; dy = dx + N; drec = dy + M;
     if (wg) {
       dq0 = drec + (size_t)nbatch * kBatchRec; dl0 = dq0 + n; du0 = dl0 + m; dPx = du0 + m; dAx = dPx + NP;
-      if (Px) be::h2d(d, dPx, Px, sizeof(double) * NP);
-      if (Ax) be::h2d(d, dAx, Ax, sizeof(double) * NA);
       const bool devv = be::device_vec_updates();       // then the solver's own q, l, u are resident (unscaled): no upload for NULL arguments
       if (!q) { if (devv) dq0 = d.qraw; else be::h2d(d, dq0, e.q0_.data(), sizeof(double) * n); }
       if (!l) { if (devv) dl0 = d.lraw; else be::h2d(d, dl0, e.l0_.data(), sizeof(double) * m); }
       if (!u) { if (devv) du0 = d.uraw; else be::h2d(d, du0, e.u0_.data(), sizeof(double) * m); }
     }
+    else { dPx = drec + (size_t)nbatch * kBatchRec; dAx = dPx + NP; }
+    if (Px) be::h2d(d, dPx, Px, sizeof(double) * NP);
+    if (Ax) be::h2d(d, dAx, Ax, sizeof(double) * NA);
     if (q) be::h2d(d, dq, q, sizeof(double) * N);
     if (l) be::h2d(d, dl, l, sizeof(double) * M);
     if (u) be::h2d(d, du, u, sizeof(double) * M);
@@ -904,9 +905,20 @@ int Engine::batch_solve_device(int nbatch, const double *q, const double *l, con
 // Chunks of kLsW problems, one after the other, each from its transposes in to its transposes out (be::lockstep_chunk).  q / l / u / x / y / rec are
 // DEVICE arrays in the caller's numbering; the settings are read once, in front of the first chunk.  The handle's iterates are not touched: the route
 // has its own workspace (lsw_, allocated on first use, freed with the handle) and, with polishing, its own polish work block (lspw_, likewise).
-int Engine::run_lockstep(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream) {
+int Engine::run_lockstep(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream,
+                         bool mat, const double *Px, const double *Ax) {
   const size_t need = lockstep_ws_doubles(n, m);
   if (!lsw_) { lsw_ = dev_vec<double>(d_, need); be::sync(d_); }
+  // per-problem matrices: the matrix block (allocated by the first such call) and, on a reordered handle, the value maps the lockstep adjoint uploads too
+  const int nzP = d_.nzP, nzA = d_.nzA;
+  const size_t mneed = lockstep_mat_ws_doubles(n, m, d_.A.nnz, d_.B.nnz);
+  if (mat) {
+    bool fresh = false;
+    if (!lsmw_) { lsmw_ = dev_vec<double>(d_, mneed); fresh = true; }
+    if (reordered_ && !d_pvmap_ && nzP > 0) { d_pvmap_ = dev_vec<int>(d_, nzP); be::h2d(d_, d_pvmap_, PvalMap_.data(), sizeof(int) * nzP); fresh = true; }
+    if (reordered_ && !d_avmap_ && nzA > 0) { d_avmap_ = dev_vec<int>(d_, nzA); be::h2d(d_, d_avmap_, AvalMap_.data(), sizeof(int) * nzA); fresh = true; }
+    if (fresh) be::sync(d_);
+  }
   LockstepParams p;
   fill_batch_settings(p, warm);                       // the settings snapshot of the batch path
   p.n = n; p.m = m; p.A = d_.A; p.B = d_.B; p.D = d_.D; p.Dinv = d_.Dinv; p.E = d_.E; p.Einv = d_.Einv;
@@ -915,7 +927,12 @@ int Engine::run_lockstep(int nbatch, const double *q, const double *l, const dou
   // at least 1 + polish_refine_iter steps, the inner systems to polish_pcg_tol within kMaxCg iterations.  Its work block is allocated by the first such call.
   double pst[kLsPolStat] = {0, 0, 0, 0, 0, 0, 0}, ptot[kLsPolStat] = {0, 0, 0, 0, 0, 0, 0};
   const size_t pneed = lockstep_polish_ws_doubles(n, m);
-  if (settings.polishing) {
+  double mst[kLsMatStat] = {0, 0}, mtot[kLsMatStat] = {0, 0};
+  if (mat) {
+    p.mat_ws = lsmw_; p.mat_stat = mst; p.mat_iters = std::max(0, (int)settings.scaling);
+    p.pvmap = reordered_ ? d_pvmap_ : nullptr; p.avmap = reordered_ ? d_avmap_ : nullptr;
+  }
+  if (settings.polishing && !mat) {                   // (the per-problem-matrix entries pass polish off)
     if (!lspw_) { lspw_ = dev_vec<double>(d_, pneed); be::sync(d_); }
     const double de = std::max(settings.delta, pol_.polish_delta_floor);
     p.polish = 1; p.pol_rho = clamp_rho(1.0 / de); p.pol_min_steps = 1 + std::max(0, (int)settings.polish_refine_iter);
@@ -929,18 +946,83 @@ int Engine::run_lockstep(int nbatch, const double *q, const double *l, const dou
     p.count = std::min(kLsW, nbatch - b0);
     p.q = q ? q + (size_t)b0 * n : nullptr; p.l = l ? l + (size_t)b0 * m : nullptr; p.u = u ? u + (size_t)b0 * m : nullptr;
     p.x = x + (size_t)b0 * n; p.y = y + (size_t)b0 * m; p.rec = rec + (size_t)b0 * kBatchRec;
+    p.Px = (mat && Px) ? Px + (size_t)b0 * nzP : nullptr; p.Ax = (mat && Ax) ? Ax + (size_t)b0 * nzA : nullptr;
     p.time_limit = limit > 0 ? std::max(limit - (now_s() - t0), 1e-9) : 0.0;
     double st[4] = {0, 0, 0, 0};
     std::fill(pst, pst + kLsPolStat, 0.0);
+    if (mat) lsm_last_count_ = 0;                     // (the block is being overwritten)
     const int err = be::lockstep_chunk(d_, p, stream, st);
     if (err) return err;
+    if (mat) { lsm_last_count_ = p.count; mtot[0] += mst[0]; mtot[1] += mst[1]; }
     tot[0] = std::max(tot[0], st[0]); tot[1] += st[1]; tot[2] += st[2]; tot[3] += st[3];
     for (int k = 0; k < kLsPolStat; k++) ptot[k] = k == 3 ? std::max(ptot[k], pst[k]) : ptot[k] + pst[k];
   }
   const double r[OSQP_HIP_LOCKSTEP_LAST_REC] = {(double)chunks, (double)kLsW, tot[0], tot[1], tot[2], tot[3], (double)(need * sizeof(double)), 0.0};
   std::copy(r, r + OSQP_HIP_LOCKSTEP_LAST_REC, ls_rec_);
   std::copy(ptot, ptot + kLsPolStat, ls_pol_rec_);
-  ls_pol_rec_[kLsPolStat] = settings.polishing ? (double)(pneed * sizeof(double)) : 0.0;
+  ls_pol_rec_[kLsPolStat] = (settings.polishing && !mat) ? (double)(pneed * sizeof(double)) : 0.0;
+  if (mat) {
+    const double rm[OSQP_HIP_LOCKSTEP_MAT_LAST_REC] = {(double)chunks, (double)kLsW, tot[0], tot[1], tot[2], tot[3], (double)(mneed * sizeof(double)), mtot[0]};
+    std::copy(rm, rm + OSQP_HIP_LOCKSTEP_MAT_LAST_REC, lsm_rec_);
+  }
+  return OSQP_NO_ERROR;
+}
+
+// ---- per-problem matrices on the lockstep route (include/osqp_hip.h osqp_hip_batch_solve_lockstep_mat)
+// What lockstep_applies() declines, a handle without device assembly and a handle whose stored upper triangle of P holds a repeated (j, j) entry (the
+// single-handle assembly sums those with a floating-point atomic; the chunk's assembly has one writer per entry) are declined.
+bool Engine::lockstep_mat_applies() {
+  if (!lockstep_applies() || !be::device_assembly() || !d_.Praw || !d_.Araw) return false;
+  for (int j = 0; j < n; j++) {
+    int diag = 0;
+    for (int k = P_.p[j]; k < P_.p[j + 1]; k++) diag += P_.i[k] == j;
+    if (diag > 1) return false;
+  }
+  return true;
+}
+
+int Engine::batch_solve_lockstep_mat(int nbatch, const double *Px, const double *Ax, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm) {
+  BatchStage s{*this, nbatch, &Engine::lockstep_mat_applies, /*own_row=*/reordered_ ? ipr_.data() : nullptr, /*wg=*/false};
+  if (const int err = s.in(q, l, u, x, y, rec, warm, Px, Ax)) return err;
+  const int err = run_lockstep(nbatch, q ? s.dq : nullptr, l ? s.dl : nullptr, u ? s.du : nullptr, s.dx, s.dy, s.drec, warm, nullptr, true, Px ? s.dPx : nullptr, Ax ? s.dAx : nullptr);
+  if (!err) s.out(x, y, rec);
+  return err;
+}
+
+int Engine::batch_solve_lockstep_mat_device(int nbatch, const double *Px, const double *Ax, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream) {
+  const int enter = batch_enter(nbatch, true, x, y, rec, &Engine::lockstep_mat_applies);
+  if (enter != kBatchEnter) return enter;
+  be::sync(d_);                                     // the solver's own stream first: pending updates of the resident q / l / u, the raw matrix values
+  return run_lockstep(nbatch, q, l, u, x, y, rec, warm, stream, true, Px, Ax);
+}
+
+int Engine::lockstep_mat_last_record(double *rec) const {
+  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (!rec) return OSQP_DATA_VALIDATION_ERROR;
+  std::copy(lsm_rec_, lsm_rec_ + OSQP_HIP_LOCKSTEP_MAT_LAST_REC, rec);
+  return OSQP_NO_ERROR;
+}
+
+// D, E, c of problem b of the last chunk the last call with per-problem matrices processed, in the caller's numbering: read back from the matrix block
+// (lockstep_hip.hip "matrices of a chunk": [Aval | Bval | D | Dinv | E | Einv], problem-minor) and the chunk's scalar state (row 11 of kLsScal: c)
+int Engine::lockstep_mat_scaling(int b, double *D, double *E, double *c) {
+  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (!D || (m > 0 && !E) || !c) return OSQP_DATA_VALIDATION_ERROR;
+  if (!lsmw_ || !lsw_ || b < 0 || b >= lsm_last_count_) return OSQP_DATA_NOT_INITIALIZED;
+  be::activate(d_);
+  be::ext_wait(d_);
+  const size_t nW = (size_t)n * kLsW, mW = (size_t)m * kLsW;
+  const double *dD = lsmw_ + (size_t)kLsW * ((size_t)d_.A.nnz + (size_t)d_.B.nnz), *dE = dD + 2 * nW;
+  std::vector<double> h(std::max(nW, mW));
+  be::d2h(d_, h.data(), dD, sizeof(double) * nW);
+  for (int j = 0; j < n; j++) D[reordered_ ? pc_[j] : j] = h[(size_t)j * kLsW + b];
+  if (m > 0) {
+    be::d2h(d_, h.data(), dE, sizeof(double) * mW);
+    for (int i = 0; i < m; i++) E[reordered_ ? pr_[i] : i] = h[(size_t)i * kLsW + b];
+  }
+  double cs[kLsW];
+  be::d2h(d_, cs, lsw_ + lockstep_sc_offset(n, m) + (size_t)kLsMatScalC * kLsW, sizeof(cs));
+  *c = cs[b];
   return OSQP_NO_ERROR;
 }
 

@@ -1,5 +1,6 @@
 // lockstep_hip.hip -- the LOCKSTEP batch route (include/osqp_hip.h osqp_hip_batch_solve_lockstep; engine_api.cpp Engine::batch_solve_lockstep):
-// a batch of QPs that share this handle's P, A, scaling and settings and differ in q / l / u, at ANY size a handle can be set up for.  The two batch
+// a batch of QPs that share this handle's P, A, scaling and settings and differ in q / l / u (or, osqp_hip_batch_solve_lockstep_mat, have their own values of
+// P and A on the handle's pattern and their own scaling: "matrices of a chunk"), at ANY size a handle can be set up for.  The two batch
 // kernels of batch_hip.hip keep one problem in one workgroup's LDS; here the ADMM / PCG iteration of k_batch_admm's non-direct variants runs on BLOCK
 // VECTORS instead: kLsW = 64 problems advance together, LANES ARE PROBLEMS.
 //
@@ -43,11 +44,13 @@ enum LsSlot {
   PS_COUNT = PS_N0 + 17
 };
 static_assert(PS_COUNT <= kLsSlots, "lockstep_ws_doubles reserves kLsSlots partial slots");
-enum LsScal { SC_RHOBAR = 0, SC_EQF, SC_EPSCG, SC_EPSPREV, SC_RZ, SC_RN, SC_TOL, SC_ALPHA, SC_BETA, SC_BEST /* adjoint: smallest error so far */, SC_NACT /* adjoint: active rows */, SC_COUNT };
+enum LsScal { SC_RHOBAR = 0, SC_EQF, SC_EPSCG, SC_EPSPREV, SC_RZ, SC_RN, SC_TOL, SC_ALPHA, SC_BETA, SC_BEST /* adjoint: smallest error so far */, SC_NACT /* adjoint: active rows */,
+              SC_C /* per-problem matrices: the problem's cost scale c, 1 / c, this pass's factor */, SC_CINV, SC_CT, SC_COUNT };
 enum LsInt { IW_DONE = 0, IW_STATUS, IW_RHOUPD, IW_PCG, IW_RELRULE, IW_CGON, IW_RHOCH, IW_STEPS /* adjoint: recurrence steps */, IW_WORSE /* adjoint: steps in a row without progress */,
              IW_SIDE /* direct route: single_rho_rule's side at the previous adaptation point */, IW_POL /* polish: 1 attempted, 2 attempted and rejected */, IW_COUNT };
 enum LsWord { WD_CGANY = 0, WD_LIVE, WD_RHOANY, WD_PCGSUM, WD_CGIT /* PCG iterations of the current ADMM iteration that some problem needed */,
               WD_POLACC /* polish: problems accepted */, WD_POLREJ /* rejected */, WD_COUNT };
+static_assert(SC_C == kLsMatScalC, "Engine::lockstep_mat_scaling reads c from this row");
 static_assert(SC_COUNT <= kLsScal && IW_COUNT + 1 <= kLsInt, "lockstep_ws_doubles reserves kLsScal / kLsInt rows");
 
 struct LsWs {
@@ -98,12 +101,14 @@ __device__ __forceinline__ double ls_fold(const double *part, int G, int slot, d
 // ---------------------------------------------------------------------------------------------------------------- row passes
 // Rows [r0, r1) of M belong to this wave (the partition depends on the row count and the grid alone).  F: begin(row); load(c, g) issues the gathers
 // of one entry; fma(c, v, g, acc) adds it; row(row, acc) is the epilogue.  Everything about an entry but the gathered operands is wave-uniform.
-template <int NG, int NA, class F>
+// MAT (per-problem matrices, "matrices of a chunk" below): M.val is a block, entry k of problem b at k * 64 + b -- the value is one more 512-byte line per
+// entry, loaded with the column indices ahead of the gathers, in place of a broadcast.
+template <int NG, int NA, bool MAT = false, class F>
 __device__ __forceinline__ void ls_rows(const DevCsr &M, F &f) {
   const int nw = gridDim.x * 4, rpw = (M.nrows + nw - 1) / nw;
   const int r0 = ((int)blockIdx.x * 4 + ls_wave()) * rpw, r1 = min(r0 + rpw, M.nrows);
   const int *__restrict__ rp = M.rowptr, *__restrict__ col = M.col;
-  const double *__restrict__ val = M.val;
+  const double *__restrict__ val = MAT ? M.val + ls_lane() : M.val;
   for (int row = r0; row < r1; row++) {
     int k = __builtin_amdgcn_readfirstlane(rp[row]);
     const int k1 = __builtin_amdgcn_readfirstlane(rp[row + 1]);
@@ -114,14 +119,14 @@ __device__ __forceinline__ void ls_rows(const DevCsr &M, F &f) {
     for (; k + 4 <= k1; k += 4) {
       int c[4]; double v[4], g[4][NG];
 #pragma unroll
-      for (int u = 0; u < 4; u++) { c[u] = __builtin_amdgcn_readfirstlane(col[k + u]); v[u] = val[k + u]; }
+      for (int u = 0; u < 4; u++) { c[u] = __builtin_amdgcn_readfirstlane(col[k + u]); v[u] = MAT ? val[(size_t)(k + u) * 64] : val[k + u]; }
 #pragma unroll
       for (int u = 0; u < 4; u++) f.load(c[u], g[u]);
 #pragma unroll
       for (int u = 0; u < 4; u++) f.fma(c[u], v[u], g[u], acc);
     }
     for (; k < k1; k++) {
-      const int c = __builtin_amdgcn_readfirstlane(col[k]); const double v = val[k];
+      const int c = __builtin_amdgcn_readfirstlane(col[k]); const double v = MAT ? val[(size_t)k * 64] : val[k];
       double g[NG];
       f.load(c, g); f.fma(c, v, g, acc);
     }
@@ -129,6 +134,12 @@ __device__ __forceinline__ void ls_rows(const DevCsr &M, F &f) {
   }
 }
 #define IX(j) ((size_t)(j) * 64 + lane)
+// a scaling D / Dinv / E / Einv: the handle's vector, or (MAT) the problem's own column of a block
+template <bool MAT> __device__ __forceinline__ double ls_sv(const double *v, int j, int lane) { return MAT ? v[IX(j)] : v[j]; }
+// a kernel body with and without per-problem matrices: NAME the shared route's kernel, k_lsm_NAME the other
+#define LS_KERNEL_PAIR(NAME) \
+  __global__ __launch_bounds__(256) void k_ls_##NAME(LsK k) { ls_##NAME<false>(k); } \
+  __global__ __launch_bounds__(256) void k_lsm_##NAME(LsK k) { ls_##NAME<true>(k); }
 
 // Minv = 1 / diag(K_b) = 1 / (B_jj + sum_i rho_i,b A_ij^2), for the problems whose rho has just been set (one pass over the A' part of B, squared entries)
 struct FMinv {
@@ -138,11 +149,12 @@ struct FMinv {
   __device__ __forceinline__ void fma(int c, double v, const double (&g)[1], double (&a)[2]) const { if (c >= n) a[0] += g[0] * v * v; else if (c == cur) a[1] = v; }
   __device__ __forceinline__ void row(int j, const double (&a)[2]) const { if (flag[lane]) Minv[IX(j)] = precond ? 1.0 / (a[1] + a[0]) : 1.0; }
 };
-__global__ __launch_bounds__(256) void k_ls_minv(LsK k) {
+template <bool MAT> __device__ __forceinline__ void ls_minv(const LsK &k) {
   if (!k.w.word[WD_RHOANY]) return;
   FMinv f{k.w.rho, k.w.Minv, k.w.iw + IW_RHOCH * W, k.P.n, k.P.precond, ls_lane(), 0};
-  ls_rows<1, 2>(k.P.B, f);
+  ls_rows<1, 2, MAT>(k.P.B, f);
 }
+LS_KERNEL_PAIR(minv)
 
 // rhs = sigma x - q + A'(rho z - y);  r = rhs - K x~ with K x~ = B [x~; rho z~];  p = Minv r   (k_batch_admm: "rhs = ...", _osqp.py:649-650)
 struct FRhs {
@@ -161,14 +173,15 @@ struct FRhs {
     rz += rr * zz; rn = nanmax(rn, fabs(rr)); bn = nanmax(bn, fabs(rhs));
   }
 };
-__global__ __launch_bounds__(256) void k_ls_rhs(LsK k) {
+template <bool MAT> __device__ __forceinline__ void ls_rhs(const LsK &k) {
   __shared__ double lds[3 * 256];
   const int lane = ls_lane();
   FRhs f{k.w, k.P.sigma, k.P.n, lane, !k.w.iw[IW_DONE * W + lane]};
-  ls_rows<2, 2>(k.P.B, f);
+  ls_rows<2, 2, MAT>(k.P.B, f);
   const double vm[2] = {f.bn, f.rn}, vs[1] = {f.rz};
   ls_put<2, 1>(k.w.part, PS_BN, vm, vs, lds);
 }
+LS_KERNEL_PAIR(rhs)
 
 // Kp = B [p; t],  <p, Kp>
 struct FKp {
@@ -179,18 +192,19 @@ struct FKp {
   __device__ __forceinline__ void fma(int, double v, const double (&g)[1], double (&a)[1]) const { a[0] += v * g[0]; }
   __device__ __forceinline__ void row(int j, const double (&a)[1]) { if (on) w.Kp[IX(j)] = a[0]; pkp += a[0] * w.p[IX(j)]; }
 };
-__global__ __launch_bounds__(256) void k_ls_kp(LsK k) {
+template <bool MAT> __device__ __forceinline__ void ls_kp(const LsK &k) {
   __shared__ double lds[256];
   if (!k.w.word[WD_CGANY]) return;
   const int lane = ls_lane();
   FKp f{k.w, k.P.n, lane, k.w.iw[IW_CGON * W + lane]};
-  ls_rows<1, 1>(k.P.B, f);
+  ls_rows<1, 1, MAT>(k.P.B, f);
   const double vs[1] = {f.pkp};
   ls_put<0, 1>(k.w.part, PS_PKP, vs, vs, lds);
 }
+LS_KERNEL_PAIR(kp)
 
 // the n side of k_batch_admm's residuals(), with the second stage of both infeasibility tests (A' dy, P dx) from the same pass
-struct FResN {
+template <bool MAT> struct FResN {
   const LsWs &w; const double *D, *Dinv; double sigma; int n, lane;
   ResRowsB rb = {};                                                           // (step_rules.h: named fields)
   double atdy_u = 0, atdy_s = 0, pdx_u = 0, pdx_s = 0;                        // second stages
@@ -203,20 +217,21 @@ struct FResN {
     a[0] += pn ? p0 : 0.0; a[2] += pn ? p1 : 0.0; a[1] += pn ? 0.0 : p0; a[3] += pn ? 0.0 : p1;
   }
   __device__ __forceinline__ void row(int j, const double (&a)[4]) {
-    const double dxj = w.dx[IX(j)], di = Dinv[j];
-    res_row_b(rb, a[0], a[1], sigma, w.x[IX(j)], w.q[IX(j)], dxj, D[j], di);
+    const double dxj = w.dx[IX(j)], di = ls_sv<MAT>(Dinv, j, lane);
+    res_row_b(rb, a[0], a[1], sigma, w.x[IX(j)], w.q[IX(j)], dxj, ls_sv<MAT>(D, j, lane), di);
     const double pdx = a[2] - sigma * dxj, atdy = a[3];
     atdy_u = nanmax(atdy_u, fabs(di * atdy)); atdy_s = nanmax(atdy_s, fabs(atdy)); pdx_u = nanmax(pdx_u, fabs(di * pdx)); pdx_s = nanmax(pdx_s, fabs(pdx));
   }
 };
-__global__ __launch_bounds__(256) void k_ls_resn(LsK k) {
+template <bool MAT> __device__ __forceinline__ void ls_resn(const LsK &k) {
   __shared__ double lds[17 * 256];
-  FResN f{k.w, k.P.D, k.P.Dinv, k.P.sigma, k.P.n, ls_lane()};
-  ls_rows<2, 4>(k.P.B, f);
+  FResN<MAT> f{k.w, k.P.D, k.P.Dinv, k.P.sigma, k.P.n, ls_lane()};
+  ls_rows<2, 4, MAT>(k.P.B, f);
   const ResRowsB &b = f.rb;                                                   // (the slot order of PS_N0)
   const double vm[14] = {b.dua_u, b.px_u, b.aty_u, b.dua_s, b.px_s, b.aty_s, b.dxn_u, b.dxn_s, b.qn_s, b.qn_u, f.atdy_u, f.atdy_s, f.pdx_u, f.pdx_s}, vs[3] = {b.xpx, b.qx, b.qdx};
   ls_put<14, 3>(k.w.part, PS_N0, vm, vs, lds);
 }
+LS_KERNEL_PAIR(resn)
 
 // z = z~ = A x at the start;  t = rho z - y,  t2 = rho z~  (what the next k_ls_rhs gathers)
 struct FInitZ {
@@ -229,10 +244,11 @@ struct FInitZ {
     w.z[IX(i)] = a[0]; w.zt[IX(i)] = a[0]; w.t[IX(i)] = rh * a[0] - w.y[IX(i)]; w.t2[IX(i)] = rh * a[0];
   }
 };
-__global__ __launch_bounds__(256) void k_ls_initz(LsK k) {
+template <bool MAT> __device__ __forceinline__ void ls_initz(const LsK &k) {
   FInitZ f{k.w, ls_lane()};
-  ls_rows<1, 1>(k.P.A, f);
+  ls_rows<1, 1, MAT>(k.P.A, f);
 }
+LS_KERNEL_PAIR(initz)
 
 // t = rho .* (A p)
 struct FT {
@@ -242,12 +258,13 @@ struct FT {
   __device__ __forceinline__ void fma(int, double v, const double (&g)[1], double (&a)[1]) const { a[0] += v * g[0]; }
   __device__ __forceinline__ void row(int i, const double (&a)[1]) const { if (on) w.t[IX(i)] = w.rho[IX(i)] * a[0]; }
 };
-__global__ __launch_bounds__(256) void k_ls_t(LsK k) {
+template <bool MAT> __device__ __forceinline__ void ls_t(const LsK &k) {
   if (!k.w.word[WD_CGANY]) return;
   const int lane = ls_lane();
   FT f{k.w, lane, k.w.iw[IW_CGON * W + lane]};
-  ls_rows<1, 1>(k.P.A, f);
+  ls_rows<1, 1, MAT>(k.P.A, f);
 }
+LS_KERNEL_PAIR(t)
 
 // z~ = A x~;  z, y update (_osqp.py:660-703);  and, elementwise,  x = alpha x~ + (1 - alpha) x,  dx
 struct FUpd {
@@ -263,9 +280,9 @@ struct FUpd {
     w.t[IX(i)] = rh * s.z - s.y; w.t2[IX(i)] = rh * a;
   }
 };
-__global__ __launch_bounds__(256) void k_ls_upd(LsK k) {
+template <bool MAT> __device__ __forceinline__ void ls_upd(const LsK &k) {
   const int lane = ls_lane(), live = !k.w.iw[IW_DONE * W + lane];
-  if (k.P.m > 0) { FUpd f{k.w, k.P.alpha, lane, live}; ls_rows<1, 1>(k.P.A, f); }
+  if (k.P.m > 0) { FUpd f{k.w, k.P.alpha, lane, live}; ls_rows<1, 1, MAT>(k.P.A, f); }
   if (!live) return;
   const size_t tot = (size_t)k.P.n * 64;
   for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < tot; e += (size_t)gridDim.x * 256) {
@@ -273,10 +290,11 @@ __global__ __launch_bounds__(256) void k_ls_upd(LsK k) {
     k.w.dx[e] = c.dx; k.w.x[e] = c.x;
   }
 }
+LS_KERNEL_PAIR(upd)
 
 // the m side of residuals(), with A dx of the dual infeasibility test (largest value over the rows with a finite upper bound, largest negated value over
 // those with a finite lower one: "no row violates" is two comparisons of these with the threshold, which only the fold knows)
-struct FResM {
+template <bool MAT> struct FResM {
   const LsWs &w; const double *E, *Einv; int lane, unsc;
   ResRowsA ra = {};                                                           // (step_rules.h: named fields)
   double adx_hi = -INFINITY, adx_lo = -INFINITY;                              // second stage
@@ -284,21 +302,22 @@ struct FResM {
   __device__ __forceinline__ void load(int c, double (&g)[2]) const { g[0] = w.x[IX(c)]; g[1] = w.dx[IX(c)]; }
   __device__ __forceinline__ void fma(int, double v, const double (&g)[2], double (&a)[2]) const { a[0] += v * g[0]; a[1] += v * g[1]; }
   __device__ __forceinline__ void row(int i, const double (&a)[2]) {
-    const double ei = Einv[i], li = w.l[IX(i)], ui = w.u[IX(i)];
-    res_row_a(ra, a[0], w.z[IX(i)], w.dy[IX(i)], li, ui, E[i], ei);
+    const double ei = ls_sv<MAT>(Einv, i, lane), li = w.l[IX(i)], ui = w.u[IX(i)];
+    res_row_a(ra, a[0], w.z[IX(i)], w.dy[IX(i)], li, ui, ls_sv<MAT>(E, i, lane), ei);
     const double adx = unsc ? ei * a[1] : a[1];
     if (upper_is_finite(ui)) adx_hi = nanmax(adx_hi, adx);
     if (lower_is_finite(li)) adx_lo = nanmax(adx_lo, -adx);
   }
 };
-__global__ __launch_bounds__(256) void k_ls_resm(LsK k) {
+template <bool MAT> __device__ __forceinline__ void ls_resm(const LsK &k) {
   __shared__ double lds[11 * 256];
-  FResM f{k.w, k.P.E, k.P.Einv, ls_lane(), k.P.unscaled};
-  ls_rows<2, 2>(k.P.A, f);
+  FResM<MAT> f{k.w, k.P.E, k.P.Einv, ls_lane(), k.P.unscaled};
+  ls_rows<2, 2, MAT>(k.P.A, f);
   const ResRowsA &a = f.ra;                                                   // (the slot order of PS_M0)
   const double vm[10] = {a.pri_u, a.ax_u, a.z_u, a.pri_s, a.ax_s, a.z_s, a.dy_u, a.dy_s, f.adx_hi, f.adx_lo}, vs[1] = {a.pinf_lhs};
   ls_put<10, 1>(k.w.part, PS_M0, vm, vs, lds);
 }
+LS_KERNEL_PAIR(resm)
 
 // ---------------------------------------------------------------------------------------------------------------- elementwise kernels
 // rho by constraint class and the problem's rho_bar (_osqp.py:520-522), for the problems whose rho has just been set; t, t2 follow
@@ -390,7 +409,7 @@ __global__ __launch_bounds__(256) void k_ls_cgbeta(LsK k) {
 
 // Every check_termination / adaptive_rho_interval iterations: the batch family's decisions (term_rules.h: batch_check, batch_rho_rule -- single_rho_rule on the direct route --, batch_tol_rule), per problem.
 // mode 0: a boundary of the loop;  1: the residuals of the start (sets the first inner tolerance);  2: the time limit has passed.
-__global__ __launch_bounds__(256) void k_ls_decide(LsK k, int iter, int at_check, int at_rho, int mode) {
+template <bool MAT> __device__ __forceinline__ void ls_decide(const LsK &k, int iter, int at_check, int at_rho, int mode) {
   __shared__ double lds[256];
   const LockstepParams &P = k.P;
   const int lane = ls_lane(), G = k.w.G;
@@ -414,7 +433,7 @@ __global__ __launch_bounds__(256) void k_ls_decide(LsK k, int iter, int at_check
     auto put_tol = [&]() { sc[SC_EPSPREV * W + lane] = eps_prev; sc[SC_EPSCG * W + lane] = eps_cg; iw[IW_RELRULE * W + lane] = rel_rule; };
     if (mode == 1) { batch_tol_init(P.cg_frac, R.dua_s, &eps_prev, &eps_cg, &rel_rule); put_tol(); }
     else {
-      const TermSet tset = {P.eps_abs, P.eps_rel, P.eps_pinf, P.eps_dinf, P.c, P.cinv, P.m, P.unscaled, P.scaling};
+      const TermSet tset = {P.eps_abs, P.eps_rel, P.eps_pinf, P.eps_dinf, MAT ? sc[SC_C * W + lane] : P.c, MAT ? sc[SC_CINV * W + lane] : P.cinv, P.m, P.unscaled, P.scaling};
       const double rho_bar = sc[SC_RHOBAR * W + lane];
       double obj, prim_res, dual_res, rho_new;
       term_info(tset, R, &obj, &prim_res, &dual_res);
@@ -446,6 +465,8 @@ __global__ __launch_bounds__(256) void k_ls_decide(LsK k, int iter, int at_check
   for (int o = 32; o > 0; o >>= 1) pcg += __shfl_xor(pcg, o);
   if (threadIdx.x == 0) { k.w.word[WD_LIVE] = __popcll(live); k.w.word[WD_RHOANY] = chg != 0ull; k.w.word[WD_PCGSUM] = pcg; }
 }
+__global__ __launch_bounds__(256) void k_ls_decide(LsK k, int iter, int at_check, int at_rho, int mode) { ls_decide<false>(k, iter, at_check, at_rho, mode); }
+__global__ __launch_bounds__(256) void k_lsm_decide(LsK k, int iter, int at_check, int at_rho, int mode) { ls_decide<true>(k, iter, at_check, at_rho, mode); }
 
 // ---------------------------------------------------------------------------------------------------------------- transposes
 // tile[b][jl] <- src[b][perm(j0 + jl)] for the chunk's problems (coalesced along j without a permutation), zero elsewhere
@@ -466,7 +487,7 @@ __device__ __forceinline__ void ls_tile_out(double *dst, int width, int j0, int 
 }
 
 // q <- c D q,  x <- Dinv x (warm) or 0,  x~ = x,  dx = 0   (k_batch_admm "load the problem")
-__global__ __launch_bounds__(256) void k_ls_load_n(LsK k) {
+template <bool MAT> __device__ __forceinline__ void ls_load_n(const LsK &k) {
   __shared__ double tile[64][65];
   const LockstepParams &P = k.P;
   const int lane = ls_lane(), wv = ls_wave(), j0 = blockIdx.x * 64;
@@ -475,18 +496,19 @@ __global__ __launch_bounds__(256) void k_ls_load_n(LsK k) {
   for (int jl = wv; jl < 64 && j0 + jl < P.n; jl += 4) {
     const int j = j0 + jl;
     const double qv = P.q ? tile[lane][jl] : P.q0[j];
-    k.w.q[IX(j)] = mine ? in_q(P.c, P.D[j], qv) : 0.0;
+    k.w.q[IX(j)] = mine ? in_q(MAT ? k.w.sc[SC_C * W + lane] : P.c, ls_sv<MAT>(P.D, j, lane), qv) : 0.0;
   }
   __syncthreads();
   if (P.warm) ls_tile_in(P.x, P.n, j0, P.count, P.pc, tile);
   for (int jl = wv; jl < 64 && j0 + jl < P.n; jl += 4) {
     const int j = j0 + jl;
-    const double xv = (P.warm && mine) ? in_x(tile[lane][jl], P.Dinv[j]) : 0.0;
+    const double xv = (P.warm && mine) ? in_x(tile[lane][jl], ls_sv<MAT>(P.Dinv, j, lane)) : 0.0;
     k.w.x[IX(j)] = xv; k.w.xs[IX(j)] = xv; k.w.dx[IX(j)] = 0.0;
   }
 }
+LS_KERNEL_PAIR(load_n)
 // l, u <- E clamp(l, u),  y <- c Einv y (warm) or 0,  dy = 0;  the problem's number of inequality rows (decides its equality weight)
-__global__ __launch_bounds__(256) void k_ls_load_m(LsK k) {
+template <bool MAT> __device__ __forceinline__ void ls_load_m(const LsK &k) {
   __shared__ double tile[64][65];
   __shared__ double red[256];
   const LockstepParams &P = k.P;
@@ -503,7 +525,7 @@ __global__ __launch_bounds__(256) void k_ls_load_m(LsK k) {
     const int il = wv + 4 * s, i = i0 + il;
     if (i < P.m) {
       const double uv = P.u ? tile[lane][il] : P.u0[i];
-      const double li = mine ? in_l(P.E[i], lo[s]) : -OSQP_INFTY, ui = mine ? in_u(P.E[i], uv) : OSQP_INFTY;
+      const double li = mine ? in_l(ls_sv<MAT>(P.E, i, lane), lo[s]) : -OSQP_INFTY, ui = mine ? in_u(ls_sv<MAT>(P.E, i, lane), uv) : OSQP_INFTY;
       k.w.l[IX(i)] = li; k.w.u[IX(i)] = ui; k.w.dy[IX(i)] = 0.0;
       cnt += row_class(li, ui, P.rho_is_vec) == 0 ? 1.0 : 0.0;
     }
@@ -512,12 +534,13 @@ __global__ __launch_bounds__(256) void k_ls_load_m(LsK k) {
   if (P.warm) ls_tile_in(P.y, P.m, i0, P.count, P.pr, tile);
   for (int il = wv; il < 64 && i0 + il < P.m; il += 4) {
     const int i = i0 + il;
-    k.w.y[IX(i)] = (P.warm && mine) ? in_y(tile[lane][il], P.Einv[i], P.c) : 0.0;
+    k.w.y[IX(i)] = (P.warm && mine) ? in_y(tile[lane][il], ls_sv<MAT>(P.Einv, i, lane), MAT ? k.w.sc[SC_C * W + lane] : P.c) : 0.0;
   }
   red[wv * 64 + lane] = cnt;
   __syncthreads();
   if (wv == 0) k.w.parti[(size_t)blockIdx.x * 64 + lane] = ((red[lane] + red[64 + lane]) + red[128 + lane]) + red[192 + lane];
 }
+LS_KERNEL_PAIR(load_m)
 // the chunk's per-problem state: rho_bar, the equality weight (engine.cpp classify_constraints), counters; lanes >= count are terminated
 __global__ __launch_bounds__(256) void k_ls_init(LsK k, int tiles_m) {
   __shared__ double lds[256];
@@ -533,27 +556,29 @@ __global__ __launch_bounds__(256) void k_ls_init(LsK k, int tiles_m) {
 }
 
 // x = D x, y = cinv E y (_osqp.py:1110-1112); certificates in place of x / y for infeasible problems; the records
-__global__ __launch_bounds__(256) void k_ls_store_n(LsK k) {
+template <bool MAT> __device__ __forceinline__ void ls_store_n(const LsK &k) {
   __shared__ double tile[64][65];
   const LockstepParams &P = k.P;
   const int lane = ls_lane(), wv = ls_wave(), j0 = blockIdx.x * 64, status = k.w.iw[IW_STATUS * W + lane];
   for (int jl = wv; jl < 64 && j0 + jl < P.n; jl += 4) {
     const int j = j0 + jl;
-    tile[lane][jl] = batch_out_x(status, P.unscaled, P.scaling, P.D[j], k.w.x[IX(j)], k.w.dx[IX(j)]);
+    tile[lane][jl] = batch_out_x(status, P.unscaled, P.scaling, ls_sv<MAT>(P.D, j, lane), k.w.x[IX(j)], k.w.dx[IX(j)]);
   }
   ls_tile_out(P.x, P.n, j0, P.count, P.pc, tile);
   if (blockIdx.x == 0) for (int e = threadIdx.x; e < P.count * kBatchRec; e += 256) P.rec[e] = k.w.rec[e];
 }
-__global__ __launch_bounds__(256) void k_ls_store_m(LsK k) {
+LS_KERNEL_PAIR(store_n)
+template <bool MAT> __device__ __forceinline__ void ls_store_m(const LsK &k) {
   __shared__ double tile[64][65];
   const LockstepParams &P = k.P;
   const int lane = ls_lane(), wv = ls_wave(), i0 = blockIdx.x * 64, status = k.w.iw[IW_STATUS * W + lane];
   for (int il = wv; il < 64 && i0 + il < P.m; il += 4) {
     const int i = i0 + il;
-    tile[lane][il] = batch_out_y(status, P.unscaled, P.scaling, P.cinv, P.E[i], k.w.y[IX(i)], k.w.dy[IX(i)]);
+    tile[lane][il] = batch_out_y(status, P.unscaled, P.scaling, MAT ? k.w.sc[SC_CINV * W + lane] : P.cinv, ls_sv<MAT>(P.E, i, lane), k.w.y[IX(i)], k.w.dy[IX(i)]);
   }
   ls_tile_out(P.y, P.m, i0, P.count, P.pr, tile);
 }
+LS_KERNEL_PAIR(store_m)
 // ---------------------------------------------------------------------------------------------------------------- adjoint derivatives of a chunk
 // The backward pass (include/osqp_hip.h osqp_hip_batch_adjoint_lockstep): per problem the adjoint system  [P, A_a'; A_a, 0] [r_x; r_a] = -[dx; dy_a]  is the
 // KKT system of  min 1/2 r'Pr + dx'r  s.t.  A_a r = -dy_a  and is solved by the recurrence of Engine::run_recurrence -- THIS route's ADMM iteration
@@ -1088,6 +1113,155 @@ __global__ __launch_bounds__(256) void k_lwa_zero(LwK k) {
   const size_t tot = (size_t)(k.P.n + k.d.r) * 64;
   for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < tot; e += (size_t)gridDim.x * 256) { k.w.x[e] = 0.0; k.w.xs[e] = 0.0; k.w.dx[e] = 0.0; }
 }
+// ---------------------------------------------------------------------------------------------------------------- matrices of a chunk
+// PER-PROBLEM MATRICES (include/osqp_hip.h osqp_hip_batch_solve_lockstep_mat; LockstepParams::mat_ws): every problem of the chunk has its own values of P
+// and A on the handle's sparsity pattern.  The matrix block keeps them problem-minor like every block vector -- entry k of problem b at k * 64 + b -- next to the
+// problem's own D, Dinv (n x 64), E, Einv (m x 64); c, 1 / c are rows SC_C / SC_CINV of the scalar state.  In front of the transposes in:
+//   assembly       the chunk's rows of Px / Ax go through 64 x 64 LDS tiles (coalesced along the entries on the way in, along the problems on the way out)
+//                  to the engine's positions (Dev::AmA / AmB / Pm1 / Pm2; a reordered handle's value maps first).  B's diagonal is zeroed before (k_lsm_begin)
+//                  and receives sigma after the equilibration; one writer per (entry, lane): a handle with a repeated (j, j) entry is declined by the engine.
+//                  Lanes >= count receive the handle's raw values (and its q): nothing non-finite is manufactured in a dead lane.
+//   equilibration  the Ruiz iteration of the single-QP setup (backend_hip.hip ruiz(): _osqp.py:389-497) per lane, with the operand orders of k_ruiz_scale_A /
+//                  k_ruiz_scale_B / k_ruiz_cost: dt, et from the row maxima of B, A (k_lsm_norms); A <- et A dt, E *= et, B <- dt [P | A'] [dt | et], q *= dt,
+//                  D *= dt and, from the same pass, the column norms of the scaled P and max |q| through ls_put (k_lsm_scale); ct, c *= ct from ls_fold
+//                  (k_lsm_cost); P *= ct, q *= ct (k_lsm_cost_apply).  Then Dinv, Einv, 1 / c and sigma on B's diagonal (k_lsm_finish).  Four launches per
+//                  iteration.  The scratch lives in block vectors that are dead before k_ls_load_*: dt in r, et in t, the problem's q in q.
+// The strips of rows are ls_rows' (from the row counts and the grid alone), so c's sum has a fixed order that depends on (n, m) only.
+struct LsMat {
+  double *Aval, *Bval, *D, *Dinv, *E, *Einv;
+  const double *Praw, *Araw;
+  const int *Pm1, *Pm2, *AmA, *AmB, *Bdiag;
+  int nzP, nzA;
+};
+struct LsMK { LockstepParams P; LsWs w; LsMat t; };
+__device__ __forceinline__ double ls_limit_scaling(double v) { return v < 1e-4 ? 1.0 : (v > 1e4 ? 1e4 : v); }     // _osqp.py:363-387
+// this wave's strip of `nrows` rows (ls_rows' partition)
+__device__ __forceinline__ void ls_strip(int nrows, int &r0, int &r1) {
+  const int nw = gridDim.x * 4, rpw = (nrows + nw - 1) / nw;
+  r0 = ((int)blockIdx.x * 4 + ls_wave()) * rpw; r1 = min(r0 + rpw, nrows);
+}
+// the problem's raw q (the handle's for lanes >= count) in the engine's numbering, D = E = c = 1, B's diagonal zero.  Grid: the tiles of n.
+__global__ __launch_bounds__(256) void k_lsm_begin(LsMK k) {
+  __shared__ double tile[64][65];
+  const LockstepParams &P = k.P;
+  const int lane = ls_lane(), wv = ls_wave(), j0 = blockIdx.x * 64;
+  const bool mine = lane < P.count;
+  if (P.q) ls_tile_in(P.q, P.n, j0, P.count, P.pc, tile);
+  for (int jl = wv; jl < 64 && j0 + jl < P.n; jl += 4) {
+    const int j = j0 + jl;
+    k.w.q[IX(j)] = (P.q && mine) ? tile[lane][jl] : P.q0[j];
+    k.t.D[IX(j)] = 1.0; k.t.Bval[IX(k.t.Bdiag[j])] = 0.0;
+  }
+  const size_t mt = (size_t)P.m * 64;
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < mt; e += (size_t)gridDim.x * 256) k.t.E[e] = 1.0;
+  if (blockIdx.x == 0 && threadIdx.x < 64) k.w.sc[SC_C * W + lane] = 1.0;
+}
+// 64 of the caller's entries per workgroup, 16 per wave: the tile comes in coalesced along the entries; an entry's engine positions are wave-uniform and its
+// 64 values leave as one line each.  SYM: P's upper triangle (both mirrored positions of B), else A (A and its copy in B).
+template <bool SYM>
+__global__ __launch_bounds__(256) void k_lsm_asm(LsMK k) {
+  __shared__ double tile[64][65];
+  const LockstepParams &P = k.P;
+  const int nz = SYM ? k.t.nzP : k.t.nzA, lane = ls_lane(), wv = ls_wave(), e0 = blockIdx.x * 64;
+  const double *src = SYM ? P.Px : P.Ax, *raw = SYM ? k.t.Praw : k.t.Araw;
+  const int *__restrict__ map = SYM ? P.pvmap : P.avmap;
+  const bool own = src != nullptr && lane < P.count;
+  if (src) ls_tile_in(src, nz, e0, P.count, nullptr, tile);
+  for (int el = wv * 16; el < wv * 16 + 16 && e0 + el < nz; el++) {
+    const int e = e0 + el, pos = __builtin_amdgcn_readfirstlane(map ? map[e] : e);
+    const double v = own ? tile[lane][el] : raw[pos];
+    if (SYM) {
+      const int p1 = __builtin_amdgcn_readfirstlane(k.t.Pm1[pos]), p2 = __builtin_amdgcn_readfirstlane(k.t.Pm2[pos]);
+      k.t.Bval[IX(p1)] = v;
+      if (p2 >= 0 && p2 != p1) k.t.Bval[IX(p2)] = v;
+    } else {
+      k.t.Aval[IX(__builtin_amdgcn_readfirstlane(k.t.AmA[pos]))] = v; k.t.Bval[IX(__builtin_amdgcn_readfirstlane(k.t.AmB[pos]))] = v;
+    }
+  }
+}
+// dt_j = 1 / sqrt(limit(max |row j of B|)) (KKT column j = row j of [P | A']),  et_i = 1 / sqrt(limit(max |row i of A|))
+__global__ __launch_bounds__(256) void k_lsm_norms(LsMK k) {
+  const int lane = ls_lane();
+  int r0, r1;
+  ls_strip(k.P.n, r0, r1);
+  for (int j = r0; j < r1; j++) {
+    const int k0 = __builtin_amdgcn_readfirstlane(k.P.B.rowptr[j]), k1 = __builtin_amdgcn_readfirstlane(k.P.B.rowptr[j + 1]);
+    double mx = 0.0;
+#pragma unroll 4
+    for (int e = k0; e < k1; e++) mx = fmax(mx, fabs(k.t.Bval[IX(e)]));
+    k.w.r[IX(j)] = 1.0 / sqrt(ls_limit_scaling(mx));
+  }
+  ls_strip(k.P.m, r0, r1);
+  for (int i = r0; i < r1; i++) {
+    const int k0 = __builtin_amdgcn_readfirstlane(k.P.A.rowptr[i]), k1 = __builtin_amdgcn_readfirstlane(k.P.A.rowptr[i + 1]);
+    double mx = 0.0;
+#pragma unroll 4
+    for (int e = k0; e < k1; e++) mx = fmax(mx, fabs(k.t.Aval[IX(e)]));
+    k.w.t[IX(i)] = 1.0 / sqrt(ls_limit_scaling(mx));
+  }
+}
+// A <- diag(et) A diag(dt), E *= et;  B <- [diag(dt) P diag(dt) | diag(dt) A' diag(et)], q *= dt, D *= dt;  per problem the sum of the scaled P's column
+// norms and max |q| to the partials (slots PS_BN: max |q|, PS_BN + 1: the sum)
+__global__ __launch_bounds__(256) void k_lsm_scale(LsMK k) {
+  __shared__ double lds[2 * 256];
+  const int lane = ls_lane(), n = k.P.n;
+  const double *dt = k.w.r, *et = k.w.t;
+  int r0, r1;
+  ls_strip(k.P.m, r0, r1);
+  for (int i = r0; i < r1; i++) {
+    const int k0 = __builtin_amdgcn_readfirstlane(k.P.A.rowptr[i]), k1 = __builtin_amdgcn_readfirstlane(k.P.A.rowptr[i + 1]);
+    const double ei = et[IX(i)];
+    for (int e = k0; e < k1; e++) { const int c = __builtin_amdgcn_readfirstlane(k.P.A.col[e]); k.t.Aval[IX(e)] *= ei * dt[IX(c)]; }
+    k.t.E[IX(i)] *= ei;
+  }
+  double sum = 0.0, nq = 0.0;
+  ls_strip(n, r0, r1);
+  for (int j = r0; j < r1; j++) {
+    const int k0 = __builtin_amdgcn_readfirstlane(k.P.B.rowptr[j]), k1 = __builtin_amdgcn_readfirstlane(k.P.B.rowptr[j + 1]);
+    const double dj = dt[IX(j)];
+    double mx = 0.0;
+    for (int e = k0; e < k1; e++) {
+      const int c = __builtin_amdgcn_readfirstlane(k.P.B.col[e]);
+      const double v = k.t.Bval[IX(e)] * (c < n ? dt[IX(c)] * dj : et[IX(c - n)] * dj);      // (same factor, same order of operands, as the entry's copy in A)
+      k.t.Bval[IX(e)] = v;
+      if (c < n) mx = fmax(mx, fabs(v));
+    }
+    const double qj = k.w.q[IX(j)] * dj;
+    k.w.q[IX(j)] = qj; k.t.D[IX(j)] *= dj;
+    sum += mx; nq = fmax(nq, fabs(qj));
+  }
+  const double vm[1] = {nq}, vs[1] = {sum};
+  ls_put<1, 1>(k.w.part, PS_BN, vm, vs, lds);
+}
+// cost normalisation per problem: ct = 1 / limit(max(limit(||q||_inf), mean_j ||P_:j||_inf)),  c *= ct   (_osqp.py:443-448).  One workgroup.
+__global__ __launch_bounds__(256) void k_lsm_cost(LsMK k) {
+  __shared__ double lds[256];
+  const int lane = ls_lane(), G = k.w.G;
+  const double nq = ls_fold<true>(k.w.part, G, PS_BN, lds), sum = ls_fold<false>(k.w.part, G, PS_BN + 1, lds);
+  if (threadIdx.x >= 64) return;
+  const double mean = sum / (double)(k.P.n > 0 ? k.P.n : 1);
+  const double ct = 1.0 / ls_limit_scaling(fmax(ls_limit_scaling(nq), mean));
+  k.w.sc[SC_CT * W + lane] = ct; k.w.sc[SC_C * W + lane] *= ct;
+}
+// P <- ct P (the P part comes first in a row of B = [P | A']),  q <- ct q
+__global__ __launch_bounds__(256) void k_lsm_cost_apply(LsMK k) {
+  const int lane = ls_lane(), n = k.P.n;
+  const double ct = k.w.sc[SC_CT * W + lane];
+  int r0, r1;
+  ls_strip(n, r0, r1);
+  for (int j = r0; j < r1; j++) {
+    const int k0 = __builtin_amdgcn_readfirstlane(k.P.B.rowptr[j]), k1 = __builtin_amdgcn_readfirstlane(k.P.B.rowptr[j + 1]);
+    for (int e = k0; e < k1 && __builtin_amdgcn_readfirstlane(k.P.B.col[e]) < n; e++) k.t.Bval[IX(e)] *= ct;
+    k.w.q[IX(j)] *= ct;
+  }
+}
+// Dinv, Einv, 1 / c;  sigma on B's diagonal
+__global__ __launch_bounds__(256) void k_lsm_finish(LsMK k) {
+  const int lane = ls_lane();
+  for (int j = (int)blockIdx.x * 4 + ls_wave(); j < k.P.n; j += (int)gridDim.x * 4) { k.t.Dinv[IX(j)] = 1.0 / k.t.D[IX(j)]; k.t.Bval[IX(k.t.Bdiag[j])] += k.P.sigma; }
+  for (int i = (int)blockIdx.x * 4 + ls_wave(); i < k.P.m; i += (int)gridDim.x * 4) k.t.Einv[IX(i)] = 1.0 / k.t.E[IX(i)];
+  if (blockIdx.x == 0 && threadIdx.x < 64) k.w.sc[SC_CINV * W + lane] = 1.0 / k.w.sc[SC_C * W + lane];
+}
 #undef IX
 
 }  // namespace
@@ -1108,50 +1282,76 @@ int lockstep_chunk(Dev &d, const LockstepParams &p, void *stream, double *stat) 
   w.part = take((size_t)kLsSlots * G * W); w.parti = take((size_t)(tm > 0 ? tm : 1) * W); w.sc = take((size_t)kLsScal * W); w.rec = take((size_t)W * kBatchRec);
   w.iw = reinterpret_cast<int *>(take((size_t)kLsInt * W / 2)); w.word = w.iw + IW_COUNT * W;
   w.G = G;
-  if ((size_t)(c - p.ws) > lockstep_ws_doubles(n, m)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if ((size_t)(c - p.ws) > lockstep_ws_doubles(n, m) || (size_t)(w.sc - p.ws) != lockstep_sc_offset(n, m)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  // per-problem matrices ("matrices of a chunk" above): the chunk's kernels read the matrix block in place of the handle's arrays
+  const bool mat = p.mat_ws != nullptr;
+  LsMat mt{};
+  if (mat) {
+    if (!d.Praw || !d.Araw || p.polish) return OSQP_FUNC_NOT_IMPLEMENTED;
+    const size_t aW = (size_t)p.A.nnz * W, bW = (size_t)p.B.nnz * W;
+    double *cm = p.mat_ws;
+    auto takem = [&cm](size_t cnt) { double *r = cm; cm += cnt; return r; };
+    mt.Aval = takem(aW); mt.Bval = takem(bW); mt.D = takem(nW); mt.Dinv = takem(nW); mt.E = takem(mW); mt.Einv = takem(mW);
+    if ((size_t)(cm - p.mat_ws) > lockstep_mat_ws_doubles(n, m, p.A.nnz, p.B.nnz)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+    mt.Praw = d.Praw; mt.Araw = d.Araw; mt.Pm1 = d.Pm1; mt.Pm2 = d.Pm2; mt.AmA = d.AmA; mt.AmB = d.AmB; mt.Bdiag = d.Bdiag; mt.nzP = d.nzP; mt.nzA = d.nzA;
+    k.P.A.val = mt.Aval; k.P.B.val = mt.Bval; k.P.D = mt.D; k.P.Dinv = mt.Dinv; k.P.E = mt.E; k.P.Einv = mt.Einv;
+  }
   long launches = 0;
   auto go = [&](auto kern, int grid, auto... args) { hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, k, args...); launches++; };
   hipEvent_t e0, e1;
   HIP_CHECK(hipEventCreate(&e0)); HIP_CHECK(hipEventCreate(&e1));
   HIP_CHECK(hipEventRecord(e0, s));
+  hipEvent_t em = nullptr;
+  if (mat) {
+    const LsMK km{k.P, w, mt};
+    auto gm = [&](auto kern, int grid) { hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, km); launches++; };
+    gm(k_lsm_begin, tn);
+    if (mt.nzA > 0) gm(k_lsm_asm<false>, (mt.nzA + 63) / 64);
+    if (mt.nzP > 0) gm(k_lsm_asm<true>, (mt.nzP + 63) / 64);
+    for (int it = 0; it < p.mat_iters; it++) { gm(k_lsm_norms, G); gm(k_lsm_scale, G); gm(k_lsm_cost, 1); gm(k_lsm_cost_apply, G); }
+    gm(k_lsm_finish, G);
+    HIP_CHECK(hipEventCreate(&em));
+    HIP_CHECK(hipEventRecord(em, s));
+    if (p.mat_stat) p.mat_stat[1] = (double)launches;
+  }
   auto now_s = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const double t_begin = now_s();
   int words[WD_COUNT] = {0, p.count, 0, 0, 0, 0, 0};
   auto fetch = [&]() { HIP_CHECK(hipMemcpyAsync(words, w.word, sizeof(words), hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s)); };
-  auto residuals = [&]() { if (m > 0) go(k_ls_resm, G); go(k_ls_resn, G); };
-  auto new_rho = [&]() { if (m > 0) go(k_ls_setrho, G); go(k_ls_minv, G); };
+  auto residuals = [&]() { if (m > 0) go(mat ? k_lsm_resm : k_ls_resm, G); go(mat ? k_lsm_resn : k_ls_resn, G); };
+  auto new_rho = [&]() { if (m > 0) go(k_ls_setrho, G); go(mat ? k_lsm_minv : k_ls_minv, G); };
 
-  go(k_ls_load_n, tn);
-  if (m > 0) go(k_ls_load_m, tm);
+  go(mat ? k_lsm_load_n : k_ls_load_n, tn);
+  if (m > 0) go(mat ? k_lsm_load_m : k_ls_load_m, tm);
   go(k_ls_init, 1, m > 0 ? tm : 0);
   new_rho();
-  if (m > 0) go(k_ls_initz, G);
+  if (m > 0) go(mat ? k_lsm_initz : k_ls_initz, G);
   residuals();
-  go(k_ls_decide, 1, 0, 0, 0, 1);
+  go(mat ? k_lsm_decide : k_ls_decide, 1, 0, 0, 0, 1);
   int iter = 0, cg_est = 4;
   while (words[WD_LIVE] > 0 && iter < p.max_iter) {
     iter++;
-    go(k_ls_rhs, G);
+    go(mat ? k_lsm_rhs : k_ls_rhs, G);
     go(k_ls_cginit, 1);
     // PCG: as many iterations as the previous ADMM iteration needed (+ 1) are enqueued without synchronising; then the host reads the words and
     // goes on in groups of four while some problem's PCG is still running, up to cg_max_iter.  The estimate decides how many launches return at
     // once, never how far a problem's PCG runs.
     for (int it = 0, grp = cg_est; it < p.cg_max; grp = 4) {
       for (const int end = std::min(it + grp, p.cg_max); it < end; it++) {
-        if (m > 0) go(k_ls_t, G);
-        go(k_ls_kp, G); go(k_ls_cgalpha, 1); go(k_ls_cgupd, G); go(k_ls_cgbeta, 1); go(k_ls_cgp, G);
+        if (m > 0) go(mat ? k_lsm_t : k_ls_t, G);
+        go(mat ? k_lsm_kp : k_ls_kp, G); go(k_ls_cgalpha, 1); go(k_ls_cgupd, G); go(k_ls_cgbeta, 1); go(k_ls_cgp, G);
       }
       fetch();
       if (!words[WD_CGANY]) break;
     }
     cg_est = std::max(2, words[WD_CGIT] + 1);
-    go(k_ls_upd, G);
+    go(mat ? k_lsm_upd : k_ls_upd, G);
     const int at_check = (p.check > 0 && iter % p.check == 0) || iter >= p.max_iter;
     const int at_rho = p.rho_interval > 0 && iter % p.rho_interval == 0;
     const bool late = p.time_limit > 0 && std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - t_begin > p.time_limit;
     if (!at_check && !at_rho && !late) continue;
     residuals();
-    go(k_ls_decide, 1, iter, late ? 1 : at_check, at_rho, late ? 2 : 0);
+    go(mat ? k_lsm_decide : k_ls_decide, 1, iter, late ? 1 : at_check, at_rho, late ? 2 : 0);
     if (at_rho && !late) new_rho();
     if (at_check || late) fetch();
   }
@@ -1212,12 +1412,13 @@ int lockstep_chunk(Dev &d, const LockstepParams &p, void *stream, double *stat) 
     HIP_CHECK(hipEventRecord(ep1, s));
     pol_launches = launches - launches0;
   }
-  go(k_ls_store_n, tn);
-  if (m > 0) go(k_ls_store_m, tm);
+  go(mat ? k_lsm_store_n : k_ls_store_n, tn);
+  if (m > 0) go(mat ? k_lsm_store_m : k_ls_store_m, tm);
   HIP_CHECK(hipEventRecord(e1, s));
   fetch();
   float ms = 0.f, pms = 0.f;
   HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+  if (mat) { float mms = 0.f; HIP_CHECK(hipEventElapsedTime(&mms, e0, em)); HIP_CHECK(hipEventDestroy(em)); if (p.mat_stat) p.mat_stat[0] = mms; }
   if (polished) { HIP_CHECK(hipEventElapsedTime(&pms, ep0, ep1)); HIP_CHECK(hipEventDestroy(ep0)); HIP_CHECK(hipEventDestroy(ep1)); }
   HIP_CHECK(hipEventDestroy(e0)); HIP_CHECK(hipEventDestroy(e1));
   HIP_CHECK(hipGetLastError());

@@ -138,6 +138,10 @@ PROTOTYPES = {
     'osqp_hip_batch_solve_lockstep_device': (C.c_int, [SolverP, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     'osqp_hip_lockstep_last_record': (C.c_int, [SolverP, c_double_p]),
     'osqp_hip_lockstep_polish_last_record': (C.c_int, [SolverP, c_double_p]),
+    'osqp_hip_batch_solve_lockstep_mat': (C.c_int, [SolverP, C.c_int] + [c_double_p] * 8 + [C.c_int]),
+    'osqp_hip_batch_solve_lockstep_mat_device': (C.c_int, [SolverP, C.c_int] + [C.c_void_p] * 8 + [C.c_int, C.c_void_p]),
+    'osqp_hip_lockstep_mat_last_record': (C.c_int, [SolverP, c_double_p]),
+    'osqp_hip_lockstep_mat_scaling': (C.c_int, [SolverP, C.c_int, c_double_p, c_double_p, c_double_p]),
     'osqp_hip_batch_solve_lockstep_direct': (C.c_int, [SolverP, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int]),
     'osqp_hip_batch_solve_lockstep_direct_device': (C.c_int, [SolverP, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     'osqp_hip_lockstep_direct_last_record': (C.c_int, [SolverP, c_double_p]),

@@ -388,15 +388,17 @@ class OSQPSolver:
         if st:
             raise self._batch_error(st)
 
-    def hip_batch_solve_lockstep(self, q=None, l=None, u=None, x0=None, y0=None, nbatch=None):
-        """hip_batch_solve for problems of ANY size (osqp_hip_batch_solve_lockstep): shared P / A, 64 problems at a time on block vectors.
-        Same arguments (no Px / Ax), same checks, same returns: x (B, n), y (B, m), rec (B, BATCH_REC).  With the setting polishing every SOLVED
-        problem is polished on the device (rec[:, 8] = 1 kept, -1 rejected; lockstep_polish_last_record)."""
-        return self._lockstep_host(self._lib.osqp_hip_batch_solve_lockstep, q, l, u, x0, y0, nbatch)
+    def hip_batch_solve_lockstep(self, q=None, l=None, u=None, x0=None, y0=None, nbatch=None, Px=None, Ax=None):
+        """hip_batch_solve for problems of ANY size (osqp_hip_batch_solve_lockstep): 64 problems at a time on block vectors.
+        Same arguments, same checks, same returns: x (B, n), y (B, m), rec (B, BATCH_REC).  With the setting polishing every SOLVED
+        problem is polished on the device (rec[:, 8] = 1 kept, -1 rejected; lockstep_polish_last_record).
+        Px (B, nnz(triu P)) / Ax (B, nnz(A)): per-problem matrix values in the CSC order given at setup (osqp_hip_batch_solve_lockstep_mat): every
+        problem is scaled as a solver set up with its data alone; no polish on that entry (lockstep_mat_last_record, lockstep_mat_scaling)."""
+        return self._lockstep_host(self._lib.osqp_hip_batch_solve_lockstep, q, l, u, x0, y0, nbatch, Px, Ax)
 
-    def _lockstep_host(self, entry, q, l, u, x0, y0, nbatch):
+    def _lockstep_host(self, entry, q, l, u, x0, y0, nbatch, Px=None, Ax=None):
         """The host-array call of a lockstep route (`entry`: its C entry point): widths checked here, then the engine."""
-        arrs = [a for a in (q, l, u, x0, y0) if a is not None]
+        arrs = [a for a in (q, l, u, x0, y0, Px, Ax) if a is not None]
         B = int(nbatch) if nbatch is not None else int(np.asarray(arrs[0]).shape[0])
 
         def rows(a, name, width):
@@ -409,18 +411,52 @@ class OSQPSolver:
         x = np.zeros((B, self.n)) if x0 is None else rows(x0, 'x0', self.n).copy()
         y = np.zeros((B, self.m)) if y0 is None else rows(y0, 'y0', self.m).copy()
         rec = np.zeros((B, self.BATCH_REC))
-        st = entry(self._p, B, _ptr(q, _lib.c_double_p), _ptr(l, _lib.c_double_p), _ptr(u, _lib.c_double_p),
-                   _ptr(x, _lib.c_double_p), _ptr(y, _lib.c_double_p), _ptr(rec, _lib.c_double_p), int(warm))
+        if Px is not None or Ax is not None:
+            Px, Ax = (None if a is None else rows(a, name, w) for a, name, w in ((Px, 'Px', self.nnz_P), (Ax, 'Ax', self.nnz_A)))
+            st = self._lib.osqp_hip_batch_solve_lockstep_mat(self._p, B, _ptr(Px, _lib.c_double_p), _ptr(Ax, _lib.c_double_p), _ptr(q, _lib.c_double_p),
+                                                             _ptr(l, _lib.c_double_p), _ptr(u, _lib.c_double_p), _ptr(x, _lib.c_double_p), _ptr(y, _lib.c_double_p),
+                                                             _ptr(rec, _lib.c_double_p), int(warm))
+        else:
+            st = entry(self._p, B, _ptr(q, _lib.c_double_p), _ptr(l, _lib.c_double_p), _ptr(u, _lib.c_double_p),
+                       _ptr(x, _lib.c_double_p), _ptr(y, _lib.c_double_p), _ptr(rec, _lib.c_double_p), int(warm))
         if st:
             raise self._batch_error(st)
         return x, y, rec
 
-    def hip_batch_solve_lockstep_device(self, nbatch, q_ptr, l_ptr, u_ptr, x_ptr, y_ptr, rec_ptr, warm=False, stream=None):
+    def hip_batch_solve_lockstep_device(self, nbatch, q_ptr, l_ptr, u_ptr, x_ptr, y_ptr, rec_ptr, warm=False, stream=None, Px_ptr=None, Ax_ptr=None):
         """osqp_hip_batch_solve_lockstep_device: raw device addresses (int or None) laid out as in hip_batch_solve_lockstep; the work goes on `stream`
-        (None: the solver's) and the call returns when the results are there.  nbatch == 0: does the route apply?"""
-        st = self._lib.osqp_hip_batch_solve_lockstep_device(self._p, int(nbatch), q_ptr, l_ptr, u_ptr, x_ptr, y_ptr, rec_ptr, int(bool(warm)), stream)
+        (None: the solver's) and the call returns when the results are there.  nbatch == 0: does the route apply?
+        Px_ptr / Ax_ptr: per-problem matrix values on the device (osqp_hip_batch_solve_lockstep_mat_device)."""
+        if Px_ptr is not None or Ax_ptr is not None:
+            st = self._lib.osqp_hip_batch_solve_lockstep_mat_device(self._p, int(nbatch), Px_ptr, Ax_ptr, q_ptr, l_ptr, u_ptr, x_ptr, y_ptr, rec_ptr, int(bool(warm)), stream)
+        else:
+            st = self._lib.osqp_hip_batch_solve_lockstep_device(self._p, int(nbatch), q_ptr, l_ptr, u_ptr, x_ptr, y_ptr, rec_ptr, int(bool(warm)), stream)
         if st:
             raise self._batch_error(st)
+
+    # OSQP_HIP_LOCKSTEP_MAT_LAST_REC doubles of osqp_hip_lockstep_mat_last_record
+    LOCKSTEP_MAT_LAST_FIELDS = ('chunks', 'width', 'admm_iters_max', 'pcg_iters', 'kernel_launches', 'gpu_ms', 'matrix_block_bytes', 'prepare_gpu_ms')
+
+    def lockstep_mat_last_record(self):
+        """osqp_hip_lockstep_mat_last_record as a dict (LOCKSTEP_MAT_LAST_FIELDS): what the last lockstep call with per-problem matrices of this handle
+        did; zeros before the first."""
+        rec = np.zeros(len(self.LOCKSTEP_MAT_LAST_FIELDS))
+        st = self._lib.osqp_hip_lockstep_mat_last_record(self._p, _ptr(rec, _lib.c_double_p))
+        if st:
+            raise ValueError(str(int(st)))
+        out = dict(zip(self.LOCKSTEP_MAT_LAST_FIELDS, rec.tolist()))
+        for k in ('chunks', 'width', 'admm_iters_max', 'pcg_iters', 'kernel_launches', 'matrix_block_bytes'):
+            out[k] = int(out[k])
+        return out
+
+    def lockstep_mat_scaling(self, b):
+        """osqp_hip_lockstep_mat_scaling: (D, E, c) of problem b of the last chunk the last lockstep call with per-problem matrices processed, numbered
+        like hip_scaling().  ValueError with code OSQP_DATA_NOT_INITIALIZED before the first call or for b outside that chunk."""
+        D, E, c = np.zeros(self.n), np.zeros(self.m), C.c_double()
+        st = self._lib.osqp_hip_lockstep_mat_scaling(self._p, int(b), _ptr(D, _lib.c_double_p), _ptr(E, _lib.c_double_p), C.byref(c))
+        if st:
+            raise self._batch_error(st)
+        return D, E, c.value
 
     # OSQP_HIP_LOCKSTEP_LAST_REC doubles of osqp_hip_lockstep_last_record
     LOCKSTEP_LAST_FIELDS = ('chunks', 'width', 'admm_iters_max', 'pcg_iters', 'kernel_launches', 'gpu_ms', 'workspace_bytes', 'reserved')

@@ -17,6 +17,9 @@ threads.  Here one persistent engine handle plays that role:
     64 problems at a time on block vectors, any size; host tensors through the host entry, ROCm tensors zero-copy through the device entry), or, with
     ``large_batch='lockstep_direct'``, to its direct form for a Woodbury handle with a diagonal K0 (osqp_hip_batch_solve_lockstep_direct: the
     factor-model portfolio QP, which the lockstep route declines); a handle the chosen route declines raises as ``'lockstep'`` always has.
+    With ``large_batch='lockstep'`` (one rank) a forward with 2-D P_val and / or A_val that the single launch declines makes ONE call of the lockstep
+    route with per-element matrices (osqp_hip_batch_solve_lockstep_mat; ``mat_lockstep_launches`` counts them) in place of the per-element loop; its
+    backward stays the per-element loop.
 
 Like the reference, a batch element that is not solved raises RuntimeError (:158-162).
 
@@ -77,6 +80,7 @@ class OSQP(Module):
         self.adjoint_launches = 0    # launches of the adjoint kernel made by this layer's backward passes (one per backward; one per element where the batch kernel does not hold the problem)
         self.last_adjoint_rec = None # (nb, 4) record of the last backward: status, active rows, residual, reserved (ext_hip ADJOINT_FIELDS)
         self._grad_maps = None
+        self.mat_lockstep_launches = 0   # calls of the lockstep route with per-element matrices made by this layer's forwards (large_batch='lockstep')
 
     # ------------------------------------------------------------------ the persistent handle
     def _matrices(self, P_val, A_val):
@@ -163,6 +167,10 @@ class OSQP(Module):
                     if str(e) != str(int(osqp_amd.SolverError.OSQP_FUNC_NOT_IMPLEMENTED)):
                         raise
                     x = rec = None
+                    if self.large_batch == 'lockstep':                                  # any size, every element on its own matrices: ONE call (osqp_hip_batch_solve_lockstep_mat)
+                        x, y, rec = s._solver.hip_batch_solve_lockstep(q=qn, l=ln, u=un, Px=(Pn[:, self._triu_pick] if batched[0] else None), Ax=(An if batched[2] else None), nbatch=nb)
+                        self.last_dual = y
+                        self.mat_lockstep_launches += 1
             if x is None:
                 x, rec = self._loop(Pn, qn, An, ln, un, nb, batched, dev_index)
         bad = np.nonzero(rec[:, 0] != int(osqp_amd.SolverStatus.OSQP_SOLVED))[0]
