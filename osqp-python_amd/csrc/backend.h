@@ -19,6 +19,7 @@
 #include <cstdint>
 #include <stdexcept>
 
+#include "lockstep_layout.h"     // the lockstep routes' work blocks: kLsW, kBatchRec, the pointer sets, one carve per set, the size functions
 #include "band_ldl.h"            // the padded band of the batch path's direct solve: kBatchNB, kBatchDirectMaxBw, the layout
 
 namespace osqp_hip {
@@ -328,8 +329,7 @@ struct Dev {
   void *impl = nullptr;          // backend private (events, graphs, pinned staging)
 };
 
-// Batched small-QP solve (batch_hip.hip): nbatch problems sharing the solver's scaled A / B, one workgroup each.
-constexpr int kBatchRec = 12;     // doubles per problem in the result record of the batch kernels (OSQP_HIP_BATCH_REC in include/osqp_hip.h)
+// Batched small-QP solve (batch_hip.hip): nbatch problems sharing the solver's scaled A / B, one workgroup each (kBatchRec: lockstep_layout.h).
 // The settings snapshot every batch route runs with (Engine::fill_batch_settings): base of BatchParams and LockstepParams
 struct BatchSettings {
   double c = 1, cinv = 1, sigma = 0, alpha = 0, rho0 = 0, eq_factor = 0, eps_abs = 0, eps_rel = 0, eps_pinf = 0, eps_dinf = 0, cg_frac = 0, rho_tol = 0;
@@ -465,16 +465,7 @@ struct AdjointPcg {
 
 // Lockstep batch route (lockstep_hip.hip; include/osqp_hip.h osqp_hip_batch_solve_lockstep): QPs that share the handle's scaled A / B and differ in
 // q / l / u, at any size, kLsW problems at a time on block vectors (element (j, b) at j * kLsW + b: lanes are problems).
-constexpr int kLsW = 64;          // chunk width: one wave's lanes
-constexpr int kLsSlots = 32;      // partial-reduction slots of a chunk ([slot][workgroup][kLsW])
-constexpr int kLsScal = 16, kLsInt = 12;      // rows of the per-problem fp64 / int32 state ([row][kLsW])
-// workgroups of the row passes (four waves each, a wave owns a strip of rows): from the row counts alone, so that the partition -- and with it every
-// sum's order -- does not depend on what a chunk holds
-inline int lockstep_grid(int n, int m) { const int r = n > m ? n : m, g = (r + 15) / 16; return g < 1 ? 1 : (g > 256 ? 256 : g); }
-// doubles of a chunk's workspace: eight n- and nine m-block vectors, the partials, the per-problem state and records
-inline size_t lockstep_ws_doubles(int n, int m) {
-  return (size_t)kLsW * (8 * (size_t)n + 9 * (size_t)m + (size_t)kLsSlots * lockstep_grid(n, m) + (size_t)(m + 63) / 64 + 1 + kLsScal + kBatchRec + kLsInt) + 64;
-}
+// (chunk width kLsW, the state's row counts, lockstep_grid and the work blocks' layout and sizes: lockstep_layout.h)
 struct LockstepParams : BatchSettings {
   int n = 0, m = 0, count = 0;  // count: problems of this chunk (1 .. kLsW)
   DevCsr A, B;
@@ -510,16 +501,6 @@ struct LockstepParams : BatchSettings {
 };
 constexpr int kLsPolStat = 7;
 constexpr int kLsMatStat = 2;
-constexpr int kLsMatScalC = 11;   // row of the per-problem scalar state that holds c (lockstep_hip.hip SC_C; 1 / c follows)
-// where the per-problem scalar state sits in a chunk's workspace (lockstep_hip.hip lockstep_chunk's carve-up: the block vectors, the partials, parti)
-inline size_t lockstep_sc_offset(int n, int m) {
-  const size_t tm = (size_t)(m + 63) / 64;
-  return (size_t)kLsW * (8 * (size_t)n + 9 * (size_t)m + (size_t)kLsSlots * lockstep_grid(n, m) + (tm > 0 ? tm : 1));
-}
-// doubles of the matrix block of a chunk with per-problem matrices: both value arrays, D, Dinv, E, Einv
-inline size_t lockstep_mat_ws_doubles(int n, int m, int nzA, int nzB) { return (size_t)kLsW * ((size_t)nzA + (size_t)nzB + 2 * (size_t)n + 2 * (size_t)m) + 64; }
-// doubles of the polish work block: the scaled ADMM x (n) and y, z, l, u (m) of every problem of the chunk
-inline size_t lockstep_polish_ws_doubles(int n, int m) { return (size_t)kLsW * ((size_t)n + 4 * (size_t)m) + 64; }
 
 // Adjoint derivatives of a chunk on the lockstep route (lockstep_hip.hip lockstep_adjoint_chunk; include/osqp_hip.h osqp_hip_batch_adjoint_lockstep):
 // the recurrence of Engine::run_recurrence per problem on block vectors.  The base carries the matrices, the scalings, the permutations, the shared
@@ -533,41 +514,21 @@ struct LockstepAdjointParams : LockstepParams {
   double *dP = nullptr, *dq = nullptr, *dA = nullptr, *dl = nullptr, *du = nullptr, *arec = nullptr;      // the chunk's rows of the outputs, each optional
   int min_steps = 1, max_steps = 60; double gain = 0.9;                        // RecurrenceRule{true, 0.9, 60} with 1 + polish_refine_iter
 };
-// doubles of the adjoint's work block: the forward's set, then x, dx, r_x (n), y, dy, r_y (m) and the row codes (m ints)
-inline size_t lockstep_adjoint_ws_doubles(int n, int m) {
-  return lockstep_ws_doubles(n, m) + (size_t)kLsW * (3 * (size_t)n + 3 * (size_t)m + ((size_t)m + 1) / 2) + 64;
-}
 
 // The DIRECT lockstep route for a Woodbury handle whose K0 is diagonal (lockstep_hip.hip "lockstep DIRECT"; include/osqp_hip.h
 // osqp_hip_batch_solve_lockstep_direct): the base's A / B are the handle's; Av is the view of A the row passes read -- the one-entry rows as they are, long
 // row a as the single entry 1.0 at column n + a -- and WT / rows / islong are DevWb's (the dense transpose of the long rows, their indices, the row flags).
-struct LockstepDirectParams : LockstepParams {
+struct LockstepDirectView {
   int r = 0;                    // long rows (1 .. kWbMaxRows)
   DevCsr Av;
   const double *WT = nullptr; const int *rows = nullptr; const unsigned char *islong = nullptr;
 };
-// columns of a block of the products with the long rows (a multiple of 64, at most 128 blocks): from n alone, like lockstep_grid
-inline int lockstep_direct_colblock(int n) { const int t = (n + 63) / 64; return 64 * ((t + 127) / 128 > 0 ? (t + 127) / 128 : 1); }
-// doubles of a chunk's workspace: x, x~, dx with n + r rows, four n- and nine m-block vectors, the partials and state of the lockstep route, then S
-// (r x r per problem), two sets of column-block partials, h, the inversion counts
-inline size_t lockstep_direct_ws_doubles(int n, int m, int r) {
-  const size_t gc = ((size_t)n + lockstep_direct_colblock(n) - 1) / lockstep_direct_colblock(n);
-  return (size_t)kLsW * (3 * ((size_t)n + r) + 4 * (size_t)n + 9 * (size_t)m + (size_t)kLsSlots * lockstep_grid(n, m) + (size_t)(m + 63) / 64 + 1 + kLsScal + kBatchRec + kLsInt +
-                         (size_t)r * r + 2 * gc * r + r + 1) + 64;
-}
+struct LockstepDirectParams : LockstepParams { LockstepDirectView v; };
 
 // Adjoint derivatives of a chunk on the DIRECT route (lockstep_hip.hip lockstep_direct_adjoint_chunk; include/osqp_hip.h
 // osqp_hip_batch_adjoint_lockstep_direct): LockstepAdjointParams as Engine::run_lockstep_adjoint fills them (cg_max and pcg_rel are not read: there is
 // no PCG), with LockstepDirectParams' view of A and the dense rows' data.
-struct LockstepDirectAdjointParams : LockstepAdjointParams {
-  int r = 0;                    // long rows (1 .. kWbMaxRows)
-  DevCsr Av;
-  const double *WT = nullptr; const int *rows = nullptr; const unsigned char *islong = nullptr;
-};
-// doubles of its work block: the direct forward's set, then x, dx, r_x (n), y, dy, r_y (m) and the row codes (m ints)
-inline size_t lockstep_direct_adjoint_ws_doubles(int n, int m, int r) {
-  return lockstep_direct_ws_doubles(n, m, r) + (size_t)kLsW * (3 * (size_t)n + 3 * (size_t)m + ((size_t)m + 1) / 2) + 64;
-}
+struct LockstepDirectAdjointParams : LockstepAdjointParams { LockstepDirectView v; };
 
 namespace be {
 

@@ -168,11 +168,10 @@ void Engine::free_all() {
   if (lsaw_) { be::dfree(d_, lsaw_); lsaw_ = nullptr; }
   if (lsdw_) { be::dfree(d_, lsdw_); lsdw_ = nullptr; }
   if (lsdaw_) { be::dfree(d_, lsdaw_); lsdaw_ = nullptr; }
-  if (lsdabuf_) { be::dfree(d_, lsdabuf_); lsdabuf_ = nullptr; lsdabuf_cap_ = 0; }
+  for (DevScratch *sc : {&lsabuf_, &lsdabuf_}) if (sc->buf) { be::dfree(d_, sc->buf); *sc = DevScratch{}; }
   if (lsd_vval_) { be::dfree(d_, lsd_vval_); lsd_vval_ = nullptr; }
   if (lsd_vrp_) { be::dfree(d_, lsd_vrp_); be::dfree(d_, lsd_vcol_); be::dfree(d_, lsd_vsrc_); lsd_vrp_ = lsd_vcol_ = lsd_vsrc_ = nullptr; lsd_nv_ = 0; }
   wb_k0diag_ = false;
-  if (lsabuf_) { be::dfree(d_, lsabuf_); lsabuf_ = nullptr; lsabuf_cap_ = 0; }
   if (d_pvmap_) { be::dfree(d_, d_pvmap_); d_pvmap_ = nullptr; }
   if (d_avmap_) { be::dfree(d_, d_avmap_); d_avmap_ = nullptr; }
   free_batch_direct(); free_batch_spectral(); free_batch_wave();

@@ -160,33 +160,39 @@ class Engine {
   // mat: the per-problem-matrix entries (Px / Ax device arrays in the caller's CSC order, either may be nullptr); the shared entries leave it false
   int run_lockstep(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream,
                    bool mat = false, const double *Px = nullptr, const double *Ax = nullptr);
+  void fill_lockstep_handle(LockstepParams &p);       // the handle's matrices, scalings, shared vectors and permutations: every lockstep route
+  int last_record(const double *src, int cnt, double *rec) const;      // behind every *_last_record
   double *lsmw_ = nullptr;                            // matrix block of one lockstep chunk (lockstep_mat_ws_doubles), allocated by the first call with per-problem matrices
   double lsm_rec_[OSQP_HIP_LOCKSTEP_MAT_LAST_REC] = {0, 0, 0, 0, 0, 0, 0, 0};      // record of the last such call (osqp_hip_lockstep_mat_last_record)
   int lsm_last_count_ = 0;                            // problems of the last chunk that call processed (0: no call yet): what lockstep_mat_scaling reads
   bool lockstep_mat_applies();
   // direct lockstep route: the structural decision of prepare_wb (K0 diagonal, small mode -- not DevWb::exact, which a failed inversion clears), the
-  // chunk's workspace (lockstep_direct_ws_doubles(n, m, r)) and the view of A (LockstepDirectParams::Av), both built on first use, the last call's record
+  // chunk's workspace (lockstep_direct_ws_doubles(n, m, r)) and the view of A (LockstepDirectView::Av), both built on first use, the last call's record
   bool wb_k0diag_ = false;
   double *lsdw_ = nullptr, *lsd_vval_ = nullptr;
   int *lsd_vrp_ = nullptr, *lsd_vcol_ = nullptr, *lsd_vsrc_ = nullptr; int lsd_nv_ = 0;
   double lsd_rec_[OSQP_HIP_LOCKSTEP_DIRECT_LAST_REC] = {0, 0, 0, 0, 0, 0, 0, 0};
   bool lockstep_direct_applies();
   int prepare_lockstep_direct_view();                 // builds the view of A on first use (both directions of the direct route read it)
+  int fill_lockstep_direct_view(LockstepDirectView &v, void *stream);      // ... and fills a chunk's view from it, values refreshed
   int run_lockstep_direct(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream);
   double *lsaw_ = nullptr;                            // work block of one lockstep adjoint chunk (lockstep_adjoint_ws_doubles(n, m)), allocated on first use
-  double *lsabuf_ = nullptr; size_t lsabuf_cap_ = 0;  // device scratch of batch_adjoint_lockstep (host-array entry point), kept across calls
-  int *d_pvmap_ = nullptr, *d_avmap_ = nullptr;       // device copies of PvalMap_ / AvalMap_ (reordered handle), uploaded by the first lockstep adjoint
+  struct DevScratch { double *buf = nullptr; size_t cap = 0; };
+  DevScratch lsabuf_, lsdabuf_;                       // device scratch of batch_adjoint_lockstep / _direct (host-array entry points), kept across calls
+  int *d_pvmap_ = nullptr, *d_avmap_ = nullptr;       // device copies of PvalMap_ / AvalMap_ (reordered handle), uploaded by the first call that reads them
+  bool ensure_value_maps();
   double lsa_rec_[OSQP_HIP_LOCKSTEP_ADJOINT_LAST_REC] = {0, 0, 0, 0, 0, 0, 0, 0};     // record of the last lockstep adjoint call (osqp_hip_lockstep_adjoint_last_record)
   bool lockstep_adjoint_applies();
-  int run_lockstep_adjoint(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
-                           double *dP, double *dq, double *dA, double *dl, double *du, double *arec, void *stream);
-  // the backward pass on the direct route: its own work block (lockstep_direct_adjoint_ws_doubles(n, m, r)), host-entry scratch and record
+  // the arrays of a backward pass (host or device, as the entry says); one body per entry kind and one chunk loop serve both routes (direct: the
+  // direct route's applicability, work block, chunk function and record)
+  struct LockstepAdjointIO { const double *l, *u, *x, *y, *dx, *dy; double *dP, *dq, *dA, *dl, *du, *arec; };
+  int adjoint_lockstep_host(bool direct, int nbatch, const LockstepAdjointIO &h);
+  int adjoint_lockstep_device(bool direct, int nbatch, const LockstepAdjointIO &a, void *stream);
+  int run_lockstep_adjoint(bool direct, int nbatch, const LockstepAdjointIO &a, void *stream);
+  // the backward pass on the direct route: its own work block (lockstep_direct_adjoint_ws_doubles(n, m, r)) and record
   double *lsdaw_ = nullptr;
-  double *lsdabuf_ = nullptr; size_t lsdabuf_cap_ = 0;
   double lsda_rec_[OSQP_HIP_LOCKSTEP_DIRECT_ADJOINT_LAST_REC] = {0, 0, 0, 0, 0, 0, 0, 0};
   bool lockstep_direct_adjoint_applies();
-  int run_lockstep_direct_adjoint(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
-                                  double *dP, double *dq, double *dA, double *dl, double *du, double *arec, void *stream);
   // what the four batch entry points begin with, and the host staging of the two that take host arrays (engine_api.cpp)
   bool batch_applies();                               // the workgroup route: the QP fits one workgroup's LDS and the handle is not reordered
   bool batch_applies_prepared();

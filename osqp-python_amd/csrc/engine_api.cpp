@@ -905,24 +905,48 @@ int Engine::batch_solve_device(int nbatch, const double *q, const double *l, con
 // Chunks of kLsW problems, one after the other, each from its transposes in to its transposes out (be::lockstep_chunk).  q / l / u / x / y / rec are
 // DEVICE arrays in the caller's numbering; the settings are read once, in front of the first chunk.  The handle's iterates are not touched: the route
 // has its own workspace (lsw_, allocated on first use, freed with the handle) and, with polishing, its own polish work block (lspw_, likewise).
+// what every lockstep route takes from the handle: the matrices, the scalings, the shared vectors, the permutations of a reordered handle
+void Engine::fill_lockstep_handle(LockstepParams &p) {
+  p.n = n; p.m = m; p.A = d_.A; p.B = d_.B; p.D = d_.D; p.Dinv = d_.Dinv; p.E = d_.E; p.Einv = d_.Einv;
+  p.q0 = d_.qraw; p.l0 = d_.lraw; p.u0 = d_.uraw; p.pc = reordered_ ? d_pc_ : nullptr; p.pr = reordered_ ? d_pr_ : nullptr;
+}
+// device copies of PvalMap_ / AvalMap_ (reordered handle; per-problem matrices and the adjoint read them); true: something was uploaded, sync before use
+bool Engine::ensure_value_maps() {
+  bool fresh = false;
+  if (reordered_ && !d_pvmap_ && d_.nzP > 0) { d_pvmap_ = dev_vec<int>(d_, d_.nzP); be::h2d(d_, d_pvmap_, PvalMap_.data(), sizeof(int) * d_.nzP); fresh = true; }
+  if (reordered_ && !d_avmap_ && d_.nzA > 0) { d_avmap_ = dev_vec<int>(d_, d_.nzA); be::h2d(d_, d_avmap_, AvalMap_.data(), sizeof(int) * d_.nzA); fresh = true; }
+  return fresh;
+}
+// what the *_last_record getters share
+int Engine::last_record(const double *src, int cnt, double *rec) const {
+  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (!rec) return OSQP_DATA_VALIDATION_ERROR;
+  std::copy(src, src + cnt, rec);
+  return OSQP_NO_ERROR;
+}
+int Engine::lockstep_last_record(double *rec) const { return last_record(ls_rec_, OSQP_HIP_LOCKSTEP_LAST_REC, rec); }
+int Engine::lockstep_polish_last_record(double *rec) const { return last_record(ls_pol_rec_, OSQP_HIP_LOCKSTEP_POLISH_LAST_REC, rec); }
+int Engine::lockstep_mat_last_record(double *rec) const { return last_record(lsm_rec_, OSQP_HIP_LOCKSTEP_MAT_LAST_REC, rec); }
+int Engine::lockstep_direct_last_record(double *rec) const { return last_record(lsd_rec_, OSQP_HIP_LOCKSTEP_DIRECT_LAST_REC, rec); }
+int Engine::lockstep_adjoint_last_record(double *rec) const { return last_record(lsa_rec_, OSQP_HIP_LOCKSTEP_ADJOINT_LAST_REC, rec); }
+int Engine::lockstep_direct_adjoint_last_record(double *rec) const { return last_record(lsda_rec_, OSQP_HIP_LOCKSTEP_DIRECT_ADJOINT_LAST_REC, rec); }
+
 int Engine::run_lockstep(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream,
                          bool mat, const double *Px, const double *Ax) {
   const size_t need = lockstep_ws_doubles(n, m);
   if (!lsw_) { lsw_ = dev_vec<double>(d_, need); be::sync(d_); }
-  // per-problem matrices: the matrix block (allocated by the first such call) and, on a reordered handle, the value maps the lockstep adjoint uploads too
+  // per-problem matrices: the matrix block (allocated by the first such call) and, on a reordered handle, the value maps
   const int nzP = d_.nzP, nzA = d_.nzA;
   const size_t mneed = lockstep_mat_ws_doubles(n, m, d_.A.nnz, d_.B.nnz);
   if (mat) {
-    bool fresh = false;
+    bool fresh = ensure_value_maps();
     if (!lsmw_) { lsmw_ = dev_vec<double>(d_, mneed); fresh = true; }
-    if (reordered_ && !d_pvmap_ && nzP > 0) { d_pvmap_ = dev_vec<int>(d_, nzP); be::h2d(d_, d_pvmap_, PvalMap_.data(), sizeof(int) * nzP); fresh = true; }
-    if (reordered_ && !d_avmap_ && nzA > 0) { d_avmap_ = dev_vec<int>(d_, nzA); be::h2d(d_, d_avmap_, AvalMap_.data(), sizeof(int) * nzA); fresh = true; }
     if (fresh) be::sync(d_);
   }
   LockstepParams p;
   fill_batch_settings(p, warm);                       // the settings snapshot of the batch path
-  p.n = n; p.m = m; p.A = d_.A; p.B = d_.B; p.D = d_.D; p.Dinv = d_.Dinv; p.E = d_.E; p.Einv = d_.Einv;
-  p.q0 = d_.qraw; p.l0 = d_.lraw; p.u0 = d_.uraw; p.pc = reordered_ ? d_pc_ : nullptr; p.pr = reordered_ ? d_pr_ : nullptr; p.ws = lsw_;
+  fill_lockstep_handle(p);
+  p.ws = lsw_;
   // polish (settings.polishing): the recurrence of Engine::run_recurrence as Engine::polish calls it, per problem on block vectors -- rho_bar = 1 / delta_eff,
   // at least 1 + polish_refine_iter steps, the inner systems to polish_pcg_tol within kMaxCg iterations.  Its work block is allocated by the first such call.
   double pst[kLsPolStat] = {0, 0, 0, 0, 0, 0, 0}, ptot[kLsPolStat] = {0, 0, 0, 0, 0, 0, 0};
@@ -996,15 +1020,8 @@ int Engine::batch_solve_lockstep_mat_device(int nbatch, const double *Px, const 
   return run_lockstep(nbatch, q, l, u, x, y, rec, warm, stream, true, Px, Ax);
 }
 
-int Engine::lockstep_mat_last_record(double *rec) const {
-  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  if (!rec) return OSQP_DATA_VALIDATION_ERROR;
-  std::copy(lsm_rec_, lsm_rec_ + OSQP_HIP_LOCKSTEP_MAT_LAST_REC, rec);
-  return OSQP_NO_ERROR;
-}
-
 // D, E, c of problem b of the last chunk the last call with per-problem matrices processed, in the caller's numbering: read back from the matrix block
-// (lockstep_hip.hip "matrices of a chunk": [Aval | Bval | D | Dinv | E | Einv], problem-minor) and the chunk's scalar state (row 11 of kLsScal: c)
+// and the chunk's scalar state (row kLsMatScalC), where lockstep_layout.h's carves put them
 int Engine::lockstep_mat_scaling(int b, double *D, double *E, double *c) {
   if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   if (!D || (m > 0 && !E) || !c) return OSQP_DATA_VALIDATION_ERROR;
@@ -1012,7 +1029,10 @@ int Engine::lockstep_mat_scaling(int b, double *D, double *E, double *c) {
   be::activate(d_);
   be::ext_wait(d_);
   const size_t nW = (size_t)n * kLsW, mW = (size_t)m * kLsW;
-  const double *dD = lsmw_ + (size_t)kLsW * ((size_t)d_.A.nnz + (size_t)d_.B.nnz), *dE = dD + 2 * nW;
+  LsCursor cm{lsmw_};
+  LsMatVecs t;
+  lockstep_carve_mat(cm, t, n, m, d_.A.nnz, d_.B.nnz);
+  const double *dD = t.D, *dE = t.E;
   std::vector<double> h(std::max(nW, mW));
   be::d2h(d_, h.data(), dD, sizeof(double) * nW);
   for (int j = 0; j < n; j++) D[reordered_ ? pc_[j] : j] = h[(size_t)j * kLsW + b];
@@ -1041,20 +1061,6 @@ int Engine::batch_solve_lockstep_device(int nbatch, const double *q, const doubl
   return run_lockstep(nbatch, q, l, u, x, y, rec, warm, stream);
 }
 
-int Engine::lockstep_last_record(double *rec) const {
-  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  if (!rec) return OSQP_DATA_VALIDATION_ERROR;
-  std::copy(ls_rec_, ls_rec_ + OSQP_HIP_LOCKSTEP_LAST_REC, rec);
-  return OSQP_NO_ERROR;
-}
-
-int Engine::lockstep_polish_last_record(double *rec) const {
-  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  if (!rec) return OSQP_DATA_VALIDATION_ERROR;
-  std::copy(ls_pol_rec_, ls_pol_rec_ + OSQP_HIP_LOCKSTEP_POLISH_LAST_REC, rec);
-  return OSQP_NO_ERROR;
-}
-
 // ------------------------------------------------------------------------------------------------ direct lockstep route (Woodbury handles)
 // lockstep_hip.hip "lockstep DIRECT": the lockstep iteration with the PCG replaced by the Woodbury formula per problem.  Applies to a handle in the small
 // Woodbury mode whose K0 setup found structurally diagonal (prepare_wb: wb_k0diag_), as numbered by the caller: a reordered handle declines.
@@ -1080,21 +1086,26 @@ int Engine::prepare_lockstep_direct_view() {
   return OSQP_NO_ERROR;
 }
 
+// The direct view of both directions of the direct route: built on first use, filled, its values refreshed from A's current ones on `stream`
+int Engine::fill_lockstep_direct_view(LockstepDirectView &v, void *stream) {
+  if (const int err = prepare_lockstep_direct_view()) return err;
+  v.r = d_.wb.r; v.WT = d_.wb.WT; v.rows = d_.wb.rows; v.islong = d_.wb.islong;
+  v.Av = d_.A; v.Av.ncols = n + v.r; v.Av.nnz = lsd_nv_; v.Av.rowptr = lsd_vrp_; v.Av.col = lsd_vcol_; v.Av.val = lsd_vval_;
+  return be::lockstep_direct_values(d_, lsd_nv_, lsd_vsrc_, lsd_vval_, stream);      // (A's values may have changed since the last call)
+}
+
 int Engine::run_lockstep_direct(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream) {
   const int r = d_.wb.r;
   const size_t need = lockstep_direct_ws_doubles(n, m, r);
-  if (const int err = prepare_lockstep_direct_view()) return err;
-  if (!lsdw_) { lsdw_ = dev_vec<double>(d_, need); be::sync(d_); }
   LockstepDirectParams p;
+  if (const int err = fill_lockstep_direct_view(p.v, stream)) return err;
+  if (!lsdw_) { lsdw_ = dev_vec<double>(d_, need); be::sync(d_); }
   fill_batch_settings(p, warm);
-  p.n = n; p.m = m; p.A = d_.A; p.B = d_.B; p.D = d_.D; p.Dinv = d_.Dinv; p.E = d_.E; p.Einv = d_.Einv;
-  p.q0 = d_.qraw; p.l0 = d_.lraw; p.u0 = d_.uraw; p.ws = lsdw_;
-  p.r = r; p.WT = d_.wb.WT; p.rows = d_.wb.rows; p.islong = d_.wb.islong;
+  fill_lockstep_handle(p);
+  p.ws = lsdw_;
   // adaptive rho as the handle's own solve decides it (ctl_setup: the tolerance on the square-root scale where P has a quadratic part, the persistence
   // test), not as the batch family does: an element then takes the path update(q, l, u) + solve() takes from the same rho
   p.rho_tol_single = pol_rho_tol(settings.adaptive_rho_tolerance, has_quad(), pol_.rho_tol_exp); p.rho_persist = pol_.rho_persist;
-  p.Av = d_.A; p.Av.ncols = n + r; p.Av.nnz = lsd_nv_; p.Av.rowptr = lsd_vrp_; p.Av.col = lsd_vcol_; p.Av.val = lsd_vval_;
-  if (const int err = be::lockstep_direct_values(d_, lsd_nv_, lsd_vsrc_, lsd_vval_, stream)) return err;      // (A's values may have changed since the last call)
   const double t0 = now_s(), limit = settings.time_limit > 0 && settings.time_limit < 1e9 ? settings.time_limit : 0.0;
   double tot[4] = {0, 0, 0, 0};
   int chunks = 0;
@@ -1128,13 +1139,6 @@ int Engine::batch_solve_lockstep_direct_device(int nbatch, const double *q, cons
   return run_lockstep_direct(nbatch, q, l, u, x, y, rec, warm, stream);
 }
 
-int Engine::lockstep_direct_last_record(double *rec) const {
-  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  if (!rec) return OSQP_DATA_VALIDATION_ERROR;
-  std::copy(lsd_rec_, lsd_rec_ + OSQP_HIP_LOCKSTEP_DIRECT_LAST_REC, rec);
-  return OSQP_NO_ERROR;
-}
-
 // ---- the backward pass of a lockstep batch (lockstep_hip.hip lockstep_adjoint_chunk): chunk after chunk like run_lockstep.  Every array is a DEVICE
 // array in the caller's numbering (dP / dA: the caller's CSC order).  The recurrence's settings are those of Engine::run_recurrence as the single-QP
 // adjoint calls it: rho_bar = 1 / delta_eff on the active rows with equality factor 1, alpha = 1, PCG to polish_pcg_tol within kMaxCg, progress rule
@@ -1142,168 +1146,102 @@ int Engine::lockstep_direct_last_record(double *rec) const {
 // solution, graphs and history -- and the forward route's workspace and record -- are not touched.
 bool Engine::lockstep_adjoint_applies() { return be::lockstep_adjoint_chunk && be::device_assembly() && be::device_vec_updates() && !d_.wb.on; }
 
-int Engine::run_lockstep_adjoint(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
-                                 double *dP, double *dq, double *dA, double *dl, double *du, double *arec, void *stream) {
-  const size_t need = lockstep_adjoint_ws_doubles(n, m);
+// The backward pass on the direct route (lockstep_hip.hip lockstep_direct_adjoint_chunk) is the same settings and chunking on the handles
+// lockstep_direct_applies accepts.  The recurrence's rho is fixed, so S_b is inverted once per problem.  The work block (lsdaw_) and the host entry's
+// scratch are that route's own; the view of A is the forward's (read only, its values refreshed per call); the handle's solve state, the forward route's
+// workspace and its record are not written.
+bool Engine::lockstep_direct_adjoint_applies() { return lockstep_direct_applies() && be::lockstep_direct_adjoint_chunk && be::device_assembly(); }
+
+// Both routes' chunk loop.  direct selects the applicability, the work block, the chunk function and the record.
+int Engine::run_lockstep_adjoint(bool direct, int nbatch, const LockstepAdjointIO &a, void *stream) {
   const int nzP = d_.nzP, nzA = d_.nzA;
-  bool fresh = false;
-  if (!lsaw_) { lsaw_ = dev_vec<double>(d_, need); fresh = true; }
-  if (reordered_ && !d_pvmap_ && nzP > 0) { d_pvmap_ = dev_vec<int>(d_, nzP); be::h2d(d_, d_pvmap_, PvalMap_.data(), sizeof(int) * nzP); fresh = true; }
-  if (reordered_ && !d_avmap_ && nzA > 0) { d_avmap_ = dev_vec<int>(d_, nzA); be::h2d(d_, d_avmap_, AvalMap_.data(), sizeof(int) * nzA); fresh = true; }
+  const size_t need = direct ? lockstep_direct_adjoint_ws_doubles(n, m, d_.wb.r) : lockstep_adjoint_ws_doubles(n, m);
+  LockstepDirectAdjointParams p;                      // (the PCG route takes its LockstepAdjointParams base)
+  if (direct) if (const int err = fill_lockstep_direct_view(p.v, stream)) return err;
+  double *&ws = direct ? lsdaw_ : lsaw_;
+  bool fresh = ensure_value_maps();
+  if (!ws) { ws = dev_vec<double>(d_, need); fresh = true; }
   if (fresh) be::sync(d_);
-  LockstepAdjointParams p;
   fill_batch_settings(p, 0);
+  fill_lockstep_handle(p);
+  p.ws = ws;
+  // the recurrence's settings; the direct route has no PCG
   const double de = std::max(settings.delta, pol_.polish_delta_floor);
-  p.alpha = 1.0; p.rho0 = clamp_rho(1.0 / de); p.eq_factor = 1.0; p.cg_max = kMaxCg; p.pcg_rel = pol_.polish_pcg_tol;
+  p.alpha = 1.0; p.rho0 = clamp_rho(1.0 / de); p.eq_factor = 1.0; p.cg_max = direct ? 0 : kMaxCg; p.pcg_rel = direct ? 0.0 : pol_.polish_pcg_tol;
   p.min_steps = 1 + std::max(0, (int)settings.polish_refine_iter); p.max_steps = 60; p.gain = 0.9;
-  p.n = n; p.m = m; p.A = d_.A; p.B = d_.B; p.D = d_.D; p.Dinv = d_.Dinv; p.E = d_.E; p.Einv = d_.Einv;
-  p.l0 = d_.lraw; p.u0 = d_.uraw; p.pc = reordered_ ? d_pc_ : nullptr; p.pr = reordered_ ? d_pr_ : nullptr; p.ws = lsaw_;
   p.nzP = nzP; p.nzA = nzA; p.Pi = d_.Pi; p.Pj = d_.Pj; p.Ai = d_.Ai; p.Aj = d_.Aj; p.Pmap = reordered_ ? d_pvmap_ : nullptr; p.Amap = reordered_ ? d_avmap_ : nullptr;
   double tot[4] = {0, 0, 0, 0};
   int chunks = 0;
-  auto at = [](auto *a, size_t off) { return a ? a + off : nullptr; };
+  auto at = [](auto *v, size_t off) { return v ? v + off : nullptr; };
   for (int b0 = 0; b0 < nbatch; b0 += kLsW, chunks++) {
     const size_t b = (size_t)b0;
     p.count = std::min(kLsW, nbatch - b0);
-    p.l = at(l, b * m); p.u = at(u, b * m); p.sx = x + b * n; p.sy = at(y, b * m); p.gx = dx + b * n; p.gy = at(dy, b * m);
-    p.dP = at(dP, b * nzP); p.dq = at(dq, b * n); p.dA = at(dA, b * nzA); p.dl = at(dl, b * m); p.du = at(du, b * m); p.arec = at(arec, b * kAdjointRec);
+    p.l = at(a.l, b * m); p.u = at(a.u, b * m); p.sx = a.x + b * n; p.sy = at(a.y, b * m); p.gx = a.dx + b * n; p.gy = at(a.dy, b * m);
+    p.dP = at(a.dP, b * nzP); p.dq = at(a.dq, b * n); p.dA = at(a.dA, b * nzA); p.dl = at(a.dl, b * m); p.du = at(a.du, b * m); p.arec = at(a.arec, b * kAdjointRec);
     double st[4] = {0, 0, 0, 0};
-    const int err = be::lockstep_adjoint_chunk(d_, p, stream, st);
+    const int err = direct ? be::lockstep_direct_adjoint_chunk(d_, p, stream, st) : be::lockstep_adjoint_chunk(d_, p, stream, st);
     if (err) return err;
     tot[0] = std::max(tot[0], st[0]); tot[1] += st[1]; tot[2] += st[2]; tot[3] += st[3];
   }
+  static_assert(OSQP_HIP_LOCKSTEP_ADJOINT_LAST_REC == OSQP_HIP_LOCKSTEP_DIRECT_ADJOINT_LAST_REC, "one record text for both adjoint routes");
   const double r[OSQP_HIP_LOCKSTEP_ADJOINT_LAST_REC] = {(double)chunks, (double)kLsW, tot[0], tot[1], tot[2], tot[3], (double)(need * sizeof(double)), 0.0};
-  std::copy(r, r + OSQP_HIP_LOCKSTEP_ADJOINT_LAST_REC, lsa_rec_);
+  std::copy(r, r + OSQP_HIP_LOCKSTEP_ADJOINT_LAST_REC, direct ? lsda_rec_ : lsa_rec_);
   return OSQP_NO_ERROR;
+}
+
+// the host-array entry of both routes: one device scratch block per route, kept for the next call
+int Engine::adjoint_lockstep_host(bool direct, int nbatch, const LockstepAdjointIO &h) {
+  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (nbatch <= 0 || !h.x || (!h.y && m > 0) || !h.dx) return OSQP_DATA_VALIDATION_ERROR;
+  be::activate(d_);
+  if (!(direct ? lockstep_direct_adjoint_applies() : lockstep_adjoint_applies())) return OSQP_FUNC_NOT_IMPLEMENTED;
+  be::ext_wait(d_);
+  DevScratch &sc = direct ? lsdabuf_ : lsabuf_;
+  const size_t nb = (size_t)nbatch, N = nb * n, M = nb * m, NP = nb * (size_t)d_.nzP, NA = nb * (size_t)d_.nzA;
+  // [l | u | x | y | dx | dy | dP | dq | dA | dl | du | arec]
+  const size_t need = 3 * N + 6 * M + NP + NA + nb * kAdjointRec;
+  if (need > sc.cap) { if (sc.buf) be::dfree(d_, sc.buf); sc.cap = 0; sc.buf = dev_vec<double>(d_, need); sc.cap = need; }
+  double *d_l = sc.buf, *d_u = d_l + M, *d_x = d_u + M, *d_y = d_x + N, *d_dx = d_y + M, *d_dy = d_dx + N;
+  double *o_dP = d_dy + M, *o_dq = o_dP + NP, *o_dA = o_dq + N, *o_dl = o_dA + NA, *o_du = o_dl + M, *o_rec = o_du + M;
+  auto up = [&](double *dst, const double *src, size_t cnt) { if (src && cnt) be::h2d(d_, dst, src, sizeof(double) * cnt); };
+  up(d_l, h.l, M); up(d_u, h.u, M); up(d_x, h.x, N); up(d_y, h.y, M); up(d_dx, h.dx, N); up(d_dy, h.dy, M);
+  be::sync(d_);
+  const LockstepAdjointIO dv{h.l ? d_l : nullptr, h.u ? d_u : nullptr, d_x, d_y, d_dx, h.dy ? d_dy : nullptr, h.dP ? o_dP : nullptr, h.dq ? o_dq : nullptr,
+                             h.dA ? o_dA : nullptr, h.dl ? o_dl : nullptr, h.du ? o_du : nullptr, h.arec ? o_rec : nullptr};
+  if (const int err = run_lockstep_adjoint(direct, nbatch, dv, nullptr)) return err;
+  auto down = [&](double *dst, const double *src, size_t cnt) { if (dst && cnt) be::d2h(d_, dst, src, sizeof(double) * cnt); };
+  down(h.dP, o_dP, NP); down(h.dq, o_dq, N); down(h.dA, o_dA, NA); down(h.dl, o_dl, M); down(h.du, o_du, M); down(h.arec, o_rec, nb * kAdjointRec);
+  return OSQP_NO_ERROR;
+}
+
+// the device-array entry of both routes
+int Engine::adjoint_lockstep_device(bool direct, int nbatch, const LockstepAdjointIO &a, void *stream) {
+  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (nbatch < 0) return OSQP_DATA_VALIDATION_ERROR;
+  be::activate(d_);
+  if (!(direct ? lockstep_direct_adjoint_applies() : lockstep_adjoint_applies())) return OSQP_FUNC_NOT_IMPLEMENTED;
+  if (nbatch == 0) return OSQP_NO_ERROR;              // (the applicability query, as osqp_hip_batch_solve_lockstep_device answers it)
+  if (!a.x || (!a.y && m > 0) || !a.dx) return OSQP_DATA_VALIDATION_ERROR;
+  be::ext_wait(d_);
+  be::sync(d_);                                       // the solver's own stream first: pending updates of the resident l / u, the matrices
+  return run_lockstep_adjoint(direct, nbatch, a, stream);
 }
 
 int Engine::batch_adjoint_lockstep(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
                                    double *dP, double *dq, double *dA, double *dl, double *du, double *arec) {
-  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  if (nbatch <= 0 || !x || (!y && m > 0) || !dx) return OSQP_DATA_VALIDATION_ERROR;
-  be::activate(d_);
-  if (!lockstep_adjoint_applies()) return OSQP_FUNC_NOT_IMPLEMENTED;
-  be::ext_wait(d_);
-  const size_t nb = (size_t)nbatch, N = nb * n, M = nb * m, NP = nb * (size_t)d_.nzP, NA = nb * (size_t)d_.nzA;
-  // one device scratch block, kept for the next call: [l | u | x | y | dx | dy | dP | dq | dA | dl | du | arec]
-  const size_t need = 3 * N + 6 * M + NP + NA + nb * kAdjointRec;
-  if (need > lsabuf_cap_) { if (lsabuf_) be::dfree(d_, lsabuf_); lsabuf_cap_ = 0; lsabuf_ = dev_vec<double>(d_, need); lsabuf_cap_ = need; }
-  double *d_l = lsabuf_, *d_u = d_l + M, *d_x = d_u + M, *d_y = d_x + N, *d_dx = d_y + M, *d_dy = d_dx + N;
-  double *o_dP = d_dy + M, *o_dq = o_dP + NP, *o_dA = o_dq + N, *o_dl = o_dA + NA, *o_du = o_dl + M, *o_rec = o_du + M;
-  auto up = [&](double *dst, const double *src, size_t cnt) { if (src && cnt) be::h2d(d_, dst, src, sizeof(double) * cnt); };
-  up(d_l, l, M); up(d_u, u, M); up(d_x, x, N); up(d_y, y, M); up(d_dx, dx, N); up(d_dy, dy, M);
-  be::sync(d_);
-  const int err = run_lockstep_adjoint(nbatch, l ? d_l : nullptr, u ? d_u : nullptr, d_x, d_y, d_dx, dy ? d_dy : nullptr, dP ? o_dP : nullptr, dq ? o_dq : nullptr,
-                                       dA ? o_dA : nullptr, dl ? o_dl : nullptr, du ? o_du : nullptr, arec ? o_rec : nullptr, nullptr);
-  if (err) return err;
-  auto down = [&](double *dst, const double *src, size_t cnt) { if (dst && cnt) be::d2h(d_, dst, src, sizeof(double) * cnt); };
-  down(dP, o_dP, NP); down(dq, o_dq, N); down(dA, o_dA, NA); down(dl, o_dl, M); down(du, o_du, M); down(arec, o_rec, nb * kAdjointRec);
-  return OSQP_NO_ERROR;
+  return adjoint_lockstep_host(false, nbatch, {l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec});
 }
-
 int Engine::batch_adjoint_lockstep_device(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
                                           double *dP, double *dq, double *dA, double *dl, double *du, double *arec, void *stream) {
-  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  if (nbatch < 0) return OSQP_DATA_VALIDATION_ERROR;
-  be::activate(d_);
-  if (!lockstep_adjoint_applies()) return OSQP_FUNC_NOT_IMPLEMENTED;
-  if (nbatch == 0) return OSQP_NO_ERROR;              // (the applicability query, as osqp_hip_batch_solve_lockstep_device answers it)
-  if (!x || (!y && m > 0) || !dx) return OSQP_DATA_VALIDATION_ERROR;
-  be::ext_wait(d_);
-  be::sync(d_);                                       // the solver's own stream first: pending updates of the resident l / u, the matrices
-  return run_lockstep_adjoint(nbatch, l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec, stream);
+  return adjoint_lockstep_device(false, nbatch, {l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec}, stream);
 }
-
-int Engine::lockstep_adjoint_last_record(double *rec) const {
-  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  if (!rec) return OSQP_DATA_VALIDATION_ERROR;
-  std::copy(lsa_rec_, lsa_rec_ + OSQP_HIP_LOCKSTEP_ADJOINT_LAST_REC, rec);
-  return OSQP_NO_ERROR;
-}
-
-// ---- the backward pass on the direct route (lockstep_hip.hip lockstep_direct_adjoint_chunk): run_lockstep_adjoint's settings and chunking on the handles
-// lockstep_direct_applies accepts.  The recurrence's rho is fixed, so S_b is inverted once per problem.  The work block (lsdaw_) and the host entry's
-// scratch are this route's own; the view of A is the forward's (read only, its values refreshed per call); the handle's solve state, the forward route's
-// workspace and its record are not written.
-bool Engine::lockstep_direct_adjoint_applies() { return lockstep_direct_applies() && be::lockstep_direct_adjoint_chunk && be::device_assembly(); }
-
-int Engine::run_lockstep_direct_adjoint(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
-                                        double *dP, double *dq, double *dA, double *dl, double *du, double *arec, void *stream) {
-  const int r = d_.wb.r, nzP = d_.nzP, nzA = d_.nzA;
-  const size_t need = lockstep_direct_adjoint_ws_doubles(n, m, r);
-  if (const int err = prepare_lockstep_direct_view()) return err;
-  if (!lsdaw_) { lsdaw_ = dev_vec<double>(d_, need); be::sync(d_); }
-  LockstepDirectAdjointParams p;
-  fill_batch_settings(p, 0);
-  const double de = std::max(settings.delta, pol_.polish_delta_floor);
-  p.alpha = 1.0; p.rho0 = clamp_rho(1.0 / de); p.eq_factor = 1.0; p.cg_max = 0; p.pcg_rel = 0.0;
-  p.min_steps = 1 + std::max(0, (int)settings.polish_refine_iter); p.max_steps = 60; p.gain = 0.9;
-  p.n = n; p.m = m; p.A = d_.A; p.B = d_.B; p.D = d_.D; p.Dinv = d_.Dinv; p.E = d_.E; p.Einv = d_.Einv;
-  p.l0 = d_.lraw; p.u0 = d_.uraw; p.ws = lsdaw_;
-  p.nzP = nzP; p.nzA = nzA; p.Pi = d_.Pi; p.Pj = d_.Pj; p.Ai = d_.Ai; p.Aj = d_.Aj;
-  p.r = r; p.WT = d_.wb.WT; p.rows = d_.wb.rows; p.islong = d_.wb.islong;
-  p.Av = d_.A; p.Av.ncols = n + r; p.Av.nnz = lsd_nv_; p.Av.rowptr = lsd_vrp_; p.Av.col = lsd_vcol_; p.Av.val = lsd_vval_;
-  if (const int err = be::lockstep_direct_values(d_, lsd_nv_, lsd_vsrc_, lsd_vval_, stream)) return err;      // (A's values may have changed since the last call)
-  double tot[4] = {0, 0, 0, 0};
-  int chunks = 0;
-  auto at = [](auto *a, size_t off) { return a ? a + off : nullptr; };
-  for (int b0 = 0; b0 < nbatch; b0 += kLsW, chunks++) {
-    const size_t b = (size_t)b0;
-    p.count = std::min(kLsW, nbatch - b0);
-    p.l = at(l, b * m); p.u = at(u, b * m); p.sx = x + b * n; p.sy = at(y, b * m); p.gx = dx + b * n; p.gy = at(dy, b * m);
-    p.dP = at(dP, b * nzP); p.dq = at(dq, b * n); p.dA = at(dA, b * nzA); p.dl = at(dl, b * m); p.du = at(du, b * m); p.arec = at(arec, b * kAdjointRec);
-    double st[4] = {0, 0, 0, 0};
-    const int err = be::lockstep_direct_adjoint_chunk(d_, p, stream, st);
-    if (err) return err;
-    tot[0] = std::max(tot[0], st[0]); tot[1] += st[1]; tot[2] += st[2]; tot[3] += st[3];
-  }
-  const double rr[OSQP_HIP_LOCKSTEP_DIRECT_ADJOINT_LAST_REC] = {(double)chunks, (double)kLsW, tot[0], tot[1], tot[2], tot[3], (double)(need * sizeof(double)), 0.0};
-  std::copy(rr, rr + OSQP_HIP_LOCKSTEP_DIRECT_ADJOINT_LAST_REC, lsda_rec_);
-  return OSQP_NO_ERROR;
-}
-
 int Engine::batch_adjoint_lockstep_direct(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
                                           double *dP, double *dq, double *dA, double *dl, double *du, double *arec) {
-  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  if (nbatch <= 0 || !x || (!y && m > 0) || !dx) return OSQP_DATA_VALIDATION_ERROR;
-  be::activate(d_);
-  if (!lockstep_direct_adjoint_applies()) return OSQP_FUNC_NOT_IMPLEMENTED;
-  be::ext_wait(d_);
-  const size_t nb = (size_t)nbatch, N = nb * n, M = nb * m, NP = nb * (size_t)d_.nzP, NA = nb * (size_t)d_.nzA;
-  // one device scratch block, kept for the next call: [l | u | x | y | dx | dy | dP | dq | dA | dl | du | arec]
-  const size_t need = 3 * N + 6 * M + NP + NA + nb * kAdjointRec;
-  if (need > lsdabuf_cap_) { if (lsdabuf_) be::dfree(d_, lsdabuf_); lsdabuf_cap_ = 0; lsdabuf_ = dev_vec<double>(d_, need); lsdabuf_cap_ = need; }
-  double *d_l = lsdabuf_, *d_u = d_l + M, *d_x = d_u + M, *d_y = d_x + N, *d_dx = d_y + M, *d_dy = d_dx + N;
-  double *o_dP = d_dy + M, *o_dq = o_dP + NP, *o_dA = o_dq + N, *o_dl = o_dA + NA, *o_du = o_dl + M, *o_rec = o_du + M;
-  auto up = [&](double *dst, const double *src, size_t cnt) { if (src && cnt) be::h2d(d_, dst, src, sizeof(double) * cnt); };
-  up(d_l, l, M); up(d_u, u, M); up(d_x, x, N); up(d_y, y, M); up(d_dx, dx, N); up(d_dy, dy, M);
-  be::sync(d_);
-  const int err = run_lockstep_direct_adjoint(nbatch, l ? d_l : nullptr, u ? d_u : nullptr, d_x, d_y, d_dx, dy ? d_dy : nullptr, dP ? o_dP : nullptr, dq ? o_dq : nullptr,
-                                              dA ? o_dA : nullptr, dl ? o_dl : nullptr, du ? o_du : nullptr, arec ? o_rec : nullptr, nullptr);
-  if (err) return err;
-  auto down = [&](double *dst, const double *src, size_t cnt) { if (dst && cnt) be::d2h(d_, dst, src, sizeof(double) * cnt); };
-  down(dP, o_dP, NP); down(dq, o_dq, N); down(dA, o_dA, NA); down(dl, o_dl, M); down(du, o_du, M); down(arec, o_rec, nb * kAdjointRec);
-  return OSQP_NO_ERROR;
+  return adjoint_lockstep_host(true, nbatch, {l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec});
 }
-
 int Engine::batch_adjoint_lockstep_direct_device(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
                                                  double *dP, double *dq, double *dA, double *dl, double *du, double *arec, void *stream) {
-  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  if (nbatch < 0) return OSQP_DATA_VALIDATION_ERROR;
-  be::activate(d_);
-  if (!lockstep_direct_adjoint_applies()) return OSQP_FUNC_NOT_IMPLEMENTED;
-  if (nbatch == 0) return OSQP_NO_ERROR;              // (the applicability query)
-  if (!x || (!y && m > 0) || !dx) return OSQP_DATA_VALIDATION_ERROR;
-  be::ext_wait(d_);
-  be::sync(d_);                                       // the solver's own stream first: pending updates of the resident l / u, the matrices
-  return run_lockstep_direct_adjoint(nbatch, l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec, stream);
-}
-
-int Engine::lockstep_direct_adjoint_last_record(double *rec) const {
-  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  if (!rec) return OSQP_DATA_VALIDATION_ERROR;
-  std::copy(lsda_rec_, lsda_rec_ + OSQP_HIP_LOCKSTEP_DIRECT_ADJOINT_LAST_REC, rec);
-  return OSQP_NO_ERROR;
+  return adjoint_lockstep_device(true, nbatch, {l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec}, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ adjoint derivatives
@@ -1514,12 +1452,7 @@ int Engine::adjoint_compute_pcg(const double *x, const double *y, const double *
   return adj_ok_ ? OSQP_NO_ERROR : OSQP_LINSYS_SOLVER_INIT_ERROR;
 }
 
-int Engine::adjoint_last_record(double *rec) const {
-  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  if (!rec) return OSQP_DATA_VALIDATION_ERROR;
-  std::copy(adj_rec_, adj_rec_ + OSQP_HIP_ADJOINT_LAST_REC, rec);
-  return OSQP_NO_ERROR;
-}
+int Engine::adjoint_last_record(double *rec) const { return last_record(adj_rec_, OSQP_HIP_ADJOINT_LAST_REC, rec); }
 
 int Engine::adjoint_get_mat(OSQPCscMatrix *dP, OSQPCscMatrix *dA) {
   if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;

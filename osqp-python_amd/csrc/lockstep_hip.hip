@@ -17,9 +17,12 @@
 //               (its record is written at that moment).  Lanes >= count are "terminated" from the start.
 //   driving     per ADMM iteration the host enqueues the PCG iterations (six launches each) the previous one needed, plus one, without synchronising,
 //               reads the word block, and goes on in groups of four up to cg_max_iter while the device word "some problem's PCG is still running"
-//               is set; that word makes the launches past the last problem's convergence return at once.  Termination, the infeasibility tests, the
-//               statuses at max_iter and adaptive rho are decided per problem on the device (k_ls_decide: k_batch_admm's formulas, cited there);
-//               the host reads one small word block per termination check.
+//               is set; that word makes the launches past the last problem's convergence return at once (ls_pcg).  Termination, the infeasibility
+//               tests, the statuses at max_iter and adaptive rho are decided per problem on the device (k_ls_decide: k_batch_admm's formulas, cited
+//               there); the host reads one small word block per termination check.  The host side is written once -- "driving" in front of the chunk
+//               functions: LsRun (stream, launches, words, events), LsPcgKernels (the kernels on the handle's or the chunk's own matrices), ls_pcg,
+//               ls_recurrence (polish and both adjoints), LwRun (the direct route's argument views and launch groups) -- and each of the four chunk
+//               functions is its own sequence over these.  Where the work blocks' vectors sit: lockstep_layout.h, one carve per pointer set.
 // Transposes (LDS tiles, coalesced on both sides) move a chunk between the API's [nbatch][n] row-major arrays and the block vectors; they apply
 // k_batch_admm's load / store scaling and, for a handle that works on a permuted copy, gather / scatter through the permutations.
 // The BACKWARD pass of a chunk (osqp_hip_batch_adjoint_lockstep; lockstep_adjoint_chunk below): the adjoint system of every problem by the recurrence polish
@@ -51,15 +54,9 @@ enum LsInt { IW_DONE = 0, IW_STATUS, IW_RHOUPD, IW_PCG, IW_RELRULE, IW_CGON, IW_
 enum LsWord { WD_CGANY = 0, WD_LIVE, WD_RHOANY, WD_PCGSUM, WD_CGIT /* PCG iterations of the current ADMM iteration that some problem needed */,
               WD_POLACC /* polish: problems accepted */, WD_POLREJ /* rejected */, WD_COUNT };
 static_assert(SC_C == kLsMatScalC, "Engine::lockstep_mat_scaling reads c from this row");
-static_assert(SC_COUNT <= kLsScal && IW_COUNT + 1 <= kLsInt, "lockstep_ws_doubles reserves kLsScal / kLsInt rows");
+static_assert(SC_COUNT <= kLsScal && IW_COUNT + 1 == kLsInt, "lockstep_layout.h reserves kLsScal / kLsInt rows; the word block is the last int row");
 
-struct LsWs {
-  double *x, *xs, *r, *p, *Kp, *q, *Minv, *dx;        // n x W
-  double *z, *y, *t, *t2, *l, *u, *rho, *zt, *dy;     // m x W
-  double *part, *parti, *sc, *rec;
-  int *iw, *word;
-  int G;
-};
+// (LsWs and the other pointer sets: lockstep_layout.h, with their carves)
 struct LsK { LockstepParams P; LsWs w; };
 
 __device__ __forceinline__ int ls_lane() { return threadIdx.x & 63; }
@@ -587,7 +584,6 @@ LS_KERNEL_PAIR(store_m)
 // in with the classification (step_rules.h adjoint_active: the text k_batch_adjoint and EAdjClass call), the progress rule per problem (term_rules.h
 // recurrence_ends: Engine::run_recurrence's), the unscaling and the residual of the unregularised system, the transposes out and the gradients at the
 // stored entries.  Extra block vectors: the unscaled x, dx, r_x (n) and y, dy, r_y (m) and the row codes (ints, packed like iw).
-struct LsAdjWs { double *ax, *gdx, *rx, *ay, *gdy, *ry; int *code; };
 struct LsAK { LockstepAdjointParams P; LsWs w; LsAdjWs a; };
 enum LsAdjSlot { AS_ACT = PS_BN /* sum: active rows (before the first k_ls_rhs) */, AS_RM = PS_M0 /* max, after the last step: */, AS_GM, AS_RN, AS_GN };
 
@@ -820,7 +816,6 @@ __global__ __launch_bounds__(256) void k_ls_adj_grad(LsAK k) {
 // normal-cone projection against the problem's own bounds (k_ls_pol_cone), the accept test against the record (k_ls_pol_accept: term_info,
 // polish_accept) and, for a rejected problem, the ADMM x, y, z back (k_ls_pol_end).  A problem that does not take part is "terminated" all the way: no
 // kernel stores to its lane.  The saved vectors live in a work block of their own (backend.h lockstep_polish_ws_doubles).
-struct LsPolWs { double *x, *y, *z, *l, *u; };        // the scaled ADMM x (n) and y, z, l, u (m)
 struct LsPK { LockstepParams P; LsWs w; LsPolWs s; };
 
 // per problem: takes part iff SOLVED; IW_DONE becomes "not in the recurrence"; rho_bar = 1 / delta_eff with equality factor 1, flagged for k_ls_setrho / k_ls_minv
@@ -935,7 +930,7 @@ __global__ __launch_bounds__(256) void k_ls_pol_end(LsPK k, double secs) {
 // on it) and p = Minv r_0 with Minv = 1 / D0 (k_lw_d0), then  g = A_L p  (k_lw_prod: column blocks, [GC][r][64] partials),  h = S^-1 g  (k_lw_h: the
 // partials folded in block order, rows of h spread over workgroups and waves),  x~ += p - Minv A_L' h  (k_lw_x), k_ls_upd.
 // The dense rows in the row passes over A: ls_rows gives a wave a strip of ROWS, so a row with thousands of entries is one wave's serial walk.  The passes
-// (k_ls_initz, k_ls_upd, k_ls_resm) therefore run on a VIEW of A (LockstepDirectParams::Av) in which long row a is the single entry 1.0 at column n + a,
+// (k_ls_initz, k_ls_upd, k_ls_resm) therefore run on a VIEW of A (LockstepDirectView::Av) in which long row a is the single entry 1.0 at column n + a,
 // and the block vectors x, x~, dx carry r more rows: (A_L x)_a, (A_L x~)_a, (A_L dx)_a.  x~'s rows follow k_wbz's identity  A_L x~ += h ./ rho_L  (A_L of
 // the update is g - (S - diag(1 / rho_L)) h = h ./ rho_L), x's and dx's follow by linearity from k_ls_upd's own elementwise loop (run over n + r rows); at
 // the start and in front of every residual pass the rows of x and x~ are recomputed from the products (k_lw_prod twice, k_lw_setl), so the carried
@@ -943,9 +938,7 @@ __global__ __launch_bounds__(256) void k_ls_pol_end(LsPK k, double secs) {
 // S_b is formed (k_lw_s) and inverted in place (k_lw_inv: one workgroup per problem, S_b in LDS, Gauss-Jordan without pivoting) at the start and for exactly
 // the problems whose rho_bar k_ls_decide has changed.  A pivot that is not positive and finite makes that problem's inverse NaN: its x~ and residuals
 // are NaN from the next iteration on and k_ls_decide ends it with OSQP_NON_CVX (term_rules.h: non-finite residuals); no other lane reads it.
-struct LwWs {
-  double *S, *pg, *pg2, *h;             // [r][r][64] S, then S^-1;  [GC][r][64] partials of A_L v (two sets);  [r][64]
-  int *fact;                            // [64] inversions of S per problem
+struct LwWs : LwVecs {                  // (S, pg, pg2, h, fact: lockstep_layout.h)
   const double *WT; const int *rows; const unsigned char *islong;
   int r, GC, cb;                        // long rows; column blocks and their width
 };
@@ -1127,8 +1120,7 @@ __global__ __launch_bounds__(256) void k_lwa_zero(LwK k) {
 //                  (k_lsm_cost); P *= ct, q *= ct (k_lsm_cost_apply).  Then Dinv, Einv, 1 / c and sigma on B's diagonal (k_lsm_finish).  Four launches per
 //                  iteration.  The scratch lives in block vectors that are dead before k_ls_load_*: dt in r, et in t, the problem's q in q.
 // The strips of rows are ls_rows' (from the row counts and the grid alone), so c's sum has a fixed order that depends on (n, m) only.
-struct LsMat {
-  double *Aval, *Bval, *D, *Dinv, *E, *Einv;
+struct LsMat : LsMatVecs {              // (Aval, Bval, D, Dinv, E, Einv: lockstep_layout.h)
   const double *Praw, *Araw;
   const int *Pm1, *Pm2, *AmA, *AmB, *Bdiag;
   int nzP, nzA;
@@ -1264,442 +1256,371 @@ __global__ __launch_bounds__(256) void k_lsm_finish(LsMK k) {
 }
 #undef IX
 
+// ---------------------------------------------------------------------------------------------------------------- driving
+// The pieces the four chunk functions below are made of, each written once.
+inline double ls_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+inline hipStream_t ls_stream(Dev &d, void *stream) {
+  HIP_CHECK(hipSetDevice(d.device));
+  return stream ? static_cast<hipStream_t>(stream) : st(d);
+}
+// What a chunk function holds while it runs: the stream, the launch count, the host's copy of the word block, its events.  The events are destroyed on
+// every way out (HIP_CHECK throws); the ones a chunk does not use are never created.
+struct LsRun {
+  struct Ev {
+    hipEvent_t e = nullptr;
+    ~Ev() { if (e) (void)hipEventDestroy(e); }
+    void record(hipStream_t s) { if (!e) HIP_CHECK(hipEventCreate(&e)); HIP_CHECK(hipEventRecord(e, s)); }
+  };
+  hipStream_t s;
+  const int *dword;                      // the chunk's word block on the device
+  int words[WD_COUNT];
+  long launches = 0;
+  double t_sync;                         // the host's clock when it last waited for the stream: the time the GPU's work is known to have taken
+  Ev e0, e1, em, ep0, ep1;               // the chunk; end of the matrix block's preparation; polish
+  LsRun(hipStream_t stream, const int *word, int count) : s(stream), dword(word), words{0, count, 0, 0, 0, 0, 0}, t_sync(ls_now()) {}
+  template <class K, class A, class... X> void gol(K kern, int grid, size_t lds, const A &a, X... x) { hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, a, x...); launches++; }
+  template <class K, class A, class... X> void go(K kern, int grid, const A &a, X... x) { gol(kern, grid, 0, a, x...); }
+  void fetch() { HIP_CHECK(hipMemcpyAsync(words, dword, sizeof(words), hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s)); t_sync = ls_now(); }
+  static float ms(const Ev &a, const Ev &b) { float v = 0.f; HIP_CHECK(hipEventElapsedTime(&v, a.e, b.e)); return v; }
+  // the end of a chunk: the last read of the words (with dfact: the direct route's inversion counts, summed into *nfact), the chunk's GPU ms
+  float finish(const int *dfact = nullptr, long *nfact = nullptr) {
+    int fact[W];
+    e1.record(s);
+    if (dfact) HIP_CHECK(hipMemcpyAsync(fact, dfact, sizeof(fact), hipMemcpyDeviceToHost, s));
+    fetch();
+    const float v = ms(e0, e1);
+    HIP_CHECK(hipGetLastError());
+    if (dfact) { *nfact = 0; for (int b = 0; b < W; b++) *nfact += fact[b]; }
+    return v;
+  }
+};
+
+// The kernels of the PCG route that come in two instantiations: on the handle's matrices, on the chunk's own ("matrices of a chunk")
+using LsKern = void (*)(LsK);
+struct LsPcgKernels {
+  LsKern load_n, load_m, minv, initz, rhs, t, kp, upd, resm, resn;
+  void (*decide)(LsK, int, int, int, int);
+  LsKern store_n, store_m;
+};
+constexpr LsPcgKernels kLsShared = {k_ls_load_n, k_ls_load_m, k_ls_minv, k_ls_initz, k_ls_rhs, k_ls_t, k_ls_kp, k_ls_upd, k_ls_resm, k_ls_resn, k_ls_decide, k_ls_store_n, k_ls_store_m};
+constexpr LsPcgKernels kLsOwnMat = {k_lsm_load_n, k_lsm_load_m, k_lsm_minv, k_lsm_initz, k_lsm_rhs, k_lsm_t, k_lsm_kp, k_lsm_upd, k_lsm_resm, k_lsm_resn, k_lsm_decide, k_lsm_store_n, k_lsm_store_m};
+
+// One PCG solve for every problem of the chunk: as many iterations as the previous solve needed (+ 1: est) are enqueued without synchronising; then the
+// host reads the words and goes on in groups of four while some problem's PCG is still running, up to cg_max.  The estimate decides how many launches
+// return at once, never how far a problem's PCG runs.
+void ls_pcg(LsRun &R, const LsPcgKernels &K, const LsK &k, int &est) {
+  const int G = k.w.G, cg_max = k.P.cg_max;
+  R.go(K.rhs, G, k);
+  R.go(k_ls_cginit, 1, k);
+  for (int it = 0, grp = est; it < cg_max; grp = 4) {
+    for (const int end = std::min(it + grp, cg_max); it < end; it++) {
+      if (k.P.m > 0) R.go(K.t, G, k);
+      R.go(K.kp, G, k); R.go(k_ls_cgalpha, 1, k); R.go(k_ls_cgupd, G, k); R.go(k_ls_cgbeta, 1, k); R.go(k_ls_cgp, G, k);
+    }
+    R.fetch();
+    if (!R.words[WD_CGANY]) break;
+  }
+  est = std::max(2, R.words[WD_CGIT] + 1);
+}
+
+// The recurrence of polish and of both adjoints: while a problem is live and below the step cap -- step() (the solve and k_ls_upd), the residuals (km:
+// what k_ls_resm reads A through), decide(), a read of the words.  Returns the steps taken.
+template <class Step, class Decide>
+int ls_recurrence(LsRun &R, const LsK &km, const LsK &kn, int max_steps, Step step, Decide decide) {
+  int steps = 0;
+  while (R.words[WD_LIVE] > 0 && steps < max_steps) {
+    steps++;
+    step();
+    if (km.P.m > 0) R.go(k_ls_resm, km.w.G, km);
+    R.go(k_ls_resn, kn.w.G, kn);
+    decide();
+    R.fetch();
+  }
+  return steps;
+}
+
+// The adjoint's launches after the recurrence that both backward passes share: the outputs the caller asked for
+void ls_adjoint_outputs(LsRun &R, const LsAK &ka, int tn, int tm) {
+  const LockstepAdjointParams &p = ka.P;
+  if (p.dq) R.go(k_ls_adj_out_n, tn, ka);
+  if (p.m > 0 && (p.dl || p.du)) R.go(k_ls_adj_out_m, tm, ka);
+  if (p.dP && p.nzP > 0) R.go(k_ls_adj_grad<true>, (p.nzP + 63) / 64, ka);
+  if (p.dA && p.nzA > 0) R.go(k_ls_adj_grad<false>, (p.nzA + 63) / 64, ka);
+}
+
+// The direct route's kernel arguments and launch groups.  k: what k_lw_* take.  Of this file's other kernels kb sees the handle as it is, kv reads A
+// through the view, ku does too and runs k_ls_upd's elementwise loop over n + r rows.
+struct LwRun {
+  LwK k;
+  LsK kb, kv, ku;
+  int G, r, GC;
+  size_t lds_inv, lds_h;
+  LwRun(const LockstepParams &p, const LockstepDirectView &v, const LsWs &w, const LwVecs &d) : k{p, w, {}}, kb{p, w} {
+    const int cb = lockstep_direct_colblock(p.n);
+    G = w.G; r = v.r; GC = lockstep_direct_colblocks(p.n);
+    static_cast<LwVecs &>(k.d) = d;
+    k.d.WT = v.WT; k.d.rows = v.rows; k.d.islong = v.islong; k.d.r = r; k.d.GC = GC; k.d.cb = cb;
+    kv = kb; kv.P.A = v.Av;
+    ku = kv; ku.P.n = p.n + r;
+    lds_inv = sizeof(double) * ((size_t)r * r + r); lds_h = sizeof(double) * (size_t)r * 64;
+    if (lds_inv > 64 * 1024) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_lw_inv), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_inv));
+  }
+  // rho from rho_bar, D0, S and its inverse (for the problems whose rho has just been set)
+  void factor(LsRun &R) const { R.go(k_ls_setrho, G, kb); R.go(k_lw_d0, G, k); R.go(k_lw_s, r * ((r + 7) / 8), k); R.gol(k_lw_inv, W, lds_inv, k); }
+  // x~ by the Woodbury formula, then the ADMM update
+  void solve(LsRun &R) const {
+    R.go(k_ls_rhs, G, kb);
+    R.go(k_lw_prod, GC, k, (const double *)k.w.p, k.d.pg);
+    R.gol(k_lw_h, (r + 15) / 16, lds_h, k);
+    R.gol(k_lw_x, G, lds_h, k);
+    R.go(k_ls_upd, G, ku);
+  }
+  // the rows n .. n + r - 1 of x and x~ from the products
+  void long_rows(LsRun &R, int start) const {
+    R.go(k_lw_prod, GC, k, (const double *)k.w.x, k.d.pg); R.go(k_lw_prod, GC, k, (const double *)k.w.xs, k.d.pg2); R.go(k_lw_setl, 1, k, start);
+  }
+};
+
 }  // namespace
 
 // One chunk of at most kLsW problems, from the transposes in to the transposes out, on `stream` (nullptr: the solver's); returns when the chunk's
-// results are in p.x / p.y / p.rec.  stat: {ADMM iterations of the slowest problem, PCG iterations summed, kernel launches, GPU ms}.
+// results are in p.x / p.y / p.rec.  The time limit is tested against the host's clock in every iteration.
+// stat: {ADMM iterations of the slowest problem, PCG iterations summed, kernel launches, GPU ms}.
 int lockstep_chunk(Dev &d, const LockstepParams &p, void *stream, double *stat) {
-  HIP_CHECK(hipSetDevice(d.device));
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : st(d);
-  const int n = p.n, m = p.m, G = lockstep_grid(n, m), tn = (n + 63) / 64, tm = (m + 63) / 64;
-  const size_t nW = (size_t)n * W, mW = (size_t)m * W;
+  const hipStream_t s = ls_stream(d, stream);
+  const int n = p.n, m = p.m, tn = (n + 63) / 64, tm = (m + 63) / 64;
+  const bool mat = p.mat_ws != nullptr, pol = p.polish && p.pol_ws;
   LsK k{p, {}};
-  LsWs &w = k.w;
-  double *c = p.ws;
-  auto take = [&c](size_t cnt) { double *r = c; c += cnt; return r; };
-  w.x = take(nW); w.xs = take(nW); w.r = take(nW); w.p = take(nW); w.Kp = take(nW); w.q = take(nW); w.Minv = take(nW); w.dx = take(nW);
-  w.z = take(mW); w.y = take(mW); w.t = take(mW); w.t2 = take(mW); w.l = take(mW); w.u = take(mW); w.rho = take(mW); w.zt = take(mW); w.dy = take(mW);
-  w.part = take((size_t)kLsSlots * G * W); w.parti = take((size_t)(tm > 0 ? tm : 1) * W); w.sc = take((size_t)kLsScal * W); w.rec = take((size_t)W * kBatchRec);
-  w.iw = reinterpret_cast<int *>(take((size_t)kLsInt * W / 2)); w.word = w.iw + IW_COUNT * W;
-  w.G = G;
-  if ((size_t)(c - p.ws) > lockstep_ws_doubles(n, m) || (size_t)(w.sc - p.ws) != lockstep_sc_offset(n, m)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  // per-problem matrices ("matrices of a chunk" above): the chunk's kernels read the matrix block in place of the handle's arrays
-  const bool mat = p.mat_ws != nullptr;
   LsMat mt{};
+  LsPK kq{p, {}, {}};
+  LsCursor c{p.ws}, cm{p.mat_ws}, cp{p.pol_ws};
+  if (!lockstep_layout(c, n, m, k.w, nullptr)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  // per-problem matrices ("matrices of a chunk" above): the chunk's kernels read the matrix block in place of the handle's arrays
   if (mat) {
     if (!d.Praw || !d.Araw || p.polish) return OSQP_FUNC_NOT_IMPLEMENTED;
-    const size_t aW = (size_t)p.A.nnz * W, bW = (size_t)p.B.nnz * W;
-    double *cm = p.mat_ws;
-    auto takem = [&cm](size_t cnt) { double *r = cm; cm += cnt; return r; };
-    mt.Aval = takem(aW); mt.Bval = takem(bW); mt.D = takem(nW); mt.Dinv = takem(nW); mt.E = takem(mW); mt.Einv = takem(mW);
-    if ((size_t)(cm - p.mat_ws) > lockstep_mat_ws_doubles(n, m, p.A.nnz, p.B.nnz)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+    if (!lockstep_mat_layout(cm, n, m, p.A.nnz, p.B.nnz, mt)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
     mt.Praw = d.Praw; mt.Araw = d.Araw; mt.Pm1 = d.Pm1; mt.Pm2 = d.Pm2; mt.AmA = d.AmA; mt.AmB = d.AmB; mt.Bdiag = d.Bdiag; mt.nzP = d.nzP; mt.nzA = d.nzA;
     k.P.A.val = mt.Aval; k.P.B.val = mt.Bval; k.P.D = mt.D; k.P.Dinv = mt.Dinv; k.P.E = mt.E; k.P.Einv = mt.Einv;
   }
-  long launches = 0;
-  auto go = [&](auto kern, int grid, auto... args) { hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, k, args...); launches++; };
-  hipEvent_t e0, e1;
-  HIP_CHECK(hipEventCreate(&e0)); HIP_CHECK(hipEventCreate(&e1));
-  HIP_CHECK(hipEventRecord(e0, s));
-  hipEvent_t em = nullptr;
+  if (pol && !lockstep_polish_layout(cp, n, m, kq.s)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  const LsWs &w = k.w;
+  const int G = w.G;
+  const LsPcgKernels &K = mat ? kLsOwnMat : kLsShared;
+  LsRun R(s, w.word, p.count);
+  R.e0.record(s);
   if (mat) {
     const LsMK km{k.P, w, mt};
-    auto gm = [&](auto kern, int grid) { hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, km); launches++; };
-    gm(k_lsm_begin, tn);
-    if (mt.nzA > 0) gm(k_lsm_asm<false>, (mt.nzA + 63) / 64);
-    if (mt.nzP > 0) gm(k_lsm_asm<true>, (mt.nzP + 63) / 64);
-    for (int it = 0; it < p.mat_iters; it++) { gm(k_lsm_norms, G); gm(k_lsm_scale, G); gm(k_lsm_cost, 1); gm(k_lsm_cost_apply, G); }
-    gm(k_lsm_finish, G);
-    HIP_CHECK(hipEventCreate(&em));
-    HIP_CHECK(hipEventRecord(em, s));
-    if (p.mat_stat) p.mat_stat[1] = (double)launches;
+    R.go(k_lsm_begin, tn, km);
+    if (mt.nzA > 0) R.go(k_lsm_asm<false>, (mt.nzA + 63) / 64, km);
+    if (mt.nzP > 0) R.go(k_lsm_asm<true>, (mt.nzP + 63) / 64, km);
+    for (int it = 0; it < p.mat_iters; it++) { R.go(k_lsm_norms, G, km); R.go(k_lsm_scale, G, km); R.go(k_lsm_cost, 1, km); R.go(k_lsm_cost_apply, G, km); }
+    R.go(k_lsm_finish, G, km);
+    R.em.record(s);
+    if (p.mat_stat) p.mat_stat[1] = (double)R.launches;
   }
-  auto now_s = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const double t_begin = now_s();
-  int words[WD_COUNT] = {0, p.count, 0, 0, 0, 0, 0};
-  auto fetch = [&]() { HIP_CHECK(hipMemcpyAsync(words, w.word, sizeof(words), hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s)); };
-  auto residuals = [&]() { if (m > 0) go(mat ? k_lsm_resm : k_ls_resm, G); go(mat ? k_lsm_resn : k_ls_resn, G); };
-  auto new_rho = [&]() { if (m > 0) go(k_ls_setrho, G); go(mat ? k_lsm_minv : k_ls_minv, G); };
+  const double t_begin = ls_now();
+  auto late_now = [&]() { return p.time_limit > 0 && ls_now() - t_begin > p.time_limit; };
+  auto residuals = [&]() { if (m > 0) R.go(K.resm, G, k); R.go(K.resn, G, k); };
+  auto new_rho = [&]() { if (m > 0) R.go(k_ls_setrho, G, k); R.go(K.minv, G, k); };
 
-  go(mat ? k_lsm_load_n : k_ls_load_n, tn);
-  if (m > 0) go(mat ? k_lsm_load_m : k_ls_load_m, tm);
-  go(k_ls_init, 1, m > 0 ? tm : 0);
+  R.go(K.load_n, tn, k);
+  if (m > 0) R.go(K.load_m, tm, k);
+  R.go(k_ls_init, 1, k, m > 0 ? tm : 0);
   new_rho();
-  if (m > 0) go(mat ? k_lsm_initz : k_ls_initz, G);
+  if (m > 0) R.go(K.initz, G, k);
   residuals();
-  go(mat ? k_lsm_decide : k_ls_decide, 1, 0, 0, 0, 1);
+  R.go(K.decide, 1, k, 0, 0, 0, 1);
   int iter = 0, cg_est = 4;
-  while (words[WD_LIVE] > 0 && iter < p.max_iter) {
+  while (R.words[WD_LIVE] > 0 && iter < p.max_iter) {
     iter++;
-    go(mat ? k_lsm_rhs : k_ls_rhs, G);
-    go(k_ls_cginit, 1);
-    // PCG: as many iterations as the previous ADMM iteration needed (+ 1) are enqueued without synchronising; then the host reads the words and
-    // goes on in groups of four while some problem's PCG is still running, up to cg_max_iter.  The estimate decides how many launches return at
-    // once, never how far a problem's PCG runs.
-    for (int it = 0, grp = cg_est; it < p.cg_max; grp = 4) {
-      for (const int end = std::min(it + grp, p.cg_max); it < end; it++) {
-        if (m > 0) go(mat ? k_lsm_t : k_ls_t, G);
-        go(mat ? k_lsm_kp : k_ls_kp, G); go(k_ls_cgalpha, 1); go(k_ls_cgupd, G); go(k_ls_cgbeta, 1); go(k_ls_cgp, G);
-      }
-      fetch();
-      if (!words[WD_CGANY]) break;
-    }
-    cg_est = std::max(2, words[WD_CGIT] + 1);
-    go(mat ? k_lsm_upd : k_ls_upd, G);
+    ls_pcg(R, K, k, cg_est);
+    R.go(K.upd, G, k);
     const int at_check = (p.check > 0 && iter % p.check == 0) || iter >= p.max_iter;
     const int at_rho = p.rho_interval > 0 && iter % p.rho_interval == 0;
-    const bool late = p.time_limit > 0 && std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - t_begin > p.time_limit;
+    const bool late = late_now();
     if (!at_check && !at_rho && !late) continue;
     residuals();
-    go(mat ? k_lsm_decide : k_ls_decide, 1, iter, late ? 1 : at_check, at_rho, late ? 2 : 0);
+    R.go(K.decide, 1, k, iter, late ? 1 : at_check, at_rho, late ? 2 : 0);
     if (at_rho && !late) new_rho();
-    if (at_check || late) fetch();
+    if (at_check || late) R.fetch();
   }
-  // polish ("polish of a chunk" above): driven like lockstep_adjoint_chunk's recurrence.  A chunk whose time limit has passed does not polish.
-  bool polished = false;
+  // polish ("polish of a chunk" above).  A chunk whose time limit has passed does not polish.
+  const bool polished = pol && !late_now();
   int pcg_admm = 0, pol_steps = 0, pol_pcg = 0, pol_att = 0;
   long pol_launches = 0;
-  hipEvent_t ep0 = nullptr, ep1 = nullptr;
-  if (p.polish && p.pol_ws && !(p.time_limit > 0 && now_s() - t_begin > p.time_limit)) {
-    polished = true;
-    const long launches0 = launches;
-    const double t_pol = now_s();
-    LsPK kq{p, w, {}};
-    double *cp = p.pol_ws;
-    auto takep = [&cp](size_t cnt) { double *r = cp; cp += cnt; return r; };
-    kq.s.x = takep(nW); kq.s.y = takep(mW); kq.s.z = takep(mW); kq.s.l = takep(mW); kq.s.u = takep(mW);
-    if ((size_t)(cp - p.pol_ws) > lockstep_polish_ws_doubles(n, m)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (polished) {
+    const long launches0 = R.launches;
+    const double t_pol = ls_now();
+    kq.w = w;
     LsK kp = k;                                        // what the ADMM's kernels take in the recurrence: alpha = 1, the recurrence's PCG rule
     kp.P.alpha = 1.0; kp.P.cg_max = p.pol_cg_max; kp.P.pcg_rel = p.pol_pcg_rel;
-    auto gk = [&](auto kern, int grid) { hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, kp); launches++; };
-    auto gq = [&](auto kern, int grid, auto... args) { hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, kq, args...); launches++; };
-    HIP_CHECK(hipEventCreate(&ep0)); HIP_CHECK(hipEventCreate(&ep1));
-    HIP_CHECK(hipEventRecord(ep0, s));
-    gq(k_ls_pol_begin, 1);
-    fetch();                                           // (WD_PCGSUM: still the ADMM's)
-    pcg_admm = words[WD_PCGSUM]; pol_att = words[WD_LIVE];
+    R.ep0.record(s);
+    R.go(k_ls_pol_begin, 1, kq);
+    R.fetch();                                         // (WD_PCGSUM: still the ADMM's)
+    pcg_admm = R.words[WD_PCGSUM]; pol_att = R.words[WD_LIVE];
     if (pol_att > 0) {
-      gq(k_ls_pol_class, G);
-      if (m > 0) gk(k_ls_setrho, G);
-      gk(k_ls_minv, G);
+      R.go(k_ls_pol_class, G, kq);
+      if (m > 0) R.go(k_ls_setrho, G, kp);
+      R.go(k_ls_minv, G, kp);
       int cg_pol = 4;
-      while (words[WD_LIVE] > 0 && pol_steps < kLsPolMaxSteps) {
-        pol_steps++;
-        gk(k_ls_rhs, G);
-        gk(k_ls_cginit, 1);
-        for (int it = 0, grp = cg_pol; it < kp.P.cg_max; grp = 4) {
-          for (const int end = std::min(it + grp, kp.P.cg_max); it < end; it++) {
-            if (m > 0) gk(k_ls_t, G);
-            gk(k_ls_kp, G); gk(k_ls_cgalpha, 1); gk(k_ls_cgupd, G); gk(k_ls_cgbeta, 1); gk(k_ls_cgp, G);
-          }
-          fetch();
-          if (!words[WD_CGANY]) break;
-        }
-        cg_pol = std::max(2, words[WD_CGIT] + 1);
-        gk(k_ls_upd, G);
-        if (m > 0) gk(k_ls_resm, G);
-        gk(k_ls_resn, G);
-        gq(k_ls_pol_decide, 1);
-        fetch();
-      }
-      pol_pcg = words[WD_PCGSUM];
-      if (m > 0) { gq(k_ls_pol_cone, G); gk(k_ls_resm, G); }
-      gk(k_ls_resn, G);
-      gq(k_ls_pol_accept, 1);
-      fetch();
-      gq(k_ls_pol_end, G, now_s() - t_pol);
+      pol_steps = ls_recurrence(R, kp, kp, kLsPolMaxSteps, [&]() { ls_pcg(R, kLsShared, kp, cg_pol); R.go(k_ls_upd, G, kp); }, [&]() { R.go(k_ls_pol_decide, 1, kq); });
+      pol_pcg = R.words[WD_PCGSUM];
+      if (m > 0) { R.go(k_ls_pol_cone, G, kq); R.go(k_ls_resm, G, kp); }
+      R.go(k_ls_resn, G, kp);
+      R.go(k_ls_pol_accept, 1, kq);
+      R.fetch();
+      R.go(k_ls_pol_end, G, kq, ls_now() - t_pol);
     }
-    HIP_CHECK(hipEventRecord(ep1, s));
-    pol_launches = launches - launches0;
+    R.ep1.record(s);
+    pol_launches = R.launches - launches0;
   }
-  go(mat ? k_lsm_store_n : k_ls_store_n, tn);
-  if (m > 0) go(mat ? k_lsm_store_m : k_ls_store_m, tm);
-  HIP_CHECK(hipEventRecord(e1, s));
-  fetch();
-  float ms = 0.f, pms = 0.f;
-  HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-  if (mat) { float mms = 0.f; HIP_CHECK(hipEventElapsedTime(&mms, e0, em)); HIP_CHECK(hipEventDestroy(em)); if (p.mat_stat) p.mat_stat[0] = mms; }
-  if (polished) { HIP_CHECK(hipEventElapsedTime(&pms, ep0, ep1)); HIP_CHECK(hipEventDestroy(ep0)); HIP_CHECK(hipEventDestroy(ep1)); }
-  HIP_CHECK(hipEventDestroy(e0)); HIP_CHECK(hipEventDestroy(e1));
-  HIP_CHECK(hipGetLastError());
+  R.go(K.store_n, tn, k);
+  if (m > 0) R.go(K.store_m, tm, k);
+  const float ms = R.finish(), pms = polished ? LsRun::ms(R.ep0, R.ep1) : 0.f;
+  if (mat && p.mat_stat) p.mat_stat[0] = LsRun::ms(R.e0, R.em);
   // (the chunk's statistics are the ADMM part's; polish's go to their own block)
-  if (stat) { stat[0] = iter; stat[1] = polished ? pcg_admm : words[WD_PCGSUM]; stat[2] = (double)(launches - pol_launches); stat[3] = ms - pms; }
+  if (stat) { stat[0] = iter; stat[1] = polished ? pcg_admm : R.words[WD_PCGSUM]; stat[2] = (double)(R.launches - pol_launches); stat[3] = ms - pms; }
   if (polished && p.pol_stat) {
     double *ps = p.pol_stat;
-    ps[0] = pol_att; ps[1] = words[WD_POLACC]; ps[2] = words[WD_POLREJ]; ps[3] = pol_steps; ps[4] = pol_pcg; ps[5] = (double)pol_launches; ps[6] = pms;
+    ps[0] = pol_att; ps[1] = R.words[WD_POLACC]; ps[2] = R.words[WD_POLREJ]; ps[3] = pol_steps; ps[4] = pol_pcg; ps[5] = (double)pol_launches; ps[6] = pms;
   }
   return OSQP_NO_ERROR;
 }
 
 // The backward pass of one chunk, from the transposes in to the transposes out, on `stream` (nullptr: the solver's); returns when the chunk's results are
-// there.  The work block is the forward's set followed by the adjoint's own vectors.  Driving as in lockstep_chunk: per step the PCG iterations the
-// previous step needed, plus one, are enqueued without synchronising, then groups of four; after every step the host reads the word block and ends the
-// chunk when no problem is live.  stat: {recurrence steps of the slowest problem, PCG iterations summed, kernel launches, GPU ms}.
+// there.  The work block is the forward's set followed by the adjoint's own vectors; after every step of the recurrence the host reads the word block
+// and ends the chunk when no problem is live.  stat: {recurrence steps of the slowest problem, PCG iterations summed, kernel launches, GPU ms}.
 int lockstep_adjoint_chunk(Dev &d, const LockstepAdjointParams &p, void *stream, double *stat) {
-  HIP_CHECK(hipSetDevice(d.device));
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : st(d);
-  const int n = p.n, m = p.m, G = lockstep_grid(n, m), tn = (n + 63) / 64, tm = (m + 63) / 64;
-  const size_t nW = (size_t)n * W, mW = (size_t)m * W;
+  const hipStream_t s = ls_stream(d, stream);
+  const int n = p.n, m = p.m, tn = (n + 63) / 64, tm = (m + 63) / 64;
   LsAK ka{p, {}, {}};
-  LsWs &w = ka.w;
-  double *c = p.ws;
-  auto take = [&c](size_t cnt) { double *r = c; c += cnt; return r; };
-  w.x = take(nW); w.xs = take(nW); w.r = take(nW); w.p = take(nW); w.Kp = take(nW); w.q = take(nW); w.Minv = take(nW); w.dx = take(nW);
-  w.z = take(mW); w.y = take(mW); w.t = take(mW); w.t2 = take(mW); w.l = take(mW); w.u = take(mW); w.rho = take(mW); w.zt = take(mW); w.dy = take(mW);
-  w.part = take((size_t)kLsSlots * G * W); w.parti = take((size_t)(tm > 0 ? tm : 1) * W); w.sc = take((size_t)kLsScal * W); w.rec = take((size_t)W * kBatchRec);
-  w.iw = reinterpret_cast<int *>(take((size_t)kLsInt * W / 2)); w.word = w.iw + IW_COUNT * W;
-  w.G = G;
-  if ((size_t)(c - p.ws) > lockstep_ws_doubles(n, m)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  c = p.ws + lockstep_ws_doubles(n, m);
-  LsAdjWs &a = ka.a;
-  a.ax = take(nW); a.gdx = take(nW); a.rx = take(nW); a.ay = take(mW); a.gdy = take(mW); a.ry = take(mW); a.code = reinterpret_cast<int *>(take((mW + 1) / 2));
-  if ((size_t)(c - p.ws) > lockstep_adjoint_ws_doubles(n, m)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  const LsK k{p, w};                                    // what the forward's kernels take: the base of the parameters, the same block vectors
-  long launches = 0;
-  auto go = [&](auto kern, int grid) { hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, k); launches++; };
-  auto goa = [&](auto kern, int grid) { hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, ka); launches++; };
-  hipEvent_t e0, e1;
-  HIP_CHECK(hipEventCreate(&e0)); HIP_CHECK(hipEventCreate(&e1));
-  HIP_CHECK(hipEventRecord(e0, s));
-  int words[WD_COUNT] = {0, p.count, 0, 0, 0, 0, 0};
-  auto fetch = [&]() { HIP_CHECK(hipMemcpyAsync(words, w.word, sizeof(words), hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s)); };
+  LsCursor c{p.ws};
+  if (!lockstep_layout(c, n, m, ka.w, &ka.a)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  const LsK k{p, ka.w};                                 // what the forward's kernels take: the base of the parameters, the same block vectors
+  const int G = k.w.G;
+  LsRun R(s, k.w.word, p.count);
+  R.e0.record(s);
 
-  goa(k_ls_adj_load_n, tn);
-  if (m > 0) { goa(k_ls_adj_load_m, tm); goa(k_ls_adj_class, G); }
-  goa(k_ls_adj_init, 1);
-  if (m > 0) go(k_ls_setrho, G);
-  go(k_ls_minv, G);
-  fetch();
-  int step = 0, cg_est = 4;
-  while (words[WD_LIVE] > 0 && step < p.max_steps) {
-    step++;
-    go(k_ls_rhs, G);
-    go(k_ls_cginit, 1);
-    for (int it = 0, grp = cg_est; it < p.cg_max; grp = 4) {
-      for (const int end = std::min(it + grp, p.cg_max); it < end; it++) {
-        if (m > 0) go(k_ls_t, G);
-        go(k_ls_kp, G); go(k_ls_cgalpha, 1); go(k_ls_cgupd, G); go(k_ls_cgbeta, 1); go(k_ls_cgp, G);
-      }
-      fetch();
-      if (!words[WD_CGANY]) break;
-    }
-    cg_est = std::max(2, words[WD_CGIT] + 1);
-    go(k_ls_upd, G);
-    if (m > 0) go(k_ls_resm, G);
-    go(k_ls_resn, G);
-    goa(k_ls_adj_decide, 1);
-    fetch();
-  }
-  goa(k_ls_adj_unscale, G);
-  if (m > 0) goa(k_ls_adj_resm, G);
-  goa(k_ls_adj_resn, G);
-  goa(k_ls_adj_final, 1);
-  if (p.dq) goa(k_ls_adj_out_n, tn);
-  if (m > 0 && (p.dl || p.du)) goa(k_ls_adj_out_m, tm);
-  if (p.dP && p.nzP > 0) goa(k_ls_adj_grad<true>, (p.nzP + 63) / 64);
-  if (p.dA && p.nzA > 0) goa(k_ls_adj_grad<false>, (p.nzA + 63) / 64);
-  HIP_CHECK(hipEventRecord(e1, s));
-  const int pcg_sum = words[WD_PCGSUM];
-  fetch();
-  float ms = 0.f;
-  HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-  HIP_CHECK(hipEventDestroy(e0)); HIP_CHECK(hipEventDestroy(e1));
-  HIP_CHECK(hipGetLastError());
-  if (stat) { stat[0] = step; stat[1] = pcg_sum; stat[2] = (double)launches; stat[3] = ms; }
+  R.go(k_ls_adj_load_n, tn, ka);
+  if (m > 0) { R.go(k_ls_adj_load_m, tm, ka); R.go(k_ls_adj_class, G, ka); }
+  R.go(k_ls_adj_init, 1, ka);
+  if (m > 0) R.go(k_ls_setrho, G, k);
+  R.go(k_ls_minv, G, k);
+  R.fetch();
+  int cg_est = 4;
+  const int step = ls_recurrence(R, k, k, p.max_steps, [&]() { ls_pcg(R, kLsShared, k, cg_est); R.go(k_ls_upd, G, k); }, [&]() { R.go(k_ls_adj_decide, 1, ka); });
+  R.go(k_ls_adj_unscale, G, ka);
+  if (m > 0) R.go(k_ls_adj_resm, G, ka);
+  R.go(k_ls_adj_resn, G, ka);
+  R.go(k_ls_adj_final, 1, ka);
+  ls_adjoint_outputs(R, ka, tn, tm);
+  const int pcg_sum = R.words[WD_PCGSUM];
+  const float ms = R.finish();
+  if (stat) { stat[0] = step; stat[1] = pcg_sum; stat[2] = (double)R.launches; stat[3] = ms; }
   return OSQP_NO_ERROR;
 }
 
 // One chunk of the DIRECT route ("lockstep DIRECT" above), from the transposes in to the transposes out, on `stream` (nullptr: the solver's).  A fixed
-// launch sequence without an inner convergence test: five launches per ADMM iteration (k_ls_rhs, k_lw_prod, k_lw_h, k_lw_x, k_ls_upd), enqueued back to
-// back; at a termination check the host reads the word block once.  The time limit is tested against the host's clock as of the last such read (in
-// between the host runs ahead of the GPU): a chunk past its limit ends at the iteration after the check that saw it, with OSQP_TIME_LIMIT_REACHED for the
-// problems still running.  stat: {ADMM iterations of the slowest problem, inversions of S summed over the problems, kernel launches, GPU ms}.
+// launch sequence without an inner convergence test: five launches per ADMM iteration (LwRun::solve), enqueued back to back; at a termination check the
+// host reads the word block once.  The time limit is tested against the host's clock as of the last such read (in between the host runs ahead of the
+// GPU): a chunk past its limit ends at the iteration after the check that saw it, with OSQP_TIME_LIMIT_REACHED for the problems still running.
+// stat: {ADMM iterations of the slowest problem, inversions of S summed over the problems, kernel launches, GPU ms}.
 int lockstep_direct_chunk(Dev &d, const LockstepDirectParams &p, void *stream, double *stat) {
-  HIP_CHECK(hipSetDevice(d.device));
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : st(d);
-  const int n = p.n, m = p.m, r = p.r, G = lockstep_grid(n, m), tn = (n + 63) / 64, tm = (m + 63) / 64;
+  const hipStream_t s = ls_stream(d, stream);
+  const int n = p.n, m = p.m, r = p.v.r, tn = (n + 63) / 64, tm = (m + 63) / 64;
   if (r < 1 || r > kWbMaxRows || m < 1) return OSQP_FUNC_NOT_IMPLEMENTED;
-  const int cb = lockstep_direct_colblock(n), GC = (n + cb - 1) / cb;
-  const size_t nW = (size_t)n * W, mW = (size_t)m * W, xW = (size_t)(n + r) * W;
-  LwK k{p, {}, {}};
-  LsWs &w = k.w;
-  double *c = p.ws;
-  auto take = [&c](size_t cnt) { double *q = c; c += cnt; return q; };
-  w.x = take(xW); w.xs = take(xW); w.dx = take(xW); w.r = take(nW); w.p = take(nW); w.q = take(nW); w.Minv = take(nW); w.Kp = nullptr;
-  w.z = take(mW); w.y = take(mW); w.t = take(mW); w.t2 = take(mW); w.l = take(mW); w.u = take(mW); w.rho = take(mW); w.zt = take(mW); w.dy = take(mW);
-  w.part = take((size_t)kLsSlots * G * W); w.parti = take((size_t)tm * W); w.sc = take((size_t)kLsScal * W); w.rec = take((size_t)W * kBatchRec);
-  w.iw = reinterpret_cast<int *>(take((size_t)kLsInt * W / 2)); w.word = w.iw + IW_COUNT * W;
-  w.G = G;
-  LwWs &x = k.d;
-  x.S = take((size_t)r * r * W); x.pg = take((size_t)GC * r * W); x.pg2 = take((size_t)GC * r * W); x.h = take((size_t)r * W);
-  x.fact = reinterpret_cast<int *>(take(W / 2));
-  x.WT = p.WT; x.rows = p.rows; x.islong = p.islong; x.r = r; x.GC = GC; x.cb = cb;
-  if ((size_t)(c - p.ws) > lockstep_direct_ws_doubles(n, m, r)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  const size_t lds_inv = sizeof(double) * ((size_t)r * r + r), lds_h = sizeof(double) * (size_t)r * 64;
-  if (lds_inv > 64 * 1024) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_lw_inv), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_inv));
-  // what this file's kernels take: the same block vectors; kv reads A through the view, ku does too and runs k_ls_upd's elementwise loop over n + r rows
-  const LsK kb{p, w};
-  LsK kv = kb; kv.P.A = p.Av;
-  LsK ku = kv; ku.P.n = n + r;
-  long launches = 0;
-  auto go = [&](auto kern, int grid, const LsK &a, auto... args) { hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, a, args...); launches++; };
-  auto gow = [&](auto kern, int grid, size_t lds, auto... args) { hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, k, args...); launches++; };
-  struct Ev { hipEvent_t e = nullptr; ~Ev() { if (e) (void)hipEventDestroy(e); } } ev0, ev1;      // (destroyed on every way out: HIP_CHECK throws)
-  HIP_CHECK(hipEventCreate(&ev0.e)); HIP_CHECK(hipEventCreate(&ev1.e));
-  const hipEvent_t e0 = ev0.e, e1 = ev1.e;
-  HIP_CHECK(hipEventRecord(e0, s));
-  auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const double t_begin = now();
-  double t_sync = t_begin;                 // the host's clock when it last waited for the stream: the time the GPU's work is known to have taken
-  int words[WD_COUNT] = {0, p.count, 0, 0, 0, 0, 0};
-  auto fetch = [&]() { HIP_CHECK(hipMemcpyAsync(words, w.word, sizeof(words), hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s)); t_sync = now(); };
-  auto long_rows = [&](int start) { gow(k_lw_prod, GC, 0, (const double *)w.x, x.pg); gow(k_lw_prod, GC, 0, (const double *)w.xs, x.pg2); gow(k_lw_setl, 1, 0, start); };
-  auto residuals = [&]() { go(k_ls_resm, G, kv); go(k_ls_resn, G, kb); };
-  auto new_rho = [&]() { go(k_ls_setrho, G, kb); gow(k_lw_d0, G, 0); gow(k_lw_s, r * ((r + 7) / 8), 0); gow(k_lw_inv, W, lds_inv); };
+  LsWs w;
+  LwVecs x;
+  LsCursor c{p.ws};
+  if (!lockstep_direct_layout(c, n, m, r, w, x, nullptr)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  const LwRun D(p, p.v, w, x);
+  const LsK &kb = D.kb, &kv = D.kv;
+  const int G = w.G;
+  LsRun R(s, w.word, p.count);
+  R.e0.record(s);
+  const double t_begin = R.t_sync;
+  auto residuals = [&]() { R.go(k_ls_resm, G, kv); R.go(k_ls_resn, G, kb); };
 
   HIP_CHECK(hipMemsetAsync(x.fact, 0, sizeof(int) * W, s));
-  go(k_ls_load_n, tn, kb);
-  go(k_ls_load_m, tm, kb);
-  go(k_ls_init, 1, kb, tm);
-  new_rho();
-  long_rows(1);
-  go(k_ls_initz, G, kv);
+  R.go(k_ls_load_n, tn, kb);
+  R.go(k_ls_load_m, tm, kb);
+  R.go(k_ls_init, 1, kb, tm);
+  D.factor(R);
+  D.long_rows(R, 1);
+  R.go(k_ls_initz, G, kv);
   residuals();
-  go(k_ls_decide, 1, kb, 0, 0, 0, 1);
+  R.go(k_ls_decide, 1, kb, 0, 0, 0, 1);
   int iter = 0;
-  while (words[WD_LIVE] > 0 && iter < p.max_iter) {
+  while (R.words[WD_LIVE] > 0 && iter < p.max_iter) {
     iter++;
-    go(k_ls_rhs, G, kb);
-    gow(k_lw_prod, GC, 0, (const double *)w.p, x.pg);
-    gow(k_lw_h, (r + 15) / 16, lds_h);
-    gow(k_lw_x, G, lds_h);
-    go(k_ls_upd, G, ku);
+    D.solve(R);
     const int at_check = (p.check > 0 && iter % p.check == 0) || iter >= p.max_iter;
     const int at_rho = p.rho_interval > 0 && iter % p.rho_interval == 0;
-    const bool late = p.time_limit > 0 && t_sync - t_begin > p.time_limit;      // (as of the last check: the host enqueues ahead of the GPU in between)
+    const bool late = p.time_limit > 0 && R.t_sync - t_begin > p.time_limit;    // (as of the last check: the host enqueues ahead of the GPU in between)
     if (!at_check && !at_rho && !late) continue;
-    long_rows(0);
+    D.long_rows(R, 0);
     residuals();
-    go(k_ls_decide, 1, kb, iter, late ? 1 : at_check, at_rho, late ? 2 : 0);
-    if (at_rho && !late) new_rho();
-    if (at_check || late) fetch();
+    R.go(k_ls_decide, 1, kb, iter, late ? 1 : at_check, at_rho, late ? 2 : 0);
+    if (at_rho && !late) D.factor(R);
+    if (at_check || late) R.fetch();
   }
-  go(k_ls_store_n, tn, kb);
-  go(k_ls_store_m, tm, kb);
-  HIP_CHECK(hipEventRecord(e1, s));
-  int fact[W];
-  HIP_CHECK(hipMemcpyAsync(fact, x.fact, sizeof(fact), hipMemcpyDeviceToHost, s));
-  fetch();
-  float ms = 0.f;
-  HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-  HIP_CHECK(hipGetLastError());
+  R.go(k_ls_store_n, tn, kb);
+  R.go(k_ls_store_m, tm, kb);
   long nfact = 0;
-  for (int b = 0; b < W; b++) nfact += fact[b];
-  if (stat) { stat[0] = iter; stat[1] = (double)nfact; stat[2] = (double)launches; stat[3] = ms; }
+  const float ms = R.finish(x.fact, &nfact);
+  if (stat) { stat[0] = iter; stat[1] = (double)nfact; stat[2] = (double)R.launches; stat[3] = ms; }
   return OSQP_NO_ERROR;
 }
 
 // The backward pass of one chunk on the DIRECT route, from the transposes in to the transposes out, on `stream` (nullptr: the solver's); returns when the
-// chunk's results are there.  The sequence is lockstep_adjoint_chunk's with lockstep_direct_chunk's solve in place of the PCG; the work block is the direct
-// forward's set followed by the adjoint's own vectors.  The classification's operand x~ = Dinv x sits in the block vector x~ (n + r rows; its last r
+// chunk's results are there.  The sequence is lockstep_adjoint_chunk's with LwRun's solve in place of the PCG; the work block is the direct forward's
+// set followed by the adjoint's own vectors.  The classification's operand x~ = Dinv x sits in the block vector x~ (n + r rows; its last r
 // from the products), so that k_ls_adj_class reads A through the view like every other row pass here; x, x~ and dx are zeroed over n + r rows afterwards.
 // rho is set, and S formed and inverted, once; a step is eleven launches and one read of the word block.  A pivot of S_b that is not positive and finite
 // leaves NaN iterates in that lane alone: its residual is not below the threshold and it ends with status 3.
 // stat: {recurrence steps of the slowest problem, inversions of S summed over the problems, kernel launches, GPU ms}.
 int lockstep_direct_adjoint_chunk(Dev &d, const LockstepDirectAdjointParams &p, void *stream, double *stat) {
-  HIP_CHECK(hipSetDevice(d.device));
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : st(d);
-  const int n = p.n, m = p.m, r = p.r, G = lockstep_grid(n, m), tn = (n + 63) / 64, tm = (m + 63) / 64;
+  const hipStream_t s = ls_stream(d, stream);
+  const int n = p.n, m = p.m, r = p.v.r, tn = (n + 63) / 64, tm = (m + 63) / 64;
   if (r < 1 || r > kWbMaxRows || m < 1) return OSQP_FUNC_NOT_IMPLEMENTED;
-  const int cb = lockstep_direct_colblock(n), GC = (n + cb - 1) / cb;
-  const size_t nW = (size_t)n * W, mW = (size_t)m * W, xW = (size_t)(n + r) * W;
-  LwK k{p, {}, {}};
-  LsWs &w = k.w;
-  double *c = p.ws;
-  auto take = [&c](size_t cnt) { double *q = c; c += cnt; return q; };
-  w.x = take(xW); w.xs = take(xW); w.dx = take(xW); w.r = take(nW); w.p = take(nW); w.q = take(nW); w.Minv = take(nW); w.Kp = nullptr;
-  w.z = take(mW); w.y = take(mW); w.t = take(mW); w.t2 = take(mW); w.l = take(mW); w.u = take(mW); w.rho = take(mW); w.zt = take(mW); w.dy = take(mW);
-  w.part = take((size_t)kLsSlots * G * W); w.parti = take((size_t)tm * W); w.sc = take((size_t)kLsScal * W); w.rec = take((size_t)W * kBatchRec);
-  w.iw = reinterpret_cast<int *>(take((size_t)kLsInt * W / 2)); w.word = w.iw + IW_COUNT * W;
-  w.G = G;
-  LwWs &x = k.d;
-  x.S = take((size_t)r * r * W); x.pg = take((size_t)GC * r * W); x.pg2 = take((size_t)GC * r * W); x.h = take((size_t)r * W);
-  x.fact = reinterpret_cast<int *>(take(W / 2));
-  x.WT = p.WT; x.rows = p.rows; x.islong = p.islong; x.r = r; x.GC = GC; x.cb = cb;
-  if ((size_t)(c - p.ws) > lockstep_direct_ws_doubles(n, m, r)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  c = p.ws + lockstep_direct_ws_doubles(n, m, r);
-  LsAK ka{p, w, {}};
-  LsAdjWs &a = ka.a;
-  a.ax = take(nW); a.gdx = take(nW); a.rx = take(nW); a.ay = take(mW); a.gdy = take(mW); a.ry = take(mW); a.code = reinterpret_cast<int *>(take((mW + 1) / 2));
-  if ((size_t)(c - p.ws) > lockstep_direct_adjoint_ws_doubles(n, m, r)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  const size_t lds_inv = sizeof(double) * ((size_t)r * r + r), lds_h = sizeof(double) * (size_t)r * 64;
-  if (lds_inv > 64 * 1024) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_lw_inv), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_inv));
-  // the forward's kernels as lockstep_direct_chunk calls them: kb as the handle is, kv through the view, ku through the view with n + r rows of x
-  const LsK kb{p, w};
-  LsK kv = kb; kv.P.A = p.Av;
-  LsK ku = kv; ku.P.n = n + r;
-  // the adjoint's: kl makes k_ls_adj_load_n put x~ = Dinv x where k_ls_adj_class, through the view (kc), will gather it -- the first n rows of the block
-  // vector x~ -- by exchanging the roles of p and x~ (the zeros then go to p, which k_ls_rhs overwrites)
+  LsAK ka{p, {}, {}};
+  LwVecs x;
+  LsCursor c{p.ws};
+  if (!lockstep_direct_layout(c, n, m, r, ka.w, x, &ka.a)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  const LsWs &w = ka.w;
+  const LwRun D(p, p.v, w, x);
+  const int G = w.G, GC = D.GC;
+  // the adjoint's own views: kl makes k_ls_adj_load_n put x~ = Dinv x where k_ls_adj_class, through the view (kc), will gather it -- the first n rows of the
+  // block vector x~ -- by exchanging the roles of p and x~ (the zeros then go to p, which k_ls_rhs overwrites)
   LsAK kl = ka; kl.w.p = w.xs; kl.w.xs = w.p;
-  LsAK kc = ka; kc.P.A = p.Av; kc.w.p = w.xs;
-  long launches = 0;
-  auto go = [&](auto kern, int grid, const LsK &q) { hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, q); launches++; };
-  auto goa = [&](auto kern, int grid, const LsAK &q) { hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, q); launches++; };
-  auto gow = [&](auto kern, int grid, size_t lds, auto... args) { hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, k, args...); launches++; };
-  struct Ev { hipEvent_t e = nullptr; ~Ev() { if (e) (void)hipEventDestroy(e); } } ev0, ev1;      // (destroyed on every way out: HIP_CHECK throws)
-  HIP_CHECK(hipEventCreate(&ev0.e)); HIP_CHECK(hipEventCreate(&ev1.e));
-  const hipEvent_t e0 = ev0.e, e1 = ev1.e;
-  HIP_CHECK(hipEventRecord(e0, s));
-  int words[WD_COUNT] = {0, p.count, 0, 0, 0, 0, 0};
-  auto fetch = [&]() { HIP_CHECK(hipMemcpyAsync(words, w.word, sizeof(words), hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s)); };
-  auto long_rows_of = [&](double *v) { gow(k_lw_prod, GC, 0, (const double *)v, x.pg); gow(k_lwa_setl, (r + 3) / 4, 0, v); };
+  LsAK kc = ka; kc.P.A = p.v.Av; kc.w.p = w.xs;
+  LsRun R(s, w.word, p.count);
+  R.e0.record(s);
+  auto long_rows_of = [&](double *v) { R.go(k_lw_prod, GC, D.k, (const double *)v, x.pg); R.go(k_lwa_setl, (r + 3) / 4, D.k, v); };
 
   HIP_CHECK(hipMemsetAsync(x.fact, 0, sizeof(int) * W, s));
-  goa(k_ls_adj_load_n, tn, kl);
-  goa(k_ls_adj_load_m, tm, ka);
+  R.go(k_ls_adj_load_n, tn, kl);
+  R.go(k_ls_adj_load_m, tm, ka);
   long_rows_of(w.xs);
-  goa(k_ls_adj_class, G, kc);
-  goa(k_ls_adj_init, 1, ka);
-  gow(k_lwa_zero, G, 0);
-  go(k_ls_setrho, G, kb); gow(k_lw_d0, G, 0); gow(k_lw_s, r * ((r + 7) / 8), 0); gow(k_lw_inv, W, lds_inv);
-  fetch();
-  int step = 0;
-  while (words[WD_LIVE] > 0 && step < p.max_steps) {
-    step++;
-    go(k_ls_rhs, G, kb);
-    gow(k_lw_prod, GC, 0, (const double *)w.p, x.pg);
-    gow(k_lw_h, (r + 15) / 16, lds_h);
-    gow(k_lw_x, G, lds_h);
-    go(k_ls_upd, G, ku);
-    gow(k_lw_prod, GC, 0, (const double *)w.x, x.pg); gow(k_lw_prod, GC, 0, (const double *)w.xs, x.pg2); gow(k_lw_setl, 1, 0, 0);
-    go(k_ls_resm, G, kv);
-    go(k_ls_resn, G, kb);
-    goa(k_ls_adj_decide, 1, ka);
-    fetch();
-  }
-  goa(k_ls_adj_unscale, G, ka);
+  R.go(k_ls_adj_class, G, kc);
+  R.go(k_ls_adj_init, 1, ka);
+  R.go(k_lwa_zero, G, D.k);
+  D.factor(R);
+  R.fetch();
+  const int step = ls_recurrence(R, D.kv, D.kb, p.max_steps, [&]() { D.solve(R); D.long_rows(R, 0); }, [&]() { R.go(k_ls_adj_decide, 1, ka); });
+  R.go(k_ls_adj_unscale, G, ka);
   long_rows_of(w.x);
-  goa(k_ls_adj_resm, G, kc);
-  goa(k_ls_adj_resn, G, ka);
-  goa(k_ls_adj_final, 1, ka);
-  if (p.dq) goa(k_ls_adj_out_n, tn, ka);
-  if (p.dl || p.du) goa(k_ls_adj_out_m, tm, ka);
-  if (p.dP && p.nzP > 0) goa(k_ls_adj_grad<true>, (p.nzP + 63) / 64, ka);
-  if (p.dA && p.nzA > 0) goa(k_ls_adj_grad<false>, (p.nzA + 63) / 64, ka);
-  HIP_CHECK(hipEventRecord(e1, s));
-  int fact[W];
-  HIP_CHECK(hipMemcpyAsync(fact, x.fact, sizeof(fact), hipMemcpyDeviceToHost, s));
-  fetch();
-  float ms = 0.f;
-  HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-  HIP_CHECK(hipGetLastError());
+  R.go(k_ls_adj_resm, G, kc);
+  R.go(k_ls_adj_resn, G, ka);
+  R.go(k_ls_adj_final, 1, ka);
+  ls_adjoint_outputs(R, ka, tn, tm);
   long nfact = 0;
-  for (int b = 0; b < W; b++) nfact += fact[b];
-  if (stat) { stat[0] = step; stat[1] = (double)nfact; stat[2] = (double)launches; stat[3] = ms; }
+  const float ms = R.finish(x.fact, &nfact);
+  if (stat) { stat[0] = step; stat[1] = (double)nfact; stat[2] = (double)R.launches; stat[3] = ms; }
   return OSQP_NO_ERROR;
 }
 
-// the values of the view of A (LockstepDirectParams::Av) from A's current ones, on `stream` (nullptr: the solver's)
+// the values of the view of A (LockstepDirectView::Av) from A's current ones, on `stream` (nullptr: the solver's)
 int lockstep_direct_values(Dev &d, int nv, const int *src, double *out, void *stream) {
   HIP_CHECK(hipSetDevice(d.device));
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : st(d);

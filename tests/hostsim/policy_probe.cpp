@@ -1,6 +1,7 @@
 // TEST INFRASTRUCTURE: the rules of osqp-python_amd/csrc/policy.h (one text, compiled for the host driver and for the device's k_decide)
 // and of term_rules.h (the termination / rho / record rules it shares with the batch kernels) behind a C ABI, so that the CPU tier can exercise
-// each rule on its own (tests/test_policy_rules.py, tests/test_batch_rules.py).  Never part of the product.
+// each rule on its own (tests/test_policy_rules.py, tests/test_batch_rules.py); and the layout of the lockstep routes' work blocks (lockstep_layout.h, which
+// backend.h includes; tests/test_lockstep_layout.py).  Never part of the product.
 #include <cstring>
 #include <string>
 
@@ -123,7 +124,71 @@ void br_record(double *rc, int status, int iter, double obj, double prim_res, do
 }
 double br_out_x(int status, int unscaled, int scaling, double Dj, double xj, double dxj) { return batch_out_x(status, unscaled, scaling, Dj, xj, dxj); }
 double br_out_y(int status, int unscaled, int scaling, double cinv, double Ei, double yi, double dyi) { return batch_out_y(status, unscaled, scaling, cinv, Ei, yi, dyi); }
+
+// ---- lockstep_layout.h: the work blocks of a lockstep chunk as the drivers carve them (tests/test_lockstep_layout.py).  which: 0 forward, 1 adjoint
+// (forward's block, then the adjoint's vectors), 2 direct forward, 3 direct adjoint, 4 polish, 5 matrix block.  base: nullptr for the counting cursor.
+// ranges: (offset, doubles) of every range in carve order (at most kLayoutRanges);  info: end of the carve, fits (0 / 1), offset of the scalar state
+// (which <= 3).  Returns the number of ranges.
+constexpr int kLayoutRanges = 48;
+int ll_carve(int which, double *base, int n, int m, int r, int nzA, int nzB, size_t *ranges, size_t *info) {
+  LsCursor c; c.base = base; c.log = ranges;
+  LsWs w; LsAdjWs a; LwVecs d; LsPolWs s; LsMatVecs t;
+  bool fits = false;
+  switch (which) {
+    case 0: fits = lockstep_layout(c, n, m, w, nullptr); break;
+    case 1: fits = lockstep_layout(c, n, m, w, &a); break;
+    case 2: fits = lockstep_direct_layout(c, n, m, r, w, d, nullptr); break;
+    case 3: fits = lockstep_direct_layout(c, n, m, r, w, d, &a); break;
+    case 4: fits = lockstep_polish_layout(c, n, m, s); break;
+    default: fits = lockstep_mat_layout(c, n, m, nzA, nzB, t); break;
+  }
+  info[0] = c.off; info[1] = fits ? 1 : 0;
+  if (which <= 3) { LsCursor c2; LsWs w2; info[2] = lockstep_carve_base(c2, w2, n, m, which >= 2 ? n + r : n, which < 2); }
+  return c.nlog;
 }
+size_t ll_size(int which, int n, int m, int r, int nzA, int nzB) {
+  switch (which) {
+    case 0: return lockstep_ws_doubles(n, m);
+    case 1: return lockstep_adjoint_ws_doubles(n, m);
+    case 2: return lockstep_direct_ws_doubles(n, m, r);
+    case 3: return lockstep_direct_adjoint_ws_doubles(n, m, r);
+    case 4: return lockstep_polish_ws_doubles(n, m);
+    default: return lockstep_mat_ws_doubles(n, m, nzA, nzB);
+  }
+}
+size_t ll_sc_offset(int n, int m) { return lockstep_sc_offset(n, m); }
+int ll_const(int which) { const int v[] = {kLsW, kLsSlots, kLsScal, kLsInt, kLsMatScalC, kBatchRec, kLayoutRanges}; return v[which]; }
+int ll_grid(int n, int m) { return lockstep_grid(n, m); }
+int ll_colblocks(int n) { return lockstep_direct_colblocks(n); }
+}
+
+// Stand-alone form of the layout probe (-DLAYOUT_PROBE_MAIN: g++ -fsanitize=address,undefined of this file alone): every carve over the test's grid, once
+// with the counting cursor and once over a heap block of exactly the size function's doubles, whose every range is written at both ends.
+#ifdef LAYOUT_PROBE_MAIN
+#include <cstdio>
+int main() {
+  const int ns[] = {1, 63, 64, 65, 400, 8193}, ms[] = {0, 1, 64, 65, 800}, rs[] = {1, 2, 128};
+  long carves = 0, ranges = 0;
+  for (int n : ns) for (int m : ms) for (int r : rs) for (int which = 0; which < 6; which++) {
+    if ((which == 2 || which == 3) && m < 1) continue;            // (the direct drivers decline m < 1)
+    const int nzA = 3 * m, nzB = 3 * m + 2 * n;
+    size_t cnt[2 * kLayoutRanges], got[2 * kLayoutRanges], info[3], info2[3];
+    const int k = ll_carve(which, nullptr, n, m, r, nzA, nzB, cnt, info);
+    const size_t size = ll_size(which, n, m, r, nzA, nzB);
+    if (!info[1] || info[0] > size) { std::printf("carve %d n %d m %d r %d: end %zu > size %zu\n", which, n, m, r, info[0], size); return 1; }
+    double *block = new double[size];
+    if (ll_carve(which, block, n, m, r, nzA, nzB, got, info2) != k || info2[0] != info[0]) { std::printf("carve %d: the two cursors differ\n", which); return 1; }
+    for (int q = 0; q < k; q++) {
+      if (got[2 * q] != cnt[2 * q] || got[2 * q + 1] != cnt[2 * q + 1]) { std::printf("carve %d range %d: the two cursors differ\n", which, q); return 1; }
+      if (got[2 * q + 1]) { block[got[2 * q]] = 1.0; block[got[2 * q] + got[2 * q + 1] - 1] = 2.0; }
+    }
+    delete[] block;
+    carves++; ranges += k;
+  }
+  std::printf("layout probe: %ld carves, %ld ranges, no finding\n", carves, ranges);
+  return 0;
+}
+#endif
 
 // Stand-alone form (-DPOLICY_PROBE_MAIN: g++ -fsanitize=address,undefined of this file alone): br_ctl_check and br_rel_kkt on a few blocks, both passes,
 // m == 0 and zero norms included; prints what it got and returns 0.

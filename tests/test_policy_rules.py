@@ -12,7 +12,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, 'tests', 'hostsim', 'policy_probe.cpp')
 OUT = os.path.join(ROOT, 'tests', '_build', 'libpolicy_probe.so')
-DEPS = [SRC] + [os.path.join(ROOT, 'osqp-python_amd', 'csrc', h) for h in ('policy.h', 'term_rules.h', 'step_rules.h', 'backend.h', 'band_ldl.h')]
+DEPS = [SRC] + [os.path.join(ROOT, 'osqp-python_amd', 'csrc', h) for h in ('policy.h', 'term_rules.h', 'step_rules.h', 'backend.h', 'lockstep_layout.h', 'band_ldl.h')]
 
 
 @pytest.fixture(scope='module')

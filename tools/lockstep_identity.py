@@ -1,0 +1,125 @@
+#!/usr/bin/env python3
+"""Bit identity of the lockstep routes between two builds of the engine: what a change of the host drivers (lockstep_hip.hip's chunk functions,
+Engine::run_lockstep*) must leave exactly as it was.
+
+--dump FILE runs, with fixed seeds and no time limit, on problems.banded_qp(400, window=40) at B = 70 and eps 1e-8 (one full chunk and a ragged one):
+the forward route, the forward with polishing, the forward with per-element Px / Ax, the adjoint; on problems.portfolio_qp(200, 10) and (600, 4) at
+B = 70: the direct forward and the direct adjoint (a handle the direct route declines -- (200, 10): no dense row -- is kept as its return code); and the m = 0 tridiagonal case at n = 900, B = 3, with polish.  Every returned array and every *_last_record
+field except the timings goes into an .npz.  --compare A B exits non-zero unless every array is equal (NaNs in the same places) and every record field
+is equal: kernel launches, iteration / step counts, PCG iterations, inversions, polish counts, workspace bytes.
+
+    python tools/lockstep_identity.py --dump prof_out/identity_this.npz          (OSQP_HIP_LIBRARY selects the other build)
+    python tools/lockstep_identity.py --compare prof_out/identity_parent.npz prof_out/identity_this.npz
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+import scipy.sparse as sp
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, 'osqp-python_amd'))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tools'))
+
+TIMINGS = ('gpu_ms', 'seconds', 'prepare_gpu_ms')
+REC_SECONDS = 9          # column of a batch record that holds the polish seconds
+
+
+def handle(P, q, A, l, u, **kw):
+    import osqp_amd
+    s = osqp_amd.OSQP(algebra='hip')
+    st = dict(verbose=False, eps_abs=1e-8, eps_rel=1e-8, max_iter=20000, warm_starting=False)
+    st.update(kw)
+    s.setup(P, q, A, l, u, **st)
+    return s._solver
+
+
+def dump(path):
+    import problems
+    from lockstep_mat_bench import batch
+    out = {}
+
+    def keep(tag, arrays, record):
+        for k, v in arrays.items():
+            out['%s/%s' % (tag, k)] = np.asarray(v)
+        for k, v in record.items():
+            if k not in TIMINGS:
+                out['%s/last.%s' % (tag, k)] = np.float64(v)
+
+    def fwd(x, y, rec):
+        rec = rec.copy(); rec[:, REC_SECONDS] = 0.0          # (wall time of the polish)
+        return dict(x=x, y=y, rec=rec)
+
+    B = 70
+    P, q, A, l, u = problems.banded_qp(400, window=40)
+    A = sp.csc_matrix(A); A.sort_indices()
+    Px, Ax, Q, L, U = batch(P, q, A, l, u, B)
+    e = handle(P, q, A, l, u)
+    x, y, rec = e.hip_batch_solve_lockstep(q=Q, l=L, u=U)
+    keep('forward', fwd(x, y, rec), e.lockstep_last_record())
+    dx = x - 0.1 * np.random.default_rng(2).standard_normal(x.shape)
+    dy = 0.1 * np.random.default_rng(4).standard_normal(y.shape)
+    keep('adjoint', e.hip_batch_adjoint_lockstep(x, y, dx, dy, l=L, u=U), e.lockstep_adjoint_last_record())
+    xm, ym, recm = e.hip_batch_solve_lockstep(q=Q, l=L, u=U, Px=Px, Ax=Ax)
+    keep('mat', fwd(xm, ym, recm), e.lockstep_mat_last_record())
+    keep('mat_base', {}, e.lockstep_last_record())
+    e = handle(P, q, A, l, u, polishing=True)
+    keep('polish', fwd(*e.hip_batch_solve_lockstep(q=Q, l=L, u=U)), e.lockstep_last_record())
+    keep('polish_part', {}, e.lockstep_polish_last_record())
+
+    # portfolio_qp(200, 10) has no row past kLongRow entries, so the handle is no Woodbury one and the direct route declines it: the answer is what is kept.
+    # portfolio_qp(600, 4) (the GPU suites' shape: r = 5) is the handle the direct drivers run on.
+    for na, k in ((200, 10), (600, 4)):
+        tag = 'direct_%d_%d' % (na, k)
+        P, q, A, l, u = problems.portfolio_qp(na, k)
+        rng = np.random.default_rng(1)
+        Q = np.stack([np.concatenate([-rng.standard_normal(na), np.zeros(k)]) for _ in range(B)])
+        e = handle(P, q, A, l, u, max_iter=50000)
+        try:
+            x, y, rec = e.hip_batch_solve_lockstep_direct(q=Q)
+        except ValueError as err:
+            keep(tag, dict(declined=err.code), {})
+            print('%s: declined (%s)' % (tag, err.code))
+            continue
+        keep(tag, fwd(x, y, rec), e.lockstep_direct_last_record())
+        dx = x - 0.1 * np.random.default_rng(2).standard_normal(x.shape)
+        keep(tag + '_adjoint', e.hip_batch_adjoint_lockstep_direct(x, y, dx), e.lockstep_direct_adjoint_last_record())
+
+    n = 900
+    rng = np.random.default_rng(3)
+    d = 1.0 + rng.random(n)
+    off = 0.3 * rng.standard_normal(n - 1)
+    P = sp.diags([off, d + 1.0, off], [-1, 0, 1], format='csc')
+    q = rng.standard_normal(n)
+    Q = np.stack([q + 0.1 * b * rng.standard_normal(n) for b in range(3)])
+    e = handle(P, q, sp.csc_matrix((0, n)), np.zeros(0), np.zeros(0), polishing=True, max_iter=4000, check_termination=25)
+    keep('m0', fwd(*e.hip_batch_solve_lockstep(q=Q)), e.lockstep_last_record())
+    keep('m0_polish_part', {}, e.lockstep_polish_last_record())
+
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    np.savez(path, **out)
+    print('%d entries -> %s' % (len(out), path))
+
+
+def compare(pa, pb):
+    a, b = np.load(pa), np.load(pb)
+    bad = sorted(set(a.files) ^ set(b.files))
+    for k in sorted(set(a.files) & set(b.files)):
+        if a[k].shape != b[k].shape or not np.array_equal(a[k], b[k], equal_nan=True):
+            bad.append(k)
+    for k in bad:
+        print('DIFFERS: %s' % k)
+    print('%d entries compared, %d differences' % (len(set(a.files) | set(b.files)), len(bad)))
+    return 1 if bad else 0
+
+
+if __name__ == '__main__':
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--dump', metavar='FILE')
+    ap.add_argument('--compare', nargs=2, metavar=('A', 'B'))
+    args = ap.parse_args()
+    if args.dump:
+        dump(args.dump)
+    sys.exit(compare(*args.compare) if args.compare else 0)
