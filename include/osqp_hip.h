@@ -632,6 +632,30 @@ typedef struct {
   OSQPFloat minpiv;                /* out (op 2) */
 } OSQPHipDenseTest;
 OSQPInt osqp_hip_test_dense(OSQPSolver *solver, OSQPHipDenseTest *t);
+/* Test hook (used by tests/ only): the padded band of the batch path's direct solve (csrc/band_ldl.h) on the CALLER's matrix, in ONE workgroup of
+   `threads` threads (64 or 256; guard = 1, the adjoint's pivot rule with pivot_floor, exists with 256 only -- the three forms the product runs):
+   band_clear, the caller's entries scattered at band_slot(), band_factor, band_solve once per right-hand side, on the solver's stream, synchronous.
+     band   [n (bw + 1)]  band[c (bw + 1) + k] = K[c + k][c], lower triangle; entries with c + k >= n are never read
+     perm   [n]           position in the band's order -> variable (a permutation of 0 .. n-1)
+     rhs    [nrhs n]      right-hand sides in the caller's variable order, 0 <= nrhs <= 8
+     x      [nrhs n + 16] in/out: copied to the device first and back whole, so a cell the kernel did not write keeps the caller's value
+     image  [band_doubles(n, bw) = 8 + roundup8(n) (bw + 8) + 64]  out: the band's whole LDS allocation from its first double (front padding, columns,
+                          slack) as it stands after the last substitution: unit-lower L^ at the slots, zeros everywhere else
+     dinv   [n]           out: 1 / D
+     bad                  out: band_factor's result (guard = 1: a pivot was replaced)
+   Everything is checked before anything is launched -- n >= 1, 0 <= bw <= min(56, n - 1), threads / guard / nrhs as above, perm a permutation, every
+   length exactly as listed, band + two vectors within the product's 144 KB of LDS: anything else is OSQP_DATA_VALIDATION_ERROR. */
+typedef struct {
+  OSQPInt n, bw, threads, guard, nrhs;
+  OSQPFloat pivot_floor;
+  long long band_len, perm_len, rhs_len, x_len, image_len, dinv_len;
+  const OSQPFloat *band;
+  const OSQPInt *perm;
+  const OSQPFloat *rhs;
+  OSQPFloat *x, *image, *dinv;
+  OSQPInt bad;                     /* out */
+} OSQPHipBandTest;
+OSQPInt osqp_hip_test_band(OSQPSolver *solver, OSQPHipBandTest *t);
 /* Weight of equality rows relative to inequality rows, rho_eq = factor * rho, used when equality and inequality rows are
    mixed (default 10; the reference's 1e3 is kept when every active row is an equality).  See engine.cpp (Engine::classify_constraints)
    classify_constraints() for the rationale.  Takes effect immediately (rho vector + preconditioner are rebuilt). */

@@ -719,6 +719,20 @@ void test_spmv(Dev &d, int which, const double *in_dev, double *out_dev);   // 0
 // lockstep_chunk: a backend without it still links, and the driver answers OSQP_FUNC_NOT_IMPLEMENTED.
 struct DenseProbe { int op, M, N, K; double alpha, beta; long as_i, as_k, bs_k, bs_j, cs_i, cs_j; const double *A, *B; double *C; };
 double test_dense(Dev &d, const DenseProbe &p) __attribute__((weak));
+// the band of band_ldl.h on the caller's DEVICE operands (include/osqp_hip.h osqp_hip_test_band, which has validated every field: nothing is checked
+// here): one workgroup of `threads` clears the band, scatters `band`, factors with `tri` (band_tri_pairs(bw)) and solves the nrhs right-hand sides into x;
+// image / dinv / bad receive the LDS image, 1 / D and band_factor's result.  Runs on d.stream and synchronises.  Weak like test_dense.
+struct BandProbe {
+  int n, bw, threads, guard, nrhs, ntri; double pivot_floor;
+  const double *band; const int *perm, *tri; const double *rhs; double *x, *image, *dinv; int *bad;
+};
+// LDS of the probe's workgroup (bytes): the band and two vectors of band_cols(n); 0: above the cap of the product's own kernels (batch_direct_lds_bytes)
+inline size_t test_band_lds_bytes(int n, int bw) {
+  if (n < 1 || n > 144 * 1024 / 8 || bw < 0 || bw > kBatchDirectMaxBw) return 0;
+  const size_t b = sizeof(double) * (band_doubles(n, bw) + (size_t)2 * band_cols(n));
+  return b <= 144 * 1024 ? b : 0;
+}
+int test_band(Dev &d, const BandProbe &p) __attribute__((weak));
 float time_kernel(Dev &d, int which, int reps);                             // mean ms per launch
 
 }  // namespace be

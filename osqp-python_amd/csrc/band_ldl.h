@@ -1,7 +1,8 @@
 // band_ldl.h -- the padded band of the small-QP batch path and the arithmetic on it: ONE text for the layout (host + device), the banded LDL'
 // factorisation and the wave-0 substitutions in their general form.  k_batch_admm (its ADMM system and, with POLISH, the polish system) and
 // k_batch_adjoint call the device part (HIP compilations only); be::batch_direct_lds_bytes, batch_adjoint_lds_bytes and
-// Engine::prepare_batch_direct size and address the band with the host part (plain C++: compiles under g++ with the rest of backend.h).
+// Engine::prepare_batch_direct size and address the band with the host part (plain C++: compiles under g++ with the rest of backend.h), which also
+// builds band_factor's pair list.  tests/test_gpu_band_kernels.py runs the device part on its own (k_test_band in batch_hip.hip) and pins the invariants.
 // Assembling a matrix into the band stays with each kernel.  One more reader of the invariants below lives outside this file: the
 // register-resident n <= 128 form of the substitutions in k_batch_admm (batch_hip.hip), whose two fetch lambdas carry the text of
 // band_fetch_fwd / band_fetch_bwd -- a change to the padding has to be made there as well.
@@ -17,6 +18,7 @@
 //   * after band_factor the diagonal slots are zero too (unit-lower L^ read as 0 there) and 1 / D lives in a vector of its own.
 #pragma once
 #include <stddef.h>
+#include <vector>
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #endif
@@ -30,6 +32,13 @@ constexpr int band_stride(int bw) { return bw + kBatchNB; }
 constexpr int band_cols(int n) { return (n + kBatchNB - 1) / kBatchNB * kBatchNB; }
 constexpr int band_slot(int bw, int c, int r) { return c * band_stride(bw) + (r - c); }
 constexpr size_t band_doubles(int n, int bw) { return (size_t)kBandFront + (size_t)band_cols(n) * (size_t)band_stride(bw) + (size_t)kBandSlack; }
+// the pairs (a | b << 8), 1 <= a <= b <= bw, of one elimination step's trailing update: band_factor's `tri` (Engine::prepare_batch_direct and the
+// diagnostic entry osqp_hip_test_band upload this list)
+inline std::vector<int> band_tri_pairs(int bw) {
+  std::vector<int> tri;
+  for (int a = 1; a <= bw; a++) for (int b = a; b <= bw; b++) tri.push_back(a | (b << 8));
+  return tri;
+}
 
 #if defined(__HIPCC__)
 // ---------------------------------------------------------------------------------------------------------------- device part

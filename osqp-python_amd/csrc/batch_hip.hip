@@ -1432,5 +1432,43 @@ int batch_solve(Dev &d, const BatchParams &p, void *stream) {
   return OSQP_NO_ERROR;
 }
 
+// ---- diagnostic entry (backend.h test_band, include/osqp_hip.h osqp_hip_test_band): band_ldl.h's functions, unchanged, on a test's matrix ----
+// One workgroup.  LDS: the band, then wbuf and dinv (band_cols(n) doubles each); right-hand sides and results stay in global memory.  The host has
+// validated every field (Engine::test_band).
+namespace {
+template <int kBB, bool GUARD>
+__global__ __launch_bounds__(kBB) void k_test_band(BandProbe P) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  const int n = P.n, bw = P.bw, tid = threadIdx.x, nimg = (int)band_doubles(n, bw), nband = n * (bw + 1);
+  double *Lb = sm + kBandFront, *wbuf = sm + nimg, *dinv = wbuf + band_cols(n);
+  band_clear<kBB>(Lb, n, bw);
+  for (int s_ = tid; s_ < nband; s_ += kBB) {
+    const int c = s_ / (bw + 1), k = s_ - c * (bw + 1);
+    if (c + k < n) Lb[band_slot(bw, c, c + k)] = P.band[s_];
+  }
+  __syncthreads();
+  const bool bad = band_factor<kBB, GUARD>(Lb, n, bw, dinv, P.tri, P.ntri, P.pivot_floor);
+  for (int r = 0; r < P.nrhs; r++) band_solve<kBB>(Lb, n, bw, dinv, P.perm, wbuf, P.rhs + (size_t)r * n, P.x + (size_t)r * n, [](int) {});
+  for (int s_ = tid; s_ < nimg; s_ += kBB) P.image[s_] = sm[s_];
+  for (int c = tid; c < n; c += kBB) P.dinv[c] = dinv[c];
+  if (tid == 0) *P.bad = bad ? 1 : 0;
+}
+}  // namespace
+
+int test_band(Dev &d, const BandProbe &p) {
+  if (hipSetDevice(d.device) != hipSuccess) return OSQP_ALGEBRA_LOAD_ERROR;
+  const size_t lds = test_band_lds_bytes(p.n, p.bw);
+  if (!lds) return OSQP_DATA_VALIDATION_ERROR;
+  using Kernel = void (*)(BandProbe);
+  const Kernel k = p.threads == 64 ? &k_test_band<64, false> : (p.guard ? &k_test_band<256, true> : &k_test_band<256, false>);
+  if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { (void)hipGetLastError(); return OSQP_FUNC_NOT_IMPLEMENTED; }
+  hipStream_t st = static_cast<hipStream_t>(d.stream);
+  hipLaunchKernelGGL(k, dim3(1), dim3(p.threads), lds, st, p);
+  hipError_t e = hipGetLastError();                    // (a refused launch) ...
+  if (e == hipSuccess) e = hipStreamSynchronize(st);   // ... or the kernel's own
+  if (e != hipSuccess) throw DeviceError(std::string("osqp_hip: band probe kernel failed: ") + hipGetErrorString(e));
+  return OSQP_NO_ERROR;
+}
+
 }  // namespace be
 }  // namespace osqp_hip

@@ -47,6 +47,7 @@ class Engine {
   int time_kernel(int which, int reps, double *ms);
   int test_spmv(int which, const double *in, double *out);
   int test_dense(OSQPHipDenseTest *t);
+  int test_band(OSQPHipBandTest *t);
   int trace_read(unsigned long long *out, int count);
   int get_scaling(double *D, double *E, double *c);
   int get_reordering(int *perm_cols, int *perm_rows) const;

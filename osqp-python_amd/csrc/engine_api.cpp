@@ -584,8 +584,7 @@ void Engine::prepare_batch_direct() {
     kp_row[p] = prods[p].row; kp_a[p] = prods[p].a; kp_b[p] = prods[p].b;
   }
   ke_ptr.push_back((int)prods.size());
-  std::vector<int> tri;
-  for (int a = 1; a <= bw; a++) for (int b = a; b <= bw; b++) tri.push_back(a | (b << 8));
+  const std::vector<int> tri = band_tri_pairs(bw);
   auto up = [&](const std::vector<int> &h) { int *p = dev_vec<int>(d_, h.size()); if (!h.empty()) be::h2d(d_, p, h.data(), sizeof(int) * h.size()); return p; };
   bd_.perm = up(order); bd_.bp_slot = up(bp_slot); bd_.ke_slot = up(ke_slot); bd_.ke_ptr = up(ke_ptr);
   bd_.kp_row = up(kp_row); bd_.kp_a = up(kp_a); bd_.kp_b = up(kp_b); bd_.tri = up(tri);
@@ -1547,6 +1546,47 @@ int Engine::test_dense(OSQPHipDenseTest *t) {
                          a.p + t->a_off, b.p + t->b_off, c.p + t->c_off};
   t->minpiv = be::test_dense(d_, p);
   be::d2h(d_, t->C, c.p, sizeof(double) * nc);
+  return OSQP_NO_ERROR;
+}
+int Engine::test_band(OSQPHipBandTest *t) {
+  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (!be::test_band) return OSQP_FUNC_NOT_IMPLEMENTED;
+  // everything the kernel indexes with is checked here: the kernel itself checks nothing
+  if (!t || t->n < 1 || t->bw < 0 || t->bw > kBatchDirectMaxBw || t->bw > t->n - 1 || t->nrhs < 0 || t->nrhs > 8) return OSQP_DATA_VALIDATION_ERROR;
+  if (!(t->threads == 64 || t->threads == 256) || !(t->guard == 0 || t->guard == 1) || (t->threads == 64 && t->guard == 1)) return OSQP_DATA_VALIDATION_ERROR;
+  if (!be::test_band_lds_bytes(t->n, t->bw)) return OSQP_DATA_VALIDATION_ERROR;                 // (also bounds n: every length below fits an int)
+  const int n = t->n, bw = t->bw, nrhs = t->nrhs;
+  const size_t nband = (size_t)n * (bw + 1), nx = (size_t)nrhs * n + 16, nimg = band_doubles(n, bw);
+  if (t->band_len != (long long)nband || t->perm_len != n || t->rhs_len != (long long)nrhs * n || t->x_len != (long long)nx || t->image_len != (long long)nimg || t->dinv_len != n)
+    return OSQP_DATA_VALIDATION_ERROR;
+  if (!t->band || !t->perm || (nrhs > 0 && !t->rhs) || !t->x || !t->image || !t->dinv) return OSQP_DATA_VALIDATION_ERROR;
+  std::vector<char> seen(n, 0);
+  for (int k = 0; k < n; k++) {
+    const int v = t->perm[k];
+    if (v < 0 || v >= n || seen[v]) return OSQP_DATA_VALIDATION_ERROR;
+    seen[v] = 1;
+  }
+  be::activate(d_);
+  const std::vector<int> tri = band_tri_pairs(bw);
+  struct Buf { Dev &d; void *p; ~Buf() { if (p) be::dfree(d, p); } };
+  Buf band{d_, dev_vec<double>(d_, nband)}, perm{d_, dev_vec<int>(d_, n)}, dtri{d_, dev_vec<int>(d_, tri.size())}, rhs{d_, dev_vec<double>(d_, (size_t)nrhs * n)};
+  Buf x{d_, dev_vec<double>(d_, nx)}, image{d_, dev_vec<double>(d_, nimg)}, dinv{d_, dev_vec<double>(d_, n)}, bad{d_, dev_vec<int>(d_, 1)};
+  be::h2d(d_, band.p, t->band, sizeof(double) * nband);
+  be::h2d(d_, perm.p, t->perm, sizeof(int) * n);
+  if (!tri.empty()) be::h2d(d_, dtri.p, tri.data(), sizeof(int) * tri.size());
+  if (nrhs > 0) be::h2d(d_, rhs.p, t->rhs, sizeof(double) * nrhs * n);
+  be::h2d(d_, x.p, t->x, sizeof(double) * nx);
+  const be::BandProbe p{n, bw, t->threads, t->guard, nrhs, (int)tri.size(), t->pivot_floor, static_cast<const double *>(band.p), static_cast<const int *>(perm.p),
+                        static_cast<const int *>(dtri.p), static_cast<const double *>(rhs.p), static_cast<double *>(x.p), static_cast<double *>(image.p),
+                        static_cast<double *>(dinv.p), static_cast<int *>(bad.p)};
+  const int st = be::test_band(d_, p);
+  if (st != OSQP_NO_ERROR) return st;
+  int hbad = 0;
+  be::d2h(d_, t->x, x.p, sizeof(double) * nx);
+  be::d2h(d_, t->image, image.p, sizeof(double) * nimg);
+  be::d2h(d_, t->dinv, dinv.p, sizeof(double) * n);
+  be::d2h(d_, &hbad, bad.p, sizeof(int));
+  t->bad = hbad;
   return OSQP_NO_ERROR;
 }
 int Engine::get_reordering(int *perm_cols, int *perm_rows) const {

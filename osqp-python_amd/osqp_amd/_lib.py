@@ -75,6 +75,12 @@ class DenseTestStruct(C.Structure):   # OSQPHipDenseTest, include/osqp_hip.h (sa
                 [('A', c_double_p), ('B', c_double_p), ('C', c_double_p), ('minpiv', C.c_double)])
 
 
+class BandTestStruct(C.Structure):    # OSQPHipBandTest, include/osqp_hip.h (same order)
+    _fields_ = ([(k, C.c_int) for k in ('n', 'bw', 'threads', 'guard', 'nrhs')] + [('pivot_floor', C.c_double)] +
+                [(k, C.c_longlong) for k in ('band_len', 'perm_len', 'rhs_len', 'x_len', 'image_len', 'dinv_len')] +
+                [('band', c_double_p), ('perm', c_int_p), ('rhs', c_double_p), ('x', c_double_p), ('image', c_double_p), ('dinv', c_double_p), ('bad', C.c_int)])
+
+
 SolverP = C.POINTER(SolverStruct)
 
 
@@ -123,6 +129,7 @@ PROTOTYPES = {
     'osqp_hip_trace_read': (C.c_int, [SolverP, C.POINTER(C.c_ulonglong), C.c_int]),
     'osqp_hip_test_spmv': (C.c_int, [SolverP, C.c_int, c_double_p, c_double_p]),
     'osqp_hip_test_dense': (C.c_int, [SolverP, C.POINTER(DenseTestStruct)]),
+    'osqp_hip_test_band': (C.c_int, [SolverP, C.POINTER(BandTestStruct)]),
     'osqp_hip_set_rho_eq_factor': (C.c_int, [SolverP, C.c_double]),
     'osqp_hip_default_policy': (None, [C.POINTER(PolicyStruct)]),
     'osqp_hip_set_default_policy': (None, [C.POINTER(PolicyStruct)]),

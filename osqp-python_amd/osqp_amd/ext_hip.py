@@ -340,6 +340,24 @@ class OSQPSolver:
         st = int(self._lib.osqp_hip_test_dense(self._p, C.byref(t)))
         return st, out, float(t.minpiv)
 
+    def hip_test_band(self, n, bw, band, perm, rhs=None, x=None, threads=256, guard=0, pivot_floor=0.0):
+        """The padded band of the batch path's direct solve on one matrix (osqp_hip_test_band): band[c (bw + 1) + k] = K[c + k][c], perm [n], rhs [nrhs, n],
+        x = the canvas the solutions are written into (nrhs n + 16 doubles; default: NaN).  Every length is passed as it is: the entry validates.
+        Returns (status, x canvas after the call, image, dinv, bad)."""
+        band = np.ascontiguousarray(band, dtype=np.float64).ravel()
+        perm = np.ascontiguousarray(perm, dtype=np.int32).ravel()
+        rhs = np.zeros((0, max(int(n), 0))) if rhs is None else np.ascontiguousarray(rhs, dtype=np.float64)
+        nrhs = rhs.shape[0] if rhs.ndim == 2 else 1
+        rhs = rhs.ravel()
+        out = np.full(nrhs * max(int(n), 0) + 16, np.nan) if x is None else np.array(x, dtype=np.float64).ravel()      # (a copy: the caller's canvas stays as it was)
+        image = np.full(8 + (max(int(n), 0) + 7) // 8 * 8 * (max(int(bw), 0) + 8) + 64, np.nan)                        # band_doubles(n, bw), csrc/band_ldl.h
+        dinv = np.full(max(int(n), 0), np.nan)
+        t = _lib.BandTestStruct(int(n), int(bw), int(threads), int(guard), int(nrhs), float(pivot_floor), band.size, perm.size, rhs.size, out.size, image.size, dinv.size,
+                                _ptr(band, _lib.c_double_p), _ptr(perm, _lib.c_int_p), _ptr(rhs, _lib.c_double_p), _ptr(out, _lib.c_double_p),
+                                _ptr(image, _lib.c_double_p), _ptr(dinv, _lib.c_double_p), 0)
+        st = int(self._lib.osqp_hip_test_band(self._p, C.byref(t)))
+        return st, out, image, dinv, int(t.bad)
+
     def hip_set_rho_eq_factor(self, factor):
         return self._lib.osqp_hip_set_rho_eq_factor(self._p, float(factor))
 

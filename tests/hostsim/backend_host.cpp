@@ -352,6 +352,50 @@ double test_dense(Dev &, const DenseProbe &p) {
   }
   return p.N > 0 ? host_spd_inverse(p.C, p.cs_i, p.N) : 0.0;
 }
+// The band of band_ldl.h as textbook loops on a dense lower triangle (the CPU tier drives the GPU test's cases, bounds and checks through them:
+// tests/test_band_ref.py): K = L^ D L^' row by row, the pivot rule of band_factor's GUARD, two substitutions, and the outputs in the kernel's layout --
+// L^ strictly lower at band_slot(), zeros everywhere else in the image, 1 / D.
+int test_band(Dev &, const BandProbe &p) {
+  const int n = p.n, bw = p.bw;
+  std::vector<double> L((size_t)n * n, 0.0), D(n);
+  bool bad = false;
+  for (int c = 0; c < n; c++) {
+    double pv = p.band[(size_t)c * (bw + 1)];
+    for (int j = std::max(0, c - bw); j < c; j++) pv -= L[(size_t)c * n + j] * L[(size_t)c * n + j] * D[j];
+    if (p.guard && (!(pv > 0.0) || pv > 1e300)) { bad = true; pv = (std::fabs(pv) > p.pivot_floor && std::fabs(pv) <= 1e300) ? std::fabs(pv) : 1.0; }
+    D[c] = pv;
+    for (int r = c + 1; r <= std::min(n - 1, c + bw); r++) {
+      double v = p.band[(size_t)c * (bw + 1) + (r - c)];
+      for (int j = std::max(0, r - bw); j < c; j++) v -= L[(size_t)r * n + j] * L[(size_t)c * n + j] * D[j];
+      L[(size_t)r * n + c] = v / pv;
+    }
+  }
+  const size_t nimg = band_doubles(n, bw);
+  for (size_t s = 0; s < nimg; s++) p.image[s] = 0.0;
+  for (int c = 0; c < n; c++) {
+    p.dinv[c] = 1.0 / D[c];
+    for (int r = c + 1; r <= std::min(n - 1, c + bw); r++) p.image[kBandFront + band_slot(bw, c, r)] = L[(size_t)r * n + c];
+  }
+  std::vector<double> v(n);
+  for (int s = 0; s < p.nrhs; s++) {
+    const double *rhs = p.rhs + (size_t)s * n;
+    double *out = p.x + (size_t)s * n;
+    for (int k = 0; k < n; k++) {
+      double a = rhs[p.perm[k]];
+      for (int j = std::max(0, k - bw); j < k; j++) a -= L[(size_t)k * n + j] * v[j];
+      v[k] = a;
+    }
+    for (int k = 0; k < n; k++) v[k] /= D[k];
+    for (int k = n - 1; k >= 0; k--) {
+      double a = v[k];
+      for (int j = k + 1; j <= std::min(n - 1, k + bw); j++) a -= L[(size_t)j * n + k] * v[j];
+      v[k] = a;
+    }
+    for (int k = 0; k < n; k++) out[p.perm[k]] = v[k];
+  }
+  *p.bad = bad ? 1 : 0;
+  return OSQP_NO_ERROR;
+}
 float time_kernel(Dev &, int, int) { return 0.f; }
 
 }  // namespace be
