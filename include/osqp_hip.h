@@ -656,6 +656,35 @@ typedef struct {
   OSQPInt bad;                     /* out */
 } OSQPHipBandTest;
 OSQPInt osqp_hip_test_band(OSQPSolver *solver, OSQPHipBandTest *t);
+/* Test hook (used by tests/ only): the Woodbury correction M^-1 (csrc/woodbury_hip.hip) of a set-up handle whose correction is on,
+   at the handle's CURRENT matrices and rho vector, through the product's own functions: with refactor != 0 wb_factor (D0, then S / S^-1 of the small
+   form, the device-factorised row-space form, or T / T^-1 of the column-space form, with their checks), then the caller's r is copied to the PCG's
+   residual vector, the `converged` flag is cleared and wb_apply(parity, direct) runs -- with direct != 0 the caller's x0 is loaded to x~ first and the
+   last kernel adds u to it.  Synchronous.  Vectors are in the caller's numbering; everything is in the SCALED problem (osqp_hip_get_scaling).
+     r      [n]                right-hand side                          x0  [n with direct, else 0]  x~ before the call
+     u      [n + 16]           M^-1 r                                   xs  [n + 16]                 x~ after the call (x0 + u with direct)
+     dinv0  [n + 16]           1 / D0                                   rho [m + 16]                 the rho vector
+     S, Sinv [order^2 + 16]    the dense system and its inverse, row-major: S (order = long rows, in the order of idx) in the small and the row-space
+                               form, T (order = dense columns, in the order of idx) in the column-space form
+     idx    [order + 16]       the long rows (forms 0, 1) / the dense columns (form 2) in the order S / T lists them
+   Of every output exactly the listed count is written: the 16 cells behind it keep the caller's values.  form: 0 small, 1 row space, 2 column space;
+   rows: long rows; exact: the direct mode's verdict (DevWb::exact) after the call; info: the two status words of the factorisation; done / iters: the
+   PCG's `converged` flag and iteration count after the call; gamma = <r, u> and rnorm = max |r|: the partial results the last kernel left for the
+   PCG (slots of the given parity), one per workgroup, folded here on the host in index order (sum, maximum) -- the PCG folds the same values in
+   another order.  Everything the call overwrites -- residual, u, x~, the flags, those partial slots -- is restored before it returns, and a
+   re-factorisation recomputes what the handle already holds: a solve after the call is the solve without it.
+   OSQP_FUNC_NOT_IMPLEMENTED: the backend has no Woodbury correction, or this handle's is off.  Every length and flag is checked before anything is
+   launched (anything else than listed: OSQP_DATA_VALIDATION_ERROR). */
+typedef struct {
+  OSQPInt refactor, parity, direct;
+  long long r_len, x0_len, u_len, xs_len, dinv0_len, s_len, sinv_len, rho_len, idx_len;
+  const OSQPFloat *r, *x0;
+  OSQPFloat *u, *xs, *dinv0, *S, *Sinv, *rho;
+  OSQPInt *idx;
+  OSQPInt form, order, rows, exact, info[2], done, iters;   /* out */
+  OSQPFloat gamma, rnorm;                                    /* out */
+} OSQPHipWoodburyTest;
+OSQPInt osqp_hip_test_woodbury(OSQPSolver *solver, OSQPHipWoodburyTest *t);
 /* Weight of equality rows relative to inequality rows, rho_eq = factor * rho, used when equality and inequality rows are
    mixed (default 10; the reference's 1e3 is kept when every active row is an equality).  See engine.cpp (Engine::classify_constraints)
    classify_constraints() for the rationale.  Takes effect immediately (rho vector + preconditioner are rebuilt). */

@@ -733,6 +733,15 @@ inline size_t test_band_lds_bytes(int n, int bw) {
   return b <= 144 * 1024 ? b : 0;
 }
 int test_band(Dev &d, const BandProbe &p) __attribute__((weak));
+// the Woodbury correction of a handle with d.wb.on (include/osqp_hip.h osqp_hip_test_woodbury, which has validated every field: nothing is checked here).
+// HOST vectors in the engine's numbering: r [n], x0 [n] (direct), u / xs / dinv0 [n], S / Sinv [order^2], rho [m].  wb_factor (refactor), r -> d.r,
+// x0 -> d.xs, F_DONE cleared, wb_apply(parity, direct); d.r, d.uu, d.xs, the flags and the four gamma / rn partial slots are saved before and
+// restored after.  gamma / rnorm: the kGrid partials of SL_GAMMA0 + parity / SL_RN0 + parity folded on the host in index order.  Weak like test_dense.
+struct WbProbe {
+  int refactor, parity, direct; const double *r, *x0; double *u, *xs, *dinv0, *S, *Sinv, *rho;
+  int exact, info[2], done, iters; double gamma, rnorm;
+};
+int test_woodbury(Dev &d, WbProbe &p) __attribute__((weak));
 float time_kernel(Dev &d, int which, int reps);                             // mean ms per launch
 
 }  // namespace be

@@ -48,6 +48,7 @@ class Engine {
   int test_spmv(int which, const double *in, double *out);
   int test_dense(OSQPHipDenseTest *t);
   int test_band(OSQPHipBandTest *t);
+  int test_woodbury(OSQPHipWoodburyTest *t);
   int trace_read(unsigned long long *out, int count);
   int get_scaling(double *D, double *E, double *c);
   int get_reordering(int *perm_cols, int *perm_rows) const;

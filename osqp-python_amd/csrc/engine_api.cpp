@@ -1589,6 +1589,32 @@ int Engine::test_band(OSQPHipBandTest *t) {
   t->bad = hbad;
   return OSQP_NO_ERROR;
 }
+int Engine::test_woodbury(OSQPHipWoodburyTest *t) {
+  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (!be::test_woodbury || !d_.wb.on) return OSQP_FUNC_NOT_IMPLEMENTED;
+  // every length is checked here: the backend copies exactly these counts
+  if (!t || !(t->parity == 0 || t->parity == 1) || !(t->direct == 0 || t->direct == 1)) return OSQP_DATA_VALIDATION_ERROR;
+  const DevWb &w = d_.wb;
+  const long long nn = n, mm = m, ord = w.dual ? w.cd : w.r, tail = 16;
+  if (t->r_len != nn || t->x0_len != (t->direct ? nn : 0) || t->u_len != nn + tail || t->xs_len != nn + tail || t->dinv0_len != nn + tail ||
+      t->s_len != ord * ord + tail || t->sinv_len != ord * ord + tail || t->rho_len != mm + tail || t->idx_len != ord + tail)
+    return OSQP_DATA_VALIDATION_ERROR;
+  if (!t->r || (t->direct && !t->x0) || !t->u || !t->xs || !t->dinv0 || !t->S || !t->Sinv || !t->rho || !t->idx) return OSQP_DATA_VALIDATION_ERROR;
+  be::activate(d_);
+  std::vector<double> hr(n), hx0(t->direct ? n : 0), hu(n), hxs(n), hd(n), hrho(m);
+  for (int j = 0; j < n; j++) { const int c = reordered_ ? pc_[j] : j; hr[j] = t->r[c]; if (t->direct) hx0[j] = t->x0[c]; }
+  std::vector<int> hidx((size_t)ord);
+  be::d2h(d_, hidx.data(), w.dual ? w.dcol : w.rows, sizeof(int) * (size_t)ord);
+  be::WbProbe p{t->refactor != 0, t->parity, t->direct, hr.data(), hx0.data(), hu.data(), hxs.data(), hd.data(), t->S, t->Sinv, hrho.data(), 0, {0, 0}, 0, 0, 0.0, 0.0};
+  const int st = be::test_woodbury(d_, p);
+  if (st != OSQP_NO_ERROR) return st;
+  for (int j = 0; j < n; j++) { const int c = reordered_ ? pc_[j] : j; t->u[c] = hu[j]; t->xs[c] = hxs[j]; t->dinv0[c] = hd[j]; }
+  for (int i = 0; i < m; i++) t->rho[reordered_ ? pr_[i] : i] = hrho[i];
+  for (long long k = 0; k < ord; k++) t->idx[k] = reordered_ ? (w.dual ? pc_[hidx[k]] : pr_[hidx[k]]) : hidx[k];
+  t->form = w.dual ? 2 : (w.large ? 1 : 0); t->order = (int)ord; t->rows = w.r; t->exact = p.exact; t->info[0] = p.info[0]; t->info[1] = p.info[1];
+  t->done = p.done; t->iters = p.iters; t->gamma = p.gamma; t->rnorm = p.rnorm;
+  return OSQP_NO_ERROR;
+}
 int Engine::get_reordering(int *perm_cols, int *perm_rows) const {
   if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   if (!perm_cols || (m > 0 && !perm_rows)) return OSQP_DATA_VALIDATION_ERROR;

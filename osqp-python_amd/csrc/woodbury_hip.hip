@@ -813,5 +813,62 @@ void wb_factor(Dev &d) {
   if (ok != 1) w.exact = 0;                                   // the direct mode trusts S^-1: || S S^-1 - I ||_max must be at rounding level
 }
 
+// Diagnostic (backend.h WbProbe; include/osqp_hip.h osqp_hip_test_woodbury): wb_factor and wb_apply as a solve calls them, on the caller's right-hand side.
+// Everything the two overwrite of a solve's state -- d.r, d.uu, d.xs, the flags, the gamma / rn partial slots (also the probe of wb_factor_large writes
+// them) -- is saved first and put back last, also when one of them throws; what wb_factor writes besides is a function of the matrices and the rho vector.
+int test_woodbury(Dev &d, WbProbe &p) {
+  HIP_CHECK(hipSetDevice(d.device));
+  DevWb &w = d.wb;
+  const size_t n = d.n, m = d.m, ord = w.dual ? (size_t)w.cd : (size_t)w.r;
+  static_assert(SL_GAMMA1 == SL_GAMMA0 + 1 && SL_RN0 == SL_GAMMA0 + 2 && SL_RN1 == SL_GAMMA0 + 3, "the four saved partial slots are contiguous");
+  struct Saved {
+    Dev &d; hipStream_t s;
+    struct V { double *ptr; size_t cnt; double *bak; } v[4];
+    int flags[F_COUNT]; bool have = false;
+    Saved(Dev &d_, hipStream_t s_) : d(d_), s(s_), v{{d_.r, (size_t)d_.n, nullptr}, {d_.uu, (size_t)d_.n, nullptr}, {d_.xs, (size_t)d_.n, nullptr}, {d_.part + (size_t)SL_GAMMA0 * kGrid, 4 * (size_t)kGrid, nullptr}} {}
+    void save() {
+      for (auto &e : v) {
+        HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&e.bak), e.cnt * sizeof(double)));
+        HIP_CHECK(hipMemcpyAsync(e.bak, e.ptr, e.cnt * sizeof(double), hipMemcpyDeviceToDevice, s));
+      }
+      HIP_CHECK(hipMemcpyAsync(flags, d.flags, sizeof(flags), hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+      have = true;
+    }
+    ~Saved() {                                                // (no throw from here: a failed restore leaves the device error for the next call to report)
+      if (have) {
+        for (auto &e : v) if (e.bak) (void)hipMemcpyAsync(e.ptr, e.bak, e.cnt * sizeof(double), hipMemcpyDeviceToDevice, s);
+        (void)hipMemcpyAsync(d.flags, flags, sizeof(flags), hipMemcpyHostToDevice, s);
+        (void)hipStreamSynchronize(s);
+      }
+      for (auto &e : v) if (e.bak) (void)hipFree(e.bak);
+    }
+  } saved(d, st(d));
+  saved.save();
+  if (p.refactor) wb_factor(d);
+  HIP_CHECK(hipMemcpyAsync(d.r, p.r, n * sizeof(double), hipMemcpyHostToDevice, st(d)));
+  if (p.direct) HIP_CHECK(hipMemcpyAsync(d.xs, p.x0, n * sizeof(double), hipMemcpyHostToDevice, st(d)));
+  HIP_CHECK(hipMemsetAsync(d.flags + F_DONE, 0, sizeof(int), st(d)));
+  wb_apply(d, p.parity, p.direct);
+  std::vector<double> part(2 * (size_t)kGrid);
+  int flags[F_COUNT];
+  HIP_CHECK(hipMemcpyAsync(p.u, d.uu, n * sizeof(double), hipMemcpyDeviceToHost, st(d)));
+  HIP_CHECK(hipMemcpyAsync(p.xs, d.xs, n * sizeof(double), hipMemcpyDeviceToHost, st(d)));
+  HIP_CHECK(hipMemcpyAsync(p.dinv0, w.Dinv0, n * sizeof(double), hipMemcpyDeviceToHost, st(d)));
+  HIP_CHECK(hipMemcpyAsync(p.S, w.S, ord * ord * sizeof(double), hipMemcpyDeviceToHost, st(d)));
+  HIP_CHECK(hipMemcpyAsync(p.Sinv, w.Sinv, ord * ord * sizeof(double), hipMemcpyDeviceToHost, st(d)));
+  if (m) HIP_CHECK(hipMemcpyAsync(p.rho, d.rho, m * sizeof(double), hipMemcpyDeviceToHost, st(d)));
+  HIP_CHECK(hipMemcpyAsync(p.info, w.info, 2 * sizeof(int), hipMemcpyDeviceToHost, st(d)));
+  HIP_CHECK(hipMemcpyAsync(flags, d.flags, sizeof(flags), hipMemcpyDeviceToHost, st(d)));
+  HIP_CHECK(hipMemcpyAsync(part.data(), d.part + (size_t)(SL_GAMMA0 + p.parity) * kGrid, kGrid * sizeof(double), hipMemcpyDeviceToHost, st(d)));
+  HIP_CHECK(hipMemcpyAsync(part.data() + kGrid, d.part + (size_t)(SL_RN0 + p.parity) * kGrid, kGrid * sizeof(double), hipMemcpyDeviceToHost, st(d)));
+  HIP_CHECK(hipStreamSynchronize(st(d)));
+  // the consumers (pcg_hip.hip: partial_load + partial_fold_sum / _max + a block reduction) fold these kGrid values in a lane-strided order; here: index order
+  double g = 0.0, rn = 0.0;
+  for (int k = 0; k < kGrid; k++) { g += part[k]; const double v = part[kGrid + k]; if (v > rn || v != v) rn = v; }
+  p.gamma = g; p.rnorm = rn; p.exact = w.exact; p.done = flags[F_DONE]; p.iters = flags[F_ITERS];
+  return OSQP_NO_ERROR;
+}
+
 }  // namespace be
 }  // namespace osqp_hip

@@ -81,6 +81,14 @@ class BandTestStruct(C.Structure):    # OSQPHipBandTest, include/osqp_hip.h (sam
                 [('band', c_double_p), ('perm', c_int_p), ('rhs', c_double_p), ('x', c_double_p), ('image', c_double_p), ('dinv', c_double_p), ('bad', C.c_int)])
 
 
+class WoodburyTestStruct(C.Structure):    # OSQPHipWoodburyTest, include/osqp_hip.h (same order)
+    _fields_ = ([(k, C.c_int) for k in ('refactor', 'parity', 'direct')] +
+                [(k, C.c_longlong) for k in ('r_len', 'x0_len', 'u_len', 'xs_len', 'dinv0_len', 's_len', 'sinv_len', 'rho_len', 'idx_len')] +
+                [(k, c_double_p) for k in ('r', 'x0', 'u', 'xs', 'dinv0', 'S', 'Sinv', 'rho')] + [('idx', c_int_p)] +
+                [(k, C.c_int) for k in ('form', 'order', 'rows', 'exact')] + [('info', C.c_int * 2), ('done', C.c_int), ('iters', C.c_int)] +
+                [('gamma', C.c_double), ('rnorm', C.c_double)])
+
+
 SolverP = C.POINTER(SolverStruct)
 
 
@@ -130,6 +138,7 @@ PROTOTYPES = {
     'osqp_hip_test_spmv': (C.c_int, [SolverP, C.c_int, c_double_p, c_double_p]),
     'osqp_hip_test_dense': (C.c_int, [SolverP, C.POINTER(DenseTestStruct)]),
     'osqp_hip_test_band': (C.c_int, [SolverP, C.POINTER(BandTestStruct)]),
+    'osqp_hip_test_woodbury': (C.c_int, [SolverP, C.POINTER(WoodburyTestStruct)]),
     'osqp_hip_set_rho_eq_factor': (C.c_int, [SolverP, C.c_double]),
     'osqp_hip_default_policy': (None, [C.POINTER(PolicyStruct)]),
     'osqp_hip_set_default_policy': (None, [C.POINTER(PolicyStruct)]),

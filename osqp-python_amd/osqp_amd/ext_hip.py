@@ -358,6 +358,30 @@ class OSQPSolver:
         st = int(self._lib.osqp_hip_test_band(self._p, C.byref(t)))
         return st, out, image, dinv, int(t.bad)
 
+    def hip_test_woodbury(self, r, x0=None, refactor=1, parity=0, direct=0, order=None, lens=None):
+        """The Woodbury correction of this handle on one right-hand side (osqp_hip_test_woodbury): optionally wb_factor, then wb_apply(parity, direct) on
+        r [n] (direct: x~ starts from x0 [n]).  order: of the dense system (default: from hip_stats()).  Every output is a NaN canvas of its count + 16;
+        lens = {field: length} overrides a length as it is passed (the entry validates).  Returns (status, dict) with the canvases u, xs, dinv0, S, Sinv,
+        rho, idx (int32, -1) as the call left them and form, order, rows, exact, info, done, iters, gamma, rnorm."""
+        n, m = self.n, self.m
+        if order is None:
+            s = self.hip_stats()
+            order = int(s['woodbury_dual_cols']) or int(s['woodbury_rows'])
+        r = np.ascontiguousarray(r, dtype=np.float64).ravel()
+        x0 = np.zeros(0) if x0 is None else np.ascontiguousarray(x0, dtype=np.float64).ravel()
+        cnt = dict(u=n + 16, xs=n + 16, dinv0=n + 16, S=order * order + 16, Sinv=order * order + 16, rho=m + 16)
+        out = {k: np.full(v, np.nan) for k, v in cnt.items()}
+        out['idx'] = np.full(order + 16, -1, dtype=np.int32)
+        ln = dict(r_len=r.size, x0_len=x0.size, u_len=cnt['u'], xs_len=cnt['xs'], dinv0_len=cnt['dinv0'], s_len=cnt['S'], sinv_len=cnt['Sinv'], rho_len=cnt['rho'], idx_len=order + 16)
+        ln.update(lens or {})
+        t = _lib.WoodburyTestStruct(int(refactor), int(parity), int(direct), *[int(ln[k]) for k in ('r_len', 'x0_len', 'u_len', 'xs_len', 'dinv0_len', 's_len', 'sinv_len', 'rho_len', 'idx_len')],
+                                    _ptr(r, _lib.c_double_p), _ptr(x0, _lib.c_double_p), *[_ptr(out[k], _lib.c_double_p) for k in ('u', 'xs', 'dinv0', 'S', 'Sinv', 'rho')],
+                                    _ptr(out['idx'], _lib.c_int_p))
+        st = int(self._lib.osqp_hip_test_woodbury(self._p, C.byref(t)))
+        out.update(form=int(t.form), order=int(t.order), rows=int(t.rows), exact=int(t.exact), info=(int(t.info[0]), int(t.info[1])), done=int(t.done), iters=int(t.iters),
+                   gamma=float(t.gamma), rnorm=float(t.rnorm))
+        return st, out
+
     def hip_set_rho_eq_factor(self, factor):
         return self._lib.osqp_hip_set_rho_eq_factor(self._p, float(factor))
 

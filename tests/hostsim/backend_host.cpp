@@ -30,8 +30,8 @@ int init(Dev &d, int) { d.impl = new Impl(); return 0; }
 void destroy(Dev &d) { delete static_cast<Impl *>(d.impl); d.impl = nullptr; }
 void *alloc(Dev &, size_t bytes) { return std::calloc(1, bytes); }
 void dfree(Dev &, void *p) { std::free(p); }
-void h2d(Dev &, void *dst, const void *src, size_t b) { std::memcpy(dst, src, b); }
-void d2h(Dev &, void *dst, const void *src, size_t b) { std::memcpy(dst, src, b); }
+void h2d(Dev &, void *dst, const void *src, size_t b) { if (b) std::memcpy(dst, src, b); }      // (b == 0: an empty vector's data() may be null, which memcpy must not be given)
+void d2h(Dev &, void *dst, const void *src, size_t b) { if (b) std::memcpy(dst, src, b); }
 void zero(Dev &, void *dst, size_t b) { std::memset(dst, 0, b); }
 void sync(Dev &) {}
 static thread_local double g_ev[2];
@@ -62,8 +62,13 @@ void f1_refresh(Dev &) {}
 bool kf_supported() { return false; }
 void wbf_iteration(Dev &) {}
 void kf_values(Dev &, int) {}
+#ifdef HOSTSIM_WB_ENTRY_PROBE              // (tests/hostsim/wb_entry_probe.cpp alone: Engine::prepare_wb builds the symbolic plan, so that the host side of osqp_hip_test_woodbury has a handle to validate against)
+bool wb_supported() { return true; }
+bool wb_large_supported() { return true; }
+#else
 bool wb_supported() { return false; }
 bool wb_large_supported() { return false; }
+#endif
 void wb_refresh(Dev &) {}
 void wb_apply(Dev &, int, int) {}
 void wb_direct(Dev &) {}
