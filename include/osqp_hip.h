@@ -338,14 +338,14 @@ OSQPInt osqp_hip_lockstep_polish_last_record(OSQPSolver *solver, OSQPFloat *rec)
  * POLISH is off on this entry whatever settings.polishing says: record fields 8 and 9 stay 0.
  * Returns OSQP_FUNC_NOT_IMPLEMENTED for whatever osqp_hip_batch_solve_lockstep declines, for a handle without device-side assembly, and for a handle whose
  * stored upper triangle of P holds a repeated (j, j) entry (the single-handle assembly sums those; this route has one writer per entry).
- * OUT OF SCOPE: polish and adjoint derivatives with per-problem matrices, the direct (Woodbury) route, multi-rank sharding of this entry, repeated
- * diagonal entries of P.
+ * OUT OF SCOPE: polish with per-problem matrices, the direct (Woodbury) route, multi-rank sharding of this entry, repeated diagonal entries of P.  (The
+ * backward pass with per-problem matrices: osqp_hip_batch_adjoint_lockstep_mat below.)
  * osqp_hip_lockstep_mat_last_record: OSQP_HIP_LOCKSTEP_MAT_LAST_REC doubles {chunks, chunk width, ADMM iterations of the slowest problem, PCG iterations
  * summed, kernel launches of the whole call, GPU ms of the whole call, bytes of the matrix block, GPU ms spent in assembly + equilibration}; all zero
  * before the first call.  osqp_hip_lockstep_last_record is written as by any lockstep call.
  * osqp_hip_lockstep_mat_scaling: D (n), E (m) and c of problem b of the LAST chunk the last such call processed, numbered as osqp_hip_get_scaling numbers
  * the handle's -- so that the per-problem equilibration can be checked directly.  OSQP_DATA_NOT_INITIALIZED before the first call or for b outside
- * that chunk. */
+ * that chunk -- and after a call of osqp_hip_batch_adjoint_lockstep_mat[_device], which overwrites the matrix block, until the next forward call. */
 #define OSQP_HIP_LOCKSTEP_MAT_LAST_REC 8
 OSQPInt osqp_hip_batch_solve_lockstep_mat(OSQPSolver *solver, OSQPInt nbatch, const OSQPFloat *Px, const OSQPFloat *Ax, const OSQPFloat *q, const OSQPFloat *l,
                                           const OSQPFloat *u, OSQPFloat *x, OSQPFloat *y, OSQPFloat *rec, OSQPInt warm);
@@ -392,8 +392,8 @@ OSQPInt osqp_hip_lockstep_direct_last_record(OSQPSolver *solver, OSQPFloat *rec)
  * The outputs of a problem with a nonzero status are written and hold its last iterate; the other problems are untouched by it.  INDEPENDENCE as on
  * the forward route: a problem's outputs and record are bit-identical whatever else is in the batch and wherever in it the problem sits.
  * A reordered handle is served in the caller's numbering.  The handle's iterates, rho, info, solution, launch graphs and history are not touched, nor
- * are the forward route's workspace and record: the work block is this route's own (allocated by the first call, freed with the handle).  No
- * per-problem matrices.  Returns OSQP_FUNC_NOT_IMPLEMENTED on a handle with a Woodbury-corrected preconditioner and in the host simulator.
+ * are the forward route's workspace and record: the work block is this route's own (allocated by the first call, freed with the handle).
+ * Per-problem matrices: osqp_hip_batch_adjoint_lockstep_mat below.  Returns OSQP_FUNC_NOT_IMPLEMENTED on a handle with a Woodbury-corrected preconditioner and in the host simulator.
  * _device: stream semantics of osqp_hip_batch_solve_lockstep_device -- the call returns when the results are there; nbatch == 0 answers applicability.
  * osqp_hip_lockstep_adjoint_last_record: OSQP_HIP_LOCKSTEP_ADJOINT_LAST_REC doubles {chunks, chunk width, recurrence steps of the slowest problem, PCG
  * iterations summed over the problems, kernel launches, GPU ms, workspace bytes, reserved}; all zero before the first call. */
@@ -405,6 +405,31 @@ OSQPInt osqp_hip_batch_adjoint_lockstep_device(OSQPSolver *solver, OSQPInt nbatc
                                                const OSQPFloat *y_dev, const OSQPFloat *dx_dev, const OSQPFloat *dy_dev, OSQPFloat *dP_dev, OSQPFloat *dq_dev,
                                                OSQPFloat *dA_dev, OSQPFloat *dl_dev, OSQPFloat *du_dev, OSQPFloat *arec_dev, void *stream);
 OSQPInt osqp_hip_lockstep_adjoint_last_record(OSQPSolver *solver, OSQPFloat *rec);
+/* ADJOINT DERIVATIVES ON THE LOCKSTEP ROUTE WITH PER-PROBLEM MATRICES -- the backward pass of osqp_hip_batch_solve_lockstep_mat: problem b's adjoint system
+ * is solved on its own P_b, A_b, scaled by its own D_b, E_b, c_b.  Px is nbatch x nnz(triu P), Ax nbatch x nnz(A), in the CSC order given at setup; either
+ * may be NULL: the handle's own raw values for every problem (as on the forward entry).  Every other argument, the OSQP_HIP_ADJOINT_REC record, the
+ * statuses 0 / 2 / 3, the nbatch == 0 query, the stream semantics and INDEPENDENCE (a problem's matrices being part of the problem) are
+ * osqp_hip_batch_adjoint_lockstep[_device]'s; dP / dA are per problem in the caller's CSC order.  A chunk's matrices are assembled and equilibrated as
+ * on the forward entry (5 + 4 x settings.scaling launches in front of its transposes in), with the handle's q for every problem: the adjoint does not
+ * depend on the cost scale c in exact arithmetic.  A reordered handle is served.
+ * MATRIX BLOCK: the forward entry's, allocated by whichever of the two entries is called first.  A call here overwrites it, so
+ * osqp_hip_lockstep_mat_scaling answers OSQP_DATA_NOT_INITIALIZED from then until the next forward call; the forward entry's results do not depend on
+ * calls made here in between.  The handle's own matrices, scaling, iterates, graphs and history are not touched.
+ * Returns OSQP_FUNC_NOT_IMPLEMENTED unless both osqp_hip_batch_adjoint_lockstep and osqp_hip_batch_solve_lockstep_mat serve the handle: a Woodbury
+ * handle, the host simulator, a handle without device-side assembly, a repeated (j, j) entry in the stored upper triangle of P.
+ * OUT OF SCOPE: the direct (Woodbury) route, multi-rank sharding of this entry.
+ * osqp_hip_lockstep_mat_adjoint_last_record: OSQP_HIP_LOCKSTEP_MAT_ADJOINT_LAST_REC doubles {chunks, chunk width, recurrence steps of the slowest
+ * problem, PCG iterations summed over the problems, kernel launches of the whole call, GPU ms of the whole call, bytes of the matrix block, GPU ms spent
+ * in assembly + equilibration}; all zero before the first call.  osqp_hip_lockstep_adjoint_last_record is written as by any lockstep adjoint call. */
+#define OSQP_HIP_LOCKSTEP_MAT_ADJOINT_LAST_REC 8
+OSQPInt osqp_hip_batch_adjoint_lockstep_mat(OSQPSolver *solver, OSQPInt nbatch, const OSQPFloat *Px, const OSQPFloat *Ax, const OSQPFloat *l, const OSQPFloat *u,
+                                            const OSQPFloat *x, const OSQPFloat *y, const OSQPFloat *dx, const OSQPFloat *dy, OSQPFloat *dP, OSQPFloat *dq,
+                                            OSQPFloat *dA, OSQPFloat *dl, OSQPFloat *du, OSQPFloat *arec);
+OSQPInt osqp_hip_batch_adjoint_lockstep_mat_device(OSQPSolver *solver, OSQPInt nbatch, const OSQPFloat *Px_dev, const OSQPFloat *Ax_dev, const OSQPFloat *l_dev,
+                                                   const OSQPFloat *u_dev, const OSQPFloat *x_dev, const OSQPFloat *y_dev, const OSQPFloat *dx_dev,
+                                                   const OSQPFloat *dy_dev, OSQPFloat *dP_dev, OSQPFloat *dq_dev, OSQPFloat *dA_dev, OSQPFloat *dl_dev,
+                                                   OSQPFloat *du_dev, OSQPFloat *arec_dev, void *stream);
+OSQPInt osqp_hip_lockstep_mat_adjoint_last_record(OSQPSolver *solver, OSQPFloat *rec);
 /* ADJOINT DERIVATIVES ON THE DIRECT LOCKSTEP ROUTE -- the backward pass of osqp_hip_batch_solve_lockstep_direct, on exactly the handles that call accepts
  * (OSQP_FUNC_NOT_IMPLEMENTED for every other one: no Woodbury correction, r > 128, a K0 that is not diagonal, a reordered handle, the host simulator).
  * Arguments, the classification, the recurrence and its ending rule, the unscaling, the residual of the unregularised system, the outputs (dA at every

@@ -145,6 +145,16 @@ OSQPInt osqp_hip_batch_adjoint_lockstep_device(OSQPSolver *s, OSQPInt nbatch, co
   return guarded(s, [&](Engine &e) { return e.batch_adjoint_lockstep_device(nbatch, l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec, stream); });
 }
 OSQPInt osqp_hip_lockstep_adjoint_last_record(OSQPSolver *s, OSQPFloat *rec) { return guarded(s, [&](Engine &e) { return e.lockstep_adjoint_last_record(rec); }); }
+OSQPInt osqp_hip_batch_adjoint_lockstep_mat(OSQPSolver *s, OSQPInt nbatch, const OSQPFloat *Px, const OSQPFloat *Ax, const OSQPFloat *l, const OSQPFloat *u, const OSQPFloat *x, const OSQPFloat *y,
+                                            const OSQPFloat *dx, const OSQPFloat *dy, OSQPFloat *dP, OSQPFloat *dq, OSQPFloat *dA, OSQPFloat *dl, OSQPFloat *du, OSQPFloat *arec) {
+  return guarded(s, [&](Engine &e) { return e.batch_adjoint_lockstep_mat(nbatch, Px, Ax, l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec); });
+}
+OSQPInt osqp_hip_batch_adjoint_lockstep_mat_device(OSQPSolver *s, OSQPInt nbatch, const OSQPFloat *Px, const OSQPFloat *Ax, const OSQPFloat *l, const OSQPFloat *u, const OSQPFloat *x,
+                                                   const OSQPFloat *y, const OSQPFloat *dx, const OSQPFloat *dy, OSQPFloat *dP, OSQPFloat *dq, OSQPFloat *dA, OSQPFloat *dl, OSQPFloat *du,
+                                                   OSQPFloat *arec, void *stream) {
+  return guarded(s, [&](Engine &e) { return e.batch_adjoint_lockstep_mat_device(nbatch, Px, Ax, l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec, stream); });
+}
+OSQPInt osqp_hip_lockstep_mat_adjoint_last_record(OSQPSolver *s, OSQPFloat *rec) { return guarded(s, [&](Engine &e) { return e.lockstep_mat_adjoint_last_record(rec); }); }
 OSQPInt osqp_hip_batch_adjoint_lockstep_direct(OSQPSolver *s, OSQPInt nbatch, const OSQPFloat *l, const OSQPFloat *u, const OSQPFloat *x, const OSQPFloat *y, const OSQPFloat *dx,
                                                const OSQPFloat *dy, OSQPFloat *dP, OSQPFloat *dq, OSQPFloat *dA, OSQPFloat *dl, OSQPFloat *du, OSQPFloat *rec) {
   return guarded(s, [&](Engine &e) { return e.batch_adjoint_lockstep_direct(nbatch, l, u, x, y, dx, dy, dP, dq, dA, dl, du, rec); });

@@ -493,7 +493,9 @@ struct LockstepParams : BatchSettings {
   // (m x kLsW), assembled from the chunk's rows Px / Ax of the caller's [nbatch][nnz(triu P)] / [nbatch][nnz(A)] arrays (the caller's CSC order; nullptr: the
   // handle's raw values for every problem) and equilibrated per problem in front of the transposes in; c and 1 / c are rows of the per-problem scalar
   // state.  pvmap / avmap: caller's position -> the engine's (reordered handle; nullptr: identity).  mat_iters: settings.scaling.  mat_stat (host,
-  // kLsMatStat doubles, nullptr: not wanted): GPU ms and kernel launches of the assembly + equilibration.  Set by Engine::run_lockstep alone.
+  // kLsMatStat doubles, nullptr: not wanted): GPU ms and kernel launches of the assembly + equilibration.  Set by Engine::run_lockstep and, for the
+  // backward pass with per-problem matrices (osqp_hip_batch_adjoint_lockstep_mat), by Engine::run_lockstep_adjoint: lockstep_adjoint_chunk then prepares the
+  // chunk's matrices in the same block by the same launches, with the handle's q for every problem (q == nullptr).
   double *mat_ws = nullptr, *mat_stat = nullptr;
   const double *Px = nullptr, *Ax = nullptr;
   const int *pvmap = nullptr, *avmap = nullptr;
@@ -505,7 +507,7 @@ constexpr int kLsMatStat = 2;
 // Adjoint derivatives of a chunk on the lockstep route (lockstep_hip.hip lockstep_adjoint_chunk; include/osqp_hip.h osqp_hip_batch_adjoint_lockstep):
 // the recurrence of Engine::run_recurrence per problem on block vectors.  The base carries the matrices, the scalings, the permutations, the shared
 // bounds l0 / u0, the chunk's rows of l / u and the settings the forward's kernels read (alpha = 1, cg_max = kMaxCg, pcg_rel = polish_pcg_tol, rho0 =
-// 1 / delta_eff, eq_factor = 1); q / x / y / rec of the base are not used.
+// 1 / delta_eff, eq_factor = 1); q / x / y / rec of the base are not used.  With mat_ws set the chunk runs on its problems' own matrices and scalings.
 struct LockstepAdjointParams : LockstepParams {
   int nzP = 0, nzA = 0;
   const int *Pi = nullptr, *Pj = nullptr, *Ai = nullptr, *Aj = nullptr;       // Dev's assembly maps: row and column of every stored entry, the engine's CSC order

@@ -84,6 +84,13 @@ class Engine {
   int batch_adjoint_lockstep_device(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
                                     double *dP, double *dq, double *dA, double *dl, double *du, double *arec, void *stream);
   int lockstep_adjoint_last_record(double *rec) const;
+  // The backward pass with a P_val / A_val per problem (include/osqp_hip.h osqp_hip_batch_adjoint_lockstep_mat): Px / Ax as batch_solve_lockstep_mat takes
+  // them, the rest as above; serves the handles both that entry and batch_adjoint_lockstep serve.
+  int batch_adjoint_lockstep_mat(int nbatch, const double *Px, const double *Ax, const double *l, const double *u, const double *x, const double *y, const double *dx,
+                                 const double *dy, double *dP, double *dq, double *dA, double *dl, double *du, double *arec);
+  int batch_adjoint_lockstep_mat_device(int nbatch, const double *Px, const double *Ax, const double *l, const double *u, const double *x, const double *y, const double *dx,
+                                        const double *dy, double *dP, double *dq, double *dA, double *dl, double *du, double *arec, void *stream);
+  int lockstep_mat_adjoint_last_record(double *rec) const;
   // The backward pass of a batch on the direct lockstep route (include/osqp_hip.h osqp_hip_batch_adjoint_lockstep_direct; lockstep_hip.hip
   // lockstep_direct_adjoint_chunk): the same arguments and semantics on the handles batch_solve_lockstep_direct accepts, OSQP_FUNC_NOT_IMPLEMENTED elsewhere.
   int batch_adjoint_lockstep_direct(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
@@ -186,8 +193,10 @@ class Engine {
   double lsa_rec_[OSQP_HIP_LOCKSTEP_ADJOINT_LAST_REC] = {0, 0, 0, 0, 0, 0, 0, 0};     // record of the last lockstep adjoint call (osqp_hip_lockstep_adjoint_last_record)
   bool lockstep_adjoint_applies();
   // the arrays of a backward pass (host or device, as the entry says); one body per entry kind and one chunk loop serve both routes (direct: the
-  // direct route's applicability, work block, chunk function and record)
-  struct LockstepAdjointIO { const double *l, *u, *x, *y, *dx, *dy; double *dP, *dq, *dA, *dl, *du, *arec; };
+  // direct route's applicability, work block, chunk function and record).  mat: the entries with per-problem matrices (PCG route only; Px / Ax in the
+  // caller's CSC order, either may be nullptr) -- the matrix block is the forward's lsmw_, the record lsma_rec_ next to lsa_rec_.
+  struct LockstepAdjointIO { const double *l, *u, *x, *y, *dx, *dy; double *dP, *dq, *dA, *dl, *du, *arec; bool mat = false; const double *Px = nullptr, *Ax = nullptr; };
+  double lsma_rec_[OSQP_HIP_LOCKSTEP_MAT_ADJOINT_LAST_REC] = {0, 0, 0, 0, 0, 0, 0, 0};     // record of the last such call (osqp_hip_lockstep_mat_adjoint_last_record)
   int adjoint_lockstep_host(bool direct, int nbatch, const LockstepAdjointIO &h);
   int adjoint_lockstep_device(bool direct, int nbatch, const LockstepAdjointIO &a, void *stream);
   int run_lockstep_adjoint(bool direct, int nbatch, const LockstepAdjointIO &a, void *stream);

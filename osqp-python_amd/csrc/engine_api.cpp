@@ -928,6 +928,7 @@ int Engine::lockstep_polish_last_record(double *rec) const { return last_record(
 int Engine::lockstep_mat_last_record(double *rec) const { return last_record(lsm_rec_, OSQP_HIP_LOCKSTEP_MAT_LAST_REC, rec); }
 int Engine::lockstep_direct_last_record(double *rec) const { return last_record(lsd_rec_, OSQP_HIP_LOCKSTEP_DIRECT_LAST_REC, rec); }
 int Engine::lockstep_adjoint_last_record(double *rec) const { return last_record(lsa_rec_, OSQP_HIP_LOCKSTEP_ADJOINT_LAST_REC, rec); }
+int Engine::lockstep_mat_adjoint_last_record(double *rec) const { return last_record(lsma_rec_, OSQP_HIP_LOCKSTEP_MAT_ADJOINT_LAST_REC, rec); }
 int Engine::lockstep_direct_adjoint_last_record(double *rec) const { return last_record(lsda_rec_, OSQP_HIP_LOCKSTEP_DIRECT_ADJOINT_LAST_REC, rec); }
 
 int Engine::run_lockstep(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream,
@@ -1151,15 +1152,20 @@ bool Engine::lockstep_adjoint_applies() { return be::lockstep_adjoint_chunk && b
 // workspace and its record are not written.
 bool Engine::lockstep_direct_adjoint_applies() { return lockstep_direct_applies() && be::lockstep_direct_adjoint_chunk && be::device_assembly(); }
 
-// Both routes' chunk loop.  direct selects the applicability, the work block, the chunk function and the record.
+// Both routes' chunk loop.  direct selects the applicability, the work block, the chunk function and the record.  a.mat (PCG route): every chunk assembles
+// and equilibrates its problems' own matrices in the forward's matrix block (lsmw_: one block per handle, allocated by whichever entry comes first), which
+// this call therefore overwrites -- lockstep_mat_scaling answers OSQP_DATA_NOT_INITIALIZED until the next forward call.
 int Engine::run_lockstep_adjoint(bool direct, int nbatch, const LockstepAdjointIO &a, void *stream) {
   const int nzP = d_.nzP, nzA = d_.nzA;
+  const bool mat = a.mat && !direct;
   const size_t need = direct ? lockstep_direct_adjoint_ws_doubles(n, m, d_.wb.r) : lockstep_adjoint_ws_doubles(n, m);
+  const size_t mneed = lockstep_mat_ws_doubles(n, m, d_.A.nnz, d_.B.nnz);
   LockstepDirectAdjointParams p;                      // (the PCG route takes its LockstepAdjointParams base)
   if (direct) if (const int err = fill_lockstep_direct_view(p.v, stream)) return err;
   double *&ws = direct ? lsdaw_ : lsaw_;
   bool fresh = ensure_value_maps();
   if (!ws) { ws = dev_vec<double>(d_, need); fresh = true; }
+  if (mat && !lsmw_) { lsmw_ = dev_vec<double>(d_, mneed); fresh = true; }
   if (fresh) be::sync(d_);
   fill_batch_settings(p, 0);
   fill_lockstep_handle(p);
@@ -1169,6 +1175,11 @@ int Engine::run_lockstep_adjoint(bool direct, int nbatch, const LockstepAdjointI
   p.alpha = 1.0; p.rho0 = clamp_rho(1.0 / de); p.eq_factor = 1.0; p.cg_max = direct ? 0 : kMaxCg; p.pcg_rel = direct ? 0.0 : pol_.polish_pcg_tol;
   p.min_steps = 1 + std::max(0, (int)settings.polish_refine_iter); p.max_steps = 60; p.gain = 0.9;
   p.nzP = nzP; p.nzA = nzA; p.Pi = d_.Pi; p.Pj = d_.Pj; p.Ai = d_.Ai; p.Aj = d_.Aj; p.Pmap = reordered_ ? d_pvmap_ : nullptr; p.Amap = reordered_ ? d_avmap_ : nullptr;
+  double mst[kLsMatStat] = {0, 0}, mtot = 0;
+  if (mat) {
+    p.mat_ws = lsmw_; p.mat_stat = mst; p.mat_iters = std::max(0, (int)settings.scaling); p.pvmap = p.Pmap; p.avmap = p.Amap;
+    lsm_last_count_ = 0;                              // (the block is being overwritten)
+  }
   double tot[4] = {0, 0, 0, 0};
   int chunks = 0;
   auto at = [](auto *v, size_t off) { return v ? v + off : nullptr; };
@@ -1177,14 +1188,19 @@ int Engine::run_lockstep_adjoint(bool direct, int nbatch, const LockstepAdjointI
     p.count = std::min(kLsW, nbatch - b0);
     p.l = at(a.l, b * m); p.u = at(a.u, b * m); p.sx = a.x + b * n; p.sy = at(a.y, b * m); p.gx = a.dx + b * n; p.gy = at(a.dy, b * m);
     p.dP = at(a.dP, b * nzP); p.dq = at(a.dq, b * n); p.dA = at(a.dA, b * nzA); p.dl = at(a.dl, b * m); p.du = at(a.du, b * m); p.arec = at(a.arec, b * kAdjointRec);
+    if (mat) { p.Px = at(a.Px, b * nzP); p.Ax = at(a.Ax, b * nzA); }
     double st[4] = {0, 0, 0, 0};
     const int err = direct ? be::lockstep_direct_adjoint_chunk(d_, p, stream, st) : be::lockstep_adjoint_chunk(d_, p, stream, st);
     if (err) return err;
-    tot[0] = std::max(tot[0], st[0]); tot[1] += st[1]; tot[2] += st[2]; tot[3] += st[3];
+    tot[0] = std::max(tot[0], st[0]); tot[1] += st[1]; tot[2] += st[2]; tot[3] += st[3]; mtot += mst[0];
   }
   static_assert(OSQP_HIP_LOCKSTEP_ADJOINT_LAST_REC == OSQP_HIP_LOCKSTEP_DIRECT_ADJOINT_LAST_REC, "one record text for both adjoint routes");
   const double r[OSQP_HIP_LOCKSTEP_ADJOINT_LAST_REC] = {(double)chunks, (double)kLsW, tot[0], tot[1], tot[2], tot[3], (double)(need * sizeof(double)), 0.0};
   std::copy(r, r + OSQP_HIP_LOCKSTEP_ADJOINT_LAST_REC, direct ? lsda_rec_ : lsa_rec_);
+  if (mat) {
+    const double rm[OSQP_HIP_LOCKSTEP_MAT_ADJOINT_LAST_REC] = {(double)chunks, (double)kLsW, tot[0], tot[1], tot[2], tot[3], (double)(mneed * sizeof(double)), mtot};
+    std::copy(rm, rm + OSQP_HIP_LOCKSTEP_MAT_ADJOINT_LAST_REC, lsma_rec_);
+  }
   return OSQP_NO_ERROR;
 }
 
@@ -1193,20 +1209,23 @@ int Engine::adjoint_lockstep_host(bool direct, int nbatch, const LockstepAdjoint
   if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   if (nbatch <= 0 || !h.x || (!h.y && m > 0) || !h.dx) return OSQP_DATA_VALIDATION_ERROR;
   be::activate(d_);
-  if (!(direct ? lockstep_direct_adjoint_applies() : lockstep_adjoint_applies())) return OSQP_FUNC_NOT_IMPLEMENTED;
+  if (!(direct ? lockstep_direct_adjoint_applies() : lockstep_adjoint_applies()) || (h.mat && (direct || !lockstep_mat_applies()))) return OSQP_FUNC_NOT_IMPLEMENTED;
   be::ext_wait(d_);
   DevScratch &sc = direct ? lsdabuf_ : lsabuf_;
   const size_t nb = (size_t)nbatch, N = nb * n, M = nb * m, NP = nb * (size_t)d_.nzP, NA = nb * (size_t)d_.nzA;
-  // [l | u | x | y | dx | dy | dP | dq | dA | dl | du | arec]
-  const size_t need = 3 * N + 6 * M + NP + NA + nb * kAdjointRec;
+  const size_t MP = (h.mat && h.Px) ? NP : 0, MA = (h.mat && h.Ax) ? NA : 0;
+  // [l | u | x | y | dx | dy | dP | dq | dA | dl | du | arec | Px | Ax]   (the last two: per-problem matrices, where given)
+  const size_t need = 3 * N + 6 * M + NP + NA + nb * kAdjointRec + MP + MA;
   if (need > sc.cap) { if (sc.buf) be::dfree(d_, sc.buf); sc.cap = 0; sc.buf = dev_vec<double>(d_, need); sc.cap = need; }
   double *d_l = sc.buf, *d_u = d_l + M, *d_x = d_u + M, *d_y = d_x + N, *d_dx = d_y + M, *d_dy = d_dx + N;
   double *o_dP = d_dy + M, *o_dq = o_dP + NP, *o_dA = o_dq + N, *o_dl = o_dA + NA, *o_du = o_dl + M, *o_rec = o_du + M;
+  double *d_Px = o_rec + nb * kAdjointRec, *d_Ax = d_Px + MP;
   auto up = [&](double *dst, const double *src, size_t cnt) { if (src && cnt) be::h2d(d_, dst, src, sizeof(double) * cnt); };
-  up(d_l, h.l, M); up(d_u, h.u, M); up(d_x, h.x, N); up(d_y, h.y, M); up(d_dx, h.dx, N); up(d_dy, h.dy, M);
+  up(d_l, h.l, M); up(d_u, h.u, M); up(d_x, h.x, N); up(d_y, h.y, M); up(d_dx, h.dx, N); up(d_dy, h.dy, M); up(d_Px, h.Px, MP); up(d_Ax, h.Ax, MA);
   be::sync(d_);
   const LockstepAdjointIO dv{h.l ? d_l : nullptr, h.u ? d_u : nullptr, d_x, d_y, d_dx, h.dy ? d_dy : nullptr, h.dP ? o_dP : nullptr, h.dq ? o_dq : nullptr,
-                             h.dA ? o_dA : nullptr, h.dl ? o_dl : nullptr, h.du ? o_du : nullptr, h.arec ? o_rec : nullptr};
+                             h.dA ? o_dA : nullptr, h.dl ? o_dl : nullptr, h.du ? o_du : nullptr, h.arec ? o_rec : nullptr,
+                             h.mat, MP ? d_Px : nullptr, MA ? d_Ax : nullptr};
   if (const int err = run_lockstep_adjoint(direct, nbatch, dv, nullptr)) return err;
   auto down = [&](double *dst, const double *src, size_t cnt) { if (dst && cnt) be::d2h(d_, dst, src, sizeof(double) * cnt); };
   down(h.dP, o_dP, NP); down(h.dq, o_dq, N); down(h.dA, o_dA, NA); down(h.dl, o_dl, M); down(h.du, o_du, M); down(h.arec, o_rec, nb * kAdjointRec);
@@ -1218,7 +1237,7 @@ int Engine::adjoint_lockstep_device(bool direct, int nbatch, const LockstepAdjoi
   if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   if (nbatch < 0) return OSQP_DATA_VALIDATION_ERROR;
   be::activate(d_);
-  if (!(direct ? lockstep_direct_adjoint_applies() : lockstep_adjoint_applies())) return OSQP_FUNC_NOT_IMPLEMENTED;
+  if (!(direct ? lockstep_direct_adjoint_applies() : lockstep_adjoint_applies()) || (a.mat && (direct || !lockstep_mat_applies()))) return OSQP_FUNC_NOT_IMPLEMENTED;
   if (nbatch == 0) return OSQP_NO_ERROR;              // (the applicability query, as osqp_hip_batch_solve_lockstep_device answers it)
   if (!a.x || (!a.y && m > 0) || !a.dx) return OSQP_DATA_VALIDATION_ERROR;
   be::ext_wait(d_);
@@ -1233,6 +1252,14 @@ int Engine::batch_adjoint_lockstep(int nbatch, const double *l, const double *u,
 int Engine::batch_adjoint_lockstep_device(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
                                           double *dP, double *dq, double *dA, double *dl, double *du, double *arec, void *stream) {
   return adjoint_lockstep_device(false, nbatch, {l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec}, stream);
+}
+int Engine::batch_adjoint_lockstep_mat(int nbatch, const double *Px, const double *Ax, const double *l, const double *u, const double *x, const double *y, const double *dx,
+                                       const double *dy, double *dP, double *dq, double *dA, double *dl, double *du, double *arec) {
+  return adjoint_lockstep_host(false, nbatch, {l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec, true, Px, Ax});
+}
+int Engine::batch_adjoint_lockstep_mat_device(int nbatch, const double *Px, const double *Ax, const double *l, const double *u, const double *x, const double *y, const double *dx,
+                                              const double *dy, double *dP, double *dq, double *dA, double *dl, double *du, double *arec, void *stream) {
+  return adjoint_lockstep_device(false, nbatch, {l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec, true, Px, Ax}, stream);
 }
 int Engine::batch_adjoint_lockstep_direct(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
                                           double *dP, double *dq, double *dA, double *dl, double *du, double *arec) {

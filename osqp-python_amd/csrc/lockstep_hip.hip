@@ -26,7 +26,8 @@
 // Transposes (LDS tiles, coalesced on both sides) move a chunk between the API's [nbatch][n] row-major arrays and the block vectors; they apply
 // k_batch_admm's load / store scaling and, for a handle that works on a permuted copy, gather / scatter through the permutations.
 // The BACKWARD pass of a chunk (osqp_hip_batch_adjoint_lockstep; lockstep_adjoint_chunk below): the adjoint system of every problem by the recurrence polish
-// and the single-QP adjoint run, which is this file's iteration with alpha = 1 and a fixed rho -- see "adjoint derivatives of a chunk".
+// and the single-QP adjoint run, which is this file's iteration with alpha = 1 and a fixed rho -- see "adjoint derivatives of a chunk"; with matrices of
+// the chunk's own (osqp_hip_batch_adjoint_lockstep_mat) the same pass behind the forward's assembly and equilibration, on the k_lsm_* instantiations.
 // POLISH (settings.polishing): the chunk's SOLVED problems are polished by that same recurrence between the ADMM loop and the transposes out -- see
 // "polish of a chunk".
 #include "hip_common.h"
@@ -134,9 +135,10 @@ __device__ __forceinline__ void ls_rows(const DevCsr &M, F &f) {
 // a scaling D / Dinv / E / Einv: the handle's vector, or (MAT) the problem's own column of a block
 template <bool MAT> __device__ __forceinline__ double ls_sv(const double *v, int j, int lane) { return MAT ? v[IX(j)] : v[j]; }
 // a kernel body with and without per-problem matrices: NAME the shared route's kernel, k_lsm_NAME the other
-#define LS_KERNEL_PAIR(NAME) \
-  __global__ __launch_bounds__(256) void k_ls_##NAME(LsK k) { ls_##NAME<false>(k); } \
-  __global__ __launch_bounds__(256) void k_lsm_##NAME(LsK k) { ls_##NAME<true>(k); }
+#define LS_KERNEL_PAIR_OF(ARG, NAME) \
+  __global__ __launch_bounds__(256) void k_ls_##NAME(ARG k) { ls_##NAME<false>(k); } \
+  __global__ __launch_bounds__(256) void k_lsm_##NAME(ARG k) { ls_##NAME<true>(k); }
+#define LS_KERNEL_PAIR(NAME) LS_KERNEL_PAIR_OF(LsK, NAME)
 
 // Minv = 1 / diag(K_b) = 1 / (B_jj + sum_i rho_i,b A_ij^2), for the problems whose rho has just been set (one pass over the A' part of B, squared entries)
 struct FMinv {
@@ -584,11 +586,14 @@ LS_KERNEL_PAIR(store_m)
 // in with the classification (step_rules.h adjoint_active: the text k_batch_adjoint and EAdjClass call), the progress rule per problem (term_rules.h
 // recurrence_ends: Engine::run_recurrence's), the unscaling and the residual of the unregularised system, the transposes out and the gradients at the
 // stored entries.  Extra block vectors: the unscaled x, dx, r_x (n) and y, dy, r_y (m) and the row codes (ints, packed like iw).
+// The five kernels here that read matrix values or scalings (load_n, class, unscale, resm, resn) are bodies ls_adj_NAME<MAT> like the forward's: k_ls_adj_NAME
+// on the handle's, k_lsm_adj_NAME on the chunk's own matrix block ("matrices of a chunk" below), D / Dinv / E / Einv per lane and c, 1 / c from the rows
+// SC_C / SC_CINV of the scalar state.  The others read neither and serve both.
 struct LsAK { LockstepAdjointParams P; LsWs w; LsAdjWs a; };
 enum LsAdjSlot { AS_ACT = PS_BN /* sum: active rows (before the first k_ls_rhs) */, AS_RM = PS_M0 /* max, after the last step: */, AS_GM, AS_RN, AS_GN };
 
 // x (kept), x~ = Dinv x into p (the classification's operand; k_ls_rhs overwrites it), q~ = c D dx, dx (kept), the zero start
-__global__ __launch_bounds__(256) void k_ls_adj_load_n(LsAK k) {
+template <bool MAT> __device__ __forceinline__ void ls_adj_load_n(const LsAK &k) {
   __shared__ double tile[64][65];
   const LockstepAdjointParams &P = k.P;
   const int lane = ls_lane(), wv = ls_wave(), j0 = blockIdx.x * 64;
@@ -596,7 +601,7 @@ __global__ __launch_bounds__(256) void k_ls_adj_load_n(LsAK k) {
   for (int jl = wv; jl < 64 && j0 + jl < P.n; jl += 4) {
     const int j = j0 + jl;
     const double xv = tile[lane][jl];
-    k.a.ax[IX(j)] = xv; k.w.p[IX(j)] = in_x(xv, P.Dinv[j]);
+    k.a.ax[IX(j)] = xv; k.w.p[IX(j)] = in_x(xv, ls_sv<MAT>(P.Dinv, j, lane));
     k.w.x[IX(j)] = 0.0; k.w.xs[IX(j)] = 0.0; k.w.dx[IX(j)] = 0.0;
   }
   __syncthreads();
@@ -604,9 +609,10 @@ __global__ __launch_bounds__(256) void k_ls_adj_load_n(LsAK k) {
   for (int jl = wv; jl < 64 && j0 + jl < P.n; jl += 4) {
     const int j = j0 + jl;
     const double gv = tile[lane][jl];
-    k.a.gdx[IX(j)] = gv; k.w.q[IX(j)] = in_q(P.c, P.D[j], gv);
+    k.a.gdx[IX(j)] = gv; k.w.q[IX(j)] = in_q(MAT ? k.w.sc[SC_C * W + lane] : P.c, ls_sv<MAT>(P.D, j, lane), gv);
   }
 }
+LS_KERNEL_PAIR_OF(LsAK, adj_load_n)
 // y, dy (kept) and the caller's bounds (clamped, unscaled: k_ls_adj_class turns them into the recurrence's)
 __global__ __launch_bounds__(256) void k_ls_adj_load_m(LsAK k) {
   __shared__ double tile[64][65];
@@ -632,30 +638,31 @@ __global__ __launch_bounds__(256) void k_ls_adj_load_m(LsAK k) {
   }
 }
 // z = Einv (A x~) in the caller's units, the row's code, the recurrence's bounds (active: l = u = z = -E dy; the others free) and zero start
-struct FAdjClass {
+template <bool MAT> struct FAdjClass {
   const LsWs &w; const LsAdjWs &a; const double *E, *Einv; int has_dy, lane;
   double cnt = 0;
   __device__ __forceinline__ void begin(int) {}
   __device__ __forceinline__ void load(int c, double (&g)[1]) const { g[0] = w.p[IX(c)]; }
   __device__ __forceinline__ void fma(int, double v, const double (&g)[1], double (&acc)[1]) const { acc[0] += v * g[0]; }
   __device__ __forceinline__ void row(int i, const double (&acc)[1]) {
-    const double zi = Einv[i] * acc[0];
+    const double zi = ls_sv<MAT>(Einv, i, lane) * acc[0];
     const RowActive act = adjoint_active(zi, w.l[IX(i)], w.u[IX(i)], a.ay[IX(i)]);
     const int kc = act.low ? 1 : (act.upp ? 2 : 0);
-    const double b = (kc && has_dy) ? -(E[i] * a.gdy[IX(i)]) : 0.0;
+    const double b = (kc && has_dy) ? -(ls_sv<MAT>(E, i, lane) * a.gdy[IX(i)]) : 0.0;
     a.code[IX(i)] = kc;
     w.l[IX(i)] = kc ? b : -OSQP_INFTY; w.u[IX(i)] = kc ? b : OSQP_INFTY;
     w.z[IX(i)] = b; w.zt[IX(i)] = 0.0; w.y[IX(i)] = 0.0; w.dy[IX(i)] = 0.0;
     cnt += kc ? 1.0 : 0.0;
   }
 };
-__global__ __launch_bounds__(256) void k_ls_adj_class(LsAK k) {
+template <bool MAT> __device__ __forceinline__ void ls_adj_class(const LsAK &k) {
   __shared__ double lds[256];
-  FAdjClass f{k.w, k.a, k.P.E, k.P.Einv, k.P.gy != nullptr, ls_lane()};
-  ls_rows<1, 1>(k.P.A, f);
+  FAdjClass<MAT> f{k.w, k.a, k.P.E, k.P.Einv, k.P.gy != nullptr, ls_lane()};
+  ls_rows<1, 1, MAT>(k.P.A, f);
   const double vs[1] = {f.cnt};
   ls_put<0, 1>(k.w.part, AS_ACT, vs, vs, lds);
 }
+LS_KERNEL_PAIR_OF(LsAK, adj_class)
 // the chunk's per-problem state: rho_bar = 1 / delta_eff with equality factor 1; a problem with more active rows than variables (status 2) and the
 // lanes >= count are finished before the first step
 __global__ __launch_bounds__(256) void k_ls_adj_init(LsAK k) {
@@ -695,16 +702,19 @@ __global__ __launch_bounds__(256) void k_ls_adj_decide(LsAK k) {
   if (threadIdx.x == 0) { k.w.word[WD_LIVE] = __popcll(live); k.w.word[WD_RHOANY] = 0; k.w.word[WD_PCGSUM] = pcg; }
 }
 // r_x = D x,  r_y = cinv E y on the active rows and exactly 0 elsewhere (y itself too: the residual's A' multiplies it)
-__global__ __launch_bounds__(256) void k_ls_adj_unscale(LsAK k) {
+// (MAT: element e of a block is row e >> 6 of lane e & 63 -- this thread's lane, the stride being a multiple of 64 -- so the problem's own D, E sit at e)
+template <bool MAT> __device__ __forceinline__ void ls_adj_unscale(const LsAK &k) {
   const size_t nt = (size_t)k.P.n * 64, mt = (size_t)k.P.m * 64, stride = (size_t)gridDim.x * 256;
-  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < nt; e += stride) k.a.rx[e] = k.P.D[e >> 6] * k.w.x[e];
+  const double cinv = MAT ? k.w.sc[SC_CINV * W + ls_lane()] : k.P.cinv;
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < nt; e += stride) k.a.rx[e] = k.P.D[MAT ? e : e >> 6] * k.w.x[e];
   for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < mt; e += stride) {
     const double ys = k.a.code[e] ? k.w.y[e] : 0.0;
-    k.w.y[e] = ys; k.a.ry[e] = k.P.cinv * k.P.E[e >> 6] * ys;
+    k.w.y[e] = ys; k.a.ry[e] = cinv * k.P.E[MAT ? e : e >> 6] * ys;
   }
 }
+LS_KERNEL_PAIR_OF(LsAK, adj_unscale)
 // rows n .. n + active of g - K_a r:  -dy_i - (A r_x)_i  on the active rows (adjoint_hip.hip EAdjResM)
-struct FAdjResM {
+template <bool MAT> struct FAdjResM {
   const LsWs &w; const LsAdjWs &a; const double *Einv; int lane;
   double rm = 0, gm = 0;
   __device__ __forceinline__ void begin(int) {}
@@ -713,18 +723,19 @@ struct FAdjResM {
   __device__ __forceinline__ void row(int i, const double (&acc)[1]) {
     if (!a.code[IX(i)]) return;
     const double dyi = a.gdy[IX(i)];
-    rm = nanmax(rm, fabs(dyi + Einv[i] * acc[0])); gm = nanmax(gm, fabs(dyi));
+    rm = nanmax(rm, fabs(dyi + ls_sv<MAT>(Einv, i, lane) * acc[0])); gm = nanmax(gm, fabs(dyi));
   }
 };
-__global__ __launch_bounds__(256) void k_ls_adj_resm(LsAK k) {
+template <bool MAT> __device__ __forceinline__ void ls_adj_resm(const LsAK &k) {
   __shared__ double lds[2 * 256];
-  FAdjResM f{k.w, k.a, k.P.Einv, ls_lane()};
-  ls_rows<1, 1>(k.P.A, f);
+  FAdjResM<MAT> f{k.w, k.a, k.P.Einv, ls_lane()};
+  ls_rows<1, 1, MAT>(k.P.A, f);
   const double vm[2] = {f.rm, f.gm};
   ls_put<2, 0>(k.w.part, AS_RM, vm, vm, lds);
 }
+LS_KERNEL_PAIR_OF(LsAK, adj_resm)
 // rows 0 .. n:  -dx_j - (P r_x + A_a' r_a)_j;  row j of B [x~; y~] is  c D_j (P r_x + A' r_y)_j + sigma x~_j  (adjoint_hip.hip EAdjResN)
-struct FAdjResN {
+template <bool MAT> struct FAdjResN {
   const LsWs &w; const LsAdjWs &a; const double *Dinv; double sigma, cinv; int n, lane;
   double rn = 0, gn = 0;
   __device__ __forceinline__ void begin(int) {}
@@ -734,17 +745,20 @@ struct FAdjResN {
     acc[0] += pn ? p : 0.0; acc[1] += pn ? 0.0 : p;
   }
   __device__ __forceinline__ void row(int j, const double (&acc)[2]) {
-    const double kr = cinv * Dinv[j] * ((acc[0] - sigma * w.x[IX(j)]) + acc[1]), dxj = a.gdx[IX(j)];
+    const double kr = cinv * ls_sv<MAT>(Dinv, j, lane) * ((acc[0] - sigma * w.x[IX(j)]) + acc[1]), dxj = a.gdx[IX(j)];
     rn = nanmax(rn, fabs(dxj + kr)); gn = nanmax(gn, fabs(dxj));
   }
 };
-__global__ __launch_bounds__(256) void k_ls_adj_resn(LsAK k) {
+// (sigma sits on B's diagonal after the equilibration on both routes: the term is the same with per-problem matrices)
+template <bool MAT> __device__ __forceinline__ void ls_adj_resn(const LsAK &k) {
   __shared__ double lds[2 * 256];
-  FAdjResN f{k.w, k.a, k.P.Dinv, k.P.sigma, k.P.cinv, k.P.n, ls_lane()};
-  ls_rows<1, 2>(k.P.B, f);
+  const int lane = ls_lane();
+  FAdjResN<MAT> f{k.w, k.a, k.P.Dinv, k.P.sigma, MAT ? k.w.sc[SC_CINV * W + lane] : k.P.cinv, k.P.n, lane};
+  ls_rows<1, 2, MAT>(k.P.B, f);
   const double vm[2] = {f.rn, f.gn};
   ls_put<2, 0>(k.w.part, AS_RN, vm, vm, lds);
 }
+LS_KERNEL_PAIR_OF(LsAK, adj_resn)
 // the record: {status, active rows, residual max |g - K_a r| / max |g|, recurrence steps}
 __global__ __launch_bounds__(256) void k_ls_adj_final(LsAK k) {
   __shared__ double lds[256];
@@ -1323,20 +1337,44 @@ void ls_pcg(LsRun &R, const LsPcgKernels &K, const LsK &k, int &est) {
   est = std::max(2, R.words[WD_CGIT] + 1);
 }
 
-// The recurrence of polish and of both adjoints: while a problem is live and below the step cap -- step() (the solve and k_ls_upd), the residuals (km:
-// what k_ls_resm reads A through), decide(), a read of the words.  Returns the steps taken.
+// The recurrence of polish and of the adjoints: while a problem is live and below the step cap -- step() (the solve and k_ls_upd), the residuals (K: the
+// handle's matrices or the chunk's own; km: what K.resm reads A through), decide(), a read of the words.  Returns the steps taken.
 template <class Step, class Decide>
-int ls_recurrence(LsRun &R, const LsK &km, const LsK &kn, int max_steps, Step step, Decide decide) {
+int ls_recurrence(LsRun &R, const LsPcgKernels &K, const LsK &km, const LsK &kn, int max_steps, Step step, Decide decide) {
   int steps = 0;
   while (R.words[WD_LIVE] > 0 && steps < max_steps) {
     steps++;
     step();
-    if (km.P.m > 0) R.go(k_ls_resm, km.w.G, km);
-    R.go(k_ls_resn, kn.w.G, kn);
+    if (km.P.m > 0) R.go(K.resm, km.w.G, km);
+    R.go(K.resn, kn.w.G, kn);
     decide();
     R.fetch();
   }
   return steps;
+}
+
+// The matrices of a chunk ("matrices of a chunk" above), for the forward and the backward pass alike.  ls_mat_block: the carve of the matrix block -- asked
+// "does it fit" before any event or launch -- and P's matrices and scalings pointed at it.  ls_mat_prepare: the assembly and the equilibration, in front of
+// the chunk's transposes in; R.em marks their end, mat_stat[1] is their launch count.  The scratch (dt in r, et in t, the problem's q in q) and the rows
+// SC_C / SC_CINV / SC_CT belong to the work block of the chunk that calls.
+int ls_mat_block(const Dev &d, LockstepParams &P, LsMat &mt) {
+  LsCursor cm{P.mat_ws};
+  if (!d.Praw || !d.Araw || P.polish) return OSQP_FUNC_NOT_IMPLEMENTED;
+  if (!lockstep_mat_layout(cm, P.n, P.m, P.A.nnz, P.B.nnz, mt)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  mt.Praw = d.Praw; mt.Araw = d.Araw; mt.Pm1 = d.Pm1; mt.Pm2 = d.Pm2; mt.AmA = d.AmA; mt.AmB = d.AmB; mt.Bdiag = d.Bdiag; mt.nzP = d.nzP; mt.nzA = d.nzA;
+  P.A.val = mt.Aval; P.B.val = mt.Bval; P.D = mt.D; P.Dinv = mt.Dinv; P.E = mt.E; P.Einv = mt.Einv;
+  return OSQP_NO_ERROR;
+}
+void ls_mat_prepare(LsRun &R, const LsMK &km) {
+  const int G = km.w.G, tn = (km.P.n + 63) / 64;
+  const long launches0 = R.launches;
+  R.go(k_lsm_begin, tn, km);
+  if (km.t.nzA > 0) R.go(k_lsm_asm<false>, (km.t.nzA + 63) / 64, km);
+  if (km.t.nzP > 0) R.go(k_lsm_asm<true>, (km.t.nzP + 63) / 64, km);
+  for (int it = 0; it < km.P.mat_iters; it++) { R.go(k_lsm_norms, G, km); R.go(k_lsm_scale, G, km); R.go(k_lsm_cost, 1, km); R.go(k_lsm_cost_apply, G, km); }
+  R.go(k_lsm_finish, G, km);
+  R.em.record(R.s);
+  if (km.P.mat_stat) km.P.mat_stat[1] = (double)(R.launches - launches0);
 }
 
 // The adjoint's launches after the recurrence that both backward passes share: the outputs the caller asked for
@@ -1393,31 +1431,17 @@ int lockstep_chunk(Dev &d, const LockstepParams &p, void *stream, double *stat) 
   LsK k{p, {}};
   LsMat mt{};
   LsPK kq{p, {}, {}};
-  LsCursor c{p.ws}, cm{p.mat_ws}, cp{p.pol_ws};
+  LsCursor c{p.ws}, cp{p.pol_ws};
   if (!lockstep_layout(c, n, m, k.w, nullptr)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   // per-problem matrices ("matrices of a chunk" above): the chunk's kernels read the matrix block in place of the handle's arrays
-  if (mat) {
-    if (!d.Praw || !d.Araw || p.polish) return OSQP_FUNC_NOT_IMPLEMENTED;
-    if (!lockstep_mat_layout(cm, n, m, p.A.nnz, p.B.nnz, mt)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-    mt.Praw = d.Praw; mt.Araw = d.Araw; mt.Pm1 = d.Pm1; mt.Pm2 = d.Pm2; mt.AmA = d.AmA; mt.AmB = d.AmB; mt.Bdiag = d.Bdiag; mt.nzP = d.nzP; mt.nzA = d.nzA;
-    k.P.A.val = mt.Aval; k.P.B.val = mt.Bval; k.P.D = mt.D; k.P.Dinv = mt.Dinv; k.P.E = mt.E; k.P.Einv = mt.Einv;
-  }
+  if (mat) if (const int err = ls_mat_block(d, k.P, mt)) return err;
   if (pol && !lockstep_polish_layout(cp, n, m, kq.s)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   const LsWs &w = k.w;
   const int G = w.G;
   const LsPcgKernels &K = mat ? kLsOwnMat : kLsShared;
   LsRun R(s, w.word, p.count);
   R.e0.record(s);
-  if (mat) {
-    const LsMK km{k.P, w, mt};
-    R.go(k_lsm_begin, tn, km);
-    if (mt.nzA > 0) R.go(k_lsm_asm<false>, (mt.nzA + 63) / 64, km);
-    if (mt.nzP > 0) R.go(k_lsm_asm<true>, (mt.nzP + 63) / 64, km);
-    for (int it = 0; it < p.mat_iters; it++) { R.go(k_lsm_norms, G, km); R.go(k_lsm_scale, G, km); R.go(k_lsm_cost, 1, km); R.go(k_lsm_cost_apply, G, km); }
-    R.go(k_lsm_finish, G, km);
-    R.em.record(s);
-    if (p.mat_stat) p.mat_stat[1] = (double)R.launches;
-  }
+  if (mat) ls_mat_prepare(R, LsMK{k.P, w, mt});
   const double t_begin = ls_now();
   auto late_now = [&]() { return p.time_limit > 0 && ls_now() - t_begin > p.time_limit; };
   auto residuals = [&]() { if (m > 0) R.go(K.resm, G, k); R.go(K.resn, G, k); };
@@ -1463,7 +1487,7 @@ int lockstep_chunk(Dev &d, const LockstepParams &p, void *stream, double *stat) 
       if (m > 0) R.go(k_ls_setrho, G, kp);
       R.go(k_ls_minv, G, kp);
       int cg_pol = 4;
-      pol_steps = ls_recurrence(R, kp, kp, kLsPolMaxSteps, [&]() { ls_pcg(R, kLsShared, kp, cg_pol); R.go(k_ls_upd, G, kp); }, [&]() { R.go(k_ls_pol_decide, 1, kq); });
+      pol_steps = ls_recurrence(R, kLsShared, kp, kp, kLsPolMaxSteps, [&]() { ls_pcg(R, kLsShared, kp, cg_pol); R.go(k_ls_upd, G, kp); }, [&]() { R.go(k_ls_pol_decide, 1, kq); });
       pol_pcg = R.words[WD_PCGSUM];
       if (m > 0) { R.go(k_ls_pol_cone, G, kq); R.go(k_ls_resm, G, kp); }
       R.go(k_ls_resn, G, kp);
@@ -1490,32 +1514,44 @@ int lockstep_chunk(Dev &d, const LockstepParams &p, void *stream, double *stat) 
 // The backward pass of one chunk, from the transposes in to the transposes out, on `stream` (nullptr: the solver's); returns when the chunk's results are
 // there.  The work block is the forward's set followed by the adjoint's own vectors; after every step of the recurrence the host reads the word block
 // and ends the chunk when no problem is live.  stat: {recurrence steps of the slowest problem, PCG iterations summed, kernel launches, GPU ms}.
+// PER-PROBLEM MATRICES (p.mat_ws != nullptr; include/osqp_hip.h osqp_hip_batch_adjoint_lockstep_mat): problem b's adjoint system is solved on its own P_b, A_b
+// under its own D_b, E_b, c_b -- the forward's preparation (ls_mat_prepare) runs in front of the transposes in, with the handle's q for every problem (the
+// adjoint does not depend on c in exact arithmetic; the shared adjoint runs on the handle's c too), and from then on the kernels are kLsOwnMat's and the
+// k_lsm_adj_* twins.  The preparation's scratch is dead before it is written again: q by k_ls_adj_load_n, t by k_ls_setrho (k_ls_rhs where m = 0 never
+// gathers it), r by the first k_ls_rhs.  c, 1 / c and ct are rows SC_C / SC_CINV / SC_CT of the scalar state of THIS work block (the adjoint's, not the
+// forward's); no kernel of the backward pass writes them -- k_ls_adj_init sets the rows below SC_C it needs, the PCG's folds SC_RZ .. SC_BETA.
 int lockstep_adjoint_chunk(Dev &d, const LockstepAdjointParams &p, void *stream, double *stat) {
   const hipStream_t s = ls_stream(d, stream);
   const int n = p.n, m = p.m, tn = (n + 63) / 64, tm = (m + 63) / 64;
+  const bool mat = p.mat_ws != nullptr;
   LsAK ka{p, {}, {}};
+  LsMat mt{};
   LsCursor c{p.ws};
   if (!lockstep_layout(c, n, m, ka.w, &ka.a)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  const LsK k{p, ka.w};                                 // what the forward's kernels take: the base of the parameters, the same block vectors
+  if (mat) if (const int err = ls_mat_block(d, ka.P, mt)) return err;
+  const LsK k{ka.P, ka.w};                              // what the forward's kernels take: the base of the parameters, the same block vectors
   const int G = k.w.G;
+  const LsPcgKernels &K = mat ? kLsOwnMat : kLsShared;
   LsRun R(s, k.w.word, p.count);
   R.e0.record(s);
+  if (mat) ls_mat_prepare(R, LsMK{k.P, k.w, mt});
 
-  R.go(k_ls_adj_load_n, tn, ka);
-  if (m > 0) { R.go(k_ls_adj_load_m, tm, ka); R.go(k_ls_adj_class, G, ka); }
+  R.go(mat ? k_lsm_adj_load_n : k_ls_adj_load_n, tn, ka);
+  if (m > 0) { R.go(k_ls_adj_load_m, tm, ka); R.go(mat ? k_lsm_adj_class : k_ls_adj_class, G, ka); }
   R.go(k_ls_adj_init, 1, ka);
   if (m > 0) R.go(k_ls_setrho, G, k);
-  R.go(k_ls_minv, G, k);
+  R.go(K.minv, G, k);
   R.fetch();
   int cg_est = 4;
-  const int step = ls_recurrence(R, k, k, p.max_steps, [&]() { ls_pcg(R, kLsShared, k, cg_est); R.go(k_ls_upd, G, k); }, [&]() { R.go(k_ls_adj_decide, 1, ka); });
-  R.go(k_ls_adj_unscale, G, ka);
-  if (m > 0) R.go(k_ls_adj_resm, G, ka);
-  R.go(k_ls_adj_resn, G, ka);
+  const int step = ls_recurrence(R, K, k, k, p.max_steps, [&]() { ls_pcg(R, K, k, cg_est); R.go(K.upd, G, k); }, [&]() { R.go(k_ls_adj_decide, 1, ka); });
+  R.go(mat ? k_lsm_adj_unscale : k_ls_adj_unscale, G, ka);
+  if (m > 0) R.go(mat ? k_lsm_adj_resm : k_ls_adj_resm, G, ka);
+  R.go(mat ? k_lsm_adj_resn : k_ls_adj_resn, G, ka);
   R.go(k_ls_adj_final, 1, ka);
   ls_adjoint_outputs(R, ka, tn, tm);
   const int pcg_sum = R.words[WD_PCGSUM];
   const float ms = R.finish();
+  if (mat && p.mat_stat) p.mat_stat[0] = LsRun::ms(R.e0, R.em);
   if (stat) { stat[0] = step; stat[1] = pcg_sum; stat[2] = (double)R.launches; stat[3] = ms; }
   return OSQP_NO_ERROR;
 }
@@ -1607,7 +1643,7 @@ int lockstep_direct_adjoint_chunk(Dev &d, const LockstepDirectAdjointParams &p, 
   R.go(k_lwa_zero, G, D.k);
   D.factor(R);
   R.fetch();
-  const int step = ls_recurrence(R, D.kv, D.kb, p.max_steps, [&]() { D.solve(R); D.long_rows(R, 0); }, [&]() { R.go(k_ls_adj_decide, 1, ka); });
+  const int step = ls_recurrence(R, kLsShared, D.kv, D.kb, p.max_steps, [&]() { D.solve(R); D.long_rows(R, 0); }, [&]() { R.go(k_ls_adj_decide, 1, ka); });
   R.go(k_ls_adj_unscale, G, ka);
   long_rows_of(w.x);
   R.go(k_ls_adj_resm, G, kc);

@@ -19,7 +19,7 @@ threads.  Here one persistent engine handle plays that role:
     factor-model portfolio QP, which the lockstep route declines); a handle the chosen route declines raises as ``'lockstep'`` always has.
     With ``large_batch='lockstep'`` (one rank) a forward with 2-D P_val and / or A_val that the single launch declines makes ONE call of the lockstep
     route with per-element matrices (osqp_hip_batch_solve_lockstep_mat; ``mat_lockstep_launches`` counts them) in place of the per-element loop; its
-    backward stays the per-element loop.
+    backward is the per-element loop unless ``large_backward='lockstep'`` (below).
 
 Like the reference, a batch element that is not solved raises RuntimeError (:158-162).
 
@@ -35,7 +35,11 @@ the batch sum -- or, with ``large_backward='lockstep'`` (default ``'loop'``: unc
 (``osqp_hip_batch_adjoint_lockstep``; ``adjoint_launches`` rises by 1; an element whose adjoint system was not solved raises RuntimeError as the
 per-element route does), or, with ``large_backward='lockstep_direct'``, ONE call of its direct form on a Woodbury handle with a diagonal K0
 (``osqp_hip_batch_adjoint_lockstep_direct``: the backward of ``large_batch='lockstep_direct'``; a handle the route declines goes on to the per-element
-loop, as with ``'lockstep'``).  A ``torch.distributed`` job (world size > 1) raises NotImplementedError in backward.  With no input requiring grad,
+loop, as with ``'lockstep'``).  With ``large_backward='lockstep'`` and 2-D P_val and / or A_val that the batch adjoint kernel declines, the backward is
+ONE call of the lockstep adjoint with per-element matrices (``osqp_hip_batch_adjoint_lockstep_mat``: every element's adjoint system on its own matrices
+and scaling; ``adjoint_launches`` rises by 1 and ``mat_lockstep_adjoint_launches`` counts these calls; host tensors through the host entry, ROCm tensors
+zero-copy through the device entry) in place of update(Px, Ax) + the single-handle adjoint per element; a handle that entry declines goes on to the
+per-element loop.  A ``torch.distributed`` job (world size > 1) raises NotImplementedError in backward.  With no input requiring grad,
 forward behaves exactly as before.
 """
 import numpy as np
@@ -81,6 +85,7 @@ class OSQP(Module):
         self.last_adjoint_rec = None # (nb, 4) record of the last backward: status, active rows, residual, reserved (ext_hip ADJOINT_FIELDS)
         self._grad_maps = None
         self.mat_lockstep_launches = 0   # calls of the lockstep route with per-element matrices made by this layer's forwards (large_batch='lockstep')
+        self.mat_lockstep_adjoint_launches = 0   # calls of the lockstep adjoint with per-element matrices made by this layer's backwards (large_backward='lockstep')
 
     # ------------------------------------------------------------------ the persistent handle
     def _matrices(self, P_val, A_val):
@@ -281,10 +286,12 @@ class OSQP(Module):
                 if k in res: res[k][i] = v
         return {k: torch.as_tensor(v) for k, v in res.items()}
 
-    def _backward_lockstep(self, ext, l_val, u_val, x, y, g, nb, want):
+    def _backward_lockstep(self, ext, l_val, u_val, x, y, g, nb, want, P_val=None, A_val=None):
         """Backward of a shared-matrix batch past the batch adjoint kernel, with large_backward='lockstep' or 'lockstep_direct': one call of the lockstep
         adjoint (or of its direct form) for the whole batch (cuda tensors: zero-copy through the device entry on torch's current stream).  An element whose adjoint system was not solved raises as
-        _backward_loop does.  None: this handle is not on the route (the caller goes on to the per-element loop)."""
+        _backward_loop does.  None: this handle is not on the route (the caller goes on to the per-element loop).
+        P_val / A_val (2-D; 'lockstep' only): per-element matrices -- the same one call through osqp_hip_batch_adjoint_lockstep_mat[_device]."""
+        mat = P_val is not None or A_val is not None
         widths = {'dP': len(self._triu_pick), 'dq': self.n, 'dA': ext.nnz_A, 'dl': self.m, 'du': self.m}
         direct = self.large_backward == 'lockstep_direct'
         host_entry = ext.hip_batch_adjoint_lockstep_direct if direct else ext.hip_batch_adjoint_lockstep
@@ -297,19 +304,24 @@ class OSQP(Module):
                 res = {k: torch.empty((nb, widths[k]), dtype=torch.float64, device=dev) for k in want}
                 res['rec'] = torch.empty((nb, 4), dtype=torch.float64, device=dev)     # OSQP_HIP_ADJOINT_REC
                 ptr = lambda t: None if t is None else t.data_ptr()
+                Pxd = None if P_val is None else f64(P_val, P_val.shape[-1])[:, torch.as_tensor(self._triu_pick, device=dev)].contiguous()
+                Axd = None if A_val is None else f64(A_val, A_val.shape[-1])
+                matkw = dict(Px_ptr=ptr(Pxd), Ax_ptr=ptr(Axd)) if mat else {}
                 device_entry(nb, xd.data_ptr(), yd.data_ptr(), gd.data_ptr(), None, ld.data_ptr(), ud.data_ptr(),
                              ptr(res.get('dP')), ptr(res.get('dq')), ptr(res.get('dA')), ptr(res.get('dl')), ptr(res.get('du')),
-                             res['rec'].data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
+                             res['rec'].data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream, **matkw)
             else:
                 bc = lambda a, k: np.broadcast_to(np.asarray(a, dtype=float).reshape(-1, k), (nb, k))
+                matkw = dict(Px=None if P_val is None else _np(P_val)[:, self._triu_pick], Ax=None if A_val is None else _np(A_val)) if mat else {}
                 res = host_entry(bc(_np(torch.as_tensor(x)), self.n), bc(_np(torch.as_tensor(y)), self.m), bc(_np(g), self.n), None,
-                                 l=bc(_np(l_val), self.m), u=bc(_np(u_val), self.m), want=want)
+                                 l=bc(_np(l_val), self.m), u=bc(_np(u_val), self.m), want=want, **matkw)
                 res = {k: torch.as_tensor(v) for k, v in res.items()}
         except ValueError as e:
             if str(e) != str(int(osqp_amd.SolverError.OSQP_FUNC_NOT_IMPLEMENTED)):
                 raise
             return None
         self.adjoint_launches += 1
+        self.mat_lockstep_adjoint_launches += int(mat)
         rec = res['rec'].cpu().numpy()
         bad = np.nonzero(rec[:, 0] != 0)[0]
         if bad.size:
@@ -364,6 +376,8 @@ class OSQP(Module):
             res = None
             if self.large_backward in ('lockstep', 'lockstep_direct') and not batched[0] and not batched[2]:
                 res = self._backward_lockstep(s._solver, l_val, u_val, x, y, g, nb, want)      # shared matrices, any size: ONE call (osqp_hip_batch_adjoint_lockstep[_direct])
+            elif self.large_backward == 'lockstep':                                             # per-element matrices, any size: ONE call (osqp_hip_batch_adjoint_lockstep_mat)
+                res = self._backward_lockstep(s._solver, l_val, u_val, x, y, g, nb, want, P_val if batched[0] else None, A_val if batched[2] else None)
         if res is None:
             # outside the batch kernel (the forward ran _loop): the single-handle adjoint per element
             bc = lambda a, k: np.broadcast_to(np.asarray(a, dtype=float).reshape(-1, k), (nb, k))
