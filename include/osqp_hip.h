@@ -335,14 +335,19 @@ OSQPInt osqp_hip_lockstep_polish_last_record(OSQPSolver *solver, OSQPFloat *rec)
  * equilibration are 5 + 4 x settings.scaling launches in front of its transposes in.
  * INDEPENDENCE as above, a problem's matrices being part of the problem.  A reordered handle is served.  The handle's own matrices, scaling, iterates,
  * graphs and history are not touched.
- * POLISH is off on this entry whatever settings.polishing says: record fields 8 and 9 stay 0.
+ * POLISH as above: with settings.polishing every problem of a chunk that ends OSQP_SOLVED is polished on its OWN P_b, A_b under its own D_b, E_b, c_b --
+ * the active rows are guessed in the problem's own scaled space, the recurrence runs on the chunk's matrix block, the accept test uses the problem's own
+ * cost scale: what osqp_solve's polish does on a handle set up with that problem alone.  Record fields 8 and 9, the rejection rule, the time_limit rule
+ * and osqp_hip_lockstep_polish_last_record (filled by these calls too, the polish work block's bytes included) are the shared entry's.  With
+ * polishing = 0 record fields 8 and 9 stay 0 and the call issues exactly the launches it issues without this paragraph.
  * Returns OSQP_FUNC_NOT_IMPLEMENTED for whatever osqp_hip_batch_solve_lockstep declines, for a handle without device-side assembly, and for a handle whose
  * stored upper triangle of P holds a repeated (j, j) entry (the single-handle assembly sums those; this route has one writer per entry).
- * OUT OF SCOPE: polish with per-problem matrices, the direct (Woodbury) route, multi-rank sharding of this entry, repeated diagonal entries of P.  (The
- * backward pass with per-problem matrices: osqp_hip_batch_adjoint_lockstep_mat below.)
+ * OUT OF SCOPE: the direct (Woodbury) route, multi-rank sharding of this entry, repeated diagonal entries of P.  (The backward pass with per-problem
+ * matrices: osqp_hip_batch_adjoint_lockstep_mat below; it does not polish.)
  * osqp_hip_lockstep_mat_last_record: OSQP_HIP_LOCKSTEP_MAT_LAST_REC doubles {chunks, chunk width, ADMM iterations of the slowest problem, PCG iterations
- * summed, kernel launches of the whole call, GPU ms of the whole call, bytes of the matrix block, GPU ms spent in assembly + equilibration}; all zero
- * before the first call.  osqp_hip_lockstep_last_record is written as by any lockstep call.
+ * summed, kernel launches and GPU ms of the call -- assembly and equilibration included, polish apart (its launches, PCG iterations and GPU ms are
+ * osqp_hip_lockstep_polish_last_record's) --, bytes of the matrix block, GPU ms spent in assembly + equilibration}; all zero before the first call.
+ * osqp_hip_lockstep_last_record is written as by any lockstep call.
  * osqp_hip_lockstep_mat_scaling: D (n), E (m) and c of problem b of the LAST chunk the last such call processed, numbered as osqp_hip_get_scaling numbers
  * the handle's -- so that the per-problem equilibration can be checked directly.  OSQP_DATA_NOT_INITIALIZED before the first call or for b outside
  * that chunk -- and after a call of osqp_hip_batch_adjoint_lockstep_mat[_device], which overwrites the matrix block, until the next forward call. */

@@ -484,7 +484,7 @@ struct LockstepParams : BatchSettings {
   // on / off, rho_bar = 1 / delta_eff on the guessed-active rows, at least pol_min_steps = 1 + polish_refine_iter steps of the recurrence, its PCG to
   // ||r|| <= pol_pcg_rel ||rhs|| within pol_cg_max iterations, the polish work block (lockstep_polish_ws_doubles(n, m) doubles, device) and where the
   // chunk's polish statistics go (host, kLsPolStat doubles: problems attempted, accepted, rejected, recurrence steps of the slowest problem, PCG
-  // iterations summed, kernel launches, GPU ms; nullptr: not wanted).  Set by Engine::run_lockstep alone: the adjoint and direct routes leave polish off.
+  // iterations summed, kernel launches, GPU ms; nullptr: not wanted).  Set by Engine::run_lockstep alone, for the shared and the per-problem-matrix entries alike: the adjoint and direct routes leave polish off.
   int polish = 0, pol_min_steps = 1, pol_cg_max = 0;
   double pol_rho = 0, pol_pcg_rel = 0;
   double *pol_ws = nullptr, *pol_stat = nullptr;

@@ -66,7 +66,7 @@ class Engine {
   int batch_solve_lockstep_device(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream);
   int lockstep_last_record(double *rec) const;
   // The same route with a P_val / A_val per problem (include/osqp_hip.h osqp_hip_batch_solve_lockstep_mat; lockstep_hip.hip "matrices of a chunk"): Px / Ax are
-  // [nbatch][nnz(triu P)] / [nbatch][nnz(A)] in the CSC order given at setup, either may be NULL (the handle's own raw values); no polish.
+  // [nbatch][nnz(triu P)] / [nbatch][nnz(A)] in the CSC order given at setup, either may be NULL (the handle's own raw values); polishes as the shared entry does.
   int batch_solve_lockstep_mat(int nbatch, const double *Px, const double *Ax, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm);
   int batch_solve_lockstep_mat_device(int nbatch, const double *Px, const double *Ax, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream);
   int lockstep_mat_last_record(double *rec) const;

@@ -956,7 +956,7 @@ int Engine::run_lockstep(int nbatch, const double *q, const double *l, const dou
     p.mat_ws = lsmw_; p.mat_stat = mst; p.mat_iters = std::max(0, (int)settings.scaling);
     p.pvmap = reordered_ ? d_pvmap_ : nullptr; p.avmap = reordered_ ? d_avmap_ : nullptr;
   }
-  if (settings.polishing && !mat) {                   // (the per-problem-matrix entries pass polish off)
+  if (settings.polishing) {                           // (with per-problem matrices too: the chunk polishes on its own matrix block)
     if (!lspw_) { lspw_ = dev_vec<double>(d_, pneed); be::sync(d_); }
     const double de = std::max(settings.delta, pol_.polish_delta_floor);
     p.polish = 1; p.pol_rho = clamp_rho(1.0 / de); p.pol_min_steps = 1 + std::max(0, (int)settings.polish_refine_iter);
@@ -984,7 +984,7 @@ int Engine::run_lockstep(int nbatch, const double *q, const double *l, const dou
   const double r[OSQP_HIP_LOCKSTEP_LAST_REC] = {(double)chunks, (double)kLsW, tot[0], tot[1], tot[2], tot[3], (double)(need * sizeof(double)), 0.0};
   std::copy(r, r + OSQP_HIP_LOCKSTEP_LAST_REC, ls_rec_);
   std::copy(ptot, ptot + kLsPolStat, ls_pol_rec_);
-  ls_pol_rec_[kLsPolStat] = (settings.polishing && !mat) ? (double)(pneed * sizeof(double)) : 0.0;
+  ls_pol_rec_[kLsPolStat] = settings.polishing ? (double)(pneed * sizeof(double)) : 0.0;
   if (mat) {
     const double rm[OSQP_HIP_LOCKSTEP_MAT_LAST_REC] = {(double)chunks, (double)kLsW, tot[0], tot[1], tot[2], tot[3], (double)(mneed * sizeof(double)), mtot[0]};
     std::copy(rm, rm + OSQP_HIP_LOCKSTEP_MAT_LAST_REC, lsm_rec_);

@@ -29,7 +29,7 @@
 // and the single-QP adjoint run, which is this file's iteration with alpha = 1 and a fixed rho -- see "adjoint derivatives of a chunk"; with matrices of
 // the chunk's own (osqp_hip_batch_adjoint_lockstep_mat) the same pass behind the forward's assembly and equilibration, on the k_lsm_* instantiations.
 // POLISH (settings.polishing): the chunk's SOLVED problems are polished by that same recurrence between the ADMM loop and the transposes out -- see
-// "polish of a chunk".
+// "polish of a chunk".  With per-problem matrices it runs on the chunk's own matrix block.
 #include "hip_common.h"
 
 namespace osqp_hip {
@@ -830,6 +830,10 @@ __global__ __launch_bounds__(256) void k_ls_adj_grad(LsAK k) {
 // normal-cone projection against the problem's own bounds (k_ls_pol_cone), the accept test against the record (k_ls_pol_accept: term_info,
 // polish_accept) and, for a rejected problem, the ADMM x, y, z back (k_ls_pol_end).  A problem that does not take part is "terminated" all the way: no
 // kernel stores to its lane.  The saved vectors live in a work block of their own (backend.h lockstep_polish_ws_doubles).
+// With per-problem matrices ("matrices of a chunk" below) the recurrence runs on kLsOwnMat and the two kernels here that read matrix values or the cost
+// scale are bodies ls_pol_NAME<MAT> like the forward's: k_lsm_pol_cone walks the chunk's own A, k_lsm_pol_accept takes c, 1 / c per lane.  The others
+// read neither and serve both: k_ls_pol_class classifies on the scaled z, l, u, y -- with a per-lane E and c each problem's own scaled space, which is
+// what Engine::polish does on a handle set up with that problem alone.
 struct LsPK { LockstepParams P; LsWs w; LsPolWs s; };
 
 // per problem: takes part iff SOLVED; IW_DONE becomes "not in the recurrence"; rho_bar = 1 / delta_eff with equality factor 1, flagged for k_ls_setrho / k_ls_minv
@@ -895,13 +899,16 @@ struct FPolCone {
     w.l[IX(i)] = l; w.u[IX(i)] = u; w.z[IX(i)] = c.z; w.y[IX(i)] = c.y;
   }
 };
-__global__ __launch_bounds__(256) void k_ls_pol_cone(LsPK k) {
+template <bool MAT> __device__ __forceinline__ void ls_pol_cone(const LsPK &k) {
   const int lane = ls_lane();
   FPolCone f{k.w, k.s, lane, k.w.iw[IW_POL * W + lane]};
-  ls_rows<1, 1>(k.P.A, f);
+  ls_rows<1, 1, MAT>(k.P.A, f);
 }
-// the info fields of the polished point (term_rules.h term_info on the slots k_ls_resm / k_ls_resn have put) against the record's: kept or rejected
-__global__ __launch_bounds__(256) void k_ls_pol_accept(LsPK k) {
+LS_KERNEL_PAIR_OF(LsPK, pol_cone)
+// the info fields of the polished point (term_rules.h term_info on the slots k_ls_resm / k_ls_resn have put) against the record's: kept or rejected.
+// MAT: the problem's own cost scale, as ls_decide<MAT> takes it -- rows SC_C / SC_CINV of the scalar state, which ls_mat_prepare wrote and nothing since:
+// k_ls_init, the decisions and the PCG's folds write rows below SC_BEST, k_ls_pol_begin SC_RHOBAR, SC_EQF and SC_BEST, k_ls_pol_decide SC_BEST.
+template <bool MAT> __device__ __forceinline__ void ls_pol_accept(const LsPK &k) {
   __shared__ double lds[256];
   const LockstepParams &P = k.P;
   const int lane = ls_lane(), G = k.w.G;
@@ -915,7 +922,7 @@ __global__ __launch_bounds__(256) void k_ls_pol_accept(LsPK k) {
   const int pol = iw[IW_POL * W + lane];
   bool ok = false;
   if (pol) {
-    const TermSet tset = {P.eps_abs, P.eps_rel, P.eps_pinf, P.eps_dinf, P.c, P.cinv, P.m, P.unscaled, P.scaling};
+    const TermSet tset = {P.eps_abs, P.eps_rel, P.eps_pinf, P.eps_dinf, MAT ? k.w.sc[SC_C * W + lane] : P.c, MAT ? k.w.sc[SC_CINV * W + lane] : P.cinv, P.m, P.unscaled, P.scaling};
     double obj, prim_res, dual_res;
     term_info(tset, R, &obj, &prim_res, &dual_res);
     double *rc = k.w.rec + (size_t)lane * kBatchRec;
@@ -926,6 +933,7 @@ __global__ __launch_bounds__(256) void k_ls_pol_accept(LsPK k) {
   const unsigned long long acc = __ballot(pol && ok), rej = __ballot(pol && !ok);
   if (threadIdx.x == 0) { k.w.word[WD_POLACC] = __popcll(acc); k.w.word[WD_POLREJ] = __popcll(rej); }
 }
+LS_KERNEL_PAIR_OF(LsPK, pol_accept)
 // the record's polish seconds for every problem that was attempted; a rejected problem's ADMM x, y, z back
 __global__ __launch_bounds__(256) void k_ls_pol_end(LsPK k, double secs) {
   const int lane = ls_lane(), pol = k.w.iw[IW_POL * W + lane];
@@ -1359,7 +1367,7 @@ int ls_recurrence(LsRun &R, const LsPcgKernels &K, const LsK &km, const LsK &kn,
 // SC_C / SC_CINV / SC_CT belong to the work block of the chunk that calls.
 int ls_mat_block(const Dev &d, LockstepParams &P, LsMat &mt) {
   LsCursor cm{P.mat_ws};
-  if (!d.Praw || !d.Araw || P.polish) return OSQP_FUNC_NOT_IMPLEMENTED;
+  if (!d.Praw || !d.Araw) return OSQP_FUNC_NOT_IMPLEMENTED;
   if (!lockstep_mat_layout(cm, P.n, P.m, P.A.nnz, P.B.nnz, mt)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   mt.Praw = d.Praw; mt.Araw = d.Araw; mt.Pm1 = d.Pm1; mt.Pm2 = d.Pm2; mt.AmA = d.AmA; mt.AmB = d.AmB; mt.Bdiag = d.Bdiag; mt.nzP = d.nzP; mt.nzA = d.nzA;
   P.A.val = mt.Aval; P.B.val = mt.Bval; P.D = mt.D; P.Dinv = mt.Dinv; P.E = mt.E; P.Einv = mt.Einv;
@@ -1475,7 +1483,7 @@ int lockstep_chunk(Dev &d, const LockstepParams &p, void *stream, double *stat) 
   if (polished) {
     const long launches0 = R.launches;
     const double t_pol = ls_now();
-    kq.w = w;
+    kq.P = k.P; kq.w = w;                              // (k.P: with a matrix block, A.val, B.val, D .. Einv point at it)
     LsK kp = k;                                        // what the ADMM's kernels take in the recurrence: alpha = 1, the recurrence's PCG rule
     kp.P.alpha = 1.0; kp.P.cg_max = p.pol_cg_max; kp.P.pcg_rel = p.pol_pcg_rel;
     R.ep0.record(s);
@@ -1485,13 +1493,13 @@ int lockstep_chunk(Dev &d, const LockstepParams &p, void *stream, double *stat) 
     if (pol_att > 0) {
       R.go(k_ls_pol_class, G, kq);
       if (m > 0) R.go(k_ls_setrho, G, kp);
-      R.go(k_ls_minv, G, kp);
+      R.go(K.minv, G, kp);
       int cg_pol = 4;
-      pol_steps = ls_recurrence(R, kLsShared, kp, kp, kLsPolMaxSteps, [&]() { ls_pcg(R, kLsShared, kp, cg_pol); R.go(k_ls_upd, G, kp); }, [&]() { R.go(k_ls_pol_decide, 1, kq); });
+      pol_steps = ls_recurrence(R, K, kp, kp, kLsPolMaxSteps, [&]() { ls_pcg(R, K, kp, cg_pol); R.go(K.upd, G, kp); }, [&]() { R.go(k_ls_pol_decide, 1, kq); });
       pol_pcg = R.words[WD_PCGSUM];
-      if (m > 0) { R.go(k_ls_pol_cone, G, kq); R.go(k_ls_resm, G, kp); }
-      R.go(k_ls_resn, G, kp);
-      R.go(k_ls_pol_accept, 1, kq);
+      if (m > 0) { R.go(mat ? k_lsm_pol_cone : k_ls_pol_cone, G, kq); R.go(K.resm, G, kp); }
+      R.go(K.resn, G, kp);
+      R.go(mat ? k_lsm_pol_accept : k_ls_pol_accept, 1, kq);
       R.fetch();
       R.go(k_ls_pol_end, G, kq, ls_now() - t_pol);
     }

@@ -435,7 +435,8 @@ class OSQPSolver:
         Same arguments, same checks, same returns: x (B, n), y (B, m), rec (B, BATCH_REC).  With the setting polishing every SOLVED
         problem is polished on the device (rec[:, 8] = 1 kept, -1 rejected; lockstep_polish_last_record).
         Px (B, nnz(triu P)) / Ax (B, nnz(A)): per-problem matrix values in the CSC order given at setup (osqp_hip_batch_solve_lockstep_mat): every
-        problem is scaled as a solver set up with its data alone; no polish on that entry (lockstep_mat_last_record, lockstep_mat_scaling)."""
+        problem is scaled as a solver set up with its data alone and, with the setting polishing, polished on its own matrices as above
+        (lockstep_mat_last_record: the ADMM part; lockstep_polish_last_record: polish; lockstep_mat_scaling)."""
         return self._lockstep_host(self._lib.osqp_hip_batch_solve_lockstep, q, l, u, x0, y0, nbatch, Px, Ax)
 
     def _lockstep_host(self, entry, q, l, u, x0, y0, nbatch, Px=None, Ax=None):

@@ -20,6 +20,10 @@ threads.  Here one persistent engine handle plays that role:
     With ``large_batch='lockstep'`` (one rank) a forward with 2-D P_val and / or A_val that the single launch declines makes ONE call of the lockstep
     route with per-element matrices (osqp_hip_batch_solve_lockstep_mat; ``mat_lockstep_launches`` counts them) in place of the per-element loop; its
     backward is the per-element loop unless ``large_backward='lockstep'`` (below).
+  * ``polishing=True`` (default False: every forward as before) is passed to ``setup``: the handle polishes every solved problem, on whichever route the
+    forward takes -- the one-workgroup kernel, the per-element loop, the lockstep route with shared or with per-element matrices (there the polish runs
+    on the device inside the one call; ``lockstep_polish_last_record`` of the handle counts attempted / accepted / rejected).  The adjoint classifies the
+    active rows from (x, y), and a polished point gives a clean active set.  With ``large_batch='lockstep_direct'`` the route does not polish.
 
 Like the reference, a batch element that is not solved raises RuntimeError (:158-162).
 
@@ -63,7 +67,7 @@ def _distributed():
 
 
 class OSQP(Module):
-    def __init__(self, P_idx, P_shape, A_idx, A_shape, eps_rel=1e-5, eps_abs=1e-5, verbose=False, max_iter=10000, algebra='hip', solver_type='indirect', large_batch='loop', large_backward='loop'):
+    def __init__(self, P_idx, P_shape, A_idx, A_shape, eps_rel=1e-5, eps_abs=1e-5, verbose=False, max_iter=10000, algebra='hip', solver_type='indirect', large_batch='loop', large_backward='loop', polishing=False):
         super().__init__()
         if large_batch not in ('loop', 'lockstep', 'lockstep_direct'):
             raise ValueError("large_batch: 'loop', 'lockstep' or 'lockstep_direct'")
@@ -74,6 +78,7 @@ class OSQP(Module):
         self.P_idx, self.P_shape, self.A_idx, self.A_shape = P_idx, P_shape, A_idx, A_shape
         self.eps_rel, self.eps_abs, self.verbose, self.max_iter = eps_rel, eps_abs, verbose, max_iter
         self.algebra, self.solver_type = algebra, solver_type
+        self.polishing = bool(polishing)   # settings.polishing of the handle this layer sets up (default off: every forward as before)
         self.n, self.m = P_shape[0], A_shape[0]
         self._solver = None          # the persistent handle (reference: the `solvers` list kept across forwards)
         self._Pv = self._Av = None   # matrix values currently on the handle
@@ -85,6 +90,7 @@ class OSQP(Module):
         self.last_adjoint_rec = None # (nb, 4) record of the last backward: status, active rows, residual, reserved (ext_hip ADJOINT_FIELDS)
         self._grad_maps = None
         self.mat_lockstep_launches = 0   # calls of the lockstep route with per-element matrices made by this layer's forwards (large_batch='lockstep')
+        self.last_rec = None         # per-element record of the last forward that ran on host arrays (ext_hip BATCH_FIELDS where a batch route made it: status_polish is column 8)
         self.mat_lockstep_adjoint_launches = 0   # calls of the lockstep adjoint with per-element matrices made by this layer's backwards (large_backward='lockstep')
 
     # ------------------------------------------------------------------ the persistent handle
@@ -102,7 +108,7 @@ class OSQP(Module):
                 self._triu_pick = tag.data.astype(int) - 1
             s = osqp_amd.OSQP(algebra=self.algebra)
             s.setup(P, q0, A, l0, u0, solver_type=self.solver_type, verbose=self.verbose, eps_abs=self.eps_abs, eps_rel=self.eps_rel,
-                    max_iter=self.max_iter, warm_starting=False, device=device)
+                    max_iter=self.max_iter, warm_starting=False, device=device, **({'polishing': True} if self.polishing else {}))
             self._solver, self._device = s, device
             self._Pv, self._Av = np.array(P_val, dtype=float), np.array(A_val, dtype=float)
             self.setup_count += 1
@@ -178,6 +184,7 @@ class OSQP(Module):
                         self.mat_lockstep_launches += 1
             if x is None:
                 x, rec = self._loop(Pn, qn, An, ln, un, nb, batched, dev_index)
+        self.last_rec = rec
         bad = np.nonzero(rec[:, 0] != int(osqp_amd.SolverStatus.OSQP_SOLVED))[0]
         if bad.size:
             raise RuntimeError('Unable to solve QP, status: %d (batch element %d)' % (int(rec[bad[0], 0]), int(bad[0])))

@@ -3,13 +3,16 @@
 Engine::run_lockstep*) must leave exactly as it was.
 
 --dump FILE runs, with fixed seeds and no time limit, on problems.banded_qp(400, window=40) at B = 70 and eps 1e-8 (one full chunk and a ragged one):
-the forward route, the forward with polishing, the forward with per-element Px / Ax, the adjoint; on problems.portfolio_qp(200, 10) and (600, 4) at
+the forward route, the forward with polishing, the forward with per-element Px / Ax (and that with polishing: its ADMM part, the polished result, and
+the same handle with polishing switched off), the adjoint; on problems.portfolio_qp(200, 10) and (600, 4) at
 B = 70: the direct forward and the direct adjoint (a handle the direct route declines -- (200, 10): no dense row -- is kept as its return code); and the m = 0 tridiagonal case at n = 900, B = 3, with polish.  Every returned array and every *_last_record
 field except the timings goes into an .npz.  --compare A B exits non-zero unless every array is equal (NaNs in the same places) and every record field
-is equal: kernel launches, iteration / step counts, PCG iterations, inversions, polish counts, workspace bytes.
+is equal: kernel launches, iteration / step counts, PCG iterations, inversions, polish counts, workspace bytes.  --feature TAG ..: entries under these
+tags are what build B is meant to change (mat_polish, when A is a build from before polish reached the per-element-matrix entry); they are printed with
+both sides' figures and not counted.
 
     python tools/lockstep_identity.py --dump prof_out/identity_this.npz          (OSQP_HIP_LIBRARY selects the other build)
-    python tools/lockstep_identity.py --compare prof_out/identity_parent.npz prof_out/identity_this.npz
+    python tools/lockstep_identity.py --compare prof_out/identity_parent.npz prof_out/identity_this.npz [--feature mat_polish]
 """
 import argparse
 import os
@@ -27,13 +30,17 @@ TIMINGS = ('gpu_ms', 'seconds', 'prepare_gpu_ms')
 REC_SECONDS = 9          # column of a batch record that holds the polish seconds
 
 
-def handle(P, q, A, l, u, **kw):
+def outer(P, q, A, l, u, **kw):
     import osqp_amd
     s = osqp_amd.OSQP(algebra='hip')
     st = dict(verbose=False, eps_abs=1e-8, eps_rel=1e-8, max_iter=20000, warm_starting=False)
     st.update(kw)
     s.setup(P, q, A, l, u, **st)
-    return s._solver
+    return s
+
+
+def handle(P, q, A, l, u, **kw):
+    return outer(P, q, A, l, u, **kw)._solver
 
 
 def dump(path):
@@ -65,9 +72,20 @@ def dump(path):
     xm, ym, recm = e.hip_batch_solve_lockstep(q=Q, l=L, u=U, Px=Px, Ax=Ax)
     keep('mat', fwd(xm, ym, recm), e.lockstep_mat_last_record())
     keep('mat_base', {}, e.lockstep_last_record())
-    e = handle(P, q, A, l, u, polishing=True)
+    so = outer(P, q, A, l, u, polishing=True)
+    e = so._solver
     keep('polish', fwd(*e.hip_batch_solve_lockstep(q=Q, l=L, u=U)), e.lockstep_last_record())
     keep('polish_part', {}, e.lockstep_polish_last_record())
+    # per-element matrices on the polishing handle.  mat_polish_admm: the ADMM part of that call (record fields status, iter, rho, rho_updates, pcg_iters,
+    # rho_estimate; lockstep_mat_last_record), which polish must leave as the unpolished call has it.  mat_polish_off: the same handle with polishing
+    # switched off.  mat_polish (FEATURE below): the polished x, y, rec and the polish record -- a build from before polish reached this entry returns the
+    # ADMM point there.
+    xq, yq, recq = e.hip_batch_solve_lockstep(q=Q, l=L, u=U, Px=Px, Ax=Ax)
+    keep('mat_polish', fwd(xq, yq, recq), e.lockstep_polish_last_record())
+    keep('mat_polish_admm', dict(rec=recq[:, [0, 1, 5, 6, 7, 10]]), e.lockstep_mat_last_record())
+    so.update_settings(polishing=False)
+    keep('mat_polish_off', fwd(*e.hip_batch_solve_lockstep(q=Q, l=L, u=U, Px=Px, Ax=Ax)), e.lockstep_mat_last_record())
+    keep('mat_polish_off_part', {}, e.lockstep_polish_last_record())
 
     # portfolio_qp(200, 10) has no row past kLongRow entries, so the handle is no Woodbury one and the direct route declines it: the answer is what is kept.
     # portfolio_qp(600, 4) (the GPU suites' shape: r = 5) is the handle the direct drivers run on.
@@ -103,15 +121,25 @@ def dump(path):
     print('%d entries -> %s' % (len(out), path))
 
 
-def compare(pa, pb):
+def compare(pa, pb, feature=()):
     a, b = np.load(pa), np.load(pb)
-    bad = sorted(set(a.files) ^ set(b.files))
+    own = lambda k: k.split('/')[0] in feature
+    bad = sorted(k for k in set(a.files) ^ set(b.files) if not own(k))
+    new = []
     for k in sorted(set(a.files) & set(b.files)):
         if a[k].shape != b[k].shape or not np.array_equal(a[k], b[k], equal_nan=True):
-            bad.append(k)
+            (new if own(k) else bad).append(k)
     for k in bad:
         print('DIFFERS: %s' % k)
-    print('%d entries compared, %d differences' % (len(set(a.files) | set(b.files)), len(bad)))
+    for k in new:                                        # (what the feature is: shown with both sides' figures, not counted)
+        va, vb = a[k], b[k]
+        print('FEATURE: %s  %s -> %s' % (k, *(('%g' % v) if v.ndim == 0 else 'array%s' % (v.shape,) for v in (va, vb))))
+    for tag in feature:
+        k = '%s/rec' % tag
+        if k in a.files and k in b.files:
+            print('FEATURE: %s status_polish == 1: %d -> %d of %d' % (tag, int((a[k][:, 8] == 1).sum()), int((b[k][:, 8] == 1).sum()), len(b[k])))
+    ncmp = len([k for k in set(a.files) | set(b.files) if not own(k)])
+    print('%d entries compared, %d differences; %d feature entries differ' % (ncmp, len(bad), len(new)))
     return 1 if bad else 0
 
 
@@ -119,7 +147,8 @@ if __name__ == '__main__':
     ap = argparse.ArgumentParser()
     ap.add_argument('--dump', metavar='FILE')
     ap.add_argument('--compare', nargs=2, metavar=('A', 'B'))
+    ap.add_argument('--feature', nargs='*', default=[], metavar='TAG', help='tags whose entries B is meant to change: reported, not counted as differences')
     args = ap.parse_args()
     if args.dump:
         dump(args.dump)
-    sys.exit(compare(*args.compare) if args.compare else 0)
+    sys.exit(compare(*args.compare, feature=tuple(args.feature)) if args.compare else 0)
