@@ -781,14 +781,29 @@ __device__ __forceinline__ void f1_body(const Dev &d, const int k, const bool ve
   [[maybe_unused]] double *spnxt = MIX ? gptr(f.spill) + (size_t)nxt * (f.nsp + 2) : nullptr;
   [[maybe_unused]] const int *spk = MIX ? gptr(f.spk) : nullptr;
   double g_acc = 0.0, rn_acc = 0.0, dl_acc = 0.0, bn_acc = 0.0;
-  // the vector update of one own column (operands in registers): stores s_{k-1}, r_k, p_{k-1}, x~; returns u_k
-  auto own_update = [&](int j, double mi, double r, double w, double sp, double pp, double x) -> double {
-    double sn, rn, un;
-    f1_upd(sc, mi, r, w, sp, sn, rn, un);
-    const double pn = fma(sc.beta, sc.general ? pp : 0.0, mi * r);
-    gst(xs_w + j, fma(sc.alpha, pn, x)); gst(p_w + j, pn); gst(snew + j, sn); gst(rnxt + j, rn);
-    g_acc += rn * un; rn_acc = nanmax(rn_acc, fabs(rn));
+  // the vector update of one own column (operands in registers): x~, p_{k-1}, s_{k-1}, r_k into `o` -- NOT stored here -- and u_k returned.
+  // (A result store issued in front of f1_stream_wait() is waited for there: loads and stores share the one VM counter.  The own columns of the
+  //  lanes' FIRST window element -- all of a block's own columns on the headline problem -- are held in registers and stored behind the products
+  //  phase, next to the request of the next block's stream (own_store); the second element's and the columns outside the window store at once.
+  //  Measured, DESIGN.md section 4.2 "Own-column results leave behind the stream wait": NOT the stores' acknowledgement -- the "products staged" phase
+  //  stays at 1.24 - 1.32 us -- but their issue and address arithmetic leave the path between the requests and the wait: F-only kernel 10.23 - 10.28 ->
+  //  10.03 - 10.05 us per launch, configs[1] 35.76 - 35.78 -> 35.44 - 35.60 ms.  Both elements held: 128 VGPRs and 12 bytes of scratch in the
+  //  <4, true, *> instantiations.  Stored between the wait and its barrier instead: no gain (35.6 - 36.0 ms).  The same for KA's dx, x, x_g: KA unchanged
+  //  (9.4 us), and the compiler then guards the block loops of the slot kernel with `s_waitcnt vmcnt(0)` at their heads, which sits out the whole first
+  //  stream: F launch 10.1 -> 10.3 - 10.5 us.)
+  struct Own { double x, p, s, r; };
+  auto own_update = [&](double mi, double r, double w, double sp, double pp, double x, Own &o) -> double {
+    double un;
+    f1_upd(sc, mi, r, w, sp, o.s, o.r, un);
+    o.p = fma(sc.beta, sc.general ? pp : 0.0, mi * r);
+    o.x = fma(sc.alpha, o.p, x);
+    g_acc += o.r * un; rn_acc = nanmax(rn_acc, fabs(o.r));
     return un;
+  };
+  // F_k: x~, p, s, r;  F_0: x~ <- x_g (o.x), x~_prev <- x~ (o.p), r_0 (o.r)
+  auto own_store = [&](int j, const Own &o) {
+    if constexpr (FIRST) { gst(rnxt + j, o.r); gst(gptr(d.xsp) + j, o.p); gst(xs_w + j, o.x); }
+    else { gst(xs_w + j, o.x); gst(p_w + j, o.p); gst(snew + j, o.s); gst(rnxt + j, o.r); }
   };
   const int xcd = blockIdx.x & 7, slot0 = blockIdx.x >> 3, slots = gridDim.x >> 3;
   const int per = (d.A.nblk + 7) >> 3;
@@ -884,7 +899,12 @@ __device__ __forceinline__ void f1_body(const Dev &d, const int k, const bool ve
     // (a (P + sigma I) entry whose column lies outside the window: its operand is recomputed from its parts in the product phase below -- requested
     //  THERE: held from here they would cost 7 + 2 D registers across the block's register peak for a case banded problems never meet)
     KT(3);
-    // ---- u_k on the window -> LDS; the lane of an own column also performs that column's vector update
+    // ---- u_k on the window -> LDS; the lane of an own column also performs that column's vector update (first element: results held in wo[0])
+    // (the default values are not optional: without them the <4, true, *> instantiations spill 12 bytes per lane)
+    constexpr int kHeld = 1;
+    Own wo[CW];
+#pragma unroll
+    for (int u = 0; u < CW; u++) wo[u] = Own{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int u = 0; u < CW; u++) {
       if (gather_on(u)) {
@@ -897,14 +917,14 @@ __device__ __forceinline__ void f1_body(const Dev &d, const int k, const bool ve
           const double r0 = w;                              // rhs - K x_g: the slices' sum, the same expression in every workgroup that holds the column
           un = wm[u] * r0;
           if (wown[u]) {
-            const int j = g0 + e;
-            gst(rnxt + j, r0); gst(gptr(d.xsp) + j, wx[u]); gst(xs_w + j, wpp[u]);
+            wo[u] = Own{wpp[u], wx[u], 0.0, r0};
             g_acc += r0 * un; rn_acc = nanmax(rn_acc, fabs(r0));
           }
         } else {
-          if (wown[u]) un = own_update(g0 + e, wm[u], wr[u], w, wsv[u], wpp[u], wx[u]);
+          if (wown[u]) un = own_update(wm[u], wr[u], w, wsv[u], wpp[u], wx[u], wo[u]);
           else { double sn, rn; f1_upd(sc, wm[u], wr[u], w, wsv[u], sn, rn, un); }
         }
+        if (u >= kHeld) { if (wown[u]) own_store(g0 + e, wo[u]); }
         if (wown[u]) L.uown[g0 + e - cs0] = un;
         L.win[e] = un;                                      // (an active wave's clamped lanes store the same value)
       }
@@ -925,7 +945,7 @@ __device__ __forceinline__ void f1_body(const Dev &d, const int k, const bool ve
         un = mi * r0;
         gst(rnxt + j, r0); gst(gptr(d.xsp) + j, ar.d(8u * j, oxs)); gst(xs_w + j, gptr(d.xg)[j]);
         g_acc += r0 * un; rn_acc = nanmax(rn_acc, fabs(r0));
-      } else un = own_update(j, mi, ar.d(8u * j, orr), wj, ar.d(8u * j, osp), ar.d(8u * j, op), ar.d(8u * j, oxs));
+      } else { Own o; un = own_update(mi, ar.d(8u * j, orr), wj, ar.d(8u * j, osp), ar.d(8u * j, op), ar.d(8u * j, oxs), o); own_store(j, o); }
       if (!vec_only) L.uown[jj] = un;
     }
     if (vec_only) continue;
@@ -980,6 +1000,10 @@ __device__ __forceinline__ void f1_body(const Dev &d, const int k, const bool ve
       const int bn = __builtin_amdgcn_readfirstlane(xcd * per + sl + slots);
       if (bn < d.A.nblk) f1_stream_issue<!WT>(f.stream, bn, S);
     }
+    // ---- the held own columns go out: nothing on this block's path waits for a store again (the barriers below are bare s_barrier; the next
+    //      block's f1_stream_wait(), or the end of the kernel, sits them out)
+#pragma unroll
+    for (int u = 0; u < kHeld; u++) { if (wown[u]) own_store(g0 + tid + u * kBlock, wo[u]); }      // (wown[u]: the lane's element is inside the window, unclamped)
     // ---- row sums: t = rho .* (A u) -> LDS
     // (first pass peeled: its operands are in registers -- a shared loop body would carry the later passes' load waits, and any `s_waitcnt vmcnt`
     //  executed here waits for the stream requested above as well)
