@@ -371,7 +371,7 @@ OSQPInt osqp_hip_lockstep_mat_scaling(OSQPSolver *solver, OSQPInt b, OSQPFloat *
  * rule of osqp_solve on this handle -- the tolerance on the policy's square-root scale (OSQPHipPolicy::rho_tol_exp / OSQP_HIP_RHO_TOL_EXP; the literal
  * value for an LP) and the persistence test (rho_persist / OSQP_HIP_RHO_PERSIST) -- so an element takes the iterations, status and iterate that
  * osqp_update_data_vec + osqp_solve give from the same settings.rho (a loop over one handle starts each solve from the rho the previous one left).  No
- * polish, no duality-gap test, no per-problem matrices.  The decision is the structural one taken at setup, whatever became of the single handle's direct
+ * polish, no duality-gap test; per-problem matrices: osqp_hip_batch_solve_lockstep_direct_mat below.  The decision is the structural one taken at setup, whatever became of the single handle's direct
  * mode since.  Returns OSQP_FUNC_NOT_IMPLEMENTED for every other handle: no Woodbury correction, the large mode (r > 128: the lasso), a K0 that is not
  * diagonal, the host simulator -- and a handle that works on a permuted copy (OSQPHipStats::reordered): this route DECLINES it rather than gather
  * through the permutations.  The handle's own iterates, solution, info and launch history are not touched.
@@ -383,6 +383,28 @@ OSQPInt osqp_hip_batch_solve_lockstep_direct(OSQPSolver *solver, OSQPInt nbatch,
 OSQPInt osqp_hip_batch_solve_lockstep_direct_device(OSQPSolver *solver, OSQPInt nbatch, const OSQPFloat *q_dev, const OSQPFloat *l_dev, const OSQPFloat *u_dev,
                                                     OSQPFloat *x_dev, OSQPFloat *y_dev, OSQPFloat *rec_dev, OSQPInt warm_start, void *stream);
 OSQPInt osqp_hip_lockstep_direct_last_record(OSQPSolver *solver, OSQPFloat *rec);
+/* LOCKSTEP DIRECT WITH PER-PROBLEM MATRICES -- osqp_hip_batch_solve_lockstep_direct for a batch whose elements have their own values of P and A on the handle's
+ * sparsity pattern (a factor model per day or per sample: the reference's 2-D P_val / A_val).  Px ([nbatch][nnz of the upper triangle of P]) and Ax
+ * ([nbatch][nnz(A)]) are in the CSC order given at setup, as osqp_hip_batch_solve_lockstep_mat takes them; either may be NULL: that side takes the handle's
+ * CURRENT values (osqp_update_data_mat included) for every problem.  Problem b is solved as a handle set up with (P_b, q_b, A_b, l_b, u_b) alone would solve
+ * it under this handle's settings: its own Ruiz equilibration D_b, E_b, c_b (settings.scaling iterations, on the device, per lane), its own D0_b, S_b and
+ * S_b^-1, the direct route's rho rule with this handle's tolerance.  The other arguments, the nbatch == 0 query, stream semantics, the record per problem,
+ * statuses / certificates (in the problem's own units) / time_limit and the INDEPENDENCE guarantee are those of osqp_hip_batch_solve_lockstep_direct[_device].
+ * No polish, no backward pass with per-problem matrices on this route.  The handle is only read: its matrices, scaling, dense rows, S, iterates, settings and
+ * launch history are not touched.  Returns OSQP_FUNC_NOT_IMPLEMENTED unless osqp_hip_batch_solve_lockstep_direct serves the handle AND the chunk's
+ * assembly does (device assembly, no repeated (j, j) entry in the stored triangle of P); in the host simulator always.
+ * Device memory: 512 (nnz(A) + nnz(B) + 2 n + 2 m + n r + nnz of the view) bytes for one chunk, allocated by the first such call (22 MB of dense rows at
+ * n = 2020, r = 21; 139 MB at n = 2127, r = 128).
+ * osqp_hip_lockstep_direct_mat_last_record: OSQP_HIP_LOCKSTEP_DIRECT_MAT_LAST_REC doubles {chunks, chunk width, ADMM iterations of the slowest problem,
+ * inversions of S summed over the problems, kernel launches, GPU ms, bytes of that block, GPU ms of the assembly + equilibration + the fill of the dense
+ * rows (part of the GPU ms)}; all zero before the first such call.  Such a call also updates osqp_hip_lockstep_direct_last_record. */
+#define OSQP_HIP_LOCKSTEP_DIRECT_MAT_LAST_REC 8
+OSQPInt osqp_hip_batch_solve_lockstep_direct_mat(OSQPSolver *solver, OSQPInt nbatch, const OSQPFloat *Px, const OSQPFloat *Ax, const OSQPFloat *q, const OSQPFloat *l,
+                                                 const OSQPFloat *u, OSQPFloat *x, OSQPFloat *y, OSQPFloat *rec, OSQPInt warm);
+OSQPInt osqp_hip_batch_solve_lockstep_direct_mat_device(OSQPSolver *solver, OSQPInt nbatch, const OSQPFloat *Px_dev, const OSQPFloat *Ax_dev, const OSQPFloat *q_dev,
+                                                        const OSQPFloat *l_dev, const OSQPFloat *u_dev, OSQPFloat *x_dev, OSQPFloat *y_dev, OSQPFloat *rec_dev,
+                                                        OSQPInt warm_start, void *stream);
+OSQPInt osqp_hip_lockstep_direct_mat_last_record(OSQPSolver *solver, OSQPFloat *rec);
 /* ADJOINT DERIVATIVES ON THE LOCKSTEP ROUTE -- the backward pass of osqp_hip_batch_solve_lockstep: the quantities osqp_hip_batch_adjoint (below) defines,
  * for a batch that shares this handle's P and A, at any size, OSQP_HIP_LOCKSTEP_WIDTH problems at a time on block vectors.  Per problem: the rows are
  * classified by the rule given there (caller's units, z = A x on the x passed in; bounds clamped to +-OSQP_INFTY), and the adjoint system is solved by

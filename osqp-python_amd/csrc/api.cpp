@@ -136,6 +136,15 @@ OSQPInt osqp_hip_batch_solve_lockstep_direct_device(OSQPSolver *s, OSQPInt nbatc
   return guarded(s, [&](Engine &e) { return e.batch_solve_lockstep_direct_device(nbatch, q, l, u, x, y, rec, warm, stream); });
 }
 OSQPInt osqp_hip_lockstep_direct_last_record(OSQPSolver *s, OSQPFloat *rec) { return guarded(s, [&](Engine &e) { return e.lockstep_direct_last_record(rec); }); }
+OSQPInt osqp_hip_batch_solve_lockstep_direct_mat(OSQPSolver *s, OSQPInt nbatch, const OSQPFloat *Px, const OSQPFloat *Ax, const OSQPFloat *q, const OSQPFloat *l, const OSQPFloat *u, OSQPFloat *x,
+                                                 OSQPFloat *y, OSQPFloat *rec, OSQPInt warm) {
+  return guarded(s, [&](Engine &e) { return e.batch_solve_lockstep_direct_mat(nbatch, Px, Ax, q, l, u, x, y, rec, warm); });
+}
+OSQPInt osqp_hip_batch_solve_lockstep_direct_mat_device(OSQPSolver *s, OSQPInt nbatch, const OSQPFloat *Px, const OSQPFloat *Ax, const OSQPFloat *q, const OSQPFloat *l, const OSQPFloat *u,
+                                                        OSQPFloat *x, OSQPFloat *y, OSQPFloat *rec, OSQPInt warm, void *stream) {
+  return guarded(s, [&](Engine &e) { return e.batch_solve_lockstep_direct_mat_device(nbatch, Px, Ax, q, l, u, x, y, rec, warm, stream); });
+}
+OSQPInt osqp_hip_lockstep_direct_mat_last_record(OSQPSolver *s, OSQPFloat *rec) { return guarded(s, [&](Engine &e) { return e.lockstep_direct_mat_last_record(rec); }); }
 OSQPInt osqp_hip_batch_adjoint_lockstep(OSQPSolver *s, OSQPInt nbatch, const OSQPFloat *l, const OSQPFloat *u, const OSQPFloat *x, const OSQPFloat *y, const OSQPFloat *dx,
                                         const OSQPFloat *dy, OSQPFloat *dP, OSQPFloat *dq, OSQPFloat *dA, OSQPFloat *dl, OSQPFloat *du, OSQPFloat *arec) {
   return guarded(s, [&](Engine &e) { return e.batch_adjoint_lockstep(nbatch, l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec); });

@@ -520,10 +520,15 @@ struct LockstepAdjointParams : LockstepParams {
 // The DIRECT lockstep route for a Woodbury handle whose K0 is diagonal (lockstep_hip.hip "lockstep DIRECT"; include/osqp_hip.h
 // osqp_hip_batch_solve_lockstep_direct): the base's A / B are the handle's; Av is the view of A the row passes read -- the one-entry rows as they are, long
 // row a as the single entry 1.0 at column n + a -- and WT / rows / islong are DevWb's (the dense transpose of the long rows, their indices, the row flags).
+// PER-PROBLEM MATRICES on this route (the base's mat_ws / Px / Ax; include/osqp_hip.h osqp_hip_batch_solve_lockstep_direct_mat): mat_ws is then
+// lockstep_direct_mat_ws_doubles(n, m, r, nnz(A), nnz(B), Av.nnz) doubles -- the matrix block, the chunk's own dense rows and view values -- and the chunk
+// fills the latter two from the block's scaled values through wtpos ([n r]: where entry (long row a, column j) sits in A.val, at j r + a; -1: no entry)
+// and vsrc ([Av.nnz]: where a view entry sits in A.val; -1: a long row's 1.0).
 struct LockstepDirectView {
   int r = 0;                    // long rows (1 .. kWbMaxRows)
   DevCsr Av;
   const double *WT = nullptr; const int *rows = nullptr; const unsigned char *islong = nullptr;
+  const int *wtpos = nullptr, *vsrc = nullptr;
 };
 struct LockstepDirectParams : LockstepParams { LockstepDirectView v; };
 

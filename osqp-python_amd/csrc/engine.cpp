@@ -168,6 +168,9 @@ void Engine::free_all() {
   if (lsaw_) { be::dfree(d_, lsaw_); lsaw_ = nullptr; }
   if (lsdw_) { be::dfree(d_, lsdw_); lsdw_ = nullptr; }
   if (lsdaw_) { be::dfree(d_, lsdaw_); lsdaw_ = nullptr; }
+  if (lsdmw_) { be::dfree(d_, lsdmw_); lsdmw_ = nullptr; }
+  if (lsd_wtpos_) { be::dfree(d_, lsd_wtpos_); lsd_wtpos_ = nullptr; }
+  std::fill(lsdm_rec_, lsdm_rec_ + OSQP_HIP_LOCKSTEP_DIRECT_MAT_LAST_REC, 0.0);
   for (DevScratch *sc : {&lsabuf_, &lsdabuf_}) if (sc->buf) { be::dfree(d_, sc->buf); *sc = DevScratch{}; }
   if (lsd_vval_) { be::dfree(d_, lsd_vval_); lsd_vval_ = nullptr; }
   if (lsd_vrp_) { be::dfree(d_, lsd_vrp_); be::dfree(d_, lsd_vcol_); be::dfree(d_, lsd_vsrc_); lsd_vrp_ = lsd_vcol_ = lsd_vsrc_ = nullptr; lsd_nv_ = 0; }

@@ -77,6 +77,11 @@ class Engine {
   int batch_solve_lockstep_direct(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm);
   int batch_solve_lockstep_direct_device(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream);
   int lockstep_direct_last_record(double *rec) const;
+  // The direct route with a P_val / A_val per problem (include/osqp_hip.h osqp_hip_batch_solve_lockstep_direct_mat; lockstep_hip.hip lockstep_direct_chunk):
+  // Px / Ax as batch_solve_lockstep_mat takes them, on the handles batch_solve_lockstep_direct accepts and the chunk's assembly can serve.  No polish.
+  int batch_solve_lockstep_direct_mat(int nbatch, const double *Px, const double *Ax, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm);
+  int batch_solve_lockstep_direct_mat_device(int nbatch, const double *Px, const double *Ax, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream);
+  int lockstep_direct_mat_last_record(double *rec) const;
   // The backward pass of such a batch (include/osqp_hip.h osqp_hip_batch_adjoint_lockstep; lockstep_hip.hip lockstep_adjoint_chunk): the adjoint system of
   // every problem by the recurrence polish runs, on block vectors, in a work block of its own.  Any output may be nullptr.
   int batch_adjoint_lockstep(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
@@ -175,6 +180,7 @@ class Engine {
   double lsm_rec_[OSQP_HIP_LOCKSTEP_MAT_LAST_REC] = {0, 0, 0, 0, 0, 0, 0, 0};      // record of the last such call (osqp_hip_lockstep_mat_last_record)
   int lsm_last_count_ = 0;                            // problems of the last chunk that call processed (0: no call yet): what lockstep_mat_scaling reads
   bool lockstep_mat_applies();
+  bool mat_assembly_applies();                        // what a chunk's own assembly needs of a handle, on either lockstep route
   // direct lockstep route: the structural decision of prepare_wb (K0 diagonal, small mode -- not DevWb::exact, which a failed inversion clears), the
   // chunk's workspace (lockstep_direct_ws_doubles(n, m, r)) and the view of A (LockstepDirectView::Av), both built on first use, the last call's record
   bool wb_k0diag_ = false;
@@ -184,7 +190,14 @@ class Engine {
   bool lockstep_direct_applies();
   int prepare_lockstep_direct_view();                 // builds the view of A on first use (both directions of the direct route read it)
   int fill_lockstep_direct_view(LockstepDirectView &v, void *stream);      // ... and fills a chunk's view from it, values refreshed
-  int run_lockstep_direct(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream);
+  int run_lockstep_direct(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream,
+                          bool mat = false, const double *Px = nullptr, const double *Ax = nullptr);
+  // ... with per-problem matrices: the block of one such chunk (lockstep_direct_mat_ws_doubles), allocated by the first such call, the position map of the
+  // dense rows (LockstepDirectView::wtpos), built once per handle, and the record of the last such call (osqp_hip_lockstep_direct_mat_last_record)
+  double *lsdmw_ = nullptr; int *lsd_wtpos_ = nullptr;
+  double lsdm_rec_[OSQP_HIP_LOCKSTEP_DIRECT_MAT_LAST_REC] = {0, 0, 0, 0, 0, 0, 0, 0};
+  bool lockstep_direct_mat_applies();
+  void prepare_lockstep_direct_wtpos();
   double *lsaw_ = nullptr;                            // work block of one lockstep adjoint chunk (lockstep_adjoint_ws_doubles(n, m)), allocated on first use
   struct DevScratch { double *buf = nullptr; size_t cap = 0; };
   DevScratch lsabuf_, lsdabuf_;                       // device scratch of batch_adjoint_lockstep / _direct (host-array entry points), kept across calls

@@ -927,6 +927,7 @@ int Engine::lockstep_last_record(double *rec) const { return last_record(ls_rec_
 int Engine::lockstep_polish_last_record(double *rec) const { return last_record(ls_pol_rec_, OSQP_HIP_LOCKSTEP_POLISH_LAST_REC, rec); }
 int Engine::lockstep_mat_last_record(double *rec) const { return last_record(lsm_rec_, OSQP_HIP_LOCKSTEP_MAT_LAST_REC, rec); }
 int Engine::lockstep_direct_last_record(double *rec) const { return last_record(lsd_rec_, OSQP_HIP_LOCKSTEP_DIRECT_LAST_REC, rec); }
+int Engine::lockstep_direct_mat_last_record(double *rec) const { return last_record(lsdm_rec_, OSQP_HIP_LOCKSTEP_DIRECT_MAT_LAST_REC, rec); }
 int Engine::lockstep_adjoint_last_record(double *rec) const { return last_record(lsa_rec_, OSQP_HIP_LOCKSTEP_ADJOINT_LAST_REC, rec); }
 int Engine::lockstep_mat_adjoint_last_record(double *rec) const { return last_record(lsma_rec_, OSQP_HIP_LOCKSTEP_MAT_ADJOINT_LAST_REC, rec); }
 int Engine::lockstep_direct_adjoint_last_record(double *rec) const { return last_record(lsda_rec_, OSQP_HIP_LOCKSTEP_DIRECT_ADJOINT_LAST_REC, rec); }
@@ -995,8 +996,8 @@ int Engine::run_lockstep(int nbatch, const double *q, const double *l, const dou
 // ---- per-problem matrices on the lockstep route (include/osqp_hip.h osqp_hip_batch_solve_lockstep_mat)
 // What lockstep_applies() declines, a handle without device assembly and a handle whose stored upper triangle of P holds a repeated (j, j) entry (the
 // single-handle assembly sums those with a floating-point atomic; the chunk's assembly has one writer per entry) are declined.
-bool Engine::lockstep_mat_applies() {
-  if (!lockstep_applies() || !be::device_assembly() || !d_.Praw || !d_.Araw) return false;
+bool Engine::mat_assembly_applies() {
+  if (!be::device_assembly() || !d_.Praw || !d_.Araw) return false;
   for (int j = 0; j < n; j++) {
     int diag = 0;
     for (int k = P_.p[j]; k < P_.p[j + 1]; k++) diag += P_.i[k] == j;
@@ -1004,6 +1005,7 @@ bool Engine::lockstep_mat_applies() {
   }
   return true;
 }
+bool Engine::lockstep_mat_applies() { return lockstep_applies() && mat_assembly_applies(); }
 
 int Engine::batch_solve_lockstep_mat(int nbatch, const double *Px, const double *Ax, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm) {
   BatchStage s{*this, nbatch, &Engine::lockstep_mat_applies, /*own_row=*/reordered_ ? ipr_.data() : nullptr, /*wg=*/false};
@@ -1094,7 +1096,28 @@ int Engine::fill_lockstep_direct_view(LockstepDirectView &v, void *stream) {
   return be::lockstep_direct_values(d_, lsd_nv_, lsd_vsrc_, lsd_vval_, stream);      // (A's values may have changed since the last call)
 }
 
-int Engine::run_lockstep_direct(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream) {
+// ---- per-problem matrices on the direct route (include/osqp_hip.h osqp_hip_batch_solve_lockstep_direct_mat).  What lockstep_direct_applies() accepts, with
+// the conditions of the chunk's assembly (lockstep_mat_applies: device assembly, the raw values resident, no repeated (j, j) in the stored triangle of P).
+bool Engine::lockstep_direct_mat_applies() { return lockstep_direct_applies() && mat_assembly_applies(); }
+
+// where entry (long row a, column j) of A sits in the engine's A.val, at j r + a (-1: no entry): what fills a chunk's own dense rows.  Once per handle.
+void Engine::prepare_lockstep_direct_wtpos() {
+  if (lsd_wtpos_) return;
+  const int r = d_.wb.r;
+  std::vector<int> pos((size_t)n * r, -1);
+  int a = 0;
+  for (int i = 0; i < m; i++) {
+    if (Arp_[i + 1] - Arp_[i] <= kLongRow) continue;
+    for (int k = Arp_[i]; k < Arp_[i + 1]; k++) pos[(size_t)Arj_[k] * r + a] = k;
+    a++;
+  }
+  lsd_wtpos_ = dev_vec<int>(d_, pos.size());
+  be::h2d(d_, lsd_wtpos_, pos.data(), sizeof(int) * pos.size());
+  be::sync(d_);
+}
+
+int Engine::run_lockstep_direct(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream,
+                                bool mat, const double *Px, const double *Ax) {
   const int r = d_.wb.r;
   const size_t need = lockstep_direct_ws_doubles(n, m, r);
   LockstepDirectParams p;
@@ -1103,6 +1126,16 @@ int Engine::run_lockstep_direct(int nbatch, const double *q, const double *l, co
   fill_batch_settings(p, warm);
   fill_lockstep_handle(p);
   p.ws = lsdw_;
+  // per-problem matrices: the block (the matrix block, the chunk's own dense rows and view values; allocated by the first such call) and the position map
+  const int nzP = d_.nzP, nzA = d_.nzA;
+  const size_t mneed = lockstep_direct_mat_ws_doubles(n, m, r, d_.A.nnz, d_.B.nnz, lsd_nv_);
+  double mst[kLsMatStat] = {0, 0}, mtot[kLsMatStat] = {0, 0};
+  if (mat) {
+    prepare_lockstep_direct_wtpos();
+    if (!lsdmw_) { lsdmw_ = dev_vec<double>(d_, mneed); be::sync(d_); }
+    p.mat_ws = lsdmw_; p.mat_stat = mst; p.mat_iters = std::max(0, (int)settings.scaling);
+    p.v.wtpos = lsd_wtpos_; p.v.vsrc = lsd_vsrc_;
+  }
   // adaptive rho as the handle's own solve decides it (ctl_setup: the tolerance on the square-root scale where P has a quadratic part, the persistence
   // test), not as the batch family does: an element then takes the path update(q, l, u) + solve() takes from the same rho
   p.rho_tol_single = pol_rho_tol(settings.adaptive_rho_tolerance, has_quad(), pol_.rho_tol_exp); p.rho_persist = pol_.rho_persist;
@@ -1113,14 +1146,20 @@ int Engine::run_lockstep_direct(int nbatch, const double *q, const double *l, co
     p.count = std::min(kLsW, nbatch - b0);
     p.q = q ? q + (size_t)b0 * n : nullptr; p.l = l ? l + (size_t)b0 * m : nullptr; p.u = u ? u + (size_t)b0 * m : nullptr;
     p.x = x + (size_t)b0 * n; p.y = y + (size_t)b0 * m; p.rec = rec + (size_t)b0 * kBatchRec;
+    p.Px = (mat && Px) ? Px + (size_t)b0 * nzP : nullptr; p.Ax = (mat && Ax) ? Ax + (size_t)b0 * nzA : nullptr;
     p.time_limit = limit > 0 ? std::max(limit - (now_s() - t0), 1e-9) : 0.0;
     double st[4] = {0, 0, 0, 0};
     const int err = be::lockstep_direct_chunk(d_, p, stream, st);
     if (err) return err;
+    if (mat) { mtot[0] += mst[0]; mtot[1] += mst[1]; }
     tot[0] = std::max(tot[0], st[0]); tot[1] += st[1]; tot[2] += st[2]; tot[3] += st[3];
   }
   const double rr[OSQP_HIP_LOCKSTEP_DIRECT_LAST_REC] = {(double)chunks, (double)kLsW, tot[0], tot[1], tot[2], tot[3], (double)(need * sizeof(double)), now_s() - t0};
   std::copy(rr, rr + OSQP_HIP_LOCKSTEP_DIRECT_LAST_REC, lsd_rec_);
+  if (mat) {
+    const double rm[OSQP_HIP_LOCKSTEP_DIRECT_MAT_LAST_REC] = {(double)chunks, (double)kLsW, tot[0], tot[1], tot[2], tot[3], (double)(mneed * sizeof(double)), mtot[0]};
+    std::copy(rm, rm + OSQP_HIP_LOCKSTEP_DIRECT_MAT_LAST_REC, lsdm_rec_);
+  }
   return OSQP_NO_ERROR;
 }
 
@@ -1137,6 +1176,21 @@ int Engine::batch_solve_lockstep_direct_device(int nbatch, const double *q, cons
   if (enter != kBatchEnter) return enter;
   be::sync(d_);                                     // the solver's own stream first: pending updates of the resident q / l / u, the matrices
   return run_lockstep_direct(nbatch, q, l, u, x, y, rec, warm, stream);
+}
+
+int Engine::batch_solve_lockstep_direct_mat(int nbatch, const double *Px, const double *Ax, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm) {
+  BatchStage s{*this, nbatch, &Engine::lockstep_direct_mat_applies, /*own_row=*/nullptr, /*wg=*/false};
+  if (const int err = s.in(q, l, u, x, y, rec, warm, Px, Ax)) return err;
+  const int err = run_lockstep_direct(nbatch, q ? s.dq : nullptr, l ? s.dl : nullptr, u ? s.du : nullptr, s.dx, s.dy, s.drec, warm, nullptr, true, Px ? s.dPx : nullptr, Ax ? s.dAx : nullptr);
+  if (!err) s.out(x, y, rec);
+  return err;
+}
+
+int Engine::batch_solve_lockstep_direct_mat_device(int nbatch, const double *Px, const double *Ax, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream) {
+  const int enter = batch_enter(nbatch, true, x, y, rec, &Engine::lockstep_direct_mat_applies);
+  if (enter != kBatchEnter) return enter;
+  be::sync(d_);                                     // the solver's own stream first: pending updates of the resident q / l / u, the raw matrix values
+  return run_lockstep_direct(nbatch, q, l, u, x, y, rec, warm, stream, true, Px, Ax);
 }
 
 // ---- the backward pass of a lockstep batch (lockstep_hip.hip lockstep_adjoint_chunk): chunk after chunk like run_lockstep.  Every array is a DEVICE

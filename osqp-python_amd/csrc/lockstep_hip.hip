@@ -960,11 +960,20 @@ __global__ __launch_bounds__(256) void k_ls_pol_end(LsPK k, double secs) {
 // S_b is formed (k_lw_s) and inverted in place (k_lw_inv: one workgroup per problem, S_b in LDS, Gauss-Jordan without pivoting) at the start and for exactly
 // the problems whose rho_bar k_ls_decide has changed.  A pivot that is not positive and finite makes that problem's inverse NaN: its x~ and residuals
 // are NaN from the next iteration on and k_ls_decide ends it with OSQP_NON_CVX (term_rules.h: non-finite residuals); no other lane reads it.
+// PER-PROBLEM MATRICES on this route (osqp_hip_batch_solve_lockstep_direct_mat; lockstep_direct_chunk with mat_ws): the chunk's own matrix block ("matrices
+// of a chunk" below) and, behind it, the dense rows per lane -- WT of problem b: entry (column j, long row a) at ((j r + a) 64 + b) -- and the view's
+// values per lane ([nv][64]).  The four kernels here that read matrix values (d0, s, prod, x) are bodies lw_NAME<MAT>: k_lw_NAME on the handle's arrays,
+// k_lwm_NAME on the chunk's, where a value of WT is one 512-byte line per wave in place of a wave-uniform scalar load; inv, h, setl read none.
 struct LwWs : LwVecs {                  // (S, pg, pg2, h, fact: lockstep_layout.h)
   const double *WT; const int *rows; const unsigned char *islong;
   int r, GC, cb;                        // long rows; column blocks and their width
 };
 struct LwK { LockstepParams P; LsWs w; LwWs d; };
+
+// a kernel body on the handle's dense rows and on the chunk's own ("per-problem matrices" below): k_lw_NAME the shared route's kernel, k_lwm_NAME the other
+#define LW_KERNEL_PAIR(NAME) \
+  __global__ __launch_bounds__(256) void k_lw_##NAME(LwK k) { lw_##NAME<false>(k); } \
+  __global__ __launch_bounds__(256) void k_lwm_##NAME(LwK k) { lw_##NAME<true>(k); }
 
 // Minv = 1 / D0,  D0 = B_jj + sum over the ONE-ENTRY rows i of column j of rho_i,b A_ij^2  (k_ls_minv's diagonal without the long rows' squares)
 struct FD0 {
@@ -974,14 +983,17 @@ struct FD0 {
   __device__ __forceinline__ void fma(int c, double v, const double (&g)[1], double (&a)[2]) const { if (c >= n) a[0] += g[0] * v * v; else if (c == cur) a[1] = v; }
   __device__ __forceinline__ void row(int j, const double (&a)[2]) const { if (flag[lane]) Minv[IX(j)] = 1.0 / (a[1] + a[0]); }
 };
-__global__ __launch_bounds__(256) void k_lw_d0(LwK k) {
+template <bool MAT> __device__ __forceinline__ void lw_d0(const LwK &k) {
   if (!k.w.word[WD_RHOANY]) return;
   FD0 f{k.w.rho, k.w.Minv, k.w.iw + IW_RHOCH * W, k.d.islong, k.P.n, ls_lane(), 0};
-  ls_rows<1, 2>(k.P.B, f);
+  ls_rows<1, 2, MAT>(k.P.B, f);
 }
+LW_KERNEL_PAIR(d0)
 // S[a][c] = (a == c) / rho_a + sum_j A_L[a, j] Minv_j A_L[c, j] for the problems whose rho has just been set.  Workgroup (a, eight columns c): wave w takes
 // the columns j = w, w + 4, .. of A_L (WT: column j of A_L contiguous), the four waves are combined in wave order.
-__global__ __launch_bounds__(256) void k_lw_s(LwK k) {
+// MAT: a value of WT is one 512-byte line per (j, a) and wave; the ten lines of a column (row a's, Minv's, the eight of c0 ..) are requested together, and
+// no column is skipped: whether A_L[a, j] is zero is no longer wave-uniform, and the terms the shared form skips are exact zeros.
+template <bool MAT> __device__ __forceinline__ void lw_s(const LwK &k) {
   __shared__ double lds[8 * 256];
   if (!k.w.word[WD_RHOANY]) return;
   const int lane = ls_lane(), wv = ls_wave(), r = k.d.r, n = k.P.n, cch = (r + 7) / 8;
@@ -990,13 +1002,26 @@ __global__ __launch_bounds__(256) void k_lw_s(LwK k) {
   double acc[8];
 #pragma unroll
   for (int u = 0; u < 8; u++) acc[u] = 0.0;
-  for (int j = wv; j < n; j += 4) {
-    const double *__restrict__ wt = WT + (size_t)j * r;
-    const double va = wt[a];                            // (wave-uniform)
-    if (va == 0.0) continue;
-    const double t = va * k.w.Minv[IX(j)];
+  if constexpr (MAT) {
+    for (int j = wv; j < n; j += 4) {
+      const double *__restrict__ wt = WT + (size_t)j * r * 64 + lane;
+      double wc[8];
+      const double va = wt[(size_t)a * 64], mi = k.w.Minv[IX(j)];
 #pragma unroll
-    for (int u = 0; u < 8; u++) acc[u] += t * (c0 + u < r ? wt[c0 + u] : 0.0);
+      for (int u = 0; u < 8; u++) wc[u] = wt[(size_t)min(c0 + u, r - 1) * 64];
+      const double t = va * mi;
+#pragma unroll
+      for (int u = 0; u < 8; u++) acc[u] += t * (c0 + u < r ? wc[u] : 0.0);
+    }
+  } else {
+    for (int j = wv; j < n; j += 4) {
+      const double *__restrict__ wt = WT + (size_t)j * r;
+      const double va = wt[a];                            // (wave-uniform)
+      if (va == 0.0) continue;
+      const double t = va * k.w.Minv[IX(j)];
+#pragma unroll
+      for (int u = 0; u < 8; u++) acc[u] += t * (c0 + u < r ? wt[c0 + u] : 0.0);
+    }
   }
 #pragma unroll
   for (int u = 0; u < 8; u++) lds[(u * 4 + wv) * 64 + lane] = acc[u];
@@ -1010,6 +1035,7 @@ __global__ __launch_bounds__(256) void k_lw_s(LwK k) {
     if (k.w.iw[IW_RHOCH * W + lane]) k.d.S[((size_t)a * r + c) * 64 + lane] = v;
   }
 }
+LW_KERNEL_PAIR(s)
 // S_b <- S_b^-1 in place: workgroup b holds S_b (r x r) and the pivot column in LDS, 8 (r^2 + r) bytes <= 129 KB at r = 128
 __global__ __launch_bounds__(256) void k_lw_inv(LwK k) {
   extern __shared__ double lw_lds[];
@@ -1037,23 +1063,50 @@ __global__ __launch_bounds__(256) void k_lw_inv(LwK k) {
   if (t == 0) k.d.fact[b] += 1;
 }
 // out[block][a] = sum over the block's columns j of A_L[a, j] v_j: workgroup = a block of cb columns, wave w takes the rows 8 w .. 8 w + 7, + 32, ..
-__global__ __launch_bounds__(256) void k_lw_prod(LwK k, const double *v, double *out) {
-  const int lane = ls_lane(), wv = ls_wave(), r = k.d.r, j0 = (int)blockIdx.x * k.d.cb, j1 = min(j0 + k.d.cb, k.P.n);
+// MAT: a value is a 512-byte line of the chunk's own WT and no longer a scalar load, so the rows are spread further -- workgroup (column block, eight
+// rows), a wave takes two of them (grid: GC x ceil(r / 8), from (n, r) alone) -- and eight columns are in flight: sixteen lines of WT and eight of v are
+// requested before the first FMA.  A row's sum keeps the order of the block's columns: the partials are the shared form's, term for term.
+template <bool MAT> __device__ __forceinline__ void lw_prod(const LwK &k, const double *v, double *out) {
+  const int lane = ls_lane(), wv = ls_wave(), r = k.d.r;
   const double *__restrict__ WT = k.d.WT;
-  for (int a0 = wv * 8; a0 < r; a0 += 32) {
-    double acc[8];
+  if constexpr (MAT) {
+    const int rg = (r + 7) / 8, g = (int)blockIdx.x / rg, a = ((int)blockIdx.x % rg) * 8 + 2 * wv;
+    if (a >= r) return;
+    const int j0 = g * k.d.cb, j1 = min(j0 + k.d.cb, k.P.n);
+    const bool two = a + 1 < r;                          // (a wave whose second row is past r reads its first row twice and stores once)
+    const size_t st = (size_t)r * 64;
+    const double *__restrict__ w0 = WT + ((size_t)j0 * r + a) * 64 + lane, *__restrict__ w1 = w0 + (two ? 64 : 0), *__restrict__ vj = v + IX(j0);
+    double s0 = 0.0, s1 = 0.0;
+    int j = j0;
+    for (; j + 8 <= j1; j += 8, w0 += 8 * st, w1 += 8 * st, vj += 8 * 64) {
+      double e0[8], e1[8], vv[8];
 #pragma unroll
-    for (int u = 0; u < 8; u++) acc[u] = 0.0;
-    for (int j = j0; j < j1; j++) {
-      const double vj = v[IX(j)];
-      const double *__restrict__ wt = WT + (size_t)j * r + a0;
+      for (int u = 0; u < 8; u++) { e0[u] = w0[u * st]; e1[u] = w1[u * st]; vv[u] = vj[u * 64]; }
 #pragma unroll
-      for (int u = 0; u < 8; u++) acc[u] += (a0 + u < r ? wt[u] : 0.0) * vj;
+      for (int u = 0; u < 8; u++) { s0 += e0[u] * vv[u]; s1 += e1[u] * vv[u]; }
     }
+    for (; j < j1; j++, w0 += st, w1 += st, vj += 64) { const double vv = vj[0]; s0 += w0[0] * vv; s1 += w1[0] * vv; }
+    out[((size_t)g * r + a) * 64 + lane] = s0;
+    if (two) out[((size_t)g * r + a + 1) * 64 + lane] = s1;
+  } else {
+    const int j0 = (int)blockIdx.x * k.d.cb, j1 = min(j0 + k.d.cb, k.P.n);
+    for (int a0 = wv * 8; a0 < r; a0 += 32) {
+      double acc[8];
 #pragma unroll
-    for (int u = 0; u < 8; u++) if (a0 + u < r) out[((size_t)blockIdx.x * r + a0 + u) * 64 + lane] = acc[u];
+      for (int u = 0; u < 8; u++) acc[u] = 0.0;
+      for (int j = j0; j < j1; j++) {
+        const double vj = v[IX(j)];
+        const double *__restrict__ wt = WT + (size_t)j * r + a0;
+#pragma unroll
+        for (int u = 0; u < 8; u++) acc[u] += (a0 + u < r ? wt[u] : 0.0) * vj;
+      }
+#pragma unroll
+      for (int u = 0; u < 8; u++) if (a0 + u < r) out[((size_t)blockIdx.x * r + a0 + u) * 64 + lane] = acc[u];
+    }
   }
 }
+__global__ __launch_bounds__(256) void k_lw_prod(LwK k, const double *v, double *out) { lw_prod<false>(k, v, out); }
+__global__ __launch_bounds__(256) void k_lwm_prod(LwK k, const double *v, double *out) { lw_prod<true>(k, v, out); }
 // the sum of GC partials `st` doubles apart, in block order, eight loads in flight (the additions keep their order)
 __device__ __forceinline__ double lw_fold(const double *s, int GC, size_t st) {
   double a = 0.0;
@@ -1096,7 +1149,9 @@ __global__ __launch_bounds__(256) void k_lw_h(LwK k) {
   }
 }
 // x~_j += p_j - Minv_j sum_a A_L[a, j] h_a  (h in LDS; wave w of workgroup g takes the columns 4 g + w, + 4 G, ..)
-__global__ __launch_bounds__(256) void k_lw_x(LwK k) {
+// MAT: column j's r values are r consecutive lines of the chunk's own WT, requested eight at a time (with p and Minv in the first group); the sum keeps
+// the order of the rows.
+template <bool MAT> __device__ __forceinline__ void lw_x(const LwK &k) {
   extern __shared__ double lw_lds[];
   const int lane = ls_lane(), r = k.d.r;
   for (int e = threadIdx.x; e < r * 64; e += 256) lw_lds[e] = k.d.h[e];
@@ -1104,15 +1159,54 @@ __global__ __launch_bounds__(256) void k_lw_x(LwK k) {
   if (k.w.iw[IW_DONE * W + lane]) return;
   const double *__restrict__ WT = k.d.WT;
   for (int j = (int)blockIdx.x * 4 + ls_wave(); j < k.P.n; j += (int)gridDim.x * 4) {
-    const double *__restrict__ wt = WT + (size_t)j * r;
     double s = 0.0;
-    for (int a = 0; a < r; a++) s += wt[a] * lw_lds[a * 64 + lane];
-    k.w.xs[IX(j)] += k.w.p[IX(j)] - k.w.Minv[IX(j)] * s;
+    if constexpr (MAT) {
+      const double *__restrict__ wt = WT + (size_t)j * r * 64 + lane;
+      const double pj = k.w.p[IX(j)], mi = k.w.Minv[IX(j)], xj = k.w.xs[IX(j)];
+      int a = 0;
+      for (; a + 8 <= r; a += 8) {
+        double e[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) e[u] = wt[(size_t)(a + u) * 64];
+#pragma unroll
+        for (int u = 0; u < 8; u++) s += e[u] * lw_lds[(a + u) * 64 + lane];
+      }
+      if (a < r) {
+        double e[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) e[u] = wt[(size_t)min(a + u, r - 1) * 64];
+#pragma unroll
+        for (int u = 0; u < 8; u++) if (a + u < r) s += e[u] * lw_lds[(a + u) * 64 + lane];
+      }
+      k.w.xs[IX(j)] = xj + (pj - mi * s);
+    } else {
+      const double *__restrict__ wt = WT + (size_t)j * r;
+      for (int a = 0; a < r; a++) s += wt[a] * lw_lds[a * 64 + lane];
+      k.w.xs[IX(j)] += k.w.p[IX(j)] - k.w.Minv[IX(j)] * s;
+    }
   }
 }
+LW_KERNEL_PAIR(x)
 // the view's values: a copy of A's at the one-entry rows, 1.0 at a long row's single entry
 __global__ __launch_bounds__(256) void k_lw_vals(int nv, const int *src, const double *Aval, double *out) {
   for (int e = blockIdx.x * 256 + threadIdx.x; e < nv; e += gridDim.x * 256) out[e] = src[e] >= 0 ? Aval[src[e]] : 1.0;
+}
+// ... and per lane (MAT): entry e of problem b at e * 64 + b, from the chunk's scaled values of A; a wave per entry, its source position wave-uniform
+__global__ __launch_bounds__(256) void k_lwm_vals(int nv, const int *src, const double *Aval, double *out) {
+  const int lane = ls_lane();
+  for (int e = (int)blockIdx.x * 4 + ls_wave(); e < nv; e += (int)gridDim.x * 4) {
+    const int sp = __builtin_amdgcn_readfirstlane(src[e]);
+    out[IX(e)] = sp >= 0 ? Aval[IX(sp)] : 1.0;
+  }
+}
+// the chunk's own WT: entry (column j, long row a) of problem b at ((j r + a) 64 + b), from the chunk's scaled values of A through the position map
+// (pos[j r + a]: where the entry sits in A.val, -1: A_L has none there -- zero).  A wave per entry.
+__global__ __launch_bounds__(256) void k_lwm_wt(int cnt, const int *pos, const double *Aval, double *out) {
+  const int lane = ls_lane();
+  for (int e = (int)blockIdx.x * 4 + ls_wave(); e < cnt; e += (int)gridDim.x * 4) {
+    const int sp = __builtin_amdgcn_readfirstlane(pos[e]);
+    out[IX(e)] = sp >= 0 ? Aval[IX(sp)] : 0.0;
+  }
 }
 // ---- the backward pass of the direct route (lockstep_direct_adjoint_chunk below).  "adjoint derivatives of a chunk" with the PCG replaced by the solve
 // above: rho never changes in the recurrence (alpha = 1, rho_bar = 1 / delta_eff on the active rows, rho_min on the others), so S_b is formed and
@@ -1401,30 +1495,31 @@ struct LwRun {
   LsK kb, kv, ku;
   int G, r, GC;
   size_t lds_inv, lds_h;
-  LwRun(const LockstepParams &p, const LockstepDirectView &v, const LsWs &w, const LwVecs &d) : k{p, w, {}}, kb{p, w} {
+  bool mat;                              // per-problem matrices: p's A / B / scalings, v.Av.val and v.WT are the chunk's own blocks, the kernels the MAT forms
+  LwRun(const LockstepParams &p, const LockstepDirectView &v, const LsWs &w, const LwVecs &d, bool own = false) : k{p, w, {}}, kb{p, w}, mat(own) {
     const int cb = lockstep_direct_colblock(p.n);
     G = w.G; r = v.r; GC = lockstep_direct_colblocks(p.n);
     static_cast<LwVecs &>(k.d) = d;
     k.d.WT = v.WT; k.d.rows = v.rows; k.d.islong = v.islong; k.d.r = r; k.d.GC = GC; k.d.cb = cb;
     kv = kb; kv.P.A = v.Av;
-    ku = kv; ku.P.n = p.n + r;
+    ku = kv; ku.P.n = p.n + r;            // (k_ls_upd reads no scaling: nothing launched with ku indexes D .. Einv)
     lds_inv = sizeof(double) * ((size_t)r * r + r); lds_h = sizeof(double) * (size_t)r * 64;
     if (lds_inv > 64 * 1024) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_lw_inv), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_inv));
   }
+  const LsPcgKernels &K() const { return mat ? kLsOwnMat : kLsShared; }
+  void prod(LsRun &R, const double *v, double *out) const { if (mat) R.go(k_lwm_prod, GC * ((r + 7) / 8), k, v, out); else R.go(k_lw_prod, GC, k, v, out); }
   // rho from rho_bar, D0, S and its inverse (for the problems whose rho has just been set)
-  void factor(LsRun &R) const { R.go(k_ls_setrho, G, kb); R.go(k_lw_d0, G, k); R.go(k_lw_s, r * ((r + 7) / 8), k); R.gol(k_lw_inv, W, lds_inv, k); }
+  void factor(LsRun &R) const { R.go(k_ls_setrho, G, kb); R.go(mat ? k_lwm_d0 : k_lw_d0, G, k); R.go(mat ? k_lwm_s : k_lw_s, r * ((r + 7) / 8), k); R.gol(k_lw_inv, W, lds_inv, k); }
   // x~ by the Woodbury formula, then the ADMM update
   void solve(LsRun &R) const {
-    R.go(k_ls_rhs, G, kb);
-    R.go(k_lw_prod, GC, k, (const double *)k.w.p, k.d.pg);
+    R.go(K().rhs, G, kb);
+    prod(R, k.w.p, k.d.pg);
     R.gol(k_lw_h, (r + 15) / 16, lds_h, k);
-    R.gol(k_lw_x, G, lds_h, k);
-    R.go(k_ls_upd, G, ku);
+    R.gol(mat ? k_lwm_x : k_lw_x, G, lds_h, k);
+    R.go(K().upd, G, ku);
   }
   // the rows n .. n + r - 1 of x and x~ from the products
-  void long_rows(LsRun &R, int start) const {
-    R.go(k_lw_prod, GC, k, (const double *)k.w.x, k.d.pg); R.go(k_lw_prod, GC, k, (const double *)k.w.xs, k.d.pg2); R.go(k_lw_setl, 1, k, start);
-  }
+  void long_rows(LsRun &R, int start) const { prod(R, k.w.x, k.d.pg); prod(R, k.w.xs, k.d.pg2); R.go(k_lw_setl, 1, k, start); }
 };
 
 }  // namespace
@@ -1569,31 +1664,56 @@ int lockstep_adjoint_chunk(Dev &d, const LockstepAdjointParams &p, void *stream,
 // host reads the word block once.  The time limit is tested against the host's clock as of the last such read (in between the host runs ahead of the
 // GPU): a chunk past its limit ends at the iteration after the check that saw it, with OSQP_TIME_LIMIT_REACHED for the problems still running.
 // stat: {ADMM iterations of the slowest problem, inversions of S summed over the problems, kernel launches, GPU ms}.
-int lockstep_direct_chunk(Dev &d, const LockstepDirectParams &p, void *stream, double *stat) {
+// PER-PROBLEM MATRICES (p.mat_ws != nullptr; include/osqp_hip.h osqp_hip_batch_solve_lockstep_direct_mat): problem b runs on its own P_b, A_b under its own
+// D_b, E_b, c_b.  In front of the transposes in: ls_mat_prepare (the PCG route's assembly and equilibration, unchanged), then the chunk's own WT and view
+// values from the block's scaled A (k_lwm_wt, k_lwm_vals); R.em marks the end of all three.  From then on the row passes are kLsOwnMat's and the four
+// kernels that read matrix values are the k_lwm_* forms; D0_b, S_b and S_b^-1 follow from them per lane.  The handle's own arrays are only read.
+int lockstep_direct_chunk(Dev &d, const LockstepDirectParams &p0, void *stream, double *stat) {
   const hipStream_t s = ls_stream(d, stream);
-  const int n = p.n, m = p.m, r = p.v.r, tn = (n + 63) / 64, tm = (m + 63) / 64;
+  const int n = p0.n, m = p0.m, r = p0.v.r, tn = (n + 63) / 64, tm = (m + 63) / 64;
+  const bool mat = p0.mat_ws != nullptr;
   if (r < 1 || r > kWbMaxRows || m < 1) return OSQP_FUNC_NOT_IMPLEMENTED;
   LsWs w;
   LwVecs x;
-  LsCursor c{p.ws};
+  LsCursor c{p0.ws};
   if (!lockstep_direct_layout(c, n, m, r, w, x, nullptr)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  const LwRun D(p, p.v, w, x);
+  LockstepDirectParams p = p0;
+  LsMat mt{};
+  LwMatVecs xm{};
+  if (mat) {
+    if (!p.v.wtpos || !p.v.vsrc) return OSQP_FUNC_NOT_IMPLEMENTED;
+    if (const int err = ls_mat_block(d, p, mt)) return err;
+    LsCursor cm{p.mat_ws};
+    LsMatVecs again;
+    if (!lockstep_direct_mat_layout(cm, n, m, r, p.A.nnz, p.B.nnz, p.v.Av.nnz, again, xm)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+    p.v.WT = xm.WT; p.v.Av.val = xm.vval;
+  }
+  const LwRun D(p, p.v, w, x, mat);
   const LsK &kb = D.kb, &kv = D.kv;
+  const LsPcgKernels &K = D.K();
   const int G = w.G;
   LsRun R(s, w.word, p.count);
   R.e0.record(s);
+  if (mat) {
+    const int nv = p.v.Av.nnz, nwt = n * r;
+    ls_mat_prepare(R, LsMK{p, w, mt});
+    R.go(k_lwm_wt, std::min(1024, (nwt + 3) / 4), nwt, p.v.wtpos, (const double *)mt.Aval, xm.WT);
+    R.go(k_lwm_vals, std::min(1024, (nv + 3) / 4), nv, p.v.vsrc, (const double *)mt.Aval, xm.vval);
+    R.em.record(s);
+    if (p.mat_stat) p.mat_stat[1] += 2;
+  }
   const double t_begin = R.t_sync;
-  auto residuals = [&]() { R.go(k_ls_resm, G, kv); R.go(k_ls_resn, G, kb); };
+  auto residuals = [&]() { R.go(K.resm, G, kv); R.go(K.resn, G, kb); };
 
   HIP_CHECK(hipMemsetAsync(x.fact, 0, sizeof(int) * W, s));
-  R.go(k_ls_load_n, tn, kb);
-  R.go(k_ls_load_m, tm, kb);
+  R.go(K.load_n, tn, kb);
+  R.go(K.load_m, tm, kb);
   R.go(k_ls_init, 1, kb, tm);
   D.factor(R);
   D.long_rows(R, 1);
-  R.go(k_ls_initz, G, kv);
+  R.go(K.initz, G, kv);
   residuals();
-  R.go(k_ls_decide, 1, kb, 0, 0, 0, 1);
+  R.go(K.decide, 1, kb, 0, 0, 0, 1);
   int iter = 0;
   while (R.words[WD_LIVE] > 0 && iter < p.max_iter) {
     iter++;
@@ -1604,14 +1724,15 @@ int lockstep_direct_chunk(Dev &d, const LockstepDirectParams &p, void *stream, d
     if (!at_check && !at_rho && !late) continue;
     D.long_rows(R, 0);
     residuals();
-    R.go(k_ls_decide, 1, kb, iter, late ? 1 : at_check, at_rho, late ? 2 : 0);
+    R.go(K.decide, 1, kb, iter, late ? 1 : at_check, at_rho, late ? 2 : 0);
     if (at_rho && !late) D.factor(R);
     if (at_check || late) R.fetch();
   }
-  R.go(k_ls_store_n, tn, kb);
-  R.go(k_ls_store_m, tm, kb);
+  R.go(K.store_n, tn, kb);
+  R.go(K.store_m, tm, kb);
   long nfact = 0;
   const float ms = R.finish(x.fact, &nfact);
+  if (mat && p.mat_stat) p.mat_stat[0] = LsRun::ms(R.e0, R.em);
   if (stat) { stat[0] = iter; stat[1] = (double)nfact; stat[2] = (double)R.launches; stat[3] = ms; }
   return OSQP_NO_ERROR;
 }

@@ -34,6 +34,7 @@ struct LwVecs {                                                            // di
   int *fact;                            // [64] inversions of S per problem
 };
 struct LsMatVecs { double *Aval, *Bval, *D, *Dinv, *E, *Einv; };          // per-problem matrices: [nnz][W] values, n x W and m x W scalings
+struct LwMatVecs { double *WT, *vval; };                                  // direct route with per-problem matrices: [n][r][W] dense rows, [nv][W] values of the view of A
 
 // ---- the size functions (doubles; the closed forms include slack the carves do not use)
 // a chunk's workspace: eight n- and nine m-block vectors, the partials, the per-problem state and records
@@ -58,6 +59,12 @@ inline size_t lockstep_direct_ws_doubles(int n, int m, int r) {
 // its adjoint's: the direct forward's set, then the adjoint's own vectors
 inline size_t lockstep_direct_adjoint_ws_doubles(int n, int m, int r) {
   return lockstep_direct_ws_doubles(n, m, r) + (size_t)kLsW * (3 * (size_t)n + 3 * (size_t)m + ((size_t)m + 1) / 2) + 64;
+}
+
+// the direct route's block with per-problem matrices: the matrix block, then the chunk's own dense rows (entry (column j, long row a) of problem b at
+// ((j r + a) W + b), zero where A_L has no entry) and the values of the view of A (nv entries: the one-entry rows' and 1.0 per long row)
+inline size_t lockstep_direct_mat_ws_doubles(int n, int m, int r, int nzA, int nzB, int nv) {
+  return lockstep_mat_ws_doubles(n, m, nzA, nzB) + (size_t)kLsW * ((size_t)n * r + (size_t)nv) + 64;
 }
 
 // ---- the carves
@@ -129,6 +136,12 @@ inline bool lockstep_polish_layout(LsCursor &c, int n, int m, LsPolWs &s) { lock
 inline bool lockstep_mat_layout(LsCursor &c, int n, int m, int nzA, int nzB, LsMatVecs &t) {
   lockstep_carve_mat(c, t, n, m, nzA, nzB);
   return c.off <= lockstep_mat_ws_doubles(n, m, nzA, nzB);
+}
+// (the matrix block comes first and sits where lockstep_mat_layout puts it: ls_mat_block carves it from the same base)
+inline bool lockstep_direct_mat_layout(LsCursor &c, int n, int m, int r, int nzA, int nzB, int nv, LsMatVecs &t, LwMatVecs &d) {
+  lockstep_carve_mat(c, t, n, m, nzA, nzB);
+  d.WT = c.take((size_t)n * r * kLsW); d.vval = c.take((size_t)nv * kLsW);
+  return c.off <= lockstep_direct_mat_ws_doubles(n, m, r, nzA, nzB, nv);
 }
 // where the per-problem scalar state sits in a chunk's workspace: the counting carve's answer
 inline size_t lockstep_sc_offset(int n, int m) { LsCursor c; LsWs w; return lockstep_carve_base(c, w, n, m, n, true); }

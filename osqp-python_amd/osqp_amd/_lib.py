@@ -161,6 +161,9 @@ PROTOTYPES = {
     'osqp_hip_batch_solve_lockstep_direct': (C.c_int, [SolverP, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int]),
     'osqp_hip_batch_solve_lockstep_direct_device': (C.c_int, [SolverP, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     'osqp_hip_lockstep_direct_last_record': (C.c_int, [SolverP, c_double_p]),
+    'osqp_hip_batch_solve_lockstep_direct_mat': (C.c_int, [SolverP, C.c_int] + [c_double_p] * 8 + [C.c_int]),
+    'osqp_hip_batch_solve_lockstep_direct_mat_device': (C.c_int, [SolverP, C.c_int] + [C.c_void_p] * 8 + [C.c_int, C.c_void_p]),
+    'osqp_hip_lockstep_direct_mat_last_record': (C.c_int, [SolverP, c_double_p]),
     'osqp_hip_batch_adjoint_lockstep': (C.c_int, [SolverP, C.c_int] + [c_double_p] * 12),
     'osqp_hip_batch_adjoint_lockstep_device': (C.c_int, [SolverP, C.c_int] + [C.c_void_p] * 13),
     'osqp_hip_lockstep_adjoint_last_record': (C.c_int, [SolverP, c_double_p]),

@@ -439,8 +439,9 @@ class OSQPSolver:
         (lockstep_mat_last_record: the ADMM part; lockstep_polish_last_record: polish; lockstep_mat_scaling)."""
         return self._lockstep_host(self._lib.osqp_hip_batch_solve_lockstep, q, l, u, x0, y0, nbatch, Px, Ax)
 
-    def _lockstep_host(self, entry, q, l, u, x0, y0, nbatch, Px=None, Ax=None):
-        """The host-array call of a lockstep route (`entry`: its C entry point): widths checked here, then the engine."""
+    def _lockstep_host(self, entry, q, l, u, x0, y0, nbatch, Px=None, Ax=None, mat_entry=None):
+        """The host-array call of a lockstep route (`entry`: its C entry point; `mat_entry`: the one that takes Px / Ax, the lockstep route's by default):
+        widths checked here, then the engine."""
         arrs = [a for a in (q, l, u, x0, y0, Px, Ax) if a is not None]
         B = int(nbatch) if nbatch is not None else int(np.asarray(arrs[0]).shape[0])
 
@@ -456,9 +457,9 @@ class OSQPSolver:
         rec = np.zeros((B, self.BATCH_REC))
         if Px is not None or Ax is not None:
             Px, Ax = (None if a is None else rows(a, name, w) for a, name, w in ((Px, 'Px', self.nnz_P), (Ax, 'Ax', self.nnz_A)))
-            st = self._lib.osqp_hip_batch_solve_lockstep_mat(self._p, B, _ptr(Px, _lib.c_double_p), _ptr(Ax, _lib.c_double_p), _ptr(q, _lib.c_double_p),
-                                                             _ptr(l, _lib.c_double_p), _ptr(u, _lib.c_double_p), _ptr(x, _lib.c_double_p), _ptr(y, _lib.c_double_p),
-                                                             _ptr(rec, _lib.c_double_p), int(warm))
+            st = (mat_entry or self._lib.osqp_hip_batch_solve_lockstep_mat)(self._p, B, _ptr(Px, _lib.c_double_p), _ptr(Ax, _lib.c_double_p), _ptr(q, _lib.c_double_p),
+                                                                            _ptr(l, _lib.c_double_p), _ptr(u, _lib.c_double_p), _ptr(x, _lib.c_double_p), _ptr(y, _lib.c_double_p),
+                                                                            _ptr(rec, _lib.c_double_p), int(warm))
         else:
             st = entry(self._p, B, _ptr(q, _lib.c_double_p), _ptr(l, _lib.c_double_p), _ptr(u, _lib.c_double_p),
                        _ptr(x, _lib.c_double_p), _ptr(y, _lib.c_double_p), _ptr(rec, _lib.c_double_p), int(warm))
@@ -530,18 +531,40 @@ class OSQPSolver:
             out[k] = int(out[k])
         return out
 
-    def hip_batch_solve_lockstep_direct(self, q=None, l=None, u=None, x0=None, y0=None, nbatch=None):
+    def hip_batch_solve_lockstep_direct(self, q=None, l=None, u=None, x0=None, y0=None, nbatch=None, Px=None, Ax=None):
         """hip_batch_solve_lockstep for the handles it declines (osqp_hip_batch_solve_lockstep_direct): a Woodbury-corrected handle in the small mode
         whose K0 is diagonal (the factor-model portfolio QP) -- the Woodbury formula per problem in place of the PCG.  Same arguments, checks and
-        returns; every other handle raises with OSQP_FUNC_NOT_IMPLEMENTED."""
-        return self._lockstep_host(self._lib.osqp_hip_batch_solve_lockstep_direct, q, l, u, x0, y0, nbatch)
+        returns; every other handle raises with OSQP_FUNC_NOT_IMPLEMENTED.
+        Px (B, nnz(triu P)) / Ax (B, nnz(A)): per-problem matrix values in the CSC order given at setup (osqp_hip_batch_solve_lockstep_direct_mat); either
+        alone is allowed, the other side takes the handle's current values.  Every problem is scaled and solved as a solver set up with its data alone
+        (lockstep_direct_mat_last_record)."""
+        return self._lockstep_host(self._lib.osqp_hip_batch_solve_lockstep_direct, q, l, u, x0, y0, nbatch, Px, Ax, mat_entry=self._lib.osqp_hip_batch_solve_lockstep_direct_mat)
 
-    def hip_batch_solve_lockstep_direct_device(self, nbatch, q_ptr, l_ptr, u_ptr, x_ptr, y_ptr, rec_ptr, warm=False, stream=None):
+    def hip_batch_solve_lockstep_direct_device(self, nbatch, q_ptr, l_ptr, u_ptr, x_ptr, y_ptr, rec_ptr, warm=False, stream=None, Px_ptr=None, Ax_ptr=None):
         """osqp_hip_batch_solve_lockstep_direct_device: raw device addresses (int or None) laid out as in hip_batch_solve_lockstep; the work goes on
-        `stream` (None: the solver's) and the call returns when the results are there.  nbatch == 0: does the route apply?"""
-        st = self._lib.osqp_hip_batch_solve_lockstep_direct_device(self._p, int(nbatch), q_ptr, l_ptr, u_ptr, x_ptr, y_ptr, rec_ptr, int(bool(warm)), stream)
+        `stream` (None: the solver's) and the call returns when the results are there.  nbatch == 0: does the route apply?
+        Px_ptr / Ax_ptr: per-problem matrix values on the device (osqp_hip_batch_solve_lockstep_direct_mat_device)."""
+        if Px_ptr is not None or Ax_ptr is not None:
+            st = self._lib.osqp_hip_batch_solve_lockstep_direct_mat_device(self._p, int(nbatch), Px_ptr, Ax_ptr, q_ptr, l_ptr, u_ptr, x_ptr, y_ptr, rec_ptr, int(bool(warm)), stream)
+        else:
+            st = self._lib.osqp_hip_batch_solve_lockstep_direct_device(self._p, int(nbatch), q_ptr, l_ptr, u_ptr, x_ptr, y_ptr, rec_ptr, int(bool(warm)), stream)
         if st:
             raise self._batch_error(st)
+
+    # OSQP_HIP_LOCKSTEP_DIRECT_MAT_LAST_REC doubles of osqp_hip_lockstep_direct_mat_last_record
+    LOCKSTEP_DIRECT_MAT_LAST_FIELDS = ('chunks', 'width', 'admm_iters_max', 'factorisations', 'kernel_launches', 'gpu_ms', 'matrix_block_bytes', 'prepare_gpu_ms')
+
+    def lockstep_direct_mat_last_record(self):
+        """osqp_hip_lockstep_direct_mat_last_record as a dict (LOCKSTEP_DIRECT_MAT_LAST_FIELDS): what the last direct lockstep call with per-problem
+        matrices of this handle did; zeros before the first."""
+        rec = np.zeros(len(self.LOCKSTEP_DIRECT_MAT_LAST_FIELDS))
+        st = self._lib.osqp_hip_lockstep_direct_mat_last_record(self._p, _ptr(rec, _lib.c_double_p))
+        if st:
+            raise ValueError(str(int(st)))
+        out = dict(zip(self.LOCKSTEP_DIRECT_MAT_LAST_FIELDS, rec.tolist()))
+        for k in ('chunks', 'width', 'admm_iters_max', 'factorisations', 'kernel_launches', 'matrix_block_bytes'):
+            out[k] = int(out[k])
+        return out
 
     # OSQP_HIP_LOCKSTEP_DIRECT_LAST_REC doubles of osqp_hip_lockstep_direct_last_record
     LOCKSTEP_DIRECT_LAST_FIELDS = ('chunks', 'width', 'admm_iters_max', 'factorisations', 'kernel_launches', 'gpu_ms', 'workspace_bytes', 'seconds')

@@ -20,6 +20,10 @@ threads.  Here one persistent engine handle plays that role:
     With ``large_batch='lockstep'`` (one rank) a forward with 2-D P_val and / or A_val that the single launch declines makes ONE call of the lockstep
     route with per-element matrices (osqp_hip_batch_solve_lockstep_mat; ``mat_lockstep_launches`` counts them) in place of the per-element loop; its
     backward is the per-element loop unless ``large_backward='lockstep'`` (below).
+    With ``large_batch='lockstep_direct'`` (one rank) such a forward on a Woodbury handle with a diagonal K0 makes ONE call of the direct route with per-element
+    matrices (osqp_hip_batch_solve_lockstep_direct_mat: every element scaled and solved on its own P_val / A_val; ``mat_lockstep_direct_launches`` counts
+    them; host and ROCm tensors alike through the host entry); a handle that entry declines goes on to the per-element loop as before.  The backward of such a
+    forward is unchanged -- the per-element loop -- and on a Woodbury handle it still raises NotImplementedError.
   * ``polishing=True`` (default False: every forward as before) is passed to ``setup``: the handle polishes every solved problem, on whichever route the
     forward takes -- the one-workgroup kernel, the per-element loop, the lockstep route with shared or with per-element matrices (there the polish runs
     on the device inside the one call; ``lockstep_polish_last_record`` of the handle counts attempted / accepted / rejected).  The adjoint classifies the
@@ -91,6 +95,7 @@ class OSQP(Module):
         self._grad_maps = None
         self.mat_lockstep_launches = 0   # calls of the lockstep route with per-element matrices made by this layer's forwards (large_batch='lockstep')
         self.last_rec = None         # per-element record of the last forward that ran on host arrays (ext_hip BATCH_FIELDS where a batch route made it: status_polish is column 8)
+        self.mat_lockstep_direct_launches = 0   # calls of the direct lockstep route with per-element matrices made by this layer's forwards (large_batch='lockstep_direct')
         self.mat_lockstep_adjoint_launches = 0   # calls of the lockstep adjoint with per-element matrices made by this layer's backwards (large_backward='lockstep')
 
     # ------------------------------------------------------------------ the persistent handle
@@ -182,6 +187,15 @@ class OSQP(Module):
                         x, y, rec = s._solver.hip_batch_solve_lockstep(q=qn, l=ln, u=un, Px=(Pn[:, self._triu_pick] if batched[0] else None), Ax=(An if batched[2] else None), nbatch=nb)
                         self.last_dual = y
                         self.mat_lockstep_launches += 1
+                    elif self.large_batch == 'lockstep_direct':                         # a Woodbury handle with a diagonal K0, every element on its own matrices: ONE call (osqp_hip_batch_solve_lockstep_direct_mat)
+                        try:
+                            x, y, rec = s._solver.hip_batch_solve_lockstep_direct(q=qn, l=ln, u=un, Px=(Pn[:, self._triu_pick] if batched[0] else None), Ax=(An if batched[2] else None), nbatch=nb)
+                            self.last_dual = y
+                            self.mat_lockstep_direct_launches += 1
+                        except ValueError as e2:                                        # a handle that entry declines: the per-element loop, as before
+                            if str(e2) != str(int(osqp_amd.SolverError.OSQP_FUNC_NOT_IMPLEMENTED)):
+                                raise
+                            x = rec = None
             if x is None:
                 x, rec = self._loop(Pn, qn, An, ln, un, nb, batched, dev_index)
         self.last_rec = rec
