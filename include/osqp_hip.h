@@ -390,7 +390,7 @@ OSQPInt osqp_hip_lockstep_direct_last_record(OSQPSolver *solver, OSQPFloat *rec)
  * it under this handle's settings: its own Ruiz equilibration D_b, E_b, c_b (settings.scaling iterations, on the device, per lane), its own D0_b, S_b and
  * S_b^-1, the direct route's rho rule with this handle's tolerance.  The other arguments, the nbatch == 0 query, stream semantics, the record per problem,
  * statuses / certificates (in the problem's own units) / time_limit and the INDEPENDENCE guarantee are those of osqp_hip_batch_solve_lockstep_direct[_device].
- * No polish, no backward pass with per-problem matrices on this route.  The handle is only read: its matrices, scaling, dense rows, S, iterates, settings and
+ * No polish on this route; the backward pass with per-problem matrices is osqp_hip_batch_adjoint_lockstep_direct_mat below.  The handle is only read: its matrices, scaling, dense rows, S, iterates, settings and
  * launch history are not touched.  Returns OSQP_FUNC_NOT_IMPLEMENTED unless osqp_hip_batch_solve_lockstep_direct serves the handle AND the chunk's
  * assembly does (device assembly, no repeated (j, j) entry in the stored triangle of P); in the host simulator always.
  * Device memory: 512 (nnz(A) + nnz(B) + 2 n + 2 m + n r + nnz of the view) bytes for one chunk, allocated by the first such call (22 MB of dense rows at
@@ -444,7 +444,7 @@ OSQPInt osqp_hip_lockstep_adjoint_last_record(OSQPSolver *solver, OSQPFloat *rec
  * calls made here in between.  The handle's own matrices, scaling, iterates, graphs and history are not touched.
  * Returns OSQP_FUNC_NOT_IMPLEMENTED unless both osqp_hip_batch_adjoint_lockstep and osqp_hip_batch_solve_lockstep_mat serve the handle: a Woodbury
  * handle, the host simulator, a handle without device-side assembly, a repeated (j, j) entry in the stored upper triangle of P.
- * OUT OF SCOPE: the direct (Woodbury) route, multi-rank sharding of this entry.
+ * OUT OF SCOPE: multi-rank sharding of this entry.  (The direct (Woodbury) route: osqp_hip_batch_adjoint_lockstep_direct_mat below.)
  * osqp_hip_lockstep_mat_adjoint_last_record: OSQP_HIP_LOCKSTEP_MAT_ADJOINT_LAST_REC doubles {chunks, chunk width, recurrence steps of the slowest
  * problem, PCG iterations summed over the problems, kernel launches of the whole call, GPU ms of the whole call, bytes of the matrix block, GPU ms spent
  * in assembly + equilibration}; all zero before the first call.  osqp_hip_lockstep_adjoint_last_record is written as by any lockstep adjoint call. */
@@ -476,6 +476,33 @@ OSQPInt osqp_hip_batch_adjoint_lockstep_direct_device(OSQPSolver *solver, OSQPIn
                                                       const OSQPFloat *y_dev, const OSQPFloat *dx_dev, const OSQPFloat *dy_dev, OSQPFloat *dP_dev, OSQPFloat *dq_dev,
                                                       OSQPFloat *dA_dev, OSQPFloat *dl_dev, OSQPFloat *du_dev, OSQPFloat *arec_dev, void *stream);
 OSQPInt osqp_hip_lockstep_direct_adjoint_last_record(OSQPSolver *solver, OSQPFloat *rec);
+/* ... WITH PER-PROBLEM MATRICES -- the backward pass of osqp_hip_batch_solve_lockstep_direct_mat: osqp_hip_batch_adjoint_lockstep_direct's semantics on the
+ * element's OWN matrices.  Problem b's adjoint system is solved on its own P_b, A_b (the dense rows' values included: one factor model per problem), scaled
+ * by its own D_b, E_b, c_b, with the Woodbury formula per problem: D0_b, S_b and S_b^-1 are the problem's own, S_b is inverted once.  Px is nbatch x
+ * nnz(triu P), Ax nbatch x nnz(A), in the CSC order given at setup, as osqp_hip_batch_solve_lockstep_direct_mat takes them; either may be NULL: the handle's
+ * own raw values for every problem.  Every other argument, the OSQP_HIP_ADJOINT_REC record, the statuses 0 / 2 / 3, the stream semantics and INDEPENDENCE
+ * (a problem's matrices being part of the problem) are osqp_hip_batch_adjoint_lockstep_direct[_device]'s; dP / dA are per problem at every stored entry, the
+ * dense rows' included.  nbatch == 0 on the device entry answers applicability and does nothing else.  A chunk's matrices are prepared as on the forward
+ * entry (assembly, equilibration, the chunk's own dense rows and view values: 7 + 4 x settings.scaling launches in front of its transposes in), with the
+ * handle's q for every problem: the adjoint does not depend on the cost scale c in exact arithmetic.
+ * MATRIX BLOCK: the forward entry's, allocated by whichever of the two entries is called first.  A call here overwrites it; the forward entry prepares it
+ * anew in every call, so its results do not depend on calls made here in between.  The handle's own matrices, scaling, iterates, graphs and history, the
+ * forward route's workspace and its records are not touched.
+ * Returns OSQP_FUNC_NOT_IMPLEMENTED for everything either parent entry declines: what osqp_hip_batch_adjoint_lockstep_direct declines (no Woodbury
+ * correction, r > 128, a K0 that is not diagonal, a reordered handle, the host simulator) and what osqp_hip_batch_solve_lockstep_direct_mat declines (a handle
+ * without device-side assembly, a repeated (j, j) entry in the stored upper triangle of P).  It does not polish.
+ * osqp_hip_lockstep_direct_mat_adjoint_last_record: OSQP_HIP_LOCKSTEP_DIRECT_MAT_ADJOINT_LAST_REC doubles {chunks, chunk width, recurrence steps of the
+ * slowest problem, inversions of S summed over the problems, kernel launches of the whole call, GPU ms of the whole call, bytes of the matrix block, GPU
+ * ms spent in the preparation}; all zero before the first call.  osqp_hip_lockstep_direct_adjoint_last_record is written as by any direct adjoint call. */
+#define OSQP_HIP_LOCKSTEP_DIRECT_MAT_ADJOINT_LAST_REC 8
+OSQPInt osqp_hip_batch_adjoint_lockstep_direct_mat(OSQPSolver *solver, OSQPInt nbatch, const OSQPFloat *Px, const OSQPFloat *Ax, const OSQPFloat *l, const OSQPFloat *u,
+                                                   const OSQPFloat *x, const OSQPFloat *y, const OSQPFloat *dx, const OSQPFloat *dy, OSQPFloat *dP, OSQPFloat *dq,
+                                                   OSQPFloat *dA, OSQPFloat *dl, OSQPFloat *du, OSQPFloat *arec);
+OSQPInt osqp_hip_batch_adjoint_lockstep_direct_mat_device(OSQPSolver *solver, OSQPInt nbatch, const OSQPFloat *Px_dev, const OSQPFloat *Ax_dev, const OSQPFloat *l_dev,
+                                                          const OSQPFloat *u_dev, const OSQPFloat *x_dev, const OSQPFloat *y_dev, const OSQPFloat *dx_dev,
+                                                          const OSQPFloat *dy_dev, OSQPFloat *dP_dev, OSQPFloat *dq_dev, OSQPFloat *dA_dev, OSQPFloat *dl_dev,
+                                                          OSQPFloat *du_dev, OSQPFloat *arec_dev, void *stream);
+OSQPInt osqp_hip_lockstep_direct_mat_adjoint_last_record(OSQPSolver *solver, OSQPFloat *rec);
 
 /* ADJOINT DERIVATIVES of a batch of solved QPs -- the backward pass of osqp_hip_batch_solve[_mat]: ONE launch, one workgroup per problem
  * (batch_hip.hip k_batch_adjoint).  For problem b with solution x (n), y (m) and incoming gradients dx = dL/dx (n), dy = dL/dy (m; NULL = 0):

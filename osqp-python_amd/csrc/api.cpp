@@ -173,6 +173,17 @@ OSQPInt osqp_hip_batch_adjoint_lockstep_direct_device(OSQPSolver *s, OSQPInt nba
   return guarded(s, [&](Engine &e) { return e.batch_adjoint_lockstep_direct_device(nbatch, l, u, x, y, dx, dy, dP, dq, dA, dl, du, rec, stream); });
 }
 OSQPInt osqp_hip_lockstep_direct_adjoint_last_record(OSQPSolver *s, OSQPFloat *rec) { return guarded(s, [&](Engine &e) { return e.lockstep_direct_adjoint_last_record(rec); }); }
+OSQPInt osqp_hip_batch_adjoint_lockstep_direct_mat(OSQPSolver *s, OSQPInt nbatch, const OSQPFloat *Px, const OSQPFloat *Ax, const OSQPFloat *l, const OSQPFloat *u, const OSQPFloat *x,
+                                                   const OSQPFloat *y, const OSQPFloat *dx, const OSQPFloat *dy, OSQPFloat *dP, OSQPFloat *dq, OSQPFloat *dA, OSQPFloat *dl, OSQPFloat *du,
+                                                   OSQPFloat *arec) {
+  return guarded(s, [&](Engine &e) { return e.batch_adjoint_lockstep_direct_mat(nbatch, Px, Ax, l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec); });
+}
+OSQPInt osqp_hip_batch_adjoint_lockstep_direct_mat_device(OSQPSolver *s, OSQPInt nbatch, const OSQPFloat *Px, const OSQPFloat *Ax, const OSQPFloat *l, const OSQPFloat *u,
+                                                          const OSQPFloat *x, const OSQPFloat *y, const OSQPFloat *dx, const OSQPFloat *dy, OSQPFloat *dP, OSQPFloat *dq, OSQPFloat *dA,
+                                                          OSQPFloat *dl, OSQPFloat *du, OSQPFloat *arec, void *stream) {
+  return guarded(s, [&](Engine &e) { return e.batch_adjoint_lockstep_direct_mat_device(nbatch, Px, Ax, l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec, stream); });
+}
+OSQPInt osqp_hip_lockstep_direct_mat_adjoint_last_record(OSQPSolver *s, OSQPFloat *rec) { return guarded(s, [&](Engine &e) { return e.lockstep_direct_mat_adjoint_last_record(rec); }); }
 OSQPInt osqp_hip_adjoint_last_record(OSQPSolver *s, OSQPFloat *rec) { return guarded(s, [&](Engine &e) { return e.adjoint_last_record(rec); }); }
 OSQPInt osqp_hip_batch_adjoint(OSQPSolver *s, OSQPInt nbatch, const OSQPFloat *Px, const OSQPFloat *Ax, const OSQPFloat *l, const OSQPFloat *u, const OSQPFloat *x, const OSQPFloat *y,
                                const OSQPFloat *dx, const OSQPFloat *dy, OSQPFloat *dP, OSQPFloat *dq, OSQPFloat *dA, OSQPFloat *dl, OSQPFloat *du, OSQPFloat *arec) {

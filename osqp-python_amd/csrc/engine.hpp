@@ -103,6 +103,13 @@ class Engine {
   int batch_adjoint_lockstep_direct_device(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
                                            double *dP, double *dq, double *dA, double *dl, double *du, double *arec, void *stream);
   int lockstep_direct_adjoint_last_record(double *rec) const;
+  // ... with a P_val / A_val per problem (include/osqp_hip.h osqp_hip_batch_adjoint_lockstep_direct_mat): Px / Ax as batch_solve_lockstep_direct_mat takes
+  // them, the rest as above; serves the handles both that entry and batch_adjoint_lockstep_direct serve.
+  int batch_adjoint_lockstep_direct_mat(int nbatch, const double *Px, const double *Ax, const double *l, const double *u, const double *x, const double *y, const double *dx,
+                                        const double *dy, double *dP, double *dq, double *dA, double *dl, double *du, double *arec);
+  int batch_adjoint_lockstep_direct_mat_device(int nbatch, const double *Px, const double *Ax, const double *l, const double *u, const double *x, const double *y, const double *dx,
+                                               const double *dy, double *dP, double *dq, double *dA, double *dl, double *du, double *arec, void *stream);
+  int lockstep_direct_mat_adjoint_last_record(double *rec) const;
   // Adjoint derivatives (include/osqp_hip.h osqp_hip_batch_adjoint; batch_hip.hip k_batch_adjoint): one launch for the batch.  Host arrays, or -- _device --
   // device arrays and a caller's stream with the semantics of batch_solve_device.  Px / Ax / l / u: nullptr = this solver's own values for every problem.
   int batch_adjoint(int nbatch, const double *Px, const double *Ax, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
@@ -206,8 +213,9 @@ class Engine {
   double lsa_rec_[OSQP_HIP_LOCKSTEP_ADJOINT_LAST_REC] = {0, 0, 0, 0, 0, 0, 0, 0};     // record of the last lockstep adjoint call (osqp_hip_lockstep_adjoint_last_record)
   bool lockstep_adjoint_applies();
   // the arrays of a backward pass (host or device, as the entry says); one body per entry kind and one chunk loop serve both routes (direct: the
-  // direct route's applicability, work block, chunk function and record).  mat: the entries with per-problem matrices (PCG route only; Px / Ax in the
-  // caller's CSC order, either may be nullptr) -- the matrix block is the forward's lsmw_, the record lsma_rec_ next to lsa_rec_.
+  // direct route's applicability, work block, chunk function and record).  mat: the entries with per-problem matrices (Px / Ax in the
+  // caller's CSC order, either may be nullptr) -- the matrix block is the forward's of that route (lsmw_ / lsdmw_), the record lsma_rec_ / lsdma_rec_ next to
+  // lsa_rec_ / lsda_rec_.
   struct LockstepAdjointIO { const double *l, *u, *x, *y, *dx, *dy; double *dP, *dq, *dA, *dl, *du, *arec; bool mat = false; const double *Px = nullptr, *Ax = nullptr; };
   double lsma_rec_[OSQP_HIP_LOCKSTEP_MAT_ADJOINT_LAST_REC] = {0, 0, 0, 0, 0, 0, 0, 0};     // record of the last such call (osqp_hip_lockstep_mat_adjoint_last_record)
   int adjoint_lockstep_host(bool direct, int nbatch, const LockstepAdjointIO &h);
@@ -216,6 +224,7 @@ class Engine {
   // the backward pass on the direct route: its own work block (lockstep_direct_adjoint_ws_doubles(n, m, r)) and record
   double *lsdaw_ = nullptr;
   double lsda_rec_[OSQP_HIP_LOCKSTEP_DIRECT_ADJOINT_LAST_REC] = {0, 0, 0, 0, 0, 0, 0, 0};
+  double lsdma_rec_[OSQP_HIP_LOCKSTEP_DIRECT_MAT_ADJOINT_LAST_REC] = {0, 0, 0, 0, 0, 0, 0, 0};     // record of the last such call with per-problem matrices (osqp_hip_lockstep_direct_mat_adjoint_last_record)
   bool lockstep_direct_adjoint_applies();
   // what the four batch entry points begin with, and the host staging of the two that take host arrays (engine_api.cpp)
   bool batch_applies();                               // the workgroup route: the QP fits one workgroup's LDS and the handle is not reordered

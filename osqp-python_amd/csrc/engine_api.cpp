@@ -931,6 +931,7 @@ int Engine::lockstep_direct_mat_last_record(double *rec) const { return last_rec
 int Engine::lockstep_adjoint_last_record(double *rec) const { return last_record(lsa_rec_, OSQP_HIP_LOCKSTEP_ADJOINT_LAST_REC, rec); }
 int Engine::lockstep_mat_adjoint_last_record(double *rec) const { return last_record(lsma_rec_, OSQP_HIP_LOCKSTEP_MAT_ADJOINT_LAST_REC, rec); }
 int Engine::lockstep_direct_adjoint_last_record(double *rec) const { return last_record(lsda_rec_, OSQP_HIP_LOCKSTEP_DIRECT_ADJOINT_LAST_REC, rec); }
+int Engine::lockstep_direct_mat_adjoint_last_record(double *rec) const { return last_record(lsdma_rec_, OSQP_HIP_LOCKSTEP_DIRECT_MAT_ADJOINT_LAST_REC, rec); }
 
 int Engine::run_lockstep(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream,
                          bool mat, const double *Px, const double *Ax) {
@@ -1206,20 +1207,23 @@ bool Engine::lockstep_adjoint_applies() { return be::lockstep_adjoint_chunk && b
 // workspace and its record are not written.
 bool Engine::lockstep_direct_adjoint_applies() { return lockstep_direct_applies() && be::lockstep_direct_adjoint_chunk && be::device_assembly(); }
 
-// Both routes' chunk loop.  direct selects the applicability, the work block, the chunk function and the record.  a.mat (PCG route): every chunk assembles
-// and equilibrates its problems' own matrices in the forward's matrix block (lsmw_: one block per handle, allocated by whichever entry comes first), which
-// this call therefore overwrites -- lockstep_mat_scaling answers OSQP_DATA_NOT_INITIALIZED until the next forward call.
+// Both routes' chunk loop.  direct selects the applicability, the work block, the chunk function and the record.  a.mat: every chunk assembles and
+// equilibrates its problems' own matrices in the forward's matrix block of that route (PCG: lsmw_; direct: lsdmw_, which also holds the chunk's own dense
+// rows and view values -- one block per handle, allocated by whichever entry comes first), which this call therefore overwrites -- lockstep_mat_scaling
+// answers OSQP_DATA_NOT_INITIALIZED until the next forward call.  A forward call prepares its block anew, so its results do not depend on this one.
 int Engine::run_lockstep_adjoint(bool direct, int nbatch, const LockstepAdjointIO &a, void *stream) {
   const int nzP = d_.nzP, nzA = d_.nzA;
-  const bool mat = a.mat && !direct;
+  const bool mat = a.mat;
   const size_t need = direct ? lockstep_direct_adjoint_ws_doubles(n, m, d_.wb.r) : lockstep_adjoint_ws_doubles(n, m);
-  const size_t mneed = lockstep_mat_ws_doubles(n, m, d_.A.nnz, d_.B.nnz);
   LockstepDirectAdjointParams p;                      // (the PCG route takes its LockstepAdjointParams base)
   if (direct) if (const int err = fill_lockstep_direct_view(p.v, stream)) return err;
+  const size_t mneed = direct ? lockstep_direct_mat_ws_doubles(n, m, d_.wb.r, d_.A.nnz, d_.B.nnz, lsd_nv_) : lockstep_mat_ws_doubles(n, m, d_.A.nnz, d_.B.nnz);
   double *&ws = direct ? lsdaw_ : lsaw_;
+  double *&mws = direct ? lsdmw_ : lsmw_;
   bool fresh = ensure_value_maps();
   if (!ws) { ws = dev_vec<double>(d_, need); fresh = true; }
-  if (mat && !lsmw_) { lsmw_ = dev_vec<double>(d_, mneed); fresh = true; }
+  if (mat && !mws) { mws = dev_vec<double>(d_, mneed); fresh = true; }
+  if (mat && direct) { prepare_lockstep_direct_wtpos(); p.v.wtpos = lsd_wtpos_; p.v.vsrc = lsd_vsrc_; }
   if (fresh) be::sync(d_);
   fill_batch_settings(p, 0);
   fill_lockstep_handle(p);
@@ -1231,8 +1235,8 @@ int Engine::run_lockstep_adjoint(bool direct, int nbatch, const LockstepAdjointI
   p.nzP = nzP; p.nzA = nzA; p.Pi = d_.Pi; p.Pj = d_.Pj; p.Ai = d_.Ai; p.Aj = d_.Aj; p.Pmap = reordered_ ? d_pvmap_ : nullptr; p.Amap = reordered_ ? d_avmap_ : nullptr;
   double mst[kLsMatStat] = {0, 0}, mtot = 0;
   if (mat) {
-    p.mat_ws = lsmw_; p.mat_stat = mst; p.mat_iters = std::max(0, (int)settings.scaling); p.pvmap = p.Pmap; p.avmap = p.Amap;
-    lsm_last_count_ = 0;                              // (the block is being overwritten)
+    p.mat_ws = mws; p.mat_stat = mst; p.mat_iters = std::max(0, (int)settings.scaling); p.pvmap = p.Pmap; p.avmap = p.Amap;
+    if (!direct) lsm_last_count_ = 0;                 // (the block is being overwritten)
   }
   double tot[4] = {0, 0, 0, 0};
   int chunks = 0;
@@ -1253,7 +1257,8 @@ int Engine::run_lockstep_adjoint(bool direct, int nbatch, const LockstepAdjointI
   std::copy(r, r + OSQP_HIP_LOCKSTEP_ADJOINT_LAST_REC, direct ? lsda_rec_ : lsa_rec_);
   if (mat) {
     const double rm[OSQP_HIP_LOCKSTEP_MAT_ADJOINT_LAST_REC] = {(double)chunks, (double)kLsW, tot[0], tot[1], tot[2], tot[3], (double)(mneed * sizeof(double)), mtot};
-    std::copy(rm, rm + OSQP_HIP_LOCKSTEP_MAT_ADJOINT_LAST_REC, lsma_rec_);
+    static_assert(OSQP_HIP_LOCKSTEP_MAT_ADJOINT_LAST_REC == OSQP_HIP_LOCKSTEP_DIRECT_MAT_ADJOINT_LAST_REC, "one record text for both routes with per-problem matrices");
+    std::copy(rm, rm + OSQP_HIP_LOCKSTEP_MAT_ADJOINT_LAST_REC, direct ? lsdma_rec_ : lsma_rec_);
   }
   return OSQP_NO_ERROR;
 }
@@ -1263,7 +1268,7 @@ int Engine::adjoint_lockstep_host(bool direct, int nbatch, const LockstepAdjoint
   if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   if (nbatch <= 0 || !h.x || (!h.y && m > 0) || !h.dx) return OSQP_DATA_VALIDATION_ERROR;
   be::activate(d_);
-  if (!(direct ? lockstep_direct_adjoint_applies() : lockstep_adjoint_applies()) || (h.mat && (direct || !lockstep_mat_applies()))) return OSQP_FUNC_NOT_IMPLEMENTED;
+  if (!(direct ? lockstep_direct_adjoint_applies() : lockstep_adjoint_applies()) || (h.mat && !(direct ? lockstep_direct_mat_applies() : lockstep_mat_applies()))) return OSQP_FUNC_NOT_IMPLEMENTED;
   be::ext_wait(d_);
   DevScratch &sc = direct ? lsdabuf_ : lsabuf_;
   const size_t nb = (size_t)nbatch, N = nb * n, M = nb * m, NP = nb * (size_t)d_.nzP, NA = nb * (size_t)d_.nzA;
@@ -1291,7 +1296,7 @@ int Engine::adjoint_lockstep_device(bool direct, int nbatch, const LockstepAdjoi
   if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   if (nbatch < 0) return OSQP_DATA_VALIDATION_ERROR;
   be::activate(d_);
-  if (!(direct ? lockstep_direct_adjoint_applies() : lockstep_adjoint_applies()) || (a.mat && (direct || !lockstep_mat_applies()))) return OSQP_FUNC_NOT_IMPLEMENTED;
+  if (!(direct ? lockstep_direct_adjoint_applies() : lockstep_adjoint_applies()) || (a.mat && !(direct ? lockstep_direct_mat_applies() : lockstep_mat_applies()))) return OSQP_FUNC_NOT_IMPLEMENTED;
   if (nbatch == 0) return OSQP_NO_ERROR;              // (the applicability query, as osqp_hip_batch_solve_lockstep_device answers it)
   if (!a.x || (!a.y && m > 0) || !a.dx) return OSQP_DATA_VALIDATION_ERROR;
   be::ext_wait(d_);
@@ -1322,6 +1327,14 @@ int Engine::batch_adjoint_lockstep_direct(int nbatch, const double *l, const dou
 int Engine::batch_adjoint_lockstep_direct_device(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
                                                  double *dP, double *dq, double *dA, double *dl, double *du, double *arec, void *stream) {
   return adjoint_lockstep_device(true, nbatch, {l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec}, stream);
+}
+int Engine::batch_adjoint_lockstep_direct_mat(int nbatch, const double *Px, const double *Ax, const double *l, const double *u, const double *x, const double *y, const double *dx,
+                                              const double *dy, double *dP, double *dq, double *dA, double *dl, double *du, double *arec) {
+  return adjoint_lockstep_host(true, nbatch, {l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec, true, Px, Ax});
+}
+int Engine::batch_adjoint_lockstep_direct_mat_device(int nbatch, const double *Px, const double *Ax, const double *l, const double *u, const double *x, const double *y, const double *dx,
+                                                     const double *dy, double *dP, double *dq, double *dA, double *dl, double *du, double *arec, void *stream) {
+  return adjoint_lockstep_device(true, nbatch, {l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec, true, Px, Ax}, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ adjoint derivatives

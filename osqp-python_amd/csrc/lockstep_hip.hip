@@ -1210,7 +1210,8 @@ __global__ __launch_bounds__(256) void k_lwm_wt(int cnt, const int *pos, const d
 }
 // ---- the backward pass of the direct route (lockstep_direct_adjoint_chunk below).  "adjoint derivatives of a chunk" with the PCG replaced by the solve
 // above: rho never changes in the recurrence (alpha = 1, rho_bar = 1 / delta_eff on the active rows, rho_min on the others), so S_b is formed and
-// inverted ONCE per problem.  The kernels are those two sections'; what they do not cover is the two below.
+// inverted ONCE per problem.  The kernels are those two sections'; what they do not cover is the two below.  With per-problem matrices
+// (osqp_hip_batch_adjoint_lockstep_direct_mat) the same pass behind the forward's preparation, on the k_lsm_adj_* twins and the k_lwm_* forms.
 // the rows n .. n + r - 1 of `dst` from ONE set of k_lw_prod's partials (pg), folded in block order, for every lane: a wave per row
 __global__ __launch_bounds__(256) void k_lwa_setl(LwK k, double *dst) {
   const int lane = ls_lane(), r = k.d.r;
@@ -1744,43 +1745,86 @@ int lockstep_direct_chunk(Dev &d, const LockstepDirectParams &p0, void *stream, 
 // rho is set, and S formed and inverted, once; a step is eleven launches and one read of the word block.  A pivot of S_b that is not positive and finite
 // leaves NaN iterates in that lane alone: its residual is not below the threshold and it ends with status 3.
 // stat: {recurrence steps of the slowest problem, inversions of S summed over the problems, kernel launches, GPU ms}.
+// PER-PROBLEM MATRICES (p.mat_ws != nullptr; include/osqp_hip.h osqp_hip_batch_adjoint_lockstep_direct_mat): problem b's adjoint system is solved on its own
+// P_b, A_b under its own D_b, E_b, c_b, by the Woodbury formula per lane.  The block is the direct forward's (the matrix block, then the chunk's own WT and
+// view values); in front of the transposes in it is prepared as lockstep_direct_chunk prepares it -- ls_mat_prepare with the handle's q for every problem (as
+// lockstep_adjoint_chunk: the adjoint does not depend on c in exact arithmetic), then k_lwm_wt and k_lwm_vals on the block's scaled A; R.em marks the end of
+// all three.  From then on the row passes are kLsOwnMat's and the k_lsm_adj_* twins, the dense rows' kernels the k_lwm_* forms; a step
+// stays eleven launches.  The shared path launches what it launched before.
+// The preparation's scratch is dead before it is written again.  Its users are the k_lsm_* kernels of ls_mat_prepare alone: k_lwm_wt / k_lwm_vals read the
+// block's Aval and write the block's WT / vval, nothing of the work block.  Then, in launch order:
+//   q           written by k_lsm_adj_load_n (q~ = c D dx, all n rows, every lane) -- the first launch after the preparation; nothing reads q before.
+//   et in t     the launches up to D.factor -- adj_load_n / adj_load_m, k_lwm_prod + k_lwa_setl (read x~, write pg and rows n .. n + r - 1 of x~),
+//               k_lsm_adj_class (reads x~, l, u, ay, gdy; writes code, l, u, z, zt, y, dy), k_ls_adj_init (scalar rows, iw), k_lwa_zero (x, x~, dx over
+//               n + r rows: none of them is r, t or q) -- neither read nor write t.  k_ls_setrho, D.factor's first launch, writes t = rho z - y and t2 over all
+//               m rows for every lane (k_ls_adj_init flags them all; m >= 1 here), and the first reader of t is the first k_lsm_rhs, after it.
+//   dt in r     D.factor's other launches (k_lwm_d0: Minv; k_lwm_s: S; k_lw_inv: S, fact) do not touch r; the first k_lsm_rhs writes r for every live lane
+//               before k_lwm_prod .. k_lwm_x, which read p and Minv, not r.  A lane that is not live (>= count, or status 2) keeps dt in r: no kernel
+//               reads r but k_ls_rhs' successors in the PCG, which this route does not have.
+//   SC_C, SC_CINV, SC_CT   rows of THIS work block's scalar state (the direct adjoint's, not the forward's).  After the preparation they are only read
+//               (adj_load_n, adj_unscale, adj_resn): k_ls_adj_init writes SC_RHOBAR, SC_EQF, SC_EPSCG, SC_EPSPREV, SC_BEST, SC_NACT and k_ls_adj_decide SC_BEST,
+//               all below SC_C; there are no PCG folds here.
+// The block vectors x, x~, dx have n + r rows here; the preparation never uses them.
 int lockstep_direct_adjoint_chunk(Dev &d, const LockstepDirectAdjointParams &p, void *stream, double *stat) {
   const hipStream_t s = ls_stream(d, stream);
   const int n = p.n, m = p.m, r = p.v.r, tn = (n + 63) / 64, tm = (m + 63) / 64;
+  const bool mat = p.mat_ws != nullptr;
   if (r < 1 || r > kWbMaxRows || m < 1) return OSQP_FUNC_NOT_IMPLEMENTED;
   LsAK ka{p, {}, {}};
   LwVecs x;
   LsCursor c{p.ws};
   if (!lockstep_direct_layout(c, n, m, r, ka.w, x, &ka.a)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  LockstepDirectView v = p.v;
+  LsMat mt{};
+  LwMatVecs xm{};
+  if (mat) {
+    if (!v.wtpos || !v.vsrc) return OSQP_FUNC_NOT_IMPLEMENTED;
+    if (const int err = ls_mat_block(d, ka.P, mt)) return err;
+    LsCursor cm{p.mat_ws};
+    LsMatVecs again;
+    if (!lockstep_direct_mat_layout(cm, n, m, r, p.A.nnz, p.B.nnz, v.Av.nnz, again, xm)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+    v.WT = xm.WT; v.Av.val = xm.vval;
+  }
   const LsWs &w = ka.w;
-  const LwRun D(p, p.v, w, x);
-  const int G = w.G, GC = D.GC;
+  const LwRun D(ka.P, v, w, x, mat);
+  const LsPcgKernels &K = D.K();
+  const int G = w.G;
   // the adjoint's own views: kl makes k_ls_adj_load_n put x~ = Dinv x where k_ls_adj_class, through the view (kc), will gather it -- the first n rows of the
-  // block vector x~ -- by exchanging the roles of p and x~ (the zeros then go to p, which k_ls_rhs overwrites)
+  // block vector x~ -- by exchanging the roles of p and x~ (the zeros then go to p, which k_ls_rhs overwrites).  With per-problem matrices kc's A is the view
+  // on the chunk's per-lane values ([nv][64]); E, Einv, D, Dinv are the block's in all three (ka.P after ls_mat_block).
   LsAK kl = ka; kl.w.p = w.xs; kl.w.xs = w.p;
-  LsAK kc = ka; kc.P.A = p.v.Av; kc.w.p = w.xs;
+  LsAK kc = ka; kc.P.A = v.Av; kc.w.p = w.xs;
   LsRun R(s, w.word, p.count);
   R.e0.record(s);
-  auto long_rows_of = [&](double *v) { R.go(k_lw_prod, GC, D.k, (const double *)v, x.pg); R.go(k_lwa_setl, (r + 3) / 4, D.k, v); };
+  if (mat) {
+    const int nv = v.Av.nnz, nwt = n * r;
+    ls_mat_prepare(R, LsMK{ka.P, w, mt});
+    R.go(k_lwm_wt, std::min(1024, (nwt + 3) / 4), nwt, v.wtpos, (const double *)mt.Aval, xm.WT);
+    R.go(k_lwm_vals, std::min(1024, (nv + 3) / 4), nv, v.vsrc, (const double *)mt.Aval, xm.vval);
+    R.em.record(s);
+    if (p.mat_stat) p.mat_stat[1] += 2;
+  }
+  auto long_rows_of = [&](double *vec) { D.prod(R, vec, x.pg); R.go(k_lwa_setl, (r + 3) / 4, D.k, vec); };
 
   HIP_CHECK(hipMemsetAsync(x.fact, 0, sizeof(int) * W, s));
-  R.go(k_ls_adj_load_n, tn, kl);
+  R.go(mat ? k_lsm_adj_load_n : k_ls_adj_load_n, tn, kl);
   R.go(k_ls_adj_load_m, tm, ka);
   long_rows_of(w.xs);
-  R.go(k_ls_adj_class, G, kc);
+  R.go(mat ? k_lsm_adj_class : k_ls_adj_class, G, kc);
   R.go(k_ls_adj_init, 1, ka);
   R.go(k_lwa_zero, G, D.k);
   D.factor(R);
   R.fetch();
-  const int step = ls_recurrence(R, kLsShared, D.kv, D.kb, p.max_steps, [&]() { D.solve(R); D.long_rows(R, 0); }, [&]() { R.go(k_ls_adj_decide, 1, ka); });
-  R.go(k_ls_adj_unscale, G, ka);
+  const int step = ls_recurrence(R, K, D.kv, D.kb, p.max_steps, [&]() { D.solve(R); D.long_rows(R, 0); }, [&]() { R.go(k_ls_adj_decide, 1, ka); });
+  R.go(mat ? k_lsm_adj_unscale : k_ls_adj_unscale, G, ka);
   long_rows_of(w.x);
-  R.go(k_ls_adj_resm, G, kc);
-  R.go(k_ls_adj_resn, G, ka);
+  R.go(mat ? k_lsm_adj_resm : k_ls_adj_resm, G, kc);
+  R.go(mat ? k_lsm_adj_resn : k_ls_adj_resn, G, ka);
   R.go(k_ls_adj_final, 1, ka);
   ls_adjoint_outputs(R, ka, tn, tm);
   long nfact = 0;
   const float ms = R.finish(x.fact, &nfact);
+  if (mat && p.mat_stat) p.mat_stat[0] = LsRun::ms(R.e0, R.em);
   if (stat) { stat[0] = step; stat[1] = (double)nfact; stat[2] = (double)R.launches; stat[3] = ms; }
   return OSQP_NO_ERROR;
 }

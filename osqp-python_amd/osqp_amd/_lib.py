@@ -173,6 +173,9 @@ PROTOTYPES = {
     'osqp_hip_batch_adjoint_lockstep_direct': (C.c_int, [SolverP, C.c_int] + [c_double_p] * 12),
     'osqp_hip_batch_adjoint_lockstep_direct_device': (C.c_int, [SolverP, C.c_int] + [C.c_void_p] * 13),
     'osqp_hip_lockstep_direct_adjoint_last_record': (C.c_int, [SolverP, c_double_p]),
+    'osqp_hip_batch_adjoint_lockstep_direct_mat': (C.c_int, [SolverP, C.c_int] + [c_double_p] * 14),
+    'osqp_hip_batch_adjoint_lockstep_direct_mat_device': (C.c_int, [SolverP, C.c_int] + [C.c_void_p] * 15),
+    'osqp_hip_lockstep_direct_mat_adjoint_last_record': (C.c_int, [SolverP, c_double_p]),
     'osqp_hip_batch_adjoint': (C.c_int, [SolverP, C.c_int] + [c_double_p] * 14),
     'osqp_hip_batch_adjoint_device': (C.c_int, [SolverP, C.c_int] + [C.c_void_p] * 15),
     'osqp_hip_capabilities': (C.c_int, []),

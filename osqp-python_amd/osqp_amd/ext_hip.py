@@ -635,8 +635,9 @@ class OSQPSolver:
         problem's adjoint system on its own matrices and scaling -- the backward of hip_batch_solve_lockstep(Px=, Ax=) (lockstep_mat_adjoint_last_record)."""
         return self._adjoint_lockstep_host(self._lib.osqp_hip_batch_adjoint_lockstep, x, y, dx, dy, l, u, want, Px, Ax)
 
-    def _adjoint_lockstep_host(self, entry, x, y, dx, dy, l, u, want, Px=None, Ax=None):
-        """The host-array call of a lockstep adjoint route (`entry`: its C entry point): widths checked here, then the engine."""
+    def _adjoint_lockstep_host(self, entry, x, y, dx, dy, l, u, want, Px=None, Ax=None, mat_entry=None):
+        """The host-array call of a lockstep adjoint route (`entry`: its C entry point; `mat_entry`: the one with per-problem matrices, None: the PCG
+        route's): widths checked here, then the engine."""
         if x is None or y is None or dx is None:
             raise ValueError('x, y and dx are required')
         x = np.ascontiguousarray(x, dtype=np.float64)
@@ -657,8 +658,8 @@ class OSQPSolver:
         outs = (_ptr(out['dP'], dp), _ptr(out['dq'], dp), _ptr(out['dA'], dp), _ptr(out['dl'], dp), _ptr(out['du'], dp), _ptr(rec, dp))
         if Px is not None or Ax is not None:
             Px, Ax = rows(Px, 'Px', self.nnz_P), rows(Ax, 'Ax', self.nnz_A)
-            st = self._lib.osqp_hip_batch_adjoint_lockstep_mat(self._p, B, _ptr(Px, dp), _ptr(Ax, dp), _ptr(l, dp), _ptr(u, dp), _ptr(x, dp), _ptr(y, dp),
-                                                               _ptr(dx, dp), _ptr(dy, dp), *outs)
+            st = (mat_entry or self._lib.osqp_hip_batch_adjoint_lockstep_mat)(self._p, B, _ptr(Px, dp), _ptr(Ax, dp), _ptr(l, dp), _ptr(u, dp), _ptr(x, dp), _ptr(y, dp),
+                                                                              _ptr(dx, dp), _ptr(dy, dp), *outs)
         else:
             st = entry(self._p, B, _ptr(l, dp), _ptr(u, dp), _ptr(x, dp), _ptr(y, dp), _ptr(dx, dp), _ptr(dy, dp), *outs)
         if st:
@@ -710,20 +711,44 @@ class OSQPSolver:
             out[k] = int(out[k])
         return out
 
-    def hip_batch_adjoint_lockstep_direct(self, x, y, dx, dy=None, l=None, u=None, want=('dP', 'dq', 'dA', 'dl', 'du')):
+    def hip_batch_adjoint_lockstep_direct(self, x, y, dx, dy=None, l=None, u=None, want=('dP', 'dq', 'dA', 'dl', 'du'), Px=None, Ax=None):
         """hip_batch_adjoint_lockstep for the handles it declines (osqp_hip_batch_adjoint_lockstep_direct): the backward pass of
         hip_batch_solve_lockstep_direct, on the handles that call accepts -- the recurrence's linear solve is the Woodbury formula per problem, S inverted
-        once.  Same arguments, same checks, same returns; every other handle raises ValueError with OSQP_FUNC_NOT_IMPLEMENTED."""
-        return self._adjoint_lockstep_host(self._lib.osqp_hip_batch_adjoint_lockstep_direct, x, y, dx, dy, l, u, want)
+        once.  Same arguments, same checks, same returns; every other handle raises ValueError with OSQP_FUNC_NOT_IMPLEMENTED.
+        Px (B, nnz(triu P)) / Ax (B, nnz(A)): per-problem matrix values in the CSC order given at setup (osqp_hip_batch_adjoint_lockstep_direct_mat): every
+        problem's adjoint system on its own matrices, dense rows and scaling -- the backward of hip_batch_solve_lockstep_direct(Px=, Ax=)
+        (lockstep_direct_mat_adjoint_last_record)."""
+        return self._adjoint_lockstep_host(self._lib.osqp_hip_batch_adjoint_lockstep_direct, x, y, dx, dy, l, u, want, Px, Ax,
+                                           mat_entry=self._lib.osqp_hip_batch_adjoint_lockstep_direct_mat)
 
     def hip_batch_adjoint_lockstep_direct_device(self, nbatch, x_ptr, y_ptr, dx_ptr, dy_ptr=None, l_ptr=None, u_ptr=None,
-                                                 dP_ptr=None, dq_ptr=None, dA_ptr=None, dl_ptr=None, du_ptr=None, rec_ptr=None, stream=None):
+                                                 dP_ptr=None, dq_ptr=None, dA_ptr=None, dl_ptr=None, du_ptr=None, rec_ptr=None, stream=None, Px_ptr=None, Ax_ptr=None):
         """osqp_hip_batch_adjoint_lockstep_direct_device: raw device addresses (int or None) laid out as in hip_batch_adjoint_lockstep; the work goes on
-        `stream` (None: the solver's) and the call returns when the results are there.  nbatch == 0: does the route apply?"""
-        st = self._lib.osqp_hip_batch_adjoint_lockstep_direct_device(self._p, int(nbatch), l_ptr, u_ptr, x_ptr, y_ptr, dx_ptr, dy_ptr,
-                                                                     dP_ptr, dq_ptr, dA_ptr, dl_ptr, du_ptr, rec_ptr, stream)
+        `stream` (None: the solver's) and the call returns when the results are there.  nbatch == 0: does the route apply?
+        Px_ptr / Ax_ptr: per-problem matrix values on the device (osqp_hip_batch_adjoint_lockstep_direct_mat_device)."""
+        if Px_ptr is not None or Ax_ptr is not None:
+            st = self._lib.osqp_hip_batch_adjoint_lockstep_direct_mat_device(self._p, int(nbatch), Px_ptr, Ax_ptr, l_ptr, u_ptr, x_ptr, y_ptr, dx_ptr, dy_ptr,
+                                                                             dP_ptr, dq_ptr, dA_ptr, dl_ptr, du_ptr, rec_ptr, stream)
+        else:
+            st = self._lib.osqp_hip_batch_adjoint_lockstep_direct_device(self._p, int(nbatch), l_ptr, u_ptr, x_ptr, y_ptr, dx_ptr, dy_ptr,
+                                                                         dP_ptr, dq_ptr, dA_ptr, dl_ptr, du_ptr, rec_ptr, stream)
         if st:
             raise self._batch_error(st)
+
+    # OSQP_HIP_LOCKSTEP_DIRECT_MAT_ADJOINT_LAST_REC doubles of osqp_hip_lockstep_direct_mat_adjoint_last_record
+    LOCKSTEP_DIRECT_MAT_ADJOINT_LAST_FIELDS = ('chunks', 'width', 'steps_max', 'inversions', 'kernel_launches', 'gpu_ms', 'matrix_block_bytes', 'prepare_gpu_ms')
+
+    def lockstep_direct_mat_adjoint_last_record(self):
+        """osqp_hip_lockstep_direct_mat_adjoint_last_record as a dict (LOCKSTEP_DIRECT_MAT_ADJOINT_LAST_FIELDS): what the last direct lockstep adjoint
+        call with per-problem matrices of this handle did; zeros before the first."""
+        rec = np.zeros(len(self.LOCKSTEP_DIRECT_MAT_ADJOINT_LAST_FIELDS))
+        st = self._lib.osqp_hip_lockstep_direct_mat_adjoint_last_record(self._p, _ptr(rec, _lib.c_double_p))
+        if st:
+            raise ValueError(str(int(st)))
+        out = dict(zip(self.LOCKSTEP_DIRECT_MAT_ADJOINT_LAST_FIELDS, rec.tolist()))
+        for k in ('chunks', 'width', 'steps_max', 'inversions', 'kernel_launches', 'matrix_block_bytes'):
+            out[k] = int(out[k])
+        return out
 
     # OSQP_HIP_LOCKSTEP_DIRECT_ADJOINT_LAST_REC doubles of osqp_hip_lockstep_direct_adjoint_last_record
     LOCKSTEP_DIRECT_ADJOINT_LAST_FIELDS = ('chunks', 'width', 'steps_max', 'inversions', 'kernel_launches', 'gpu_ms', 'workspace_bytes', 'reserved')

@@ -23,7 +23,7 @@ threads.  Here one persistent engine handle plays that role:
     With ``large_batch='lockstep_direct'`` (one rank) such a forward on a Woodbury handle with a diagonal K0 makes ONE call of the direct route with per-element
     matrices (osqp_hip_batch_solve_lockstep_direct_mat: every element scaled and solved on its own P_val / A_val; ``mat_lockstep_direct_launches`` counts
     them; host and ROCm tensors alike through the host entry); a handle that entry declines goes on to the per-element loop as before.  The backward of such a
-    forward is unchanged -- the per-element loop -- and on a Woodbury handle it still raises NotImplementedError.
+    forward is the per-element loop, which raises NotImplementedError on a Woodbury handle, unless ``large_backward='lockstep_direct'`` (below).
   * ``polishing=True`` (default False: every forward as before) is passed to ``setup``: the handle polishes every solved problem, on whichever route the
     forward takes -- the one-workgroup kernel, the per-element loop, the lockstep route with shared or with per-element matrices (there the polish runs
     on the device inside the one call; ``lockstep_polish_last_record`` of the handle counts attempted / accepted / rejected).  The adjoint classifies the
@@ -47,7 +47,11 @@ loop, as with ``'lockstep'``).  With ``large_backward='lockstep'`` and 2-D P_val
 ONE call of the lockstep adjoint with per-element matrices (``osqp_hip_batch_adjoint_lockstep_mat``: every element's adjoint system on its own matrices
 and scaling; ``adjoint_launches`` rises by 1 and ``mat_lockstep_adjoint_launches`` counts these calls; host tensors through the host entry, ROCm tensors
 zero-copy through the device entry) in place of update(Px, Ax) + the single-handle adjoint per element; a handle that entry declines goes on to the
-per-element loop.  A ``torch.distributed`` job (world size > 1) raises NotImplementedError in backward.  With no input requiring grad,
+per-element loop.  With ``large_backward='lockstep_direct'`` and 2-D P_val and / or A_val the backward is likewise ONE call of the direct lockstep adjoint
+with per-element matrices (``osqp_hip_batch_adjoint_lockstep_direct_mat``: every element's adjoint system on its own matrices, dense rows and scaling by the
+Woodbury formula -- the backward of ``large_batch='lockstep_direct'`` with per-element factor models; ``adjoint_launches`` rises by 1 and
+``mat_lockstep_direct_adjoint_launches`` counts these calls; host tensors through the host entry, ROCm tensors zero-copy through the device entry on torch's
+current stream); a handle the route declines goes on to the per-element loop.  A ``torch.distributed`` job (world size > 1) raises NotImplementedError in backward.  With no input requiring grad,
 forward behaves exactly as before.
 """
 import numpy as np
@@ -97,6 +101,7 @@ class OSQP(Module):
         self.last_rec = None         # per-element record of the last forward that ran on host arrays (ext_hip BATCH_FIELDS where a batch route made it: status_polish is column 8)
         self.mat_lockstep_direct_launches = 0   # calls of the direct lockstep route with per-element matrices made by this layer's forwards (large_batch='lockstep_direct')
         self.mat_lockstep_adjoint_launches = 0   # calls of the lockstep adjoint with per-element matrices made by this layer's backwards (large_backward='lockstep')
+        self.mat_lockstep_direct_adjoint_launches = 0   # calls of the direct lockstep adjoint with per-element matrices made by this layer's backwards (large_backward='lockstep_direct')
 
     # ------------------------------------------------------------------ the persistent handle
     def _matrices(self, P_val, A_val):
@@ -311,7 +316,8 @@ class OSQP(Module):
         """Backward of a shared-matrix batch past the batch adjoint kernel, with large_backward='lockstep' or 'lockstep_direct': one call of the lockstep
         adjoint (or of its direct form) for the whole batch (cuda tensors: zero-copy through the device entry on torch's current stream).  An element whose adjoint system was not solved raises as
         _backward_loop does.  None: this handle is not on the route (the caller goes on to the per-element loop).
-        P_val / A_val (2-D; 'lockstep' only): per-element matrices -- the same one call through osqp_hip_batch_adjoint_lockstep_mat[_device]."""
+        P_val / A_val (2-D): per-element matrices -- the same one call through osqp_hip_batch_adjoint_lockstep_mat[_device] or, with 'lockstep_direct',
+        osqp_hip_batch_adjoint_lockstep_direct_mat[_device]."""
         mat = P_val is not None or A_val is not None
         widths = {'dP': len(self._triu_pick), 'dq': self.n, 'dA': ext.nnz_A, 'dl': self.m, 'du': self.m}
         direct = self.large_backward == 'lockstep_direct'
@@ -342,7 +348,10 @@ class OSQP(Module):
                 raise
             return None
         self.adjoint_launches += 1
-        self.mat_lockstep_adjoint_launches += int(mat)
+        if direct:
+            self.mat_lockstep_direct_adjoint_launches += int(mat)
+        else:
+            self.mat_lockstep_adjoint_launches += int(mat)
         rec = res['rec'].cpu().numpy()
         bad = np.nonzero(rec[:, 0] != 0)[0]
         if bad.size:
@@ -397,7 +406,7 @@ class OSQP(Module):
             res = None
             if self.large_backward in ('lockstep', 'lockstep_direct') and not batched[0] and not batched[2]:
                 res = self._backward_lockstep(s._solver, l_val, u_val, x, y, g, nb, want)      # shared matrices, any size: ONE call (osqp_hip_batch_adjoint_lockstep[_direct])
-            elif self.large_backward == 'lockstep':                                             # per-element matrices, any size: ONE call (osqp_hip_batch_adjoint_lockstep_mat)
+            elif self.large_backward in ('lockstep', 'lockstep_direct'):                        # per-element matrices, any size: ONE call (osqp_hip_batch_adjoint_lockstep[_direct]_mat)
                 res = self._backward_lockstep(s._solver, l_val, u_val, x, y, g, nb, want, P_val if batched[0] else None, A_val if batched[2] else None)
         if res is None:
             # outside the batch kernel (the forward ran _loop): the single-handle adjoint per element
