@@ -112,78 +112,78 @@ OSQPInt osqp_hip_batch_solve_device(OSQPSolver *s, OSQPInt nbatch, const OSQPFlo
 }
 OSQPInt osqp_hip_adjoint_compute_at(OSQPSolver *s, const OSQPFloat *x, const OSQPFloat *y, const OSQPFloat *dx, const OSQPFloat *dy) { return guarded(s, [&](Engine &e) { return e.adjoint_compute_at(x, y, dx, dy); }); }
 OSQPInt osqp_hip_batch_solve_lockstep(OSQPSolver *s, OSQPInt nbatch, const OSQPFloat *q, const OSQPFloat *l, const OSQPFloat *u, OSQPFloat *x, OSQPFloat *y, OSQPFloat *rec, OSQPInt warm) {
-  return guarded(s, [&](Engine &e) { return e.batch_solve_lockstep(nbatch, q, l, u, x, y, rec, warm); });
+  return guarded(s, [&](Engine &e) { return e.solve_lockstep_host(false, nbatch, {q, l, u, x, y, rec, warm}); });
 }
 OSQPInt osqp_hip_batch_solve_lockstep_device(OSQPSolver *s, OSQPInt nbatch, const OSQPFloat *q, const OSQPFloat *l, const OSQPFloat *u, OSQPFloat *x, OSQPFloat *y, OSQPFloat *rec, OSQPInt warm, void *stream) {
-  return guarded(s, [&](Engine &e) { return e.batch_solve_lockstep_device(nbatch, q, l, u, x, y, rec, warm, stream); });
+  return guarded(s, [&](Engine &e) { return e.solve_lockstep_device(false, nbatch, {q, l, u, x, y, rec, warm}, stream); });
 }
-OSQPInt osqp_hip_lockstep_last_record(OSQPSolver *s, OSQPFloat *rec) { return guarded(s, [&](Engine &e) { return e.lockstep_last_record(rec); }); }
-OSQPInt osqp_hip_lockstep_polish_last_record(OSQPSolver *s, OSQPFloat *rec) { return guarded(s, [&](Engine &e) { return e.lockstep_polish_last_record(rec); }); }
+OSQPInt osqp_hip_lockstep_last_record(OSQPSolver *s, OSQPFloat *rec) { return guarded(s, [&](Engine &e) { return e.lockstep_last(Engine::kLsRecSolve, rec); }); }
+OSQPInt osqp_hip_lockstep_polish_last_record(OSQPSolver *s, OSQPFloat *rec) { return guarded(s, [&](Engine &e) { return e.lockstep_last(Engine::kLsRecPolish, rec); }); }
 OSQPInt osqp_hip_batch_solve_lockstep_mat(OSQPSolver *s, OSQPInt nbatch, const OSQPFloat *Px, const OSQPFloat *Ax, const OSQPFloat *q, const OSQPFloat *l, const OSQPFloat *u, OSQPFloat *x, OSQPFloat *y,
                                           OSQPFloat *rec, OSQPInt warm) {
-  return guarded(s, [&](Engine &e) { return e.batch_solve_lockstep_mat(nbatch, Px, Ax, q, l, u, x, y, rec, warm); });
+  return guarded(s, [&](Engine &e) { return e.solve_lockstep_host(false, nbatch, {q, l, u, x, y, rec, warm, true, Px, Ax}); });
 }
 OSQPInt osqp_hip_batch_solve_lockstep_mat_device(OSQPSolver *s, OSQPInt nbatch, const OSQPFloat *Px, const OSQPFloat *Ax, const OSQPFloat *q, const OSQPFloat *l, const OSQPFloat *u, OSQPFloat *x,
                                                  OSQPFloat *y, OSQPFloat *rec, OSQPInt warm, void *stream) {
-  return guarded(s, [&](Engine &e) { return e.batch_solve_lockstep_mat_device(nbatch, Px, Ax, q, l, u, x, y, rec, warm, stream); });
+  return guarded(s, [&](Engine &e) { return e.solve_lockstep_device(false, nbatch, {q, l, u, x, y, rec, warm, true, Px, Ax}, stream); });
 }
-OSQPInt osqp_hip_lockstep_mat_last_record(OSQPSolver *s, OSQPFloat *rec) { return guarded(s, [&](Engine &e) { return e.lockstep_mat_last_record(rec); }); }
+OSQPInt osqp_hip_lockstep_mat_last_record(OSQPSolver *s, OSQPFloat *rec) { return guarded(s, [&](Engine &e) { return e.lockstep_last(Engine::kLsRecMat, rec); }); }
 OSQPInt osqp_hip_lockstep_mat_scaling(OSQPSolver *s, OSQPInt b, OSQPFloat *D, OSQPFloat *E, OSQPFloat *c) { return guarded(s, [&](Engine &e) { return e.lockstep_mat_scaling(b, D, E, c); }); }
 OSQPInt osqp_hip_batch_solve_lockstep_direct(OSQPSolver *s, OSQPInt nbatch, const OSQPFloat *q, const OSQPFloat *l, const OSQPFloat *u, OSQPFloat *x, OSQPFloat *y, OSQPFloat *rec, OSQPInt warm) {
-  return guarded(s, [&](Engine &e) { return e.batch_solve_lockstep_direct(nbatch, q, l, u, x, y, rec, warm); });
+  return guarded(s, [&](Engine &e) { return e.solve_lockstep_host(true, nbatch, {q, l, u, x, y, rec, warm}); });
 }
 OSQPInt osqp_hip_batch_solve_lockstep_direct_device(OSQPSolver *s, OSQPInt nbatch, const OSQPFloat *q, const OSQPFloat *l, const OSQPFloat *u, OSQPFloat *x, OSQPFloat *y, OSQPFloat *rec, OSQPInt warm, void *stream) {
-  return guarded(s, [&](Engine &e) { return e.batch_solve_lockstep_direct_device(nbatch, q, l, u, x, y, rec, warm, stream); });
+  return guarded(s, [&](Engine &e) { return e.solve_lockstep_device(true, nbatch, {q, l, u, x, y, rec, warm}, stream); });
 }
-OSQPInt osqp_hip_lockstep_direct_last_record(OSQPSolver *s, OSQPFloat *rec) { return guarded(s, [&](Engine &e) { return e.lockstep_direct_last_record(rec); }); }
+OSQPInt osqp_hip_lockstep_direct_last_record(OSQPSolver *s, OSQPFloat *rec) { return guarded(s, [&](Engine &e) { return e.lockstep_last(Engine::kLsRecDirect, rec); }); }
 OSQPInt osqp_hip_batch_solve_lockstep_direct_mat(OSQPSolver *s, OSQPInt nbatch, const OSQPFloat *Px, const OSQPFloat *Ax, const OSQPFloat *q, const OSQPFloat *l, const OSQPFloat *u, OSQPFloat *x,
                                                  OSQPFloat *y, OSQPFloat *rec, OSQPInt warm) {
-  return guarded(s, [&](Engine &e) { return e.batch_solve_lockstep_direct_mat(nbatch, Px, Ax, q, l, u, x, y, rec, warm); });
+  return guarded(s, [&](Engine &e) { return e.solve_lockstep_host(true, nbatch, {q, l, u, x, y, rec, warm, true, Px, Ax}); });
 }
 OSQPInt osqp_hip_batch_solve_lockstep_direct_mat_device(OSQPSolver *s, OSQPInt nbatch, const OSQPFloat *Px, const OSQPFloat *Ax, const OSQPFloat *q, const OSQPFloat *l, const OSQPFloat *u,
                                                         OSQPFloat *x, OSQPFloat *y, OSQPFloat *rec, OSQPInt warm, void *stream) {
-  return guarded(s, [&](Engine &e) { return e.batch_solve_lockstep_direct_mat_device(nbatch, Px, Ax, q, l, u, x, y, rec, warm, stream); });
+  return guarded(s, [&](Engine &e) { return e.solve_lockstep_device(true, nbatch, {q, l, u, x, y, rec, warm, true, Px, Ax}, stream); });
 }
-OSQPInt osqp_hip_lockstep_direct_mat_last_record(OSQPSolver *s, OSQPFloat *rec) { return guarded(s, [&](Engine &e) { return e.lockstep_direct_mat_last_record(rec); }); }
+OSQPInt osqp_hip_lockstep_direct_mat_last_record(OSQPSolver *s, OSQPFloat *rec) { return guarded(s, [&](Engine &e) { return e.lockstep_last(Engine::kLsRecDirectMat, rec); }); }
 OSQPInt osqp_hip_batch_adjoint_lockstep(OSQPSolver *s, OSQPInt nbatch, const OSQPFloat *l, const OSQPFloat *u, const OSQPFloat *x, const OSQPFloat *y, const OSQPFloat *dx,
                                         const OSQPFloat *dy, OSQPFloat *dP, OSQPFloat *dq, OSQPFloat *dA, OSQPFloat *dl, OSQPFloat *du, OSQPFloat *arec) {
-  return guarded(s, [&](Engine &e) { return e.batch_adjoint_lockstep(nbatch, l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec); });
+  return guarded(s, [&](Engine &e) { return e.adjoint_lockstep_host(false, nbatch, {l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec}); });
 }
 OSQPInt osqp_hip_batch_adjoint_lockstep_device(OSQPSolver *s, OSQPInt nbatch, const OSQPFloat *l, const OSQPFloat *u, const OSQPFloat *x, const OSQPFloat *y, const OSQPFloat *dx,
                                                const OSQPFloat *dy, OSQPFloat *dP, OSQPFloat *dq, OSQPFloat *dA, OSQPFloat *dl, OSQPFloat *du, OSQPFloat *arec, void *stream) {
-  return guarded(s, [&](Engine &e) { return e.batch_adjoint_lockstep_device(nbatch, l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec, stream); });
+  return guarded(s, [&](Engine &e) { return e.adjoint_lockstep_device(false, nbatch, {l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec}, stream); });
 }
-OSQPInt osqp_hip_lockstep_adjoint_last_record(OSQPSolver *s, OSQPFloat *rec) { return guarded(s, [&](Engine &e) { return e.lockstep_adjoint_last_record(rec); }); }
+OSQPInt osqp_hip_lockstep_adjoint_last_record(OSQPSolver *s, OSQPFloat *rec) { return guarded(s, [&](Engine &e) { return e.lockstep_last(Engine::kLsRecAdjoint, rec); }); }
 OSQPInt osqp_hip_batch_adjoint_lockstep_mat(OSQPSolver *s, OSQPInt nbatch, const OSQPFloat *Px, const OSQPFloat *Ax, const OSQPFloat *l, const OSQPFloat *u, const OSQPFloat *x, const OSQPFloat *y,
                                             const OSQPFloat *dx, const OSQPFloat *dy, OSQPFloat *dP, OSQPFloat *dq, OSQPFloat *dA, OSQPFloat *dl, OSQPFloat *du, OSQPFloat *arec) {
-  return guarded(s, [&](Engine &e) { return e.batch_adjoint_lockstep_mat(nbatch, Px, Ax, l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec); });
+  return guarded(s, [&](Engine &e) { return e.adjoint_lockstep_host(false, nbatch, {l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec, true, Px, Ax}); });
 }
 OSQPInt osqp_hip_batch_adjoint_lockstep_mat_device(OSQPSolver *s, OSQPInt nbatch, const OSQPFloat *Px, const OSQPFloat *Ax, const OSQPFloat *l, const OSQPFloat *u, const OSQPFloat *x,
                                                    const OSQPFloat *y, const OSQPFloat *dx, const OSQPFloat *dy, OSQPFloat *dP, OSQPFloat *dq, OSQPFloat *dA, OSQPFloat *dl, OSQPFloat *du,
                                                    OSQPFloat *arec, void *stream) {
-  return guarded(s, [&](Engine &e) { return e.batch_adjoint_lockstep_mat_device(nbatch, Px, Ax, l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec, stream); });
+  return guarded(s, [&](Engine &e) { return e.adjoint_lockstep_device(false, nbatch, {l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec, true, Px, Ax}, stream); });
 }
-OSQPInt osqp_hip_lockstep_mat_adjoint_last_record(OSQPSolver *s, OSQPFloat *rec) { return guarded(s, [&](Engine &e) { return e.lockstep_mat_adjoint_last_record(rec); }); }
+OSQPInt osqp_hip_lockstep_mat_adjoint_last_record(OSQPSolver *s, OSQPFloat *rec) { return guarded(s, [&](Engine &e) { return e.lockstep_last(Engine::kLsRecMatAdjoint, rec); }); }
 OSQPInt osqp_hip_batch_adjoint_lockstep_direct(OSQPSolver *s, OSQPInt nbatch, const OSQPFloat *l, const OSQPFloat *u, const OSQPFloat *x, const OSQPFloat *y, const OSQPFloat *dx,
                                                const OSQPFloat *dy, OSQPFloat *dP, OSQPFloat *dq, OSQPFloat *dA, OSQPFloat *dl, OSQPFloat *du, OSQPFloat *rec) {
-  return guarded(s, [&](Engine &e) { return e.batch_adjoint_lockstep_direct(nbatch, l, u, x, y, dx, dy, dP, dq, dA, dl, du, rec); });
+  return guarded(s, [&](Engine &e) { return e.adjoint_lockstep_host(true, nbatch, {l, u, x, y, dx, dy, dP, dq, dA, dl, du, rec}); });
 }
 OSQPInt osqp_hip_batch_adjoint_lockstep_direct_device(OSQPSolver *s, OSQPInt nbatch, const OSQPFloat *l, const OSQPFloat *u, const OSQPFloat *x, const OSQPFloat *y, const OSQPFloat *dx,
                                                       const OSQPFloat *dy, OSQPFloat *dP, OSQPFloat *dq, OSQPFloat *dA, OSQPFloat *dl, OSQPFloat *du, OSQPFloat *rec, void *stream) {
-  return guarded(s, [&](Engine &e) { return e.batch_adjoint_lockstep_direct_device(nbatch, l, u, x, y, dx, dy, dP, dq, dA, dl, du, rec, stream); });
+  return guarded(s, [&](Engine &e) { return e.adjoint_lockstep_device(true, nbatch, {l, u, x, y, dx, dy, dP, dq, dA, dl, du, rec}, stream); });
 }
-OSQPInt osqp_hip_lockstep_direct_adjoint_last_record(OSQPSolver *s, OSQPFloat *rec) { return guarded(s, [&](Engine &e) { return e.lockstep_direct_adjoint_last_record(rec); }); }
+OSQPInt osqp_hip_lockstep_direct_adjoint_last_record(OSQPSolver *s, OSQPFloat *rec) { return guarded(s, [&](Engine &e) { return e.lockstep_last(Engine::kLsRecDirectAdjoint, rec); }); }
 OSQPInt osqp_hip_batch_adjoint_lockstep_direct_mat(OSQPSolver *s, OSQPInt nbatch, const OSQPFloat *Px, const OSQPFloat *Ax, const OSQPFloat *l, const OSQPFloat *u, const OSQPFloat *x,
                                                    const OSQPFloat *y, const OSQPFloat *dx, const OSQPFloat *dy, OSQPFloat *dP, OSQPFloat *dq, OSQPFloat *dA, OSQPFloat *dl, OSQPFloat *du,
                                                    OSQPFloat *arec) {
-  return guarded(s, [&](Engine &e) { return e.batch_adjoint_lockstep_direct_mat(nbatch, Px, Ax, l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec); });
+  return guarded(s, [&](Engine &e) { return e.adjoint_lockstep_host(true, nbatch, {l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec, true, Px, Ax}); });
 }
 OSQPInt osqp_hip_batch_adjoint_lockstep_direct_mat_device(OSQPSolver *s, OSQPInt nbatch, const OSQPFloat *Px, const OSQPFloat *Ax, const OSQPFloat *l, const OSQPFloat *u,
                                                           const OSQPFloat *x, const OSQPFloat *y, const OSQPFloat *dx, const OSQPFloat *dy, OSQPFloat *dP, OSQPFloat *dq, OSQPFloat *dA,
                                                           OSQPFloat *dl, OSQPFloat *du, OSQPFloat *arec, void *stream) {
-  return guarded(s, [&](Engine &e) { return e.batch_adjoint_lockstep_direct_mat_device(nbatch, Px, Ax, l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec, stream); });
+  return guarded(s, [&](Engine &e) { return e.adjoint_lockstep_device(true, nbatch, {l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec, true, Px, Ax}, stream); });
 }
-OSQPInt osqp_hip_lockstep_direct_mat_adjoint_last_record(OSQPSolver *s, OSQPFloat *rec) { return guarded(s, [&](Engine &e) { return e.lockstep_direct_mat_adjoint_last_record(rec); }); }
+OSQPInt osqp_hip_lockstep_direct_mat_adjoint_last_record(OSQPSolver *s, OSQPFloat *rec) { return guarded(s, [&](Engine &e) { return e.lockstep_last(Engine::kLsRecDirectMatAdjoint, rec); }); }
 OSQPInt osqp_hip_adjoint_last_record(OSQPSolver *s, OSQPFloat *rec) { return guarded(s, [&](Engine &e) { return e.adjoint_last_record(rec); }); }
 OSQPInt osqp_hip_batch_adjoint(OSQPSolver *s, OSQPInt nbatch, const OSQPFloat *Px, const OSQPFloat *Ax, const OSQPFloat *l, const OSQPFloat *u, const OSQPFloat *x, const OSQPFloat *y,
                                const OSQPFloat *dx, const OSQPFloat *dy, OSQPFloat *dP, OSQPFloat *dq, OSQPFloat *dA, OSQPFloat *dl, OSQPFloat *du, OSQPFloat *arec) {

@@ -484,7 +484,7 @@ struct LockstepParams : BatchSettings {
   // on / off, rho_bar = 1 / delta_eff on the guessed-active rows, at least pol_min_steps = 1 + polish_refine_iter steps of the recurrence, its PCG to
   // ||r|| <= pol_pcg_rel ||rhs|| within pol_cg_max iterations, the polish work block (lockstep_polish_ws_doubles(n, m) doubles, device) and where the
   // chunk's polish statistics go (host, kLsPolStat doubles: problems attempted, accepted, rejected, recurrence steps of the slowest problem, PCG
-  // iterations summed, kernel launches, GPU ms; nullptr: not wanted).  Set by Engine::run_lockstep alone, for the shared and the per-problem-matrix entries alike: the adjoint and direct routes leave polish off.
+  // iterations summed, kernel launches, GPU ms; nullptr: not wanted).  Set by Engine::run_lockstep_solve on the PCG route alone, for the shared and the per-problem-matrix entries alike: the adjoint and direct routes leave polish off.
   int polish = 0, pol_min_steps = 1, pol_cg_max = 0;
   double pol_rho = 0, pol_pcg_rel = 0;
   double *pol_ws = nullptr, *pol_stat = nullptr;
@@ -493,7 +493,7 @@ struct LockstepParams : BatchSettings {
   // (m x kLsW), assembled from the chunk's rows Px / Ax of the caller's [nbatch][nnz(triu P)] / [nbatch][nnz(A)] arrays (the caller's CSC order; nullptr: the
   // handle's raw values for every problem) and equilibrated per problem in front of the transposes in; c and 1 / c are rows of the per-problem scalar
   // state.  pvmap / avmap: caller's position -> the engine's (reordered handle; nullptr: identity).  mat_iters: settings.scaling.  mat_stat (host,
-  // kLsMatStat doubles, nullptr: not wanted): GPU ms and kernel launches of the assembly + equilibration.  Set by Engine::run_lockstep and, for the
+  // kLsMatStat doubles, nullptr: not wanted): GPU ms and kernel launches of the assembly + equilibration.  Set by Engine::run_lockstep_solve and, for the
   // backward pass with per-problem matrices (osqp_hip_batch_adjoint_lockstep_mat), by Engine::run_lockstep_adjoint: lockstep_adjoint_chunk then prepares the
   // chunk's matrices in the same block by the same launches, with the handle's q for every problem (q == nullptr).
   double *mat_ws = nullptr, *mat_stat = nullptr;

@@ -161,17 +161,13 @@ void Engine::free_all() {
   if (d_batch_iters_) { be::dfree(d_, d_batch_iters_); d_batch_iters_ = nullptr; d_batch_iters_n_ = 0; }
   batch_order_.clear();
   if (ckpt_) { be::dfree(d_, ckpt_); ckpt_ = nullptr; }
-  if (lsw_) { be::dfree(d_, lsw_); lsw_ = nullptr; }
+  for (LsRoute &rt : lsr_) {
+    for (double *blk : {rt.ws, rt.mat_ws, rt.adj_ws, rt.adj_buf.buf}) if (blk) be::dfree(d_, blk);
+    rt = LsRoute{};
+  }
   if (lspw_) { be::dfree(d_, lspw_); lspw_ = nullptr; }
-  if (lsmw_) { be::dfree(d_, lsmw_); lsmw_ = nullptr; }
-  lsm_last_count_ = 0; std::fill(lsm_rec_, lsm_rec_ + OSQP_HIP_LOCKSTEP_MAT_LAST_REC, 0.0);
-  if (lsaw_) { be::dfree(d_, lsaw_); lsaw_ = nullptr; }
-  if (lsdw_) { be::dfree(d_, lsdw_); lsdw_ = nullptr; }
-  if (lsdaw_) { be::dfree(d_, lsdaw_); lsdaw_ = nullptr; }
-  if (lsdmw_) { be::dfree(d_, lsdmw_); lsdmw_ = nullptr; }
   if (lsd_wtpos_) { be::dfree(d_, lsd_wtpos_); lsd_wtpos_ = nullptr; }
-  std::fill(lsdm_rec_, lsdm_rec_ + OSQP_HIP_LOCKSTEP_DIRECT_MAT_LAST_REC, 0.0);
-  for (DevScratch *sc : {&lsabuf_, &lsdabuf_}) if (sc->buf) { be::dfree(d_, sc->buf); *sc = DevScratch{}; }
+  lsm_last_count_ = 0; std::fill(&ls_last_[0][0], &ls_last_[0][0] + sizeof(ls_last_) / sizeof(double), 0.0);
   if (lsd_vval_) { be::dfree(d_, lsd_vval_); lsd_vval_ = nullptr; }
   if (lsd_vrp_) { be::dfree(d_, lsd_vrp_); be::dfree(d_, lsd_vcol_); be::dfree(d_, lsd_vsrc_); lsd_vrp_ = lsd_vcol_ = lsd_vsrc_ = nullptr; lsd_nv_ = 0; }
   wb_k0diag_ = false;

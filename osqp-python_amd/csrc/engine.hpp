@@ -60,56 +60,24 @@ class Engine {
   // values for every problem) -- the reference's forward with a P_val / A_val per batch element (nn/torch.py:128-157): still ONE launch
   int batch_solve(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, double *zs_dev = nullptr, const double *Px = nullptr, const double *Ax = nullptr);
   int batch_solve_device(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream, const double *Px = nullptr, const double *Ax = nullptr);
-  // The lockstep route (include/osqp_hip.h osqp_hip_batch_solve_lockstep; lockstep_hip.hip): shared P / A, any size, kLsW problems at a time on block
-  // vectors.  Host arrays, or -- _device -- device arrays and a caller's stream; both return when the results are there.
-  int batch_solve_lockstep(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm);
-  int batch_solve_lockstep_device(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream);
-  int lockstep_last_record(double *rec) const;
-  // The same route with a P_val / A_val per problem (include/osqp_hip.h osqp_hip_batch_solve_lockstep_mat; lockstep_hip.hip "matrices of a chunk"): Px / Ax are
-  // [nbatch][nnz(triu P)] / [nbatch][nnz(A)] in the CSC order given at setup, either may be NULL (the handle's own raw values); polishes as the shared entry does.
-  int batch_solve_lockstep_mat(int nbatch, const double *Px, const double *Ax, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm);
-  int batch_solve_lockstep_mat_device(int nbatch, const double *Px, const double *Ax, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream);
-  int lockstep_mat_last_record(double *rec) const;
-  int lockstep_mat_scaling(int b, double *D, double *E, double *c);
-  int lockstep_polish_last_record(double *rec) const;
-  // The direct lockstep route for a Woodbury handle with a diagonal K0 (include/osqp_hip.h osqp_hip_batch_solve_lockstep_direct; lockstep_hip.hip "lockstep
-  // DIRECT"): the same arguments and semantics; every other handle -- a reordered one included -- gets OSQP_FUNC_NOT_IMPLEMENTED.
-  int batch_solve_lockstep_direct(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm);
-  int batch_solve_lockstep_direct_device(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream);
-  int lockstep_direct_last_record(double *rec) const;
-  // The direct route with a P_val / A_val per problem (include/osqp_hip.h osqp_hip_batch_solve_lockstep_direct_mat; lockstep_hip.hip lockstep_direct_chunk):
-  // Px / Ax as batch_solve_lockstep_mat takes them, on the handles batch_solve_lockstep_direct accepts and the chunk's assembly can serve.  No polish.
-  int batch_solve_lockstep_direct_mat(int nbatch, const double *Px, const double *Ax, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm);
-  int batch_solve_lockstep_direct_mat_device(int nbatch, const double *Px, const double *Ax, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream);
-  int lockstep_direct_mat_last_record(double *rec) const;
-  // The backward pass of such a batch (include/osqp_hip.h osqp_hip_batch_adjoint_lockstep; lockstep_hip.hip lockstep_adjoint_chunk): the adjoint system of
-  // every problem by the recurrence polish runs, on block vectors, in a work block of its own.  Any output may be nullptr.
-  int batch_adjoint_lockstep(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
-                             double *dP, double *dq, double *dA, double *dl, double *du, double *arec);
-  int batch_adjoint_lockstep_device(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
-                                    double *dP, double *dq, double *dA, double *dl, double *du, double *arec, void *stream);
-  int lockstep_adjoint_last_record(double *rec) const;
-  // The backward pass with a P_val / A_val per problem (include/osqp_hip.h osqp_hip_batch_adjoint_lockstep_mat): Px / Ax as batch_solve_lockstep_mat takes
-  // them, the rest as above; serves the handles both that entry and batch_adjoint_lockstep serve.
-  int batch_adjoint_lockstep_mat(int nbatch, const double *Px, const double *Ax, const double *l, const double *u, const double *x, const double *y, const double *dx,
-                                 const double *dy, double *dP, double *dq, double *dA, double *dl, double *du, double *arec);
-  int batch_adjoint_lockstep_mat_device(int nbatch, const double *Px, const double *Ax, const double *l, const double *u, const double *x, const double *y, const double *dx,
-                                        const double *dy, double *dP, double *dq, double *dA, double *dl, double *du, double *arec, void *stream);
-  int lockstep_mat_adjoint_last_record(double *rec) const;
-  // The backward pass of a batch on the direct lockstep route (include/osqp_hip.h osqp_hip_batch_adjoint_lockstep_direct; lockstep_hip.hip
-  // lockstep_direct_adjoint_chunk): the same arguments and semantics on the handles batch_solve_lockstep_direct accepts, OSQP_FUNC_NOT_IMPLEMENTED elsewhere.
-  int batch_adjoint_lockstep_direct(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
-                                    double *dP, double *dq, double *dA, double *dl, double *du, double *arec);
-  int batch_adjoint_lockstep_direct_device(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
-                                           double *dP, double *dq, double *dA, double *dl, double *du, double *arec, void *stream);
-  int lockstep_direct_adjoint_last_record(double *rec) const;
-  // ... with a P_val / A_val per problem (include/osqp_hip.h osqp_hip_batch_adjoint_lockstep_direct_mat): Px / Ax as batch_solve_lockstep_direct_mat takes
-  // them, the rest as above; serves the handles both that entry and batch_adjoint_lockstep_direct serve.
-  int batch_adjoint_lockstep_direct_mat(int nbatch, const double *Px, const double *Ax, const double *l, const double *u, const double *x, const double *y, const double *dx,
-                                        const double *dy, double *dP, double *dq, double *dA, double *dl, double *du, double *arec);
-  int batch_adjoint_lockstep_direct_mat_device(int nbatch, const double *Px, const double *Ax, const double *l, const double *u, const double *x, const double *y, const double *dx,
-                                               const double *dy, double *dP, double *dq, double *dA, double *dl, double *du, double *arec, void *stream);
-  int lockstep_direct_mat_adjoint_last_record(double *rec) const;
+  // The lockstep family (lockstep_hip.hip; include/osqp_hip.h documents every entry point, its arguments and its record).  Four axes:
+  //   route      direct = false: block-vector PCG, any handle lockstep_applies() takes; true: the Woodbury formula per problem, a handle in the small
+  //              Woodbury mode with a diagonal K0 (lockstep_direct_applies()).  Every other handle gets OSQP_FUNC_NOT_IMPLEMENTED;
+  //   matrices   mat = false: the handle's P / A for every problem; true: Px / Ax are [nbatch][nnz(triu P)] / [nbatch][nnz(A)] in the CSC order given at
+  //              setup, either may be nullptr (the handle's own raw values), on the handles mat_assembly_applies() also takes;
+  //   direction  solve (LockstepSolveIO; the PCG route polishes with settings.polishing) or adjoint (LockstepAdjointIO; any output may be nullptr);
+  //   arrays     _host: host arrays, staged through a device scratch block; _device: device arrays and a caller's stream, nbatch == 0 asks whether the
+  //              route applies.  Both return when the results are there.
+  // Every call leaves what it did in the records of its kind (LsRec, read by lockstep_last): its route's base record and, with mat, the mat record too.
+  struct LockstepSolveIO { const double *q, *l, *u; double *x, *y, *rec; int warm; bool mat = false; const double *Px = nullptr, *Ax = nullptr; };
+  struct LockstepAdjointIO { const double *l, *u, *x, *y, *dx, *dy; double *dP, *dq, *dA, *dl, *du, *arec; bool mat = false; const double *Px = nullptr, *Ax = nullptr; };
+  enum LsRec { kLsRecSolve, kLsRecPolish, kLsRecMat, kLsRecDirect, kLsRecDirectMat, kLsRecAdjoint, kLsRecMatAdjoint, kLsRecDirectAdjoint, kLsRecDirectMatAdjoint, kLsRecCount };      // one per public *_last_record
+  int solve_lockstep_host(bool direct, int nbatch, const LockstepSolveIO &h);
+  int solve_lockstep_device(bool direct, int nbatch, const LockstepSolveIO &a, void *stream);
+  int adjoint_lockstep_host(bool direct, int nbatch, const LockstepAdjointIO &h);
+  int adjoint_lockstep_device(bool direct, int nbatch, const LockstepAdjointIO &a, void *stream);
+  int lockstep_last(LsRec which, double *rec) const;
+  int lockstep_mat_scaling(int b, double *D, double *E, double *c);      // D, E, c of problem b of the last chunk of the last PCG-route solve with mat
   // Adjoint derivatives (include/osqp_hip.h osqp_hip_batch_adjoint; batch_hip.hip k_batch_adjoint): one launch for the batch.  Host arrays, or -- _device --
   // device arrays and a caller's stream with the semantics of batch_solve_device.  Px / Ax / l / u: nullptr = this solver's own values for every problem.
   int batch_adjoint(int nbatch, const double *Px, const double *Ax, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
@@ -174,63 +142,45 @@ class Engine {
   std::map<std::pair<int, int>, void *> graphs_;
   double *bbuf_ = nullptr; size_t bbuf_cap_ = 0;      // device scratch of batch_solve, kept across calls
   double *bmat_ = nullptr; size_t bmat_cap_ = 0;      // per-problem matrices: scaled values, equilibration and products of every problem (BatchParams::Aval_b ..), kept across calls
-  double *lsw_ = nullptr;                             // workspace of one lockstep chunk (lockstep_ws_doubles(n, m)), allocated on first use
-  double ls_rec_[OSQP_HIP_LOCKSTEP_LAST_REC] = {0, 0, 0, 0, 0, 0, 0, 0};      // record of the last lockstep call (osqp_hip_lockstep_last_record)
-  double *lspw_ = nullptr;                            // polish work block of one lockstep chunk (lockstep_polish_ws_doubles(n, m)), allocated by the first polishing call
-  double ls_pol_rec_[OSQP_HIP_LOCKSTEP_POLISH_LAST_REC] = {0, 0, 0, 0, 0, 0, 0, 0};      // polish record of the last lockstep call (osqp_hip_lockstep_polish_last_record)
-  // mat: the per-problem-matrix entries (Px / Ax device arrays in the caller's CSC order, either may be nullptr); the shared entries leave it false
-  int run_lockstep(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream,
-                   bool mat = false, const double *Px = nullptr, const double *Ax = nullptr);
-  void fill_lockstep_handle(LockstepParams &p);       // the handle's matrices, scalings, shared vectors and permutations: every lockstep route
-  int last_record(const double *src, int cnt, double *rec) const;      // behind every *_last_record
-  double *lsmw_ = nullptr;                            // matrix block of one lockstep chunk (lockstep_mat_ws_doubles), allocated by the first call with per-problem matrices
-  double lsm_rec_[OSQP_HIP_LOCKSTEP_MAT_LAST_REC] = {0, 0, 0, 0, 0, 0, 0, 0};      // record of the last such call (osqp_hip_lockstep_mat_last_record)
-  int lsm_last_count_ = 0;                            // problems of the last chunk that call processed (0: no call yet): what lockstep_mat_scaling reads
-  bool lockstep_mat_applies();
-  bool mat_assembly_applies();                        // what a chunk's own assembly needs of a handle, on either lockstep route
-  // direct lockstep route: the structural decision of prepare_wb (K0 diagonal, small mode -- not DevWb::exact, which a failed inversion clears), the
-  // chunk's workspace (lockstep_direct_ws_doubles(n, m, r)) and the view of A (LockstepDirectView::Av), both built on first use, the last call's record
-  bool wb_k0diag_ = false;
-  double *lsdw_ = nullptr, *lsd_vval_ = nullptr;
-  int *lsd_vrp_ = nullptr, *lsd_vcol_ = nullptr, *lsd_vsrc_ = nullptr; int lsd_nv_ = 0;
-  double lsd_rec_[OSQP_HIP_LOCKSTEP_DIRECT_LAST_REC] = {0, 0, 0, 0, 0, 0, 0, 0};
-  bool lockstep_direct_applies();
-  int prepare_lockstep_direct_view();                 // builds the view of A on first use (both directions of the direct route read it)
-  int fill_lockstep_direct_view(LockstepDirectView &v, void *stream);      // ... and fills a chunk's view from it, values refreshed
-  int run_lockstep_direct(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream,
-                          bool mat = false, const double *Px = nullptr, const double *Ax = nullptr);
-  // ... with per-problem matrices: the block of one such chunk (lockstep_direct_mat_ws_doubles), allocated by the first such call, the position map of the
-  // dense rows (LockstepDirectView::wtpos), built once per handle, and the record of the last such call (osqp_hip_lockstep_direct_mat_last_record)
-  double *lsdmw_ = nullptr; int *lsd_wtpos_ = nullptr;
-  double lsdm_rec_[OSQP_HIP_LOCKSTEP_DIRECT_MAT_LAST_REC] = {0, 0, 0, 0, 0, 0, 0, 0};
-  bool lockstep_direct_mat_applies();
-  void prepare_lockstep_direct_wtpos();
-  double *lsaw_ = nullptr;                            // work block of one lockstep adjoint chunk (lockstep_adjoint_ws_doubles(n, m)), allocated on first use
+  // The lockstep routes' state.  Each route (index: direct) has its own blocks, allocated on first use and freed with the handle -- a handle's Woodbury
+  // state can change over its life, so nothing is shared across routes: ws, the workspace of one solve chunk (lockstep_ws_doubles(n, m) /
+  // lockstep_direct_ws_doubles(n, m, r)); mat_ws, the matrix block of a chunk with per-problem matrices, solve or adjoint (lockstep_mat_ws_doubles /
+  // lockstep_direct_mat_ws_doubles, which also holds the chunk's own dense rows and view values); adj_ws, the work block of one adjoint chunk
+  // (lockstep_adjoint_ws_doubles / lockstep_direct_adjoint_ws_doubles); adj_buf, the device scratch of the adjoint's host-array entry, kept across calls.
   struct DevScratch { double *buf = nullptr; size_t cap = 0; };
-  DevScratch lsabuf_, lsdabuf_;                       // device scratch of batch_adjoint_lockstep / _direct (host-array entry points), kept across calls
+  struct LsRoute { double *ws = nullptr, *mat_ws = nullptr, *adj_ws = nullptr; DevScratch adj_buf; } lsr_[2];
+  double *lspw_ = nullptr;                            // polish work block of one PCG-route chunk (lockstep_polish_ws_doubles(n, m)), allocated by the first polishing call
+  double ls_last_[kLsRecCount][8] = {};               // what lockstep_last reads: the record of the last call of each kind, zeros before the first
+  int lsm_last_count_ = 0;                            // problems of the last chunk the last PCG-route solve with mat processed (0: none, or the block was overwritten since): what lockstep_mat_scaling reads
   int *d_pvmap_ = nullptr, *d_avmap_ = nullptr;       // device copies of PvalMap_ / AvalMap_ (reordered handle), uploaded by the first call that reads them
   bool ensure_value_maps();
-  double lsa_rec_[OSQP_HIP_LOCKSTEP_ADJOINT_LAST_REC] = {0, 0, 0, 0, 0, 0, 0, 0};     // record of the last lockstep adjoint call (osqp_hip_lockstep_adjoint_last_record)
+  void fill_lockstep_handle(LockstepParams &p);       // the handle's matrices, scalings, shared vectors and permutations: every lockstep route
+  int last_record(const double *src, int cnt, double *rec) const;      // behind every *_last_record
+  // direct route: the structural decision of prepare_wb (K0 diagonal, small mode -- not DevWb::exact, which a failed inversion clears), the view of A
+  // (LockstepDirectView::Av) both directions read, built on first use, and -- with mat -- the position map of the dense rows (LockstepDirectView::wtpos)
+  bool wb_k0diag_ = false;
+  double *lsd_vval_ = nullptr;
+  int *lsd_vrp_ = nullptr, *lsd_vcol_ = nullptr, *lsd_vsrc_ = nullptr, *lsd_wtpos_ = nullptr; int lsd_nv_ = 0;
+  int prepare_lockstep_direct_view();
+  int fill_lockstep_direct_view(LockstepDirectView &v, void *stream);      // ... and fills a chunk's view from it, values refreshed
+  void prepare_lockstep_direct_wtpos();
+  // which handles a route takes: solve by (direct, mat) -- solve_applies picks among the four --, the adjoint needs its own predicate as well
+  bool lockstep_applies();
+  bool mat_assembly_applies();                        // what a chunk's own assembly needs of a handle, on either route
+  bool lockstep_mat_applies();
+  bool lockstep_direct_applies();
+  bool lockstep_direct_mat_applies();
   bool lockstep_adjoint_applies();
-  // the arrays of a backward pass (host or device, as the entry says); one body per entry kind and one chunk loop serve both routes (direct: the
-  // direct route's applicability, work block, chunk function and record).  mat: the entries with per-problem matrices (Px / Ax in the
-  // caller's CSC order, either may be nullptr) -- the matrix block is the forward's of that route (lsmw_ / lsdmw_), the record lsma_rec_ / lsdma_rec_ next to
-  // lsa_rec_ / lsda_rec_.
-  struct LockstepAdjointIO { const double *l, *u, *x, *y, *dx, *dy; double *dP, *dq, *dA, *dl, *du, *arec; bool mat = false; const double *Px = nullptr, *Ax = nullptr; };
-  double lsma_rec_[OSQP_HIP_LOCKSTEP_MAT_ADJOINT_LAST_REC] = {0, 0, 0, 0, 0, 0, 0, 0};     // record of the last such call (osqp_hip_lockstep_mat_adjoint_last_record)
-  int adjoint_lockstep_host(bool direct, int nbatch, const LockstepAdjointIO &h);
-  int adjoint_lockstep_device(bool direct, int nbatch, const LockstepAdjointIO &a, void *stream);
-  int run_lockstep_adjoint(bool direct, int nbatch, const LockstepAdjointIO &a, void *stream);
-  // the backward pass on the direct route: its own work block (lockstep_direct_adjoint_ws_doubles(n, m, r)) and record
-  double *lsdaw_ = nullptr;
-  double lsda_rec_[OSQP_HIP_LOCKSTEP_DIRECT_ADJOINT_LAST_REC] = {0, 0, 0, 0, 0, 0, 0, 0};
-  double lsdma_rec_[OSQP_HIP_LOCKSTEP_DIRECT_MAT_ADJOINT_LAST_REC] = {0, 0, 0, 0, 0, 0, 0, 0};     // record of the last such call with per-problem matrices (osqp_hip_lockstep_direct_mat_adjoint_last_record)
   bool lockstep_direct_adjoint_applies();
+  using Applies = bool (Engine::*)();
+  static Applies solve_applies(bool direct, bool mat);
+  // one chunk loop per direction serves both routes: direct selects the blocks, the chunk function and the records
+  int run_lockstep_solve(bool direct, int nbatch, const LockstepSolveIO &a, void *stream);
+  int run_lockstep_adjoint(bool direct, int nbatch, const LockstepAdjointIO &a, void *stream);
   // what the four batch entry points begin with, and the host staging of the two that take host arrays (engine_api.cpp)
   bool batch_applies();                               // the workgroup route: the QP fits one workgroup's LDS and the handle is not reordered
   bool batch_applies_prepared();
-  bool lockstep_applies();
-  int batch_enter(int nbatch, bool query, const double *x, const double *y, const double *rec, bool (Engine::*applies)());
+  int batch_enter(int nbatch, bool query, const double *x, const double *y, const double *rec, Applies applies);
   struct BatchStage;
   double *abuf_ = nullptr; size_t abuf_cap_ = 0;      // device scratch of batch_adjoint (host-array entry point), kept across calls
   bool adjoint_applicable();                          // the problem fits k_batch_adjoint (the forward's direct variant + the adjoint's own LDS)

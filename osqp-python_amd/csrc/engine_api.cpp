@@ -773,7 +773,7 @@ bool Engine::lockstep_applies() { return be::lockstep_chunk && be::device_vec_up
 // depends on the handle alone, so every rank of a job reaches the same decision before its first collective (osqp_amd/sharded.py).
 // Returns kBatchEnter to go on, else what the entry point returns.
 constexpr int kBatchEnter = -1;
-int Engine::batch_enter(int nbatch, bool query, const double *x, const double *y, const double *rec, bool (Engine::*applies)()) {
+int Engine::batch_enter(int nbatch, bool query, const double *x, const double *y, const double *rec, Applies applies) {
   if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   if (query && nbatch == 0) return (this->*applies)() ? OSQP_NO_ERROR : OSQP_FUNC_NOT_IMPLEMENTED;
   if (nbatch <= 0 || !x || !y || !rec) return OSQP_DATA_VALIDATION_ERROR;
@@ -783,16 +783,16 @@ int Engine::batch_enter(int nbatch, bool query, const double *x, const double *y
   return kBatchEnter;
 }
 
-// Host staging of a batch given as host arrays (batch_solve, batch_solve_lockstep).  in: batch_enter, l <= u for every member, the device scratch
+// Host staging of a batch given as host arrays (batch_solve, solve_lockstep_host).  in: batch_enter, l <= u for every member, the device scratch
 // block bbuf_ = [q | l | u | x | y | rec | tail] (kept for the next call), the uploads; out: the downloads.  What the two routes do differently:
 //   own_row   where row i of the caller's numbering sits in l0_ / u0_, the host copies of the handle's own bounds (nullptr: at i).  The lockstep route
 //             passes ipr_ on a reordered handle -- the copies are kept in the engine's numbering; the workgroup route refuses reordered handles;
 //   wg        the workgroup route appends [q0 | l0 | u0 | Px | Ax]: the handle's own vectors for the arguments given as NULL, uploaded where they
 //             are not resident (!be::device_vec_updates(); dq0 .. du0 point at the resident ones otherwise), and the per-problem matrix values.  The
-//             lockstep route reads d_.qraw .. itself; its per-problem matrix values (batch_solve_lockstep_mat) follow the records directly.
+//             lockstep route reads d_.qraw .. itself; its per-problem matrix values (LockstepSolveIO::mat) follow the records directly.
 struct Engine::BatchStage {
   Engine &e; int nbatch;
-  bool (Engine::*applies)();                          // the route
+  Applies applies;                                    // the route
   const int *own_row; bool wg;
   size_t N = 0, M = 0;
   double *dq = nullptr, *dl = nullptr, *du = nullptr, *dx = nullptr, *dy = nullptr, *drec = nullptr, *dq0 = nullptr, *dl0 = nullptr, *du0 = nullptr, *dPx = nullptr, *dAx = nullptr;
@@ -900,10 +900,16 @@ int Engine::batch_solve_device(int nbatch, const double *q, const double *l, con
   return err;
 }
 
-// ------------------------------------------------------------------------------------------------ lockstep route
-// Chunks of kLsW problems, one after the other, each from its transposes in to its transposes out (be::lockstep_chunk).  q / l / u / x / y / rec are
-// DEVICE arrays in the caller's numbering; the settings are read once, in front of the first chunk.  The handle's iterates are not touched: the route
-// has its own workspace (lsw_, allocated on first use, freed with the handle) and, with polishing, its own polish work block (lspw_, likewise).
+// ------------------------------------------------------------------------------------------------ lockstep routes
+// Chunks of kLsW problems, one after the other, each from its transposes in to its transposes out.  The axes (engine.hpp): the route -- PCG on block
+// vectors (be::lockstep_chunk), or direct: the Woodbury formula per problem in its place (lockstep_hip.hip "lockstep DIRECT") --, shared or per-problem
+// matrices, solve or adjoint, host or device arrays.  One chunk loop per direction (run_lockstep_solve, run_lockstep_adjoint) and one body per kind of
+// arrays serve every entry point.  The handle's iterates, rho, info, solution, graphs and history are not touched: each route has its own blocks (lsr_).
+static_assert(OSQP_HIP_LOCKSTEP_LAST_REC == 8 && OSQP_HIP_LOCKSTEP_POLISH_LAST_REC == 8 && OSQP_HIP_LOCKSTEP_MAT_LAST_REC == 8 && OSQP_HIP_LOCKSTEP_DIRECT_LAST_REC == 8 &&
+              OSQP_HIP_LOCKSTEP_DIRECT_MAT_LAST_REC == 8 && OSQP_HIP_LOCKSTEP_ADJOINT_LAST_REC == 8 && OSQP_HIP_LOCKSTEP_MAT_ADJOINT_LAST_REC == 8 &&
+              OSQP_HIP_LOCKSTEP_DIRECT_ADJOINT_LAST_REC == 8 && OSQP_HIP_LOCKSTEP_DIRECT_MAT_ADJOINT_LAST_REC == 8, "one table (Engine::ls_last_) and one record text for every lockstep record");
+constexpr int kLsRecLen = 8;
+
 // what every lockstep route takes from the handle: the matrices, the scalings, the shared vectors, the permutations of a reordered handle
 void Engine::fill_lockstep_handle(LockstepParams &p) {
   p.n = n; p.m = m; p.A = d_.A; p.B = d_.B; p.D = d_.D; p.Dinv = d_.Dinv; p.E = d_.E; p.Einv = d_.Einv;
@@ -923,80 +929,17 @@ int Engine::last_record(const double *src, int cnt, double *rec) const {
   std::copy(src, src + cnt, rec);
   return OSQP_NO_ERROR;
 }
-int Engine::lockstep_last_record(double *rec) const { return last_record(ls_rec_, OSQP_HIP_LOCKSTEP_LAST_REC, rec); }
-int Engine::lockstep_polish_last_record(double *rec) const { return last_record(ls_pol_rec_, OSQP_HIP_LOCKSTEP_POLISH_LAST_REC, rec); }
-int Engine::lockstep_mat_last_record(double *rec) const { return last_record(lsm_rec_, OSQP_HIP_LOCKSTEP_MAT_LAST_REC, rec); }
-int Engine::lockstep_direct_last_record(double *rec) const { return last_record(lsd_rec_, OSQP_HIP_LOCKSTEP_DIRECT_LAST_REC, rec); }
-int Engine::lockstep_direct_mat_last_record(double *rec) const { return last_record(lsdm_rec_, OSQP_HIP_LOCKSTEP_DIRECT_MAT_LAST_REC, rec); }
-int Engine::lockstep_adjoint_last_record(double *rec) const { return last_record(lsa_rec_, OSQP_HIP_LOCKSTEP_ADJOINT_LAST_REC, rec); }
-int Engine::lockstep_mat_adjoint_last_record(double *rec) const { return last_record(lsma_rec_, OSQP_HIP_LOCKSTEP_MAT_ADJOINT_LAST_REC, rec); }
-int Engine::lockstep_direct_adjoint_last_record(double *rec) const { return last_record(lsda_rec_, OSQP_HIP_LOCKSTEP_DIRECT_ADJOINT_LAST_REC, rec); }
-int Engine::lockstep_direct_mat_adjoint_last_record(double *rec) const { return last_record(lsdma_rec_, OSQP_HIP_LOCKSTEP_DIRECT_MAT_ADJOINT_LAST_REC, rec); }
+int Engine::lockstep_last(LsRec which, double *rec) const { return last_record(ls_last_[which], kLsRecLen, rec); }
 
-int Engine::run_lockstep(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream,
-                         bool mat, const double *Px, const double *Ax) {
-  const size_t need = lockstep_ws_doubles(n, m);
-  if (!lsw_) { lsw_ = dev_vec<double>(d_, need); be::sync(d_); }
-  // per-problem matrices: the matrix block (allocated by the first such call) and, on a reordered handle, the value maps
-  const int nzP = d_.nzP, nzA = d_.nzA;
-  const size_t mneed = lockstep_mat_ws_doubles(n, m, d_.A.nnz, d_.B.nnz);
-  if (mat) {
-    bool fresh = ensure_value_maps();
-    if (!lsmw_) { lsmw_ = dev_vec<double>(d_, mneed); fresh = true; }
-    if (fresh) be::sync(d_);
-  }
-  LockstepParams p;
-  fill_batch_settings(p, warm);                       // the settings snapshot of the batch path
-  fill_lockstep_handle(p);
-  p.ws = lsw_;
-  // polish (settings.polishing): the recurrence of Engine::run_recurrence as Engine::polish calls it, per problem on block vectors -- rho_bar = 1 / delta_eff,
-  // at least 1 + polish_refine_iter steps, the inner systems to polish_pcg_tol within kMaxCg iterations.  Its work block is allocated by the first such call.
-  double pst[kLsPolStat] = {0, 0, 0, 0, 0, 0, 0}, ptot[kLsPolStat] = {0, 0, 0, 0, 0, 0, 0};
-  const size_t pneed = lockstep_polish_ws_doubles(n, m);
-  double mst[kLsMatStat] = {0, 0}, mtot[kLsMatStat] = {0, 0};
-  if (mat) {
-    p.mat_ws = lsmw_; p.mat_stat = mst; p.mat_iters = std::max(0, (int)settings.scaling);
-    p.pvmap = reordered_ ? d_pvmap_ : nullptr; p.avmap = reordered_ ? d_avmap_ : nullptr;
-  }
-  if (settings.polishing) {                           // (with per-problem matrices too: the chunk polishes on its own matrix block)
-    if (!lspw_) { lspw_ = dev_vec<double>(d_, pneed); be::sync(d_); }
-    const double de = std::max(settings.delta, pol_.polish_delta_floor);
-    p.polish = 1; p.pol_rho = clamp_rho(1.0 / de); p.pol_min_steps = 1 + std::max(0, (int)settings.polish_refine_iter);
-    p.pol_cg_max = kMaxCg; p.pol_pcg_rel = pol_.polish_pcg_tol; p.pol_ws = lspw_; p.pol_stat = pst;
-  }
-  const double t0 = now_s(), limit = settings.time_limit > 0 && settings.time_limit < 1e9 ? settings.time_limit : 0.0;
-  double tot[4] = {0, 0, 0, 0};
-  int chunks = 0;
-  std::fill(ls_pol_rec_, ls_pol_rec_ + OSQP_HIP_LOCKSTEP_POLISH_LAST_REC, 0.0);
-  for (int b0 = 0; b0 < nbatch; b0 += kLsW, chunks++) {
-    p.count = std::min(kLsW, nbatch - b0);
-    p.q = q ? q + (size_t)b0 * n : nullptr; p.l = l ? l + (size_t)b0 * m : nullptr; p.u = u ? u + (size_t)b0 * m : nullptr;
-    p.x = x + (size_t)b0 * n; p.y = y + (size_t)b0 * m; p.rec = rec + (size_t)b0 * kBatchRec;
-    p.Px = (mat && Px) ? Px + (size_t)b0 * nzP : nullptr; p.Ax = (mat && Ax) ? Ax + (size_t)b0 * nzA : nullptr;
-    p.time_limit = limit > 0 ? std::max(limit - (now_s() - t0), 1e-9) : 0.0;
-    double st[4] = {0, 0, 0, 0};
-    std::fill(pst, pst + kLsPolStat, 0.0);
-    if (mat) lsm_last_count_ = 0;                     // (the block is being overwritten)
-    const int err = be::lockstep_chunk(d_, p, stream, st);
-    if (err) return err;
-    if (mat) { lsm_last_count_ = p.count; mtot[0] += mst[0]; mtot[1] += mst[1]; }
-    tot[0] = std::max(tot[0], st[0]); tot[1] += st[1]; tot[2] += st[2]; tot[3] += st[3];
-    for (int k = 0; k < kLsPolStat; k++) ptot[k] = k == 3 ? std::max(ptot[k], pst[k]) : ptot[k] + pst[k];
-  }
-  const double r[OSQP_HIP_LOCKSTEP_LAST_REC] = {(double)chunks, (double)kLsW, tot[0], tot[1], tot[2], tot[3], (double)(need * sizeof(double)), 0.0};
-  std::copy(r, r + OSQP_HIP_LOCKSTEP_LAST_REC, ls_rec_);
-  std::copy(ptot, ptot + kLsPolStat, ls_pol_rec_);
-  ls_pol_rec_[kLsPolStat] = settings.polishing ? (double)(pneed * sizeof(double)) : 0.0;
-  if (mat) {
-    const double rm[OSQP_HIP_LOCKSTEP_MAT_LAST_REC] = {(double)chunks, (double)kLsW, tot[0], tot[1], tot[2], tot[3], (double)(mneed * sizeof(double)), mtot[0]};
-    std::copy(rm, rm + OSQP_HIP_LOCKSTEP_MAT_LAST_REC, lsm_rec_);
-  }
-  return OSQP_NO_ERROR;
+// ---- which handles the routes take
+// The direct route: a handle in the small Woodbury mode whose K0 setup found structurally diagonal (prepare_wb: wb_k0diag_), as numbered by the caller: a
+// reordered handle declines.
+bool Engine::lockstep_direct_applies() {
+  return be::lockstep_direct_chunk && be::lockstep_direct_values && be::device_vec_updates() && d_.wb.on && !d_.wb.large && d_.wb.r >= 1 && d_.wb.r <= kWbMaxRows && wb_k0diag_ && !reordered_;
 }
-
-// ---- per-problem matrices on the lockstep route (include/osqp_hip.h osqp_hip_batch_solve_lockstep_mat)
-// What lockstep_applies() declines, a handle without device assembly and a handle whose stored upper triangle of P holds a repeated (j, j) entry (the
-// single-handle assembly sums those with a floating-point atomic; the chunk's assembly has one writer per entry) are declined.
+// Per-problem matrices, on either route (include/osqp_hip.h osqp_hip_batch_solve_lockstep_mat): a handle without device assembly and a handle whose stored
+// upper triangle of P holds a repeated (j, j) entry (the single-handle assembly sums those with a floating-point atomic; the chunk's assembly has one
+// writer per entry) are declined.
 bool Engine::mat_assembly_applies() {
   if (!be::device_assembly() || !d_.Praw || !d_.Araw) return false;
   for (int j = 0; j < n; j++) {
@@ -1007,70 +950,15 @@ bool Engine::mat_assembly_applies() {
   return true;
 }
 bool Engine::lockstep_mat_applies() { return lockstep_applies() && mat_assembly_applies(); }
-
-int Engine::batch_solve_lockstep_mat(int nbatch, const double *Px, const double *Ax, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm) {
-  BatchStage s{*this, nbatch, &Engine::lockstep_mat_applies, /*own_row=*/reordered_ ? ipr_.data() : nullptr, /*wg=*/false};
-  if (const int err = s.in(q, l, u, x, y, rec, warm, Px, Ax)) return err;
-  const int err = run_lockstep(nbatch, q ? s.dq : nullptr, l ? s.dl : nullptr, u ? s.du : nullptr, s.dx, s.dy, s.drec, warm, nullptr, true, Px ? s.dPx : nullptr, Ax ? s.dAx : nullptr);
-  if (!err) s.out(x, y, rec);
-  return err;
+bool Engine::lockstep_direct_mat_applies() { return lockstep_direct_applies() && mat_assembly_applies(); }
+bool Engine::lockstep_adjoint_applies() { return be::lockstep_adjoint_chunk && be::device_assembly() && be::device_vec_updates() && !d_.wb.on; }
+bool Engine::lockstep_direct_adjoint_applies() { return lockstep_direct_applies() && be::lockstep_direct_adjoint_chunk && be::device_assembly(); }
+Engine::Applies Engine::solve_applies(bool direct, bool mat) {
+  static constexpr Applies table[2][2] = {{&Engine::lockstep_applies, &Engine::lockstep_mat_applies}, {&Engine::lockstep_direct_applies, &Engine::lockstep_direct_mat_applies}};
+  return table[direct][mat];
 }
 
-int Engine::batch_solve_lockstep_mat_device(int nbatch, const double *Px, const double *Ax, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream) {
-  const int enter = batch_enter(nbatch, true, x, y, rec, &Engine::lockstep_mat_applies);
-  if (enter != kBatchEnter) return enter;
-  be::sync(d_);                                     // the solver's own stream first: pending updates of the resident q / l / u, the raw matrix values
-  return run_lockstep(nbatch, q, l, u, x, y, rec, warm, stream, true, Px, Ax);
-}
-
-// D, E, c of problem b of the last chunk the last call with per-problem matrices processed, in the caller's numbering: read back from the matrix block
-// and the chunk's scalar state (row kLsMatScalC), where lockstep_layout.h's carves put them
-int Engine::lockstep_mat_scaling(int b, double *D, double *E, double *c) {
-  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  if (!D || (m > 0 && !E) || !c) return OSQP_DATA_VALIDATION_ERROR;
-  if (!lsmw_ || !lsw_ || b < 0 || b >= lsm_last_count_) return OSQP_DATA_NOT_INITIALIZED;
-  be::activate(d_);
-  be::ext_wait(d_);
-  const size_t nW = (size_t)n * kLsW, mW = (size_t)m * kLsW;
-  LsCursor cm{lsmw_};
-  LsMatVecs t;
-  lockstep_carve_mat(cm, t, n, m, d_.A.nnz, d_.B.nnz);
-  const double *dD = t.D, *dE = t.E;
-  std::vector<double> h(std::max(nW, mW));
-  be::d2h(d_, h.data(), dD, sizeof(double) * nW);
-  for (int j = 0; j < n; j++) D[reordered_ ? pc_[j] : j] = h[(size_t)j * kLsW + b];
-  if (m > 0) {
-    be::d2h(d_, h.data(), dE, sizeof(double) * mW);
-    for (int i = 0; i < m; i++) E[reordered_ ? pr_[i] : i] = h[(size_t)i * kLsW + b];
-  }
-  double cs[kLsW];
-  be::d2h(d_, cs, lsw_ + lockstep_sc_offset(n, m) + (size_t)kLsMatScalC * kLsW, sizeof(cs));
-  *c = cs[b];
-  return OSQP_NO_ERROR;
-}
-
-int Engine::batch_solve_lockstep(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm) {
-  BatchStage s{*this, nbatch, &Engine::lockstep_applies, /*own_row=*/reordered_ ? ipr_.data() : nullptr, /*wg=*/false};
-  if (const int err = s.in(q, l, u, x, y, rec, warm)) return err;
-  const int err = run_lockstep(nbatch, q ? s.dq : nullptr, l ? s.dl : nullptr, u ? s.du : nullptr, s.dx, s.dy, s.drec, warm, nullptr);
-  if (!err) s.out(x, y, rec);
-  return err;
-}
-
-int Engine::batch_solve_lockstep_device(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream) {
-  const int enter = batch_enter(nbatch, true, x, y, rec, &Engine::lockstep_applies);
-  if (enter != kBatchEnter) return enter;
-  be::sync(d_);                                     // the solver's own stream first: pending updates of the resident q / l / u, the matrices
-  return run_lockstep(nbatch, q, l, u, x, y, rec, warm, stream);
-}
-
-// ------------------------------------------------------------------------------------------------ direct lockstep route (Woodbury handles)
-// lockstep_hip.hip "lockstep DIRECT": the lockstep iteration with the PCG replaced by the Woodbury formula per problem.  Applies to a handle in the small
-// Woodbury mode whose K0 setup found structurally diagonal (prepare_wb: wb_k0diag_), as numbered by the caller: a reordered handle declines.
-bool Engine::lockstep_direct_applies() {
-  return be::lockstep_direct_chunk && be::lockstep_direct_values && be::device_vec_updates() && d_.wb.on && !d_.wb.large && d_.wb.r >= 1 && d_.wb.r <= kWbMaxRows && wb_k0diag_ && !reordered_;
-}
-
+// ---- the direct route's view of A and position map
 int Engine::prepare_lockstep_direct_view() {
   if (lsd_vrp_) return OSQP_NO_ERROR;
   // the view of A: a one-entry row keeps its entry (vsrc: where it sits in A.val), long row a becomes the entry 1.0 at column n + a
@@ -1097,10 +985,6 @@ int Engine::fill_lockstep_direct_view(LockstepDirectView &v, void *stream) {
   return be::lockstep_direct_values(d_, lsd_nv_, lsd_vsrc_, lsd_vval_, stream);      // (A's values may have changed since the last call)
 }
 
-// ---- per-problem matrices on the direct route (include/osqp_hip.h osqp_hip_batch_solve_lockstep_direct_mat).  What lockstep_direct_applies() accepts, with
-// the conditions of the chunk's assembly (lockstep_mat_applies: device assembly, the raw values resident, no repeated (j, j) in the stored triangle of P).
-bool Engine::lockstep_direct_mat_applies() { return lockstep_direct_applies() && mat_assembly_applies(); }
-
 // where entry (long row a, column j) of A sits in the engine's A.val, at j r + a (-1: no entry): what fills a chunk's own dense rows.  Once per handle.
 void Engine::prepare_lockstep_direct_wtpos() {
   if (lsd_wtpos_) return;
@@ -1117,117 +1001,150 @@ void Engine::prepare_lockstep_direct_wtpos() {
   be::sync(d_);
 }
 
-int Engine::run_lockstep_direct(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream,
-                                bool mat, const double *Px, const double *Ax) {
-  const int r = d_.wb.r;
-  const size_t need = lockstep_direct_ws_doubles(n, m, r);
-  LockstepDirectParams p;
-  if (const int err = fill_lockstep_direct_view(p.v, stream)) return err;
-  if (!lsdw_) { lsdw_ = dev_vec<double>(d_, need); be::sync(d_); }
-  fill_batch_settings(p, warm);
-  fill_lockstep_handle(p);
-  p.ws = lsdw_;
-  // per-problem matrices: the block (the matrix block, the chunk's own dense rows and view values; allocated by the first such call) and the position map
+// ---- solve: the chunk loop of both routes.  Every array of `a` is a DEVICE array in the caller's numbering; the settings are read once, in front of the
+// first chunk.  What the routes do differently is said here, once:
+//   PCG     the value maps of a reordered handle and lsm_last_count_ (with mat), polish and its record (settings.polishing);
+//   direct  the view of A (and, with mat, the position map of the dense rows), the single-QP rho rule, the call's seconds in slot 7 of its record.
+int Engine::run_lockstep_solve(bool direct, int nbatch, const LockstepSolveIO &a, void *stream) {
+  const bool mat = a.mat;
   const int nzP = d_.nzP, nzA = d_.nzA;
-  const size_t mneed = lockstep_direct_mat_ws_doubles(n, m, r, d_.A.nnz, d_.B.nnz, lsd_nv_);
-  double mst[kLsMatStat] = {0, 0}, mtot[kLsMatStat] = {0, 0};
+  LsRoute &rt = lsr_[direct];
+  LockstepDirectParams p;                             // (the PCG route takes its LockstepParams base)
+  // direct: the view before any allocation -- its value refresh is a launch on `stream`
+  if (direct) if (const int err = fill_lockstep_direct_view(p.v, stream)) return err;
+  const size_t need = direct ? lockstep_direct_ws_doubles(n, m, d_.wb.r) : lockstep_ws_doubles(n, m);
+  const size_t mneed = direct ? lockstep_direct_mat_ws_doubles(n, m, d_.wb.r, d_.A.nnz, d_.B.nnz, lsd_nv_) : lockstep_mat_ws_doubles(n, m, d_.A.nnz, d_.B.nnz);
+  if (!rt.ws) { rt.ws = dev_vec<double>(d_, need); be::sync(d_); }
+  fill_batch_settings(p, a.warm);                     // the settings snapshot of the batch path
+  fill_lockstep_handle(p);
+  p.ws = rt.ws;
+  // per-problem matrices: the route's matrix block (allocated by the first such call, solve or adjoint) and what maps the caller's values into it
+  double mst[kLsMatStat] = {0, 0}, mtot = 0;
   if (mat) {
-    prepare_lockstep_direct_wtpos();
-    if (!lsdmw_) { lsdmw_ = dev_vec<double>(d_, mneed); be::sync(d_); }
-    p.mat_ws = lsdmw_; p.mat_stat = mst; p.mat_iters = std::max(0, (int)settings.scaling);
-    p.v.wtpos = lsd_wtpos_; p.v.vsrc = lsd_vsrc_;
+    bool fresh = false;
+    if (direct) { prepare_lockstep_direct_wtpos(); p.v.wtpos = lsd_wtpos_; p.v.vsrc = lsd_vsrc_; }
+    else { fresh = ensure_value_maps(); p.pvmap = reordered_ ? d_pvmap_ : nullptr; p.avmap = reordered_ ? d_avmap_ : nullptr; }
+    if (!rt.mat_ws) { rt.mat_ws = dev_vec<double>(d_, mneed); fresh = true; }
+    if (fresh) be::sync(d_);
+    p.mat_ws = rt.mat_ws; p.mat_stat = mst; p.mat_iters = std::max(0, (int)settings.scaling);
   }
-  // adaptive rho as the handle's own solve decides it (ctl_setup: the tolerance on the square-root scale where P has a quadratic part, the persistence
-  // test), not as the batch family does: an element then takes the path update(q, l, u) + solve() takes from the same rho
-  p.rho_tol_single = pol_rho_tol(settings.adaptive_rho_tolerance, has_quad(), pol_.rho_tol_exp); p.rho_persist = pol_.rho_persist;
+  // PCG, polish (settings.polishing; with per-problem matrices too: the chunk polishes on its own matrix block): the recurrence of Engine::run_recurrence as
+  // Engine::polish calls it, per problem on block vectors -- rho_bar = 1 / delta_eff, at least 1 + polish_refine_iter steps, the inner systems to
+  // polish_pcg_tol within kMaxCg iterations.  Its work block is allocated by the first such call.  A direct call does not polish and leaves the record alone.
+  double pst[kLsPolStat] = {0, 0, 0, 0, 0, 0, 0}, ptot[kLsPolStat] = {0, 0, 0, 0, 0, 0, 0};
+  const size_t pneed = lockstep_polish_ws_doubles(n, m);
+  if (!direct && settings.polishing) {
+    if (!lspw_) { lspw_ = dev_vec<double>(d_, pneed); be::sync(d_); }
+    const double de = std::max(settings.delta, pol_.polish_delta_floor);
+    p.polish = 1; p.pol_rho = clamp_rho(1.0 / de); p.pol_min_steps = 1 + std::max(0, (int)settings.polish_refine_iter);
+    p.pol_cg_max = kMaxCg; p.pol_pcg_rel = pol_.polish_pcg_tol; p.pol_ws = lspw_; p.pol_stat = pst;
+  }
+  // direct, adaptive rho as the handle's own solve decides it (ctl_setup: the tolerance on the square-root scale where P has a quadratic part, the
+  // persistence test), not as the batch family does: an element then takes the path update(q, l, u) + solve() takes from the same rho
+  if (direct) { p.rho_tol_single = pol_rho_tol(settings.adaptive_rho_tolerance, has_quad(), pol_.rho_tol_exp); p.rho_persist = pol_.rho_persist; }
   const double t0 = now_s(), limit = settings.time_limit > 0 && settings.time_limit < 1e9 ? settings.time_limit : 0.0;
   double tot[4] = {0, 0, 0, 0};
   int chunks = 0;
+  if (!direct) std::fill(ls_last_[kLsRecPolish], ls_last_[kLsRecPolish] + kLsRecLen, 0.0);
   for (int b0 = 0; b0 < nbatch; b0 += kLsW, chunks++) {
     p.count = std::min(kLsW, nbatch - b0);
-    p.q = q ? q + (size_t)b0 * n : nullptr; p.l = l ? l + (size_t)b0 * m : nullptr; p.u = u ? u + (size_t)b0 * m : nullptr;
-    p.x = x + (size_t)b0 * n; p.y = y + (size_t)b0 * m; p.rec = rec + (size_t)b0 * kBatchRec;
-    p.Px = (mat && Px) ? Px + (size_t)b0 * nzP : nullptr; p.Ax = (mat && Ax) ? Ax + (size_t)b0 * nzA : nullptr;
+    p.q = a.q ? a.q + (size_t)b0 * n : nullptr; p.l = a.l ? a.l + (size_t)b0 * m : nullptr; p.u = a.u ? a.u + (size_t)b0 * m : nullptr;
+    p.x = a.x + (size_t)b0 * n; p.y = a.y + (size_t)b0 * m; p.rec = a.rec + (size_t)b0 * kBatchRec;
+    p.Px = (mat && a.Px) ? a.Px + (size_t)b0 * nzP : nullptr; p.Ax = (mat && a.Ax) ? a.Ax + (size_t)b0 * nzA : nullptr;
     p.time_limit = limit > 0 ? std::max(limit - (now_s() - t0), 1e-9) : 0.0;
     double st[4] = {0, 0, 0, 0};
-    const int err = be::lockstep_direct_chunk(d_, p, stream, st);
+    std::fill(pst, pst + kLsPolStat, 0.0);
+    if (mat && !direct) lsm_last_count_ = 0;          // (the block is being overwritten)
+    const int err = direct ? be::lockstep_direct_chunk(d_, p, stream, st) : be::lockstep_chunk(d_, p, stream, st);
     if (err) return err;
-    if (mat) { mtot[0] += mst[0]; mtot[1] += mst[1]; }
-    tot[0] = std::max(tot[0], st[0]); tot[1] += st[1]; tot[2] += st[2]; tot[3] += st[3];
+    if (mat && !direct) lsm_last_count_ = p.count;
+    tot[0] = std::max(tot[0], st[0]); tot[1] += st[1]; tot[2] += st[2]; tot[3] += st[3]; mtot += mst[0];
+    for (int k = 0; k < kLsPolStat; k++) ptot[k] = k == 3 ? std::max(ptot[k], pst[k]) : ptot[k] + pst[k];
   }
-  const double rr[OSQP_HIP_LOCKSTEP_DIRECT_LAST_REC] = {(double)chunks, (double)kLsW, tot[0], tot[1], tot[2], tot[3], (double)(need * sizeof(double)), now_s() - t0};
-  std::copy(rr, rr + OSQP_HIP_LOCKSTEP_DIRECT_LAST_REC, lsd_rec_);
+  // the records: the route's own (a PCG call with mat writes it as well), the mat record, the PCG route's polish record
+  const double r[kLsRecLen] = {(double)chunks, (double)kLsW, tot[0], tot[1], tot[2], tot[3], (double)(need * sizeof(double)), direct ? now_s() - t0 : 0.0};
+  std::copy(r, r + kLsRecLen, ls_last_[direct ? kLsRecDirect : kLsRecSolve]);
   if (mat) {
-    const double rm[OSQP_HIP_LOCKSTEP_DIRECT_MAT_LAST_REC] = {(double)chunks, (double)kLsW, tot[0], tot[1], tot[2], tot[3], (double)(mneed * sizeof(double)), mtot[0]};
-    std::copy(rm, rm + OSQP_HIP_LOCKSTEP_DIRECT_MAT_LAST_REC, lsdm_rec_);
+    const double rm[kLsRecLen] = {(double)chunks, (double)kLsW, tot[0], tot[1], tot[2], tot[3], (double)(mneed * sizeof(double)), mtot};
+    std::copy(rm, rm + kLsRecLen, ls_last_[direct ? kLsRecDirectMat : kLsRecMat]);
+  }
+  if (!direct) {
+    std::copy(ptot, ptot + kLsPolStat, ls_last_[kLsRecPolish]);
+    ls_last_[kLsRecPolish][kLsPolStat] = settings.polishing ? (double)(pneed * sizeof(double)) : 0.0;
   }
   return OSQP_NO_ERROR;
 }
 
-int Engine::batch_solve_lockstep_direct(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm) {
-  BatchStage s{*this, nbatch, &Engine::lockstep_direct_applies, /*own_row=*/nullptr, /*wg=*/false};
-  if (const int err = s.in(q, l, u, x, y, rec, warm)) return err;
-  const int err = run_lockstep_direct(nbatch, q ? s.dq : nullptr, l ? s.dl : nullptr, u ? s.du : nullptr, s.dx, s.dy, s.drec, warm, nullptr);
-  if (!err) s.out(x, y, rec);
+// the host-array entry of both routes, staged like batch_solve.  The PCG route serves a reordered handle, whose own bounds are kept in the engine's numbering.
+int Engine::solve_lockstep_host(bool direct, int nbatch, const LockstepSolveIO &h) {
+  BatchStage s{*this, nbatch, solve_applies(direct, h.mat), /*own_row=*/(!direct && reordered_) ? ipr_.data() : nullptr, /*wg=*/false};
+  const double *Px = h.mat ? h.Px : nullptr, *Ax = h.mat ? h.Ax : nullptr;
+  if (const int err = s.in(h.q, h.l, h.u, h.x, h.y, h.rec, h.warm, Px, Ax)) return err;
+  const LockstepSolveIO dv{h.q ? s.dq : nullptr, h.l ? s.dl : nullptr, h.u ? s.du : nullptr, s.dx, s.dy, s.drec, h.warm, h.mat, Px ? s.dPx : nullptr, Ax ? s.dAx : nullptr};
+  const int err = run_lockstep_solve(direct, nbatch, dv, nullptr);
+  if (!err) s.out(h.x, h.y, h.rec);
   return err;
 }
 
-int Engine::batch_solve_lockstep_direct_device(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream) {
-  const int enter = batch_enter(nbatch, true, x, y, rec, &Engine::lockstep_direct_applies);
+// the device-array entry of both routes
+int Engine::solve_lockstep_device(bool direct, int nbatch, const LockstepSolveIO &a, void *stream) {
+  const int enter = batch_enter(nbatch, true, a.x, a.y, a.rec, solve_applies(direct, a.mat));
   if (enter != kBatchEnter) return enter;
-  be::sync(d_);                                     // the solver's own stream first: pending updates of the resident q / l / u, the matrices
-  return run_lockstep_direct(nbatch, q, l, u, x, y, rec, warm, stream);
+  be::sync(d_);                                       // the solver's own stream first: pending updates of the resident q / l / u, the matrices, the raw matrix values
+  return run_lockstep_solve(direct, nbatch, a, stream);
 }
 
-int Engine::batch_solve_lockstep_direct_mat(int nbatch, const double *Px, const double *Ax, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm) {
-  BatchStage s{*this, nbatch, &Engine::lockstep_direct_mat_applies, /*own_row=*/nullptr, /*wg=*/false};
-  if (const int err = s.in(q, l, u, x, y, rec, warm, Px, Ax)) return err;
-  const int err = run_lockstep_direct(nbatch, q ? s.dq : nullptr, l ? s.dl : nullptr, u ? s.du : nullptr, s.dx, s.dy, s.drec, warm, nullptr, true, Px ? s.dPx : nullptr, Ax ? s.dAx : nullptr);
-  if (!err) s.out(x, y, rec);
-  return err;
+// D, E, c of problem b of the last chunk the last PCG-route solve with per-problem matrices processed, in the caller's numbering: read back from the matrix
+// block and the chunk's scalar state (row kLsMatScalC), where lockstep_layout.h's carves put them
+int Engine::lockstep_mat_scaling(int b, double *D, double *E, double *c) {
+  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (!D || (m > 0 && !E) || !c) return OSQP_DATA_VALIDATION_ERROR;
+  const LsRoute &rt = lsr_[0];
+  if (!rt.mat_ws || !rt.ws || b < 0 || b >= lsm_last_count_) return OSQP_DATA_NOT_INITIALIZED;
+  be::activate(d_);
+  be::ext_wait(d_);
+  const size_t nW = (size_t)n * kLsW, mW = (size_t)m * kLsW;
+  LsCursor cm{rt.mat_ws};
+  LsMatVecs t;
+  lockstep_carve_mat(cm, t, n, m, d_.A.nnz, d_.B.nnz);
+  const double *dD = t.D, *dE = t.E;
+  std::vector<double> h(std::max(nW, mW));
+  be::d2h(d_, h.data(), dD, sizeof(double) * nW);
+  for (int j = 0; j < n; j++) D[reordered_ ? pc_[j] : j] = h[(size_t)j * kLsW + b];
+  if (m > 0) {
+    be::d2h(d_, h.data(), dE, sizeof(double) * mW);
+    for (int i = 0; i < m; i++) E[reordered_ ? pr_[i] : i] = h[(size_t)i * kLsW + b];
+  }
+  double cs[kLsW];
+  be::d2h(d_, cs, rt.ws + lockstep_sc_offset(n, m) + (size_t)kLsMatScalC * kLsW, sizeof(cs));
+  *c = cs[b];
+  return OSQP_NO_ERROR;
 }
 
-int Engine::batch_solve_lockstep_direct_mat_device(int nbatch, const double *Px, const double *Ax, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, void *stream) {
-  const int enter = batch_enter(nbatch, true, x, y, rec, &Engine::lockstep_direct_mat_applies);
-  if (enter != kBatchEnter) return enter;
-  be::sync(d_);                                     // the solver's own stream first: pending updates of the resident q / l / u, the raw matrix values
-  return run_lockstep_direct(nbatch, q, l, u, x, y, rec, warm, stream, true, Px, Ax);
-}
-
-// ---- the backward pass of a lockstep batch (lockstep_hip.hip lockstep_adjoint_chunk): chunk after chunk like run_lockstep.  Every array is a DEVICE
-// array in the caller's numbering (dP / dA: the caller's CSC order).  The recurrence's settings are those of Engine::run_recurrence as the single-QP
-// adjoint calls it: rho_bar = 1 / delta_eff on the active rows with equality factor 1, alpha = 1, PCG to polish_pcg_tol within kMaxCg, progress rule
-// {rhs_norm, 0.9, 60} after at least 1 + polish_refine_iter steps.  The work block (lsaw_) is this route's own: the handle's iterates, rho, info,
-// solution, graphs and history -- and the forward route's workspace and record -- are not touched.
-bool Engine::lockstep_adjoint_applies() { return be::lockstep_adjoint_chunk && be::device_assembly() && be::device_vec_updates() && !d_.wb.on; }
-
-// The backward pass on the direct route (lockstep_hip.hip lockstep_direct_adjoint_chunk) is the same settings and chunking on the handles
-// lockstep_direct_applies accepts.  The recurrence's rho is fixed, so S_b is inverted once per problem.  The work block (lsdaw_) and the host entry's
-// scratch are that route's own; the view of A is the forward's (read only, its values refreshed per call); the handle's solve state, the forward route's
-// workspace and its record are not written.
-bool Engine::lockstep_direct_adjoint_applies() { return lockstep_direct_applies() && be::lockstep_direct_adjoint_chunk && be::device_assembly(); }
-
-// Both routes' chunk loop.  direct selects the applicability, the work block, the chunk function and the record.  a.mat: every chunk assembles and
-// equilibrates its problems' own matrices in the forward's matrix block of that route (PCG: lsmw_; direct: lsdmw_, which also holds the chunk's own dense
-// rows and view values -- one block per handle, allocated by whichever entry comes first), which this call therefore overwrites -- lockstep_mat_scaling
-// answers OSQP_DATA_NOT_INITIALIZED until the next forward call.  A forward call prepares its block anew, so its results do not depend on this one.
+// ---- adjoint: the chunk loop of both routes (lockstep_hip.hip lockstep_adjoint_chunk / lockstep_direct_adjoint_chunk), chunk after chunk like
+// run_lockstep_solve.  Every array is a DEVICE array in the caller's numbering (dP / dA: the caller's CSC order).  The recurrence's settings are those of
+// Engine::run_recurrence as the single-QP adjoint calls it: rho_bar = 1 / delta_eff on the active rows with equality factor 1, alpha = 1, PCG to
+// polish_pcg_tol within kMaxCg (direct: no PCG -- the recurrence's rho is fixed, so S_b is inverted once per problem), progress rule {rhs_norm, 0.9, 60}
+// after at least 1 + polish_refine_iter steps.  The work block (adj_ws) is the direction's own; the direct route's view of A is the forward's (read only,
+// its values refreshed per call); the forward's workspace and records are not written.  a.mat: every chunk assembles and equilibrates its problems' own
+// matrices in the route's matrix block, which this call therefore overwrites -- lockstep_mat_scaling answers OSQP_DATA_NOT_INITIALIZED until the next
+// forward call.  A forward call prepares its block anew, so its results do not depend on this one.
 int Engine::run_lockstep_adjoint(bool direct, int nbatch, const LockstepAdjointIO &a, void *stream) {
   const int nzP = d_.nzP, nzA = d_.nzA;
   const bool mat = a.mat;
+  LsRoute &rt = lsr_[direct];
   const size_t need = direct ? lockstep_direct_adjoint_ws_doubles(n, m, d_.wb.r) : lockstep_adjoint_ws_doubles(n, m);
   LockstepDirectAdjointParams p;                      // (the PCG route takes its LockstepAdjointParams base)
   if (direct) if (const int err = fill_lockstep_direct_view(p.v, stream)) return err;
   const size_t mneed = direct ? lockstep_direct_mat_ws_doubles(n, m, d_.wb.r, d_.A.nnz, d_.B.nnz, lsd_nv_) : lockstep_mat_ws_doubles(n, m, d_.A.nnz, d_.B.nnz);
-  double *&ws = direct ? lsdaw_ : lsaw_;
-  double *&mws = direct ? lsdmw_ : lsmw_;
   bool fresh = ensure_value_maps();
-  if (!ws) { ws = dev_vec<double>(d_, need); fresh = true; }
-  if (mat && !mws) { mws = dev_vec<double>(d_, mneed); fresh = true; }
+  if (!rt.adj_ws) { rt.adj_ws = dev_vec<double>(d_, need); fresh = true; }
+  if (mat && !rt.mat_ws) { rt.mat_ws = dev_vec<double>(d_, mneed); fresh = true; }
   if (mat && direct) { prepare_lockstep_direct_wtpos(); p.v.wtpos = lsd_wtpos_; p.v.vsrc = lsd_vsrc_; }
   if (fresh) be::sync(d_);
   fill_batch_settings(p, 0);
   fill_lockstep_handle(p);
-  p.ws = ws;
+  p.ws = rt.adj_ws;
   // the recurrence's settings; the direct route has no PCG
   const double de = std::max(settings.delta, pol_.polish_delta_floor);
   p.alpha = 1.0; p.rho0 = clamp_rho(1.0 / de); p.eq_factor = 1.0; p.cg_max = direct ? 0 : kMaxCg; p.pcg_rel = direct ? 0.0 : pol_.polish_pcg_tol;
@@ -1235,7 +1152,7 @@ int Engine::run_lockstep_adjoint(bool direct, int nbatch, const LockstepAdjointI
   p.nzP = nzP; p.nzA = nzA; p.Pi = d_.Pi; p.Pj = d_.Pj; p.Ai = d_.Ai; p.Aj = d_.Aj; p.Pmap = reordered_ ? d_pvmap_ : nullptr; p.Amap = reordered_ ? d_avmap_ : nullptr;
   double mst[kLsMatStat] = {0, 0}, mtot = 0;
   if (mat) {
-    p.mat_ws = mws; p.mat_stat = mst; p.mat_iters = std::max(0, (int)settings.scaling); p.pvmap = p.Pmap; p.avmap = p.Amap;
+    p.mat_ws = rt.mat_ws; p.mat_stat = mst; p.mat_iters = std::max(0, (int)settings.scaling); p.pvmap = p.Pmap; p.avmap = p.Amap;
     if (!direct) lsm_last_count_ = 0;                 // (the block is being overwritten)
   }
   double tot[4] = {0, 0, 0, 0};
@@ -1252,13 +1169,11 @@ int Engine::run_lockstep_adjoint(bool direct, int nbatch, const LockstepAdjointI
     if (err) return err;
     tot[0] = std::max(tot[0], st[0]); tot[1] += st[1]; tot[2] += st[2]; tot[3] += st[3]; mtot += mst[0];
   }
-  static_assert(OSQP_HIP_LOCKSTEP_ADJOINT_LAST_REC == OSQP_HIP_LOCKSTEP_DIRECT_ADJOINT_LAST_REC, "one record text for both adjoint routes");
-  const double r[OSQP_HIP_LOCKSTEP_ADJOINT_LAST_REC] = {(double)chunks, (double)kLsW, tot[0], tot[1], tot[2], tot[3], (double)(need * sizeof(double)), 0.0};
-  std::copy(r, r + OSQP_HIP_LOCKSTEP_ADJOINT_LAST_REC, direct ? lsda_rec_ : lsa_rec_);
+  const double r[kLsRecLen] = {(double)chunks, (double)kLsW, tot[0], tot[1], tot[2], tot[3], (double)(need * sizeof(double)), 0.0};
+  std::copy(r, r + kLsRecLen, ls_last_[direct ? kLsRecDirectAdjoint : kLsRecAdjoint]);
   if (mat) {
-    const double rm[OSQP_HIP_LOCKSTEP_MAT_ADJOINT_LAST_REC] = {(double)chunks, (double)kLsW, tot[0], tot[1], tot[2], tot[3], (double)(mneed * sizeof(double)), mtot};
-    static_assert(OSQP_HIP_LOCKSTEP_MAT_ADJOINT_LAST_REC == OSQP_HIP_LOCKSTEP_DIRECT_MAT_ADJOINT_LAST_REC, "one record text for both routes with per-problem matrices");
-    std::copy(rm, rm + OSQP_HIP_LOCKSTEP_MAT_ADJOINT_LAST_REC, direct ? lsdma_rec_ : lsma_rec_);
+    const double rm[kLsRecLen] = {(double)chunks, (double)kLsW, tot[0], tot[1], tot[2], tot[3], (double)(mneed * sizeof(double)), mtot};
+    std::copy(rm, rm + kLsRecLen, ls_last_[direct ? kLsRecDirectMatAdjoint : kLsRecMatAdjoint]);
   }
   return OSQP_NO_ERROR;
 }
@@ -1268,9 +1183,9 @@ int Engine::adjoint_lockstep_host(bool direct, int nbatch, const LockstepAdjoint
   if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   if (nbatch <= 0 || !h.x || (!h.y && m > 0) || !h.dx) return OSQP_DATA_VALIDATION_ERROR;
   be::activate(d_);
-  if (!(direct ? lockstep_direct_adjoint_applies() : lockstep_adjoint_applies()) || (h.mat && !(direct ? lockstep_direct_mat_applies() : lockstep_mat_applies()))) return OSQP_FUNC_NOT_IMPLEMENTED;
+  if (!(direct ? lockstep_direct_adjoint_applies() : lockstep_adjoint_applies()) || (h.mat && !(this->*solve_applies(direct, true))())) return OSQP_FUNC_NOT_IMPLEMENTED;
   be::ext_wait(d_);
-  DevScratch &sc = direct ? lsdabuf_ : lsabuf_;
+  DevScratch &sc = lsr_[direct].adj_buf;
   const size_t nb = (size_t)nbatch, N = nb * n, M = nb * m, NP = nb * (size_t)d_.nzP, NA = nb * (size_t)d_.nzA;
   const size_t MP = (h.mat && h.Px) ? NP : 0, MA = (h.mat && h.Ax) ? NA : 0;
   // [l | u | x | y | dx | dy | dP | dq | dA | dl | du | arec | Px | Ax]   (the last two: per-problem matrices, where given)
@@ -1296,45 +1211,12 @@ int Engine::adjoint_lockstep_device(bool direct, int nbatch, const LockstepAdjoi
   if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   if (nbatch < 0) return OSQP_DATA_VALIDATION_ERROR;
   be::activate(d_);
-  if (!(direct ? lockstep_direct_adjoint_applies() : lockstep_adjoint_applies()) || (a.mat && !(direct ? lockstep_direct_mat_applies() : lockstep_mat_applies()))) return OSQP_FUNC_NOT_IMPLEMENTED;
+  if (!(direct ? lockstep_direct_adjoint_applies() : lockstep_adjoint_applies()) || (a.mat && !(this->*solve_applies(direct, true))())) return OSQP_FUNC_NOT_IMPLEMENTED;
   if (nbatch == 0) return OSQP_NO_ERROR;              // (the applicability query, as osqp_hip_batch_solve_lockstep_device answers it)
   if (!a.x || (!a.y && m > 0) || !a.dx) return OSQP_DATA_VALIDATION_ERROR;
   be::ext_wait(d_);
   be::sync(d_);                                       // the solver's own stream first: pending updates of the resident l / u, the matrices
   return run_lockstep_adjoint(direct, nbatch, a, stream);
-}
-
-int Engine::batch_adjoint_lockstep(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
-                                   double *dP, double *dq, double *dA, double *dl, double *du, double *arec) {
-  return adjoint_lockstep_host(false, nbatch, {l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec});
-}
-int Engine::batch_adjoint_lockstep_device(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
-                                          double *dP, double *dq, double *dA, double *dl, double *du, double *arec, void *stream) {
-  return adjoint_lockstep_device(false, nbatch, {l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec}, stream);
-}
-int Engine::batch_adjoint_lockstep_mat(int nbatch, const double *Px, const double *Ax, const double *l, const double *u, const double *x, const double *y, const double *dx,
-                                       const double *dy, double *dP, double *dq, double *dA, double *dl, double *du, double *arec) {
-  return adjoint_lockstep_host(false, nbatch, {l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec, true, Px, Ax});
-}
-int Engine::batch_adjoint_lockstep_mat_device(int nbatch, const double *Px, const double *Ax, const double *l, const double *u, const double *x, const double *y, const double *dx,
-                                              const double *dy, double *dP, double *dq, double *dA, double *dl, double *du, double *arec, void *stream) {
-  return adjoint_lockstep_device(false, nbatch, {l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec, true, Px, Ax}, stream);
-}
-int Engine::batch_adjoint_lockstep_direct(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
-                                          double *dP, double *dq, double *dA, double *dl, double *du, double *arec) {
-  return adjoint_lockstep_host(true, nbatch, {l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec});
-}
-int Engine::batch_adjoint_lockstep_direct_device(int nbatch, const double *l, const double *u, const double *x, const double *y, const double *dx, const double *dy,
-                                                 double *dP, double *dq, double *dA, double *dl, double *du, double *arec, void *stream) {
-  return adjoint_lockstep_device(true, nbatch, {l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec}, stream);
-}
-int Engine::batch_adjoint_lockstep_direct_mat(int nbatch, const double *Px, const double *Ax, const double *l, const double *u, const double *x, const double *y, const double *dx,
-                                              const double *dy, double *dP, double *dq, double *dA, double *dl, double *du, double *arec) {
-  return adjoint_lockstep_host(true, nbatch, {l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec, true, Px, Ax});
-}
-int Engine::batch_adjoint_lockstep_direct_mat_device(int nbatch, const double *Px, const double *Ax, const double *l, const double *u, const double *x, const double *y, const double *dx,
-                                                     const double *dy, double *dP, double *dq, double *dA, double *dl, double *du, double *arec, void *stream) {
-  return adjoint_lockstep_device(true, nbatch, {l, u, x, y, dx, dy, dP, dq, dA, dl, du, arec, true, Px, Ax}, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ adjoint derivatives

@@ -195,7 +195,7 @@ OSQP_HD inline int ctl_stage2(const Ctl &c, const double *r2, bool approximate) 
 }
 
 // the tolerance of ctl_rho_rule: the setting's on this engine's square-root scale (tol_exp, default 0.5); LPs keep the literal value.  Also what the
-// direct lockstep route hands its kernel (Engine::run_lockstep_direct): one text, so a batch element and the handle's own solve test against the same value
+// direct lockstep route hands its kernel (Engine::run_lockstep_solve): one text, so a batch element and the handle's own solve test against the same value
 OSQP_HD inline double pol_rho_tol(double rho_tolerance, int has_quad, double tol_exp) { return pow(rho_tolerance, has_quad ? tol_exp : 1.0); }
 // adapt_rho (_osqp.py:910-930) on the indirect path.  Returns true when rho_bar changed.
 // An update costs this path two small kernels, not a refactorisation -- the reason for the reference's factor-5 guard -- so the tolerance

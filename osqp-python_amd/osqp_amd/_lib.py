@@ -150,32 +150,8 @@ PROTOTYPES = {
     'osqp_hip_batch_solve_mat_device': (C.c_int, [SolverP, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     'osqp_hip_adjoint_compute_at': (C.c_int, [SolverP] + [c_double_p] * 4),
     'osqp_hip_adjoint_last_record': (C.c_int, [SolverP, c_double_p]),
-    'osqp_hip_batch_solve_lockstep': (C.c_int, [SolverP, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int]),
-    'osqp_hip_batch_solve_lockstep_device': (C.c_int, [SolverP, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
-    'osqp_hip_lockstep_last_record': (C.c_int, [SolverP, c_double_p]),
     'osqp_hip_lockstep_polish_last_record': (C.c_int, [SolverP, c_double_p]),
-    'osqp_hip_batch_solve_lockstep_mat': (C.c_int, [SolverP, C.c_int] + [c_double_p] * 8 + [C.c_int]),
-    'osqp_hip_batch_solve_lockstep_mat_device': (C.c_int, [SolverP, C.c_int] + [C.c_void_p] * 8 + [C.c_int, C.c_void_p]),
-    'osqp_hip_lockstep_mat_last_record': (C.c_int, [SolverP, c_double_p]),
     'osqp_hip_lockstep_mat_scaling': (C.c_int, [SolverP, C.c_int, c_double_p, c_double_p, c_double_p]),
-    'osqp_hip_batch_solve_lockstep_direct': (C.c_int, [SolverP, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int]),
-    'osqp_hip_batch_solve_lockstep_direct_device': (C.c_int, [SolverP, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
-    'osqp_hip_lockstep_direct_last_record': (C.c_int, [SolverP, c_double_p]),
-    'osqp_hip_batch_solve_lockstep_direct_mat': (C.c_int, [SolverP, C.c_int] + [c_double_p] * 8 + [C.c_int]),
-    'osqp_hip_batch_solve_lockstep_direct_mat_device': (C.c_int, [SolverP, C.c_int] + [C.c_void_p] * 8 + [C.c_int, C.c_void_p]),
-    'osqp_hip_lockstep_direct_mat_last_record': (C.c_int, [SolverP, c_double_p]),
-    'osqp_hip_batch_adjoint_lockstep': (C.c_int, [SolverP, C.c_int] + [c_double_p] * 12),
-    'osqp_hip_batch_adjoint_lockstep_device': (C.c_int, [SolverP, C.c_int] + [C.c_void_p] * 13),
-    'osqp_hip_lockstep_adjoint_last_record': (C.c_int, [SolverP, c_double_p]),
-    'osqp_hip_batch_adjoint_lockstep_mat': (C.c_int, [SolverP, C.c_int] + [c_double_p] * 14),
-    'osqp_hip_batch_adjoint_lockstep_mat_device': (C.c_int, [SolverP, C.c_int] + [C.c_void_p] * 15),
-    'osqp_hip_lockstep_mat_adjoint_last_record': (C.c_int, [SolverP, c_double_p]),
-    'osqp_hip_batch_adjoint_lockstep_direct': (C.c_int, [SolverP, C.c_int] + [c_double_p] * 12),
-    'osqp_hip_batch_adjoint_lockstep_direct_device': (C.c_int, [SolverP, C.c_int] + [C.c_void_p] * 13),
-    'osqp_hip_lockstep_direct_adjoint_last_record': (C.c_int, [SolverP, c_double_p]),
-    'osqp_hip_batch_adjoint_lockstep_direct_mat': (C.c_int, [SolverP, C.c_int] + [c_double_p] * 14),
-    'osqp_hip_batch_adjoint_lockstep_direct_mat_device': (C.c_int, [SolverP, C.c_int] + [C.c_void_p] * 15),
-    'osqp_hip_lockstep_direct_mat_adjoint_last_record': (C.c_int, [SolverP, c_double_p]),
     'osqp_hip_batch_adjoint': (C.c_int, [SolverP, C.c_int] + [c_double_p] * 14),
     'osqp_hip_batch_adjoint_device': (C.c_int, [SolverP, C.c_int] + [C.c_void_p] * 15),
     'osqp_hip_capabilities': (C.c_int, []),
@@ -187,6 +163,14 @@ PROTOTYPES = {
     'osqp_hip_linsys_init': (C.c_int, [C.POINTER(LinSysP), C.POINTER(CscStruct), C.POINTER(CscStruct), c_double_p,
                                        C.POINTER(SettingsStruct), c_double_p, c_double_p, C.c_int]),
 }
+# the lockstep family (include/osqp_hip.h): route x matrices (Px, Ax in front) x direction x host / device arrays, and a last-record getter for each but the last axis
+for _stem in ('lockstep', 'lockstep_direct'):
+    for _mat, _k in (('', 0), ('_mat', 2)):
+        PROTOTYPES['osqp_hip_batch_solve_%s%s' % (_stem, _mat)] = (C.c_int, [SolverP, C.c_int] + [c_double_p] * (6 + _k) + [C.c_int])
+        PROTOTYPES['osqp_hip_batch_solve_%s%s_device' % (_stem, _mat)] = (C.c_int, [SolverP, C.c_int] + [C.c_void_p] * (6 + _k) + [C.c_int, C.c_void_p])
+        PROTOTYPES['osqp_hip_batch_adjoint_%s%s' % (_stem, _mat)] = (C.c_int, [SolverP, C.c_int] + [c_double_p] * (12 + _k))
+        PROTOTYPES['osqp_hip_batch_adjoint_%s%s_device' % (_stem, _mat)] = (C.c_int, [SolverP, C.c_int] + [C.c_void_p] * (13 + _k))
+        PROTOTYPES['osqp_hip_%s%s_last_record' % (_stem, _mat)] = PROTOTYPES['osqp_hip_%s%s_adjoint_last_record' % (_stem, _mat)] = (C.c_int, [SolverP, c_double_p])
 
 
 PRINT_FN = C.CFUNCTYPE(None, C.c_char_p, C.c_void_p)      # osqp_hip_print_fn

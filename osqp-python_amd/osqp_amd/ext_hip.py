@@ -73,6 +73,16 @@ def _ptr(a, typ):
     return None if a is None else a.ctypes.data_as(typ)
 
 
+def _rows(a, name, B, width):
+    """`a` as (B, width) float64 in C order -- the C side reads exactly B * width entries; None stays None."""
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.size != B * width or (a.ndim > 1 and a.shape[-1] != width):
+        raise ValueError('%s: expected %d problems of width %d, got shape %s' % (name, B, width, a.shape))
+    return a.reshape(B, width)
+
+
 class CSC:
     """bindings.cpp.in:12-62: zero-copy int32/f64 views of a SciPy CSC matrix."""
 
@@ -392,32 +402,7 @@ class OSQPSolver:
         """Solve a batch of QPs sharing this solver's P, A and settings (osqp_hip_batch_solve).  q: (B, n), l/u: (B, m).
         Px (B, nnz(triu P)) / Ax (B, nnz(A)): per-problem matrix values in the CSC order given at setup (osqp_hip_batch_solve_mat: the reference's
         per-element P_val / A_val, nn/torch.py:128-157) -- still one launch.  Returns x (B, n), y (B, m), rec (B, BATCH_REC) with columns BATCH_FIELDS."""
-        arrs = [a for a in (q, l, u, x0, y0, Px, Ax) if a is not None]
-        B = int(nbatch) if nbatch is not None else int(np.asarray(arrs[0]).shape[0])
-
-        def rows(a, name, width):                   # (B, width) float64, C order: the C side reads exactly B * width entries
-            a = np.ascontiguousarray(a, dtype=np.float64)
-            if a.size != B * width or (a.ndim > 1 and a.shape[-1] != width):
-                raise ValueError('%s: expected %d problems of width %d, got shape %s' % (name, B, width, a.shape))
-            return a.reshape(B, width)
-        q, l, u = (None if a is None else rows(a, name, w) for a, name, w in ((q, 'q', self.n), (l, 'l', self.m), (u, 'u', self.m)))
-        warm = x0 is not None or y0 is not None      # a missing one starts from zero, like warm_start(x=None) / (y=None) of a single solver
-        # (l, u are clamped to +-OSQP_INFTY inside the kernel, like interface.py:334-337)
-        x = np.zeros((B, self.n)) if x0 is None else rows(x0, 'x0', self.n).copy()
-        y = np.zeros((B, self.m)) if y0 is None else rows(y0, 'y0', self.m).copy()
-        rec = np.zeros((B, self.BATCH_REC))
-        if Px is not None or Ax is not None:
-            Px, Ax = (None if a is None else rows(a, name, w) for a, name, w in ((Px, 'Px', self.nnz_P), (Ax, 'Ax', self.nnz_A)))
-            st = self._lib.osqp_hip_batch_solve_mat(self._p, B, _ptr(Px, _lib.c_double_p), _ptr(Ax, _lib.c_double_p), _ptr(q, _lib.c_double_p), _ptr(l, _lib.c_double_p),
-                                                    _ptr(u, _lib.c_double_p), _ptr(x, _lib.c_double_p), _ptr(y, _lib.c_double_p), _ptr(rec, _lib.c_double_p), int(warm))
-            if st:
-                raise self._batch_error(st)
-            return x, y, rec
-        st = self._lib.osqp_hip_batch_solve(self._p, B, _ptr(q, _lib.c_double_p), _ptr(l, _lib.c_double_p), _ptr(u, _lib.c_double_p),
-                                            _ptr(x, _lib.c_double_p), _ptr(y, _lib.c_double_p), _ptr(rec, _lib.c_double_p), int(warm))
-        if st:
-            raise self._batch_error(st)
-        return x, y, rec
+        return self._lockstep_host(self._lib.osqp_hip_batch_solve, q, l, u, x0, y0, nbatch, Px, Ax, mat_entry=self._lib.osqp_hip_batch_solve_mat)
 
     def hip_batch_solve_device(self, nbatch, q_ptr, l_ptr, u_ptr, x_ptr, y_ptr, rec_ptr, warm=False, stream=None, Px_ptr=None, Ax_ptr=None):
         """osqp_hip_batch_solve_device: raw device addresses (int or None) of float64 arrays laid out as in hip_batch_solve;
@@ -440,43 +425,49 @@ class OSQPSolver:
         return self._lockstep_host(self._lib.osqp_hip_batch_solve_lockstep, q, l, u, x0, y0, nbatch, Px, Ax)
 
     def _lockstep_host(self, entry, q, l, u, x0, y0, nbatch, Px=None, Ax=None, mat_entry=None):
-        """The host-array call of a lockstep route (`entry`: its C entry point; `mat_entry`: the one that takes Px / Ax, the lockstep route's by default):
-        widths checked here, then the engine."""
+        """The host-array call of a batch solve, the one-launch route's or a lockstep route's (`entry`: its C entry point; `mat_entry`: the one that takes
+        Px / Ax, the lockstep route's by default): widths checked here, then the engine."""
         arrs = [a for a in (q, l, u, x0, y0, Px, Ax) if a is not None]
         B = int(nbatch) if nbatch is not None else int(np.asarray(arrs[0]).shape[0])
-
-        def rows(a, name, width):
-            a = np.ascontiguousarray(a, dtype=np.float64)
-            if a.size != B * width or (a.ndim > 1 and a.shape[-1] != width):
-                raise ValueError('%s: expected %d problems of width %d, got shape %s' % (name, B, width, a.shape))
-            return a.reshape(B, width)
-        q, l, u = (None if a is None else rows(a, name, w) for a, name, w in ((q, 'q', self.n), (l, 'l', self.m), (u, 'u', self.m)))
-        warm = x0 is not None or y0 is not None      # a missing one starts from zero, as in hip_batch_solve
-        x = np.zeros((B, self.n)) if x0 is None else rows(x0, 'x0', self.n).copy()
-        y = np.zeros((B, self.m)) if y0 is None else rows(y0, 'y0', self.m).copy()
+        q, l, u = _rows(q, 'q', B, self.n), _rows(l, 'l', B, self.m), _rows(u, 'u', B, self.m)
+        warm = x0 is not None or y0 is not None      # a missing one starts from zero, like warm_start(x=None) / (y=None) of a single solver
+        # (l, u are clamped to +-OSQP_INFTY inside the kernel, like interface.py:334-337)
+        x = np.zeros((B, self.n)) if x0 is None else _rows(x0, 'x0', B, self.n).copy()
+        y = np.zeros((B, self.m)) if y0 is None else _rows(y0, 'y0', B, self.m).copy()
         rec = np.zeros((B, self.BATCH_REC))
+        dp = _lib.c_double_p
+        args = (_ptr(q, dp), _ptr(l, dp), _ptr(u, dp), _ptr(x, dp), _ptr(y, dp), _ptr(rec, dp), int(warm))
         if Px is not None or Ax is not None:
-            Px, Ax = (None if a is None else rows(a, name, w) for a, name, w in ((Px, 'Px', self.nnz_P), (Ax, 'Ax', self.nnz_A)))
-            st = (mat_entry or self._lib.osqp_hip_batch_solve_lockstep_mat)(self._p, B, _ptr(Px, _lib.c_double_p), _ptr(Ax, _lib.c_double_p), _ptr(q, _lib.c_double_p),
-                                                                            _ptr(l, _lib.c_double_p), _ptr(u, _lib.c_double_p), _ptr(x, _lib.c_double_p), _ptr(y, _lib.c_double_p),
-                                                                            _ptr(rec, _lib.c_double_p), int(warm))
+            Px, Ax = _rows(Px, 'Px', B, self.nnz_P), _rows(Ax, 'Ax', B, self.nnz_A)
+            st = (mat_entry or self._lib.osqp_hip_batch_solve_lockstep_mat)(self._p, B, _ptr(Px, dp), _ptr(Ax, dp), *args)
         else:
-            st = entry(self._p, B, _ptr(q, _lib.c_double_p), _ptr(l, _lib.c_double_p), _ptr(u, _lib.c_double_p),
-                       _ptr(x, _lib.c_double_p), _ptr(y, _lib.c_double_p), _ptr(rec, _lib.c_double_p), int(warm))
+            st = entry(self._p, B, *args)
         if st:
             raise self._batch_error(st)
         return x, y, rec
+
+    def _device_call(self, stem, nbatch, Px_ptr, Ax_ptr, *args):
+        """The device-array call of a lockstep route: `<stem>_mat_device` when a matrix pointer is given, `<stem>_device` otherwise."""
+        if Px_ptr is not None or Ax_ptr is not None:
+            st = getattr(self._lib, stem + '_mat_device')(self._p, int(nbatch), Px_ptr, Ax_ptr, *args)
+        else:
+            st = getattr(self._lib, stem + '_device')(self._p, int(nbatch), *args)
+        if st:
+            raise self._batch_error(st)
+
+    def _last_record(self, entry_name, fields):
+        """One of the engine's *_last_record entries as a dict over `fields`: counts as int, timings and the reserved slot as float."""
+        rec = np.zeros(len(fields))
+        st = getattr(self._lib, entry_name)(self._p, _ptr(rec, _lib.c_double_p))
+        if st:
+            raise ValueError(str(int(st)))
+        return {k: v if k in ('gpu_ms', 'seconds', 'prepare_gpu_ms', 'reserved') else int(v) for k, v in zip(fields, rec.tolist())}
 
     def hip_batch_solve_lockstep_device(self, nbatch, q_ptr, l_ptr, u_ptr, x_ptr, y_ptr, rec_ptr, warm=False, stream=None, Px_ptr=None, Ax_ptr=None):
         """osqp_hip_batch_solve_lockstep_device: raw device addresses (int or None) laid out as in hip_batch_solve_lockstep; the work goes on `stream`
         (None: the solver's) and the call returns when the results are there.  nbatch == 0: does the route apply?
         Px_ptr / Ax_ptr: per-problem matrix values on the device (osqp_hip_batch_solve_lockstep_mat_device)."""
-        if Px_ptr is not None or Ax_ptr is not None:
-            st = self._lib.osqp_hip_batch_solve_lockstep_mat_device(self._p, int(nbatch), Px_ptr, Ax_ptr, q_ptr, l_ptr, u_ptr, x_ptr, y_ptr, rec_ptr, int(bool(warm)), stream)
-        else:
-            st = self._lib.osqp_hip_batch_solve_lockstep_device(self._p, int(nbatch), q_ptr, l_ptr, u_ptr, x_ptr, y_ptr, rec_ptr, int(bool(warm)), stream)
-        if st:
-            raise self._batch_error(st)
+        self._device_call('osqp_hip_batch_solve_lockstep', nbatch, Px_ptr, Ax_ptr, q_ptr, l_ptr, u_ptr, x_ptr, y_ptr, rec_ptr, int(bool(warm)), stream)
 
     # OSQP_HIP_LOCKSTEP_MAT_LAST_REC doubles of osqp_hip_lockstep_mat_last_record
     LOCKSTEP_MAT_LAST_FIELDS = ('chunks', 'width', 'admm_iters_max', 'pcg_iters', 'kernel_launches', 'gpu_ms', 'matrix_block_bytes', 'prepare_gpu_ms')
@@ -484,14 +475,7 @@ class OSQPSolver:
     def lockstep_mat_last_record(self):
         """osqp_hip_lockstep_mat_last_record as a dict (LOCKSTEP_MAT_LAST_FIELDS): what the last lockstep call with per-problem matrices of this handle
         did; zeros before the first."""
-        rec = np.zeros(len(self.LOCKSTEP_MAT_LAST_FIELDS))
-        st = self._lib.osqp_hip_lockstep_mat_last_record(self._p, _ptr(rec, _lib.c_double_p))
-        if st:
-            raise ValueError(str(int(st)))
-        out = dict(zip(self.LOCKSTEP_MAT_LAST_FIELDS, rec.tolist()))
-        for k in ('chunks', 'width', 'admm_iters_max', 'pcg_iters', 'kernel_launches', 'matrix_block_bytes'):
-            out[k] = int(out[k])
-        return out
+        return self._last_record('osqp_hip_lockstep_mat_last_record', self.LOCKSTEP_MAT_LAST_FIELDS)
 
     def lockstep_mat_scaling(self, b):
         """osqp_hip_lockstep_mat_scaling: (D, E, c) of problem b of the last chunk the last lockstep call with per-problem matrices processed, numbered
@@ -507,14 +491,7 @@ class OSQPSolver:
 
     def lockstep_last_record(self):
         """osqp_hip_lockstep_last_record as a dict (LOCKSTEP_LAST_FIELDS): what the last lockstep call of this handle did; zeros before the first."""
-        rec = np.zeros(len(self.LOCKSTEP_LAST_FIELDS))
-        st = self._lib.osqp_hip_lockstep_last_record(self._p, _ptr(rec, _lib.c_double_p))
-        if st:
-            raise ValueError(str(int(st)))
-        out = dict(zip(self.LOCKSTEP_LAST_FIELDS, rec.tolist()))
-        for k in ('chunks', 'width', 'admm_iters_max', 'pcg_iters', 'kernel_launches', 'workspace_bytes'):
-            out[k] = int(out[k])
-        return out
+        return self._last_record('osqp_hip_lockstep_last_record', self.LOCKSTEP_LAST_FIELDS)
 
     # OSQP_HIP_LOCKSTEP_POLISH_LAST_REC doubles of osqp_hip_lockstep_polish_last_record
     LOCKSTEP_POLISH_LAST_FIELDS = ('attempted', 'accepted', 'rejected', 'steps_max', 'pcg_iters', 'kernel_launches', 'gpu_ms', 'workspace_bytes')
@@ -522,14 +499,7 @@ class OSQPSolver:
     def lockstep_polish_last_record(self):
         """osqp_hip_lockstep_polish_last_record as a dict (LOCKSTEP_POLISH_LAST_FIELDS): the polish part of the last lockstep call of this handle
         (settings.polishing); zeros before the first call and after a call without polishing."""
-        rec = np.zeros(len(self.LOCKSTEP_POLISH_LAST_FIELDS))
-        st = self._lib.osqp_hip_lockstep_polish_last_record(self._p, _ptr(rec, _lib.c_double_p))
-        if st:
-            raise ValueError(str(int(st)))
-        out = dict(zip(self.LOCKSTEP_POLISH_LAST_FIELDS, rec.tolist()))
-        for k in ('attempted', 'accepted', 'rejected', 'steps_max', 'pcg_iters', 'kernel_launches', 'workspace_bytes'):
-            out[k] = int(out[k])
-        return out
+        return self._last_record('osqp_hip_lockstep_polish_last_record', self.LOCKSTEP_POLISH_LAST_FIELDS)
 
     def hip_batch_solve_lockstep_direct(self, q=None, l=None, u=None, x0=None, y0=None, nbatch=None, Px=None, Ax=None):
         """hip_batch_solve_lockstep for the handles it declines (osqp_hip_batch_solve_lockstep_direct): a Woodbury-corrected handle in the small mode
@@ -544,12 +514,7 @@ class OSQPSolver:
         """osqp_hip_batch_solve_lockstep_direct_device: raw device addresses (int or None) laid out as in hip_batch_solve_lockstep; the work goes on
         `stream` (None: the solver's) and the call returns when the results are there.  nbatch == 0: does the route apply?
         Px_ptr / Ax_ptr: per-problem matrix values on the device (osqp_hip_batch_solve_lockstep_direct_mat_device)."""
-        if Px_ptr is not None or Ax_ptr is not None:
-            st = self._lib.osqp_hip_batch_solve_lockstep_direct_mat_device(self._p, int(nbatch), Px_ptr, Ax_ptr, q_ptr, l_ptr, u_ptr, x_ptr, y_ptr, rec_ptr, int(bool(warm)), stream)
-        else:
-            st = self._lib.osqp_hip_batch_solve_lockstep_direct_device(self._p, int(nbatch), q_ptr, l_ptr, u_ptr, x_ptr, y_ptr, rec_ptr, int(bool(warm)), stream)
-        if st:
-            raise self._batch_error(st)
+        self._device_call('osqp_hip_batch_solve_lockstep_direct', nbatch, Px_ptr, Ax_ptr, q_ptr, l_ptr, u_ptr, x_ptr, y_ptr, rec_ptr, int(bool(warm)), stream)
 
     # OSQP_HIP_LOCKSTEP_DIRECT_MAT_LAST_REC doubles of osqp_hip_lockstep_direct_mat_last_record
     LOCKSTEP_DIRECT_MAT_LAST_FIELDS = ('chunks', 'width', 'admm_iters_max', 'factorisations', 'kernel_launches', 'gpu_ms', 'matrix_block_bytes', 'prepare_gpu_ms')
@@ -557,14 +522,7 @@ class OSQPSolver:
     def lockstep_direct_mat_last_record(self):
         """osqp_hip_lockstep_direct_mat_last_record as a dict (LOCKSTEP_DIRECT_MAT_LAST_FIELDS): what the last direct lockstep call with per-problem
         matrices of this handle did; zeros before the first."""
-        rec = np.zeros(len(self.LOCKSTEP_DIRECT_MAT_LAST_FIELDS))
-        st = self._lib.osqp_hip_lockstep_direct_mat_last_record(self._p, _ptr(rec, _lib.c_double_p))
-        if st:
-            raise ValueError(str(int(st)))
-        out = dict(zip(self.LOCKSTEP_DIRECT_MAT_LAST_FIELDS, rec.tolist()))
-        for k in ('chunks', 'width', 'admm_iters_max', 'factorisations', 'kernel_launches', 'matrix_block_bytes'):
-            out[k] = int(out[k])
-        return out
+        return self._last_record('osqp_hip_lockstep_direct_mat_last_record', self.LOCKSTEP_DIRECT_MAT_LAST_FIELDS)
 
     # OSQP_HIP_LOCKSTEP_DIRECT_LAST_REC doubles of osqp_hip_lockstep_direct_last_record
     LOCKSTEP_DIRECT_LAST_FIELDS = ('chunks', 'width', 'admm_iters_max', 'factorisations', 'kernel_launches', 'gpu_ms', 'workspace_bytes', 'seconds')
@@ -572,14 +530,7 @@ class OSQPSolver:
     def lockstep_direct_last_record(self):
         """osqp_hip_lockstep_direct_last_record as a dict (LOCKSTEP_DIRECT_LAST_FIELDS): what the last direct lockstep call of this handle did; zeros
         before the first."""
-        rec = np.zeros(len(self.LOCKSTEP_DIRECT_LAST_FIELDS))
-        st = self._lib.osqp_hip_lockstep_direct_last_record(self._p, _ptr(rec, _lib.c_double_p))
-        if st:
-            raise ValueError(str(int(st)))
-        out = dict(zip(self.LOCKSTEP_DIRECT_LAST_FIELDS, rec.tolist()))
-        for k in ('chunks', 'width', 'admm_iters_max', 'factorisations', 'kernel_launches', 'workspace_bytes'):
-            out[k] = int(out[k])
-        return out
+        return self._last_record('osqp_hip_lockstep_direct_last_record', self.LOCKSTEP_DIRECT_LAST_FIELDS)
 
     ADJOINT_FIELDS = ('status', 'active_rows', 'residual', 'reserved')
     ADJOINT_REC = len(ADJOINT_FIELDS)    # OSQP_HIP_ADJOINT_REC
@@ -592,16 +543,8 @@ class OSQPSolver:
         dl, du (B, m) -- and 'rec' (B, ADJOINT_REC) with columns ADJOINT_FIELDS."""
         x = np.ascontiguousarray(x, dtype=np.float64)
         B = 1 if x.ndim == 1 else int(x.shape[0])
-
-        def rows(a, name, width):
-            if a is None:
-                return None
-            a = np.ascontiguousarray(a, dtype=np.float64)
-            if a.size != B * width or (a.ndim > 1 and a.shape[-1] != width):
-                raise ValueError('%s: expected %d problems of width %d, got shape %s' % (name, B, width, a.shape))
-            return a.reshape(B, width)
-        x, y, dx, dy, l, u = (rows(a, nm, w) for a, nm, w in ((x, 'x', self.n), (y, 'y', self.m), (dx, 'dx', self.n), (dy, 'dy', self.m), (l, 'l', self.m), (u, 'u', self.m)))
-        Px, Ax = rows(Px, 'Px', self.nnz_P), rows(Ax, 'Ax', self.nnz_A)
+        x, y, dx, dy, l, u = (_rows(a, nm, B, w) for a, nm, w in ((x, 'x', self.n), (y, 'y', self.m), (dx, 'dx', self.n), (dy, 'dy', self.m), (l, 'l', self.m), (u, 'u', self.m)))
+        Px, Ax = _rows(Px, 'Px', B, self.nnz_P), _rows(Ax, 'Ax', B, self.nnz_A)
         if x is None or y is None or dx is None:
             raise ValueError('x, y and dx are required')
         widths = {'dP': self.nnz_P, 'dq': self.n, 'dA': self.nnz_A, 'dl': self.m, 'du': self.m}
@@ -642,22 +585,14 @@ class OSQPSolver:
             raise ValueError('x, y and dx are required')
         x = np.ascontiguousarray(x, dtype=np.float64)
         B = 1 if x.ndim == 1 else int(x.shape[0])
-
-        def rows(a, name, width):
-            if a is None:
-                return None
-            a = np.ascontiguousarray(a, dtype=np.float64)
-            if a.size != B * width or (a.ndim > 1 and a.shape[-1] != width):
-                raise ValueError('%s: expected %d problems of width %d, got shape %s' % (name, B, width, a.shape))
-            return a.reshape(B, width)
-        x, y, dx, dy, l, u = (rows(a, nm, w) for a, nm, w in ((x, 'x', self.n), (y, 'y', self.m), (dx, 'dx', self.n), (dy, 'dy', self.m), (l, 'l', self.m), (u, 'u', self.m)))
+        x, y, dx, dy, l, u = (_rows(a, nm, B, w) for a, nm, w in ((x, 'x', self.n), (y, 'y', self.m), (dx, 'dx', self.n), (dy, 'dy', self.m), (l, 'l', self.m), (u, 'u', self.m)))
         widths = {'dP': self.nnz_P, 'dq': self.n, 'dA': self.nnz_A, 'dl': self.m, 'du': self.m}
         out = {k: (np.zeros((B, widths[k])) if k in want else None) for k in widths}
         rec = np.zeros((B, self.ADJOINT_REC))
         dp = _lib.c_double_p
         outs = (_ptr(out['dP'], dp), _ptr(out['dq'], dp), _ptr(out['dA'], dp), _ptr(out['dl'], dp), _ptr(out['du'], dp), _ptr(rec, dp))
         if Px is not None or Ax is not None:
-            Px, Ax = rows(Px, 'Px', self.nnz_P), rows(Ax, 'Ax', self.nnz_A)
+            Px, Ax = _rows(Px, 'Px', B, self.nnz_P), _rows(Ax, 'Ax', B, self.nnz_A)
             st = (mat_entry or self._lib.osqp_hip_batch_adjoint_lockstep_mat)(self._p, B, _ptr(Px, dp), _ptr(Ax, dp), _ptr(l, dp), _ptr(u, dp), _ptr(x, dp), _ptr(y, dp),
                                                                               _ptr(dx, dp), _ptr(dy, dp), *outs)
         else:
@@ -673,14 +608,7 @@ class OSQPSolver:
         """osqp_hip_batch_adjoint_lockstep_device: raw device addresses (int or None) laid out as in hip_batch_adjoint_lockstep; the work goes on `stream`
         (None: the solver's) and the call returns when the results are there.  nbatch == 0: does the route apply?
         Px_ptr / Ax_ptr: per-problem matrix values on the device (osqp_hip_batch_adjoint_lockstep_mat_device)."""
-        if Px_ptr is not None or Ax_ptr is not None:
-            st = self._lib.osqp_hip_batch_adjoint_lockstep_mat_device(self._p, int(nbatch), Px_ptr, Ax_ptr, l_ptr, u_ptr, x_ptr, y_ptr, dx_ptr, dy_ptr,
-                                                                      dP_ptr, dq_ptr, dA_ptr, dl_ptr, du_ptr, rec_ptr, stream)
-        else:
-            st = self._lib.osqp_hip_batch_adjoint_lockstep_device(self._p, int(nbatch), l_ptr, u_ptr, x_ptr, y_ptr, dx_ptr, dy_ptr,
-                                                                  dP_ptr, dq_ptr, dA_ptr, dl_ptr, du_ptr, rec_ptr, stream)
-        if st:
-            raise self._batch_error(st)
+        self._device_call('osqp_hip_batch_adjoint_lockstep', nbatch, Px_ptr, Ax_ptr, l_ptr, u_ptr, x_ptr, y_ptr, dx_ptr, dy_ptr, dP_ptr, dq_ptr, dA_ptr, dl_ptr, du_ptr, rec_ptr, stream)
 
     # OSQP_HIP_LOCKSTEP_MAT_ADJOINT_LAST_REC doubles of osqp_hip_lockstep_mat_adjoint_last_record
     LOCKSTEP_MAT_ADJOINT_LAST_FIELDS = ('chunks', 'width', 'steps_max', 'pcg_iters', 'kernel_launches', 'gpu_ms', 'matrix_block_bytes', 'prepare_gpu_ms')
@@ -688,28 +616,14 @@ class OSQPSolver:
     def lockstep_mat_adjoint_last_record(self):
         """osqp_hip_lockstep_mat_adjoint_last_record as a dict (LOCKSTEP_MAT_ADJOINT_LAST_FIELDS): what the last lockstep adjoint call with per-problem
         matrices of this handle did; zeros before the first."""
-        rec = np.zeros(len(self.LOCKSTEP_MAT_ADJOINT_LAST_FIELDS))
-        st = self._lib.osqp_hip_lockstep_mat_adjoint_last_record(self._p, _ptr(rec, _lib.c_double_p))
-        if st:
-            raise ValueError(str(int(st)))
-        out = dict(zip(self.LOCKSTEP_MAT_ADJOINT_LAST_FIELDS, rec.tolist()))
-        for k in ('chunks', 'width', 'steps_max', 'pcg_iters', 'kernel_launches', 'matrix_block_bytes'):
-            out[k] = int(out[k])
-        return out
+        return self._last_record('osqp_hip_lockstep_mat_adjoint_last_record', self.LOCKSTEP_MAT_ADJOINT_LAST_FIELDS)
 
     # OSQP_HIP_LOCKSTEP_ADJOINT_LAST_REC doubles of osqp_hip_lockstep_adjoint_last_record
     LOCKSTEP_ADJOINT_LAST_FIELDS = ('chunks', 'width', 'steps_max', 'pcg_iters', 'kernel_launches', 'gpu_ms', 'workspace_bytes', 'reserved')
 
     def lockstep_adjoint_last_record(self):
         """osqp_hip_lockstep_adjoint_last_record as a dict (LOCKSTEP_ADJOINT_LAST_FIELDS): what the last lockstep adjoint call of this handle did; zeros before the first."""
-        rec = np.zeros(len(self.LOCKSTEP_ADJOINT_LAST_FIELDS))
-        st = self._lib.osqp_hip_lockstep_adjoint_last_record(self._p, _ptr(rec, _lib.c_double_p))
-        if st:
-            raise ValueError(str(int(st)))
-        out = dict(zip(self.LOCKSTEP_ADJOINT_LAST_FIELDS, rec.tolist()))
-        for k in ('chunks', 'width', 'steps_max', 'pcg_iters', 'kernel_launches', 'workspace_bytes'):
-            out[k] = int(out[k])
-        return out
+        return self._last_record('osqp_hip_lockstep_adjoint_last_record', self.LOCKSTEP_ADJOINT_LAST_FIELDS)
 
     def hip_batch_adjoint_lockstep_direct(self, x, y, dx, dy=None, l=None, u=None, want=('dP', 'dq', 'dA', 'dl', 'du'), Px=None, Ax=None):
         """hip_batch_adjoint_lockstep for the handles it declines (osqp_hip_batch_adjoint_lockstep_direct): the backward pass of
@@ -726,14 +640,7 @@ class OSQPSolver:
         """osqp_hip_batch_adjoint_lockstep_direct_device: raw device addresses (int or None) laid out as in hip_batch_adjoint_lockstep; the work goes on
         `stream` (None: the solver's) and the call returns when the results are there.  nbatch == 0: does the route apply?
         Px_ptr / Ax_ptr: per-problem matrix values on the device (osqp_hip_batch_adjoint_lockstep_direct_mat_device)."""
-        if Px_ptr is not None or Ax_ptr is not None:
-            st = self._lib.osqp_hip_batch_adjoint_lockstep_direct_mat_device(self._p, int(nbatch), Px_ptr, Ax_ptr, l_ptr, u_ptr, x_ptr, y_ptr, dx_ptr, dy_ptr,
-                                                                             dP_ptr, dq_ptr, dA_ptr, dl_ptr, du_ptr, rec_ptr, stream)
-        else:
-            st = self._lib.osqp_hip_batch_adjoint_lockstep_direct_device(self._p, int(nbatch), l_ptr, u_ptr, x_ptr, y_ptr, dx_ptr, dy_ptr,
-                                                                         dP_ptr, dq_ptr, dA_ptr, dl_ptr, du_ptr, rec_ptr, stream)
-        if st:
-            raise self._batch_error(st)
+        self._device_call('osqp_hip_batch_adjoint_lockstep_direct', nbatch, Px_ptr, Ax_ptr, l_ptr, u_ptr, x_ptr, y_ptr, dx_ptr, dy_ptr, dP_ptr, dq_ptr, dA_ptr, dl_ptr, du_ptr, rec_ptr, stream)
 
     # OSQP_HIP_LOCKSTEP_DIRECT_MAT_ADJOINT_LAST_REC doubles of osqp_hip_lockstep_direct_mat_adjoint_last_record
     LOCKSTEP_DIRECT_MAT_ADJOINT_LAST_FIELDS = ('chunks', 'width', 'steps_max', 'inversions', 'kernel_launches', 'gpu_ms', 'matrix_block_bytes', 'prepare_gpu_ms')
@@ -741,14 +648,7 @@ class OSQPSolver:
     def lockstep_direct_mat_adjoint_last_record(self):
         """osqp_hip_lockstep_direct_mat_adjoint_last_record as a dict (LOCKSTEP_DIRECT_MAT_ADJOINT_LAST_FIELDS): what the last direct lockstep adjoint
         call with per-problem matrices of this handle did; zeros before the first."""
-        rec = np.zeros(len(self.LOCKSTEP_DIRECT_MAT_ADJOINT_LAST_FIELDS))
-        st = self._lib.osqp_hip_lockstep_direct_mat_adjoint_last_record(self._p, _ptr(rec, _lib.c_double_p))
-        if st:
-            raise ValueError(str(int(st)))
-        out = dict(zip(self.LOCKSTEP_DIRECT_MAT_ADJOINT_LAST_FIELDS, rec.tolist()))
-        for k in ('chunks', 'width', 'steps_max', 'inversions', 'kernel_launches', 'matrix_block_bytes'):
-            out[k] = int(out[k])
-        return out
+        return self._last_record('osqp_hip_lockstep_direct_mat_adjoint_last_record', self.LOCKSTEP_DIRECT_MAT_ADJOINT_LAST_FIELDS)
 
     # OSQP_HIP_LOCKSTEP_DIRECT_ADJOINT_LAST_REC doubles of osqp_hip_lockstep_direct_adjoint_last_record
     LOCKSTEP_DIRECT_ADJOINT_LAST_FIELDS = ('chunks', 'width', 'steps_max', 'inversions', 'kernel_launches', 'gpu_ms', 'workspace_bytes', 'reserved')
@@ -756,14 +656,7 @@ class OSQPSolver:
     def lockstep_direct_adjoint_last_record(self):
         """osqp_hip_lockstep_direct_adjoint_last_record as a dict (LOCKSTEP_DIRECT_ADJOINT_LAST_FIELDS): what the last direct lockstep adjoint call of this
         handle did; zeros before the first."""
-        rec = np.zeros(len(self.LOCKSTEP_DIRECT_ADJOINT_LAST_FIELDS))
-        st = self._lib.osqp_hip_lockstep_direct_adjoint_last_record(self._p, _ptr(rec, _lib.c_double_p))
-        if st:
-            raise ValueError(str(int(st)))
-        out = dict(zip(self.LOCKSTEP_DIRECT_ADJOINT_LAST_FIELDS, rec.tolist()))
-        for k in ('chunks', 'width', 'steps_max', 'inversions', 'kernel_launches', 'workspace_bytes'):
-            out[k] = int(out[k])
-        return out
+        return self._last_record('osqp_hip_lockstep_direct_adjoint_last_record', self.LOCKSTEP_DIRECT_ADJOINT_LAST_FIELDS)
 
     def _batch_error(self, st):
         """ValueError(str(code)) as the pybind layer raises for a failed call (callers compare str(e) with the code); `.reason` says why

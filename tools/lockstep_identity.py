@@ -1,11 +1,15 @@
 #!/usr/bin/env python3
 """Bit identity of the lockstep routes between two builds of the engine: what a change of the host drivers (lockstep_hip.hip's chunk functions,
-Engine::run_lockstep*) must leave exactly as it was.
+Engine::run_lockstep_solve / run_lockstep_adjoint and the entry points over them) must leave exactly as it was.
 
 --dump FILE runs, with fixed seeds and no time limit, on problems.banded_qp(400, window=40) at B = 70 and eps 1e-8 (one full chunk and a ragged one):
 the forward route, the forward with polishing, the forward with per-element Px / Ax (and that with polishing: its ADMM part, the polished result, and
-the same handle with polishing switched off), the adjoint; on problems.portfolio_qp(200, 10) and (600, 4) at
-B = 70: the direct forward and the direct adjoint (a handle the direct route declines -- (200, 10): no dense row -- is kept as its return code); and the m = 0 tridiagonal case at n = 900, B = 3, with polish.  Every returned array and every *_last_record
+the same handle with polishing switched off), the adjoint, the adjoint with per-element Px / Ax; on problems.portfolio_qp(200, 10) and (600, 4) at
+B = 70: the direct forward and the direct adjoint, both also with per-element Px / Ax drawn as tests/test_gpu_lockstep_direct_mat.py draws them (a handle
+the direct route declines -- (200, 10): no dense row -- is kept as its return code); and the m = 0 tridiagonal case at n = 900, B = 3, with polish.  On both
+routes there is one forward call each with only Px and only Ax, and every case above is run again through its *_device entry, the same inputs as torch
+tensors on torch's current stream (tags <tag>_dev).  A call with per-element matrices is kept with its own record and its route's base record
+(<tag>_base).  The tool's Python is the same text for both dumps: the C ABI is what two builds share.  Every returned array and every *_last_record
 field except the timings goes into an .npz.  --compare A B exits non-zero unless every array is equal (NaNs in the same places) and every record field
 is equal: kernel launches, iteration / step counts, PCG iterations, inversions, polish counts, workspace bytes.  --feature TAG ..: entries under these
 tags are what build B is meant to change (mat_polish, when A is a build from before polish reached the per-element-matrix entry); they are printed with
@@ -59,6 +63,32 @@ def dump(path):
         rec = rec.copy(); rec[:, REC_SECONDS] = 0.0          # (wall time of the polish)
         return dict(x=x, y=y, rec=rec)
 
+    # the *_device entries: the same inputs as torch ROCm tensors, the work on torch's current stream (None stays None: the handle's own values)
+    def dev(*arrays):
+        import torch
+        return [None if a is None else torch.tensor(np.ascontiguousarray(a), dtype=torch.float64, device='cuda') for a in arrays]
+
+    def ptr(t):
+        return None if t is None else t.data_ptr()
+
+    def stream():
+        import torch
+        return torch.cuda.current_stream().cuda_stream
+
+    def fwd_dev(entry, e, nb, q=None, l=None, u=None, Px=None, Ax=None):
+        q, l, u, Px, Ax = dev(q, l, u, Px, Ax)
+        x, y, rec = dev(np.zeros((nb, e.n)), np.zeros((nb, e.m)), np.zeros((nb, e.BATCH_REC)))
+        entry(nb, ptr(q), ptr(l), ptr(u), ptr(x), ptr(y), ptr(rec), warm=False, stream=stream(), Px_ptr=ptr(Px), Ax_ptr=ptr(Ax))
+        return fwd(*(t.cpu().numpy() for t in (x, y, rec)))
+
+    def adj_dev(entry, e, x, y, dx, dy=None, l=None, u=None, Px=None, Ax=None):
+        nb = x.shape[0]
+        x, y, dx, dy, l, u, Px, Ax = dev(x, y, dx, dy, l, u, Px, Ax)
+        names = ('dP', 'dq', 'dA', 'dl', 'du', 'rec')
+        outs = dev(*(np.zeros((nb, w)) for w in (e.nnz_P, e.n, e.nnz_A, e.m, e.m, e.ADJOINT_REC)))
+        entry(nb, ptr(x), ptr(y), ptr(dx), ptr(dy), ptr(l), ptr(u), *(ptr(t) for t in outs), stream=stream(), Px_ptr=ptr(Px), Ax_ptr=ptr(Ax))
+        return {k: t.cpu().numpy() for k, t in zip(names, outs)}
+
     B = 70
     P, q, A, l, u = problems.banded_qp(400, window=40)
     A = sp.csc_matrix(A); A.sort_indices()
@@ -72,6 +102,17 @@ def dump(path):
     xm, ym, recm = e.hip_batch_solve_lockstep(q=Q, l=L, u=U, Px=Px, Ax=Ax)
     keep('mat', fwd(xm, ym, recm), e.lockstep_mat_last_record())
     keep('mat_base', {}, e.lockstep_last_record())
+    dxm = xm - 0.1 * np.random.default_rng(2).standard_normal(xm.shape)
+    keep('mat_adjoint', e.hip_batch_adjoint_lockstep(xm, ym, dxm, dy, l=L, u=U, Px=Px, Ax=Ax), e.lockstep_mat_adjoint_last_record())
+    keep('mat_adjoint_base', {}, e.lockstep_adjoint_last_record())
+    for tag, kw in (('mat_px_only', dict(Px=Px)), ('mat_ax_only', dict(Ax=Ax))):        # one-sided: the other side is the handle's own values
+        keep(tag, fwd(*e.hip_batch_solve_lockstep(q=Q, l=L, u=U, **kw)), e.lockstep_mat_last_record())
+    keep('forward_dev', fwd_dev(e.hip_batch_solve_lockstep_device, e, B, Q, L, U), e.lockstep_last_record())
+    keep('adjoint_dev', adj_dev(e.hip_batch_adjoint_lockstep_device, e, x, y, dx, dy, L, U), e.lockstep_adjoint_last_record())
+    keep('mat_dev', fwd_dev(e.hip_batch_solve_lockstep_device, e, B, Q, L, U, Px, Ax), e.lockstep_mat_last_record())
+    keep('mat_dev_base', {}, e.lockstep_last_record())
+    keep('mat_adjoint_dev', adj_dev(e.hip_batch_adjoint_lockstep_device, e, xm, ym, dxm, dy, L, U, Px, Ax), e.lockstep_mat_adjoint_last_record())
+    keep('mat_adjoint_dev_base', {}, e.lockstep_adjoint_last_record())
     so = outer(P, q, A, l, u, polishing=True)
     e = so._solver
     keep('polish', fwd(*e.hip_batch_solve_lockstep(q=Q, l=L, u=U)), e.lockstep_last_record())
@@ -104,6 +145,26 @@ def dump(path):
         keep(tag, fwd(x, y, rec), e.lockstep_direct_last_record())
         dx = x - 0.1 * np.random.default_rng(2).standard_normal(x.shape)
         keep(tag + '_adjoint', e.hip_batch_adjoint_lockstep_direct(x, y, dx), e.lockstep_direct_adjoint_last_record())
+        # per-element Px / Ax as tests/test_gpu_lockstep_direct_mat.py builds them: Ax first, then Px, from one default_rng(3)
+        Pt, Ac = sp.csc_matrix(sp.triu(P)), sp.csc_matrix(A)
+        Pt.sort_indices(); Ac.sort_indices()
+        rng = np.random.default_rng(3)
+        Ax = Ac.data * (1.0 + 0.1 * rng.standard_normal((B, Ac.nnz)))
+        Px = Pt.data * (1.0 + 0.2 * rng.random((B, Pt.nnz)))
+        xm, ym, recm = e.hip_batch_solve_lockstep_direct(q=Q, Px=Px, Ax=Ax)
+        keep(tag + '_mat', fwd(xm, ym, recm), e.lockstep_direct_mat_last_record())
+        keep(tag + '_mat_base', {}, e.lockstep_direct_last_record())
+        dxm = xm - 0.1 * np.random.default_rng(2).standard_normal(xm.shape)
+        keep(tag + '_mat_adjoint', e.hip_batch_adjoint_lockstep_direct(xm, ym, dxm, Px=Px, Ax=Ax), e.lockstep_direct_mat_adjoint_last_record())
+        keep(tag + '_mat_adjoint_base', {}, e.lockstep_direct_adjoint_last_record())
+        for side, kw in (('_mat_px_only', dict(Px=Px)), ('_mat_ax_only', dict(Ax=Ax))):
+            keep(tag + side, fwd(*e.hip_batch_solve_lockstep_direct(q=Q, **kw)), e.lockstep_direct_mat_last_record())
+        keep(tag + '_dev', fwd_dev(e.hip_batch_solve_lockstep_direct_device, e, B, Q), e.lockstep_direct_last_record())
+        keep(tag + '_adjoint_dev', adj_dev(e.hip_batch_adjoint_lockstep_direct_device, e, x, y, dx), e.lockstep_direct_adjoint_last_record())
+        keep(tag + '_mat_dev', fwd_dev(e.hip_batch_solve_lockstep_direct_device, e, B, Q, Px=Px, Ax=Ax), e.lockstep_direct_mat_last_record())
+        keep(tag + '_mat_dev_base', {}, e.lockstep_direct_last_record())
+        keep(tag + '_mat_adjoint_dev', adj_dev(e.hip_batch_adjoint_lockstep_direct_device, e, xm, ym, dxm, Px=Px, Ax=Ax), e.lockstep_direct_mat_adjoint_last_record())
+        keep(tag + '_mat_adjoint_dev_base', {}, e.lockstep_direct_adjoint_last_record())
 
     n = 900
     rng = np.random.default_rng(3)
