@@ -541,23 +541,7 @@ class OSQPSolver:
         l / u (B, m), Px (B, nnz(triu P)), Ax (B, nnz(A)): what the batch was solved with, None = this solver's own values.
         Returns a dict with the arrays named in `want` -- dP (B, nnz(triu P)) and dA (B, nnz(A)) in the CSC order given at setup, dq (B, n),
         dl, du (B, m) -- and 'rec' (B, ADJOINT_REC) with columns ADJOINT_FIELDS."""
-        x = np.ascontiguousarray(x, dtype=np.float64)
-        B = 1 if x.ndim == 1 else int(x.shape[0])
-        x, y, dx, dy, l, u = (_rows(a, nm, B, w) for a, nm, w in ((x, 'x', self.n), (y, 'y', self.m), (dx, 'dx', self.n), (dy, 'dy', self.m), (l, 'l', self.m), (u, 'u', self.m)))
-        Px, Ax = _rows(Px, 'Px', B, self.nnz_P), _rows(Ax, 'Ax', B, self.nnz_A)
-        if x is None or y is None or dx is None:
-            raise ValueError('x, y and dx are required')
-        widths = {'dP': self.nnz_P, 'dq': self.n, 'dA': self.nnz_A, 'dl': self.m, 'du': self.m}
-        out = {k: (np.zeros((B, widths[k])) if k in want else None) for k in widths}
-        rec = np.zeros((B, self.ADJOINT_REC))
-        dp = _lib.c_double_p
-        st = self._lib.osqp_hip_batch_adjoint(self._p, B, _ptr(Px, dp), _ptr(Ax, dp), _ptr(l, dp), _ptr(u, dp), _ptr(x, dp), _ptr(y, dp), _ptr(dx, dp), _ptr(dy, dp),
-                                              _ptr(out['dP'], dp), _ptr(out['dq'], dp), _ptr(out['dA'], dp), _ptr(out['dl'], dp), _ptr(out['du'], dp), _ptr(rec, dp))
-        if st:
-            raise self._batch_error(st)
-        res = {k: v for k, v in out.items() if v is not None}
-        res['rec'] = rec
-        return res
+        return self._adjoint_host(self._lib.osqp_hip_batch_adjoint, x, y, dx, dy, l, u, want, Px, Ax, always_mat=True)
 
     def hip_batch_adjoint_device(self, nbatch, x_ptr, y_ptr, dx_ptr, dy_ptr=None, l_ptr=None, u_ptr=None, Px_ptr=None, Ax_ptr=None,
                                  dP_ptr=None, dq_ptr=None, dA_ptr=None, dl_ptr=None, du_ptr=None, rec_ptr=None, stream=None):
@@ -576,11 +560,11 @@ class OSQPSolver:
         LOCKSTEP_ADJOINT_FIELDS.
         Px (B, nnz(triu P)) / Ax (B, nnz(A)): per-problem matrix values in the CSC order given at setup (osqp_hip_batch_adjoint_lockstep_mat): every
         problem's adjoint system on its own matrices and scaling -- the backward of hip_batch_solve_lockstep(Px=, Ax=) (lockstep_mat_adjoint_last_record)."""
-        return self._adjoint_lockstep_host(self._lib.osqp_hip_batch_adjoint_lockstep, x, y, dx, dy, l, u, want, Px, Ax)
+        return self._adjoint_host(self._lib.osqp_hip_batch_adjoint_lockstep, x, y, dx, dy, l, u, want, Px, Ax)
 
-    def _adjoint_lockstep_host(self, entry, x, y, dx, dy, l, u, want, Px=None, Ax=None, mat_entry=None):
-        """The host-array call of a lockstep adjoint route (`entry`: its C entry point; `mat_entry`: the one with per-problem matrices, None: the PCG
-        route's): widths checked here, then the engine."""
+    def _adjoint_host(self, entry, x, y, dx, dy, l, u, want, Px=None, Ax=None, mat_entry=None, always_mat=False):
+        """The host-array call of a batch adjoint, the one-launch route's or a lockstep route's (`entry`: its C entry point; `mat_entry`: the one with
+        per-problem matrices, None: the PCG route's; `always_mat`: `entry` itself takes Px / Ax, given or not): widths checked here, then the engine."""
         if x is None or y is None or dx is None:
             raise ValueError('x, y and dx are required')
         x = np.ascontiguousarray(x, dtype=np.float64)
@@ -591,9 +575,9 @@ class OSQPSolver:
         rec = np.zeros((B, self.ADJOINT_REC))
         dp = _lib.c_double_p
         outs = (_ptr(out['dP'], dp), _ptr(out['dq'], dp), _ptr(out['dA'], dp), _ptr(out['dl'], dp), _ptr(out['du'], dp), _ptr(rec, dp))
-        if Px is not None or Ax is not None:
+        if always_mat or Px is not None or Ax is not None:
             Px, Ax = _rows(Px, 'Px', B, self.nnz_P), _rows(Ax, 'Ax', B, self.nnz_A)
-            st = (mat_entry or self._lib.osqp_hip_batch_adjoint_lockstep_mat)(self._p, B, _ptr(Px, dp), _ptr(Ax, dp), _ptr(l, dp), _ptr(u, dp), _ptr(x, dp), _ptr(y, dp),
+            st = (entry if always_mat else mat_entry or self._lib.osqp_hip_batch_adjoint_lockstep_mat)(self._p, B, _ptr(Px, dp), _ptr(Ax, dp), _ptr(l, dp), _ptr(u, dp), _ptr(x, dp), _ptr(y, dp),
                                                                               _ptr(dx, dp), _ptr(dy, dp), *outs)
         else:
             st = entry(self._p, B, _ptr(l, dp), _ptr(u, dp), _ptr(x, dp), _ptr(y, dp), _ptr(dx, dp), _ptr(dy, dp), *outs)
@@ -632,8 +616,8 @@ class OSQPSolver:
         Px (B, nnz(triu P)) / Ax (B, nnz(A)): per-problem matrix values in the CSC order given at setup (osqp_hip_batch_adjoint_lockstep_direct_mat): every
         problem's adjoint system on its own matrices, dense rows and scaling -- the backward of hip_batch_solve_lockstep_direct(Px=, Ax=)
         (lockstep_direct_mat_adjoint_last_record)."""
-        return self._adjoint_lockstep_host(self._lib.osqp_hip_batch_adjoint_lockstep_direct, x, y, dx, dy, l, u, want, Px, Ax,
-                                           mat_entry=self._lib.osqp_hip_batch_adjoint_lockstep_direct_mat)
+        return self._adjoint_host(self._lib.osqp_hip_batch_adjoint_lockstep_direct, x, y, dx, dy, l, u, want, Px, Ax,
+                                  mat_entry=self._lib.osqp_hip_batch_adjoint_lockstep_direct_mat)
 
     def hip_batch_adjoint_lockstep_direct_device(self, nbatch, x_ptr, y_ptr, dx_ptr, dy_ptr=None, l_ptr=None, u_ptr=None,
                                                  dP_ptr=None, dq_ptr=None, dA_ptr=None, dl_ptr=None, du_ptr=None, rec_ptr=None, stream=None, Px_ptr=None, Ax_ptr=None):

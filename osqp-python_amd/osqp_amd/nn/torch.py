@@ -1,58 +1,44 @@
-"""Forward pass of the reference's torch layer (/root/reference/src/osqp/nn/torch.py:22-230) on the MI355X engine.
+"""The reference's torch layer (/root/reference/src/osqp/nn/torch.py:22-290) on the MI355X engine.
 
-The reference keeps one ``osqp.OSQP`` object per batch element alive ACROSS forward calls -- the first call sets them up, every
-later call only ``update()``s and ``solve()``s them (nn/torch.py:113-140, 200-224) -- and fans the elements out over joblib
-threads.  Here one persistent engine handle plays that role:
+The reference keeps one ``osqp.OSQP`` object per batch element alive across forward calls (nn/torch.py:113-140, 200-224) and fans the elements out
+over joblib threads.  Here ONE persistent engine handle plays that role: set up once (``setup_count``), afterwards only ``update()``d when the matrix
+values change, and a forward or a backward is one call of a batch entry of that handle wherever one takes the problem.  Which entry is the route table
+below, and ``_FORWARD`` / ``_BACKWARD`` are that table as data: ``_walk`` tries the entries of a row in order.  NI: the entry raised ValueError with the
+engine's not-implemented code (the problem does not fit one workgroup, or the handle is not on that route); any other error of an entry comes out as it is.
 
-  * P_val and A_val shared by the whole batch (1-D tensors): the handle is set up ONCE (``setup_count`` counts it); later
-    forwards re-upload the matrix values only if they changed (``osqp_update_data_mat``: device-side re-assembly) and solve
-    the whole batch with ONE kernel launch (one workgroup per problem: the reference's update(q,l,u)+solve() per element).
-    q / l / u that live on the GPU (torch ROCm tensors) are handed over ZERO-COPY by device pointer on torch's current
-    stream (``osqp_hip_batch_solve_device``) and the solution is produced on the device;
-  * with ``torch.distributed`` initialised (world size > 1) the batch is block-partitioned over the ranks, every rank solves its
-    share on its own GPU, and the rows are all-gathered (``osqp_amd.sharded``) -- the multi-GPU form of the reference's thread pool;
-  * per-element P_val / A_val (2-D tensors, :128-157, 184-217): the SAME single launch -- every workgroup reads its own element's matrix values, assembled
-    and equilibrated per element by a launch in front of it (osqp_hip_batch_solve_mat); only a problem too large for one workgroup falls back to the
-    single-QP handle, one element after the other -- or, with ``large_batch='lockstep'``, goes to the lockstep route (osqp_hip_batch_solve_lockstep:
-    64 problems at a time on block vectors, any size; host tensors through the host entry, ROCm tensors zero-copy through the device entry), or, with
-    ``large_batch='lockstep_direct'``, to its direct form for a Woodbury handle with a diagonal K0 (osqp_hip_batch_solve_lockstep_direct: the
-    factor-model portfolio QP, which the lockstep route declines); a handle the chosen route declines raises as ``'lockstep'`` always has.
-    With ``large_batch='lockstep'`` (one rank) a forward with 2-D P_val and / or A_val that the single launch declines makes ONE call of the lockstep
-    route with per-element matrices (osqp_hip_batch_solve_lockstep_mat; ``mat_lockstep_launches`` counts them) in place of the per-element loop; its
-    backward is the per-element loop unless ``large_backward='lockstep'`` (below).
-    With ``large_batch='lockstep_direct'`` (one rank) such a forward on a Woodbury handle with a diagonal K0 makes ONE call of the direct route with per-element
-    matrices (osqp_hip_batch_solve_lockstep_direct_mat: every element scaled and solved on its own P_val / A_val; ``mat_lockstep_direct_launches`` counts
-    them; host and ROCm tensors alike through the host entry); a handle that entry declines goes on to the per-element loop as before.  The backward of such a
-    forward is the per-element loop, which raises NotImplementedError on a Woodbury handle, unless ``large_backward='lockstep_direct'`` (below).
-  * ``polishing=True`` (default False: every forward as before) is passed to ``setup``: the handle polishes every solved problem, on whichever route the
-    forward takes -- the one-workgroup kernel, the per-element loop, the lockstep route with shared or with per-element matrices (there the polish runs
-    on the device inside the one call; ``lockstep_polish_last_record`` of the handle counts attempted / accepted / rejected).  The adjoint classifies the
-    active rows from (x, y), and a polished point gives a clean active set.  With ``large_batch='lockstep_direct'`` the route does not polish.
+Forward (nn/torch.py:113-230), one rank.  P_val and A_val 1-D: shared by the batch; 2-D: per element (:128-157, 184-217).
 
-Like the reference, a batch element that is not solved raises RuntimeError (:158-162).
+  matrices     q, l, u        entries tried in order, by ``large_batch``                                                  counter
+  shared       host arrays    hip_batch_solve; on NI 'loop': _loop | 'lockstep': hip_batch_solve_lockstep (NI raises)      none
+                              | 'lockstep_direct': hip_batch_solve_lockstep_direct (NI raises)
+  shared       ROCm tensors   hip_batch_solve_device (zero-copy, torch's current stream); on NI 'loop': the row above,     none
+                              which asks hip_batch_solve again | 'lockstep': hip_batch_solve_lockstep_device (NI raises)
+                              | 'lockstep_direct': hip_batch_solve_lockstep_direct_device (NI raises)
+  per element  either, as     hip_batch_solve(Px, Ax);                                                                     mat_batch_launches
+               host arrays    on NI 'loop': _loop                                                                          none
+                              | 'lockstep': hip_batch_solve_lockstep(Px, Ax) (NI raises)                                   mat_lockstep_launches
+                              | 'lockstep_direct': hip_batch_solve_lockstep_direct(Px, Ax); on NI: _loop                   mat_lockstep_direct_launches
 
-Backward (the reference's :233-290): when an input requires grad, ``forward`` runs as a ``torch.autograd.Function`` and the returned tensor carries a
-grad_fn.  ``backward(dl_dx)`` makes ONE launch of the adjoint kernel for the whole batch (``osqp_hip_batch_adjoint``; ``adjoint_launches`` counts
-them) on the solution and duals the forward kept, and returns (dP, dq, dA, dl, du) shaped like the inputs: an input shared by the batch (1-D) gets
-the sum over the batch, as autograd's ``expand`` would give.  dP holds, for every entry of P_val (the full symmetric pattern P_idx), the value
-(r_i x_j + r_j x_i) / 2 of its position -- the same in either triangle.  Gradients arriving on the GPU go through the device-pointer entry point
-on torch's current stream, zero-copy.  ``last_adjoint_rec`` keeps the kernel's record per element (status, active rows, residual).  A problem the
-batch kernel cannot hold (its forward ran one element after the other on the handle) is differentiated the same way: the single-handle adjoint
-(``osqp_hip_adjoint_compute_at``: the PCG route for large QPs, at the (x, y) the forward kept) once per element, ``adjoint_launches`` counting every call, shared inputs receiving
-the batch sum -- or, with ``large_backward='lockstep'`` (default ``'loop'``: unchanged) and shared P_val / A_val, ONE call of the lockstep adjoint for the whole batch
-(``osqp_hip_batch_adjoint_lockstep``; ``adjoint_launches`` rises by 1; an element whose adjoint system was not solved raises RuntimeError as the
-per-element route does), or, with ``large_backward='lockstep_direct'``, ONE call of its direct form on a Woodbury handle with a diagonal K0
-(``osqp_hip_batch_adjoint_lockstep_direct``: the backward of ``large_batch='lockstep_direct'``; a handle the route declines goes on to the per-element
-loop, as with ``'lockstep'``).  With ``large_backward='lockstep'`` and 2-D P_val and / or A_val that the batch adjoint kernel declines, the backward is
-ONE call of the lockstep adjoint with per-element matrices (``osqp_hip_batch_adjoint_lockstep_mat``: every element's adjoint system on its own matrices
-and scaling; ``adjoint_launches`` rises by 1 and ``mat_lockstep_adjoint_launches`` counts these calls; host tensors through the host entry, ROCm tensors
-zero-copy through the device entry) in place of update(Px, Ax) + the single-handle adjoint per element; a handle that entry declines goes on to the
-per-element loop.  With ``large_backward='lockstep_direct'`` and 2-D P_val and / or A_val the backward is likewise ONE call of the direct lockstep adjoint
-with per-element matrices (``osqp_hip_batch_adjoint_lockstep_direct_mat``: every element's adjoint system on its own matrices, dense rows and scaling by the
-Woodbury formula -- the backward of ``large_batch='lockstep_direct'`` with per-element factor models; ``adjoint_launches`` rises by 1 and
-``mat_lockstep_direct_adjoint_launches`` counts these calls; host tensors through the host entry, ROCm tensors zero-copy through the device entry on torch's
-current stream); a handle the route declines goes on to the per-element loop.  A ``torch.distributed`` job (world size > 1) raises NotImplementedError in backward.  With no input requiring grad,
-forward behaves exactly as before.
+  Two asymmetries, kept as they grew: with shared matrices a handle that 'lockstep_direct' declines raises, with per-element matrices it goes on to
+  _loop; and per-element 'lockstep' raises where per-element 'lockstep_direct' goes on.
+  _loop is the reference's own route: update(Px, Ax, q, l, u) + solve() per element on the handle (:136-157).  A batch element that is not solved
+  raises RuntimeError (:158-162).  ``last_dual`` keeps the duals, ``last_rec`` the per-element record of a forward that ran on host arrays.
+  ``polishing=True`` is passed to ``setup``: the handle polishes every solved problem on whichever route takes it ('lockstep_direct' does not polish).
+  With ``torch.distributed`` initialised (world size > 1) the batch entries above do not apply: shared matrices are block-partitioned over the ranks
+  and the rows all-gathered (``osqp_amd.sharded``, host or device), on NI _loop; per-element matrices take _loop.
+
+Backward (nn/torch.py:233-290): when an input requires grad, ``forward`` runs as a ``torch.autograd.Function`` on the (x, y) the forward kept.
+
+  gradient       entries tried in order, by ``large_backward``; every NI goes on
+  host tensor    hip_batch_adjoint; 'lockstep': hip_batch_adjoint_lockstep | 'lockstep_direct': hip_batch_adjoint_lockstep_direct; _backward_loop
+  ROCm tensor    the same entries with the suffix _device (zero-copy, torch's current stream); _backward_loop
+
+  The lockstep entries are given Px / Ax only for a 2-D side.  ``adjoint_launches`` rises by 1 per call made and by 1 per element in _backward_loop
+  (the single-handle adjoint at the forward's (x, y), which raises NotImplementedError on a handle it does not take); ``mat_lockstep_adjoint_launches``
+  / ``mat_lockstep_direct_adjoint_launches`` by 1 when that call was given matrices.  ``last_adjoint_rec`` keeps the record per element (ext_hip
+  ADJOINT_FIELDS); an element whose adjoint system a lockstep entry did not solve raises RuntimeError.  The gradients are shaped like the inputs: an
+  input shared by the batch (1-D) gets the batch sum, and dP holds for every entry of P_val (the full symmetric pattern P_idx) the value
+  (r_i x_j + r_j x_i) / 2 of its position, the same in either triangle.  A ``torch.distributed`` job (world size > 1) raises NotImplementedError.
 """
 import numpy as np
 import scipy.sparse as spa
@@ -61,6 +47,32 @@ from torch.nn import Module
 
 import osqp_amd
 from osqp_amd import sharded
+
+NEXT, RAISE = 'next', 'raise'      # what NI from an entry does: on to the next entry of the row, or out of the layer
+ONE, MANY = 'one', 'many'          # an entry for one rank only / for a torch.distributed job only (None: either)
+
+# A row of the route table: (entry, counters it bumps, the large_batch / large_backward it needs or None, ranks, what NI does).
+_FORWARD = {   # (per-element matrices, q / l / u as ROCm tensors); per-element matrices always go through the host entries
+    (False, False): [('hip_batch_solve', (), None, ONE, NEXT),
+                     ('solve_batch_sharded', (), None, MANY, NEXT),
+                     ('hip_batch_solve_lockstep', (), 'lockstep', ONE, RAISE),
+                     ('hip_batch_solve_lockstep_direct', (), 'lockstep_direct', ONE, RAISE),
+                     ('_loop', (), None, None, RAISE)],
+    (False, True): [('hip_batch_solve_device', (), None, ONE, NEXT),
+                    ('solve_batch_sharded_device', (), None, MANY, NEXT),
+                    ('hip_batch_solve_lockstep_device', (), 'lockstep', ONE, RAISE),
+                    ('hip_batch_solve_lockstep_direct_device', (), 'lockstep_direct', ONE, RAISE)],      # nothing left: the row of host arrays
+    (True, False): [('hip_batch_solve', ('mat_batch_launches',), None, ONE, NEXT),
+                    ('hip_batch_solve_lockstep', ('mat_lockstep_launches',), 'lockstep', ONE, RAISE),
+                    ('hip_batch_solve_lockstep_direct', ('mat_lockstep_direct_launches',), 'lockstep_direct', ONE, NEXT),
+                    ('_loop', (), None, None, RAISE)],
+}
+_BACKWARD = {  # per-element matrices; the entries are the host ones, a ROCm gradient takes their _device forms
+    mat: [('hip_batch_adjoint', ('adjoint_launches',), None, ONE, NEXT),
+          ('hip_batch_adjoint_lockstep', ('adjoint_launches',) + (('mat_lockstep_adjoint_launches',) if mat else ()), 'lockstep', ONE, NEXT),
+          ('hip_batch_adjoint_lockstep_direct', ('adjoint_launches',) + (('mat_lockstep_direct_adjoint_launches',) if mat else ()), 'lockstep_direct', ONE, NEXT),
+          ('_backward_loop', (), None, ONE, RAISE)]
+    for mat in (False, True)}
 
 
 def _np(t):
@@ -72,6 +84,42 @@ def _distributed():
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         return dist.get_rank(), dist.get_world_size()
     return 0, 1
+
+
+def _declined(e):
+    """True for the ValueError of an entry that declines (the table's NI); every other one is raised again."""
+    if str(e) != str(int(osqp_amd.SolverError.OSQP_FUNC_NOT_IMPLEMENTED)):
+        raise e
+    return True
+
+
+def _batch_shape(params):
+    """Which of (P_val, q_val, A_val, l_val, u_val) are per element (2-D), and the batch size."""
+    batched = [p.ndimension() == 2 for p in params]
+    return batched, max([p.size(0) for p, b in zip(params, batched) if b], default=1)
+
+
+def _dev_index(t):
+    return (t.device.index or 0) if t.is_cuda else (torch.cuda.current_device() if torch.cuda.is_available() else 0)
+
+
+def _forward_rows(a, nb, k):
+    return a if a.ndim == 2 else np.broadcast_to(a, (nb, k))                          # nn/torch.py:184-188
+
+
+def _host_rows(t, nb, k):
+    return np.broadcast_to(np.asarray(_np(torch.as_tensor(t)), dtype=float).reshape(-1, k), (nb, k))
+
+
+def _device_rows(t, dev, nb, k):
+    return torch.as_tensor(t).detach().to(device=dev, dtype=torch.float64).reshape(-1, k).expand(nb, k).contiguous()
+
+
+def _check_solved(status):
+    """status: the status column of a forward's record, a numpy array or a host tensor."""
+    bad = np.nonzero(np.asarray(status) != int(osqp_amd.SolverStatus.OSQP_SOLVED))[0]
+    if bad.size:
+        raise RuntimeError('Unable to solve QP, status: %d (batch element %d)' % (int(status[bad[0]]), int(bad[0])))
 
 
 class OSQP(Module):
@@ -97,6 +145,7 @@ class OSQP(Module):
         self.adjoint_launches = 0    # launches of the adjoint kernel made by this layer's backward passes (one per backward; one per element where the batch kernel does not hold the problem)
         self.last_adjoint_rec = None # (nb, 4) record of the last backward: status, active rows, residual, reserved (ext_hip ADJOINT_FIELDS)
         self._grad_maps = None
+        self.mat_batch_launches = 0      # calls of the one-workgroup kernel with per-element matrices made by this layer's forwards
         self.mat_lockstep_launches = 0   # calls of the lockstep route with per-element matrices made by this layer's forwards (large_batch='lockstep')
         self.last_rec = None         # per-element record of the last forward that ran on host arrays (ext_hip BATCH_FIELDS where a batch route made it: status_polish is column 8)
         self.mat_lockstep_direct_launches = 0   # calls of the direct lockstep route with per-element matrices made by this layer's forwards (large_batch='lockstep_direct')
@@ -127,6 +176,29 @@ class OSQP(Module):
             self._Pv, self._Av = np.array(P_val, dtype=float), np.array(A_val, dtype=float)
         return self._solver
 
+    def _per_element(self, Pn, An, batched):
+        """(Px, Ax) of a batch entry: the upper triangle of a 2-D P_val, a 2-D A_val, None for a shared side."""
+        return (Pn[:, self._triu_pick] if batched[0] else None), (An if batched[2] else None)
+
+    def _walk(self, routes, mode, world, call):
+        """The one ladder of forward and backward: call(entry) for the entries of `routes` that apply to `mode` (large_batch / large_backward) and to
+        `world`, in order, until one does not decline; its counters are bumped here and nowhere else.  Returns (entry, what call returned), or
+        (None, None) where every entry that applies declined and was allowed to."""
+        for entry, counters, needs, ranks, on_decline in routes:
+            if needs not in (None, mode) or (ranks is not None and (ranks == ONE) != (world == 1)):
+                continue
+            try:
+                out = call(entry)
+            except ValueError as e:
+                if on_decline == RAISE:
+                    raise
+                _declined(e)
+                continue
+            for c in counters:
+                setattr(self, c, getattr(self, c) + 1)
+            return entry, out
+        return None, None
+
     # ------------------------------------------------------------------ forward
     def forward(self, P_val, q_val, A_val, l_val, u_val):
         params = (P_val, q_val, A_val, l_val, u_val)
@@ -134,86 +206,59 @@ class OSQP(Module):
             return _OSQPFunction.apply(self, *params)
         return self._solve(*params)
 
+    def _walk_forward(self, routes, world, call):
+        """_walk for a forward, whose call(entry) returns (x, y, rec): keeps the duals and returns (x, rec); None where _walk found no entry."""
+        entry, out = self._walk(routes, self.large_batch, world, call)
+        if entry is None:
+            return None
+        x, y, rec = out
+        if y is not None:
+            self.last_dual = y
+        return x, rec
+
     def _solve(self, P_val, q_val, A_val, l_val, u_val):
         params = [P_val, q_val, A_val, l_val, u_val]
         for p in params:
             assert p.ndimension() <= 2, 'Unexpected number of dimensions'
         dtype, device = q_val.dtype, q_val.device
-        batched = [p.ndimension() == 2 for p in params]
-        nb = max([p.size(0) for p, b in zip(params, batched) if b], default=1)
-        shared = not batched[0] and not batched[2]
+        batched, nb = _batch_shape(params)
+        mat = batched[0] or batched[2]
         Pn, An = _np(P_val), _np(A_val)                                                # (small: the matrix VALUES, once per forward)
         rank, world = _distributed()
-        if shared and q_val.is_cuda:                                                   # data on the GPU: zero-copy (one rank, or this rank's share)
+        if not mat and q_val.is_cuda:                                                  # data on the GPU: zero-copy (one rank, or this rank's share)
             out = self._forward_device(Pn, An, q_val, l_val, u_val, nb, rank, world)
             if out is not None:
                 return out if any(batched) else out.squeeze(0)
-        bc = lambda a, k: a if a.ndim == 2 else np.broadcast_to(a, (nb, k))          # nn/torch.py:184-188
-        qn, ln, un = bc(_np(q_val), self.n), bc(_np(l_val), self.m), bc(_np(u_val), self.m)
-        if shared:                                                                      # shared matrices: batched kernel
-            dev_index = (device.index or 0) if q_val.is_cuda else (torch.cuda.current_device() if torch.cuda.is_available() else 0)
+        qn, ln, un = _forward_rows(_np(q_val), nb, self.n), _forward_rows(_np(l_val), nb, self.m), _forward_rows(_np(u_val), nb, self.m)
+        dev_index = _dev_index(q_val)
+        if not mat:
             s = self._handle(Pn, An, qn[0], ln[0], un[0], device=dev_index)
-            try:
-                if world > 1:
-                    table, xl, yl, (lo, hi) = sharded.solve_batch_sharded(s, q=qn, l=ln, u=un, rank=rank, world=world,
-                                                                         device=device if q_val.is_cuda else None)
-                    x = sharded.gather_rows(xl, nb, device=device if q_val.is_cuda else None)
-                    rec = np.zeros((nb, 8)); rec[:, 0:5] = table[:, 1:6]
-                else:
-                    x, y, rec = s._solver.hip_batch_solve(q=qn, l=ln, u=un)
-                    self.last_dual = y
-            except ValueError as e:                                                    # only "does not fit one workgroup's LDS" falls back
-                if str(e) != str(int(osqp_amd.SolverError.OSQP_FUNC_NOT_IMPLEMENTED)):
-                    raise
-                if self.large_batch == 'lockstep' and world == 1:                      # any size, 64 problems at a time (osqp_hip_batch_solve_lockstep)
-                    x, y, rec = s._solver.hip_batch_solve_lockstep(q=qn, l=ln, u=un)
-                    self.last_dual = y
-                elif self.large_batch == 'lockstep_direct' and world == 1:             # a Woodbury handle with a diagonal K0 (osqp_hip_batch_solve_lockstep_direct)
-                    x, y, rec = s._solver.hip_batch_solve_lockstep_direct(q=qn, l=ln, u=un)
-                    self.last_dual = y
-                else:
-                    x, rec = self._loop(Pn, qn, An, ln, un, nb, batched, dev_index)
-        else:
-            dev_index = (device.index or 0) if q_val.is_cuda else (torch.cuda.current_device() if torch.cuda.is_available() else 0)
-            x = rec = None
-            if world == 1:                                                              # per-element matrices: one launch (osqp_hip_batch_solve_mat)
-                # (the handle's OWN matrices matter only for the side that is shared; a batched side keeps what the handle holds -- no re-assembly per forward)
-                have = self._solver is not None and self._device == dev_index
-                s = self._handle((self._Pv if have else Pn[0]) if batched[0] else Pn, (self._Av if have else An[0]) if batched[2] else An, qn[0], ln[0], un[0], device=dev_index)
-                try:
-                    x, y, rec = s._solver.hip_batch_solve(q=qn, l=ln, u=un, Px=(Pn[:, self._triu_pick] if batched[0] else None), Ax=(An if batched[2] else None), nbatch=nb)
-                    self.last_dual = y
-                    self.mat_batch_launches = getattr(self, 'mat_batch_launches', 0) + 1
-                except ValueError as e:
-                    if str(e) != str(int(osqp_amd.SolverError.OSQP_FUNC_NOT_IMPLEMENTED)):
-                        raise
-                    x = rec = None
-                    if self.large_batch == 'lockstep':                                  # any size, every element on its own matrices: ONE call (osqp_hip_batch_solve_lockstep_mat)
-                        x, y, rec = s._solver.hip_batch_solve_lockstep(q=qn, l=ln, u=un, Px=(Pn[:, self._triu_pick] if batched[0] else None), Ax=(An if batched[2] else None), nbatch=nb)
-                        self.last_dual = y
-                        self.mat_lockstep_launches += 1
-                    elif self.large_batch == 'lockstep_direct':                         # a Woodbury handle with a diagonal K0, every element on its own matrices: ONE call (osqp_hip_batch_solve_lockstep_direct_mat)
-                        try:
-                            x, y, rec = s._solver.hip_batch_solve_lockstep_direct(q=qn, l=ln, u=un, Px=(Pn[:, self._triu_pick] if batched[0] else None), Ax=(An if batched[2] else None), nbatch=nb)
-                            self.last_dual = y
-                            self.mat_lockstep_direct_launches += 1
-                        except ValueError as e2:                                        # a handle that entry declines: the per-element loop, as before
-                            if str(e2) != str(int(osqp_amd.SolverError.OSQP_FUNC_NOT_IMPLEMENTED)):
-                                raise
-                            x = rec = None
-            if x is None:
-                x, rec = self._loop(Pn, qn, An, ln, un, nb, batched, dev_index)
+        elif world == 1:
+            # (the handle's OWN matrices matter only for the side that is shared; a batched side keeps what the handle holds -- no re-assembly per forward)
+            have = self._solver is not None and self._device == dev_index
+            s = self._handle((self._Pv if have else Pn[0]) if batched[0] else Pn, (self._Av if have else An[0]) if batched[2] else An, qn[0], ln[0], un[0], device=dev_index)
+
+        def call(entry):
+            if entry == '_loop':
+                return self._loop(Pn, qn, An, ln, un, nb, batched, dev_index)
+            if entry == 'solve_batch_sharded':
+                dev = device if q_val.is_cuda else None
+                table, xl, yl, (lo, hi) = sharded.solve_batch_sharded(s, q=qn, l=ln, u=un, rank=rank, world=world, device=dev)
+                x = sharded.gather_rows(xl, nb, device=dev)
+                rec = np.zeros((nb, 8)); rec[:, 0:5] = table[:, 1:6]
+                return x, None, rec
+            Px, Ax = self._per_element(Pn, An, batched)
+            return getattr(s._solver, entry)(q=qn, l=ln, u=un, Px=Px, Ax=Ax, nbatch=nb)
+        x, rec = self._walk_forward(_FORWARD[mat, False], world, call)
         self.last_rec = rec
-        bad = np.nonzero(rec[:, 0] != int(osqp_amd.SolverStatus.OSQP_SOLVED))[0]
-        if bad.size:
-            raise RuntimeError('Unable to solve QP, status: %d (batch element %d)' % (int(rec[bad[0], 0]), int(bad[0])))
+        _check_solved(rec[:, 0])
         out = torch.as_tensor(x, dtype=dtype, device=device)
         return out if any(batched) else out.squeeze(0)
 
     def _forward_device(self, Pn, An, q_val, l_val, u_val, nb, rank=0, world=1):
-        """q, l, u stay where they are (float64, contiguous, (nb, .) on q_val's device); x comes back as a device tensor.  In a
-        distributed job (world > 1) this rank solves its contiguous share by device pointer and the shares meet in two all_gathers of
-        device tensors (records, solutions) -- no host copy of q, l, u or x (sharded.solve_batch_sharded_device)."""
+        """q, l, u stay where they are (float64, contiguous, (nb, .) on q_val's device); x comes back as a device tensor, None where the device row
+        of the table is used up.  In a distributed job (world > 1) this rank solves its contiguous share by device pointer and the shares meet in two
+        all_gathers of device tensors (records, solutions) -- no host copy of q, l, u or x (sharded.solve_batch_sharded_device)."""
         dev = q_val.device
         exp = lambda t, k: t.detach().to(device=dev, dtype=torch.float64).expand(nb, k).contiguous()
         qd, ld, ud = exp(q_val, self.n), exp(l_val, self.m), exp(u_val, self.m)
@@ -221,40 +266,22 @@ class OSQP(Module):
             s = self._handle(Pn, An, qd[0].cpu().numpy(), ld[0].cpu().numpy(), ud[0].cpu().numpy(), device=dev.index or 0)
         else:
             s = self._handle(Pn, An, None, None, None, device=dev.index or 0)
-        if world > 1:
-            try:
+
+        def call(entry):
+            if entry == 'solve_batch_sharded_device':
                 table, xl, yl, (lo, hi) = sharded.solve_batch_sharded_device(s, q=qd, l=ld, u=ud, rank=rank, world=world)
-            except ValueError as e:
-                if str(e) != str(int(osqp_amd.SolverError.OSQP_FUNC_NOT_IMPLEMENTED)):
-                    raise
-                return None
-            st = table[:, 1].to('cpu')                                                  # 8 bytes per problem: the statuses
-            bad = torch.nonzero(st != int(osqp_amd.SolverStatus.OSQP_SOLVED)).flatten()
-            if bad.numel():
-                raise RuntimeError('Unable to solve QP, status: %d (batch element %d)' % (int(st[bad[0]]), int(bad[0])))
-            self.last_dual = sharded.gather_rows_device(yl, nb)
-            return sharded.gather_rows_device(xl, nb).to(q_val.dtype)
-        x = torch.empty((nb, self.n), dtype=torch.float64, device=dev)
-        y = torch.empty((nb, self.m), dtype=torch.float64, device=dev)
-        rec = torch.empty((nb, 12), dtype=torch.float64, device=dev)    # OSQP_HIP_BATCH_REC
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        try:
-            s._solver.hip_batch_solve_device(nb, qd.data_ptr(), ld.data_ptr(), ud.data_ptr(), x.data_ptr(), y.data_ptr(), rec.data_ptr(),
-                                             warm=False, stream=stream)
-        except ValueError as e:
-            if str(e) != str(int(osqp_amd.SolverError.OSQP_FUNC_NOT_IMPLEMENTED)):
-                raise
-            if self.large_batch not in ('lockstep', 'lockstep_direct'):
-                return None                                                            # does not fit one workgroup's LDS
-            entry = s._solver.hip_batch_solve_lockstep_device if self.large_batch == 'lockstep' else s._solver.hip_batch_solve_lockstep_direct_device
-            entry(nb, qd.data_ptr(), ld.data_ptr(), ud.data_ptr(), x.data_ptr(), y.data_ptr(), rec.data_ptr(),
-                                                      warm=False, stream=stream)
-        st = rec[:, 0].to('cpu')                                                        # (waits for the stream)
-        bad = torch.nonzero(st != int(osqp_amd.SolverStatus.OSQP_SOLVED)).flatten()
-        if bad.numel():
-            raise RuntimeError('Unable to solve QP, status: %d (batch element %d)' % (int(st[bad[0]]), int(bad[0])))
-        self.last_dual = y
-        return x.to(q_val.dtype)
+                _check_solved(table[:, 1].to('cpu'))                                    # 8 bytes per problem: the statuses
+                y = sharded.gather_rows_device(yl, nb)
+                return sharded.gather_rows_device(xl, nb), y, None
+            x = torch.empty((nb, self.n), dtype=torch.float64, device=dev)
+            y = torch.empty((nb, self.m), dtype=torch.float64, device=dev)
+            rec = torch.empty((nb, 12), dtype=torch.float64, device=dev)    # OSQP_HIP_BATCH_REC
+            getattr(s._solver, entry)(nb, qd.data_ptr(), ld.data_ptr(), ud.data_ptr(), x.data_ptr(), y.data_ptr(), rec.data_ptr(),
+                                      warm=False, stream=torch.cuda.current_stream(dev).cuda_stream)
+            _check_solved(rec[:, 0].to('cpu'))                                          # (waits for the stream)
+            return x, y, rec
+        out = self._walk_forward(_FORWARD[False, True], world, call)
+        return None if out is None else out[0].to(q_val.dtype)
 
     def _loop(self, Pn, qn, An, ln, un, nb, batched, dev_index=0):
         """Per-element matrices (or a problem too large for the batch kernel): the single-QP engine, one element after the
@@ -269,8 +296,7 @@ class OSQP(Module):
             x[i] = r.x
             y[i] = r.y
             rec[i, 0], rec[i, 1], rec[i, 2] = r.info.status_val, r.info.iter, r.info.obj_val
-        self.last_dual = y
-        return x, rec
+        return x, y, rec
 
     # ------------------------------------------------------------------ backward
     def _p_map(self, nP):
@@ -312,108 +338,62 @@ class OSQP(Module):
                 if k in res: res[k][i] = v
         return {k: torch.as_tensor(v) for k, v in res.items()}
 
-    def _backward_lockstep(self, ext, l_val, u_val, x, y, g, nb, want, P_val=None, A_val=None):
-        """Backward of a shared-matrix batch past the batch adjoint kernel, with large_backward='lockstep' or 'lockstep_direct': one call of the lockstep
-        adjoint (or of its direct form) for the whole batch (cuda tensors: zero-copy through the device entry on torch's current stream).  An element whose adjoint system was not solved raises as
-        _backward_loop does.  None: this handle is not on the route (the caller goes on to the per-element loop).
-        P_val / A_val (2-D): per-element matrices -- the same one call through osqp_hip_batch_adjoint_lockstep_mat[_device] or, with 'lockstep_direct',
-        osqp_hip_batch_adjoint_lockstep_direct_mat[_device]."""
-        mat = P_val is not None or A_val is not None
-        widths = {'dP': len(self._triu_pick), 'dq': self.n, 'dA': ext.nnz_A, 'dl': self.m, 'du': self.m}
-        direct = self.large_backward == 'lockstep_direct'
-        host_entry = ext.hip_batch_adjoint_lockstep_direct if direct else ext.hip_batch_adjoint_lockstep
-        device_entry = ext.hip_batch_adjoint_lockstep_direct_device if direct else ext.hip_batch_adjoint_lockstep_device
-        try:
-            if g.is_cuda:
-                dev = g.device
-                f64 = lambda t, k: torch.as_tensor(t).detach().to(device=dev, dtype=torch.float64).reshape(-1, k).expand(nb, k).contiguous()
-                xd, yd, gd, ld, ud = f64(x, self.n), f64(y, self.m), f64(g, self.n), f64(l_val, self.m), f64(u_val, self.m)
-                res = {k: torch.empty((nb, widths[k]), dtype=torch.float64, device=dev) for k in want}
-                res['rec'] = torch.empty((nb, 4), dtype=torch.float64, device=dev)     # OSQP_HIP_ADJOINT_REC
-                ptr = lambda t: None if t is None else t.data_ptr()
-                Pxd = None if P_val is None else f64(P_val, P_val.shape[-1])[:, torch.as_tensor(self._triu_pick, device=dev)].contiguous()
-                Axd = None if A_val is None else f64(A_val, A_val.shape[-1])
-                matkw = dict(Px_ptr=ptr(Pxd), Ax_ptr=ptr(Axd)) if mat else {}
-                device_entry(nb, xd.data_ptr(), yd.data_ptr(), gd.data_ptr(), None, ld.data_ptr(), ud.data_ptr(),
-                             ptr(res.get('dP')), ptr(res.get('dq')), ptr(res.get('dA')), ptr(res.get('dl')), ptr(res.get('du')),
-                             res['rec'].data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream, **matkw)
-            else:
-                bc = lambda a, k: np.broadcast_to(np.asarray(a, dtype=float).reshape(-1, k), (nb, k))
-                matkw = dict(Px=None if P_val is None else _np(P_val)[:, self._triu_pick], Ax=None if A_val is None else _np(A_val)) if mat else {}
-                res = host_entry(bc(_np(torch.as_tensor(x)), self.n), bc(_np(torch.as_tensor(y)), self.m), bc(_np(g), self.n), None,
-                                 l=bc(_np(l_val), self.m), u=bc(_np(u_val), self.m), want=want, **matkw)
-                res = {k: torch.as_tensor(v) for k, v in res.items()}
-        except ValueError as e:
-            if str(e) != str(int(osqp_amd.SolverError.OSQP_FUNC_NOT_IMPLEMENTED)):
-                raise
-            return None
-        self.adjoint_launches += 1
-        if direct:
-            self.mat_lockstep_direct_adjoint_launches += int(mat)
-        else:
-            self.mat_lockstep_adjoint_launches += int(mat)
-        rec = res['rec'].cpu().numpy()
-        bad = np.nonzero(rec[:, 0] != 0)[0]
-        if bad.size:
-            i = int(bad[0])
-            self.last_adjoint_rec = res['rec']
-            raise RuntimeError('adjoint derivatives of batch element %d: error %d (status %d, residual %.3e)'
-                               % (i, int(osqp_amd.SolverError.OSQP_LINSYS_SOLVER_INIT_ERROR), int(rec[i, 0]), rec[i, 2]))
-        return res
+    def _adjoint_call(self, ext, saved, Pn, An, x, y, g, nb, batched, want):
+        """The one marshalling of a batch adjoint: launch(entry) calls that host entry of `ext` on host arrays or, for a gradient on the GPU, its
+        _device form by device pointer on torch's current stream (zero-copy), and returns the gradients named in `want` and 'rec' as tensors."""
+        P_val, q_val, A_val, l_val, u_val = saved
+        if not g.is_cuda:
+            Px, Ax = self._per_element(Pn, An, batched)
+            xn, yn, gn, ln, un = (_host_rows(t, nb, k) for t, k in ((x, self.n), (y, self.m), (g, self.n), (l_val, self.m), (u_val, self.m)))
+            return lambda entry: {k: torch.as_tensor(v) for k, v in getattr(ext, entry)(xn, yn, gn, None, l=ln, u=un, Px=Px, Ax=Ax, want=want).items()}
+        dev = g.device
+        xd, yd, gd, ld, ud = (_device_rows(t, dev, nb, k) for t, k in ((x, self.n), (y, self.m), (g, self.n), (l_val, self.m), (u_val, self.m)))
+        Pxd = _device_rows(P_val, dev, nb, Pn.shape[-1])[:, torch.as_tensor(self._triu_pick, device=dev)].contiguous() if batched[0] else None
+        Axd = _device_rows(A_val, dev, nb, An.shape[-1]) if batched[2] else None
+        widths = {'dP': len(self._triu_pick), 'dq': self.n, 'dA': An.shape[-1], 'dl': self.m, 'du': self.m}
+        res = {k: torch.empty((nb, widths[k]), dtype=torch.float64, device=dev) for k in want}
+        res['rec'] = torch.empty((nb, 4), dtype=torch.float64, device=dev)             # OSQP_HIP_ADJOINT_REC
+        ptr = lambda t: None if t is None else t.data_ptr()
+
+        def launch(entry):
+            getattr(ext, entry + '_device')(nb, x_ptr=ptr(xd), y_ptr=ptr(yd), dx_ptr=ptr(gd), dy_ptr=None, l_ptr=ptr(ld), u_ptr=ptr(ud), Px_ptr=ptr(Pxd), Ax_ptr=ptr(Axd),
+                                            dP_ptr=ptr(res.get('dP')), dq_ptr=ptr(res.get('dq')), dA_ptr=ptr(res.get('dA')), dl_ptr=ptr(res.get('dl')), du_ptr=ptr(res.get('du')),
+                                            rec_ptr=ptr(res['rec']), stream=torch.cuda.current_stream(dev).cuda_stream)
+            return res
+        return launch
 
     def _backward(self, saved, x, y, dl_dx, needs):
-        P_val, q_val, A_val, l_val, u_val = saved
-        params = [P_val, q_val, A_val, l_val, u_val]
-        batched = [p.ndimension() == 2 for p in params]
-        nb = max([p.size(0) for p, b in zip(params, batched) if b], default=1)
+        P_val, q_val, A_val, l_val, u_val = params = list(saved)
+        batched, nb = _batch_shape(params)
         if _distributed()[1] > 1:
             raise NotImplementedError('osqp_amd.nn.torch.OSQP: backward in a torch.distributed job (world size > 1) is not implemented')
         if y is None:
             raise NotImplementedError('osqp_amd.nn.torch.OSQP: backward needs the duals of the forward, which this forward did not keep')
-        s = self._solver
         Pn, An = _np(P_val), _np(A_val)
         # the handle's own values of a SHARED side are what the forward solved with (an intermediate forward may have replaced them)
-        self._handle(self._Pv if batched[0] else Pn, self._Av if batched[2] else An, None, None, None, device=self._device)
+        s = self._handle(self._Pv if batched[0] else Pn, self._Av if batched[2] else An, None, None, None, device=self._device)
         p_map = self._p_map(Pn.shape[-1])      # (A_val is in the CSC order of A, as the forward takes it)
         want = tuple(k for k, need in zip(('dP', 'dq', 'dA', 'dl', 'du'), needs) if need)
         g = dl_dx.detach().reshape(-1, self.n)
         if g.shape[0] != nb:
             g = g.expand(nb, self.n)
-        try:
-            if g.is_cuda:
-                dev = g.device
-                f64 = lambda t, k: torch.as_tensor(t).detach().to(device=dev, dtype=torch.float64).reshape(-1, k).expand(nb, k).contiguous()
-                xd, yd, gd, ld, ud = f64(x, self.n), f64(y, self.m), f64(g, self.n), f64(l_val, self.m), f64(u_val, self.m)
-                Pxd = f64(P_val, Pn.shape[-1])[:, torch.as_tensor(self._triu_pick, device=dev)].contiguous() if batched[0] else None
-                Axd = f64(A_val, An.shape[-1]) if batched[2] else None
-                widths = {'dP': len(self._triu_pick), 'dq': self.n, 'dA': An.shape[-1], 'dl': self.m, 'du': self.m}
-                res = {k: torch.empty((nb, widths[k]), dtype=torch.float64, device=dev) for k in want}
-                res['rec'] = torch.empty((nb, 4), dtype=torch.float64, device=dev)     # OSQP_HIP_ADJOINT_REC
-                ptr = lambda t: None if t is None else t.data_ptr()
-                s._solver.hip_batch_adjoint_device(nb, xd.data_ptr(), yd.data_ptr(), gd.data_ptr(), None, ld.data_ptr(), ud.data_ptr(), ptr(Pxd), ptr(Axd),
-                                                   ptr(res.get('dP')), ptr(res.get('dq')), ptr(res.get('dA')), ptr(res.get('dl')), ptr(res.get('du')),
-                                                   res['rec'].data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
-            else:
-                bc = lambda a, k: np.broadcast_to(np.asarray(a, dtype=float).reshape(-1, k), (nb, k))
-                res = s._solver.hip_batch_adjoint(bc(_np(torch.as_tensor(x)), self.n), bc(_np(torch.as_tensor(y)), self.m), bc(_np(g), self.n), None,
-                                                  l=bc(_np(l_val), self.m), u=bc(_np(u_val), self.m),
-                                                  Px=Pn[:, self._triu_pick] if batched[0] else None, Ax=An if batched[2] else None, want=want)
-                res = {k: torch.as_tensor(v) for k, v in res.items()}
-            self.adjoint_launches += 1
-        except ValueError as e:
-            if str(e) != str(int(osqp_amd.SolverError.OSQP_FUNC_NOT_IMPLEMENTED)):
-                raise
-            res = None
-            if self.large_backward in ('lockstep', 'lockstep_direct') and not batched[0] and not batched[2]:
-                res = self._backward_lockstep(s._solver, l_val, u_val, x, y, g, nb, want)      # shared matrices, any size: ONE call (osqp_hip_batch_adjoint_lockstep[_direct])
-            elif self.large_backward in ('lockstep', 'lockstep_direct'):                        # per-element matrices, any size: ONE call (osqp_hip_batch_adjoint_lockstep[_direct]_mat)
-                res = self._backward_lockstep(s._solver, l_val, u_val, x, y, g, nb, want, P_val if batched[0] else None, A_val if batched[2] else None)
-        if res is None:
+        launch = self._adjoint_call(s._solver, saved, Pn, An, x, y, g, nb, batched, want)
+
+        def call(entry):
+            if entry != '_backward_loop':
+                return launch(entry)
             # outside the batch kernel (the forward ran _loop): the single-handle adjoint per element
-            bc = lambda a, k: np.broadcast_to(np.asarray(a, dtype=float).reshape(-1, k), (nb, k))
-            res = self._backward_loop(Pn, An, bc(_np(l_val), self.m), bc(_np(u_val), self.m), bc(_np(torch.as_tensor(x)), self.n), bc(_np(torch.as_tensor(y)), self.m),
-                                      _np(g).reshape(nb, self.n), nb, batched, want)
+            return self._backward_loop(Pn, An, _host_rows(l_val, nb, self.m), _host_rows(u_val, nb, self.m), _host_rows(x, nb, self.n), _host_rows(y, nb, self.m),
+                                       _np(g).reshape(nb, self.n), nb, batched, want)
+        entry, res = self._walk(_BACKWARD[batched[0] or batched[2]], self.large_backward, 1, call)
         self.last_adjoint_rec = res['rec']
+        if 'lockstep' in entry:                            # an element whose adjoint system was not solved raises as _backward_loop does
+            rec = res['rec'].cpu().numpy()
+            bad = np.nonzero(rec[:, 0] != 0)[0]
+            if bad.size:
+                i = int(bad[0])
+                raise RuntimeError('adjoint derivatives of batch element %d: error %d (status %d, residual %.3e)'
+                                   % (i, int(osqp_amd.SolverError.OSQP_LINSYS_SOLVER_INIT_ERROR), int(rec[i, 0]), rec[i, 2]))
         if 'dP' in res:                                    # engine order (upper triangle, CSC) -> the order of P_val, either triangle the same value
             res['dP'] = res['dP'][:, torch.as_tensor(p_map, device=res['dP'].device)]
         grads = []
