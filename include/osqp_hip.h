@@ -371,12 +371,23 @@ OSQPInt osqp_hip_lockstep_mat_scaling(OSQPSolver *solver, OSQPInt b, OSQPFloat *
  * rule of osqp_solve on this handle -- the tolerance on the policy's square-root scale (OSQPHipPolicy::rho_tol_exp / OSQP_HIP_RHO_TOL_EXP; the literal
  * value for an LP) and the persistence test (rho_persist / OSQP_HIP_RHO_PERSIST) -- so an element takes the iterations, status and iterate that
  * osqp_update_data_vec + osqp_solve give from the same settings.rho (a loop over one handle starts each solve from the rho the previous one left).  No
- * polish, no duality-gap test; per-problem matrices: osqp_hip_batch_solve_lockstep_direct_mat below.  The decision is the structural one taken at setup, whatever became of the single handle's direct
- * mode since.  Returns OSQP_FUNC_NOT_IMPLEMENTED for every other handle: no Woodbury correction, the large mode (r > 128: the lasso), a K0 that is not
+ * duality-gap test; per-problem matrices: osqp_hip_batch_solve_lockstep_direct_mat below.  The decision is the structural one taken at setup, whatever became of the single handle's direct
+ * mode since.
+ * POLISH as on osqp_hip_batch_solve_lockstep (settings.polishing, delta, polish_refine_iter): every problem of a chunk that ends OSQP_SOLVED is polished
+ * between the ADMM loop and the transposes out by the same recurrence, with the Woodbury solve in place of the PCG -- rho_bar = 1 / delta on the
+ * guessed-active rows, RHO_MIN on the others (inactive dense rows included), so S_b is formed and inverted once more per attempted problem and at no
+ * step; these inversions are not counted in the direct record.  Record fields 8 and 9, the rejection rule (a rejected problem keeps its ADMM x, y and
+ * fields bit for bit), the time_limit rule (tested against the host's clock when the chunk's ADMM loop ends) and the polish work block are the shared
+ * paragraph's; osqp_hip_lockstep_polish_last_record is filled by a polishing direct call too, with 0 for the PCG iterations.  With polishing = 0 record
+ * fields 8 and 9 stay 0, the call issues exactly the launches it issues without this paragraph and leaves the polish record as it was -- except that
+ * the first such call after a polishing direct call zeroes it (the record is the last call's that could polish).  A polished point's dual residual is
+ * bounded by the recurrence's y step, which multiplies a rounding error by rho_bar = 1 / delta: about 1e-9 relative at delta = 1e-6.
+ * Returns OSQP_FUNC_NOT_IMPLEMENTED for every other handle: no Woodbury correction, the large mode (r > 128: the lasso), a K0 that is not
  * diagonal, the host simulator -- and a handle that works on a permuted copy (OSQPHipStats::reordered): this route DECLINES it rather than gather
  * through the permutations.  The handle's own iterates, solution, info and launch history are not touched.
  * osqp_hip_lockstep_direct_last_record: OSQP_HIP_LOCKSTEP_DIRECT_LAST_REC doubles {chunks, chunk width, ADMM iterations of the slowest problem,
- * inversions of S summed over the problems, kernel launches, GPU ms, workspace bytes, seconds of the call's chunks}; all zero before the first call. */
+ * inversions of S summed over the problems, kernel launches, GPU ms, workspace bytes, seconds of the call's chunks}; all zero before the first call.
+ * The inversions, launches and GPU ms are the ADMM part's: polish's are osqp_hip_lockstep_polish_last_record's. */
 #define OSQP_HIP_LOCKSTEP_DIRECT_LAST_REC 8
 OSQPInt osqp_hip_batch_solve_lockstep_direct(OSQPSolver *solver, OSQPInt nbatch, const OSQPFloat *q, const OSQPFloat *l, const OSQPFloat *u,
                                              OSQPFloat *x, OSQPFloat *y, OSQPFloat *rec, OSQPInt warm);
@@ -390,7 +401,8 @@ OSQPInt osqp_hip_lockstep_direct_last_record(OSQPSolver *solver, OSQPFloat *rec)
  * it under this handle's settings: its own Ruiz equilibration D_b, E_b, c_b (settings.scaling iterations, on the device, per lane), its own D0_b, S_b and
  * S_b^-1, the direct route's rho rule with this handle's tolerance.  The other arguments, the nbatch == 0 query, stream semantics, the record per problem,
  * statuses / certificates (in the problem's own units) / time_limit and the INDEPENDENCE guarantee are those of osqp_hip_batch_solve_lockstep_direct[_device].
- * No polish on this route; the backward pass with per-problem matrices is osqp_hip_batch_adjoint_lockstep_direct_mat below.  The handle is only read: its matrices, scaling, dense rows, S, iterates, settings and
+ * POLISH as on osqp_hip_batch_solve_lockstep_direct, each problem on its OWN P_b, A_b, dense rows and S_b under its own D_b, E_b, c_b (what osqp_solve's
+ * polish does on a handle set up with that problem alone).  The backward pass with per-problem matrices is osqp_hip_batch_adjoint_lockstep_direct_mat below.  The handle is only read: its matrices, scaling, dense rows, S, iterates, settings and
  * launch history are not touched.  Returns OSQP_FUNC_NOT_IMPLEMENTED unless osqp_hip_batch_solve_lockstep_direct serves the handle AND the chunk's
  * assembly does (device assembly, no repeated (j, j) entry in the stored triangle of P); in the host simulator always.
  * Device memory: 512 (nnz(A) + nnz(B) + 2 n + 2 m + n r + nnz of the view) bytes for one chunk, allocated by the first such call (22 MB of dense rows at

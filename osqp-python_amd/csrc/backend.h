@@ -484,8 +484,11 @@ struct LockstepParams : BatchSettings {
   // on / off, rho_bar = 1 / delta_eff on the guessed-active rows, at least pol_min_steps = 1 + polish_refine_iter steps of the recurrence, its PCG to
   // ||r|| <= pol_pcg_rel ||rhs|| within pol_cg_max iterations, the polish work block (lockstep_polish_ws_doubles(n, m) doubles, device) and where the
   // chunk's polish statistics go (host, kLsPolStat doubles: problems attempted, accepted, rejected, recurrence steps of the slowest problem, PCG
-  // iterations summed, kernel launches, GPU ms; nullptr: not wanted).  Set by Engine::run_lockstep_solve on the PCG route alone, for the shared and the per-problem-matrix entries alike: the adjoint and direct routes leave polish off.
-  int polish = 0, pol_min_steps = 1, pol_cg_max = 0;
+  // iterations summed, kernel launches, GPU ms; nullptr: not wanted).  Set by Engine::run_lockstep_solve on both routes, for the shared and the
+  // per-problem-matrix entries alike; the adjoints leave polish off.  The DIRECT route (lockstep_direct_chunk) has no PCG: pol_cg_max and pol_pcg_rel are not
+  // read there and the PCG count is 0; pol_prod2 != 0 refreshes the dense rows of x and x~ in its recurrence by one two-operand product (k_lw_prod2),
+  // 0 by two k_lw_prod launches -- the same bits (an A/B switch).
+  int polish = 0, pol_min_steps = 1, pol_cg_max = 0, pol_prod2 = 1;
   double pol_rho = 0, pol_pcg_rel = 0;
   double *pol_ws = nullptr, *pol_stat = nullptr;
   // PER-PROBLEM MATRICES (lockstep_hip.hip "matrices of a chunk"; include/osqp_hip.h osqp_hip_batch_solve_lockstep_mat): mat_ws != nullptr switches the chunk to

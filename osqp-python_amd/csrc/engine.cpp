@@ -15,7 +15,7 @@ namespace osqp_hip {
 const BatchEnv &batch_env() {
   static const BatchEnv e = [] {                 // (once per process)
     auto num = [](const char *name, int dflt) { const char *v = std::getenv(name); return v ? std::atoi(v) : dflt; };
-    return BatchEnv{num("OSQP_HIP_WAVE_SPLIT", -1), num("OSQP_HIP_WAVE_CUS", -1), num("OSQP_HIP_BATCH_WIDE_ROUNDS", 1 << 20)};
+    return BatchEnv{num("OSQP_HIP_WAVE_SPLIT", -1), num("OSQP_HIP_WAVE_CUS", -1), num("OSQP_HIP_BATCH_WIDE_ROUNDS", 1 << 20), num("OSQP_HIP_LS_POL_PROD2", 1)};
   }();
   return e;
 }

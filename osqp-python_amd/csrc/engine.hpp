@@ -149,7 +149,8 @@ class Engine {
   // (lockstep_adjoint_ws_doubles / lockstep_direct_adjoint_ws_doubles); adj_buf, the device scratch of the adjoint's host-array entry, kept across calls.
   struct DevScratch { double *buf = nullptr; size_t cap = 0; };
   struct LsRoute { double *ws = nullptr, *mat_ws = nullptr, *adj_ws = nullptr; DevScratch adj_buf; } lsr_[2];
-  double *lspw_ = nullptr;                            // polish work block of one PCG-route chunk (lockstep_polish_ws_doubles(n, m)), allocated by the first polishing call
+  double *lspw_ = nullptr;                            // polish work block of one lockstep chunk, either route (lockstep_polish_ws_doubles(n, m)), allocated by the first polishing call
+  bool ls_pol_direct_ = false;                        // the polish record (ls_last_[kLsRecPolish]) was written by a polishing DIRECT call
   double ls_last_[kLsRecCount][8] = {};               // what lockstep_last reads: the record of the last call of each kind, zeros before the first
   int lsm_last_count_ = 0;                            // problems of the last chunk the last PCG-route solve with mat processed (0: none, or the block was overwritten since): what lockstep_mat_scaling reads
   int *d_pvmap_ = nullptr, *d_avmap_ = nullptr;       // device copies of PvalMap_ / AvalMap_ (reordered handle), uploaded by the first call that reads them

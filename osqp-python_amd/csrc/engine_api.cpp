@@ -1003,7 +1003,7 @@ void Engine::prepare_lockstep_direct_wtpos() {
 
 // ---- solve: the chunk loop of both routes.  Every array of `a` is a DEVICE array in the caller's numbering; the settings are read once, in front of the
 // first chunk.  What the routes do differently is said here, once:
-//   PCG     the value maps of a reordered handle and lsm_last_count_ (with mat), polish and its record (settings.polishing);
+//   PCG     the value maps of a reordered handle and lsm_last_count_ (with mat), the PCG rule of polish's recurrence;
 //   direct  the view of A (and, with mat, the position map of the dense rows), the single-QP rho rule, the call's seconds in slot 7 of its record.
 int Engine::run_lockstep_solve(bool direct, int nbatch, const LockstepSolveIO &a, void *stream) {
   const bool mat = a.mat;
@@ -1028,16 +1028,22 @@ int Engine::run_lockstep_solve(bool direct, int nbatch, const LockstepSolveIO &a
     if (fresh) be::sync(d_);
     p.mat_ws = rt.mat_ws; p.mat_stat = mst; p.mat_iters = std::max(0, (int)settings.scaling);
   }
-  // PCG, polish (settings.polishing; with per-problem matrices too: the chunk polishes on its own matrix block): the recurrence of Engine::run_recurrence as
-  // Engine::polish calls it, per problem on block vectors -- rho_bar = 1 / delta_eff, at least 1 + polish_refine_iter steps, the inner systems to
-  // polish_pcg_tol within kMaxCg iterations.  Its work block is allocated by the first such call.  A direct call does not polish and leaves the record alone.
+  // polish (settings.polishing; with per-problem matrices too: the chunk polishes on its own matrix block): the recurrence of Engine::run_recurrence as
+  // Engine::polish calls it, per problem on block vectors -- rho_bar = 1 / delta_eff, at least 1 + polish_refine_iter steps; on the PCG route the inner
+  // systems to polish_pcg_tol within kMaxCg iterations, on the direct route the Woodbury solve with S_b inverted once per problem.  The work block is one
+  // per handle, shared by both routes, allocated by the first such call.  The polish record: a PCG call always writes it; a direct call writes it when
+  // the handle polishes, and once more -- zeros -- when polishing has been switched off since the direct call that wrote it (the record is then no
+  // longer that of the last direct call); any other direct call leaves it exactly as it was.
   double pst[kLsPolStat] = {0, 0, 0, 0, 0, 0, 0}, ptot[kLsPolStat] = {0, 0, 0, 0, 0, 0, 0};
   const size_t pneed = lockstep_polish_ws_doubles(n, m);
-  if (!direct && settings.polishing) {
+  const bool pol_record = !direct || settings.polishing || ls_pol_direct_;
+  if (settings.polishing) {
     if (!lspw_) { lspw_ = dev_vec<double>(d_, pneed); be::sync(d_); }
     const double de = std::max(settings.delta, pol_.polish_delta_floor);
     p.polish = 1; p.pol_rho = clamp_rho(1.0 / de); p.pol_min_steps = 1 + std::max(0, (int)settings.polish_refine_iter);
-    p.pol_cg_max = kMaxCg; p.pol_pcg_rel = pol_.polish_pcg_tol; p.pol_ws = lspw_; p.pol_stat = pst;
+    p.pol_ws = lspw_; p.pol_stat = pst;
+    if (direct) p.pol_prod2 = batch_env().ls_pol_prod2;
+    else { p.pol_cg_max = kMaxCg; p.pol_pcg_rel = pol_.polish_pcg_tol; }
   }
   // direct, adaptive rho as the handle's own solve decides it (ctl_setup: the tolerance on the square-root scale where P has a quadratic part, the
   // persistence test), not as the batch family does: an element then takes the path update(q, l, u) + solve() takes from the same rho
@@ -1045,7 +1051,7 @@ int Engine::run_lockstep_solve(bool direct, int nbatch, const LockstepSolveIO &a
   const double t0 = now_s(), limit = settings.time_limit > 0 && settings.time_limit < 1e9 ? settings.time_limit : 0.0;
   double tot[4] = {0, 0, 0, 0};
   int chunks = 0;
-  if (!direct) std::fill(ls_last_[kLsRecPolish], ls_last_[kLsRecPolish] + kLsRecLen, 0.0);
+  if (pol_record) std::fill(ls_last_[kLsRecPolish], ls_last_[kLsRecPolish] + kLsRecLen, 0.0);
   for (int b0 = 0; b0 < nbatch; b0 += kLsW, chunks++) {
     p.count = std::min(kLsW, nbatch - b0);
     p.q = a.q ? a.q + (size_t)b0 * n : nullptr; p.l = a.l ? a.l + (size_t)b0 * m : nullptr; p.u = a.u ? a.u + (size_t)b0 * m : nullptr;
@@ -1061,14 +1067,15 @@ int Engine::run_lockstep_solve(bool direct, int nbatch, const LockstepSolveIO &a
     tot[0] = std::max(tot[0], st[0]); tot[1] += st[1]; tot[2] += st[2]; tot[3] += st[3]; mtot += mst[0];
     for (int k = 0; k < kLsPolStat; k++) ptot[k] = k == 3 ? std::max(ptot[k], pst[k]) : ptot[k] + pst[k];
   }
-  // the records: the route's own (a PCG call with mat writes it as well), the mat record, the PCG route's polish record
+  // the records: the route's own (a PCG call with mat writes it as well), the mat record, the polish record (a PCG call, and a direct call that polishes)
   const double r[kLsRecLen] = {(double)chunks, (double)kLsW, tot[0], tot[1], tot[2], tot[3], (double)(need * sizeof(double)), direct ? now_s() - t0 : 0.0};
   std::copy(r, r + kLsRecLen, ls_last_[direct ? kLsRecDirect : kLsRecSolve]);
   if (mat) {
     const double rm[kLsRecLen] = {(double)chunks, (double)kLsW, tot[0], tot[1], tot[2], tot[3], (double)(mneed * sizeof(double)), mtot};
     std::copy(rm, rm + kLsRecLen, ls_last_[direct ? kLsRecDirectMat : kLsRecMat]);
   }
-  if (!direct) {
+  if (pol_record) {
+    ls_pol_direct_ = direct && settings.polishing;
     std::copy(ptot, ptot + kLsPolStat, ls_last_[kLsRecPolish]);
     ls_last_[kLsRecPolish][kLsPolStat] = settings.polishing ? (double)(pneed * sizeof(double)) : 0.0;
   }

@@ -22,6 +22,7 @@ namespace osqp_hip {
 struct BatchEnv {
   int wave_split, wave_cus;     // OSQP_HIP_WAVE_SPLIT / OSQP_HIP_WAVE_CUS: BatchParams::wv_split / wv_cus
   int wide_rounds;              // OSQP_HIP_BATCH_WIDE_ROUNDS: BatchParams::wide_rounds
+  int ls_pol_prod2;             // OSQP_HIP_LS_POL_PROD2: LockstepParams::pol_prod2 (0: polish on the direct lockstep route refreshes the dense rows by two k_lw_prod launches)
 };
 const BatchEnv &batch_env();
 

@@ -29,7 +29,8 @@
 // and the single-QP adjoint run, which is this file's iteration with alpha = 1 and a fixed rho -- see "adjoint derivatives of a chunk"; with matrices of
 // the chunk's own (osqp_hip_batch_adjoint_lockstep_mat) the same pass behind the forward's assembly and equilibration, on the k_lsm_* instantiations.
 // POLISH (settings.polishing): the chunk's SOLVED problems are polished by that same recurrence between the ADMM loop and the transposes out -- see
-// "polish of a chunk".  With per-problem matrices it runs on the chunk's own matrix block.
+// "polish of a chunk".  With per-problem matrices it runs on the chunk's own matrix block.  The DIRECT route (Woodbury handles, "lockstep DIRECT") polishes by
+// the same kernels with its own solve in place of the PCG: lockstep_direct_chunk.
 #include "hip_common.h"
 
 namespace osqp_hip {
@@ -1107,6 +1108,56 @@ template <bool MAT> __device__ __forceinline__ void lw_prod(const LwK &k, const 
 }
 __global__ __launch_bounds__(256) void k_lw_prod(LwK k, const double *v, double *out) { lw_prod<false>(k, v, out); }
 __global__ __launch_bounds__(256) void k_lwm_prod(LwK k, const double *v, double *out) { lw_prod<true>(k, v, out); }
+// lw_prod for TWO operands in one pass over WT: out = A_L v and out2 = A_L v2, same grid, same partition, same loops.  Every value of WT is loaded once and
+// multiplies both operands; each accumulator receives its terms in lw_prod's order, so both partial sets are those of two lw_prod launches bit for bit.
+// MAT: 24 lines in flight per wave and group of eight columns become 32 (sixteen of WT, eight of each operand).  Used by polish's recurrence on the direct
+// route (LwRun::long_rows2), where x and x~ are refreshed after every step and WT -- n r 512 bytes per chunk with per-problem matrices -- is the traffic.
+template <bool MAT> __device__ __forceinline__ void lw_prod2(const LwK &k, const double *v, const double *v2, double *out, double *out2) {
+  const int lane = ls_lane(), wv = ls_wave(), r = k.d.r;
+  const double *__restrict__ WT = k.d.WT;
+  if constexpr (MAT) {
+    const int rg = (r + 7) / 8, g = (int)blockIdx.x / rg, a = ((int)blockIdx.x % rg) * 8 + 2 * wv;
+    if (a >= r) return;
+    const int j0 = g * k.d.cb, j1 = min(j0 + k.d.cb, k.P.n);
+    const bool two = a + 1 < r;
+    const size_t st = (size_t)r * 64;
+    const double *__restrict__ w0 = WT + ((size_t)j0 * r + a) * 64 + lane, *__restrict__ w1 = w0 + (two ? 64 : 0);
+    const double *__restrict__ vj = v + IX(j0), *__restrict__ uj = v2 + IX(j0);
+    double s0 = 0.0, s1 = 0.0, t0 = 0.0, t1 = 0.0;
+    int j = j0;
+    for (; j + 8 <= j1; j += 8, w0 += 8 * st, w1 += 8 * st, vj += 8 * 64, uj += 8 * 64) {
+      double e0[8], e1[8], vv[8], uu[8];
+#pragma unroll
+      for (int u = 0; u < 8; u++) { e0[u] = w0[u * st]; e1[u] = w1[u * st]; vv[u] = vj[u * 64]; uu[u] = uj[u * 64]; }
+#pragma unroll
+      for (int u = 0; u < 8; u++) { s0 += e0[u] * vv[u]; s1 += e1[u] * vv[u]; t0 += e0[u] * uu[u]; t1 += e1[u] * uu[u]; }
+    }
+    for (; j < j1; j++, w0 += st, w1 += st, vj += 64, uj += 64) {
+      const double e0 = w0[0], e1 = w1[0], vv = vj[0], uu = uj[0];
+      s0 += e0 * vv; s1 += e1 * vv; t0 += e0 * uu; t1 += e1 * uu;
+    }
+    const size_t o = ((size_t)g * r + a) * 64 + lane;
+    out[o] = s0; out2[o] = t0;
+    if (two) { out[o + 64] = s1; out2[o + 64] = t1; }
+  } else {
+    const int j0 = (int)blockIdx.x * k.d.cb, j1 = min(j0 + k.d.cb, k.P.n);
+    for (int a0 = wv * 8; a0 < r; a0 += 32) {
+      double acc[8], acc2[8];
+#pragma unroll
+      for (int u = 0; u < 8; u++) { acc[u] = 0.0; acc2[u] = 0.0; }
+      for (int j = j0; j < j1; j++) {
+        const double vj = v[IX(j)], uj = v2[IX(j)];
+        const double *__restrict__ wt = WT + (size_t)j * r + a0;
+#pragma unroll
+        for (int u = 0; u < 8; u++) { const double e = a0 + u < r ? wt[u] : 0.0; acc[u] += e * vj; acc2[u] += e * uj; }
+      }
+#pragma unroll
+      for (int u = 0; u < 8; u++) if (a0 + u < r) { const size_t o = ((size_t)blockIdx.x * r + a0 + u) * 64 + lane; out[o] = acc[u]; out2[o] = acc2[u]; }
+    }
+  }
+}
+__global__ __launch_bounds__(256) void k_lw_prod2(LwK k, const double *v, const double *v2, double *out, double *out2) { lw_prod2<false>(k, v, v2, out, out2); }
+__global__ __launch_bounds__(256) void k_lwm_prod2(LwK k, const double *v, const double *v2, double *out, double *out2) { lw_prod2<true>(k, v, v2, out, out2); }
 // the sum of GC partials `st` doubles apart, in block order, eight loads in flight (the additions keep their order)
 __device__ __forceinline__ double lw_fold(const double *s, int GC, size_t st) {
   double a = 0.0;
@@ -1521,6 +1572,12 @@ struct LwRun {
   }
   // the rows n .. n + r - 1 of x and x~ from the products
   void long_rows(LsRun &R, int start) const { prod(R, k.w.x, k.d.pg); prod(R, k.w.xs, k.d.pg2); R.go(k_lw_setl, 1, k, start); }
+  // the same rows with both products from one pass over WT (k_lw_prod2: the same partials bit for bit); polish's recurrence
+  void long_rows2(LsRun &R) const {
+    if (mat) R.go(k_lwm_prod2, GC * ((r + 7) / 8), k, (const double *)k.w.x, (const double *)k.w.xs, k.d.pg, k.d.pg2);
+    else R.go(k_lw_prod2, GC, k, (const double *)k.w.x, (const double *)k.w.xs, k.d.pg, k.d.pg2);
+    R.go(k_lw_setl, 1, k, 0);
+  }
 };
 
 }  // namespace
@@ -1664,7 +1721,8 @@ int lockstep_adjoint_chunk(Dev &d, const LockstepAdjointParams &p, void *stream,
 // launch sequence without an inner convergence test: five launches per ADMM iteration (LwRun::solve), enqueued back to back; at a termination check the
 // host reads the word block once.  The time limit is tested against the host's clock as of the last such read (in between the host runs ahead of the
 // GPU): a chunk past its limit ends at the iteration after the check that saw it, with OSQP_TIME_LIMIT_REACHED for the problems still running.
-// stat: {ADMM iterations of the slowest problem, inversions of S summed over the problems, kernel launches, GPU ms}.
+// stat: {ADMM iterations of the slowest problem, inversions of S summed over the problems, kernel launches, GPU ms} -- the ADMM part's; with p.polish the
+// chunk's SOLVED problems are polished in front of the transposes out and polish's figures go to p.pol_stat (as lockstep_chunk's; the PCG count is 0).
 // PER-PROBLEM MATRICES (p.mat_ws != nullptr; include/osqp_hip.h osqp_hip_batch_solve_lockstep_direct_mat): problem b runs on its own P_b, A_b under its own
 // D_b, E_b, c_b.  In front of the transposes in: ls_mat_prepare (the PCG route's assembly and equilibration, unchanged), then the chunk's own WT and view
 // values from the block's scaled A (k_lwm_wt, k_lwm_vals); R.em marks the end of all three.  From then on the row passes are kLsOwnMat's and the four
@@ -1689,6 +1747,9 @@ int lockstep_direct_chunk(Dev &d, const LockstepDirectParams &p0, void *stream, 
     if (!lockstep_direct_mat_layout(cm, n, m, r, p.A.nnz, p.B.nnz, p.v.Av.nnz, again, xm)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
     p.v.WT = xm.WT; p.v.Av.val = xm.vval;
   }
+  LsPolWs pws{};
+  LsCursor cp{p.pol_ws};
+  if (p.polish && p.pol_ws && !lockstep_polish_layout(cp, n, m, pws)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   const LwRun D(p, p.v, w, x, mat);
   const LsK &kb = D.kb, &kv = D.kv;
   const LsPcgKernels &K = D.K();
@@ -1729,12 +1790,54 @@ int lockstep_direct_chunk(Dev &d, const LockstepDirectParams &p0, void *stream, 
     if (at_rho && !late) D.factor(R);
     if (at_check || late) R.fetch();
   }
+  // polish ("polish of a chunk" above, with the direct adjoint's step in place of the PCG).  A chunk whose time limit has passed -- by the host's clock
+  // now, not as of the last check -- does not polish.  The recurrence's rho is fixed: rho_bar = 1 / delta_eff on the guessed-active rows, rho_min on
+  // the others (k_ls_pol_class frees them, so k_ls_setrho classes them loose -- the inactive dense rows too), alpha = 1; S_b is formed and inverted once
+  // per attempted problem (Dp.factor) and never at a step.  A step is LwRun::solve and the refresh of the dense rows of x and x~; the cone projection
+  // and the accept test's row pass read A through the view, so no wave walks a dense row.  k_ls_pol_end restores the first n rows of a rejected
+  // problem's x: nothing behind it reads the rows >= n (k_ls_store_n runs over n rows, k_ls_store_m over y and dy).
+  const bool polished = p.polish && p.pol_ws && !(p.time_limit > 0 && ls_now() - t_begin > p.time_limit);
+  int pol_steps = 0, pol_att = 0;
+  long pol_launches = 0;
+  if (polished) {
+    const LsPK kq{kv.P, w, pws};                         // (kv.P: with a matrix block its A is the view on the chunk's own values, B.val, D .. Einv the block's)
+    const long launches0 = R.launches;
+    const double t_pol = ls_now();
+    LockstepDirectParams pp = p;
+    pp.alpha = 1.0;
+    const LwRun Dp(pp, pp.v, w, x, mat);
+    R.ep0.record(s);
+    R.go(k_ls_pol_begin, 1, kq);
+    R.fetch();
+    pol_att = R.words[WD_LIVE];
+    if (pol_att > 0) {
+      R.go(k_ls_pol_class, G, kq);
+      Dp.factor(R);
+      pol_steps = ls_recurrence(R, K, Dp.kv, Dp.kb, kLsPolMaxSteps,
+                                [&]() { Dp.solve(R); if (p.pol_prod2) Dp.long_rows2(R); else Dp.long_rows(R, 0); }, [&]() { R.go(k_ls_pol_decide, 1, kq); });
+      Dp.prod(R, w.x, x.pg);
+      R.go(k_lwa_setl, (r + 3) / 4, Dp.k, w.x);
+      R.go(mat ? k_lsm_pol_cone : k_ls_pol_cone, G, kq);
+      R.go(K.resm, G, Dp.kv);
+      R.go(K.resn, G, Dp.kb);
+      R.go(mat ? k_lsm_pol_accept : k_ls_pol_accept, 1, kq);
+      R.fetch();
+      R.go(k_ls_pol_end, G, kq, ls_now() - t_pol);
+    }
+    R.ep1.record(s);
+    pol_launches = R.launches - launches0;
+  }
   R.go(K.store_n, tn, kb);
   R.go(K.store_m, tm, kb);
   long nfact = 0;
-  const float ms = R.finish(x.fact, &nfact);
+  const float ms = R.finish(x.fact, &nfact), pms = polished ? LsRun::ms(R.ep0, R.ep1) : 0.f;
   if (mat && p.mat_stat) p.mat_stat[0] = LsRun::ms(R.e0, R.em);
-  if (stat) { stat[0] = iter; stat[1] = (double)nfact; stat[2] = (double)R.launches; stat[3] = ms; }
+  // (the chunk's statistics are the ADMM part's: k_lw_inv has counted one inversion for every problem polish attempted; polish's go to their own block)
+  if (stat) { stat[0] = iter; stat[1] = (double)(nfact - pol_att); stat[2] = (double)(R.launches - pol_launches); stat[3] = ms - pms; }
+  if (polished && p.pol_stat) {
+    double *ps = p.pol_stat;
+    ps[0] = pol_att; ps[1] = R.words[WD_POLACC]; ps[2] = R.words[WD_POLREJ]; ps[3] = pol_steps; ps[4] = 0.0; ps[5] = (double)pol_launches; ps[6] = pms;
+  }
   return OSQP_NO_ERROR;
 }
 

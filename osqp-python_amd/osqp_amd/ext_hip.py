@@ -498,7 +498,8 @@ class OSQPSolver:
 
     def lockstep_polish_last_record(self):
         """osqp_hip_lockstep_polish_last_record as a dict (LOCKSTEP_POLISH_LAST_FIELDS): the polish part of the last lockstep call of this handle
-        (settings.polishing); zeros before the first call and after a call without polishing."""
+        (settings.polishing) -- hip_batch_solve_lockstep, or hip_batch_solve_lockstep_direct on a polishing handle (pcg_iters is 0 there); zeros before the
+        first call and after a call without polishing (a direct call on a handle that never polished leaves it as it was)."""
         return self._last_record('osqp_hip_lockstep_polish_last_record', self.LOCKSTEP_POLISH_LAST_FIELDS)
 
     def hip_batch_solve_lockstep_direct(self, q=None, l=None, u=None, x0=None, y0=None, nbatch=None, Px=None, Ax=None):
@@ -507,7 +508,9 @@ class OSQPSolver:
         returns; every other handle raises with OSQP_FUNC_NOT_IMPLEMENTED.
         Px (B, nnz(triu P)) / Ax (B, nnz(A)): per-problem matrix values in the CSC order given at setup (osqp_hip_batch_solve_lockstep_direct_mat); either
         alone is allowed, the other side takes the handle's current values.  Every problem is scaled and solved as a solver set up with its data alone
-        (lockstep_direct_mat_last_record)."""
+        (lockstep_direct_mat_last_record).
+        settings.polishing: every problem that ends OSQP_SOLVED is polished (record columns 8 and 9: status_polish 1 / -1, the chunk's polish seconds), on
+        its own matrices where Px / Ax are given; lockstep_polish_last_record has the polish part of the call, lockstep_direct_last_record the ADMM part."""
         return self._lockstep_host(self._lib.osqp_hip_batch_solve_lockstep_direct, q, l, u, x0, y0, nbatch, Px, Ax, mat_entry=self._lib.osqp_hip_batch_solve_lockstep_direct_mat)
 
     def hip_batch_solve_lockstep_direct_device(self, nbatch, q_ptr, l_ptr, u_ptr, x_ptr, y_ptr, rec_ptr, warm=False, stream=None, Px_ptr=None, Ax_ptr=None):

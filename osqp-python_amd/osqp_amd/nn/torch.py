@@ -23,7 +23,7 @@ Forward (nn/torch.py:113-230), one rank.  P_val and A_val 1-D: shared by the bat
   _loop; and per-element 'lockstep' raises where per-element 'lockstep_direct' goes on.
   _loop is the reference's own route: update(Px, Ax, q, l, u) + solve() per element on the handle (:136-157).  A batch element that is not solved
   raises RuntimeError (:158-162).  ``last_dual`` keeps the duals, ``last_rec`` the per-element record of a forward that ran on host arrays.
-  ``polishing=True`` is passed to ``setup``: the handle polishes every solved problem on whichever route takes it ('lockstep_direct' does not polish).
+  ``polishing=True`` is passed to ``setup``: the handle polishes every solved problem on whichever route takes it ('lockstep_direct' included).
   With ``torch.distributed`` initialised (world size > 1) the batch entries above do not apply: shared matrices are block-partitioned over the ranks
   and the rows all-gathered (``osqp_amd.sharded``, host or device), on NI _loop; per-element matrices take _loop.
 

@@ -6,17 +6,18 @@ Engine::run_lockstep_solve / run_lockstep_adjoint and the entry points over them
 the forward route, the forward with polishing, the forward with per-element Px / Ax (and that with polishing: its ADMM part, the polished result, and
 the same handle with polishing switched off), the adjoint, the adjoint with per-element Px / Ax; on problems.portfolio_qp(200, 10) and (600, 4) at
 B = 70: the direct forward and the direct adjoint, both also with per-element Px / Ax drawn as tests/test_gpu_lockstep_direct_mat.py draws them (a handle
-the direct route declines -- (200, 10): no dense row -- is kept as its return code); and the m = 0 tridiagonal case at n = 900, B = 3, with polish.  On both
+the direct route declines -- (200, 10): no dense row -- is kept as its return code), and the direct forward on a polishing handle, shared and with
+per-element matrices (its ADMM part, the polished result, and the same handle with polishing switched off); and the m = 0 tridiagonal case at n = 900, B = 3, with polish.  On both
 routes there is one forward call each with only Px and only Ax, and every case above is run again through its *_device entry, the same inputs as torch
 tensors on torch's current stream (tags <tag>_dev).  A call with per-element matrices is kept with its own record and its route's base record
 (<tag>_base).  The tool's Python is the same text for both dumps: the C ABI is what two builds share.  Every returned array and every *_last_record
 field except the timings goes into an .npz.  --compare A B exits non-zero unless every array is equal (NaNs in the same places) and every record field
 is equal: kernel launches, iteration / step counts, PCG iterations, inversions, polish counts, workspace bytes.  --feature TAG ..: entries under these
-tags are what build B is meant to change (mat_polish, when A is a build from before polish reached the per-element-matrix entry); they are printed with
-both sides' figures and not counted.
+tags are what build B is meant to change (mat_polish, when A is a build from before polish reached the per-element-matrix entry; direct_600_4_polish and
+direct_600_4_mat_polish, when A is a build from before polish reached the direct route); they are printed with both sides' figures and not counted.
 
     python tools/lockstep_identity.py --dump prof_out/identity_this.npz          (OSQP_HIP_LIBRARY selects the other build)
-    python tools/lockstep_identity.py --compare prof_out/identity_parent.npz prof_out/identity_this.npz [--feature mat_polish]
+    python tools/lockstep_identity.py --compare prof_out/identity_parent.npz prof_out/identity_this.npz [--feature mat_polish direct_600_4_polish ..]
 """
 import argparse
 import os
@@ -165,6 +166,20 @@ def dump(path):
         keep(tag + '_mat_dev_base', {}, e.lockstep_direct_last_record())
         keep(tag + '_mat_adjoint_dev', adj_dev(e.hip_batch_adjoint_lockstep_direct_device, e, xm, ym, dxm, Px=Px, Ax=Ax), e.lockstep_direct_mat_adjoint_last_record())
         keep(tag + '_mat_adjoint_dev_base', {}, e.lockstep_direct_adjoint_last_record())
+        # the polishing direct handle, shared and per-element matrices.  <tag>_polish / <tag>_mat_polish (FEATURE below): the polished x, y, rec and the polish
+        # record -- a build from before polish reached the direct route returns the ADMM point and status_polish 0 there.  *_admm: the ADMM part of those calls
+        # (record fields status, iter, rho, rho_updates, pcg_iters, rho_estimate; the direct records), which polish must leave as it was.  *_off: the same
+        # handle with polishing switched off.
+        so = outer(P, q, A, l, u, max_iter=50000, polishing=True)
+        e = so._solver
+        for t, kw, last in ((tag + '_polish', dict(), e.lockstep_direct_last_record), (tag + '_mat_polish', dict(Px=Px, Ax=Ax), e.lockstep_direct_mat_last_record)):
+            xq, yq, recq = e.hip_batch_solve_lockstep_direct(q=Q, **kw)
+            keep(t, fwd(xq, yq, recq), e.lockstep_polish_last_record())
+            keep(t + '_admm', dict(rec=recq[:, [0, 1, 5, 6, 7, 10]]), last())
+        so.update_settings(polishing=False)
+        for t, kw, last in ((tag + '_polish_off', dict(), e.lockstep_direct_last_record), (tag + '_mat_polish_off', dict(Px=Px, Ax=Ax), e.lockstep_direct_mat_last_record)):
+            keep(t, fwd(*e.hip_batch_solve_lockstep_direct(q=Q, **kw)), last())
+            keep(t + '_part', {}, e.lockstep_polish_last_record())
 
     n = 900
     rng = np.random.default_rng(3)
