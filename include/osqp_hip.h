@@ -776,6 +776,79 @@ typedef struct {
   OSQPFloat gamma, rnorm;                                    /* out */
 } OSQPHipWoodburyTest;
 OSQPInt osqp_hip_test_woodbury(OSQPSolver *solver, OSQPHipWoodburyTest *t);
+/* Test hook (used by tests/ only): single launches of the lockstep block-vector kernels (csrc/lockstep_hip.hip) on a work block the
+   caller fills -- POKE, RUN, PEEK.  The entry builds the kernel arguments exactly as a lockstep solve of this handle does (settings, matrices, scalings,
+   permutations, value maps, the route's resident work block and, with mat, its resident matrix block, allocated as a first solve would), uploads the
+   caller's whole blocks into them, launches the listed ops in order on the solver's stream -- each op is ONE kernel launch, with the arguments and the grid
+   the drivers use (one text serves both) --, synchronises, and downloads the whole blocks and x / y / rec.  No host loop of a solve runs.
+     route    0: the PCG route.  1: the direct route of a Woodbury handle with a diagonal K0 (osqp_hip_batch_solve_lockstep_direct): the blocks are then that
+              route's -- dws_need / dmat_need doubles (lockstep_direct_ws_doubles(n, m, r), lockstep_direct_mat_ws_doubles) -- and the ops are the kernels that route
+              launches: LOAD_N LOAD_M INIT STORE_N STORE_M INITZ RHS UPD RESM RESN SETRHO (INITZ and RESM read A through the view, UPD runs over n + r rows), with
+              mat the matrices of a chunk, and the ops from D0 on (VALS and WT: with mat only).  On route 0 the ops from D0 on do not belong
+     mat      0: the handle's matrices (k_ls_*);  1: per-problem matrices (k_lsm_*), mat_ws is then the chunk's matrix block
+     count    1 .. 64 problems;  warm: as the solve entries'
+     ops      [nops], 1 <= nops <= 64, each an OSQPHipLockstepOp that belongs to (route, mat) and to this handle: the ops from BEGIN on need mat = 1, ASM_A /
+              ASM_P need stored entries, and the ops a solve never launches with m = 0 (LOAD_M, STORE_M, INITZ, T, RESM, SETRHO) need m > 0
+     q l u    [count][n] / [count][m] in the caller's numbering, each optional (NULL with length 0: the handle's own vector)
+     x y rec  [count][n], [count][m], [count][OSQP_HIP_BATCH_REC]: in (warm start) and out; always uploaded whole and downloaded whole
+     Px Ax    with mat: [count][nnz(triu P)] / [count][nnz(A)] in the CSC order given at setup, each optional (NULL with length 0: the handle's values)
+     ws       the chunk's WHOLE work block, in and out: ws_need doubles (csrc/lockstep_layout.h lockstep_ws_doubles(n, m), the engine's numbering)
+     mat_ws   with mat: the WHOLE matrix block, in and out: mat_need doubles (lockstep_mat_ws_doubles); without: NULL with length 0
+   What the references need of the handle, each group optional (length 0 and NULL pointers: not wanted; else every pointer of the group and the exact length),
+   in the ENGINE's numbering (osqp_hip_get_reordering):
+     A_rowptr [m + 1], A_col / A_val [nnzA], B_rowptr [n + 1], B_col / B_val [nnzB]    the scaled CSR of A and of B = [P + sigma I | A']
+     D Dinv [n], E Einv [m]; c                                                          the handle's scaling
+     Pm1 Pm2 pvmap Praw [nzP], AmA AmB avmap Araw [nzA], Bdiag [n]                      the assembly maps (Pm2 = -1: a diagonal entry), the value maps of a
+                                                                                        reordered handle (the identity otherwise), the raw values
+   and, with route 1, the direct route's view (each group as above):
+     Av_rowptr [m + 1], Av_col Av_val vsrc [nv]                                         the view of A: a long row is the single entry 1.0 at column n + a; where a
+                                                                                        view entry sits in A_val (-1: a long row's 1.0)
+     WT wtpos [n r], rows [r], islong [m]                                               the dense rows (entry (column j, long row a) at j r + a), where each sits in
+                                                                                        A_val (-1: none), the long rows' indices, the row flags (0 / 1)
+   r, GC, cb, nv (the long rows, the column blocks of the products and their width, the view's entries) and dws_need / dmat_need are written with the sizes
+   where the direct route takes the handle (0 otherwise).
+   Whenever the handle is ready and t is not NULL the sizes n, m, nnzA, nnzB, nzP, nzA, G (lockstep_grid), ws_need, mat_need are written first, whatever the
+   call then answers: a caller learns the lengths from a call it expects to be rejected.  Everything else is checked BEFORE anything is allocated, uploaded
+   or launched: a NULL struct, a length other than listed, a NULL pointer where a length is given, an op that does not belong, count or nops outside
+   1 .. 64, route or mat outside {0, 1} give OSQP_DATA_VALIDATION_ERROR and nothing runs; a handle the route declines (the solve entry's own predicate)
+   gives OSQP_FUNC_NOT_IMPLEMENTED -- with route 1 in front of the op and length checks, because that route's lengths exist only where it takes the handle.  The contents of the blocks are NOT checked and need not be: the kernels take every index from the handle's arrays and
+   the carve; the blocks hold values, 0/1 flags and counters only.  The resident blocks are a solve's scratch -- every solve rewrites what it reads -- so a
+   solve after the call is the solve without it. */
+typedef enum {
+  OSQP_HIP_LS_LOAD_N = 0, OSQP_HIP_LS_LOAD_M, OSQP_HIP_LS_INIT, OSQP_HIP_LS_STORE_N, OSQP_HIP_LS_STORE_M,                       /* transposes and state */
+  OSQP_HIP_LS_MINV, OSQP_HIP_LS_INITZ, OSQP_HIP_LS_RHS, OSQP_HIP_LS_T, OSQP_HIP_LS_KP, OSQP_HIP_LS_UPD, OSQP_HIP_LS_RESM, OSQP_HIP_LS_RESN,   /* row passes */
+  OSQP_HIP_LS_SETRHO, OSQP_HIP_LS_CGUPD, OSQP_HIP_LS_CGP,                                                                       /* elementwise */
+  OSQP_HIP_LS_CGINIT, OSQP_HIP_LS_CGALPHA, OSQP_HIP_LS_CGBETA,                                                                  /* folds */
+  OSQP_HIP_LS_BEGIN, OSQP_HIP_LS_ASM_A, OSQP_HIP_LS_ASM_P, OSQP_HIP_LS_NORMS, OSQP_HIP_LS_SCALE, OSQP_HIP_LS_COST, OSQP_HIP_LS_COST_APPLY, OSQP_HIP_LS_FINISH,   /* matrices of a chunk */
+  OSQP_HIP_LS_D0, OSQP_HIP_LS_S, OSQP_HIP_LS_INV,                                                                               /* direct route: the factor */
+  OSQP_HIP_LS_PROD_X, OSQP_HIP_LS_PROD_XS, OSQP_HIP_LS_PROD_P, OSQP_HIP_LS_PROD2,       /* the products with the long rows: x -> pg, x~ -> pg2, p -> pg; both of the first two in one pass */
+  OSQP_HIP_LS_SETL0, OSQP_HIP_LS_SETL1, OSQP_HIP_LS_H, OSQP_HIP_LS_X,                   /* k_lw_setl with start 0 / 1, k_lw_h, k_lw_x */
+  OSQP_HIP_LS_VALS, OSQP_HIP_LS_WT,                                                     /* the chunk's own view values and dense rows (mat) */
+  OSQP_HIP_LS_OP_COUNT
+} OSQPHipLockstepOp;
+typedef struct {
+  OSQPInt route, mat, count, warm, nops;
+  const OSQPInt *ops;
+  long long q_len, l_len, u_len, x_len, y_len, rec_len, px_len, ax_len, ws_len, mat_len;
+  long long arp_len, anz_len, brp_len, bnz_len, n_len, m_len, pmap_len, amap_len, bdiag_len;
+  long long avrp_len, av_len, wt_len, rows_len, islong_len;
+  const OSQPFloat *q, *l, *u;
+  OSQPFloat *x, *y, *rec;
+  const OSQPFloat *Px, *Ax;
+  OSQPFloat *ws, *mat_ws;
+  OSQPInt *A_rowptr, *A_col, *B_rowptr, *B_col;
+  OSQPFloat *A_val, *B_val, *D, *Dinv, *E, *Einv;
+  OSQPInt *Pm1, *Pm2, *pvmap, *AmA, *AmB, *avmap, *Bdiag;
+  OSQPFloat *Praw, *Araw;
+  OSQPInt *Av_rowptr, *Av_col, *vsrc, *wtpos, *rows, *islong;
+  OSQPFloat *Av_val, *WT;
+  OSQPInt n, m, nnzA, nnzB, nzP, nzA, G;          /* out */
+  long long ws_need, mat_need;                    /* out */
+  OSQPFloat c;                                    /* out (with the n_len group) */
+  OSQPInt r, GC, cb, nv;                          /* out: the direct route */
+  long long dws_need, dmat_need;                  /* out: the direct route */
+} OSQPHipLockstepTest;
+OSQPInt osqp_hip_test_lockstep(OSQPSolver *solver, OSQPHipLockstepTest *t);
 /* Weight of equality rows relative to inequality rows, rho_eq = factor * rho, used when equality and inequality rows are
    mixed (default 10; the reference's 1e3 is kept when every active row is an equality).  See engine.cpp (Engine::classify_constraints)
    classify_constraints() for the rationale.  Takes effect immediately (rho vector + preconditioner are rebuilt). */

@@ -752,6 +752,13 @@ struct WbProbe {
   int exact, info[2], done, iters; double gamma, rnorm;
 };
 int test_woodbury(Dev &d, WbProbe &p) __attribute__((weak));
+// single launches of the lockstep kernels (include/osqp_hip.h osqp_hip_test_lockstep, which has validated every field, staged the caller's arrays and uploaded
+// the blocks: nothing is checked here).  p: the parameters of a chunk as Engine::run_lockstep_solve builds them (ws / mat_ws: the route's resident blocks,
+// q .. Ax: DEVICE arrays).  The body carves the blocks as lockstep_chunk does, launches ops[0 .. nops) -- OSQPHipLockstepOp, one kernel launch each, through
+// the launch text of the drivers -- on d.stream, synchronises and answers hipGetLastError.  Weak like test_woodbury.
+// direct: the direct route (p.v: the view as Engine::fill_lockstep_direct_view fills it, with wtpos / vsrc where mat).
+struct LsProbe { LockstepDirectParams p; bool direct; int nops; const int *ops; };
+int test_lockstep(Dev &d, const LsProbe &t) __attribute__((weak));
 float time_kernel(Dev &d, int which, int reps);                             // mean ms per launch
 
 }  // namespace be

@@ -49,6 +49,7 @@ class Engine {
   int test_dense(OSQPHipDenseTest *t);
   int test_band(OSQPHipBandTest *t);
   int test_woodbury(OSQPHipWoodburyTest *t);
+  int test_lockstep(OSQPHipLockstepTest *t);
   int trace_read(unsigned long long *out, int count);
   int get_scaling(double *D, double *E, double *c);
   int get_reordering(int *perm_cols, int *perm_rows) const;
@@ -155,6 +156,7 @@ class Engine {
   int lsm_last_count_ = 0;                            // problems of the last chunk the last PCG-route solve with mat processed (0: none, or the block was overwritten since): what lockstep_mat_scaling reads
   int *d_pvmap_ = nullptr, *d_avmap_ = nullptr;       // device copies of PvalMap_ / AvalMap_ (reordered handle), uploaded by the first call that reads them
   bool ensure_value_maps();
+  void fill_lockstep_solve(LsRoute &rt, LockstepParams &p, bool direct, bool mat, int warm, size_t need, size_t mneed);   // what a forward chunk's parameters keep from chunk to chunk: run_lockstep_solve and test_lockstep
   void fill_lockstep_handle(LockstepParams &p);       // the handle's matrices, scalings, shared vectors and permutations: every lockstep route
   int last_record(const double *src, int cnt, double *rec) const;      // behind every *_last_record
   // direct route: the structural decision of prepare_wb (K0 diagonal, small mode -- not DevWb::exact, which a failed inversion clears), the view of A

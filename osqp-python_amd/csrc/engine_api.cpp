@@ -915,6 +915,22 @@ void Engine::fill_lockstep_handle(LockstepParams &p) {
   p.n = n; p.m = m; p.A = d_.A; p.B = d_.B; p.D = d_.D; p.Dinv = d_.Dinv; p.E = d_.E; p.Einv = d_.Einv;
   p.q0 = d_.qraw; p.l0 = d_.lraw; p.u0 = d_.uraw; p.pc = reordered_ ? d_pc_ : nullptr; p.pr = reordered_ ? d_pr_ : nullptr;
 }
+// The parameters of a forward chunk that do not change from chunk to chunk, for run_lockstep_solve and for the diagnostic entry (test_lockstep), which
+// therefore launches on what a solve launches on: the route's work block (allocated by the first call), the settings snapshot of the batch path, the
+// handle; with per-problem matrices the route's matrix block (allocated by the first such call, solve or adjoint), the value maps of a reordered handle
+// (PCG route; the direct route's position maps are its caller's) and the equilibration's iteration count.
+void Engine::fill_lockstep_solve(LsRoute &rt, LockstepParams &p, bool direct, bool mat, int warm, size_t need, size_t mneed) {
+  if (!rt.ws) { rt.ws = dev_vec<double>(d_, need); be::sync(d_); }
+  fill_batch_settings(p, warm);
+  fill_lockstep_handle(p);
+  p.ws = rt.ws;
+  if (!mat) return;
+  bool fresh = false;
+  if (!direct) { fresh = ensure_value_maps(); p.pvmap = reordered_ ? d_pvmap_ : nullptr; p.avmap = reordered_ ? d_avmap_ : nullptr; }
+  if (!rt.mat_ws) { rt.mat_ws = dev_vec<double>(d_, mneed); fresh = true; }
+  if (fresh) be::sync(d_);
+  p.mat_ws = rt.mat_ws; p.mat_iters = std::max(0, (int)settings.scaling);
+}
 // device copies of PvalMap_ / AvalMap_ (reordered handle; per-problem matrices and the adjoint read them); true: something was uploaded, sync before use
 bool Engine::ensure_value_maps() {
   bool fresh = false;
@@ -1014,20 +1030,10 @@ int Engine::run_lockstep_solve(bool direct, int nbatch, const LockstepSolveIO &a
   if (direct) if (const int err = fill_lockstep_direct_view(p.v, stream)) return err;
   const size_t need = direct ? lockstep_direct_ws_doubles(n, m, d_.wb.r) : lockstep_ws_doubles(n, m);
   const size_t mneed = direct ? lockstep_direct_mat_ws_doubles(n, m, d_.wb.r, d_.A.nnz, d_.B.nnz, lsd_nv_) : lockstep_mat_ws_doubles(n, m, d_.A.nnz, d_.B.nnz);
-  if (!rt.ws) { rt.ws = dev_vec<double>(d_, need); be::sync(d_); }
-  fill_batch_settings(p, a.warm);                     // the settings snapshot of the batch path
-  fill_lockstep_handle(p);
-  p.ws = rt.ws;
-  // per-problem matrices: the route's matrix block (allocated by the first such call, solve or adjoint) and what maps the caller's values into it
   double mst[kLsMatStat] = {0, 0}, mtot = 0;
-  if (mat) {
-    bool fresh = false;
-    if (direct) { prepare_lockstep_direct_wtpos(); p.v.wtpos = lsd_wtpos_; p.v.vsrc = lsd_vsrc_; }
-    else { fresh = ensure_value_maps(); p.pvmap = reordered_ ? d_pvmap_ : nullptr; p.avmap = reordered_ ? d_avmap_ : nullptr; }
-    if (!rt.mat_ws) { rt.mat_ws = dev_vec<double>(d_, mneed); fresh = true; }
-    if (fresh) be::sync(d_);
-    p.mat_ws = rt.mat_ws; p.mat_stat = mst; p.mat_iters = std::max(0, (int)settings.scaling);
-  }
+  if (mat && direct) { prepare_lockstep_direct_wtpos(); p.v.wtpos = lsd_wtpos_; p.v.vsrc = lsd_vsrc_; }
+  fill_lockstep_solve(rt, p, direct, mat, a.warm, need, mneed);
+  if (mat) p.mat_stat = mst;
   // polish (settings.polishing; with per-problem matrices too: the chunk polishes on its own matrix block): the recurrence of Engine::run_recurrence as
   // Engine::polish calls it, per problem on block vectors -- rho_bar = 1 / delta_eff, at least 1 + polish_refine_iter steps; on the PCG route the inner
   // systems to polish_pcg_tol within kMaxCg iterations, on the direct route the Woodbury solve with S_b inverted once per problem.  The work block is one
@@ -1596,6 +1602,131 @@ int Engine::test_woodbury(OSQPHipWoodburyTest *t) {
   for (long long k = 0; k < ord; k++) t->idx[k] = reordered_ ? (w.dual ? pc_[hidx[k]] : pr_[hidx[k]]) : hidx[k];
   t->form = w.dual ? 2 : (w.large ? 1 : 0); t->order = (int)ord; t->rows = w.r; t->exact = p.exact; t->info[0] = p.info[0]; t->info[1] = p.info[1];
   t->done = p.done; t->iters = p.iters; t->gamma = p.gamma; t->rnorm = p.rnorm;
+  return OSQP_NO_ERROR;
+}
+// Single launches of the lockstep kernels on the caller's blocks (include/osqp_hip.h osqp_hip_test_lockstep).  The sizes first, then EVERY check, then the
+// parameters as run_lockstep_solve builds them, the staging of the caller's arrays, the blocks up, be::test_lockstep, the blocks down.
+int Engine::test_lockstep(OSQPHipLockstepTest *t) {
+  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (!t) return OSQP_DATA_VALIDATION_ERROR;
+  const long long nn = n, mm = m, nnzA = d_.A.nnz, nnzB = d_.B.nnz, nzP = d_.nzP, nzA = d_.nzA;
+  t->n = n; t->m = m; t->nnzA = d_.A.nnz; t->nnzB = d_.B.nnz; t->nzP = d_.nzP; t->nzA = d_.nzA; t->G = lockstep_grid(n, m);
+  t->ws_need = (long long)lockstep_ws_doubles(n, m); t->mat_need = (long long)lockstep_mat_ws_doubles(n, m, d_.A.nnz, d_.B.nnz);
+  t->r = t->GC = t->cb = t->nv = 0; t->dws_need = t->dmat_need = 0;
+  if (!be::test_lockstep) return OSQP_FUNC_NOT_IMPLEMENTED;
+  // the direct route's sizes, where it takes the handle: the view is built as its first solve builds it (host work and uploads, no launch)
+  const bool dapplies = lockstep_direct_applies() && prepare_lockstep_direct_view() == OSQP_NO_ERROR;
+  const long long rr = dapplies ? d_.wb.r : 0, nv = dapplies ? lsd_nv_ : 0;
+  if (dapplies) {
+    t->r = d_.wb.r; t->GC = lockstep_direct_colblocks(n); t->cb = lockstep_direct_colblock(n); t->nv = lsd_nv_;
+    t->dws_need = (long long)lockstep_direct_ws_doubles(n, m, d_.wb.r); t->dmat_need = (long long)lockstep_direct_mat_ws_doubles(n, m, d_.wb.r, d_.A.nnz, d_.B.nnz, lsd_nv_);
+  }
+  const bool direct = t->route == 1;
+  const long long need = direct ? t->dws_need : t->ws_need, mneed = direct ? t->dmat_need : t->mat_need;
+  // ---- every check
+  if (!(t->route == 0 || t->route == 1) || !(t->mat == 0 || t->mat == 1) || !(t->warm == 0 || t->warm == 1)) return OSQP_DATA_VALIDATION_ERROR;
+  if (t->count < 1 || t->count > kLsW || t->nops < 1 || t->nops > 64 || !t->ops) return OSQP_DATA_VALIDATION_ERROR;
+  const bool mat = t->mat != 0;
+  if (direct && !dapplies) return OSQP_FUNC_NOT_IMPLEMENTED;                    // (the direct route's lengths exist only where it takes the handle)
+  for (int k = 0; k < t->nops; k++) {
+    const int op = t->ops[k];
+    if (op < 0 || op >= OSQP_HIP_LS_OP_COUNT) return OSQP_DATA_VALIDATION_ERROR;
+    const bool mat_op = (op >= OSQP_HIP_LS_BEGIN && op <= OSQP_HIP_LS_FINISH) || op == OSQP_HIP_LS_VALS || op == OSQP_HIP_LS_WT;
+    if (mat_op && !mat) return OSQP_DATA_VALIDATION_ERROR;
+    if (!direct && op >= OSQP_HIP_LS_D0) return OSQP_DATA_VALIDATION_ERROR;
+    // the direct route has no PCG (and no Kp): of the PCG route's kernels it launches the transposes, the state, rhs, upd, the residuals, initz and setrho
+    const bool pcg_only = op == OSQP_HIP_LS_MINV || op == OSQP_HIP_LS_T || op == OSQP_HIP_LS_KP || op == OSQP_HIP_LS_CGUPD || op == OSQP_HIP_LS_CGP ||
+                          op == OSQP_HIP_LS_CGINIT || op == OSQP_HIP_LS_CGALPHA || op == OSQP_HIP_LS_CGBETA;
+    if (direct && pcg_only) return OSQP_DATA_VALIDATION_ERROR;
+    if ((op == OSQP_HIP_LS_ASM_A && nzA == 0) || (op == OSQP_HIP_LS_ASM_P && nzP == 0)) return OSQP_DATA_VALIDATION_ERROR;
+    const bool m_only = op == OSQP_HIP_LS_LOAD_M || op == OSQP_HIP_LS_STORE_M || op == OSQP_HIP_LS_INITZ || op == OSQP_HIP_LS_T || op == OSQP_HIP_LS_RESM || op == OSQP_HIP_LS_SETRHO;
+    if (m_only && m == 0) return OSQP_DATA_VALIDATION_ERROR;
+  }
+  const long long cnt = t->count;
+  // an optional array: absent (NULL, length 0) or there with exactly `len`; a required one: there with exactly `len` (an empty one may be NULL)
+  auto optional = [](const void *p, long long have, long long len) { return p ? have == len : have == 0; };
+  auto required = [](const void *p, long long have, long long len) { return have == len && (p || len == 0); };
+  if (!optional(t->q, t->q_len, cnt * nn) || !optional(t->l, t->l_len, cnt * mm) || !optional(t->u, t->u_len, cnt * mm)) return OSQP_DATA_VALIDATION_ERROR;
+  if (!required(t->x, t->x_len, cnt * nn) || !required(t->y, t->y_len, cnt * mm) || !required(t->rec, t->rec_len, cnt * kBatchRec)) return OSQP_DATA_VALIDATION_ERROR;
+  if (!optional(t->Px, t->px_len, mat ? cnt * nzP : 0) || !optional(t->Ax, t->ax_len, mat ? cnt * nzA : 0)) return OSQP_DATA_VALIDATION_ERROR;
+  if (!required(t->ws, t->ws_len, need) || !t->ws) return OSQP_DATA_VALIDATION_ERROR;
+  if (mat ? (!t->mat_ws || t->mat_len != mneed) : (t->mat_ws || t->mat_len != 0)) return OSQP_DATA_VALIDATION_ERROR;
+  // the handle's arrays: a group is wanted as a whole or not at all
+  auto group = [](long long have, long long len, std::initializer_list<const void *> ptrs) {
+    bool any = false, all = true;
+    for (const void *p : ptrs) { any = any || p; all = all && p; }
+    return have == 0 ? (len == 0 || !any) : (have == len && all);      // (an array that is empty on this handle -- m = 0 -- may have any pointer)
+  };
+  if (!group(t->arp_len, mm + 1, {t->A_rowptr}) || !group(t->anz_len, nnzA, {t->A_col, t->A_val}) || !group(t->brp_len, nn + 1, {t->B_rowptr}) ||
+      !group(t->bnz_len, nnzB, {t->B_col, t->B_val}) || !group(t->n_len, nn, {t->D, t->Dinv}) || !group(t->m_len, mm, {t->E, t->Einv}) ||
+      !group(t->pmap_len, nzP, {t->Pm1, t->Pm2, t->pvmap, t->Praw}) || !group(t->amap_len, nzA, {t->AmA, t->AmB, t->avmap, t->Araw}) || !group(t->bdiag_len, nn, {t->Bdiag}))
+    return OSQP_DATA_VALIDATION_ERROR;
+  if ((t->pmap_len || t->amap_len || t->bdiag_len) && !(d_.Praw && d_.Araw && d_.Bdiag)) return OSQP_DATA_VALIDATION_ERROR;      // (a backend without device assembly keeps no maps)
+  // the direct route's view: with route 1 only (the lengths are then known: the route takes the handle, or the call is declined below with nothing written)
+  const bool view_wanted = t->avrp_len || t->av_len || t->wt_len || t->rows_len || t->islong_len || t->Av_rowptr || t->Av_col || t->Av_val || t->vsrc || t->WT || t->wtpos || t->rows || t->islong;
+  if (view_wanted && !direct) return OSQP_DATA_VALIDATION_ERROR;
+  if (direct && (!group(t->avrp_len, mm + 1, {t->Av_rowptr}) || !group(t->av_len, nv, {t->Av_col, t->Av_val, t->vsrc}) || !group(t->wt_len, nn * rr, {t->WT, t->wtpos}) ||
+                             !group(t->rows_len, rr, {t->rows}) || !group(t->islong_len, mm, {t->islong})))
+    return OSQP_DATA_VALIDATION_ERROR;
+  // ---- the route
+  if (!(this->*solve_applies(direct, mat))()) return OSQP_FUNC_NOT_IMPLEMENTED;
+  be::activate(d_);
+  be::ext_wait(d_);
+  // ---- the parameters of a chunk, as run_lockstep_solve builds them
+  LsRoute &rt = lsr_[direct];
+  be::LsProbe pr{};
+  pr.direct = direct;
+  LockstepDirectParams &p = pr.p;
+  if (direct) if (const int err = fill_lockstep_direct_view(p.v, nullptr)) return err;
+  if ((direct && mat) || t->wt_len) prepare_lockstep_direct_wtpos();
+  if (direct && mat) { p.v.wtpos = lsd_wtpos_; p.v.vsrc = lsd_vsrc_; }
+  fill_lockstep_solve(rt, p, direct, mat, t->warm, (size_t)need, (size_t)mneed);
+  p.count = t->count;
+  if (mat && !direct) lsm_last_count_ = 0;                                    // (the block is being overwritten)
+  // ---- the caller's arrays, staged on the device for the duration of the call
+  struct Buf { Dev &d; double *p; ~Buf() { if (p) be::dfree(d, p); } };
+  auto stage = [&](const double *src, long long len) -> double * {
+    if (!src) return nullptr;
+    double *dst = dev_vec<double>(d_, (size_t)len);
+    be::h2d(d_, dst, src, sizeof(double) * (size_t)len);
+    return dst;
+  };
+  Buf bq{d_, stage(t->q, t->q_len)}, bl{d_, stage(t->l, t->l_len)}, bu{d_, stage(t->u, t->u_len)}, bx{d_, stage(t->x, t->x_len)}, by{d_, stage(t->y, t->y_len)};
+  Buf brec{d_, stage(t->rec, t->rec_len)}, bPx{d_, stage(t->Px, t->px_len)}, bAx{d_, stage(t->Ax, t->ax_len)};
+  Buf by0{d_, (!by.p) ? dev_vec<double>(d_, 1) : nullptr};                     // (m = 0: a solve's y is a valid pointer that no kernel follows)
+  p.q = bq.p; p.l = bl.p; p.u = bu.p; p.x = bx.p; p.y = by.p ? by.p : by0.p; p.rec = brec.p; p.Px = bPx.p; p.Ax = bAx.p;
+  be::h2d(d_, rt.ws, t->ws, sizeof(double) * (size_t)need);
+  if (mat) be::h2d(d_, rt.mat_ws, t->mat_ws, sizeof(double) * (size_t)mneed);
+  be::sync(d_);
+  pr.nops = t->nops; pr.ops = t->ops;
+  const int st = be::test_lockstep(d_, pr);
+  if (st != OSQP_NO_ERROR) return st;
+  be::d2h(d_, t->ws, rt.ws, sizeof(double) * (size_t)need);
+  if (mat) be::d2h(d_, t->mat_ws, rt.mat_ws, sizeof(double) * (size_t)mneed);
+  if (t->x_len) be::d2h(d_, t->x, bx.p, sizeof(double) * (size_t)t->x_len);
+  if (t->y_len) be::d2h(d_, t->y, by.p, sizeof(double) * (size_t)t->y_len);
+  be::d2h(d_, t->rec, brec.p, sizeof(double) * (size_t)t->rec_len);
+  // ---- what the references need of the handle
+  auto ints = [&](int *dst, const int *src, long long len) { if (dst && len) be::d2h(d_, dst, src, sizeof(int) * (size_t)len); };
+  auto dbls = [&](double *dst, const double *src, long long len) { if (dst && len) be::d2h(d_, dst, src, sizeof(double) * (size_t)len); };
+  ints(t->A_rowptr, d_.A.rowptr, t->arp_len); ints(t->A_col, d_.A.col, t->anz_len); dbls(t->A_val, d_.A.val, t->anz_len);
+  ints(t->B_rowptr, d_.B.rowptr, t->brp_len); ints(t->B_col, d_.B.col, t->bnz_len); dbls(t->B_val, d_.B.val, t->bnz_len);
+  dbls(t->D, d_.D, t->n_len); dbls(t->Dinv, d_.Dinv, t->n_len); dbls(t->E, d_.E, t->m_len); dbls(t->Einv, d_.Einv, t->m_len);
+  ints(t->Pm1, d_.Pm1, t->pmap_len); ints(t->Pm2, d_.Pm2, t->pmap_len); dbls(t->Praw, d_.Praw, t->pmap_len);
+  ints(t->AmA, d_.AmA, t->amap_len); ints(t->AmB, d_.AmB, t->amap_len); dbls(t->Araw, d_.Araw, t->amap_len);
+  ints(t->Bdiag, d_.Bdiag, t->bdiag_len);
+  for (long long k = 0; k < t->pmap_len; k++) t->pvmap[k] = reordered_ ? PvalMap_[k] : (int)k;
+  for (long long k = 0; k < t->amap_len; k++) t->avmap[k] = reordered_ ? AvalMap_[k] : (int)k;
+  t->c = c_;
+  if (direct) {
+    ints(t->Av_rowptr, lsd_vrp_, t->avrp_len); ints(t->Av_col, lsd_vcol_, t->av_len); dbls(t->Av_val, lsd_vval_, t->av_len); ints(t->vsrc, lsd_vsrc_, t->av_len);
+    dbls(t->WT, d_.wb.WT, t->wt_len); ints(t->wtpos, lsd_wtpos_, t->wt_len); ints(t->rows, d_.wb.rows, t->rows_len);
+    if (t->islong_len) {
+      std::vector<unsigned char> fl((size_t)m);
+      be::d2h(d_, fl.data(), d_.wb.islong, (size_t)m);
+      for (int i = 0; i < m; i++) t->islong[i] = fl[i];
+    }
+  }
   return OSQP_NO_ERROR;
 }
 int Engine::get_reordering(int *perm_cols, int *perm_rows) const {

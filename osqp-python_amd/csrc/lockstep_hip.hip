@@ -1473,17 +1473,63 @@ struct LsPcgKernels {
 constexpr LsPcgKernels kLsShared = {k_ls_load_n, k_ls_load_m, k_ls_minv, k_ls_initz, k_ls_rhs, k_ls_t, k_ls_kp, k_ls_upd, k_ls_resm, k_ls_resn, k_ls_decide, k_ls_store_n, k_ls_store_m};
 constexpr LsPcgKernels kLsOwnMat = {k_lsm_load_n, k_lsm_load_m, k_lsm_minv, k_lsm_initz, k_lsm_rhs, k_lsm_t, k_lsm_kp, k_lsm_upd, k_lsm_resm, k_lsm_resn, k_lsm_decide, k_lsm_store_n, k_lsm_store_m};
 
+// ONE LAUNCH of a forward kernel of the PCG route, by its public name (include/osqp_hip.h OSQPHipLockstepOp): the kernel, its arguments and ITS GRID are
+// stated here once, for every driver below and for the diagnostic entry (test_lockstep), which therefore launches what a solve launches.  The grids: G
+// workgroups for the row passes and the elementwise kernels (k.w.G: lockstep_grid), the 64-wide tiles of n / m for the transposes, one workgroup for the
+// folds and the state.  (decide, the adjoint's, polish's and the direct route's own kernels are launched where they are used.)
+inline int ls_tiles(int cnt) { return (cnt + 63) / 64; }
+void ls_go(LsRun &R, const LsPcgKernels &K, int op, const LsK &k) {
+  const int G = k.w.G, tn = ls_tiles(k.P.n), tm = ls_tiles(k.P.m);
+  switch (op) {
+    case OSQP_HIP_LS_LOAD_N: R.go(K.load_n, tn, k); break;
+    case OSQP_HIP_LS_LOAD_M: R.go(K.load_m, tm, k); break;
+    case OSQP_HIP_LS_INIT: R.go(k_ls_init, 1, k, k.P.m > 0 ? tm : 0); break;
+    case OSQP_HIP_LS_STORE_N: R.go(K.store_n, tn, k); break;
+    case OSQP_HIP_LS_STORE_M: R.go(K.store_m, tm, k); break;
+    case OSQP_HIP_LS_MINV: R.go(K.minv, G, k); break;
+    case OSQP_HIP_LS_INITZ: R.go(K.initz, G, k); break;
+    case OSQP_HIP_LS_RHS: R.go(K.rhs, G, k); break;
+    case OSQP_HIP_LS_T: R.go(K.t, G, k); break;
+    case OSQP_HIP_LS_KP: R.go(K.kp, G, k); break;
+    case OSQP_HIP_LS_UPD: R.go(K.upd, G, k); break;
+    case OSQP_HIP_LS_RESM: R.go(K.resm, G, k); break;
+    case OSQP_HIP_LS_RESN: R.go(K.resn, G, k); break;
+    case OSQP_HIP_LS_SETRHO: R.go(k_ls_setrho, G, k); break;
+    case OSQP_HIP_LS_CGUPD: R.go(k_ls_cgupd, G, k); break;
+    case OSQP_HIP_LS_CGP: R.go(k_ls_cgp, G, k); break;
+    case OSQP_HIP_LS_CGINIT: R.go(k_ls_cginit, 1, k); break;
+    case OSQP_HIP_LS_CGALPHA: R.go(k_ls_cgalpha, 1, k); break;
+    case OSQP_HIP_LS_CGBETA: R.go(k_ls_cgbeta, 1, k); break;
+    default: throw std::logic_error("ls_go: not a forward kernel of the PCG route");
+  }
+}
+// the same for the matrices of a chunk: 64 stored entries per workgroup for the assembly
+void ls_mat_go(LsRun &R, int op, const LsMK &km) {
+  const int G = km.w.G;
+  switch (op) {
+    case OSQP_HIP_LS_BEGIN: R.go(k_lsm_begin, ls_tiles(km.P.n), km); break;
+    case OSQP_HIP_LS_ASM_A: R.go(k_lsm_asm<false>, ls_tiles(km.t.nzA), km); break;
+    case OSQP_HIP_LS_ASM_P: R.go(k_lsm_asm<true>, ls_tiles(km.t.nzP), km); break;
+    case OSQP_HIP_LS_NORMS: R.go(k_lsm_norms, G, km); break;
+    case OSQP_HIP_LS_SCALE: R.go(k_lsm_scale, G, km); break;
+    case OSQP_HIP_LS_COST: R.go(k_lsm_cost, 1, km); break;
+    case OSQP_HIP_LS_COST_APPLY: R.go(k_lsm_cost_apply, G, km); break;
+    case OSQP_HIP_LS_FINISH: R.go(k_lsm_finish, G, km); break;
+    default: throw std::logic_error("ls_mat_go: not a kernel of the matrices of a chunk");
+  }
+}
+
 // One PCG solve for every problem of the chunk: as many iterations as the previous solve needed (+ 1: est) are enqueued without synchronising; then the
 // host reads the words and goes on in groups of four while some problem's PCG is still running, up to cg_max.  The estimate decides how many launches
 // return at once, never how far a problem's PCG runs.
 void ls_pcg(LsRun &R, const LsPcgKernels &K, const LsK &k, int &est) {
-  const int G = k.w.G, cg_max = k.P.cg_max;
-  R.go(K.rhs, G, k);
-  R.go(k_ls_cginit, 1, k);
+  const int cg_max = k.P.cg_max;
+  ls_go(R, K, OSQP_HIP_LS_RHS, k);
+  ls_go(R, K, OSQP_HIP_LS_CGINIT, k);
   for (int it = 0, grp = est; it < cg_max; grp = 4) {
     for (const int end = std::min(it + grp, cg_max); it < end; it++) {
-      if (k.P.m > 0) R.go(K.t, G, k);
-      R.go(K.kp, G, k); R.go(k_ls_cgalpha, 1, k); R.go(k_ls_cgupd, G, k); R.go(k_ls_cgbeta, 1, k); R.go(k_ls_cgp, G, k);
+      if (k.P.m > 0) ls_go(R, K, OSQP_HIP_LS_T, k);
+      ls_go(R, K, OSQP_HIP_LS_KP, k); ls_go(R, K, OSQP_HIP_LS_CGALPHA, k); ls_go(R, K, OSQP_HIP_LS_CGUPD, k); ls_go(R, K, OSQP_HIP_LS_CGBETA, k); ls_go(R, K, OSQP_HIP_LS_CGP, k);
     }
     R.fetch();
     if (!R.words[WD_CGANY]) break;
@@ -1499,8 +1545,8 @@ int ls_recurrence(LsRun &R, const LsPcgKernels &K, const LsK &km, const LsK &kn,
   while (R.words[WD_LIVE] > 0 && steps < max_steps) {
     steps++;
     step();
-    if (km.P.m > 0) R.go(K.resm, km.w.G, km);
-    R.go(K.resn, kn.w.G, kn);
+    if (km.P.m > 0) ls_go(R, K, OSQP_HIP_LS_RESM, km);
+    ls_go(R, K, OSQP_HIP_LS_RESN, kn);
     decide();
     R.fetch();
   }
@@ -1520,13 +1566,12 @@ int ls_mat_block(const Dev &d, LockstepParams &P, LsMat &mt) {
   return OSQP_NO_ERROR;
 }
 void ls_mat_prepare(LsRun &R, const LsMK &km) {
-  const int G = km.w.G, tn = (km.P.n + 63) / 64;
   const long launches0 = R.launches;
-  R.go(k_lsm_begin, tn, km);
-  if (km.t.nzA > 0) R.go(k_lsm_asm<false>, (km.t.nzA + 63) / 64, km);
-  if (km.t.nzP > 0) R.go(k_lsm_asm<true>, (km.t.nzP + 63) / 64, km);
-  for (int it = 0; it < km.P.mat_iters; it++) { R.go(k_lsm_norms, G, km); R.go(k_lsm_scale, G, km); R.go(k_lsm_cost, 1, km); R.go(k_lsm_cost_apply, G, km); }
-  R.go(k_lsm_finish, G, km);
+  ls_mat_go(R, OSQP_HIP_LS_BEGIN, km);
+  if (km.t.nzA > 0) ls_mat_go(R, OSQP_HIP_LS_ASM_A, km);
+  if (km.t.nzP > 0) ls_mat_go(R, OSQP_HIP_LS_ASM_P, km);
+  for (int it = 0; it < km.P.mat_iters; it++) { ls_mat_go(R, OSQP_HIP_LS_NORMS, km); ls_mat_go(R, OSQP_HIP_LS_SCALE, km); ls_mat_go(R, OSQP_HIP_LS_COST, km); ls_mat_go(R, OSQP_HIP_LS_COST_APPLY, km); }
+  ls_mat_go(R, OSQP_HIP_LS_FINISH, km);
   R.em.record(R.s);
   if (km.P.mat_stat) km.P.mat_stat[1] = (double)(R.launches - launches0);
 }
@@ -1559,25 +1604,50 @@ struct LwRun {
     if (lds_inv > 64 * 1024) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_lw_inv), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_inv));
   }
   const LsPcgKernels &K() const { return mat ? kLsOwnMat : kLsShared; }
-  void prod(LsRun &R, const double *v, double *out) const { if (mat) R.go(k_lwm_prod, GC * ((r + 7) / 8), k, v, out); else R.go(k_lw_prod, GC, k, v, out); }
+  // the chunk's own dense rows and view values (per-problem matrices): what k_lwm_wt / k_lwm_vals fill, from the matrix block's scaled A
+  const double *Aval = nullptr; const int *wtpos = nullptr, *vsrc = nullptr; double *WTown = nullptr, *vval = nullptr; int nv = 0;
+  void own(const double *aval, const LockstepDirectView &v, const LwMatVecs &xm) { Aval = aval; wtpos = v.wtpos; vsrc = v.vsrc; WTown = xm.WT; vval = xm.vval; nv = v.Av.nnz; }
+  // ONE LAUNCH of the direct route, by its public name (include/osqp_hip.h OSQPHipLockstepOp): kernel, arguments, grid and dynamic LDS stated here once, for
+  // the launch groups below, the chunk functions and the diagnostic entry (test_lockstep).  The PCG route's kernels this route reuses go through ls_go with
+  // the argument view that belongs to them: initz and resm read A through the view (kv), upd runs over n + r rows (ku), the others see the handle (kb).
+  // The grids: G for d0 and x, a workgroup per (row a, eight columns) of S, a workgroup per problem for the inversion (S_b and a column in dynamic LDS,
+  // raised above 64 KB in the constructor), the column blocks for the products -- times the groups of eight rows with per-problem matrices --, one
+  // workgroup for setl, sixteen rows of h per workgroup, a wave per entry (at most 1024 workgroups) for the chunk's own WT and view values.
+  const LsK &arg(int op) const { return (op == OSQP_HIP_LS_INITZ || op == OSQP_HIP_LS_RESM) ? kv : (op == OSQP_HIP_LS_UPD ? ku : kb); }
+  void prod_to(LsRun &R, const double *v, double *out) const { if (mat) R.go(k_lwm_prod, GC * ((r + 7) / 8), k, v, out); else R.go(k_lw_prod, GC, k, v, out); }
+  void go(LsRun &R, int op) const {
+    switch (op) {
+      case OSQP_HIP_LS_D0: R.go(mat ? k_lwm_d0 : k_lw_d0, G, k); break;
+      case OSQP_HIP_LS_S: R.go(mat ? k_lwm_s : k_lw_s, r * ((r + 7) / 8), k); break;
+      case OSQP_HIP_LS_INV: R.gol(k_lw_inv, W, lds_inv, k); break;
+      case OSQP_HIP_LS_PROD_X: prod_to(R, k.w.x, k.d.pg); break;
+      case OSQP_HIP_LS_PROD_XS: prod_to(R, k.w.xs, k.d.pg2); break;
+      case OSQP_HIP_LS_PROD_P: prod_to(R, k.w.p, k.d.pg); break;
+      case OSQP_HIP_LS_PROD2:
+        if (mat) R.go(k_lwm_prod2, GC * ((r + 7) / 8), k, (const double *)k.w.x, (const double *)k.w.xs, k.d.pg, k.d.pg2);
+        else R.go(k_lw_prod2, GC, k, (const double *)k.w.x, (const double *)k.w.xs, k.d.pg, k.d.pg2);
+        break;
+      case OSQP_HIP_LS_SETL0: R.go(k_lw_setl, 1, k, 0); break;
+      case OSQP_HIP_LS_SETL1: R.go(k_lw_setl, 1, k, 1); break;
+      case OSQP_HIP_LS_H: R.gol(k_lw_h, (r + 15) / 16, lds_h, k); break;
+      case OSQP_HIP_LS_X: R.gol(mat ? k_lwm_x : k_lw_x, G, lds_h, k); break;
+      case OSQP_HIP_LS_WT: { const int nwt = k.P.n * r; R.go(k_lwm_wt, std::min(1024, (nwt + 3) / 4), nwt, wtpos, Aval, WTown); break; }
+      case OSQP_HIP_LS_VALS: R.go(k_lwm_vals, std::min(1024, (nv + 3) / 4), nv, vsrc, Aval, vval); break;
+      default: ls_go(R, K(), op, arg(op));
+    }
+  }
+  // x -> pg for another operand (the adjoint's and polish's own vectors)
+  void prod(LsRun &R, const double *v, double *out) const { prod_to(R, v, out); }
   // rho from rho_bar, D0, S and its inverse (for the problems whose rho has just been set)
-  void factor(LsRun &R) const { R.go(k_ls_setrho, G, kb); R.go(mat ? k_lwm_d0 : k_lw_d0, G, k); R.go(mat ? k_lwm_s : k_lw_s, r * ((r + 7) / 8), k); R.gol(k_lw_inv, W, lds_inv, k); }
+  void factor(LsRun &R) const { go(R, OSQP_HIP_LS_SETRHO); go(R, OSQP_HIP_LS_D0); go(R, OSQP_HIP_LS_S); go(R, OSQP_HIP_LS_INV); }
   // x~ by the Woodbury formula, then the ADMM update
-  void solve(LsRun &R) const {
-    R.go(K().rhs, G, kb);
-    prod(R, k.w.p, k.d.pg);
-    R.gol(k_lw_h, (r + 15) / 16, lds_h, k);
-    R.gol(mat ? k_lwm_x : k_lw_x, G, lds_h, k);
-    R.go(K().upd, G, ku);
-  }
+  void solve(LsRun &R) const { go(R, OSQP_HIP_LS_RHS); go(R, OSQP_HIP_LS_PROD_P); go(R, OSQP_HIP_LS_H); go(R, OSQP_HIP_LS_X); go(R, OSQP_HIP_LS_UPD); }
   // the rows n .. n + r - 1 of x and x~ from the products
-  void long_rows(LsRun &R, int start) const { prod(R, k.w.x, k.d.pg); prod(R, k.w.xs, k.d.pg2); R.go(k_lw_setl, 1, k, start); }
+  void long_rows(LsRun &R, int start) const { go(R, OSQP_HIP_LS_PROD_X); go(R, OSQP_HIP_LS_PROD_XS); go(R, start ? OSQP_HIP_LS_SETL1 : OSQP_HIP_LS_SETL0); }
   // the same rows with both products from one pass over WT (k_lw_prod2: the same partials bit for bit); polish's recurrence
-  void long_rows2(LsRun &R) const {
-    if (mat) R.go(k_lwm_prod2, GC * ((r + 7) / 8), k, (const double *)k.w.x, (const double *)k.w.xs, k.d.pg, k.d.pg2);
-    else R.go(k_lw_prod2, GC, k, (const double *)k.w.x, (const double *)k.w.xs, k.d.pg, k.d.pg2);
-    R.go(k_lw_setl, 1, k, 0);
-  }
+  void long_rows2(LsRun &R) const { go(R, OSQP_HIP_LS_PROD2); go(R, OSQP_HIP_LS_SETL0); }
+  // the chunk's own dense rows and view values from the matrix block's scaled A (per-problem matrices; after ls_mat_prepare)
+  void own_rows(LsRun &R) const { go(R, OSQP_HIP_LS_WT); go(R, OSQP_HIP_LS_VALS); }
 };
 
 }  // namespace
@@ -1587,7 +1657,7 @@ struct LwRun {
 // stat: {ADMM iterations of the slowest problem, PCG iterations summed, kernel launches, GPU ms}.
 int lockstep_chunk(Dev &d, const LockstepParams &p, void *stream, double *stat) {
   const hipStream_t s = ls_stream(d, stream);
-  const int n = p.n, m = p.m, tn = (n + 63) / 64, tm = (m + 63) / 64;
+  const int n = p.n, m = p.m;
   const bool mat = p.mat_ws != nullptr, pol = p.polish && p.pol_ws;
   LsK k{p, {}};
   LsMat mt{};
@@ -1605,21 +1675,21 @@ int lockstep_chunk(Dev &d, const LockstepParams &p, void *stream, double *stat) 
   if (mat) ls_mat_prepare(R, LsMK{k.P, w, mt});
   const double t_begin = ls_now();
   auto late_now = [&]() { return p.time_limit > 0 && ls_now() - t_begin > p.time_limit; };
-  auto residuals = [&]() { if (m > 0) R.go(K.resm, G, k); R.go(K.resn, G, k); };
-  auto new_rho = [&]() { if (m > 0) R.go(k_ls_setrho, G, k); R.go(K.minv, G, k); };
+  auto residuals = [&]() { if (m > 0) ls_go(R, K, OSQP_HIP_LS_RESM, k); ls_go(R, K, OSQP_HIP_LS_RESN, k); };
+  auto new_rho = [&]() { if (m > 0) ls_go(R, K, OSQP_HIP_LS_SETRHO, k); ls_go(R, K, OSQP_HIP_LS_MINV, k); };
 
-  R.go(K.load_n, tn, k);
-  if (m > 0) R.go(K.load_m, tm, k);
-  R.go(k_ls_init, 1, k, m > 0 ? tm : 0);
+  ls_go(R, K, OSQP_HIP_LS_LOAD_N, k);
+  if (m > 0) ls_go(R, K, OSQP_HIP_LS_LOAD_M, k);
+  ls_go(R, K, OSQP_HIP_LS_INIT, k);
   new_rho();
-  if (m > 0) R.go(K.initz, G, k);
+  if (m > 0) ls_go(R, K, OSQP_HIP_LS_INITZ, k);
   residuals();
   R.go(K.decide, 1, k, 0, 0, 0, 1);
   int iter = 0, cg_est = 4;
   while (R.words[WD_LIVE] > 0 && iter < p.max_iter) {
     iter++;
     ls_pcg(R, K, k, cg_est);
-    R.go(K.upd, G, k);
+    ls_go(R, K, OSQP_HIP_LS_UPD, k);
     const int at_check = (p.check > 0 && iter % p.check == 0) || iter >= p.max_iter;
     const int at_rho = p.rho_interval > 0 && iter % p.rho_interval == 0;
     const bool late = late_now();
@@ -1645,13 +1715,13 @@ int lockstep_chunk(Dev &d, const LockstepParams &p, void *stream, double *stat) 
     pcg_admm = R.words[WD_PCGSUM]; pol_att = R.words[WD_LIVE];
     if (pol_att > 0) {
       R.go(k_ls_pol_class, G, kq);
-      if (m > 0) R.go(k_ls_setrho, G, kp);
-      R.go(K.minv, G, kp);
+      if (m > 0) ls_go(R, K, OSQP_HIP_LS_SETRHO, kp);
+      ls_go(R, K, OSQP_HIP_LS_MINV, kp);
       int cg_pol = 4;
-      pol_steps = ls_recurrence(R, K, kp, kp, kLsPolMaxSteps, [&]() { ls_pcg(R, K, kp, cg_pol); R.go(K.upd, G, kp); }, [&]() { R.go(k_ls_pol_decide, 1, kq); });
+      pol_steps = ls_recurrence(R, K, kp, kp, kLsPolMaxSteps, [&]() { ls_pcg(R, K, kp, cg_pol); ls_go(R, K, OSQP_HIP_LS_UPD, kp); }, [&]() { R.go(k_ls_pol_decide, 1, kq); });
       pol_pcg = R.words[WD_PCGSUM];
-      if (m > 0) { R.go(mat ? k_lsm_pol_cone : k_ls_pol_cone, G, kq); R.go(K.resm, G, kp); }
-      R.go(K.resn, G, kp);
+      if (m > 0) { R.go(mat ? k_lsm_pol_cone : k_ls_pol_cone, G, kq); ls_go(R, K, OSQP_HIP_LS_RESM, kp); }
+      ls_go(R, K, OSQP_HIP_LS_RESN, kp);
       R.go(mat ? k_lsm_pol_accept : k_ls_pol_accept, 1, kq);
       R.fetch();
       R.go(k_ls_pol_end, G, kq, ls_now() - t_pol);
@@ -1659,8 +1729,8 @@ int lockstep_chunk(Dev &d, const LockstepParams &p, void *stream, double *stat) 
     R.ep1.record(s);
     pol_launches = R.launches - launches0;
   }
-  R.go(K.store_n, tn, k);
-  if (m > 0) R.go(K.store_m, tm, k);
+  ls_go(R, K, OSQP_HIP_LS_STORE_N, k);
+  if (m > 0) ls_go(R, K, OSQP_HIP_LS_STORE_M, k);
   const float ms = R.finish(), pms = polished ? LsRun::ms(R.ep0, R.ep1) : 0.f;
   if (mat && p.mat_stat) p.mat_stat[0] = LsRun::ms(R.e0, R.em);
   // (the chunk's statistics are the ADMM part's; polish's go to their own block)
@@ -1669,6 +1739,55 @@ int lockstep_chunk(Dev &d, const LockstepParams &p, void *stream, double *stat) 
     double *ps = p.pol_stat;
     ps[0] = pol_att; ps[1] = R.words[WD_POLACC]; ps[2] = R.words[WD_POLREJ]; ps[3] = pol_steps; ps[4] = pol_pcg; ps[5] = (double)pol_launches; ps[6] = pms;
   }
+  return OSQP_NO_ERROR;
+}
+
+// Diagnostic (backend.h LsProbe; include/osqp_hip.h osqp_hip_test_lockstep, which has validated everything and uploaded the blocks): the carve of
+// lockstep_chunk, then the listed ops -- one launch each through ls_go / ls_mat_go, the drivers' own launch text -- on the solver's stream.  No host loop,
+// no event, no read of the words.
+int test_lockstep(Dev &d, const LsProbe &t) {
+  const hipStream_t s = ls_stream(d, nullptr);
+  const int n = t.p.n, m = t.p.m;
+  const bool mat = t.p.mat_ws != nullptr;
+  LockstepDirectParams p = t.p;
+  LsWs w;
+  LsMat mt{};
+  LsCursor c{p.ws};
+  if (!t.direct) {
+    if (!lockstep_layout(c, n, m, w, nullptr)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+    if (mat) if (const int err = ls_mat_block(d, p, mt)) return err;
+    const LsK k{p, w};
+    const LsPcgKernels &K = mat ? kLsOwnMat : kLsShared;
+    const LsMK km{p, w, mt};
+    LsRun R(s, w.word, p.count);
+    for (int i = 0; i < t.nops; i++) {
+      if (t.ops[i] >= OSQP_HIP_LS_BEGIN) ls_mat_go(R, t.ops[i], km);
+      else ls_go(R, K, t.ops[i], k);
+    }
+  } else {                                               // the direct route: lockstep_direct_chunk's carve and LwRun
+    const int r = p.v.r;
+    LwVecs x;
+    LwMatVecs xm{};
+    if (!lockstep_direct_layout(c, n, m, r, w, x, nullptr)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+    if (mat) {
+      if (!p.v.wtpos || !p.v.vsrc) return OSQP_FUNC_NOT_IMPLEMENTED;
+      if (const int err = ls_mat_block(d, p, mt)) return err;
+      LsCursor cm{p.mat_ws};
+      LsMatVecs again;
+      if (!lockstep_direct_mat_layout(cm, n, m, r, p.A.nnz, p.B.nnz, p.v.Av.nnz, again, xm)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+      p.v.WT = xm.WT; p.v.Av.val = xm.vval;
+    }
+    LwRun D(p, p.v, w, x, mat);
+    if (mat) D.own(mt.Aval, p.v, xm);
+    const LsMK km{p, w, mt};
+    LsRun R(s, w.word, p.count);
+    for (int i = 0; i < t.nops; i++) {
+      if (t.ops[i] >= OSQP_HIP_LS_BEGIN && t.ops[i] <= OSQP_HIP_LS_FINISH) ls_mat_go(R, t.ops[i], km);
+      else D.go(R, t.ops[i]);
+    }
+  }
+  HIP_CHECK(hipStreamSynchronize(s));
+  HIP_CHECK(hipGetLastError());
   return OSQP_NO_ERROR;
 }
 
@@ -1683,7 +1802,7 @@ int lockstep_chunk(Dev &d, const LockstepParams &p, void *stream, double *stat) 
 // forward's); no kernel of the backward pass writes them -- k_ls_adj_init sets the rows below SC_C it needs, the PCG's folds SC_RZ .. SC_BETA.
 int lockstep_adjoint_chunk(Dev &d, const LockstepAdjointParams &p, void *stream, double *stat) {
   const hipStream_t s = ls_stream(d, stream);
-  const int n = p.n, m = p.m, tn = (n + 63) / 64, tm = (m + 63) / 64;
+  const int n = p.n, m = p.m, tn = ls_tiles(n), tm = ls_tiles(m);
   const bool mat = p.mat_ws != nullptr;
   LsAK ka{p, {}, {}};
   LsMat mt{};
@@ -1700,11 +1819,11 @@ int lockstep_adjoint_chunk(Dev &d, const LockstepAdjointParams &p, void *stream,
   R.go(mat ? k_lsm_adj_load_n : k_ls_adj_load_n, tn, ka);
   if (m > 0) { R.go(k_ls_adj_load_m, tm, ka); R.go(mat ? k_lsm_adj_class : k_ls_adj_class, G, ka); }
   R.go(k_ls_adj_init, 1, ka);
-  if (m > 0) R.go(k_ls_setrho, G, k);
-  R.go(K.minv, G, k);
+  if (m > 0) ls_go(R, K, OSQP_HIP_LS_SETRHO, k);
+  ls_go(R, K, OSQP_HIP_LS_MINV, k);
   R.fetch();
   int cg_est = 4;
-  const int step = ls_recurrence(R, K, k, k, p.max_steps, [&]() { ls_pcg(R, K, k, cg_est); R.go(K.upd, G, k); }, [&]() { R.go(k_ls_adj_decide, 1, ka); });
+  const int step = ls_recurrence(R, K, k, k, p.max_steps, [&]() { ls_pcg(R, K, k, cg_est); ls_go(R, K, OSQP_HIP_LS_UPD, k); }, [&]() { R.go(k_ls_adj_decide, 1, ka); });
   R.go(mat ? k_lsm_adj_unscale : k_ls_adj_unscale, G, ka);
   if (m > 0) R.go(mat ? k_lsm_adj_resm : k_ls_adj_resm, G, ka);
   R.go(mat ? k_lsm_adj_resn : k_ls_adj_resn, G, ka);
@@ -1729,7 +1848,7 @@ int lockstep_adjoint_chunk(Dev &d, const LockstepAdjointParams &p, void *stream,
 // kernels that read matrix values are the k_lwm_* forms; D0_b, S_b and S_b^-1 follow from them per lane.  The handle's own arrays are only read.
 int lockstep_direct_chunk(Dev &d, const LockstepDirectParams &p0, void *stream, double *stat) {
   const hipStream_t s = ls_stream(d, stream);
-  const int n = p0.n, m = p0.m, r = p0.v.r, tn = (n + 63) / 64, tm = (m + 63) / 64;
+  const int n = p0.n, m = p0.m, r = p0.v.r;
   const bool mat = p0.mat_ws != nullptr;
   if (r < 1 || r > kWbMaxRows || m < 1) return OSQP_FUNC_NOT_IMPLEMENTED;
   LsWs w;
@@ -1750,30 +1869,29 @@ int lockstep_direct_chunk(Dev &d, const LockstepDirectParams &p0, void *stream, 
   LsPolWs pws{};
   LsCursor cp{p.pol_ws};
   if (p.polish && p.pol_ws && !lockstep_polish_layout(cp, n, m, pws)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  const LwRun D(p, p.v, w, x, mat);
+  LwRun D(p, p.v, w, x, mat);
+  if (mat) D.own(mt.Aval, p.v, xm);
   const LsK &kb = D.kb, &kv = D.kv;
   const LsPcgKernels &K = D.K();
   const int G = w.G;
   LsRun R(s, w.word, p.count);
   R.e0.record(s);
   if (mat) {
-    const int nv = p.v.Av.nnz, nwt = n * r;
     ls_mat_prepare(R, LsMK{p, w, mt});
-    R.go(k_lwm_wt, std::min(1024, (nwt + 3) / 4), nwt, p.v.wtpos, (const double *)mt.Aval, xm.WT);
-    R.go(k_lwm_vals, std::min(1024, (nv + 3) / 4), nv, p.v.vsrc, (const double *)mt.Aval, xm.vval);
+    D.own_rows(R);
     R.em.record(s);
     if (p.mat_stat) p.mat_stat[1] += 2;
   }
   const double t_begin = R.t_sync;
-  auto residuals = [&]() { R.go(K.resm, G, kv); R.go(K.resn, G, kb); };
+  auto residuals = [&]() { D.go(R, OSQP_HIP_LS_RESM); D.go(R, OSQP_HIP_LS_RESN); };
 
   HIP_CHECK(hipMemsetAsync(x.fact, 0, sizeof(int) * W, s));
-  R.go(K.load_n, tn, kb);
-  R.go(K.load_m, tm, kb);
-  R.go(k_ls_init, 1, kb, tm);
+  D.go(R, OSQP_HIP_LS_LOAD_N);
+  D.go(R, OSQP_HIP_LS_LOAD_M);
+  D.go(R, OSQP_HIP_LS_INIT);
   D.factor(R);
   D.long_rows(R, 1);
-  R.go(K.initz, G, kv);
+  D.go(R, OSQP_HIP_LS_INITZ);
   residuals();
   R.go(K.decide, 1, kb, 0, 0, 0, 1);
   int iter = 0;
@@ -1818,8 +1936,8 @@ int lockstep_direct_chunk(Dev &d, const LockstepDirectParams &p0, void *stream, 
       Dp.prod(R, w.x, x.pg);
       R.go(k_lwa_setl, (r + 3) / 4, Dp.k, w.x);
       R.go(mat ? k_lsm_pol_cone : k_ls_pol_cone, G, kq);
-      R.go(K.resm, G, Dp.kv);
-      R.go(K.resn, G, Dp.kb);
+      Dp.go(R, OSQP_HIP_LS_RESM);
+      Dp.go(R, OSQP_HIP_LS_RESN);
       R.go(mat ? k_lsm_pol_accept : k_ls_pol_accept, 1, kq);
       R.fetch();
       R.go(k_ls_pol_end, G, kq, ls_now() - t_pol);
@@ -1827,8 +1945,8 @@ int lockstep_direct_chunk(Dev &d, const LockstepDirectParams &p0, void *stream, 
     R.ep1.record(s);
     pol_launches = R.launches - launches0;
   }
-  R.go(K.store_n, tn, kb);
-  R.go(K.store_m, tm, kb);
+  D.go(R, OSQP_HIP_LS_STORE_N);
+  D.go(R, OSQP_HIP_LS_STORE_M);
   long nfact = 0;
   const float ms = R.finish(x.fact, &nfact), pms = polished ? LsRun::ms(R.ep0, R.ep1) : 0.f;
   if (mat && p.mat_stat) p.mat_stat[0] = LsRun::ms(R.e0, R.em);
@@ -1870,7 +1988,7 @@ int lockstep_direct_chunk(Dev &d, const LockstepDirectParams &p0, void *stream, 
 // The block vectors x, x~, dx have n + r rows here; the preparation never uses them.
 int lockstep_direct_adjoint_chunk(Dev &d, const LockstepDirectAdjointParams &p, void *stream, double *stat) {
   const hipStream_t s = ls_stream(d, stream);
-  const int n = p.n, m = p.m, r = p.v.r, tn = (n + 63) / 64, tm = (m + 63) / 64;
+  const int n = p.n, m = p.m, r = p.v.r, tn = ls_tiles(n), tm = ls_tiles(m);
   const bool mat = p.mat_ws != nullptr;
   if (r < 1 || r > kWbMaxRows || m < 1) return OSQP_FUNC_NOT_IMPLEMENTED;
   LsAK ka{p, {}, {}};
@@ -1889,7 +2007,8 @@ int lockstep_direct_adjoint_chunk(Dev &d, const LockstepDirectAdjointParams &p, 
     v.WT = xm.WT; v.Av.val = xm.vval;
   }
   const LsWs &w = ka.w;
-  const LwRun D(ka.P, v, w, x, mat);
+  LwRun D(ka.P, v, w, x, mat);
+  if (mat) D.own(mt.Aval, v, xm);
   const LsPcgKernels &K = D.K();
   const int G = w.G;
   // the adjoint's own views: kl makes k_ls_adj_load_n put x~ = Dinv x where k_ls_adj_class, through the view (kc), will gather it -- the first n rows of the
@@ -1900,10 +2019,8 @@ int lockstep_direct_adjoint_chunk(Dev &d, const LockstepDirectAdjointParams &p, 
   LsRun R(s, w.word, p.count);
   R.e0.record(s);
   if (mat) {
-    const int nv = v.Av.nnz, nwt = n * r;
     ls_mat_prepare(R, LsMK{ka.P, w, mt});
-    R.go(k_lwm_wt, std::min(1024, (nwt + 3) / 4), nwt, v.wtpos, (const double *)mt.Aval, xm.WT);
-    R.go(k_lwm_vals, std::min(1024, (nv + 3) / 4), nv, v.vsrc, (const double *)mt.Aval, xm.vval);
+    D.own_rows(R);
     R.em.record(s);
     if (p.mat_stat) p.mat_stat[1] += 2;
   }

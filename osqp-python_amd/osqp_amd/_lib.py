@@ -89,6 +89,24 @@ class WoodburyTestStruct(C.Structure):    # OSQPHipWoodburyTest, include/osqp_hi
                 [('gamma', C.c_double), ('rnorm', C.c_double)])
 
 
+LOCKSTEP_OPS = ('load_n', 'load_m', 'init', 'store_n', 'store_m', 'minv', 'initz', 'rhs', 't', 'kp', 'upd', 'resm', 'resn', 'setrho', 'cgupd', 'cgp',
+                'cginit', 'cgalpha', 'cgbeta', 'begin', 'asm_a', 'asm_p', 'norms', 'scale', 'cost', 'cost_apply', 'finish',
+                'd0', 's', 'inv', 'prod_x', 'prod_xs', 'prod_p', 'prod2', 'setl0', 'setl1', 'h', 'x', 'vals', 'wt')      # OSQPHipLockstepOp, in order
+LOCKSTEP_TEST_LENS = ('q_len', 'l_len', 'u_len', 'x_len', 'y_len', 'rec_len', 'px_len', 'ax_len', 'ws_len', 'mat_len',
+                      'arp_len', 'anz_len', 'brp_len', 'bnz_len', 'n_len', 'm_len', 'pmap_len', 'amap_len', 'bdiag_len',
+                      'avrp_len', 'av_len', 'wt_len', 'rows_len', 'islong_len')
+
+
+class LockstepTestStruct(C.Structure):    # OSQPHipLockstepTest, include/osqp_hip.h (same order)
+    _fields_ = ([(k, C.c_int) for k in ('route', 'mat', 'count', 'warm', 'nops')] + [('ops', c_int_p)] + [(k, C.c_longlong) for k in LOCKSTEP_TEST_LENS] +
+                [(k, c_double_p) for k in ('q', 'l', 'u', 'x', 'y', 'rec', 'Px', 'Ax', 'ws', 'mat_ws')] +
+                [(k, c_int_p) for k in ('A_rowptr', 'A_col', 'B_rowptr', 'B_col')] + [(k, c_double_p) for k in ('A_val', 'B_val', 'D', 'Dinv', 'E', 'Einv')] +
+                [(k, c_int_p) for k in ('Pm1', 'Pm2', 'pvmap', 'AmA', 'AmB', 'avmap', 'Bdiag')] + [(k, c_double_p) for k in ('Praw', 'Araw')] +
+                [(k, c_int_p) for k in ('Av_rowptr', 'Av_col', 'vsrc', 'wtpos', 'rows', 'islong')] + [(k, c_double_p) for k in ('Av_val', 'WT')] +
+                [(k, C.c_int) for k in ('n', 'm', 'nnzA', 'nnzB', 'nzP', 'nzA', 'G')] + [('ws_need', C.c_longlong), ('mat_need', C.c_longlong), ('c', C.c_double)] +
+                [(k, C.c_int) for k in ('r', 'GC', 'cb', 'nv')] + [('dws_need', C.c_longlong), ('dmat_need', C.c_longlong)])
+
+
 SolverP = C.POINTER(SolverStruct)
 
 
@@ -139,6 +157,7 @@ PROTOTYPES = {
     'osqp_hip_test_dense': (C.c_int, [SolverP, C.POINTER(DenseTestStruct)]),
     'osqp_hip_test_band': (C.c_int, [SolverP, C.POINTER(BandTestStruct)]),
     'osqp_hip_test_woodbury': (C.c_int, [SolverP, C.POINTER(WoodburyTestStruct)]),
+    'osqp_hip_test_lockstep': (C.c_int, [SolverP, C.POINTER(LockstepTestStruct)]),
     'osqp_hip_set_rho_eq_factor': (C.c_int, [SolverP, C.c_double]),
     'osqp_hip_default_policy': (None, [C.POINTER(PolicyStruct)]),
     'osqp_hip_set_default_policy': (None, [C.POINTER(PolicyStruct)]),

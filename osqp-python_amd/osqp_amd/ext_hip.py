@@ -392,6 +392,74 @@ class OSQPSolver:
                    gamma=float(t.gamma), rnorm=float(t.rnorm))
         return st, out
 
+    def hip_get_reordering(self):
+        """osqp_hip_get_reordering: (perm_cols [n], perm_rows [m]) -- the caller's index of the engine's k-th variable / constraint (the identity
+        unless the handle works on a permuted copy)."""
+        pc, pr = np.zeros(self.n, np.int32), np.zeros(max(self.m, 1), np.int32)
+        st = int(self._lib.osqp_hip_get_reordering(self._p, _ptr(pc, _lib.c_int_p), _ptr(pr, _lib.c_int_p)))
+        if st:
+            raise ValueError('osqp_hip_get_reordering failed: %d' % st)
+        return pc, pr[:self.m]
+
+    def hip_test_lockstep_sizes(self):
+        """The sizes osqp_hip_test_lockstep reports (n, m, nnzA, nnzB, nzP, nzA, G, ws_need, mat_need and, where the direct route takes the handle, r, GC, cb,
+        nv, dws_need, dmat_need), from a call that is rejected: nothing runs."""
+        t = _lib.LockstepTestStruct()
+        st = int(self._lib.osqp_hip_test_lockstep(self._p, C.byref(t)))
+        return st, {k: int(getattr(t, k)) for k in ('n', 'm', 'nnzA', 'nnzB', 'nzP', 'nzA', 'G', 'ws_need', 'mat_need', 'r', 'GC', 'cb', 'nv', 'dws_need', 'dmat_need')}
+
+    def hip_test_lockstep(self, ops, ws, mat_ws=None, count=64, warm=0, q=None, l=None, u=None, x=None, y=None, rec=None, Px=None, Ax=None,
+                          route=0, handle=False, maps=False, view=False, lens=None):
+        """Single launches of the lockstep kernels on the caller's blocks (osqp_hip_test_lockstep): ops = names of _lib.LOCKSTEP_OPS (or raw ints), one kernel
+        launch each; ws / mat_ws: the whole work / matrix block (mat_ws given: the per-problem-matrix kernels).  q, l, u, Px, Ax: (count, width) or None;
+        x, y, rec: (count, width), default zeros.  route = 1: the direct route (ws / mat_ws are then that route's blocks).  handle / maps / view: also return the
+        engine's CSR and scalings / assembly maps / the direct route's view of A and dense rows.  Every array is copied: the caller's
+        stay as they were.  lens = {field: length} overrides a length as it is passed (the entry validates).  Returns (status, dict)."""
+        _, sz = self.hip_test_lockstep_sizes()
+        n, m = sz['n'], sz['m']
+        mat = mat_ws is not None
+        codes = np.array([_lib.LOCKSTEP_OPS.index(o) if isinstance(o, str) else int(o) for o in ops], dtype=np.int32)
+        f64 = lambda a: None if a is None else np.array(a, dtype=np.float64).ravel()
+        count = int(count)
+        cz = max(count, 0)
+        out = dict(ws=f64(ws), mat_ws=f64(mat_ws), x=np.zeros(cz * n) if x is None else f64(x), y=np.zeros(cz * m) if y is None else f64(y),
+                   rec=np.zeros(cz * self.BATCH_REC) if rec is None else f64(rec))
+        ins = dict(q=f64(q), l=f64(l), u=f64(u), Px=f64(Px), Ax=f64(Ax))
+        size = lambda a: 0 if a is None else a.size
+        ln = dict(q_len=size(ins['q']), l_len=size(ins['l']), u_len=size(ins['u']), x_len=out['x'].size, y_len=out['y'].size, rec_len=out['rec'].size,
+                  px_len=size(ins['Px']), ax_len=size(ins['Ax']), ws_len=out['ws'].size, mat_len=size(out['mat_ws']))
+        ln.update({k: 0 for k in _lib.LOCKSTEP_TEST_LENS if k not in ln})
+        ia = {k: None for k in ('A_rowptr', 'A_col', 'B_rowptr', 'B_col', 'Pm1', 'Pm2', 'pvmap', 'AmA', 'AmB', 'avmap', 'Bdiag', 'Av_rowptr', 'Av_col', 'vsrc', 'wtpos', 'rows', 'islong')}
+        da = {k: None for k in ('A_val', 'B_val', 'D', 'Dinv', 'E', 'Einv', 'Praw', 'Araw', 'Av_val', 'WT')}
+        if handle:
+            ln.update(arp_len=m + 1, anz_len=sz['nnzA'], brp_len=n + 1, bnz_len=sz['nnzB'], n_len=n, m_len=m)
+            ia.update(A_rowptr=np.zeros(m + 1, np.int32), A_col=np.zeros(sz['nnzA'], np.int32), B_rowptr=np.zeros(n + 1, np.int32), B_col=np.zeros(sz['nnzB'], np.int32))
+            da.update(A_val=np.zeros(sz['nnzA']), B_val=np.zeros(sz['nnzB']), D=np.zeros(n), Dinv=np.zeros(n), E=np.zeros(m), Einv=np.zeros(m))
+        if maps:
+            ln.update(pmap_len=sz['nzP'], amap_len=sz['nzA'], bdiag_len=n)
+            ia.update({k: np.zeros(sz['nzP'], np.int32) for k in ('Pm1', 'Pm2', 'pvmap')}, **{k: np.zeros(sz['nzA'], np.int32) for k in ('AmA', 'AmB', 'avmap')}, Bdiag=np.zeros(n, np.int32))
+            da.update(Praw=np.zeros(sz['nzP']), Araw=np.zeros(sz['nzA']))
+        if view:
+            nv, nr = sz['nv'], n * sz['r']
+            ln.update(avrp_len=m + 1, av_len=nv, wt_len=nr, rows_len=sz['r'], islong_len=m)
+            ia.update(Av_rowptr=np.zeros(m + 1, np.int32), Av_col=np.zeros(nv, np.int32), vsrc=np.zeros(nv, np.int32), wtpos=np.zeros(nr, np.int32), rows=np.zeros(sz['r'], np.int32), islong=np.zeros(m, np.int32))
+            da.update(Av_val=np.zeros(nv), WT=np.zeros(nr))
+        for k in [k for k, v in list(ia.items()) + list(da.items()) if v is not None and v.size == 0]:      # (an empty group is "not wanted")
+            (ia if k in ia else da)[k] = None
+        ln.update(lens or {})
+        dp, ip = _lib.c_double_p, _lib.c_int_p
+        t = _lib.LockstepTestStruct(int(route), int(mat), count, int(warm), codes.size, _ptr(codes, ip), *[int(ln[k]) for k in _lib.LOCKSTEP_TEST_LENS],
+                                    _ptr(ins['q'], dp), _ptr(ins['l'], dp), _ptr(ins['u'], dp), _ptr(out['x'], dp), _ptr(out['y'], dp), _ptr(out['rec'], dp),
+                                    _ptr(ins['Px'], dp), _ptr(ins['Ax'], dp), _ptr(out['ws'], dp), _ptr(out['mat_ws'], dp),
+                                    *[_ptr(ia[k], ip) for k in ('A_rowptr', 'A_col', 'B_rowptr', 'B_col')], *[_ptr(da[k], dp) for k in ('A_val', 'B_val', 'D', 'Dinv', 'E', 'Einv')],
+                                    *[_ptr(ia[k], ip) for k in ('Pm1', 'Pm2', 'pvmap', 'AmA', 'AmB', 'avmap', 'Bdiag')], _ptr(da['Praw'], dp), _ptr(da['Araw'], dp),
+                                    *[_ptr(ia[k], ip) for k in ('Av_rowptr', 'Av_col', 'vsrc', 'wtpos', 'rows', 'islong')], _ptr(da['Av_val'], dp), _ptr(da['WT'], dp))
+        st = int(self._lib.osqp_hip_test_lockstep(self._p, C.byref(t)))
+        out.update(ia)
+        out.update(da)
+        out.update(sz, c=float(t.c), x=out['x'].reshape(cz, n), y=out['y'].reshape(cz, m), rec=out['rec'].reshape(cz, self.BATCH_REC))
+        return st, out
+
     def hip_set_rho_eq_factor(self, factor):
         return self._lib.osqp_hip_set_rho_eq_factor(self._p, float(factor))
 

@@ -38,8 +38,12 @@ static thread_local double g_ev[2];
 void ev_mark(Dev &, int which) { g_ev[which ? 1 : 0] = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 double ev_ms(Dev &) { return 1e3 * (g_ev[1] - g_ev[0]); }
 void activate(Dev &) {}
+#ifdef HOSTSIM_LS_ENTRY_PROBE              // (tests/hostsim/ls_entry_probe.cpp alone: the lockstep routes take a handle whose vectors are resident, so that the host side of osqp_hip_test_lockstep reaches its backend call; the probe solves nothing)
+bool device_vec_updates() { return true; }
+#else
 bool device_vec_updates() { return false; }
-void copy_in(Dev &, void *dst, const void *src, size_t bytes, int) { std::memcpy(dst, src, bytes); }
+#endif
+void copy_in(Dev &, void *dst, const void *src, size_t bytes, int) { if (bytes) std::memcpy(dst, src, bytes); }
 void stream_wait(Dev &, void *) {}
 void scale_q(Dev &, double) {}
 void scale_bounds(Dev &, int) {}

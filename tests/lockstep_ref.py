@@ -1,0 +1,1695 @@
+"""Kernel-level references of the lockstep block-vector kernels (osqp-python_amd/csrc/lockstep_hip.hip), ONE LAUNCH AT A TIME: every op of the diagnostic
+entry osqp_hip_test_lockstep (include/osqp_hip.h: poke a work block, run listed launches, peek) has a reference here that maps the uploaded block plus the
+handle's arrays to the expected block -- a few lines of numpy per kernel, sums in np.longdouble, the elementwise rules restated from step_rules.h.  Nothing
+restates a recurrence: errors do not accumulate from one launch to the next.  tests/test_gpu_lockstep_kernels.py runs the references against the GPU,
+tests/test_lockstep_ref.py against the numpy stand-in below (Standin: plain fp64 loops over the same layout, with the kernels' strips, unrolls and folds),
+where every planted mistake must also be NOTICED.
+
+WHERE THINGS SIT comes from the carve log of lockstep_layout.h (the probe tests/test_lockstep_layout.py builds), not from a second list of offsets; what is
+written once here is the ORDER of the carve and of the rows:
+  FWD     lockstep_carve_base: x xs dx r p Kp q Minv | z y t t2 l u rho zt dy | part parti sc rec iw     (element (j, b) of a block vector at j * 64 + b)
+  MATV    lockstep_carve_mat:  Aval Bval D Dinv E Einv
+  PS_*    enum LsSlot: part[slot][workgroup][lane]   SC_* enum LsScal   IW_* enum LsInt (the word block WD_* is its last row)   rec: [lane][12]
+
+THE BOUND is the project's rule (wb_ref.py, band_ref.py), per lane and per output vector:
+    err <= 64 * max(e64, k * 2^-53) * scale
+e64: the error of the same formula evaluated in plain fp64 numpy against the long-double reference (relative to scale), k: the number of terms of the
+longest sum behind the output (a row's length, a workgroup's rows, G), scale: the lane's max |reference| over the vector.  Nothing is tuned to what a kernel
+returns; the assertion is ratio <= 1.  One refinement that follows from the data, not from a result: a vector that holds clamped infinite bounds (E * 1e30)
+next to finite entries is judged as two vectors (entries above 1e15 and the rest), or the finite entries would be checked against a scale of 1e29.
+EXACT checks (bit comparisons): outputs in frozen lanes, every double and int of both blocks that the op does not list as an output, the caller's arrays
+it does not write, copies and transposes, a closed gate.
+
+Lanes are problems: besides the references, HOMOGENEOUS lists ops whose outputs must scale exactly when lane b's inputs are lane 32's times 2^(b - 32).
+
+The direct route (route = 1; handles DIRECT_HANDLES): its own layout (x, x~, dx with n + r rows, no Kp, S pg pg2 h fact; WT and vval behind the matrix block),
+the row passes through the view of A, references for d0, s, inv, the three prod ops, prod2, setl 0 / 1, h, x, vals, wt; S^-1 is judged entry by entry against a
+long-double Gauss-Jordan AND by its residual against numpy's own inverse (judge_inverse)."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import scipy.sparse as sp
+
+from test_policy_rules import DEPS, OUT, ROOT, SRC
+
+W = 64
+LD = np.longdouble
+U53 = 2.0 ** -53
+INFTY = 1e30                                   # OSQP_INFTY
+FWD = ('x', 'xs', 'dx', 'r', 'p', 'Kp', 'q', 'Minv', 'z', 'y', 't', 't2', 'l', 'u', 'rho', 'zt', 'dy', 'part', 'parti', 'sc', 'rec', 'iw')
+MATV = ('Aval', 'Bval', 'D', 'Dinv', 'E', 'Einv')
+FWD_DIRECT = tuple(nm for nm in FWD if nm != 'Kp') + ('S', 'pg', 'pg2', 'h', 'fact')      # lockstep_direct_layout: the base without Kp, then lockstep_carve_direct
+PS_BN, PS_RN, PS_RZ, PS_PKP, PS_M0 = 0, 1, 2, 3, 4
+PS_N0 = PS_M0 + 11
+SC = dict(RHOBAR=0, EQF=1, EPSCG=2, EPSPREV=3, RZ=4, RN=5, TOL=6, ALPHA=7, BETA=8, BEST=9, NACT=10, C=11, CINV=12, CT=13)
+IW = dict(DONE=0, STATUS=1, RHOUPD=2, PCG=3, RELRULE=4, CGON=5, RHOCH=6, STEPS=7, WORSE=8, SIDE=9, POL=10, WORD=11)
+WD = dict(CGANY=0, LIVE=1, RHOANY=2, PCGSUM=3, CGIT=4, POLACC=5, POLREJ=6)
+UNSOLVED = 11                                  # osqp_status_type
+KSLOTS, KSCAL, KINT, KREC = 32, 16, 12, 12
+
+
+def layout_lib():
+    if not (os.path.exists(OUT) and all(os.path.getmtime(OUT) >= os.path.getmtime(f) for f in DEPS)):
+        os.makedirs(os.path.dirname(OUT), exist_ok=True)
+        subprocess.check_call(['g++', '-O2', '-std=c++17', '-shared', '-fPIC', '-I', os.path.join(ROOT, 'include'), '-o', OUT, SRC])
+    L = C.CDLL(OUT)
+    SP = C.POINTER(C.c_size_t)
+    L.ll_carve.argtypes = [C.c_int, C.c_void_p] + [C.c_int] * 5 + [SP, SP]; L.ll_carve.restype = C.c_int
+    L.ll_size.argtypes = [C.c_int] * 6; L.ll_size.restype = C.c_size_t
+    L.ll_const.argtypes = [C.c_int]; L.ll_const.restype = C.c_int
+    assert [L.ll_const(k) for k in range(6)] == [W, KSLOTS, KSCAL, KINT, SC['C'], KREC]
+    return L
+
+
+class Layout:
+    """(offset, doubles) of every range of the forward and the matrix block, from the counting cursor of lockstep_layout.h"""
+    def __init__(self, n, m, nnzA, nnzB, r=0, nv=0):
+        """r > 0: the direct route's blocks (lockstep_direct_layout: x, x~, dx with n + r rows, no Kp, then S pg pg2 h fact; the matrix block followed by the
+        chunk's own dense rows WT [n r] and view values vval [nv], as lockstep_direct_mat_layout takes them behind lockstep_carve_mat)"""
+        L = layout_lib()
+        self.n, self.m, self.nnzA, self.nnzB, self.r, self.nv = n, m, nnzA, nnzB, r, nv
+        self.G = min(256, max(1, (max(n, m) + 15) // 16))
+        self.tm = max(1, (m + 63) // 64)
+        self.cb = 64 * max(1, ((n + 63) // 64 + 127) // 128)                    # lockstep_direct_colblock / _colblocks
+        self.GC = (n + self.cb - 1) // self.cb
+        fwd = FWD_DIRECT if r else FWD
+        for which, names, attr in ((2 if r else 0, fwd, 'fwd'), (5, MATV, 'mat')):
+            cap = L.ll_const(6)
+            ranges, info = (C.c_size_t * (2 * cap))(), (C.c_size_t * 3)()
+            k = L.ll_carve(which, None, n, m, r, nnzA, nnzB, ranges, info)
+            assert k == len(names) and info[1]
+            setattr(self, attr, {nm: (int(ranges[2 * q]), int(ranges[2 * q + 1])) for q, nm in enumerate(names)})
+            end = int(info[0])
+        self.ws_doubles = int(L.ll_size(2 if r else 0, n, m, r, nnzA, nnzB))
+        self.mat_doubles = int(L.ll_size(5, n, m, 0, nnzA, nnzB))
+        if r:
+            self.mat['WT'] = (end, n * r * W); self.mat['vval'] = (end + n * r * W, nv * W)
+            self.mat_doubles += W * (n * r + nv) + 64                            # lockstep_direct_mat_ws_doubles
+            assert self.fwd['x'][1] == (n + r) * W and self.fwd['S'][1] == r * r * W and self.fwd['pg'][1] == self.GC * r * W and self.fwd['fact'][1] == W // 2
+        assert self.fwd['part'][1] == KSLOTS * self.G * W and self.fwd['parti'][1] == self.tm * W
+
+
+class Blk:
+    """A work block (and, optionally, a matrix block) with named VIEWS: v('x') is (n, 64), part (32, G, 64), parti (tiles, 64), sc (16, 64), rec (64, 12),
+    iw (12, 64) int32 (row 11: the word block)."""
+    def __init__(self, lay, ws, mat=None):
+        self.lay, self.ws, self.mat = lay, ws, mat
+        assert ws.size == lay.ws_doubles and (mat is None or mat.size == lay.mat_doubles)
+
+    def copy(self):
+        return Blk(self.lay, self.ws.copy(), None if self.mat is None else self.mat.copy())
+
+    def v(self, name):
+        if name in self.lay.mat and name not in self.lay.fwd:
+            o, c = self.lay.mat[name]
+            return self.mat[o:o + c].reshape(-1, W)
+        o, c = self.lay.fwd[name]
+        a = self.ws[o:o + c]
+        if name == 'fact':
+            return a.view(np.int32)
+        if name in ('pg', 'pg2'):
+            return a.reshape(self.lay.GC, self.lay.r, W)
+        if name == 'part':
+            return a.reshape(KSLOTS, self.lay.G, W)
+        if name == 'rec':
+            return a.reshape(W, KREC)
+        if name == 'iw':
+            return a.view(np.int32).reshape(KINT, W)
+        return a.reshape(-1, W)
+
+    def get(self, key):
+        name, idx = key if isinstance(key, tuple) else (key, None)
+        a = self.v(name)
+        return a if idx is None else a[idx]
+
+
+S_COND = 40.0        # bound on cond_2 of the S that poke() hands k_lw_inv (M M' / r + I, M standard normal: eigenvalues in [1, about 5]); the measured largest
+                     # over r in {1, 7, 9, 33, 128} and 64 lanes is below 6, and every judged inverse asserts cond_2(S) <= S_COND
+
+
+def lane_scales():
+    return 2.0 ** ((np.arange(W) % 9) - 4.0)
+
+
+def poke(lay, seed, mat, count=W, frozen=(), cgoff=(), rhooff=(), wide=False, bdiag=None):
+    """A block of random values whose magnitudes differ by lane, consistent where the kernels need it (l <= u in every class, rho > 0, Minv > 0, D E c > 0),
+    flags as asked: lanes >= count and `frozen` have IW_DONE, `cgoff` IW_CGON = 0, `rhooff` IW_RHOCH = 0; both gates open."""
+    rng = np.random.default_rng(seed)
+    sc = lane_scales()
+    ws = (rng.standard_normal(lay.ws_doubles).reshape(-1, W) * sc).ravel()
+    b = Blk(lay, ws, None)
+    if mat:
+        msc = sc.copy()
+        if wide:
+            msc[5], msc[6] = 1e-7, 1e7                       # (rows below / above the clamp of limit_scaling)
+        mm = (rng.standard_normal(lay.mat_doubles).reshape(-1, W) * msc).ravel()
+        b.mat = mm
+        for nm in ('D', 'Dinv', 'E', 'Einv'):
+            b.v(nm)[:] = 0.5 + rng.random(b.v(nm).shape)
+        b.v('Bval')[:] = np.where(np.abs(b.v('Bval')) < 0.05 * msc, 0.05 * msc, b.v('Bval'))
+        if bdiag is not None:
+            b.v('Bval')[bdiag] = np.abs(b.v('Bval')[bdiag])              # (P + sigma I has a positive diagonal: Minv divides by it plus a sum of squares)
+    m = lay.m
+    if m:
+        lo = rng.standard_normal((m, W)) * sc
+        kind = rng.integers(0, 5, size=(m, W))               # 0 two-sided, 1 equality, 2 loose, 3 only upper, 4 only lower
+        up = lo + (0.1 + rng.random((m, W))) * sc
+        b.v('l')[:] = np.where(kind == 1, lo, np.where((kind == 2) | (kind == 3), -INFTY, lo))
+        b.v('u')[:] = np.where(kind == 1, lo, np.where((kind == 2) | (kind == 4), INFTY, up))
+        b.v('rho')[:] = 10.0 ** rng.uniform(-2, 1, size=(m, W))
+    b.v('Minv')[:] = 0.05 + rng.random((lay.n, W))
+    if lay.r:                                                # the direct route: S symmetric positive definite and well conditioned per lane (S_COND), counts
+        r = lay.r
+        M = rng.standard_normal((r, r, W))
+        S = np.einsum('acb,dcb->adb', M, M) / r + np.eye(r)[:, :, None]
+        b.v('S')[:] = (S * sc * sc).reshape(r * r, W)
+        b.v('fact')[:] = rng.integers(0, 5, W)
+        if mat:
+            b.v('WT')[:] = np.where(rng.random(b.v('WT').shape) < 0.1, 0.0, b.v('WT'))       # (A_L has no entry at some (j, a): exact zeros)
+    for slot in (PS_RZ, PS_PKP):                             # <r, Minv r> and <p, Kp> are positive: cgalpha / cgbeta divide by their folds
+        b.v('part')[slot] = np.abs(b.v('part')[slot])
+    s = b.v('sc')
+    s[SC['RHOBAR']] = 10.0 ** rng.uniform(-2, 1, W); s[SC['EQF']] = 7.0; s[SC['EPSCG']] = 1e-9; s[SC['TOL']] = 1e-3 * sc
+    s[SC['RZ']] = (0.5 + rng.random(W)) * sc * sc; s[SC['C']] = 0.5 + rng.random(W); s[SC['CINV']] = 1.0 / s[SC['C']]; s[SC['CT']] = 0.5 + rng.random(W)
+    iw = b.v('iw')
+    iw[:] = rng.integers(0, 5, size=iw.shape)
+    lanes = np.arange(W)
+    iw[IW['DONE']] = (lanes >= count) | np.isin(lanes, frozen)
+    iw[IW['CGON']] = ~np.isin(lanes, cgoff) & ~iw[IW['DONE']].astype(bool)
+    iw[IW['RHOCH']] = ~np.isin(lanes, rhooff)
+    iw[IW['RELRULE']] = lanes % 2
+    iw[IW['STATUS']] = rng.choice([1, 3, 5, 7, UNSOLVED], size=W)          # solved, primal / dual infeasible, max_iter, unsolved
+    iw[IW['WORD']] = 0
+    iw[IW['WORD'], WD['CGANY']] = 1; iw[IW['WORD'], WD['RHOANY']] = 1; iw[IW['WORD'], WD['LIVE']] = count; iw[IW['WORD'], WD['CGIT']] = 3
+    return b
+
+
+class Case:
+    """The API arrays of a call, the CALLER's numbering: q x (count, n), l u y (count, m), rec (count, 12), Px Ax with mat"""
+    def __init__(self, H, count, seed, warm=0, mat=False):
+        rng = np.random.default_rng(seed)
+        sc = lane_scales()[:count, None]
+        n, m = H.n, H.m
+        self.count, self.warm = count, warm
+        self.q = rng.standard_normal((count, n)) * sc
+        self.x = rng.standard_normal((count, n)) * sc
+        self.y = rng.standard_normal((count, m)) * sc
+        lo = rng.standard_normal((count, m)) * sc
+        kind = rng.integers(0, 5, size=(count, m))
+        self.l = np.where((kind == 2) | (kind == 3), -np.inf, lo)                 # (infinite bounds as a caller passes them: the load clamps)
+        self.u = np.where(kind == 1, lo, np.where((kind == 2) | (kind == 4), np.inf, lo + (0.1 + rng.random((count, m))) * sc))
+        self.rec = rng.standard_normal((count, KREC))
+        self.Px = self.Ax = None
+        if mat:
+            self.Px = H.Praw * (1 + 0.2 * rng.random((count, H.Praw.size)))
+            self.Ax = H.Araw * (1 + 0.3 * rng.standard_normal((count, H.Araw.size)))
+
+    def kw(self):
+        return dict(count=self.count, warm=self.warm, q=self.q, l=self.l, u=self.u, x=self.x, y=self.y, rec=self.rec, Px=self.Px, Ax=self.Ax)
+
+
+class Handle:
+    """What a reference needs of a handle, the ENGINE's numbering: CSR of A and B = [P + sigma I | A'], D .. Einv, c, the permutations (pc[j]: the caller's
+    index of engine column j), the settings the kernels read, with mat the assembly maps.  from_entry: out of osqp_hip_test_lockstep's answer."""
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+        self.G = min(256, max(1, (max(self.n, self.m) + 15) // 16))
+        self.cinv = 1.0 / self.c
+        self.r = int(getattr(self, 'r', 0))                   # > 0: a handle of the direct route, with its view Av, WT [n, r], rows [r], islong [m], wtpos, vsrc
+        self.lay = Layout(self.n, self.m, int(self.A[0][-1]), int(self.B[0][-1]), self.r, len(self.Av[1]) if self.r else 0)
+
+    @staticmethod
+    def from_entry(out, settings, pc, pr, eq_factor, q_caller):
+        n, m = out['n'], out['m']
+        z = lambda a, dt: np.zeros(0, dt) if a is None else a
+        A = (out['A_rowptr'], z(out['A_col'], np.int32), z(out['A_val'], float))
+        B = (out['B_rowptr'], out['B_col'], out['B_val'])
+        kw = dict(n=n, m=m, A=A, B=B, D=out['D'], Dinv=out['Dinv'], E=z(out['E'], float), Einv=z(out['Einv'], float), c=out['c'], pc=np.asarray(pc), pr=np.asarray(pr),
+                  sigma=settings.sigma, alpha=settings.alpha, rho0=min(max(settings.rho, 1e-6), 1e6), eq_factor=eq_factor, precond=int(settings.cg_precond == 1),
+                  rho_is_vec=int(settings.rho_is_vec), scaling=int(settings.scaling), unscaled=int(bool(settings.scaling) and not settings.scaled_termination),
+                  cg_max=int(settings.cg_max_iter), pcg_rel=0.0, mat_iters=max(0, int(settings.scaling)), q0=np.asarray(q_caller, float)[np.asarray(pc)])
+        for k in ('Pm1', 'Pm2', 'pvmap', 'AmA', 'AmB', 'avmap', 'Bdiag', 'Praw', 'Araw'):            # (an empty array comes back as None)
+            kw[k] = z(out.get(k), float if k in ('Praw', 'Araw') else np.int32)
+        if out.get('Av_rowptr') is not None:                 # the direct route's view
+            kw.update(r=out['r'], Av=(out['Av_rowptr'], out['Av_col'], out['Av_val']), WT=out['WT'].reshape(n, out['r']), rows=out['rows'], islong=out['islong'].astype(bool),
+                      wtpos=out['wtpos'], vsrc=out['vsrc'])
+            assert (out['GC'], out['cb']) == ((n + out['cb'] - 1) // out['cb'], 64 * max(1, ((n + 63) // 64 + 127) // 128))
+        return Handle(**kw)
+
+    @staticmethod
+    def synthetic(P, A, seed=0, sigma=1e-6, direct=False, **kw):
+        """A handle built in numpy alone (CPU tier): D, E random in [0.5, 1.5], c = 0.7, the scaled CSR from them, the identity permutation and the
+        assembly maps of the upper triangle."""
+        rng = np.random.default_rng(seed)
+        n, m = P.shape[0], A.shape[0]
+        D, E, c = 0.5 + rng.random(n), 0.5 + rng.random(m), 0.7
+        Pu = sp.triu(P, format='csc'); Pu.sort_indices()
+        Ac = sp.csc_matrix(A); Ac.sort_indices()
+        Pfull = sp.csr_matrix(Pu + sp.triu(Pu, 1).T)
+        As = sp.csr_matrix(sp.diags(E) @ Ac @ sp.diags(D)); As.sort_indices()
+        Bs = sp.hstack([c * (sp.diags(D) @ Pfull @ sp.diags(D)) + sigma * sp.eye(n), As.T]).tocsr(); Bs.sort_indices()
+        csr = lambda M: (M.indptr.astype(np.int32), M.indices.astype(np.int32), M.data.astype(float))
+        Araw, Praw = Ac.data.copy(), Pu.data.copy()
+        # where every stored entry of the caller's CSC arrays sits in the CSR value arrays
+        posA = {(i, j): k for i in range(m) for k, j in zip(range(As.indptr[i], As.indptr[i + 1]), As.indices[As.indptr[i]:As.indptr[i + 1]])}
+        posB = {(i, j): k for i in range(n) for k, j in zip(range(Bs.indptr[i], Bs.indptr[i + 1]), Bs.indices[Bs.indptr[i]:Bs.indptr[i + 1]])}
+        Ai, Aj = Ac.indices, np.repeat(np.arange(n), np.diff(Ac.indptr))
+        Pi, Pj = Pu.indices, np.repeat(np.arange(n), np.diff(Pu.indptr))
+        st = dict(q0=np.linspace(-1, 1, n), sigma=sigma, alpha=1.6, rho0=0.1, eq_factor=7.0, precond=1, rho_is_vec=1, scaling=10, unscaled=1, cg_max=20, pcg_rel=0.0, mat_iters=10)
+        st.update(kw)
+        if direct:                                           # the view and the dense rows, as Engine::prepare_lockstep_direct_view / _wtpos and DevWb hold them
+            cnt = np.diff(As.indptr)
+            rows = np.nonzero(cnt > 128)[0]
+            r = len(rows)
+            vrp, vcol, vsrc, a = [0], [], [], 0
+            WT, wtpos = np.zeros((n, r)), np.full((n, r), -1, np.int32)
+            for i in range(m):
+                if cnt[i] > 128:
+                    for k in range(As.indptr[i], As.indptr[i + 1]):
+                        WT[As.indices[k], a] = As.data[k]; wtpos[As.indices[k], a] = k
+                    vcol.append(n + a); vsrc.append(-1); a += 1
+                else:
+                    vcol += list(As.indices[As.indptr[i]:As.indptr[i + 1]]); vsrc += list(range(As.indptr[i], As.indptr[i + 1]))
+                vrp.append(len(vcol))
+            vsrc = np.array(vsrc, np.int32)
+            st.update(r=r, Av=(np.array(vrp, np.int32), np.array(vcol, np.int32), np.where(vsrc >= 0, As.data[np.maximum(vsrc, 0)], 1.0)), WT=WT, rows=rows.astype(np.int32),
+                      islong=cnt > 128, wtpos=wtpos.ravel(), vsrc=vsrc)
+        return Handle(n=n, m=m, A=csr(As), B=csr(Bs), D=D, Dinv=1 / D, E=E, Einv=1 / E, c=c, pc=np.arange(n), pr=np.arange(m), Praw=Praw, Araw=Araw,
+                      AmA=np.array([posA[(i, j)] for i, j in zip(Ai, Aj)], np.int32), AmB=np.array([posB[(j, n + i)] for i, j in zip(Ai, Aj)], np.int32),
+                      Pm1=np.array([posB[(i, j)] for i, j in zip(Pi, Pj)], np.int32), Pm2=np.array([posB[(j, i)] if i != j else -1 for i, j in zip(Pi, Pj)], np.int32),
+                      Bdiag=np.array([posB[(j, j)] for j in range(n)], np.int32), pvmap=np.arange(Pu.nnz, dtype=np.int32), avmap=np.arange(Ac.nnz, dtype=np.int32), **st)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the problems behind the handles
+def problem_T():
+    """n = 3, m = 0: G = 1, three of four waves have empty strips, no row of A, parti keeps its row"""
+    P = sp.csc_matrix(np.array([[2.0, 0.5, 0.0], [0.5, 3.0, 0.0], [0.0, 0.0, 1.5]]))
+    return P, np.array([1.0, -2.0, 0.5]), sp.csc_matrix((0, 3)), np.zeros(0), np.zeros(0)
+
+
+def problem_S():
+    """n = 70, m = 37: G = 5 (not a multiple of 4), ragged last strips, two n tiles (64 + 6), one m tile; A's rows have 0, 1, .. 9 entries cyclically and row 36
+    has 67; P's band varies so that the P part of B's rows has every length 1 .. 6; l / u cover all three classes, infinite bounds and l = u."""
+    n, m = 70, 37
+    rng = np.random.default_rng(70)
+    rows, cols = [], []
+    for i in range(m):
+        k = 67 if i == m - 1 else i % 10
+        cc = np.sort(rng.choice(n, size=k, replace=False))
+        rows += [i] * k; cols += list(cc)
+    A = sp.csc_matrix((rng.standard_normal(len(rows)) + 0.1, (rows, cols)), shape=(m, n)); A.sort_indices()
+    pi, pj = [], []
+    j0, size = 0, 1
+    while j0 < n:                                            # dense diagonal blocks of 1, 2, .. 6 columns, again and again: a row of a block of s has s entries
+        for a in range(j0, min(j0 + size, n)):
+            for c in range(a + 1, min(j0 + size, n)):
+                pi.append(a); pj.append(c)
+        j0, size = j0 + size, size % 6 + 1
+    off = sp.csc_matrix((0.3 * rng.standard_normal(len(pi)), (pi, pj)), shape=(n, n))
+    off = off + off.T
+    P = (off + sp.diags(1.0 + np.asarray(abs(off).sum(axis=1)).ravel() + rng.random(n))).tocsc(); P.sort_indices()
+    lens = set(np.diff(sp.csr_matrix(P).indptr))
+    assert set(range(1, 7)) <= lens, lens
+    assert sorted(set(np.diff(sp.csr_matrix(A).indptr))) == list(range(10)) + [67]
+    kind = np.arange(m) % 5
+    lo = rng.standard_normal(m)
+    l = np.where((kind == 2) | (kind == 3), -np.inf, lo)
+    u = np.where(kind == 1, lo, np.where((kind == 2) | (kind == 4), np.inf, lo + 1.0))
+    return P, rng.standard_normal(n), A, l, u
+
+
+def problem_C():
+    """n = 4100, m = 130: G clamped at 256, rpw = 5 on the n side with about 200 empty waves, rpw = 1 on the m side"""
+    import problems
+    P, q, A, l, u = problems.banded_qp(4100, m=130, window=40)
+    return sp.csc_matrix(P), q, sp.csc_matrix(A), l, u
+
+
+def problem_D(na, k, seed=3):
+    """A factor-model QP with DENSE F (tests/test_gpu_lockstep_direct.py's _factor_qp at density 1): n = na + k, m = k + 1 + na, P diagonal; every row of
+    [F' | -I] and the budget row has more than 128 entries (na > 128): r = k + 1 long rows next to one-entry rows -- the direct route's handle."""
+    rng = np.random.default_rng(seed)
+    F = rng.standard_normal((na, k)) / np.sqrt(na)
+    P = sp.diags(np.concatenate([2.0 * (0.2 + rng.random(na)) * np.sqrt(max(k, 1)), 2.0 * np.ones(k)])).tocsc()
+    q = np.concatenate([-rng.standard_normal(na), np.zeros(k)])
+    A = sp.vstack([sp.hstack([sp.csc_matrix(F.T), -sp.eye(k)]), sp.hstack([sp.csc_matrix(np.ones((1, na))), sp.csc_matrix((1, k))]),
+                   sp.hstack([sp.eye(na), sp.csc_matrix((na, k))])], format='csc')
+    A.sort_indices()
+    l = np.concatenate([np.zeros(k), [1.0], np.zeros(na)])
+    u = np.concatenate([np.zeros(k), [1.0], np.ones(na)])
+    assert na > 128 and (np.diff(sp.csr_matrix(A).indptr)[:k + 1] > 128).all()
+    return P, q, A, l, u
+
+
+# the direct handles: name -> (na, k); r = k + 1 long rows, n = na + k
+DIRECT_HANDLES = {'D1': (200, 0), 'D7': (200, 6), 'D9': (200, 8), 'D33': (200, 32),       # n about 200: GC = 4 < 8; r below 8, odd, cch = 2, a second a0 pass, a wave whose second row is past r
+                  'D9w': (573, 8),                                                           # n = 581 = 9 * 64 + 5: GC = 10 = 8 + 2, the last column block shorter than the unroll
+                  'D2x': (8200, 1),                                                          # n = 8201 > 8192: cb = 128, GC = 65
+                  'D128': (200, 127)}                                                        # r = 128: the inversion's dynamic LDS above 64 KB, 16 rows of h per workgroup and 8 workgroups
+
+
+# ---------------------------------------------------------------------------------------------------------------- numerics shared by the references
+def nanmax_reduce(a, axis=0, start=None):
+    """the kernels' nanmax fold (step_rules.h): a NaN sticks, otherwise the maximum (from `start`)"""
+    bad = np.isnan(a).any(axis=axis)
+    v = np.where(np.isnan(a), -np.inf, a).max(axis=axis, initial=-np.inf) if a.shape[axis] else np.full(np.delete(a.shape, axis), -np.inf, a.dtype)
+    if start is not None:
+        v = np.maximum(v, start)
+    return np.where(bad, np.nan, v)
+
+
+def spmm(rowptr, col, val, X, dt, pick=None):
+    """(M X) per lane: val (nnz, 64) or (nnz,), X (ncols, 64); pick: mask of the stored entries that take part.  Sums in dt, entry after entry."""
+    nrows = len(rowptr) - 1
+    v = np.asarray(val, dt)
+    if v.ndim == 1:
+        v = v[:, None]
+    prod = v * np.asarray(X, dt)[col] if len(col) else np.zeros((0, W), dt)
+    if pick is not None:
+        prod = np.where(pick[:, None], prod, 0)
+    out = np.zeros((nrows, W), dt)
+    for i in range(nrows):                                   # (reduceat mistreats empty rows; the handles are small)
+        if rowptr[i + 1] > rowptr[i]:
+            out[i] = prod[rowptr[i]:rowptr[i + 1]].sum(axis=0)
+    return out
+
+
+def strips(nrows, G):
+    """rows of every workgroup under ls_rows' partition: rpw = ceil(nrows / 4G), wave (g, w) owns [(4g + w) rpw, +rpw) cut at nrows"""
+    rpw = (nrows + 4 * G - 1) // (4 * G)
+    return [np.arange(min(4 * g * rpw, nrows), min(4 * (g + 1) * rpw, nrows)) for g in range(G)], rpw
+
+
+def put(vals, groups, kind, dt):
+    """a statistic's partial per workgroup, (G, 64): kind 'max' (nanmax from 0), 'maxneg' (nanmax from -inf), 'sum'"""
+    out = np.zeros((len(groups), W), dt)
+    for g, rows in enumerate(groups):
+        if kind == 'sum':
+            out[g] = vals[rows].sum(axis=0)
+        else:
+            out[g] = nanmax_reduce(vals[rows], 0, 0.0 if kind == 'max' else -np.inf)
+    return out
+
+
+class Ref:
+    """op -> {key: (expected, k, exact lanes)} with expected in dtype dt over the whole range the op may write (frozen lanes: the value before, exact).
+    key: a view's name, or (name, index); ('io', 'x' | 'y' | 'rec'): the caller's arrays, transposed to (width, count)."""
+    def __init__(self, H, b0, case, dt):
+        self.H, self.b, self.c, self.dt, self.mat = H, b0, case, dt, b0.mat is not None
+
+    def V(self, name):
+        return self.b.v(name).astype(self.dt)
+
+    def sv(self, name):                         # ls_sv: the handle's vector or the lane's own column
+        return self.V(name) if self.mat else np.asarray(getattr(self.H, name), self.dt)[:, None] * np.ones((1, W), self.dt)
+
+    def Av(self):
+        return self.V('Aval') if self.mat else np.asarray(self.H.A[2], self.dt)[:, None] * np.ones((1, W), self.dt)
+
+    def Bv(self):
+        return self.V('Bval') if self.mat else np.asarray(self.H.B[2], self.dt)[:, None] * np.ones((1, W), self.dt)
+
+    def cs(self, inv=False):
+        H = self.H
+        return self.V('sc')[SC['CINV' if inv else 'C']] if self.mat else np.full(W, H.cinv if inv else H.c, self.dt)
+
+    def iw(self, name):
+        return self.b.v('iw')[IW[name]].astype(bool)
+
+    def word(self, name):
+        return int(self.b.v('iw')[IW['WORD'], WD[name]])
+
+    def keep(self, mask, new, name):
+        """new where the lane is in mask, the block's value elsewhere (those lanes are exact)"""
+        return np.where(mask[None, :], new, self.V(name)), ~mask
+
+    def Ax(self, X):
+        """A X as the row passes over A compute it: on the direct route through the VIEW (a long row is the entry 1.0 at column n + a of X's n + r rows)"""
+        H = self.H
+        if H.r:
+            vals = self.V('vval') if self.mat else np.asarray(H.Av[2], self.dt)[:, None] * np.ones((1, W), self.dt)
+            return spmm(H.Av[0], H.Av[1], vals, X, self.dt)
+        rp, col, _ = H.A
+        return spmm(rp, col, self.Av(), X[:H.n], self.dt)
+
+    def WTv(self):
+        """the dense rows (n, r, 64): the handle's for every lane, or the chunk's own"""
+        H = self.H
+        return self.V('WT').reshape(H.n, H.r, W) if self.mat else np.asarray(H.WT, self.dt)[:, :, None] * np.ones((1, 1, W), self.dt)
+
+    def klen(self, M):
+        return int(np.diff(M[0]).max()) if len(M[0]) > 1 else 0
+
+    def run(self, op):
+        return getattr(self, 'op_' + op)()
+
+    # ---- row passes
+    def op_minv(self):
+        if not self.word('RHOANY'):
+            return {}
+        H, dt = self.H, self.dt
+        rp, col, _ = H.B
+        rowof = np.repeat(np.arange(H.n), np.diff(rp))
+        Bv = self.Bv()
+        s = spmm(rp, col, Bv * Bv, np.vstack([np.zeros((H.n, W), dt), self.V('rho')]), dt, pick=col >= H.n)
+        diag = np.zeros((H.n, W), dt)
+        d = col == rowof
+        diag[rowof[d]] = Bv[d]
+        new = 1 / (diag + s) if H.precond else np.ones((H.n, W), dt)
+        v, ex = self.keep(self.iw('RHOCH'), new, 'Minv')
+        return {'Minv': (v, self.klen(H.B) + 1, ex)}
+
+    def _rhs(self):
+        H, dt = self.H, self.dt
+        rp, col, _ = H.B
+        Bv = self.Bv()
+        zn = np.zeros((H.n, W), dt)
+        a0 = spmm(rp, col, Bv, np.vstack([zn, self.V('t')]), dt, pick=col >= H.n)
+        a1 = spmm(rp, col, Bv, np.vstack([self.V('xs')[:H.n], self.V('t2')]), dt)
+        rhs = H.sigma * self.V('x')[:H.n] - self.V('q') + a0
+        rr = rhs - a1
+        return rhs, rr, self.V('Minv') * rr
+
+    def op_rhs(self):
+        H, dt = self.H, self.dt
+        rhs, rr, zz = self._rhs()
+        live = ~self.iw('DONE')
+        groups, rpw = strips(H.n, H.G)
+        k = self.klen(H.B) + 2
+        r, ex = self.keep(live, rr, 'r')
+        p, _ = self.keep(live, zz, 'p')
+        return {'r': (r, k, ex), 'p': (p, k, ex), ('part', PS_BN): (put(np.abs(rhs), groups, 'max', dt), k, None), ('part', PS_RN): (put(np.abs(rr), groups, 'max', dt), k, None),
+                ('part', PS_RZ): (put(rr * zz, groups, 'sum', dt), k + 4 * rpw, None)}
+
+    def op_kp(self):
+        if not self.word('CGANY'):
+            return {}
+        H, dt = self.H, self.dt
+        rp, col, _ = H.B
+        a = spmm(rp, col, self.Bv(), np.vstack([self.V('p'), self.V('t')]), dt)
+        groups, rpw = strips(H.n, H.G)
+        v, ex = self.keep(self.iw('CGON'), a, 'Kp')
+        return {'Kp': (v, self.klen(H.B), ex), ('part', PS_PKP): (put(a * self.V('p'), groups, 'sum', dt), self.klen(H.B) + 4 * rpw, None)}
+
+    def op_initz(self):
+        a, rho, k = self.Ax(self.V('x')), self.V('rho'), self.klen(self.H.A if not self.H.r else self.H.Av)
+        return {'z': (a, k, None), 'zt': (a, k, None), 't': (rho * a - self.V('y'), k + 1, None), 't2': (rho * a, k, None)}
+
+    def op_t(self):
+        if not self.word('CGANY'):
+            return {}
+        v, ex = self.keep(self.iw('CGON'), self.V('rho') * self.Ax(self.V('p')), 't')
+        return {'t': (v, self.klen(self.H.A), ex)}
+
+    def op_upd(self):
+        H, dt = self.H, self.dt
+        live = ~self.iw('DONE')
+        out, al = {}, dt(H.alpha)
+        if H.m > 0:
+            a, rho, z, y = self.Ax(self.V('xs')), self.V('rho'), self.V('z'), self.V('y')
+            zr = al * a + (1 - al) * z                                                    # step_row
+            zn = np.minimum(np.maximum(zr + y / rho, self.V('l')), self.V('u'))
+            dy = rho * (zr - zn)
+            k = self.klen(H.Av if H.r else H.A) + 3
+            for nm, val in (('y', y + dy), ('dy', dy), ('z', zn), ('zt', a), ('t', rho * zn - (y + dy)), ('t2', rho * a)):
+                v, ex = self.keep(live, val, nm)
+                out[nm] = (v, k, ex)
+        xs, x = self.V('xs'), self.V('x')
+        n = x.shape[0]                                                                    # (n; n + r on the direct route, which runs this loop over all of x)
+        xn = (1 - al) * x + al * xs                                                       # step_col
+        v, ex = self.keep(live, xn - x, 'dx')
+        out['dx'] = (v[:n], 2, ex)
+        v, ex = self.keep(live, xn, 'x')
+        out['x'] = (v[:n], 2, ex)
+        return out
+
+    def op_resm(self):
+        H, dt = self.H, self.dt
+        rp, col, _ = H.A
+        ax, adx = self.Ax(self.V('x')), self.Ax(self.V('dx'))
+        z, dy, l, u, E, Ei = self.V('z'), self.V('dy'), self.V('l'), self.V('u'), self.sv('E'), self.sv('Einv')
+        pr = ax - z
+        sup = u * np.maximum(dy, 0) + l * np.minimum(dy, 0)                               # support_term
+        if H.unscaled:
+            adx = Ei * adx
+        hi = np.where(u < INFTY * 1e-4, adx, -np.inf); lo = np.where(l > -INFTY * 1e-4, -adx, -np.inf)
+        groups, rpw = strips(H.m, H.G)
+        k = self.klen(H.Av if H.r else H.A) + 1
+        mx = [np.abs(Ei * pr), np.abs(Ei * ax), np.abs(Ei * z), np.abs(pr), np.abs(ax), np.abs(z), np.abs(E * dy), np.abs(dy)]
+        out = {('part', PS_M0 + s): (put(v, groups, 'max', dt), k, None) for s, v in enumerate(mx)}
+        out[('part', PS_M0 + 8)] = (put(hi, groups, 'maxneg', dt), k, None)
+        out[('part', PS_M0 + 9)] = (put(lo, groups, 'maxneg', dt), k, None)
+        out[('part', PS_M0 + 10)] = (put(sup, groups, 'sum', dt), 2 * 4 * rpw, None)
+        return out
+
+    def op_resn(self):
+        H, dt = self.H, self.dt
+        rp, col, _ = H.B
+        Bv, pn = self.Bv(), col < H.n
+        zn, zm = np.zeros((H.n, W), dt), np.zeros((H.m, W), dt)
+        x, dx, q, D, Di = self.V('x')[:H.n], self.V('dx')[:H.n], self.V('q'), self.sv('D'), self.sv('Dinv')
+        sp_ = spmm(rp, col, Bv, np.vstack([x, zm]), dt, pick=pn)
+        sa = spmm(rp, col, Bv, np.vstack([zn, self.V('y')]), dt, pick=~pn)
+        pdx = spmm(rp, col, Bv, np.vstack([dx, zm]), dt, pick=pn) - H.sigma * dx
+        atdy = spmm(rp, col, Bv, np.vstack([zn, self.V('dy')]), dt, pick=~pn)
+        px = sp_ - H.sigma * x
+        dr = px + q + sa
+        groups, rpw = strips(H.n, H.G)
+        k = self.klen(H.B) + 3
+        mx = [np.abs(Di * dr), np.abs(Di * px), np.abs(Di * sa), np.abs(dr), np.abs(px), np.abs(sa), np.abs(D * dx), np.abs(dx), np.abs(q), np.abs(Di * q),
+              np.abs(Di * atdy), np.abs(atdy), np.abs(Di * pdx), np.abs(pdx)]
+        out = {('part', PS_N0 + s): (put(v, groups, 'max', dt), k, None) for s, v in enumerate(mx)}
+        for s, v in enumerate((x * px, q * x, q * dx)):
+            out[('part', PS_N0 + 14 + s)] = (put(v, groups, 'sum', dt), k + 4 * rpw, None)
+        return out
+
+    # ---- elementwise
+    def row_rho(self, l, u, rb, eqf):
+        H = self.H
+        cls = np.where((l < -INFTY * 1e-4) & (u > INFTY * 1e-4), -1, np.where(u - l < 1e-4, 1, 0)) if H.rho_is_vec else np.zeros(l.shape, int)
+        return np.where(cls == -1, self.dt(1e-6), np.where(cls == 1, (eqf * rb)[None, :], rb[None, :])), cls
+
+    def op_setrho(self):
+        if not self.word('RHOANY'):
+            return {}
+        s = self.V('sc')
+        rh, _ = self.row_rho(self.V('l'), self.V('u'), s[SC['RHOBAR']], s[SC['EQF']])
+        on = self.iw('RHOCH')
+        out = {}
+        for nm, val in (('rho', rh), ('t', rh * self.V('z') - self.V('y')), ('t2', rh * self.V('zt'))):
+            v, ex = self.keep(on, val, nm)
+            out[nm] = (v, 2, ex)
+        return out
+
+    def op_cgupd(self):
+        if not self.word('CGANY'):
+            return {}
+        H, dt = self.H, self.dt
+        on, al = self.iw('CGON'), self.V('sc')[SC['ALPHA']]
+        rr = self.V('r') - al * self.V('Kp')
+        xs, ex = self.keep(on, self.V('xs') + al * self.V('p'), 'xs')
+        r, _ = self.keep(on, rr, 'r')
+        j = np.arange(H.n)
+        groups = [j[(j % (4 * H.G)) // 4 == g] for g in range(H.G)]
+        kk = (H.n + 4 * H.G - 1) // (4 * H.G) * 4
+        onf = on[None, :]
+        return {'xs': (xs, 2, ex), 'r': (r, 2, ex), ('part', PS_RN): (put(np.where(onf, np.abs(rr), 0), groups, 'max', dt), 2, None),
+                ('part', PS_RZ): (put(np.where(onf, rr * (self.V('Minv') * rr), 0), groups, 'sum', dt), kk + 2, None)}
+
+    def op_cgp(self):
+        if not self.word('CGANY'):
+            return {}
+        v, ex = self.keep(self.iw('CGON'), self.V('Minv') * self.V('r') + self.V('sc')[SC['BETA']] * self.V('p'), 'p')
+        return {'p': (v, 2, ex)}
+
+    # ---- folds
+    def fold(self, slot, kind, name='part', G=None):
+        p = self.V(name)[slot] if name == 'part' else self.V(name)
+        p = p[:self.H.G if G is None else G]
+        return nanmax_reduce(p, 0) if kind == 'max' else p.sum(axis=0)
+
+    def ints(self, row, val):
+        return (np.asarray(val).astype(np.int32), 0, np.ones(W, bool))
+
+    def op_cginit(self):
+        H, dt = self.H, self.dt
+        bn, rn, rz = self.fold(PS_BN, 'max'), self.fold(PS_RN, 'max'), self.fold(PS_RZ, 'sum')
+        eps = self.V('sc')[SC['EPSCG']]
+        tol = np.maximum(H.pcg_rel * bn, 1e-15) if H.pcg_rel > 0 else np.where(self.iw('RELRULE'), np.maximum(dt(0.1) * bn, dt(1e-13)), np.maximum(dt(1e-14) * bn, eps))
+        on = ~self.iw('DONE') & (H.cg_max > 0) & (rn > tol)
+        return {('sc', SC['RZ']): (rz, H.G, None), ('sc', SC['RN']): (rn, 1, None), ('sc', SC['TOL']): (tol, 1, None), ('iw', IW['CGON']): self.ints(0, on),
+                ('word', WD['CGANY']): int(on.any()), ('word', WD['CGIT']): 0}
+
+    def op_cgalpha(self):
+        if not self.word('CGANY'):
+            return {}
+        pkp = self.fold(PS_PKP, 'sum')
+        on = self.iw('CGON')
+        with np.errstate(all='ignore'):
+            al = np.where(on, self.V('sc')[SC['RZ']] / pkp, 0)
+        return {('sc', SC['ALPHA']): (al, self.H.G, ~on)}
+
+    def op_cgbeta(self):
+        if not self.word('CGANY'):
+            return {}
+        G = self.H.G
+        rn2, rz2 = self.fold(PS_RN, 'max'), self.fold(PS_RZ, 'sum')
+        on, s, iw = self.iw('CGON'), self.V('sc'), self.b.v('iw')
+        on2 = on & (rn2 > s[SC['TOL']])
+        return {('sc', SC['BETA']): (np.where(on, rz2 / s[SC['RZ']], s[SC['BETA']]), G, ~on), ('sc', SC['RZ']): (np.where(on, rz2, s[SC['RZ']]), G, ~on),
+                ('sc', SC['RN']): (np.where(on, rn2, s[SC['RN']]), 1, ~on), ('iw', IW['PCG']): self.ints(0, iw[IW['PCG']] + on), ('iw', IW['CGON']): self.ints(0, on2),
+                ('word', WD['CGANY']): int(on2.any()), ('word', WD['CGIT']): self.word('CGIT') + 1}
+
+    # ---- transposes and state
+    def lanes_in(self, a, perm, fill=0.0):
+        """(count, width) caller's numbering -> (width, 64) engine's numbering, `fill` in the lanes >= count"""
+        out = np.full((a.shape[1], W), fill, self.dt)
+        out[:, :a.shape[0]] = np.asarray(a, self.dt)[:, perm].T
+        return out
+
+    def op_load_n(self):
+        H, c, dt = self.H, self.c, self.dt
+        mine = np.arange(W) < c.count
+        q = np.where(mine[None, :], self.cs()[None, :] * self.sv('D') * self.lanes_in(c.q, H.pc), 0)      # in_q: c * D * q
+        xv = np.where(mine[None, :], self.lanes_in(c.x, H.pc) * self.sv('Dinv'), 0) if c.warm else np.zeros((H.n, W), dt)
+        return {'q': (q, 2, None), 'x': (xv, 1, None), 'xs': (xv, 1, None), 'dx': (np.zeros((H.n, W), dt), 0, np.ones(W, bool))}
+
+    def op_load_m(self):
+        H, c, dt = self.H, self.c, self.dt
+        mine = (np.arange(W) < c.count)[None, :]
+        E = self.sv('E')
+        l = np.where(mine, E * np.maximum(self.lanes_in(c.l, H.pr), -INFTY), -INFTY)
+        u = np.where(mine, E * np.minimum(self.lanes_in(c.u, H.pr), INFTY), INFTY)
+        y = np.where(mine, self.lanes_in(c.y, H.pr) * self.sv('Einv') * self.cs()[None, :], 0) if c.warm else np.zeros((H.m, W), dt)
+        _, cls = self.row_rho(l, u, np.ones(W, dt), np.ones(W, dt))
+        parti = np.stack([(cls[64 * t:64 * t + 64] == 0).sum(axis=0) for t in range((H.m + 63) // 64)]).astype(dt)
+        return {'l': (l, 1, None), 'u': (u, 1, None), 'y': (y, 2, None), 'dy': (np.zeros((H.m, W), dt), 0, np.ones(W, bool)), 'parti': (parti, 0, np.ones(W, bool))}
+
+    def op_init(self):
+        H, dt = self.H, self.dt
+        tm = (H.m + 63) // 64
+        nin = self.V('parti')[:tm].sum(axis=0) if H.m > 0 else np.zeros(W, dt)
+        lanes = np.arange(W)
+        ex = np.ones(W, bool)
+        f = lambda v: (np.full(W, v, dt), 0, ex)
+        out = {('sc', SC['RHOBAR']): f(H.rho0), ('sc', SC['EQF']): (np.where(nin == 0, dt(1e3), dt(H.eq_factor)), 0, ex), ('sc', SC['EPSCG']): f(0.0), ('sc', SC['EPSPREV']): f(np.inf),
+               ('iw', IW['DONE']): self.ints(0, lanes >= self.c.count), ('iw', IW['STATUS']): self.ints(0, np.full(W, UNSOLVED)), ('iw', IW['RELRULE']): self.ints(0, np.ones(W)),
+               ('iw', IW['RHOCH']): self.ints(0, np.ones(W))}
+        for nm in ('RHOUPD', 'PCG', 'CGON', 'SIDE'):
+            out[('iw', IW[nm])] = self.ints(0, np.zeros(W))
+        out.update({('word', WD['CGANY']): 0, ('word', WD['LIVE']): self.c.count, ('word', WD['RHOANY']): 1, ('word', WD['PCGSUM']): 0, ('word', WD['CGIT']): 0})
+        return out
+
+    def out_lanes(self, v, perm):
+        """(width, 64) engine's numbering -> (width, count) caller's numbering"""
+        out = np.zeros((len(perm), self.c.count), self.dt)
+        out[perm] = v[:, :self.c.count]
+        return out
+
+    def op_store_n(self):
+        H, c, dt = self.H, self.c, self.dt
+        st = self.b.v('iw')[IW['STATUS']]
+        dinf, pinf = np.isin(st, (5, 6))[None, :], np.isin(st, (3, 4))[None, :]
+        D, x, dx = self.sv('D'), self.V('x')[:H.n], self.V('dx')[:H.n]
+        v = np.where(dinf, D * dx if H.unscaled else dx, np.where(pinf, np.nan, D * x if H.scaling else x))        # batch_out_x
+        return {('io', 'x'): (self.out_lanes(v, H.pc), 1, None), ('io', 'rec'): (self.V('rec')[:c.count].T, 0, np.ones(c.count, bool))}
+
+    def op_store_m(self):
+        H, dt = self.H, self.dt
+        st = self.b.v('iw')[IW['STATUS']]
+        dinf, pinf = np.isin(st, (5, 6))[None, :], np.isin(st, (3, 4))[None, :]
+        E, y, dy = self.sv('E'), self.V('y'), self.V('dy')
+        v = np.where(pinf, E * dy if H.unscaled else dy, np.where(dinf, np.nan, self.cs(True)[None, :] * E * y if H.scaling else y))      # batch_out_y
+        return {('io', 'y'): (self.out_lanes(v, H.pr), 2, None)}
+
+    # ---- matrices of a chunk
+    def op_begin(self):
+        H, c, dt = self.H, self.c, self.dt
+        ex = np.ones(W, bool)
+        q = self.lanes_in(c.q, H.pc)
+        q[:, c.count:] = np.asarray(H.q0, dt)[:, None]
+        Bv = self.V('Bval')
+        Bv[H.Bdiag] = 0
+        one = lambda r: (np.ones((r, W), dt), 0, ex)
+        return {'q': (q, 0, ex), 'D': one(H.n), 'E': one(H.m), 'Bval': (Bv, 0, ex), ('sc', SC['C']): (np.ones(W, dt), 0, ex)}
+
+    def _asm(self, src, raw, vmap):
+        c, dt = self.c, self.dt
+        v = np.asarray(raw, dt)[vmap][:, None] * np.ones((1, W), dt)                      # entry e of the caller goes to position vmap[e]; dead lanes: the handle's raw value THERE
+        if src is not None:
+            v[:, :c.count] = np.asarray(src, dt).T
+        return v
+
+    def op_asm_a(self):
+        H = self.H
+        v = self._asm(self.c.Ax, H.Araw, H.avmap)
+        A, B = self.V('Aval'), self.V('Bval')
+        A[H.AmA[H.avmap]] = v
+        B[H.AmB[H.avmap]] = v
+        ex = np.ones(W, bool)
+        return {'Aval': (A, 0, ex), 'Bval': (B, 0, ex)}
+
+    def op_asm_p(self):
+        H = self.H
+        v = self._asm(self.c.Px, H.Praw, H.pvmap)
+        B = self.V('Bval')
+        p1, p2 = H.Pm1[H.pvmap], H.Pm2[H.pvmap]
+        B[p1] = v
+        mir = (p2 >= 0) & (p2 != p1)
+        B[p2[mir]] = v[mir]
+        return {'Bval': (B, 0, np.ones(W, bool))}
+
+    def limit(self, v):
+        return np.where(v < 1e-4, 1.0, np.where(v > 1e4, 1e4, v)).astype(self.dt)
+
+    def rowmax(self, M, vals, pick=None):
+        rp = M[0]
+        a = np.abs(vals) if pick is None else np.where(pick[:, None], np.abs(vals), 0)
+        return np.stack([np.fmax.reduce(a[rp[i]:rp[i + 1]], axis=0, initial=0.0) if rp[i + 1] > rp[i] else np.zeros(W, self.dt) for i in range(len(rp) - 1)]) if len(rp) > 1 else np.zeros((0, W), self.dt)
+
+    def op_norms(self):
+        H = self.H
+        return {'r': (1 / np.sqrt(self.limit(self.rowmax(H.B, self.V('Bval')))), 2, None), 't': (1 / np.sqrt(self.limit(self.rowmax(H.A, self.V('Aval')))), 2, None)}
+
+    def op_scale(self):
+        H, dt = self.H, self.dt
+        dtv, et = self.V('r'), self.V('t')
+        rpA, colA, _ = H.A
+        rpB, colB, _ = H.B
+        rowA, rowB = np.repeat(np.arange(H.m), np.diff(rpA)), np.repeat(np.arange(H.n), np.diff(rpB))
+        A = self.V('Aval') * (et[rowA] * dtv[colA]) if H.m else self.V('Aval')
+        fac = np.vstack([dtv, et])[colB] * dtv[rowB]
+        B = self.V('Bval') * fac
+        q = self.V('q') * dtv
+        groups, rpw = strips(H.n, H.G)
+        mx = self.rowmax(H.B, B, pick=colB < H.n)
+        return {'Aval': (A, 2, None), 'E': (self.V('E') * et, 1, None), 'Bval': (B, 2, None), 'q': (q, 1, None), 'D': (self.V('D') * dtv, 1, None),
+                ('part', PS_BN): (put(np.abs(q), groups, 'max', dt), 1, None), ('part', PS_BN + 1): (put(mx, groups, 'sum', dt), 4 * rpw + 2, None)}
+
+    def op_cost(self):
+        H = self.H
+        nq, s = self.fold(PS_BN, 'max'), self.fold(PS_BN + 1, 'sum')
+        # (fmax, not nanmax: k_lsm_cost takes the larger of the two as the single-QP setup does)
+        ct = 1 / self.limit(np.fmax(self.limit(nq), s / max(H.n, 1)))
+        return {('sc', SC['CT']): (ct, H.G + 1, None), ('sc', SC['C']): (self.V('sc')[SC['C']] * ct, H.G + 2, None)}
+
+    def op_cost_apply(self):
+        H = self.H
+        rpB, colB, _ = H.B
+        ct = self.V('sc')[SC['CT']][None, :]
+        B = self.V('Bval')
+        B = np.where((colB < H.n)[:, None], B * ct, B)
+        return {'Bval': (B, 1, None), 'q': (self.V('q') * ct, 1, None)}
+
+    def op_finish(self):
+        H = self.H
+        B = self.V('Bval')
+        B[H.Bdiag] = B[H.Bdiag] + H.sigma
+        out = {'Dinv': (1 / self.V('D'), 1, None), 'Bval': (B, 1, None), ('sc', SC['CINV']): (1 / self.V('sc')[SC['C']], 1, None)}
+        if H.m:
+            out['Einv'] = (1 / self.V('E'), 1, None)
+        return out
+
+
+    # ---- the direct route
+    def op_d0(self):
+        if not self.word('RHOANY'):
+            return {}
+        H, dt = self.H, self.dt
+        rp, col, _ = H.B
+        rowof = np.repeat(np.arange(H.n), np.diff(rp))
+        Bv = self.Bv()
+        short = (col >= H.n) & ~np.asarray(H.islong)[np.maximum(col - H.n, 0)]
+        s = spmm(rp, col, Bv * Bv, np.vstack([np.zeros((H.n, W), dt), self.V('rho')]), dt, pick=short)
+        diag = np.zeros((H.n, W), dt)
+        d = col == rowof
+        diag[rowof[d]] = Bv[d]
+        v, ex = self.keep(self.iw('RHOCH'), 1 / (diag + s), 'Minv')
+        return {'Minv': (v, self.klen(H.B) + 1, ex)}
+
+    def op_s(self):
+        if not self.word('RHOANY'):
+            return {}
+        H = self.H
+        on = self.iw('RHOCH')
+        lanes = np.nonzero(on)[0]                            # (only the lanes that are written are computed: r = 128 is 16 M terms per lane)
+        WT, Minv = self.WTv()[:, :, lanes], self.V('Minv')[:, lanes]
+        S = np.zeros((H.r, H.r, W), self.dt)
+        for k, b in enumerate(lanes):
+            S[:, :, b] = (WT[:, :, k].T * Minv[:, k]) @ WT[:, :, k]
+        S[np.arange(H.r), np.arange(H.r)] += 1 / self.V('rho')[H.rows]
+        v, ex = self.keep(on, S.reshape(H.r * H.r, W), 'S')
+        return {'S': (v, H.n + 1, ex)}
+
+    def gauss_jordan(self, S):
+        """k_lw_inv per lane: in place, without pivoting; a pivot that is not positive and finite makes the lane's inverse NaN"""
+        M, r = S.copy(), S.shape[0]
+        for kk in range(r):
+            p = M[kk, kk]
+            with np.errstate(all='ignore'):
+                ip = np.where((p > 0) & np.isfinite(p), 1 / p, np.nan)
+            col = M[:, kk].copy()
+            row = M[kk] * ip
+            row[kk] = ip
+            M[:, kk] = 0
+            M = M - col[:, None, :] * row[None, :, :]
+            M[kk] = row
+        return M
+
+    def op_inv(self):
+        """S^-1 is judged by its residual (judge_inverse); here: which lanes are inverted, the reference inverse, the counts"""
+        if not self.word('RHOANY'):
+            return {}
+        H = self.H
+        on = self.iw('RHOCH') & ~self.iw('DONE')
+        S = self.V('S').reshape(H.r, H.r, W)
+        lanes = np.nonzero(on)[0]
+        inv = np.zeros((H.r, H.r, W), self.dt)
+        with np.errstate(all='ignore'):
+            inv[:, :, lanes] = self.gauss_jordan(S[:, :, lanes])
+        inv = inv.reshape(H.r * H.r, W)
+        v, ex = self.keep(on, inv, 'S')
+        return {'S': (v, H.r, ex), 'fact': ((self.b.v('fact') + on).astype(np.int32), 0, None)}
+
+    def prod(self, v):
+        H = self.H
+        t = self.WTv() * v[:H.n, None, :]
+        return np.stack([t[g * H.lay.cb:min((g + 1) * H.lay.cb, H.n)].sum(axis=0) for g in range(H.lay.GC)])
+
+    def op_prod_x(self):
+        return {'pg': (self.prod(self.V('x')), self.H.lay.cb, None)}
+
+    def op_prod_xs(self):
+        return {'pg2': (self.prod(self.V('xs')), self.H.lay.cb, None)}
+
+    def op_prod_p(self):
+        return {'pg': (self.prod(self.V('p')), self.H.lay.cb, None)}
+
+    def op_prod2(self):
+        return {'pg': (self.prod(self.V('x')), self.H.lay.cb, None), 'pg2': (self.prod(self.V('xs')), self.H.lay.cb, None)}
+
+    def setl(self, start):
+        H, dt = self.H, self.dt
+        live = ~self.iw('DONE') | bool(start)
+        out = {}
+        for nm, pg in (('x', 'pg'), ('xs', 'pg2')):
+            full = self.V(nm)
+            full[H.n:] = np.where(live[None, :], self.V(pg).sum(axis=0), full[H.n:])
+            out[nm] = (full, H.lay.GC, ~live)
+        if start:
+            dx = self.V('dx')
+            dx[H.n:] = 0
+            out['dx'] = (dx, 0, np.ones(W, bool))
+        return out
+
+    def op_setl0(self):
+        return self.setl(0)
+
+    def op_setl1(self):
+        return self.setl(1)
+
+    def op_h(self):
+        H = self.H
+        live = ~self.iw('DONE')
+        g = self.V('pg').sum(axis=0)
+        h = np.einsum('acb,cb->ab', self.V('S').reshape(H.r, H.r, W), g)
+        xs = self.V('xs')
+        xs[H.n:] = np.where(live[None, :], xs[H.n:] + h / self.V('rho')[H.rows], xs[H.n:])
+        hv, ex = self.keep(live, h, 'h')
+        return {'h': (hv, H.r + H.lay.GC, ex), 'xs': (xs, H.r + H.lay.GC + 1, ex)}
+
+    def op_x(self):
+        H = self.H
+        live = ~self.iw('DONE')
+        s = np.einsum('jab,ab->jb', self.WTv(), self.V('h'))
+        xs = self.V('xs')
+        xs[:H.n] = np.where(live[None, :], xs[:H.n] + (self.V('p') - self.V('Minv') * s), xs[:H.n])
+        return {'xs': (xs, H.r + 2, ~live)}
+
+    def op_vals(self):
+        H = self.H
+        A = self.V('Aval')
+        v = np.where((H.vsrc >= 0)[:, None], A[np.maximum(H.vsrc, 0)], 1.0)
+        return {'vval': (v, 0, np.ones(W, bool))}
+
+    def op_wt(self):
+        H = self.H
+        A = self.V('Aval')
+        v = np.where((H.wtpos >= 0)[:, None], A[np.maximum(H.wtpos, 0)], 0.0)
+        return {'WT': (v, 0, np.ones(W, bool))}
+
+
+# ---------------------------------------------------------------------------------------------------------------- the judge
+def _same(a, b):
+    return a.shape == b.shape and np.array_equal(a.view(np.uint64) if a.dtype == np.float64 else a, b.view(np.uint64) if b.dtype == np.float64 else b)
+
+
+def judge(op, H, b0, case, b1, io1, skip=None):
+    """Everything about ONE launch: the listed outputs against the rule (-> worst ratio to the bound), the exact lanes bit for bit, and every other double
+    and int of both blocks and of the caller's arrays bit-unchanged.  io1: {'x', 'y', 'rec'} after the call, (count, width).  skip: lanes whose VALUES are not judged (lanes that hold planted NaN / Inf / 1e308, where fp64
+    overflows and long double does not); they still count for everything that must stay unchanged.  Raises AssertionError."""
+    with np.errstate(all='ignore'):
+        ref, r64 = Ref(H, b0, case, LD).run(op), Ref(H, b0, case, np.float64).run(op)
+    lay = b0.lay
+    touched = np.zeros(lay.ws_doubles, bool)
+    mtouched = None if b0.mat is None else np.zeros(lay.mat_doubles, bool)
+    itouched = np.zeros((KINT, W), bool)
+    iot = {k: False for k in ('x', 'y', 'rec')}
+    worst, problems = 0.0, []
+    for key, val in ref.items():
+        name, idx = key if isinstance(key, tuple) else (key, None)
+        if name == 'word':
+            itouched[IW['WORD'], idx] = True
+            got = int(b1.v('iw')[IW['WORD'], idx])
+            if got != val:
+                problems.append('%s word %d: %d, expected %d' % (op, idx, got, val))
+            continue
+        want, k, exact = val
+        if want is None:
+            continue
+        if name == 'iw':
+            itouched[idx] = True
+            if not np.array_equal(b1.v('iw')[idx], want):
+                problems.append('%s iw row %d: lanes %s differ' % (op, idx, np.nonzero(b1.v('iw')[idx] != want)[0][:8]))
+            continue
+        if name == 'fact':                                   # (the direct route's inversion counts: 64 ints)
+            o, c = lay.fwd['fact']
+            touched[o:o + c] = True
+            if not np.array_equal(b1.v('fact'), want):
+                problems.append('%s fact: lanes %s differ' % (op, np.nonzero(b1.v('fact') != want)[0][:8]))
+            continue
+        if name == 'io':
+            iot[idx] = True
+            got = np.asarray(io1[idx], np.float64).T
+        else:
+            got = b1.get(key)
+            # mark the range as an output
+            if name in lay.mat and name not in lay.fwd:
+                o, c = lay.mat[name]; tgt = mtouched
+            else:
+                o, c = lay.fwd[name]; tgt = touched
+            if idx is None:
+                tgt[o:o + want.size] = True
+            elif name == 'part':
+                tgt[o + idx * lay.G * W:o + (idx + 1) * lay.G * W] = True
+            else:
+                tgt[o + idx * W:o + (idx + 1) * W] = True
+            got = got[:want.shape[0]] if got.ndim == 2 and want.ndim == 2 else got
+            if got.ndim > 2:                                 # (pg, pg2: [block][row][lane]) -- a vector per lane all the same
+                got, want, r64[key] = got.reshape(-1, W), want.reshape(-1, W), (np.asarray(r64[key][0]).reshape(-1, W),) + tuple(r64[key][1:])
+        want64 = np.asarray(r64[key][0], np.float64)
+        got2, want2, w642 = (np.atleast_2d(a) for a in (got, want, want64))
+        if skip is not None and got2.shape == want2.shape:
+            use = ~np.isin(np.arange(got2.shape[1]), skip)
+            got2, want2, w642 = got2[:, use], want2[:, use], w642[:, use]
+            exact = None if exact is None else exact[use]
+        if got2.shape != want2.shape:
+            problems.append('%s %s: shape %s, expected %s' % (op, key, got2.shape, want2.shape)); continue
+        if want2.size == 0:                      # (m = 0: the m-side vectors are empty)
+            continue
+        if exact is not None and exact.any():
+            g, w = got2[:, exact], want2[:, exact].astype(np.float64)
+            if not _same(np.ascontiguousarray(g), np.ascontiguousarray(w)):
+                problems.append('%s %s: exact lanes %s are not bit-equal' % (op, key, np.nonzero(exact)[0][np.nonzero((g != w).any(axis=0) & ~(np.isnan(g) & np.isnan(w)).all(axis=0))[0]][:8]))
+        fin = np.isfinite(want2)
+        odd = ~fin & ~((np.isnan(want2) & np.isnan(got2)) | (want2 == got2))
+        if odd.any():
+            problems.append('%s %s: %d non-finite entries differ (lanes %s)' % (op, key, odd.sum(), np.unique(np.nonzero(odd)[1])[:8]))
+        for cls in (fin & (np.abs(want2) > 1e15), fin & ~(np.abs(want2) > 1e15)):
+            with np.errstate(all='ignore'):
+                err = np.where(cls, np.abs(got2.astype(LD) - want2), 0).max(axis=0)
+                err = np.where(np.isnan(err), np.inf, err)
+                scale = np.where(cls, np.abs(want2), 0).max(axis=0)
+                e64 = np.where(cls & np.isfinite(w642), np.abs(w642.astype(LD) - want2), 0).max(axis=0)
+                bound = 64 * np.maximum(e64, max(k, 1) * U53 * scale)
+                ratio = np.where(err == 0, 0.0, np.where(bound > 0, err / np.where(bound > 0, bound, 1), np.inf)).astype(np.float64)
+            worst = max(worst, float(ratio.max()))
+            if (ratio > 1).any():
+                b = int(np.argmax(ratio))
+                problems.append('%s %s: ratio %.3g to the bound in lane %d (err %.3g, scale %.3g, k %d)' % (op, key, ratio[b], b, float(err[b]), float(scale[b]), k))
+    # ---- everything else: bit-unchanged
+    ir = lay.fwd['iw']
+    touched[ir[0]:ir[0] + ir[1]] = True
+    bad = np.nonzero((b0.ws.view(np.uint64) != b1.ws.view(np.uint64)) & ~touched)[0]
+    if bad.size:
+        where = [nm for nm in lay.fwd if lay.fwd[nm][0] <= bad[0] < sum(lay.fwd[nm])]
+        problems.append('%s: %d doubles outside its outputs changed, first at %d (%s row %d lane %d)' % (op, bad.size, bad[0], where, (bad[0] - (lay.fwd[where[0]][0] if where else 0)) // W, bad[0] % W))
+    ibad = np.nonzero((b0.v('iw') != b1.v('iw')) & ~itouched)
+    if ibad[0].size:
+        problems.append('%s: ints outside its outputs changed: rows %s lanes %s' % (op, ibad[0][:8], ibad[1][:8]))
+    if b0.mat is not None:
+        bad = np.nonzero((b0.mat.view(np.uint64) != b1.mat.view(np.uint64)) & ~mtouched)[0]
+        if bad.size:
+            problems.append('%s: %d doubles of the matrix block outside its outputs changed, first at %d' % (op, bad.size, bad[0]))
+    for k in ('x', 'y', 'rec'):
+        if not iot[k] and not _same(np.ascontiguousarray(np.asarray(io1[k], np.float64)).ravel(), np.ascontiguousarray(getattr(case, k)).ravel()):
+            problems.append("%s: the caller's %s changed" % (op, k))
+    assert not problems, '\n'.join(problems)
+    return worst
+
+
+def judge_inverse(H, b0, b1):
+    """k_lw_inv by its residual, per inverted lane: max |S Sinv - I| <= 64 max(e64, r 2^-53) with e64 the same residual of numpy's own fp64 inverse (scale: max |I| = 1).
+    Asserts cond_2(S) <= S_COND for every judged lane.  -> (worst ratio, largest condition number)"""
+    r = H.r
+    iw = b0.v('iw')
+    on = np.nonzero(iw[IW['RHOCH']].astype(bool) & ~iw[IW['DONE']].astype(bool))[0]
+    S, Si = b0.v('S').reshape(r, r, W), b1.v('S').reshape(r, r, W)
+    worst, cond = 0.0, 0.0
+    for b in on:
+        if not (np.isfinite(S[:, :, b]).all() and (np.linalg.eigvalsh((S[:, :, b] + S[:, :, b].T) / 2) > 0).all()):
+            continue                                         # (a lane planted with a non-positive pivot: judged by judge(), all NaN)
+        cond = max(cond, float(np.linalg.cond(S[:, :, b])))
+        A = S[:, :, b].astype(LD)
+        res = float(np.abs(A @ Si[:, :, b].astype(LD) - np.eye(r)).max())
+        e64 = float(np.abs(A @ np.linalg.inv(S[:, :, b]).astype(LD) - np.eye(r)).max())
+        worst = max(worst, res / (64 * max(e64, r * U53)))
+    assert cond <= S_COND, cond
+    assert worst <= 1.0, 'inv: residual ratio %.3g to the bound' % worst
+    return worst, cond
+
+
+# ---------------------------------------------------------------------------------------------------------------- lanes are problems: exact scaling
+# ops that are homogeneous in some of their inputs: op -> (inputs to scale, {output: power of the factor})
+HOMOGENEOUS = {'initz': (('x', 'y'), {'z': 1, 'zt': 1, 't': 1, 't2': 1}), 't': (('p',), {'t': 1}), 'kp': (('p', 't'), {'Kp': 1, ('part', PS_PKP): 2}),
+               'cgp': (('r', 'p'), {'p': 1})}
+
+
+def identical_lanes(b):
+    """a copy of the block(s) with lane 0's contents in every lane and every lane live; the word block stays as it was"""
+    b = b.copy()
+    iw0 = b.v('iw').copy()
+    b.ws.reshape(-1, W)[:] = b.ws.reshape(-1, W)[:, :1]
+    if b.mat is not None:
+        b.mat.reshape(-1, W)[:] = b.mat.reshape(-1, W)[:, :1]
+    iw = b.v('iw')
+    iw[:] = iw0                                              # (the int rows are packed two to a double: the copy above scrambled them)
+    iw[:IW['WORD']] = iw0[:IW['WORD'], :1]
+    iw[IW['DONE']] = 0; iw[IW['CGON']] = 1; iw[IW['RHOCH']] = 1
+    return b
+
+
+def scaled_lanes(b, op):
+    """the block with lane 0's contents in every lane, every lane live, and the op's homogeneous inputs of lane b times 2^(b - 32)"""
+    b = identical_lanes(b)
+    for nm in HOMOGENEOUS[op][0]:
+        b.v(nm)[:] *= 2.0 ** (np.arange(W) - 32.0)
+    return b
+
+
+def check_scaled_lanes(b1, op):
+    """every output of lane b is lane 32's times 2^(power (b - 32)), bit for bit (powers of two: no rounding differs between lanes)"""
+    for key, power in HOMOGENEOUS[op][1].items():
+        a = b1.get(key)
+        want = a[..., 32:33] * 2.0 ** (power * (np.arange(W) - 32.0))
+        assert np.array_equal(a.view(np.uint64), want.view(np.uint64)), (op, key, np.nonzero((a != want).any(axis=tuple(range(a.ndim - 1))))[0][:8])
+
+
+# ---------------------------------------------------------------------------------------------------------------- the numpy stand-in of the entry
+STANDIN_OPS = ('load_n', 'load_m', 'init', 'store_n', 'store_m', 'minv', 'initz', 'rhs', 't', 'kp', 'upd', 'resm', 'resn', 'setrho', 'cgupd', 'cgp',
+               'cginit', 'cgalpha', 'cgbeta', 'begin', 'asm_a', 'asm_p', 'norms', 'scale', 'cost', 'cost_apply', 'finish',
+               'd0', 's', 'inv', 'prod_x', 'prod_xs', 'prod_p', 'prod2', 'setl0', 'setl1', 'h', 'x', 'vals', 'wt')        # every op of the entry
+# what each route launches (Engine::test_lockstep validates the same): the direct route has no PCG and no Kp
+PCG_ONLY = ('minv', 't', 'kp', 'cgupd', 'cgp', 'cginit', 'cgalpha', 'cgbeta')
+DIRECT_ONLY = ('d0', 's', 'inv', 'prod_x', 'prod_xs', 'prod_p', 'prod2', 'setl0', 'setl1', 'h', 'x', 'vals', 'wt')
+MAT_ONLY = ('begin', 'asm_a', 'asm_p', 'norms', 'scale', 'cost', 'cost_apply', 'finish', 'vals', 'wt')
+
+
+def route_ops(H, mat):
+    """the ops that belong to a handle's route, to mat and to the handle (m = 0: what a solve never launches then)"""
+    m_side = ('load_m', 'store_m', 'initz', 't', 'resm', 'setrho', 'asm_a')
+    return [op for op in STANDIN_OPS if op not in (PCG_ONLY if H.r else DIRECT_ONLY) and (mat or op not in MAT_ONLY) and (H.m > 0 or op not in m_side)]
+
+
+class Standin:
+    """osqp_hip_test_lockstep in plain fp64 numpy for every op (STANDIN_OPS): the same block layout, ls_rows' strips, four-entry unroll and tail, ls_put's and ls_fold's
+    wave orders, vectorised over the 64 lanes only.  bug: one planted mistake (tests/test_lockstep_ref.py lists them)."""
+    def __init__(self, H, bug=None):
+        self.H, self.bug = H, bug
+
+    def call(self, ops, blk, case):
+        b = blk.copy()
+        io = self.io = dict(x=case.x.copy(), y=case.y.copy(), rec=case.rec.copy())
+        with np.errstate(all='ignore'):                      # (planted NaN / Inf / 1e308 are inputs here)
+            for op in ops:
+                getattr(self, 'k_' + op)(b, case)
+        return b, io
+
+    # -- the device functions
+    def vals(self, b, which):
+        H = self.H
+        if which == 'A' and H.r:                             # the direct route reads A through the view
+            return (b.v('vval') if b.mat is not None else H.Av[2][:, None] * np.ones((1, W))), H.Av
+        M = H.A if which == 'A' else H.B
+        return (b.v(which + 'val') if b.mat is not None else M[2][:, None] * np.ones((1, W))), M
+
+    def rows(self, b, which, NA, load, row, g_of=None):
+        """ls_rows: per workgroup the rows of its four waves; load(c) -> the gathered operands, fma handled here as acc[a] += v * g[a] unless load returns a
+        callable.  Returns nothing: row(j, acc, g, w) is the epilogue."""
+        val, M = self.vals(b, which)
+        rp, col = M[0], M[1]
+        nrows, G = len(rp) - 1, self.H.G
+        rpw = (nrows + 4 * G - 1) // (4 * G)
+        for g in range(G):
+            for w in range(4):
+                r0 = (4 * g + w) * rpw
+                r1 = min(r0 + rpw, nrows)
+                if self.bug == 'strip_loses_last_row' and r1 - r0 == rpw and rpw > 1:
+                    r1 -= 1
+                for j in range(r0, r1):
+                    k, k1 = int(rp[j]), int(rp[j + 1])
+                    acc = [np.zeros(W) for _ in range(NA)]
+                    if self.bug == 'tail_drops_last_of_5' and k1 - k == 5:
+                        k1 -= 1
+                    for e in range(k, k1):                   # (four in flight, then the tail: the same order of additions)
+                        load(j, int(col[e]), val[e], acc)
+                    row(j, acc, g, w)
+
+    def put(self, b, slot0, kinds, wave_vals):
+        """ls_put: wave_vals[g][w] = list of statistics; combined in wave order"""
+        part = b.v('part')
+        for g, waves in enumerate(wave_vals):
+            for s, kind in enumerate(kinds):
+                vs = [waves[w][s] for w in range(4)]
+                if kind == 'max':
+                    v = _nanmax(_nanmax(_nanmax(vs[0], vs[1]), vs[2]), vs[3])
+                else:
+                    v = ((vs[0] + vs[1]) + vs[2]) + vs[3]
+                part[slot0 + s, g] = v
+
+    def fold(self, part, G, kind):
+        acc = [np.full(W, -np.inf) if kind == 'max' else np.zeros(W) for _ in range(4)]
+        gs = range(G - 1 if self.bug == 'fold_skips_last_partial' else G)
+        for g in gs:
+            acc[g % 4] = _nanmax(acc[g % 4], part[g]) if kind == 'max' else acc[g % 4] + part[g]
+        return _nanmax(_nanmax(_nanmax(acc[0], acc[1]), acc[2]), acc[3]) if kind == 'max' else ((acc[0] + acc[1]) + acc[2]) + acc[3]
+
+    def lane(self, a):
+        return np.roll(a, -1, axis=-1) if self.bug == 'lane_reads_next_lane' else a
+
+    # -- the kernels
+    def k_minv(self, b, c):
+        H = self.H
+        if not b.v('iw')[IW['WORD'], WD['RHOANY']]:
+            return
+        rho, Minv, flag = b.v('rho'), b.v('Minv'), b.v('iw')[IW['RHOCH']].astype(bool)
+        def load(j, cc, v, acc):
+            if cc >= H.n:
+                if not (self.bug == 'minv_without_rho_term' and j == H.n // 2):
+                    acc[0] += rho[cc - H.n] * v * v
+            elif cc == j:
+                acc[1] = v * np.ones(W)
+        def row(j, acc, g, w):
+            Minv[j] = np.where(flag, 1.0 / (acc[1] + acc[0]) if H.precond else 1.0, Minv[j])
+        self.rows(b, 'B', 2, load, row)
+
+    def k_rhs(self, b, c):
+        H = self.H
+        live = ~b.v('iw')[IW['DONE']].astype(bool)
+        if self.bug == 'store_to_frozen_lane':
+            live = np.ones(W, bool)
+        st = [[[np.zeros(W), np.zeros(W), np.zeros(W)] for _ in range(4)] for _ in range(H.G)]
+        x, xs, q, t, t2, Minv, r, p = (b.v(k) for k in ('x', 'xs', 'q', 't', 't2', 'Minv', 'r', 'p'))
+        def load(j, cc, v, acc):
+            if cc < H.n:
+                acc[1] += v * xs[cc]
+            else:
+                acc[0] += v * t[cc - H.n]; acc[1] += v * t2[cc - H.n]
+        def row(j, acc, g, w):
+            rhs = H.sigma * x[j] - q[j] + acc[0]; rr = rhs - acc[1]; zz = Minv[j] * rr
+            r[j] = np.where(live, rr, r[j]); p[j] = np.where(live, zz, p[j])
+            s = st[g][w]
+            s[2] = s[2] + rr * zz; s[1] = _nanmax(s[1], np.abs(rr)); s[0] = _nanmax(s[0], np.abs(rhs))
+        self.rows(b, 'B', 2, load, row)
+        self.put(b, PS_BN, ('max', 'max', 'sum'), st)
+
+    def k_kp(self, b, c):
+        H = self.H
+        if not b.v('iw')[IW['WORD'], WD['CGANY']]:
+            return
+        on = b.v('iw')[IW['CGON']].astype(bool)
+        st = [[[np.zeros(W)] for _ in range(4)] for _ in range(H.G)]
+        p, t, Kp = b.v('p'), b.v('t'), b.v('Kp')
+        def load(j, cc, v, acc):
+            acc[0] += v * (self.lane(p[cc]) if cc < H.n else t[cc - H.n])
+        def row(j, acc, g, w):
+            Kp[j] = np.where(on, acc[0], Kp[j]); st[g][w][0] = st[g][w][0] + acc[0] * p[j]
+        self.rows(b, 'B', 1, load, row)
+        self.put(b, PS_PKP, ('sum',), st)
+
+    def k_initz(self, b, c):
+        x, rho, y = b.v('x'), b.v('rho'), b.v('y')
+        flat = b.ws
+        zo = b.lay.fwd['z'][0]
+        def load(j, cc, v, acc):
+            acc[0] += v * x[cc]
+        def row(i, acc, g, w):
+            a = acc[0]
+            b.v('z')[i] = a; b.v('zt')[i] = a; b.v('t')[i] = rho[i] * a - y[i]; b.v('t2')[i] = rho[i] * a
+            if self.bug == 'store_one_row_past' and i == self.H.m - 1:
+                flat[zo + (i + 1) * W:zo + (i + 2) * W] = a
+        self.rows(b, 'A', 1, load, row)
+
+    def k_t(self, b, c):
+        if not b.v('iw')[IW['WORD'], WD['CGANY']]:
+            return
+        on, p, rho, t = b.v('iw')[IW['CGON']].astype(bool), b.v('p'), b.v('rho'), b.v('t')
+        def load(j, cc, v, acc):
+            acc[0] += v * p[cc]
+        def row(i, acc, g, w):
+            t[i] = np.where(on, rho[i] * acc[0], t[i])
+        self.rows(b, 'A', 1, load, row)
+
+    def k_setrho(self, b, c):
+        H = self.H
+        if not b.v('iw')[IW['WORD'], WD['RHOANY']]:
+            return
+        on = b.v('iw')[IW['RHOCH']].astype(bool)[None, :]
+        rb, eqf = b.v('sc')[SC['RHOBAR']], b.v('sc')[SC['EQF']]
+        l, u = b.v('l'), b.v('u')
+        cls = np.where((l < -INFTY * 1e-4) & (u > INFTY * 1e-4), -1, np.where(u - l < 1e-4, 1, 0)) if H.rho_is_vec else np.zeros(l.shape, int)
+        rh = np.where(cls == -1, 1e-6, np.where(cls == 1, (eqf * rb)[None, :], rb[None, :]))
+        t, t2 = rh * b.v('z') - b.v('y'), rh * b.v('zt')
+        b.v('rho')[:] = np.where(on, rh, b.v('rho')); b.v('t')[:] = np.where(on, t, b.v('t')); b.v('t2')[:] = np.where(on, t2, b.v('t2'))
+
+    def k_cgupd(self, b, c):
+        H = self.H
+        if not b.v('iw')[IW['WORD'], WD['CGANY']]:
+            return
+        on, al = b.v('iw')[IW['CGON']].astype(bool), b.v('sc')[SC['ALPHA']]
+        st = [[[np.zeros(W), np.zeros(W)] for _ in range(4)] for _ in range(H.G)]
+        xs, p, r, Kp, Minv = (b.v(k) for k in ('xs', 'p', 'r', 'Kp', 'Minv'))
+        for j in range(H.n):
+            g, w = (j % (4 * H.G)) // 4, j % 4
+            rr = r[j] - al * Kp[j]; zz = Minv[j] * rr
+            xs[j] = np.where(on, xs[j] + al * p[j], xs[j]); r[j] = np.where(on, rr, r[j])
+            st[g][w][1] = np.where(on, st[g][w][1] + rr * zz, st[g][w][1]); st[g][w][0] = np.where(on, _nanmax(st[g][w][0], np.abs(rr)), st[g][w][0])
+        self.put(b, PS_RN, ('max', 'sum'), st)
+
+    def k_cgp(self, b, c):
+        if not b.v('iw')[IW['WORD'], WD['CGANY']]:
+            return
+        on = b.v('iw')[IW['CGON']].astype(bool)[None, :]
+        b.v('p')[:] = np.where(on, b.v('Minv') * b.v('r') + b.v('sc')[SC['BETA']] * b.v('p'), b.v('p'))
+
+    def k_cginit(self, b, c):
+        H, part, sc, iw = self.H, b.v('part'), b.v('sc'), b.v('iw')
+        bn, rn, rz = self.fold(part[PS_BN], H.G, 'max'), self.fold(part[PS_RN], H.G, 'max'), self.fold(part[PS_RZ], H.G, 'sum')
+        tol = np.maximum(H.pcg_rel * bn, 1e-15) if H.pcg_rel > 0 else np.where(iw[IW['RELRULE']] != 0, np.maximum(0.1 * bn, 1e-13), np.maximum(1e-14 * bn, sc[SC['EPSCG']]))
+        on = (iw[IW['DONE']] == 0) & (H.cg_max > 0) & (rn > tol)
+        sc[SC['RZ']] = rz; sc[SC['RN']] = rn; sc[SC['TOL']] = tol
+        iw[IW['CGON']] = on
+        iw[IW['WORD'], WD['CGANY']] = int(on.any()); iw[IW['WORD'], WD['CGIT']] = 0
+
+    def k_cgalpha(self, b, c):
+        iw, sc = b.v('iw'), b.v('sc')
+        if not iw[IW['WORD'], WD['CGANY']]:
+            return
+        pkp = self.fold(b.v('part')[PS_PKP], self.H.G, 'sum')
+        with np.errstate(all='ignore'):
+            sc[SC['ALPHA']] = np.where(iw[IW['CGON']] != 0, sc[SC['RZ']] / pkp, 0.0)
+
+    def k_cgbeta(self, b, c):
+        iw, sc, G = b.v('iw'), b.v('sc'), self.H.G
+        if not iw[IW['WORD'], WD['CGANY']]:
+            return
+        rn2, rz2 = self.fold(b.v('part')[PS_RN], G, 'max'), self.fold(b.v('part')[PS_RZ], G, 'sum')
+        on = iw[IW['CGON']] != 0
+        with np.errstate(all='ignore'):
+            sc[SC['BETA']] = np.where(on, rz2 / sc[SC['RZ']], sc[SC['BETA']])
+        sc[SC['RZ']] = np.where(on, rz2, sc[SC['RZ']]); sc[SC['RN']] = np.where(on, rn2, sc[SC['RN']])
+        iw[IW['PCG']] += on
+        on2 = on & (rn2 > sc[SC['TOL']])
+        iw[IW['CGON']] = on2
+        iw[IW['WORD'], WD['CGANY']] = int(on2.any()); iw[IW['WORD'], WD['CGIT']] += 1
+
+    def k_load_n(self, b, c):
+        H = self.H
+        mat = b.mat is not None
+        mine = (np.arange(W) < c.count)[None, :]
+        def tile(a):
+            out = np.zeros((H.n, W)); out[:, :c.count] = a[:, H.pc].T
+            return self.lane(out)
+        D = b.v('D') if mat else H.D[:, None]
+        Dinv = b.v('Dinv') if mat else H.Dinv[:, None]
+        cc = b.v('sc')[SC['C']][None, :] if mat else H.c
+        b.v('q')[:] = np.where(mine, cc * D * tile(c.q), 0.0)
+        xv = np.where(mine, tile(c.x) * Dinv, 0.0) if c.warm else np.zeros((H.n, W))
+        b.v('x')[:H.n] = xv; b.v('xs')[:H.n] = xv; b.v('dx')[:H.n] = 0.0
+
+    def k_norms(self, b, c):
+        H = self.H
+        lim = (lambda v: v) if self.bug == 'norms_without_clamp' else (lambda v: np.where(v < 1e-4, 1.0, np.where(v > 1e4, 1e4, v)))
+        for M, vals, dst in ((H.B, b.v('Bval'), b.v('r')), (H.A, b.v('Aval'), b.v('t'))):
+            rp = M[0]
+            for j in range(len(rp) - 1):
+                mx = np.zeros(W)
+                for e in range(rp[j], rp[j + 1]):
+                    mx = np.fmax(mx, np.abs(vals[e]))
+                with np.errstate(all='ignore'):
+                    dst[j] = 1.0 / np.sqrt(lim(mx))
+
+    # -- scalings and cost scale as a kernel reads them (ls_sv): the handle's vector or the lane's own column
+    def sv(self, b, name):
+        return b.v(name) if b.mat is not None else np.asarray(getattr(self.H, name))[:, None] * np.ones((1, W))
+
+    def cs(self, b, inv=False):
+        return b.v('sc')[SC['CINV' if inv else 'C']] if b.mat is not None else np.full(W, self.H.cinv if inv else self.H.c)
+
+    def tile_in(self, a, perm, width):
+        """ls_tile_in: (count, width) caller's numbering -> (width, 64) engine's numbering, zero in the lanes >= count"""
+        out = np.zeros((width, W))
+        out[:, :a.shape[0]] = a[:, perm].T
+        return out
+
+    def k_load_m(self, b, c):
+        H = self.H
+        mine = (np.arange(W) < c.count)[None, :]
+        E, Einv = self.sv(b, 'E'), self.sv(b, 'Einv')
+        l = np.where(mine, E * np.fmax(self.tile_in(c.l, H.pr, H.m), -INFTY), -INFTY)
+        u = np.where(mine, E * np.fmin(self.tile_in(c.u, H.pr, H.m), INFTY), INFTY)
+        b.v('l')[:] = l; b.v('u')[:] = u; b.v('dy')[:] = 0.0
+        b.v('y')[:] = np.where(mine, self.tile_in(c.y, H.pr, H.m) * Einv * self.cs(b)[None, :], 0.0) if c.warm else 0.0
+        loose = (l < -INFTY * 1e-4) & (u > INFTY * 1e-4)
+        ineq = (~loose & ~(u - l < 1e-4)) if H.rho_is_vec else np.ones(l.shape, bool)
+        for t in range((H.m + 63) // 64):                    # a tile's count: wave w takes rows w, w + 4, ..; the four waves in order
+            cnt = [np.zeros(W) for _ in range(4)]
+            for i in range(64 * t, min(64 * t + 64, H.m)):
+                cnt[i % 4] = cnt[i % 4] + ineq[i]
+            b.v('parti')[t] = ((cnt[0] + cnt[1]) + cnt[2]) + cnt[3]
+
+    def k_init(self, b, c):
+        H = self.H
+        tm = (H.m + 63) // 64 if H.m > 0 else 0
+        nin = self.fold(b.v('parti'), tm, 'sum')
+        sc, iw, lanes = b.v('sc'), b.v('iw'), np.arange(W)
+        sc[SC['RHOBAR']] = H.rho0; sc[SC['EQF']] = np.where(nin == 0.0, 1e3, H.eq_factor); sc[SC['EPSCG']] = 0.0; sc[SC['EPSPREV']] = np.inf
+        iw[IW['DONE']] = lanes >= c.count; iw[IW['STATUS']] = UNSOLVED
+        for nm, v in (('RHOUPD', 0), ('PCG', 0), ('RELRULE', 1), ('CGON', 0), ('RHOCH', 1), ('SIDE', 0)):
+            iw[IW[nm]] = v
+        for nm, v in (('CGANY', 0), ('LIVE', c.count), ('RHOANY', 1), ('PCGSUM', 0), ('CGIT', 0)):
+            iw[IW['WORD'], WD[nm]] = v
+
+    def tile_out(self, v, perm, dst, count):
+        for bb in range(count):
+            dst[bb, perm] = v[:, bb]
+
+    def k_store_n(self, b, c):
+        H = self.H
+        st = b.v('iw')[IW['STATUS']]
+        D, x, dx = self.sv(b, 'D'), b.v('x')[:H.n], b.v('dx')[:H.n]
+        v = np.empty((H.n, W))
+        for lane in range(W):                                # batch_out_x, lane by lane
+            if st[lane] in (5, 6):
+                v[:, lane] = D[:, lane] * dx[:, lane] if H.unscaled else dx[:, lane]
+            elif st[lane] in (3, 4):
+                v[:, lane] = np.nan
+            else:
+                v[:, lane] = D[:, lane] * x[:, lane] if H.scaling else x[:, lane]
+        self.tile_out(v, H.pc, self.io['x'], c.count)
+        self.io['rec'][:] = b.v('rec')[:c.count]
+
+    def k_store_m(self, b, c):
+        H = self.H
+        st = b.v('iw')[IW['STATUS']]
+        E, y, dy, ci = self.sv(b, 'E'), b.v('y'), b.v('dy'), self.cs(b, True)
+        v = np.empty((H.m, W))
+        for lane in range(W):                                # batch_out_y
+            if st[lane] in (3, 4):
+                v[:, lane] = E[:, lane] * dy[:, lane] if H.unscaled else dy[:, lane]
+            elif st[lane] in (5, 6):
+                v[:, lane] = np.nan
+            else:
+                v[:, lane] = ci[lane] * E[:, lane] * y[:, lane] if H.scaling else y[:, lane]
+        self.tile_out(v, H.pr, self.io['y'], c.count)
+
+    def k_upd(self, b, c):
+        H = self.H
+        live = ~b.v('iw')[IW['DONE']].astype(bool)
+        al = H.alpha
+        xs, rho, z, y, l, u = (b.v(k) for k in ('xs', 'rho', 'z', 'y', 'l', 'u'))
+        if H.m > 0:
+            def load(j, cc, v, acc):
+                acc[0] += v * xs[cc]
+            def row(i, acc, g, w):
+                a = acc[0]
+                zr = al * a + (1.0 - al) * z[i]              # step_row (the kernel writes this sum as one FMA: within the bound)
+                zn = np.fmin(np.fmax(zr + y[i] / rho[i], l[i]), u[i])
+                dy = rho[i] * (zr - zn)
+                yn = y[i] + dy
+                for nm, val in (('y', yn), ('dy', dy), ('z', zn), ('zt', a), ('t', rho[i] * zn - yn), ('t2', rho[i] * a)):
+                    b.v(nm)[i] = np.where(live, val, b.v(nm)[i])
+            self.rows(b, 'A', 1, load, row)
+        x = b.v('x')
+        xn = (1.0 - al) * x + al * xs                        # step_col
+        b.v('dx')[:] = np.where(live[None, :], xn - x, b.v('dx')); x[:] = np.where(live[None, :], xn, x)
+
+    def k_resm(self, b, c):
+        H = self.H
+        x, dx, z, dyv, l, u = (b.v(k) for k in ('x', 'dx', 'z', 'dy', 'l', 'u'))
+        E, Ei = self.sv(b, 'E'), self.sv(b, 'Einv')
+        st = [[[np.zeros(W) for _ in range(8)] + [np.full(W, -np.inf), np.full(W, -np.inf), np.zeros(W)] for _ in range(4)] for _ in range(H.G)]
+        def load(j, cc, v, acc):
+            acc[0] += v * x[cc]; acc[1] += v * dx[cc]
+        def row(i, acc, g, w):
+            s = st[g][w]
+            ax, pr = acc[0], acc[0] - z[i]
+            for k, val in enumerate((Ei[i] * pr, Ei[i] * ax, Ei[i] * z[i], pr, ax, z[i], E[i] * dyv[i], dyv[i])):
+                s[k] = _nanmax(s[k], np.abs(val))
+            s[10] = s[10] + (u[i] * np.fmax(dyv[i], 0.0) + l[i] * np.fmin(dyv[i], 0.0))
+            adx = Ei[i] * acc[1] if H.unscaled else acc[1]
+            s[8] = np.where(u[i] < INFTY * 1e-4, _nanmax(s[8], adx), s[8]); s[9] = np.where(l[i] > -INFTY * 1e-4, _nanmax(s[9], -adx), s[9])
+        self.rows(b, 'A', 2, load, row)
+        self.put(b, PS_M0, ('max',) * 10 + ('sum',), st)
+
+    def k_resn(self, b, c):
+        H = self.H
+        x, dx, q, y, dyv = (b.v(k) for k in ('x', 'dx', 'q', 'y', 'dy'))
+        D, Di = self.sv(b, 'D'), self.sv(b, 'Dinv')
+        st = [[[np.zeros(W) for _ in range(17)] for _ in range(4)] for _ in range(H.G)]
+        def load(j, cc, v, acc):
+            if cc < H.n:
+                acc[0] += v * x[cc]; acc[2] += v * dx[cc]
+            else:
+                acc[1] += v * y[cc - H.n]; acc[3] += v * dyv[cc - H.n]
+        def row(j, acc, g, w):
+            s = st[g][w]
+            px = acc[0] - H.sigma * x[j]; dr = px + q[j] + acc[1]
+            pdx = acc[2] - H.sigma * dx[j]; atdy = acc[3]
+            for k, val in enumerate((Di[j] * dr, Di[j] * px, Di[j] * acc[1], dr, px, acc[1], D[j] * dx[j], dx[j], q[j], Di[j] * q[j], Di[j] * atdy, atdy, Di[j] * pdx, pdx)):
+                s[k] = _nanmax(s[k], np.abs(val))
+            s[14] = s[14] + x[j] * px; s[15] = s[15] + q[j] * x[j]; s[16] = s[16] + q[j] * dx[j]
+        self.rows(b, 'B', 4, load, row)
+        self.put(b, PS_N0, ('max',) * 14 + ('sum',) * 3, st)
+
+    def k_begin(self, b, c):
+        H = self.H
+        q = self.tile_in(c.q, H.pc, H.n)
+        q[:, c.count:] = np.asarray(H.q0)[:, None]
+        b.v('q')[:] = q; b.v('D')[:] = 1.0; b.v('E')[:] = 1.0; b.v('sc')[SC['C']] = 1.0
+        for j in range(H.n):
+            b.v('Bval')[H.Bdiag[j]] = 0.0
+
+    def asm(self, b, c, src, raw, vmap, write):
+        for e in range(len(vmap)):                           # one caller's entry after the other, as a workgroup's waves take them
+            pos = int(vmap[e])
+            v = np.full(W, raw[pos])
+            if src is not None:
+                v[:c.count] = src[:, e]
+            write(pos, v)
+
+    def k_asm_a(self, b, c):
+        H = self.H
+        def write(pos, v):
+            b.v('Aval')[H.AmA[pos]] = v; b.v('Bval')[H.AmB[pos]] = v
+        self.asm(b, c, c.Ax, H.Araw, H.avmap, write)
+
+    def k_asm_p(self, b, c):
+        H = self.H
+        def write(pos, v):
+            b.v('Bval')[H.Pm1[pos]] = v
+            if H.Pm2[pos] >= 0 and H.Pm2[pos] != H.Pm1[pos]:
+                b.v('Bval')[H.Pm2[pos]] = v
+        self.asm(b, c, c.Px, H.Praw, H.pvmap, write)
+
+    def strip_rows(self, nrows):
+        """ls_strip: (g, w, rows) of every wave"""
+        G = self.H.G
+        rpw = (nrows + 4 * G - 1) // (4 * G)
+        return [(g, w, range((4 * g + w) * rpw, min((4 * g + w) * rpw + rpw, nrows))) for g in range(G) for w in range(4)]
+
+    def k_scale(self, b, c):
+        H = self.H
+        dt, et, Av, Bv, q = b.v('r'), b.v('t'), b.v('Aval'), b.v('Bval'), b.v('q')
+        rpA, colA = H.A[0], H.A[1]
+        rpB, colB = H.B[0], H.B[1]
+        for g, w, rows in self.strip_rows(H.m):
+            for i in rows:
+                for e in range(rpA[i], rpA[i + 1]):
+                    Av[e] = Av[e] * (et[i] * dt[colA[e]])
+                b.v('E')[i] = b.v('E')[i] * et[i]
+        st = [[[np.zeros(W), np.zeros(W)] for _ in range(4)] for _ in range(H.G)]
+        for g, w, rows in self.strip_rows(H.n):
+            for j in rows:
+                mx = np.zeros(W)
+                for e in range(rpB[j], rpB[j + 1]):
+                    cc = colB[e]
+                    v = Bv[e] * (dt[cc] * dt[j] if cc < H.n else et[cc - H.n] * dt[j])
+                    Bv[e] = v
+                    if cc < H.n:
+                        mx = np.fmax(mx, np.abs(v))
+                qj = q[j] * dt[j]
+                q[j] = qj; b.v('D')[j] = b.v('D')[j] * dt[j]
+                st[g][w][1] = st[g][w][1] + mx; st[g][w][0] = np.fmax(st[g][w][0], np.abs(qj))
+        self.put(b, PS_BN, ('max', 'sum'), st)
+
+    def k_cost(self, b, c):
+        H, sc = self.H, b.v('sc')
+        lim = lambda v: np.where(v < 1e-4, 1.0, np.where(v > 1e4, 1e4, v))
+        nq, sm = self.fold(b.v('part')[PS_BN], H.G, 'max'), self.fold(b.v('part')[PS_BN + 1], H.G, 'sum')
+        ct = 1.0 / lim(np.fmax(lim(nq), sm / max(H.n, 1)))
+        sc[SC['CT']] = ct; sc[SC['C']] = sc[SC['C']] * ct
+
+    def k_cost_apply(self, b, c):
+        H = self.H
+        ct, Bv, rpB, colB = b.v('sc')[SC['CT']], b.v('Bval'), self.H.B[0], self.H.B[1]
+        for g, w, rows in self.strip_rows(H.n):
+            for j in rows:
+                for e in range(rpB[j], rpB[j + 1]):
+                    if colB[e] >= H.n:
+                        break                                # (the P part comes first in a row of B)
+                    Bv[e] = Bv[e] * ct
+                b.v('q')[j] = b.v('q')[j] * ct
+
+    def k_finish(self, b, c):
+        H = self.H
+        for j in range(H.n):
+            b.v('Dinv')[j] = 1.0 / b.v('D')[j]
+            b.v('Bval')[H.Bdiag[j]] = b.v('Bval')[H.Bdiag[j]] + H.sigma
+        for i in range(H.m):
+            b.v('Einv')[i] = 1.0 / b.v('E')[i]
+        b.v('sc')[SC['CINV']] = 1.0 / b.v('sc')[SC['C']]
+
+    # -- the direct route
+    def wt(self, b):
+        H = self.H
+        return b.v('WT').reshape(H.n, H.r, W) if b.mat is not None else H.WT[:, :, None] * np.ones((1, 1, W))
+
+    def k_d0(self, b, c):
+        H = self.H
+        if not b.v('iw')[IW['WORD'], WD['RHOANY']]:
+            return
+        rho, Minv, flag = b.v('rho'), b.v('Minv'), b.v('iw')[IW['RHOCH']].astype(bool)
+        def load(j, cc, v, acc):
+            if cc >= H.n:
+                if not H.islong[cc - H.n]:
+                    acc[0] += rho[cc - H.n] * v * v
+            elif cc == j:
+                acc[1] = v * np.ones(W)
+        def row(j, acc, g, w):
+            Minv[j] = np.where(flag, 1.0 / (acc[1] + acc[0]), Minv[j])
+        self.rows(b, 'B', 2, load, row)
+
+    def k_s(self, b, c):
+        H, r = self.H, self.H.r
+        if not b.v('iw')[IW['WORD'], WD['RHOANY']]:
+            return
+        WT, Minv, rho, flag, S = self.wt(b), b.v('Minv'), b.v('rho'), b.v('iw')[IW['RHOCH']].astype(bool), b.v('S')
+        for a in range(r):                                   # workgroup (a, eight columns): wave w takes j = w, w + 4, ..; the waves in order
+            for cc in range(r):
+                acc = [np.zeros(W) for _ in range(4)]
+                for j in range(H.n):
+                    acc[j % 4] = acc[j % 4] + (WT[j, a] * Minv[j]) * WT[j, cc]
+                v = ((acc[0] + acc[1]) + acc[2]) + acc[3]
+                if cc == a:
+                    v = v + 1.0 / rho[H.rows[a]]
+                S[a * r + cc] = np.where(flag, v, S[a * r + cc])
+
+    def k_inv(self, b, c):
+        H, r = self.H, self.H.r
+        iw = b.v('iw')
+        if not iw[IW['WORD'], WD['RHOANY']]:
+            return
+        on = iw[IW['RHOCH']].astype(bool) & ~iw[IW['DONE']].astype(bool)
+        inv = Ref.gauss_jordan(None, b.v('S').reshape(r, r, W).copy()).reshape(r * r, W)
+        b.v('S')[:] = np.where(on[None, :], inv, b.v('S'))
+        b.v('fact')[:] += on
+
+    def prod_into(self, b, v, name):
+        """lw_prod: the handle's form (a wave takes eight rows, a0 = 8 w, + 32, ..) and the chunk's own (a wave takes two rows; `two`: the second exists)"""
+        H, r, lay = self.H, self.H.r, self.H.lay
+        WT = self.wt(b)
+        o, cnt = lay.fwd[name]
+        flat = b.ws[o:]                                      # (flat from the vector's start: a store past a block's rows lands where the kernel's would)
+        for g in range(lay.GC):
+            j0, j1 = g * lay.cb, min((g + 1) * lay.cb, H.n)
+            if b.mat is None:
+                for a in range(r):
+                    acc = np.zeros(W)
+                    for j in range(j0, j1):
+                        acc = acc + WT[j, a] * v[j]
+                    flat[(g * r + a) * W:(g * r + a + 1) * W] = acc
+            else:
+                for a in range(0, r, 2):
+                    two = True if self.bug == 'prod_two_edge_reads_row_r' else a + 1 < r
+                    s0, s1 = np.zeros(W), np.zeros(W)
+                    WTf = b.v('WT')                          # ((j r + a), 64): row r of column j IS row 0 of column j + 1
+                    for j in range(j0, j1):
+                        s0 = s0 + WTf[j * r + a] * v[j]
+                        if two and j * r + a + 1 < WTf.shape[0]:
+                            s1 = s1 + WTf[j * r + a + 1] * v[j]
+                    flat[(g * r + a) * W:(g * r + a + 1) * W] = s0
+                    if two:
+                        flat[(g * r + a + 1) * W:(g * r + a + 2) * W] = s1
+
+    def k_prod_x(self, b, c):
+        self.prod_into(b, b.v('x'), 'pg')
+
+    def k_prod_xs(self, b, c):
+        self.prod_into(b, b.v('xs'), 'pg2')
+
+    def k_prod_p(self, b, c):
+        self.prod_into(b, b.v('p'), 'pg')
+
+    def k_prod2(self, b, c):
+        self.prod_into(b, b.v('x'), 'pg'); self.prod_into(b, b.v('xs'), 'pg2')
+
+    def lw_fold(self, part):
+        a = np.zeros(W)
+        G = part.shape[0] - (1 if self.bug == 'fold_skips_last_partial' else 0)
+        for g in range(G):
+            a = a + part[g]
+        return a
+
+    def setl(self, b, start):
+        H = self.H
+        live = ~b.v('iw')[IW['DONE']].astype(bool) | bool(start)
+        for a in range(H.r):
+            sx, ss = self.lw_fold(b.v('pg')[:, a]), self.lw_fold(b.v('pg2')[:, a])
+            b.v('x')[H.n + a] = np.where(live, sx, b.v('x')[H.n + a]); b.v('xs')[H.n + a] = np.where(live, ss, b.v('xs')[H.n + a])
+            if start:
+                b.v('dx')[H.n + a] = 0.0
+
+    def k_setl0(self, b, c):
+        self.setl(b, 0)
+
+    def k_setl1(self, b, c):
+        self.setl(b, 1)
+
+    def k_h(self, b, c):
+        H, r = self.H, self.H.r
+        live = ~b.v('iw')[IW['DONE']].astype(bool)
+        g = [self.lw_fold(b.v('pg')[:, cc]) for cc in range(r)]
+        S, rho = b.v('S'), b.v('rho')
+        for a in range(r):
+            h = np.zeros(W)
+            for cc in range(r):
+                h = h + S[a * r + cc] * g[cc]
+            b.v('h')[a] = np.where(live, h, b.v('h')[a])
+            b.v('xs')[H.n + a] = np.where(live, b.v('xs')[H.n + a] + h / rho[H.rows[a]], b.v('xs')[H.n + a])
+
+    def k_x(self, b, c):
+        H, r = self.H, self.H.r
+        live = ~b.v('iw')[IW['DONE']].astype(bool)
+        WT, h, xs, p, Minv = self.wt(b), b.v('h').copy(), b.v('xs'), b.v('p'), b.v('Minv')
+        for j in range(H.n):
+            sm = np.zeros(W)
+            for a in range(r):
+                sm = sm + WT[j, a] * h[a]
+            xs[j] = np.where(live, xs[j] + (p[j] - Minv[j] * sm), xs[j])
+
+    def k_vals(self, b, c):
+        H = self.H
+        for e in range(len(H.vsrc)):
+            b.v('vval')[e] = b.v('Aval')[H.vsrc[e]] if H.vsrc[e] >= 0 else 1.0
+
+    def k_wt(self, b, c):
+        H = self.H
+        for e in range(len(H.wtpos)):
+            b.v('WT')[e] = b.v('Aval')[H.wtpos[e]] if H.wtpos[e] >= 0 else 0.0
+
+
+def _nanmax(r, a):
+    return np.where((a > r) | np.isnan(a), a, r)
