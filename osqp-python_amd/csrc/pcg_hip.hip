@@ -649,14 +649,34 @@ __device__ __forceinline__ F1Fold f1_fold_issue(const double *part, const int pa
   f.a = partial_load(part + (SL_GAMMA0 + prev) * kGrid); f.b = partial_load(part + (SL_DELTA + prev) * kGrid); f.c = partial_load(part + (SL_RN0 + prev) * kGrid);
   return f;
 }
+// The fold's three further inputs -- the PCG tolerance, gamma_{k-2}, alpha_{k-2} -- sit at wave-uniform addresses and were written by EARLIER launches.
+// SCAL (the F1 form): they arrive as scalar loads.  As vector loads they are requested behind the 24 KB of partials and the first block's stream, and
+// memory returns a wave's vector requests in order, through the same path of the CU that four workgroups' partials are queuing in: the fold then ends a
+// round trip behind its partials.  The scalar cache is a path of its own and, like the vector caches, starts every launch empty (slot_read_scalar reads
+// the previous launch's phase record the same way).
+// The load goes through the CONSTANT address space, which tells the compiler that the word does not change during the launch.  That holds only because
+// no launch reads back a word it wrote itself: F_k stores gamma_{k-1}, alpha_{k-1} and loads the entries k - 2; the one word a launch both loads and
+// stores is S_TOL_NOW in F_1, where the loaded value is dead (the tolerance is recomputed from ||rhs|| before its first use).  A fold that came to
+// use a word of its own launch must fetch that word with SCAL = false.
+// What it gains, what else was tried (the first block's requests ahead of this fold: they fit, and do not pay -- the fold waits for the volume of its
+// partials, not for a latency) and every figure: DESIGN.md section 4.2 "The fold's scalars as scalar loads", profiles/r12a_f1_fold_overlap_ab.txt.
+// The K form keeps its vector loads (SCAL = false).
+template <bool SCAL, class P>
+__device__ __forceinline__ double f1_fold_ld(P p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  if constexpr (SCAL) return *(const double __attribute__((address_space(4))) *)(unsigned long long)p;
+#endif
+  return *p;
+}
+template <bool SCAL = false>
 __device__ __forceinline__ bool f1_fold_finish(const Dev &d, const int k, const int admm_par, const int probe, const F1Fold &f, double *red, F1Scal &sc) {
   double *gam = gptr(d.scal) + S_HIST, *alp = gptr(d.scal) + S_HIST + kMaxCg + 1;
   const int tid = threadIdx.x;
   sc = F1Scal{0.0, 0.0, k >= 2};
   if (probe == 1) { sc.alpha = 1e-3; sc.beta = k >= 2 ? 0.5 : 0.0; return true; }
   if (k == 0) return true;                                  // F_0 builds r_0 itself (from the slices KA / the chunk's first launch left): nothing to fold yet
-  double tol = gptr(d.scal)[S_TOL_NOW];
-  const double glast = k >= 2 ? gam[k - 2] : 1.0, alast = k >= 2 ? alp[k - 2] : 1.0;
+  double tol = f1_fold_ld<SCAL>(gptr(d.scal) + S_TOL_NOW);
+  const double glast = k >= 2 ? f1_fold_ld<SCAL>(gam + k - 2) : 1.0, alast = k >= 2 ? f1_fold_ld<SCAL>(alp + k - 2) : 1.0;
   double gamma = partial_fold_sum(f.a), rn = partial_fold_max(f.c), delta = partial_fold_sum(f.b);
   block_sum_max_sum(gamma, rn, delta, red);
   if (k == 1 && probe == 0) {
@@ -1088,7 +1108,7 @@ template <int D, bool MIX, bool WT>
 __device__ __forceinline__ bool f1_iteration(const Dev &d, const int k, const int cap, const int admm_par, const int probe, F1Lds &L, F1Stream &S, const F1Rec &rec0, const F1Fold &fold, const int par) {
   KT(0);
   F1Scal sc;
-  if (!f1_fold_finish(d, k, admm_par, probe, fold, L.red, sc)) return false;
+  if (!f1_fold_finish<true>(d, k, admm_par, probe, fold, L.red, sc)) return false;
   const bool vec_only = !probe && k >= cap;                 // the last budgeted update: no operator apply follows
   if (k == 0) f1_body<D, true, MIX, WT>(d, k, vec_only, sc, L, S, rec0, par);
   else f1_body<D, false, MIX, WT>(d, k, vec_only, sc, L, S, rec0, par);
