@@ -89,7 +89,8 @@ typedef struct {
   OSQPInt   scaled_termination;
   OSQPInt   check_termination;            /* interval; 0 = only at max_iter */
   OSQPInt   check_dualgap;                /* termination additionally requires |duality gap| < eps_abs + eps_rel max(|obj|, |dual obj|); honoured by osqp_solve (small QPs
-                                             then take the host-driven loop, not the one-launch kernel); the batch entry points have no gap test and IGNORE it */
+                                             then take the host-driven loop, not the one-launch kernel) and by every batch entry point, per problem on the
+                                             device (record field duality_gap; the adjoint entries have no termination test and do not read it) */
   OSQPFloat time_limit;
   OSQPFloat delta;
   OSQPInt   polish_refine_iter;
@@ -248,7 +249,12 @@ OSQPInt osqp_hip_time_kernel(OSQPSolver *solver, OSQPInt which, OSQPInt reps, do
    one workgroup per problem, iterates in LDS).  q: nbatch x n, l/u: nbatch x m, row-major, NULL = the solver's current
    vector for every problem.  x: nbatch x n, y: nbatch x m (in: warm start if warm != 0; out: solution, or the
    infeasibility certificate).  rec: nbatch x OSQP_HIP_BATCH_REC doubles {status_val, iter, obj_val, prim_res, dual_res, rho, rho_updates,
-   pcg_iters, status_polish, polish_time, rho_estimate, reserved}.  With the `polishing` setting, every SOLVED problem of a directly-solved batch is polished inside
+   pcg_iters, status_polish, polish_time, rho_estimate, duality_gap}.  duality_gap is 0 unless settings.check_dualgap is set: then a problem ends
+   SOLVED (SOLVED_INACCURATE at max_iter) only if, besides the residual tests, |gap| < eps_abs + eps_rel max(|obj_val|, |dual_obj_val|) (x 10 on the
+   approximate pass), with osqp_solve's definitions on the problem's own scaled data -- dual_obj_val = (-1/2 x'Px - sum_i support(l_i, u_i, y_i)) / c over
+   the finite sides the sign of y_i selects, gap = obj_val - dual_obj_val --, and the field is the gap of the point the record describes (the ADMM
+   point; the polished one where polish was accepted; NaN where x or y is a certificate or not finite): dual_obj_val = obj_val - duality_gap.  A
+   batch with the setting does not take the wave-per-problem kernel (OSQPHipStats::batch_wave_split = -1), as with polishing.  With the `polishing` setting, every SOLVED problem of a directly-solved batch is polished inside
    the kernel (reduced KKT system of the guessed active set, regularised by `delta`, factorised in LDS, `polish_refine_iter` refinement
    steps: /root/reference/src/osqppurepy/_osqp.py:1710-1828); the PCG variants do not polish (status_polish = 0).  The linear system of each ADMM iteration is solved DIRECTLY (banded LDL' of the reduced KKT matrix in LDS under a
    bandwidth-reducing ordering; pcg_iters = 0, equality weight 1e3 as in the reference) when that band fits next to the iterates
@@ -289,7 +295,8 @@ OSQPInt osqp_hip_batch_solve_mat_device(OSQPSolver *solver, OSQPInt nbatch, cons
  * A' diag(rho_b) A stopped per problem at cg_tol_fraction x the scaled dual residual (non-increasing; relative before the first residual), equality
  * weight and adaptive rho per problem, termination / approximate statuses at max_iter / infeasibility certificates in x, y / OSQP_NON_CVX on
  * non-finite residuals decided per problem on the device every check_termination / adaptive_rho_interval iterations; time_limit ends a chunk with
- * OSQP_TIME_LIMIT_REACHED for its unfinished problems.  check_dualgap is ignored; per-problem matrices: osqp_hip_batch_solve_lockstep_mat below.
+ * OSQP_TIME_LIMIT_REACHED for its unfinished problems.  check_dualgap is honoured per problem (the record's duality_gap, as on osqp_hip_batch_solve: one more launch, k_ls_supp, in front of
+ * every termination check, none without the setting; after an accepted polish the field is the polished point's gap); per-problem matrices: osqp_hip_batch_solve_lockstep_mat below.
  * POLISH: with settings.polishing every problem of a chunk that ends OSQP_SOLVED is polished before the chunk is written out, all of them at once, by the
  * recurrence osqp_solve's polish runs on the PCG path: the active rows guessed from the ADMM (z, y) (equality rows always), the reduced KKT system solved
  * by steps of this route's own iteration with alpha = 1 and rho = 1 / max(delta, OSQP_HIP_POLISH_DELTA_FLOOR) on the active rows, the others free, the
@@ -370,8 +377,8 @@ OSQPInt osqp_hip_lockstep_mat_scaling(OSQPSolver *solver, OSQPInt b, OSQPFloat *
  * ADAPTIVE RHO is per problem too, but NOT by the batch family's rule (the reference's factor test against adaptive_rho_tolerance): this route applies the
  * rule of osqp_solve on this handle -- the tolerance on the policy's square-root scale (OSQPHipPolicy::rho_tol_exp / OSQP_HIP_RHO_TOL_EXP; the literal
  * value for an LP) and the persistence test (rho_persist / OSQP_HIP_RHO_PERSIST) -- so an element takes the iterations, status and iterate that
- * osqp_update_data_vec + osqp_solve give from the same settings.rho (a loop over one handle starts each solve from the rho the previous one left).  No
- * duality-gap test; per-problem matrices: osqp_hip_batch_solve_lockstep_direct_mat below.  The decision is the structural one taken at setup, whatever became of the single handle's direct
+ * osqp_update_data_vec + osqp_solve give from the same settings.rho (a loop over one handle starts each solve from the rho the previous one left).  The
+ * duality-gap test of check_dualgap as on the PCG route; per-problem matrices: osqp_hip_batch_solve_lockstep_direct_mat below.  The decision is the structural one taken at setup, whatever became of the single handle's direct
  * mode since.
  * POLISH as on osqp_hip_batch_solve_lockstep (settings.polishing, delta, polish_refine_iter): every problem of a chunk that ends OSQP_SOLVED is polished
  * between the ADMM loop and the transposes out by the same recurrence, with the Woodbury solve in place of the PCG -- rho_bar = 1 / delta on the
@@ -788,7 +795,7 @@ OSQPInt osqp_hip_test_woodbury(OSQPSolver *solver, OSQPHipWoodburyTest *t);
      mat      0: the handle's matrices (k_ls_*);  1: per-problem matrices (k_lsm_*), mat_ws is then the chunk's matrix block
      count    1 .. 64 problems;  warm: as the solve entries'
      ops      [nops], 1 <= nops <= 64, each an OSQPHipLockstepOp that belongs to (route, mat) and to this handle: the ops from BEGIN on need mat = 1, ASM_A /
-              ASM_P need stored entries, and the ops a solve never launches with m = 0 (LOAD_M, STORE_M, INITZ, T, RESM, SETRHO) need m > 0
+              ASM_P need stored entries, and the ops a solve never launches with m = 0 (LOAD_M, STORE_M, INITZ, T, RESM, SETRHO, SUPP) need m > 0
      q l u    [count][n] / [count][m] in the caller's numbering, each optional (NULL with length 0: the handle's own vector)
      x y rec  [count][n], [count][m], [count][OSQP_HIP_BATCH_REC]: in (warm start) and out; always uploaded whole and downloaded whole
      Px Ax    with mat: [count][nnz(triu P)] / [count][nnz(A)] in the CSC order given at setup, each optional (NULL with length 0: the handle's values)
@@ -824,6 +831,7 @@ typedef enum {
   OSQP_HIP_LS_PROD_X, OSQP_HIP_LS_PROD_XS, OSQP_HIP_LS_PROD_P, OSQP_HIP_LS_PROD2,       /* the products with the long rows: x -> pg, x~ -> pg2, p -> pg; both of the first two in one pass */
   OSQP_HIP_LS_SETL0, OSQP_HIP_LS_SETL1, OSQP_HIP_LS_H, OSQP_HIP_LS_X,                   /* k_lw_setl with start 0 / 1, k_lw_h, k_lw_x */
   OSQP_HIP_LS_VALS, OSQP_HIP_LS_WT,                                                     /* the chunk's own view values and dense rows (mat) */
+  OSQP_HIP_LS_SUPP,                                                                     /* k_ls_supp (check_dualgap): both routes, with and without mat; needs m > 0 */
   OSQP_HIP_LS_OP_COUNT
 } OSQPHipLockstepOp;
 typedef struct {

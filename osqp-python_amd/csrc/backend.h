@@ -334,6 +334,8 @@ struct Dev {
 struct BatchSettings {
   double c = 1, cinv = 1, sigma = 0, alpha = 0, rho0 = 0, eq_factor = 0, eps_abs = 0, eps_rel = 0, eps_pinf = 0, eps_dinf = 0, cg_frac = 0, rho_tol = 0;
   int max_iter = 0, check = 0, rho_interval = 0, cg_max = 0, unscaled = 0, scaling = 0, precond = 0, rho_is_vec = 0, warm = 0;
+  int check_dualgap = 0;        // settings.check_dualgap: the forward routes test the duality gap per problem (term_rules.h batch_check_gap) and write it to
+                                // the record's column 11; the adjoint entries fill this struct too and never read it
 };
 struct BatchParams : BatchSettings {
   int n, m, nbatch;
@@ -343,7 +345,7 @@ struct BatchParams : BatchSettings {
   const double *q0, *l0, *u0;   // UNSCALED shared vectors [n] / [m]
   double *x, *y;                // in: UNSCALED warm start (if warm), out: UNSCALED solution  [nbatch][n] / [nbatch][m]
   double *rec;                  // [nbatch][kBatchRec]: status, iter, obj, prim_res, dual_res, rho, rho_updates, pcg_iters, status_polish, polish seconds,
-                                // rho_estimate (_osqp.py:1275, at the ADMM point), reserved
+                                // rho_estimate (_osqp.py:1275, at the ADMM point), duality_gap (with check_dualgap; else 0)
   int *iters_out = nullptr;     // optional [nbatch]: ADMM iterations of every problem (device; feeds the next call's launch order)
   const int *order = nullptr;   // optional [nbatch]: workgroup w solves problem order[w] (longest-expected first: the batch ends with its slowest
                                 // problems otherwise; Engine::batch_solve keeps the order of the previous call's iteration counts)

@@ -175,7 +175,10 @@ __device__ __forceinline__ void dd_acc(double a, double v, double &hi, double &l
 // use) -- 5.0 us per ADMM iteration, the form for batches that fit the chip in two rounds (latency: 256 QPs 1.0 ms, 512 QPs 1.5 ms).  2: the 256
 // registers of two resident workgroups, ~150 of the kernel's values in scratch -- 8 us per iteration, but twice the problems in flight: 4096 QPs
 // 8.4 ms against 10.1 (and 10.6 for the banded form).  batch_solve picks by batch size.
-template <int kBB, int EA, int EB, bool DIRECT, bool POLISH = false, bool N128 = false, bool SPEC = false, int SPW = 1>
+// GAP (settings.check_dualgap): like POLISH a separate instantiation of every variant, for the same reason -- with the duality-gap test as a run-time
+// branch the instantiations at 256 registers spill 12 - 56 bytes more and the others take 4 - 7 registers more; the GAP = false kernels are the kernels
+// without the setting, to the bit.
+template <int kBB, int EA, int EB, bool DIRECT, bool POLISH = false, bool N128 = false, bool SPEC = false, int SPW = 1, bool GAP = false>
 __global__ __launch_bounds__(kBB, (DIRECT && kBB == 256 && EA <= 8) ? (SPEC ? SPW : 2) : 1) void k_batch_admm(BatchParams P) {
   static_assert(!SPEC || (DIRECT && !POLISH && kBB == 256), "the spectral form: 256 threads, direct, no polish");
 #ifdef OSQP_HIP_KTRACE
@@ -609,6 +612,16 @@ __global__ __launch_bounds__(kBB, (DIRECT && kBB == 256 && EA <= 8) ? (SPEC ? SP
     viol = red.sum(viol);
     return viol == 0.0;
   };
+  // settings.check_dualgap: the support function of the scaled box at y, the dual objective and the gap of the point residuals() has just measured
+  // (term_rules.h term_dual_obj; a pass of its own, compiled into the GAP instantiations only: residuals() is what it was).  Uniform over the workgroup.  Nothing
+  // of it lives across an ADMM iteration: the record's gap is formed again behind the loop, from the same point by the same text -- the same bits.
+  constexpr bool gap_on = GAP;                                                         // (batch_solve picks the instantiation by P.check_dualgap)
+  auto duality_gap = [&](double obj_of_point, double *dual_obj) {
+    double sp = 0.0;
+    for (int i = tid; i < m; i += kBB) sp += support_finite(l[i], u[i], y[i]);
+    *dual_obj = term_dual_obj(tset, R, red.sum(sp));
+    return obj_of_point - *dual_obj;
+  };
 
   while (true) {
     iter++;
@@ -674,7 +687,9 @@ __global__ __launch_bounds__(kBB, (DIRECT && kBB == 256 && EA <= 8) ? (SPEC ? SP
     residuals();
     BT2_END(tk_res);
     term_info(tset, R, &obj, &prim_res, &dual_res);
-    const int st = batch_check(tset, R, prim_res, dual_res, iter, P.max_iter, at_check, pinf_stage2, pdx_stage2, adx_stage2, &obj);
+    double dual_obj = 0.0, gap = 0.0;
+    if (gap_on && at_check) gap = duality_gap(obj, &dual_obj);
+    const int st = batch_check_gap(tset, R, prim_res, dual_res, iter, P.max_iter, at_check, pinf_stage2, pdx_stage2, adx_stage2, &obj, gap_on, dual_obj, gap);
     if (st != kBatchGoOn) { status = st; break; }
     double rho_new;
     if (at_rho && batch_rho_rule(rho_bar, P.rho_tol, R, &rho_new)) { rho_bar = rho_new; set_rho(rho_bar); rho_updates++; }
@@ -690,6 +705,9 @@ __global__ __launch_bounds__(kBB, (DIRECT && kBB == 256 && EA <= 8) ? (SPEC ? SP
   // Then z = A x, the normal-cone projection (:1773-1780) and the accept test on the residuals (:1786-1793).
   // rho estimate of the ADMM point (_osqp.py:1275, :880-908), before any polish
   const double rho_est = term_rho_estimate(rho_bar, R);
+  // check_dualgap: the gap of the ADMM point the loop ended at (where obj carries a status convention instead, batch_record_gap writes NaN)
+  double rec_gap = 0.0;
+  if (gap_on) { double dobj; rec_gap = duality_gap(obj, &dobj); }
   int status_polish = 0;
   [[maybe_unused]] unsigned long long pol_ticks = 0;
   if constexpr (DIRECT && POLISH) {
@@ -736,8 +754,10 @@ __global__ __launch_bounds__(kBB, (DIRECT && kBB == 256 && EA <= 8) ? (SPEC ? SP
       residuals();
       double pobj, ppri, pdua;
       term_info(tset, R, &pobj, &ppri, &pdua);
-      if (polish_accept(ppri, pdua, pri0, dua0)) { obj = pobj; prim_res = ppri; dual_res = pdua; status_polish = 1; }
-      else {
+      if (polish_accept(ppri, pdua, pri0, dua0)) {
+        obj = pobj; prim_res = ppri; dual_res = pdua; status_polish = 1;
+        if (gap_on) { double dobj; rec_gap = duality_gap(obj, &dobj); }              // (the record's gap is the polished point's; uniform: so are its barriers)
+      } else {
         status_polish = -1;
         for (int j = tid; j < n; j += kBB) x[j] = p[j];
         for (int i = tid; i < m; i += kBB) { z[i] = zt[i]; y[i] = dy[i]; }
@@ -754,6 +774,7 @@ __global__ __launch_bounds__(kBB, (DIRECT && kBB == 256 && EA <= 8) ? (SPEC ? SP
     double *rc = P.rec + (size_t)b * kBatchRec;
     batch_record(rc, status, iter, obj, prim_res, dual_res, rho_bar, rho_updates, (double)pcg_total, rho_est);
     rc[8] = status_polish; rc[9] = 1e-8 * (double)pol_ticks;      // (100 MHz wall clock -> seconds)
+    if (gap_on) batch_record_gap(rc, status, rec_gap);
     if (P.iters_out) P.iters_out[b] = iter;
 #ifdef OSQP_HIP_KTRACE
     rc[5] = (double)tk_fact; rc[6] = (double)tk_solve; rc[7] = (double)(wall_clock64() - tk_all);
@@ -1369,16 +1390,17 @@ int batch_solve(Dev &d, const BatchParams &p, void *stream) {
   int cus = 256;
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, d.device);
   const BatchPlan pl = plan_batch(p, cus);
+  const bool gap = p.check_dualgap != 0;                  // (settings.check_dualgap: the GAP instantiation of whichever variant is launched)
   bool spectral = false;
   // spectral workgroup kernel on the first q.nbatch positions of the launch order, on stream s; false: the device refused the LDS reservation
   auto spec_launch = [&](const BatchParams &q, int w, hipStream_t s) {
     bool ok = false;
     with_const<2, 4, 6, 8>(pl.spec_e, [&](auto E) {
-      with_const<1, 2>(w, [&](auto W) {
-        const BatchKernel k = &k_batch_admm<256, decltype(E)::value, decltype(E)::value, true, false, false, true, decltype(W)::value>;
+      with_const<1, 2>(w, [&](auto W) { with_bool(gap, [&](auto GAP) {
+        const BatchKernel k = &k_batch_admm<256, decltype(E)::value, decltype(E)::value, true, false, false, true, decltype(W)::value, decltype(GAP)::value>;
         ok = reserve_lds(k, pl.lds_spec);
         if (ok) hipLaunchKernelGGL(k, dim3(q.nbatch), dim3(256), pl.lds_spec, s, q); else (void)hipGetLastError();
-      });
+      }); });
     });
     return ok;
   };
@@ -1414,19 +1436,23 @@ int batch_solve(Dev &d, const BatchParams &p, void *stream) {
     if (pl.direct && !reserve_lds(k, pl.lds)) throw DeviceError("osqp_hip: cannot reserve LDS for the direct batch kernel");
     hipLaunchKernelGGL(k, dim3(p.nbatch), dim3(pl.tb), pl.lds, st, pm);
   };
-  switch (pl.variant) {
-    case 2:
-      with_const<2, 4, 6, 8, 16>(pl.e, [&](auto E) { with_bool(pl.pol, [&](auto POL) { with_bool(pl.small, [&](auto SMALL) {
-        launch(&k_batch_admm<256, decltype(E)::value, decltype(E)::value, true, decltype(POL)::value, decltype(SMALL)::value>); }); }); });
-      break;
-    case 1:
-      with_const<8, 16, 24>(pl.e, [&](auto E) { with_bool(pl.pol, [&](auto POL) { launch(&k_batch_admm<64, decltype(E)::value, decltype(E)::value, true, decltype(POL)::value, false>); }); });
-      break;
-    case 3: with_const<8, 16, 24>(pl.e, [&](auto E) { launch(&k_batch_admm<64, decltype(E)::value, decltype(E)::value, false>); }); break;
-    case 4: with_const<2, 4, 8>(pl.e, [&](auto E) { launch(&k_batch_admm<256, decltype(E)::value, decltype(E)::value, false>); }); break;
-    case 5: launch(&k_batch_admm<256, 0, 0, false>); break;
-    default: return OSQP_FUNC_NOT_IMPLEMENTED;
-  }
+  with_bool(gap, [&](auto GAPT) {
+    constexpr bool GAP = decltype(GAPT)::value;
+    switch (pl.variant) {
+      case 2:
+        with_const<2, 4, 6, 8, 16>(pl.e, [&](auto E) { with_bool(pl.pol, [&](auto POL) { with_bool(pl.small, [&](auto SMALL) {
+          launch(&k_batch_admm<256, decltype(E)::value, decltype(E)::value, true, decltype(POL)::value, decltype(SMALL)::value, false, 1, GAP>); }); }); });
+        break;
+      case 1:
+        with_const<8, 16, 24>(pl.e, [&](auto E) { with_bool(pl.pol, [&](auto POL) { launch(&k_batch_admm<64, decltype(E)::value, decltype(E)::value, true, decltype(POL)::value, false, false, 1, GAP>); }); });
+        break;
+      case 3: with_const<8, 16, 24>(pl.e, [&](auto E) { launch(&k_batch_admm<64, decltype(E)::value, decltype(E)::value, false, false, false, false, 1, GAP>); }); break;
+      case 4: with_const<2, 4, 8>(pl.e, [&](auto E) { launch(&k_batch_admm<256, decltype(E)::value, decltype(E)::value, false, false, false, false, 1, GAP>); }); break;
+      case 5: launch(&k_batch_admm<256, 0, 0, false, false, false, false, 1, GAP>); break;
+      default: break;
+    }
+  });
+  if (pl.variant < 1 || pl.variant > 5) return OSQP_FUNC_NOT_IMPLEMENTED;
   hipError_t e = stream ? hipGetLastError() : hipStreamSynchronize(st);
   if (e != hipSuccess) throw DeviceError(std::string("osqp_hip: batch kernel failed: ") + hipGetErrorString(e));
   return OSQP_NO_ERROR;

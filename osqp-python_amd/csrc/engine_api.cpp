@@ -337,7 +337,8 @@ void Engine::prepare_batch_wave() {
 // (behind attach_batch_direct: the form needs the spectral decomposition)
 void Engine::attach_batch_wave(BatchParams &p, int nbatch) {
   // OSQPHipPolicy::batch_wave; automatic = where it measured faster (tools/batch_size_sweep.py): large batches, smaller ones only with a launch order
-  if (!p.sp_V || pol_.batch_wave < 0 || p.mat_on || p.polish) return;
+  // (k_batch_wave has no duality-gap test: with check_dualgap the whole batch stays on k_batch_admm, which has, as with polish)
+  if (!p.sp_V || pol_.batch_wave < 0 || p.mat_on || p.polish || p.check_dualgap) return;
   if (pol_.batch_wave == 0 && nbatch < (p.order ? kBatchWaveMinOrdered : kBatchWaveMin)) return;
   prepare_batch_wave();
   if (!bwv_.ok) return;
@@ -600,6 +601,7 @@ void Engine::fill_batch_settings(BatchSettings &p, int warm) {
   p.max_iter = settings.max_iter; p.check = settings.check_termination; p.rho_interval = settings.adaptive_rho ? auto_rho_interval() : 0;
   p.cg_max = settings.cg_max_iter; p.unscaled = settings.scaling && !settings.scaled_termination; p.scaling = settings.scaling;
   p.precond = settings.cg_precond == OSQP_DIAGONAL_PRECONDITIONER; p.rho_is_vec = settings.rho_is_vec; p.warm = warm;
+  p.check_dualgap = settings.check_dualgap != 0;
 }
 void Engine::fill_batch_params(BatchParams &p, int nbatch, int warm) {
   fill_batch_settings(p, warm);
@@ -1633,13 +1635,13 @@ int Engine::test_lockstep(OSQPHipLockstepTest *t) {
     if (op < 0 || op >= OSQP_HIP_LS_OP_COUNT) return OSQP_DATA_VALIDATION_ERROR;
     const bool mat_op = (op >= OSQP_HIP_LS_BEGIN && op <= OSQP_HIP_LS_FINISH) || op == OSQP_HIP_LS_VALS || op == OSQP_HIP_LS_WT;
     if (mat_op && !mat) return OSQP_DATA_VALIDATION_ERROR;
-    if (!direct && op >= OSQP_HIP_LS_D0) return OSQP_DATA_VALIDATION_ERROR;
+    if (!direct && op >= OSQP_HIP_LS_D0 && op != OSQP_HIP_LS_SUPP) return OSQP_DATA_VALIDATION_ERROR;
     // the direct route has no PCG (and no Kp): of the PCG route's kernels it launches the transposes, the state, rhs, upd, the residuals, initz and setrho
     const bool pcg_only = op == OSQP_HIP_LS_MINV || op == OSQP_HIP_LS_T || op == OSQP_HIP_LS_KP || op == OSQP_HIP_LS_CGUPD || op == OSQP_HIP_LS_CGP ||
                           op == OSQP_HIP_LS_CGINIT || op == OSQP_HIP_LS_CGALPHA || op == OSQP_HIP_LS_CGBETA;
     if (direct && pcg_only) return OSQP_DATA_VALIDATION_ERROR;
     if ((op == OSQP_HIP_LS_ASM_A && nzA == 0) || (op == OSQP_HIP_LS_ASM_P && nzP == 0)) return OSQP_DATA_VALIDATION_ERROR;
-    const bool m_only = op == OSQP_HIP_LS_LOAD_M || op == OSQP_HIP_LS_STORE_M || op == OSQP_HIP_LS_INITZ || op == OSQP_HIP_LS_T || op == OSQP_HIP_LS_RESM || op == OSQP_HIP_LS_SETRHO;
+    const bool m_only = op == OSQP_HIP_LS_LOAD_M || op == OSQP_HIP_LS_STORE_M || op == OSQP_HIP_LS_INITZ || op == OSQP_HIP_LS_T || op == OSQP_HIP_LS_RESM || op == OSQP_HIP_LS_SETRHO || op == OSQP_HIP_LS_SUPP;
     if (m_only && m == 0) return OSQP_DATA_VALIDATION_ERROR;
   }
   const long long cnt = t->count;

@@ -361,6 +361,22 @@ __global__ __launch_bounds__(256) void k_ls_cgp(LsK k) {
   for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < tot; e += (size_t)gridDim.x * 256) k.w.p[e] = k.w.Minv[e] * k.w.r[e] + be * k.w.p[e];
 }
 
+// settings.check_dualgap: per problem the support function of the scaled box at y, sum_i support_finite(l_i, u_i, y_i) (step_rules.h; what backend_hip.hip
+// reduces for R_SUPP), for the dual objective of the next decision (term_rules.h term_dual_obj).  Rows by wave like k_ls_cgupd: wave w of workgroup g
+// takes rows (4 g + w), + 4 G, .. -- fixed by the grid --, a lane adds its own problem's terms in row order, ls_put combines the four waves.  The partials
+// go to PS_PKP: written by k_ls_kp and read by k_ls_cgalpha inside a PCG solve only, and this kernel runs between an iteration's k_ls_upd and the
+// decision (the direct route and polish's accept test: no PCG is running either).  l, u, y carry all m rows on the direct route too.  Launched only with
+// the setting, in front of a decision that tests termination; it stores to PS_PKP alone.
+constexpr int PS_SUPP = PS_PKP;
+__global__ __launch_bounds__(256) void k_ls_supp(LsK k) {
+  __shared__ double lds[256];
+  const int lane = ls_lane();
+  double sp = 0.0;
+  for (int i = (int)blockIdx.x * 4 + ls_wave(); i < k.P.m; i += (int)gridDim.x * 4) sp += support_finite(k.w.l[IX(i)], k.w.u[IX(i)], k.w.y[IX(i)]);
+  const double vs[1] = {sp};
+  ls_put<0, 1>(k.w.part, PS_SUPP, vs, vs, lds);
+}
+
 // ---------------------------------------------------------------------------------------------------------------- folds (one workgroup each)
 __device__ __forceinline__ void ls_any(int *word, int flag) {
   const unsigned long long bal = __ballot(flag);
@@ -421,6 +437,8 @@ template <bool MAT> __device__ __forceinline__ void ls_decide(const LsK &k, int 
   const double adx_hi = mx(M0 + 8), adx_lo = mx(M0 + 9);                                                                      // second stages: folded with the rest
   const ResRowsB rb = {mx(N0), mx(N0 + 1), mx(N0 + 2), mx(N0 + 3), mx(N0 + 4), mx(N0 + 5), mx(N0 + 6), mx(N0 + 7), mx(N0 + 8), mx(N0 + 9), sm(N0 + 14), sm(N0 + 15), sm(N0 + 16)};
   const double atdy_u = mx(N0 + 10), atdy_s = mx(N0 + 11), pdx_u = mx(N0 + 12), pdx_s = mx(N0 + 13);
+  const bool gap_on = P.check_dualgap && at_check && mode != 1;                                                               // (uniform: so is the fold's barrier)
+  const double supp = (gap_on && P.m > 0) ? sm(PS_SUPP) : 0.0;                                                                // (k_ls_supp, launched in front of this decision)
   if (threadIdx.x >= 64) return;
   int *iw = k.w.iw; double *sc = k.w.sc;
   const int done = iw[IW_DONE * W + lane];
@@ -437,9 +455,10 @@ template <bool MAT> __device__ __forceinline__ void ls_decide(const LsK &k, int 
       const double rho_bar = sc[SC_RHOBAR * W + lane];
       double obj, prim_res, dual_res, rho_new;
       term_info(tset, R, &obj, &prim_res, &dual_res);
-      int status = batch_check(tset, R, prim_res, dual_res, iter, P.max_iter, at_check != 0,
-                               [&](double &au, double &as) { au = atdy_u; as = atdy_s; }, [&](double &pu, double &ps) { pu = pdx_u; ps = pdx_s; },
-                               [&](double thr) { return !(adx_hi > thr) && !(adx_lo > thr); }, &obj);
+      const double dual_obj = gap_on ? term_dual_obj(tset, R, supp) : 0.0, gap = gap_on ? obj - dual_obj : 0.0;               // (check_dualgap: the ADMM point's)
+      int status = batch_check_gap(tset, R, prim_res, dual_res, iter, P.max_iter, at_check != 0,
+                                   [&](double &au, double &as) { au = atdy_u; as = atdy_s; }, [&](double &pu, double &ps) { pu = pdx_u; ps = pdx_s; },
+                                   [&](double thr) { return !(adx_hi > thr) && !(adx_lo > thr); }, &obj, gap_on, dual_obj, gap);
       if (status == kBatchGoOn && mode == 2) status = OSQP_TIME_LIMIT_REACHED;
       const bool single = P.rho_tol_single > 0.0;                                            // (the direct route: the rule of the handle's own solve)
       bool rho_big = single ? false : batch_rho_rule(rho_bar, P.rho_tol, R, &rho_new);       // (rho_new: also the record's rho estimate)
@@ -450,6 +469,7 @@ template <bool MAT> __device__ __forceinline__ void ls_decide(const LsK &k, int 
       }
       if (status != kBatchGoOn) {
         batch_record(k.w.rec + (size_t)lane * kBatchRec, status, iter, obj, prim_res, dual_res, rho_bar, iw[IW_RHOUPD * W + lane], iw[IW_PCG * W + lane], rho_new);
+        if (gap_on) batch_record_gap(k.w.rec + (size_t)lane * kBatchRec, status, gap);
         iw[IW_DONE * W + lane] = 1; iw[IW_STATUS * W + lane] = status;
       } else {
         if (at_rho && rho_big) { sc[SC_RHOBAR * W + lane] = rho_new; iw[IW_RHOUPD * W + lane] += 1; rhoch = 1; }
@@ -918,6 +938,8 @@ template <bool MAT> __device__ __forceinline__ void ls_pol_accept(const LsPK &k)
   R.pri_u = has_m ? ls_fold<true>(k.w.part, G, PS_M0, lds) : 0.0; R.pri_s = has_m ? ls_fold<true>(k.w.part, G, PS_M0 + 3, lds) : 0.0;
   R.dua_u = ls_fold<true>(k.w.part, G, PS_N0, lds); R.dua_s = ls_fold<true>(k.w.part, G, PS_N0 + 3, lds);
   R.xpx = ls_fold<false>(k.w.part, G, PS_N0 + 14, lds); R.qx = ls_fold<false>(k.w.part, G, PS_N0 + 15, lds);
+  const bool gap_on = P.check_dualgap != 0;                                       // (uniform; k_ls_supp has run on the polished y and the problem's own bounds)
+  const double supp = (gap_on && has_m) ? ls_fold<false>(k.w.part, G, PS_SUPP, lds) : 0.0;
   if (threadIdx.x >= 64) return;
   int *iw = k.w.iw;
   const int pol = iw[IW_POL * W + lane];
@@ -928,8 +950,10 @@ template <bool MAT> __device__ __forceinline__ void ls_pol_accept(const LsPK &k)
     term_info(tset, R, &obj, &prim_res, &dual_res);
     double *rc = k.w.rec + (size_t)lane * kBatchRec;
     ok = polish_accept(prim_res, dual_res, rc[3], rc[4]);
-    if (ok) { rc[2] = obj; rc[3] = prim_res; rc[4] = dual_res; rc[8] = 1.0; }
-    else { rc[8] = -1.0; iw[IW_POL * W + lane] = 2; }
+    if (ok) {
+      rc[2] = obj; rc[3] = prim_res; rc[4] = dual_res; rc[8] = 1.0;
+      if (gap_on) { const double dual_obj = term_dual_obj(tset, R, supp); batch_record_gap(rc, OSQP_SOLVED, obj - dual_obj); }      // (a rejected problem keeps its ADMM gap)
+    } else { rc[8] = -1.0; iw[IW_POL * W + lane] = 2; }
   }
   const unsigned long long acc = __ballot(pol && ok), rej = __ballot(pol && !ok);
   if (threadIdx.x == 0) { k.w.word[WD_POLACC] = __popcll(acc); k.w.word[WD_POLREJ] = __popcll(rej); }
@@ -1500,6 +1524,7 @@ void ls_go(LsRun &R, const LsPcgKernels &K, int op, const LsK &k) {
     case OSQP_HIP_LS_CGINIT: R.go(k_ls_cginit, 1, k); break;
     case OSQP_HIP_LS_CGALPHA: R.go(k_ls_cgalpha, 1, k); break;
     case OSQP_HIP_LS_CGBETA: R.go(k_ls_cgbeta, 1, k); break;
+    case OSQP_HIP_LS_SUPP: R.go(k_ls_supp, G, k); break;
     default: throw std::logic_error("ls_go: not a forward kernel of the PCG route");
   }
 }
@@ -1677,6 +1702,7 @@ int lockstep_chunk(Dev &d, const LockstepParams &p, void *stream, double *stat) 
   auto late_now = [&]() { return p.time_limit > 0 && ls_now() - t_begin > p.time_limit; };
   auto residuals = [&]() { if (m > 0) ls_go(R, K, OSQP_HIP_LS_RESM, k); ls_go(R, K, OSQP_HIP_LS_RESN, k); };
   auto new_rho = [&]() { if (m > 0) ls_go(R, K, OSQP_HIP_LS_SETRHO, k); ls_go(R, K, OSQP_HIP_LS_MINV, k); };
+  const bool gap_check = p.check_dualgap && m > 0;       // settings.check_dualgap: k_ls_supp in front of every decision that tests termination (m = 0: no support term)
 
   ls_go(R, K, OSQP_HIP_LS_LOAD_N, k);
   if (m > 0) ls_go(R, K, OSQP_HIP_LS_LOAD_M, k);
@@ -1695,6 +1721,7 @@ int lockstep_chunk(Dev &d, const LockstepParams &p, void *stream, double *stat) 
     const bool late = late_now();
     if (!at_check && !at_rho && !late) continue;
     residuals();
+    if (gap_check && (at_check || late)) ls_go(R, K, OSQP_HIP_LS_SUPP, k);
     R.go(K.decide, 1, k, iter, late ? 1 : at_check, at_rho, late ? 2 : 0);
     if (at_rho && !late) new_rho();
     if (at_check || late) R.fetch();
@@ -1722,6 +1749,7 @@ int lockstep_chunk(Dev &d, const LockstepParams &p, void *stream, double *stat) 
       pol_pcg = R.words[WD_PCGSUM];
       if (m > 0) { R.go(mat ? k_lsm_pol_cone : k_ls_pol_cone, G, kq); ls_go(R, K, OSQP_HIP_LS_RESM, kp); }
       ls_go(R, K, OSQP_HIP_LS_RESN, kp);
+      if (gap_check) ls_go(R, K, OSQP_HIP_LS_SUPP, kp);  // (the polished y against the bounds k_ls_pol_cone has put back: an accepted problem's column 11)
       R.go(mat ? k_lsm_pol_accept : k_ls_pol_accept, 1, kq);
       R.fetch();
       R.go(k_ls_pol_end, G, kq, ls_now() - t_pol);
@@ -1761,7 +1789,7 @@ int test_lockstep(Dev &d, const LsProbe &t) {
     const LsMK km{p, w, mt};
     LsRun R(s, w.word, p.count);
     for (int i = 0; i < t.nops; i++) {
-      if (t.ops[i] >= OSQP_HIP_LS_BEGIN) ls_mat_go(R, t.ops[i], km);
+      if (t.ops[i] >= OSQP_HIP_LS_BEGIN && t.ops[i] <= OSQP_HIP_LS_FINISH) ls_mat_go(R, t.ops[i], km);
       else ls_go(R, K, t.ops[i], k);
     }
   } else {                                               // the direct route: lockstep_direct_chunk's carve and LwRun
@@ -1904,6 +1932,7 @@ int lockstep_direct_chunk(Dev &d, const LockstepDirectParams &p0, void *stream, 
     if (!at_check && !at_rho && !late) continue;
     D.long_rows(R, 0);
     residuals();
+    if (p.check_dualgap && (at_check || late)) D.go(R, OSQP_HIP_LS_SUPP);        // (settings.check_dualgap: l, u, y carry all m rows, the dense ones included)
     R.go(K.decide, 1, kb, iter, late ? 1 : at_check, at_rho, late ? 2 : 0);
     if (at_rho && !late) D.factor(R);
     if (at_check || late) R.fetch();
@@ -1938,6 +1967,7 @@ int lockstep_direct_chunk(Dev &d, const LockstepDirectParams &p0, void *stream, 
       R.go(mat ? k_lsm_pol_cone : k_ls_pol_cone, G, kq);
       Dp.go(R, OSQP_HIP_LS_RESM);
       Dp.go(R, OSQP_HIP_LS_RESN);
+      if (p.check_dualgap) Dp.go(R, OSQP_HIP_LS_SUPP);
       R.go(mat ? k_lsm_pol_accept : k_ls_pol_accept, 1, kq);
       R.fetch();
       R.go(k_ls_pol_end, G, kq, ls_now() - t_pol);

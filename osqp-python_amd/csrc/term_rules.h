@@ -57,6 +57,14 @@ OSQP_HDI double term_rel_kkt(int m, double prim_res, double pn, double dual_res,
 }
 // the x10 of the approximate pass (_osqp.py:1012-1016)
 OSQP_HDI double term_eps(double eps, bool approx) { return (approx ? 10.0 : 1.0) * eps; }
+// The duality gap of a check, for the batch family (settings.check_dualgap; the single-QP driver keeps policy.h ctl_info / ctl_stage1's own text, for the
+// reason given there).  supp: sum_i support_finite(l_i, u_i, y_i) on the scaled bounds and dual (step_rules.h).  The gap is the CALLER's subtraction
+// obj - dual_obj on the two stored values; the test is ctl_stage1's: |gap| < eps_abs + eps_rel max(|obj|, |dual_obj|), x10 on the approximate pass.  A NaN
+// in supp makes dual_obj and the gap NaN and the comparison false: never "solved".
+OSQP_HDI double term_dual_obj(const TermSet &s, const TermRes &R, double supp) { return (-0.5 * R.xpx - supp) * (s.scaling ? s.cinv : 1.0); }
+OSQP_HDI bool term_gap_ok(const TermSet &s, double obj, double dual_obj, double gap, bool approx) {
+  return fabs(gap) < term_eps(s.eps_abs, approx) + term_eps(s.eps_rel, approx) * fmax(fabs(obj), fabs(dual_obj));
+}
 
 // check_termination (_osqp.py:998-1077) as far as it goes without another SpMV: the NON_CVX guard (:1025-1028), the residual tests with their
 // normalisations (:728-751, :766-794) and the FIRST stage of is_primal_infeasible (:796-813) / is_dual_infeasible (:822-846)
@@ -110,9 +118,12 @@ OSQP_HDI bool term_is_dinf(int status) { return status == OSQP_DUAL_INFEASIBLE |
 // k_batch_admm / k_batch_wave run their extra SpMVs and reductions inside them (the decision is uniform over the workgroup / wave: so are the barriers),
 // k_ls_decide returns what it has folded already.  *obj follows the status: NAN for OSQP_NON_CVX, +-OSQP_INFTY for the infeasible ones (:1045-1070).
 constexpr int kBatchGoOn = 0;
+// batch_check_gap: the same check with settings.check_dualgap: gap_on, and then dual_obj (term_dual_obj) and gap = *obj - dual_obj of the point -- "solved"
+// additionally needs term_gap_ok on that pass (policy.h ctl_stage1's rule: the infeasibility tests are untouched, they ask for a residual test that FAILED).
+// batch_check is batch_check_gap with gap_on false.
 template <class PinfCb, class PdxCb, class AdxCb>
-OSQP_HDI int batch_check(const TermSet &s, const TermRes &R, double prim_res, double dual_res, int iter, int max_iter, bool at_check, PinfCb &&pinf_cb,
-                         PdxCb &&pdx_cb, AdxCb &&adx_cb, double *obj) {
+OSQP_HDI int batch_check_gap(const TermSet &s, const TermRes &R, double prim_res, double dual_res, int iter, int max_iter, bool at_check, PinfCb &&pinf_cb,
+                             PdxCb &&pdx_cb, AdxCb &&adx_cb, double *obj, bool gap_on, double dual_obj, double gap) {
   for (int approx = 0; approx < 2 && at_check; approx++) {
     if (approx && iter < max_iter) break;
     if (term_non_cvx(prim_res, dual_res)) { *obj = NAN; return OSQP_NON_CVX; }
@@ -129,11 +140,16 @@ OSQP_HDI int batch_check(const TermSet &s, const TermRes &R, double prim_res, do
       pdx_cb(pu, ps);
       if (term_dinf_pdx_ok(s, approx, d.nd, pu, ps)) dinf = adx_cb(term_adx_thr(s, approx, d.nd));
     }
-    if (p.ok && d.ok) return approx ? OSQP_SOLVED_INACCURATE : OSQP_SOLVED;
+    if (p.ok && d.ok && (!gap_on || term_gap_ok(s, *obj, dual_obj, gap, approx))) return approx ? OSQP_SOLVED_INACCURATE : OSQP_SOLVED;
     if (pinf) { *obj = OSQP_INFTY; return approx ? OSQP_PRIMAL_INFEASIBLE_INACCURATE : OSQP_PRIMAL_INFEASIBLE; }
     if (dinf) { *obj = -OSQP_INFTY; return approx ? OSQP_DUAL_INFEASIBLE_INACCURATE : OSQP_DUAL_INFEASIBLE; }
   }
   return iter >= max_iter ? (int)OSQP_MAX_ITER_REACHED : kBatchGoOn;
+}
+template <class PinfCb, class PdxCb, class AdxCb>
+OSQP_HDI int batch_check(const TermSet &s, const TermRes &R, double prim_res, double dual_res, int iter, int max_iter, bool at_check, PinfCb &&pinf_cb,
+                         PdxCb &&pdx_cb, AdxCb &&adx_cb, double *obj) {
+  return batch_check_gap(s, R, prim_res, dual_res, iter, max_iter, at_check, pinf_cb, pdx_cb, adx_cb, obj, false, 0.0, 0.0);
 }
 
 // adapt_rho (_osqp.py:910-930) with the reference's plain factor test (the single-QP path's square-root / persistence rule is policy.h ctl_rho_rule)
@@ -189,13 +205,16 @@ OSQP_HDI bool recurrence_ends(double err, double gain, int steps, int min_steps,
 }
 
 // The record of a batch problem (backend.h kBatchRec = 12 doubles; include/osqp_hip.h OSQP_HIP_BATCH_REC): status, iter, obj, prim_res, dual_res, rho,
-// rho_updates, pcg_iters, status_polish, polish seconds, rho_estimate (_osqp.py:1275, at the ADMM point), reserved.  The polish fields and the reserved
-// one are zeroed: the polishing variants and the OSQP_HIP_KTRACE build overwrite theirs afterwards.
+// rho_updates, pcg_iters, status_polish, polish seconds, rho_estimate (_osqp.py:1275, at the ADMM point), duality_gap (check_dualgap only).  The polish fields
+// and the gap are zeroed: the polishing variants, batch_record_gap and the OSQP_HIP_KTRACE build overwrite theirs afterwards.
 OSQP_HDI void batch_record(double *rc, int status, int iter, double obj, double prim_res, double dual_res, double rho_bar, int rho_updates, double pcg,
                            double rho_est) {
   rc[0] = status; rc[1] = iter; rc[2] = obj; rc[3] = prim_res; rc[4] = dual_res; rc[5] = rho_bar; rc[6] = rho_updates; rc[7] = pcg;
   rc[8] = 0.0; rc[9] = 0.0; rc[10] = rho_est; rc[11] = 0.0;
 }
+// Column 11 with settings.check_dualgap, written AFTER batch_record (and again after an accepted polish, with the polished point's gap): the duality gap of
+// the point the record describes; NAN where the record describes no point (x or y is a certificate, or the iterates are not finite).
+OSQP_HDI void batch_record_gap(double *rc, int status, double gap) { rc[11] = (term_is_pinf(status) || term_is_dinf(status) || status == OSQP_NON_CVX) ? NAN : gap; }
 
 // What a batch problem's caller reads in x / y: x = D x, y = cinv E y (_osqp.py:1110-1112); for an infeasible problem the certificate (dx for dual, dy
 // for primal infeasibility: :815-820, :870-878) in one and NAN in the other.  Dj, Ei: the equilibration's entries; xj, dxj, yi, dyi: scaled iterates.

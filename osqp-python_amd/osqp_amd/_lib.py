@@ -92,6 +92,7 @@ class WoodburyTestStruct(C.Structure):    # OSQPHipWoodburyTest, include/osqp_hi
 LOCKSTEP_OPS = ('load_n', 'load_m', 'init', 'store_n', 'store_m', 'minv', 'initz', 'rhs', 't', 'kp', 'upd', 'resm', 'resn', 'setrho', 'cgupd', 'cgp',
                 'cginit', 'cgalpha', 'cgbeta', 'begin', 'asm_a', 'asm_p', 'norms', 'scale', 'cost', 'cost_apply', 'finish',
                 'd0', 's', 'inv', 'prod_x', 'prod_xs', 'prod_p', 'prod2', 'setl0', 'setl1', 'h', 'x', 'vals', 'wt')      # OSQPHipLockstepOp, in order
+LOCKSTEP_MORE_OPS = {'supp': len(LOCKSTEP_OPS)}        # the ops behind them: OSQP_HIP_LS_SUPP (k_ls_supp, settings.check_dualgap)
 LOCKSTEP_TEST_LENS = ('q_len', 'l_len', 'u_len', 'x_len', 'y_len', 'rec_len', 'px_len', 'ax_len', 'ws_len', 'mat_len',
                       'arp_len', 'anz_len', 'brp_len', 'bnz_len', 'n_len', 'm_len', 'pmap_len', 'amap_len', 'bdiag_len',
                       'avrp_len', 'av_len', 'wt_len', 'rows_len', 'islong_len')

@@ -410,7 +410,7 @@ class OSQPSolver:
 
     def hip_test_lockstep(self, ops, ws, mat_ws=None, count=64, warm=0, q=None, l=None, u=None, x=None, y=None, rec=None, Px=None, Ax=None,
                           route=0, handle=False, maps=False, view=False, lens=None):
-        """Single launches of the lockstep kernels on the caller's blocks (osqp_hip_test_lockstep): ops = names of _lib.LOCKSTEP_OPS (or raw ints), one kernel
+        """Single launches of the lockstep kernels on the caller's blocks (osqp_hip_test_lockstep): ops = names of _lib.LOCKSTEP_OPS / LOCKSTEP_MORE_OPS (or raw ints), one kernel
         launch each; ws / mat_ws: the whole work / matrix block (mat_ws given: the per-problem-matrix kernels).  q, l, u, Px, Ax: (count, width) or None;
         x, y, rec: (count, width), default zeros.  route = 1: the direct route (ws / mat_ws are then that route's blocks).  handle / maps / view: also return the
         engine's CSR and scalings / assembly maps / the direct route's view of A and dense rows.  Every array is copied: the caller's
@@ -418,7 +418,8 @@ class OSQPSolver:
         _, sz = self.hip_test_lockstep_sizes()
         n, m = sz['n'], sz['m']
         mat = mat_ws is not None
-        codes = np.array([_lib.LOCKSTEP_OPS.index(o) if isinstance(o, str) else int(o) for o in ops], dtype=np.int32)
+        code = lambda o: _lib.LOCKSTEP_MORE_OPS[o] if o in _lib.LOCKSTEP_MORE_OPS else _lib.LOCKSTEP_OPS.index(o)
+        codes = np.array([code(o) if isinstance(o, str) else int(o) for o in ops], dtype=np.int32)
         f64 = lambda a: None if a is None else np.array(a, dtype=np.float64).ravel()
         count = int(count)
         cz = max(count, 0)
@@ -463,13 +464,14 @@ class OSQPSolver:
     def hip_set_rho_eq_factor(self, factor):
         return self._lib.osqp_hip_set_rho_eq_factor(self._p, float(factor))
 
-    BATCH_FIELDS = ('status_val', 'iter', 'obj_val', 'prim_res', 'dual_res', 'rho', 'rho_updates', 'pcg_iters', 'status_polish', 'polish_time', 'rho_estimate', 'reserved')
+    BATCH_FIELDS = ('status_val', 'iter', 'obj_val', 'prim_res', 'dual_res', 'rho', 'rho_updates', 'pcg_iters', 'status_polish', 'polish_time', 'rho_estimate', 'duality_gap')
     BATCH_REC = len(BATCH_FIELDS)        # OSQP_HIP_BATCH_REC
 
     def hip_batch_solve(self, q=None, l=None, u=None, x0=None, y0=None, nbatch=None, Px=None, Ax=None):
         """Solve a batch of QPs sharing this solver's P, A and settings (osqp_hip_batch_solve).  q: (B, n), l/u: (B, m).
         Px (B, nnz(triu P)) / Ax (B, nnz(A)): per-problem matrix values in the CSC order given at setup (osqp_hip_batch_solve_mat: the reference's
-        per-element P_val / A_val, nn/torch.py:128-157) -- still one launch.  Returns x (B, n), y (B, m), rec (B, BATCH_REC) with columns BATCH_FIELDS."""
+        per-element P_val / A_val, nn/torch.py:128-157) -- still one launch.  Returns x (B, n), y (B, m), rec (B, BATCH_REC) with columns BATCH_FIELDS
+        (duality_gap: 0 unless settings.check_dualgap, which every batch route honours per problem; dual_obj_val = obj_val - duality_gap)."""
         return self._lockstep_host(self._lib.osqp_hip_batch_solve, q, l, u, x0, y0, nbatch, Px, Ax, mat_entry=self._lib.osqp_hip_batch_solve_mat)
 
     def hip_batch_solve_device(self, nbatch, q_ptr, l_ptr, u_ptr, x_ptr, y_ptr, rec_ptr, warm=False, stream=None, Px_ptr=None, Ax_ptr=None):

@@ -123,7 +123,7 @@ def _check_solved(status):
 
 
 class OSQP(Module):
-    def __init__(self, P_idx, P_shape, A_idx, A_shape, eps_rel=1e-5, eps_abs=1e-5, verbose=False, max_iter=10000, algebra='hip', solver_type='indirect', large_batch='loop', large_backward='loop', polishing=False):
+    def __init__(self, P_idx, P_shape, A_idx, A_shape, eps_rel=1e-5, eps_abs=1e-5, verbose=False, max_iter=10000, algebra='hip', solver_type='indirect', large_batch='loop', large_backward='loop', polishing=False, check_dualgap=False):
         super().__init__()
         if large_batch not in ('loop', 'lockstep', 'lockstep_direct'):
             raise ValueError("large_batch: 'loop', 'lockstep' or 'lockstep_direct'")
@@ -135,6 +135,7 @@ class OSQP(Module):
         self.eps_rel, self.eps_abs, self.verbose, self.max_iter = eps_rel, eps_abs, verbose, max_iter
         self.algebra, self.solver_type = algebra, solver_type
         self.polishing = bool(polishing)   # settings.polishing of the handle this layer sets up (default off: every forward as before)
+        self.check_dualgap = bool(check_dualgap)   # settings.check_dualgap of that handle: every batch route then tests the duality gap per element (last_rec column 11)
         self.n, self.m = P_shape[0], A_shape[0]
         self._solver = None          # the persistent handle (reference: the `solvers` list kept across forwards)
         self._Pv = self._Av = None   # matrix values currently on the handle
@@ -147,7 +148,7 @@ class OSQP(Module):
         self._grad_maps = None
         self.mat_batch_launches = 0      # calls of the one-workgroup kernel with per-element matrices made by this layer's forwards
         self.mat_lockstep_launches = 0   # calls of the lockstep route with per-element matrices made by this layer's forwards (large_batch='lockstep')
-        self.last_rec = None         # per-element record of the last forward that ran on host arrays (ext_hip BATCH_FIELDS where a batch route made it: status_polish is column 8)
+        self.last_rec = None         # per-element record of the last forward that ran on host arrays (ext_hip BATCH_FIELDS where a batch route made it: status_polish is column 8, duality_gap column 11)
         self.mat_lockstep_direct_launches = 0   # calls of the direct lockstep route with per-element matrices made by this layer's forwards (large_batch='lockstep_direct')
         self.mat_lockstep_adjoint_launches = 0   # calls of the lockstep adjoint with per-element matrices made by this layer's backwards (large_backward='lockstep')
         self.mat_lockstep_direct_adjoint_launches = 0   # calls of the direct lockstep adjoint with per-element matrices made by this layer's backwards (large_backward='lockstep_direct')
@@ -167,7 +168,8 @@ class OSQP(Module):
                 self._triu_pick = tag.data.astype(int) - 1
             s = osqp_amd.OSQP(algebra=self.algebra)
             s.setup(P, q0, A, l0, u0, solver_type=self.solver_type, verbose=self.verbose, eps_abs=self.eps_abs, eps_rel=self.eps_rel,
-                    max_iter=self.max_iter, warm_starting=False, device=device, **({'polishing': True} if self.polishing else {}))
+                    max_iter=self.max_iter, warm_starting=False, device=device, **({'polishing': True} if self.polishing else {}),
+                    **({'check_dualgap': True} if self.check_dualgap else {}))
             self._solver, self._device = s, device
             self._Pv, self._Av = np.array(P_val, dtype=float), np.array(A_val, dtype=float)
             self.setup_count += 1
