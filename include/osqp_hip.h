@@ -857,6 +857,35 @@ typedef struct {
   long long dws_need, dmat_need;                  /* out: the direct route */
 } OSQPHipLockstepTest;
 OSQPInt osqp_hip_test_lockstep(OSQPSolver *solver, OSQPHipLockstepTest *t);
+/* Test hook (used by tests/ only): a few ADMM iterations of the PCG path (csrc/pcg_hip.hip; DESIGN.md sections 2, 4.2, 4.3) from iterates the caller
+   gives, through the handle's OWN launch path, with everything the kernels left behind read back -- POKE, RUN, PEEK on a set-up handle.
+     POKE   x [n], z [m], y [m], xt [n] (x~): SCALED iterates (osqp_hip_get_scaling) in the caller's numbering.  They are uploaded; then the entry does
+            what the driver does after a warm start or a rho change: z~ = A x~, t0 = rho z~, v = rho z - y, and the PCG start without history
+            (x_g = x~_prev = x~).
+     RUN    `iters` ADMM iterations (1 .. 8), every PCG capped at `cap` iterations (0 .. 16) and stopped by ||r_i||_inf <= max(tol_rel ||rhs||_inf, tol_abs),
+            tested before iteration i: with tol_rel = tol_abs = 0 every PCG with a nonzero residual runs exactly `cap` iterations.  A handle without slots
+            enqueues the chunk as a solve does (captured once per (iters, cap) when the handle replays graphs); a handle with slots begins a chunk of `iters`
+            iterations and enqueues the slot pairs `iters` iterations of `cap` PCG iterations need plus one spare pair, then synchronises ONCE.  No boundary
+            group, no termination test, no rho adaptation, no top-up: a chunk the slots did not finish is OSQP_ALGEBRA_LOAD_ERROR.
+     PEEK   x, z, y, xt, zt (z~), dx, dy, v, t0, xg (the next PCG's start), rho [m] and Minv [n] as they stand on the device -- each read where the
+            form keeps it --, the chunk's PCG statistics, the last PCG's tolerance and start residual, and hist [3 cap] = gamma[0 .. cap), alpha[0 .. cap),
+            beta[0 .. cap) of the LAST PCG as far as the form records them (beta: the fused pair only; entries the PCG did not reach are stale).
+            form: 0 three-kernel, 1 fused pair enqueued by the host, 2 slot two-kernel, 3 F1 (f1_D replicas, f1_mix), 4 K form; launches: kernel launches enqueued.
+   Every length is exact (n_len = n, m_len = m, hist_len = 3 cap; a NULL pointer only where the length is 0) and everything is checked before anything is
+   uploaded or launched: anything else is OSQP_DATA_VALIDATION_ERROR.  A handle whose Woodbury correction is on answers OSQP_FUNC_NOT_IMPLEMENTED
+   (osqp_hip_test_woodbury is its tier).  The handle's iterates STAY as the run left them, like after a warm start: a later osqp_solve with
+   warm_starting = 0 cold-starts and is the solve of a fresh handle bit for bit; with warm_starting = 1 it continues from them. */
+typedef struct {
+  OSQPInt iters, cap;
+  OSQPFloat tol_rel, tol_abs;
+  long long n_len, m_len, hist_len;
+  const OSQPFloat *x_in, *z_in, *y_in, *xt_in;
+  OSQPFloat *x, *z, *y, *xt, *zt, *dx, *dy, *v, *t0, *xg, *rho, *Minv, *hist;          /* out */
+  OSQPInt form, f1_D, f1_mix, launches;                                                /* out */
+  OSQPInt stat_sum, stat_max, stat_unconv, stat_n, pcg_iters, pcg_done;                /* out: F_STAT_SUM / MAX / UNCONV / N of the chunk, F_ITERS / F_DONE of the last PCG */
+  OSQPFloat tol_now, rn0;                                                              /* out: S_TOL_NOW, S_RN0 of the last PCG */
+} OSQPHipAdmmTest;
+OSQPInt osqp_hip_test_admm(OSQPSolver *solver, OSQPHipAdmmTest *t);
 /* Weight of equality rows relative to inequality rows, rho_eq = factor * rho, used when equality and inequality rows are
    mixed (default 10; the reference's 1e3 is kept when every active row is an equality).  See engine.cpp (Engine::classify_constraints)
    classify_constraints() for the rationale.  Takes effect immediately (rho vector + preconditioner are rebuilt). */

@@ -50,6 +50,7 @@ class Engine {
   int test_band(OSQPHipBandTest *t);
   int test_woodbury(OSQPHipWoodburyTest *t);
   int test_lockstep(OSQPHipLockstepTest *t);
+  int test_admm(OSQPHipAdmmTest *t);
   int trace_read(unsigned long long *out, int count);
   int get_scaling(double *D, double *E, double *c);
   int get_reordering(int *perm_cols, int *perm_rows) const;

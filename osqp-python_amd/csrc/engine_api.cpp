@@ -1731,6 +1731,59 @@ int Engine::test_lockstep(OSQPHipLockstepTest *t) {
   }
   return OSQP_NO_ERROR;
 }
+// A few ADMM iterations of the PCG path from the caller's iterates, through the handle's own launch path (include/osqp_hip.h osqp_hip_test_admm): every
+// check first, then POKE (the four vectors up, the refresh of init_iterates(0), which also clears the PCG start's history), RUN (run_chunk, or run_slots with the
+// pairs the chunk needs plus one spare, and ONE synchronising fetch), PEEK.  Host code over operations that exist: it runs on the host simulator too.
+int Engine::test_admm(OSQPHipAdmmTest *t) {
+  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (!t) return OSQP_DATA_VALIDATION_ERROR;
+  if (t->iters < 1 || t->iters > 8 || t->cap < 0 || t->cap > 16) return OSQP_DATA_VALIDATION_ERROR;
+  if (!std::isfinite(t->tol_rel) || !std::isfinite(t->tol_abs) || t->tol_rel < 0.0 || t->tol_abs < 0.0) return OSQP_DATA_VALIDATION_ERROR;
+  if (t->n_len != (long long)n || t->m_len != (long long)m || t->hist_len != 3LL * t->cap) return OSQP_DATA_VALIDATION_ERROR;
+  if (!t->x_in || !t->xt_in || !t->x || !t->xt || !t->dx || !t->xg || !t->Minv || (t->cap > 0 && !t->hist)) return OSQP_DATA_VALIDATION_ERROR;
+  if (m > 0 && (!t->z_in || !t->y_in || !t->z || !t->y || !t->zt || !t->dy || !t->v || !t->t0 || !t->rho)) return OSQP_DATA_VALIDATION_ERROR;
+  if (d_.wb.on) return OSQP_FUNC_NOT_IMPLEMENTED;                       // (the Woodbury correction has its own tier: osqp_hip_test_woodbury)
+  be::activate(d_);
+  be::ext_wait(d_);
+  const int iters = t->iters, cap = t->cap;
+  const size_t nb = sizeof(double) * (size_t)n, mb = sizeof(double) * (size_t)m;
+  // ---- POKE
+  {
+    std::vector<double> hx(n), hxt(n), hz(m), hy(m);
+    for (int j = 0; j < n; j++) { const int c = reordered_ ? pc_[j] : j; hx[j] = t->x_in[c]; hxt[j] = t->xt_in[c]; }
+    for (int i = 0; i < m; i++) { const int r = reordered_ ? pr_[i] : i; hz[i] = t->z_in[r]; hy[i] = t->y_in[r]; }
+    be::h2d(d_, d_.x, hx.data(), nb); be::h2d(d_, d_.xs, hxt.data(), nb);
+    if (m > 0) { be::h2d(d_, d_.z, hz.data(), mb); be::h2d(d_, d_.y, hy.data(), mb); }
+  }
+  be::init_iterates(d_, 0);
+  be::set_pcg_tol(d_, t->tol_rel, t->tol_abs);
+  int flags[F_COUNT] = {0};
+  be::fetch_flags(d_, flags);                                           // (clears the statistics an earlier chunk may have left)
+  // ---- RUN
+  sync_graph_scalars();
+  const bool slots = use_slots_ && be::slots_supported(d_);
+  const double launches0 = stats_.kernel_launches;
+  if (!slots) run_chunk(iters, cap);
+  else run_slots(iters, (int)std::ceil(0.5 * iters * be::slot_launches(d_, cap)) + 1, cap);
+  be::fetch_flags(d_, flags);
+  t->launches = (int)(stats_.kernel_launches - launches0);
+  t->form = !slots ? (be::pcg_fused(d_) ? 1 : 0) : (d_.f1.on ? 3 : (d_.kf.on ? 4 : 2));
+  t->f1_D = d_.f1.on ? d_.f1.D : 0; t->f1_mix = d_.f1.on ? d_.f1.mix : 0;
+  if (slots && be::slot_done(d_) < iters) return OSQP_ALGEBRA_LOAD_ERROR;      // the string was too short for the chunk: nothing is topped up here
+  // ---- PEEK
+  std::vector<double> hn(n), hm(m);
+  auto peek_n = [&](double *dst, const double *src) { be::d2h(d_, hn.data(), src, nb); for (int j = 0; j < n; j++) dst[reordered_ ? pc_[j] : j] = hn[j]; };
+  auto peek_m = [&](double *dst, const double *src) { if (m == 0) return; be::d2h(d_, hm.data(), src, mb); for (int i = 0; i < m; i++) dst[reordered_ ? pr_[i] : i] = hm[i]; };
+  peek_n(t->x, d_.x); peek_n(t->xt, d_.xs); peek_n(t->dx, d_.dx); peek_n(t->xg, d_.xg); peek_n(t->Minv, d_.Minv);
+  peek_m(t->z, d_.z); peek_m(t->y, d_.y); peek_m(t->zt, d_.zt); peek_m(t->dy, d_.dy); peek_m(t->v, d_.v); peek_m(t->t0, d_.t0); peek_m(t->rho, d_.rho);
+  t->stat_sum = flags[F_STAT_SUM]; t->stat_max = flags[F_STAT_MAX]; t->stat_unconv = flags[F_STAT_UNCONV]; t->stat_n = flags[F_STAT_N];
+  t->pcg_iters = flags[F_ITERS]; t->pcg_done = flags[F_DONE];
+  double sc[2] = {0.0, 0.0};
+  be::d2h(d_, &sc[0], d_.scal + S_TOL_NOW, sizeof(double)); be::d2h(d_, &sc[1], d_.scal + S_RN0, sizeof(double));
+  t->tol_now = sc[0]; t->rn0 = sc[1];
+  for (int q = 0; q < 3 && cap > 0; q++) be::d2h(d_, t->hist + (size_t)q * cap, d_.scal + S_HIST + (size_t)q * (kMaxCg + 1), sizeof(double) * (size_t)cap);
+  return OSQP_NO_ERROR;
+}
 int Engine::get_reordering(int *perm_cols, int *perm_rows) const {
   if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   if (!perm_cols || (m > 0 && !perm_rows)) return OSQP_DATA_VALIDATION_ERROR;

@@ -506,7 +506,10 @@ __global__ __launch_bounds__(kBlock) void k_slot_a(Dev d) {
   if (st.ph == P_K1) {                                 // first A-apply of this ADMM iteration's PCG: stopping test on r_0, t_0 = rho .* (A u_0)
     GVec g{d.uu};
     EK1 e{d.rho, d.t};
-    if (process_rows_fd<1>(d.A, g, e, lds.k1, PreK1{d, 0, 0, lds.k1.red, st.admm & 1}, fd)) { st.ph = P_K2F; st.k = 0; }
+    if (process_rows_fd<1>(d.A, g, e, lds.k1, PreK1{d, 0, 0, lds.k1.red, st.admm & 1}, fd)) {
+      if (st.cap < 1) { st.ph = P_KA; st.used = 0; st.conv = 0; }      // a cap of 0 budgets no PCG iteration: KA in the next A slot, as the other forms do (used = 0, cut off)
+      else { st.ph = P_K2F; st.k = 0; }
+    }
     else {                                             // the warm start already meets the tolerance: no PCG iteration, KA right here
       __syncthreads();
       slot_ka(d, lds.k1, 0, 1, fd, st.admm, st.target, st.seq);

@@ -108,6 +108,17 @@ class LockstepTestStruct(C.Structure):    # OSQPHipLockstepTest, include/osqp_hi
                 [(k, C.c_int) for k in ('r', 'GC', 'cb', 'nv')] + [('dws_need', C.c_longlong), ('dmat_need', C.c_longlong)])
 
 
+ADMM_TEST_OUT = ('x', 'z', 'y', 'xt', 'zt', 'dx', 'dy', 'v', 't0', 'xg', 'rho', 'Minv', 'hist')      # the output arrays of OSQPHipAdmmTest, in order
+
+
+class AdmmTestStruct(C.Structure):    # OSQPHipAdmmTest, include/osqp_hip.h (same order)
+    _fields_ = ([('iters', C.c_int), ('cap', C.c_int), ('tol_rel', C.c_double), ('tol_abs', C.c_double)] +
+                [(k, C.c_longlong) for k in ('n_len', 'm_len', 'hist_len')] +
+                [(k, c_double_p) for k in ('x_in', 'z_in', 'y_in', 'xt_in')] + [(k, c_double_p) for k in ADMM_TEST_OUT] +
+                [(k, C.c_int) for k in ('form', 'f1_D', 'f1_mix', 'launches', 'stat_sum', 'stat_max', 'stat_unconv', 'stat_n', 'pcg_iters', 'pcg_done')] +
+                [('tol_now', C.c_double), ('rn0', C.c_double)])
+
+
 SolverP = C.POINTER(SolverStruct)
 
 
@@ -159,6 +170,7 @@ PROTOTYPES = {
     'osqp_hip_test_band': (C.c_int, [SolverP, C.POINTER(BandTestStruct)]),
     'osqp_hip_test_woodbury': (C.c_int, [SolverP, C.POINTER(WoodburyTestStruct)]),
     'osqp_hip_test_lockstep': (C.c_int, [SolverP, C.POINTER(LockstepTestStruct)]),
+    'osqp_hip_test_admm': (C.c_int, [SolverP, C.POINTER(AdmmTestStruct)]),
     'osqp_hip_set_rho_eq_factor': (C.c_int, [SolverP, C.c_double]),
     'osqp_hip_default_policy': (None, [C.POINTER(PolicyStruct)]),
     'osqp_hip_set_default_policy': (None, [C.POINTER(PolicyStruct)]),

@@ -392,6 +392,27 @@ class OSQPSolver:
                    gamma=float(t.gamma), rnorm=float(t.rnorm))
         return st, out
 
+    def hip_test_admm(self, x, z, y, xt, iters=1, cap=0, tol_rel=0.0, tol_abs=0.0, lens=None):
+        """`iters` ADMM iterations of the PCG path from the SCALED iterates x [n], z [m], y [m], xt [n] (x~) through this handle's own launch path
+        (osqp_hip_test_admm: POKE, RUN, PEEK; every PCG capped at `cap` iterations, stopped at max(tol_rel ||rhs||, tol_abs)).  lens = {field: length}
+        overrides a length as it is passed (the entry validates).  Returns (status, dict): the NaN canvases x, z, y, xt, zt, dx, dy, v, t0, xg, rho, Minv
+        and hist [3, cap] (gamma, alpha, beta) as the call left them, and form, f1_D, f1_mix, launches, stat_sum, stat_max, stat_unconv, stat_n,
+        pcg_iters, pcg_done, tol_now, rn0.  The handle's iterates stay as the run left them."""
+        n, m = self.n, self.m
+        ins = [np.ascontiguousarray(a, dtype=np.float64).ravel() for a in (x, z, y, xt)]
+        size = dict(x=n, z=m, y=m, xt=n, zt=m, dx=n, dy=m, v=m, t0=m, xg=n, rho=m, Minv=n, hist=3 * max(int(cap), 0))
+        out = {k: np.full(size[k], np.nan) for k in _lib.ADMM_TEST_OUT}
+        ln = dict(n_len=n, m_len=m, hist_len=size['hist'])
+        ln.update(lens or {})
+        t = _lib.AdmmTestStruct(int(iters), int(cap), float(tol_rel), float(tol_abs), int(ln['n_len']), int(ln['m_len']), int(ln['hist_len']),
+                                *[_ptr(a if a.size else None, _lib.c_double_p) for a in ins],
+                                *[_ptr(out[k] if out[k].size else None, _lib.c_double_p) for k in _lib.ADMM_TEST_OUT])
+        st = int(self._lib.osqp_hip_test_admm(self._p, C.byref(t)))
+        out['hist'] = out['hist'].reshape(3, -1)
+        out.update({k: int(getattr(t, k)) for k in ('form', 'f1_D', 'f1_mix', 'launches', 'stat_sum', 'stat_max', 'stat_unconv', 'stat_n', 'pcg_iters', 'pcg_done')})
+        out.update(tol_now=float(t.tol_now), rn0=float(t.rn0))
+        return st, out
+
     def hip_get_reordering(self):
         """osqp_hip_get_reordering: (perm_cols [n], perm_rows [m]) -- the caller's index of the engine's k-th variable / constraint (the identity
         unless the handle works on a permuted copy)."""

@@ -110,6 +110,7 @@ void k1(Dev &d, int i) {
   if (d.flags[F_DONE]) return;
   Impl &s = im(d);
   double tol = std::max(d.scal[S_TOL_REL] * s.bnorm, d.scal[S_TOL_ABS]);
+  if (i == 0) d.scal[S_TOL_NOW] = tol;                  // (as k_k1's stopping test records it)
   if (!(s.rnorm > tol)) { d.flags[F_DONE] = 1; d.flags[F_ITERS] = i; return; }
   for (int r = 0; r < d.m; r++) {
     double a = 0;
