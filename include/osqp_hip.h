@@ -886,6 +886,52 @@ typedef struct {
   OSQPFloat tol_now, rn0;                                                              /* out: S_TOL_NOW, S_RN0 of the last PCG */
 } OSQPHipAdmmTest;
 OSQPInt osqp_hip_test_admm(OSQPSolver *solver, OSQPHipAdmmTest *t);
+/* Test hook (used by tests/ only): the CHUNK BOUNDARY of a single-QP solve on vectors the caller gives -- the residual kernels and their two-level fold,
+   the second stage of the infeasibility tests, the kernels that follow a rho change, and the device-driven boundary group with the rules of csrc/policy.h
+   between them (DESIGN.md sections 2, 2.1) -- POKE, RUN, PEEK on a set-up handle.
+     POKE   x, dx, xt (x~) [n] and z, y, dy, zt (z~) [m]: SCALED vectors (osqp_hip_get_scaling) in the caller's numbering.  They are uploaded into the
+            handle's own arrays and NO refresh kernel runs: the kernels under test read exactly what was given.
+     RUN    mode 0 (any handle; the host simulator too): the residual pass, then for the bits of `need` (1: primal, 2: dual) the second-stage kernels of
+            the infeasibility tests -- the dual one with the caller's threshold `thr` and `unscaled` --, then the fetch of the residual block.
+            mode 1: the device-driven boundary group.  The state block is built as a solve builds it (settings snapshot, PCG tolerance from a residual pass
+            of the poked vectors, the first chunk), then the caller's `iter` (the iteration count the finished chunk ends at), `at_check`, `chunk_done`
+            and `status_in` are set, rho_flag and stage2 cleared, the block uploaded, the residual block and the chunk's PCG statistics zeroed -- a kernel
+            that should idle leaves zeros -- and the group enqueued `groups` times (1 or 2) as a solve enqueues it (replayed from a captured graph where
+            the handle replays graphs); then the block is read back.
+     PEEK   res [OSQP_HIP_RES_COUNT] as it stands on the device (osqp_hip_res_name gives the order); rho, rho_inv, v, t0, ztg [m]; xg, xsp, Minv [n];
+            tol_rel / tol_abs: the PCG tolerance scalars on the device; launches: kernel launches enqueued; form as osqp_hip_test_admm reports it.  In
+            mode 1 `dev` holds the fields of the state block a boundary writes, as the device left them, and `host` the same fields of the HOST's twin: the
+            host's compilation of the same rules applied `groups` times to a copy of the uploaded block, with the residual block the device produced.
+   Afterwards, with keep = 0, the handle's own rho is applied again (rho vector, v, t0, preconditioner, explicit K): a later osqp_solve with
+   warm_starting = 0 is a fresh handle's solve bit for bit.  With keep = 1 a rho the group changed STAYS and the handle adopts it as a device-driven solve
+   does (settings.rho): the next osqp_hip_test_admm runs at the new rho.
+   Every length is exact (n_len = n, m_len = m, res_len = OSQP_HIP_RES_COUNT; a NULL pointer only where the length is 0) and everything is checked before
+   anything is uploaded or launched: mode, unscaled, keep, at_check, chunk_done outside {0, 1}, need outside 0 .. 3, groups outside {1, 2}, status_in
+   outside 0 .. 2, iter < 0, thr negative or not finite give OSQP_DATA_VALIDATION_ERROR.  Mode 1 answers OSQP_FUNC_NOT_IMPLEMENTED on a handle without the
+   slot form or without a device state block (the host simulator), and on one whose Woodbury correction is on (osqp_hip_test_woodbury is its tier). */
+#define OSQP_HIP_RES_COUNT 28
+typedef struct {
+  OSQPInt status, osqp_status, need, stage2, rho_flag, rho_updates, iter, boundaries;
+  OSQPInt ch_next, ch_at_check, ch_kind, ch_tight, budget[2];
+  OSQPFloat rho_bar, rho_estimate, tol_rel, tol_abs;
+  OSQPFloat obj_val, prim_res, dual_res, dual_obj_val, duality_gap, rel_kkt_error;
+  OSQPFloat inf_nd_p, inf_nd_d, inf_thr_d;
+  OSQPInt inf_unscaled;
+} OSQPHipBoundaryCtl;
+typedef struct {
+  OSQPInt mode, need, unscaled, groups, keep;
+  OSQPInt iter, at_check, chunk_done, status_in;                                       /* mode 1 */
+  OSQPFloat thr;
+  long long n_len, m_len, res_len;
+  const OSQPFloat *x_in, *dx_in, *xt_in, *z_in, *y_in, *dy_in, *zt_in;
+  OSQPFloat *res, *rho, *rho_inv, *v, *t0, *ztg, *xg, *xsp, *Minv;                     /* out */
+  OSQPFloat tol_rel, tol_abs;                                                          /* out */
+  OSQPInt launches, form;                                                              /* out */
+  OSQPHipBoundaryCtl dev, host;                                                        /* out (mode 1) */
+} OSQPHipBoundaryTest;
+OSQPInt osqp_hip_test_boundary(OSQPSolver *solver, OSQPHipBoundaryTest *t);
+/* name of entry q of the residual block ("R_PRI_U", ...), NULL outside 0 .. OSQP_HIP_RES_COUNT - 1 */
+const char *osqp_hip_res_name(OSQPInt q);
 /* Weight of equality rows relative to inequality rows, rho_eq = factor * rho, used when equality and inequality rows are
    mixed (default 10; the reference's 1e3 is kept when every active row is an equality).  See engine.cpp (Engine::classify_constraints)
    classify_constraints() for the rationale.  Takes effect immediately (rho vector + preconditioner are rebuilt). */

@@ -95,6 +95,8 @@ OSQPInt osqp_hip_test_band(OSQPSolver *s, OSQPHipBandTest *t) { return guarded(s
 OSQPInt osqp_hip_test_woodbury(OSQPSolver *s, OSQPHipWoodburyTest *t) { return guarded(s, [&](Engine &e) { return e.test_woodbury(t); }); }
 OSQPInt osqp_hip_test_lockstep(OSQPSolver *s, OSQPHipLockstepTest *t) { return guarded(s, [&](Engine &e) { return e.test_lockstep(t); }); }
 OSQPInt osqp_hip_test_admm(OSQPSolver *s, OSQPHipAdmmTest *t) { return guarded(s, [&](Engine &e) { return e.test_admm(t); }); }
+OSQPInt osqp_hip_test_boundary(OSQPSolver *s, OSQPHipBoundaryTest *t) { return guarded(s, [&](Engine &e) { return e.test_boundary(t); }); }
+const char *osqp_hip_res_name(OSQPInt q) { return Engine::res_name(q); }
 OSQPInt osqp_hip_set_rho_eq_factor(OSQPSolver *s, OSQPFloat f) { return guarded(s, [&](Engine &e) { return e.set_rho_eq_factor(f); }); }
 void osqp_hip_default_policy(OSQPHipPolicy *p) { Engine::default_policy(p); }
 void osqp_hip_set_default_policy(const OSQPHipPolicy *p) { Engine::set_default_policy(p); }

@@ -97,8 +97,9 @@ __device__ __forceinline__ bool ctl_stage2_due(const Dev &d, int bits) { return 
 __global__ __launch_bounds__(kBlock) void k_res_final(Dev d, int q0, int cond) {        // cond 1: first stage of a boundary group, 2: its second stage
   __shared__ double sred[2 * kWaves];
   if (cond == 1 && !ctl_res_due(d)) return;
-  if (cond == 2 && !ctl_stage2_due(d, NEED_PINF | NEED_DINF)) return;
   const int q = q0 + blockIdx.x;
+  // (second stage: only the quantities of a test that is pending -- the partials of the other test are whatever an earlier boundary left)
+  if (cond == 2 && !ctl_stage2_due(d, q <= R_ATDY_S ? NEED_PINF : NEED_DINF)) return;
   const double *slot = d.part + (SL_RES0 + q) * kGrid;
   const double v = res_is_sum(q) ? partial_sum(slot, sred) : partial_max(slot, sred);
   if (threadIdx.x == 0) d.res[q] = v;

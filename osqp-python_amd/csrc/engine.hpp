@@ -51,6 +51,8 @@ class Engine {
   int test_woodbury(OSQPHipWoodburyTest *t);
   int test_lockstep(OSQPHipLockstepTest *t);
   int test_admm(OSQPHipAdmmTest *t);
+  int test_boundary(OSQPHipBoundaryTest *t);
+  static const char *res_name(int q);
   int trace_read(unsigned long long *out, int count);
   int get_scaling(double *D, double *E, double *c);
   int get_reordering(int *perm_cols, int *perm_rows) const;

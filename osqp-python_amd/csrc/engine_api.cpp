@@ -1784,6 +1784,123 @@ int Engine::test_admm(OSQPHipAdmmTest *t) {
   for (int q = 0; q < 3 && cap > 0; q++) be::d2h(d_, t->hist + (size_t)q * cap, d_.scal + S_HIST + (size_t)q * (kMaxCg + 1), sizeof(double) * (size_t)cap);
   return OSQP_NO_ERROR;
 }
+// The order of Dev::res (backend.h ResId) by name, for the tests' reference (include/osqp_hip.h osqp_hip_res_name)
+const char *Engine::res_name(int q) {
+  static const char *const names[] = {
+    "R_PRI_U", "R_AX_U", "R_Z_U", "R_PRI_S", "R_AX_S", "R_Z_S", "R_DY_U", "R_DY_S", "R_PINF_LHS", "R_SUPP",
+    "R_DUA_U", "R_PX_U", "R_ATY_U", "R_DUA_S", "R_PX_S", "R_ATY_S", "R_DX_U", "R_DX_S", "R_XPX", "R_QX", "R_QDX",
+    "R_QN_S", "R_QN_U",
+    "R_ATDY_U", "R_ATDY_S", "R_PDX_U", "R_PDX_S", "R_ADX_VIOL"};
+  static_assert(sizeof(names) / sizeof(names[0]) == R_COUNT, "one name per entry of Dev::res");
+  static_assert(OSQP_HIP_RES_COUNT == R_COUNT, "include/osqp_hip.h states the length of Dev::res");
+  static_assert(R_PRI_U == 0 && R_SUPP == 9 && R_DUA_U == 10 && R_QDX == 20 && R_QN_U == 22 && R_ATDY_U == 23 && R_ADX_VIOL == 27, "the names follow ResId's order");
+  return (q >= 0 && q < R_COUNT) ? names[q] : nullptr;
+}
+namespace {
+OSQPHipBoundaryCtl boundary_fields(const Ctl &c) {
+  OSQPHipBoundaryCtl o;
+  o.status = c.status; o.osqp_status = c.osqp_status; o.need = c.need; o.stage2 = c.stage2; o.rho_flag = c.rho_flag; o.rho_updates = c.rho_updates;
+  o.iter = c.iter; o.boundaries = c.boundaries; o.ch_next = c.ch_next; o.ch_at_check = c.ch_at_check; o.ch_kind = c.ch_kind; o.ch_tight = c.ch_tight;
+  o.budget[0] = c.budget[0]; o.budget[1] = c.budget[1];
+  o.rho_bar = c.rho_bar; o.rho_estimate = c.rho_estimate; o.tol_rel = c.tol_rel; o.tol_abs = c.tol_abs;
+  o.obj_val = c.obj_val; o.prim_res = c.prim_res; o.dual_res = c.dual_res; o.dual_obj_val = c.dual_obj_val; o.duality_gap = c.duality_gap; o.rel_kkt_error = c.rel_kkt_error;
+  o.inf_nd_p = c.inf_nd_p; o.inf_nd_d = c.inf_nd_d; o.inf_thr_d = c.inf_thr_d; o.inf_unscaled = c.inf_unscaled;
+  return o;
+}
+// what ONE boundary group does to the state block, on the host: backend_hip.hip k_decide's two stages around policy.h's rules, with the residual block
+// and the chunk statistics the device had
+void boundary_twin_group(Ctl &c, const double *res, const int *flags) {
+  if (c.status != CTL_RUNNING) return;
+  if (!c.chunk_done) { c.rho_flag = 0; return; }
+  c.chunk_done = 0;
+  if (c.boundaries >= 0 && c.boundaries < kCtlHist) c.hist[c.boundaries] = c.seq_end - c.seq_begin;
+  for (int q = 0; q < F_COUNT; q++) c.last_flags[q] = flags[q];
+  int st = ctl_boundary(c, res, flags);
+  if (st == CTL_RUNNING && c.stage2) st = ctl_boundary_stage2(c, res, c.last_flags);
+  c.status = st;
+}
+}  // namespace
+// The chunk boundary on the caller's vectors (include/osqp_hip.h osqp_hip_test_boundary): every check first, then POKE (seven vectors up, nothing
+// refreshed), RUN (mode 0: the host-synchronous launches of a boundary; mode 1: the device-driven group, as admm_core / run_device_driven set it up and
+// enqueue it), PEEK.  Mode 0 is host code over operations that exist: it runs on the host simulator too.
+int Engine::test_boundary(OSQPHipBoundaryTest *t) {
+  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (!t) return OSQP_DATA_VALIDATION_ERROR;
+  auto bit = [](int v) { return v == 0 || v == 1; };
+  if (!bit(t->mode) || !bit(t->unscaled) || !bit(t->keep) || t->need < 0 || t->need > (NEED_PINF | NEED_DINF)) return OSQP_DATA_VALIDATION_ERROR;
+  if (!std::isfinite(t->thr) || t->thr < 0.0) return OSQP_DATA_VALIDATION_ERROR;
+  if (t->mode == 1 && (!bit(t->at_check) || !bit(t->chunk_done) || t->groups < 1 || t->groups > 2 || t->iter < 0 || t->status_in < CTL_RUNNING || t->status_in > CTL_NEED_HOST)) return OSQP_DATA_VALIDATION_ERROR;
+  if (t->n_len != (long long)n || t->m_len != (long long)m || t->res_len != (long long)R_COUNT) return OSQP_DATA_VALIDATION_ERROR;
+  if (!t->x_in || !t->dx_in || !t->xt_in || !t->res || !t->xg || !t->xsp || !t->Minv) return OSQP_DATA_VALIDATION_ERROR;
+  if (m > 0 && (!t->z_in || !t->y_in || !t->dy_in || !t->zt_in || !t->rho || !t->rho_inv || !t->v || !t->t0 || !t->ztg)) return OSQP_DATA_VALIDATION_ERROR;
+  const bool slots = use_slots_ && be::slots_supported(d_);
+  if (t->mode == 1 && (!slots || !be::ctl_supported(d_) || d_.wb.on)) return OSQP_FUNC_NOT_IMPLEMENTED;
+  be::activate(d_);
+  be::ext_wait(d_);
+  const size_t nb = sizeof(double) * (size_t)n, mb = sizeof(double) * (size_t)m;
+  // ---- POKE
+  {
+    std::vector<double> hn(n), hm(m);
+    auto poke_n = [&](double *dst, const double *src) { for (int j = 0; j < n; j++) hn[j] = src[reordered_ ? pc_[j] : j]; be::h2d(d_, dst, hn.data(), nb); };
+    auto poke_m = [&](double *dst, const double *src) { if (m == 0) return; for (int i = 0; i < m; i++) hm[i] = src[reordered_ ? pr_[i] : i]; be::h2d(d_, dst, hm.data(), mb); };
+    poke_n(d_.x, t->x_in); poke_n(d_.dx, t->dx_in); poke_n(d_.xs, t->xt_in);
+    poke_m(d_.z, t->z_in); poke_m(d_.y, t->y_in); poke_m(d_.dy, t->dy_in); poke_m(d_.zt, t->zt_in);
+  }
+  // ---- RUN
+  sync_graph_scalars();
+  const double launches0 = stats_.kernel_launches;
+  t->form = !slots ? (be::pcg_fused(d_) ? 1 : 0) : (d_.f1.on ? 3 : (d_.kf.on ? 4 : 2));
+  double res[R_COUNT];
+  if (t->mode == 0) {
+    be::residuals(d_); stats_.kernel_launches += 3;
+    if (t->need & NEED_PINF) { be::infeas_primal(d_); stats_.kernel_launches += 2; }
+    if (t->need & NEED_DINF) { be::infeas_dual(d_, t->thr, t->unscaled); stats_.kernel_launches += 3; }
+    be::fetch_res(d_, res);
+  } else {
+    Ctl &c = ctl_;
+    ctl_setup();
+    int flags[F_COUNT] = {0};
+    be::fetch_flags(d_, flags);                                         // (clears the statistics an earlier chunk may have left)
+    for (int q = 0; q < F_COUNT; q++) flags[q] = 0;
+    {
+      double r0[R_COUNT];
+      be::residuals(d_); be::fetch_res(d_, r0);
+      ctl_init_tol(c, r0);
+    }
+    ctl_next_chunk(c);
+    c.ch_next = t->iter; c.ch_at_check = t->at_check; c.chunk_done = t->chunk_done; c.status = t->status_in; c.rho_flag = 0; c.stage2 = 0;
+    Ctl twin = c;
+    be::ctl_upload(d_, c);
+    be::zero(d_, d_.res, sizeof(double) * R_COUNT);
+    const int diagonal = settings.cg_precond == OSQP_DIAGONAL_PRECONDITIONER;
+    for (int g = 0; g < t->groups; g++) run_group(diagonal);
+    Ctl dn;
+    be::ctl_download(d_, &dn);
+    be::fetch_res(d_, res);
+    for (int g = 0; g < t->groups; g++) boundary_twin_group(twin, res, flags);
+    t->dev = boundary_fields(dn); t->host = boundary_fields(twin);
+    c = dn;
+  }
+  t->launches = (int)(stats_.kernel_launches - launches0);
+  // ---- PEEK
+  for (int q = 0; q < R_COUNT; q++) t->res[q] = res[q];
+  std::vector<double> hn(n), hm(m);
+  auto peek_n = [&](double *dst, const double *src) { be::d2h(d_, hn.data(), src, nb); for (int j = 0; j < n; j++) dst[reordered_ ? pc_[j] : j] = hn[j]; };
+  auto peek_m = [&](double *dst, const double *src) { if (m == 0) return; be::d2h(d_, hm.data(), src, mb); for (int i = 0; i < m; i++) dst[reordered_ ? pr_[i] : i] = hm[i]; };
+  peek_n(t->xg, d_.xg); peek_n(t->xsp, d_.xsp); peek_n(t->Minv, d_.Minv);
+  peek_m(t->rho, d_.rho); peek_m(t->rho_inv, d_.rho_inv); peek_m(t->v, d_.v); peek_m(t->t0, d_.t0); peek_m(t->ztg, d_.ztg);
+  double sc[2] = {0.0, 0.0};
+  be::d2h(d_, sc, d_.scal + S_TOL_REL, sizeof(double) * 2);
+  static_assert(S_TOL_ABS == S_TOL_REL + 1, "the two tolerance scalars are read in one copy");
+  t->tol_rel = sc[0]; t->tol_abs = sc[1];
+  // ---- afterwards
+  if (t->mode == 1) {
+    if (t->keep && ctl_.rho_bar != rho_bar_) { rho_bar_ = ctl_.rho_bar; settings.rho = rho_bar_; }      // (applied on the device, as run_device_driven adopts it)
+    else apply_rho(rho_bar_);
+    be::sync(d_);
+  }
+  return OSQP_NO_ERROR;
+}
 int Engine::get_reordering(int *perm_cols, int *perm_rows) const {
   if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   if (!perm_cols || (m > 0 && !perm_rows)) return OSQP_DATA_VALIDATION_ERROR;

@@ -151,6 +151,13 @@ OSQP_HD inline void ctl_info(Ctl &c, const double *res) {
   // (written out on Ctl's own fields, not through term_info: routed through it the device compiler fuses the product of obj_val into the
   //  subtraction of duality_gap, and the gap's last bits change.  For the same reason the subtraction stays here, on the stored fields, and
   //  only what comes after it -- term_rel_kkt: quotients and maxima, nothing to fuse -- is term_rules.h's, shared with the small-problem path)
+  // (... and written out was not enough: inside k_decide, where this function is inlined, the device compiler still contracted obj_val's product into the
+  //  subtraction -- duality_gap of a device-driven check differed from the host's by one rounding of obj_val, found by tests/test_gpu_boundary_kernels.py
+  //  scenario (c).  Contraction is therefore switched off for this body: the gap is the difference of the two STORED values on both sides.  The two other
+  //  sums have an exact product, 0.5 x'Px, so nothing else changes)
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
   const bool unsc = c.scaling && !c.scaled_termination;
   const double ci = c.scaling ? c.cinv : 1.0;
   c.obj_val = (0.5 * res[R_XPX] + res[R_QX]) * ci;

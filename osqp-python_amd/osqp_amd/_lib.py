@@ -119,6 +119,25 @@ class AdmmTestStruct(C.Structure):    # OSQPHipAdmmTest, include/osqp_hip.h (sam
                 [('tol_now', C.c_double), ('rn0', C.c_double)])
 
 
+BOUNDARY_CTL_INTS = ('status', 'osqp_status', 'need', 'stage2', 'rho_flag', 'rho_updates', 'iter', 'boundaries', 'ch_next', 'ch_at_check', 'ch_kind', 'ch_tight')
+BOUNDARY_CTL_DOUBLES = ('rho_bar', 'rho_estimate', 'tol_rel', 'tol_abs', 'obj_val', 'prim_res', 'dual_res', 'dual_obj_val', 'duality_gap', 'rel_kkt_error',
+                        'inf_nd_p', 'inf_nd_d', 'inf_thr_d')
+BOUNDARY_TEST_IN = ('x', 'dx', 'xt', 'z', 'y', 'dy', 'zt')                                       # the input arrays of OSQPHipBoundaryTest, in order ([n] x 3, [m] x 4)
+BOUNDARY_TEST_OUT = ('res', 'rho', 'rho_inv', 'v', 't0', 'ztg', 'xg', 'xsp', 'Minv')             # its output arrays, in order
+RES_COUNT = 28                                                                                   # OSQP_HIP_RES_COUNT
+
+
+class BoundaryCtlStruct(C.Structure):    # OSQPHipBoundaryCtl, include/osqp_hip.h (same order)
+    _fields_ = ([(k, C.c_int) for k in BOUNDARY_CTL_INTS] + [('budget', C.c_int * 2)] + [(k, C.c_double) for k in BOUNDARY_CTL_DOUBLES] + [('inf_unscaled', C.c_int)])
+
+
+class BoundaryTestStruct(C.Structure):    # OSQPHipBoundaryTest, include/osqp_hip.h (same order)
+    _fields_ = ([(k, C.c_int) for k in ('mode', 'need', 'unscaled', 'groups', 'keep', 'iter', 'at_check', 'chunk_done', 'status_in')] + [('thr', C.c_double)] +
+                [(k, C.c_longlong) for k in ('n_len', 'm_len', 'res_len')] +
+                [(k + '_in', c_double_p) for k in BOUNDARY_TEST_IN] + [(k, c_double_p) for k in BOUNDARY_TEST_OUT] +
+                [('tol_rel', C.c_double), ('tol_abs', C.c_double), ('launches', C.c_int), ('form', C.c_int), ('dev', BoundaryCtlStruct), ('host', BoundaryCtlStruct)])
+
+
 SolverP = C.POINTER(SolverStruct)
 
 
@@ -171,6 +190,8 @@ PROTOTYPES = {
     'osqp_hip_test_woodbury': (C.c_int, [SolverP, C.POINTER(WoodburyTestStruct)]),
     'osqp_hip_test_lockstep': (C.c_int, [SolverP, C.POINTER(LockstepTestStruct)]),
     'osqp_hip_test_admm': (C.c_int, [SolverP, C.POINTER(AdmmTestStruct)]),
+    'osqp_hip_test_boundary': (C.c_int, [SolverP, C.POINTER(BoundaryTestStruct)]),
+    'osqp_hip_res_name': (C.c_char_p, [C.c_int]),
     'osqp_hip_set_rho_eq_factor': (C.c_int, [SolverP, C.c_double]),
     'osqp_hip_default_policy': (None, [C.POINTER(PolicyStruct)]),
     'osqp_hip_set_default_policy': (None, [C.POINTER(PolicyStruct)]),

@@ -413,6 +413,45 @@ class OSQPSolver:
         out.update(tol_now=float(t.tol_now), rn0=float(t.rn0))
         return st, out
 
+    def hip_res_names(self):
+        """The order of the residual block (backend.h ResId) as a list of names: 'R_PRI_U', ... (osqp_hip_res_name)."""
+        names = []
+        while True:
+            s = self._lib.osqp_hip_res_name(len(names))
+            if s is None:
+                return names
+            names.append(s.decode())
+
+    def hip_test_boundary(self, x, dx, xt, z, y, dy, zt, mode=0, need=0, thr=0.0, unscaled=0, iter=0, at_check=1, chunk_done=1, status_in=0, groups=1, keep=0,
+                          lens=None):
+        """The chunk boundary on the SCALED vectors x, dx, xt [n] and z, y, dy, zt [m] (osqp_hip_test_boundary: POKE, RUN, PEEK).  mode 0: the residual
+        pass, the second-stage kernels of the infeasibility tests for the bits of `need` (1 primal, 2 dual, with thr / unscaled), the fetch.  mode 1: the
+        device-driven boundary group, `groups` times, on a state block with the caller's iter / at_check / chunk_done / status_in.  lens = {field: length}
+        overrides a length as it is passed (the entry validates).  Returns (status, dict): the NaN canvases res (a dict by name: 'R_PRI_U', ...; 'res_vec'
+        is the array), rho, rho_inv, v, t0, ztg, xg, xsp, Minv as the call left them, tol_rel, tol_abs, launches, form and, in mode 1, dev / host: dicts
+        of the state block's fields as the device left them and as the host's rules give them."""
+        n, m = self.n, self.m
+        ins = [np.ascontiguousarray(a, dtype=np.float64).ravel() for a in (x, dx, xt, z, y, dy, zt)]
+        size = dict(res=_lib.RES_COUNT, rho=m, rho_inv=m, v=m, t0=m, ztg=m, xg=n, xsp=n, Minv=n)
+        out = {k: np.full(size[k], np.nan) for k in _lib.BOUNDARY_TEST_OUT}
+        ln = dict(n_len=n, m_len=m, res_len=_lib.RES_COUNT)
+        ln.update(lens or {})
+        t = _lib.BoundaryTestStruct(int(mode), int(need), int(unscaled), int(groups), int(keep), int(iter), int(at_check), int(chunk_done), int(status_in), float(thr),
+                                    int(ln['n_len']), int(ln['m_len']), int(ln['res_len']),
+                                    *[_ptr(a if a.size else None, _lib.c_double_p) for a in ins],
+                                    *[_ptr(out[k] if out[k].size else None, _lib.c_double_p) for k in _lib.BOUNDARY_TEST_OUT])
+        st = int(self._lib.osqp_hip_test_boundary(self._p, C.byref(t)))
+        out['res_vec'] = out['res']
+        out['res'] = dict(zip(self.hip_res_names(), out['res_vec']))
+        out.update(tol_rel=float(t.tol_rel), tol_abs=float(t.tol_abs), launches=int(t.launches), form=int(t.form))
+        for side in ('dev', 'host'):
+            c = getattr(t, side)
+            d = {k: int(getattr(c, k)) for k in _lib.BOUNDARY_CTL_INTS + ('inf_unscaled',)}
+            d.update({k: float(getattr(c, k)) for k in _lib.BOUNDARY_CTL_DOUBLES})
+            d['budget'] = (int(c.budget[0]), int(c.budget[1]))
+            out[side] = d
+        return st, out
+
     def hip_get_reordering(self):
         """osqp_hip_get_reordering: (perm_cols [n], perm_rows [m]) -- the caller's index of the engine's k-th variable / constraint (the identity
         unless the handle works on a permuted copy)."""
