@@ -857,6 +857,54 @@ typedef struct {
   long long dws_need, dmat_need;                  /* out: the direct route */
 } OSQPHipLockstepTest;
 OSQPInt osqp_hip_test_lockstep(OSQPSolver *solver, OSQPHipLockstepTest *t);
+/* Test hook (used by tests/ only): osqp_hip_test_lockstep for the kernels csrc/lockstep_hip.hip adds for the BACKWARD PASS and for POLISH -- POKE, RUN, PEEK,
+   each op ONE kernel launch with the kernel (shared or own-matrix twin), the arguments and the grid the drivers use (ls_adj_go / ls_pol_go: one text serves
+   the drivers and this entry).  No host loop, no recurrence.
+     mode     0: ADJOINT.  The arguments are LockstepAdjointParams as osqp_hip_batch_adjoint_lockstep* builds them (recurrence settings, scalings, the entry
+              maps of the gradients); ws is the WHOLE adjoint work block, in and out: adj_need doubles (lockstep_adjoint_ws_doubles(n, m); route 1: dadj_need,
+              lockstep_direct_adjoint_ws_doubles(n, m, r)) -- the forward's block followed by ax gdx rx | ay gdy ry | code (packed ints).
+              1: POLISH.  The arguments are LockstepParams as a polishing osqp_hip_batch_solve_lockstep* builds them (pol_rho, pol_min_steps, check_dualgap,
+              the epsilons) whatever settings.polishing says; ws is the forward block (ws_need / dws_need) and pol_ws the WHOLE polish block, in and out:
+              pol_need doubles (lockstep_polish_ws_doubles(n, m): x | y z l u).
+     route, mat, count   as osqp_hip_test_lockstep's; mat = 1 picks the k_lsm_* twin where one exists, mat_ws is then the matrix block (mat_need / dmat_need)
+     ops      [nops], 1 <= nops <= 64, each an OSQPHipLockstepBackOp of this mode.  ADJ_*: mode 0 (on route 1 LOAD_N writes x~ = Dinv x to the block vector
+              x~, CLASS and RESM read A through the view, as the direct backward pass launches them); GRAD_P / GRAD_A: k_ls_adj_grad<true / false>.
+              LWA_SETL_X / LWA_SETL_XS (k_lwa_setl into x / x~) and LWA_ZERO: route 1, either mode.  POL_*: mode 1; POL_END takes `secs`.
+              ADJ_LOAD_M, ADJ_CLASS, ADJ_RESM, ADJ_OUT_M and POL_CONE need m > 0; GRAD_P / GRAD_A need stored entries; an op that stores to a caller's
+              array needs it: ADJ_OUT_N dq, ADJ_OUT_M dl or du, GRAD_P dP, GRAD_A dA.
+     mode 0 arrays, [count][...] in the caller's numbering (dP / dA: the CSC order given at setup):
+       in     sx gx [count][n], sy [count][m]: required.  gy l u [count][m]: each optional (NULL with length 0: zero / the handle's own bounds)
+       out    dq [count][n], dl du [count][m], dP [count][nnz(triu P)], dA [count][nnz(A)], arec [count][OSQP_HIP_ADJOINT_REC]: each optional; uploaded whole and
+              downloaded whole, so that what an op does not write comes back as it went in
+     mode 1 arrays: x y rec as osqp_hip_test_lockstep's (no polish kernel stores to them: they come back as they went in)
+   The arrays of the other mode must be absent.  Out: the sizes n, m, nzP, nzA, G, r and ws_need, dws_need, adj_need, dadj_need, mat_need, dmat_need,
+   pol_need are written first whenever the handle is ready and t is not NULL (the direct route's where it takes the handle, 0 otherwise); after a call that
+   ran, the scalars the references need and do not restate: gain, min_steps, max_steps, rho0 (the adjoint recurrence: as built in mode 0, the struct's defaults
+   in mode 1), pol_rho, pol_min_steps (as built in mode 1, the defaults in mode 0), pol_max_steps, adjoint_tol (OSQP_HIP_ADJOINT_TOL), check_dualgap.
+   Everything is checked BEFORE anything is allocated, uploaded or launched (OSQP_DATA_VALIDATION_ERROR, nothing runs): a length other than listed, a NULL
+   pointer where a length is given, an array of the other mode, an op outside the enum, of the other mode, of the other route, an m-side op with m = 0, a
+   gradient without stored entries, an output op without its array, mat = 1 without the matrix block.  A handle the route declines (the solve / adjoint
+   entry's own predicate): OSQP_FUNC_NOT_IMPLEMENTED.  The resident blocks are scratch: a solve or backward pass after the call is the one without it. */
+typedef enum {
+  OSQP_HIP_LSB_ADJ_LOAD_N = 0, OSQP_HIP_LSB_ADJ_LOAD_M, OSQP_HIP_LSB_ADJ_CLASS, OSQP_HIP_LSB_ADJ_INIT, OSQP_HIP_LSB_ADJ_DECIDE, OSQP_HIP_LSB_ADJ_UNSCALE,
+  OSQP_HIP_LSB_ADJ_RESM, OSQP_HIP_LSB_ADJ_RESN, OSQP_HIP_LSB_ADJ_FINAL, OSQP_HIP_LSB_ADJ_OUT_N, OSQP_HIP_LSB_ADJ_OUT_M, OSQP_HIP_LSB_ADJ_GRAD_P, OSQP_HIP_LSB_ADJ_GRAD_A,
+  OSQP_HIP_LSB_LWA_SETL_X, OSQP_HIP_LSB_LWA_SETL_XS, OSQP_HIP_LSB_LWA_ZERO,
+  OSQP_HIP_LSB_POL_BEGIN, OSQP_HIP_LSB_POL_CLASS, OSQP_HIP_LSB_POL_DECIDE, OSQP_HIP_LSB_POL_CONE, OSQP_HIP_LSB_POL_ACCEPT, OSQP_HIP_LSB_POL_END,
+  OSQP_HIP_LSB_OP_COUNT
+} OSQPHipLockstepBackOp;
+typedef struct {
+  OSQPInt mode, route, mat, count, nops;
+  const OSQPInt *ops;
+  OSQPFloat secs;
+  long long sx_len, sy_len, gx_len, gy_len, l_len, u_len, dq_len, dl_len, du_len, dp_len, da_len, arec_len, x_len, y_len, rec_len, ws_len, mat_len, pol_len;
+  const OSQPFloat *sx, *sy, *gx, *gy, *l, *u;
+  OSQPFloat *dq, *dl, *du, *dP, *dA, *arec, *x, *y, *rec, *ws, *mat_ws, *pol_ws;
+  OSQPInt n, m, nzP, nzA, G, r;                                                           /* out */
+  long long ws_need, dws_need, adj_need, dadj_need, mat_need, dmat_need, pol_need;        /* out */
+  OSQPInt min_steps, max_steps, pol_min_steps, pol_max_steps, check_dualgap;              /* out */
+  OSQPFloat gain, rho0, pol_rho, adjoint_tol;                                             /* out */
+} OSQPHipLockstepBackTest;
+OSQPInt osqp_hip_test_lockstep_back(OSQPSolver *solver, OSQPHipLockstepBackTest *t);
 /* Test hook (used by tests/ only): a few ADMM iterations of the PCG path (csrc/pcg_hip.hip; DESIGN.md sections 2, 4.2, 4.3) from iterates the caller
    gives, through the handle's OWN launch path, with everything the kernels left behind read back -- POKE, RUN, PEEK on a set-up handle.
      POKE   x [n], z [m], y [m], xt [n] (x~): SCALED iterates (osqp_hip_get_scaling) in the caller's numbering.  They are uploaded; then the entry does

@@ -94,6 +94,7 @@ OSQPInt osqp_hip_test_dense(OSQPSolver *s, OSQPHipDenseTest *t) { return guarded
 OSQPInt osqp_hip_test_band(OSQPSolver *s, OSQPHipBandTest *t) { return guarded(s, [&](Engine &e) { return e.test_band(t); }); }
 OSQPInt osqp_hip_test_woodbury(OSQPSolver *s, OSQPHipWoodburyTest *t) { return guarded(s, [&](Engine &e) { return e.test_woodbury(t); }); }
 OSQPInt osqp_hip_test_lockstep(OSQPSolver *s, OSQPHipLockstepTest *t) { return guarded(s, [&](Engine &e) { return e.test_lockstep(t); }); }
+OSQPInt osqp_hip_test_lockstep_back(OSQPSolver *s, OSQPHipLockstepBackTest *t) { return guarded(s, [&](Engine &e) { return e.test_lockstep_back(t); }); }
 OSQPInt osqp_hip_test_admm(OSQPSolver *s, OSQPHipAdmmTest *t) { return guarded(s, [&](Engine &e) { return e.test_admm(t); }); }
 OSQPInt osqp_hip_test_boundary(OSQPSolver *s, OSQPHipBoundaryTest *t) { return guarded(s, [&](Engine &e) { return e.test_boundary(t); }); }
 const char *osqp_hip_res_name(OSQPInt q) { return Engine::res_name(q); }

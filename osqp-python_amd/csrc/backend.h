@@ -761,6 +761,12 @@ int test_woodbury(Dev &d, WbProbe &p) __attribute__((weak));
 // direct: the direct route (p.v: the view as Engine::fill_lockstep_direct_view fills it, with wtpos / vsrc where mat).
 struct LsProbe { LockstepDirectParams p; bool direct; int nops; const int *ops; };
 int test_lockstep(Dev &d, const LsProbe &t) __attribute__((weak));
+// the same for the kernels of the backward pass and of polish (include/osqp_hip.h osqp_hip_test_lockstep_back; OSQPHipLockstepBackOp).  polish == false: a is
+// what Engine::run_lockstep_adjoint builds (a.ws: the route's adjoint work block; sx .. arec: DEVICE arrays), the carve is lockstep_adjoint_chunk's or the
+// direct backward pass's.  polish == true: p is what a polishing Engine::run_lockstep_solve builds (p.ws, p.pol_ws: the route's forward block and the polish
+// block), the carve is lockstep_chunk's / lockstep_direct_chunk's.  secs: what POL_END writes.  pol_max_steps (out): polish's step cap.  Weak as well.
+struct LsBackProbe { LockstepDirectAdjointParams a; LockstepDirectParams p; bool polish, direct; int nops; const int *ops; double secs; int pol_max_steps; };
+int test_lockstep_back(Dev &d, LsBackProbe &t) __attribute__((weak));
 float time_kernel(Dev &d, int which, int reps);                             // mean ms per launch
 
 }  // namespace be

@@ -50,6 +50,7 @@ class Engine {
   int test_band(OSQPHipBandTest *t);
   int test_woodbury(OSQPHipWoodburyTest *t);
   int test_lockstep(OSQPHipLockstepTest *t);
+  int test_lockstep_back(OSQPHipLockstepBackTest *t);
   int test_admm(OSQPHipAdmmTest *t);
   int test_boundary(OSQPHipBoundaryTest *t);
   static const char *res_name(int q);
@@ -160,6 +161,8 @@ class Engine {
   int *d_pvmap_ = nullptr, *d_avmap_ = nullptr;       // device copies of PvalMap_ / AvalMap_ (reordered handle), uploaded by the first call that reads them
   bool ensure_value_maps();
   void fill_lockstep_solve(LsRoute &rt, LockstepParams &p, bool direct, bool mat, int warm, size_t need, size_t mneed);   // what a forward chunk's parameters keep from chunk to chunk: run_lockstep_solve and test_lockstep
+  void fill_lockstep_polish(LockstepParams &p, bool direct);      // polish's settings and work block (allocated by the first call): a polishing run_lockstep_solve and test_lockstep_back
+  void fill_lockstep_adjoint(LsRoute &rt, LockstepDirectAdjointParams &p, bool direct, bool mat, size_t need, size_t mneed);   // what a backward chunk's parameters keep from chunk to chunk: run_lockstep_adjoint and test_lockstep_back
   void fill_lockstep_handle(LockstepParams &p);       // the handle's matrices, scalings, shared vectors and permutations: every lockstep route
   int last_record(const double *src, int cnt, double *rec) const;      // behind every *_last_record
   // direct route: the structural decision of prepare_wb (K0 diagonal, small mode -- not DevWb::exact, which a failed inversion clears), the view of A

@@ -933,6 +933,37 @@ void Engine::fill_lockstep_solve(LsRoute &rt, LockstepParams &p, bool direct, bo
   if (fresh) be::sync(d_);
   p.mat_ws = rt.mat_ws; p.mat_iters = std::max(0, (int)settings.scaling);
 }
+// Polish of a chunk's solved problems: the recurrence of Engine::run_recurrence as Engine::polish calls it -- rho_bar = 1 / delta_eff, at least
+// 1 + polish_refine_iter steps; on the PCG route the inner systems to polish_pcg_tol within kMaxCg iterations.  The work block is one per handle.
+void Engine::fill_lockstep_polish(LockstepParams &p, bool direct) {
+  if (!lspw_) { lspw_ = dev_vec<double>(d_, lockstep_polish_ws_doubles(n, m)); be::sync(d_); }
+  const double de = std::max(settings.delta, pol_.polish_delta_floor);
+  p.polish = 1; p.pol_rho = clamp_rho(1.0 / de); p.pol_min_steps = 1 + std::max(0, (int)settings.polish_refine_iter);
+  p.pol_ws = lspw_;
+  if (direct) p.pol_prod2 = batch_env().ls_pol_prod2;
+  else { p.pol_cg_max = kMaxCg; p.pol_pcg_rel = pol_.polish_pcg_tol; }
+}
+// The parameters of a backward chunk that do not change from chunk to chunk, for run_lockstep_adjoint and the diagnostic entry (test_lockstep_back): the
+// direction's work block and, with mat, the route's matrix block (each allocated by the first call that needs it), the value maps of a reordered handle, the
+// settings snapshot, the handle, the recurrence's settings (the direct route has no PCG) and the entry maps of the gradients.  p.v: filled by the caller.
+void Engine::fill_lockstep_adjoint(LsRoute &rt, LockstepDirectAdjointParams &p, bool direct, bool mat, size_t need, size_t mneed) {
+  bool fresh = ensure_value_maps();
+  if (!rt.adj_ws) { rt.adj_ws = dev_vec<double>(d_, need); fresh = true; }
+  if (mat && !rt.mat_ws) { rt.mat_ws = dev_vec<double>(d_, mneed); fresh = true; }
+  if (mat && direct) { prepare_lockstep_direct_wtpos(); p.v.wtpos = lsd_wtpos_; p.v.vsrc = lsd_vsrc_; }
+  if (fresh) be::sync(d_);
+  fill_batch_settings(p, 0);
+  fill_lockstep_handle(p);
+  p.ws = rt.adj_ws;
+  const double de = std::max(settings.delta, pol_.polish_delta_floor);
+  p.alpha = 1.0; p.rho0 = clamp_rho(1.0 / de); p.eq_factor = 1.0; p.cg_max = direct ? 0 : kMaxCg; p.pcg_rel = direct ? 0.0 : pol_.polish_pcg_tol;
+  p.min_steps = 1 + std::max(0, (int)settings.polish_refine_iter); p.max_steps = 60; p.gain = 0.9;
+  p.nzP = d_.nzP; p.nzA = d_.nzA; p.Pi = d_.Pi; p.Pj = d_.Pj; p.Ai = d_.Ai; p.Aj = d_.Aj; p.Pmap = reordered_ ? d_pvmap_ : nullptr; p.Amap = reordered_ ? d_avmap_ : nullptr;
+  if (mat) {
+    p.mat_ws = rt.mat_ws; p.mat_iters = std::max(0, (int)settings.scaling); p.pvmap = p.Pmap; p.avmap = p.Amap;
+    if (!direct) lsm_last_count_ = 0;                 // (the block is being overwritten)
+  }
+}
 // device copies of PvalMap_ / AvalMap_ (reordered handle; per-problem matrices and the adjoint read them); true: something was uploaded, sync before use
 bool Engine::ensure_value_maps() {
   bool fresh = false;
@@ -1045,14 +1076,7 @@ int Engine::run_lockstep_solve(bool direct, int nbatch, const LockstepSolveIO &a
   double pst[kLsPolStat] = {0, 0, 0, 0, 0, 0, 0}, ptot[kLsPolStat] = {0, 0, 0, 0, 0, 0, 0};
   const size_t pneed = lockstep_polish_ws_doubles(n, m);
   const bool pol_record = !direct || settings.polishing || ls_pol_direct_;
-  if (settings.polishing) {
-    if (!lspw_) { lspw_ = dev_vec<double>(d_, pneed); be::sync(d_); }
-    const double de = std::max(settings.delta, pol_.polish_delta_floor);
-    p.polish = 1; p.pol_rho = clamp_rho(1.0 / de); p.pol_min_steps = 1 + std::max(0, (int)settings.polish_refine_iter);
-    p.pol_ws = lspw_; p.pol_stat = pst;
-    if (direct) p.pol_prod2 = batch_env().ls_pol_prod2;
-    else { p.pol_cg_max = kMaxCg; p.pol_pcg_rel = pol_.polish_pcg_tol; }
-  }
+  if (settings.polishing) { fill_lockstep_polish(p, direct); p.pol_stat = pst; }
   // direct, adaptive rho as the handle's own solve decides it (ctl_setup: the tolerance on the square-root scale where P has a quadratic part, the
   // persistence test), not as the batch family does: an element then takes the path update(q, l, u) + solve() takes from the same rho
   if (direct) { p.rho_tol_single = pol_rho_tol(settings.adaptive_rho_tolerance, has_quad(), pol_.rho_tol_exp); p.rho_persist = pol_.rho_persist; }
@@ -1152,24 +1176,9 @@ int Engine::run_lockstep_adjoint(bool direct, int nbatch, const LockstepAdjointI
   LockstepDirectAdjointParams p;                      // (the PCG route takes its LockstepAdjointParams base)
   if (direct) if (const int err = fill_lockstep_direct_view(p.v, stream)) return err;
   const size_t mneed = direct ? lockstep_direct_mat_ws_doubles(n, m, d_.wb.r, d_.A.nnz, d_.B.nnz, lsd_nv_) : lockstep_mat_ws_doubles(n, m, d_.A.nnz, d_.B.nnz);
-  bool fresh = ensure_value_maps();
-  if (!rt.adj_ws) { rt.adj_ws = dev_vec<double>(d_, need); fresh = true; }
-  if (mat && !rt.mat_ws) { rt.mat_ws = dev_vec<double>(d_, mneed); fresh = true; }
-  if (mat && direct) { prepare_lockstep_direct_wtpos(); p.v.wtpos = lsd_wtpos_; p.v.vsrc = lsd_vsrc_; }
-  if (fresh) be::sync(d_);
-  fill_batch_settings(p, 0);
-  fill_lockstep_handle(p);
-  p.ws = rt.adj_ws;
-  // the recurrence's settings; the direct route has no PCG
-  const double de = std::max(settings.delta, pol_.polish_delta_floor);
-  p.alpha = 1.0; p.rho0 = clamp_rho(1.0 / de); p.eq_factor = 1.0; p.cg_max = direct ? 0 : kMaxCg; p.pcg_rel = direct ? 0.0 : pol_.polish_pcg_tol;
-  p.min_steps = 1 + std::max(0, (int)settings.polish_refine_iter); p.max_steps = 60; p.gain = 0.9;
-  p.nzP = nzP; p.nzA = nzA; p.Pi = d_.Pi; p.Pj = d_.Pj; p.Ai = d_.Ai; p.Aj = d_.Aj; p.Pmap = reordered_ ? d_pvmap_ : nullptr; p.Amap = reordered_ ? d_avmap_ : nullptr;
+  fill_lockstep_adjoint(rt, p, direct, mat, need, mneed);
   double mst[kLsMatStat] = {0, 0}, mtot = 0;
-  if (mat) {
-    p.mat_ws = rt.mat_ws; p.mat_stat = mst; p.mat_iters = std::max(0, (int)settings.scaling); p.pvmap = p.Pmap; p.avmap = p.Amap;
-    if (!direct) lsm_last_count_ = 0;                 // (the block is being overwritten)
-  }
+  if (mat) p.mat_stat = mst;
   double tot[4] = {0, 0, 0, 0};
   int chunks = 0;
   auto at = [](auto *v, size_t off) { return v ? v + off : nullptr; };
@@ -1606,6 +1615,17 @@ int Engine::test_woodbury(OSQPHipWoodburyTest *t) {
   t->done = p.done; t->iters = p.iters; t->gamma = p.gamma; t->rnorm = p.rnorm;
   return OSQP_NO_ERROR;
 }
+// What both lockstep diagnostic entries stage a caller's array with: a device copy for the duration of the call (nullptr: the array is absent), freed on
+// every way out.
+namespace {
+struct LsStaged { Dev &d; double *p; ~LsStaged() { if (p) be::dfree(d, p); } };
+double *ls_stage(Dev &d, const double *src, long long len) {
+  if (!src) return nullptr;
+  double *dst = dev_vec<double>(d, (size_t)len);
+  be::h2d(d, dst, src, sizeof(double) * (size_t)len);
+  return dst;
+}
+}  // namespace
 // Single launches of the lockstep kernels on the caller's blocks (include/osqp_hip.h osqp_hip_test_lockstep).  The sizes first, then EVERY check, then the
 // parameters as run_lockstep_solve builds them, the staging of the caller's arrays, the blocks up, be::test_lockstep, the blocks down.
 int Engine::test_lockstep(OSQPHipLockstepTest *t) {
@@ -1686,13 +1706,8 @@ int Engine::test_lockstep(OSQPHipLockstepTest *t) {
   p.count = t->count;
   if (mat && !direct) lsm_last_count_ = 0;                                    // (the block is being overwritten)
   // ---- the caller's arrays, staged on the device for the duration of the call
-  struct Buf { Dev &d; double *p; ~Buf() { if (p) be::dfree(d, p); } };
-  auto stage = [&](const double *src, long long len) -> double * {
-    if (!src) return nullptr;
-    double *dst = dev_vec<double>(d_, (size_t)len);
-    be::h2d(d_, dst, src, sizeof(double) * (size_t)len);
-    return dst;
-  };
+  using Buf = LsStaged;
+  auto stage = [&](const double *src, long long len) { return ls_stage(d_, src, len); };
   Buf bq{d_, stage(t->q, t->q_len)}, bl{d_, stage(t->l, t->l_len)}, bu{d_, stage(t->u, t->u_len)}, bx{d_, stage(t->x, t->x_len)}, by{d_, stage(t->y, t->y_len)};
   Buf brec{d_, stage(t->rec, t->rec_len)}, bPx{d_, stage(t->Px, t->px_len)}, bAx{d_, stage(t->Ax, t->ax_len)};
   Buf by0{d_, (!by.p) ? dev_vec<double>(d_, 1) : nullptr};                     // (m = 0: a solve's y is a valid pointer that no kernel follows)
@@ -1729,6 +1744,108 @@ int Engine::test_lockstep(OSQPHipLockstepTest *t) {
       for (int i = 0; i < m; i++) t->islong[i] = fl[i];
     }
   }
+  return OSQP_NO_ERROR;
+}
+// The same for the kernels of the backward pass and of polish (include/osqp_hip.h osqp_hip_test_lockstep_back).  The sizes first, then EVERY check, then the
+// parameters as run_lockstep_adjoint (mode 0) or a polishing run_lockstep_solve (mode 1) builds them, the staging, the blocks up, be::test_lockstep_back, the
+// blocks and every staged output array down.
+int Engine::test_lockstep_back(OSQPHipLockstepBackTest *t) {
+  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (!t) return OSQP_DATA_VALIDATION_ERROR;
+  const long long nn = n, mm = m, nzP = d_.nzP, nzA = d_.nzA;
+  t->n = n; t->m = m; t->nzP = d_.nzP; t->nzA = d_.nzA; t->G = lockstep_grid(n, m); t->r = 0;
+  t->ws_need = (long long)lockstep_ws_doubles(n, m); t->adj_need = (long long)lockstep_adjoint_ws_doubles(n, m);
+  t->mat_need = (long long)lockstep_mat_ws_doubles(n, m, d_.A.nnz, d_.B.nnz); t->pol_need = (long long)lockstep_polish_ws_doubles(n, m);
+  t->dws_need = t->dadj_need = t->dmat_need = 0;
+  if (!be::test_lockstep_back) return OSQP_FUNC_NOT_IMPLEMENTED;
+  const bool dapplies = lockstep_direct_applies() && prepare_lockstep_direct_view() == OSQP_NO_ERROR;
+  if (dapplies) {
+    t->r = d_.wb.r; t->dws_need = (long long)lockstep_direct_ws_doubles(n, m, d_.wb.r); t->dadj_need = (long long)lockstep_direct_adjoint_ws_doubles(n, m, d_.wb.r);
+    t->dmat_need = (long long)lockstep_direct_mat_ws_doubles(n, m, d_.wb.r, d_.A.nnz, d_.B.nnz, lsd_nv_);
+  }
+  // ---- every check
+  if (!(t->mode == 0 || t->mode == 1) || !(t->route == 0 || t->route == 1) || !(t->mat == 0 || t->mat == 1)) return OSQP_DATA_VALIDATION_ERROR;
+  if (t->count < 1 || t->count > kLsW || t->nops < 1 || t->nops > 64 || !t->ops) return OSQP_DATA_VALIDATION_ERROR;
+  const bool polish = t->mode == 1, direct = t->route == 1, mat = t->mat != 0;
+  if (direct && !dapplies) return OSQP_FUNC_NOT_IMPLEMENTED;                    // (the direct route's lengths exist only where it takes the handle)
+  const long long need = polish ? (direct ? t->dws_need : t->ws_need) : (direct ? t->dadj_need : t->adj_need), mneed = direct ? t->dmat_need : t->mat_need;
+  for (int k = 0; k < t->nops; k++) {
+    const int op = t->ops[k];
+    if (op < 0 || op >= OSQP_HIP_LSB_OP_COUNT) return OSQP_DATA_VALIDATION_ERROR;
+    const bool adj_op = op <= OSQP_HIP_LSB_ADJ_GRAD_A, lwa_op = op >= OSQP_HIP_LSB_LWA_SETL_X && op <= OSQP_HIP_LSB_LWA_ZERO, pol_op = op >= OSQP_HIP_LSB_POL_BEGIN;
+    if ((adj_op && polish) || (pol_op && !polish) || (lwa_op && !direct)) return OSQP_DATA_VALIDATION_ERROR;
+    const bool m_only = op == OSQP_HIP_LSB_ADJ_LOAD_M || op == OSQP_HIP_LSB_ADJ_CLASS || op == OSQP_HIP_LSB_ADJ_RESM || op == OSQP_HIP_LSB_ADJ_OUT_M || op == OSQP_HIP_LSB_POL_CONE;
+    if (m_only && m == 0) return OSQP_DATA_VALIDATION_ERROR;
+    if ((op == OSQP_HIP_LSB_ADJ_GRAD_P && (nzP == 0 || !t->dP)) || (op == OSQP_HIP_LSB_ADJ_GRAD_A && (nzA == 0 || !t->dA))) return OSQP_DATA_VALIDATION_ERROR;
+    if ((op == OSQP_HIP_LSB_ADJ_OUT_N && !t->dq) || (op == OSQP_HIP_LSB_ADJ_OUT_M && !t->dl && !t->du)) return OSQP_DATA_VALIDATION_ERROR;
+  }
+  const long long cnt = t->count, an = polish ? 0 : cnt * nn, am = polish ? 0 : cnt * mm, pn = polish ? cnt * nn : 0, pm = polish ? cnt * mm : 0;
+  auto optional = [](const void *p, long long have, long long len) { return p ? have == len : have == 0; };
+  auto required = [](const void *p, long long have, long long len) { return have == len && (p || len == 0); };
+  if (!required(t->sx, t->sx_len, an) || !required(t->gx, t->gx_len, an) || !required(t->sy, t->sy_len, am)) return OSQP_DATA_VALIDATION_ERROR;
+  if (!optional(t->gy, t->gy_len, am) || !optional(t->l, t->l_len, am) || !optional(t->u, t->u_len, am)) return OSQP_DATA_VALIDATION_ERROR;
+  if (!optional(t->dq, t->dq_len, an) || !optional(t->dl, t->dl_len, am) || !optional(t->du, t->du_len, am) || !optional(t->dP, t->dp_len, polish ? 0 : cnt * nzP) ||
+      !optional(t->dA, t->da_len, polish ? 0 : cnt * nzA) || !optional(t->arec, t->arec_len, polish ? 0 : cnt * kAdjointRec))
+    return OSQP_DATA_VALIDATION_ERROR;
+  if (!required(t->x, t->x_len, pn) || !required(t->y, t->y_len, pm) || !required(t->rec, t->rec_len, polish ? cnt * kBatchRec : 0)) return OSQP_DATA_VALIDATION_ERROR;
+  if (polish ? (!t->x || !t->rec) : (t->x || t->y || t->rec)) return OSQP_DATA_VALIDATION_ERROR;
+  if (!t->ws || t->ws_len != need) return OSQP_DATA_VALIDATION_ERROR;
+  if (mat ? (!t->mat_ws || t->mat_len != mneed) : (t->mat_ws || t->mat_len != 0)) return OSQP_DATA_VALIDATION_ERROR;
+  if (polish ? (!t->pol_ws || t->pol_len != t->pol_need) : (t->pol_ws || t->pol_len != 0)) return OSQP_DATA_VALIDATION_ERROR;
+  // ---- the route
+  if (!(this->*solve_applies(direct, mat))()) return OSQP_FUNC_NOT_IMPLEMENTED;
+  if (!polish && !(direct ? lockstep_direct_adjoint_applies() : lockstep_adjoint_applies())) return OSQP_FUNC_NOT_IMPLEMENTED;
+  be::activate(d_);
+  be::ext_wait(d_);
+  // ---- the parameters of a chunk
+  LsRoute &rt = lsr_[direct];
+  be::LsBackProbe pr{};
+  pr.polish = polish; pr.direct = direct; pr.nops = t->nops; pr.ops = t->ops; pr.secs = t->secs;
+  using Buf = LsStaged;
+  auto stage = [&](const double *src, long long len) { return ls_stage(d_, src, len); };
+  double *block = nullptr;
+  if (polish) {
+    LockstepDirectParams &p = pr.p;
+    if (direct) if (const int err = fill_lockstep_direct_view(p.v, nullptr)) return err;
+    if (direct && mat) { prepare_lockstep_direct_wtpos(); p.v.wtpos = lsd_wtpos_; p.v.vsrc = lsd_vsrc_; }
+    fill_lockstep_solve(rt, p, direct, mat, 0, (size_t)need, (size_t)mneed);
+    fill_lockstep_polish(p, direct);
+    p.count = t->count;
+    if (mat && !direct) lsm_last_count_ = 0;                                  // (the block is being overwritten)
+    block = rt.ws;
+  } else {
+    LockstepDirectAdjointParams &p = pr.a;
+    if (direct) if (const int err = fill_lockstep_direct_view(p.v, nullptr)) return err;
+    fill_lockstep_adjoint(rt, p, direct, mat, (size_t)need, (size_t)mneed);
+    p.count = t->count;
+    block = rt.adj_ws;
+  }
+  Buf bsx{d_, stage(t->sx, t->sx_len)}, bsy{d_, stage(t->sy, t->sy_len)}, bgx{d_, stage(t->gx, t->gx_len)}, bgy{d_, stage(t->gy, t->gy_len)}, bl{d_, stage(t->l, t->l_len)}, bu{d_, stage(t->u, t->u_len)};
+  Buf bdq{d_, stage(t->dq, t->dq_len)}, bdl{d_, stage(t->dl, t->dl_len)}, bdu{d_, stage(t->du, t->du_len)}, bdP{d_, stage(t->dP, t->dp_len)}, bdA{d_, stage(t->dA, t->da_len)};
+  Buf barec{d_, stage(t->arec, t->arec_len)}, bx{d_, stage(t->x, t->x_len)}, by{d_, stage(t->y, t->y_len)}, brec{d_, stage(t->rec, t->rec_len)};
+  Buf by0{d_, (polish && !by.p) ? dev_vec<double>(d_, 1) : nullptr};            // (m = 0: a solve's y is a valid pointer that no kernel follows)
+  if (polish) { pr.p.x = bx.p; pr.p.y = by.p ? by.p : by0.p; pr.p.rec = brec.p; }
+  else {
+    LockstepAdjointParams &p = pr.a;
+    p.sx = bsx.p; p.sy = bsy.p; p.gx = bgx.p; p.gy = bgy.p; p.l = bl.p; p.u = bu.p;
+    p.dq = bdq.p; p.dl = bdl.p; p.du = bdu.p; p.dP = bdP.p; p.dA = bdA.p; p.arec = barec.p;
+  }
+  be::h2d(d_, block, t->ws, sizeof(double) * (size_t)need);
+  if (mat) be::h2d(d_, rt.mat_ws, t->mat_ws, sizeof(double) * (size_t)mneed);
+  if (polish) be::h2d(d_, lspw_, t->pol_ws, sizeof(double) * (size_t)t->pol_need);
+  be::sync(d_);
+  const int st = be::test_lockstep_back(d_, pr);
+  if (st != OSQP_NO_ERROR) return st;
+  be::d2h(d_, t->ws, block, sizeof(double) * (size_t)need);
+  if (mat) be::d2h(d_, t->mat_ws, rt.mat_ws, sizeof(double) * (size_t)mneed);
+  if (polish) be::d2h(d_, t->pol_ws, lspw_, sizeof(double) * (size_t)t->pol_need);
+  auto down = [&](double *dst, const double *src, long long len) { if (dst && src && len) be::d2h(d_, dst, src, sizeof(double) * (size_t)len); };
+  down(t->dq, bdq.p, t->dq_len); down(t->dl, bdl.p, t->dl_len); down(t->du, bdu.p, t->du_len); down(t->dP, bdP.p, t->dp_len); down(t->dA, bdA.p, t->da_len);
+  down(t->arec, barec.p, t->arec_len); down(t->x, bx.p, t->x_len); down(t->y, by.p, t->y_len); down(t->rec, brec.p, t->rec_len);
+  // ---- the scalars the references need
+  t->gain = pr.a.gain; t->min_steps = pr.a.min_steps; t->max_steps = pr.a.max_steps; t->rho0 = pr.a.rho0;
+  t->pol_rho = pr.p.pol_rho; t->pol_min_steps = pr.p.pol_min_steps; t->pol_max_steps = pr.pol_max_steps; t->check_dualgap = polish ? pr.p.check_dualgap : pr.a.check_dualgap;
+  t->adjoint_tol = kAdjointTol;
   return OSQP_NO_ERROR;
 }
 // A few ADMM iterations of the PCG path from the caller's iterates, through the handle's own launch path (include/osqp_hip.h osqp_hip_test_admm): every

@@ -1500,7 +1500,7 @@ constexpr LsPcgKernels kLsOwnMat = {k_lsm_load_n, k_lsm_load_m, k_lsm_minv, k_ls
 // ONE LAUNCH of a forward kernel of the PCG route, by its public name (include/osqp_hip.h OSQPHipLockstepOp): the kernel, its arguments and ITS GRID are
 // stated here once, for every driver below and for the diagnostic entry (test_lockstep), which therefore launches what a solve launches.  The grids: G
 // workgroups for the row passes and the elementwise kernels (k.w.G: lockstep_grid), the 64-wide tiles of n / m for the transposes, one workgroup for the
-// folds and the state.  (decide, the adjoint's, polish's and the direct route's own kernels are launched where they are used.)
+// folds and the state.  (decide is launched where it is used; the adjoint's and polish's kernels: ls_adj_go / ls_pol_go; the direct route's own: LwRun::go / lwa_go.)
 inline int ls_tiles(int cnt) { return (cnt + 63) / 64; }
 void ls_go(LsRun &R, const LsPcgKernels &K, int op, const LsK &k) {
   const int G = k.w.G, tn = ls_tiles(k.P.n), tm = ls_tiles(k.P.m);
@@ -1601,13 +1601,51 @@ void ls_mat_prepare(LsRun &R, const LsMK &km) {
   if (km.P.mat_stat) km.P.mat_stat[1] = (double)(R.launches - launches0);
 }
 
-// The adjoint's launches after the recurrence that both backward passes share: the outputs the caller asked for
-void ls_adjoint_outputs(LsRun &R, const LsAK &ka, int tn, int tm) {
+// ONE LAUNCH of a kernel of the backward pass, by its public name (include/osqp_hip.h OSQPHipLockstepBackOp): the kernel -- on the handle's matrices or, mat, its
+// twin on the chunk's own --, its arguments and ITS GRID are stated here once, for both backward passes and for the diagnostic entry (test_lockstep_back).
+// The grids: the 64-wide tiles of n / m for the transposes, G for the row passes and the elementwise kernel, one workgroup for the folds and the state, 64
+// stored entries per workgroup for the gradients.  ka: the argument view the caller's route gives the op (LwAdjViews on the direct route).
+void ls_adj_go(LsRun &R, bool mat, int op, const LsAK &ka) {
   const LockstepAdjointParams &p = ka.P;
-  if (p.dq) R.go(k_ls_adj_out_n, tn, ka);
-  if (p.m > 0 && (p.dl || p.du)) R.go(k_ls_adj_out_m, tm, ka);
-  if (p.dP && p.nzP > 0) R.go(k_ls_adj_grad<true>, (p.nzP + 63) / 64, ka);
-  if (p.dA && p.nzA > 0) R.go(k_ls_adj_grad<false>, (p.nzA + 63) / 64, ka);
+  const int G = ka.w.G, tn = ls_tiles(p.n), tm = ls_tiles(p.m);
+  switch (op) {
+    case OSQP_HIP_LSB_ADJ_LOAD_N: R.go(mat ? k_lsm_adj_load_n : k_ls_adj_load_n, tn, ka); break;
+    case OSQP_HIP_LSB_ADJ_LOAD_M: R.go(k_ls_adj_load_m, tm, ka); break;
+    case OSQP_HIP_LSB_ADJ_CLASS: R.go(mat ? k_lsm_adj_class : k_ls_adj_class, G, ka); break;
+    case OSQP_HIP_LSB_ADJ_INIT: R.go(k_ls_adj_init, 1, ka); break;
+    case OSQP_HIP_LSB_ADJ_DECIDE: R.go(k_ls_adj_decide, 1, ka); break;
+    case OSQP_HIP_LSB_ADJ_UNSCALE: R.go(mat ? k_lsm_adj_unscale : k_ls_adj_unscale, G, ka); break;
+    case OSQP_HIP_LSB_ADJ_RESM: R.go(mat ? k_lsm_adj_resm : k_ls_adj_resm, G, ka); break;
+    case OSQP_HIP_LSB_ADJ_RESN: R.go(mat ? k_lsm_adj_resn : k_ls_adj_resn, G, ka); break;
+    case OSQP_HIP_LSB_ADJ_FINAL: R.go(k_ls_adj_final, 1, ka); break;
+    case OSQP_HIP_LSB_ADJ_OUT_N: R.go(k_ls_adj_out_n, tn, ka); break;
+    case OSQP_HIP_LSB_ADJ_OUT_M: R.go(k_ls_adj_out_m, tm, ka); break;
+    case OSQP_HIP_LSB_ADJ_GRAD_P: R.go(k_ls_adj_grad<true>, (p.nzP + 63) / 64, ka); break;
+    case OSQP_HIP_LSB_ADJ_GRAD_A: R.go(k_ls_adj_grad<false>, (p.nzA + 63) / 64, ka); break;
+    default: throw std::logic_error("ls_adj_go: not a kernel of the backward pass");
+  }
+}
+// the same for polish: one workgroup for the state, the decisions and the accept test, G for the elementwise kernels and the row pass
+void ls_pol_go(LsRun &R, bool mat, int op, const LsPK &kq, double secs = 0.0) {
+  const int G = kq.w.G;
+  switch (op) {
+    case OSQP_HIP_LSB_POL_BEGIN: R.go(k_ls_pol_begin, 1, kq); break;
+    case OSQP_HIP_LSB_POL_CLASS: R.go(k_ls_pol_class, G, kq); break;
+    case OSQP_HIP_LSB_POL_DECIDE: R.go(k_ls_pol_decide, 1, kq); break;
+    case OSQP_HIP_LSB_POL_CONE: R.go(mat ? k_lsm_pol_cone : k_ls_pol_cone, G, kq); break;
+    case OSQP_HIP_LSB_POL_ACCEPT: R.go(mat ? k_lsm_pol_accept : k_ls_pol_accept, 1, kq); break;
+    case OSQP_HIP_LSB_POL_END: R.go(k_ls_pol_end, G, kq, secs); break;
+    default: throw std::logic_error("ls_pol_go: not a kernel of polish");
+  }
+}
+
+// The adjoint's launches after the recurrence that both backward passes share: the outputs the caller asked for
+void ls_adjoint_outputs(LsRun &R, bool mat, const LsAK &ka) {
+  const LockstepAdjointParams &p = ka.P;
+  if (p.dq) ls_adj_go(R, mat, OSQP_HIP_LSB_ADJ_OUT_N, ka);
+  if (p.m > 0 && (p.dl || p.du)) ls_adj_go(R, mat, OSQP_HIP_LSB_ADJ_OUT_M, ka);
+  if (p.dP && p.nzP > 0) ls_adj_go(R, mat, OSQP_HIP_LSB_ADJ_GRAD_P, ka);
+  if (p.dA && p.nzA > 0) ls_adj_go(R, mat, OSQP_HIP_LSB_ADJ_GRAD_A, ka);
 }
 
 // The direct route's kernel arguments and launch groups.  k: what k_lw_* take.  Of this file's other kernels kb sees the handle as it is, kv reads A
@@ -1663,6 +1701,16 @@ struct LwRun {
   }
   // x -> pg for another operand (the adjoint's and polish's own vectors)
   void prod(LsRun &R, const double *v, double *out) const { prod_to(R, v, out); }
+  // ONE LAUNCH of the two kernels the direct backward pass and the direct polish add (OSQPHipLockstepBackOp LWA_*): a wave per long row for k_lwa_setl -- into
+  // x or into x~ --, G for the zero start over n + r rows
+  void lwa_go(LsRun &R, int op) const {
+    switch (op) {
+      case OSQP_HIP_LSB_LWA_SETL_X: R.go(k_lwa_setl, (r + 3) / 4, k, k.w.x); break;
+      case OSQP_HIP_LSB_LWA_SETL_XS: R.go(k_lwa_setl, (r + 3) / 4, k, k.w.xs); break;
+      case OSQP_HIP_LSB_LWA_ZERO: R.go(k_lwa_zero, G, k); break;
+      default: throw std::logic_error("LwRun::lwa_go: not a kernel of the direct backward pass");
+    }
+  }
   // rho from rho_bar, D0, S and its inverse (for the problems whose rho has just been set)
   void factor(LsRun &R) const { go(R, OSQP_HIP_LS_SETRHO); go(R, OSQP_HIP_LS_D0); go(R, OSQP_HIP_LS_S); go(R, OSQP_HIP_LS_INV); }
   // x~ by the Woodbury formula, then the ADMM update
@@ -1673,6 +1721,15 @@ struct LwRun {
   void long_rows2(LsRun &R) const { go(R, OSQP_HIP_LS_PROD2); go(R, OSQP_HIP_LS_SETL0); }
   // the chunk's own dense rows and view values from the matrix block's scaled A (per-problem matrices; after ls_mat_prepare)
   void own_rows(LsRun &R) const { go(R, OSQP_HIP_LS_WT); go(R, OSQP_HIP_LS_VALS); }
+};
+// The direct backward pass's argument views, stated once for the driver and the diagnostic entry: kl makes k_ls_adj_load_n put x~ = Dinv x where
+// k_ls_adj_class, through the view (kc), will gather it -- the first n rows of the block vector x~ -- by exchanging the roles of p and x~ (the zeros then go
+// to p, which k_ls_rhs overwrites); k_ls_adj_resm reads A through the view too.  With per-problem matrices kc's A is the view on the chunk's per-lane values
+// ([nv][64]); E, Einv, D, Dinv are the block's in all three (ka.P after ls_mat_block).
+struct LwAdjViews {
+  LsAK ka, kl, kc;
+  LwAdjViews(const LsAK &a, const DevCsr &Av) : ka(a), kl(a), kc(a) { kl.w.p = a.w.xs; kl.w.xs = a.w.p; kc.P.A = Av; kc.w.p = a.w.xs; }
+  const LsAK &arg(int op) const { return op == OSQP_HIP_LSB_ADJ_LOAD_N ? kl : ((op == OSQP_HIP_LSB_ADJ_CLASS || op == OSQP_HIP_LSB_ADJ_RESM) ? kc : ka); }
 };
 
 }  // namespace
@@ -1693,7 +1750,6 @@ int lockstep_chunk(Dev &d, const LockstepParams &p, void *stream, double *stat) 
   if (mat) if (const int err = ls_mat_block(d, k.P, mt)) return err;
   if (pol && !lockstep_polish_layout(cp, n, m, kq.s)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   const LsWs &w = k.w;
-  const int G = w.G;
   const LsPcgKernels &K = mat ? kLsOwnMat : kLsShared;
   LsRun R(s, w.word, p.count);
   R.e0.record(s);
@@ -1737,22 +1793,22 @@ int lockstep_chunk(Dev &d, const LockstepParams &p, void *stream, double *stat) 
     LsK kp = k;                                        // what the ADMM's kernels take in the recurrence: alpha = 1, the recurrence's PCG rule
     kp.P.alpha = 1.0; kp.P.cg_max = p.pol_cg_max; kp.P.pcg_rel = p.pol_pcg_rel;
     R.ep0.record(s);
-    R.go(k_ls_pol_begin, 1, kq);
+    ls_pol_go(R, mat, OSQP_HIP_LSB_POL_BEGIN, kq);
     R.fetch();                                         // (WD_PCGSUM: still the ADMM's)
     pcg_admm = R.words[WD_PCGSUM]; pol_att = R.words[WD_LIVE];
     if (pol_att > 0) {
-      R.go(k_ls_pol_class, G, kq);
+      ls_pol_go(R, mat, OSQP_HIP_LSB_POL_CLASS, kq);
       if (m > 0) ls_go(R, K, OSQP_HIP_LS_SETRHO, kp);
       ls_go(R, K, OSQP_HIP_LS_MINV, kp);
       int cg_pol = 4;
-      pol_steps = ls_recurrence(R, K, kp, kp, kLsPolMaxSteps, [&]() { ls_pcg(R, K, kp, cg_pol); ls_go(R, K, OSQP_HIP_LS_UPD, kp); }, [&]() { R.go(k_ls_pol_decide, 1, kq); });
+      pol_steps = ls_recurrence(R, K, kp, kp, kLsPolMaxSteps, [&]() { ls_pcg(R, K, kp, cg_pol); ls_go(R, K, OSQP_HIP_LS_UPD, kp); }, [&]() { ls_pol_go(R, mat, OSQP_HIP_LSB_POL_DECIDE, kq); });
       pol_pcg = R.words[WD_PCGSUM];
-      if (m > 0) { R.go(mat ? k_lsm_pol_cone : k_ls_pol_cone, G, kq); ls_go(R, K, OSQP_HIP_LS_RESM, kp); }
+      if (m > 0) { ls_pol_go(R, mat, OSQP_HIP_LSB_POL_CONE, kq); ls_go(R, K, OSQP_HIP_LS_RESM, kp); }
       ls_go(R, K, OSQP_HIP_LS_RESN, kp);
       if (gap_check) ls_go(R, K, OSQP_HIP_LS_SUPP, kp);  // (the polished y against the bounds k_ls_pol_cone has put back: an accepted problem's column 11)
-      R.go(mat ? k_lsm_pol_accept : k_ls_pol_accept, 1, kq);
+      ls_pol_go(R, mat, OSQP_HIP_LSB_POL_ACCEPT, kq);
       R.fetch();
-      R.go(k_ls_pol_end, G, kq, ls_now() - t_pol);
+      ls_pol_go(R, mat, OSQP_HIP_LSB_POL_END, kq, ls_now() - t_pol);
     }
     R.ep1.record(s);
     pol_launches = R.launches - launches0;
@@ -1819,6 +1875,69 @@ int test_lockstep(Dev &d, const LsProbe &t) {
   return OSQP_NO_ERROR;
 }
 
+// Diagnostic (backend.h LsBackProbe; include/osqp_hip.h osqp_hip_test_lockstep_back, which has validated everything and uploaded the blocks): the carve of
+// the backward pass (lockstep_adjoint_chunk / lockstep_direct_adjoint_chunk) or of a polishing chunk (lockstep_chunk / lockstep_direct_chunk), then the
+// listed ops -- one launch each through ls_adj_go / ls_pol_go / LwRun::lwa_go with the drivers' argument views -- on the solver's stream.  No host loop.
+int test_lockstep_back(Dev &d, LsBackProbe &t) {
+  const hipStream_t s = ls_stream(d, nullptr);
+  const LockstepParams &base = t.polish ? static_cast<const LockstepParams &>(t.p) : static_cast<const LockstepParams &>(t.a);
+  const int n = base.n, m = base.m;
+  const bool mat = base.mat_ws != nullptr, direct = t.direct;
+  t.pol_max_steps = kLsPolMaxSteps;
+  LockstepDirectView v = t.polish ? t.p.v : t.a.v;
+  const int r = v.r;
+  if (direct && (r < 1 || r > kWbMaxRows || m < 1)) return OSQP_FUNC_NOT_IMPLEMENTED;
+  LsAK ka{t.a, {}, {}};
+  LockstepDirectParams p = t.p;
+  LockstepParams &P = t.polish ? static_cast<LockstepParams &>(p) : static_cast<LockstepParams &>(ka.P);      // (what ls_mat_block points at the matrix block)
+  LsWs w;
+  LwVecs x;
+  LsMat mt{};
+  LwMatVecs xm{};
+  LsPolWs pws{};
+  LsCursor c{base.ws}, cp{p.pol_ws};
+  if (!(direct ? lockstep_direct_layout(c, n, m, r, w, x, t.polish ? nullptr : &ka.a) : lockstep_layout(c, n, m, w, t.polish ? nullptr : &ka.a))) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (mat) {
+    if (direct && (!v.wtpos || !v.vsrc)) return OSQP_FUNC_NOT_IMPLEMENTED;
+    if (const int err = ls_mat_block(d, P, mt)) return err;
+    if (direct) {
+      LsCursor cm{P.mat_ws};
+      LsMatVecs again;
+      if (!lockstep_direct_mat_layout(cm, n, m, r, P.A.nnz, P.B.nnz, v.Av.nnz, again, xm)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+      v.WT = xm.WT; v.Av.val = xm.vval;
+    }
+  }
+  if (t.polish && !lockstep_polish_layout(cp, n, m, pws)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  ka.w = w;
+  p.v = v;
+  LsRun R(s, w.word, base.count);
+  auto lwa = [](int op) { return op >= OSQP_HIP_LSB_LWA_SETL_X && op <= OSQP_HIP_LSB_LWA_ZERO; };
+  if (!direct) {
+    const LsPK kq{p, w, pws};
+    for (int i = 0; i < t.nops; i++) {
+      if (t.polish) ls_pol_go(R, mat, t.ops[i], kq, t.secs); else ls_adj_go(R, mat, t.ops[i], ka);
+    }
+  } else if (t.polish) {                                 // lockstep_direct_chunk's polish: kq from the solve's own parameters (A through the view), the k_lwa launch from the alpha = 1 set
+    const LwRun D(p, p.v, w, x, mat);
+    const LsPK kq{D.kv.P, w, pws};
+    LockstepDirectParams pp = p;
+    pp.alpha = 1.0;
+    const LwRun Dp(pp, pp.v, w, x, mat);
+    for (int i = 0; i < t.nops; i++) {
+      if (lwa(t.ops[i])) Dp.lwa_go(R, t.ops[i]); else ls_pol_go(R, mat, t.ops[i], kq, t.secs);
+    }
+  } else {
+    const LwRun D(ka.P, v, w, x, mat);
+    const LwAdjViews V(ka, v.Av);
+    for (int i = 0; i < t.nops; i++) {
+      if (lwa(t.ops[i])) D.lwa_go(R, t.ops[i]); else ls_adj_go(R, mat, t.ops[i], V.arg(t.ops[i]));
+    }
+  }
+  HIP_CHECK(hipStreamSynchronize(s));
+  HIP_CHECK(hipGetLastError());
+  return OSQP_NO_ERROR;
+}
+
 // The backward pass of one chunk, from the transposes in to the transposes out, on `stream` (nullptr: the solver's); returns when the chunk's results are
 // there.  The work block is the forward's set followed by the adjoint's own vectors; after every step of the recurrence the host reads the word block
 // and ends the chunk when no problem is live.  stat: {recurrence steps of the slowest problem, PCG iterations summed, kernel launches, GPU ms}.
@@ -1830,7 +1949,7 @@ int test_lockstep(Dev &d, const LsProbe &t) {
 // forward's); no kernel of the backward pass writes them -- k_ls_adj_init sets the rows below SC_C it needs, the PCG's folds SC_RZ .. SC_BETA.
 int lockstep_adjoint_chunk(Dev &d, const LockstepAdjointParams &p, void *stream, double *stat) {
   const hipStream_t s = ls_stream(d, stream);
-  const int n = p.n, m = p.m, tn = ls_tiles(n), tm = ls_tiles(m);
+  const int n = p.n, m = p.m;
   const bool mat = p.mat_ws != nullptr;
   LsAK ka{p, {}, {}};
   LsMat mt{};
@@ -1838,25 +1957,24 @@ int lockstep_adjoint_chunk(Dev &d, const LockstepAdjointParams &p, void *stream,
   if (!lockstep_layout(c, n, m, ka.w, &ka.a)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   if (mat) if (const int err = ls_mat_block(d, ka.P, mt)) return err;
   const LsK k{ka.P, ka.w};                              // what the forward's kernels take: the base of the parameters, the same block vectors
-  const int G = k.w.G;
   const LsPcgKernels &K = mat ? kLsOwnMat : kLsShared;
   LsRun R(s, k.w.word, p.count);
   R.e0.record(s);
   if (mat) ls_mat_prepare(R, LsMK{k.P, k.w, mt});
 
-  R.go(mat ? k_lsm_adj_load_n : k_ls_adj_load_n, tn, ka);
-  if (m > 0) { R.go(k_ls_adj_load_m, tm, ka); R.go(mat ? k_lsm_adj_class : k_ls_adj_class, G, ka); }
-  R.go(k_ls_adj_init, 1, ka);
+  ls_adj_go(R, mat, OSQP_HIP_LSB_ADJ_LOAD_N, ka);
+  if (m > 0) { ls_adj_go(R, mat, OSQP_HIP_LSB_ADJ_LOAD_M, ka); ls_adj_go(R, mat, OSQP_HIP_LSB_ADJ_CLASS, ka); }
+  ls_adj_go(R, mat, OSQP_HIP_LSB_ADJ_INIT, ka);
   if (m > 0) ls_go(R, K, OSQP_HIP_LS_SETRHO, k);
   ls_go(R, K, OSQP_HIP_LS_MINV, k);
   R.fetch();
   int cg_est = 4;
-  const int step = ls_recurrence(R, K, k, k, p.max_steps, [&]() { ls_pcg(R, K, k, cg_est); ls_go(R, K, OSQP_HIP_LS_UPD, k); }, [&]() { R.go(k_ls_adj_decide, 1, ka); });
-  R.go(mat ? k_lsm_adj_unscale : k_ls_adj_unscale, G, ka);
-  if (m > 0) R.go(mat ? k_lsm_adj_resm : k_ls_adj_resm, G, ka);
-  R.go(mat ? k_lsm_adj_resn : k_ls_adj_resn, G, ka);
-  R.go(k_ls_adj_final, 1, ka);
-  ls_adjoint_outputs(R, ka, tn, tm);
+  const int step = ls_recurrence(R, K, k, k, p.max_steps, [&]() { ls_pcg(R, K, k, cg_est); ls_go(R, K, OSQP_HIP_LS_UPD, k); }, [&]() { ls_adj_go(R, mat, OSQP_HIP_LSB_ADJ_DECIDE, ka); });
+  ls_adj_go(R, mat, OSQP_HIP_LSB_ADJ_UNSCALE, ka);
+  if (m > 0) ls_adj_go(R, mat, OSQP_HIP_LSB_ADJ_RESM, ka);
+  ls_adj_go(R, mat, OSQP_HIP_LSB_ADJ_RESN, ka);
+  ls_adj_go(R, mat, OSQP_HIP_LSB_ADJ_FINAL, ka);
+  ls_adjoint_outputs(R, mat, ka);
   const int pcg_sum = R.words[WD_PCGSUM];
   const float ms = R.finish();
   if (mat && p.mat_stat) p.mat_stat[0] = LsRun::ms(R.e0, R.em);
@@ -1901,7 +2019,6 @@ int lockstep_direct_chunk(Dev &d, const LockstepDirectParams &p0, void *stream, 
   if (mat) D.own(mt.Aval, p.v, xm);
   const LsK &kb = D.kb, &kv = D.kv;
   const LsPcgKernels &K = D.K();
-  const int G = w.G;
   LsRun R(s, w.word, p.count);
   R.e0.record(s);
   if (mat) {
@@ -1954,23 +2071,23 @@ int lockstep_direct_chunk(Dev &d, const LockstepDirectParams &p0, void *stream, 
     pp.alpha = 1.0;
     const LwRun Dp(pp, pp.v, w, x, mat);
     R.ep0.record(s);
-    R.go(k_ls_pol_begin, 1, kq);
+    ls_pol_go(R, mat, OSQP_HIP_LSB_POL_BEGIN, kq);
     R.fetch();
     pol_att = R.words[WD_LIVE];
     if (pol_att > 0) {
-      R.go(k_ls_pol_class, G, kq);
+      ls_pol_go(R, mat, OSQP_HIP_LSB_POL_CLASS, kq);
       Dp.factor(R);
       pol_steps = ls_recurrence(R, K, Dp.kv, Dp.kb, kLsPolMaxSteps,
-                                [&]() { Dp.solve(R); if (p.pol_prod2) Dp.long_rows2(R); else Dp.long_rows(R, 0); }, [&]() { R.go(k_ls_pol_decide, 1, kq); });
+                                [&]() { Dp.solve(R); if (p.pol_prod2) Dp.long_rows2(R); else Dp.long_rows(R, 0); }, [&]() { ls_pol_go(R, mat, OSQP_HIP_LSB_POL_DECIDE, kq); });
       Dp.prod(R, w.x, x.pg);
-      R.go(k_lwa_setl, (r + 3) / 4, Dp.k, w.x);
-      R.go(mat ? k_lsm_pol_cone : k_ls_pol_cone, G, kq);
+      Dp.lwa_go(R, OSQP_HIP_LSB_LWA_SETL_X);
+      ls_pol_go(R, mat, OSQP_HIP_LSB_POL_CONE, kq);
       Dp.go(R, OSQP_HIP_LS_RESM);
       Dp.go(R, OSQP_HIP_LS_RESN);
       if (p.check_dualgap) Dp.go(R, OSQP_HIP_LS_SUPP);
-      R.go(mat ? k_lsm_pol_accept : k_ls_pol_accept, 1, kq);
+      ls_pol_go(R, mat, OSQP_HIP_LSB_POL_ACCEPT, kq);
       R.fetch();
-      R.go(k_ls_pol_end, G, kq, ls_now() - t_pol);
+      ls_pol_go(R, mat, OSQP_HIP_LSB_POL_END, kq, ls_now() - t_pol);
     }
     R.ep1.record(s);
     pol_launches = R.launches - launches0;
@@ -2018,7 +2135,7 @@ int lockstep_direct_chunk(Dev &d, const LockstepDirectParams &p0, void *stream, 
 // The block vectors x, x~, dx have n + r rows here; the preparation never uses them.
 int lockstep_direct_adjoint_chunk(Dev &d, const LockstepDirectAdjointParams &p, void *stream, double *stat) {
   const hipStream_t s = ls_stream(d, stream);
-  const int n = p.n, m = p.m, r = p.v.r, tn = ls_tiles(n), tm = ls_tiles(m);
+  const int n = p.n, m = p.m, r = p.v.r;
   const bool mat = p.mat_ws != nullptr;
   if (r < 1 || r > kWbMaxRows || m < 1) return OSQP_FUNC_NOT_IMPLEMENTED;
   LsAK ka{p, {}, {}};
@@ -2040,12 +2157,7 @@ int lockstep_direct_adjoint_chunk(Dev &d, const LockstepDirectAdjointParams &p, 
   LwRun D(ka.P, v, w, x, mat);
   if (mat) D.own(mt.Aval, v, xm);
   const LsPcgKernels &K = D.K();
-  const int G = w.G;
-  // the adjoint's own views: kl makes k_ls_adj_load_n put x~ = Dinv x where k_ls_adj_class, through the view (kc), will gather it -- the first n rows of the
-  // block vector x~ -- by exchanging the roles of p and x~ (the zeros then go to p, which k_ls_rhs overwrites).  With per-problem matrices kc's A is the view
-  // on the chunk's per-lane values ([nv][64]); E, Einv, D, Dinv are the block's in all three (ka.P after ls_mat_block).
-  LsAK kl = ka; kl.w.p = w.xs; kl.w.xs = w.p;
-  LsAK kc = ka; kc.P.A = v.Av; kc.w.p = w.xs;
+  const LwAdjViews V(ka, v.Av);                         // (which op takes which view: LwAdjViews)
   LsRun R(s, w.word, p.count);
   R.e0.record(s);
   if (mat) {
@@ -2054,24 +2166,25 @@ int lockstep_direct_adjoint_chunk(Dev &d, const LockstepDirectAdjointParams &p, 
     R.em.record(s);
     if (p.mat_stat) p.mat_stat[1] += 2;
   }
-  auto long_rows_of = [&](double *vec) { D.prod(R, vec, x.pg); R.go(k_lwa_setl, (r + 3) / 4, D.k, vec); };
+  auto long_rows_of = [&](double *vec, int setl) { D.prod(R, vec, x.pg); D.lwa_go(R, setl); };
+  auto adj = [&](int op) { ls_adj_go(R, mat, op, V.arg(op)); };
 
   HIP_CHECK(hipMemsetAsync(x.fact, 0, sizeof(int) * W, s));
-  R.go(mat ? k_lsm_adj_load_n : k_ls_adj_load_n, tn, kl);
-  R.go(k_ls_adj_load_m, tm, ka);
-  long_rows_of(w.xs);
-  R.go(mat ? k_lsm_adj_class : k_ls_adj_class, G, kc);
-  R.go(k_ls_adj_init, 1, ka);
-  R.go(k_lwa_zero, G, D.k);
+  adj(OSQP_HIP_LSB_ADJ_LOAD_N);
+  adj(OSQP_HIP_LSB_ADJ_LOAD_M);
+  long_rows_of(w.xs, OSQP_HIP_LSB_LWA_SETL_XS);
+  adj(OSQP_HIP_LSB_ADJ_CLASS);
+  adj(OSQP_HIP_LSB_ADJ_INIT);
+  D.lwa_go(R, OSQP_HIP_LSB_LWA_ZERO);
   D.factor(R);
   R.fetch();
-  const int step = ls_recurrence(R, K, D.kv, D.kb, p.max_steps, [&]() { D.solve(R); D.long_rows(R, 0); }, [&]() { R.go(k_ls_adj_decide, 1, ka); });
-  R.go(mat ? k_lsm_adj_unscale : k_ls_adj_unscale, G, ka);
-  long_rows_of(w.x);
-  R.go(mat ? k_lsm_adj_resm : k_ls_adj_resm, G, kc);
-  R.go(mat ? k_lsm_adj_resn : k_ls_adj_resn, G, ka);
-  R.go(k_ls_adj_final, 1, ka);
-  ls_adjoint_outputs(R, ka, tn, tm);
+  const int step = ls_recurrence(R, K, D.kv, D.kb, p.max_steps, [&]() { D.solve(R); D.long_rows(R, 0); }, [&]() { adj(OSQP_HIP_LSB_ADJ_DECIDE); });
+  adj(OSQP_HIP_LSB_ADJ_UNSCALE);
+  long_rows_of(w.x, OSQP_HIP_LSB_LWA_SETL_X);
+  adj(OSQP_HIP_LSB_ADJ_RESM);
+  adj(OSQP_HIP_LSB_ADJ_RESN);
+  adj(OSQP_HIP_LSB_ADJ_FINAL);
+  ls_adjoint_outputs(R, mat, ka);
   long nfact = 0;
   const float ms = R.finish(x.fact, &nfact);
   if (mat && p.mat_stat) p.mat_stat[0] = LsRun::ms(R.e0, R.em);

@@ -108,6 +108,26 @@ class LockstepTestStruct(C.Structure):    # OSQPHipLockstepTest, include/osqp_hi
                 [(k, C.c_int) for k in ('r', 'GC', 'cb', 'nv')] + [('dws_need', C.c_longlong), ('dmat_need', C.c_longlong)])
 
 
+LOCKSTEP_BACK_OPS = ('adj_load_n', 'adj_load_m', 'adj_class', 'adj_init', 'adj_decide', 'adj_unscale', 'adj_resm', 'adj_resn', 'adj_final', 'adj_out_n', 'adj_out_m',
+                     'adj_grad_p', 'adj_grad_a', 'lwa_setl_x', 'lwa_setl_xs', 'lwa_zero',
+                     'pol_begin', 'pol_class', 'pol_decide', 'pol_cone', 'pol_accept', 'pol_end')      # OSQPHipLockstepBackOp, in order
+LOCKSTEP_BACK_IN = ('sx', 'sy', 'gx', 'gy', 'l', 'u')                                                  # the arrays of OSQPHipLockstepBackTest, in order: in,
+LOCKSTEP_BACK_IO = ('dq', 'dl', 'du', 'dP', 'dA', 'arec', 'x', 'y', 'rec', 'ws', 'mat_ws', 'pol_ws')   # in and out
+LOCKSTEP_BACK_LENS = ('sx_len', 'sy_len', 'gx_len', 'gy_len', 'l_len', 'u_len', 'dq_len', 'dl_len', 'du_len', 'dp_len', 'da_len', 'arec_len', 'x_len', 'y_len', 'rec_len',
+                      'ws_len', 'mat_len', 'pol_len')
+LOCKSTEP_BACK_SIZES = ('n', 'm', 'nzP', 'nzA', 'G', 'r', 'ws_need', 'dws_need', 'adj_need', 'dadj_need', 'mat_need', 'dmat_need', 'pol_need')
+LOCKSTEP_BACK_SCALARS = ('min_steps', 'max_steps', 'pol_min_steps', 'pol_max_steps', 'check_dualgap', 'gain', 'rho0', 'pol_rho', 'adjoint_tol')
+
+
+class LockstepBackTestStruct(C.Structure):    # OSQPHipLockstepBackTest, include/osqp_hip.h (same order)
+    _fields_ = ([(k, C.c_int) for k in ('mode', 'route', 'mat', 'count', 'nops')] + [('ops', c_int_p), ('secs', C.c_double)] + [(k, C.c_longlong) for k in LOCKSTEP_BACK_LENS] +
+                [(k, c_double_p) for k in LOCKSTEP_BACK_IN + LOCKSTEP_BACK_IO] +
+                [(k, C.c_int) for k in ('n', 'm', 'nzP', 'nzA', 'G', 'r')] +
+                [(k, C.c_longlong) for k in ('ws_need', 'dws_need', 'adj_need', 'dadj_need', 'mat_need', 'dmat_need', 'pol_need')] +
+                [(k, C.c_int) for k in ('min_steps', 'max_steps', 'pol_min_steps', 'pol_max_steps', 'check_dualgap')] +
+                [(k, C.c_double) for k in ('gain', 'rho0', 'pol_rho', 'adjoint_tol')])
+
+
 ADMM_TEST_OUT = ('x', 'z', 'y', 'xt', 'zt', 'dx', 'dy', 'v', 't0', 'xg', 'rho', 'Minv', 'hist')      # the output arrays of OSQPHipAdmmTest, in order
 
 
@@ -189,6 +209,7 @@ PROTOTYPES = {
     'osqp_hip_test_band': (C.c_int, [SolverP, C.POINTER(BandTestStruct)]),
     'osqp_hip_test_woodbury': (C.c_int, [SolverP, C.POINTER(WoodburyTestStruct)]),
     'osqp_hip_test_lockstep': (C.c_int, [SolverP, C.POINTER(LockstepTestStruct)]),
+    'osqp_hip_test_lockstep_back': (C.c_int, [SolverP, C.POINTER(LockstepBackTestStruct)]),
     'osqp_hip_test_admm': (C.c_int, [SolverP, C.POINTER(AdmmTestStruct)]),
     'osqp_hip_test_boundary': (C.c_int, [SolverP, C.POINTER(BoundaryTestStruct)]),
     'osqp_hip_res_name': (C.c_char_p, [C.c_int]),

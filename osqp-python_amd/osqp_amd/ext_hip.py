@@ -521,6 +521,31 @@ class OSQPSolver:
         out.update(sz, c=float(t.c), x=out['x'].reshape(cz, n), y=out['y'].reshape(cz, m), rec=out['rec'].reshape(cz, self.BATCH_REC))
         return st, out
 
+    def hip_test_lockstep_back(self, ops, ws, mode='adjoint', mat_ws=None, pol_ws=None, count=64, route=0, secs=0.0, lens=None, **arrays):
+        """Single launches of the lockstep kernels of the backward pass (mode 'adjoint') and of polish (mode 'polish') on the caller's blocks
+        (osqp_hip_test_lockstep_back): ops = names of _lib.LOCKSTEP_BACK_OPS (or raw ints), one kernel launch each; ws: the whole adjoint work block, or the
+        forward block with pol_ws the whole polish block; mat_ws given: the per-problem-matrix twins.  arrays: sx sy gx gy l u (in), dq dl du dP dA arec
+        (adjoint, in and out), x y rec (polish), each (count, width) or None.  Every array is copied.  lens = {field: length} overrides a length as it is
+        passed (the entry validates).  Returns (status, dict): the blocks, the arrays, the sizes and, after a call that ran, the scalars of the mode."""
+        names = _lib.LOCKSTEP_BACK_IN + _lib.LOCKSTEP_BACK_IO
+        assert set(arrays) <= set(names), arrays.keys()
+        codes = np.array([_lib.LOCKSTEP_BACK_OPS.index(o) if isinstance(o, str) else int(o) for o in ops], dtype=np.int32)
+        f64 = lambda a: None if a is None else np.array(a, dtype=np.float64).ravel()
+        shapes = {k: np.shape(v) for k, v in arrays.items() if v is not None}
+        out = {k: f64(arrays.get(k)) for k in names}
+        out.update(ws=f64(ws), mat_ws=f64(mat_ws), pol_ws=f64(pol_ws))
+        ln = {k: (0 if out[a] is None else out[a].size) for k, a in zip(_lib.LOCKSTEP_BACK_LENS, names)}
+        ln.update(lens or {})
+        dp = _lib.c_double_p
+        t = _lib.LockstepBackTestStruct(int(mode == 'polish') if isinstance(mode, str) else int(mode), int(route), int(mat_ws is not None), int(count), codes.size,
+                                        _ptr(codes, _lib.c_int_p), float(secs), *[int(ln[k]) for k in _lib.LOCKSTEP_BACK_LENS], *[_ptr(out[k], dp) for k in names])
+        st = int(self._lib.osqp_hip_test_lockstep_back(self._p, C.byref(t)))
+        for k, shp in shapes.items():
+            out[k] = out[k].reshape(shp)
+        out.update({k: int(getattr(t, k)) for k in _lib.LOCKSTEP_BACK_SIZES})
+        out.update({k: getattr(t, k) for k in _lib.LOCKSTEP_BACK_SCALARS})
+        return st, out
+
     def hip_set_rho_eq_factor(self, factor):
         return self._lib.osqp_hip_set_rho_eq_factor(self._p, float(factor))
 

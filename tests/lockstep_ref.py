@@ -926,6 +926,43 @@ def _same(a, b):
     return a.shape == b.shape and np.array_equal(a.view(np.uint64) if a.dtype == np.float64 else a, b.view(np.uint64) if b.dtype == np.float64 else b)
 
 
+def compare(label, got, want, want64, k, exact, skip, problems):
+    """One output vector against THE BOUND, per lane (the last axis): the exact lanes bit for bit, the non-finite entries as they are, the finite ones by
+    err <= 64 max(e64, k 2^-53) scale (entries above 1e15 and the rest as two vectors).  Findings go to `problems`; returns the worst ratio."""
+    worst = 0.0
+    got2, want2, w642 = (np.atleast_2d(a) for a in (got, want, np.asarray(want64, np.float64)))
+    if skip is not None and got2.shape == want2.shape:
+        use = ~np.isin(np.arange(got2.shape[1]), skip)
+        got2, want2, w642 = got2[:, use], want2[:, use], w642[:, use]
+        exact = None if exact is None else exact[use]
+    if got2.shape != want2.shape:
+        problems.append('%s: shape %s, expected %s' % (label, got2.shape, want2.shape))
+        return worst
+    if want2.size == 0:                      # (m = 0: the m-side vectors are empty)
+        return worst
+    if exact is not None and exact.any():
+        g, w = got2[:, exact], want2[:, exact].astype(np.float64)
+        if not _same(np.ascontiguousarray(g), np.ascontiguousarray(w)):
+            problems.append('%s: exact lanes %s are not bit-equal' % (label, np.nonzero(exact)[0][np.nonzero((g != w).any(axis=0) & ~(np.isnan(g) & np.isnan(w)).all(axis=0))[0]][:8]))
+    fin = np.isfinite(want2)
+    odd = ~fin & ~((np.isnan(want2) & np.isnan(got2)) | (want2 == got2))
+    if odd.any():
+        problems.append('%s: %d non-finite entries differ (lanes %s)' % (label, odd.sum(), np.unique(np.nonzero(odd)[1])[:8]))
+    for cls in (fin & (np.abs(want2) > 1e15), fin & ~(np.abs(want2) > 1e15)):
+        with np.errstate(all='ignore'):
+            err = np.where(cls, np.abs(got2.astype(LD) - want2), 0).max(axis=0)
+            err = np.where(np.isnan(err), np.inf, err)
+            scale = np.where(cls, np.abs(want2), 0).max(axis=0)
+            e64 = np.where(cls & np.isfinite(w642), np.abs(w642.astype(LD) - want2), 0).max(axis=0)
+            bound = 64 * np.maximum(e64, max(k, 1) * U53 * scale)
+            ratio = np.where(err == 0, 0.0, np.where(bound > 0, err / np.where(bound > 0, bound, 1), np.inf)).astype(np.float64)
+        worst = max(worst, float(ratio.max()))
+        if (ratio > 1).any():
+            b = int(np.argmax(ratio))
+            problems.append('%s: ratio %.3g to the bound in lane %d (err %.3g, scale %.3g, k %d)' % (label, ratio[b], b, float(err[b]), float(scale[b]), k))
+    return worst
+
+
 def judge(op, H, b0, case, b1, io1, skip=None):
     """Everything about ONE launch: the listed outputs against the rule (-> worst ratio to the bound), the exact lanes bit for bit, and every other double
     and int of both blocks and of the caller's arrays bit-unchanged.  io1: {'x', 'y', 'rec'} after the call, (count, width).  skip: lanes whose VALUES are not judged (lanes that hold planted NaN / Inf / 1e308, where fp64
@@ -979,36 +1016,7 @@ def judge(op, H, b0, case, b1, io1, skip=None):
             got = got[:want.shape[0]] if got.ndim == 2 and want.ndim == 2 else got
             if got.ndim > 2:                                 # (pg, pg2: [block][row][lane]) -- a vector per lane all the same
                 got, want, r64[key] = got.reshape(-1, W), want.reshape(-1, W), (np.asarray(r64[key][0]).reshape(-1, W),) + tuple(r64[key][1:])
-        want64 = np.asarray(r64[key][0], np.float64)
-        got2, want2, w642 = (np.atleast_2d(a) for a in (got, want, want64))
-        if skip is not None and got2.shape == want2.shape:
-            use = ~np.isin(np.arange(got2.shape[1]), skip)
-            got2, want2, w642 = got2[:, use], want2[:, use], w642[:, use]
-            exact = None if exact is None else exact[use]
-        if got2.shape != want2.shape:
-            problems.append('%s %s: shape %s, expected %s' % (op, key, got2.shape, want2.shape)); continue
-        if want2.size == 0:                      # (m = 0: the m-side vectors are empty)
-            continue
-        if exact is not None and exact.any():
-            g, w = got2[:, exact], want2[:, exact].astype(np.float64)
-            if not _same(np.ascontiguousarray(g), np.ascontiguousarray(w)):
-                problems.append('%s %s: exact lanes %s are not bit-equal' % (op, key, np.nonzero(exact)[0][np.nonzero((g != w).any(axis=0) & ~(np.isnan(g) & np.isnan(w)).all(axis=0))[0]][:8]))
-        fin = np.isfinite(want2)
-        odd = ~fin & ~((np.isnan(want2) & np.isnan(got2)) | (want2 == got2))
-        if odd.any():
-            problems.append('%s %s: %d non-finite entries differ (lanes %s)' % (op, key, odd.sum(), np.unique(np.nonzero(odd)[1])[:8]))
-        for cls in (fin & (np.abs(want2) > 1e15), fin & ~(np.abs(want2) > 1e15)):
-            with np.errstate(all='ignore'):
-                err = np.where(cls, np.abs(got2.astype(LD) - want2), 0).max(axis=0)
-                err = np.where(np.isnan(err), np.inf, err)
-                scale = np.where(cls, np.abs(want2), 0).max(axis=0)
-                e64 = np.where(cls & np.isfinite(w642), np.abs(w642.astype(LD) - want2), 0).max(axis=0)
-                bound = 64 * np.maximum(e64, max(k, 1) * U53 * scale)
-                ratio = np.where(err == 0, 0.0, np.where(bound > 0, err / np.where(bound > 0, bound, 1), np.inf)).astype(np.float64)
-            worst = max(worst, float(ratio.max()))
-            if (ratio > 1).any():
-                b = int(np.argmax(ratio))
-                problems.append('%s %s: ratio %.3g to the bound in lane %d (err %.3g, scale %.3g, k %d)' % (op, key, ratio[b], b, float(err[b]), float(scale[b]), k))
+        worst = max(worst, compare('%s %s' % (op, key), got, want, r64[key][0], k, exact, skip, problems))
     # ---- everything else: bit-unchanged
     ir = lay.fwd['iw']
     touched[ir[0]:ir[0] + ir[1]] = True

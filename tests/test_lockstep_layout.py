@@ -118,6 +118,23 @@ def test_adjoint_vectors_start_at_the_forward_size_function(lib, which, forward)
         assert ranges[-1][1] == (m * W + 1) // 2                                  # m x 64 int32 codes
 
 
+@pytest.mark.parametrize('which', [ADJOINT, DIRECT_ADJOINT])
+def test_adjoint_carve_is_ax_gdx_rx_ay_gdy_ry_code_back_to_back(lib, which):
+    """lockstep_carve_adjoint as tests/lockstep_back_ref.py names it (ADJV): three n x 64 vectors, three m x 64 vectors, the packed int codes"""
+    for n, m, r in cases(which):
+        ranges, end, fits, _ = carve(lib, which, n, m, r)
+        adj = ranges[-7:]
+        assert [c for _, c in adj] == [n * W] * 3 + [m * W] * 3 + [(m * W + 1) // 2], (n, m, r)
+        assert all(o + c == o2 for (o, c), (o2, _) in zip(adj, adj[1:])) and sum(adj[-1]) == end <= size(lib, which, n, m, r)
+
+
+def test_polish_carve_is_x_y_z_l_u_back_to_back(lib):
+    """lockstep_carve_polish as tests/lockstep_back_ref.py names it (POLV): the saved x (n x 64), then y, z, l, u (m x 64 each), from offset 0"""
+    for n, m, _ in cases(POLISH):
+        ranges, end, fits, _ = carve(lib, POLISH, n, m)
+        assert ranges == [(0, n * W)] + [(n * W + k * m * W, m * W) for k in range(4)] and fits and end == W * (n + 4 * m) <= size(lib, POLISH, n, m)
+
+
 def test_scalar_state_sits_at_lockstep_sc_offset_and_c_in_its_row(lib):
     scal, c_row = lib.ll_const(2), lib.ll_const(4)
     for n, m in itertools.product(NS, MS):
