@@ -565,12 +565,17 @@ OSQPInt osqp_hip_batch_adjoint_device(OSQPSolver *solver, OSQPInt nbatch, const 
  * Return value of osqp_adjoint_derivative_compute on this route: OSQP_NO_ERROR with residual < OSQP_HIP_ADJOINT_TOL; OSQP_LINSYS_SOLVER_INIT_ERROR
  * when the recurrence stalled at or above it (status 3: dependent active rows -- the derivative is not defined, or was not reached) or when there are
  * more active rows than variables (status 2); _get_mat / _get_vec then answer OSQP_DATA_NOT_INITIALIZED.
- * NOT on this route: a handle whose PCG runs a Woodbury-corrected preconditioner (OSQPHipStats::woodbury_rows > 0; the portfolio one-launch form is
- * one of its modes) answers OSQP_FUNC_NOT_IMPLEMENTED -- the route changes the constraint classes on the device and does not keep the correction's
- * cached inverses and state consistent with them, as polish's host-side classification does; so does the host simulator.  osqp_hip_batch_adjoint[_device] keep their own eligibility.
+ * A handle whose PCG runs a Woodbury-corrected preconditioner (OSQPHipStats::woodbury_rows > 0; the portfolio one-launch form is one of its modes)
+ * answers OSQP_FUNC_NOT_IMPLEMENTED by default and takes this route with OSQPHipPolicy::adjoint_woodbury = 1 (OSQP_HIP_ADJOINT_WOODBURY): the
+ * correction is re-formed from the adjoint's classes and rho vector (a direct mode whose check or probe fails there runs as the PCG's preconditioner),
+ * the large form's inverse goes to a buffer of the call's own so that the solve's cached inverses stay alive, and everything of the correction a solve
+ * reads -- the direct-mode flag, the slot flag, rho_bar's key, the inverse in use and the cache table, the factorisation counters -- is put back; a
+ * Woodbury system that is not positive definite at the adjoint's rho ends the call with status 3 and the correction still on.  The host simulator
+ * answers OSQP_FUNC_NOT_IMPLEMENTED whatever the field says.  osqp_hip_batch_adjoint[_device] keep their own eligibility.
  * osqp_hip_adjoint_last_record: what the last osqp_adjoint_derivative_compute of the handle found, OSQP_HIP_ADJOINT_LAST_REC doubles
  *   {status (0 / 2 / 3 as above; the batch kernel's own codes on its route), active rows, residual, recurrence steps (0 on the batch route),
- *    seconds in the recurrence, seconds in the gradient kernels, seconds of the whole call, reserved};  all zero before the first call. */
+ *    seconds in the recurrence, seconds in the gradient kernels, seconds of the whole call, PCG iterations of the recurrence's linear solves (one per
+ *    step where a Woodbury direct mode is the solve; 0 on the batch route)};  all zero before the first call. */
 #define OSQP_HIP_ADJOINT_LAST_REC 8
 /* osqp_hip_adjoint_compute_at: osqp_adjoint_derivative_compute (either route) at a solution the CALLER holds -- x (n), y (m) of an earlier solve with the
  * data now on the handle.  The derivative depends on (P, A, l, u, x, y) only, so no OSQP_SOLVED solve on the current data is asked for; x = y = NULL
@@ -700,6 +705,10 @@ typedef struct {
                                  launch order from a previous call (measured, MPC batch, with a launch order: 4096 QPs 2.8 ms against 5.7, 2048 1.8 against
                                  3.0, 1280 1.7 against 1.9, 1024 1.7 against 1.6; without: 2048 3.5 against 3.6, 1536 3.5 against 3.1 -- below that a
                                  problem's own latency on one wave decides); 1: at every batch size; -1: never */
+  OSQPInt adjoint_woodbury;   /* 0 (default): a handle whose PCG runs a Woodbury-corrected preconditioner (OSQPHipStats::woodbury_rows > 0) answers
+                                 OSQP_FUNC_NOT_IMPLEMENTED to osqp_adjoint_derivative_compute / osqp_hip_adjoint_compute_at; 1: it takes the PCG route, with the
+                                 correction following the adjoint's constraint classes and its state saved and put back (Engine::adjoint_compute_pcg).  May be
+                                 set on a live handle; OSQP_HIP_ADJOINT_WOODBURY, anything but 0 = on */
 } OSQPHipPolicy;
 void    osqp_hip_default_policy(OSQPHipPolicy *policy);
 OSQPInt osqp_hip_set_policy(OSQPSolver *solver, const OSQPHipPolicy *policy);

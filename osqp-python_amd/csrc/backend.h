@@ -27,6 +27,7 @@ namespace osqp_hip {
 // A failed HIP runtime call.  Thrown by the backend, caught at the C-API boundary (api.cpp) and reported as an
 // osqp_error_type value -- the library never calls abort() and never falls back to a CPU path.
 struct DeviceError : std::runtime_error { using std::runtime_error::runtime_error; };
+struct NotPositiveDefinite : DeviceError { using DeviceError::DeviceError; };      // be::precond: the Woodbury system at this rho vector has no positive definite factorisation (the device itself is fine)
 
 #ifndef OSQP_HIP_KBLOCK
 #define OSQP_HIP_KBLOCK 256

@@ -30,7 +30,7 @@ void policy_from_env(OSQPHipPolicy &p, bool runtime_only) {
   auto num = [](const char *name, OSQPInt &v) { if (const char *e = std::getenv(name)) v = std::atoi(e); };
   auto real = [](const char *name, OSQPFloat &v) { if (const char *e = std::getenv(name)) v = std::atof(e); };
   on("OSQP_HIP_SMALL_DIRECT", p.small_direct); num("OSQP_HIP_DEVICE_DRIVEN", p.device_driven); on("OSQP_HIP_BATCH_REORDER", p.batch_reorder);
-  num("OSQP_HIP_BATCH_WAVE", p.batch_wave);
+  num("OSQP_HIP_BATCH_WAVE", p.batch_wave); on("OSQP_HIP_ADJOINT_WOODBURY", p.adjoint_woodbury);
   num("OSQP_HIP_RHO_WINDOW", p.rho_window); real("OSQP_HIP_RHO_WINDOW_TOL", p.rho_window_tol); on("OSQP_HIP_RHO_PERSIST", p.rho_persist);
   if (const char *e = std::getenv("OSQP_HIP_RHO_TOL_EXP")) { const double v = std::atof(e); p.rho_tol_exp = v > 0 && v <= 1 ? v : 0.5; }
   real("OSQP_HIP_BUDGET_TOLERATE", p.budget_tolerate); real("OSQP_HIP_BUDGET_SIGMA", p.budget_sigma); num("OSQP_HIP_BUDGET_SLACK", p.budget_slack);
@@ -69,7 +69,7 @@ void Engine::default_policy(OSQPHipPolicy *p) {
   p->polish_delta_floor = 1e-3; p->polish_pcg_tol = 1e-15; p->woodbury = 1; p->woodbury_direct = 1; p->woodbury_large = 1; p->woodbury_cache = 1;
   p->slot_poll = 1; p->poll_low = 6; p->poll_first = 0.8; p->poll_frac = 0.75; p->poll_wait = 0.7;
   p->finish_pairs = 12; p->poll_sleep_us = 30;
-  p->reorder = 1; p->kform = 0; p->woodbury_dual = 1; p->woodbury_vendor = 0; p->woodbury_fused = 1; p->woodbury_direct_tol = 1e-6; p->debug_fail_refactor = 0; p->batch_wave = 0;
+  p->reorder = 1; p->kform = 0; p->woodbury_dual = 1; p->woodbury_vendor = 0; p->woodbury_fused = 1; p->woodbury_direct_tol = 1e-6; p->debug_fail_refactor = 0; p->batch_wave = 0; p->adjoint_woodbury = 0;
 }
 void Engine::set_default_policy(const OSQPHipPolicy *p) {
   g_default_policy_set = p != nullptr;
@@ -156,6 +156,7 @@ void Engine::free_all() {
   if (bmat_) { be::dfree(d_, bmat_); bmat_ = nullptr; bmat_cap_ = 0; }
   if (abuf_) { be::dfree(d_, abuf_); abuf_ = nullptr; abuf_cap_ = 0; }
   if (adjw_) { be::dfree(d_, adjw_); adjw_ = nullptr; adjw_cap_ = 0; }
+  if (adj_sinv_) { be::dfree(d_, adj_sinv_); adj_sinv_ = nullptr; adj_sinv_cap_ = 0; }
   adj_ok_ = false;
   if (d_batch_order_) { be::dfree(d_, d_batch_order_); d_batch_order_ = nullptr; batch_order_cap_ = 0; }
   if (d_batch_iters_) { be::dfree(d_, d_batch_iters_); d_batch_iters_ = nullptr; d_batch_iters_n_ = 0; }
@@ -955,11 +956,12 @@ int Engine::run_recurrence(const RecurrenceRule &rule, double *res) {
   int flags[F_COUNT];
   double best = std::numeric_limits<double>::infinity();
   int worse = 0, steps = 0;
+  recurrence_pcg_ = 0;
   const int min_steps = 1 + std::max(0, settings.polish_refine_iter);
   for (int s = 0; s < kRecurrenceMaxSteps; s++) {
     be::set_pcg_tol(d_, pol_.polish_pcg_tol, 1e-15);  // ||r|| <= polish_pcg_tol ||rhs||
     exec_chunk_sync(1, kMaxCg, true, 1, res, flags);
-    steps = s + 1;
+    steps = s + 1; recurrence_pcg_ += flags[F_STAT_SUM];
     // residuals of the reduced KKT system: Aa x - ba (active rows) and P x + q + Aa' ya, in the scaled space
     const double err = rhs_norm ? recurrence_err_rhs(res[R_PRI_S], res[R_DUA_S], res[R_QN_S], res[R_Z_S])
                                 : recurrence_err_polish(res[R_PRI_S], res[R_AX_S], res[R_Z_S], res[R_DUA_S], res[R_ATY_S], res[R_PX_S], res[R_QN_S]);

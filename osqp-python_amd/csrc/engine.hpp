@@ -199,6 +199,17 @@ class Engine {
   bool adjoint_pcg_applicable() const;
   int adjoint_compute_pcg(const double *x, const double *y, const double *dx, const double *dy);
   double *adjw_ = nullptr; size_t adjw_cap_ = 0;      // its device scratch (saved state, inputs, results), kept across calls
+  // ... on a handle with a Woodbury-corrected preconditioner (OSQPHipPolicy::adjoint_woodbury): what of DevWb / DevWbx a solve reads and the call may
+  // change -- the direct-mode flag (a failed check of S^-1 clears it for good), the slot flag, rho_bar's key, the inverse in use and the large form's
+  // cache table.  Every device array of the correction is either a function of (matrices, rho vector) that be::precond re-forms, or lives within one
+  // chunk.  The large form factorises the adjoint's system into a buffer of the call's own (adj_sinv_, kept across calls), so
+  // that the solve's cached inverses stay alive and putting rho back is a look-up.
+  struct WbSave { int exact, slots; double rho_key; double *Sinv; double *cache_buf[DevWb::kCache]; double cache_rho[DevWb::kCache]; int cache_used, cache_next, cache_hits; };
+  void wb_save(WbSave &s) const;
+  void wb_enter_adjoint();                            // large form: the cache table shows one free buffer, adj_sinv_, and no entry
+  void wb_restore_state(const WbSave &s);             // before recurrence_restore_rho: flags, the inverse in use, the cache table
+  void wb_restore_keys(const WbSave &s);              // after it: what its set_rho / look-up moved on (rho_key, cache_hits, cache_next)
+  double *adj_sinv_ = nullptr; size_t adj_sinv_cap_ = 0;
   double adj_rec_[OSQP_HIP_ADJOINT_LAST_REC] = {0, 0, 0, 0, 0, 0, 0, 0};      // record of the last adjoint_compute (include/osqp_hip.h osqp_hip_adjoint_last_record)
   int *d_batch_iters_ = nullptr; int d_batch_iters_n_ = 0;      // device-pointer path: iteration counts of the previous call (its records never reach the host)
   std::vector<int> batch_order_; int *d_batch_order_ = nullptr; size_t batch_order_cap_ = 0;   // problems by descending iteration count of the previous batch call
@@ -312,6 +323,7 @@ class Engine {
   void recurrence_save(RecurrenceSave &s) const;
   struct RecurrenceRule { bool rhs_norm; double gain; int max_steps; };
   int run_recurrence(const RecurrenceRule &rule, double *res);
+  double recurrence_pcg_ = 0;                  // PCG iterations of the last run_recurrence, all steps (the call's statistics are restored: this is what is left of them)
   void recurrence_restore_launch(const RecurrenceSave &s);
   void recurrence_restore_rho(const RecurrenceSave &s);
   void apply_scaled_bounds(const std::vector<double> &ls, const std::vector<double> &us);

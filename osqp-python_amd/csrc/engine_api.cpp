@@ -1309,12 +1309,40 @@ int Engine::batch_adjoint_device(int nbatch, const double *Px, const double *Ax,
 }
 
 // The PCG path's adjoint (adjoint_hip.hip) holds every handle whose solve runs the multi-kernel PCG form with a Jacobi-family preconditioner.  A handle
-// with a Woodbury-corrected preconditioner (dense rows; the portfolio one-launch form is one of its modes) is left out.  polish runs the same
-// recurrence there, but through the host classification (classify_constraints), which also invalidates the cached Woodbury inverses when the
-// classes change; this route changes the classes on the device, past that bookkeeping, and saves / restores none of DevWb's state.  Not built, not
-// measured: OSQP_FUNC_NOT_IMPLEMENTED.
+// with a Woodbury-corrected preconditioner (dense rows; the portfolio one-launch form is one of its modes) is taken with OSQPHipPolicy::adjoint_woodbury
+// only: the route changes the constraint classes on the device, past the host classification that keeps the correction's bookkeeping in step for
+// polish, so adjoint_compute_pcg saves and restores that bookkeeping itself (WbSave below).  The default stays OSQP_FUNC_NOT_IMPLEMENTED.
 bool Engine::adjoint_pcg_applicable() const {
-  return be::adjoint_load && be::adjoint_residual && be::adjoint_gradients && be::device_assembly() && be::device_vec_updates() && !d_.wb.on;
+  return be::adjoint_load && be::adjoint_residual && be::adjoint_gradients && be::device_assembly() && be::device_vec_updates() && (!d_.wb.on || pol_.adjoint_woodbury != 0);
+}
+
+void Engine::wb_save(WbSave &s) const {
+  const DevWb &w = d_.wb;
+  s.exact = w.exact; s.slots = w.x.slots; s.rho_key = w.rho_key; s.Sinv = w.Sinv;
+  for (int k = 0; k < DevWb::kCache; k++) { s.cache_buf[k] = w.cache_buf[k]; s.cache_rho[k] = w.cache_rho[k]; }
+  s.cache_used = w.cache_used; s.cache_next = w.cache_next; s.cache_hits = w.cache_hits;
+}
+// Large form: the adjoint's classes give another rho vector under a rho_bar the handle may have seen, so no cached inverse may be looked up (with the
+// probe off nothing would notice), and the factorisation must not evict the inverse the solve is using.  For the length of the recurrence the table
+// holds one free buffer of the call's own and no entry.
+void Engine::wb_enter_adjoint() {
+  DevWb &w = d_.wb;
+  if (!w.large) return;
+  const size_t ord = w.dual ? (size_t)w.cd : (size_t)w.r, need = ord * ord;
+  if (need > adj_sinv_cap_) { if (adj_sinv_) be::dfree(d_, adj_sinv_); adj_sinv_cap_ = 0; adj_sinv_ = dev_vec<double>(d_, need); adj_sinv_cap_ = need; }
+  w.cache_buf[0] = adj_sinv_; w.cache_rho[0] = -1.0;
+  for (int k = 1; k < DevWb::kCache; k++) { w.cache_buf[k] = nullptr; w.cache_rho[k] = -1.0; }
+  w.cache_used = 1; w.cache_next = 0;
+}
+void Engine::wb_restore_state(const WbSave &s) {
+  DevWb &w = d_.wb;
+  w.exact = s.exact; w.x.slots = s.slots; w.Sinv = s.Sinv;
+  for (int k = 0; k < DevWb::kCache; k++) { w.cache_buf[k] = s.cache_buf[k]; w.cache_rho[k] = s.cache_rho[k]; }
+  w.cache_used = s.cache_used; w.cache_next = s.cache_next;
+}
+void Engine::wb_restore_keys(const WbSave &s) {
+  DevWb &w = d_.wb;
+  w.rho_key = s.rho_key; w.cache_hits = s.cache_hits; w.cache_next = s.cache_next;
 }
 
 // osqp_adjoint_derivative_compute: needs the solution of a solve that ended OSQP_SOLVED on the current data (every data update resets the status);
@@ -1352,6 +1380,11 @@ int Engine::adjoint_compute_at(const double *x, const double *y, const double *d
 // zero start, unscale, evaluate the unregularised residual, run the gradient kernels.  Everything the recurrence touches -- q, the bounds and
 // classes, the iterates and the PCG's starting vectors, rho, alpha, the predictions and statistics -- is saved first and put back bit for bit: a
 // solve after this call runs as if the call had not been made.  info, solution and the history feed are never written.
+// On a handle with a Woodbury-corrected preconditioner (wb): run_recurrence's set_rho + precond re-form D0, the weights and S (or T) from the device
+// rho vector of the adjoint's classes, in every mode; a direct mode whose check (small form) or probe (large form) does not hold there -- the lasso's
+// row pairs lose their equal weights -- runs as the PCG's preconditioner.  WbSave is put back around recurrence_restore_rho, which re-forms the
+// correction at the solve's rho: launches in the small form, a look-up of the solve's own cached inverse in the large form (a second factorisation
+// where the cache is off).  A Woodbury system that is not positive definite at the adjoint's rho ends the call with status 3, the correction kept.
 int Engine::adjoint_compute_pcg(const double *x, const double *y, const double *dx, const double *dy) {
   const double t_begin = now_s();
   be::ext_wait(d_);
@@ -1383,20 +1416,26 @@ int Engine::adjoint_compute_pcg(const double *x, const double *y, const double *
   const OSQPInfo info0 = info;
   RecurrenceSave keep;
   recurrence_save(keep);
+  const bool wb = d_.wb.on != 0;
+  WbSave wkeep{};
+  if (wb) wb_save(wkeep);
   auto put_back = [&]() {
     recurrence_restore_launch(keep);
     for (const Kept &k : kept) if (k.dev == d_.l || k.dev == d_.u || k.dev == reinterpret_cast<double *>(d_.ctype)) be::copy_in(d_, k.dev, k.copy, k.bytes, 1);
     d_.rho_eq_factor = keep.eq_factor;
+    if (wb) wb_restore_state(wkeep);
     recurrence_restore_rho(keep);                   // rho, the preconditioner (and K's values) from the solve's classes again ...
+    if (wb) wb_restore_keys(wkeep);
     for (const Kept &k : kept) be::copy_in(d_, k.dev, k.copy, k.bytes, 1);      // ... then every vector as the solve left it (set_rho rewrites v, t0 and the PCG's start)
     info = info0;
     be::sync(d_);
   };
   double rec[kAdjointPcgRec] = {0, 0, 0, 0};
   int steps = 0;
-  double t_rec = 0, t_grad = 0;
-  bool singular = false;
+  double t_rec = 0, t_grad = 0, pcg = 0;
+  bool singular = false, not_spd = false;
   try {
+    if (wb) wb_enter_adjoint();
     be::adjoint_load(d_, a);
     be::d2h(d_, rec, o_rec, sizeof(double));
     singular = rec[0] > (double)n;                  // more active rows than variables: K_a is singular, nothing to iterate on
@@ -1407,6 +1446,7 @@ int Engine::adjoint_compute_pcg(const double *x, const double *y, const double *
       // cap (under polish's rule the n = 100k banded QP with a random dy ended at 3.2e-5 after 12 steps; with this one at 5.4e-10 after 23:
       // DESIGN.md section 6)
       steps = run_recurrence(RecurrenceRule{true, 0.9, 60}, res);
+      pcg = recurrence_pcg_;
       t_rec = now_s() - t0;
       be::adjoint_residual(d_, a);
       be::sync(d_);
@@ -1416,11 +1456,14 @@ int Engine::adjoint_compute_pcg(const double *x, const double *y, const double *
       t_grad = now_s() - t1;
       be::d2h(d_, rec, o_rec, sizeof(double) * kAdjointPcgRec);
     }
+  } catch (const NotPositiveDefinite &) {           // the correction at the adjoint's rho vector: the handle keeps it for its solves, the call reports "not solved"
+    if (!wb) { put_back(); throw; }
+    not_spd = true;
   } catch (...) {
     put_back();
     throw;
   }
-  const double resid = singular ? INFINITY : (rec[2] > 0.0 ? rec[1] / rec[2] : (rec[1] > 0.0 ? INFINITY : 0.0));
+  const double resid = (singular || not_spd) ? INFINITY : (rec[2] > 0.0 ? rec[1] / rec[2] : (rec[1] > 0.0 ? INFINITY : 0.0));
   const int status = singular ? 2 : (resid < kAdjointTol ? 0 : 3);
   if (status == 0) {
     std::vector<double> t;
@@ -1446,7 +1489,7 @@ int Engine::adjoint_compute_pcg(const double *x, const double *y, const double *
   }
   put_back();
   adj_rec_[0] = status; adj_rec_[1] = rec[0]; adj_rec_[2] = resid; adj_rec_[3] = steps;
-  adj_rec_[4] = t_rec; adj_rec_[5] = t_grad; adj_rec_[6] = now_s() - t_begin;
+  adj_rec_[4] = t_rec; adj_rec_[5] = t_grad; adj_rec_[6] = now_s() - t_begin; adj_rec_[7] = pcg;
   adj_ok_ = status == 0;
   return adj_ok_ ? OSQP_NO_ERROR : OSQP_LINSYS_SOLVER_INIT_ERROR;
 }

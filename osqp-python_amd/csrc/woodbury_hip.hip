@@ -775,7 +775,7 @@ static void wb_factor_large(Dev &d) {
   HIP_CHECK(hipMemcpyAsync(info, w.info, sizeof(info), hipMemcpyDeviceToHost, st(d)));
   HIP_CHECK(hipMemcpyAsync(chk, out, sizeof(double) * (w.probe ? 4 : 2), hipMemcpyDeviceToHost, st(d)));
   HIP_CHECK(hipStreamSynchronize(st(d)));
-  if (info[0] != 0 || info[1] != 0 || !(piv > 0.0)) throw DeviceError("osqp_hip: the Woodbury system of the preconditioner is not positive definite");
+  if (info[0] != 0 || info[1] != 0 || !(piv > 0.0)) throw NotPositiveDefinite("osqp_hip: the Woodbury system of the preconditioner is not positive definite");
   const bool inv_ok = chk[0] <= 1e-8 * chk[1];
   w.exact = (w.probe && inv_ok && chk[2] <= w.exact_tol * chk[3]) ? 1 : 0;
   if (inv_ok) for (int k = 0; k < w.cache_used; k++) if (w.cache_buf[k] == w.Sinv) w.cache_rho[k] = w.rho_key;      // (the entry is valid from here on)
@@ -809,7 +809,7 @@ void wb_factor(Dev &d) {
   int ok = 0;
   HIP_CHECK(hipMemcpyAsync(&ok, w.info, sizeof(int), hipMemcpyDeviceToHost, st(d)));
   HIP_CHECK(hipStreamSynchronize(st(d)));
-  if (ok < 0) throw DeviceError("osqp_hip: the Woodbury system of the preconditioner is not positive definite");
+  if (ok < 0) throw NotPositiveDefinite("osqp_hip: the Woodbury system of the preconditioner is not positive definite");
   if (ok != 1) w.exact = 0;                                   // the direct mode trusts S^-1: || S S^-1 - I ||_max must be at rounding level
 }
 

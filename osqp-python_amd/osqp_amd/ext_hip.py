@@ -252,7 +252,7 @@ class OSQPSolver:
         return self._lib.osqp_hip_adjoint_compute_at(self._p, _ptr(x, dp), _ptr(y, dp), _ptr(dx, dp), _ptr(dy, dp))
 
     # OSQP_HIP_ADJOINT_LAST_REC doubles of osqp_hip_adjoint_last_record
-    ADJOINT_LAST_FIELDS = ('status', 'active_rows', 'residual', 'steps', 'recurrence_s', 'gradient_s', 'total_s', 'reserved')
+    ADJOINT_LAST_FIELDS = ('status', 'active_rows', 'residual', 'steps', 'recurrence_s', 'gradient_s', 'total_s', 'pcg_iters')
 
     def adjoint_last_record(self):
         """osqp_hip_adjoint_last_record as a dict (ADJOINT_LAST_FIELDS): what the last adjoint_derivative_compute of this handle found."""
@@ -261,7 +261,7 @@ class OSQPSolver:
         if st:
             raise ValueError(str(int(st)))
         out = dict(zip(self.ADJOINT_LAST_FIELDS, rec.tolist()))
-        for k in ('status', 'active_rows', 'steps'):
+        for k in ('status', 'active_rows', 'steps', 'pcg_iters'):
             out[k] = int(out[k])
         return out
 

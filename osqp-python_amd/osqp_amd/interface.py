@@ -291,12 +291,13 @@ class OSQP:
     def _adjoint_status(self, status):
         if status == SolverError.OSQP_FUNC_NOT_IMPLEMENTED:
             raise NotImplementedError('adjoint derivatives are not available on this handle: its PCG runs a Woodbury-corrected preconditioner '
-                                      '(dense rows), which neither the batch kernel nor the PCG route of the adjoint holds -- or the backend has no adjoint kernels')
+                                      '(dense rows), which the batch kernel does not hold and the PCG route of the adjoint takes only with '
+                                      's._solver.set_policy(adjoint_woodbury=1) or OSQP_HIP_ADJOINT_WOODBURY=1 -- or the backend has no adjoint kernels')
         if status:
             raise OSQPException(int(status))
 
     def adjoint_last_record(self):
-        """What the last adjoint_derivative_compute found: dict(status, active_rows, residual, steps, recurrence_s, gradient_s, total_s, reserved)."""
+        """What the last adjoint_derivative_compute found: dict(status, active_rows, residual, steps, recurrence_s, gradient_s, total_s, pcg_iters)."""
         return self._solver.adjoint_last_record()
 
     def adjoint_derivative_compute(self, dx=None, dy=None):

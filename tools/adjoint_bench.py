@@ -3,6 +3,7 @@ stream, after a warm-up, over several repetitions; median and spread reported).
 
     python tools/adjoint_bench.py [--batch 4096] [--reps 20] [--warmup 5] [--out profiles/NAME.json]
     python tools/adjoint_bench.py --single [--n 100000] [--eps 1e-8] [--reps 20] [--warmup 5] [--out profiles/NAME.json]      (see single())
+    python tools/adjoint_bench.py --single --woodbury [--eps 1e-8] [--reps 5] [--warmup 1] [--only TEXT] [--out profiles/NAME.json]      (see woodbury())
 
 forward  = osqp_hip_batch_solve_device (every solve launch of the batch);  backward = osqp_hip_batch_adjoint_device (ONE launch: k_batch_adjoint)
 with all five gradients, and with dq alone (what the dP / dA stores of nbatch x (nnz(P) + nnz(A)) doubles cost).  One JSON line."""
@@ -61,6 +62,88 @@ def single(a):
             f.write(text + '\n')
 
 
+def woodbury(a):
+    """--single --woodbury: the backward of ONE QP whose linear solve runs the Woodbury-corrected preconditioner (OSQPHipPolicy::adjoint_woodbury = 1):
+    the four problems of tests/test_gpu_adjoint_woodbury.py and BASELINE configs[2] / configs[3] at full size, the lasso also with the inverse cache
+    off (putting rho back is then a second factorisation instead of a look-up).  Per problem: the mode, one cold solve of the handle (wall time of
+    its first solve), then osqp_adjoint_derivative_compute with a random dy -- wall time per call, median over --reps after --warmup -- with the
+    record's split (recurrence, gradient kernels), the recurrence's steps and its PCG iterations per step.  One JSON object, a list under "problems"."""
+    import time
+    import scipy.sparse as spa
+    import osqp_amd
+    import problems
+
+    def banded_dense():
+        P, q, A, l, u = problems.banded_qp(3000, window=30)
+        rng = np.random.default_rng(1)
+        dense = spa.random(6, 3000, density=0.3, random_state=rng, data_rvs=rng.standard_normal, format='csc')
+        x0 = 0.1 * rng.standard_normal(3000)
+        half = np.array([1.0, 1.0, 1.0, 1e3, 1e3, 1e3])
+        return P, q, spa.vstack([A, dense], format='csc'), np.concatenate([l, dense @ x0 - half]), np.concatenate([u, dense @ x0 + half])
+    full = []
+
+    def lasso_full():                                  # (generated once: 50 M entries)
+        if not full:
+            full.append(problems.lasso_qp(5000, 10000))
+        return full[0]
+    cases = [('portfolio_qp(600, 4)', lambda: problems.portfolio_qp(600, 4), {}), ('portfolio_qp(2000, 20)', lambda: problems.portfolio_qp(2000, 20), {}),
+             ('lasso_qp(300, 600)', lambda: problems.lasso_qp(300, 600), {}), ('banded_qp(3000, window=30) + 6 dense rows', banded_dense, {}),
+             ('configs[3] portfolio_qp(10000, 100)', lambda: problems.portfolio_qp(10000, 100), {}),
+             ('configs[2] lasso_qp(5000, 10000)', lambda: lasso_full(), {}),
+             ('configs[2] lasso_qp(5000, 10000), inverse cache off', lambda: lasso_full(), {'OSQP_HIP_WOODBURY_CACHE': '0'})]
+    if a.only:
+        cases = [c for c in cases if a.only in c[0]]
+    os.environ['OSQP_HIP_SMALL_DIRECT'] = '0'
+    med = lambda v: float(np.median(v))
+    out = []
+    for name, make, env in cases:
+        P, q, A, l, u = make()
+        n, m = len(q), len(l)
+        os.environ.update(env)
+        try:
+            s = osqp_amd.OSQP(algebra='hip')
+            s.setup(P, q, A, l, u, eps_abs=a.eps, eps_rel=a.eps, verbose=False, max_iter=200000)
+        finally:
+            for k in env:
+                os.environ.pop(k)
+        s._solver.set_policy(adjoint_woodbury=1)
+        t0 = time.perf_counter()
+        r = s.solve()
+        cold = time.perf_counter() - t0
+        st = s._solver.hip_stats()
+        assert r.info.status_val == osqp_amd.SolverStatus.OSQP_SOLVED and st['woodbury_rows'] > 0
+        rng = np.random.default_rng(7)
+        dx, dy = r.x - 0.1 * rng.standard_normal(n), rng.standard_normal(m)
+        tot, rec_s, grad_s, rec, err = [], [], [], None, None
+        for k in range(a.warmup + a.reps):
+            t0 = time.perf_counter()
+            try:
+                s.adjoint_derivative_compute(dx=dx, dy=dy)
+            except ArithmeticError as e:            # the recurrence stalled above the threshold: the record says where
+                err = str(e)
+            t1 = time.perf_counter()
+            rec = s.adjoint_last_record()
+            if k >= a.warmup:
+                tot.append(t1 - t0); rec_s.append(rec['recurrence_s']); grad_s.append(rec['gradient_s'])
+        after = s._solver.hip_stats()
+        line = dict(problem=name, n=n, m=m, nnzA=int(A.nnz), eps=a.eps, woodbury_rows=int(st['woodbury_rows']), woodbury_direct=int(st['woodbury_direct']),
+                    woodbury_dual_cols=int(st['woodbury_dual_cols']), woodbury_one_launch=int(st['woodbury_one_launch']), preconditioner=s._solver.hip_preconditioner(),
+                    solve_iter=int(r.info.iter), cold_solve_ms=1e3 * cold, solve_factorisations=int(st['woodbury_factorisations']), solve_cache_hits=int(st['woodbury_cache_hits']),
+                    status=rec['status'], active_rows=rec['active_rows'], residual=rec['residual'], recurrence_steps=rec['steps'], pcg_iters=rec['pcg_iters'],
+                    pcg_iters_per_step=rec['pcg_iters'] / max(rec['steps'], 1), backward_ms_median=1e3 * med(tot), backward_ms_min=1e3 * min(tot), backward_ms_max=1e3 * max(tot),
+                    recurrence_ms_median=1e3 * med(rec_s), gradient_kernel_ms_median=1e3 * med(grad_s), backward_over_cold_solve=med(tot) / cold,
+                    stats_unchanged_by_the_calls=all(after[k] == st[k] for k in ('woodbury_rows', 'woodbury_direct', 'woodbury_factorisations', 'woodbury_cache_hits')))
+        if err:
+            line['error'] = err
+        print(json.dumps(line), flush=True)
+        out.append(line)
+        del s
+    text = json.dumps(dict(tool='adjoint_bench --single --woodbury', reps=a.reps, warmup=a.warmup, problems=out), indent=1)
+    if a.out:
+        with open(a.out, 'w') as f:
+            f.write(text + '\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--single', action='store_true', help='one large QP on the PCG path instead of the MPC batch')
@@ -70,7 +153,11 @@ def main():
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--eps', type=float, default=1e-6)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--woodbury', action='store_true', help='with --single: the QPs with dense rows (Woodbury handles) instead of the banded QP')
+    ap.add_argument('--only', default=None, help='with --woodbury: the problems whose name contains this text')
     a = ap.parse_args()
+    if a.single and a.woodbury:
+        return woodbury(a)
     if a.single:
         return single(a)
     import torch
