@@ -220,8 +220,8 @@ typedef struct {
 /* OSQPHipStats::preconditioner.  `cg_precond = OSQP_DIAGONAL_PRECONDITIONER` (bindings.cpp.in:426, the reference's only preconditioner) selects the
    Jacobi family: plain Jacobi M = diag(K), and -- this engine's addition, on by default, OSQPHipPolicy::woodbury / woodbury_large = 0 switch it
    off -- the same diagonal with the rows of A that hold more than 128 entries treated exactly through the Woodbury identity (1..128 such rows:
-   r x r system inverted on the host; up to 16384 rows carrying most of A: formed, factorised and inverted on the device with rocBLAS / rocSOLVER,
-   which are loaded on demand).  Which one a handle runs is reported here, never implied. */
+   r x r system inverted on the host; up to 16384 rows carrying most of A: formed and inverted on the device by this engine's own fp64
+   matrix-core kernels, dense_hip.hip).  Which one a handle runs is reported here, never implied. */
 enum { OSQP_HIP_PRECOND_NONE = 0, OSQP_HIP_PRECOND_JACOBI = 1, OSQP_HIP_PRECOND_JACOBI_WOODBURY = 2, OSQP_HIP_PRECOND_JACOBI_WOODBURY_DENSE = 3 };
 OSQPInt osqp_hip_get_stats(OSQPSolver *solver, OSQPHipStats *out);
 
@@ -648,8 +648,8 @@ typedef struct {
   OSQPInt window;             /* windowed row blocks (16-bit local column indices, input window in LDS)                         [setup] */
   OSQPInt woodbury;           /* a few dense rows of A (1..128 rows with > 128 entries) are treated exactly in the preconditioner   [setup] */
   OSQPInt woodbury_direct;    /* ... and when the rest of K is diagonal, that preconditioner IS K^-1: the linear solve without PCG iterations [setup] */
-  OSQPInt woodbury_large;     /* up to 16384 dense rows carrying most of A: the same correction with the r x r system formed, factorised and inverted on
-                                 the device (rocBLAS / rocSOLVER, loaded on demand; off where they are missing)                    [setup] */
+  OSQPInt woodbury_large;     /* up to 16384 dense rows carrying most of A: the same correction with the r x r system formed and inverted on the device
+                                 by this engine's own fp64 matrix-core kernels (dense_hip.hip; no vendor library)                  [setup] */
   OSQPInt device_driven;      /* chunk boundaries (termination test, adaptive rho, PCG tolerance / budget) decided on the device; 2: also for the Woodbury
                                  direct mode in two launches (there the host-synchronous loop is the faster one and the default) */
   OSQPInt small_direct;       /* small QPs: the whole solve as ONE launch of the batch kernel's direct (banded LDL') variant */
@@ -697,9 +697,9 @@ typedef struct {
                                  split into dense columns (two or more entries) and singletons (one: the lasso's -y_i); with fewer dense columns than 3/4 of the dense
                                  rows, the cd x cd system  T = D0_C + A_d' diag(w) A_d  on the dense columns replaces the r x r system S (lasso 5k x 10k: 5 000 against
                                  10 000: an eighth of the factorisation, a quarter of the inverse); 0: always the row-space form                                [setup] */
-  OSQPInt woodbury_vendor;    /* 0 (default): the dense system of the device-factorised Woodbury form is formed and inverted by this engine's own kernels on the fp64 matrix
-                                 cores (dense_hip.hip: a strided MFMA GEMM + block Gauss-Jordan inversion); 1: rocBLAS dgemm + rocSOLVER dpotrf / dpotri, loaded on
-                                 demand (the route of rounds 3-5, kept for A/B runs; without the libraries osqp_setup falls back to plain Jacobi)            [setup] */
+  OSQPInt woodbury_vendor;    /* RETIRED: accepted and ignored.  It selected rocBLAS / rocSOLVER for the dense system of the device-factorised Woodbury form (the route of
+                                 rounds 3-5, then an A/B switch); that route is gone, this engine's own kernels (dense_hip.hip: a strided MFMA GEMM + block Gauss-Jordan
+                                 inversion) are the only one.  The field keeps its place: the struct is append-only                                           */
   OSQPInt batch_wave;         /* batch solves in the spectral form: one WAVE per problem, eight problems in flight per CU, the longest-expected problems on the
                                  workgroup kernel beside it (batch_hip.hip k_batch_wave).  0 (default): for batches of at least 2048 problems, or 1280 with a
                                  launch order from a previous call (measured, MPC batch, with a launch order: 4096 QPs 2.8 ms against 5.7, 2048 1.8 against

@@ -159,9 +159,9 @@ struct DevKf {
 constexpr int kWbMaxRows = 128;
 // MANY dense rows (lasso: 10 000 sample rows of 5 000 entries next to two-entry rows): the same correction with S formed, factorised
 // and inverted on the device -- W = A_L D0^-1/2 as a dense r x ct block (ct = columns the long rows touch), S = W W' + diag(1 / rho_L)
-// by one fp64 GEMM, Cholesky + inverse by the ROCm dense solver library (rocBLAS / rocSOLVER, loaded on demand: without them this
-// mode is simply off), h = S^-1 g by a dense matrix-vector kernel (r^2 x 8 bytes per application).  Whether M = K (the direct mode) is
-// decided NUMERICALLY after every factorisation: M^-1 (K v) must reproduce a probe vector v to 1e-9.
+// by one fp64 GEMM and S^-1 by a block Gauss-Jordan inverse, both this engine's own kernels on the matrix cores (dense_hip.hip; no
+// vendor library), h = S^-1 g by a dense matrix-vector kernel (r^2 x 8 bytes per application).  Whether M = K (the direct mode) is
+// decided NUMERICALLY after every factorisation: M^-1 (K v) must reproduce a probe vector v to DevWb::exact_tol.
 constexpr int kWbLargeMax = 16384;
 inline size_t wb_inverse_work(int n) { return (size_t)n * 64 * 3 + 2 * 64 * 64 + 8; }      // dense_hip.hip dense_spd_inverse: column panel, row panel, R, two pivot blocks
 // The direct mode in TWO launches per ADMM iteration (wbdirect_hip.hip): P diagonal, every short row of A has exactly one entry, n <= kWbxMaxN.
@@ -230,7 +230,6 @@ struct DevWb {
   // row-space form (S = 1 / rho_L + A_L D0^-1 A_L', r x r) -- with cd x cd instead of r x r to form, factorise, invert and stream per application:
   // lasso 5k x 10k: cd = 5 000 against r = 10 000 -- an eighth of the factorisation's flops, a quarter of the inverse's bytes.
   // In this form: ct = cd, colmap = index among the dense columns, W [r][cd] = sqrt(w_a) A_d, S = T, Sinv = T^-1 (cd x cd).
-  int vendor = 0;                // 1: form / factorise / invert the dense system with rocBLAS + rocSOLVER (A/B switch, OSQPHipPolicy::woodbury_vendor); 0: dense_hip.hip
   double *gjwork = nullptr;      // [wb_inverse_work(order) + 1] panels of the block Gauss-Jordan inverse, the smallest pivot behind them
   int dual = 0, cd = 0;
   int *kind = nullptr;           // [n] 0: no long row touches the column, 1: dense, 2: singleton
@@ -641,7 +640,7 @@ inline double slot_launches(const Dev &d, double pcg) { return (d.wb.on && d.wb.
 bool kf_supported();                       // the K form exists (false: the host simulator)
 void kf_values(Dev &d, int cond = 0);      // K.val <- term lists with the current rho / A.val / B.val (no-op without the form; cond: inside a boundary group, only when it updated rho)
 void f1_refresh(Dev &d);                   // f1.pval <- B.val (no-op without a plan)
-bool wb_supported();
+bool wb_supported();                       // Woodbury preconditioner available (false: the host simulator)
 bool wbx_supported();                      // the two-launch direct mode exists (false: the host simulator)
 void wbx_init(Dev &d);                     // once per handle, after the plan is uploaded (LDS attribute of its kernels on d.device)
 void wbx_refresh(Dev &d);                  // tiles / one-entry-row values <- A.val
@@ -650,7 +649,7 @@ void wbx_slot_pair(Dev &d);                // the two launches as a pair of slot
 inline bool wbx_active(const Dev &d) { return d.wb.on && d.wb.exact && d.wb.x.on; }
 inline bool wbx_slots(const Dev &d) { return wbx_active(d) && d.wb.x.slots; }
 void wbx_chunk(Dev &d, int niter);         // niter ADMM iterations: X(rhs), { Y, X } x (niter - 1), Y, X(update): 2 niter + 1 launches on d.stream
-bool wb_large_supported();                 // the dense solver libraries could be loaded                       // Woodbury preconditioner available (false: the host simulator)
+bool wb_large_supported();                 // the device-factorised form exists (false: the host simulator)
 void wb_refresh(Dev &d);                   // wb.AL / ALT / WT values <- A.val (after assembly / equilibration / matrix updates)
 void wb_direct(Dev &d);                    // exact mode: x~ = x_g + M^-1 r_0 (after kb_rhs + wb_apply(0)); marks the solve as converged after one step
 inline bool wbf_active(const Dev &d) { return d.wb.on && d.wb.exact && d.wb.dual && d.wb.fused; }

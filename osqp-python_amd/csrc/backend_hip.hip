@@ -433,7 +433,8 @@ void destroy(Dev &d) {
   (void)hipEventDestroy(p.ev0); (void)hipEventDestroy(p.ev1); (void)hipEventDestroy(p.ev_s0); (void)hipEventDestroy(p.ev_s1); (void)hipEventDestroy(p.ev_ext); (void)hipEventDestroy(p.ev_wait); (void)hipHostFree(p.pin_res); (void)hipHostFree(p.pin_flags);
   (void)hipHostFree(p.pin_poll); if (p.side) (void)hipStreamDestroy(p.side);
   (void)hipHostFree(p.pin_ctl); (void)hipHostFree(p.pin_ctl2);
-  if (p.blas) wb_release_blas(p.blas);                 // (woodbury_hip.hip: the rocBLAS handle of the device-factorised form)
+  if (p.gj.s2) (void)hipStreamDestroy(p.gj.s2);        // (dense_hip.hip gj_aux: the lookahead stream of the device-factorised Woodbury form and its four events)
+  for (int q = 0; q < 2; q++) { if (p.gj.ready[q]) (void)hipEventDestroy(p.gj.ready[q]); if (p.gj.done[q]) (void)hipEventDestroy(p.gj.done[q]); }
   batch_release(d);
   for (int k = 1; k < DevWb::kCache; k++) if (d.wb.cache_buf[k]) { (void)hipFree(d.wb.cache_buf[k]); d.wb.cache_buf[k] = nullptr; }      // (buffer 0 is the engine's own Sinv allocation)
   dev_release(d);

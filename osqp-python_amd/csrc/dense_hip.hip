@@ -1,6 +1,6 @@
 // dense_hip.hip -- the dense fp64 work of the device-factorised Woodbury correction (backend.h DevWb::large), hand-written for gfx950's matrix cores:
-// forming the system (S = W W' / T = W' W: one GEMM) and inverting it (SPD, order up to kWbLargeMax).  Until round 5 this was rocBLAS dgemm +
-// rocSOLVER dpotrf / dpotri, loaded on demand (woodbury_hip.hip keeps that route as an A/B switch, OSQPHipPolicy::woodbury_vendor).
+// forming the system (S = W W' / T = W' W: one GEMM) and inverting it (SPD, order up to kWbLargeMax).  These kernels are the only route (until round 5 the
+// vendor GEMM / Cholesky / inverse did this work; that route was removed, OSQPHipPolicy::woodbury_vendor is accepted and ignored).
 //
 //   dense_gemm      C = beta C + alpha A B  on v_mfma_f64_16x16x4 (operand layout: tools/mfma_f64_layout.hip -- A: lane l holds A(l % 16, l / 16),
 //                   B: B(l / 16, l % 16), result register r of lane l = C(l / 16 + 4 r, l % 16)).  A workgroup of four waves owns a 64 x 64 tile of C
@@ -15,8 +15,8 @@
 //                   n^3 work is dense_gemm.  Second form (end of round 6): only the tiles on and above the diagonal are kept current (n^3 flops, half the
 //                   bytes) and the next pivot block is inverted on a second stream under the rank update: 17.3 -> 12.1 ms at order 5 000 (see the function).
 //                   Measured (MI355X, round 6): the GEMM forms the lasso's systems at 40 TFLOP/s (order 5 000, inner dimension 10 000: 12 ms) and 54 TFLOP/s
-//                   (order 10 000, inner 15 000: 55 ms; rocBLAS: 8.4 / 43 ms); the inverse takes 28.5 ms at order 5 000 and 121 ms at 10 000 (rocSOLVER
-//                   potrf + potri: 23 / 84 ms) with the pivot block inverted in LDS (221 us per block: 17.5 of the 28.5 ms) -- see k_gj_pivot for its register form.  Block steps of 128
+//                   (order 10 000, inner 15 000: 55 ms; the vendor GEMM: 8.4 / 43 ms); the inverse takes 28.5 ms at order 5 000 and 121 ms at 10 000 (the vendor
+//                   Cholesky + inverse: 23 / 84 ms) with the pivot block inverted in LDS (221 us per block: 17.5 of the 28.5 ms) -- see k_gj_pivot for its register form.  Block steps of 128
 //                   columns: 30.6 / 103 ms (the 128-step pivot chain costs what the halved traffic of the rank update saves at order 5 000).
 //                   Accuracy: Gauss-Jordan without pivoting loses about three digits against the Cholesky route on an ill-conditioned system (row-space S of
 //                   the lasso at rho = 0.1: |M^-1 K v - v| 2.5e-6 against 5e-9) -- the correction is then used as a preconditioner only (the direct mode
@@ -249,25 +249,24 @@ void dense_gemm_sym(void *stream, int N, int K, double alpha, const double *A, l
 // on a second stream, UNDER the rank update of the other tiles instead of in front of the next step.  Pivot blocks alternate between two buffers.
 // (First form: full matrix, pivot in line: 17.3 ms at order 5 000, profiles/r06k_*.)
 size_t dense_spd_inverse_work(int n) { return (size_t)n * kGjNb * 3 + (size_t)kGjNb * kGjNb * 2 + 8; }
-namespace {
-struct GjAux { int dev = -1; hipStream_t s2 = nullptr; hipEvent_t ready[2] = {nullptr, nullptr}, done[2] = {nullptr, nullptr}; };
-GjAux &gj_aux() {
-  static thread_local GjAux a;
-  int dev = 0;
-  HIP_CHECK(hipGetDevice(&dev));
-  if (a.dev != dev) {                                       // (one auxiliary stream + four events per host thread and device; never inside a capture: the factorisation is host-driven)
-    HIP_CHECK(hipStreamCreateWithFlags(&a.s2, hipStreamNonBlocking));
-    for (int q = 0; q < 2; q++) { HIP_CHECK(hipEventCreateWithFlags(&a.ready[q], hipEventDisableTiming)); HIP_CHECK(hipEventCreateWithFlags(&a.done[q], hipEventDisableTiming)); }
-    a.dev = dev;
+// The lookahead stream and its four events belong to the handle (hip_common.h Impl::gj; released by destroy).  Never inside a capture: the factorisation is host-driven.
+GjAux *gj_aux(Dev &d) {
+  static const bool lookahead = []() { const char *e = std::getenv("OSQP_HIP_GJ_LOOKAHEAD"); return !(e && e[0] == '0'); }();
+  if (!lookahead) return nullptr;
+  GjAux &a = im(d).gj;
+  if (!a.done[1]) {                                         // (the last one created: a throw part-way leaves the rest to destroy and is taken up again here)
+    HIP_CHECK(hipSetDevice(d.device));
+    if (!a.s2) HIP_CHECK(hipStreamCreateWithFlags(&a.s2, hipStreamNonBlocking));
+    for (int q = 0; q < 2; q++) {
+      if (!a.ready[q]) HIP_CHECK(hipEventCreateWithFlags(&a.ready[q], hipEventDisableTiming));
+      if (!a.done[q]) HIP_CHECK(hipEventCreateWithFlags(&a.done[q], hipEventDisableTiming));
+    }
   }
-  return a;
+  return &a;
 }
-}  // namespace
-void dense_spd_inverse(void *stream, double *A, long ld, int n, double *work, double *minpiv) {
+void dense_spd_inverse(void *stream, double *A, long ld, int n, double *work, double *minpiv, GjAux *aux) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   double *Ck = work, *Rw = Ck + (size_t)n * kGjNb, *R = Rw + (size_t)n * kGjNb, *Pb = R + (size_t)n * kGjNb;
-  static const bool lookahead = []() { const char *e = std::getenv("OSQP_HIP_GJ_LOOKAHEAD"); return !(e && e[0] == '0'); }();
-  GjAux *aux = lookahead ? &gj_aux() : nullptr;
   hipLaunchKernelGGL(k_set1, dim3(1), dim3(1), 0, s, minpiv, 1e300);
   const int nblk = (n + kGjNb - 1) / kGjNb;
   hipLaunchKernelGGL(k_gj_pivot, dim3(1), dim3(256), 0, s, A, ld, 0, std::min(kGjNb, n), Pb, minpiv, 0, nullptr, nullptr, 0L, 0);
@@ -312,7 +311,7 @@ double test_dense(Dev &d, const DenseProbe &p) {
     const size_t nw = dense_spd_inverse_work(p.N);
     double *work = static_cast<double *>(alloc(d, sizeof(double) * (nw + 1)));
     try {
-      dense_spd_inverse(d.stream, p.C, p.cs_i, p.N, work, work + nw);
+      dense_spd_inverse(d.stream, p.C, p.cs_i, p.N, work, work + nw, gj_aux(d));
       d2h(d, &minpiv, work + nw, sizeof(double));
     } catch (...) { dfree(d, work); throw; }
     dfree(d, work);

@@ -516,7 +516,7 @@ void Engine::prepare_wb(const std::vector<int> &Arp, const std::vector<int> &Arj
     w.pv = dev_vec<double>(d_, (size_t)n + m + n + 4 + r);
   } else w.WT = dev_vec<double>(d_, (size_t)n * r);
   w.info = dev_vec<int>(d_, 2); w.dbg = dev_vec<int>(d_, 1);
-  if (large) { w.vendor = pol_.woodbury_vendor != 0; w.gjwork = dev_vec<double>(d_, wb_inverse_work((int)ord) + 1); }
+  if (large) w.gjwork = dev_vec<double>(d_, wb_inverse_work((int)ord) + 1);
   if (pol_.debug_fail_refactor > 0) { const int v = pol_.debug_fail_refactor; be::h2d(d_, w.dbg, &v, sizeof(int)); }
   w.on = 1;
   // K0 diagonal <=> P has diagonal entries only and every short row of A has exactly one entry: then M = K (backend.h DevWb::exact)

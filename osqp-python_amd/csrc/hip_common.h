@@ -4,7 +4,8 @@
 // namespace: each unit compiles its own copy (templates and forceinline device functions; no relocatable device code needed).
 //   backend_hip.hip    handle / memory / graphs, residual + boundary kernels, rho / preconditioner / init, vector updates, assembly + Ruiz
 //   pcg_hip.hip        the ADMM / PCG hot path: KB, K1, K2, Kv, K2F, K1F, KA, the slot kernels, the one-launch form (F1), the timing probes
-//   woodbury_hip.hip   Woodbury-corrected preconditioner (both forms), the on-demand dense libraries
+//   woodbury_hip.hip   Woodbury-corrected preconditioner (both forms)
+//   dense_hip.hip      the dense fp64 GEMM and SPD inverse of its device-factorised form
 //   wbdirect_hip.hip   the Woodbury direct mode in two launches per ADMM iteration (self-contained)
 //   batch_hip.hip      one workgroup per small QP (self-contained)
 #pragma once
@@ -38,6 +39,9 @@ namespace be {
     }                                                                                                         \
   } while (0)
 
+// what dense_spd_inverse's lookahead pivot needs beside the caller's stream (dense_hip.hip): a handle's Impl owns one (gj_aux creates it, destroy releases it)
+struct GjAux { hipStream_t s2 = nullptr; hipEvent_t ready[2] = {nullptr, nullptr}, done[2] = {nullptr, nullptr}; };
+
 namespace {
 
 // partial-reduction slots inside Dev::part (each kGrid doubles)
@@ -68,7 +72,7 @@ struct Impl {
   int *pin_poll = nullptr;       // [kSlotInts]
   Ctl *pin_ctl = nullptr, *pin_ctl2 = nullptr;   // staging of the state block (upload / poll + download)
   int epoch = 0;                 // chunks begun (slot_begin); the device copy sits behind the two records
-  void *blas = nullptr;          // rocblas_handle of the large-rank Woodbury factorisation (created on first use)
+  GjAux gj;                      // lookahead stream and events of the device-factorised Woodbury form's inverse (dense_hip.hip gj_aux: created on first use)
   // device-resident copy of Dev for the F1 slot kernel (pcg_hip.hip dev_publish): {head block, Dev}, and what was last uploaded
   void *dev_block = nullptr; unsigned char *pin_block = nullptr; unsigned char *shadow_block = nullptr;
 };
@@ -573,9 +577,9 @@ void dev_release(Dev &d);                  // pcg_hip.hip: free it (called by de
 // dense_hip.hip: the dense fp64 building blocks of the device-factorised Woodbury correction on the matrix cores (strided operands; SPD inverse in place)
 void dense_gemm(void *stream, int M, int N, int K, double alpha, const double *A, long as_i, long as_k, const double *B, long bs_k, long bs_j, double beta, double *C, long cs_i, long cs_j);
 void dense_gemm_sym(void *stream, int N, int K, double alpha, const double *A, long as_i, long as_k, const double *B, long bs_k, long bs_j, double *C, long ld);
-void dense_spd_inverse(void *stream, double *A, long ld, int n, double *work, double *minpiv);
+void dense_spd_inverse(void *stream, double *A, long ld, int n, double *work, double *minpiv, GjAux *aux);      // aux == nullptr: every pivot block in line on the one stream
 size_t dense_spd_inverse_work(int n);
-void wb_release_blas(void *handle);        // woodbury_hip.hip: destroy the rocBLAS handle a Dev's Impl holds (called by destroy)
+GjAux *gj_aux(Dev &d);                     // the handle's lookahead stream and events, created on first use; nullptr under OSQP_HIP_GJ_LOOKAHEAD=0
 
 }  // namespace be
 }  // namespace osqp_hip

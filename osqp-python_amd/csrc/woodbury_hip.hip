@@ -1,11 +1,6 @@
 // woodbury_hip.hip -- Woodbury-corrected Jacobi preconditioner for the dense rows of A (backend.h DevWb): the small form
-// (r <= 128 rows, S inverted on the host) and the device-factorised form (r <= 16384: one fp64 GEMM + Cholesky + inverse through rocBLAS / rocSOLVER,
-// loaded on demand).  Split out of backend_hip.hip in round 4.
-#include <rocblas/rocblas.h>          // types and prototypes only: the libraries are dlopen()ed (dense_libs)
-#include <rocsolver/rocsolver.h>
-#include <dlfcn.h>
-#include <initializer_list>
-#include <mutex>
+// (r <= 128 rows, S inverted on the host) and the device-factorised form (order <= 16384: one fp64 GEMM and a block Gauss-Jordan inverse on the matrix
+// cores, dense_hip.hip).  Split out of backend_hip.hip in round 4.
 #include "hip_common.h"
 
 namespace osqp_hip {
@@ -577,47 +572,6 @@ __global__ void k_wb_seq(double *g, int r) { for (int a = blockIdx.x * blockDim.
 
 }  // namespace
 
-// ---- dense solver libraries, loaded on first use (rocBLAS: fp64 GEMM; rocSOLVER: Cholesky factorisation and inverse).  Nothing of the
-// engine links against them: where they are missing the large-rank mode is off and such problems keep the Jacobi preconditioner.
-namespace {
-struct DenseLibs {
-  bool tried = false, ok = false;
-  void *hblas = nullptr, *hsolver = nullptr;
-  rocblas_status (*create)(rocblas_handle *) = nullptr;
-  rocblas_status (*destroy)(rocblas_handle) = nullptr;
-  rocblas_status (*set_stream)(rocblas_handle, hipStream_t) = nullptr;
-  rocblas_status (*dgemm)(rocblas_handle, rocblas_operation, rocblas_operation, rocblas_int, rocblas_int, rocblas_int, const double *, const double *, rocblas_int,
-                          const double *, rocblas_int, const double *, double *, rocblas_int) = nullptr;
-  rocblas_status (*dpotrf)(rocblas_handle, const rocblas_fill, const rocblas_int, double *, const rocblas_int, rocblas_int *) = nullptr;
-  rocblas_status (*dpotri)(rocblas_handle, const rocblas_fill, const rocblas_int, double *, const rocblas_int, rocblas_int *) = nullptr;
-};
-DenseLibs &dense_libs() {
-  static DenseLibs L;
-  static std::mutex mu;
-  std::lock_guard<std::mutex> lock(mu);
-  if (L.tried) return L;
-  L.tried = true;
-  auto open_any = [](std::initializer_list<const char *> names) -> void * { for (const char *nm : names) if (void *h = dlopen(nm, RTLD_NOW | RTLD_LOCAL)) return h; return nullptr; };
-  L.hblas = open_any({"librocblas.so.5", "librocblas.so", "/opt/rocm/lib/librocblas.so"});
-  L.hsolver = open_any({"librocsolver.so.0", "librocsolver.so", "/opt/rocm/lib/librocsolver.so"});
-  if (!L.hblas || !L.hsolver) return L;
-  auto sym = [](void *h, const char *nm) { return dlsym(h, nm); };
-  L.create = reinterpret_cast<decltype(L.create)>(sym(L.hblas, "rocblas_create_handle"));
-  L.destroy = reinterpret_cast<decltype(L.destroy)>(sym(L.hblas, "rocblas_destroy_handle"));
-  L.set_stream = reinterpret_cast<decltype(L.set_stream)>(sym(L.hblas, "rocblas_set_stream"));
-  L.dgemm = reinterpret_cast<decltype(L.dgemm)>(sym(L.hblas, "rocblas_dgemm"));
-  L.dpotrf = reinterpret_cast<decltype(L.dpotrf)>(sym(L.hsolver, "rocsolver_dpotrf"));
-  L.dpotri = reinterpret_cast<decltype(L.dpotri)>(sym(L.hsolver, "rocsolver_dpotri"));
-  L.ok = L.create && L.destroy && L.set_stream && L.dgemm && L.dpotrf && L.dpotri;
-  return L;
-}
-}  // namespace
-
-namespace {
-
-}  // namespace
-
-void wb_release_blas(void *handle) { if (handle && dense_libs().ok) (void)dense_libs().destroy(static_cast<rocblas_handle>(handle)); }
 bool wb_supported() { return true; }
 void wb_refresh(Dev &d) {
   if (!d.wb.on) return;
@@ -661,29 +615,15 @@ void wbf_iteration(Dev &d) {
   hipLaunchKernelGGL(k_wbf_x, dim3(std::min((d.n + kBlock - 1) / kBlock, kGrid)), dim3(kBlock), 0, st(d), d);
   if (d.wb.thin) hipLaunchKernelGGL(k_wbf_s2, dim3(std::min((d.m + kBlock - 1) / kBlock, 4 * kGrid)), dim3(kBlock), 0, st(d), d);
   else LAUNCH(k_wbf_s, d, d);
-}      // (own kernels: dense_hip.hip; the vendor route needs the libraries, checked where it is asked for)
+}
 
-// D0, W, S = W W' + 1 / rho_L, S^-1 -- all on the device (r up to kWbLargeMax); then the two numerical checks
+// D0, W, S = W W' + 1 / rho_L, S^-1 -- all on the device, by this engine's dense kernels (dense_hip.hip; order up to kWbLargeMax); then the two numerical checks
 static void wb_factor_large(Dev &d) {
   DevWb &w = d.wb;
-  Impl &p = im(d);
-  rocblas_handle h = nullptr;
-  static DenseLibs none;
-  DenseLibs &L = w.vendor ? dense_libs() : none;             // (the libraries are touched only on the vendor route)
-  if (w.vendor) {
-    if (!L.ok) throw DeviceError("osqp_hip: the dense solver libraries are not available");
-    if (!p.blas) {
-      rocblas_handle hh = nullptr;
-      if (L.create(&hh) != rocblas_status_success) throw DeviceError("osqp_hip: rocblas_create_handle failed");
-      p.blas = hh;
-    }
-    h = static_cast<rocblas_handle>(p.blas);
-    if (L.set_stream(h, st(d)) != rocblas_status_success) throw DeviceError("osqp_hip: rocblas_set_stream failed");
-  }
   const int ct = w.ct;
   const int r = w.dual ? w.cd : w.r;                         // order of the dense system: S (row space, r x r) or T (column space, cd x cd)
   const bool log = w.log != 0;
-  double tlap[6] = {0, 0, 0, 0, 0, 0};
+  double tlap[5] = {0, 0, 0, 0, 0};
   auto lap = [&](int k) { if (log) { HIP_CHECK(hipStreamSynchronize(st(d))); tlap[k] = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); } };
   lap(0);
   LAUNCH(k_wb_diag, d, d, 0);
@@ -731,37 +671,25 @@ static void wb_factor_large(Dev &d) {
     if (slot < 0) { slot = w.cache_next % std::max(1, w.cache_used); w.cache_next += 1; }
     w.Sinv = w.cache_buf[slot]; w.cache_rho[slot] = -1.0; w.cache_next = slot + 1;
   }
-  const double one = 1.0, zero = 0.0;
   if (w.dual) {
     LAUNCH(k_wbd_fillW, d, d);
     lap(1);
-    // W is r x cd row-major = cd x r column-major (ld cd): T = W_cm W_cm' (cd x cd, inner dimension r)
-    if (!w.vendor) dense_gemm_sym(st(d), r, w.r, 1.0, w.W, 1, r, w.W, r, 1, w.S, r);             // T(i, j) = sum_a W[a][i] W[a][j]: one triangle on the matrix cores, mirrored
-    else if (L.dgemm(h, rocblas_operation_none, rocblas_operation_transpose, r, r, w.r, &one, w.W, r, w.W, r, &zero, w.S, r) != rocblas_status_success)
-      throw DeviceError("osqp_hip: rocblas_dgemm failed");
+    // W is r x cd row-major: T = W' W (cd x cd, inner dimension r)
+    dense_gemm_sym(st(d), r, w.r, 1.0, w.W, 1, r, w.W, r, 1, w.S, r);             // T(i, j) = sum_a W[a][i] W[a][j]: one triangle on the matrix cores, mirrored
     LAUNCH(k_wbd_adddiag, d, d);
   } else {
-  LAUNCH(k_wb_fillW, d, d);
-  lap(1);
-  // W is r x ct row-major = ct x r column-major (ld ct): S = W' W in the library's convention
-  if (!w.vendor) dense_gemm_sym(st(d), r, ct, 1.0, w.W, ct, 1, w.W, 1, ct, w.S, r);               // S(a, b) = sum_j W[a][j] W[b][j]
-  else if (L.dgemm(h, rocblas_operation_transpose, rocblas_operation_none, r, r, ct, &one, w.W, ct, w.W, ct, &zero, w.S, r) != rocblas_status_success)
-    throw DeviceError("osqp_hip: rocblas_dgemm failed");
-  LAUNCH(k_wb_adddiag, d, d);
+    LAUNCH(k_wb_fillW, d, d);
+    lap(1);
+    // W is r x ct row-major: S = W W' (r x r, inner dimension ct)
+    dense_gemm_sym(st(d), r, ct, 1.0, w.W, ct, 1, w.W, 1, ct, w.S, r);            // S(a, b) = sum_j W[a][j] W[b][j]
+    LAUNCH(k_wb_adddiag, d, d);
   }
   lap(2);
   HIP_CHECK(hipMemcpyAsync(w.Sinv, w.S, sizeof(double) * (size_t)r * r, hipMemcpyDeviceToDevice, st(d)));
   double *minpiv = w.gjwork + wb_inverse_work(r);
-  if (!w.vendor) {
-    HIP_CHECK(hipMemsetAsync(w.info, 0, 2 * sizeof(int), st(d)));
-    dense_spd_inverse(st(d), w.Sinv, r, r, w.gjwork, minpiv);      // block Gauss-Jordan on the matrix cores (dense_hip.hip)
-    lap(3); lap(4);
-  } else {
-  if (L.dpotrf(h, rocblas_fill_lower, r, w.Sinv, r, w.info) != rocblas_status_success) throw DeviceError("osqp_hip: rocsolver_dpotrf failed");
+  HIP_CHECK(hipMemsetAsync(w.info, 0, 2 * sizeof(int), st(d)));
+  dense_spd_inverse(st(d), w.Sinv, r, r, w.gjwork, minpiv, gj_aux(d));      // block Gauss-Jordan on the matrix cores (dense_hip.hip)
   lap(3);
-  if (L.dpotri(h, rocblas_fill_lower, r, w.Sinv, r, w.info + 1) != rocblas_status_success) throw DeviceError("osqp_hip: rocsolver_dpotri failed");
-  lap(4);
-  }
   hipLaunchKernelGGL(k_wb_symm, dim3(std::min(r, 8 * kGrid)), dim3(kBlock), 0, st(d), w.Sinv, r);
   // S^-1 against S on a fixed vector:  S (S^-1 g) = g
   hipLaunchKernelGGL(k_wb_seq, dim3(64), dim3(256), 0, st(d), w.g, r);
@@ -771,7 +699,7 @@ static void wb_factor_large(Dev &d) {
   if (w.probe) probe();
   int info[2] = {0, 0};
   double chk[4] = {0, 1, 0, 1}, piv = 1.0;
-  if (!w.vendor) HIP_CHECK(hipMemcpyAsync(&piv, minpiv, sizeof(double), hipMemcpyDeviceToHost, st(d)));
+  HIP_CHECK(hipMemcpyAsync(&piv, minpiv, sizeof(double), hipMemcpyDeviceToHost, st(d)));
   HIP_CHECK(hipMemcpyAsync(info, w.info, sizeof(info), hipMemcpyDeviceToHost, st(d)));
   HIP_CHECK(hipMemcpyAsync(chk, out, sizeof(double) * (w.probe ? 4 : 2), hipMemcpyDeviceToHost, st(d)));
   HIP_CHECK(hipStreamSynchronize(st(d)));
@@ -780,9 +708,9 @@ static void wb_factor_large(Dev &d) {
   w.exact = (w.probe && inv_ok && chk[2] <= w.exact_tol * chk[3]) ? 1 : 0;
   if (inv_ok) for (int k = 0; k < w.cache_used; k++) if (w.cache_buf[k] == w.Sinv) w.cache_rho[k] = w.rho_key;      // (the entry is valid from here on)
   if (log) {
-    lap(5);
-    std::fprintf(stderr, "osqp_hip woodbury (%s): order %d ct %d  |S S^-1 g - g| %.2e / %.2e   |M^-1 K v - v| %.2e / %.2e   direct %d;  D0 + W %.1f ms, GEMM %.1f ms, Cholesky %.1f ms, inverse %.1f ms, mirror + checks %.1f ms\n",
-                 w.dual ? "column space" : "row space", r, ct, chk[0], chk[1], chk[2], chk[3], w.exact, 1e3 * (tlap[1] - tlap[0]), 1e3 * (tlap[2] - tlap[1]), 1e3 * (tlap[3] - tlap[2]), 1e3 * (tlap[4] - tlap[3]), 1e3 * (tlap[5] - tlap[4]));
+    lap(4);
+    std::fprintf(stderr, "osqp_hip woodbury (%s): order %d ct %d  |S S^-1 g - g| %.2e / %.2e   |M^-1 K v - v| %.2e / %.2e   direct %d;  D0 + W %.1f ms, GEMM %.1f ms, inverse %.1f ms, mirror + checks %.1f ms\n",
+                 w.dual ? "column space" : "row space", r, ct, chk[0], chk[1], chk[2], chk[3], w.exact, 1e3 * (tlap[1] - tlap[0]), 1e3 * (tlap[2] - tlap[1]), 1e3 * (tlap[3] - tlap[2]), 1e3 * (tlap[4] - tlap[3]));
   }
 }
 // D0, S, S^-1 (with its check) and the second tile of the two-launch direct mode: launches only -- conditional inside a boundary group

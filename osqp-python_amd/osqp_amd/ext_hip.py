@@ -296,8 +296,6 @@ class OSQPSolver:
         if int(st['preconditioner']) == 3:
             cd = int(st.get('woodbury_dual_cols', 0))
             name += (', column space (%d x %d)' % (cd, cd)) if cd else ', row space'
-            if self.get_policy().get('woodbury_vendor'):
-                name += ' -- vendor route (rocBLAS / rocSOLVER)'
         return name
 
     def get_policy(self):

@@ -28,6 +28,7 @@ def test_policy_defaults_roundtrip_and_validation(backend):
         m = osqp_amd.OSQP(); m.setup(P, q, A, l, u, verbose=False, eps_abs=1e-6, eps_rel=1e-6)
         pol = m._solver.get_policy()
         assert pol['rho_window'] == 10 and pol['device_driven'] == 1
+        assert pol['woodbury_vendor'] == 0 and p.woodbury_vendor == 0      # (retired, accepted and ignored: the field keeps its name and place)
         m._solver.set_policy(rho_window=0, rho_persist=0, rho_tol_exp=1.0, small_direct=0)       # the reference's literal rho rule
         pol = m._solver.get_policy()
         assert (pol['rho_window'], pol['rho_persist'], pol['rho_tol_exp'], pol['small_direct']) == (0, 0, 1.0, 0)
