@@ -241,7 +241,10 @@ OSQPInt osqp_hip_get_stats(OSQPSolver *solver, OSQPHipStats *out);
    Woodbury direct mode (0 when it is not on): 20 = one ADMM iteration of the two-launch form (k_wbx_y + k_wbx_x; `reps` iterations as one chunk, time per
    iteration), 21 = the kernels of M^-1 = K^-1 of the unfused form (k_wb_p1, k_wb_p2 / k_wb_gemv, k_wb_p3; column space: the five k_wbd_* launches),
    23 = one ADMM iteration of the fused column-space direct mode (seven launches: k_wbf_r, k_wbf_beta, k_wbf_g, k_wbd_gemv, k_wbf_t, k_wbf_x, k_wbf_s).
-   The kernels run in a side-effect-free "probe" mode or on saved-and-restored state; solver state is unchanged. */
+   Dense KKT mode (osqp_hip_dense_kkt; OSQP_FUNC_NOT_IMPLEMENTED unless the handle's record shows state 1): 24 = its hot path alone (k_dk_apply:
+   u = K^-1 r_0, x~ = x_g + u), 25 = one ADMM iteration of the mode (KB, k_dk_apply, KA) as a solve runs it -- a captured chunk of `reps` (at most 1024)
+   iterations replayed between the event pair, time per iteration; 25 moves the handle's iterates on.
+   Otherwise the kernels run in a side-effect-free "probe" mode or on saved-and-restored state; solver state is unchanged. */
 OSQPInt osqp_hip_time_kernel(OSQPSolver *solver, OSQPInt which, OSQPInt reps, double *mean_ms);
 
 /* Batched solve of `nbatch` QPs that share this solver's P, A, scaling and settings and differ in q / l / u (BASELINE
@@ -1009,6 +1012,50 @@ void    osqp_hip_set_default_print(osqp_hip_print_fn fn, void *user);
 OSQPInt osqp_hip_set_print(OSQPSolver *solver, osqp_hip_print_fn fn, void *user);
 /* name of the compute backend compiled into this library: "hip-gfx950" for the product */
 const char *osqp_hip_backend(void);
+
+/* DENSE KKT MODE (csrc/densekkt_hip.hip): exact linear solves for a single QP of a few hundred to a few thousand variables.
+   The handle holds K^-1 = (P + sigma I + A' diag(rho) A)^-1 as a dense n x n matrix on the device (8 n^2 bytes, plus 8 m n bytes of work space); an ADMM
+   iteration is then three launches with an exact solve instead of a PCG.  Opt-in per handle, off by default.
+     on = 1   allocates, forms and inverts K for the handle's current rho and checks the inverse (max |K^-1 K v - v| <= 1e-6 max |v| on a probe vector).
+              Synchronous: the inverse is in place when the call returns.  Every later change of rho (adaptive updates inside osqp_solve, osqp_update_rho),
+              of the matrix values (osqp_update_data_mat) or of the bounds (osqp_update_data_vec with l / u: the constraint classes decide rho_i)
+              factorises again.  Polish and the adjoint derivatives run on the PCG path as without the mode; the inverse is re-formed behind them.
+              OSQP_FUNC_NOT_IMPLEMENTED -- the handle is left untouched, nothing is allocated -- on a backend without the mode, on a handle with a
+              Woodbury correction (it has its own direct modes), without device-side assembly, with m = 0, with n > OSQP_HIP_DENSE_KKT_MAX_N or with
+              m n > 2^25 (the work matrix).  OSQP_MEM_ALLOC_ERROR when the device has no room.  A reordered handle (OSQPHipPolicy::reorder) is served.
+     on = 0   frees everything; from the next solve on the handle computes what a handle computes on which the mode was never enabled.
+   The batch and lockstep entry points do not consult the mode.  osqp_hip_dense_kkt_last_record copies OSQP_HIP_DENSE_KKT_REC doubles:
+     0 state      0 off; 1 K^-1 accepted: the solves run direct (OSQPHipStats::pcg_iters_total = 0); 2 enabled, but the inverse for the current rho was
+                  refused (a pivot <= 0, or the probe above 1e-6): the handle runs its ordinary PCG path until a later factorisation is accepted
+     1 order      n (0 while off)
+     2, 3         factorisations during the last osqp_solve, their wall-clock milliseconds
+     4, 5         probe value and smallest pivot of the last inversion
+     6            device bytes the mode holds
+     7            factorisations since the mode was enabled */
+#define OSQP_HIP_DENSE_KKT_MAX_N 1000    /* the largest size of the sweep in DESIGN.md section 6 at which the mode is slower on neither family (it began at 4096) */
+#define OSQP_HIP_DENSE_KKT_REC 8
+OSQPInt osqp_hip_dense_kkt(OSQPSolver *solver, OSQPInt on);
+OSQPInt osqp_hip_dense_kkt_last_record(OSQPSolver *solver, OSQPFloat *rec);
+/* Test hook (used by tests/ only): the mode's kernels on a handle with the mode ON (else OSQP_FUNC_NOT_IMPLEMENTED).  Everything is in the SCALED problem
+   (osqp_hip_get_scaling) and in the ENGINE's numbering (osqp_hip_get_reordering).  Synchronous.
+     op OSQP_HIP_DK_FORM    factorises as a rho update does and copies out  K [n^2 + 16]  row-major AS FORMED, before the inversion, and  rho [m + 16], the
+                            vector it was formed with.  Not counted in the record's factorisations.
+     op OSQP_HIP_DK_APPLY   the hot path on the caller's  r [n]  (r_0) and  xg [n]  (x_g):  xs [n + 16] = x~ = x_g + K^-1 r_0,  u [n + 16] = K^-1 r_0,  done /
+                            iters: the PCG's flags as the launch leaves them.  Needs state 1.
+     op OSQP_HIP_DK_PROBE   the probe alone against the inverse in place: probe.
+   Of an output exactly the listed count is written (the 16 cells behind it keep the caller's values); a field an op does not list has length 0.  Every
+   vector of the handle the call overwrites is restored before it returns: a solve after the call is the solve without it.  Every length and pointer
+   is checked before anything is launched (anything else than listed: OSQP_DATA_VALIDATION_ERROR). */
+enum { OSQP_HIP_DK_FORM = 0, OSQP_HIP_DK_APPLY = 1, OSQP_HIP_DK_PROBE = 2 };
+typedef struct {
+  OSQPInt op;
+  long long r_len, xg_len, k_len, rho_len, xs_len, u_len;
+  const OSQPFloat *r, *xg;
+  OSQPFloat *K, *rho, *xs, *u;
+  OSQPInt state, order, done, iters;   /* out */
+  OSQPFloat probe, minpiv;             /* out */
+} OSQPHipDenseKktTest;
+OSQPInt osqp_hip_test_dense_kkt(OSQPSolver *solver, OSQPHipDenseKktTest *t);
 
 #ifdef __cplusplus
 }

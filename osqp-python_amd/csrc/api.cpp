@@ -99,6 +99,9 @@ OSQPInt osqp_hip_test_admm(OSQPSolver *s, OSQPHipAdmmTest *t) { return guarded(s
 OSQPInt osqp_hip_test_boundary(OSQPSolver *s, OSQPHipBoundaryTest *t) { return guarded(s, [&](Engine &e) { return e.test_boundary(t); }); }
 const char *osqp_hip_res_name(OSQPInt q) { return Engine::res_name(q); }
 OSQPInt osqp_hip_set_rho_eq_factor(OSQPSolver *s, OSQPFloat f) { return guarded(s, [&](Engine &e) { return e.set_rho_eq_factor(f); }); }
+OSQPInt osqp_hip_dense_kkt(OSQPSolver *s, OSQPInt on) { return guarded(s, [&](Engine &e) { return e.dense_kkt(on); }); }
+OSQPInt osqp_hip_dense_kkt_last_record(OSQPSolver *s, OSQPFloat *rec) { return guarded(s, [&](Engine &e) { return e.dense_kkt_last_record(rec); }); }
+OSQPInt osqp_hip_test_dense_kkt(OSQPSolver *s, OSQPHipDenseKktTest *t) { return guarded(s, [&](Engine &e) { return e.test_dense_kkt(t); }); }
 void osqp_hip_default_policy(OSQPHipPolicy *p) { Engine::default_policy(p); }
 void osqp_hip_set_default_policy(const OSQPHipPolicy *p) { Engine::set_default_policy(p); }
 OSQPInt osqp_hip_set_policy(OSQPSolver *s, const OSQPHipPolicy *p) { return guarded(s, [&](Engine &e) { return e.set_policy(p); }); }

@@ -258,6 +258,30 @@ struct DevWb {
   int *bq_ptr = nullptr, *bq_idx = nullptr, *bq_col = nullptr;            // per dense column: its entries of B outside the dense rows (position in B.val, column of B)
 };
 
+// DENSE KKT mode (densekkt_hip.hip; include/osqp_hip.h osqp_hip_dense_kkt): a single QP with n between a few hundred and a
+// few thousand holds  K^-1 = (P + sigma I + A' diag(rho) A)^-1  as a dense n x n matrix (n = 2 048: 33.5 MB, resident in the Infinity Cache), formed and
+// inverted by the dense kernels of dense_hip.hip wherever rho or the matrices change (be::precond -> dk_factor).  An ADMM iteration is then three launches
+// with an EXACT linear solve:  kb_rhs;  dk_apply (u = K^-1 r_0, x~ = x_g + u);  ka  -- whatever n is, against k + 2 launches of an inexact PCG.
+// Whether the inverse is good enough is decided numerically after every factorisation, by the probe of the Woodbury direct mode:
+// max |K^-1 (K v) - v| <= kDkProbeTol max |v|  with K v from the handle's own sparse products.
+constexpr int kDkMaxN = 1000;                 // OSQP_HIP_DENSE_KKT_MAX_N: what the sweep of DESIGN.md section 6 supports (above it a rho update's factorisation costs more than the iterations save)
+constexpr long long kDkMaxW = 1LL << 25;      // entries of the m x n work matrix (256 MB)
+constexpr double kDkProbeTol = 1e-6;          // OSQPHipPolicy::woodbury_direct_tol's default, with the same meaning
+struct DevDk {
+  int on = 0;                    // the mode is enabled for this handle (buffers allocated)
+  int state = 0;                 // 0 off; 1 K^-1 accepted by the probe: the solves run direct; 2 refused for the current rho: the handle's ordinary PCG path
+  int suspend = 0;               // inside Engine::run_recurrence (rho = 1 / delta: no unpivoted inverse of that K): precond leaves the mode alone, chunks take the PCG path
+  double *Kinv = nullptr;        // [n][n] full storage; the address is fixed for the life of the mode (captured launches hold it)
+  double *W = nullptr;           // [m][n] sqrt(rho_i) A_ij
+  double *work = nullptr;        // [dense_spd_inverse_work(n) + 1] panels of the inverse, the smallest pivot behind them
+  double *pv = nullptr;          // [n + m + n + 2] probe vector v, rho .* (A v), v again, the two results of the comparison
+  // host-side bookkeeping of the factorisations (dk_factor)
+  double probe = 0.0, minpiv = 0.0, fac_ms = 0.0;
+  long long nfac = 0;
+  double bytes = 0.0;
+};
+inline bool dk_direct(const DevDk &k) { return k.on && k.state == 1 && !k.suspend; }
+
 // indices into Dev::res (results of the residual kernels, reduced on the device)
 enum ResId {
   R_PRI_U = 0, R_AX_U, R_Z_U, R_PRI_S, R_AX_S, R_Z_S, R_DY_U, R_DY_S, R_PINF_LHS, R_SUPP,   // m-side
@@ -327,6 +351,7 @@ struct Dev {
   void *stream = nullptr;        // hipStream_t (product) / unused (host simulator)
   void *bside = nullptr, *bev0 = nullptr, *bev1 = nullptr;      // batch path: second stream + fork / join events (batch_hip.hip, created on first use)
   void *impl = nullptr;          // backend private (events, graphs, pinned staging)
+  DevDk dk;                      // dense KKT mode (dk.on; never together with wb.on).  Last: every other field keeps its offset
 };
 
 // Batched small-QP solve (batch_hip.hip): nbatch problems sharing the solver's scaled A / B, one workgroup each (kBatchRec: lockstep_layout.h).
@@ -754,6 +779,23 @@ struct WbProbe {
   int exact, info[2], done, iters; double gamma, rnorm;
 };
 int test_woodbury(Dev &d, WbProbe &p) __attribute__((weak));
+// ---- dense KKT mode (DevDk; densekkt_hip.hip).  Weak like lockstep_chunk: the host simulator has none of it, and the driver answers
+// OSQP_FUNC_NOT_IMPLEMENTED where the symbols are absent.
+// dk_enable: the buffers, all or nothing (OSQP_MEM_ALLOC_ERROR: the device has no room; nothing stays allocated); d.dk.on = 1, no factorisation yet.
+// dk_release: frees them, d.dk = DevDk().  dk_factor: W, K = W' W + P + sigma I, K^-1 in place, the probe; synchronous; sets d.dk.state (1 / 2), probe,
+// minpiv and counts itself; K_out (host, n^2): K as formed, copied out before the inversion.  A fixed launch sequence without atomics on doubles:
+// repeated factorisations of the same data are bit-identical.  Called by be::precond on a handle with the mode on and not suspended.
+// dk_apply: u = K^-1 r_0 (Dev::r) into Dev::uu, x~ = x_g + u into Dev::xs, F_DONE = 1 / F_ITERS = 0 (ka then counts a converged solve of no PCG
+// iteration); one launch on d.stream, capturable.
+int dk_enable(Dev &d) __attribute__((weak));
+void dk_release(Dev &d) __attribute__((weak));
+void dk_factor(Dev &d, double *K_out = nullptr) __attribute__((weak));
+void dk_apply(Dev &d) __attribute__((weak));
+// the diagnostic entry (include/osqp_hip.h osqp_hip_test_dense_kkt, which has validated every field: nothing is checked here).  HOST vectors in the engine's
+// numbering.  op 0 FORM: dk_factor with K [n^2] copied out before the inversion, rho [m].  op 1 APPLY: r -> d.r, xg -> d.xg, F_DONE cleared, dk_apply; xs, u
+// [n], done / iters.  op 2 PROBE: the probe alone against the inverse in place.  d.r, d.uu, d.xs, d.xg and the flags are saved before and restored after.
+struct DkProbe { int op; const double *r, *xg; double *K, *rho, *xs, *u; int done, iters, state; double probe, minpiv; };
+int test_dense_kkt(Dev &d, DkProbe &p) __attribute__((weak));
 // single launches of the lockstep kernels (include/osqp_hip.h osqp_hip_test_lockstep, which has validated every field, staged the caller's arrays and uploaded
 // the blocks: nothing is checked here).  p: the parameters of a chunk as Engine::run_lockstep_solve builds them (ws / mat_ws: the route's resident blocks,
 // q .. Ax: DEVICE arrays).  The body carves the blocks as lockstep_chunk does, launches ops[0 .. nops) -- OSQPHipLockstepOp, one kernel launch each, through

@@ -576,6 +576,7 @@ void precond(Dev &d, int diagonal) {
   else LAUNCH(k_fill, d, d.Minv, d.n, 1.0);
   kf_values(d, 0);                                        // K form: K.val from the current rho / matrix values (every caller of precond has just changed one of them)
   if (d.wb.on) wb_factor(d);
+  if (d.dk.on && !d.dk.suspend) dk_factor(d);             // dense KKT mode: K^-1 for the new rho / matrix values (densekkt_hip.hip; synchronous)
 }
 void set_pcg_tol(Dev &d, double rel, double ab) {
   HIP_CHECK(hipSetDevice(d.device));

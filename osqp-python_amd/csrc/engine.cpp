@@ -152,6 +152,8 @@ void Engine::free_all() {
   if (!dev_ready_) return;
   try { be::activate(d_); be::ext_wait(d_); be::sync(d_); } catch (const DeviceError &) {}       // runs in the destructor: release what we can
   drop_graphs();
+  if (d_.dk.on && be::dk_release) be::dk_release(d_);
+  dk_solve_nfac_ = 0; dk_solve_ms_ = 0;
   if (bbuf_) { be::dfree(d_, bbuf_); bbuf_ = nullptr; bbuf_cap_ = 0; }
   if (bmat_) { be::dfree(d_, bmat_); bmat_ = nullptr; bmat_cap_ = 0; }
   if (abuf_) { be::dfree(d_, abuf_); abuf_ = nullptr; abuf_cap_ = 0; }
@@ -400,9 +402,12 @@ void Engine::set_status(int st) {
 void Engine::run_chunk(int niter, int budget) {
   const bool fused = be::pcg_fused(d_), wb = d_.wb.on != 0;
   const bool xy = wb && d_.wb.exact && d_.wb.x.on;       // the direct mode in two launches per ADMM iteration (wbdirect_hip.hip)
+  const bool dk = dk_direct(d_.dk);                      // dense KKT mode: KB, K^-1 r_0, KA (densekkt_hip.hip); no PCG, hence no budget
+  if (dk) budget = 0;
   auto enqueue = [&](int count) {
     if (xy) { be::wbx_chunk(d_, count); return; }
     for (int it = 0; it < count; it++) {
+      if (dk) { be::kb_rhs(d_); be::dk_apply(d_); be::ka(d_, 0); continue; }
       if (be::wbf_active(d_)) { be::wbf_iteration(d_); continue; }      // column-space direct mode, fused: seven launches, the dense block streamed twice (backend.h DevWb::fused)
       be::kb_rhs(d_);
       if (wb) be::wb_apply(d_, 0, d_.wb.exact);
@@ -411,15 +416,15 @@ void Engine::run_chunk(int niter, int budget) {
       be::ka(d_, budget);
     }
   };
-  stats_.kernel_launches += xy ? ((d_.wb.x.one && !d_.wb.x.slots) ? niter + 1.0 : 2.0 * niter + 1) : (double)niter * ((wb && d_.wb.exact) ? (d_.wb.dual ? 7 : 5) : (fused ? 3 + 2 * budget : 2 + 3 * budget + (wb ? 3 * (budget + 1) : 0)));
+  stats_.kernel_launches += dk ? 3.0 * niter : xy ? ((d_.wb.x.one && !d_.wb.x.slots) ? niter + 1.0 : 2.0 * niter + 1) : (double)niter * ((wb && d_.wb.exact) ? (d_.wb.dual ? 7 : 5) : (fused ? 3 + 2 * budget : 2 + 3 * budget + (wb ? 3 * (budget + 1) : 0)));
   if (!(use_graph_ && be::graphs_supported())) { enqueue(niter); return; }
   // one executable graph per (ADMM iterations, PCG budget); graphs are kept below kMaxGraphNodes kernel nodes (a
   // check_termination = 0 solve would otherwise capture max_iter * (2 + 3*budget) nodes in one graph)
   constexpr int kMaxGraphNodes = 8192;
-  const int per = std::max(1, kMaxGraphNodes / (2 + 3 * budget + (wb ? 3 * (budget + 1) : 0)));
+  const int per = std::max(1, kMaxGraphNodes / (dk ? 3 : 2 + 3 * budget + (wb ? 3 * (budget + 1) : 0)));
   for (int left = niter; left > 0;) {
     const int cnt = std::min(left, per);
-    auto key = std::make_pair(cnt, budget | ((wb && d_.wb.exact) ? (1 << 24) : 0) | (xy ? (1 << 25) : 0) | (be::wbf_active(d_) ? (1 << 26) : 0));      // (the direct mode is another launch sequence: it may come and go with rho in the large-rank form)
+    auto key = std::make_pair(cnt, budget | ((wb && d_.wb.exact) ? (1 << 24) : 0) | (xy ? (1 << 25) : 0) | (be::wbf_active(d_) ? (1 << 26) : 0) | (dk ? (1 << 27) : 0));      // (the direct mode is another launch sequence: it may come and go with rho in the large-rank form)
     auto it = graphs_.find(key);
     if (it == graphs_.end()) {
       be::graph_begin(d_);
@@ -489,6 +494,8 @@ int Engine::solve() {
   if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   be::activate(d_);
   be::ev_mark(d_, 0);
+  const long long dk_n0 = d_.dk.nfac; const double dk_ms0 = d_.dk.fac_ms;
+  struct DkTally { Engine *e; long long n0; double ms0; ~DkTally() { e->dk_solve_nfac_ = e->d_.dk.on ? e->d_.dk.nfac - n0 : 0; e->dk_solve_ms_ = e->d_.dk.on ? e->d_.dk.fac_ms - ms0 : 0.0; } } dk_tally{this, dk_n0, dk_ms0};      // (dense KKT mode: the factorisations of this solve, also when it throws)
   const int err = solve_impl();
   be::ev_mark(d_, 1);
   stats_.gpu_solve_ms = be::ev_ms(d_);
@@ -609,7 +616,7 @@ void Engine::info_from_ctl() {
 // chunk's progress on a side stream and tops the string up before it runs dry.
 void Engine::exec_chunk_sync(int cnt, int lim, bool with_res, int kind, double *res, int *flags) {
   sync_graph_scalars();                                // (captured strings freeze Dev's scalars: also checked here, where strings are replayed outside admm_core -- polish, ls_solve)
-  const bool slots = use_slots_ && be::slots_supported(d_);
+  const bool slots = slot_form();
   if (!slots) {
     run_chunk(cnt, lim);
     if (with_res) { be::residuals(d_); be::fetch_res_flags(d_, res, flags); } else be::fetch_flags(d_, flags);
@@ -813,7 +820,12 @@ int Engine::run_device_driven(double t0, double *res, int *flags) {
   for (int k = 0; k < 3; k++) if (c.kind_n[k] > 0) slot_pred_[k] = c.kind_sum[k] / c.kind_n[k];
   feed_hist_.assign(c.hist, c.hist + std::min(std::max(c.boundaries, 0), (int)kCtlHist));      // (what the next solve of this handle is fed from)
   if (pol_.slot_log) { std::fprintf(stderr, "feed: this solve's chunks consumed:"); for (int h : feed_hist_) std::fprintf(stderr, " %d", h); std::fprintf(stderr, "  (boundaries %d, launches enqueued %ld)\n", c.boundaries, 2 * launched); }
-  if (c.rho_bar != rho_bar_) { rho_bar_ = c.rho_bar; settings.rho = rho_bar_; }      // (applied on the device)
+  if (c.rho_bar != rho_bar_) {                       // (applied on the device)
+    rho_bar_ = c.rho_bar; settings.rho = rho_bar_;
+    // (dense KKT mode, refused for the rho this solve began with -- a direct handle never runs device-driven: the device's rho update passed be::precond by, so
+    //  the inverse for the rho the handle now holds is formed here, and the next solve may run direct)
+    if (d_.dk.on && !d_.dk.suspend && !timed_out) be::dk_factor(d_);
+  }
   if (timed_out && c.status == CTL_RUNNING) return -2;
   return c.status;
 }
@@ -854,7 +866,7 @@ void Engine::admm_core(double t0, double *res) {
     //  that a boundary group of sixteen launches costs what the host round trip it replaces costs, and the fixed captured strings of the
     //  host-synchronous loop carry no idle launches -- 34 against 41 ms on the portfolio QP)
     d_.wb.x.slots = (pol_.device_driven >= 2) ? 1 : 0;
-    const bool slots = use_slots_ && be::slots_supported(d_);
+    const bool slots = slot_form();
     // (`verbose` changes nothing about how a solve runs: the printed lines come from the state block's log, policy.h Ctl::log)
     const bool device_driven = slots && pol_.device_driven && be::ctl_supported(d_);
     const bool first_chunk = c.iter == 0;
@@ -948,6 +960,7 @@ int Engine::run_recurrence(const RecurrenceRule &rule, double *res) {
   const double gain = rule.gain;
   const double de = std::max(settings.delta, pol_.polish_delta_floor);
   d_.rho_eq_factor = 1.0; d_.eq_from_cnt = 0;       // rho_i = rho_bar = 1 / delta_eff on the active rows
+  d_.dk.suspend = d_.dk.on;                         // dense KKT mode: K at rho = 1 / delta is too ill-conditioned for an unpivoted inverse -- the recurrence runs on the PCG path (lifted by recurrence_restore_launch)
   rho_bar_ = clamp_rho(1.0 / de);
   be::set_rho(d_, rho_bar_);
   be::precond(d_, settings.cg_precond == OSQP_DIAGONAL_PRECONDITIONER);
@@ -973,6 +986,7 @@ int Engine::run_recurrence(const RecurrenceRule &rule, double *res) {
 // what the recurrence's launches changed on the host side: alpha (and the graphs captured with it), the slot predictions, the statistics
 void Engine::recurrence_restore_launch(const RecurrenceSave &s) {
   d_.alpha = s.alpha; drop_graphs();
+  d_.dk.suspend = 0;                                // (dense KKT mode: recurrence_restore_rho's precond factorises for the solve's rho again)
   for (int k = 0; k < 3; k++) slot_pred_[k] = s.pred[k];
   stats_ = s.stats;
 }

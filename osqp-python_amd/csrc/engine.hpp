@@ -49,6 +49,7 @@ class Engine {
   int test_dense(OSQPHipDenseTest *t);
   int test_band(OSQPHipBandTest *t);
   int test_woodbury(OSQPHipWoodburyTest *t);
+  int test_dense_kkt(OSQPHipDenseKktTest *t);
   int test_lockstep(OSQPHipLockstepTest *t);
   int test_lockstep_back(OSQPHipLockstepBackTest *t);
   int test_admm(OSQPHipAdmmTest *t);
@@ -61,6 +62,9 @@ class Engine {
   void set_print(osqp_hip_print_fn fn, void *user) { print_fn_ = fn; print_user_ = user; }
   static void set_default_print(osqp_hip_print_fn fn, void *user);
   int set_rho_eq_factor(double f);
+  // dense KKT mode (include/osqp_hip.h osqp_hip_dense_kkt; backend.h DevDk): on = 1 builds and factorises (synchronous), on = 0 frees everything
+  int dense_kkt(int on);
+  int dense_kkt_last_record(double *rec) const;
   // Px / Ax: optional PER-PROBLEM matrix values (nbatch x nnz(P upper triangle as given at setup) / nbatch x nnz(A), CSC order; nullptr = this solver's
   // values for every problem) -- the reference's forward with a P_val / A_val per batch element (nn/torch.py:128-157): still ONE launch
   int batch_solve(int nbatch, const double *q, const double *l, const double *u, double *x, double *y, double *rec, int warm, double *zs_dev = nullptr, const double *Px = nullptr, const double *Ax = nullptr);
@@ -302,6 +306,9 @@ class Engine {
   void run_chunk(int niter, int budget);
   void run_slots(int begin_target, int pairs, int cap);     // slot form: [slot_begin(begin_target)] + pairs x (B slot, A slot)
   bool use_slots_ = true;
+  // a chunk runs in the slot form: not while the dense KKT mode solves direct (three fixed launches per ADMM iteration, and a rho update must re-factorise on the host)
+  bool slot_form() const { return use_slots_ && be::slots_supported(d_) && !dk_direct(d_.dk); }
+  long long dk_solve_nfac_ = 0; double dk_solve_ms_ = 0;      // factorisations of the dense KKT mode during the last osqp_solve, their wall-clock ms
   double slot_pred_[3] = {6.0, 6.0, 14.0};   // PCG iterations per ADMM iteration the slot strings are sized for, per chunk kind: first after an
                                              // adaptation point (its PCGs start from an accurately solved iterate: fewer iterations), ordinary, tight
   std::map<std::array<int, 3>, void *> sgraphs_;

@@ -640,7 +640,7 @@ void Engine::attach_batch_direct(BatchParams &p, bool spectral) {
 // polish_refine_iter refinement steps: the reference's algorithm, _osqp.py:1710-1828).  Not taken with a time limit or when
 // OSQP_HIP_SMALL_DIRECT=0.  `verbose` does not change the path: the whole loop is one launch, so the table holds its last line only.
 bool Engine::small_direct_applicable() {
-  if (!pol_.small_direct || !be::device_assembly() || settings.time_limit < 1e9 || reordered_) return false;
+  if (!pol_.small_direct || !be::device_assembly() || settings.time_limit < 1e9 || reordered_ || d_.dk.on) return false;      // (a handle with the dense KKT mode on runs that mode)
   if (settings.check_dualgap) return false;            // the one-launch kernel has no duality-gap test: the host-driven loop honours the setting
   if (!be::batch_lds_bytes(n, m)) return false;
   prepare_batch_direct();
@@ -1536,7 +1536,19 @@ int Engine::get_stats(OSQPHipStats *out) {
 int Engine::time_kernel(int which, int reps, double *ms) {
   if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   be::activate(d_);
-  if (which < 0 || which > 23 || reps <= 0 || !ms) return OSQP_DATA_VALIDATION_ERROR;
+  if (which < 0 || which > 25 || reps <= 0 || !ms) return OSQP_DATA_VALIDATION_ERROR;
+  if (which >= 24 && !dk_direct(d_.dk)) return OSQP_FUNC_NOT_IMPLEMENTED;      // 24 / 25: the dense KKT mode's hot path, on a handle that solves direct
+  if (which == 25) {
+    // one ADMM iteration of the dense KKT mode (KB, K^-1 r_0, KA) as a solve runs it: a REPLAYED chunk of `reps` iterations between the solve's event pair,
+    // ms per iteration.  The iterates move on (tools/dense_kkt_bench.py solves cold afterwards).
+    reps = std::min(reps, 1024);
+    sync_graph_scalars();
+    run_chunk(reps, 0);                                 // (captures the chunk's graph and warms it)
+    be::ev_mark(d_, 0); run_chunk(reps, 0); be::ev_mark(d_, 1);
+    *ms = be::ev_ms(d_) / reps;
+    int flags[F_COUNT]; be::fetch_flags(d_, flags);     // (the chunk's PCG statistics are not a solve's)
+    return OSQP_NO_ERROR;
+  }
   *ms = be::time_kernel(d_, which, reps);
   return OSQP_NO_ERROR;
 }
@@ -1656,6 +1668,59 @@ int Engine::test_woodbury(OSQPHipWoodburyTest *t) {
   for (long long k = 0; k < ord; k++) t->idx[k] = reordered_ ? (w.dual ? pc_[hidx[k]] : pr_[hidx[k]]) : hidx[k];
   t->form = w.dual ? 2 : (w.large ? 1 : 0); t->order = (int)ord; t->rows = w.r; t->exact = p.exact; t->info[0] = p.info[0]; t->info[1] = p.info[1];
   t->done = p.done; t->iters = p.iters; t->gamma = p.gamma; t->rnorm = p.rnorm;
+  return OSQP_NO_ERROR;
+}
+// Dense KKT mode (include/osqp_hip.h osqp_hip_dense_kkt; backend.h DevDk; densekkt_hip.hip).  A handle the mode declines is left exactly as it was.
+static_assert(OSQP_HIP_DENSE_KKT_MAX_N == kDkMaxN, "include/osqp_hip.h states the mode's size cap");
+int Engine::dense_kkt(int on) {
+  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (!(on == 0 || on == 1)) return OSQP_DATA_VALIDATION_ERROR;
+  if (!on) {
+    if (!d_.dk.on) return OSQP_NO_ERROR;
+    be::activate(d_);
+    be::ext_wait(d_); be::sync(d_); drop_graphs();        // (captured launches hold the inverse's address)
+    be::dk_release(d_);
+    dk_solve_nfac_ = 0; dk_solve_ms_ = 0;
+    return OSQP_NO_ERROR;
+  }
+  if (!be::dk_enable || !be::dk_release || !be::dk_factor || !be::dk_apply) return OSQP_FUNC_NOT_IMPLEMENTED;      // the host simulator
+  if (d_.wb.on || !be::device_assembly() || !d_.Araw || !ls_rho_.empty()) return OSQP_FUNC_NOT_IMPLEMENTED;        // Woodbury handles have their own direct modes
+  if (m == 0 || n > kDkMaxN || (long long)m * n > kDkMaxW) return OSQP_FUNC_NOT_IMPLEMENTED;
+  if (d_.dk.on) return OSQP_NO_ERROR;
+  be::activate(d_);
+  be::ext_wait(d_); be::sync(d_); drop_graphs();
+  const int err = be::dk_enable(d_);
+  if (err != OSQP_NO_ERROR) return err;
+  try { be::dk_factor(d_); }
+  catch (...) { be::dk_release(d_); throw; }
+  dk_solve_nfac_ = 0; dk_solve_ms_ = 0;
+  return OSQP_NO_ERROR;
+}
+int Engine::dense_kkt_last_record(double *rec) const {
+  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (!rec) return OSQP_DATA_VALIDATION_ERROR;
+  const DevDk &k = d_.dk;
+  const double r[OSQP_HIP_DENSE_KKT_REC] = {(double)(k.on ? k.state : 0), (double)(k.on ? n : 0), (double)dk_solve_nfac_, dk_solve_ms_, k.probe, k.minpiv, k.bytes, (double)k.nfac};
+  std::copy(r, r + OSQP_HIP_DENSE_KKT_REC, rec);
+  return OSQP_NO_ERROR;
+}
+// The mode's diagnostic entry: every length and pointer is checked here (the backend copies exactly n, m, n^2 values); host code that only checks and copies.
+int Engine::test_dense_kkt(OSQPHipDenseKktTest *t) {
+  if (!dev_ready_) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (!be::test_dense_kkt || !d_.dk.on) return OSQP_FUNC_NOT_IMPLEMENTED;
+  if (!t || t->op < OSQP_HIP_DK_FORM || t->op > OSQP_HIP_DK_PROBE) return OSQP_DATA_VALIDATION_ERROR;
+  const long long nn = n, mm = m, tail = 16;
+  const bool form = t->op == OSQP_HIP_DK_FORM, apply = t->op == OSQP_HIP_DK_APPLY;
+  if (t->k_len != (form ? nn * nn + tail : 0) || t->rho_len != (form ? mm + tail : 0) || t->r_len != (apply ? nn : 0) || t->xg_len != (apply ? nn : 0) ||
+      t->xs_len != (apply ? nn + tail : 0) || t->u_len != (apply ? nn + tail : 0)) return OSQP_DATA_VALIDATION_ERROR;
+  if ((form && (!t->K || !t->rho)) || (apply && (!t->r || !t->xg || !t->xs || !t->u))) return OSQP_DATA_VALIDATION_ERROR;
+  if (apply && d_.dk.state != 1) return OSQP_FUNC_NOT_IMPLEMENTED;      // (no accepted inverse to apply)
+  be::activate(d_);
+  be::ext_wait(d_);
+  be::DkProbe p{t->op, t->r, t->xg, t->K, t->rho, t->xs, t->u, 0, 0, 0, 0.0, 0.0};
+  const int st = be::test_dense_kkt(d_, p);
+  if (st != OSQP_NO_ERROR) return st;
+  t->state = p.state; t->order = n; t->done = p.done; t->iters = p.iters; t->probe = p.probe; t->minpiv = p.minpiv;
   return OSQP_NO_ERROR;
 }
 // What both lockstep diagnostic entries stage a caller's array with: a device copy for the duration of the call (nullptr: the array is absent), freed on
@@ -1921,7 +1986,7 @@ int Engine::test_admm(OSQPHipAdmmTest *t) {
   be::fetch_flags(d_, flags);                                           // (clears the statistics an earlier chunk may have left)
   // ---- RUN
   sync_graph_scalars();
-  const bool slots = use_slots_ && be::slots_supported(d_);
+  const bool slots = slot_form();
   const double launches0 = stats_.kernel_launches;
   if (!slots) run_chunk(iters, cap);
   else run_slots(iters, (int)std::ceil(0.5 * iters * be::slot_launches(d_, cap)) + 1, cap);
@@ -1993,7 +2058,7 @@ int Engine::test_boundary(OSQPHipBoundaryTest *t) {
   if (t->n_len != (long long)n || t->m_len != (long long)m || t->res_len != (long long)R_COUNT) return OSQP_DATA_VALIDATION_ERROR;
   if (!t->x_in || !t->dx_in || !t->xt_in || !t->res || !t->xg || !t->xsp || !t->Minv) return OSQP_DATA_VALIDATION_ERROR;
   if (m > 0 && (!t->z_in || !t->y_in || !t->dy_in || !t->zt_in || !t->rho || !t->rho_inv || !t->v || !t->t0 || !t->ztg)) return OSQP_DATA_VALIDATION_ERROR;
-  const bool slots = use_slots_ && be::slots_supported(d_);
+  const bool slots = slot_form();
   if (t->mode == 1 && (!slots || !be::ctl_supported(d_) || d_.wb.on)) return OSQP_FUNC_NOT_IMPLEMENTED;
   be::activate(d_);
   be::ext_wait(d_);

@@ -1777,6 +1777,7 @@ float time_kernel(Dev &d, int which, int reps) {
         });
         break;
       case 21: HIP_CHECK(hipMemsetAsync(d.flags + F_DONE, 0, sizeof(int), st(d))); wb_apply(d, 0, 1); break;      // (the last kernel marks the solve as converged: cleared per repetition)     // Woodbury direct mode, device-factorised form: the three kernels of M^-1 = K^-1 (long rows, S^-1 product, transposed long rows + x~)
+      case 24: dk_apply(d); break;            // dense KKT mode: u = K^-1 r_0, x~ = x_g + u alone (densekkt_hip.hip; Engine::time_kernel has checked that the mode solves direct)
       case 23: wbf_iteration(d); break;       // one ADMM iteration of the fused column-space direct mode (seven launches; the iterates move on: state saved and restored around the measurement)
       case 15: f1_probe_pair(d, 2); break;   // F1 form: one PCG iteration = one launch; two consecutive iterations as a solve runs them (buffers alternate, fold included)
       default: LAUNCH(k_k2f, d, d, 0); LAUNCH(k_k1f, d, d, 1); break;   // one FUSED PCG iteration (two kernels): repeated exact line-search steps, bounded

@@ -89,6 +89,16 @@ class WoodburyTestStruct(C.Structure):    # OSQPHipWoodburyTest, include/osqp_hi
                 [('gamma', C.c_double), ('rnorm', C.c_double)])
 
 
+class DenseKktTestStruct(C.Structure):    # OSQPHipDenseKktTest, include/osqp_hip.h (same order)
+    _fields_ = ([('op', C.c_int)] + [(k, C.c_longlong) for k in ('r_len', 'xg_len', 'k_len', 'rho_len', 'xs_len', 'u_len')] +
+                [(k, c_double_p) for k in ('r', 'xg', 'K', 'rho', 'xs', 'u')] +
+                [(k, C.c_int) for k in ('state', 'order', 'done', 'iters')] + [('probe', C.c_double), ('minpiv', C.c_double)])
+
+
+DENSE_KKT_MAX_N = 1000                    # OSQP_HIP_DENSE_KKT_MAX_N
+DENSE_KKT_REC = ('state', 'order', 'solve_factorisations', 'solve_factor_ms', 'probe', 'min_pivot', 'device_bytes', 'factorisations')      # OSQP_HIP_DENSE_KKT_REC doubles
+DENSE_KKT_OPS = ('form', 'apply', 'probe')      # OSQP_HIP_DK_FORM ..
+
 LOCKSTEP_OPS = ('load_n', 'load_m', 'init', 'store_n', 'store_m', 'minv', 'initz', 'rhs', 't', 'kp', 'upd', 'resm', 'resn', 'setrho', 'cgupd', 'cgp',
                 'cginit', 'cgalpha', 'cgbeta', 'begin', 'asm_a', 'asm_p', 'norms', 'scale', 'cost', 'cost_apply', 'finish',
                 'd0', 's', 'inv', 'prod_x', 'prod_xs', 'prod_p', 'prod2', 'setl0', 'setl1', 'h', 'x', 'vals', 'wt')      # OSQPHipLockstepOp, in order
@@ -214,6 +224,9 @@ PROTOTYPES = {
     'osqp_hip_test_boundary': (C.c_int, [SolverP, C.POINTER(BoundaryTestStruct)]),
     'osqp_hip_res_name': (C.c_char_p, [C.c_int]),
     'osqp_hip_set_rho_eq_factor': (C.c_int, [SolverP, C.c_double]),
+    'osqp_hip_dense_kkt': (C.c_int, [SolverP, C.c_int]),
+    'osqp_hip_dense_kkt_last_record': (C.c_int, [SolverP, c_double_p]),
+    'osqp_hip_test_dense_kkt': (C.c_int, [SolverP, C.POINTER(DenseKktTestStruct)]),
     'osqp_hip_default_policy': (None, [C.POINTER(PolicyStruct)]),
     'osqp_hip_set_default_policy': (None, [C.POINTER(PolicyStruct)]),
     'osqp_hip_set_policy': (C.c_int, [SolverP, C.POINTER(PolicyStruct)]),

@@ -547,6 +547,44 @@ class OSQPSolver:
     def hip_set_rho_eq_factor(self, factor):
         return self._lib.osqp_hip_set_rho_eq_factor(self._p, float(factor))
 
+    def hip_dense_kkt(self, on=True):
+        """Dense KKT mode of this handle (osqp_hip_dense_kkt): on -- form and invert K = P + sigma I + A' diag(rho) A on the device and solve every ADMM
+        iteration's linear system exactly by one dense product; off -- free it.  Returns the status (0, or OSQP_FUNC_NOT_IMPLEMENTED where the mode declines
+        the handle, which is then left untouched)."""
+        return int(self._lib.osqp_hip_dense_kkt(self._p, int(bool(on))))
+
+    def hip_dense_kkt_record(self):
+        """osqp_hip_dense_kkt_last_record as a dict (keys: _lib.DENSE_KKT_REC): state 0 off / 1 direct / 2 refused for the current rho, order,
+        factorisations of the last solve and their ms, probe value and smallest pivot of the last inversion, device bytes, factorisations since enabling."""
+        rec = np.zeros(len(_lib.DENSE_KKT_REC))
+        st = int(self._lib.osqp_hip_dense_kkt_last_record(self._p, _ptr(rec, _lib.c_double_p)))
+        if st:
+            raise RuntimeError('osqp_hip_dense_kkt_last_record failed with status %d' % st)
+        out = dict(zip(_lib.DENSE_KKT_REC, (float(v) for v in rec)))
+        for k in ('state', 'order', 'solve_factorisations', 'factorisations'):
+            out[k] = int(out[k])
+        return out
+
+    def hip_test_dense_kkt(self, op, r=None, xg=None, lens=None):
+        """The dense KKT mode's kernels on this handle (osqp_hip_test_dense_kkt; SCALED problem, the ENGINE's numbering).  op 'form': K [n, n] as formed,
+        before the inversion, and the rho vector [m]; 'apply': x~ = xg + K^-1 r and u = K^-1 r for r, xg [n]; 'probe': the probe value.  Outputs are NaN
+        canvases of their count + 16; lens = {field: length} overrides a length as it is passed (the entry validates).  Returns (status, dict) with the
+        canvases K, rho, xs, u as the call left them and state, order, done, iters, probe, minpiv."""
+        n, m = self.n, self.m
+        code = _lib.DENSE_KKT_OPS.index(op) if isinstance(op, str) else int(op)
+        f64 = lambda a: np.zeros(0) if a is None else np.ascontiguousarray(a, dtype=np.float64).ravel()
+        r, xg = f64(r), f64(xg)
+        cnt = dict(K=n * n + 16 if code == 0 else 0, rho=m + 16 if code == 0 else 0, xs=n + 16 if code == 1 else 0, u=n + 16 if code == 1 else 0)
+        out = {k: np.full(v, np.nan) for k, v in cnt.items()}
+        ln = dict(r_len=r.size, xg_len=xg.size, k_len=cnt['K'], rho_len=cnt['rho'], xs_len=cnt['xs'], u_len=cnt['u'])
+        ln.update(lens or {})
+        dp = _lib.c_double_p
+        t = _lib.DenseKktTestStruct(code, *[int(ln[k]) for k in ('r_len', 'xg_len', 'k_len', 'rho_len', 'xs_len', 'u_len')],
+                                    _ptr(r if r.size else None, dp), _ptr(xg if xg.size else None, dp), *[_ptr(out[k] if out[k].size else None, dp) for k in ('K', 'rho', 'xs', 'u')])
+        st = int(self._lib.osqp_hip_test_dense_kkt(self._p, C.byref(t)))
+        out.update(state=int(t.state), order=int(t.order), done=int(t.done), iters=int(t.iters), probe=float(t.probe), minpiv=float(t.minpiv))
+        return st, out
+
     BATCH_FIELDS = ('status_val', 'iter', 'obj_val', 'prim_res', 'dual_res', 'rho', 'rho_updates', 'pcg_iters', 'status_polish', 'polish_time', 'rho_estimate', 'duality_gap')
     BATCH_REC = len(BATCH_FIELDS)        # OSQP_HIP_BATCH_REC
 
